@@ -10,11 +10,18 @@ output audio is gathered on rank 0 (weak scaling); value = all frames of all ran
 (`python -m torch.distributed.run --nproc-per-node N bench.py ...` as a child process; the parent never touches the
 GPU and relays the child's output and exit code).  Started under torch.distributed.run it is one of the ranks.
 
-Prints ONE JSON line on rank 0.  Extra objects: `roofline` (dominant kernel class = fp16 tap-GEMM, timed live with HIP
-events on the launch stream in a separate single-lane pass after the timed region), `cpu_baseline` (the CPU oracle on
-the host cores: warm-up + median of 3, bounded sample) and `secondary` (N = 1 only: the north-star's own target
-workload, seed-uvit-whisper-small + BigVGAN, as a B = 64 throughput line and a B = 1 latency line, measured in the
-same process).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps and prints the headline line
+(`value`, `ms_per_step` = milliseconds of one timed step).  `--dump-outputs DIR` then also writes what the timed path
+returned in its last step (rank 0's mel (B, C, S) and waveform (B, S*hop)) as DIR/mel.npy and DIR/wave.npy in float32;
+the inputs are seeded, so two builds can be compared output for output.  Above 64 MB in all, the same fixed, seeded
+sample of utterances (rows) is written for both.
+
+`--full` adds the measurements that take runs of their own: `roofline` (dominant kernel class = fp16 tap-GEMM, timed
+live with HIP events on the launch stream in a separate single-lane pass after the timed region), `cpu_baseline` (the
+CPU oracle on the host cores: warm-up + median of 3, bounded sample), `secondary` (N = 1 only: the north-star's own
+target workload, seed-uvit-whisper-small + BigVGAN, as a B = 64 throughput line and a B = 1 latency line, measured in
+the same process) and, with N > 1, `ranks` (per-rank step time and the audio gather alone).  `--no-roofline`,
+`--no-cpu-baseline` and `--no-secondary` leave single objects out of a `--full` run.
 """
 import argparse
 import json
@@ -28,6 +35,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 PEAK_F16_TFLOPS = 2500.0        # dense fp16/bf16 MFMA (MI355X_MICROARCH.md)
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs: all arrays together
 
 
 def parse(argv=None):
@@ -49,10 +57,17 @@ def parse(argv=None):
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher self-test: ranks rendezvous over gloo on the CPU and rank 0 prints a JSON line without "
                          "touching the GPU (exercised by tests/test_host_cpu.py)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure roofline, cpu_baseline, secondary lines and (N > 1) per-rank diagnostics")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out cpu_baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: leave out roofline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: leave out the secondary lines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0) to DIR/<name>.npy, float32")
+    a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 # ------------------------------------------------------------------------------------------------ N > 1 launcher
@@ -89,7 +104,8 @@ def dry_run_rank(a, rank, world):
         allv = [torch.empty_like(mine) for _ in range(world)]
         dist.all_gather(allv, mine)
         allv = torch.stack(allv)
-        ranks = rank_stats(allv[:, 0].tolist(), allv[:, 1].tolist(), "gloo", world)
+        if a.full:
+            ranks = rank_stats(allv[:, 0].tolist(), allv[:, 1].tolist(), "gloo", world)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     if rank == 0:
         line = {"metric": "mel_frames_per_sec", "value": 0.0, "unit": "mel-frames/s", "n_gpus": world,
@@ -335,6 +351,31 @@ def cpu_baseline(w, nthreads):
                       f"2-step warm-up + median of 3 runs ({', '.join(f'{t:.1f}' for t in times)} s)"}
 
 
+def dump_outputs(d, arrays, seed=0):
+    """--dump-outputs: {name: tensor with the utterances along dim 0} -> d/<name>.npy in float32.  Above
+    DUMP_LIMIT_BYTES in all, the same fixed, seeded sample of rows is kept for every array (and, if even one row is too
+    large, a fixed, seeded sample of the elements of each array)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    rng = np.random.default_rng(seed)
+    total = sum(x.nbytes for x in arrays.values())
+    rows = None
+    if total > DUMP_LIMIT_BYTES:
+        n = min(x.shape[0] for x in arrays.values())
+        keep = DUMP_LIMIT_BYTES // sum(x[0].nbytes for x in arrays.values())
+        if keep >= 1:
+            rows = np.sort(rng.choice(n, min(n, keep), replace=False))
+            arrays = {k: x[rows] for k, x in arrays.items()}
+        else:
+            per = DUMP_LIMIT_BYTES // (4 * len(arrays))
+            arrays = {k: x.reshape(-1)[np.sort(rng.choice(x.size, min(per, x.size), replace=False))] for k, x in arrays.items()}
+    for k, x in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), np.ascontiguousarray(x))
+    return {"dir": d, "arrays": {k: list(x.shape) for k, x in arrays.items()},
+            "rows": None if rows is None else rows.tolist()}
+
+
 def main():
     a = parse()
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -371,7 +412,7 @@ def main():
         mel, wave = w.step()
         if world > 1:
             gather_audio(wave, [wave.size(1)] * B, B * world)
-        return wave
+        return mel, wave
 
     def sync_all():
         torch.cuda.synchronize()
@@ -384,7 +425,7 @@ def main():
     sync_all()
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        step()
+        last = step()
     torch.cuda.synchronize()
     dt_local = time.perf_counter() - t0                 # this rank's own work (its gathers included), before the barrier
     sync_all()
@@ -394,7 +435,8 @@ def main():
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
-        ranks_info = rank_diagnostics(w, dt_local, a.steps, dev, world, B, a.dist_backend)
+        if a.full:
+            ranks_info = rank_diagnostics(w, dt_local, a.steps, dev, world, B, a.dist_backend)
     frames = world * B * S * a.steps
     value = frames / dt
 
@@ -415,13 +457,16 @@ def main():
     if ranks_info is not None:
         out["ranks"] = ranks_info
 
-    if rank == 0 and not a.no_roofline:
+    if rank == 0 and a.dump_outputs:
+        out["dump"] = dump_outputs(a.dump_outputs, {"mel": last[0], "wave": last[1]})
+
+    if rank == 0 and a.full and not a.no_roofline:
         out["roofline"] = roofline(w, value / world, f"{a.model}-b{a.batch}")
 
-    if rank == 0 and world == 1 and not a.no_secondary and a.model == "tiny":
+    if rank == 0 and world == 1 and a.full and not a.no_secondary and a.model == "tiny":
         out["secondary"] = secondary_lines(a, dev)
 
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:      # reported at N = 1 only
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:      # reported at N = 1 only
         out["cpu_baseline"] = cpu_baseline(w, host_cores())
 
     if rank == 0:

@@ -283,8 +283,8 @@ def test_bench_gpus_flag_starts_the_ranks_itself():
     launcher / rendezvous / single-line contract is what is tested, the GPU work is covered by the -m gpu tests."""
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--dry-run"],
-                       capture_output=True, text=True, env=env, timeout=300)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--dry-run",
+                        "--full"], capture_output=True, text=True, env=env, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -296,6 +296,51 @@ def test_bench_gpus_flag_starts_the_ranks_itself():
     assert rk["nccl_ranks"] == 2 and rk["backend"] == "gloo"
     assert rk["step_ms_per_rank"] == [1.0, 2.0] and (rk["step_ms_min"], rk["step_ms_mean"], rk["step_ms_max"]) == (1.0, 1.5, 2.0)
     assert rk["gather_ms_per_rank"] == [0.1, 0.2] and rk["gather_ms_max"] == 0.2
+    # a plain run (no --full) carries only the headline: the per-rank diagnostics are measured in --full runs
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--dry-run"],
+                       capture_output=True, text=True, env=env, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    rec = json.loads(lines[0])
+    assert rec["n_gpus"] == 2 and rec["steps"] == 2 and "ranks" not in rec
+
+
+def test_bench_options():
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse(["--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    a = bench.parse(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse(bad)
+
+
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """--dump-outputs writes float32 .npy files; above the size limit every array keeps the same seeded rows."""
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(0)
+    mel, wave = torch.randn(8, 3, 5, generator=g).half(), torch.randn(8, 20, generator=g, dtype=torch.float64)
+    info = bench.dump_outputs(str(tmp_path / "all"), {"mel": mel, "wave": wave})
+    assert info["rows"] is None and info["arrays"] == {"mel": [8, 3, 5], "wave": [8, 20]}
+    m, w = np.load(tmp_path / "all" / "mel.npy"), np.load(tmp_path / "all" / "wave.npy")
+    assert m.dtype == np.float32 and w.dtype == np.float32
+    np.testing.assert_array_equal(m, mel.float().numpy())
+    np.testing.assert_array_equal(w, wave.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 3 * (3 * 5 + 20) * 4)          # room for three utterances
+    infos = [bench.dump_outputs(str(tmp_path / d), {"mel": mel, "wave": wave}) for d in ("s1", "s2")]
+    rows = infos[0]["rows"]
+    assert rows == infos[1]["rows"] and len(rows) == 3 and rows == sorted(set(rows))
+    for d in ("s1", "s2"):
+        np.testing.assert_array_equal(np.load(tmp_path / d / "mel.npy"), mel.float().numpy()[rows])
+        np.testing.assert_array_equal(np.load(tmp_path / d / "wave.npy"), wave.float().numpy()[rows])
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 16 * 4)                          # not even one utterance fits
+    info = bench.dump_outputs(str(tmp_path / "el"), {"mel": mel, "wave": wave})
+    assert info["arrays"] == {"mel": [8], "wave": [8]}
+    assert sum(os.path.getsize(tmp_path / "el" / f) - 128 for f in ("mel.npy", "wave.npy")) <= 16 * 4
 
 
 def test_bench_launcher_command_is_the_drivers_form():

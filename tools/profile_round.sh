@@ -1,7 +1,7 @@
 #!/bin/bash
 # Collects the judged evidence of one round on the GPU box (run through gpurun from the repo root):
 #   tools/profile_round.sh <tag> <commit>            e.g. tools/profile_round.sh r02_a $(git rev-parse --short HEAD)
-# 1. bench.py (default command, incl. secondary lines and cpu_baseline) -> gpurun_out/<tag>_bench_tiny_b64.json
+# 1. bench.py --full (default workload, incl. roofline, secondary lines and cpu_baseline) -> <out>/<tag>_bench_tiny_b64.json
 # 2. rocprofv3 --kernel-trace --stats of the same workload, two lanes and one lane (serial kernels: the averages
 #    roofline.avg_launch_ms must agree with), and of --model small                        -> *_kernel_stats.csv
 # 3. per-shape GEMM tables (SVC_PROF_DUMP)                                                 -> *_gemm_shapes_*.txt
@@ -17,20 +17,20 @@ root=$(pwd)
 out=$root/gpurun_out
 mkdir -p $out
 export TMPDIR=/tmp
-python bench.py > $out/${tag}_bench_tiny_b64.json 2> $out/${tag}_bench.err
+python bench.py --full > $out/${tag}_bench_tiny_b64.json 2> $out/${tag}_bench.err
 echo "bench done"
-python bench.py --model small --no-cpu-baseline --no-secondary > $out/${tag}_bench_small_b64.json 2>> $out/${tag}_bench.err
-python bench.py --model base --batch 32 --no-cpu-baseline --no-secondary > $out/${tag}_bench_base_b32.json 2>> $out/${tag}_bench.err
-python bench.py --model v2 --no-cpu-baseline --no-secondary > $out/${tag}_bench_v2_b64.json 2>> $out/${tag}_bench.err
-python bench.py --model v2 --batch 1 --lanes 1 --steps 10 --warmup 2 --no-cpu-baseline --no-secondary > $out/${tag}_bench_v2_b1.json 2>> $out/${tag}_bench.err
-for m in tiny small base; do python bench.py --model $m --batch 1 --lanes 1 --steps 10 --warmup 2 --no-cpu-baseline --no-secondary > $out/${tag}_bench_${m}_b1.json 2>> $out/${tag}_bench.err; done
+python bench.py --full --model small --no-cpu-baseline --no-secondary > $out/${tag}_bench_small_b64.json 2>> $out/${tag}_bench.err
+python bench.py --full --model base --batch 32 --no-cpu-baseline --no-secondary > $out/${tag}_bench_base_b32.json 2>> $out/${tag}_bench.err
+python bench.py --full --model v2 --no-cpu-baseline --no-secondary > $out/${tag}_bench_v2_b64.json 2>> $out/${tag}_bench.err
+python bench.py --full --model v2 --batch 1 --lanes 1 --steps 10 --warmup 2 --no-cpu-baseline --no-secondary > $out/${tag}_bench_v2_b1.json 2>> $out/${tag}_bench.err
+for m in tiny small base; do python bench.py --full --model $m --batch 1 --lanes 1 --steps 10 --warmup 2 --no-cpu-baseline --no-secondary > $out/${tag}_bench_${m}_b1.json 2>> $out/${tag}_bench.err; done
 echo "model lines done"
 python tools/ar_bench.py > $out/${tag}_ar_decode.json 2>> $out/${tag}_bench.err
 python tools/aa_act_bench.py > $out/${tag}_aa_act.json 2>> $out/${tag}_bench.err
 shapes() {  # name, then bench.py arguments
   local name=$1; shift
   rm -f $out/shapes.csv
-  SVC_PROF_DUMP=$out/shapes.csv python bench.py "$@" --steps 1 --warmup 1 --no-cpu-baseline --no-secondary > /dev/null 2>&1
+  SVC_PROF_DUMP=$out/shapes.csv python bench.py --full "$@" --steps 1 --warmup 1 --no-cpu-baseline --no-secondary > /dev/null 2>&1
   python tools/shape_report.py $out/shapes.csv > $out/${tag}_gemm_shapes_$name.txt
 }
 shapes tiny_b64 --model tiny
@@ -42,7 +42,7 @@ rm -f $out/shapes.csv
 cd /tmp
 prof() {  # name, then bench.py arguments
   local name=$1; shift
-  rocprofv3 --kernel-trace --stats --output-format csv -d $out/${tag}_prof_$name -- python $root/bench.py "$@" > $out/${tag}_prof_$name.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $out/${tag}_prof_$name -- python $root/bench.py --full "$@" > $out/${tag}_prof_$name.log 2>&1
   cp $(find $out/${tag}_prof_$name -name "*kernel_stats.csv" | head -1) $out/${tag}_${name}_kernel_stats.csv
   rm -rf $out/${tag}_prof_$name
 }

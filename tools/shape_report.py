@@ -1,5 +1,5 @@
-"""Per-shape GEMM table of one bench pass: run `SVC_PROF_DUMP=gpurun_out/shapes.csv python bench.py ...` then
-`python tools/shape_report.py gpurun_out/shapes.csv`.  Columns: class, M, N, K, epilogue, launches, total ms, TFLOP/s,
+"""Per-shape GEMM table of one bench pass: run `SVC_PROF_DUMP=shapes.csv python bench.py --full ...` (the roofline
+pass fills the table) then `python tools/shape_report.py shapes.csv`.  Columns: class, M, N, K, epilogue, launches, total ms, TFLOP/s,
 algorithmic GB/s -- sorted by total time."""
 import sys
 
