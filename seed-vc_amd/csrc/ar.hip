@@ -1,12 +1,16 @@
 // v2 AR model (NaiveTransformer, GQA 12q/2kv, KV cache): `forward_generate` (prefill and one-token decode step)
 // and the top-p / repetition-penalty / exponential-race sampler, as HIP kernels for gfx950.
 //
-// The one-token decode step is HBM-bound (every weight byte is read once per token), so its linears are
-// wave-per-output-row GEMV kernels streaming fp16 weights with 16-byte loads; prefill (S > 8 rows) reuses the
-// MFMA tap-GEMM on the same packed weights.  The whole decode step (38 kernels: three per layer, see "three launches
-// per layer" below) is captured once into a hipGraph and replayed per token (the reference's answer to launch overhead
-// is torch.compile "reduce-overhead", modules/v2/vc_wrapper.py:105-114); positions live in device memory and are
-// advanced inside the graph, so a replay needs no host-side argument update.
+// `svc_ar::run` takes one of three forms, by the number of rows S:
+//   * S = 1 on a shape the one-token kernels hold (`dec_step`, decided once in svc_ar_create): the decode step, three
+//     launches per layer ("S = 1 decode step" below);
+//   * S <= 8 (and S = 1 on other shapes): GEMV-pair layers, five launches per layer;
+//   * S > 8 (prefill): the MFMA tap-GEMM on the same packed weights.
+// The decode step is HBM-bound (every weight byte is read once per token), so its linears are wave-per-output-row GEMV
+// kernels streaming fp16 weights with 16-byte loads.  The whole step (38 kernels for ar_base) is captured once into a
+// hipGraph and replayed per token (the reference's answer to launch overhead is torch.compile "reduce-overhead",
+// modules/v2/vc_wrapper.py:105-114); positions live in device memory and are advanced inside the graph, so a replay
+// needs no host-side argument update.
 //
 // reference: modules/v2/ar.py:239-267 (forward_generate), :75-93 (KVCache.update), :503-567 (Attention),
 //            :600-651 (RMSNorm, bf16 RoPE table), :712-763 (sample / logits_to_probs / exponential race).
@@ -14,6 +18,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 #include "model_util.h"
@@ -55,58 +60,7 @@ __device__ __forceinline__ float wave_sum_f(float v) {      // every lane gets t
            __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 48));
 }
 
-// out[s][n] = (res ? res[s][n] : 0) + sum_k x[s][k] * W[n][k]        (one wave per output column, S <= 8 rows)
-// GLU: rows (2j, 2j+1) of W are (w1_j, w3_j): out16[s][j] = silu(a) * b
-template <bool GLU>
-__global__ __launch_bounds__(256) void gemv_kernel(const half_t* __restrict__ x, long ldx, const half_t* __restrict__ W, long ldw,
-                                                   const float* res, long ldres, float* out32, half_t* out16, long ldo,
-                                                   int S, int N, int K) {
-    const int wave = (blockIdx.x * 256 + threadIdx.x) >> 6;
-    const int lane = threadIdx.x & 63;
-    const int n_out = GLU ? N / 2 : N;
-    if (wave >= n_out) return;
-    const half_t* w0 = W + (long)(GLU ? 2 * wave : wave) * ldw;
-    const half_t* w1 = w0 + ldw;
-    float acc0[8], acc1[8];
-#pragma unroll
-    for (int s = 0; s < 8; ++s) acc0[s] = acc1[s] = 0.f;
-    for (int k0 = lane * 8; k0 < K; k0 += 512) {
-        const half8 a = *reinterpret_cast<const half8*>(w0 + k0);
-        half8 b;
-        if (GLU) b = *reinterpret_cast<const half8*>(w1 + k0);
-#pragma unroll
-        for (int s = 0; s < 8; ++s) {
-            if (s < S) {
-                const half8 xv = *reinterpret_cast<const half8*>(x + (long)s * ldx + k0);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    acc0[s] += (float)xv[j] * (float)a[j];
-                    if (GLU) acc1[s] += (float)xv[j] * (float)b[j];
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {
-        if (s < S) {
-            const float a = wave_sum_f(acc0[s]);
-            const float b = GLU ? wave_sum_f(acc1[s]) : 0.f;
-            if (lane == 0) {
-                if (GLU) {
-                    out16[(long)s * ldo + wave] = (half_t)((a / (1.f + __expf(-a))) * b);
-                } else {
-                    float o = a;
-                    if (res) o += res[(long)s * ldres + wave];
-                    if (out32) out32[(long)s * ldo + wave] = o;
-                    if (out16) out16[(long)s * ldo + wave] = (half_t)o;
-                }
-            }
-        }
-    }
-}
-
-
-// ---- decode-step GEMV (S <= 8 rows): one wave per PAIR of output rows (2w, 2w+1), fp16 weights streamed with
+// ---- GEMV-pair layers (S <= 8 rows): one wave per PAIR of output rows (2w, 2w+1), fp16 weights streamed with
 // 16-byte loads, fp32 accumulate.  NORM fuses the preceding RMSNorm (x fp32, rstd recomputed per wave: K floats
 // from L2 -- cheaper than a launch).  Epilogues: PLAIN (+residual), GLU (rows = (w1_j, w3_j) -> silu(a) * b) and
 // QKV (rows = one RoPE pair: rotate with the bf16 table, q -> q_out, k / v -> scattered into the KV cache).
@@ -330,16 +284,17 @@ __global__ __launch_bounds__(1024) void ar_attn_kernel(const float* __restrict__
 }
 
 // ------------------------------------------------------------------------------------------------ S = 1 decode step
-// Building blocks of the four-launch form (SVC_AR_DEC=1; the default three-launch form further down reuses dec_ffn13 /
-// dec_w2 and replaces dec_qkv / dec_attn by dec_w2qkv / dec_attn2).  The step is bound by launch boundaries and memory
-// round trips, not bandwidth (13.4 MB of weights per layer); every kernel issues EVERY load a wave needs before anything
-// waits:
-//   dec_qkv   : attention_norm + wqkv GEMV + RoPE + KV-cache scatter          (one wave per RoPE row pair)
-//   dec_attn  : one workgroup per head: scores, softmax, PV over the valid cache prefix, then that head's slice of wo
-//               (768 x 64) -> partial residual vectors part[head][D]          (wo's own launch disappears)
+// Three launches per layer, then the last layer's w2 and the output head.  The step is bound by launch boundaries and
+// memory round trips, not bandwidth (13.4 MB of weights per layer); every kernel issues EVERY load a wave needs before
+// anything waits:
+//   dec_qkvraw (layer 0) | dec_w2qkv (layers >= 1): this layer's unnormalised QKV GEMV, fused with the previous layer's
+//               w2 GEMV + residual ("three launches per layer" below)
+//   dec_attn2 : RMSNorm scale, RoPE, KV-cache write, attention over the valid cache prefix and the head's slice of wo
+//               -> partial residual vectors part[head][D]                     (wo's own launch disappears)
 //   dec_ffn13 : h = h_in + sum_heads part[head] (summed once per workgroup in LDS; workgroup 0 stores it to the other
 //               residual buffer), ffn_norm, w1/w3 GEMV, SwiGLU -> ff16        (4 rows per wave)
-//   dec_w2    : h_out = h + w2 GEMV                                            (2 rows per wave)
+//   dec_w2    : h_out = h + w2 GEMV, last layer                               (2 rows per wave)
+//   dec_head  : final RMSNorm + output GEMV                                   (4 rows per wave)
 // A wave owns whole weight rows; lane l owns the 16-byte chunks l, l + 64, ... of every row (and of the input vector),
 // so the input never goes through LDS and one wave reduction per row finishes it.
 constexpr int DEC_MAXC = 5;          // chunks of 8 elements per lane: reductions up to 64 * 8 * 5 = 2560 long
@@ -440,158 +395,6 @@ __device__ __forceinline__ void dec_dot(const DecW<NR>& r, int K, const void* x,
     // the NR reductions are independent DPP chains (the compiler interleaves them)
 #pragma unroll
     for (int q = 0; q < NR; ++q) out[q] = wave_sum_f(acc[q]);
-}
-
-template <int KD>
-__global__ __launch_bounds__(64) void dec_qkv_kernel(const float* __restrict__ h, const float* __restrict__ gamma, float eps,
-                                                     const half_t* __restrict__ W, int K, int N, float* __restrict__ q_out,
-                                                     float* __restrict__ kc, float* __restrict__ vc, const float* __restrict__ rope,
-                                                     const int* __restrict__ pos, int H, int Hkv, int Lmax) {
-    const int lane = threadIdx.x, r0 = 2 * blockIdx.x;
-    if (r0 >= N) return;
-    DecW<2> w;
-    dec_load_w<2, KD>(w, W, K, r0, N, K, lane);
-    // epilogue operands are fetched now, not after the reduction (each would be one more exposed round trip)
-    const int ip = pos[0], kp = pos[1];
-    const int pair = (r0 & 63) >> 1;
-    const float cs = rope[((long)ip * 32 + pair) * 2], sn = rope[((long)ip * 32 + pair) * 2 + 1];
-    float v[2];
-    dec_dot<2, false, KD>(w, K, h, gamma, eps, true, v, lane);
-    if (lane == 0) {
-        const int D = H * 64, kvd = Hkv * 64;
-        if (r0 < D + kvd) {
-            const float o0 = v[0] * cs - v[1] * sn, o1 = v[1] * cs + v[0] * sn;
-            if (r0 < D) {
-                q_out[r0] = o0;
-                q_out[r0 + 1] = o1;
-            } else {
-                const int ek = r0 - D;
-                float* dst = kc + ((long)(ek >> 6) * Lmax + kp) * 64 + (ek & 63);
-                dst[0] = o0;
-                dst[1] = o1;
-            }
-        } else {
-            const int ev = r0 - D - kvd;
-            float* dst = vc + ((long)(ev >> 6) * Lmax + kp) * 64 + (ev & 63);
-            dst[0] = v[0];
-            dst[1] = v[1];
-        }
-    }
-}
-
-// One 1024-thread workgroup per head.  part[h][n] = sum_d wo[n][64 h + d] * y_h[d]  (y_h rounded to fp16 like the
-// stand-alone path).  Latency-shaped: thread (g = tid / 16, c = tid % 16) owns float4 column c of the key AND value rows
-// g, g + 64, ... (8 per batch of 512 keys) and requests all of them -- and its piece of the wo slice -- before anything
-// waits, so a whole batch costs one memory round trip; scores are 16-lane shuffle sums, the softmax is the online form
-// across batches (one for contexts up to 512 keys), P.V is accumulated from the registers already held, and the 64
-// groups are summed through LDS.  Every global access is a coalesced 256-byte row (128-byte row slice for wo).
-__global__ __launch_bounds__(1024) void dec_attn_kernel(const float* __restrict__ q, const float* __restrict__ kc,
-                                                        const float* __restrict__ vc, const half_t* __restrict__ wo,
-                                                        float* __restrict__ part, const int* __restrict__ pos, int H, int Hkv, int Lmax) {
-    __shared__ __attribute__((aligned(16))) float pacc[64 * 64];     // per key group: 64 output columns
-    __shared__ float red[16], yv[64];
-    const int h = blockIdx.x, D = H * 64;
-    const int hk = h / (H / Hkv);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int g = tid >> 4, c = tid & 15;
-    // this head's wo column slice goes global -> LDS by LDS-DMA right away (needed last; in registers it cost 32 VGPRs
-    // and pushed the kernel into scratch)
-    constexpr int WO_TRIPS = 8;                 // wo rows up to 1024: row n = 8 lanes x 16 bytes, 128 rows per trip
-    __shared__ __attribute__((aligned(16))) half_t wo_s[1024 * 64];
-    {
-        typedef __attribute__((address_space(1))) const void* gptr_t;
-        typedef __attribute__((address_space(3))) void* lptr_t;
-        const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-#pragma unroll
-        for (int i = 0; i < WO_TRIPS; ++i) {
-            const int n = i * 128 + (tid >> 3);
-            const int nn = n < D ? n : D - 1;
-            if (i * 128 < D)
-                __builtin_amdgcn_global_load_lds((gptr_t)(wo + (long)nn * D + 64 * h + 8 * (tid & 7)),
-                                                 (lptr_t)(wo_s + (i * 128 + wave_u * 8) * 64), 16, 0, 0);
-        }
-    }
-    const int n_keys = pos[1] + 1;
-    const float4v qv = *reinterpret_cast<const float4v*>(q + (long)h * 64 + 4 * c);
-    const float* kbase = kc + (long)hk * Lmax * 64 + 4 * c;
-    const float* vbase = vc + (long)hk * Lmax * 64 + 4 * c;
-    constexpr int KB = 8;                       // keys per thread per batch
-    float m_run = -1e30f, l_run = 0.f;
-    float4v acc = {0.f, 0.f, 0.f, 0.f};
-    for (int j0 = 0; j0 < n_keys; j0 += 64 * KB) {
-        float4v kv[KB], vv[KB];
-#pragma unroll
-        for (int i = 0; i < KB; ++i) {
-            const int j = j0 + g + 64 * i;
-            const long o = (long)(j < n_keys ? j : 0) * 64;
-            kv[i] = *reinterpret_cast<const float4v*>(kbase + o);
-            vv[i] = *reinterpret_cast<const float4v*>(vbase + o);
-        }
-        float sc[KB];
-#pragma unroll
-        for (int i = 0; i < KB; ++i) sc[i] = qv[0] * kv[i][0] + qv[1] * kv[i][1] + qv[2] * kv[i][2] + qv[3] * kv[i][3];
-#pragma unroll
-        for (int o = 1; o < 16; o <<= 1)
-#pragma unroll
-            for (int i = 0; i < KB; ++i) sc[i] += __shfl_xor(sc[i], o);
-        float bm = -1e30f;
-#pragma unroll
-        for (int i = 0; i < KB; ++i) {
-            sc[i] = j0 + g + 64 * i < n_keys ? sc[i] * 0.125f : -1e30f;
-            bm = fmaxf(bm, sc[i]);
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) bm = fmaxf(bm, __shfl_xor(bm, o));
-        __syncthreads();                         // red[] of the previous batch has been read
-        if (lane == 0) red[wave] = bm;
-        __syncthreads();
-        float m_new = m_run;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) m_new = fmaxf(m_new, red[i]);
-        const float scale = expf(m_run - m_new);
-        l_run *= scale;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc[r] *= scale;
-#pragma unroll
-        for (int i = 0; i < KB; ++i) {
-            const float p = j0 + g + 64 * i < n_keys ? expf(sc[i] - m_new) : 0.f;
-            l_run += p;                          // every lane of a group carries the same p: the sum is taken from lane c == 0
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[r] += p * vv[i][r];
-        }
-        m_run = m_new;
-    }
-    // sum over the 64 key groups
-    *reinterpret_cast<float4v*>(pacc + g * 64 + 4 * c) = acc;
-    float ls = c == 0 ? l_run : 0.f;
-    ls = wave_sum_f(ls);
-    __syncthreads();
-    if (lane == 0) red[wave] = ls;
-    __syncthreads();
-    if (tid < 64) {
-        float tot = 0.f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) tot += red[i];
-        float o = 0.f;
-#pragma unroll 8
-        for (int i = 0; i < 64; ++i) o += pacc[i * 64 + tid];
-        yv[tid] = (float)(half_t)(o / tot);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // this wave's part of the wo slice has landed
-    __syncthreads();
-    const float4v y0 = *reinterpret_cast<const float4v*>(yv + 8 * (tid & 7)), y1 = *reinterpret_cast<const float4v*>(yv + 8 * (tid & 7) + 4);
-#pragma unroll
-    for (int i = 0; i < WO_TRIPS; ++i) {
-        const int n = i * 128 + (tid >> 3);
-        float o = 0.f;
-        if (n < D) {
-            const half8 wr = *reinterpret_cast<const half8*>(wo_s + n * 64 + 8 * (tid & 7));
-#pragma unroll
-            for (int j = 0; j < 4; ++j) o += y0[j] * (float)wr[j] + y1[j] * (float)wr[4 + j];
-        }
-        o += __shfl_xor(o, 1); o += __shfl_xor(o, 2); o += __shfl_xor(o, 4);
-        if (n < D && (tid & 7) == 0) part[(long)h * D + n] = o;
-    }
 }
 
 // 256 threads = 4 waves x 4 rows (2 SwiGLU outputs each).  h = h_in + sum_p part[p] is summed once per workgroup; the weight
@@ -711,11 +514,11 @@ __global__ __launch_bounds__(64) void dec_w2qkv_kernel(const half_t* __restrict_
     }
 }
 
-// Attention of the three-launch form, spread over the chip: grid = (DEC_NS wo-row slices) x (heads), 512 threads.
+// Attention of the decode step, spread over the chip: grid = (DEC_NS wo-row slices) x (heads), 512 threads.
 // q / k / v arrive unnormalised (qkv_raw).  Every workgroup of head h recomputes that head's softmax over the valid cache
 // prefix [0, kv_pos] -- <= 4096 x 64 fp32 keys and values, read from L2 / Infinity Cache -- and applies 1 / DEC_NS of the
 // head's wo column slice (D / DEC_NS rows x 64 columns, held in registers), so 96 workgroups carry the 12 heads of ar_base
-// instead of 12 (one CU per head moved 154 KB of K / V + 98 KB of wo and ran eight 1024-thread barriers).
+// instead of 12 (with one workgroup per head, a CU moved 154 KB of K / V + 98 KB of wo and ran eight 1024-thread barriers).
 //   * every request that does not depend on `pos` goes out first: the first two batches of cache rows (by position,
 //     clamped to the cache, NOT to the valid prefix), the wo rows, the layer input, q / k / v;
 //   * 1 / rms(h): every wave reduces the layer input h on its own (D floats from L2, one DPP tree: no barrier);
@@ -1126,7 +929,7 @@ struct svc_ar {
     Arena wts, ws;
     struct Layer {
         half_t *wqkv, *wo, *w13, *w2;
-        half_t* wc = nullptr;     // three-launch form: layer 0 [Nqkv][D] = wqkv diag(gamma); layers >= 1 [Nqkv][I + D] = [Wq' w2_prev | Wq']
+        half_t* wc = nullptr;     // decode step (dec_step only): layer 0 [Nqkv][D] = wqkv diag(gamma); layers >= 1 [Nqkv][I + D] = [Wq' w2_prev | Wq']
         float *g_attn, *g_ffn;
         float *kc, *vc;
     };
@@ -1151,26 +954,21 @@ struct svc_ar {
     float* emb = nullptr;         // model.embeddings.weight [V][D] fp32 (generate loop only)
     int ensure_graph();
     int ensure_gen_graph();
-    int run1(const float* x, const int* d_positions, float* logits_out, hipStream_t st);
-    int run1_fused(const float* x, const int* d_positions, float* logits_out, hipStream_t st);
-    bool have_wc = false;
+    bool dec_step = false;        // S = 1 runs the decode step (the shape fits the dec_* kernels; `wc` is composed)
 
     int reserve(int S, hipStream_t st);
     int run(const float* x, int S, const int* d_positions, float* logits_out, hipStream_t st);
+    int run_dec_step(const float* x, const int* d_positions, float* logits_out, hipStream_t st);
+    int run_gemv_layers(int S, const int* d_positions, hipStream_t st);
+    int run_gemm_layers(int S, const int* d_positions, hipStream_t st);
+    int run_head(int S, float* logits_out, hipStream_t st);
 };
 
 namespace {
+// out[s] = (res ? res[s] : 0) + W x[s] on the tap-GEMM (S > 8 rows); GLU: rows (2j, 2j+1) of W are (w1_j, w3_j) ->
+// out16[s][j] = silu(a) * b
 int lin(const half_t* x, const half_t* W, long ldw, const float* res, float* out32, half_t* out16, long ldo, int S, int N, int K,
         bool glu, hipStream_t st) {
-    if (S <= 8) {
-        const int n_out = glu ? N / 2 : N;
-        if (glu)
-            hipLaunchKernelGGL(gemv_kernel<true>, dim3(cdiv(n_out, 4)), dim3(256), 0, st, x, (long)K, W, ldw, res, ldo, out32, out16, ldo, S, N, K);
-        else
-            hipLaunchKernelGGL(gemv_kernel<false>, dim3(cdiv(n_out, 4)), dim3(256), 0, st, x, (long)K, W, ldw, res, ldo, out32, out16, ldo, S, N, K);
-        SVC_CHECK_HIP(hipGetLastError());
-        return 0;
-    }
     KGemmParams p;
     memset(&p, 0, sizeof(p));
     p.M = S; p.N = N; p.Lout = S; p.a_seq_rows = S; p.c_seq_rows = S; p.a_stride = 1; p.a_len = S;
@@ -1214,118 +1012,98 @@ int svc_ar::reserve(int S, hipStream_t st) {
     return 0;
 }
 
-// The one-token GEMV kernels are instantiated for the ar_base sizes (dim 768, intermediate 2304: reduction lengths known at
-// compile time, dead chunks pruned) and for runtime sizes (<0, 0>: any dim <= 2560 that is a multiple of 8).
-#define SVC_DEC_KD (D == 768 && I == 2304 ? 768 : 0)
-#define SVC_DEC_LAUNCH1(kern, WHICH, grid, block, lds, st, ...)                                                  \
-    do {                                                                                                          \
-        if (SVC_DEC_KD) { constexpr int KD = 768, KI = 2304; (void)KD; (void)KI; hipLaunchKernelGGL((kern<WHICH>), grid, block, lds, st, __VA_ARGS__); } \
-        else { constexpr int KD = 0, KI = 0; (void)KD; (void)KI; hipLaunchKernelGGL((kern<WHICH>), grid, block, lds, st, __VA_ARGS__); }                 \
-    } while (0)
-#define SVC_DEC_LAUNCH2(kern, grid, block, lds, st, ...)                                                         \
-    do {                                                                                                          \
-        if (SVC_DEC_KD) hipLaunchKernelGGL((kern<768, 2304>), grid, block, lds, st, __VA_ARGS__);                 \
-        else hipLaunchKernelGGL((kern<0, 0>), grid, block, lds, st, __VA_ARGS__);                                 \
-    } while (0)
-#define SVC_DEC_LAUNCH_NP(kern, NP, grid, block, lds, st, ...)                                                   \
-    do {                                                                                                          \
-        if (SVC_DEC_KD) hipLaunchKernelGGL((kern<NP, 768>), grid, block, lds, st, __VA_ARGS__);                   \
-        else hipLaunchKernelGGL((kern<NP, 0>), grid, block, lds, st, __VA_ARGS__);                                \
-    } while (0)
-
-// One-token step on the four-launches-per-layer kernels (dec_*).
-int svc_ar::run1(const float* x, const int* d_positions, float* logits_out, hipStream_t st) {
-    if (x != h32) SVC_CHECK_HIP(hipMemcpyAsync(h32, x, (size_t)D * 4, hipMemcpyDeviceToDevice, st));
-    for (int i = 0; i < L; ++i) {
-        const Layer& ly = layers[i];
-        SVC_DEC_LAUNCH1(dec_qkv_kernel, KD, dim3(Nqkv / 2), dim3(64), 0, st, h32, ly.g_attn, cfg.norm_eps, ly.wqkv, D, Nqkv, q32, ly.kc,
-                           ly.vc, rope, d_positions, H, Hkv, Lmax);
-        hipLaunchKernelGGL(dec_attn_kernel, dim3(H), dim3(1024), 0, st, q32, ly.kc, ly.vc, ly.wo, part, d_positions, H, Hkv, Lmax);
-        if (H == 12)
-            SVC_DEC_LAUNCH_NP(dec_ffn13_kernel, 12, dim3(cdiv(2 * I, 16)), dim3(256), 0, st, h32, part, H, h32b, ly.g_ffn, cfg.norm_eps,
-                               ly.w13, D, 2 * I, ff16);
-        else
-            SVC_DEC_LAUNCH_NP(dec_ffn13_kernel, 0, dim3(cdiv(2 * I, 16)), dim3(256), 0, st, h32, part, H, h32b, ly.g_ffn, cfg.norm_eps,
-                               ly.w13, D, 2 * I, ff16);
-        SVC_DEC_LAUNCH1(dec_w2_kernel, KI, dim3(D / 2), dim3(64), 0, st, ff16, ly.w2, I, D, h32b, h32);
-        SVC_CHECK_HIP(hipGetLastError());
-    }
-    SVC_DEC_LAUNCH1(dec_head_kernel, KD, dim3(cdiv(V, 16)), dim3(256), 0, st, h32, g_final, cfg.norm_eps, w_out, D, V, logits_out);
-    SVC_CHECK_HIP(hipGetLastError());
-    return 0;
+// The dec_* kernels are instantiated for the ar_base sizes (KD = dim 768, KI = intermediate 2304: reduction lengths known
+// at compile time, dead chunks pruned) and for runtime sizes (KD = KI = 0); dec_ffn13 adds NP = 12 head partials from
+// registers (NP = 0: a runtime count).  Calls f(KD, KI, NP) with the instance for this shape, as compile-time constants.
+namespace {
+template <int N> using IntC = std::integral_constant<int, N>;
+template <class F>
+int with_dec_sizes(int D, int I, int H, F&& f) {
+    const bool base = D == 768 && I == 2304;
+    if (H == 12) return base ? f(IntC<768>(), IntC<2304>(), IntC<12>()) : f(IntC<0>(), IntC<0>(), IntC<12>());
+    return base ? f(IntC<768>(), IntC<2304>(), IntC<0>()) : f(IntC<0>(), IntC<0>(), IntC<0>());
 }
-
-// One-token step, three launches per layer (dec_qkvraw | dec_w2qkv, dec_attn2, dec_ffn13) + the last w2 + head.
-int svc_ar::run1_fused(const float* x, const int* d_positions, float* logits_out, hipStream_t st) {
-    if (x != h32) SVC_CHECK_HIP(hipMemcpyAsync(h32, x, (size_t)D * 4, hipMemcpyDeviceToDevice, st));
-    for (int i = 0; i < L; ++i) {
-        const Layer& ly = layers[i];
-        if (i == 0)
-            SVC_DEC_LAUNCH1(dec_qkvraw_kernel, KD, dim3(cdiv(Nqkv, 2)), dim3(64), 0, st, h32, ly.wc, D, Nqkv, qkv32);
-        else
-            SVC_DEC_LAUNCH2(dec_w2qkv_kernel, dim3(cdiv(D + Nqkv, 2)), dim3(64), 0, st, ff16, h32b, layers[i - 1].w2, ly.wc, I, D, Nqkv, h32,
-                               qkv32);
-        hipLaunchKernelGGL(dec_attn2_kernel, dim3(DEC_NS, H), dim3(512), 0, st, h32, qkv32, cfg.norm_eps, rope, ly.kc, ly.vc, ly.wo, part,
-                           d_positions, H, Hkv, Lmax);
-        if (H == 12)
-            SVC_DEC_LAUNCH_NP(dec_ffn13_kernel, 12, dim3(cdiv(2 * I, 16)), dim3(256), 0, st, h32, part, H, h32b, ly.g_ffn, cfg.norm_eps,
-                               ly.w13, D, 2 * I, ff16);
-        else
-            SVC_DEC_LAUNCH_NP(dec_ffn13_kernel, 0, dim3(cdiv(2 * I, 16)), dim3(256), 0, st, h32, part, H, h32b, ly.g_ffn, cfg.norm_eps,
-                               ly.w13, D, 2 * I, ff16);
-        SVC_CHECK_HIP(hipGetLastError());
-    }
-    SVC_DEC_LAUNCH1(dec_w2_kernel, KI, dim3(D / 2), dim3(64), 0, st, ff16, layers[L - 1].w2, I, D, h32b, h32);
-    SVC_DEC_LAUNCH1(dec_head_kernel, KD, dim3(cdiv(V, 16)), dim3(256), 0, st, h32, g_final, cfg.norm_eps, w_out, D, V, logits_out);
-    SVC_CHECK_HIP(hipGetLastError());
-    return 0;
-}
+}  // namespace
 
 int svc_ar::run(const float* x, int S, const int* d_positions, float* logits_out, hipStream_t st) {
-    // SVC_AR_DEC: 0 = generic path, 1 = four launches per layer, 2 (default) = three launches per layer
-    static const int dec_mode = [] { const char* e = getenv("SVC_AR_DEC"); return e ? atoi(e) : 2; }();
-    if (S == 1 && dec_mode && D <= 1024 && D % 8 == 0 && I % 8 == 0 && D <= 64 * 8 * DEC_MAXC && I <= 64 * 8 * DEC_MAXC && Nqkv % 2 == 0)
-        return dec_mode >= 2 && have_wc ? run1_fused(x, d_positions, logits_out, st) : run1(x, d_positions, logits_out, st);
+    if (S == 1 && dec_step) return run_dec_step(x, d_positions, logits_out, st);
     if (x != h32) SVC_CHECK_HIP(hipMemcpyAsync(h32, x, (size_t)S * D * 4, hipMemcpyDeviceToDevice, st));
-    const size_t attn_lds = ((size_t)Lmax + 1024) * sizeof(float);
-    const bool fused = S <= 8;      // decode step: 5 launches per layer (norm / RoPE / cache scatter live in the GEMVs)
-    for (int i = 0; i < L; ++i) {
-        const Layer& ly = layers[i];
-        if (fused) {
-            GemvArgs a;
-            memset(&a, 0, sizeof(a));
-            a.x = h32; a.ldx = D; a.gamma = ly.g_attn; a.eps = cfg.norm_eps; a.W = ly.wqkv; a.ldw = D; a.S = S; a.N = Nqkv; a.K = D;
-            a.q_out = q32; a.kc = ly.kc; a.vc = ly.vc; a.rope = rope; a.pos = d_positions; a.H = H; a.Hkv = Hkv; a.Lmax = Lmax;
-            if (gemv_pair_launch<true, GV_QKV>(a, st)) return 1;
-        } else {
-            if (rmsnorm_mod_launch(h32, D, n16, D, ly.g_attn, nullptr, nullptr, 0, 0, S, D, S, cfg.norm_eps, st)) return 1;
-            if (lin(n16, ly.wqkv, D, nullptr, qkv32, nullptr, Nqkv, S, Nqkv, D, false, st)) return 1;
-            hipLaunchKernelGGL(ar_rope_cache_kernel, dim3(S), dim3(256), 0, st, qkv32, (long)Nqkv, q32, ly.kc, ly.vc, rope, d_positions,
-                               S, H, Hkv, Lmax);
+    if (S <= 8 ? run_gemv_layers(S, d_positions, st) : run_gemm_layers(S, d_positions, st)) return 1;
+    return run_head(S, logits_out, st);
+}
+
+// S = 1 decode step: three launches per layer (dec_qkvraw | dec_w2qkv, dec_attn2, dec_ffn13) + the last w2 + head.
+int svc_ar::run_dec_step(const float* x, const int* d_positions, float* logits_out, hipStream_t st) {
+    if (x != h32) SVC_CHECK_HIP(hipMemcpyAsync(h32, x, (size_t)D * 4, hipMemcpyDeviceToDevice, st));
+    return with_dec_sizes(D, I, H, [&](auto KD, auto KI, auto NP) {
+        for (int i = 0; i < L; ++i) {
+            const Layer& ly = layers[i];
+            if (i == 0)
+                hipLaunchKernelGGL((dec_qkvraw_kernel<KD>), dim3(cdiv(Nqkv, 2)), dim3(64), 0, st, h32, ly.wc, D, Nqkv, qkv32);
+            else
+                hipLaunchKernelGGL((dec_w2qkv_kernel<KD, KI>), dim3(cdiv(D + Nqkv, 2)), dim3(64), 0, st, ff16, h32b, layers[i - 1].w2,
+                                   ly.wc, I, D, Nqkv, h32, qkv32);
+            hipLaunchKernelGGL(dec_attn2_kernel, dim3(DEC_NS, H), dim3(512), 0, st, h32, qkv32, cfg.norm_eps, rope, ly.kc, ly.vc, ly.wo, part,
+                               d_positions, H, Hkv, Lmax);
+            hipLaunchKernelGGL((dec_ffn13_kernel<NP, KD>), dim3(cdiv(2 * I, 16)), dim3(256), 0, st, h32, part, H, h32b, ly.g_ffn,
+                               cfg.norm_eps, ly.w13, D, 2 * I, ff16);
             SVC_CHECK_HIP(hipGetLastError());
         }
+        hipLaunchKernelGGL((dec_w2_kernel<KI>), dim3(D / 2), dim3(64), 0, st, ff16, layers[L - 1].w2, I, D, h32b, h32);
+        hipLaunchKernelGGL((dec_head_kernel<KD>), dim3(cdiv(V, 16)), dim3(256), 0, st, h32, g_final, cfg.norm_eps, w_out, D, V, logits_out);
+        SVC_CHECK_HIP(hipGetLastError());
+        return 0;
+    });
+}
+
+// S <= 8: five launches per layer; the norms, RoPE and the cache scatter live in the GEMVs.
+int svc_ar::run_gemv_layers(int S, const int* d_positions, hipStream_t st) {
+    const size_t attn_lds = ((size_t)Lmax + 1024) * sizeof(float);
+    for (int i = 0; i < L; ++i) {
+        const Layer& ly = layers[i];
+        GemvArgs a;
+        memset(&a, 0, sizeof(a));
+        a.x = h32; a.ldx = D; a.gamma = ly.g_attn; a.eps = cfg.norm_eps; a.W = ly.wqkv; a.ldw = D; a.S = S; a.N = Nqkv; a.K = D;
+        a.q_out = q32; a.kc = ly.kc; a.vc = ly.vc; a.rope = rope; a.pos = d_positions; a.H = H; a.Hkv = Hkv; a.Lmax = Lmax;
+        if (gemv_pair_launch<true, GV_QKV>(a, st)) return 1;
         hipLaunchKernelGGL(ar_attn_kernel, dim3(S, H), dim3(1024), attn_lds, st, q32, ly.kc, ly.vc, y16, d_positions, S, H, Hkv, Lmax);
         SVC_CHECK_HIP(hipGetLastError());
-        if (fused) {
-            GemvArgs a;
-            memset(&a, 0, sizeof(a));
-            a.x = y16; a.ldx = D; a.W = ly.wo; a.ldw = D; a.res = h32; a.ldres = D; a.out32 = h32; a.ldo = D; a.S = S; a.N = D; a.K = D;
-            if (gemv_pair_launch<false, GV_PLAIN>(a, st)) return 1;
-            memset(&a, 0, sizeof(a));
-            a.x = h32; a.ldx = D; a.gamma = ly.g_ffn; a.eps = cfg.norm_eps; a.W = ly.w13; a.ldw = D; a.out16 = ff16; a.ldo = I;
-            a.S = S; a.N = 2 * I; a.K = D;
-            if (gemv_pair_launch<true, GV_GLU>(a, st)) return 1;
-            memset(&a, 0, sizeof(a));
-            a.x = ff16; a.ldx = I; a.W = ly.w2; a.ldw = I; a.res = h32; a.ldres = D; a.out32 = h32; a.ldo = D; a.S = S; a.N = D; a.K = I;
-            if (gemv_pair_launch<false, GV_PLAIN>(a, st)) return 1;
-        } else {
-            if (lin(y16, ly.wo, D, h32, h32, nullptr, D, S, D, D, false, st)) return 1;
-            if (rmsnorm_mod_launch(h32, D, n16, D, ly.g_ffn, nullptr, nullptr, 0, 0, S, D, S, cfg.norm_eps, st)) return 1;
-            if (lin(n16, ly.w13, D, nullptr, nullptr, ff16, I, S, 2 * I, D, true, st)) return 1;
-            if (lin(ff16, ly.w2, I, h32, h32, nullptr, D, S, D, I, false, st)) return 1;
-        }
+        memset(&a, 0, sizeof(a));
+        a.x = y16; a.ldx = D; a.W = ly.wo; a.ldw = D; a.res = h32; a.ldres = D; a.out32 = h32; a.ldo = D; a.S = S; a.N = D; a.K = D;
+        if (gemv_pair_launch<false, GV_PLAIN>(a, st)) return 1;
+        memset(&a, 0, sizeof(a));
+        a.x = h32; a.ldx = D; a.gamma = ly.g_ffn; a.eps = cfg.norm_eps; a.W = ly.w13; a.ldw = D; a.out16 = ff16; a.ldo = I;
+        a.S = S; a.N = 2 * I; a.K = D;
+        if (gemv_pair_launch<true, GV_GLU>(a, st)) return 1;
+        memset(&a, 0, sizeof(a));
+        a.x = ff16; a.ldx = I; a.W = ly.w2; a.ldw = I; a.res = h32; a.ldres = D; a.out32 = h32; a.ldo = D; a.S = S; a.N = D; a.K = I;
+        if (gemv_pair_launch<false, GV_PLAIN>(a, st)) return 1;
     }
-    // last token only (ar.py:255-259): final RMSNorm fused into the output GEMV
+    return 0;
+}
+
+// S > 8 (prefill): RMSNorm, tap-GEMM linears, RoPE + cache scatter, attention.
+int svc_ar::run_gemm_layers(int S, const int* d_positions, hipStream_t st) {
+    const size_t attn_lds = ((size_t)Lmax + 1024) * sizeof(float);
+    for (int i = 0; i < L; ++i) {
+        const Layer& ly = layers[i];
+        if (rmsnorm_mod_launch(h32, D, n16, D, ly.g_attn, nullptr, nullptr, 0, 0, S, D, S, cfg.norm_eps, st)) return 1;
+        if (lin(n16, ly.wqkv, D, nullptr, qkv32, nullptr, Nqkv, S, Nqkv, D, false, st)) return 1;
+        hipLaunchKernelGGL(ar_rope_cache_kernel, dim3(S), dim3(256), 0, st, qkv32, (long)Nqkv, q32, ly.kc, ly.vc, rope, d_positions,
+                           S, H, Hkv, Lmax);
+        SVC_CHECK_HIP(hipGetLastError());
+        hipLaunchKernelGGL(ar_attn_kernel, dim3(S, H), dim3(1024), attn_lds, st, q32, ly.kc, ly.vc, y16, d_positions, S, H, Hkv, Lmax);
+        SVC_CHECK_HIP(hipGetLastError());
+        if (lin(y16, ly.wo, D, h32, h32, nullptr, D, S, D, D, false, st)) return 1;
+        if (rmsnorm_mod_launch(h32, D, n16, D, ly.g_ffn, nullptr, nullptr, 0, 0, S, D, S, cfg.norm_eps, st)) return 1;
+        if (lin(n16, ly.w13, D, nullptr, nullptr, ff16, I, S, 2 * I, D, true, st)) return 1;
+        if (lin(ff16, ly.w2, I, h32, h32, nullptr, D, S, D, I, false, st)) return 1;
+    }
+    return 0;
+}
+
+// last token only (ar.py:255-259): final RMSNorm fused into the output GEMV
+int svc_ar::run_head(int S, float* logits_out, hipStream_t st) {
     GemvArgs a;
     memset(&a, 0, sizeof(a));
     a.x = h32 + (long)(S - 1) * D; a.ldx = D; a.gamma = g_final; a.eps = cfg.norm_eps; a.W = w_out; a.ldw = D;
@@ -1333,30 +1111,36 @@ int svc_ar::run(const float* x, int S, const int* d_positions, float* logits_out
     return gemv_pair_launch<true, GV_PLAIN>(a, st);
 }
 
-int svc_ar::ensure_graph() {
-    svc_ar* m = this;
-    if (!m->graph) {
-        hipStream_t cs;
-        SVC_CHECK_HIP(hipStreamCreate(&cs));
-        hipGraph_t g = nullptr;
-        SVC_CHECK_HIP(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
-        int rc = m->run(m->gx, 1, m->d_pos, m->logits, cs);
-        if (!rc) {
-            hipLaunchKernelGGL(advance_pos_kernel, dim3(1), dim3(64), 0, cs, m->d_pos, (int*)nullptr);
-            if (hipGetLastError() != hipSuccess) rc = 1;
-        }
-        const hipError_t e = hipStreamEndCapture(cs, &g);
-        if (rc || e != hipSuccess) {
-            if (g) (void)hipGraphDestroy(g);
-            (void)hipStreamDestroy(cs);
-            if (!rc) set_error(std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-            return 1;
-        }
-        SVC_CHECK_HIP(hipGraphInstantiate(&m->graph, g, nullptr, nullptr, 0));
-        (void)hipGraphDestroy(g);
+namespace {
+// Captures the launches `body` issues on a fresh stream into *exec.
+template <class F>
+int capture_graph(hipGraphExec_t* exec, F&& body) {
+    hipStream_t cs;
+    SVC_CHECK_HIP(hipStreamCreate(&cs));
+    hipGraph_t g = nullptr;
+    SVC_CHECK_HIP(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
+    const int rc = body(cs);
+    const hipError_t e = hipStreamEndCapture(cs, &g);
+    if (rc || e != hipSuccess) {
+        if (g) (void)hipGraphDestroy(g);
         (void)hipStreamDestroy(cs);
+        if (!rc) set_error(std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
+        return 1;
     }
+    SVC_CHECK_HIP(hipGraphInstantiate(exec, g, nullptr, nullptr, 0));
+    (void)hipGraphDestroy(g);
+    (void)hipStreamDestroy(cs);
     return 0;
+}
+}  // namespace
+
+int svc_ar::ensure_graph() {
+    if (graph) return 0;
+    return capture_graph(&graph, [&](hipStream_t cs) {
+        if (run(gx, 1, d_pos, logits, cs)) return 1;
+        hipLaunchKernelGGL(advance_pos_kernel, dim3(1), dim3(64), 0, cs, d_pos, (int*)nullptr);
+        return hipGetLastError() != hipSuccess ? 1 : 0;
+    });
 }
 
 int svc_ar::sample(const float* lg, const int* prev, int n_prev, int suppress, float temperature, float top_p, float rep_pen,
@@ -1370,25 +1154,12 @@ int svc_ar::sample(const float* lg, const int* prev, int n_prev, int suppress, f
 
 int svc_ar::ensure_gen_graph() {
     if (gen_graph) return 0;
-    hipStream_t cs;
-    SVC_CHECK_HIP(hipStreamCreate(&cs));
-    hipGraph_t g = nullptr;
-    SVC_CHECK_HIP(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
     // the step runs in place on h32, which holds the embedding of the previous token (written by svc_ar_generate for the
     // first step and by the sampler of every step for the next one)
-    int rc = run(h32, 1, d_pos, logits, cs);
-    if (!rc) rc = sample(logits, nullptr, 0, -1, 1.f, 1.f, 1.f, nullptr, nullptr, nullptr, d_gen, cs, true);
-    const hipError_t e = hipStreamEndCapture(cs, &g);
-    if (rc || e != hipSuccess) {
-        if (g) (void)hipGraphDestroy(g);
-        (void)hipStreamDestroy(cs);
-        if (!rc) set_error(std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-        return 1;
-    }
-    SVC_CHECK_HIP(hipGraphInstantiate(&gen_graph, g, nullptr, nullptr, 0));
-    (void)hipGraphDestroy(g);
-    (void)hipStreamDestroy(cs);
-    return 0;
+    return capture_graph(&gen_graph, [&](hipStream_t cs) {
+        if (run(h32, 1, d_pos, logits, cs)) return 1;
+        return sample(logits, nullptr, 0, -1, 1.f, 1.f, 1.f, nullptr, nullptr, nullptr, d_gen, cs, true);
+    });
 }
 
 extern "C" {
@@ -1438,13 +1209,17 @@ int svc_ar_create(const svc_ar_config_t* cfg, const svc_tensor_desc_t* weights, 
         ly.g_ffn = vec(p + "ffn_norm.weight", D);
         if (!ly.g_attn || !ly.g_ffn) return fail();
     }
-    {   // three-launch decode form: Wq' = wqkv diag(gamma_attn) and, for layers >= 1, W' = Wq' w2_prev composed in fp32
+    // S = 1 takes the decode step when the dec_* kernels hold the shape: dec_attn2 covers 64 * DA_WO * DEC_NS wo rows per
+    // head, and a lane holds DEC_MAXC chunks of 8 elements of each reduction (dim, intermediate_size).  Other shapes run
+    // S = 1 on the GEMV-pair layers.
+    m->dec_step = D <= 64 * DA_WO * DEC_NS && D <= 64 * 8 * DEC_MAXC && I <= 64 * 8 * DEC_MAXC;
+    if (m->dec_step) {   // its weights: Wq' = wqkv diag(gamma_attn) and, for layers >= 1, W' = Wq' w2_prev composed in fp32
         const int Nq = m->Nqkv;
         Arena tmp;
         float* wq = tmp.alloc_n<float>((size_t)round_up(Nq, 128) * D, st);           // Wq'            [Nq][D]
         float* w2t = tmp.alloc_n<float>((size_t)round_up(I, 128) * D, st);           // w2_prev^T      [I][D]
         float* wp = tmp.alloc_n<float>((size_t)round_up(Nq, 128) * I, st);           // W' = Wq' w2    [Nq][I]
-        bool ok = wq && w2t && wp && D % 32 == 0 && I % 8 == 0;
+        bool ok = wq && w2t && wp;
         for (int i = 0; ok && i < m->L; ++i) {
             const std::string p = "model.layers." + std::to_string(i) + ".";
             auto& ly = m->layers[i];
@@ -1470,9 +1245,11 @@ int svc_ar_create(const svc_ar_config_t* cfg, const svc_tensor_desc_t* weights, 
             ok = ok && ly.wc && !pack_f16_launch(wp, ly.wc, Nq, 1, I, I, 0, 1, ldc, 0, 1, nullptr, st) &&
                  !pack_f16_launch(wq, ly.wc + I, Nq, 1, D, D, 0, 1, ldc, 0, 1, nullptr, st);
         }
-        if (hipStreamSynchronize(st) != hipSuccess) ok = false;                           // tmp is freed on scope exit
-        m->have_wc = ok;
-        if (!ok) (void)hipGetLastError();
+        const hipError_t e = hipStreamSynchronize(st);                                 // tmp is freed on scope exit
+        if (!ok || e != hipSuccess) {
+            set_error(std::string("AR: composing the decode-step weights failed: ") + (ok ? hipGetErrorString(e) : get_error()));
+            return fail();
+        }
     }
     m->g_final = vec("model.norm.weight", D);
     m->w_out = m->wts.alloc_n<half_t>(round_up(V, 128) * (long)D, st);

@@ -12,9 +12,14 @@ LOGIT_TOL = 5e-3
 UNASSISTED_PREFIX_MIN = 160    # ar_gen_full with the PLAIN draws: all 160 tokens equal the reference run (measured; a near-tie flipped by a kernel change would show here)
 
 
-@pytest.mark.parametrize("use_graph", [False, True])
-@pytest.mark.parametrize("name", list(cases.AR_CASES))
-def test_ar_generate_steps(name, use_graph, golden):
+# prefill_split = n: the prefill runs as two calls, the last n tokens second (n <= 8: the GEMV-pair layers on a cache that
+# already holds the first part).  Split 0 keeps the ids the test had before the parameter.
+AR_STEP_PARAMS = [pytest.param(name, use_graph, split, id=f"{name}-{use_graph}" + (f"-split{split}" if split else ""))
+                  for name in cases.AR_CASES for use_graph in (False, True) for split in (0, 5)]
+
+
+@pytest.mark.parametrize("name,use_graph,prefill_split", AR_STEP_PARAMS)
+def test_ar_generate_steps(name, use_graph, prefill_split, golden):
     from seedvc_amd.ar import ARModel
     c, sd, x_prefill, input_pos, x_steps, exp_noise, meta = cases.ar_case(name)
     ar = ARModel(c, sd, "cuda:0")
@@ -22,7 +27,12 @@ def test_ar_generate_steps(name, use_graph, golden):
     ref_logits = torch.from_numpy(golden[name + ".logits"])
     ip = torch.tensor(input_pos)
     kv = torch.arange(meta["n_prefill"])
-    lg = ar.forward_generate(x_prefill.cuda(), ip, kv).cpu()
+    if prefill_split:
+        n = meta["n_prefill"] - prefill_split
+        ar.forward_generate(x_prefill[:, :n].cuda(), ip[:n], kv[:n])
+        lg = ar.forward_generate(x_prefill[:, n:].cuda(), ip[n:], kv[n:]).cpu()
+    else:
+        lg = ar.forward_generate(x_prefill.cuda(), ip, kv).cpu()
     scale = ref_logits.abs().mean().item()
     err0 = (lg[0] - ref_logits[0]).abs().max().item()
     print(f"{name}: prefill logits max err {err0:.3e} (|logits| mean {scale:.3f})")
@@ -91,37 +101,38 @@ def test_generate_loop_full_size(golden):
     assert n_plain >= UNASSISTED_PREFIX_MIN
 
 
-def test_four_launch_and_generic_step_forms_in_a_fresh_process():
-    """SVC_AR_DEC selects the one-token step form when the library is loaded (2 = three launches per layer, the default
-    the tests above exercise; 1 = four launches per layer; 0 = the generic small-S path): the other two forms are held
-    to the same reference logits in a child process each."""
-    import os
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    script = f"""
-import sys
-sys.path.insert(0, {root!r}); sys.path.insert(0, {os.path.join(root, 'tests', 'golden')!r})
-import numpy as np, torch
-import _pkgload; _pkgload.load_package()
-import cases
-from seedvc_amd.ar import ARModel
-g = dict(np.load({os.path.join(root, 'tests', 'golden', 'ar.npz')!r}))
-for name in cases.AR_CASES:
-    c, sd, x_prefill, input_pos, x_steps, exp_noise, meta = cases.ar_case(name)
-    ar = ARModel(c, sd, "cuda:0"); ar.setup_caches()
-    ref = torch.from_numpy(g[name + ".logits"])
-    ip = torch.tensor(input_pos); kv = torch.arange(meta["n_prefill"])
-    ar.forward_generate(x_prefill.cuda(), ip, kv)
+# intermediate_size 2624 > 64 * 8 * DEC_MAXC: the decode-step kernels refuse the shape, so S = 1 runs the GEMV-pair layers
+AR_GEMV_STEP = dict(dim=128, n_head=2, n_local_heads=1, n_layer=3, intermediate_size=2624, vocab_size=65, max_seq_len=64)
+
+
+@pytest.mark.parametrize("use_graph", [False, True])
+def test_ar_one_token_gemv_pair_steps(use_graph):
+    """S = 1 on a shape the decode step does not hold goes through the GEMV-pair layers: prefill, then eager or
+    hipGraph-replayed one-token steps against the oracle (pinned to the reference by test_oracle_golden.py)."""
+    import seedvc_oracle as O
+    from seedvc_amd import specs, weights
+    from seedvc_amd.ar import ARModel
+    seed, n_prefill, n_decode = 65, 9, 4
+    c = specs.ar_config(**AR_GEMV_STEP)
+    sd = weights.make_state_dict(specs.ar_state_spec(c), seed=seed, prefix="ar.")
+    x_prefill = cases.randn("ar_gemv_step.prefill", seed, 1, n_prefill, c["dim"])
+    x_steps = cases.randn("ar_gemv_step.steps", seed, n_decode, 1, 1, c["dim"])
+    caches = O.ar_new_cache(c)
+    ar = ARModel(c, sd, "cuda:0")
+    ar.setup_caches()
+    ip = torch.tensor(list(range(n_prefill // 2 + 1)) + list(range(n_prefill - n_prefill // 2 - 1)))
+    kv = torch.arange(n_prefill)
+    ref = O.ar_forward_generate(sd, c, x_prefill, ip, kv, caches)
+    lg = ar.forward_generate(x_prefill.cuda(), ip, kv).cpu()
     scale = max(ref.abs().mean().item(), 1.0)
-    for s in range(meta["n_decode"]):
+    err = (lg - ref).abs().max().item()
+    assert err < LOGIT_TOL * scale, f"prefill: {err:.3e}"
+    for s in range(n_decode):
         ip, kv = ip[-1:] + 1, kv[-1:] + 1
-        lg = ar.forward_generate(x_steps[s].cuda(), ip, kv).cpu()
-        err = (lg[0] - ref[s + 1]).abs().max().item()
-        assert err < {LOGIT_TOL} * scale, (name, s, err)
-print("AR_FORM_OK")
-"""
-    for mode in ("1", "0"):
-        env = dict(os.environ, SVC_AR_DEC=mode)
-        r = subprocess.run([sys.executable, "-c", script], capture_output=True, text=True, timeout=600, env=env)
-        assert r.returncode == 0 and "AR_FORM_OK" in r.stdout, (mode, r.stderr[-2000:])
+        ref = O.ar_forward_generate(sd, c, x_steps[s], ip, kv, caches)
+        if use_graph:
+            lg = ar.decode_step(x_steps[s].cuda(), int(ip[0]) if s == 0 else None, int(kv[0]) if s == 0 else None).cpu()
+        else:
+            lg = ar.forward_generate(x_steps[s].cuda(), ip, kv).cpu()
+        err = (lg - ref).abs().max().item()
+        assert err < LOGIT_TOL * scale, f"step {s}: {err:.3e}"
