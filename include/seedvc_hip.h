@@ -6,9 +6,8 @@
  * as void*; NULL = default stream).  The sampler, estimator and length-regulator calls do not synchronise the host in
  * steady state: HOST arrays (lengths) are copied into handle-owned pinned staging slots before the call returns, so the
  * caller may reuse them at once.  A call synchronises only when it has to grow the handle's workspace (first call, or a
- * larger batch / sequence than any before), svc_ar_generate reads tokens back every `check_every` steps, and the *_create
- * functions finish packing before they return.  The library owns only packed
- * weights and per-model workspace.  Every function returns 0 on success and non-zero on failure with a
+ * larger batch / sequence than any before), svc_ar_generate / svc_ar_generate_batch read tokens back every `check_every`
+ * steps, and the *_create functions finish packing before they return.  The library owns only packed weights and per-model workspace.  Every function returns 0 on success and non-zero on failure with a
  * message available from svc_last_error() (the Python shim re-raises it as RuntimeError, where the
  * reference raises Python exceptions: diffusion_transformer.py:121, inference.py:137,313).
  *
@@ -150,7 +149,7 @@ int svc_hift_forward(svc_hift_t* m, const float* mel, const float* f0, const flo
 int svc_bigvgan_set_microbatch(svc_bigvgan_t* m, int utterances);
 int svc_hift_set_microbatch(svc_hift_t* m, int utterances);
 
-/* ---------------------------------------------------------------- v2 AR model (decode step) */
+/* ---------------------------------------------------------------- v2 AR model (decode step, B = 1 and batched) */
 typedef struct svc_ar_config {        /* configs/v2/vc_wrapper.yaml:39-53 (modules.v2.ar.NaiveModelArgs) */
     int dim, n_head, n_local_heads, head_dim, n_layer, intermediate_size, vocab_size, max_seq_len;
     float rope_base, norm_eps;
@@ -160,7 +159,7 @@ typedef struct svc_ar svc_ar_t;
  * that `setup_caches(1, max_seq_len)` would (modules/v2/ar.py:160-179). */
 int svc_ar_create(const svc_ar_config_t* cfg, const svc_tensor_desc_t* weights, int n_weights, void* stream, svc_ar_t** out);
 void svc_ar_destroy(svc_ar_t* m);
-int svc_ar_reset(svc_ar_t* m, void* stream);      /* zero the KV cache */
+int svc_ar_reset(svc_ar_t* m, void* stream);      /* zero the KV cache (slot 0, the cache of the B = 1 calls) */
 /* Replaces `model.forward_generate(x, input_pos, kv_pos)` (modules/v2/ar.py:239-267) for B = 1: x [S][dim] fp32,
  * input_pos / kv_pos HOST [S]; logits_out [vocab] = logits of the last token. */
 int svc_ar_forward_generate(svc_ar_t* m, const float* x, int S, const int64_t* input_pos, const int64_t* kv_pos,
@@ -180,6 +179,33 @@ int svc_ar_decode_step(svc_ar_t* m, const float* x, int set_pos, int64_t input_p
 int svc_ar_generate(svc_ar_t* m, const float* x_prefill, int S, const int64_t* input_pos, const int64_t* kv_pos,
                     const float* exp_noise, int max_new, int min_tokens_before_eos, float temperature, float top_p,
                     float repetition_penalty, int check_every, int32_t* tokens_out, int32_t* n_tokens, void* stream);
+/* ---- batched AR: up to 64 sequences per decode step, each in its own SLOT (KV cache, input_pos, kv_pos).
+ * The calls above are the B = 1 path and work on slot 0, the cache svc_ar_create allocates; they are unaffected by the
+ * calls below.  One batched step reads every weight byte once for all slots (skinny MFMA GEMMs, M = B padded to 16 rows).
+ * A slot's result is bit-identical whatever B is, whichever slot it is given and whatever the other slots hold: no
+ * atomics, every reduction in a fixed order.  Cache rows at or above a sequence's kv_pos never reach its result as
+ * values (the batched attention addresses rows 0 .. kv_pos only), so a slot needs no reset between sequences.
+ *
+ * svc_ar_set_max_batch: 1 <= max_batch <= 64.  Allocates (or frees) the fp32 caches of slots 1 .. max_batch - 1,
+ * n_layer * 2 * n_local_heads * max_seq_len * 64 * 4 bytes each (25 MB for ar_base at 4096 positions).  Synchronises. */
+int svc_ar_set_max_batch(svc_ar_t* m, int max_batch, void* stream);
+/* svc_ar_forward_generate on the cache of slot `slot` (0 <= slot < max_batch). */
+int svc_ar_prefill_slot(svc_ar_t* m, int slot, const float* x, int S, const int64_t* input_pos, const int64_t* kv_pos,
+                        float* logits_out, void* stream);
+/* One token for each of slots 0 .. B-1 from a captured hipGraph (one per padded batch 16 / 32 / 48 / 64): x [B][dim],
+ * logits_out [B][vocab].  set_pos != 0 (re)sets the device positions from input_pos / kv_pos HOST [B] (required on the
+ * first step of a batch and after svc_ar_generate_batch); every call afterwards advances both by one per slot. */
+int svc_ar_decode_step_batch(svc_ar_t* m, int B, const float* x, int set_pos, const int64_t* input_pos, const int64_t* kv_pos,
+                             float* logits_out, void* stream);
+/* B independent svc_ar_generate loops in one (sequence b in slot b).  x_prefill: the prefill rows of all sequences
+ * concatenated, [sum S][dim]; S HOST [B]; input_pos / kv_pos HOST [sum S], concatenated alike; exp_noise device
+ * [B][max_new][vocab]; tokens_out device [B][max_new]; n_tokens HOST [B].  A sequence that has drawn EOS, holds max_new
+ * tokens or has filled its cache is masked, not compacted: its slot keeps running and records nothing more.  The host
+ * reads the slots' counters every `check_every` steps and returns once every sequence is finished. */
+int svc_ar_generate_batch(svc_ar_t* m, int B, const float* x_prefill, const int32_t* S, const int64_t* input_pos,
+                          const int64_t* kv_pos, const float* exp_noise, int max_new, int min_tokens_before_eos, float temperature,
+                          float top_p, float repetition_penalty, int check_every, int32_t* tokens_out, int32_t* n_tokens,
+                          void* stream);
 /* Replaces `sample(logits, previous_tokens, suppress_tokens, temperature, top_p, repetition_penalty)`
  * (modules/v2/ar.py:712-763): repetition penalty, top-p, temperature softmax, argmax(probs / q) with q = exp_noise
  * (the Exp(1) draw of multinomial_sample_one_no_sync, supplied by the caller).  suppress_token < 0 = none. */

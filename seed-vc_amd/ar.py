@@ -3,6 +3,8 @@
 `ARModel.forward_generate(x, input_pos, kv_pos)` mirrors `NaiveTransformer.forward_generate` (B = 1) and returns the
 last token's logits; `decode_step` is the hipGraph-captured one-token step (the reference's `compiled_decode_fn`);
 `sample(...)` mirrors `sample()/logits_to_probs()` with the Exp(1) noise drawn here unless supplied.
+`setup_caches(max_batch_size=B)` gives the handle B slots (one KV cache each); `generate_batch`, `prefill_slot` and
+`decode_step_batch` run up to 64 sequences per decode step on them.
 """
 import ctypes as C
 
@@ -31,8 +33,11 @@ class ARModel:
                      if "model.embeddings.weight" in state_dict else None)
 
     def setup_caches(self, max_batch_size=1, max_seq_len=None, dtype=None, device=None):
-        """Kept for call compatibility (vc_wrapper.py:328-329); the cache lives in the handle.  Resets it."""
+        """vc_wrapper.py:328-329.  The caches live in the handle: max_batch_size > 1 allocates one per slot
+        (`svc_ar_set_max_batch`; the default leaves the slots as they are); resets slot 0, the cache of the B = 1 calls."""
         with torch.cuda.device(self.device):
+            if max_batch_size > 1:
+                _lib.check(_lib.lib().svc_ar_set_max_batch(self._h, int(max_batch_size), _lib.stream_ptr()))
             _lib.check(_lib.lib().svc_ar_reset(self._h, _lib.stream_ptr()))
 
     @torch.inference_mode()
@@ -105,6 +110,72 @@ class ARModel:
                                                   C.c_float(repetition_penalty), int(check_every), _lib.ptr(toks), C.byref(n),
                                                   _lib.stream_ptr()))
         return toks[:n.value].long()[None, :]
+
+    @torch.inference_mode()
+    def prefill_slot(self, slot, x, input_pos, kv_pos):
+        """`forward_generate` on the cache of one slot (0 <= slot < max_batch_size): x (1, S, dim) -> logits (1, 1, vocab)."""
+        S = x.shape[1]
+        with torch.cuda.device(self.device):
+            xx = _lib.f32c(x, self.device).reshape(S, -1)
+            out = torch.empty(self.cfg["vocab_size"], device=self.device)
+            ip, kp = _lib.i64_host(input_pos.tolist()), _lib.i64_host(kv_pos.tolist())
+            _lib.check(_lib.lib().svc_ar_prefill_slot(self._h, int(slot), _lib.ptr(xx), S, ip, kp, _lib.ptr(out), _lib.stream_ptr()))
+        return out.reshape(1, 1, -1)
+
+    @torch.inference_mode()
+    def decode_step_batch(self, x, input_pos=None, kv_pos=None):
+        """One token for each of slots 0 .. B-1 from the captured batched step: x (B, dim) -> logits (B, vocab).  Pass the
+        B input_pos / kv_pos on the first step of a batch only (then they auto-advance)."""
+        xx = _lib.f32c(x, self.device)
+        xx = xx.reshape(-1, self.cfg["dim"])
+        B = xx.shape[0]
+        with torch.cuda.device(self.device):
+            out = torch.empty(B, self.cfg["vocab_size"], device=self.device)
+            set_pos = int(input_pos is not None)
+            ip = _lib.i64_host(torch.as_tensor(input_pos).reshape(-1).tolist()) if set_pos else None
+            kp = _lib.i64_host(torch.as_tensor(kv_pos).reshape(-1).tolist()) if set_pos else None
+            assert not set_pos or (len(ip) == B and len(kp) == B)
+            _lib.check(_lib.lib().svc_ar_decode_step_batch(self._h, B, _lib.ptr(xx), set_pos, ip, kp, _lib.ptr(out), _lib.stream_ptr()))
+        return out
+
+    @torch.inference_mode()
+    def generate_batch(self, prompt_texts, prompt_targets, exp_noise=None, top_p=0.7, temperature=0.7, repetition_penalty=1.5,
+                       max_new=4001, check_every=16):
+        """`generate` for B sequences at once (`svc_ar_generate_batch`; B <= the max_batch_size given to setup_caches):
+        lists of B prompt_text (1, Tt_b, dim) and prompt_target (1, Tp_b) tensors, exp_noise a list of B (>= n_b, vocab)
+        tensors of Exp(1) draws (drawn here when None) -> list of B (1, n_b) token tensors, each what `generate` gives
+        for that sequence alone."""
+        V, D, Lmax = self.cfg["vocab_size"], self.cfg["dim"], self.cfg["max_seq_len"]
+        B = len(prompt_texts)
+        assert B == len(prompt_targets) and (exp_noise is None or len(exp_noise) == B)
+        with torch.cuda.device(self.device):
+            sep = self._sep.reshape(1, D)
+            rows, S, input_pos, kv_pos = [], [], [], []
+            for text, tgt in zip(prompt_texts, prompt_targets):
+                text = _lib.f32c(text, self.device)[0]
+                tgt = tgt.to(self.device).long().reshape(-1)
+                rows += [sep, text, sep, self._emb[tgt]]
+                S.append(text.size(0) + 2 + tgt.numel())
+                input_pos += list(range(text.size(0) + 1)) + [0] + [i + 1 for i in range(tgt.numel())]
+                kv_pos += list(range(S[-1]))
+            emb_seq = torch.cat(rows, dim=0).contiguous()
+            cap = [min(int(max_new), Lmax - s + 1) for s in S]      # what `generate` allows each sequence
+            max_new = max(cap)
+            if exp_noise is None:
+                q = torch.empty(B, max_new, V, device=self.device).exponential_(1)
+            else:
+                q = torch.ones(B, max_new, V, device=self.device)
+                for b, e in enumerate(exp_noise):
+                    assert e.shape[0] >= cap[b] and e.shape[1] == V
+                    n = min(e.shape[0], max_new)
+                    q[b, :n] = _lib.f32c(e, self.device)[:n]
+            toks = torch.zeros(B, max_new, device=self.device, dtype=torch.int32)
+            n = (C.c_int32 * B)()
+            _lib.check(_lib.lib().svc_ar_generate_batch(self._h, B, _lib.ptr(emb_seq), (C.c_int32 * B)(*S), _lib.i64_host(input_pos),
+                                                        _lib.i64_host(kv_pos), _lib.ptr(q), max_new, 10, C.c_float(temperature),
+                                                        C.c_float(top_p), C.c_float(repetition_penalty), int(check_every),
+                                                        _lib.ptr(toks), n, _lib.stream_ptr()))
+        return [toks[b, :n[b]].long()[None, :] for b in range(B)]
 
     def close(self):
         if self._h:

@@ -12,6 +12,11 @@
 // modules/v2/vc_wrapper.py:105-114); positions live in device memory and are advanced inside the graph, so a replay
 // needs no host-side argument update.
 //
+// Up to 64 sequences decode together ("batched decode step" below): each in its own slot (KV cache, positions), the
+// linears as skinny MFMA GEMMs that read every weight byte once per step for all slots, one captured graph per padded
+// batch, and the generate loop's state per slot (svc_ar_set_max_batch / _prefill_slot / _decode_step_batch /
+// _generate_batch).  The B = 1 entry points and kernels do not change with it: slot 0 is their cache.
+//
 // reference: modules/v2/ar.py:239-267 (forward_generate), :75-93 (KVCache.update), :503-567 (Attention),
 //            :600-651 (RMSNorm, bf16 RoPE table), :712-763 (sample / logits_to_probs / exponential race).
 #include <math.h>
@@ -761,9 +766,9 @@ constexpr int SORT_N = 4096;
 // token, each lane counting over a 1/16 stride of the vocabulary held in LDS.  Writes the sorted (value, index) pairs and
 // the penalised logits.  V^2 comparisons spread over V / 16 workgroups (one CU alone needs ~100 us for them; the 78-stage
 // single-workgroup bitonic network this replaces took 74 us).
-__global__ __launch_bounds__(256) void ar_rank_kernel(const float* __restrict__ logits, int V, const int* __restrict__ prev, int n_prev,
-                                                      int suppress, float rep_pen, const GenState* __restrict__ gs,
-                                                      float* __restrict__ skey, int* __restrict__ sidx, float* __restrict__ lgp) {
+__device__ __forceinline__ void ar_rank_body(const float* __restrict__ logits, int V, const int* __restrict__ prev, int n_prev,
+                                             int suppress, float rep_pen, const GenState* __restrict__ gs,
+                                             float* __restrict__ skey, int* __restrict__ sidx, float* __restrict__ lgp) {
     if (gs) {   // generate loop: token gs->cnt; the repetition penalty sees previous_tokens[0] only (ar.py:442-444)
         prev = gs->toks; n_prev = 1;
         suppress = gs->cnt < gs->min_before_eos ? gs->eos : -1;
@@ -797,19 +802,17 @@ __global__ __launch_bounds__(256) void ar_rank_kernel(const float* __restrict__ 
     }
 }
 
+__global__ __launch_bounds__(256) void ar_rank_kernel(const float* __restrict__ logits, int V, const int* __restrict__ prev, int n_prev,
+                                                      int suppress, float rep_pen, const GenState* __restrict__ gs,
+                                                      float* __restrict__ skey, int* __restrict__ sidx, float* __restrict__ lgp) {
+    ar_rank_body(logits, V, prev, n_prev, suppress, rep_pen, gs, skey, sidx, lgp);
+}
+
 // Sampler stage 2 (one workgroup): softmax over the sorted logits, top-p cut, temperature softmax, exponential race.
-__global__ __launch_bounds__(1024) void ar_sample_kernel(const float* __restrict__ lgp, int V, const float* __restrict__ skey,
-                                                         const int* __restrict__ sidx, float temperature, float top_p,
-                                                         const float* __restrict__ exp_noise, int* __restrict__ idx_out,
-                                                         float* __restrict__ probs_out, GenState* __restrict__ gs,
-                                                         const float* __restrict__ emb, float* __restrict__ next_x, int D,
-                                                         int* __restrict__ pos) {
-    if (gs) {
-        const int t = gs->cnt;
-        temperature = gs->temperature; top_p = gs->top_p;
-        exp_noise = gs->noise + (size_t)t * V;
-        idx_out = gs->toks + t;
-    }
+// Returns the drawn token (the same value in every thread).
+__device__ __forceinline__ int ar_sample_body(const float* __restrict__ lgp, int V, const float* __restrict__ skey,
+                                              const int* __restrict__ sidx, float temperature, float top_p,
+                                              const float* __restrict__ exp_noise, float* __restrict__ probs_out) {
     __shared__ float key[SORT_N];
     __shared__ int idx[SORT_N];
     __shared__ float lg[SORT_N];       // penalised logits in vocabulary order, later reused
@@ -908,16 +911,438 @@ __global__ __launch_bounds__(1024) void ar_sample_kernel(const float* __restrict
         const int oi = r_idx[i];
         if (ob > best || (ob == best && oi < besti)) { best = ob; besti = oi; }
     }
-    idx[0] = besti;                    // every thread holds the same winner; the tail below reads idx[0]
+    idx[0] = besti;                    // every thread holds the same winner; the callers' tails read it from LDS
     __syncthreads();
-    if (tid == 0) idx_out[0] = idx[0];
+    return idx[0];
+}
+
+__global__ __launch_bounds__(1024) void ar_sample_kernel(const float* __restrict__ lgp, int V, const float* __restrict__ skey,
+                                                         const int* __restrict__ sidx, float temperature, float top_p,
+                                                         const float* __restrict__ exp_noise, int* __restrict__ idx_out,
+                                                         float* __restrict__ probs_out, GenState* __restrict__ gs,
+                                                         const float* __restrict__ emb, float* __restrict__ next_x, int D,
+                                                         int* __restrict__ pos) {
+    if (gs) {
+        const int t = gs->cnt;
+        temperature = gs->temperature; top_p = gs->top_p;
+        exp_noise = gs->noise + (size_t)t * V;
+        idx_out = gs->toks + t;
+    }
+    const int tid = threadIdx.x;
+    const int win = ar_sample_body(lgp, V, skey, sidx, temperature, top_p, exp_noise, probs_out);
+    if (tid == 0) idx_out[0] = win;
     if (gs && next_x) {
         // generate loop: this workgroup also prepares the next step -- embedding row of the token just drawn into the
         // residual buffer (ar.py:188-193,414), positions and token counter advanced (ar.py:402-403) -- which saves the
         // embed, copy and advance launches of every token (a dependent launch costs ~4.5 us whatever it does)
-        const long tk = idx[0];
+        const long tk = win;
         for (int c = tid; c < D; c += 1024) next_x[c] = emb[tk * D + c];
         if (tid == 0) { pos[0] += 1; pos[1] += 1; gs->cnt += 1; }
+    }
+}
+
+
+// ------------------------------------------------------------------------------------------ batched decode step (B <= 64)
+// One token for each of B sequences: slot b has its own KV cache, input_pos and kv_pos.  The per-token cost of the B = 1
+// step is the fp16 weight stream, which is the same for every sequence, so the linears become skinny GEMMs that read each
+// weight byte once per step for all slots; five launches per layer whatever B is:
+//   bgemm<NORM, QKV>   attention_norm + wqkv, RoPE, q -> bq, k / v -> each slot's cache row kv_pos[b]
+//   battn              one-token attention of every slot over its own cache prefix [0, kv_pos[b]]
+//   bgemm<PLAIN>       wo + residual
+//   bgemm<NORM, GLU>   ffn_norm + w1 / w3 + SwiGLU
+//   bgemm<PLAIN>       w2 + residual
+// then bgemm<NORM, PLAIN> for the final norm + output head and the sampler over B rows.  The composed `wc` matrices of
+// the B = 1 step are not used.  Nothing here uses atomics, and every reduction has a fixed order that depends on the
+// model shape alone, so a slot's result is bit-identical whatever B is and whatever the other slots hold.
+constexpr int MAXB = 64;
+
+// GenState of one slot + its loop flags.  A finished slot (EOS drawn, max_new reached, or the next position would leave the
+// cache) stays in the batch: it re-runs its last step in place (same positions, same cache row) and records nothing.
+struct GenSlot : GenState {
+    int done;
+    int max_new;
+};
+
+enum { BG_PLAIN = 0, BG_GLU = 1, BG_QKV = 2 };
+struct BGemmArgs {
+    const void* x; long ldx;            // [Bp][K], NORM ? fp32 : fp16
+    const float* gamma; float eps;
+    const half_t* W; long ldw;          // [N rounded up to 16][K] fp16
+    const float* res;                   // PLAIN: optional residual [Bp][ldo]
+    float* out32; half_t* out16; long ldo;
+    int N, K;
+    // QKV
+    float* q_out;                       // [Bp][H * 64]
+    float* const* kc; float* const* vc; // [MAXB] cache base of every slot for this layer
+    const float* rope;
+    const int* pos;                     // [0, MAXB) input_pos, [MAXB, 2 MAXB) kv_pos
+    const int* nb;                      // live slots: rows b >= *nb are padding of the M tile and touch no cache
+    int H, Hkv, Lmax;
+};
+
+// out[b][n] = sum_k x[b][k] W[n][k] on v_mfma_f32_16x16x32_f16 with the WEIGHT rows as the MFMA's M side and the batch
+// as its N side: a lane's four accumulator registers are four CONSECUTIVE output features n of one slot b, so a RoPE
+// pair, a (w1_j, w3_j) SwiGLU pair and a 16-byte store all stay inside one lane.
+// A workgroup (4 waves) owns 16 NT weight rows; the waves split K in four contiguous ranges, so a weight byte is read by
+// exactly one wave of one workgroup: it goes straight to VGPRs with 16-byte loads (no LDS round trip), and so do the
+// activation fragments (<= 64 x K, L2-resident).  The four partial tiles meet in LDS and are summed in wave order.
+// NORM: x is the fp32 residual stream; the RMSNorm weight is applied to the fragment, 1 / rms(x[b]) is one scalar per
+// output column and is applied after the reduction (the sum of squares rides along with the fragment loads).
+// MT = M tiles of 16 slots (Bp / 16): more column tiles of the same code, nothing else changes with B; NT = 16-row weight
+// tiles per workgroup; KC = K when known at compile time (the ar_base sizes: k-steps unrolled in groups whose requests all
+// go out before the group's first MFMA waits), 0 = runtime K.
+template <bool NORM, int EPI, int MT, int NT, int KC>
+__global__ __launch_bounds__(256) void bgemm_kernel(const BGemmArgs a) {
+    __shared__ __attribute__((aligned(16))) float part[4][NT * MT][4][64];
+    __shared__ float ssq[NORM ? 4 : 1][MT][64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r = lane & 15, g = lane >> 4;
+    const int n0 = blockIdx.x * (16 * NT);
+    const int K = KC ? KC : a.K;
+    const int nsteps = K >> 5, per = (nsteps + 3) >> 2;          // 32-element k-steps, a contiguous quarter per wave
+    constexpr bool FULL = KC != 0 && ((KC >> 5) % 4) == 0;
+    const int s0 = wave * per;
+    float4v acc[NT][MT];
+    float ss[MT];
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+        ss[m] = 0.f;
+#pragma unroll
+        for (int t = 0; t < NT; ++t) acc[t][m] = (float4v){0.f, 0.f, 0.f, 0.f};
+    }
+    const half_t* wrow = a.W + (long)(n0 + r) * a.ldw + 8 * g;
+    // one k-step = a lane's 16-byte fragments: NT weight rows, MT activation rows (NORM: 32 bytes of fp32 + the norm weight)
+    struct Frag {
+        half8 w[NT];
+        half8 xh[NORM ? 1 : MT];
+        float4v x0[NORM ? MT : 1], x1[NORM ? MT : 1], g0, g1;
+    };
+    auto load = [&](int s, Frag& f) {
+        const int k = 32 * s + 8 * g;
+#pragma unroll
+        for (int t = 0; t < NT; ++t) f.w[t] = *reinterpret_cast<const half8*>(wrow + (long)16 * t * a.ldw + 32 * s);
+        if constexpr (NORM) {
+            f.g0 = *reinterpret_cast<const float4v*>(a.gamma + k);
+            f.g1 = *reinterpret_cast<const float4v*>(a.gamma + k + 4);
+#pragma unroll
+            for (int m = 0; m < MT; ++m) {
+                const float* xp = reinterpret_cast<const float*>(a.x) + (long)(16 * m + r) * a.ldx + k;
+                f.x0[m] = *reinterpret_cast<const float4v*>(xp);
+                f.x1[m] = *reinterpret_cast<const float4v*>(xp + 4);
+            }
+        } else {
+#pragma unroll
+            for (int m = 0; m < MT; ++m)
+                f.xh[m] = *reinterpret_cast<const half8*>(reinterpret_cast<const half_t*>(a.x) + (long)(16 * m + r) * a.ldx + k);
+        }
+    };
+    auto mma = [&](const Frag& f) {
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+            half8 xf;
+            if constexpr (NORM) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    ss[m] += f.x0[m][j] * f.x0[m][j] + f.x1[m][j] * f.x1[m][j];
+                    xf[j] = (half_t)(f.x0[m][j] * f.g0[j]);
+                    xf[4 + j] = (half_t)(f.x1[m][j] * f.g1[j]);
+                }
+            } else {
+                xf = f.xh[m];
+            }
+#pragma unroll
+            for (int t = 0; t < NT; ++t) acc[t][m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(f.w[t], xf, acc[t][m], 0, 0, 0);
+        }
+    };
+    if constexpr (FULL) {
+        // groups of U k-steps: every request of a group is issued before its first MFMA waits (deep unroll, late vmcnt) --
+        // step by step the compiler kept ~8 requests in flight per wave, and one wave per SIMD then waits out a memory
+        // round trip per step
+        constexpr int PER = (KC >> 5) >> 2;
+        constexpr int U = NORM ? (PER % 3 == 0 ? 3 : 1) : (PER % 6 == 0 ? 6 : PER % 2 == 0 ? 2 : 1);
+#pragma unroll
+        for (int i0 = 0; i0 < PER; i0 += U) {
+            Frag f[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) load(s0 + i0 + u, f[u]);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int u = 0; u < U; ++u) mma(f[u]);
+        }
+    } else {
+        const int s1 = s0 + per < nsteps ? s0 + per : nsteps;
+        for (int s = s0; s < s1; ++s) {
+            Frag f;
+            load(s, f);
+            mma(f);
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) part[wave][t * MT + m][i][lane] = acc[t][m][i];
+    if constexpr (NORM) {
+#pragma unroll
+        for (int m = 0; m < MT; ++m) ssq[wave][m][lane] = ss[m];
+    }
+    __syncthreads();
+    // wave w finishes the tiles w, w + 4, ...: partials summed in wave order, then the epilogue
+#pragma unroll
+    for (int q0 = 0; q0 < NT * MT; q0 += 4) {
+        const int q = q0 + wave;
+        if (q >= NT * MT) break;
+        const int t = q / MT, m = q % MT;
+        float4v v;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = ((part[0][q][i][lane] + part[1][q][i][lane]) + part[2][q][i][lane]) + part[3][q][i][lane];
+        const int b = 16 * m + r;               // slot (MFMA column)
+        const int n = n0 + 16 * t + 4 * g;      // output features n .. n + 3
+        if constexpr (NORM) {
+            float tot = 0.f;
+#pragma unroll
+            for (int w = 0; w < 4; ++w)
+#pragma unroll
+                for (int gg = 0; gg < 4; ++gg) tot += ssq[w][m][r + 16 * gg];
+            const float rstd = rsqrtf(tot / (float)K + a.eps);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) v[i] *= rstd;
+        }
+        if (n >= a.N) continue;
+        if constexpr (EPI == BG_GLU) {          // rows (2 j, 2 j + 1) = (w1_j, w3_j)
+            half2v o;
+            o[0] = (half_t)((v[0] / (1.f + __expf(-v[0]))) * v[1]);
+            o[1] = (half_t)((v[2] / (1.f + __expf(-v[2]))) * v[3]);
+            *reinterpret_cast<half2v*>(a.out16 + (long)b * a.ldo + (n >> 1)) = o;
+        } else if constexpr (EPI == BG_PLAIN) {
+            if (n + 3 < a.N && (a.ldo & 3) == 0) {
+                if (a.res) v += *reinterpret_cast<const float4v*>(a.res + (long)b * a.ldo + n);
+                *reinterpret_cast<float4v*>(a.out32 + (long)b * a.ldo + n) = v;
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    if (n + i < a.N) a.out32[(long)b * a.ldo + n + i] = v[i] + (a.res ? a.res[(long)b * a.ldo + n + i] : 0.f);
+            }
+        } else {                                // QKV: n .. n + 3 = two rotation pairs of one head
+            if (b >= *a.nb) continue;
+            const int D = a.H * 64, kvd = a.Hkv * 64;
+            const int ip = a.pos[b], kp = a.pos[MAXB + b];
+            if (n < D + kvd) {
+                const float4v cs = *reinterpret_cast<const float4v*>(a.rope + ((long)ip * 32 + ((n & 63) >> 1)) * 2);
+                const float4v o = {v[0] * cs[0] - v[1] * cs[1], v[1] * cs[0] + v[0] * cs[1],
+                                   v[2] * cs[2] - v[3] * cs[3], v[3] * cs[2] + v[2] * cs[3]};
+                if (n < D) {
+                    *reinterpret_cast<float4v*>(a.q_out + (long)b * D + n) = o;
+                } else {
+                    const int e = n - D;
+                    *reinterpret_cast<float4v*>(a.kc[b] + ((long)(e >> 6) * a.Lmax + kp) * 64 + (e & 63)) = o;
+                }
+            } else {
+                const int e = n - D - kvd;
+                *reinterpret_cast<float4v*>(a.vc[b] + ((long)(e >> 6) * a.Lmax + kp) * 64 + (e & 63)) = v;
+            }
+        }
+    }
+}
+
+template <bool NORM, int EPI, int NT, int KC>
+int bgemm_launch(const BGemmArgs& a, int Bp, hipStream_t st) {
+    const dim3 grid(cdiv(a.N, 16 * NT)), block(256);
+    switch (Bp / 16) {
+        case 1: hipLaunchKernelGGL((bgemm_kernel<NORM, EPI, 1, NT, KC>), grid, block, 0, st, a); break;
+        case 2: hipLaunchKernelGGL((bgemm_kernel<NORM, EPI, 2, NT, KC>), grid, block, 0, st, a); break;
+        case 3: hipLaunchKernelGGL((bgemm_kernel<NORM, EPI, 3, NT, KC>), grid, block, 0, st, a); break;
+        default: hipLaunchKernelGGL((bgemm_kernel<NORM, EPI, 4, NT, KC>), grid, block, 0, st, a); break;
+    }
+    SVC_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// One-token attention of slot b = blockIdx.y for GT query heads of one KV head (GQA: they share every key / value row; GT = 3
+// of the 6 heads per KV head for ar_base: the cache prefix is read twice, from L2, and the per-key arithmetic -- which is
+// what a workgroup spends its time on -- is spread over twice the CUs).  512 threads, keys in chunks of 512:
+//   loads  : every cache row of the chunk is requested at once -- one memory round trip per chunk; 32 groups of 16
+//            lanes, group = keys j (mod 32), lane = 4 of the 64 columns, so a row is one 256-byte request (a thread that
+//            reads a whole key row by itself touches 64 lines per instruction and evicts them before it comes back)
+//   scores : 4 FMAs + a 16-lane DPP sum per (key, head), q (pre-scaled by 1/8) in registers; scores -> LDS
+//   softmax: one thread per key; chunk maximum per head over the 8 waves, running (max, sum) across chunks (one rescale
+//            per chunk); probabilities -> LDS
+//   PV     : the same groups and columns as the loads
+//   merge  : the 4 groups of a wave by two lane exchanges, the 8 waves through LDS in wave order.
+// Only rows 0 .. kv_pos[b] of the slot's cache are ever addressed (an index past the prefix is clamped into it and its
+// probability is exactly 0), so whatever an earlier, longer sequence left in the rows above cannot reach the result, not
+// even as 0 x value.
+constexpr int BA_CH = 512;          // one key per thread and chunk
+template <int GT>
+__global__ __launch_bounds__(512) void battn_kernel(const float* __restrict__ q, float* const* __restrict__ kc_tab,
+                                                    float* const* __restrict__ vc_tab, half_t* __restrict__ y,
+                                                    const int* __restrict__ pos, const int* __restrict__ nb, int H, int Hkv, int Lmax) {
+    __shared__ __attribute__((aligned(16))) float sc[GT][BA_CH];
+    __shared__ __attribute__((aligned(16))) float pw[8][GT][64];
+    __shared__ float redm[8][GT], redl[8][GT];
+    const int b = blockIdx.y;
+    // position and cache bases are requested together with the live-slot count, not after it: one round trip, not two
+    // (every slot has a valid position; the bases of a slot that was never allocated are null and are not used)
+    const int n_keys = pos[MAXB + b] + 1;
+    const float* kslot = kc_tab[b];
+    const float* vslot = vc_tab[b];
+    if (b >= *nb) return;
+    const int G = H / Hkv, ngrp = G / GT;
+    const int hk = blockIdx.x / ngrp, h0 = hk * G + (blockIdx.x % ngrp) * GT;
+    const int D = H * 64;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, grp = tid >> 4, c = tid & 15;
+    float4v qv[GT];                             // this lane's four columns of every head's q
+#pragma unroll
+    for (int i = 0; i < GT; ++i) qv[i] = *reinterpret_cast<const float4v*>(q + (long)b * D + (h0 + i) * 64 + 4 * c) * 0.125f;   // 1 / sqrt(64), exact
+    const float* kb = kslot + (long)hk * Lmax * 64;
+    const float* vb = vslot + (long)hk * Lmax * 64;
+    float4v acc[GT];
+    float m_run[GT], l_run[GT];
+#pragma unroll
+    for (int i = 0; i < GT; ++i) {
+        acc[i] = (float4v){0.f, 0.f, 0.f, 0.f};
+        m_run[i] = -1e30f;
+        l_run[i] = 0.f;
+    }
+    for (int c0 = 0; c0 < n_keys; c0 += BA_CH) {
+        const int nk = n_keys - c0 < BA_CH ? n_keys - c0 : BA_CH;
+        // every cache row this thread needs from the chunk is requested here, before anything waits: 16 key and 16 value
+        // quarter-rows (rows group + 32 u: a row is one 256-byte request of its 16 lanes); an index past the chunk is
+        // clamped into it and masked below.  Wave-uniform base + 32-bit lane offset: one address register per request.
+        float4v kx[BA_CH / 32], vx[BA_CH / 32];
+#pragma unroll
+        for (int u = 0; u < BA_CH / 32; ++u) {
+            const int jj = grp + 32 * u;
+            const unsigned o = (unsigned)(c0 + (jj < nk ? jj : nk - 1)) * 64u + 4u * (unsigned)c;
+            kx[u] = *reinterpret_cast<const float4v*>(kb + o);
+            vx[u] = *reinterpret_cast<const float4v*>(vb + o);
+        }
+#pragma unroll
+        for (int u = 0; u < BA_CH / 32; ++u) {
+            const int jj = grp + 32 * u;
+#pragma unroll
+            for (int i = 0; i < GT; ++i) {
+                const float a = row16_sum_f(qv[i][0] * kx[u][0] + qv[i][1] * kx[u][1] + qv[i][2] * kx[u][2] + qv[i][3] * kx[u][3]);
+                if (c == 0) sc[i][jj] = jj < nk ? a : -1e30f;
+            }
+        }
+        __syncthreads();
+        const bool has_key = tid < nk;
+        float s[GT];
+#pragma unroll
+        for (int i = 0; i < GT; ++i) s[i] = sc[i][tid];
+        float mx[GT];
+#pragma unroll
+        for (int i = 0; i < GT; ++i) {
+            mx[i] = s[i];
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) mx[i] = fmaxf(mx[i], __shfl_xor(mx[i], o));
+            if (lane == 0) redm[wave][i] = mx[i];
+        }
+        __syncthreads();
+        float scale[GT], ls[GT];
+#pragma unroll
+        for (int i = 0; i < GT; ++i) {
+            float m = m_run[i];
+#pragma unroll
+            for (int w = 0; w < 8; ++w) m = fmaxf(m, redm[w][i]);
+            scale[i] = __expf(m_run[i] - m);
+            m_run[i] = m;
+            const float p = has_key ? __expf(s[i] - m) : 0.f;
+            sc[i][tid] = p;
+            ls[i] = wave_sum_f(p);
+            if (lane == 0) redl[wave][i] = ls[i];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < GT; ++i) {
+            float l = 0.f;
+#pragma unroll
+            for (int w = 0; w < 8; ++w) l += redl[w][i];
+            l_run[i] = l_run[i] * scale[i] + l;
+            acc[i] *= scale[i];
+        }
+#pragma unroll
+        for (int u = 0; u < BA_CH / 32; ++u) {
+            const int jj = grp + 32 * u;            // sc holds 0 for the keys past the chunk
+#pragma unroll
+            for (int i = 0; i < GT; ++i) acc[i] += sc[i][jj] * vx[u];
+        }
+        __syncthreads();                        // sc, redm and redl are rewritten by the next chunk
+    }
+#pragma unroll
+    for (int i = 0; i < GT; ++i) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float a = acc[i][j];
+            a += __shfl_xor(a, 16);
+            a += __shfl_xor(a, 32);
+            acc[i][j] = a;
+        }
+        if (lane < 16) *reinterpret_cast<float4v*>(&pw[wave][i][4 * c]) = acc[i];
+    }
+    __syncthreads();
+    for (int e = tid; e < GT * 64; e += 512) {
+        const int i = e >> 6, d = e & 63;
+        float o = 0.f;
+#pragma unroll
+        for (int w = 0; w < 8; ++w) o += pw[w][i][d];
+        float l = l_run[0];                     // l_run[i] without a dynamic register index
+#pragma unroll
+        for (int k = 1; k < GT; ++k) l = i == k ? l_run[k] : l;
+        y[(long)b * D + (h0 + i) * 64 + d] = (half_t)(o / l);
+    }
+}
+
+__global__ void advance_pos_batch_kernel(int* __restrict__ pos, const int* __restrict__ nb) {
+    const int b = threadIdx.x;
+    if (b < *nb) { pos[b] += 1; pos[MAXB + b] += 1; }
+}
+
+// x[b] = embeddings[last token of slot b]
+__global__ void ar_embed_batch_kernel(const float* __restrict__ emb, const GenSlot* __restrict__ slots, float* __restrict__ x, int D) {
+    const GenSlot* gs = slots + blockIdx.x;
+    const long t = gs->toks[gs->cnt - 1];
+    for (int c = threadIdx.x; c < D; c += blockDim.x) x[(long)blockIdx.x * D + c] = emb[t * D + c];
+}
+
+__global__ __launch_bounds__(256) void ar_rank_batch_kernel(const float* __restrict__ logits, int V, const GenSlot* __restrict__ slots,
+                                                            const int* __restrict__ nb, float* __restrict__ skey,
+                                                            int* __restrict__ sidx, float* __restrict__ lgp) {
+    const int b = blockIdx.y;
+    if (b >= *nb) return;
+    ar_rank_body(logits + (long)b * V, V, nullptr, 0, -1, 1.f, slots + b, skey + (long)b * SORT_N, sidx + (long)b * SORT_N,
+                 lgp + (long)b * SORT_N);
+}
+
+// Sampler stage 2 for slot b = blockIdx.x, then the slot's loop state: record the token, embed it as the next input,
+// advance the positions -- or finish the slot (EOS; max_new tokens; the next position would leave the cache).
+__global__ __launch_bounds__(1024) void ar_sample_batch_kernel(const float* __restrict__ lgp, int V, const float* __restrict__ skey,
+                                                               const int* __restrict__ sidx, GenSlot* __restrict__ slots,
+                                                               const int* __restrict__ nb, const float* __restrict__ emb,
+                                                               float* __restrict__ next_x, int D, int* __restrict__ pos, int Lmax) {
+    const int b = blockIdx.x;
+    if (b >= *nb) return;
+    GenSlot* gs = slots + b;
+    const int tid = threadIdx.x;
+    const int t = gs->cnt, was_done = gs->done;         // read by every thread before thread 0 changes them (barriers in the body)
+    const int row = t < gs->max_new ? t : gs->max_new - 1;      // a slot finished by max_new has no noise row t
+    const int win = ar_sample_body(lgp + (long)b * SORT_N, V, skey + (long)b * SORT_N, sidx + (long)b * SORT_N, gs->temperature,
+                                   gs->top_p, gs->noise + (size_t)row * V, nullptr);
+    const bool record = !was_done && win != gs->eos;
+    const long tk = record ? win : gs->toks[t - 1];     // a finished slot keeps its last input
+    for (int c = tid; c < D; c += 1024) next_x[(long)b * D + c] = emb[tk * D + c];
+    if (tid == 0 && !was_done) {
+        gs->toks[t] = win;
+        if (!record) {
+            gs->done = 1;                               // EOS: cnt = tokens before it
+        } else {
+            const int ip = pos[b] + 1, kp = pos[MAXB + b] + 1;
+            gs->cnt = t + 1;
+            if (t + 1 >= gs->max_new || ip >= Lmax || kp >= Lmax) gs->done = 1;
+            else { pos[b] = ip; pos[MAXB + b] = kp; }
+        }
     }
 }
 
@@ -962,6 +1387,32 @@ struct svc_ar {
     int run_gemv_layers(int S, const int* d_positions, hipStream_t st);
     int run_gemm_layers(int S, const int* d_positions, hipStream_t st);
     int run_head(int S, float* logits_out, hipStream_t st);
+
+    // ---- batch (svc_ar_set_max_batch): slot 0 is the cache above, slots 1 .. max_batch - 1 are allocated on request.
+    // The batch workspace is separate from `ws` (which reserve() may reallocate): the captured batch graphs stay valid.
+    int max_batch = 1;
+    Arena slot_mem, bws;
+    std::vector<float*> slot_base;     // [max_batch], slot >= 1: layer i keys at + 2 i cache_elems(), values at + (2 i + 1) cache_elems()
+    float** d_kvtab = nullptr;         // device [L][2][MAXB] cache bases per layer (keys, values) and slot; null = no such slot
+    float *bh = nullptr, *bq = nullptr, *blogits = nullptr;      // [MAXB][D] residual / q, [MAXB][V]
+    half_t *by16 = nullptr, *bff16 = nullptr;                    // [MAXB][D], [MAXB][I]
+    int *d_bpos = nullptr, *d_nb = nullptr;
+    GenSlot* d_slots = nullptr;
+    float *b_skey = nullptr, *b_lgp = nullptr;
+    int* b_sidx = nullptr;
+    hipGraphExec_t bstep_graph[MAXB / 16] = {}, bgen_graph[MAXB / 16] = {};     // by padded batch: 16, 32, 48, 64 rows
+    int cur_nb = 0;                    // value of *d_nb
+    int bpos_n = 0;                    // slots whose device positions h_bpos mirrors (0: svc_ar_decode_step_batch needs set_pos)
+    int h_bpos[2 * MAXB] = {};
+    size_t cache_elems() const { return (size_t)Hkv * Lmax * 64; }
+    float* slot_kc(int slot, int layer) const { return slot ? slot_base[slot] + 2 * layer * cache_elems() : layers[layer].kc; }
+    float* slot_vc(int slot, int layer) const { return slot ? slot_base[slot] + (2 * layer + 1) * cache_elems() : layers[layer].vc; }
+    int ensure_batch_ws(hipStream_t st);
+    int upload_kvtab(hipStream_t st);
+    int set_nb(int B, hipStream_t st);
+    int prefill_slot(int slot, const float* x, int S, const int64_t* input_pos, const int64_t* kv_pos, float* logits_out, hipStream_t st);
+    int run_batch_step(int Bp, hipStream_t st);
+    int ensure_batch_graph(int Bp, bool gen);
 };
 
 namespace {
@@ -1162,6 +1613,134 @@ int svc_ar::ensure_gen_graph() {
     });
 }
 
+// ---- batch ---------------------------------------------------------------------------------------------------------
+int svc_ar::ensure_batch_ws(hipStream_t st) {
+    if (d_nb) return 0;
+    bh = bws.alloc_n<float>((size_t)MAXB * D, st);
+    bq = bws.alloc_n<float>((size_t)MAXB * D, st);
+    blogits = bws.alloc_n<float>((size_t)MAXB * V, st);
+    by16 = bws.alloc_n<half_t>((size_t)MAXB * D, st);
+    bff16 = bws.alloc_n<half_t>((size_t)MAXB * I, st);
+    d_bpos = bws.alloc_n<int>(2 * MAXB, st);
+    d_slots = reinterpret_cast<GenSlot*>(bws.alloc(MAXB * sizeof(GenSlot), st));
+    b_skey = bws.alloc_n<float>((size_t)MAXB * SORT_N, st);
+    b_sidx = bws.alloc_n<int>((size_t)MAXB * SORT_N, st);
+    b_lgp = bws.alloc_n<float>((size_t)MAXB * SORT_N, st);
+    d_kvtab = reinterpret_cast<float**>(bws.alloc((size_t)L * 2 * MAXB * sizeof(float*), st));
+    int* nb = bws.alloc_n<int>(1, st);
+    if (!bh || !bq || !blogits || !by16 || !bff16 || !d_bpos || !d_slots || !b_skey || !b_sidx || !b_lgp || !d_kvtab || !nb) {
+        bws.release();
+        return 1;
+    }
+    if (slot_base.empty()) slot_base.assign(1, nullptr);
+    d_nb = nb;
+    cur_nb = 0;
+    return upload_kvtab(st);
+}
+
+int svc_ar::upload_kvtab(hipStream_t st) {
+    std::vector<float*> tab((size_t)L * 2 * MAXB, nullptr);
+    for (int i = 0; i < L; ++i)
+        for (int b = 0; b < max_batch; ++b) {
+            tab[((size_t)i * 2) * MAXB + b] = slot_kc(b, i);
+            tab[((size_t)i * 2 + 1) * MAXB + b] = slot_vc(b, i);
+        }
+    SVC_CHECK_HIP(hipMemcpyAsync(d_kvtab, tab.data(), tab.size() * sizeof(float*), hipMemcpyHostToDevice, st));
+    SVC_CHECK_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
+int svc_ar::set_nb(int B, hipStream_t st) {
+    if (B == cur_nb) return 0;
+    SVC_CHECK_HIP(hipMemcpyAsync(d_nb, &B, sizeof(int), hipMemcpyHostToDevice, st));
+    SVC_CHECK_HIP(hipStreamSynchronize(st));
+    cur_nb = B;
+    return 0;
+}
+
+// svc_ar_forward_generate on one slot's cache.  Every slot, slot 0 included, takes the GEMV-pair (S <= 8) or tap-GEMM
+// layers -- never the B = 1 decode step -- so a sequence computes the same thing whichever slot it is given.
+int svc_ar::prefill_slot(int slot, const float* x, int S, const int64_t* input_pos, const int64_t* kv_pos, float* logits_out,
+                         hipStream_t st) {
+    if (reserve(S, st)) return 1;
+    std::vector<int> pos(2 * S);
+    for (int s = 0; s < S; ++s) {
+        SVC_REQUIRE(input_pos[s] >= 0 && input_pos[s] < Lmax && kv_pos[s] >= 0 && kv_pos[s] < Lmax, "position out of range");
+        pos[s] = (int)input_pos[s];
+        pos[S + s] = (int)kv_pos[s];
+    }
+    SVC_CHECK_HIP(hipMemcpyAsync(d_pos, pos.data(), pos.size() * 4, hipMemcpyHostToDevice, st));
+    SVC_CHECK_HIP(hipStreamSynchronize(st));
+    SVC_CHECK_HIP(hipMemcpyAsync(h32, x, (size_t)S * D * 4, hipMemcpyDeviceToDevice, st));
+    // the layer loops read the cache pointers from `layers`: point them at the slot while they enqueue
+    std::vector<Layer> own = layers;
+    for (int i = 0; i < L; ++i) { layers[i].kc = slot_kc(slot, i); layers[i].vc = slot_vc(slot, i); }
+    const int rc = S <= 8 ? run_gemv_layers(S, d_pos, st) : run_gemm_layers(S, d_pos, st);
+    layers = own;
+    if (rc) return 1;
+    return run_head(S, logits_out, st);
+}
+
+// The batched step on bh [Bp][D] (in place) -> blogits [Bp][V]; positions from d_bpos, live slots from d_nb.
+int svc_ar::run_batch_step(int Bp, hipStream_t st) {
+    const int G = H / Hkv;
+    const int GT = G % 3 == 0 ? 3 : G % 2 == 0 ? 2 : 1;       // query heads per attention workgroup
+    const bool base = D == 768 && I == 2304;       // ar_base: reduction lengths known at compile time
+    auto go = [&](auto KD, auto KI) {
+        for (int i = 0; i < L; ++i) {
+            const Layer& ly = layers[i];
+            float* const* kct = d_kvtab + ((size_t)i * 2) * MAXB;
+            float* const* vct = d_kvtab + ((size_t)i * 2 + 1) * MAXB;
+            BGemmArgs a;
+            memset(&a, 0, sizeof(a));
+            a.x = bh; a.ldx = D; a.gamma = ly.g_attn; a.eps = cfg.norm_eps; a.W = ly.wqkv; a.ldw = D; a.N = Nqkv; a.K = D;
+            a.q_out = bq; a.kc = kct; a.vc = vct; a.rope = rope; a.pos = d_bpos; a.nb = d_nb; a.H = H; a.Hkv = Hkv; a.Lmax = Lmax;
+            if (bgemm_launch<true, BG_QKV, 1, KD>(a, Bp, st)) return 1;
+            const dim3 ag(Hkv * (G / GT), Bp);
+            switch (GT) {
+                case 3: hipLaunchKernelGGL(battn_kernel<3>, ag, dim3(512), 0, st, bq, kct, vct, by16, d_bpos, d_nb, H, Hkv, Lmax); break;
+                case 2: hipLaunchKernelGGL(battn_kernel<2>, ag, dim3(512), 0, st, bq, kct, vct, by16, d_bpos, d_nb, H, Hkv, Lmax); break;
+                default: hipLaunchKernelGGL(battn_kernel<1>, ag, dim3(512), 0, st, bq, kct, vct, by16, d_bpos, d_nb, H, Hkv, Lmax); break;
+            }
+            SVC_CHECK_HIP(hipGetLastError());
+            memset(&a, 0, sizeof(a));
+            a.x = by16; a.ldx = D; a.W = ly.wo; a.ldw = D; a.res = bh; a.out32 = bh; a.ldo = D; a.N = D; a.K = D;
+            if (bgemm_launch<false, BG_PLAIN, 1, KD>(a, Bp, st)) return 1;
+            memset(&a, 0, sizeof(a));
+            a.x = bh; a.ldx = D; a.gamma = ly.g_ffn; a.eps = cfg.norm_eps; a.W = ly.w13; a.ldw = D; a.out16 = bff16; a.ldo = I;
+            a.N = 2 * I; a.K = D;
+            if (bgemm_launch<true, BG_GLU, 2, KD>(a, Bp, st)) return 1;
+            memset(&a, 0, sizeof(a));
+            a.x = bff16; a.ldx = I; a.W = ly.w2; a.ldw = I; a.res = bh; a.out32 = bh; a.ldo = D; a.N = D; a.K = I;
+            if (bgemm_launch<false, BG_PLAIN, 1, KI>(a, Bp, st)) return 1;
+        }
+        BGemmArgs a;
+        memset(&a, 0, sizeof(a));
+        a.x = bh; a.ldx = D; a.gamma = g_final; a.eps = cfg.norm_eps; a.W = w_out; a.ldw = D; a.out32 = blogits; a.ldo = V;
+        a.N = V; a.K = D;
+        return bgemm_launch<true, BG_PLAIN, 1, KD>(a, Bp, st);
+    };
+    return base ? go(IntC<768>(), IntC<2304>()) : go(IntC<0>(), IntC<0>());
+}
+
+// One captured chain per padded batch: the step, then either the position advance (svc_ar_decode_step_batch) or the
+// sampler over the live rows with the next embedding and the loop state (svc_ar_generate_batch).
+int svc_ar::ensure_batch_graph(int Bp, bool gen) {
+    hipGraphExec_t* ge = (gen ? bgen_graph : bstep_graph) + (Bp / 16 - 1);
+    if (*ge) return 0;
+    return capture_graph(ge, [&](hipStream_t cs) {
+        if (run_batch_step(Bp, cs)) return 1;
+        if (!gen) {
+            hipLaunchKernelGGL(advance_pos_batch_kernel, dim3(1), dim3(MAXB), 0, cs, d_bpos, d_nb);
+        } else {
+            hipLaunchKernelGGL(ar_rank_batch_kernel, dim3(cdiv(V, 16), Bp), dim3(256), 0, cs, blogits, V, d_slots, d_nb, b_skey, b_sidx, b_lgp);
+            hipLaunchKernelGGL(ar_sample_batch_kernel, dim3(Bp), dim3(1024), 0, cs, b_lgp, V, b_skey, b_sidx, d_slots, d_nb, emb, bh, D,
+                               d_bpos, Lmax);
+        }
+        return hipGetLastError() != hipSuccess ? 1 : 0;
+    });
+}
+
 extern "C" {
 
 int svc_ar_create(const svc_ar_config_t* cfg, const svc_tensor_desc_t* weights, int n_weights, void* stream, svc_ar_t** out) {
@@ -1291,6 +1870,10 @@ int svc_ar_create(const svc_ar_config_t* cfg, const svc_tensor_desc_t* weights, 
 void svc_ar_destroy(svc_ar_t* m) {
     if (m && m->graph) (void)hipGraphExecDestroy(m->graph);
     if (m && m->gen_graph) (void)hipGraphExecDestroy(m->gen_graph);
+    for (int i = 0; m && i < MAXB / 16; ++i) {
+        if (m->bstep_graph[i]) (void)hipGraphExecDestroy(m->bstep_graph[i]);
+        if (m->bgen_graph[i]) (void)hipGraphExecDestroy(m->bgen_graph[i]);
+    }
     delete m;
 }
 
@@ -1385,6 +1968,139 @@ int svc_ar_generate(svc_ar_t* m, const float* x_prefill, int S, const int64_t* i
         if (t >= max_new) done = true;
     }
     *n_tokens = n;
+    return 0;
+}
+
+int svc_ar_set_max_batch(svc_ar_t* m, int max_batch, void* stream) {
+    SVC_REQUIRE(m, "null argument");
+    SVC_REQUIRE(max_batch >= 1 && max_batch <= MAXB, "AR: max_batch must be 1 .. 64");
+    hipStream_t st = (hipStream_t)stream;
+    if (m->ensure_batch_ws(st)) return 1;
+    if (max_batch == m->max_batch) return 0;
+    SVC_CHECK_HIP(hipStreamSynchronize(st));
+    m->slot_mem.release();
+    m->slot_base.assign(1, nullptr);
+    m->max_batch = 1;
+    m->bpos_n = 0;
+    for (int b = 1; b < max_batch; ++b) {
+        float* p = m->slot_mem.alloc_n<float>((size_t)m->L * 2 * m->cache_elems(), st);
+        if (!p) {
+            m->slot_mem.release();
+            m->slot_base.assign(1, nullptr);
+            (void)m->upload_kvtab(st);
+            return 1;
+        }
+        m->slot_base.push_back(p);
+    }
+    m->max_batch = max_batch;
+    return m->upload_kvtab(st);
+}
+
+int svc_ar_prefill_slot(svc_ar_t* m, int slot, const float* x, int S, const int64_t* input_pos, const int64_t* kv_pos, float* logits_out,
+                        void* stream) {
+    SVC_REQUIRE(m && x && input_pos && kv_pos && logits_out && S >= 1, "bad argument");
+    SVC_REQUIRE(slot >= 0 && slot < m->max_batch, "AR: slot outside max_batch (svc_ar_set_max_batch)");
+    hipStream_t st = (hipStream_t)stream;
+    if (m->ensure_batch_ws(st)) return 1;
+    return m->prefill_slot(slot, x, S, input_pos, kv_pos, logits_out, st);
+}
+
+int svc_ar_decode_step_batch(svc_ar_t* m, int B, const float* x, int set_pos, const int64_t* input_pos, const int64_t* kv_pos,
+                             float* logits_out, void* stream) {
+    SVC_REQUIRE(m, "null argument");
+    SVC_REQUIRE(B >= 1 && B <= m->max_batch, "AR: batch outside 1 .. max_batch (svc_ar_set_max_batch)");
+    SVC_REQUIRE(x && logits_out, "bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    int pos[2 * MAXB];
+    if (set_pos) {
+        SVC_REQUIRE(input_pos && kv_pos, "bad argument");
+        memset(pos, 0, sizeof(pos));
+        for (int b = 0; b < B; ++b) {
+            SVC_REQUIRE(input_pos[b] >= 0 && input_pos[b] < m->Lmax && kv_pos[b] >= 0 && kv_pos[b] < m->Lmax, "position out of range");
+            pos[b] = (int)input_pos[b];
+            pos[MAXB + b] = (int)kv_pos[b];
+        }
+    } else {
+        SVC_REQUIRE(m->bpos_n == B, "AR: svc_ar_decode_step_batch needs set_pos on the first step of a batch");
+        memcpy(pos, m->h_bpos, sizeof(pos));
+        for (int b = 0; b < B; ++b) SVC_REQUIRE(pos[b] < m->Lmax && pos[MAXB + b] < m->Lmax, "position out of range");
+    }
+    if (m->ensure_batch_ws(st)) return 1;
+    if (set_pos) {
+        SVC_CHECK_HIP(hipMemcpyAsync(m->d_bpos, pos, sizeof(pos), hipMemcpyHostToDevice, st));
+        SVC_CHECK_HIP(hipStreamSynchronize(st));
+    }
+    m->bpos_n = 0;
+    const int Bp = (int)round_up(B, 16);
+    if (m->set_nb(B, st) || m->ensure_batch_graph(Bp, false)) return 1;
+    SVC_CHECK_HIP(hipMemcpyAsync(m->bh, x, (size_t)B * m->D * 4, hipMemcpyDeviceToDevice, st));
+    SVC_CHECK_HIP(hipGraphLaunch(m->bstep_graph[Bp / 16 - 1], st));
+    SVC_CHECK_HIP(hipMemcpyAsync(logits_out, m->blogits, (size_t)B * m->V * 4, hipMemcpyDeviceToDevice, st));
+    for (int b = 0; b < B; ++b) { pos[b] += 1; pos[MAXB + b] += 1; }
+    memcpy(m->h_bpos, pos, sizeof(pos));
+    m->bpos_n = B;
+    return 0;
+}
+
+// B independent svc_ar_generate loops in one: per-slot prefill and first token, then one captured batched step + sampler
+// per token for all slots; the host reads the slots' counters every `check_every` steps and stops once every slot is done.
+int svc_ar_generate_batch(svc_ar_t* m, int B, const float* x_prefill, const int32_t* S, const int64_t* input_pos, const int64_t* kv_pos,
+                          const float* exp_noise, int max_new, int min_tokens_before_eos, float temperature, float top_p,
+                          float repetition_penalty, int check_every, int32_t* tokens_out, int32_t* n_tokens, void* stream) {
+    SVC_REQUIRE(m, "null argument");
+    SVC_REQUIRE(B >= 1 && B <= m->max_batch, "AR: batch outside 1 .. max_batch (svc_ar_set_max_batch)");
+    SVC_REQUIRE(x_prefill && S && input_pos && kv_pos && exp_noise && tokens_out && n_tokens && max_new >= 1, "bad argument");
+    SVC_REQUIRE(m->emb, "svc_ar_generate_batch needs model.embeddings.weight in the state dict given to svc_ar_create");
+    long rows = 0;
+    for (int b = 0; b < B; ++b) {
+        SVC_REQUIRE(S[b] >= 1, "bad argument");
+        for (int s = 0; s < S[b]; ++s)
+            SVC_REQUIRE(input_pos[rows + s] >= 0 && input_pos[rows + s] < m->Lmax && kv_pos[rows + s] >= 0 && kv_pos[rows + s] < m->Lmax,
+                        "position out of range");
+        rows += S[b];
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int V = m->V, eos = V - 1;
+    if (check_every < 1) check_every = 16;
+    if (m->ensure_batch_ws(st)) return 1;
+    m->bpos_n = 0;
+    // per slot: prefill + first token (EOS suppressed, no previous tokens: ar.py:399-401)
+    std::vector<GenSlot> slots(B);
+    int pos[2 * MAXB] = {};
+    rows = 0;
+    for (int b = 0; b < B; ++b) {
+        const float* noise = exp_noise + (size_t)b * max_new * V;
+        int32_t* toks = tokens_out + (size_t)b * max_new;
+        if (m->prefill_slot(b, x_prefill + rows * m->D, S[b], input_pos + rows, kv_pos + rows, m->blogits + (size_t)b * V, st)) return 1;
+        if (m->sample(m->blogits + (size_t)b * V, nullptr, 0, eos, temperature, top_p, repetition_penalty, noise, toks, nullptr, nullptr, st))
+            return 1;
+        rows += S[b];
+        GenSlot& g = slots[b];
+        g.noise = noise; g.toks = toks; g.cnt = 1; g.min_before_eos = min_tokens_before_eos; g.eos = eos;
+        g.temperature = temperature; g.top_p = top_p; g.rep_pen = repetition_penalty; g.max_new = max_new;
+        const int ip = (int)input_pos[rows - 1] + 1, kp = (int)kv_pos[rows - 1] + 1;
+        g.done = max_new <= 1 || ip >= m->Lmax || kp >= m->Lmax;       // a finished slot keeps valid positions
+        pos[b] = g.done ? ip - 1 : ip;
+        pos[MAXB + b] = g.done ? kp - 1 : kp;
+    }
+    SVC_CHECK_HIP(hipMemcpyAsync(m->d_slots, slots.data(), (size_t)B * sizeof(GenSlot), hipMemcpyHostToDevice, st));
+    SVC_CHECK_HIP(hipMemcpyAsync(m->d_bpos, pos, sizeof(pos), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(ar_embed_batch_kernel, dim3(B), dim3(256), 0, st, m->emb, m->d_slots, m->bh, m->D);     // input of the first step
+    SVC_CHECK_HIP(hipGetLastError());
+    SVC_CHECK_HIP(hipStreamSynchronize(st));
+    const int Bp = (int)round_up(B, 16);
+    if (m->set_nb(B, st) || m->ensure_batch_graph(Bp, true)) return 1;
+    auto all_done = [&]() {
+        for (const GenSlot& g : slots) if (!g.done) return false;
+        return true;
+    };
+    for (int t = 1; t < max_new && !all_done();) {
+        const int t_end = std::min(max_new, t + check_every);
+        for (; t < t_end; ++t) SVC_CHECK_HIP(hipGraphLaunch(m->bgen_graph[Bp / 16 - 1], st));
+        SVC_CHECK_HIP(hipMemcpyAsync(slots.data(), m->d_slots, (size_t)B * sizeof(GenSlot), hipMemcpyDeviceToHost, st));
+        SVC_CHECK_HIP(hipStreamSynchronize(st));
+    }
+    for (int b = 0; b < B; ++b) n_tokens[b] = slots[b].cnt;
     return 0;
 }
 
