@@ -6,7 +6,7 @@
  * as void*; NULL = default stream).  The sampler, estimator and length-regulator calls do not synchronise the host in
  * steady state: HOST arrays (lengths) are copied into handle-owned pinned staging slots before the call returns, so the
  * caller may reuse them at once.  A call synchronises only when it has to grow the handle's workspace (first call, or a
- * larger batch / sequence than any before), svc_ar_generate / svc_ar_generate_batch read tokens back every `check_every`
+ * larger batch / sequence than any before), svc_ar_generate / svc_ar_generate_batch[_seeded] read tokens back every `check_every`
  * steps, and the *_create functions finish packing before they return.  The library owns only packed weights and per-model workspace.  Every function returns 0 on success and non-zero on failure with a
  * message available from svc_last_error() (the Python shim re-raises it as RuntimeError, where the
  * reference raises Python exceptions: diffusion_transformer.py:121, inference.py:137,313).
@@ -206,6 +206,18 @@ int svc_ar_generate_batch(svc_ar_t* m, int B, const float* x_prefill, const int3
                           const int64_t* kv_pos, const float* exp_noise, int max_new, int min_tokens_before_eos, float temperature,
                           float top_p, float repetition_penalty, int check_every, int32_t* tokens_out, int32_t* n_tokens,
                           void* stream);
+/* svc_ar_generate_batch with the Exp(1) draws generated inside the sampler instead of read from a tensor: seeds HOST [B],
+ * one per sequence.  The draw for vocabulary entry v at token step t (0 = the first generated token) of sequence b is
+ * q = -log(u), u = ((w >> 8) + 1) * 2^-24 in (0, 1], where w is output word v % 4 of Philox4x32-10 with key
+ * (seeds[b] & 0xffffffff, seeds[b] >> 32) and counter (v / 4, t, 0, 0): a function of (seed, t, v) alone, so the slot
+ * contract above holds unchanged, and B = 1 is the single-sequence case (slot 0).  No [B][max_new][vocab] buffer exists. */
+int svc_ar_generate_batch_seeded(svc_ar_t* m, int B, const float* x_prefill, const int32_t* S, const int64_t* input_pos,
+                                 const int64_t* kv_pos, const uint64_t* seeds, int max_new, int min_tokens_before_eos,
+                                 float temperature, float top_p, float repetition_penalty, int check_every, int32_t* tokens_out,
+                                 int32_t* n_tokens, void* stream);
+/* out device [n_steps][vocab] = exactly the draws the seeded sampler uses for `seed` at steps step0 .. step0 + n_steps - 1
+ * (handing them to svc_ar_generate_batch as exp_noise reproduces the seeded run bit for bit). */
+int svc_ar_exp_draws(svc_ar_t* m, uint64_t seed, int step0, int n_steps, float* out, void* stream);
 /* Replaces `sample(logits, previous_tokens, suppress_tokens, temperature, top_p, repetition_penalty)`
  * (modules/v2/ar.py:712-763): repetition penalty, top-p, temperature softmax, argmax(probs / q) with q = exp_noise
  * (the Exp(1) draw of multinomial_sample_one_no_sync, supplied by the caller).  suppress_token < 0 = none. */
@@ -235,6 +247,22 @@ void svc_lr_destroy(svc_lr_t* m);
 int svc_lr_forward(svc_lr_t* m, const float* x, const int64_t* tokens, const int32_t* in_lens, int B, int tin_max,
                    const int32_t* ylens, int tout_max, const float* f0, const int32_t* f0_lens, int tf0_max, float* out,
                    void* stream);
+
+/* ---------------------------------------------------------------- ragged assembly of a v2 batch
+ * Both write every element of `out`, padding included; lengths are HOST int32 [B] and are consumed before the call
+ * returns (they travel as kernel arguments: no copy to wait for, no synchronisation).
+ *
+ * Replaces `cat_condition = torch.cat([prompt_condition, cond], dim=1)` (modules/v2/vc_wrapper.py:657-660) for B
+ * utterances of different lengths: out[b] = cat(prompt_cond[b][:prompt_lens[b]], cond[b][:cond_lens[b]]), rows at and
+ * above prompt_lens[b] + cond_lens[b] zero.  prompt_cond [B][Pmax][Dc], cond [B][Smax][Dc], out [B][T][Dc];
+ * prompt_lens[b] + cond_lens[b] <= T. */
+int svc_v2_assemble_cond(const float* prompt_cond, const int32_t* prompt_lens, const float* cond, const int32_t* cond_lens, int B,
+                         int Pmax, int Smax, int Dc, int T, float* out, void* stream);
+/* Replaces `vc_mel[:, :, prompt_len:original_len]` (modules/v2/vc_wrapper.py:700) for a ragged batch: mel [B][C][T],
+ * out [B][C][Smax]; out[b][c][s] = mel[b][c][prompt_lens[b] + s] for s < x_lens[b] - prompt_lens[b], else pad_value.
+ * x_lens[b] <= T and x_lens[b] - prompt_lens[b] <= Smax. */
+int svc_mel_strip_prompt(const float* mel, const int32_t* prompt_lens, const int32_t* x_lens, int B, int C, int T, int Smax,
+                         float pad_value, float* out, void* stream);
 
 /* Replaces the reference's only native seam: anti_alias_activation_cuda.forward(inputs, up_ftr,
  * down_ftr, alpha, beta) (modules/bigvgan/alias_free_activation/cuda/anti_alias_activation.cpp:19-23,

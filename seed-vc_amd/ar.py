@@ -4,7 +4,9 @@
 last token's logits; `decode_step` is the hipGraph-captured one-token step (the reference's `compiled_decode_fn`);
 `sample(...)` mirrors `sample()/logits_to_probs()` with the Exp(1) noise drawn here unless supplied.
 `setup_caches(max_batch_size=B)` gives the handle B slots (one KV cache each); `generate_batch`, `prefill_slot` and
-`decode_step_batch` run up to 64 sequences per decode step on them.
+`decode_step_batch` run up to 64 sequences per decode step on them.  Without `exp_noise`, `generate` / `generate_batch`
+draw inside the sampler kernel from one 64-bit seed per sequence (`seed=` / `seeds=`, or fresh ones from torch's CPU
+generator): no noise tensor is allocated; `exp_draws` returns the draws a seed stands for.
 """
 import ctypes as C
 
@@ -82,11 +84,17 @@ class ARModel:
 
     @torch.inference_mode()
     def generate(self, prompt_text, prompt_target, compiled_decode_fn=None, top_p=0.7, temperature=0.7,
-                 repetition_penalty=1.5, exp_noise=None, max_new=4001, check_every=16):
+                 repetition_penalty=1.5, exp_noise=None, max_new=4001, check_every=16, seed=None):
         """`NaiveWrapper.generate` (modules/v2/ar.py:382-422): prompt_text (1, Tt, dim) condition embeddings,
         prompt_target (1, Tp) tokens -> (1, n) generated tokens.  The token loop runs on the device
-        (`svc_ar_generate`); exp_noise (max_new, vocab) pins the Exp(1) draws (drawn here when None).
+        (`svc_ar_generate`); exp_noise (max_new, vocab) pins the Exp(1) draws.  Without it the draws come from `seed`
+        (a fresh one from torch's CPU generator when None) inside the sampler: `generate_batch` with one sequence.
         compiled_decode_fn is accepted and ignored: the captured hipGraph step is always used."""
+        if exp_noise is None:
+            return self.generate_batch([prompt_text], [prompt_target], seeds=None if seed is None else [seed], top_p=top_p,
+                                       temperature=temperature, repetition_penalty=repetition_penalty, max_new=max_new,
+                                       check_every=check_every)[0]
+        assert seed is None, "give exp_noise or seed, not both"
         V, D = self.cfg["vocab_size"], self.cfg["dim"]
         with torch.cuda.device(self.device):
             text = _lib.f32c(prompt_text, self.device)
@@ -98,8 +106,6 @@ class ARModel:
             input_pos = list(range(text.size(1) + 1)) + [0] + [i + 1 for i in range(tgt_emb.size(1))]
             kv_pos = list(range(S))
             max_new = min(int(max_new), self.cfg["max_seq_len"] - S + 1)
-            if exp_noise is None:
-                exp_noise = torch.empty(max_new, V, device=self.device).exponential_(1)
             q = _lib.f32c(exp_noise, self.device)
             assert q.shape[0] >= max_new and q.shape[1] == V
             toks = torch.zeros(max_new, device=self.device, dtype=torch.int32)
@@ -139,15 +145,38 @@ class ARModel:
         return out
 
     @torch.inference_mode()
+    def exp_draws(self, seed, step0, n):
+        """(n, vocab) device tensor: the Exp(1) draws the seeded sampler uses for `seed` at token steps step0 .. step0 + n - 1
+        (`svc_ar_exp_draws`).  Given back as `exp_noise`, they reproduce the seeded run bit for bit."""
+        with torch.cuda.device(self.device):
+            out = torch.empty(int(n), self.cfg["vocab_size"], device=self.device)
+            _lib.check(_lib.lib().svc_ar_exp_draws(self._h, C.c_uint64(int(seed) & (2 ** 64 - 1)), int(step0), int(n), _lib.ptr(out),
+                                                   _lib.stream_ptr()))
+        return out
+
+    @torch.inference_mode()
     def generate_batch(self, prompt_texts, prompt_targets, exp_noise=None, top_p=0.7, temperature=0.7, repetition_penalty=1.5,
-                       max_new=4001, check_every=16):
+                       max_new=4001, check_every=16, seeds=None):
         """`generate` for B sequences at once (`svc_ar_generate_batch`; B <= the max_batch_size given to setup_caches):
         lists of B prompt_text (1, Tt_b, dim) and prompt_target (1, Tp_b) tensors, exp_noise a list of B (>= n_b, vocab)
-        tensors of Exp(1) draws (drawn here when None) -> list of B (1, n_b) token tensors, each what `generate` gives
-        for that sequence alone."""
+        tensors of Exp(1) draws -> list of B (1, n_b) token tensors, each what `generate` gives for that sequence alone.
+        Without exp_noise the sampler generates the draws from `seeds` (B integers; fresh ones from torch's CPU generator
+        when None, so `torch.manual_seed` governs them) and no noise tensor exists (`svc_ar_generate_batch_seeded`)."""
+        toks, n = self.generate_batch_raw(prompt_texts, prompt_targets, exp_noise, top_p, temperature, repetition_penalty, max_new,
+                                          check_every, seeds)
+        return [toks[b, :n[b]].long()[None, :] for b in range(len(n))]
+
+    @torch.inference_mode()
+    def generate_batch_raw(self, prompt_texts, prompt_targets, exp_noise=None, top_p=0.7, temperature=0.7, repetition_penalty=1.5,
+                           max_new=4001, check_every=16, seeds=None):
+        """`generate_batch` without the per-sequence slicing: (tokens (B, max_new) int32 on the device, list of B counts);
+        row b holds its sequence's tokens in [:n_b]."""
         V, D, Lmax = self.cfg["vocab_size"], self.cfg["dim"], self.cfg["max_seq_len"]
         B = len(prompt_texts)
-        assert B == len(prompt_targets) and (exp_noise is None or len(exp_noise) == B)
+        if B != len(prompt_targets) or (exp_noise is not None and len(exp_noise) != B) or (seeds is not None and len(seeds) != B):
+            raise ValueError("generate_batch: prompt_texts, prompt_targets and exp_noise / seeds must have one entry per sequence")
+        if exp_noise is not None and seeds is not None:
+            raise ValueError("generate_batch: give exp_noise or seeds, not both")
         with torch.cuda.device(self.device):
             sep = self._sep.reshape(1, D)
             rows, S, input_pos, kv_pos = [], [], [], []
@@ -161,21 +190,27 @@ class ARModel:
             emb_seq = torch.cat(rows, dim=0).contiguous()
             cap = [min(int(max_new), Lmax - s + 1) for s in S]      # what `generate` allows each sequence
             max_new = max(cap)
-            if exp_noise is None:
-                q = torch.empty(B, max_new, V, device=self.device).exponential_(1)
-            else:
-                q = torch.ones(B, max_new, V, device=self.device)
-                for b, e in enumerate(exp_noise):
-                    assert e.shape[0] >= cap[b] and e.shape[1] == V
-                    n = min(e.shape[0], max_new)
-                    q[b, :n] = _lib.f32c(e, self.device)[:n]
             toks = torch.zeros(B, max_new, device=self.device, dtype=torch.int32)
             n = (C.c_int32 * B)()
-            _lib.check(_lib.lib().svc_ar_generate_batch(self._h, B, _lib.ptr(emb_seq), (C.c_int32 * B)(*S), _lib.i64_host(input_pos),
-                                                        _lib.i64_host(kv_pos), _lib.ptr(q), max_new, 10, C.c_float(temperature),
-                                                        C.c_float(top_p), C.c_float(repetition_penalty), int(check_every),
-                                                        _lib.ptr(toks), n, _lib.stream_ptr()))
-        return [toks[b, :n[b]].long()[None, :] for b in range(B)]
+            tail = (max_new, 10, C.c_float(temperature), C.c_float(top_p), C.c_float(repetition_penalty), int(check_every),
+                    _lib.ptr(toks), n, _lib.stream_ptr())
+            head = (self._h, B, _lib.ptr(emb_seq), (C.c_int32 * B)(*S), _lib.i64_host(input_pos), _lib.i64_host(kv_pos))
+            if exp_noise is None:
+                if seeds is None:
+                    seeds = torch.randint(0, 2 ** 62, (B,), dtype=torch.int64).tolist()
+                sd = (C.c_uint64 * B)(*[int(v) & (2 ** 64 - 1) for v in seeds])
+                _lib.check(_lib.lib().svc_ar_generate_batch_seeded(*head, sd, *tail))
+            else:
+                if torch.is_tensor(exp_noise) and tuple(exp_noise.shape) == (B, max_new, V):
+                    q = _lib.f32c(exp_noise, self.device)       # already in the call's layout: used as it is
+                else:
+                    q = torch.ones(B, max_new, V, device=self.device)
+                    for b, e in enumerate(exp_noise):
+                        assert e.shape[0] >= cap[b] and e.shape[1] == V
+                        k = min(e.shape[0], max_new)
+                        q[b, :k] = _lib.f32c(e, self.device)[:k]
+                _lib.check(_lib.lib().svc_ar_generate_batch(*head, _lib.ptr(q), *tail))
+        return toks, list(n)
 
     def close(self):
         if self._h:

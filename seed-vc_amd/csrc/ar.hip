@@ -35,7 +35,8 @@ namespace {
 // Device-resident state of the generate loop: the captured per-token graph (decode step -> rank -> sample, which also
 // embeds the drawn token and advances the positions) reads everything that changes from token to token from here, so one graph replay per token needs no host argument.
 struct GenState {
-    const float* noise;      // [max_new][V] Exp(1) draws, row t for token t
+    const float* noise;      // [max_new][V] Exp(1) draws, row t for token t; null = draw them from `seed` (ar_exp_draw4)
+    unsigned long long seed;
     int* toks;               // [max_new] generated tokens
     int cnt;                 // index of the token being generated (>= 1 inside the loop)
     int min_before_eos, eos;
@@ -761,6 +762,52 @@ __global__ void ar_embed_kernel(const float* __restrict__ emb, const GenState* _
 
 // ---- sampler: one block, vocab <= 4096.  reference: ar.py:731-763 + :723-727
 constexpr int SORT_N = 4096;
+
+// Seeded Exp(1) draws: Philox4x32-10 (Salmon et al., SC'11), key = (seed low word, seed high word), counter =
+// (v / 4, token step, 0, 0); output word j of the call is the draw of vocabulary entry 4 (v / 4) + j.  A draw is a pure
+// function of (seed, step, v): nothing about the slot, the batch or the other sequences enters it.
+// u = ((word >> 8) + 1) * 2^-24 lies in (0, 1] and is exact in fp32, so q = -log(u) is finite (<= 16.64) and >= 0.
+__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
+                                              unsigned (&out)[4]) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0; c1 = lo1;
+        c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+__device__ __forceinline__ void ar_exp_draw4(unsigned long long seed, int step, int v4, float (&q)[4]) {
+    unsigned w[4];
+    philox4x32_10((unsigned)v4, (unsigned)step, 0u, 0u, (unsigned)seed, (unsigned)(seed >> 32), w);
+    // q = -log(k 2^-24) = n ln2 - log(m), k = m 2^(24 - n), m in [1, 2): log(m) <= 0.7 carries an absolute error of ~1e-7
+    // and n ln2 is a two-term product whose high part is exact (n <= 24, ln2_hi has 15 significant bits), so the error of
+    // q is half an fp32 ulp of q plus ~1.5e-7 -- exp(-q) reproduces u to < 1e-6 relative over the whole range (logf on u
+    // itself is 2 ulp of q off: 2e-6 at q = 8 .. 16.6).
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const unsigned k = (w[j] >> 8) + 1u;
+        const int e = 31 - __clz((int)k);
+        const float m = ldexpf((float)k, -e), n = (float)(24 - e);
+        // explicit fmaf: the sampler and svc_ar_exp_draws must round alike.  fmaxf: log(m) may overshoot ln2 by an ulp when
+        // m is just below 2 (n = 1)
+        q[j] = fmaxf(fmaf(n, 0.693145751953125f, fmaf(n, 1.42860682030941723212e-6f, -logf(m))), 0.f);
+    }
+}
+
+// out[s][v] = the draw of (seed, step0 + s, v): what the seeded sampler uses, for svc_ar_exp_draws
+__global__ __launch_bounds__(256) void ar_exp_draws_kernel(unsigned long long seed, int step0, int V, float* __restrict__ out) {
+    const int v4 = blockIdx.x * 256 + threadIdx.x, s = blockIdx.y;
+    if (4 * v4 >= V) return;
+    float q[4];
+    ar_exp_draw4(seed, step0 + s, v4, q);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (4 * v4 + j < V) out[(size_t)s * V + 4 * v4 + j] = q[j];
+}
+
 // Sampler stage 1 (many workgroups): repetition penalty + suppression, then the RANK of every logit in the descending
 // order torch.sort gives (ties: lower index first) by counting -- workgroup b ranks tokens 16 b .. 16 b + 15, 16 lanes per
 // token, each lane counting over a 1/16 stride of the vocabulary held in LDS.  Writes the sorted (value, index) pairs and
@@ -812,7 +859,8 @@ __global__ __launch_bounds__(256) void ar_rank_kernel(const float* __restrict__ 
 // Returns the drawn token (the same value in every thread).
 __device__ __forceinline__ int ar_sample_body(const float* __restrict__ lgp, int V, const float* __restrict__ skey,
                                               const int* __restrict__ sidx, float temperature, float top_p,
-                                              const float* __restrict__ exp_noise, float* __restrict__ probs_out) {
+                                              const float* __restrict__ exp_noise, unsigned long long seed, int step,
+                                              float* __restrict__ probs_out) {
     __shared__ float key[SORT_N];
     __shared__ int idx[SORT_N];
     __shared__ float lg[SORT_N];       // penalised logits in vocabulary order, later reused
@@ -823,6 +871,10 @@ __device__ __forceinline__ int ar_sample_body(const float* __restrict__ lgp, int
     __shared__ int r_idx[16];
     __shared__ double r_scan[16];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // seeded draws: thread t owns vocabulary entries 4t .. 4t+3 (one Philox call; SORT_N = 4 x 1024).  Pure integer VALU
+    // work issued before the first load is waited for, so it hides under the memory latency of the prologue.
+    float q4[4] = {1.f, 1.f, 1.f, 1.f};
+    if (!exp_noise && 4 * tid < V) ar_exp_draw4(seed, step, tid, q4);
     auto wave_max_f = [](float v) {
         v = fmaxf(v, dpp_f<DPP_XOR1>(v)); v = fmaxf(v, dpp_f<DPP_XOR2>(v));
         v = fmaxf(v, dpp_f<DPP_HALF_MIRROR>(v)); v = fmaxf(v, dpp_f<DPP_ROW_MIRROR>(v));
@@ -890,11 +942,26 @@ __device__ __forceinline__ int ar_sample_body(const float* __restrict__ lgp, int
     // exponential race: argmax probs / q (ties: the lower index)
     float best = -1.f;
     int besti = 0;
-    for (int i = tid; i < V; i += 1024) {
-        const float p = key[i] * inv;
-        if (probs_out) probs_out[i] = p;
-        const float r = p / exp_noise[i];
-        if (r > best) { best = r; besti = i; }
+    if (exp_noise) {
+        for (int i = tid; i < V; i += 1024) {
+            const float p = key[i] * inv;
+            if (probs_out) probs_out[i] = p;
+            const float r = p / exp_noise[i];
+            if (r > best) { best = r; besti = i; }
+        }
+    } else {
+        // the same race over this thread's own four entries: the maximum (ties: the lower index) does not depend on
+        // how the entries are spread over the threads
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int i = 4 * tid + j;
+            if (i < V) {
+                const float p = key[i] * inv;
+                if (probs_out) probs_out[i] = p;
+                const float r = p / q4[j];
+                if (r > best) { best = r; besti = i; }
+            }
+        }
     }
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
@@ -918,18 +985,20 @@ __device__ __forceinline__ int ar_sample_body(const float* __restrict__ lgp, int
 
 __global__ __launch_bounds__(1024) void ar_sample_kernel(const float* __restrict__ lgp, int V, const float* __restrict__ skey,
                                                          const int* __restrict__ sidx, float temperature, float top_p,
-                                                         const float* __restrict__ exp_noise, int* __restrict__ idx_out,
+                                                         const float* __restrict__ exp_noise, unsigned long long seed,
+                                                         int step, int* __restrict__ idx_out,
                                                          float* __restrict__ probs_out, GenState* __restrict__ gs,
                                                          const float* __restrict__ emb, float* __restrict__ next_x, int D,
                                                          int* __restrict__ pos) {
     if (gs) {
         const int t = gs->cnt;
         temperature = gs->temperature; top_p = gs->top_p;
-        exp_noise = gs->noise + (size_t)t * V;
+        exp_noise = gs->noise ? gs->noise + (size_t)t * V : nullptr;
+        seed = gs->seed; step = t;
         idx_out = gs->toks + t;
     }
     const int tid = threadIdx.x;
-    const int win = ar_sample_body(lgp, V, skey, sidx, temperature, top_p, exp_noise, probs_out);
+    const int win = ar_sample_body(lgp, V, skey, sidx, temperature, top_p, exp_noise, seed, step, probs_out);
     if (tid == 0) idx_out[0] = win;
     if (gs && next_x) {
         // generate loop: this workgroup also prepares the next step -- embedding row of the token just drawn into the
@@ -1327,9 +1396,9 @@ __global__ __launch_bounds__(1024) void ar_sample_batch_kernel(const float* __re
     GenSlot* gs = slots + b;
     const int tid = threadIdx.x;
     const int t = gs->cnt, was_done = gs->done;         // read by every thread before thread 0 changes them (barriers in the body)
-    const int row = t < gs->max_new ? t : gs->max_new - 1;      // a slot finished by max_new has no noise row t
+    const int row = t < gs->max_new ? t : gs->max_new - 1;      // a slot finished by max_new has no noise row t (seeded: step)
     const int win = ar_sample_body(lgp + (long)b * SORT_N, V, skey + (long)b * SORT_N, sidx + (long)b * SORT_N, gs->temperature,
-                                   gs->top_p, gs->noise + (size_t)row * V, nullptr);
+                                   gs->top_p, gs->noise ? gs->noise + (size_t)row * V : nullptr, gs->seed, row, nullptr);
     const bool record = !was_done && win != gs->eos;
     const long tk = record ? win : gs->toks[t - 1];     // a finished slot keeps its last input
     for (int c = tid; c < D; c += 1024) next_x[(long)b * D + c] = emb[tk * D + c];
@@ -1371,7 +1440,8 @@ struct svc_ar {
     float *d_skey = nullptr, *d_lgp = nullptr;   // sampler stage 1 -> stage 2
     int* d_sidx = nullptr;
     int sample(const float* lg, const int* prev, int n_prev, int suppress, float temperature, float top_p, float rep_pen,
-               const float* exp_noise, int* idx_out, float* probs_out, GenState* gs, hipStream_t st, bool prepare_next = false);
+               const float* exp_noise, int* idx_out, float* probs_out, GenState* gs, hipStream_t st, bool prepare_next = false,
+               unsigned long long seed = 0, int step = 0);      // exp_noise null (and gs null): the draws of (seed, step)
     // decode graph
     hipGraphExec_t graph = nullptr;
     hipGraphExec_t gen_graph = nullptr;   // step -> rank -> sample (+ next embedding, advance), driven by d_gen
@@ -1595,10 +1665,11 @@ int svc_ar::ensure_graph() {
 }
 
 int svc_ar::sample(const float* lg, const int* prev, int n_prev, int suppress, float temperature, float top_p, float rep_pen,
-                   const float* exp_noise, int* idx_out, float* probs_out, GenState* gs, hipStream_t st, bool prepare_next) {
+                   const float* exp_noise, int* idx_out, float* probs_out, GenState* gs, hipStream_t st, bool prepare_next,
+                   unsigned long long seed, int step) {
     hipLaunchKernelGGL(ar_rank_kernel, dim3(cdiv(V, 16)), dim3(256), 0, st, lg, V, prev, n_prev, suppress, rep_pen, gs, d_skey, d_sidx, d_lgp);
-    hipLaunchKernelGGL(ar_sample_kernel, dim3(1), dim3(1024), 0, st, d_lgp, V, d_skey, d_sidx, temperature, top_p, exp_noise, idx_out,
-                       probs_out, gs, prepare_next ? emb : nullptr, prepare_next ? h32 : nullptr, D, d_pos);
+    hipLaunchKernelGGL(ar_sample_kernel, dim3(1), dim3(1024), 0, st, d_lgp, V, d_skey, d_sidx, temperature, top_p, exp_noise, seed, step,
+                       idx_out, probs_out, gs, prepare_next ? emb : nullptr, prepare_next ? h32 : nullptr, D, d_pos);
     SVC_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -1940,7 +2011,7 @@ int svc_ar_generate(svc_ar_t* m, const float* x_prefill, int S, const int64_t* i
     const int pos[2] = {(int)input_pos[S - 1] + 1, (int)kv_pos[S - 1] + 1};
     SVC_CHECK_HIP(hipMemcpyAsync(m->d_pos, pos, 8, hipMemcpyHostToDevice, st));
     GenState gs;
-    gs.noise = exp_noise; gs.toks = tokens_out; gs.cnt = 1; gs.min_before_eos = min_tokens_before_eos; gs.eos = eos;
+    gs.noise = exp_noise; gs.seed = 0; gs.toks = tokens_out; gs.cnt = 1; gs.min_before_eos = min_tokens_before_eos; gs.eos = eos;
     gs.temperature = temperature; gs.top_p = top_p; gs.rep_pen = repetition_penalty;
     SVC_CHECK_HIP(hipMemcpyAsync(m->d_gen, &gs, sizeof(gs), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(ar_embed_kernel, dim3(1), dim3(256), 0, st, m->emb, m->d_gen, m->h32, m->D);   // input of the first step
@@ -2044,12 +2115,13 @@ int svc_ar_decode_step_batch(svc_ar_t* m, int B, const float* x, int set_pos, co
 
 // B independent svc_ar_generate loops in one: per-slot prefill and first token, then one captured batched step + sampler
 // per token for all slots; the host reads the slots' counters every `check_every` steps and stops once every slot is done.
-int svc_ar_generate_batch(svc_ar_t* m, int B, const float* x_prefill, const int32_t* S, const int64_t* input_pos, const int64_t* kv_pos,
-                          const float* exp_noise, int max_new, int min_tokens_before_eos, float temperature, float top_p,
-                          float repetition_penalty, int check_every, int32_t* tokens_out, int32_t* n_tokens, void* stream) {
+// Draws: exp_noise [B][max_new][V], or (exp_noise null) generated in the sampler from seeds HOST [B].
+static int ar_generate_batch(svc_ar_t* m, int B, const float* x_prefill, const int32_t* S, const int64_t* input_pos, const int64_t* kv_pos,
+                             const float* exp_noise, const uint64_t* seeds, int max_new, int min_tokens_before_eos, float temperature,
+                             float top_p, float repetition_penalty, int check_every, int32_t* tokens_out, int32_t* n_tokens, void* stream) {
     SVC_REQUIRE(m, "null argument");
     SVC_REQUIRE(B >= 1 && B <= m->max_batch, "AR: batch outside 1 .. max_batch (svc_ar_set_max_batch)");
-    SVC_REQUIRE(x_prefill && S && input_pos && kv_pos && exp_noise && tokens_out && n_tokens && max_new >= 1, "bad argument");
+    SVC_REQUIRE(x_prefill && S && input_pos && kv_pos && (exp_noise || seeds) && tokens_out && n_tokens && max_new >= 1, "bad argument");
     SVC_REQUIRE(m->emb, "svc_ar_generate_batch needs model.embeddings.weight in the state dict given to svc_ar_create");
     long rows = 0;
     for (int b = 0; b < B; ++b) {
@@ -2069,14 +2141,16 @@ int svc_ar_generate_batch(svc_ar_t* m, int B, const float* x_prefill, const int3
     int pos[2 * MAXB] = {};
     rows = 0;
     for (int b = 0; b < B; ++b) {
-        const float* noise = exp_noise + (size_t)b * max_new * V;
+        const float* noise = exp_noise ? exp_noise + (size_t)b * max_new * V : nullptr;
+        const unsigned long long seed = exp_noise ? 0ull : (unsigned long long)seeds[b];
         int32_t* toks = tokens_out + (size_t)b * max_new;
         if (m->prefill_slot(b, x_prefill + rows * m->D, S[b], input_pos + rows, kv_pos + rows, m->blogits + (size_t)b * V, st)) return 1;
-        if (m->sample(m->blogits + (size_t)b * V, nullptr, 0, eos, temperature, top_p, repetition_penalty, noise, toks, nullptr, nullptr, st))
+        if (m->sample(m->blogits + (size_t)b * V, nullptr, 0, eos, temperature, top_p, repetition_penalty, noise, toks, nullptr, nullptr, st,
+                      false, seed, 0))
             return 1;
         rows += S[b];
         GenSlot& g = slots[b];
-        g.noise = noise; g.toks = toks; g.cnt = 1; g.min_before_eos = min_tokens_before_eos; g.eos = eos;
+        g.noise = noise; g.seed = seed; g.toks = toks; g.cnt = 1; g.min_before_eos = min_tokens_before_eos; g.eos = eos;
         g.temperature = temperature; g.top_p = top_p; g.rep_pen = repetition_penalty; g.max_new = max_new;
         const int ip = (int)input_pos[rows - 1] + 1, kp = (int)kv_pos[rows - 1] + 1;
         g.done = max_new <= 1 || ip >= m->Lmax || kp >= m->Lmax;       // a finished slot keeps valid positions
@@ -2101,6 +2175,31 @@ int svc_ar_generate_batch(svc_ar_t* m, int B, const float* x_prefill, const int3
         SVC_CHECK_HIP(hipStreamSynchronize(st));
     }
     for (int b = 0; b < B; ++b) n_tokens[b] = slots[b].cnt;
+    return 0;
+}
+
+int svc_ar_generate_batch(svc_ar_t* m, int B, const float* x_prefill, const int32_t* S, const int64_t* input_pos, const int64_t* kv_pos,
+                          const float* exp_noise, int max_new, int min_tokens_before_eos, float temperature, float top_p,
+                          float repetition_penalty, int check_every, int32_t* tokens_out, int32_t* n_tokens, void* stream) {
+    SVC_REQUIRE(exp_noise, "bad argument");
+    return ar_generate_batch(m, B, x_prefill, S, input_pos, kv_pos, exp_noise, nullptr, max_new, min_tokens_before_eos, temperature, top_p,
+                             repetition_penalty, check_every, tokens_out, n_tokens, stream);
+}
+
+int svc_ar_generate_batch_seeded(svc_ar_t* m, int B, const float* x_prefill, const int32_t* S, const int64_t* input_pos,
+                                 const int64_t* kv_pos, const uint64_t* seeds, int max_new, int min_tokens_before_eos, float temperature,
+                                 float top_p, float repetition_penalty, int check_every, int32_t* tokens_out, int32_t* n_tokens,
+                                 void* stream) {
+    SVC_REQUIRE(seeds, "bad argument");
+    return ar_generate_batch(m, B, x_prefill, S, input_pos, kv_pos, nullptr, seeds, max_new, min_tokens_before_eos, temperature, top_p,
+                             repetition_penalty, check_every, tokens_out, n_tokens, stream);
+}
+
+int svc_ar_exp_draws(svc_ar_t* m, uint64_t seed, int step0, int n_steps, float* out, void* stream) {
+    SVC_REQUIRE(m && out && step0 >= 0 && n_steps >= 1 && n_steps <= 65535, "bad argument");
+    hipLaunchKernelGGL(ar_exp_draws_kernel, dim3(cdiv(cdiv(m->V, 4), 256), n_steps), dim3(256), 0, (hipStream_t)stream,
+                       (unsigned long long)seed, step0, m->V, out);
+    SVC_CHECK_HIP(hipGetLastError());
     return 0;
 }
 

@@ -1,7 +1,9 @@
 // C ABI glue that is not tied to one model: error reporting, the anti-aliased activation seam and the
 // op-level entry points used by the parity tests (tests/test_gpu_ops.py).
+#include <stdint.h>
 #include <string.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "model_util.h"
@@ -268,6 +270,113 @@ int svc_crossfade(float* chunk2, const float* chunk1_tail, const double* fade_in
     SVC_REQUIRE(chunk2 && chunk1_tail && fade_in && fade_out, "null argument");
     hipLaunchKernelGGL(crossfade_kernel, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, chunk2, chunk1_tail, fade_in, fade_out, n);
     SVC_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+}  // extern "C"
+
+// ---- ragged assembly of a v2 batch (modules/v2/vc_wrapper.py:657-660, :700).  Pure copies: one thread per 16 bytes of
+// output along the contiguous axis where the shape allows it, coalesced 4-byte accesses otherwise; every output element
+// is written, padding included.  Lengths travel as kernel arguments (up to RAG_MAXB utterances per launch), so no host
+// array outlives the call and nothing synchronises.
+namespace {
+constexpr int RAG_MAXB = 64;
+struct RagLens { int a[RAG_MAXB], b[RAG_MAXB]; };
+
+// out[b][t][:] = t < P_b ? prompt_cond[b][t] : t < P_b + S_b ? cond[b][t - P_b] : 0.  VT = float4v (Dc % 4 == 0) or float.
+template <class VT>
+__global__ __launch_bounds__(256) void v2_assemble_cond_kernel(const VT* __restrict__ prompt_cond, const VT* __restrict__ cond,
+                                                               const RagLens lens, int Pmax, int Smax, int Dv, int T,
+                                                               VT* __restrict__ out) {
+    const int b = blockIdx.y;
+    const int P = lens.a[b], S = lens.b[b];
+    const long n = (long)T * Dv;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const int t = (int)(i / Dv), c = (int)(i - (long)t * Dv);
+        VT v = {};
+        if (t < P) v = prompt_cond[((long)b * Pmax + t) * Dv + c];
+        else if (t < P + S) v = cond[((long)b * Smax + (t - P)) * Dv + c];
+        out[(long)b * n + i] = v;
+    }
+}
+
+// out[b][c][s] = s < x_lens[b] - P_b ? mel[b][c][P_b + s] : pad.  P_b shifts the source by an arbitrary number of floats:
+// 4-byte loads (consecutive lanes read consecutive addresses), one 16-byte store per thread when VEC (Smax % 4 == 0).
+template <bool VEC>
+__global__ __launch_bounds__(256) void mel_strip_prompt_kernel(const float* __restrict__ mel, const RagLens lens, int C, int T,
+                                                               int Smax, float pad, float* __restrict__ out) {
+    constexpr int W = VEC ? 4 : 1;
+    const int b = blockIdx.y;
+    const int P = lens.a[b], n_valid = lens.b[b] - P;
+    const int Sv = Smax / W;
+    const long n = (long)C * Sv;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const int c = (int)(i / Sv), s0 = (int)(i - (long)c * Sv) * W;
+        const float* src = mel + ((long)b * C + c) * T + P + s0;
+        float v[W];
+#pragma unroll
+        for (int j = 0; j < W; ++j) v[j] = s0 + j < n_valid ? src[j] : pad;
+        float* dst = out + ((long)b * C + c) * Smax + s0;
+        if constexpr (VEC) *reinterpret_cast<float4v*>(dst) = (float4v){v[0], v[1], v[2], v[3]};
+        else dst[0] = v[0];
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int svc_v2_assemble_cond(const float* prompt_cond, const int32_t* prompt_lens, const float* cond, const int32_t* cond_lens, int B,
+                         int Pmax, int Smax, int Dc, int T, float* out, void* stream) {
+    SVC_REQUIRE(B >= 0 && Pmax >= 0 && Smax >= 0 && Dc >= 1 && T >= 0, "bad argument");
+    if (B == 0 || T == 0) return 0;
+    SVC_REQUIRE(out && prompt_lens && cond_lens && (prompt_cond || Pmax == 0) && (cond || Smax == 0), "null argument");
+    for (int b = 0; b < B; ++b)
+        SVC_REQUIRE(prompt_lens[b] >= 0 && prompt_lens[b] <= Pmax && cond_lens[b] >= 0 && cond_lens[b] <= Smax &&
+                        (long)prompt_lens[b] + cond_lens[b] <= T,
+                    "assemble_cond: lengths outside 0 .. Pmax / 0 .. Smax, or prompt + cond frames above T");
+    const bool vec = Dc % 4 == 0 && (((uintptr_t)prompt_cond | (uintptr_t)cond | (uintptr_t)out) & 15) == 0;
+    const int Dv = vec ? Dc / 4 : Dc;
+    const int gx = (int)std::min<long>(cdiv((long)T * Dv, 256), 4096);
+    for (int b0 = 0; b0 < B; b0 += RAG_MAXB) {
+        const int nb = std::min(B - b0, RAG_MAXB);
+        RagLens l;
+        memset(&l, 0, sizeof(l));
+        for (int b = 0; b < nb; ++b) { l.a[b] = prompt_lens[b0 + b]; l.b[b] = cond_lens[b0 + b]; }
+        const float* pc = prompt_cond + (long)b0 * Pmax * Dc;
+        const float* cd = cond + (long)b0 * Smax * Dc;
+        float* o = out + (long)b0 * T * Dc;
+        if (vec)
+            hipLaunchKernelGGL(v2_assemble_cond_kernel<float4v>, dim3(gx, nb), dim3(256), 0, (hipStream_t)stream,
+                               reinterpret_cast<const float4v*>(pc), reinterpret_cast<const float4v*>(cd), l, Pmax, Smax, Dv, T,
+                               reinterpret_cast<float4v*>(o));
+        else
+            hipLaunchKernelGGL(v2_assemble_cond_kernel<float>, dim3(gx, nb), dim3(256), 0, (hipStream_t)stream, pc, cd, l, Pmax, Smax, Dv, T, o);
+        SVC_CHECK_HIP(hipGetLastError());
+    }
+    return 0;
+}
+
+int svc_mel_strip_prompt(const float* mel, const int32_t* prompt_lens, const int32_t* x_lens, int B, int C, int T, int Smax,
+                         float pad_value, float* out, void* stream) {
+    SVC_REQUIRE(B >= 0 && C >= 0 && T >= 0 && Smax >= 0, "bad argument");
+    if (B == 0 || C == 0 || Smax == 0) return 0;
+    SVC_REQUIRE(out && prompt_lens && x_lens && (mel || T == 0), "null argument");
+    for (int b = 0; b < B; ++b)
+        SVC_REQUIRE(prompt_lens[b] >= 0 && x_lens[b] >= 0 && x_lens[b] <= T && x_lens[b] - prompt_lens[b] <= Smax,
+                    "strip_prompt: x_lens outside 0 .. T, or more than Smax frames after the prompt");
+    const bool vec = Smax % 4 == 0 && ((uintptr_t)out & 15) == 0;
+    const int gx = (int)std::min<long>(cdiv((long)C * (vec ? Smax / 4 : Smax), 256), 4096);
+    for (int b0 = 0; b0 < B; b0 += RAG_MAXB) {
+        const int nb = std::min(B - b0, RAG_MAXB);
+        RagLens l;
+        memset(&l, 0, sizeof(l));
+        for (int b = 0; b < nb; ++b) { l.a[b] = prompt_lens[b0 + b]; l.b[b] = x_lens[b0 + b]; }
+        const float* src = mel + (long)b0 * C * T;
+        float* o = out + (long)b0 * C * Smax;
+        if (vec) hipLaunchKernelGGL(mel_strip_prompt_kernel<true>, dim3(gx, nb), dim3(256), 0, (hipStream_t)stream, src, l, C, T, Smax, pad_value, o);
+        else hipLaunchKernelGGL(mel_strip_prompt_kernel<false>, dim3(gx, nb), dim3(256), 0, (hipStream_t)stream, src, l, C, T, Smax, pad_value, o);
+        SVC_CHECK_HIP(hipGetLastError());
+    }
     return 0;
 }
 

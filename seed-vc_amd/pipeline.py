@@ -155,6 +155,164 @@ class HotPath:
         return out[None, :]
 
 
+# ----------------------------------------------------------------------------------------- v2: tokens in, audio out
+def v2_target_frames(frames_per_token, n_tokens):
+    """Mel frames the CFM length regulator is asked for after the AR model produced `n_tokens` tokens.  The reference
+    computes `int(source_mel_len / source_content_len * ar_out.size(1) * length_adjust)` in Python floats
+    (modules/v2/vc_wrapper.py:636-712, quoted from memory: correct it here if the reference differs); the caller passes
+    `frames_per_token = source_mel_len / source_content_len * length_adjust` and this is the one place that multiplies
+    and truncates -- in double precision, like the reference."""
+    return int(float(frames_per_token) * int(n_tokens))
+
+
+def v2_ar_prompt(target_narrow, src_narrow):
+    """The AR model's condition tokens: target then source narrow tokens along time (vc_wrapper.py:636-712, from memory)."""
+    return torch.cat([target_narrow, src_narrow], dim=1)
+
+
+def group_by_length(lengths):
+    """{S: [indices b with lengths[b] == S]} for S > 0, in order of first appearance: the vocoder runs once per group,
+    because it has no length argument and its convolutions would see another utterance's padding."""
+    groups = {}
+    for b, s in enumerate(lengths):
+        if s > 0:
+            groups.setdefault(int(s), []).append(b)
+    return groups
+
+
+LOG_MEL_FLOOR = -11.512925464970229        # log(1e-5): the mel front-end's clamp (modules/audio.py:45-82)
+
+
+class V2HotPath:
+    """The v2 chain as ONE call: narrow content tokens -> AR length regulator -> AR generate -> CFM length regulator ->
+    cat([prompt_condition, cond]) -> CFM sampler (3-way CFG) -> strip the prompt frames -> BigVGAN
+    (modules/v2/vc_wrapper.py:636-712, modules/v2/ar.py:382-422).  A batch is B independent runs of that chain.
+
+    ar: seedvc_amd.ar.ARModel (setup_caches(max_batch_size=B) done by the caller); ar_lr / cfm_lr:
+    seedvc_amd.length_regulator.InterpolateRegulator (v2_ar / v2_cfm); cfm: seedvc_amd.cfm.CFM (v2); vocoder: BigVGAN."""
+
+    def __init__(self, ar, ar_lr, cfm_lr, cfm, vocoder):
+        self.ar, self.ar_lr, self.cfm_lr, self.cfm, self.vocoder = ar, ar_lr, cfm_lr, cfm, vocoder
+        self.device = cfm.device
+        self._stacked = (None, None)
+        self.marks = None           # a list: convert_batch appends (stage name, HIP event) at its stage boundaries (tools/v2_bench.py)
+
+    def _mark(self, name):
+        if self.marks is not None:
+            ev = torch.cuda.Event(enable_timing=True)
+            ev.record()
+            self.marks.append((name, ev))
+
+    @torch.inference_mode()
+    def prepare_target(self, target_narrow, target_tokens, target_mel, style):
+        """Per-voice work done once: prompt_condition = cfm_lr(target_tokens, ylens=[P]) (vc_wrapper.py, the reference
+        computes it per call).  target_narrow (1, Nn), target_tokens (1, Np), target_mel (1, C, P), style (1, Ds)."""
+        from . import _lib
+        dev = self.device
+        P = int(target_mel.size(2))
+        tok = target_tokens.to(dev).long()
+        if P < 1 or tok.numel() < 1:
+            raise ValueError("prepare_target: the target needs at least one content token and one mel frame")
+        pc = self.cfm_lr(tok, ylens=torch.LongTensor([P]))[0]
+        return dict(narrow=target_narrow.to(dev).long(), tokens=tok, mel=_lib.f32c(target_mel, dev), style=_lib.f32c(style, dev),
+                    prompt_condition=pc, P=P)
+
+    def _stack_targets(self, targets):
+        """Padded batch tensors of the target records (kept while the same records come back in the same order)."""
+        key = tuple(id(t) for t in targets)
+        if self._stacked[0] == key:
+            return self._stacked[1]
+        dev, B = self.device, len(targets)
+        Pmax = max(t["P"] for t in targets)
+        pc = torch.zeros(B, Pmax, targets[0]["prompt_condition"].size(2), device=dev)
+        mel = torch.zeros(B, targets[0]["mel"].size(1), Pmax, device=dev)
+        for b, t in enumerate(targets):
+            pc[b, :t["P"]] = t["prompt_condition"][0]
+            mel[b, :, :t["P"]] = t["mel"][0]
+        st = dict(prompt_condition=pc, mel=mel, style=torch.cat([t["style"] for t in targets]), Pmax=Pmax, keep=list(targets))
+        self._stacked = (key, st)
+        return st
+
+    @torch.inference_mode()
+    def convert_batch(self, src_narrow, targets, frames_per_token, n_timesteps, cfg_rates=(0.7, 0.7), top_p=0.7,
+                      temperature=0.7, repetition_penalty=1.5, max_new=4001, seeds=None, exp_noise=None, z=None,
+                      random_voice=False):
+        """src_narrow: list of B (1, Ns_b) token tensors; targets: list of B records of `prepare_target`;
+        frames_per_token: list of B floats (see `v2_target_frames`); seeds | exp_noise: the AR draws (`ARModel.generate_batch`);
+        z: the sampler's noise, a (B, C, >= T) tensor or a list of B (1, C, >= P_b + S_b) tensors (torch.randn when None).
+        -> list of B dicts {tokens (1, n_b), mel (1, C, S_b), wave (1, S_b * hop)}.  One host synchronisation (the token
+        counts); everything after it is enqueued from host integers."""
+        import ctypes as C
+        from . import _lib
+        B, dev = len(src_narrow), self.device
+        if not (B == len(targets) == len(frames_per_token)):
+            raise ValueError("convert_batch: src_narrow, targets and frames_per_token must have one entry per utterance")
+        if seeds is not None and exp_noise is not None:
+            raise ValueError("convert_batch: give seeds or exp_noise, not both")
+        if B == 0:
+            return []
+        with torch.cuda.device(dev):
+            self._mark("start")
+            # AR condition: embedding-only regulator over cat([target_narrow, src_narrow]) of every utterance, one launch
+            narrow = [v2_ar_prompt(t["narrow"], s.to(dev).long()) for t, s in zip(targets, src_narrow)]
+            nlen = [int(x.size(1)) for x in narrow]
+            tok_in = torch.zeros(B, max(nlen), dtype=torch.int64, device=dev)
+            for b, x in enumerate(narrow):
+                tok_in[b, :nlen[b]] = x[0]
+            ar_cond = self.ar_lr(tok_in, in_lens=nlen)[0]
+            toks, n = self.ar.generate_batch_raw([ar_cond[b:b + 1, :nlen[b]] for b in range(B)], [t["tokens"] for t in targets],
+                                                 exp_noise, top_p, temperature, repetition_penalty, max_new, 16, seeds)
+            self._mark("ar")
+            # ---- the one synchronisation is behind us: n is a list of host integers
+            ylens = [v2_target_frames(f, k) for f, k in zip(frames_per_token, n)]
+            live = [b for b in range(B) if ylens[b] > 0]
+            Cm = self.cfm.in_channels
+            out = [dict(tokens=toks[b:b + 1, :n[b]].long(), mel=torch.zeros(1, Cm, 0, device=dev), wave=torch.zeros(1, 0, device=dev))
+                   for b in range(B)]
+            if not live:
+                return out
+            sub = [targets[b] for b in live]
+            st = self._stack_targets(sub)
+            L = len(live)
+            P = [t["P"] for t in sub]
+            S = [ylens[b] for b in live]
+            nl = [n[b] for b in live]
+            Pmax, Smax, T = st["Pmax"], max(S), max(p + s for p, s in zip(P, S))
+            # padded token rows hold zeros or an EOS: clamp so that every id is a row of the embedding
+            idx = toks if L == B else toks[torch.tensor(live, device=dev)]
+            tok = idx[:, :max(nl)].long().clamp_(max=self.cfm_lr.cfg["codebook_size"] - 1)
+            cond = self.cfm_lr(tok, ylens=torch.LongTensor(S), in_lens=nl)[0]                     # (L, Smax, Dc), rows >= S_b zero
+            Dc = cond.size(2)
+            i32 = lambda v: (C.c_int32 * len(v))(*v)                                                # noqa: E731
+            mu = torch.empty(L, T, Dc, device=dev)
+            _lib.check(_lib.lib().svc_v2_assemble_cond(_lib.ptr(st["prompt_condition"]), i32(P), _lib.ptr(cond), i32(S), L, Pmax, Smax,
+                                                       Dc, T, _lib.ptr(mu), _lib.stream_ptr()))
+            self._mark("lr_assembly")
+            x_lens = [p + s for p, s in zip(P, S)]
+            if z is not None:
+                zz = torch.zeros(L, Cm, T, device=dev)
+                for i, b in enumerate(live):
+                    if z[b].shape[-1] < x_lens[i]:
+                        raise ValueError(f"convert_batch: z[{b}] has {z[b].shape[-1]} frames, the utterance needs {x_lens[i]}")
+                    zz[i, :, :x_lens[i]] = _lib.f32c(z[b], dev).reshape(Cm, -1)[:, :x_lens[i]]
+                z = zz
+            mel = self.cfm.inference(mu, x_lens, st["mel"], st["style"], None, n_timesteps, inference_cfg_rate=list(cfg_rates),
+                                     random_voice=random_voice, z=z, prompt_lens=P)
+            self._mark("cfm")
+            vc = torch.empty(L, Cm, Smax, device=dev)
+            _lib.check(_lib.lib().svc_mel_strip_prompt(_lib.ptr(mel), i32(P), i32(x_lens), L, Cm, T, Smax, C.c_float(LOG_MEL_FLOOR),
+                                                       _lib.ptr(vc), _lib.stream_ptr()))
+            for s_len, members in group_by_length(S).items():
+                m = vc if len(members) == L else vc[torch.tensor(members, device=dev)][:, :, :s_len].contiguous()
+                wave = self.vocoder(m).reshape(len(members), -1)
+                for j, i in enumerate(members):
+                    out[live[i]]["mel"] = m[j:j + 1]
+                    out[live[i]]["wave"] = wave[j:j + 1]
+            self._mark("strip_vocoder")
+        return out
+
+
+
 # ----------------------------------------------------------------------------------------- multi-GPU sharding
 def shard_range(n_items, rank, world_size):
     """Contiguous block partition of `n_items` utterances over ranks (first ranks take the remainder)."""
