@@ -122,6 +122,20 @@ void svc_bigvgan_destroy(svc_bigvgan_t* m);
 /* Replaces `vocoder_fn(mel)` = BigVGAN.forward (modules/bigvgan/bigvgan.py:360-386).
  * mel [B][num_mels][S] -> out [B][1][S * prod(upsample_rates)]. */
 int svc_bigvgan_forward(svc_bigvgan_t* m, const float* mel, int B, int S, float* out, void* stream);
+/* The same for a batch of utterances of different lengths, in one call (BigVGAN only; HiFT has no such entry point).
+ * mel [B][num_mels][S]; lens HOST [B], 0 <= lens[b] <= S; out [B][1][S * up], up = prod(upsample_rates).
+ * out[b][0][: lens[b] * up] is the waveform of mel[b][:, :lens[b]] run alone (its convs zero-pad and its anti-aliased
+ * activations replicate at the utterance's own last frame); every sample at and above lens[b] * up is written as zero, and
+ * lens[b] == 0 gives an all-zero row.  Mel frames at and above lens[b] are never read as values: they may hold anything, NaN
+ * included.  "Run alone" is bit for bit what svc_bigvgan_forward returns for (1, num_mels, lens[b]) when lens[b] >= 192,
+ * whatever the other utterances, their order and the micro-batch size; below 192 frames a layer may take another kernel
+ * form in the padded batch than alone (the resident-tile / fp8-correction convs need 192 output rows), and the two agree
+ * within the precision's bound against the reference instead (waveform RMS < 1e-4).  Equal lengths (lens[b] == S for all b)
+ * give svc_bigvgan_forward's result bit for bit.
+ * lens is consumed before the call returns (pinned staging of the handle; no host synchronisation in steady state); B is not
+ * limited.  The utterances run longest first in micro-batches (svc_bigvgan_set_microbatch), each padded to its own longest
+ * member.  lens == NULL, a length outside [0, S], B < 1 or S < 1: error (svc_last_error), nothing enqueued. */
+int svc_bigvgan_forward_ragged(svc_bigvgan_t* m, const float* mel, const int32_t* lens, int B, int S, float* out, void* stream);
 
 typedef struct svc_hift_config {      /* configs/hifigan.yml */
     int in_channels, base_channels, nb_harmonics, sampling_rate;

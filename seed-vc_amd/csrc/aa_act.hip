@@ -224,17 +224,21 @@ __global__ __launch_bounds__(256) void aa_act_rows4_kernel(const T* __restrict__
 // Thread = (channel, time segment of SEG outputs); a rolling window of s values lives in registers.
 // mode 0: anti-aliased snake (a, inv_b per channel); mode 1: plain snake x + inv_b sin^2(a x) (HiFT);
 // mode 2: leaky relu with `slope`.
+// RAGGED (mode 0 only): sequence b holds lens[b] <= L valid rows.  Its window replicates row lens[b] - 1 (the utterance's
+// own edge), rows [lens[b], L) are written as zero in every plane, and x rows at and above lens[b] are never read.  The
+// uniform instantiation (RAGGED = false) is the code it always was: Lv and i1v fold to L and i1 at compile time.
 constexpr int SEG = 64;
 
-template <typename OutT>
+template <typename OutT, bool RAGGED>
 __global__ __launch_bounds__(256) void act_cl_kernel(const float* __restrict__ x, long ldx, OutT* __restrict__ y,
                                                      OutT* __restrict__ ylo, long ldy, Taps ft, const float* __restrict__ pa, const float* __restrict__ pinvb,
-                                                     int C, int L, int mode, float slope, int lo_fmt) {
+                                                     int C, int L, int mode, float slope, int lo_fmt, const int* __restrict__ lens) {
     const int c = blockIdx.x * 64 + (threadIdx.x & 63);
     const int seg = blockIdx.y * 4 + (threadIdx.x >> 6);
     const int b = blockIdx.z;
     const int i0 = seg * SEG;
     if (c >= ldy || i0 >= L) return;
+    const int Lv = RAGGED ? lens[b] : L;          // valid rows of this sequence
     const float* xr = x + (long)b * L * ldx + c;
     OutT* yr = y + (long)b * L * ldy + c;
     OutT* yl = ylo ? ylo + (long)b * L * ldy + c : nullptr;
@@ -254,6 +258,11 @@ __global__ __launch_bounds__(256) void act_cl_kernel(const float* __restrict__ x
     if (c >= C) {   // pad channels of the channels-last layout stay zero
         for (int i = i0; i < i1; ++i) put(i, 0.f);
         return;
+    }
+    const int i1v = RAGGED ? min(i1, Lv) : i1;    // end of this segment's valid rows
+    if constexpr (RAGGED) {
+        for (int i = max(i0, Lv); i < i1; ++i) put(i, 0.f);
+        if (i0 >= Lv) return;
     }
     if (mode != 0) {
         const float a = mode == 1 ? pa[c] : 0.f, ib = mode == 1 ? pinvb[c] : 0.f;
@@ -278,7 +287,7 @@ __global__ __launch_bounds__(256) void act_cl_kernel(const float* __restrict__ x
     // polynomial -- PMC showed this kernel at 83 % VALU issue (89 instructions per output), so instruction count is its
     // time.  BigVGAN S = 430 against the reference: 1.726e-6 with it, 1.728e-6 with the polynomial (fp16x3).
     const float a = pa[c] * 0.15915494309189535f, ib = pinvb[c];
-    const int Lm = 2 * L - 1;
+    const int Lm = 2 * Lv - 1;
     auto snake = [&](float u) -> float {
         const float sn = __builtin_amdgcn_sinf(__builtin_amdgcn_fractf(a * u));     // fract: v_sin_f32 is defined on +-256 revolutions only
         return u + ib * sn * sn;
@@ -295,12 +304,12 @@ __global__ __launch_bounds__(256) void act_cl_kernel(const float* __restrict__ x
 #pragma unroll
         for (int u = 0; u < 6; ++u) {
             const int i = ib0 + u;
-            if (i >= i1) break;
+            if (i >= i1v) break;
             float acc = 0.f;
 #pragma unroll
             for (int t = 0; t < 12; ++t) acc += ft.f[t] * sw[(2 * u + t) % 12];
             put_at(i, acc);
-            if (i + 1 < i1) {
+            if (i + 1 < i1v) {
                 // new s[2i+7] (odd m: taps 0,2,..,10) and s[2i+8] (even m: taps 1,3,..,11), both from x[i+1 .. i+6]
                 float u1 = 0.f, u2 = 0.f;
 #pragma unroll
@@ -316,7 +325,7 @@ __global__ __launch_bounds__(256) void act_cl_kernel(const float* __restrict__ x
             }
         }
     };
-    if (i0 >= 8 && i0 + SEG + 16 <= L) {
+    if (i0 >= 8 && i0 + SEG + 16 <= Lv) {
         // Interior segment (all but the first and last of a sequence): no index is ever clamped, so the rows are walked
         // with two running pointers -- the generic path below pays a clamp and a 64-bit multiply per load and per store,
         // which was ~45 % of this kernel's instructions.  Same arithmetic in the same order: bit-identical.
@@ -342,16 +351,16 @@ __global__ __launch_bounds__(256) void act_cl_kernel(const float* __restrict__ x
             yp += ldy;
             if (ylp) { put_lo(ylp, v, h); ylp += ldy; }
         };
-        for (int ib0 = i0; ib0 < i1; ib0 += 6) {
+        for (int ib0 = i0; ib0 < i1v; ib0 += 6) {
             float xn[6];
 #pragma unroll
-            for (int q = 0; q < 6; ++q) { xn[q] = *xp; xp += ldx; }     // rows ib0 + 7 .. ib0 + 12 <= i0 + 72 < L
+            for (int q = 0; q < 6; ++q) { xn[q] = *xp; xp += ldx; }     // rows ib0 + 7 .. ib0 + 12 <= i0 + 72 < Lv
             trip(ib0, xn, put_walk);
         }
         return;
     }
     auto xat = [&](int q) -> float {
-        q = q < 0 ? 0 : (q > L - 1 ? L - 1 : q);
+        q = q < 0 ? 0 : (q > Lv - 1 ? Lv - 1 : q);
         return xr[(long)q * ldx];
     };
 #pragma unroll
@@ -366,7 +375,7 @@ __global__ __launch_bounds__(256) void act_cl_kernel(const float* __restrict__ x
     }
 #pragma unroll
     for (int k = 0; k < 6; ++k) xw[k] = xat(i0 + 1 + k);
-    for (int ib0 = i0; ib0 < i1; ib0 += 6) {
+    for (int ib0 = i0; ib0 < i1v; ib0 += 6) {
         float xn[6];
 #pragma unroll
         for (int q = 0; q < 6; ++q) xn[q] = xat(ib0 + 7 + q);
@@ -469,18 +478,27 @@ int aa_act_rows_launch(const void* x, void* y, const float* up, const float* dn,
 }
 
 int act_cl_launch(const float* x, long ldx, void* y, void* y_lo, long ldy, int out_f16, const float* taps12_host, const float* a,
-                  const float* inv_b, int B, int C, int L, int mode, float slope, hipStream_t st, int lo_fmt) {
+                  const float* inv_b, int B, int C, int L, int mode, float slope, hipStream_t st, int lo_fmt, const int* lens) {
     Taps ft;
     for (int i = 0; i < 12; ++i) ft.f[i] = taps12_host ? taps12_host[i] : 0.f;
     dim3 grid(cdiv(ldy, 64), cdiv(cdiv(L, SEG), 4), B);
+    if (lens) {     // ragged batch: an instantiation of its own, so the uniform one pays nothing for it
+        SVC_REQUIRE(mode == 0, "act_cl_launch: per-sequence lengths are for the anti-aliased mode only");
+        if (out_f16)
+            hipLaunchKernelGGL((act_cl_kernel<half_t, true>), grid, dim3(256), 0, st, x, ldx, (half_t*)y, (half_t*)y_lo, ldy, ft, a, inv_b, C, L, mode, slope, lo_fmt, lens);
+        else
+            hipLaunchKernelGGL((act_cl_kernel<float, true>), grid, dim3(256), 0, st, x, ldx, (float*)y, (float*)nullptr, ldy, ft, a, inv_b, C, L, mode, slope, 0, lens);
+        SVC_CHECK_HIP(hipGetLastError());
+        return 0;
+    }
     // pointwise modes only: the anti-aliased window doubles its registers per thread in the pair form and measured slower
     if (out_f16 && mode != 0 && (ldx % 2) == 0 && (ldy % 2) == 0) {
         dim3 grid2(cdiv(ldy, 128), cdiv(cdiv(L, SEG), 4), B);
         hipLaunchKernelGGL(act_cl2_kernel, grid2, dim3(256), 0, st, x, ldx, (half_t*)y, (half_t*)y_lo, ldy, ft, a, inv_b, C, L, mode, slope, lo_fmt);
     } else if (out_f16)
-        hipLaunchKernelGGL(act_cl_kernel<half_t>, grid, dim3(256), 0, st, x, ldx, (half_t*)y, (half_t*)y_lo, ldy, ft, a, inv_b, C, L, mode, slope, lo_fmt);
+        hipLaunchKernelGGL((act_cl_kernel<half_t, false>), grid, dim3(256), 0, st, x, ldx, (half_t*)y, (half_t*)y_lo, ldy, ft, a, inv_b, C, L, mode, slope, lo_fmt, (const int*)nullptr);
     else
-        hipLaunchKernelGGL(act_cl_kernel<float>, grid, dim3(256), 0, st, x, ldx, (float*)y, (float*)nullptr, ldy, ft, a, inv_b, C, L, mode, slope, 0);
+        hipLaunchKernelGGL((act_cl_kernel<float, false>), grid, dim3(256), 0, st, x, ldx, (float*)y, (float*)nullptr, ldy, ft, a, inv_b, C, L, mode, slope, 0, (const int*)nullptr);
     SVC_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -234,8 +234,10 @@ inline int conv1d_run(const ConvW& w, const ConvRun& r, hipStream_t st) {
     return kgemm_launch(p, w.dtype, KG_EPI_STORE, st);
 }
 
-// x [B][L][cin_pad] -> y [B][L*s][cout_pad] (channels-last), written at row offset c_off of c_rows-row sequences
-inline int convT_run(const ConvW& w, ActBuf a, int B, int L, float* c32, int c_rows_q, int c_off_q, hipStream_t st) {
+// x [B][L][cin_pad] -> y [B][L*s][cout_pad] (channels-last), written at row offset c_off of c_rows-row sequences.
+// seq_len (device [B], optional): valid input rows per sequence; rows at and above it read as padding (ragged batches)
+inline int convT_run(const ConvW& w, ActBuf a, int B, int L, float* c32, int c_rows_q, int c_off_q, hipStream_t st,
+                     const int* seq_len = nullptr) {
     KGemmParams p;
     memset(&p, 0, sizeof(p));
     const int nsub = is_split(w.vd) ? 3 : 1;
@@ -244,6 +246,7 @@ inline int convT_run(const ConvW& w, ActBuf a, int B, int L, float* c32, int c_r
     p.Lout = L;
     p.a_seq_rows = L;
     p.a_len = L;
+    p.seq_len = seq_len;
     p.a_stride = 1;
     p.pad_mode = KG_PAD_ZERO;
     p.n_taps = 3 * nsub;

@@ -34,6 +34,9 @@ int aa_act_rows_launch(const void* x, void* y, const float* up12_dev, const floa
                        const float* log_beta, int B, int C, int L, int dtype, hipStream_t st);
 // channels-last activation: mode 0 anti-aliased snake, 1 plain snake, 2 leaky relu
 // y_lo != null (fp16 output only): also write the residual plane x - float(half(x)) (split-precision operands)
+// lens != null (mode 0 only): device [B] valid rows per sequence; the window replicates row lens[b] - 1, rows at and above
+// lens[b] are written as zero and never read
 int act_cl_launch(const float* x, long ldx, void* y, void* y_lo, long ldy, int out_f16, const float* taps12_host, const float* a,
-                  const float* inv_b, int B, int C, int L, int mode, float slope, hipStream_t st, int lo_fmt = 0);
+                  const float* inv_b, int B, int C, int L, int mode, float slope, hipStream_t st, int lo_fmt = 0,
+                  const int* lens = nullptr);
 }  // namespace svc

@@ -49,6 +49,34 @@ __global__ void mel_to_cl_kernel(const float* __restrict__ mel, OutT* __restrict
     if (dst_lo) dst_lo[i] = (OutT)(v - (float)h);
 }
 
+// Ragged batch: row j of the micro-batch is utterance src[j] of the caller's (B, C, S_in) mel, cut to S frames; frames at and
+// above lens[j] become zero rows by selection (they may hold NaN, and 0 * NaN is NaN) and are never loaded
+template <typename OutT>
+__global__ void mel_to_cl_ragged_kernel(const float* __restrict__ mel, OutT* __restrict__ dst, OutT* __restrict__ dst_lo,
+                                        const int* __restrict__ src, const int* __restrict__ lens, int B, int C, int S_in, int S, int ld) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)B * S * ld) return;
+    const int c = (int)(i % ld);
+    const long bs = i / ld;
+    const int s = (int)(bs % S), b = (int)(bs / S);
+    float v = 0.f;
+    if (c < C && s < lens[b]) v = mel[((long)src[b] * C + c) * S_in + s];
+    const OutT h = (OutT)v;
+    dst[i] = h;
+    if (dst_lo) dst_lo[i] = (OutT)(v - (float)h);
+}
+
+// Ragged batch, last step: waveform row j of the micro-batch ([B][L], L <= Lw) -> row src[j] of the caller's [..][Lw] output,
+// samples at and above lens[j] written as zero (w is not read there)
+__global__ void wave_scatter_kernel(const float* __restrict__ w, float* __restrict__ out, const int* __restrict__ src,
+                                    const int* __restrict__ lens, int B, long L, long Lw) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)B * Lw) return;
+    const int b = (int)(i / Lw);
+    const long n = i - (long)b * Lw;
+    out[(long)src[b] * Lw + n] = n < lens[b] ? w[(long)b * L + n] : 0.f;
+}
+
 // elementwise channels-last: y = f(x) with pad channels zeroed. mode 2 leaky relu, 3 identity (cast)
 template <typename OutT>
 __global__ void ew_cl_kernel(const float* __restrict__ x, OutT* __restrict__ y, OutT* __restrict__ y_lo, long rows, int C, int ld,
@@ -231,6 +259,19 @@ int mel_to_cl(const float* mel, ActOut dst, int vd, int B, int C, int S, int ld,
     return 0;
 }
 
+int mel_to_cl_ragged(const float* mel, ActOut dst, int vd, const int* src, const int* lens, int B, int C, int S_in, int S, int ld,
+                     hipStream_t st) {
+    const long n = (long)B * S * ld;
+    if (vd != 1)
+        hipLaunchKernelGGL(mel_to_cl_ragged_kernel<half_t>, dim3(cdiv(n, 256)), dim3(256), 0, st, mel, (half_t*)dst.hi,
+                           is_split(vd) ? (half_t*)dst.lo : nullptr, src, lens, B, C, S_in, S, ld);
+    else
+        hipLaunchKernelGGL(mel_to_cl_ragged_kernel<float>, dim3(cdiv(n, 256)), dim3(256), 0, st, mel, (float*)dst.hi, (float*)nullptr,
+                           src, lens, B, C, S_in, S, ld);
+    SVC_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
 struct SnakeP {
     float* a = nullptr;
     float* inv_b = nullptr;
@@ -262,6 +303,14 @@ struct ResBlockW {
     SnakeP a1[3], a2[3];
 };
 
+// One micro-batch of a ragged call (device pointers into the call's length table): row j is utterance src[j] of the caller's
+// batch and holds len[i][j] valid rows after i up-sampling stages
+struct RaggedMB {
+    const int* src = nullptr;
+    const int* len[9] = {};
+    int S_in = 0;           // frames per utterance of the caller's mel (its row stride)
+};
+
 }  // namespace
 
 // ================================================================================================ BigVGAN
@@ -278,22 +327,32 @@ struct svc_bigvgan {
     ActOut mel_a, act_a;
     float *x, *y, *t, *xsum;
     int microbatch = 0;
+    // ragged calls: pinned staging for the host-built length table and its device copy
+    PinnedRing staging;
+    Arena tab;
+    int* d_tab = nullptr;
+    size_t tab_cap = 0;
 
     int reserve(int B, int S, hipStream_t st);
-    int run(const float* mel, int B, int S, float* out, hipStream_t st);
+    // rg == null: B utterances of S frames each.  rg != null: micro-batch of a ragged call, `mel` / `out` are the caller's
+    // whole tensors and S the micro-batch's longest member
+    int run(const float* mel, int B, int S, float* out, hipStream_t st, const RaggedMB* rg = nullptr);
 };
 
 namespace {
 int act_cl_any(const float* x, int ld, ActOut y, int vd, const float* taps, const SnakeP& sp, int B, int C, int L, int mode,
-               float slope, hipStream_t st, int lo_fmt = 0) {
+               float slope, hipStream_t st, int lo_fmt = 0, const int* lens = nullptr) {
     return act_cl_launch(x, ld, y.hi, is_split(vd) ? y.lo : nullptr, ld, vd != 1, taps, sp.a, sp.inv_b, B, C, L, mode, slope, st,
-                         is_split(vd) ? lo_fmt : 0);
+                         is_split(vd) ? lo_fmt : 0, lens);
 }
 
 // runs one residual stack on stream buffer `x_in` (read only) producing the block output either into `y`
-// (intermediate pairs) and, for the last pair, (y_last) * out_scale + res2 -> final_dst
+// (intermediate pairs) and, for the last pair, (y_last) * out_scale + res2 -> final_dst.
+// lens (device [B], anti-aliased mode without fusion only): valid rows per sequence.  The activations are the only producers of
+// conv operands here, so masking them is enough; the raw conv outputs past lens[b] are garbage that only pointwise ops touch.
 int resblock_run(const ResBlockW& rb, int dtype, const float* taps, int act_mode, const float* x_in, float* y, float* t, ActOut act_a,
-                 int B, int L, float out_scale, const float* res2, float* final_dst, hipStream_t st, ActOut act_b = ActOut()) {
+                 int B, int L, float out_scale, const float* res2, float* final_dst, hipStream_t st, ActOut act_b = ActOut(),
+                 const int* lens = nullptr) {
     const int f16 = dtype;      // operand mode handed to the activation writers
     const int ld = cpad(rb.ch, dtype);
     const float* cur = x_in;
@@ -313,7 +372,7 @@ int resblock_run(const ResBlockW& rb, int dtype, const float* taps, int act_mode
         const bool p8_1 = dtype == 3 && conv_p8_ok(rb.c1[d], L, rb.dil[d]);
         const bool p8_2 = dtype == 3 && conv_p8_ok(rb.c2[d], L, 1);
         if (!fuse || d == 0) {
-            if (act_cl_any(cur, ld, act_a, f16, taps, rb.a1[d], B, rb.ch, L, act_mode, 0.f, st, p8_1)) return 1;
+            if (act_cl_any(cur, ld, act_a, f16, taps, rb.a1[d], B, rb.ch, L, act_mode, 0.f, st, p8_1, lens)) return 1;
         }
         ConvRun r1;
         r1.a = act_a.in(); r1.B = B; r1.Lin = L; r1.Lout = L; r1.dilation = rb.dil[d];
@@ -323,7 +382,7 @@ int resblock_run(const ResBlockW& rb, int dtype, const float* taps, int act_mode
         else { r1.c32 = t; r1.ldc32 = ld; }
         if (conv1d_run(rb.c1[d], r1, st)) return 1;
         if (!fuse) {
-            if (act_cl_any(t, ld, act_a, f16, taps, rb.a2[d], B, rb.ch, L, act_mode, 0.f, st, p8_2)) return 1;
+            if (act_cl_any(t, ld, act_a, f16, taps, rb.a2[d], B, rb.ch, L, act_mode, 0.f, st, p8_2, lens)) return 1;
         }
         ConvRun r2;
         r2.a = fuse ? act_b.in() : act_a.in(); r2.B = B; r2.Lin = L; r2.Lout = L; r2.dilation = 1;
@@ -374,9 +433,15 @@ int svc_bigvgan::reserve(int B, int S, hipStream_t st) {
     return 0;
 }
 
-int svc_bigvgan::run(const float* mel, int B, int S, float* out, hipStream_t st) {
+// Ragged micro-batches (rg): every PRODUCER OF A CONV OPERAND respects the lengths -- the mel copy, the transposed convs (which
+// read the previous stage's raw output, through the tap-GEMM's per-sequence valid-row array) and the anti-aliased activations
+// -- so each conv sees zero rows past an utterance's end exactly as its zero padding would supply them.  The convs themselves
+// are unchanged; what they write past lens[b] (x, y, t, xsum) is read only by pointwise ops and by the masked producers.
+int svc_bigvgan::run(const float* mel, int B, int S, float* out, hipStream_t st, const RaggedMB* rg) {
     const int vd = dtype;
-    if (mel_to_cl(mel, mel_a, vd, B, cfg.num_mels, S, cpad(cfg.num_mels, vd), st)) return 1;
+    if (rg) {
+        if (mel_to_cl_ragged(mel, mel_a, vd, rg->src, rg->len[0], B, cfg.num_mels, rg->S_in, S, cpad(cfg.num_mels, vd), st)) return 1;
+    } else if (mel_to_cl(mel, mel_a, vd, B, cfg.num_mels, S, cpad(cfg.num_mels, vd), st)) return 1;
     int ch = cfg.upsample_initial_channel;
     long L = S;
     {
@@ -394,23 +459,29 @@ int svc_bigvgan::run(const float* mel, int B, int S, float* out, hipStream_t st)
             if (ew_cl(xsum, act_a, vd, (long)B * L, ch, cpad(ch, vd), 3, 0.f, st)) return 1;
             a = act_a.in();
         }
-        if (convT_run(ups[i], a, B, (int)L, x, 0, 0, st)) return 1;
+        if (convT_run(ups[i], a, B, (int)L, x, 0, 0, st, rg ? rg->len[i] : nullptr)) return 1;
         L *= cfg.upsample_rates[i];
         ch /= 2;
         for (int j = 0; j < nk; ++j) {
             // x = mean_j block_j(x): block j's last conv writes (y_j) / nk + (j > 0 ? xsum : 0) into xsum
             if (resblock_run(blocks[i * nk + j], vd, taps, 0, x, y, t, act_a, B, (int)L, 1.0f / (float)nk,
-                             j > 0 ? xsum : nullptr, xsum, st)) return 1;
+                             j > 0 ? xsum : nullptr, xsum, st, ActOut(), rg ? rg->len[i + 1] : nullptr)) return 1;
         }
     }
-    if (act_cl_any(xsum, cpad(ch, vd), act_a, vd, taps, act_post, B, ch, (int)L, 0, 0.f, st)) return 1;
+    const int* len_w = rg ? rg->len[cfg.num_upsamples] : nullptr;
+    if (act_cl_any(xsum, cpad(ch, vd), act_a, vd, taps, act_post, B, ch, (int)L, 0, 0.f, st, 0, len_w)) return 1;
     {
         ConvRun r;
         r.a = act_a.in(); r.B = B; r.Lin = (int)L; r.Lout = (int)L; r.pad_left = 3;
-        r.c32 = out; r.ldc32 = 1; r.n_override = 1;
+        r.c32 = rg ? x : out; r.ldc32 = 1; r.n_override = 1;     // x is free after the last stage (B * L <= its B * L * Cpad)
         r.act = cfg.use_tanh_at_final ? KG_ACT_TANH : KG_ACT_CLAMP;
         r.act_slope = 1.0f;
         if (conv1d_run(conv_post, r, st)) return 1;
+    }
+    if (rg) {   // back to the caller's order and row length, tails zeroed
+        const long Lw = (long)rg->S_in * (L / S);
+        hipLaunchKernelGGL(wave_scatter_kernel, dim3(cdiv((long)B * Lw, 256)), dim3(256), 0, st, x, out, rg->src, len_w, B, L, Lw);
+        SVC_CHECK_HIP(hipGetLastError());
     }
     return 0;
 }
@@ -688,6 +759,67 @@ int svc_bigvgan_forward(svc_bigvgan_t* m, const float* mel, int B, int S, float*
         const int nb = std::min(mb, B - b0);
         if (m->reserve(nb, S, st)) return 1;
         if (m->run(mel + (long)b0 * m->cfg.num_mels * S, nb, S, out + (long)b0 * S * total, st)) return 1;
+    }
+    return 0;
+}
+
+int svc_bigvgan_forward_ragged(svc_bigvgan_t* m, const float* mel, const int32_t* lens, int B, int S, float* out, void* stream) {
+    SVC_REQUIRE(m && mel && lens && out && B >= 1 && S >= 1, "bad argument");
+    for (int b = 0; b < B; ++b) SVC_REQUIRE(lens[b] >= 0 && lens[b] <= S, "svc_bigvgan_forward_ragged: lens out of range");
+    hipStream_t st = (hipStream_t)stream;
+    const int nu = m->cfg.num_upsamples;
+    long total = 1;
+    for (int i = 0; i < nu; ++i) total *= m->cfg.upsample_rates[i];
+    // Longest first, micro-batch by micro-batch, each padded to its own longest member only: a batch padded to the longest
+    // utterance of all would compute B * Smax rows.  The stable sort keeps the order of equal lengths, so a batch of equal
+    // lengths runs exactly as svc_bigvgan_forward runs it.
+    std::vector<int> order(B);
+    for (int b = 0; b < B; ++b) order[b] = b;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return lens[a] > lens[b]; });
+    // length table, per micro-batch of nb rows: src[nb], then the valid rows after 0 .. nu up-sampling stages, [nb] each.
+    // Built in a pinned slot and copied once: the caller's array is consumed here and nothing waits for the stream.
+    const size_t n_tab = (size_t)B * (nu + 2);
+    if (n_tab > m->tab_cap) {
+        SVC_CHECK_HIP(hipStreamSynchronize(st));
+        m->tab.release();
+        m->d_tab = m->tab.alloc_n<int>(n_tab, st);
+        if (!m->d_tab) { m->tab_cap = 0; return 1; }
+        m->tab_cap = n_tab;
+    }
+    int* h = reinterpret_cast<int*>(m->staging.acquire(n_tab * sizeof(int)));
+    if (!h) return 1;
+    const int mb = m->microbatch > 0 ? m->microbatch : 32;
+    for (int b0 = 0; b0 < B; b0 += mb) {
+        const int nb = std::min(mb, B - b0);
+        int* row = h + (size_t)b0 * (nu + 2);
+        for (int j = 0; j < nb; ++j) {
+            row[j] = order[b0 + j];
+            long l = lens[order[b0 + j]];
+            for (int i = 0; i <= nu; ++i) {
+                row[(size_t)(i + 1) * nb + j] = (int)l;
+                if (i < nu) l *= m->cfg.upsample_rates[i];
+            }
+        }
+    }
+    SVC_CHECK_HIP(hipMemcpyAsync(m->d_tab, h, n_tab * sizeof(int), hipMemcpyHostToDevice, st));
+    if (m->staging.commit(st)) return 1;
+    for (int b0 = 0; b0 < B; b0 += mb) {
+        const int nb = std::min(mb, B - b0);
+        const int* row = m->d_tab + (size_t)b0 * (nu + 2);
+        RaggedMB rg;
+        rg.src = row;
+        for (int i = 0; i <= nu; ++i) rg.len[i] = row + (size_t)(i + 1) * nb;
+        rg.S_in = S;
+        const int Smb = lens[order[b0]];
+        if (Smb == 0) {     // nothing but empty utterances left: their rows are all tail
+            const long Lw = (long)S * total;
+            hipLaunchKernelGGL(wave_scatter_kernel, dim3(cdiv((long)nb * Lw, 256)), dim3(256), 0, st, (const float*)nullptr, out, rg.src,
+                               rg.len[nu], nb, 0L, Lw);
+            SVC_CHECK_HIP(hipGetLastError());
+            continue;
+        }
+        if (m->reserve(nb, Smb, st)) return 1;
+        if (m->run(mel, nb, Smb, out, st, &rg)) return 1;
     }
     return 0;
 }

@@ -171,8 +171,9 @@ def v2_ar_prompt(target_narrow, src_narrow):
 
 
 def group_by_length(lengths):
-    """{S: [indices b with lengths[b] == S]} for S > 0, in order of first appearance: the vocoder runs once per group,
-    because it has no length argument and its convolutions would see another utterance's padding."""
+    """{S: [indices b with lengths[b] == S]} for S > 0, in order of first appearance: the grouped vocoder path runs once
+    per group, because a plain vocoder call has no length argument and its convolutions would see another utterance's
+    padding (the ragged call, `BigVGAN.__call__(mel, lens=...)`, takes the lengths instead)."""
     groups = {}
     for b, s in enumerate(lengths):
         if s > 0:
@@ -189,10 +190,13 @@ class V2HotPath:
     (modules/v2/vc_wrapper.py:636-712, modules/v2/ar.py:382-422).  A batch is B independent runs of that chain.
 
     ar: seedvc_amd.ar.ARModel (setup_caches(max_batch_size=B) done by the caller); ar_lr / cfm_lr:
-    seedvc_amd.length_regulator.InterpolateRegulator (v2_ar / v2_cfm); cfm: seedvc_amd.cfm.CFM (v2); vocoder: BigVGAN."""
+    seedvc_amd.length_regulator.InterpolateRegulator (v2_ar / v2_cfm); cfm: seedvc_amd.cfm.CFM (v2); vocoder: BigVGAN.
+    ragged_vocoder: a batch of more than one output length takes ONE vocoder call with per-utterance lengths (True) or one
+    call per distinct length (False); a batch of one length is one plain call either way."""
 
-    def __init__(self, ar, ar_lr, cfm_lr, cfm, vocoder):
+    def __init__(self, ar, ar_lr, cfm_lr, cfm, vocoder, ragged_vocoder=True):
         self.ar, self.ar_lr, self.cfm_lr, self.cfm, self.vocoder = ar, ar_lr, cfm_lr, cfm, vocoder
+        self.ragged_vocoder = ragged_vocoder
         self.device = cfm.device
         self._stacked = (None, None)
         self.marks = None           # a list: convert_batch appends (stage name, HIP event) at its stage boundaries (tools/v2_bench.py)
@@ -302,12 +306,21 @@ class V2HotPath:
             vc = torch.empty(L, Cm, Smax, device=dev)
             _lib.check(_lib.lib().svc_mel_strip_prompt(_lib.ptr(mel), i32(P), i32(x_lens), L, Cm, T, Smax, C.c_float(LOG_MEL_FLOOR),
                                                        _lib.ptr(vc), _lib.stream_ptr()))
-            for s_len, members in group_by_length(S).items():
-                m = vc if len(members) == L else vc[torch.tensor(members, device=dev)][:, :, :s_len].contiguous()
-                wave = self.vocoder(m).reshape(len(members), -1)
-                for j, i in enumerate(members):
-                    out[live[i]]["mel"] = m[j:j + 1]
-                    out[live[i]]["wave"] = wave[j:j + 1]
+            groups = group_by_length(S)
+            if self.ragged_vocoder and len(groups) > 1:
+                # vc is already padded to Smax (floor-valued frames past S_b, which the ragged call never reads as values)
+                wave = self.vocoder(vc, lens=S).reshape(L, -1)
+                hop = wave.size(1) // Smax
+                for i in range(L):
+                    out[live[i]]["mel"] = vc[i:i + 1, :, :S[i]]
+                    out[live[i]]["wave"] = wave[i:i + 1, :S[i] * hop]
+            else:
+                for s_len, members in groups.items():
+                    m = vc if len(members) == L else vc[torch.tensor(members, device=dev)][:, :, :s_len].contiguous()
+                    wave = self.vocoder(m).reshape(len(members), -1)
+                    for j, i in enumerate(members):
+                        out[live[i]]["mel"] = m[j:j + 1]
+                        out[live[i]]["wave"] = wave[j:j + 1]
             self._mark("strip_vocoder")
         return out
 

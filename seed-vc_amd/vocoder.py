@@ -54,12 +54,23 @@ class BigVGAN:
         _lib.check(_lib.lib().svc_bigvgan_set_microbatch(self._h, int(n)))
 
     @torch.inference_mode()
-    def __call__(self, mel):
+    def __call__(self, mel, lens=None):
+        """mel (B, num_mels, S) -> (B, 1, S * up).  lens (list / LongTensor of B ints, 0 <= lens[b] <= S): a ragged batch in
+        one call -- out[b, 0, :lens[b] * up] is the waveform of mel[b, :, :lens[b]] run alone, the rest of the row is zero,
+        and frames at and above lens[b] may hold anything (svc_bigvgan_forward_ragged in include/seedvc_hip.h)."""
         B, _, S = mel.shape
+        if lens is not None:
+            lens = [int(v) for v in (lens.tolist() if torch.is_tensor(lens) else lens)]
+            if len(lens) != B:
+                raise ValueError(f"BigVGAN: lens has {len(lens)} entries, the batch has {B} utterances")
         with torch.cuda.device(self.device):
             mel = _lib.f32c(mel, self.device)
             out = torch.empty(B, 1, S * self.total_up, device=self.device, dtype=torch.float32)
-            _lib.check(_lib.lib().svc_bigvgan_forward(self._h, _lib.ptr(mel), B, S, _lib.ptr(out), _lib.stream_ptr()))
+            if lens is None:
+                _lib.check(_lib.lib().svc_bigvgan_forward(self._h, _lib.ptr(mel), B, S, _lib.ptr(out), _lib.stream_ptr()))
+            else:
+                _lib.check(_lib.lib().svc_bigvgan_forward_ragged(self._h, _lib.ptr(mel), (C.c_int32 * B)(*lens), B, S, _lib.ptr(out),
+                                                                 _lib.stream_ptr()))
         return out
 
     forward = __call__

@@ -8,7 +8,12 @@ For every B of `--batch` (default 1,64) one JSON line: per-stage milliseconds fr
 (a max_new = 1 call) and decode (the rest), composite mel frames/s and AR tokens/s, the AR share; the same stages timed
 alone in the same process and the difference to the composite ("glue"); at the largest B, seeded against explicit-noise
 generation, alternating.  Two warm-up runs, `--repeats` (5) timed runs, median and spread (max - min) of each figure.
-`--out FILE` writes the lines to FILE as one JSON document."""
+`--out FILE` writes the lines to FILE as one JSON document.
+
+`--ragged`: the same models on a batch whose output lengths ALL differ (per-utterance `frames_per_token` chosen from the
+utterances' own token counts so that the lengths spread evenly over 120 ... `--frames`, fixed shuffled order).  The
+record gives the composite and its stages with `V2HotPath.ragged_vocoder` on (one vocoder call) and off (one call per
+distinct length), alternating run by run; the stages alone and the seeded / explicit comparison are not repeated."""
 import argparse
 import ctypes as C
 import json
@@ -34,6 +39,7 @@ ap.add_argument("--repeats", type=int, default=5)
 ap.add_argument("--tokens", type=int, default=256)
 ap.add_argument("--frames", type=int, default=430, help="prompt frames and generated frames per utterance")
 ap.add_argument("--steps", type=int, default=25)
+ap.add_argument("--ragged", action="store_true", help="all output lengths differ; ragged vocoder call on against off")
 ap.add_argument("--out", default="")
 args = ap.parse_args()
 sizes = [int(b) for b in args.batch.split(",")]
@@ -91,6 +97,51 @@ for B in sizes:
     targets = [target] * B
     src = [torch.randint(0, 32, (1, 80), generator=g).to(dev) for _ in range(B)]
     seeds = list(range(1000, 1000 + B))
+    if args.ragged:
+        import random
+        n0 = [int(o["tokens"].shape[1]) for o in hp.convert_batch(src, targets, [FPT] * B, STEPS, max_new=N_TOK, seeds=seeds)]
+        want = [120 + round((P - 120) * i / max(B - 1, 1)) for i in range(B)]
+        random.Random(0).shuffle(want)
+        fpt = [(w + 0.5) / k for w, k in zip(want, n0)]            # int(fpt_b * n_b) = want_b: the token counts follow the seeds alone
+        zfix = torch.randn(B, Cm, 2 * P, generator=g).to(dev)     # the sampler's noise, fixed: both settings convert the same mels
+        run = lambda: hp.convert_batch(src, targets, fpt, STEPS, cfg_rates=(0.7, 0.7), max_new=N_TOK, seeds=seeds, z=zfix)      # noqa: E731
+        stage_names = ("ar", "lr_assembly", "cfm", "strip_vocoder")
+        per = {sw: {k: [] for k in stage_names + ("composite",)} for sw in (True, False)}
+        outs = {}
+        for sw in (True, False):
+            hp.ragged_vocoder = sw
+            run()
+            outs[sw] = run()
+        for _ in range(R):
+            for sw in (True, False):
+                hp.ragged_vocoder = sw
+                torch.cuda.synchronize()
+                hp.marks = []
+                run()
+                torch.cuda.synchronize()
+                ev = dict(hp.marks)
+                hp.marks = None
+                prev = ev["start"]
+                for k in stage_names:
+                    per[sw][k].append(prev.elapsed_time(ev[k]))
+                    prev = ev[k]
+                per[sw]["composite"].append(ev["start"].elapsed_time(ev["strip_vocoder"]))
+        S = [int(o["mel"].shape[2]) for o in outs[True]]
+        hop = outs[True][0]["wave"].shape[1] // S[0]
+        rec = {"workload": "BASELINE config 5 as one call, all output lengths different", "B": B, "repeats": R,
+               "tokens_per_utterance": [min(n0), max(n0)], "frames_per_utterance": [min(S), max(S)], "mel_frames": sum(S),
+               "vocoder_groups": len(set(S)), "sampler_steps": STEPS,
+               "same_tokens_and_mels": bool(all(torch.equal(a["tokens"], b["tokens"]) and torch.equal(a["mel"], b["mel"])
+                                                for a, b in zip(outs[True], outs[False]))),
+               "waves_bit_identical_from_192_frames": bool(all(torch.equal(a["wave"], b["wave"])
+                                                               for a, b in zip(outs[True], outs[False]) if a["mel"].shape[2] >= 192)),
+               "wave_samples_per_frame": hop}
+        for sw, name in ((True, "ragged_vocoder_on"), (False, "ragged_vocoder_off")):
+            rec[name] = {"composite": stats(per[sw]["composite"]), "stages_in_composite": {k: stats(per[sw][k]) for k in stage_names},
+                         "mel_frames_per_s": round(sum(S) / stats(per[sw]["composite"])["ms"] * 1e3, 1)}
+        print(json.dumps(rec), flush=True)
+        records.append(rec)
+        continue
     run = lambda: hp.convert_batch(src, targets, [FPT] * B, STEPS, cfg_rates=(0.7, 0.7), max_new=N_TOK, seeds=seeds)      # noqa: E731
     out = run()
     run()
