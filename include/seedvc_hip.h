@@ -325,6 +325,36 @@ int svc_kaldi_fbank(svc_campplus_t* m, const float* wave, int n_samples, float* 
 int svc_crossfade(float* chunk2, const float* chunk1_tail, const double* fade_in, const double* fade_out, int n,
                   void* stream);
 
+/* ---------------------------------------------------------------- long-form conversion as a pool of chunks
+ * The drivers' chunk loop (inference.py:470-527, seed_vc_wrapper.py:561-623) with the chunks of one or more utterances run
+ * side by side: a chunk reads the source, the shared prompt and fresh noise, never its neighbour; only the cross-fade
+ * couples neighbours, and it reads finished waveforms.  Conventions of the ragged assembly calls above: every per-chunk /
+ * per-utterance array is HOST int32 and consumed before the call returns (kernel arguments, one launch per 64 chunks),
+ * arguments are checked before anything is launched, every output element is written, nothing synchronises.
+ *
+ * Replaces `cat_condition = torch.cat([prompt_condition, cond[:, p0:p0 + s]], dim=1)` for N chunks of U utterances:
+ * prompt_cond [U][Pmax][Dc], prompt_lens [U], cond [R][Dc] (the utterances' condition rows concatenated along time),
+ * chunk k belongs to utterance utt[k] and takes rows row0[k] .. row0[k] + rows[k] - 1 of cond.  mu [N][T][Dc]:
+ *   mu[k][t] = t < P_u ? prompt_cond[u][t] : t < P_u + rows[k] ? cond[row0[k] + t - P_u] : 0        (u = utt[k])
+ * 0 <= utt[k] < U, 0 <= prompt_lens[u] <= Pmax, rows[k] >= 0, row0[k] >= 0, row0[k] + rows[k] <= R,
+ * prompt_lens[u] + rows[k] <= T, Dc >= 1. */
+int svc_chunks_gather_cond(const float* prompt_cond, const int32_t* prompt_lens, int U, int Pmax, const float* cond, int R,
+                           const int32_t* utt, const int32_t* row0, const int32_t* rows, int N, int Dc, int T, float* mu,
+                           void* stream);
+/* Replaces `_stream_wave_chunks` + `crossfade` + the final concatenation (seed_vc_wrapper.py:201-285, inference.py:343-350,
+ * :507-527) for N chunk waveforms: wave[k * stride + i], i < lens[k] (samples at and above lens[k] are never read);
+ * first[k] / last[k] != 0 flag the first / last chunk of an utterance (an utterance's chunks are consecutive and in order);
+ * fade_in / fade_out [ov]: the caller's cos^2 windows (double, device), as svc_crossfade takes them.  With
+ * body[k] = lens[k] - (last[k] ? 0 : ov) and off[k] the sum of the bodies before k, for i < body[k]:
+ *   out[off[k] + i] = wave[k][i]                                                               first[k] or i >= ov
+ *                   = float(double(wave[k][i]) * fade_in[i] + double(wave[k-1][lens[k-1] - ov + i]) * fade_out[i])   otherwise
+ * with the products and the sum rounded separately (svc_crossfade's arithmetic, bit-identical to numpy's); a last chunk
+ * shorter than ov is the `len(chunk2) < overlap` branch of `crossfade`.  Each output sample is written exactly once, the
+ * utterances follow each other in `out`.  0 <= lens[k] <= stride; lens[k] >= ov unless last[k]; first[0] and last[N-1]
+ * set, first[k] set exactly when last[k-1] is; out_len == sum(body); ov >= 0. */
+int svc_chunks_assemble(const float* wave, long long stride, const int32_t* lens, const int32_t* first, const int32_t* last, int N,
+                        const double* fade_in, const double* fade_out, int ov, float* out, long long out_len, void* stream);
+
 /* ---------------------------------------------------------------- op-level entry points (parity tests) */
 /* C[M][N] (fp32) = A[M][K] * W[N][K]^T + bias ; dtype 0: operands rounded to fp16, 1: fp32 MFMA. */
 int svc_op_linear(const float* a, const float* w, const float* bias, float* c, int M, int N, int K, int dtype,

@@ -321,6 +321,80 @@ __global__ __launch_bounds__(256) void mel_strip_prompt_kernel(const float* __re
     }
 }
 
+
+// ---- long-form conversion as a pool of chunks (inference.py:470-527 with the chunks of one or more files run side by side).
+constexpr int CHUNK_MAXN = RAG_MAXB;
+struct GatherChunks { int P[CHUNK_MAXN], utt[CHUNK_MAXN], row0[CHUNK_MAXN], rows[CHUNK_MAXN]; };
+
+// mu[k][t][:] = t < P_u ? prompt_cond[u][t] : t < P_u + rows[k] ? cond[row0[k] + t - P_u] : 0 (u = utt[k]).  Windows overlap
+// in the source, so some rows of cond are read by two chunks.  VT = float4v (Dc % 4 == 0) or float.
+template <class VT>
+__global__ __launch_bounds__(256) void chunks_gather_cond_kernel(const VT* __restrict__ prompt_cond, const VT* __restrict__ cond,
+                                                                 const GatherChunks ch, int Pmax, int Dv, int T, VT* __restrict__ mu) {
+    const int k = blockIdx.y;
+    const int P = ch.P[k], S = ch.rows[k];
+    const VT* pc = prompt_cond + (long)ch.utt[k] * Pmax * Dv;
+    const VT* cd = cond + (long)ch.row0[k] * Dv;
+    const long n = (long)T * Dv;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const int t = (int)(i / Dv);
+        VT v = {};
+        if (t < P) v = pc[i];
+        else if (t < P + S) v = cd[i - (long)P * Dv];
+        mu[(long)k * n + i] = v;
+    }
+}
+
+struct AssembleChunks {
+    long long off[CHUNK_MAXN];      // first output sample of the chunk's body
+    int len[CHUNK_MAXN], body[CHUNK_MAXN];
+    int prev_len[CHUNK_MAXN];       // samples of the chunk before it in the same utterance, -1 for a first chunk
+};
+
+// out[off[k] + i] = wave[k][i] for a first chunk or i >= ov, else float(double(wave[k][i]) * fade_in[i] +
+// double(wave[k-1][len[k-1] - ov + i]) * fade_out[i]) with separately rounded products and sum (crossfade_kernel's
+// arithmetic), i < body[k].  Each output sample is written once; no sample at or above len[k] is read.  `wave` points at
+// row k0 of the wave buffer (blockIdx.y = 0), so row k - 1 of the launch's first chunk lies before it.  VEC: 4 samples per
+// thread (the caller has checked that ov, every len and off, the row stride and the pointers are multiples of 4 floats).
+template <bool VEC>
+__global__ __launch_bounds__(256) void chunks_assemble_kernel(const float* __restrict__ wave, long stride, const AssembleChunks ch,
+                                                              const double* __restrict__ fin, const double* __restrict__ fout, int ov,
+                                                              float* __restrict__ out) {
+    constexpr int W = VEC ? 4 : 1;
+    const int k = blockIdx.y;
+    const int body = ch.body[k], prev_len = ch.prev_len[k];
+    const float* cur = wave + (long)k * stride;
+    float* dst = out + ch.off[k];
+    const int n_fade = prev_len < 0 ? 0 : ov;
+    for (long g = (long)blockIdx.x * 256 + threadIdx.x; g * W < body; g += (long)gridDim.x * 256) {
+        const int i0 = (int)g * W;
+        float v[W];
+        if constexpr (VEC) {
+            const float4v x = *reinterpret_cast<const float4v*>(cur + i0);
+            v[0] = x[0]; v[1] = x[1]; v[2] = x[2]; v[3] = x[3];
+        } else {
+            v[0] = cur[i0];
+        }
+        if (i0 < n_fade) {           // ov is a multiple of W: the whole group lies inside the seam
+            const float* tail = cur - stride + (prev_len - ov);      // prev_len >= ov: that chunk is not its utterance's last
+            float p[W];
+            if constexpr (VEC) {
+                const float4v x = *reinterpret_cast<const float4v*>(tail + i0);
+                p[0] = x[0]; p[1] = x[1]; p[2] = x[2]; p[3] = x[3];
+            } else {
+                p[0] = tail[i0];
+            }
+#pragma unroll
+            for (int j = 0; j < W; ++j) {
+                const double a = __dmul_rn((double)v[j], fin[i0 + j]);
+                const double b = __dmul_rn((double)p[j], fout[i0 + j]);
+                v[j] = (float)__dadd_rn(a, b);
+            }
+        }
+        if constexpr (VEC) *reinterpret_cast<float4v*>(dst + i0) = (float4v){v[0], v[1], v[2], v[3]};
+        else dst[i0] = v[0];
+    }
+}
 }  // namespace
 
 extern "C" {
@@ -375,6 +449,87 @@ int svc_mel_strip_prompt(const float* mel, const int32_t* prompt_lens, const int
         float* o = out + (long)b0 * C * Smax;
         if (vec) hipLaunchKernelGGL(mel_strip_prompt_kernel<true>, dim3(gx, nb), dim3(256), 0, (hipStream_t)stream, src, l, C, T, Smax, pad_value, o);
         else hipLaunchKernelGGL(mel_strip_prompt_kernel<false>, dim3(gx, nb), dim3(256), 0, (hipStream_t)stream, src, l, C, T, Smax, pad_value, o);
+        SVC_CHECK_HIP(hipGetLastError());
+    }
+    return 0;
+}
+
+int svc_chunks_gather_cond(const float* prompt_cond, const int32_t* prompt_lens, int U, int Pmax, const float* cond, int R,
+                           const int32_t* utt, const int32_t* row0, const int32_t* rows, int N, int Dc, int T, float* mu,
+                           void* stream) {
+    SVC_REQUIRE(U >= 0 && Pmax >= 0 && R >= 0 && N >= 0 && Dc >= 1 && T >= 0, "chunks_gather_cond: bad argument");
+    if (N == 0 || T == 0) return 0;
+    SVC_REQUIRE(mu && prompt_lens && utt && row0 && rows && (prompt_cond || Pmax == 0) && (cond || R == 0),
+                "chunks_gather_cond: null argument");
+    for (int u = 0; u < U; ++u)
+        SVC_REQUIRE(prompt_lens[u] >= 0 && prompt_lens[u] <= Pmax, "chunks_gather_cond: prompt_lens outside 0 .. Pmax");
+    for (int k = 0; k < N; ++k) {
+        SVC_REQUIRE(utt[k] >= 0 && utt[k] < U, "chunks_gather_cond: utt outside 0 .. U - 1");
+        SVC_REQUIRE(rows[k] >= 0 && row0[k] >= 0 && (long)row0[k] + rows[k] <= R,
+                    "chunks_gather_cond: a chunk's rows lie outside cond (0 .. R)");
+        SVC_REQUIRE((long)prompt_lens[utt[k]] + rows[k] <= T, "chunks_gather_cond: prompt + chunk frames above T");
+    }
+    const bool vec = Dc % 4 == 0 && (((uintptr_t)prompt_cond | (uintptr_t)cond | (uintptr_t)mu) & 15) == 0;
+    const int Dv = vec ? Dc / 4 : Dc;
+    const int gx = (int)std::min<long>(cdiv((long)T * Dv, 256), 4096);
+    for (int k0 = 0; k0 < N; k0 += CHUNK_MAXN) {
+        const int nk = std::min(N - k0, CHUNK_MAXN);
+        GatherChunks ch;
+        memset(&ch, 0, sizeof(ch));
+        for (int k = 0; k < nk; ++k) {
+            ch.utt[k] = utt[k0 + k]; ch.P[k] = prompt_lens[utt[k0 + k]]; ch.row0[k] = row0[k0 + k]; ch.rows[k] = rows[k0 + k];
+        }
+        float* o = mu + (long)k0 * T * Dc;
+        if (vec)
+            hipLaunchKernelGGL(chunks_gather_cond_kernel<float4v>, dim3(gx, nk), dim3(256), 0, (hipStream_t)stream,
+                               reinterpret_cast<const float4v*>(prompt_cond), reinterpret_cast<const float4v*>(cond), ch, Pmax, Dv, T,
+                               reinterpret_cast<float4v*>(o));
+        else
+            hipLaunchKernelGGL(chunks_gather_cond_kernel<float>, dim3(gx, nk), dim3(256), 0, (hipStream_t)stream, prompt_cond, cond, ch,
+                               Pmax, Dv, T, o);
+        SVC_CHECK_HIP(hipGetLastError());
+    }
+    return 0;
+}
+
+int svc_chunks_assemble(const float* wave, long long stride, const int32_t* lens, const int32_t* first, const int32_t* last, int N,
+                        const double* fade_in, const double* fade_out, int ov, float* out, long long out_len, void* stream) {
+    SVC_REQUIRE(N >= 0 && ov >= 0 && out_len >= 0 && stride >= 0, "chunks_assemble: bad argument");
+    SVC_REQUIRE(N == 0 || (lens && first && last), "chunks_assemble: null argument");
+    long long total = 0;
+    int max_body = 0;
+    for (int k = 0; k < N; ++k) {
+        SVC_REQUIRE(lens[k] >= 0 && lens[k] <= stride, "chunks_assemble: a chunk length outside 0 .. stride");
+        SVC_REQUIRE(last[k] || lens[k] >= ov, "chunks_assemble: a chunk that is not the last of its utterance is shorter than the overlap");
+        SVC_REQUIRE(k == 0 ? first[k] != 0 : (first[k] != 0) == (last[k - 1] != 0),
+                    "chunks_assemble: first / last flags do not form consecutive utterances");
+        const int body = lens[k] - (last[k] ? 0 : ov);
+        max_body = std::max(max_body, body);
+        total += body;
+    }
+    SVC_REQUIRE(N == 0 || last[N - 1], "chunks_assemble: the last chunk is not flagged last");
+    SVC_REQUIRE(total == out_len, "chunks_assemble: out_len is not the sum of the chunk bodies");
+    if (out_len == 0) return 0;
+    SVC_REQUIRE(wave && out && (ov == 0 || (fade_in && fade_out)), "chunks_assemble: null argument");
+    bool vec = ov % 4 == 0 && stride % 4 == 0 && (((uintptr_t)wave | (uintptr_t)out) & 15) == 0;
+    for (int k = 0; k < N && vec; ++k) vec = lens[k] % 4 == 0;      // then every body, and so every offset, is one too
+    const int gx = (int)std::min<long>(cdiv(cdiv(max_body, vec ? 4 : 1), 256), 4096);
+    long long off = 0;
+    for (int k0 = 0; k0 < N; k0 += CHUNK_MAXN) {
+        const int nk = std::min(N - k0, CHUNK_MAXN);
+        AssembleChunks ch;
+        memset(&ch, 0, sizeof(ch));
+        for (int k = 0; k < nk; ++k) {
+            const int g = k0 + k;
+            ch.len[k] = lens[g];
+            ch.body[k] = lens[g] - (last[g] ? 0 : ov);
+            ch.prev_len[k] = first[g] ? -1 : lens[g - 1];
+            ch.off[k] = off;
+            off += ch.body[k];
+        }
+        const float* w = wave + (long long)k0 * stride;
+        if (vec) hipLaunchKernelGGL(chunks_assemble_kernel<true>, dim3(gx, nk), dim3(256), 0, (hipStream_t)stream, w, (long)stride, ch, fade_in, fade_out, ov, out);
+        else hipLaunchKernelGGL(chunks_assemble_kernel<false>, dim3(gx, nk), dim3(256), 0, (hipStream_t)stream, w, (long)stride, ch, fade_in, fade_out, ov, out);
         SVC_CHECK_HIP(hipGetLastError());
     }
     return 0;

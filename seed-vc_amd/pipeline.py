@@ -54,6 +54,48 @@ def chunk_plan(n_src, max_source_window, overlap_frame_len):
     return plan
 
 
+def long_batch_plan(n_srcs, prompt_lens, max_context_window, overlap_frame_len=16, hop=1, max_chunks=64):
+    """Chunk table of `HotPath.convert_long_batch` from lengths alone.  n_srcs[u] source frames and prompt_lens[u] prompt
+    frames per utterance.  Each utterance is cut by `chunk_plan(n_src, max_context_window - P_u, overlap_frame_len)`, the
+    chunks of all utterances are listed utterance-major:
+      chunks       [(utterance, first source frame, frames, is_first, is_last)]
+      bodies       [output samples chunk k contributes: (frames - (0 if is_last else overlap_frame_len)) * hop]
+      out_lens     [output samples of utterance u] (0 for an utterance without source frames: it has no chunks)
+      micro_batches[(k0, k1)]: consecutive ranges of at most `max_chunks` chunks, in plan order
+    ValueError where the drivers' loop would not terminate (an utterance that needs more than one chunk while its window
+    max_context_window - P_u does not exceed the overlap) and for max_chunks < 1."""
+    if max_chunks < 1:
+        raise ValueError(f"long_batch_plan: max_chunks = {max_chunks}, at least one chunk per micro-batch is needed")
+    if len(n_srcs) != len(prompt_lens):
+        raise ValueError("long_batch_plan: n_srcs and prompt_lens must have one entry per utterance")
+    chunks, bodies, out_lens = [], [], []
+    for u, (n_src, P) in enumerate(zip(n_srcs, prompt_lens)):
+        n_src, window = int(n_src), int(max_context_window) - int(P)
+        if n_src > window and window <= overlap_frame_len:
+            raise ValueError(f"long_batch_plan: utterance {u} has {n_src} source frames, a window of {window} frames "
+                             f"(max_context_window {max_context_window} - prompt {P}) and an overlap of {overlap_frame_len}: "
+                             f"the chunk loop would not advance")
+        total = 0
+        for k, (p0, s_len, is_last) in enumerate(chunk_plan(n_src, window, overlap_frame_len)):
+            chunks.append((u, p0, s_len, k == 0, is_last))
+            bodies.append((s_len - (0 if is_last else overlap_frame_len)) * hop)
+            total += bodies[-1]
+        out_lens.append(total)
+    micro = [(k0, min(k0 + max_chunks, len(chunks))) for k0 in range(0, len(chunks), max_chunks)]
+    return dict(chunks=chunks, bodies=bodies, out_lens=out_lens, micro_batches=micro)
+
+
+def _index_runs(members):
+    """[(a, b)]: the sorted indices `members` as consecutive ranges a .. b - 1 (slices need no index tensor on the device)."""
+    runs = []
+    for i in members:
+        if runs and runs[-1][1] == i:
+            runs[-1][1] = i + 1
+        else:
+            runs.append([i, i + 1])
+    return [tuple(r) for r in runs]
+
+
 class HotPath:
     """cfm: seedvc_amd.cfm.CFM ; vocoder: seedvc_amd.vocoder.BigVGAN | HiFT."""
 
@@ -153,6 +195,131 @@ class HotPath:
         torch.cuda.current_stream(dev).synchronize()
         del keep
         return out[None, :]
+
+    @torch.inference_mode()
+    def convert_long_batch(self, utterances, n_timesteps, inference_cfg_rate, hop, max_context_window, overlap_frame_len=16,
+                           noise_fn=None, vocoder_kwargs_fn=None, max_chunks=64, ragged_vocoder=None):
+        """Long-form conversion of one or more files with every chunk in ONE pool: a chunk reads the source, its file's
+        prompt and fresh noise, never its neighbour, so the chunks of all files go through the sampler and the vocoder as
+        ragged batches of up to `max_chunks` chunks, and one launch cross-fades and concatenates them (`svc_chunks_assemble`:
+        the reference's float64 arithmetic, bit for bit).
+
+        utterances: list of (cond (1, n_src, Dc), prompt_condition (1, P, Dc), mel2 (1, C, P), style2 (1, Ds)), the
+        arguments of `convert_long_device`, one tuple per file.  -> list of (1, L_u) tensors (views of one buffer); per
+        file the chunk boundaries (`chunk_plan`), the cross-fade and the length of the drivers' loop run on it alone.  A file
+        without source frames gives (1, 0).
+
+        Per micro-batch (`long_batch_plan`, plan order = utterance-major): `svc_chunks_gather_cond` -> one `cfm.inference`
+        with per-row x_lens / prompt_lens -> `svc_mel_strip_prompt` (padding = the log-mel floor) -> the vocoder -> rows of
+        one wave buffer.  Seams are resolved once, after the last micro-batch, so a seam may cross micro-batches.
+        ragged_vocoder: None = one `vocoder(mel, lens=...)` call if the vocoder is a `BigVGAN`, else one plain call per
+        distinct chunk length (a file has at most two: full windows and its last chunk); True / False force it (a
+        micro-batch of one length is one plain call either way).  vocoder_kwargs_fn(S) -> dict of tensors with a leading
+        batch axis of 1 (HiFT's pinned draws) is called once per chunk in plan order and concatenated per length group; it
+        cannot be combined with the ragged call.
+        noise_fn(T_k) -> (1, C, T_k) is called once per chunk in plan order with T_k = P_u + frames, the calls of the
+        sequential loops.  With noise_fn=None the noise is one torch.randn per micro-batch: the same distribution, NOT the
+        stream of draws the sequential loops consume.  One host synchronisation, at the end."""
+        import ctypes as C
+        from . import _lib
+        if ragged_vocoder is None:
+            from .vocoder import BigVGAN
+            ragged_vocoder = isinstance(self.vocoder, BigVGAN)
+        if ragged_vocoder and vocoder_kwargs_fn is not None:
+            raise ValueError("convert_long_batch: vocoder_kwargs_fn pins per-chunk draws of a plain vocoder call; "
+                             "it cannot be combined with the ragged vocoder call")
+        U = len(utterances)
+        if U == 0:
+            return []
+        for u, (cond, pc, mel2, style2) in enumerate(utterances):
+            if pc.size(1) != mel2.size(2):
+                raise ValueError(f"convert_long_batch: utterance {u}: prompt_condition has {pc.size(1)} frames, mel2 {mel2.size(2)}")
+        P = [int(t[2].size(2)) for t in utterances]
+        n_src = [int(t[0].size(1)) for t in utterances]
+        plan = long_batch_plan(n_src, P, max_context_window, overlap_frame_len, hop, max_chunks)
+        chunks, out_lens = plan["chunks"], plan["out_lens"]
+        dev = utterances[0][0].device
+        ovw = overlap_frame_len * hop
+        i32 = lambda v: (C.c_int32 * len(v))(*v)                                                    # noqa: E731
+        with torch.cuda.device(dev):
+            out = torch.empty(sum(out_lens), device=dev, dtype=torch.float32)
+            offs = [sum(out_lens[:u]) for u in range(U)]
+            result = [out[o:o + n][None, :] for o, n in zip(offs, out_lens)]
+            if not chunks:
+                return result
+            N = len(chunks)
+            Pmax, Dc, Cm = max(P), utterances[0][0].size(2), utterances[0][2].size(1)
+            # the utterances' tensors, stacked once: condition rows along time, prompts padded to Pmax
+            cond_all = torch.cat([_lib.f32c(t[0], dev)[0] for t in utterances])
+            row_base = [sum(n_src[:u]) for u in range(U)]
+            pc_all = torch.zeros(U, Pmax, Dc, device=dev)
+            mel_all = torch.zeros(U, Cm, Pmax, device=dev)
+            for u, (_, pc, mel2, _) in enumerate(utterances):
+                pc_all[u, :P[u]] = pc[0]
+                mel_all[u, :, :P[u]] = mel2[0]
+            style_all = torch.cat([_lib.f32c(t[3], dev) for t in utterances])
+            utt = [c[0] for c in chunks]
+            if U > 1:
+                idx = torch.tensor(utt, device=dev)
+                mel_chunks, style_chunks = mel_all.index_select(0, idx), style_all.index_select(0, idx)
+            else:
+                mel_chunks, style_chunks = mel_all.expand(N, -1, -1), style_all.expand(N, -1)
+            fade_out = torch.from_numpy(np.cos(np.linspace(0, np.pi / 2, ovw)) ** 2).to(dev)
+            fade_in = torch.from_numpy(np.cos(np.linspace(np.pi / 2, 0, ovw)) ** 2).to(dev)
+            stride = max(c[2] for c in chunks) * hop
+            waves = torch.empty(N, stride, device=dev, dtype=torch.float32)      # row k: chunk k's waveform, lens[k] samples
+            for k0, k1 in plan["micro_batches"]:
+                mb = chunks[k0:k1]
+                n = k1 - k0
+                S = [c[2] for c in mb]
+                Pk = [P[c[0]] for c in mb]
+                x_lens = [p + s for p, s in zip(Pk, S)]
+                T, Smax = max(x_lens), max(S)
+                mu = torch.empty(n, T, Dc, device=dev)
+                _lib.check(_lib.lib().svc_chunks_gather_cond(_lib.ptr(pc_all), i32(P), U, Pmax, _lib.ptr(cond_all), cond_all.size(0),
+                                                             i32([c[0] for c in mb]), i32([row_base[c[0]] + c[1] for c in mb]),
+                                                             i32(S), n, Dc, T, _lib.ptr(mu), _lib.stream_ptr()))
+                z = None
+                if noise_fn is not None:
+                    z = torch.zeros(n, Cm, T, device=dev)
+                    for i, t_k in enumerate(x_lens):
+                        z[i, :, :t_k] = noise_fn(t_k)[0]
+                kws = [vocoder_kwargs_fn(s) for s in S] if vocoder_kwargs_fn is not None else None
+                mel = self.cfm.inference(mu, x_lens, mel_chunks[k0:k1], style_chunks[k0:k1], None, n_timesteps,
+                                         inference_cfg_rate=inference_cfg_rate, z=z, prompt_lens=Pk)
+                mel = _lib.f32c(mel, dev)
+                vc = torch.empty(n, Cm, Smax, device=dev)
+                _lib.check(_lib.lib().svc_mel_strip_prompt(_lib.ptr(mel), i32(Pk), i32(x_lens), n, Cm, T, Smax,
+                                                           C.c_float(LOG_MEL_FLOOR), _lib.ptr(vc), _lib.stream_ptr()))
+                groups = group_by_length(S)
+                if ragged_vocoder and len(groups) > 1:
+                    self._store_waves(waves, [(k0, k1)], self.vocoder(vc, lens=S), Smax * hop)
+                else:
+                    for s_len, members in groups.items():
+                        runs = _index_runs(members)
+                        m = vc if len(members) == n and s_len == Smax else \
+                            torch.cat([vc[a:b, :, :s_len] for a, b in runs]).contiguous()
+                        kw = {key: torch.cat([kws[i][key] for i in members]) for key in kws[members[0]]} if kws else {}
+                        self._store_waves(waves, [(k0 + a, k0 + b) for a, b in runs], self.vocoder(m, **kw), s_len * hop)
+            lens = [c[2] * hop for c in chunks]
+            _lib.check(_lib.lib().svc_chunks_assemble(_lib.ptr(waves), C.c_longlong(stride), i32(lens), i32([int(c[3]) for c in chunks]),
+                                                      i32([int(c[4]) for c in chunks]), N, _lib.ptr(fade_in), _lib.ptr(fade_out), ovw,
+                                                      _lib.ptr(out), C.c_longlong(out.numel()), _lib.stream_ptr()))
+            torch.cuda.current_stream(dev).synchronize()
+        return result
+
+    @staticmethod
+    def _store_waves(waves, row_ranges, wave, n_samples):
+        """Rows of a vocoder call -> rows row_ranges of the chunk wave buffer (slices: no index tensor, no synchronisation)."""
+        n_rows = sum(b - a for a, b in row_ranges)
+        wave = wave.reshape(n_rows, -1)
+        if wave.size(1) != n_samples:
+            raise ValueError(f"convert_long_batch: the vocoder gave {wave.size(1)} samples per row, {n_samples} expected "
+                             f"(frames x hop)")
+        j = 0
+        for a, b in row_ranges:
+            waves[a:b, :n_samples].copy_(wave[j:j + b - a])
+            j += b - a
 
 
 # ----------------------------------------------------------------------------------------- v2: tokens in, audio out
