@@ -355,6 +355,27 @@ int svc_chunks_gather_cond(const float* prompt_cond, const int32_t* prompt_lens,
 int svc_chunks_assemble(const float* wave, long long stride, const int32_t* lens, const int32_t* first, const int32_t* last, int N,
                         const double* fade_in, const double* fade_out, int ov, float* out, long long out_len, void* stream);
 
+/* ---------------------------------------------------------------- real-time sessions: the SOLA splice of one block step
+ * Replaces the SOLA lines of the reference GUI's audio callback (real-time-gui.py, `audio_callback`: two conv1d, an argmax,
+ * a slice at a device-resident index, the fade and the buffer update; restated from memory) for N streams in one call, with
+ * the conventions of the assembly calls above: `slots` is HOST int32 [N] and is consumed before the call returns (kernel
+ * arguments, one launch per 64 streams), arguments are checked before anything is launched, nothing synchronises, copies
+ * or allocates on the device.
+ *
+ * Row k of `wave` (wave[k * stride + i]) is the vocoder output of stream slots[k]; x = wave[k] + start; b = row slots[k]
+ * of sola_state [max_slots][Lb], read and written in place; fade_in / fade_out [Lb]: the caller's windows (float, device).
+ *   score[o] = sum_{i<Lb} x[o+i] b[i] / sqrt(sum_{i<Lb} x[o+i]^2 + 1e-8)         o = 0 .. Ls, fp32, each sum from its own terms
+ *   o*       = the lowest o with the highest score (an all-zero buffer gives 0);   offsets[k] = o*  (offsets may be NULL)
+ *   y[i]     = float(float(x[o*+i] * fade_in[i]) + float(b[i] * fade_out[i]))  i < Lb;   y[i] = x[o*+i]  Lb <= i < block + Lb
+ *   out[k][i] = y[i], i < block;   sola_state[slots[k]][i] = y[block + i], i < Lb   (the faded samples where block < Lb)
+ * No sample at or above start + block + Lb + Ls of a row is read; rows of sola_state that no slot names are not touched.
+ * N >= 0 (N == 0: success, no pointer is looked at), block >= 1, Lb >= 1, Ls >= 0, start >= 0,
+ * start + block + Lb + Ls <= stride, 2 * Lb + Ls <= 16128 (the search is staged in LDS), 0 <= slots[k] < max_slots, no slot
+ * twice in one call. */
+int svc_sola_step(const float* wave, long long stride, int start, int N, float* sola_state, int max_slots, const int32_t* slots,
+                  const float* fade_in, const float* fade_out, int block, int Lb, int Ls, float* out, int32_t* offsets,
+                  void* stream);
+
 /* ---------------------------------------------------------------- op-level entry points (parity tests) */
 /* C[M][N] (fp32) = A[M][K] * W[N][K]^T + bias ; dtype 0: operands rounded to fp16, 1: fp32 MFMA. */
 int svc_op_linear(const float* a, const float* w, const float* bias, float* c, int M, int N, int K, int dtype,

@@ -22,7 +22,7 @@ EXPORTS = [
     "svc_ar_set_max_batch", "svc_ar_prefill_slot", "svc_ar_decode_step_batch", "svc_ar_generate_batch",
     "svc_ar_generate_batch_seeded", "svc_ar_exp_draws", "svc_v2_assemble_cond", "svc_mel_strip_prompt",
     "svc_lr_create", "svc_lr_destroy", "svc_lr_forward", "svc_crossfade",
-    "svc_chunks_gather_cond", "svc_chunks_assemble",
+    "svc_chunks_gather_cond", "svc_chunks_assemble", "svc_sola_step",
     "svc_campplus_create", "svc_campplus_destroy", "svc_campplus_forward", "svc_kaldi_fbank_frames", "svc_kaldi_fbank",
     "svc_mel_create", "svc_mel_destroy", "svc_mel_frames", "svc_mel_forward",
     "svc_prof_enable", "svc_prof_collect",
@@ -97,6 +97,8 @@ def lib():
         l.svc_last_error.restype = C.c_char_p
         if l.svc_abi_version() != 1:
             raise ImportError("libseedvc_hip.so ABI version mismatch")
+        l.svc_sola_step.argtypes = [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int32),
+                                    C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = l
     return _lib
 

@@ -492,6 +492,194 @@ class V2HotPath:
         return out
 
 
+# ----------------------------------------------------------------------------------------- real-time sessions
+def realtime_geometry(sr, hop, block_time, crossfade_time, extra_time, extra_time_right, ce_dit_difference):
+    """The integer geometry of the reference GUI (real-time-gui.py: `start_vc` and `custom_infer`, quoted from memory:
+    correct it here if the reference differs).  Every time is rounded to a multiple of zc = sr // 50 samples;
+    Lb = min(crossfade_frame, 4 * zc), Ls = zc; skip_head / skip_tail / return_length count 20 ms units; the length
+    regulator is asked for S = int((skip_head + return_length + skip_tail - int(ce_dit_difference * 50)) / 50 * sr // hop)
+    mel frames and the GUI keeps `vc_wave[-(block + Lb + Ls) - tail : -tail]` of the S * hop samples, tail = skip_tail * sr // 50.
+    -> dict(S, block, Lb, Ls, tail, start, n_inf, skip_head, skip_tail, return_length): the arguments of `RealtimeEngine`.
+    ValueError where the S * hop samples do not hold n_inf + tail."""
+    zc = sr // 50
+    to_frame = lambda t: int(round(t * sr / zc)) * zc                                              # noqa: E731
+    block, crossfade_frame = to_frame(block_time), to_frame(crossfade_time)
+    Lb, Ls = min(crossfade_frame, 4 * zc), zc
+    skip_head, skip_tail = to_frame(extra_time) // zc, to_frame(extra_time_right) // zc
+    return_length = (block + Lb + Ls) // zc
+    S = int((skip_head + return_length + skip_tail - int(ce_dit_difference * 50)) / 50 * sr // hop)
+    tail = skip_tail * sr // 50
+    n_inf = block + Lb + Ls
+    if block < 1 or Lb < 1 or n_inf + tail > S * hop:
+        raise ValueError(f"realtime_geometry: block {block}, sola buffer {Lb}, search {Ls} and tail {tail} samples do not fit "
+                         f"the {S} x {hop} samples of a step")
+    return dict(S=S, block=block, Lb=Lb, Ls=Ls, tail=tail, start=S * hop - tail - n_inf, n_inf=n_inf, skip_head=skip_head,
+                skip_tail=skip_tail, return_length=return_length)
+
+
+def gui_fade_windows(Lb):
+    """(fade_in, fade_out) of the reference GUI: sin(0.5 pi linspace(0, 1, Lb))^2 and 1 - fade_in, float32, computed on the
+    host.  The engine takes its windows as arrays because device and host `sin` differ in the last bit."""
+    fade_in = torch.sin(0.5 * np.pi * torch.linspace(0.0, 1.0, steps=Lb, dtype=torch.float32)) ** 2
+    return fade_in, 1 - fade_in
+
+
+class RealtimeEngine:
+    """Block-by-block conversion of up to `max_streams` independent streams, one engine step per block: the reference GUI's
+    `custom_infer` plus the SOLA splice of its `audio_callback` (real-time-gui.py, restated from memory: correct it here if
+    the reference differs).  Per stream, given content features x (1, Tin, Din):
+
+        cond  = length_regulator(x, ylens=[S], n_quantizers=3, f0=None)[0]
+        mel   = cfm.inference(cat([prompt_condition, cond], 1), [P + S], mel2, style2, None, n_timesteps, cfg_rate)[:, :, P:]
+        wave  = vocoder(mel).reshape(-1)                                    # S * hop samples
+        infer = wave[start : start + n_inf]                                 # = vc_wave[-n_inf - tail : -tail]
+        o*    = argmax_o <infer[o : o + Lb], sola_buffer> / sqrt(|infer[o : o + Lb]|^2 + 1e-8),  o = 0 .. Ls
+        y     = infer[o*:];  y[:Lb] = y[:Lb] * fade_in + sola_buffer * fade_out
+        sola_buffer = y[block : block + Lb];  output = y[:block]
+
+    with n_inf = block + Lb + Ls and start = S * hop - tail - n_inf.  The geometry (host integers, `realtime_geometry`) is
+    shared by the streams of an engine; each stream has its own reference (`open`) and its own SOLA buffer, a row of one
+    device tensor.  A step is six enqueues -- length regulator, `svc_v2_assemble_cond` (ragged prompts), one `cfm.inference`
+    with prompt_lens, `svc_mel_strip_prompt`, one plain vocoder call (every row has S frames), `svc_sola_step` -- from host
+    integers only: nothing synchronises, and the data-dependent offset never leaves the device.
+
+    length_regulator: seedvc_amd.length_regulator.InterpolateRegulator (v1); cfm: seedvc_amd.cfm.CFM; vocoder: HiFT | BigVGAN
+    with S * hop samples per row; fade_in / fade_out: (Lb,) float32 windows (default: `gui_fade_windows`)."""
+
+    def __init__(self, length_regulator, cfm, vocoder, S, hop, block, sola_buffer, sola_search, tail=0, max_streams=64,
+                 fade_in=None, fade_out=None):
+        S, hop, block, Lb, Ls, tail = (int(v) for v in (S, hop, block, sola_buffer, sola_search, tail))
+        if block < 1 or Lb < 1 or Ls < 0 or tail < 0 or max_streams < 1:
+            raise ValueError("RealtimeEngine: block, sola_buffer and max_streams must be at least 1, sola_search and tail at least 0")
+        n_inf = block + Lb + Ls
+        if n_inf + tail > S * hop:
+            raise ValueError(f"RealtimeEngine: block + sola_buffer + sola_search + tail = {n_inf + tail} samples, a step gives "
+                             f"{S} x {hop}")
+        if (fade_in is None) != (fade_out is None):
+            raise ValueError("RealtimeEngine: give both windows or neither")
+        self.length_regulator, self.cfm, self.vocoder = length_regulator, cfm, vocoder
+        self.S, self.hop, self.block, self.Lb, self.Ls, self.tail = S, hop, block, Lb, Ls, tail
+        self.n_inf, self.start, self.max_streams = n_inf, S * hop - tail - n_inf, int(max_streams)
+        self.device = cfm.device
+        if fade_in is None:
+            fade_in, fade_out = gui_fade_windows(Lb)
+        from . import _lib
+        self.fade_in, self.fade_out = (_lib.f32c(torch.as_tensor(f), self.device).reshape(-1) for f in (fade_in, fade_out))
+        if self.fade_in.numel() != Lb or self.fade_out.numel() != Lb:
+            raise ValueError(f"RealtimeEngine: the windows must have sola_buffer = {Lb} entries")
+        self.state = torch.zeros(self.max_streams, Lb, device=self.device, dtype=torch.float32)      # row = a stream's sola_buffer
+        self._streams = {}                  # slot -> dict(prompt_condition, mel, style, P)
+        self._stacked = (None, None)
+
+    def open(self, prompt_condition, mel2, style2):
+        """A new stream on the reference (prompt_condition (1, P, Dc), mel2 (1, C, P), style2 (1, Ds)) -> its slot, the
+        lowest free one; its SOLA buffer starts from zeros."""
+        from . import _lib
+        if prompt_condition.dim() != 3 or mel2.dim() != 3 or style2.dim() != 2 or prompt_condition.size(0) != 1 or \
+                mel2.size(0) != 1 or style2.size(0) != 1 or prompt_condition.size(1) != mel2.size(2):
+            raise ValueError(f"RealtimeEngine.open: prompt_condition {tuple(prompt_condition.shape)}, mel2 {tuple(mel2.shape)} and "
+                             f"style2 {tuple(style2.shape)} are not (1, P, Dc), (1, C, P), (1, Ds)")
+        for s in self._streams.values():
+            if s["prompt_condition"].size(2) != prompt_condition.size(2) or s["mel"].size(1) != mel2.size(1) or \
+                    s["style"].size(1) != style2.size(1):
+                raise ValueError("RealtimeEngine.open: Dc, C or Ds differ from the streams already open")
+        slot = next((i for i in range(self.max_streams) if i not in self._streams), None)
+        if slot is None:
+            raise ValueError(f"RealtimeEngine.open: all {self.max_streams} slots are in use")
+        dev = self.device
+        self._streams[slot] = dict(prompt_condition=_lib.f32c(prompt_condition, dev), mel=_lib.f32c(mel2, dev),
+                                   style=_lib.f32c(style2, dev), P=int(mel2.size(2)))
+        self._stacked = (None, None)
+        self.state[slot].zero_()
+        return slot
+
+    def _check_slot(self, slot, what):
+        if not 0 <= slot < self.max_streams:
+            raise ValueError(f"RealtimeEngine.{what}: slot {slot!r} outside 0 .. {self.max_streams - 1}")
+        if slot not in self._streams:
+            raise ValueError(f"RealtimeEngine.{what}: slot {slot} is not open")
+
+    def close(self, slot):
+        self._check_slot(slot, "close")
+        del self._streams[slot]
+        self._stacked = (None, None)
+
+    def reset(self, slot):
+        """Zeroes the stream's SOLA buffer (the GUI does so when a stream restarts)."""
+        self._check_slot(slot, "reset")
+        self.state[slot].zero_()
+
+    def _stack_prompts(self, slots):
+        """Padded batch tensors of the streams' references (kept while the same slots come back in the same order)."""
+        key = tuple(slots)
+        if self._stacked[0] == key:
+            return self._stacked[1]
+        dev, n = self.device, len(slots)
+        recs = [self._streams[s] for s in slots]
+        Pmax = max(r["P"] for r in recs)
+        pc = torch.zeros(n, Pmax, recs[0]["prompt_condition"].size(2), device=dev)
+        mel = torch.zeros(n, recs[0]["mel"].size(1), Pmax, device=dev)
+        for b, r in enumerate(recs):
+            pc[b, :r["P"]] = r["prompt_condition"][0]
+            mel[b, :, :r["P"]] = r["mel"][0]
+        st = dict(prompt_condition=pc, mel=mel, style=torch.cat([r["style"] for r in recs]), Pmax=Pmax, P=[r["P"] for r in recs])
+        self._stacked = (key, st)
+        return st
+
+    @torch.inference_mode()
+    def step(self, slots, content, n_timesteps, inference_cfg_rate, z=None, vocoder_kwargs=None, return_parts=False):
+        """One block for the streams `slots` (a list of open slots, no slot twice); content (n, Tin, Din), row k for
+        slots[k]; z: the sampler's noise (n, C, Pmax + S), torch.randn when None; vocoder_kwargs: passed to the vocoder call
+        (HiFT's pinned draws).  -> (n, block) float32 on the device; with return_parts also
+        dict(mel (n, C, S), infer (n, n_inf), offsets (n,) int32)."""
+        import ctypes as C
+        from . import _lib
+        slots = [int(s) for s in slots]
+        for s in slots:
+            self._check_slot(s, "step")
+        if len(set(slots)) != len(slots):
+            raise ValueError(f"RealtimeEngine.step: a slot appears twice in {slots}")
+        n, dev, S = len(slots), self.device, self.S
+        if content.dim() != 3 or content.size(0) != n:
+            raise ValueError(f"RealtimeEngine.step: content {tuple(content.shape)} is not (n = {n}, Tin, Din)")
+        if n == 0:
+            out = torch.zeros(0, self.block, device=dev)
+            parts = dict(mel=torch.zeros(0, self.cfm.in_channels, S, device=dev), infer=torch.zeros(0, self.n_inf, device=dev),
+                         offsets=torch.zeros(0, dtype=torch.int32, device=dev))
+            return (out, parts) if return_parts else out
+        i32 = lambda v: (C.c_int32 * len(v))(*v)                                                    # noqa: E731
+        with torch.cuda.device(dev):
+            st = self._stack_prompts(slots)
+            P, Pmax = st["P"], st["Pmax"]
+            cond = self.length_regulator(content, ylens=torch.LongTensor([S] * n), n_quantizers=3, f0=None)[0]   # (n, S, Dc)
+            cond = _lib.f32c(cond, dev)
+            if cond.size(1) != S:
+                raise ValueError(f"RealtimeEngine.step: the length regulator gave {cond.size(1)} frames, {S} expected")
+            Dc, Cm, T = cond.size(2), st["mel"].size(1), Pmax + S
+            mu = torch.empty(n, T, Dc, device=dev)
+            _lib.check(_lib.lib().svc_v2_assemble_cond(_lib.ptr(st["prompt_condition"]), i32(P), _lib.ptr(cond), i32([S] * n), n, Pmax, S,
+                                                       Dc, T, _lib.ptr(mu), _lib.stream_ptr()))
+            x_lens = [p + S for p in P]
+            mel = self.cfm.inference(mu, x_lens, st["mel"], st["style"], None, n_timesteps, inference_cfg_rate=inference_cfg_rate,
+                                     z=z, prompt_lens=P)
+            mel = _lib.f32c(mel, dev)
+            vc = torch.empty(n, Cm, S, device=dev)
+            _lib.check(_lib.lib().svc_mel_strip_prompt(_lib.ptr(mel), i32(P), i32(x_lens), n, Cm, T, S, C.c_float(LOG_MEL_FLOOR),
+                                                       _lib.ptr(vc), _lib.stream_ptr()))
+            wave = _lib.f32c(self.vocoder(vc, **(vocoder_kwargs or {})), dev).reshape(n, -1)
+            if wave.size(1) != S * self.hop:
+                raise ValueError(f"RealtimeEngine.step: the vocoder gave {wave.size(1)} samples per row, {S * self.hop} expected "
+                                 f"(frames x hop)")
+            out = torch.empty(n, self.block, device=dev)
+            offsets = torch.empty(n, dtype=torch.int32, device=dev) if return_parts else None
+            _lib.check(_lib.lib().svc_sola_step(_lib.ptr(wave), wave.size(1), self.start, n, _lib.ptr(self.state), self.max_streams,
+                                                i32(slots), _lib.ptr(self.fade_in), _lib.ptr(self.fade_out), self.block, self.Lb,
+                                                self.Ls, _lib.ptr(out), _lib.ptr(offsets), _lib.stream_ptr()))
+        if return_parts:
+            return out, dict(mel=vc, infer=wave[:, self.start:self.start + self.n_inf], offsets=offsets)
+        return out
+
+
 
 # ----------------------------------------------------------------------------------------- multi-GPU sharding
 def shard_range(n_items, rank, world_size):
