@@ -122,7 +122,7 @@ void svc_bigvgan_destroy(svc_bigvgan_t* m);
 /* Replaces `vocoder_fn(mel)` = BigVGAN.forward (modules/bigvgan/bigvgan.py:360-386).
  * mel [B][num_mels][S] -> out [B][1][S * prod(upsample_rates)]. */
 int svc_bigvgan_forward(svc_bigvgan_t* m, const float* mel, int B, int S, float* out, void* stream);
-/* The same for a batch of utterances of different lengths, in one call (BigVGAN only; HiFT has no such entry point).
+/* The same for a batch of utterances of different lengths, in one call (HiFT: svc_hift_forward_ragged below).
  * mel [B][num_mels][S]; lens HOST [B], 0 <= lens[b] <= S; out [B][1][S * up], up = prod(upsample_rates).
  * out[b][0][: lens[b] * up] is the waveform of mel[b][:, :lens[b]] run alone (its convs zero-pad and its anti-aliased
  * activations replicate at the utterance's own last frame); every sample at and above lens[b] * up is written as zero, and
@@ -159,6 +159,20 @@ void svc_hift_destroy(svc_hift_t* m);
  * f0_out (optional, [B][S]) receives the f0 actually used. */
 int svc_hift_forward(svc_hift_t* m, const float* mel, const float* f0, const float* phase0, const float* noise,
                      int B, int S, float* out, float* f0_out, void* stream);
+/* The same for a batch of utterances of different lengths, in one call (the contract of svc_bigvgan_forward_ragged).
+ * lens: HOST int32 [B], 0 <= lens[b] <= S, consumed before the call returns (pinned staging inside the handle: no host
+ * synchronisation in steady state).  mel [B][80][S]; f0 [B][S] or NULL; phase0 [B][nb_harmonics+1][1]; noise
+ * [B][nb_harmonics+1][S*up], of which row b uses the first lens[b]*up samples of each harmonic: the draws of the run alone.
+ * out[b][0 .. lens[b]*up) is the waveform of mel[b][:, :lens[b]] run alone through svc_hift_forward, bit for bit (an
+ * utterance runs the kernels it would run alone: micro-batches never mix utterances whose convs choose differently);
+ * out[b][lens[b]*up ..] and f0_out[b][lens[b] ..] (f0_out optional, [B][S]) are written as zero; lens[b] == 0 gives a zero
+ * row.  Mel frames, f0 values and noise samples at and above an utterance's end are never read as values (they may hold
+ * NaN): every conv bounds its operand load by the utterance's rows, the source stops at its last sample, and the STFT /
+ * iSTFT reflect and overlap-add at its own end.  Utterances run longest first in micro-batches
+ * (svc_hift_set_microbatch), each padded to its own longest member.  Errors (lens NULL or out of range, B < 1, S < 1)
+ * return non-zero with nothing enqueued. */
+int svc_hift_forward_ragged(svc_hift_t* m, const float* mel, const int32_t* lens, const float* f0, const float* phase0,
+                            const float* noise, int B, int S, float* out, float* f0_out, void* stream);
 /* Utterances per internal pass of the vocoders (0 = default 32); results do not depend on it. */
 int svc_bigvgan_set_microbatch(svc_bigvgan_t* m, int utterances);
 int svc_hift_set_microbatch(svc_hift_t* m, int utterances);

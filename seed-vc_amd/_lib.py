@@ -16,7 +16,7 @@ EXPORTS = [
     "svc_abi_version", "svc_last_error",
     "svc_dit_create", "svc_dit_destroy", "svc_dit_set_microbatch", "svc_dit_set_fused_min_rows", "svc_dit_fused_available", "svc_dit_set_graphs", "svc_cfm_sample", "svc_dit_forward",
     "svc_bigvgan_create", "svc_bigvgan_destroy", "svc_bigvgan_forward", "svc_bigvgan_forward_ragged", "svc_bigvgan_set_microbatch",
-    "svc_hift_create", "svc_hift_destroy", "svc_hift_forward", "svc_hift_set_microbatch",
+    "svc_hift_create", "svc_hift_destroy", "svc_hift_forward", "svc_hift_forward_ragged", "svc_hift_set_microbatch",
     "svc_anti_alias_act_fwd",
     "svc_ar_create", "svc_ar_destroy", "svc_ar_reset", "svc_ar_forward_generate", "svc_ar_decode_step", "svc_ar_sample", "svc_ar_generate",
     "svc_ar_set_max_batch", "svc_ar_prefill_slot", "svc_ar_decode_step_batch", "svc_ar_generate_batch",
@@ -99,6 +99,8 @@ def lib():
             raise ImportError("libseedvc_hip.so ABI version mismatch")
         l.svc_sola_step.argtypes = [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int32),
                                     C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        l.svc_hift_forward_ragged.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = l
     return _lib
 

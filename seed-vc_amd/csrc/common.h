@@ -60,7 +60,7 @@ struct DeviceState {
     void* zero_page = nullptr;
     // handles on different threads share this state (seedvc_hip.h: different handles may run concurrently): the flags are
     // atomics; setting an attribute twice is harmless (hipFuncSetAttribute is idempotent)
-    std::atomic<unsigned> kconv_attr{0};      // bit per kconv_kernel instantiation whose LDS attribute is set on this device
+    std::atomic<unsigned long long> kconv_attr{0};      // bit per kconv_kernel instantiation whose LDS attribute is set on this device
     std::atomic<bool> fused_attr{false};
 };
 DeviceState* device_state();      // state of the CURRENT device; nullptr on failure (error set)
@@ -195,6 +195,10 @@ struct KConvParams {
     const void* zero_page;
     int w8_exp;        // nsub == 2 ("fp16 + fp8 corrections"): log2 of the power-of-two scale the fp8 weight bytes carry
     int c16_lo_fmt;    // format of the c16_lo plane written by the epilogue: 0 = fp16 residual, 1 = fp8 pair (lo_pair_p8)
+    // ragged batches (needs Lin == Lout): device [B] valid rows per sequence.  Input rows at and above seq_len[b] read as the
+    // zero padding does (they are never loaded: they may hold NaN); position tiles that start there are skipped, so output
+    // rows at and above seq_len[b] hold anything.  null = every sequence has Lin rows (the uniform instantiations)
+    const int* seq_len;
 };
 bool kconv_enabled();
 int kconv_launch(const KConvParams& p, hipStream_t st);

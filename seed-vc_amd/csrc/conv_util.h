@@ -152,6 +152,8 @@ struct ConvRun {
     int act = KG_ACT_NONE; float act_slope = 0.f;
     int n_override = 0;                   // write only the first n columns (e.g. 1-channel output)
     const int* seq_len = nullptr;         // device [B]: valid input rows per sequence (ragged batches), else Lin
+    bool seq_kconv = false;               // with seq_len: the conv may take the resident-tile kernel's ragged form (HiFT's ragged
+                                          // call); otherwise a conv with seq_len runs on the tap-GEMM as it always has
     // fused pointwise Snake towards the next conv's operand planes (c16 = hi, c16_lo = lo); c32 keeps the raw value
     const float* post_a = nullptr; const float* post_ib = nullptr; int post_n = 0; half_t* c16_lo = nullptr;
     int c16_lo_fmt = 0;                   // format of the c16_lo plane: 0 fp16 residual, 1 fp8 byte pairs (the NEXT conv runs p8)
@@ -164,11 +166,14 @@ inline int kconv_min_n() {
     return v;
 }
 
+// shortest sequence (output rows) sent to the resident-tile kernel: the ONLY length-dependent kernel choice of the vocoders
+constexpr int KCONV_MIN_ROWS = 192;
+
 // A conv of a vd == 3 model runs as fp16 + fp8 corrections iff it has the second packing and its call takes the
 // resident-tile kernel: a layer / length property, never the batch's.  The producer of its operand planes asks the same
 // question to choose the lo-plane format.
 inline bool conv_p8_ok(const ConvW& w, int Lout, int dilation) {
-    return w.w8 != nullptr && kconv_enabled() && (w.k - 1) * dilation <= 64 && Lout >= 192 && w.cout_pad >= kconv_min_n() &&
+    return w.w8 != nullptr && kconv_enabled() && (w.k - 1) * dilation <= 64 && Lout >= KCONV_MIN_ROWS && w.cout_pad >= kconv_min_n() &&
            w.cout_pad % 8 == 0;
 }
 
@@ -212,7 +217,8 @@ inline int conv1d_run(const ConvW& w, const ConvRun& r, hipStream_t st) {
     // Long stride-1 convs with several taps keep their activation tile resident in LDS (kconv.hip).  The choice depends
     // on the layer and the sequence length only, never on the batch size, so batched and single runs stay bit-identical.
     const bool kconv_ok = kconv_enabled() && w.dtype == 0 && r.stride == 1 && w.k >= 3 && (w.k - 1) * r.dilation <= 64 &&
-                          r.pad_mode == KG_PAD_ZERO && !r.seq_len && !r.n_override && p.vec_ok && r.Lout >= 192 && w.cin_pad >= 64 &&
+                          r.pad_mode == KG_PAD_ZERO && (!r.seq_len || (r.seq_kconv && r.Lin == r.Lout)) && !r.n_override && p.vec_ok &&
+                          r.Lout >= KCONV_MIN_ROWS && w.cin_pad >= 64 &&
                           p.N >= kconv_min_n();
     // (a conv and the conv it feeds inside a residual stack have the same shape, so both take the same kernel: the tap-GEMM
     // epilogue never has to write byte pairs)
@@ -229,6 +235,7 @@ inline int conv1d_run(const ConvW& w, const ConvRun& r, hipStream_t st) {
         q.post_a = r.post_a; q.post_ib = r.post_ib; q.post_n = r.post_n;
         q.res = r.res; q.ldres = r.ldres; q.res2 = r.res2; q.ldres2 = r.ldres2;
         q.out_scale = r.out_scale; q.act = r.act; q.act_slope = r.act_slope;
+        q.seq_len = r.seq_len;
         return kconv_launch(q, st);
     }
     return kgemm_launch(p, w.dtype, KG_EPI_STORE, st);

@@ -38,7 +38,10 @@ constexpr int cb_lds(int bn, int bm) { return 2 * cb_a_bytes(bm) + cb_ns(bn, bm)
 // 2.5x on unaligned windows: PMC showed SQ_LDS_BANK_CONFLICT = 40 % of SQ_LDS_IDX_ACTIVE in this kernel with it.)
 __device__ __forceinline__ int cswz(int row) { return row & 7; }
 
-template <int NSUB, int BN, int BM>
+// RAGGED: per-sequence valid rows (KConvParams::seq_len).  The masking sits on the activation-tile load, where the zero padding
+// already is: one more bound on the row, no change to the main loop or the epilogue, and the fused Snake's operand planes need no
+// masked store (a masked producer would have to select, not multiply: the raw rows past an utterance's end may be NaN).
+template <int NSUB, int BN, int BM, bool RAGGED>
 __global__ __launch_bounds__(CB_NT, BM < 256 ? 2 : 1) void kconv_kernel(const KConvParams p) {
     constexpr int CB_N = BN, CB_M = BM;
     constexpr int CB_NS = cb_ns(BN, BM);
@@ -70,6 +73,11 @@ __global__ __launch_bounds__(CB_NT, BM < 256 ? 2 : 1) void kconv_kernel(const KC
     const int tile_m = rest % n_mt;
     const int b = rest / n_mt;
     const int p0 = tile_m * CB_M;                 // first output position of this workgroup
+    int lin = p.Lin;                              // valid input rows of this sequence
+    if constexpr (RAGGED) {
+        lin = p.seq_len[b];
+        if (p0 >= lin) return;                    // a tile of padding rows only (workgroup-uniform, before any barrier)
+    }
     const int n0 = tile_n * CB_N;
     const int span = (p.k - 1) * p.dil;
     const int R = CB_M + span;                    // tile rows in use
@@ -112,7 +120,7 @@ __global__ __launch_bounds__(CB_NT, BM < 256 ? 2 : 1) void kconv_kernel(const KC
         for (int i = 0; i * 64 < R; ++i) {
             const int row = rr + 64 * i;
             const int pos = p0 - p.pad_left + row;
-            const bool ok = (row < R) & (pos >= 0) & (pos < p.Lin);
+            const bool ok = (row < R) & (pos >= 0) & (pos < lin);
             const long off = (((long)b * p.Lin + (ok ? pos : 0)) * p.cin_pad + 64L * c + ((c8 ^ cswz(row)) << 3)) * 2;
             const char* sh = ok ? reinterpret_cast<const char*>(p.a_hi) + off : zero_;
             __builtin_amdgcn_global_load_lds((gptr_t)sh, (lptr_t)(a_hi + (64 * i + wave_u * 8) * 128), 16, 0, 0);
@@ -365,22 +373,24 @@ bool kconv_enabled() {
     return !off;
 }
 
-template <int NSUB, int BN, int BM>
+template <int NSUB, int BN, int BM, bool RAGGED>
 int kconv_go(DeviceState* ds, const KConvParams& p, int grid, hipStream_t st) {
     // per device and instantiation: the attribute lives in the device's code object
-    constexpr unsigned bit = 1u << ((NSUB == 3 ? 1 : (NSUB == 2 ? 2 : 0)) + 3 * ((BN == 64 ? 3 : 0) + (BM == 64 ? 0 : (BM == 128 ? 1 : 2))));
+    constexpr unsigned long long bit = 1ull << ((NSUB == 3 ? 1 : (NSUB == 2 ? 2 : 0)) + 3 * ((BN == 64 ? 3 : 0) + (BM == 64 ? 0 : (BM == 128 ? 1 : 2))) +
+                                                (RAGGED ? 18 : 0));
     if (!(ds->kconv_attr.load(std::memory_order_acquire) & bit)) {
-        SVC_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kconv_kernel<NSUB, BN, BM>), hipFuncAttributeMaxDynamicSharedMemorySize,
+        SVC_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kconv_kernel<NSUB, BN, BM, RAGGED>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                           cb_lds(BN, BM)));
         ds->kconv_attr.fetch_or(bit, std::memory_order_release);
     }
-    hipLaunchKernelGGL((kconv_kernel<NSUB, BN, BM>), dim3(grid), dim3(CB_NT), cb_lds(BN, BM), st, p);
+    hipLaunchKernelGGL((kconv_kernel<NSUB, BN, BM, RAGGED>), dim3(grid), dim3(CB_NT), cb_lds(BN, BM), st, p);
     SVC_CHECK_HIP(hipGetLastError());
     return 0;
 }
 
 int kconv_launch(const KConvParams& p_in, hipStream_t st) {
     SVC_REQUIRE(p_in.k >= 1 && (p_in.k - 1) * p_in.dil <= CB_SPAN && p_in.cin_pad % 64 == 0 && p_in.N % 8 == 0, "kconv shape");
+    SVC_REQUIRE(!p_in.seq_len || p_in.Lin == p_in.Lout, "kconv: per-sequence lengths need Lin == Lout");
     DeviceState* ds = device_state();
     if (!ds) return 1;
     KConvParams p = p_in;
@@ -401,7 +411,8 @@ int kconv_launch(const KConvParams& p_in, hipStream_t st) {
     const bool prof = prof_enabled();
     if (prof) prof_begin(PROF_KGEMM_F16, st);
     int rc;
-#define SVC_KCONV_GO(BN_, BM_) (p.nsub == 3 ? kconv_go<3, BN_, BM_>(ds, p, grid, st) : (p.nsub == 2 ? kconv_go<2, BN_, BM_>(ds, p, grid, st) : kconv_go<1, BN_, BM_>(ds, p, grid, st)))
+#define SVC_KCONV_GO_(BN_, BM_, RG_) (p.nsub == 3 ? kconv_go<3, BN_, BM_, RG_>(ds, p, grid, st) : (p.nsub == 2 ? kconv_go<2, BN_, BM_, RG_>(ds, p, grid, st) : kconv_go<1, BN_, BM_, RG_>(ds, p, grid, st)))
+#define SVC_KCONV_GO(BN_, BM_) (p.seq_len ? SVC_KCONV_GO_(BN_, BM_, true) : SVC_KCONV_GO_(BN_, BM_, false))
     if (bn == 128) {
         if (bm == 64) rc = SVC_KCONV_GO(128, 64);
         else if (bm == 128) rc = SVC_KCONV_GO(128, 128);
@@ -410,6 +421,7 @@ int kconv_launch(const KConvParams& p_in, hipStream_t st) {
         rc = SVC_KCONV_GO(64, 256);
     }
 #undef SVC_KCONV_GO
+#undef SVC_KCONV_GO_
     if (rc) return rc;
     if (prof) {
         const double M = (double)p.B * p.Lout, K = (double)p.k * p.cin_pad;

@@ -8,6 +8,12 @@
 // precision 1 feeds fp16 operands (fp32 accumulate); precision 2 ("fp16x3") splits every operand into fp16
 // hi + lo planes and issues the three significant products hi*hi + hi*lo + lo*hi on the fp16 MFMA (fp32
 // accumulate): ~2^-22 relative product error (fp32-class results) at 3/16 of the fp32-MFMA cycles.
+//
+// Ragged batches (svc_bigvgan_forward_ragged, svc_hift_forward_ragged): utterances of different lengths in one call, longest
+// first in micro-batches padded to their own longest member, each row being that of the utterance run alone.  BigVGAN masks the
+// producers of conv operands (its activations are kernels of their own); HiFT, whose Snake is fused into the conv epilogues,
+// bounds every conv's operand LOAD instead (tap-GEMM seq_len, resident-tile conv's ragged form) and ends the source, the STFT
+// and the overlap-add at each utterance's own last sample.
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -115,7 +121,30 @@ __global__ void hift_phase_prefix_kernel(const float* __restrict__ f0, double* _
     }
 }
 
-// merged source s[b][n] = tanh(sum_h lin_w[h] * (sine_h * uv + noise_amp * noise_h) + lin_b)
+// merged source sample: tanh(sum_h lin_w[h] * (sine_h * uv + noise_amp * noise_h) + lin_b) at sample r of frame f.
+// prefix: this utterance's [NH][S] rows; phase0: its [NH]; noise: its [NH][noise_ld] rows, already at sample n
+__device__ __forceinline__ float hift_source_sample(float f0v, const double* __restrict__ prefix, const float* __restrict__ phase0,
+                                                    const float* __restrict__ noise, long noise_ld, const float* __restrict__ lin_w,
+                                                    const float* __restrict__ lin_b, int S, int NH, int f, int r, float sr,
+                                                    float sine_amp, float noise_std, float voiced_thr) {
+    const float uv = f0v > voiced_thr ? 1.f : 0.f;
+    const float namp = uv * noise_std + (1.f - uv) * sine_amp / 3.f;
+    const float two_pi = 6.283185307179586f;
+    float acc = lin_b[0];
+    for (int h = 0; h < NH; ++h) {
+        const float v = (f0v * (float)(h + 1)) / sr;
+        const double cum = prefix[(long)h * S + f] + (double)(r + 1) * (double)v;
+        const float cf = (float)cum;
+        const float frac = fmodf(cf, 1.0f);
+        const float theta = two_pi * frac;
+        const float ph = h == 0 ? 0.f : phase0[h];
+        const float sine = sine_amp * sinf(theta + ph);
+        const float val = sine * uv + namp * noise[(long)h * noise_ld];
+        acc += lin_w[h] * val;
+    }
+    return tanhf(acc);
+}
+
 __global__ void hift_source_kernel(const float* __restrict__ f0, const double* __restrict__ prefix, const float* __restrict__ phase0,
                                    const float* __restrict__ noise, const float* __restrict__ lin_w, const float* __restrict__ lin_b,
                                    float* __restrict__ s_out, int B, int S, int NH, int up, float sr, float sine_amp, float noise_std,
@@ -126,30 +155,44 @@ __global__ void hift_source_kernel(const float* __restrict__ f0, const double* _
     const int b = (int)(i / Lw);
     const long n = i - (long)b * Lw;
     const int f = (int)(n / up), r = (int)(n - (long)f * up);
-    const float f0v = f0[(long)b * S + f];
-    const float uv = f0v > voiced_thr ? 1.f : 0.f;
-    const float namp = uv * noise_std + (1.f - uv) * sine_amp / 3.f;
-    const float two_pi = 6.283185307179586f;
-    float acc = lin_b[0];
-    for (int h = 0; h < NH; ++h) {
-        const float v = (f0v * (float)(h + 1)) / sr;
-        const double cum = prefix[((long)b * NH + h) * S + f] + (double)(r + 1) * (double)v;
-        const float cf = (float)cum;
-        const float frac = fmodf(cf, 1.0f);
-        const float theta = two_pi * frac;
-        const float ph = h == 0 ? 0.f : phase0[(long)b * NH + h];
-        const float sine = sine_amp * sinf(theta + ph);
-        const float val = sine * uv + namp * noise[((long)b * NH + h) * Lw + n];
-        acc += lin_w[h] * val;
+    s_out[i] = hift_source_sample(f0[(long)b * S + f], prefix + (long)b * NH * S, phase0 + (long)b * NH, noise + (long)b * NH * Lw + n,
+                                  Lw, lin_w, lin_b, S, NH, f, r, sr, sine_amp, noise_std, voiced_thr);
+}
+
+// Ragged batch: row j of the micro-batch ([B][S] frames) is utterance src[j] of the caller's phase0 [..][NH] and noise
+// [..][NH][S_in * up]; it uses the first lens[j] * up samples of its noise rows (the draws of the run alone).  f0 and prefix are the
+// micro-batch's own [B][S] / [B][NH][S].  Samples at and above lens[j] * up are written as zero and nothing is read for them.
+__global__ void hift_source_ragged_kernel(const float* __restrict__ f0, const double* __restrict__ prefix, const float* __restrict__ phase0,
+                                          const float* __restrict__ noise, const float* __restrict__ lin_w, const float* __restrict__ lin_b,
+                                          float* __restrict__ s_out, const int* __restrict__ src, const int* __restrict__ lens, int B, int S,
+                                          int S_in, int NH, int up, float sr, float sine_amp, float noise_std, float voiced_thr) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long Lw = (long)S * up;
+    if (i >= B * Lw) return;
+    const int b = (int)(i / Lw);
+    const long n = i - (long)b * Lw;
+    const int f = (int)(n / up), r = (int)(n - (long)f * up);
+    float v = 0.f;
+    if (f < lens[b]) {
+        const long Lw_in = (long)S_in * up;
+        v = hift_source_sample(f0[(long)b * S + f], prefix + (long)b * NH * S, phase0 + (long)src[b] * NH,
+                               noise + (long)src[b] * NH * Lw_in + n, Lw_in, lin_w, lin_b, S, NH, f, r, sr, sine_amp, noise_std, voiced_thr);
     }
-    s_out[i] = tanhf(acc);
+    s_out[i] = v;
+}
+
+// Ragged batch: the caller's f0 [..][S_in] -> the micro-batch's [B][S], values at and above lens[j] zero by selection (never loaded)
+__global__ void f0_gather_kernel(const float* __restrict__ f0, float* __restrict__ dst, const int* __restrict__ src,
+                                 const int* __restrict__ lens, int B, int S, int S_in) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)B * S) return;
+    const int b = (int)(i / S), f = (int)(i - (long)b * S);
+    dst[i] = f < lens[b] ? f0[(long)src[b] * S_in + f] : 0.f;
 }
 
 // centred, reflect-padded STFT (n_fft 16, hop 4, periodic Hann): out [B][F][ld]: channels 0..8 real, 9..17 imag
-__global__ void hift_stft_kernel(const float* __restrict__ s, float* __restrict__ out, int B, long Lw, int F, int ld) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long)B * F) return;
-    const int b = (int)(i / F), fr = (int)(i - (long)b * F);
+// one frame: s = the utterance's Lw samples, o = its output row
+__device__ __forceinline__ void hift_stft_frame(const float* __restrict__ s, float* __restrict__ o, long Lw, int fr, int ld) {
     float x[16];
 #pragma unroll
     for (int n = 0; n < 16; ++n) {
@@ -157,9 +200,8 @@ __global__ void hift_stft_kernel(const float* __restrict__ s, float* __restrict_
         if (q < 0) q = -q;
         if (q >= Lw) q = 2 * (Lw - 1) - q;
         const float w = 0.5f - 0.5f * cosf(6.283185307179586f * (float)n / 16.0f);
-        x[n] = s[(long)b * Lw + q] * w;
+        x[n] = s[q] * w;
     }
-    float* o = out + i * ld;
     for (int k = 0; k < 9; ++k) {
         float re = 0.f, im = 0.f;
 #pragma unroll
@@ -173,6 +215,25 @@ __global__ void hift_stft_kernel(const float* __restrict__ s, float* __restrict_
         o[9 + k] = im;
     }
     for (int c = 18; c < ld; ++c) o[c] = 0.f;
+}
+
+__global__ void hift_stft_kernel(const float* __restrict__ s, float* __restrict__ out, int B, long Lw, int F, int ld) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)B * F) return;
+    const int b = (int)(i / F), fr = (int)(i - (long)b * F);
+    hift_stft_frame(s + (long)b * Lw, out + i * ld, Lw, fr, ld);
+}
+
+// Ragged batch: utterance b holds lw[b] samples of its Lw-sample row and gets nf[b] = lw[b] / 4 + 1 frames, reflected at ITS last
+// sample; frame rows at and above nf[b] are written as zero (the source_downs convs read them as their zero padding)
+__global__ void hift_stft_ragged_kernel(const float* __restrict__ s, float* __restrict__ out, const int* __restrict__ lw,
+                                        const int* __restrict__ nf, int B, long Lw, int F, int ld) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)B * F) return;
+    const int b = (int)(i / F), fr = (int)(i - (long)b * F);
+    float* o = out + i * ld;
+    if (fr < nf[b]) hift_stft_frame(s + (long)b * Lw, o, lw[b], fr, ld);
+    else for (int c = 0; c < ld; ++c) o[c] = 0.f;
 }
 
 // conv_post output [B][F][ld] (9 log-magnitudes | 9 phase pre-activations) -> windowed time frames [B][F][16]
@@ -202,11 +263,8 @@ __global__ void hift_frames_kernel(const float* __restrict__ x, float* __restric
 }
 
 // overlap-add + window-envelope normalisation + trim + clamp: out [B][Lw]
-__global__ void hift_ola_kernel(const float* __restrict__ frames, float* __restrict__ out, int B, int F, long Lw, float limit) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long)B * Lw) return;
-    const int b = (int)(i / Lw);
-    const long n = i - (long)b * Lw;
+// sample n of an utterance: frames = its [F][16] rows
+__device__ __forceinline__ float hift_ola_sample(const float* __restrict__ frames, int F, long n, float limit) {
     const long p = n + 8;                         // index in the untrimmed signal
     float acc = 0.f, env = 0.f;
     const long f_hi = p / 4;
@@ -216,12 +274,30 @@ __global__ void hift_ola_kernel(const float* __restrict__ frames, float* __restr
         const int o = (int)(p - 4 * f);
         if (o < 0 || o >= 16) continue;
         const float w = 0.5f - 0.5f * cosf(6.283185307179586f * (float)o / 16.0f);
-        acc += frames[((long)b * F + f) * 16 + o];
+        acc += frames[f * 16 + o];
         env += w * w;
     }
-    float v = acc / env;
-    v = fminf(fmaxf(v, -limit), limit);
-    out[i] = v;
+    const float v = acc / env;
+    return fminf(fmaxf(v, -limit), limit);
+}
+
+__global__ void hift_ola_kernel(const float* __restrict__ frames, float* __restrict__ out, int B, int F, long Lw, float limit) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)B * Lw) return;
+    const int b = (int)(i / Lw);
+    const long n = i - (long)b * Lw;
+    out[i] = hift_ola_sample(frames + (long)b * F * 16, F, n, limit);
+}
+
+// Ragged batch, last step: utterance j of the micro-batch overlap-adds its own nf[j] frames (of the F-frame row) into row src[j] of
+// the caller's [..][Lw_out] output; samples at and above lw[j] are written as zero and no frame is read for them
+__global__ void hift_ola_ragged_kernel(const float* __restrict__ frames, float* __restrict__ out, const int* __restrict__ src,
+                                       const int* __restrict__ lw, const int* __restrict__ nf, int B, int F, long Lw_out, float limit) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)B * Lw_out) return;
+    const int b = (int)(i / Lw_out);
+    const long n = i - (long)b * Lw_out;
+    out[(long)src[b] * Lw_out + n] = n < lw[b] ? hift_ola_sample(frames + (long)b * F * 16, nf[b], n, limit) : 0.f;
 }
 
 __global__ void abs_copy_kernel(const float* __restrict__ src, long ld, float* __restrict__ dst, long n) {
@@ -309,6 +385,9 @@ struct RaggedMB {
     const int* src = nullptr;
     const int* len[9] = {};
     int S_in = 0;           // frames per utterance of the caller's mel (its row stride)
+    // HiFT only: waveform samples per row (device) and the rows' frame counts on the host (len[0] again)
+    const int* lw = nullptr;
+    const int* h_len0 = nullptr;
 };
 
 }  // namespace
@@ -350,9 +429,12 @@ int act_cl_any(const float* x, int ld, ActOut y, int vd, const float* taps, cons
 // (intermediate pairs) and, for the last pair, (y_last) * out_scale + res2 -> final_dst.
 // lens (device [B], anti-aliased mode without fusion only): valid rows per sequence.  The activations are the only producers of
 // conv operands here, so masking them is enough; the raw conv outputs past lens[b] are garbage that only pointwise ops touch.
+// conv_lens (device [B], HiFT's ragged call): the convs themselves treat rows at and above conv_lens[b] as padding.  With the
+// pointwise Snake fused into the producing conv's epilogue there is no activation kernel to mask, so the bound sits on each
+// conv's operand load (tap-GEMM: seq_len; resident-tile conv: its ragged form) and the operand planes past the end hold anything.
 int resblock_run(const ResBlockW& rb, int dtype, const float* taps, int act_mode, const float* x_in, float* y, float* t, ActOut act_a,
                  int B, int L, float out_scale, const float* res2, float* final_dst, hipStream_t st, ActOut act_b = ActOut(),
-                 const int* lens = nullptr) {
+                 const int* lens = nullptr, const int* conv_lens = nullptr) {
     const int f16 = dtype;      // operand mode handed to the activation writers
     const int ld = cpad(rb.ch, dtype);
     const float* cur = x_in;
@@ -378,6 +460,7 @@ int resblock_run(const ResBlockW& rb, int dtype, const float* taps, int act_mode
         r1.a = act_a.in(); r1.B = B; r1.Lin = L; r1.Lout = L; r1.dilation = rb.dil[d];
         r1.pad_left = (rb.k * rb.dil[d] - rb.dil[d]) / 2;
         r1.p8 = p8_1;
+        r1.seq_len = conv_lens; r1.seq_kconv = true;
         if (fuse) fuse_into(r1, rb.a2[d], act_b, p8_2);
         else { r1.c32 = t; r1.ldc32 = ld; }
         if (conv1d_run(rb.c1[d], r1, st)) return 1;
@@ -388,6 +471,7 @@ int resblock_run(const ResBlockW& rb, int dtype, const float* taps, int act_mode
         r2.a = fuse ? act_b.in() : act_a.in(); r2.B = B; r2.Lin = L; r2.Lout = L; r2.dilation = 1;
         r2.pad_left = (rb.k - 1) / 2;
         r2.p8 = p8_2;
+        r2.seq_len = conv_lens; r2.seq_kconv = true;
         r2.res = cur; r2.ldres = ld;
         const bool last = d == rb.ndil - 1;
         if (last) {
@@ -528,10 +612,31 @@ struct svc_hift {
     void *f0_a, *f0_b;
     float *f0_buf, *s_buf, *stft32, *x, *y, *t, *xsum, *si, *post, *frames;
     double* prefix;
+    // ragged calls: pinned staging for the host-built length table and its device copy
+    PinnedRing staging;
+    Arena tab;
+    int* d_tab = nullptr;
+    size_t tab_cap = 0;
 
     int reserve(int B, int S, hipStream_t st);
+    // rg == null: B utterances of S frames each.  rg != null: micro-batch of a ragged call; mel / f0 / phase0 / noise / out / f0_out
+    // are the caller's whole tensors and S the micro-batch's longest member
     int run(const float* mel, const float* f0, const float* phase0, const float* noise, int B, int S, float* out, float* f0_out,
-            hipStream_t st);
+            hipStream_t st, const RaggedMB* rg = nullptr);
+    // valid rows of an utterance of S frames after `stage` up-sampling stages (the last stage's reflection pad adds one row)
+    long rows_after(int stage, long S) const {
+        long L = S;
+        for (int i = 0; i < stage; ++i) L = L * cfg.upsample_rates[i] + (i == cfg.num_upsamples - 1 && S > 0 ? 1 : 0);
+        return L;
+    }
+    // Which convs of an utterance take the resident-tile kernel depends on its stage lengths alone (KCONV_MIN_ROWS): the number
+    // of stages that reach it.  A ragged micro-batch holds utterances of ONE class, so every utterance runs the kernels it
+    // would run alone whatever its neighbours are.
+    int kernel_class(long S) const {
+        int c = 0;
+        for (int i = 0; i <= cfg.num_upsamples; ++i) c += rows_after(i, S) >= KCONV_MIN_ROWS;
+        return c;
+    }
 };
 
 int svc_hift::reserve(int B, int S, hipStream_t st) {
@@ -557,8 +662,10 @@ int svc_hift::reserve(int B, int S, hipStream_t st) {
     const int fc = cfg.f0_cond_channels;
     mel_a.hi = ws.alloc((size_t)Bc * Sc * cpad(cfg.in_channels, dtype) * vesize(dtype), st);
     mel_a.lo = ws.alloc((size_t)Bc * Sc * cpad(cfg.in_channels, dtype) * vesize(dtype), st);
-    f0_a = ws.alloc((size_t)Bc * Sc * cpad(fc, 1) * 4, st);
-    f0_b = ws.alloc((size_t)Bc * Sc * cpad(fc, 1) * 4, st);
+    // the predictor's ping-pong buffers: f0_a first holds the fp32 channels-last mel (in_channels wide), then both hold fc-wide rows
+    const size_t f0_ld = std::max(cpad(fc, 1), cpad(cfg.in_channels, 1));
+    f0_a = ws.alloc((size_t)Bc * Sc * f0_ld * 4, st);
+    f0_b = ws.alloc((size_t)Bc * Sc * f0_ld * 4, st);
     act_a.hi = ws.alloc((size_t)max_el * vesize(dtype), st);
     act_a.lo = ws.alloc((size_t)max_el * vesize(dtype), st);
     act_b.hi = ws.alloc((size_t)max_el * vesize(dtype), st);
@@ -583,9 +690,15 @@ int svc_hift::reserve(int B, int S, hipStream_t st) {
     return 0;
 }
 
+// Ragged micro-batches (rg): nothing past an utterance's end reaches its rows.  The inputs are gathered by selection (mel, f0)
+// or read up to the end only (noise); every conv, the f0 predictor's included, bounds its operand load by the utterance's
+// rows at that stage; the source stops at the last sample, the STFT reflects there and gives F_b frames, and the overlap-add
+// runs over those F_b frames.  What the convs write past the end (x, y, xsum, si, post and the operand planes) is touched by
+// pointwise ops only.
 int svc_hift::run(const float* mel, const float* f0_in, const float* phase0, const float* noise, int B, int S, float* out,
-                  float* f0_out, hipStream_t st) {
+                  float* f0_out, hipStream_t st, const RaggedMB* rg) {
     const int vd = dtype;
+    const int* len0 = rg ? rg->len[0] : nullptr;
     const int NH = cfg.nb_harmonics + 1;
     const long Lw = (long)S * up_total;
     const int F = (int)(Lw / cfg.istft_hop) + 1;
@@ -596,13 +709,16 @@ int svc_hift::run(const float* mel, const float* f0_in, const float* phase0, con
         const int fc = cfg.f0_cond_channels, fld = cpad(fc, 1);
         ActOut f0in;
         f0in.hi = f0_a;
-        if (mel_to_cl(mel, f0in, 1, B, cfg.in_channels, S, cpad(cfg.in_channels, 1), st)) return 1;
+        if (rg) {
+            if (mel_to_cl_ragged(mel, f0in, 1, rg->src, len0, B, cfg.in_channels, rg->S_in, S, cpad(cfg.in_channels, 1), st)) return 1;
+        } else if (mel_to_cl(mel, f0in, 1, B, cfg.in_channels, S, cpad(cfg.in_channels, 1), st)) return 1;
         void* src = f0_a;
         void* dst = f0_b;
         for (int i = 0; i < 5; ++i) {
             ConvRun r;
             r.a.hi = src; r.B = B; r.Lin = S; r.Lout = S; r.pad_left = 1;
             r.c32 = (float*)dst; r.ldc32 = fld; r.act = KG_ACT_ELU;
+            r.seq_len = len0;
             if (conv1d_run(f0_convs[i], r, st)) return 1;
             std::swap(src, dst);
         }
@@ -611,18 +727,38 @@ int svc_hift::run(const float* mel, const float* f0_in, const float* phase0, con
         hipLaunchKernelGGL(abs_copy_kernel, dim3(cdiv((long)B * S, 256)), dim3(256), 0, st, f0_buf, 1L, f0_buf, (long)B * S);
         SVC_CHECK_HIP(hipGetLastError());
         f0 = f0_buf;
+    } else if (rg) {    // the caller's rows, cut to the micro-batch: the prefix below is causal, so the zeros past the end are inert
+        hipLaunchKernelGGL(f0_gather_kernel, dim3(cdiv((long)B * S, 256)), dim3(256), 0, st, f0_in, f0_buf, rg->src, len0, B, S, rg->S_in);
+        SVC_CHECK_HIP(hipGetLastError());
+        f0 = f0_buf;
     }
-    if (f0_out) SVC_CHECK_HIP(hipMemcpyAsync(f0_out, f0, (size_t)B * S * 4, hipMemcpyDeviceToDevice, st));
+    if (f0_out) {
+        if (rg) {
+            hipLaunchKernelGGL(wave_scatter_kernel, dim3(cdiv((long)B * rg->S_in, 256)), dim3(256), 0, st, f0, f0_out, rg->src, len0, B,
+                               (long)S, (long)rg->S_in);
+            SVC_CHECK_HIP(hipGetLastError());
+        } else SVC_CHECK_HIP(hipMemcpyAsync(f0_out, f0, (size_t)B * S * 4, hipMemcpyDeviceToDevice, st));
+    }
     // ---- harmonic source + its STFT
     hipLaunchKernelGGL(hift_phase_prefix_kernel, dim3(cdiv(B * NH, 64)), dim3(64), 0, st, f0, prefix, B, S, NH, up_total,
                        (float)cfg.sampling_rate);
     SVC_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(hift_source_kernel, dim3(cdiv((long)B * Lw, 256)), dim3(256), 0, st, f0, prefix, phase0, noise, src_lin_w,
-                       src_lin_b, s_buf, B, S, NH, up_total, (float)cfg.sampling_rate, cfg.nsf_alpha, cfg.nsf_sigma,
-                       cfg.nsf_voiced_threshold);
-    SVC_CHECK_HIP(hipGetLastError());
     const int ld18 = cpad(cfg.istft_n_fft + 2, dtype);
-    hipLaunchKernelGGL(hift_stft_kernel, dim3(cdiv((long)B * F, 256)), dim3(256), 0, st, s_buf, stft32, B, Lw, F, ld18);
+    const int* len_f = rg ? rg->len[cfg.num_upsamples] : nullptr;      // frames of the STFT / iSTFT = rows of the last stage
+    if (rg) {
+        hipLaunchKernelGGL(hift_source_ragged_kernel, dim3(cdiv((long)B * Lw, 256)), dim3(256), 0, st, f0, prefix, phase0, noise,
+                           src_lin_w, src_lin_b, s_buf, rg->src, len0, B, S, rg->S_in, NH, up_total, (float)cfg.sampling_rate,
+                           cfg.nsf_alpha, cfg.nsf_sigma, cfg.nsf_voiced_threshold);
+        SVC_CHECK_HIP(hipGetLastError());
+        hipLaunchKernelGGL(hift_stft_ragged_kernel, dim3(cdiv((long)B * F, 256)), dim3(256), 0, st, s_buf, stft32, rg->lw, len_f, B, Lw,
+                           F, ld18);
+    } else {
+        hipLaunchKernelGGL(hift_source_kernel, dim3(cdiv((long)B * Lw, 256)), dim3(256), 0, st, f0, prefix, phase0, noise, src_lin_w,
+                           src_lin_b, s_buf, B, S, NH, up_total, (float)cfg.sampling_rate, cfg.nsf_alpha, cfg.nsf_sigma,
+                           cfg.nsf_voiced_threshold);
+        SVC_CHECK_HIP(hipGetLastError());
+        hipLaunchKernelGGL(hift_stft_kernel, dim3(cdiv((long)B * F, 256)), dim3(256), 0, st, s_buf, stft32, B, Lw, F, ld18);
+    }
     SVC_CHECK_HIP(hipGetLastError());
     ActBuf stft_in;
     stft_in.hi = stft32;
@@ -631,11 +767,14 @@ int svc_hift::run(const float* mel, const float* f0_in, const float* phase0, con
         stft_in = stft_a.in();
     }
     // ---- main path
-    if (mel_to_cl(mel, mel_a, vd, B, cfg.in_channels, S, cpad(cfg.in_channels, dtype), st)) return 1;
+    if (rg) {
+        if (mel_to_cl_ragged(mel, mel_a, vd, rg->src, len0, B, cfg.in_channels, rg->S_in, S, cpad(cfg.in_channels, dtype), st)) return 1;
+    } else if (mel_to_cl(mel, mel_a, vd, B, cfg.in_channels, S, cpad(cfg.in_channels, dtype), st)) return 1;
     {
         ConvRun r;
         r.a = mel_a.in(); r.B = B; r.Lin = S; r.Lout = S; r.pad_left = 3;
         r.c32 = xsum; r.ldc32 = cpad(bc, dtype);
+        r.seq_len = len0; r.seq_kconv = true;
         if (conv1d_run(conv_pre, r, st)) return 1;
     }
     int ch = bc;
@@ -653,18 +792,22 @@ int svc_hift::run(const float* mel, const float* f0_in, const float* phase0, con
             // of its (L*u + 1)-row sequence, then row 0 = row 2 (reflect).  One launch per utterance because the
             // one-row shift is not a whole number of GEMM output rows (each holds u samples).
             const size_t a_step = (size_t)L * ups[i].cin_pad * vesize(dtype);
+            // (ragged: each launch covers the utterance's own rows, known on the host, so it needs no length array)
             for (int b = 0; b < B; ++b) {
                 ActBuf ab;
                 ab.hi = (const char*)act_a.hi + b * a_step;
                 ab.lo = (const char*)act_a.lo + b * a_step;
-                if (convT_run(ups[i], ab, 1, (int)L, x + ((long)b * Lnew + 1) * ld, 0, 0, st)) return 1;
+                const int Lb = rg ? (int)((long)rg->h_len0[b] * (L / S)) : (int)L;
+                if (Lb == 0) continue;
+                if (convT_run(ups[i], ab, 1, Lb, x + ((long)b * Lnew + 1) * ld, 0, 0, st)) return 1;
             }
             hipLaunchKernelGGL(copy_row_kernel, dim3(cdiv((long)B * ld, 256)), dim3(256), 0, st, x, B, (int)Lnew, ld, 2, 0);
             SVC_CHECK_HIP(hipGetLastError());
         } else {
-            if (convT_run(ups[i], act_a.in(), B, (int)L, x, 0, 0, st)) return 1;
+            if (convT_run(ups[i], act_a.in(), B, (int)L, x, 0, 0, st, rg ? rg->len[i] : nullptr)) return 1;
         }
         L = Lnew;
+        const int* len_i = rg ? rg->len[i + 1] : nullptr;
         // source fusion: si = source_resblock(source_down(s_stft)); x = x + si  (generator.py:416-419)
         {
             ConvRun r;
@@ -673,13 +816,14 @@ int svc_hift::run(const float* mel, const float* f0_in, const float* phase0, con
             if (dk == 1) { r.stride = 1; r.pad_left = 0; }
             else { r.stride = dk / 2; r.pad_left = dk / 4; }
             r.c32 = si; r.ldc32 = ld;
+            r.seq_len = len_f;
             if (conv1d_run(src_down[i], r, st)) return 1;
         }
         // x <- x + source_resblock(si): last conv of the stack adds res2 = x and writes x
-        if (resblock_run(src_rb[i], dtype, nullptr, 1, si, y, t, act_a, B, (int)L, 1.0f, x, x, st, act_b)) return 1;
+        if (resblock_run(src_rb[i], dtype, nullptr, 1, si, y, t, act_a, B, (int)L, 1.0f, x, x, st, act_b, nullptr, len_i)) return 1;
         for (int j = 0; j < nk; ++j) {
             if (resblock_run(blocks[i * nk + j], dtype, nullptr, 1, x, y, t, act_a, B, (int)L, 1.0f / (float)nk,
-                             j > 0 ? xsum : nullptr, xsum, st, act_b)) return 1;
+                             j > 0 ? xsum : nullptr, xsum, st, act_b, nullptr, len_i)) return 1;
         }
     }
     if (ew_cl(xsum, act_a, vd, (long)B * L, ch, cpad(ch, dtype), 2, 0.01f, st)) return 1;     // F.leaky_relu default slope
@@ -687,11 +831,18 @@ int svc_hift::run(const float* mel, const float* f0_in, const float* phase0, con
         ConvRun r;
         r.a = act_a.in(); r.B = B; r.Lin = (int)L; r.Lout = (int)L; r.pad_left = 3;
         r.c32 = post; r.ldc32 = ld18;
+        r.seq_len = len_f; r.seq_kconv = true;
         if (conv1d_run(conv_post, r, st)) return 1;
     }
     hipLaunchKernelGGL(hift_frames_kernel, dim3(cdiv((long)B * F, 256)), dim3(256), 0, st, post, frames, (long)B * F, ld18);
     SVC_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(hift_ola_kernel, dim3(cdiv((long)B * Lw, 256)), dim3(256), 0, st, frames, out, B, F, Lw, cfg.audio_limit);
+    if (rg) {   // straight into the caller's rows, tails zeroed
+        const long Lw_out = (long)rg->S_in * up_total;
+        hipLaunchKernelGGL(hift_ola_ragged_kernel, dim3(cdiv((long)B * Lw_out, 256)), dim3(256), 0, st, frames, out, rg->src, rg->lw,
+                           len_f, B, F, Lw_out, cfg.audio_limit);
+    } else {
+        hipLaunchKernelGGL(hift_ola_kernel, dim3(cdiv((long)B * Lw, 256)), dim3(256), 0, st, frames, out, B, F, Lw, cfg.audio_limit);
+    }
     SVC_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -910,6 +1061,80 @@ int svc_hift_forward(svc_hift_t* m, const float* mel, const float* f0, const flo
         if (m->run(mel + (long)b0 * m->cfg.in_channels * S, f0 ? f0 + (long)b0 * S : nullptr, phase0 + (long)b0 * NH,
                    noise + (long)b0 * NH * Lw, nb, S, out + (long)b0 * Lw, f0_out ? f0_out + (long)b0 * S : nullptr, st))
             return 1;
+    }
+    return 0;
+}
+
+int svc_hift_forward_ragged(svc_hift_t* m, const float* mel, const int32_t* lens, const float* f0, const float* phase0,
+                            const float* noise, int B, int S, float* out, float* f0_out, void* stream) {
+    SVC_REQUIRE(m && mel && lens && phase0 && noise && out && B >= 1 && S >= 1, "bad argument");
+    for (int b = 0; b < B; ++b) SVC_REQUIRE(lens[b] >= 0 && lens[b] <= S, "svc_hift_forward_ragged: lens out of range");
+    hipStream_t st = (hipStream_t)stream;
+    const int nu = m->cfg.num_upsamples;
+    // Longest first (stable: a batch of equal lengths runs exactly as svc_hift_forward runs it), cut into micro-batches of one
+    // kernel class (svc_hift::kernel_class), each padded to its own longest member only.
+    std::vector<int> order(B);
+    for (int b = 0; b < B; ++b) order[b] = b;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return lens[a] > lens[b]; });
+    const int mb = m->microbatch > 0 ? m->microbatch : 32;
+    std::vector<int> first;     // first row of each micro-batch, then B
+    for (int b = 0; b < B; ++b)
+        if (b == 0 || b - first.back() == mb || m->kernel_class(lens[order[b]]) != m->kernel_class(lens[order[first.back()]]))
+            first.push_back(b);
+    first.push_back(B);
+    // length table, per micro-batch of nb rows: src[nb], the valid rows after 0 .. nu up-sampling stages ([nb] each; the last
+    // is the STFT's frame count as well), the waveform samples [nb].  Built in a pinned slot and copied once: the caller's array
+    // is consumed here and nothing waits for the stream.
+    const int n_arr = nu + 3;
+    const size_t n_tab = (size_t)B * n_arr;
+    if (n_tab > m->tab_cap) {
+        SVC_CHECK_HIP(hipStreamSynchronize(st));
+        m->tab.release();
+        m->d_tab = m->tab.alloc_n<int>(n_tab, st);
+        if (!m->d_tab) { m->tab_cap = 0; return 1; }
+        m->tab_cap = n_tab;
+    }
+    int* h = reinterpret_cast<int*>(m->staging.acquire(n_tab * sizeof(int)));
+    if (!h) return 1;
+    int nb_max = 0;
+    for (size_t k = 0; k + 1 < first.size(); ++k) {
+        const int b0 = first[k], nb = first[k + 1] - b0;
+        nb_max = std::max(nb_max, nb);
+        int* row = h + (size_t)b0 * n_arr;
+        for (int j = 0; j < nb; ++j) {
+            const long l = lens[order[b0 + j]];
+            row[j] = order[b0 + j];
+            for (int i = 0; i <= nu; ++i) row[(size_t)(i + 1) * nb + j] = (int)m->rows_after(i, l);
+            row[(size_t)(nu + 2) * nb + j] = (int)(l * m->up_total);
+        }
+    }
+    SVC_CHECK_HIP(hipMemcpyAsync(m->d_tab, h, n_tab * sizeof(int), hipMemcpyHostToDevice, st));
+    if (m->staging.commit(st)) return 1;
+    // one reservation for the whole call: the first micro-batch is the longest, not necessarily the largest
+    if (lens[order[0]] > 0 && m->reserve(nb_max, lens[order[0]], st)) return 1;
+    for (size_t k = 0; k + 1 < first.size(); ++k) {
+        const int b0 = first[k], nb = first[k + 1] - b0;
+        const int* row = m->d_tab + (size_t)b0 * n_arr;
+        RaggedMB rg;
+        rg.src = row;
+        for (int i = 0; i <= nu; ++i) rg.len[i] = row + (size_t)(i + 1) * nb;
+        rg.lw = row + (size_t)(nu + 2) * nb;
+        rg.h_len0 = h + (size_t)b0 * n_arr + nb;
+        rg.S_in = S;
+        const int Smb = lens[order[b0]];
+        if (Smb == 0) {     // nothing but empty utterances left: their rows are all tail
+            const long Lw = (long)S * m->up_total;
+            hipLaunchKernelGGL(wave_scatter_kernel, dim3(cdiv((long)nb * Lw, 256)), dim3(256), 0, st, (const float*)nullptr, out, rg.src,
+                               rg.lw, nb, 0L, Lw);
+            SVC_CHECK_HIP(hipGetLastError());
+            if (f0_out) {
+                hipLaunchKernelGGL(wave_scatter_kernel, dim3(cdiv((long)nb * S, 256)), dim3(256), 0, st, (const float*)nullptr, f0_out,
+                                   rg.src, rg.len[0], nb, 0L, (long)S);
+                SVC_CHECK_HIP(hipGetLastError());
+            }
+            continue;
+        }
+        if (m->run(mel, f0, phase0, noise, nb, Smb, out, f0_out, st, &rg)) return 1;
     }
     return 0;
 }

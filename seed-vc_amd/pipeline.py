@@ -117,6 +117,44 @@ class HotPath:
         return vc_target, wave.reshape(B, -1)
 
     @torch.inference_mode()
+    def convert_batch_ragged(self, mu, prompt, style, x_lens, prompt_lens, n_timesteps, inference_cfg_rate, z=None,
+                             vocoder_kwargs=None):
+        """B utterances of different lengths and prompts in one pass: mu (B, T, Dc), prompt (B, C, Pmax), style (B, Ds), x_lens /
+        prompt_lens: B host integers each (prompt + output frames, prompt frames) -> list of B pairs (mel (1, C, S_b), wave
+        (1, S_b * hop)), S_b = x_lens[b] - prompt_lens[b]: what `convert_batch` gives for each utterance alone.  The sampler with
+        per-row lengths -> `svc_mel_strip_prompt` (padding = the log-mel floor) -> ONE `vocoder(vc, lens=S)` call, BigVGAN or HiFT
+        (`svc_bigvgan_forward_ragged` / `svc_hift_forward_ragged`: no utterance sees its neighbour's padding); a batch of one
+        output length is one plain vocoder call.  vocoder_kwargs: HiFT's pinned f0 (B, Smax) / phase0 / noise (B, nh, Smax * up),
+        row b being the draws of utterance b alone in its leading part.  Everything is enqueued from the host integers:
+        no synchronisation."""
+        import ctypes as C
+        from . import _lib
+        B, T = mu.size(0), mu.size(1)
+        x_lens = [int(v) for v in (x_lens.tolist() if torch.is_tensor(x_lens) else x_lens)]
+        P = [int(v) for v in (prompt_lens.tolist() if torch.is_tensor(prompt_lens) else prompt_lens)]
+        if len(x_lens) != B or len(P) != B:
+            raise ValueError(f"convert_batch_ragged: {len(x_lens)} x_lens and {len(P)} prompt_lens for a batch of {B}")
+        S = [t - p for t, p in zip(x_lens, P)]
+        if min(S) < 0 or max(x_lens) > T or max(P) > prompt.size(-1) or min(P) < 0:
+            raise ValueError("convert_batch_ragged: need 0 <= prompt_lens[b] <= x_lens[b] <= T and prompt_lens[b] <= prompt frames")
+        dev = mu.device
+        i32 = lambda v: (C.c_int32 * len(v))(*v)                                                    # noqa: E731
+        with torch.cuda.device(dev):
+            mel = self.cfm.inference(mu, x_lens, prompt, style, None, n_timesteps, inference_cfg_rate=inference_cfg_rate,
+                                     z=z, prompt_lens=P)
+            mel = _lib.f32c(mel, dev)
+            Cm, Smax = mel.size(1), max(max(S), 1)
+            vc = torch.empty(B, Cm, Smax, device=dev)
+            _lib.check(_lib.lib().svc_mel_strip_prompt(_lib.ptr(mel), i32(P), i32(x_lens), B, Cm, T, Smax, C.c_float(LOG_MEL_FLOOR),
+                                                       _lib.ptr(vc), _lib.stream_ptr()))
+            kw = dict(vocoder_kwargs or {})
+            if len(set(S)) > 1:
+                kw["lens"] = S
+            wave = self.vocoder(vc, **kw).reshape(B, -1)
+            hop = wave.size(1) // Smax
+        return [(vc[b:b + 1, :, :S[b]], wave[b:b + 1, :S[b] * hop]) for b in range(B)]
+
+    @torch.inference_mode()
     def convert_long(self, cond, prompt_condition, mel2, style2, n_timesteps, inference_cfg_rate, hop,
                      max_context_window, overlap_frame_len=16, noise_fn=None, vocoder_kwargs_fn=None):
         """One long utterance, chunked exactly like the reference driver (inference.py:470-527): chunks of
@@ -213,7 +251,8 @@ class HotPath:
         with per-row x_lens / prompt_lens -> `svc_mel_strip_prompt` (padding = the log-mel floor) -> the vocoder -> rows of
         one wave buffer.  Seams are resolved once, after the last micro-batch, so a seam may cross micro-batches.
         ragged_vocoder: None = one `vocoder(mel, lens=...)` call if the vocoder is a `BigVGAN`, else one plain call per
-        distinct chunk length (a file has at most two: full windows and its last chunk); True / False force it (a
+        distinct chunk length (a file has at most two: full windows and its last chunk); True / False force it, for either
+        vocoder (`HiFT` takes `lens=` too; a caller who wants its draws pinned in the ragged call wraps the vocoder; a
         micro-batch of one length is one plain call either way).  vocoder_kwargs_fn(S) -> dict of tensors with a leading
         batch axis of 1 (HiFT's pinned draws) is called once per chunk in plan order and concatenated per length group; it
         cannot be combined with the ragged call.

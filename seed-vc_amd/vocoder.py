@@ -125,8 +125,17 @@ class HiFT:
         _lib.check(_lib.lib().svc_hift_set_microbatch(self._h, int(n)))
 
     @torch.inference_mode()
-    def __call__(self, x, f0=None, phase0=None, noise=None, return_f0=False):
+    def __call__(self, x, f0=None, phase0=None, noise=None, return_f0=False, lens=None):
+        """x (B, 80, S) -> (B, S * up) [, f0 (B, S)].  lens (list / LongTensor of B ints, 0 <= lens[b] <= S): a ragged batch in
+        one call -- out[b, :lens[b] * up] is the waveform of x[b, :, :lens[b]] run alone with f0[b, :lens[b]], phase0[b] and
+        noise[b, :, :lens[b] * up] (the draws of the run alone), the rest of the row and of the returned f0 is zero, and
+        frames, f0 values and noise samples past an utterance's end may hold anything (svc_hift_forward_ragged in
+        include/seedvc_hip.h).  Draws made here have the same shapes with and without lens."""
         B, _, S = x.shape
+        if lens is not None:
+            lens = [int(v) for v in (lens.tolist() if torch.is_tensor(lens) else lens)]
+            if len(lens) != B:
+                raise ValueError(f"HiFT: lens has {len(lens)} entries, the batch has {B} utterances")
         nh = self.cfg["nb_harmonics"] + 1
         Lw = S * self.total_up
         dev = self.device
@@ -140,8 +149,13 @@ class HiFT:
             f0t = _lib.f32c(f0, dev) if f0 is not None else None
             out = torch.empty(B, Lw, device=dev, dtype=torch.float32)
             f0_out = torch.empty(B, S, device=dev, dtype=torch.float32) if return_f0 else None
-            _lib.check(_lib.lib().svc_hift_forward(self._h, _lib.ptr(mel), _lib.ptr(f0t), _lib.ptr(phase0), _lib.ptr(noise),
-                                                   B, S, _lib.ptr(out), _lib.ptr(f0_out), _lib.stream_ptr()))
+            if lens is None:
+                _lib.check(_lib.lib().svc_hift_forward(self._h, _lib.ptr(mel), _lib.ptr(f0t), _lib.ptr(phase0), _lib.ptr(noise),
+                                                       B, S, _lib.ptr(out), _lib.ptr(f0_out), _lib.stream_ptr()))
+            else:
+                _lib.check(_lib.lib().svc_hift_forward_ragged(self._h, _lib.ptr(mel), (C.c_int32 * B)(*lens), _lib.ptr(f0t),
+                                                              _lib.ptr(phase0), _lib.ptr(noise), B, S, _lib.ptr(out),
+                                                              _lib.ptr(f0_out), _lib.stream_ptr()))
         return (out, f0_out) if return_f0 else out
 
     forward = __call__
