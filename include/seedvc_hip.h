@@ -246,6 +246,51 @@ int svc_ar_generate_batch_seeded(svc_ar_t* m, int B, const float* x_prefill, con
 /* out device [n_steps][vocab] = exactly the draws the seeded sampler uses for `seed` at steps step0 .. step0 + n_steps - 1
  * (handing them to svc_ar_generate_batch as exp_noise reproduces the seeded run bit for bit). */
 int svc_ar_exp_draws(svc_ar_t* m, uint64_t seed, int step0, int n_steps, float* out, void* stream);
+/* ---- ragged prefill and sessions (continuous batching).
+ * svc_ar_prefill_batch: svc_ar_prefill_slot for n sequences in one pass.  Sequence i goes to the cache of slots[i]
+ * (HOST [n], distinct, 0 <= slot < max_batch, not occupied by a session); x [sum S][dim], S HOST [n], input_pos / kv_pos
+ * HOST [sum S] are concatenated the way svc_ar_generate_batch takes them; logits_out device [n][vocab] = the logits of
+ * each sequence's last row.  Norms and linears run over all rows in one launch each (always the tap-GEMM, whatever S is),
+ * RoPE / cache scatter and the causal GQA attention (fp32 MFMA, flash-style; csrc/ar_prefill_attn.h) find every row's slot
+ * through per-pass tables that are uploaded once.  A pass takes at most 8192 rows (svc_ar_set_prefill_rows lowers that, to
+ * max_seq_len at the least); a call with more rows runs as several passes of whole sequences.
+ * Contract: a sequence's logits and the cache rows it writes are bit-identical whether it is prefilled alone or with any
+ * companions, in any slot, at any place in the concatenation.  Rows above a sequence's prefix never reach its result, not
+ * even as 0 x value.  Against svc_ar_prefill_slot the results agree to the logit tolerance, not bit for bit (another
+ * summation order in the attention; no GEMV form for short sequences).  Arguments are checked before anything is launched. */
+int svc_ar_prefill_batch(svc_ar_t* m, int n, const int32_t* slots, const float* x, const int32_t* S, const int64_t* input_pos,
+                         const int64_t* kv_pos, float* logits_out, void* stream);
+int svc_ar_set_prefill_rows(svc_ar_t* m, int rows);   /* rows of one pass: max_seq_len .. 8192 (default 8192) */
+int svc_ar_prefill_passes(svc_ar_t* m);               /* passes the last ragged prefill ran as */
+/* One request of svc_ar_admit.  Everything svc_ar_generate_batch takes per call is per request here. */
+typedef struct svc_ar_request {
+    int32_t slot;                 /* a free slot, 0 <= slot < max_batch */
+    int32_t S;                    /* its prefill rows */
+    const float* exp_noise;       /* device [max_new][vocab] Exp(1) draws, or NULL: the sampler draws them from `seed` */
+    uint64_t seed;
+    int32_t max_new;              /* >= 1 */
+    int32_t min_tokens_before_eos;
+    float temperature, top_p, repetition_penalty;
+    int32_t* tokens_out;          /* device [max_new]; must outlive the request (until svc_ar_retire) */
+} svc_ar_request_t;
+/* svc_ar_admit: one ragged prefill for the n newcomers (rows concatenated in request order), each one's first token, then
+ * ONLY these slots' loop state, positions and next-input row are written, all on the stream: slots in mid-sequence are not
+ * disturbed.  A request that is finished at admission (max_new == 1, cache full) is admitted as finished.  The first admit
+ * opens a SESSION; it is active until every slot is retired.  While it is active svc_ar_generate_batch[_seeded],
+ * svc_ar_decode_step_batch and svc_ar_set_max_batch fail with "a session is active" (they share the slot state), and so do
+ * the B = 1 calls and svc_ar_prefill_slot / _batch on an occupied slot (B = 1: slot 0).  With no session active everything
+ * behaves as before.  Synchronises.
+ * svc_ar_run: n_steps replays of the captured generate graph over slots 0 .. highest occupied one (free slots below it sit
+ * in the batch as finished slots and record nothing), then one read of the slots' counters: n_tokens / done HOST
+ * [max_batch] (a free slot reports 0 / 1).  A slot's tokens are tokens_out[0 .. n_tokens).
+ * svc_ar_retire: frees a slot (finished or not; a running sequence stops recording).  Its tokens stay in tokens_out.
+ * Contract: a request's tokens are a function of its own inputs alone -- bit-identical to the same request admitted alone
+ * and run to completion, whatever else is in flight, whichever slot it gets, however n_steps is chosen, whenever admitted. */
+int svc_ar_admit(svc_ar_t* m, int n, const svc_ar_request_t* requests, const float* x_prefill, const int64_t* input_pos,
+                 const int64_t* kv_pos, void* stream);
+int svc_ar_run(svc_ar_t* m, int n_steps, int32_t* n_tokens, int32_t* done, void* stream);
+int svc_ar_retire(svc_ar_t* m, int slot, void* stream);
+int svc_ar_session_active(svc_ar_t* m);               /* occupied slots; 0 = no session */
 /* Replaces `sample(logits, previous_tokens, suppress_tokens, temperature, top_p, repetition_penalty)`
  * (modules/v2/ar.py:712-763): repetition penalty, top-p, temperature softmax, argmax(probs / q) with q = exp_noise
  * (the Exp(1) draw of multinomial_sample_one_no_sync, supplied by the caller).  suppress_token < 0 = none. */

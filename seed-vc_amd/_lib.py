@@ -21,6 +21,8 @@ EXPORTS = [
     "svc_ar_create", "svc_ar_destroy", "svc_ar_reset", "svc_ar_forward_generate", "svc_ar_decode_step", "svc_ar_sample", "svc_ar_generate",
     "svc_ar_set_max_batch", "svc_ar_prefill_slot", "svc_ar_decode_step_batch", "svc_ar_generate_batch",
     "svc_ar_generate_batch_seeded", "svc_ar_exp_draws", "svc_v2_assemble_cond", "svc_mel_strip_prompt",
+    "svc_ar_prefill_batch", "svc_ar_set_prefill_rows", "svc_ar_prefill_passes", "svc_ar_admit", "svc_ar_run", "svc_ar_retire",
+    "svc_ar_session_active",
     "svc_lr_create", "svc_lr_destroy", "svc_lr_forward", "svc_crossfade",
     "svc_chunks_gather_cond", "svc_chunks_assemble", "svc_sola_step",
     "svc_campplus_create", "svc_campplus_destroy", "svc_campplus_forward", "svc_kaldi_fbank_frames", "svc_kaldi_fbank",
@@ -71,6 +73,13 @@ class HiftConfig(C.Structure):
 class ArConfig(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("dim", "n_head", "n_local_heads", "head_dim", "n_layer", "intermediate_size",
                                        "vocab_size", "max_seq_len")] + [("rope_base", C.c_float), ("norm_eps", C.c_float)]
+
+
+class ArRequest(C.Structure):
+    """svc_ar_request_t: one request of svc_ar_admit."""
+    _fields_ = [("slot", C.c_int32), ("S", C.c_int32), ("exp_noise", C.c_void_p), ("seed", C.c_uint64), ("max_new", C.c_int32),
+                ("min_tokens_before_eos", C.c_int32), ("temperature", C.c_float), ("top_p", C.c_float),
+                ("repetition_penalty", C.c_float), ("tokens_out", C.c_void_p)]
 
 
 class CampplusConfig(C.Structure):

@@ -7,7 +7,13 @@ last token's logits; `decode_step` is the hipGraph-captured one-token step (the 
 `decode_step_batch` run up to 64 sequences per decode step on them.  Without `exp_noise`, `generate` / `generate_batch`
 draw inside the sampler kernel from one 64-bit seed per sequence (`seed=` / `seeds=`, or fresh ones from torch's CPU
 generator): no noise tensor is allocated; `exp_draws` returns the draws a seed stands for.
+
+Continuous batching: `prefill_batch` prefills n sequences into n slots in one ragged pass; `generate_batch(...,
+prefill="ragged")` admits all B sequences with it and runs them on the session entry points (`svc_ar_admit / _run /
+_retire`); `ARSession` keeps the batch open -- requests are submitted at any time, enter free slots while others are in
+mid-sequence and leave when they finish.  A request's tokens do not depend on what else is in flight.
 """
+import collections
 import ctypes as C
 
 import torch
@@ -33,6 +39,8 @@ class ARModel:
         self._sep = state_dict["sep_token_emb"].detach().to(self.device, torch.float32) if "sep_token_emb" in state_dict else None
         self._emb = (state_dict["model.embeddings.weight"].detach().to(self.device, torch.float32)
                      if "model.embeddings.weight" in state_dict else None)
+        self.max_batch_size = 1
+        self._admitted = {}            # slot -> the admitted request (keeps its device tensors alive until it is retired)
 
     def setup_caches(self, max_batch_size=1, max_seq_len=None, dtype=None, device=None):
         """vc_wrapper.py:328-329.  The caches live in the handle: max_batch_size > 1 allocates one per slot
@@ -40,6 +48,7 @@ class ARModel:
         with torch.cuda.device(self.device):
             if max_batch_size > 1:
                 _lib.check(_lib.lib().svc_ar_set_max_batch(self._h, int(max_batch_size), _lib.stream_ptr()))
+                self.max_batch_size = int(max_batch_size)
             _lib.check(_lib.lib().svc_ar_reset(self._h, _lib.stream_ptr()))
 
     @torch.inference_mode()
@@ -129,6 +138,35 @@ class ARModel:
         return out.reshape(1, 1, -1)
 
     @torch.inference_mode()
+    def prefill_batch(self, slots, xs, input_pos, kv_pos):
+        """`prefill_slot` for n sequences in one ragged pass (`svc_ar_prefill_batch`): slots n distinct free slots, xs a list
+        of n (1, S_i, dim) tensors, input_pos / kv_pos lists of n position sequences -> logits (n, vocab)."""
+        n = len(slots)
+        if not (n == len(xs) == len(input_pos) == len(kv_pos)):
+            raise ValueError("prefill_batch: slots, xs, input_pos and kv_pos must have one entry per sequence")
+        with torch.cuda.device(self.device):
+            rows = [_lib.f32c(x, self.device).reshape(-1, self.cfg["dim"]) for x in xs]
+            S = [r.shape[0] for r in rows]
+            xx = torch.cat(rows, dim=0).contiguous() if n else torch.empty(1, self.cfg["dim"], device=self.device)
+            ip = [int(v) for p in input_pos for v in torch.as_tensor(p).reshape(-1).tolist()]
+            kp = [int(v) for p in kv_pos for v in torch.as_tensor(p).reshape(-1).tolist()]
+            if len(ip) != sum(S) or len(kp) != sum(S):
+                raise ValueError("prefill_batch: one input_pos and one kv_pos per row")
+            out = torch.empty(max(n, 1), self.cfg["vocab_size"], device=self.device)
+            _lib.check(_lib.lib().svc_ar_prefill_batch(self._h, n, (C.c_int32 * max(n, 1))(*[int(v) for v in slots]), _lib.ptr(xx),
+                                                       (C.c_int32 * max(n, 1))(*S), _lib.i64_host(ip + [0] * (not ip)),
+                                                       _lib.i64_host(kp + [0] * (not kp)), _lib.ptr(out), _lib.stream_ptr()))
+        return out[:n]
+
+    def set_prefill_rows(self, rows):
+        """Rows of one ragged-prefill pass (max_seq_len .. 8192, the default); a call with more rows runs as several passes."""
+        _lib.check(_lib.lib().svc_ar_set_prefill_rows(self._h, int(rows)))
+
+    def prefill_passes(self):
+        """Passes the last ragged prefill ran as."""
+        return int(_lib.lib().svc_ar_prefill_passes(self._h))
+
+    @torch.inference_mode()
     def decode_step_batch(self, x, input_pos=None, kv_pos=None):
         """One token for each of slots 0 .. B-1 from the captured batched step: x (B, dim) -> logits (B, vocab).  Pass the
         B input_pos / kv_pos on the first step of a batch only (then they auto-advance)."""
@@ -156,41 +194,59 @@ class ARModel:
 
     @torch.inference_mode()
     def generate_batch(self, prompt_texts, prompt_targets, exp_noise=None, top_p=0.7, temperature=0.7, repetition_penalty=1.5,
-                       max_new=4001, check_every=16, seeds=None):
+                       max_new=4001, check_every=16, seeds=None, prefill="slot"):
         """`generate` for B sequences at once (`svc_ar_generate_batch`; B <= the max_batch_size given to setup_caches):
         lists of B prompt_text (1, Tt_b, dim) and prompt_target (1, Tp_b) tensors, exp_noise a list of B (>= n_b, vocab)
         tensors of Exp(1) draws -> list of B (1, n_b) token tensors, each what `generate` gives for that sequence alone.
         Without exp_noise the sampler generates the draws from `seeds` (B integers; fresh ones from torch's CPU generator
-        when None, so `torch.manual_seed` governs them) and no noise tensor exists (`svc_ar_generate_batch_seeded`)."""
+        when None, so `torch.manual_seed` governs them) and no noise tensor exists (`svc_ar_generate_batch_seeded`).
+        prefill: "slot" prefills slot after slot inside that call; "ragged" admits all B at once with one ragged prefill and
+        runs them to completion on the session entry points (temperature, top_p and repetition_penalty may then be lists of B)."""
         toks, n = self.generate_batch_raw(prompt_texts, prompt_targets, exp_noise, top_p, temperature, repetition_penalty, max_new,
-                                          check_every, seeds)
+                                          check_every, seeds, prefill)
         return [toks[b, :n[b]].long()[None, :] for b in range(len(n))]
 
     @torch.inference_mode()
     def generate_batch_raw(self, prompt_texts, prompt_targets, exp_noise=None, top_p=0.7, temperature=0.7, repetition_penalty=1.5,
-                           max_new=4001, check_every=16, seeds=None):
+                           max_new=4001, check_every=16, seeds=None, prefill="slot"):
         """`generate_batch` without the per-sequence slicing: (tokens (B, max_new) int32 on the device, list of B counts);
         row b holds its sequence's tokens in [:n_b]."""
         V, D, Lmax = self.cfg["vocab_size"], self.cfg["dim"], self.cfg["max_seq_len"]
         B = len(prompt_texts)
+        if prefill not in ("slot", "ragged"):
+            raise ValueError('generate_batch: prefill must be "slot" or "ragged"')
         if B != len(prompt_targets) or (exp_noise is not None and len(exp_noise) != B) or (seeds is not None and len(seeds) != B):
             raise ValueError("generate_batch: prompt_texts, prompt_targets and exp_noise / seeds must have one entry per sequence")
         if exp_noise is not None and seeds is not None:
             raise ValueError("generate_batch: give exp_noise or seeds, not both")
         with torch.cuda.device(self.device):
-            sep = self._sep.reshape(1, D)
-            rows, S, input_pos, kv_pos = [], [], [], []
-            for text, tgt in zip(prompt_texts, prompt_targets):
-                text = _lib.f32c(text, self.device)[0]
-                tgt = tgt.to(self.device).long().reshape(-1)
-                rows += [sep, text, sep, self._emb[tgt]]
-                S.append(text.size(0) + 2 + tgt.numel())
-                input_pos += list(range(text.size(0) + 1)) + [0] + [i + 1 for i in range(tgt.numel())]
-                kv_pos += list(range(S[-1]))
-            emb_seq = torch.cat(rows, dim=0).contiguous()
+            emb_seq, S, input_pos, kv_pos = self._prompt_layout(prompt_texts, prompt_targets)
             cap = [min(int(max_new), Lmax - s + 1) for s in S]      # what `generate` allows each sequence
             max_new = max(cap)
             toks = torch.zeros(B, max_new, device=self.device, dtype=torch.int32)
+            if prefill == "ragged":
+                if exp_noise is None and seeds is None:
+                    seeds = torch.randint(0, 2 ** 62, (B,), dtype=torch.int64).tolist()
+                q = None if exp_noise is None else self._noise_layout(exp_noise, B, max_new, cap)
+                per = [v if isinstance(v, (list, tuple)) else [v] * B for v in (temperature, top_p, repetition_penalty)]
+                reqs, r0 = [], 0
+                for b in range(B):
+                    reqs.append(_Request(emb_seq[r0:r0 + S[b]], S[b], input_pos[r0:r0 + S[b]], kv_pos[r0:r0 + S[b]],
+                                         None if q is None else q[b], None if q is not None else seeds[b], max_new,
+                                         per[0][b], per[1][b], per[2][b], toks[b]))
+                    r0 += S[b]
+                self.session_admit(list(enumerate(reqs)), x=emb_seq)
+                try:
+                    while True:
+                        n, done = self.session_run(int(check_every) if check_every >= 1 else 16)
+                        if all(done[:B]):
+                            break
+                finally:
+                    for b in range(B):
+                        self.session_retire(b, 0)
+                return toks, list(n[:B])
+            if any(isinstance(v, (list, tuple)) for v in (temperature, top_p, repetition_penalty)):
+                raise ValueError('generate_batch: per-sequence sampling parameters need prefill="ragged"')
             n = (C.c_int32 * B)()
             tail = (max_new, 10, C.c_float(temperature), C.c_float(top_p), C.c_float(repetition_penalty), int(check_every),
                     _lib.ptr(toks), n, _lib.stream_ptr())
@@ -201,16 +257,95 @@ class ARModel:
                 sd = (C.c_uint64 * B)(*[int(v) & (2 ** 64 - 1) for v in seeds])
                 _lib.check(_lib.lib().svc_ar_generate_batch_seeded(*head, sd, *tail))
             else:
-                if torch.is_tensor(exp_noise) and tuple(exp_noise.shape) == (B, max_new, V):
-                    q = _lib.f32c(exp_noise, self.device)       # already in the call's layout: used as it is
-                else:
-                    q = torch.ones(B, max_new, V, device=self.device)
-                    for b, e in enumerate(exp_noise):
-                        assert e.shape[0] >= cap[b] and e.shape[1] == V
-                        k = min(e.shape[0], max_new)
-                        q[b, :k] = _lib.f32c(e, self.device)[:k]
+                q = self._noise_layout(exp_noise, B, max_new, cap)
                 _lib.check(_lib.lib().svc_ar_generate_batch(*head, _lib.ptr(q), *tail))
         return toks, list(n)
+
+    def _prompt_layout(self, prompt_texts, prompt_targets):
+        """The prompt of NaiveWrapper.generate (ar.py:390-396) for every sequence, concatenated: rows (sum S, dim) =
+        [sep, text, sep, embeddings of the target tokens] per sequence, list of S, input_pos and kv_pos of all rows."""
+        D = self.cfg["dim"]
+        sep = self._sep.reshape(1, D)
+        rows, S, input_pos, kv_pos = [], [], [], []
+        for text, tgt in zip(prompt_texts, prompt_targets):
+            text = _lib.f32c(text, self.device)[0]
+            tgt = tgt.to(self.device).long().reshape(-1)
+            rows += [sep, text, sep, self._emb[tgt]]
+            S.append(text.size(0) + 2 + tgt.numel())
+            input_pos += list(range(text.size(0) + 1)) + [0] + [i + 1 for i in range(tgt.numel())]
+            kv_pos += list(range(S[-1]))
+        return torch.cat(rows, dim=0).contiguous(), S, input_pos, kv_pos
+
+    def _noise_layout(self, exp_noise, B, max_new, cap):
+        """exp_noise (a list of B (>= cap_b, vocab) tensors, or one (B, max_new, vocab) tensor) as (B, max_new, vocab)."""
+        V = self.cfg["vocab_size"]
+        if torch.is_tensor(exp_noise) and tuple(exp_noise.shape) == (B, max_new, V):
+            return _lib.f32c(exp_noise, self.device)       # already in the call's layout: used as it is
+        q = torch.ones(B, max_new, V, device=self.device)
+        for b, e in enumerate(exp_noise):
+            assert e.shape[0] >= cap[b] and e.shape[1] == V
+            k = min(e.shape[0], max_new)
+            q[b, :k] = _lib.f32c(e, self.device)[:k]
+        return q
+
+    # ---- the backend of ARSession: requests, admit, run, retire
+    @torch.inference_mode()
+    def session_request(self, prompt_text, prompt_target, seed, exp_noise, max_new, top_p, temperature, repetition_penalty):
+        """One request as `session_admit` takes it; ValueError if its prompt does not fit the cache."""
+        V, Lmax = self.cfg["vocab_size"], self.cfg["max_seq_len"]
+        with torch.cuda.device(self.device):
+            rows, S, input_pos, kv_pos = self._prompt_layout([prompt_text], [prompt_target])
+            if S[0] > Lmax:
+                raise ValueError(f"ARSession: a prompt of {S[0]} rows does not fit the cache ({Lmax} positions)")
+            max_new = min(int(max_new), Lmax - S[0] + 1)
+            q = None
+            if exp_noise is not None:
+                e = _lib.f32c(exp_noise, self.device)
+                if e.dim() != 2 or e.shape[0] < max_new or e.shape[1] != V:
+                    raise ValueError("ARSession: exp_noise must be (>= max_new, vocab)")
+                q = e[:max_new].contiguous()
+            toks = torch.zeros(max_new, device=self.device, dtype=torch.int32)
+        return _Request(rows, S[0], input_pos, kv_pos, q, seed, max_new, temperature, top_p, repetition_penalty, toks)
+
+    @torch.inference_mode()
+    def session_admit(self, entries, x=None):
+        """entries: list of (slot, request) -> one `svc_ar_admit`.  x: the requests' rows already concatenated."""
+        n = len(entries)
+        with torch.cuda.device(self.device):
+            if x is None:
+                x = torch.cat([r.rows for _, r in entries], dim=0).contiguous()
+            reqs = (_lib.ArRequest * max(n, 1))()
+            ip, kp = [], []
+            for i, (slot, r) in enumerate(entries):
+                q = reqs[i]
+                q.slot, q.S, q.max_new, q.min_tokens_before_eos = int(slot), int(r.S), int(r.max_new), 10
+                q.exp_noise = r.noise.data_ptr() if r.noise is not None else None
+                q.seed = 0 if r.seed is None else int(r.seed) & (2 ** 64 - 1)
+                q.temperature, q.top_p, q.repetition_penalty = float(r.temperature), float(r.top_p), float(r.repetition_penalty)
+                q.tokens_out = r.toks.data_ptr()
+                ip += r.input_pos
+                kp += r.kv_pos
+            _lib.check(_lib.lib().svc_ar_admit(self._h, n, reqs, _lib.ptr(x), _lib.i64_host(ip), _lib.i64_host(kp), _lib.stream_ptr()))
+        for slot, r in entries:
+            self._admitted[int(slot)] = r
+
+    def session_run(self, n_steps):
+        """n_steps batched steps over the occupied slots -> (tokens so far, done flags), one entry per slot."""
+        nb = self.max_batch_size
+        n, done = (C.c_int32 * nb)(), (C.c_int32 * nb)()
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().svc_ar_run(self._h, int(n_steps), n, done, _lib.stream_ptr()))
+        return list(n), [bool(d) for d in done]
+
+    @torch.inference_mode()
+    def session_retire(self, slot, n_tokens):
+        """Frees `slot` and returns its first n_tokens tokens, (1, n_tokens); None if the slot holds no request."""
+        r = self._admitted.pop(int(slot), None)
+        if r is None:
+            return None
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().svc_ar_retire(self._h, int(slot), _lib.stream_ptr()))
+            return r.toks[:int(n_tokens)].long()[None, :]
 
     def close(self):
         if self._h:
@@ -222,3 +357,75 @@ class ARModel:
             self.close()
         except Exception:
             pass
+
+
+class _Request:
+    """One waiting or admitted sequence: its prompt rows and positions, draws (`noise` or `seed`), limits, sampling
+    parameters and token buffer."""
+    __slots__ = ("rows", "S", "input_pos", "kv_pos", "noise", "seed", "max_new", "temperature", "top_p", "repetition_penalty", "toks")
+
+    def __init__(self, rows, S, input_pos, kv_pos, noise, seed, max_new, temperature, top_p, repetition_penalty, toks):
+        self.rows, self.S, self.input_pos, self.kv_pos = rows, S, input_pos, kv_pos
+        self.noise, self.seed, self.max_new = noise, seed, max_new
+        self.temperature, self.top_p, self.repetition_penalty, self.toks = temperature, top_p, repetition_penalty, toks
+
+
+class ARSession:
+    """Continuous batching over the slots of one ARModel: FIFO, lowest free slot first.
+
+    `submit` queues a request and returns its ticket; `step` admits ALL waiting requests that fit into free slots in ONE
+    admit call (one ragged prefill), runs `steps_per_run` batched steps, retires what has finished and returns
+    [(ticket, tokens (1, n))]; `drain` steps until nothing is left.  A request's tokens do not depend on the other requests,
+    on its slot, on `steps_per_run` or on when it was admitted.  The class is plain Python: everything that touches the
+    device is the backend's (`ar.max_batch_size`, `ar.session_request / _admit / _run / _retire`)."""
+
+    def __init__(self, ar, steps_per_run=16):
+        if steps_per_run < 1:
+            raise ValueError("ARSession: steps_per_run must be at least 1")
+        self.ar, self.steps_per_run = ar, int(steps_per_run)
+        self._waiting = collections.deque()        # (ticket, request)
+        self._active = {}                          # slot -> ticket
+        self._next_ticket = 0
+
+    @property
+    def n_active(self):
+        return len(self._active)
+
+    @property
+    def n_waiting(self):
+        return len(self._waiting)
+
+    def submit(self, prompt_text, prompt_target, *, seed=None, exp_noise=None, max_new=4001, top_p=0.7, temperature=0.7,
+               repetition_penalty=1.5):
+        if (seed is None) == (exp_noise is None):
+            raise ValueError("ARSession.submit: give exactly one of seed / exp_noise")
+        req = self.ar.session_request(prompt_text, prompt_target, seed, exp_noise, max_new, top_p, temperature, repetition_penalty)
+        ticket = self._next_ticket
+        self._next_ticket += 1
+        self._waiting.append((ticket, req))
+        return ticket
+
+    def step(self):
+        free = [b for b in range(self.ar.max_batch_size) if b not in self._active]
+        entries = []
+        while self._waiting and free:
+            ticket, req = self._waiting.popleft()
+            slot = free.pop(0)
+            self._active[slot] = ticket
+            entries.append((slot, req))
+        if entries:
+            self.ar.session_admit(entries)
+        if not self._active:
+            return []
+        n_tokens, done = self.ar.session_run(self.steps_per_run)
+        out = []
+        for slot in sorted(self._active):
+            if done[slot]:
+                out.append((self._active.pop(slot), self.ar.session_retire(slot, n_tokens[slot])))
+        return out
+
+    def drain(self):
+        out = []
+        while self._waiting or self._active:
+            out += self.step()
+        return out

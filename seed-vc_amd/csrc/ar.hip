@@ -3,6 +3,7 @@
 // exponential-race sampler.  Every kernel and its launch function lives in a header that only this file includes:
 //   ar_common.h   generate-loop state (GenState, GenSlot), MAXB, SORT_N, cross-lane sums, the ar_base size dispatch
 //   ar_prefill.h  GEMV-pair linears (S <= 8 rows), RoPE + cache scatter, prefill attention
+//   ar_prefill_attn.h  the ragged prefill of n sequences in one pass (RoPE / scatter per row's slot, MFMA attention), admission
 //   ar_decode1.h  the S = 1 decode step, three launches per layer
 //   ar_batch.h    the batched decode step: skinny MFMA GEMM, one-token attention per slot
 //   ar_sampler.h  Philox draws, rank / sample kernels (one sequence and per slot), token embedding
@@ -22,6 +23,12 @@
 // per slot (svc_ar_set_max_batch / _prefill_slot / _decode_step_batch / _generate_batch).  The B = 1 entry points work on
 // slot 0, which exists from svc_ar_create on.
 //
+// Sessions (svc_ar_admit / _run / _retire) keep that batch open: sequences enter free slots while others are in
+// mid-sequence (one ragged prefill for all newcomers, svc_ar_prefill_batch), the captured batched step runs over slots
+// 0 .. highest occupied one, and a finished sequence frees its slot for the next.  Free slots sit in the batch as finished
+// slots.  While a session is active the closed-batch entry points and svc_ar_set_max_batch are refused (they share the
+// slot state), and so are the B = 1 calls while slot 0 is occupied.
+//
 // reference: modules/v2/ar.py:239-267 (forward_generate), :75-93 (KVCache.update), :503-567 (Attention),
 //            :600-651 (RMSNorm, bf16 RoPE table), :712-763 (sample / logits_to_probs / exponential race).
 #include <string.h>
@@ -32,6 +39,7 @@
 
 #include "ar_common.h"
 #include "ar_prefill.h"
+#include "ar_prefill_attn.h"
 #include "ar_decode1.h"
 #include "ar_batch.h"
 #include "ar_sampler.h"
@@ -130,7 +138,41 @@ struct svc_ar {
     int set_nb(int B, hipStream_t st);
     int run_batch_step(int Bp, hipStream_t st);
     int ensure_batch_graph(int Bp, bool gen);
+
+    // ---- ragged prefill (svc_ar_prefill_batch, svc_ar_admit).  A pass takes at most `prows_max` rows (PREFILL_ROWS unless
+    // svc_ar_set_prefill_rows lowers it; never less than max_seq_len, so a sequence always fits); a call with more rows runs
+    // as several passes of whole sequences.  The workspace is apart from `ws` and `bws`: no captured graph holds a pointer
+    // into it, so it grows with the largest pass seen.
+    static constexpr int PREFILL_ROWS = 8192;
+    Arena pws;
+    int pcap = 0, prows_max = PREFILL_ROWS, last_passes = 0;
+    float *ph32 = nullptr, *pqkv32 = nullptr, *pq32 = nullptr;
+    half_t *pn16 = nullptr, *py16 = nullptr, *pff16 = nullptr;
+    int* d_ptab = nullptr;             // the pass's tables (PrefillTabs)
+    float *plast = nullptr, *plogits = nullptr;      // [MAXB][D] last rows, [MAXB][V] first-token logits of an admission (in bws)
+    AdmitRec* d_admit = nullptr;       // [MAXB] (in bws)
+    int* d_idle_tok = nullptr;         // the one token (0) a free slot "has generated" (in bws)
+    int reserve_prefill(int rows, hipStream_t st);
+    int check_prefill_args(int n, const int* slots, const int32_t* S, const int64_t* input_pos, const int64_t* kv_pos) const;
+    int prefill_batch(int n, const int* slots, const float* x, const int32_t* S, const int64_t* input_pos, const int64_t* kv_pos,
+                      float* logits_out, hipStream_t st);
+    int prefill_pass(int n, const int* slots, const float* x, const int32_t* S, const int64_t* input_pos, const int64_t* kv_pos,
+                     float* logits_out, hipStream_t st);
+
+    // ---- session: which slots hold an admitted sequence.  Active = n_occupied > 0.
+    bool occupied[MAXB] = {};
+    int n_occupied = 0;
+    GenSlot idle_slot() const {
+        GenSlot g;
+        memset(&g, 0, sizeof(g));
+        g.toks = d_idle_tok; g.cnt = 1; g.eos = V - 1; g.temperature = 1.f; g.top_p = 1.f; g.rep_pen = 1.f;
+        g.done = 1; g.max_new = 1;
+        return g;
+    }
 };
+
+#define SVC_AR_NO_SESSION(m) SVC_REQUIRE(!(m)->n_occupied, "AR: a session is active (svc_ar_admit): retire every slot first")
+#define SVC_AR_SLOT0_FREE(m) SVC_REQUIRE(!(m)->occupied[0], "AR: a session is active and holds slot 0, the cache of the B = 1 calls")
 
 namespace {
 // out[s] = (res ? res[s] : 0) + W x[s] on the tap-GEMM (S > 8 rows); GLU: rows (2j, 2j+1) of W are (w1_j, w3_j) ->
@@ -271,6 +313,115 @@ int svc_ar::run_head(int S, float* logits_out, hipStream_t st) {
     return gemv_pair_launch<true, GV_PLAIN>(a, st);
 }
 
+// ---- ragged prefill ------------------------------------------------------------------------------------------------
+int svc_ar::reserve_prefill(int rows, hipStream_t st) {
+    if (rows <= pcap) return 0;
+    SVC_CHECK_HIP(hipStreamSynchronize(st));
+    pws.release();
+    pcap = 0;
+    const long R = rows;
+    ph32 = pws.alloc_n<float>(R * D, st);
+    pqkv32 = pws.alloc_n<float>(R * Nqkv, st);
+    pq32 = pws.alloc_n<float>(R * D, st);
+    pn16 = pws.alloc_n<half_t>(R * D, st);
+    py16 = pws.alloc_n<half_t>(R * D, st);
+    pff16 = pws.alloc_n<half_t>(R * I, st);
+    d_ptab = pws.alloc_n<int>(3 * R + 3 * (R / PA_ROWS + MAXB) + MAXB, st);
+    if (!ph32 || !pqkv32 || !pq32 || !pn16 || !py16 || !pff16 || !d_ptab) {
+        pws.release();
+        return 1;
+    }
+    SVC_CHECK_HIP(hipStreamSynchronize(st));
+    pcap = rows;
+    return 0;
+}
+
+// Everything a ragged prefill needs from its arguments, before anything is launched.
+int svc_ar::check_prefill_args(int n, const int* slots, const int32_t* S, const int64_t* input_pos, const int64_t* kv_pos) const {
+    SVC_REQUIRE(n >= 1 && n <= max_batch, "AR: n outside 1 .. max_batch (svc_ar_set_max_batch)");
+    bool seen[MAXB] = {};
+    long rows = 0;
+    for (int i = 0; i < n; ++i) {
+        SVC_REQUIRE(slots[i] >= 0 && slots[i] < max_batch, "AR: slot outside 0 .. max_batch - 1 (svc_ar_set_max_batch)");
+        SVC_REQUIRE(!seen[slots[i]], "AR: duplicate slot");
+        SVC_REQUIRE(!occupied[slots[i]], "AR: slot is occupied by a session (svc_ar_retire)");
+        seen[slots[i]] = true;
+        SVC_REQUIRE(S[i] >= 1 && S[i] <= prows_max, "AR: S outside 1 .. rows of a prefill pass");
+        SVC_REQUIRE(rows_in_cache(input_pos + rows, kv_pos + rows, S[i]), "position out of range");
+        rows += S[i];
+    }
+    return 0;
+}
+
+// One pass: n whole sequences, R <= prows_max rows, through every layer; logits of each sequence's last row.
+int svc_ar::prefill_pass(int n, const int* slots, const float* x, const int32_t* S, const int64_t* input_pos, const int64_t* kv_pos,
+                         float* logits_out, hipStream_t st) {
+    long R = 0;
+    int T = 0;
+    for (int i = 0; i < n; ++i) { R += S[i]; T += cdiv(S[i], PA_ROWS); }
+    if (reserve_prefill((int)R, st)) return 1;
+    std::vector<int> tab(3 * R + 3 * T + n);
+    int *ip = tab.data(), *kp = ip + R, *rs = kp + R, *tiles = rs + R, *last = tiles + 3 * T;
+    long r = 0;
+    for (int i = 0; i < n; ++i) {
+        for (int s0 = 0; s0 < S[i]; s0 += PA_ROWS) {
+            *tiles++ = (int)r + s0;
+            *tiles++ = std::min(PA_ROWS, S[i] - s0);
+            *tiles++ = slots[i];
+        }
+        for (int s = 0; s < S[i]; ++s, ++r) {
+            ip[r] = (int)input_pos[r];
+            kp[r] = (int)kv_pos[r];
+            rs[r] = slots[i];
+        }
+        last[i] = (int)r - 1;
+    }
+    SVC_CHECK_HIP(hipMemcpyAsync(d_ptab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    SVC_CHECK_HIP(hipStreamSynchronize(st));
+    const PrefillTabs tb{d_ptab, d_ptab + R, d_ptab + 2 * R, d_ptab + 3 * R, d_ptab + 3 * R + 3 * T};
+    SVC_CHECK_HIP(hipMemcpyAsync(ph32, x, (size_t)R * D * 4, hipMemcpyDeviceToDevice, st));
+    const int Rr = (int)R;
+    for (int i = 0; i < L; ++i) {
+        const Layer& ly = layers[i];
+        float* const* kct = d_kvtab + ((size_t)i * 2) * MAXB;
+        float* const* vct = d_kvtab + ((size_t)i * 2 + 1) * MAXB;
+        if (rmsnorm_mod_launch(ph32, D, pn16, D, ly.g_attn, nullptr, nullptr, 0, 0, Rr, D, Rr, cfg.norm_eps, st)) return 1;
+        if (lin(pn16, ly.wqkv, D, nullptr, pqkv32, nullptr, Nqkv, Rr, Nqkv, D, false, st)) return 1;
+        if (ar_rope_cache_ragged_launch(pqkv32, Nqkv, pq32, kct, vct, rope, tb, Rr, H, Hkv, Lmax, st)) return 1;
+        if (ar_prefill_attn_launch(pq32, kct, vct, py16, tb, T, H, Hkv, Lmax, st)) return 1;
+        if (lin(py16, ly.wo, D, ph32, ph32, nullptr, D, Rr, D, D, false, st)) return 1;
+        if (rmsnorm_mod_launch(ph32, D, pn16, D, ly.g_ffn, nullptr, nullptr, 0, 0, Rr, D, Rr, cfg.norm_eps, st)) return 1;
+        if (lin(pn16, ly.w13, D, nullptr, nullptr, pff16, I, Rr, 2 * I, D, true, st)) return 1;
+        if (lin(pff16, ly.w2, I, ph32, ph32, nullptr, D, Rr, D, I, false, st)) return 1;
+    }
+    // head: final RMSNorm fused into the output GEMV, on the last row of every sequence, eight rows per launch
+    if (ar_gather_rows_launch(ph32, tb.last, plast, D, n, st)) return 1;
+    for (int j0 = 0; j0 < n; j0 += 8) {
+        GemvArgs a(plast + (long)j0 * D, D, w_out, D, std::min(8, n - j0), V, D);
+        a.gamma = g_final; a.eps = cfg.norm_eps; a.out32 = logits_out + (long)j0 * V; a.ldo = V;
+        if (gemv_pair_launch<true, GV_PLAIN>(a, st)) return 1;
+    }
+    return 0;
+}
+
+// svc_ar_prefill_slot for n sequences at once (arguments checked by the caller): passes of whole sequences, greedily.
+int svc_ar::prefill_batch(int n, const int* slots, const float* x, const int32_t* S, const int64_t* input_pos, const int64_t* kv_pos,
+                          float* logits_out, hipStream_t st) {
+    if (ensure_batch_ws(st)) return 1;
+    last_passes = 0;
+    long row0 = 0;
+    for (int i0 = 0; i0 < n;) {
+        int i1 = i0;
+        long R = 0;
+        while (i1 < n && R + S[i1] <= prows_max) R += S[i1++];
+        if (prefill_pass(i1 - i0, slots + i0, x + row0 * D, S + i0, input_pos + row0, kv_pos + row0, logits_out + (long)i0 * V, st)) return 1;
+        ++last_passes;
+        row0 += R;
+        i0 = i1;
+    }
+    return 0;
+}
+
 namespace {
 // Captures the launches `body` issues on a fresh stream into `exec`.
 template <class F>
@@ -346,8 +497,12 @@ int svc_ar::ensure_batch_ws(hipStream_t st) {
     b_sidx = bws.alloc_n<int>((size_t)MAXB * SORT_N, st);
     b_lgp = bws.alloc_n<float>((size_t)MAXB * SORT_N, st);
     d_kvtab = reinterpret_cast<float**>(bws.alloc((size_t)L * 2 * MAXB * sizeof(float*), st));
+    plast = bws.alloc_n<float>((size_t)MAXB * D, st);
+    plogits = bws.alloc_n<float>((size_t)MAXB * V, st);
+    d_admit = reinterpret_cast<AdmitRec*>(bws.alloc(MAXB * sizeof(AdmitRec), st));
+    d_idle_tok = bws.alloc_n<int>(1, st);
     int* nb = bws.alloc_n<int>(1, st);
-    if (!bh || !bq || !blogits || !by16 || !bff16 || !d_bpos || !d_slots || !b_skey || !b_sidx || !b_lgp || !d_kvtab || !nb) {
+    if (!plast || !plogits || !d_admit || !d_idle_tok || !bh || !bq || !blogits || !by16 || !bff16 || !d_bpos || !d_slots || !b_skey || !b_sidx || !b_lgp || !d_kvtab || !nb) {
         bws.release();
         return 1;
     }
@@ -546,6 +701,7 @@ void svc_ar_destroy(svc_ar_t* m) { delete m; }
 
 int svc_ar_reset(svc_ar_t* m, void* stream) {
     SVC_REQUIRE(m, "null argument");
+    SVC_AR_SLOT0_FREE(m);
     for (int i = 0; i < 2 * m->L; ++i)          // slot 0 only
         SVC_CHECK_HIP(hipMemsetAsync(m->cache[i], 0, m->cache_elems() * 4, (hipStream_t)stream));
     return 0;
@@ -554,6 +710,7 @@ int svc_ar_reset(svc_ar_t* m, void* stream) {
 int svc_ar_forward_generate(svc_ar_t* m, const float* x, int S, const int64_t* input_pos, const int64_t* kv_pos, float* logits_out,
                             void* stream) {
     SVC_REQUIRE(m && x && input_pos && kv_pos && logits_out && S >= 1, "bad argument");
+    SVC_AR_SLOT0_FREE(m);
     return m->prefill(0, x, S, input_pos, kv_pos, logits_out, (hipStream_t)stream, true);      // one row: the decode step
 }
 
@@ -561,6 +718,7 @@ int svc_ar_forward_generate(svc_ar_t* m, const float* x, int S, const int64_t* i
 // positions {input_pos, kv_pos}; every replay advances both by one, as NaiveWrapper.generate does (ar.py:402-403).
 int svc_ar_decode_step(svc_ar_t* m, const float* x, int set_pos, int64_t input_pos, int64_t kv_pos, float* logits_out, void* stream) {
     SVC_REQUIRE(m && x && logits_out, "bad argument");
+    SVC_AR_SLOT0_FREE(m);
     hipStream_t st = (hipStream_t)stream;
     if (m->reserve(1, st)) return 1;
     if (set_pos) {
@@ -584,6 +742,7 @@ int svc_ar_generate(svc_ar_t* m, const float* x_prefill, int S, const int64_t* i
                     float repetition_penalty, int check_every, int32_t* tokens_out, int32_t* n_tokens, void* stream) {
     SVC_REQUIRE(m && x_prefill && input_pos && kv_pos && exp_noise && tokens_out && n_tokens && S >= 1 && max_new >= 1, "bad argument");
     SVC_REQUIRE(m->emb, "svc_ar_generate needs model.embeddings.weight in the state dict given to svc_ar_create");
+    SVC_AR_SLOT0_FREE(m);
     hipStream_t st = (hipStream_t)stream;
     const int V = m->V, eos = V - 1;
     if (check_every < 1) check_every = 16;
@@ -626,6 +785,7 @@ int svc_ar_generate(svc_ar_t* m, const float* x_prefill, int S, const int64_t* i
 int svc_ar_set_max_batch(svc_ar_t* m, int max_batch, void* stream) {
     SVC_REQUIRE(m, "null argument");
     SVC_REQUIRE(max_batch >= 1 && max_batch <= MAXB, "AR: max_batch must be 1 .. 64");
+    SVC_AR_NO_SESSION(m);
     hipStream_t st = (hipStream_t)stream;
     if (m->ensure_batch_ws(st)) return 1;
     if (max_batch == m->max_batch) return 0;
@@ -652,6 +812,7 @@ int svc_ar_prefill_slot(svc_ar_t* m, int slot, const float* x, int S, const int6
                         void* stream) {
     SVC_REQUIRE(m && x && input_pos && kv_pos && logits_out && S >= 1, "bad argument");
     SVC_REQUIRE(slot >= 0 && slot < m->max_batch, "AR: slot outside max_batch (svc_ar_set_max_batch)");
+    SVC_REQUIRE(!m->occupied[slot], "AR: slot is occupied by a session (svc_ar_retire)");
     hipStream_t st = (hipStream_t)stream;
     if (m->ensure_batch_ws(st)) return 1;
     return m->prefill(slot, x, S, input_pos, kv_pos, logits_out, st);
@@ -660,6 +821,7 @@ int svc_ar_prefill_slot(svc_ar_t* m, int slot, const float* x, int S, const int6
 int svc_ar_decode_step_batch(svc_ar_t* m, int B, const float* x, int set_pos, const int64_t* input_pos, const int64_t* kv_pos,
                              float* logits_out, void* stream) {
     SVC_REQUIRE(m, "null argument");
+    SVC_AR_NO_SESSION(m);
     SVC_REQUIRE(B >= 1 && B <= m->max_batch, "AR: batch outside 1 .. max_batch (svc_ar_set_max_batch)");
     SVC_REQUIRE(x && logits_out, "bad argument");
     hipStream_t st = (hipStream_t)stream;
@@ -701,6 +863,7 @@ static int ar_generate_batch(svc_ar_t* m, int B, const float* x_prefill, const i
                              const float* exp_noise, const uint64_t* seeds, int max_new, int min_tokens_before_eos, float temperature,
                              float top_p, float repetition_penalty, int check_every, int32_t* tokens_out, int32_t* n_tokens, void* stream) {
     SVC_REQUIRE(m, "null argument");
+    SVC_AR_NO_SESSION(m);
     SVC_REQUIRE(B >= 1 && B <= m->max_batch, "AR: batch outside 1 .. max_batch (svc_ar_set_max_batch)");
     SVC_REQUIRE(x_prefill && S && input_pos && kv_pos && (exp_noise || seeds) && tokens_out && n_tokens && max_new >= 1, "bad argument");
     SVC_REQUIRE(m->emb, "svc_ar_generate_batch needs model.embeddings.weight in the state dict given to svc_ar_create");
@@ -768,6 +931,107 @@ int svc_ar_generate_batch_seeded(svc_ar_t* m, int B, const float* x_prefill, con
     return ar_generate_batch(m, B, x_prefill, S, input_pos, kv_pos, nullptr, seeds, max_new, min_tokens_before_eos, temperature, top_p,
                              repetition_penalty, check_every, tokens_out, n_tokens, stream);
 }
+
+int svc_ar_set_prefill_rows(svc_ar_t* m, int rows) {
+    SVC_REQUIRE(m, "null argument");
+    SVC_REQUIRE(rows >= m->Lmax && rows <= svc_ar::PREFILL_ROWS, "AR: rows of a prefill pass must be max_seq_len .. 8192");
+    m->prows_max = rows;
+    return 0;
+}
+
+int svc_ar_prefill_passes(svc_ar_t* m) { return m ? m->last_passes : -1; }
+
+int svc_ar_prefill_batch(svc_ar_t* m, int n, const int32_t* slots, const float* x, const int32_t* S, const int64_t* input_pos,
+                         const int64_t* kv_pos, float* logits_out, void* stream) {
+    SVC_REQUIRE(m && slots && x && S && input_pos && kv_pos && logits_out, "bad argument");
+    if (m->check_prefill_args(n, slots, S, input_pos, kv_pos)) return 1;
+    return m->prefill_batch(n, slots, x, S, input_pos, kv_pos, logits_out, (hipStream_t)stream);
+}
+
+int svc_ar_admit(svc_ar_t* m, int n, const svc_ar_request_t* requests, const float* x_prefill, const int64_t* input_pos,
+                 const int64_t* kv_pos, void* stream) {
+    SVC_REQUIRE(m && requests && x_prefill && input_pos && kv_pos, "bad argument");
+    SVC_REQUIRE(n >= 1 && n <= m->max_batch, "AR: n outside 1 .. max_batch (svc_ar_set_max_batch)");
+    SVC_REQUIRE(m->emb, "svc_ar_admit needs model.embeddings.weight in the state dict given to svc_ar_create");
+    int slots[MAXB];
+    int32_t S[MAXB];
+    for (int i = 0; i < n; ++i) {
+        SVC_REQUIRE(requests[i].max_new >= 1 && requests[i].tokens_out, "bad argument: max_new / tokens_out of a request");
+        slots[i] = requests[i].slot;
+        S[i] = requests[i].S;
+    }
+    if (m->check_prefill_args(n, slots, S, input_pos, kv_pos)) return 1;
+    hipStream_t st = (hipStream_t)stream;
+    const int V = m->V, eos = V - 1;
+    if (m->ensure_batch_ws(st) || m->reserve(1, st)) return 1;       // reserve: the first token's sampler scratch
+    if (!m->n_occupied) {
+        // a session begins: every slot a finished one with valid positions, a zero row as its step input
+        if (ar_idle_slots_launch(m->d_slots, m->d_bpos, m->idle_slot(), 0, MAXB, st)) return 1;
+        SVC_CHECK_HIP(hipMemsetAsync(m->bh, 0, (size_t)MAXB * m->D * 4, st));
+        m->bpos_n = 0;
+    }
+    if (m->prefill_batch(n, slots, x_prefill, S, input_pos, kv_pos, m->plogits, st)) return 1;
+    std::vector<AdmitRec> recs(n);
+    long rows = 0;
+    for (int i = 0; i < n; ++i) {
+        const svc_ar_request_t& q = requests[i];
+        AdmitRec& a = recs[i];
+        memset(&a, 0, sizeof(a));
+        // first token: EOS suppressed, no previous tokens (ar.py:399-401), as begin_generate samples it
+        if (m->sample(m->plogits + (size_t)i * V, nullptr, 0, eos, q.temperature, q.top_p, q.repetition_penalty, q.exp_noise, q.tokens_out,
+                      nullptr, nullptr, st, false, (unsigned long long)q.seed, 0))
+            return 1;
+        rows += S[i];
+        GenSlot& g = a.g;
+        g.noise = q.exp_noise; g.seed = q.exp_noise ? 0ull : (unsigned long long)q.seed; g.toks = q.tokens_out; g.cnt = 1;
+        g.min_before_eos = q.min_tokens_before_eos; g.eos = eos;
+        g.temperature = q.temperature; g.top_p = q.top_p; g.rep_pen = q.repetition_penalty;
+        g.max_new = q.max_new;
+        const int ip = (int)input_pos[rows - 1] + 1, kp = (int)kv_pos[rows - 1] + 1;
+        g.done = q.max_new <= 1 || ip >= m->Lmax || kp >= m->Lmax;      // admitted as finished: it keeps valid positions
+        a.slot = q.slot;
+        a.ip = g.done ? ip - 1 : ip;
+        a.kp = g.done ? kp - 1 : kp;
+    }
+    SVC_CHECK_HIP(hipMemcpyAsync(m->d_admit, recs.data(), (size_t)n * sizeof(AdmitRec), hipMemcpyHostToDevice, st));
+    if (ar_admit_launch(m->d_admit, n, m->d_slots, m->d_bpos, m->emb, m->bh, m->D, st)) return 1;
+    SVC_CHECK_HIP(hipStreamSynchronize(st));        // `recs` may go
+    for (int i = 0; i < n; ++i) m->occupied[slots[i]] = true;
+    m->n_occupied += n;
+    return 0;
+}
+
+int svc_ar_run(svc_ar_t* m, int n_steps, int32_t* n_tokens, int32_t* done, void* stream) {
+    SVC_REQUIRE(m && n_tokens && done && n_steps >= 0, "bad argument");
+    SVC_REQUIRE(m->n_occupied > 0, "AR: no session is active (svc_ar_admit)");
+    hipStream_t st = (hipStream_t)stream;
+    int B = 0;
+    for (int b = 0; b < m->max_batch; ++b) if (m->occupied[b]) B = b + 1;
+    const int Bp = (int)round_up(B, 16);
+    if (m->set_nb(B, st) || m->ensure_batch_graph(Bp, true)) return 1;
+    for (int t = 0; t < n_steps; ++t) SVC_CHECK_HIP(hipGraphLaunch(m->bgen_graph[Bp / 16 - 1].exec, st));
+    std::vector<GenSlot> slots(B);
+    SVC_CHECK_HIP(hipMemcpyAsync(slots.data(), m->d_slots, (size_t)B * sizeof(GenSlot), hipMemcpyDeviceToHost, st));
+    SVC_CHECK_HIP(hipStreamSynchronize(st));
+    for (int b = 0; b < m->max_batch; ++b) {
+        const bool occ = b < B && m->occupied[b];
+        n_tokens[b] = occ ? slots[b].cnt : 0;
+        done[b] = occ ? slots[b].done : 1;
+    }
+    return 0;
+}
+
+int svc_ar_retire(svc_ar_t* m, int slot, void* stream) {
+    SVC_REQUIRE(m, "null argument");
+    SVC_REQUIRE(slot >= 0 && slot < m->max_batch && m->occupied[slot], "AR: slot is not occupied (svc_ar_admit)");
+    // the slot becomes a finished one that records nothing, also when its sequence was still running
+    if (ar_idle_slots_launch(m->d_slots, m->d_bpos, m->idle_slot(), slot, 1, (hipStream_t)stream)) return 1;
+    m->occupied[slot] = false;
+    m->n_occupied -= 1;
+    return 0;
+}
+
+int svc_ar_session_active(svc_ar_t* m) { return m ? m->n_occupied : 0; }
 
 int svc_ar_exp_draws(svc_ar_t* m, uint64_t seed, int step0, int n_steps, float* out, void* stream) {
     SVC_REQUIRE(m && out && step0 >= 0 && n_steps >= 1 && n_steps <= 65535, "bad argument");

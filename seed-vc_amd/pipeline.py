@@ -400,9 +400,10 @@ class V2HotPath:
     ragged_vocoder: a batch of more than one output length takes ONE vocoder call with per-utterance lengths (True) or one
     call per distinct length (False); a batch of one length is one plain call either way."""
 
-    def __init__(self, ar, ar_lr, cfm_lr, cfm, vocoder, ragged_vocoder=True):
+    def __init__(self, ar, ar_lr, cfm_lr, cfm, vocoder, ragged_vocoder=True, ar_prefill="slot"):
         self.ar, self.ar_lr, self.cfm_lr, self.cfm, self.vocoder = ar, ar_lr, cfm_lr, cfm, vocoder
         self.ragged_vocoder = ragged_vocoder
+        self.ar_prefill = ar_prefill           # "slot" | "ragged": how the AR prompts are prefilled (ARModel.generate_batch)
         self.device = cfm.device
         self._stacked = (None, None)
         self.marks = None           # a list: convert_batch appends (stage name, HIP event) at its stage boundaries (tools/v2_bench.py)
@@ -471,7 +472,8 @@ class V2HotPath:
                 tok_in[b, :nlen[b]] = x[0]
             ar_cond = self.ar_lr(tok_in, in_lens=nlen)[0]
             toks, n = self.ar.generate_batch_raw([ar_cond[b:b + 1, :nlen[b]] for b in range(B)], [t["tokens"] for t in targets],
-                                                 exp_noise, top_p, temperature, repetition_penalty, max_new, 16, seeds)
+                                                 exp_noise, top_p, temperature, repetition_penalty, max_new, 16, seeds,
+                                                 self.ar_prefill)
             self._mark("ar")
             # ---- the one synchronisation is behind us: n is a list of host integers
             ylens = [v2_target_frames(f, k) for f, k in zip(frames_per_token, n)]
