@@ -443,6 +443,37 @@ int svc_op_linear(const float* a, const float* w, const float* bias, float* c, i
  * y [B][Lout][Cout]; pad_mode 0 zero / 1 reflect / 2 replicate; explicit left pad. */
 int svc_op_conv1d(const float* x, const float* w, const float* bias, float* y, int B, int L, int Cin, int Cout,
                   int k, int dilation, int stride, int pad_left, int Lout, int pad_mode, int dtype, void* stream);
+/* Test aid (tests/test_gpu_kconv.py; no model uses it): one stride-1, zero-padded channels-last Conv1d with everything a
+ * ConvRun of the vocoders can carry, and a report of the kernel that ran.  Device pointers unless noted; NULL = absent.
+ *   x [B][L][Cin] fp32, or a_hi / a_lo: ready operand planes [B][L][cin_pad] (16-bit words, cin_pad = Cin rounded up to 64) as
+ *   a fused Snake wrote them;  w [Cout][Cin][k], bias [Cout].
+ *   dtype 0 fp16, 2 fp16x3, 3 fp16 + fp8 corrections (lo plane as byte pairs; needs a shape the resident-tile kernel takes).
+ *   seq_len: HOST [B] valid input rows per sequence (the ragged form; needs Lout == L).
+ *   epilogue, in this order: + bias, act (KG_ACT_* value, act_slope), + res, * out_scale (0 = 1), + res2;
+ *   y, res, res2 [B][c_rows][Cout] fp32 (c_rows 0 = Lout); the conv writes rows c_off .. c_off + Lout of y, the others are kept.
+ *   post_a / post_ib [Cout]: fused Snake sv = v + post_ib sin^2(post_a v) towards plane_hi / plane_lo [B][c_rows][cout_pad]
+ *   (raw 16-bit words over all cout_pad = Cout rounded up to 64 columns, written in place): hi = fp16(sv), lo = fp16(sv - hi) or,
+ *   with next_p8, the byte pair (fp8(hi), fp8(2^11 (sv - hi))); y keeps v.
+ *   bm: resident-tile position-tile override 64 | 128 | 256 (0 = the launch's choice; 128-channel form only).
+ *   force_gemm: run on the tap-GEMM (not with byte-pair planes).
+ *   took (out): 0 = tap-GEMM; else bit 0 set, bits 8..19 = BM, bits 20.. = BN of the resident-tile instantiation launched. */
+typedef struct {
+    const float* x; const uint16_t* a_hi; const uint16_t* a_lo;
+    const float* w; const float* bias;
+    int32_t B, L, Cin, Cout, k, dilation, pad_left, Lout, dtype;
+    const int32_t* seq_len;
+    const float* res; const float* res2;
+    float out_scale; int32_t act; float act_slope;
+    int32_t c_rows, c_off;
+    const float* post_a; const float* post_ib; int32_t next_p8;
+    int32_t bm, force_gemm;
+    float* y; uint16_t* plane_hi; uint16_t* plane_lo;
+    int32_t took;
+} svc_conv1d_ex_t;
+int svc_op_conv1d_ex(svc_conv1d_ex_t* args, void* stream);
+/* Test aid: the `took` word of this thread's last successful svc_op_conv1d or svc_op_conv1d_ex call (the first has no argument
+ * for it). */
+int svc_op_conv1d_last_took(void);
 /* ConvTranspose1d (k = 2*stride, padding = stride/2): x [B][L][Cin], w [Cin][Cout][k], y [B][L*stride][Cout]. */
 int svc_op_conv_transpose1d(const float* x, const float* w, const float* bias, float* y, int B, int L, int Cin,
                             int Cout, int k, int stride, int dtype, void* stream);

@@ -28,7 +28,7 @@ EXPORTS = [
     "svc_campplus_create", "svc_campplus_destroy", "svc_campplus_forward", "svc_kaldi_fbank_frames", "svc_kaldi_fbank",
     "svc_mel_create", "svc_mel_destroy", "svc_mel_frames", "svc_mel_forward",
     "svc_prof_enable", "svc_prof_collect",
-    "svc_op_linear", "svc_op_conv1d", "svc_op_conv_transpose1d", "svc_op_attention", "svc_op_rmsnorm",
+    "svc_op_linear", "svc_op_conv1d", "svc_op_conv1d_ex", "svc_op_conv1d_last_took", "svc_op_conv_transpose1d", "svc_op_attention", "svc_op_rmsnorm",
 ]
 
 
@@ -92,6 +92,16 @@ class LrConfig(C.Structure):
                                        "interpolate", "has_final_conv", "f0_condition", "n_f0_bins")]
 
 
+class Conv1dEx(C.Structure):
+    """svc_conv1d_ex_t: the arguments of svc_op_conv1d_ex (test aid)."""
+    _fields_ = [("x", C.c_void_p), ("a_hi", C.c_void_p), ("a_lo", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p)] + \
+               [(n, C.c_int32) for n in ("B", "L", "Cin", "Cout", "k", "dilation", "pad_left", "Lout", "dtype")] + \
+               [("seq_len", C.POINTER(C.c_int32)), ("res", C.c_void_p), ("res2", C.c_void_p),
+                ("out_scale", C.c_float), ("act", C.c_int32), ("act_slope", C.c_float), ("c_rows", C.c_int32), ("c_off", C.c_int32),
+                ("post_a", C.c_void_p), ("post_ib", C.c_void_p), ("next_p8", C.c_int32), ("bm", C.c_int32), ("force_gemm", C.c_int32),
+                ("y", C.c_void_p), ("plane_hi", C.c_void_p), ("plane_lo", C.c_void_p), ("took", C.c_int32)]
+
+
 _lib = None
 
 
@@ -110,6 +120,7 @@ def lib():
                                     C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         l.svc_hift_forward_ragged.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        l.svc_op_conv1d_ex.argtypes = [C.POINTER(Conv1dEx), C.c_void_p]
         _lib = l
     return _lib
 

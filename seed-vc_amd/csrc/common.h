@@ -199,6 +199,11 @@ struct KConvParams {
     // zero padding does (they are never loaded: they may hold NaN); position tiles that start there are skipped, so output
     // rows at and above seq_len[b] hold anything.  null = every sequence has Lin rows (the uniform instantiations)
     const int* seq_len;
+    // test aids (svc_op_conv1d_ex; no model sets them).  bm: position-tile override for the 128-channel form, one of 64 | 128 |
+    // 256 (0 = the launch's own choice).  took: host word (may be null) that kconv_launch sets to 1 | BM << 8 | BN << 20 of the
+    // instantiation it launched
+    int bm;
+    int* took;
 };
 bool kconv_enabled();
 int kconv_launch(const KConvParams& p, hipStream_t st);

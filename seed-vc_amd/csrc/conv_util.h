@@ -158,6 +158,10 @@ struct ConvRun {
     const float* post_a = nullptr; const float* post_ib = nullptr; int post_n = 0; half_t* c16_lo = nullptr;
     int c16_lo_fmt = 0;                   // format of the c16_lo plane: 0 fp16 residual, 1 fp8 byte pairs (the NEXT conv runs p8)
     bool p8 = false;                      // THIS conv runs as fp16 + fp8 corrections: a.lo holds byte pairs (conv_p8_ok must hold)
+    // test aids (svc_op_conv1d_ex; no model sets them)
+    int bm = 0;                           // resident-tile position-tile override (KConvParams::bm)
+    bool force_gemm = false;              // run on the tap-GEMM even where the resident-tile kernel would take the conv
+    int* took = nullptr;                  // host word: 0 = the tap-GEMM ran, else KConvParams::took
 };
 
 // smallest output width sent to the resident-tile kernel (A/B hook SVC_KCONV_MIN_N; 64-column layers use its 64-wide tile)
@@ -216,7 +220,7 @@ inline int conv1d_run(const ConvW& w, const ConvRun& r, hipStream_t st) {
     p.vec_ok = (p.N % 8 == 0) && (r.ldc32 % 8 == 0) && (r.ldc16 % 8 == 0) && (r.ldres % 8 == 0) && (r.ldres2 % 8 == 0);
     // Long stride-1 convs with several taps keep their activation tile resident in LDS (kconv.hip).  The choice depends
     // on the layer and the sequence length only, never on the batch size, so batched and single runs stay bit-identical.
-    const bool kconv_ok = kconv_enabled() && w.dtype == 0 && r.stride == 1 && w.k >= 3 && (w.k - 1) * r.dilation <= 64 &&
+    const bool kconv_ok = !r.force_gemm && kconv_enabled() && w.dtype == 0 && r.stride == 1 && w.k >= 3 && (w.k - 1) * r.dilation <= 64 &&
                           r.pad_mode == KG_PAD_ZERO && (!r.seq_len || (r.seq_kconv && r.Lin == r.Lout)) && !r.n_override && p.vec_ok &&
                           r.Lout >= KCONV_MIN_ROWS && w.cin_pad >= 64 &&
                           p.N >= kconv_min_n();
@@ -236,8 +240,10 @@ inline int conv1d_run(const ConvW& w, const ConvRun& r, hipStream_t st) {
         q.res = r.res; q.ldres = r.ldres; q.res2 = r.res2; q.ldres2 = r.ldres2;
         q.out_scale = r.out_scale; q.act = r.act; q.act_slope = r.act_slope;
         q.seq_len = r.seq_len;
+        q.bm = r.bm; q.took = r.took;
         return kconv_launch(q, st);
     }
+    if (r.took) *r.took = 0;
     return kgemm_launch(p, w.dtype, KG_EPI_STORE, st);
 }
 

@@ -406,6 +406,8 @@ int kconv_launch(const KConvParams& p_in, hipStream_t st) {
     int bm = 256;
     if (bn == 128) bm = g256 <= 96 ? 64 : 128;
     if (bn == 128 && (bm_env == 64 || bm_env == 128 || bm_env == 256)) bm = bm_env;
+    if (bn == 128 && (p.bm == 64 || p.bm == 128 || p.bm == 256)) bm = p.bm;      // test aid (svc_op_conv1d_ex)
+    if (p.took) *p.took = 1 | (bm << 8) | (bn << 20);
     const int grid = p.B * cdiv(p.Lout, bm) * cdiv(p.N, bn);
     if (grid <= 0) return 0;
     const bool prof = prof_enabled();

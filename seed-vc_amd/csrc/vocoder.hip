@@ -1140,31 +1140,107 @@ int svc_hift_forward_ragged(svc_hift_t* m, const float* mel, const int32_t* lens
 }
 
 // ---- op-level entry points for the parity tests -------------------------------------------------------
-int svc_op_conv1d(const float* x, const float* w, const float* bias, float* y, int B, int L, int Cin, int Cout, int k,
-                  int dilation, int stride, int pad_left, int Lout, int pad_mode, int dtype_in, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    const int dtype = dtype_in;    // 0 f16, 1 f32, 2 f16x3
+namespace {
+thread_local int g_conv1d_took = 0;      // svc_op_conv1d_last_took
+
+// One body for both Conv1d seams.  `e` carries what svc_op_conv1d has no argument for; stride / pad_mode are its own.
+int op_conv1d_body(svc_conv1d_ex_t& e, int stride, int pad_mode, bool ex, hipStream_t st) {
+    const int B = e.B, L = e.L, Cin = e.Cin, Cout = e.Cout, Lout = e.Lout;
+    const int dtype = e.dtype;     // 0 f16, 1 f32, 2 f16x3, 3 fp16 + fp8 corrections
+    const int c_rows = e.c_rows ? e.c_rows : Lout;
     Arena ar;
     svc_tensor_desc_t d[2];
-    d[0].name = "c.weight"; d[0].data = w; d[0].ndim = 3; d[0].shape[0] = Cout; d[0].shape[1] = Cin; d[0].shape[2] = k; d[0].shape[3] = 1;
-    d[1].name = "c.bias"; d[1].data = bias; d[1].ndim = 1; d[1].shape[0] = Cout; d[1].shape[1] = d[1].shape[2] = d[1].shape[3] = 1;
-    StateDict sd(d, bias ? 2 : 1);
+    d[0].name = "c.weight"; d[0].data = e.w; d[0].ndim = 3; d[0].shape[0] = Cout; d[0].shape[1] = Cin; d[0].shape[2] = e.k; d[0].shape[3] = 1;
+    d[1].name = "c.bias"; d[1].data = e.bias; d[1].ndim = 1; d[1].shape[0] = Cout; d[1].shape[1] = d[1].shape[2] = d[1].shape[3] = 1;
+    StateDict sd(d, e.bias ? 2 : 1);
     ConvW cw;
-    if (pack_conv1d(sd, "c", Cout, Cin, k, bias != nullptr, dtype, ar, st, &cw)) return 1;
-    void* a = ar.alloc((size_t)B * L * cw.cin_pad * vesize(dtype), st);
-    void* a_lo = ar.alloc((size_t)B * L * cw.cin_pad * vesize(dtype), st);
-    float* c = ar.alloc_n<float>((size_t)B * Lout * cw.cout_pad, st);
-    if (!a || !a_lo || !c) return 1;
-    if (pack_any(gdt(dtype), x, a, 0, B * L, 1, Cin, Cin, 0, 1, cw.cin_pad, 0, 1, nullptr, st)) return 1;
-    if (is_split(dtype))
-        if (pack_f16_lo_launch(x, (half_t*)a_lo, B * L, 1, Cin, Cin, 0, 1, cw.cin_pad, 0, 1, nullptr, st)) return 1;
+    if (pack_conv1d(sd, "c", Cout, Cin, e.k, e.bias != nullptr, dtype, ar, st, &cw)) return 1;
+    const size_t n_c = (size_t)B * c_rows * cw.cout_pad;
+    float* c = ar.alloc_n<float>(n_c, st);
+    if (!c) return 1;
     ConvRun r;
-    r.a.hi = a; r.a.lo = a_lo; r.B = B; r.Lin = L; r.Lout = Lout; r.dilation = dilation; r.stride = stride; r.pad_left = pad_left; r.pad_mode = pad_mode;
+    if (e.a_hi) {      // the caller's operand planes (a fused Snake's output fed to the next conv)
+        r.a.hi = e.a_hi; r.a.lo = e.a_lo;
+    } else {
+        void* a = ar.alloc((size_t)B * L * cw.cin_pad * vesize(dtype), st);
+        void* a_lo = ar.alloc((size_t)B * L * cw.cin_pad * vesize(dtype), st);
+        if (!a || !a_lo) return 1;
+        if (dtype == 3) {
+            // the planes as the model's activation kernels write them: leaky ReLU of slope 1 is the identity (v * 1.0f is exact)
+            if (act_cl_launch(e.x, Cin, a, a_lo, cw.cin_pad, 1, nullptr, nullptr, nullptr, B, Cin, L, 2, 1.0f, st, 1)) return 1;
+        } else {
+            if (pack_any(gdt(dtype), e.x, a, 0, B * L, 1, Cin, Cin, 0, 1, cw.cin_pad, 0, 1, nullptr, st)) return 1;
+            if (is_split(dtype))
+                if (pack_f16_lo_launch(e.x, (half_t*)a_lo, B * L, 1, Cin, Cin, 0, 1, cw.cin_pad, 0, 1, nullptr, st)) return 1;
+        }
+        r.a.hi = a; r.a.lo = a_lo;
+    }
+    r.B = B; r.Lin = L; r.Lout = Lout; r.dilation = e.dilation; r.stride = stride; r.pad_left = e.pad_left; r.pad_mode = pad_mode;
     r.c32 = c; r.ldc32 = cw.cout_pad;
+    if (ex) {
+        // rows outside [c_off, c_off + Lout) of y come back as they went in: the conv must not write them
+        if (pack_f32_launch(e.y, c, B * c_rows, 1, Cout, Cout, 0, 1, cw.cout_pad, 0, 1, nullptr, st)) return 1;
+        r.c_rows = e.c_rows; r.c_off = e.c_off;
+        r.out_scale = e.out_scale; r.act = e.act; r.act_slope = e.act_slope;
+        const float* src[2] = {e.res, e.res2};
+        for (int i = 0; i < 2; ++i) {
+            if (!src[i]) continue;
+            float* q = ar.alloc_n<float>(n_c, st);
+            if (!q) return 1;
+            if (pack_f32_launch(src[i], q, B * c_rows, 1, Cout, Cout, 0, 1, cw.cout_pad, 0, 1, nullptr, st)) return 1;
+            if (i == 0) { r.res = q; r.ldres = cw.cout_pad; } else { r.res2 = q; r.ldres2 = cw.cout_pad; }
+        }
+        if (e.seq_len) {
+            int* d_len = ar.alloc_n<int>(B, st);
+            if (!d_len) return 1;
+            SVC_CHECK_HIP(hipMemcpyAsync(d_len, e.seq_len, B * sizeof(int), hipMemcpyHostToDevice, st));
+            SVC_CHECK_HIP(hipStreamSynchronize(st));      // the caller's array is pageable
+            r.seq_len = d_len; r.seq_kconv = true;
+        }
+        if (e.post_a) {
+            r.post_a = e.post_a; r.post_ib = e.post_ib; r.post_n = Cout;
+            r.c16 = reinterpret_cast<half_t*>(e.plane_hi); r.c16_lo = reinterpret_cast<half_t*>(e.plane_lo); r.ldc16 = cw.cout_pad;
+            r.c16_lo_fmt = e.next_p8 ? 1 : 0;
+        }
+        r.p8 = dtype == 3;
+        r.bm = e.bm; r.force_gemm = e.force_gemm != 0;
+    }
+    r.took = &e.took;
     if (conv1d_run(cw, r, st)) return 1;
-    if (pack_f32_launch(c, y, B * Lout, 1, Cout, cw.cout_pad, 0, 1, Cout, 0, 1, nullptr, st)) return 1;
+    g_conv1d_took = e.took;
+    if (pack_f32_launch(c, e.y, B * c_rows, 1, Cout, cw.cout_pad, 0, 1, Cout, 0, 1, nullptr, st)) return 1;
     SVC_CHECK_HIP(hipStreamSynchronize(st));
     return 0;
+}
+}  // namespace
+
+int svc_op_conv1d(const float* x, const float* w, const float* bias, float* y, int B, int L, int Cin, int Cout, int k,
+                  int dilation, int stride, int pad_left, int Lout, int pad_mode, int dtype_in, void* stream) {
+    svc_conv1d_ex_t e;
+    memset(&e, 0, sizeof(e));
+    e.x = x; e.w = w; e.bias = bias; e.y = y;
+    e.B = B; e.L = L; e.Cin = Cin; e.Cout = Cout; e.k = k; e.dilation = dilation; e.pad_left = pad_left; e.Lout = Lout;
+    e.dtype = dtype_in;    // 0 f16, 1 f32, 2 f16x3
+    return op_conv1d_body(e, stride, pad_mode, false, (hipStream_t)stream);
+}
+
+int svc_op_conv1d_last_took(void) { return g_conv1d_took; }
+
+int svc_op_conv1d_ex(svc_conv1d_ex_t* e, void* stream) {
+    SVC_REQUIRE(e && e->w && e->y && (e->x || e->a_hi), "bad argument");
+    SVC_REQUIRE(e->B >= 1 && e->L >= 1 && e->Cin >= 1 && e->Cout >= 1 && e->k >= 1 && e->dilation >= 1 && e->Lout >= 1 && e->pad_left >= 0,
+                "svc_op_conv1d_ex: bad shape");
+    SVC_REQUIRE(e->dtype == 0 || e->dtype == 2 || e->dtype == 3, "svc_op_conv1d_ex: dtype is 0 (f16), 2 (f16x3) or 3 (fp16 + fp8 corrections)");
+    SVC_REQUIRE(e->c_off >= 0 && e->c_off + e->Lout <= (e->c_rows ? e->c_rows : e->Lout), "svc_op_conv1d_ex: the output rows do not fit c_rows");
+    SVC_REQUIRE(!e->a_hi || e->dtype == 0 || e->a_lo, "svc_op_conv1d_ex: split operand planes come in pairs");
+    SVC_REQUIRE(!e->post_a == !e->post_ib && (!e->post_a || (e->plane_hi && e->plane_lo)), "svc_op_conv1d_ex: the fused Snake needs a, 1/b and both planes");
+    SVC_REQUIRE(!e->next_p8 || e->post_a, "svc_op_conv1d_ex: next_p8 selects the format of a fused Snake's lo plane");
+    SVC_REQUIRE(!e->force_gemm || (e->dtype != 3 && !e->next_p8), "svc_op_conv1d_ex: the tap-GEMM neither reads nor writes byte-pair planes");
+    SVC_REQUIRE(e->bm == 0 || e->bm == 64 || e->bm == 128 || e->bm == 256, "svc_op_conv1d_ex: bm is 0, 64, 128 or 256");
+    if (e->seq_len)
+        for (int b = 0; b < e->B; ++b) SVC_REQUIRE(e->seq_len[b] >= 0 && e->seq_len[b] <= e->L, "svc_op_conv1d_ex: seq_len out of range");
+    e->took = 0;
+    return op_conv1d_body(*e, 1, KG_PAD_ZERO, true, (hipStream_t)stream);
 }
 
 int svc_op_conv_transpose1d(const float* x, const float* w, const float* bias, float* y, int B, int L, int Cin, int Cout, int k,

@@ -53,6 +53,72 @@ def conv1d_cl(x, w, bias, dilation=1, stride=1, pad_left=0, Lout=None, pad_mode=
     return y
 
 
+CONV_DTYPES_EX = {"f16": 0, "f16x3": 2, "p8": 3}
+PLANE_FILL = 0x7E7E      # what conv1d_cl_ex's planes hold where the conv did not write (an fp16 / fp8 NaN pattern, never zero)
+
+
+def conv1d_cl_ex(x, w, bias=None, dilation=1, pad_left=0, Lout=None, dtype="f16x3", seq_len=None, res=None, res2=None,
+                 out_scale=0.0, act=0, act_slope=0.0, c_rows=0, c_off=0, y_fill=None, post_a=None, post_ib=None, next_p8=False,
+                 bm=0, force_gemm=False, planes=None):
+    """Test aid over svc_op_conv1d_ex (include/seedvc_hip.h): one stride-1 zero-padded channels-last conv with the epilogue, the
+    fused Snake, the ragged form, the fp16 + fp8-corrections mode ("p8") and a tile-form override.
+    x (B, L, Cin) fp32, or planes = (hi, lo) int16 (B, L, cin_pad) as a fused Snake returned them (x then only gives the shape).
+    Returns (y (B, c_rows, Cout), plane_hi, plane_lo, took): the planes are int16 (B, c_rows, cout_pad) or None without a Snake,
+    took = dict(kconv=bool, bm=int, bn=int).  Rows of y the conv does not write hold y_fill."""
+    import ctypes as C
+    B, L, Cin = x.shape
+    Cout, _, k = w.shape
+    dev = x.device
+    if Lout is None:
+        Lout = L
+    rows = c_rows if c_rows else Lout
+    cin_pad, cout_pad = -(-Cin // 64) * 64, -(-Cout // 64) * 64
+    with torch.cuda.device(dev):
+        e = _lib.Conv1dEx()
+        keep = [_lib.f32c(w)]
+        e.w = keep[0].data_ptr()
+        if planes is not None:
+            hi, lo = (p.contiguous() for p in planes)
+            assert hi.shape == (B, L, cin_pad) and lo.shape == hi.shape and hi.dtype == torch.int16 and lo.dtype == torch.int16
+            keep += [hi, lo]
+            e.a_hi, e.a_lo = hi.data_ptr(), lo.data_ptr()
+        else:
+            keep.append(_lib.f32c(x))
+            e.x = keep[-1].data_ptr()
+        for name, t, shape in (("bias", bias, (Cout,)), ("res", res, (B, rows, Cout)), ("res2", res2, (B, rows, Cout)),
+                               ("post_a", post_a, (Cout,)), ("post_ib", post_ib, (Cout,))):
+            if t is not None:
+                assert tuple(t.shape) == shape, name
+                keep.append(_lib.f32c(t))
+                setattr(e, name, keep[-1].data_ptr())
+        e.B, e.L, e.Cin, e.Cout, e.k, e.dilation, e.pad_left, e.Lout = B, L, Cin, Cout, k, dilation, pad_left, Lout
+        e.dtype = CONV_DTYPES_EX[dtype]
+        if seq_len is not None:
+            assert len(seq_len) == B
+            lens = (C.c_int32 * B)(*[int(v) for v in seq_len])
+            e.seq_len = C.cast(lens, C.POINTER(C.c_int32))
+        e.out_scale, e.act, e.act_slope, e.c_rows, e.c_off = out_scale, act, act_slope, c_rows, c_off
+        e.next_p8, e.bm, e.force_gemm = int(next_p8), bm, int(force_gemm)
+        y = torch.full((B, rows, Cout), float("nan") if y_fill is None else y_fill, device=dev)
+        e.y = y.data_ptr()
+        p_hi = p_lo = None
+        if post_a is not None:
+            p_hi = torch.full((B, rows, cout_pad), PLANE_FILL, dtype=torch.int16, device=dev)
+            p_lo = torch.full((B, rows, cout_pad), PLANE_FILL, dtype=torch.int16, device=dev)
+            e.plane_hi, e.plane_lo = p_hi.data_ptr(), p_lo.data_ptr()
+        _lib.check(_lib.lib().svc_op_conv1d_ex(C.byref(e), _lib.stream_ptr()))
+    return y, p_hi, p_lo, _took(e.took)
+
+
+def _took(word):
+    return {"kconv": bool(word & 1), "bm": (word >> 8) & 0xFFF, "bn": word >> 20}
+
+
+def conv1d_last_took():
+    """which kernel this thread's last conv1d_cl / conv1d_cl_ex call ran: dict(kconv=bool, bm=int, bn=int) (test aid)"""
+    return _took(_lib.lib().svc_op_conv1d_last_took())
+
+
 def conv_transpose1d_cl(x, w, bias, stride, dtype="f32"):
     """x (B, L, Cin), w (Cin, Cout, k = 2*stride) -> (B, L*stride, Cout); padding = stride // 2."""
     B, L, Cin = x.shape
