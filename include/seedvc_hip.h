@@ -96,6 +96,23 @@ typedef struct svc_cfm_args {
  * CFM.inference + solve_euler (modules/v2/cfm.py:16-132; cosine-warped t_span, 1/2/3-way CFG). */
 int svc_cfm_sample(svc_dit_t* m, const svc_cfm_args_t* args, void* stream);
 
+/* ---- seeded noise (sampler z, HiFT's SineGen draws): per-utterance seeds, draws made inside the consuming kernels.
+ * One rule for every draw: Philox4x32-10 with key = (seed low word, seed high word) and counter = (pos, row / 4, domain, 0);
+ * output word row % 4 belongs to element (row, pos).  Domains: 0 = the AR sampler's layout (svc_ar_generate_batch_seeded),
+ * 1 = sampler z (row = mel channel, pos = frame), 2 = HiFT source noise (row = harmonic 0 .. nb_harmonics, pos = sample),
+ * 3 = HiFT phase0 (row = harmonic, pos = 0): one seed may go to every stage of a request without a draw being reused.
+ * Uniforms u = ((word >> 8) + 1) * 2^-24 in (0, 1]; normals by Box-Muller on word pairs, words (0, 1) -> rows 4q, 4q + 1 =
+ * r cos(2 pi u1), r sin(2 pi u1) with r = sqrt(-2 ln u0), words (2, 3) -> rows 4q + 2, 4q + 3 (|n| <= 5.77); phase0 =
+ * (2 u - 1) pi.  A draw is a pure function of (seed, domain, row, pos): the batch row, the padded T / S, the micro-batch and
+ * the neighbours never enter it, and the first n positions of a row are the same whatever length is asked for.
+ *
+ * svc_cfm_sample with z[b] = the draws of seeds[b]: args->z is ignored (may be NULL), everything else as svc_cfm_sample.
+ * seeds: HOST [B], consumed before the call returns.  Bit for bit svc_cfm_sample fed svc_cfm_noise_draws(seeds[b], C, T).
+ * seeds == NULL, B < 1 or a handle of another device: non-zero, svc_last_error(), nothing enqueued. */
+int svc_cfm_sample_seeded(svc_dit_t* m, const svc_cfm_args_t* args, const uint64_t* seeds, void* stream);
+/* z (device, [C][T]) = the sampler noise of `seed`: what svc_cfm_sample_seeded draws for an utterance of that seed. */
+int svc_cfm_noise_draws(uint64_t seed, int C, int T, float* z, void* stream);
+
 /* Replaces one estimator evaluation `estimator(x, prompt_x, x_lens, t, style, mu)` =
  * DiT.forward (modules/diffusion_transformer.py:486-537, modules/v2/dit_wrapper.py:114-152).
  * x, prompt_x, out: [N][in_channels][T]; style [N][style_dim]; mu [N][T][content_dim]; t scalar
@@ -173,6 +190,17 @@ int svc_hift_forward(svc_hift_t* m, const float* mel, const float* f0, const flo
  * return non-zero with nothing enqueued. */
 int svc_hift_forward_ragged(svc_hift_t* m, const float* mel, const int32_t* lens, const float* f0, const float* phase0,
                             const float* noise, int B, int S, float* out, float* f0_out, void* stream);
+/* svc_hift_forward (lens == NULL) / svc_hift_forward_ragged (lens HOST [B]) with phase0[b] and noise[b] = the draws of
+ * seeds[b] (the rule above svc_cfm_sample_seeded), made inside the source kernel: no [B][nb_harmonics+1][S*up] tensor exists,
+ * in the caller's memory or the handle's.  seeds: HOST [B], consumed before the call returns.  Bit for bit the explicit call
+ * fed svc_hift_noise_draws(seeds[b], nb_harmonics + 1, S * up); with lens, out[b][0 .. lens[b]*up) is utterance b run alone
+ * with its seed, bit for bit, whatever the other rows, S and the micro-batch.  seeds == NULL, B < 1, S < 1, a length outside
+ * [0, S] or a handle of another device: non-zero, svc_last_error(), nothing enqueued. */
+int svc_hift_forward_seeded(svc_hift_t* m, const float* mel, const int32_t* lens, const float* f0, const uint64_t* seeds, int B,
+                            int S, float* out, float* f0_out, void* stream);
+/* phase0 (device, [NH]) and noise (device, [NH][n]) of `seed`, NH = nb_harmonics + 1, n = samples (< 2^31): the tensors the
+ * explicit calls take for one utterance. */
+int svc_hift_noise_draws(uint64_t seed, int NH, long n, float* phase0, float* noise, void* stream);
 /* Utterances per internal pass of the vocoders (0 = default 32); results do not depend on it. */
 int svc_bigvgan_set_microbatch(svc_bigvgan_t* m, int utterances);
 int svc_hift_set_microbatch(svc_hift_t* m, int utterances);

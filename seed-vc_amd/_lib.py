@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libseedvc_hip.so")
 EXPORTS = [
     "svc_abi_version", "svc_last_error",
     "svc_dit_create", "svc_dit_destroy", "svc_dit_set_microbatch", "svc_dit_set_fused_min_rows", "svc_dit_fused_available", "svc_dit_set_graphs", "svc_cfm_sample", "svc_dit_forward",
+    "svc_cfm_sample_seeded", "svc_cfm_noise_draws", "svc_hift_forward_seeded", "svc_hift_noise_draws",
     "svc_bigvgan_create", "svc_bigvgan_destroy", "svc_bigvgan_forward", "svc_bigvgan_forward_ragged", "svc_bigvgan_set_microbatch",
     "svc_hift_create", "svc_hift_destroy", "svc_hift_forward", "svc_hift_forward_ragged", "svc_hift_set_microbatch",
     "svc_anti_alias_act_fwd",
@@ -121,6 +122,12 @@ def lib():
         l.svc_hift_forward_ragged.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         l.svc_op_conv1d_ex.argtypes = [C.POINTER(Conv1dEx), C.c_void_p]
+        # seeded noise: 64-bit seeds by value and as HOST arrays
+        l.svc_cfm_sample_seeded.argtypes = [C.c_void_p, C.POINTER(CfmArgs), C.POINTER(C.c_uint64), C.c_void_p]
+        l.svc_cfm_noise_draws.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        l.svc_hift_forward_seeded.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_uint64),
+                                              C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        l.svc_hift_noise_draws.argtypes = [C.c_uint64, C.c_int, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = l
     return _lib
 
@@ -174,3 +181,19 @@ def i64_host(values):
         return None
     vals = [int(v) for v in values]
     return (C.c_int64 * len(vals))(*vals)
+
+
+def seed_ints(seeds, n, what):
+    """seeds (list / tensor of n integers in [0, 2^64)) -> list of ints; ValueError for a wrong count or a seed out of range."""
+    vals = [int(v) for v in (seeds.tolist() if torch.is_tensor(seeds) else seeds)]
+    if len(vals) != n:
+        raise ValueError(f"{what}: {len(vals)} seeds for {n} utterances")
+    for v in vals:
+        if not 0 <= v < 1 << 64:
+            raise ValueError(f"{what}: seed {v} is outside [0, 2^64)")
+    return vals
+
+
+def seeds_host(seeds, n, what):
+    """The same as a HOST uint64 array for the seeded calls."""
+    return (C.c_uint64 * n)(*seed_ints(seeds, n, what))

@@ -4,7 +4,8 @@
 keeps the reference signature (modules/flow_matching.py:30-31; v2: modules/v2/cfm.py:16-25), so a
 driver that calls `model.cfm.inference(...)` (inference.py:483-505, seed_vc_wrapper.py:575-603) runs
 unchanged.  Differences that are additions, not changes: `z=` lets the caller supply the noise
-(otherwise torch.randn like the reference), and B > 1 is accepted and means B independent B=1 runs
+(otherwise torch.randn like the reference), `seeds=` gives one 64-bit seed per utterance and the noise is drawn on the
+device inside the sampler (`svc_cfm_sample_seeded`; `CFM.noise_draws` returns the same tensor), and B > 1 is accepted and means B independent B=1 runs
 (the reference sampler raises for B > 1).
 """
 import ctypes as C
@@ -110,7 +111,12 @@ class CFM:
 
     @torch.inference_mode()
     def inference(self, mu, x_lens, prompt, style, f0=None, n_timesteps=10, temperature=1.0,
-                  inference_cfg_rate=0.5, random_voice=False, z=None, prompt_lens=None):
+                  inference_cfg_rate=0.5, random_voice=False, z=None, prompt_lens=None, seeds=None):
+        """seeds: B integers in [0, 2^64) (list or tensor), exclusive with z: utterance b starts from the draws of seeds[b], a
+        pure function of (seed, channel, frame) -- the same whatever its row, T and its neighbours (include/seedvc_hip.h)."""
+        if seeds is not None and z is not None:
+            raise ValueError("CFM.inference: give seeds or z, not both")
+        seeds_keep = _lib.seeds_host(seeds, mu.size(0), "CFM.inference") if seeds is not None else None
         if self.cfg["version"] == 2 and not isinstance(f0, (type(None), torch.Tensor)):
             # v2 call form: inference(mu, x_lens, prompt, style, n_timesteps, temperature, inference_cfg_rate, ...)
             n_timesteps, f0 = f0, None
@@ -118,13 +124,15 @@ class CFM:
         dev = self.device
         with torch.cuda.device(dev):
             mu, prompt, style = (_lib.f32c(a, dev) for a in (mu, prompt, style))
-            if z is None:
-                z = torch.randn([B, self.in_channels, T], device=dev)      # flow_matching.py:50
-            z = _lib.f32c(z, dev)
+            if seeds is None:
+                if z is None:
+                    z = torch.randn([B, self.in_channels, T], device=dev)      # flow_matching.py:50
+                z = _lib.f32c(z, dev)
             out = torch.empty(B, self.in_channels, T, device=dev, dtype=torch.float32)
             a = _lib.CfmArgs()
             a.B, a.T, a.P = B, T, prompt.size(-1)
-            a.mu, a.prompt, a.style, a.z, a.out = (t.data_ptr() for t in (mu, prompt, style, z, out))
+            a.mu, a.prompt, a.style, a.out = (t.data_ptr() for t in (mu, prompt, style, out))
+            a.z = z.data_ptr() if z is not None else None
             xl = None
             if x_lens is not None:
                 xl = [int(v) for v in (x_lens.tolist() if torch.is_tensor(x_lens) else x_lens)]
@@ -141,5 +149,17 @@ class CFM:
             else:
                 a.cfg_rate[0], a.cfg_rate[1] = float(inference_cfg_rate), float(inference_cfg_rate)
             a.random_voice = int(bool(random_voice))
-            _lib.check(_lib.lib().svc_cfm_sample(self.estimator._h, C.byref(a), _lib.stream_ptr()))
+            if seeds_keep is not None:
+                _lib.check(_lib.lib().svc_cfm_sample_seeded(self.estimator._h, C.byref(a), seeds_keep, _lib.stream_ptr()))
+            else:
+                _lib.check(_lib.lib().svc_cfm_sample(self.estimator._h, C.byref(a), _lib.stream_ptr()))
         return out
+
+    @torch.inference_mode()
+    def noise_draws(self, seed, T):
+        """(1, C, T): the noise `inference(seeds=[seed])` starts an utterance of T frames from (`svc_cfm_noise_draws`)."""
+        seed = _lib.seeds_host([seed], 1, "CFM.noise_draws")[0]
+        with torch.cuda.device(self.device):
+            z = torch.empty(1, self.in_channels, int(T), device=self.device, dtype=torch.float32)
+            _lib.check(_lib.lib().svc_cfm_noise_draws(seed, self.in_channels, int(T), _lib.ptr(z), _lib.stream_ptr()))
+        return z

@@ -3,6 +3,7 @@
 // Included by ar.hip only.
 #pragma once
 #include "ar_common.h"
+#include "philox.h"
 
 namespace {
 
@@ -14,22 +15,10 @@ __global__ void ar_embed_kernel(const float* __restrict__ emb, const GenState* _
 
 // ---- sampler: one block, vocab <= 4096.  reference: ar.py:731-763 + :723-727
 
-// Seeded Exp(1) draws: Philox4x32-10 (Salmon et al., SC'11), key = (seed low word, seed high word), counter =
+// Seeded Exp(1) draws: Philox4x32-10 (philox.h), key = (seed low word, seed high word), counter =
 // (v / 4, token step, 0, 0); output word j of the call is the draw of vocabulary entry 4 (v / 4) + j.  A draw is a pure
 // function of (seed, step, v): nothing about the slot, the batch or the other sequences enters it.
 // u = ((word >> 8) + 1) * 2^-24 lies in (0, 1] and is exact in fp32, so q = -log(u) is finite (<= 16.64) and >= 0.
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
-                                              unsigned (&out)[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0; c1 = lo1;
-        c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
 __device__ __forceinline__ void ar_exp_draw4(unsigned long long seed, int step, int v4, float (&q)[4]) {
     unsigned w[4];
     philox4x32_10((unsigned)v4, (unsigned)step, 0u, 0u, (unsigned)seed, (unsigned)(seed >> 32), w);

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "model_util.h"
+#include "noise.h"
 
 namespace svc {
 static thread_local std::string g_err;
@@ -34,6 +35,45 @@ int svc_anti_alias_act_fwd(const void* x, void* y, const float* up12, const floa
     SVC_REQUIRE(x && y && up12 && down12 && log_alpha && log_beta, "null argument");
     SVC_REQUIRE(C <= 65535 && B <= 65535, "grid limit: B, C <= 65535");
     return aa_act_rows_launch(x, y, up12, down12, log_alpha, log_beta, B, C, L, dtype, (hipStream_t)stream);
+}
+
+// ---- exporters of the seeded draws (noise.h): the tensors the explicit calls take, from the device functions the seeded kernels use
+extern "C++" namespace {
+// out[row][pos] = the normal of (seed, domain, row, pos), rows x n; one Philox call per four rows
+__global__ __launch_bounds__(256) void noise_normal_rows_kernel(unsigned long long seed, unsigned domain, int rows, long n,
+                                                                float* __restrict__ out) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long q = i / n, pos = i - q * n;
+    if (4 * q >= rows) return;
+    float v[4];
+    noise_normal4(seed, domain, (unsigned)q, (unsigned)pos, v);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (4 * q + j < rows) out[(4 * q + j) * n + pos] = v[j];
+}
+
+int noise_normal_rows_launch(unsigned long long seed, unsigned domain, int rows, long n, float* out, hipStream_t st) {
+    const long total = (long)cdiv(rows, 4) * n;
+    hipLaunchKernelGGL(noise_normal_rows_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, st, seed, domain, rows, n, out);
+    SVC_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+}  // namespace
+
+int svc_cfm_noise_draws(uint64_t seed, int C, int T, float* z, void* stream) {
+    SVC_REQUIRE(z, "null argument");
+    SVC_REQUIRE(C >= 1 && T >= 1, "svc_cfm_noise_draws: C and T must be at least 1");
+    return noise_normal_rows_launch(seed, NOISE_CFM_Z, C, T, z, (hipStream_t)stream);
+}
+
+int svc_hift_noise_draws(uint64_t seed, int NH, long n, float* phase0, float* noise, void* stream) {
+    SVC_REQUIRE(phase0 && noise, "null argument");
+    SVC_REQUIRE(NH >= 1 && n >= 1 && n <= 0x7fffffffL, "svc_hift_noise_draws: NH >= 1 and 1 <= n < 2^31 (the sample index is a 32-bit counter word)");
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(noise_phase0_kernel, dim3(cdiv(NH, 64)), dim3(64), 0, st, (const unsigned long long*)nullptr,
+                       (unsigned long long)seed, 1, NH, phase0);
+    SVC_CHECK_HIP(hipGetLastError());
+    return noise_normal_rows_launch(seed, NOISE_HIFT_SOURCE, NH, n, noise, st);
 }
 
 int svc_op_linear(const float* a, const float* w, const float* bias, float* c, int M, int N, int K, int dtype, int act,

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "model_util.h"
+#include "noise.h"
 
 using namespace svc;
 
@@ -115,6 +116,7 @@ struct svc_dit {
     half_t *x16, *n16, *qk16, *vt, *ao16, *ff16, *h16, *hm16, *xr16, *wnx16, *acts16, *fl16, *fo16;
     std::vector<half_t*> skip16;
     int *d_kvlen, *d_convlen, *d_plen;
+    unsigned long long* d_seeds = nullptr;   // [cap_B] seeds of the micro-batch (svc_cfm_sample_seeded)
     int* d_convlen_w = nullptr;   // conv lengths relative to the head window
     int win0 = 0;                 // first sequence row the output head is evaluated on (0 = all rows)
     float *d_tvals, *d_tfeat, *d_th, *d_t1, *d_t1s, *d_t2, *d_mod, *d_gcond, *d_flmod, *d_stylevec;
@@ -125,9 +127,11 @@ struct svc_dit {
     int tables(const std::vector<float>& tvals, hipStream_t st);
     int statics(int n_streams, const int (*flags)[3], int B, int T, const float* mu, const float* style_dev,
                 hipStream_t st);
-    int run_group(const svc_cfm_args_t* a, int b0, int nb, int n_streams, const int (*flags)[3],
+    // seeds: HOST [a->B] or null; set, the ODE state starts from the draws of seeds[b0 + b] instead of a->z (noise.h)
+    int run_group(const svc_cfm_args_t* a, const uint64_t* seeds, int b0, int nb, int n_streams, const int (*flags)[3],
                   const std::vector<float>& tvals, const std::vector<float>& dts, float c0, float ca, float cb,
                   int stream_a, int stream_b, hipStream_t st);
+    int sample(const svc_cfm_args_t* a, const uint64_t* seeds, hipStream_t st);
     int body(int n_streams, int B, int T, int step, hipStream_t st);
     int body_fused(int n_streams, int B, int T, int step, hipStream_t st);
     int head(int n_streams, int B, int T, int step, hipStream_t st);
@@ -545,6 +549,7 @@ int svc_dit::reserve(int n_streams, int B, int T, int n_steps, hipStream_t st) {
     d_convlen = ws.alloc_n<int>(nseq, st);
     d_convlen_w = ws.alloc_n<int>(nseq, st);
     d_plen = ws.alloc_n<int>(cap_B, st);
+    d_seeds = ws.alloc_n<unsigned long long>(cap_B, st);
     const long Sx = cap_steps;
     d_tvals = ws.alloc_n<float>(Sx, st);
     d_tfeat = ws.alloc_n<float>(Sx * 256, st);
@@ -556,7 +561,7 @@ int svc_dit::reserve(int n_streams, int B, int T, int n_steps, hipStream_t st) {
     d_gcond = ws.alloc_n<float>(Sx * std::max(2L * W * NL, 1L), st);
     d_flmod = ws.alloc_n<float>(Sx * std::max(2 * W, 1), st);
     d_stylevec = ws.alloc_n<float>((long)cap_B * D, st);
-    if (!d_kvlen || !d_convlen || !d_convlen_w || !d_plen || !d_tvals || !d_tfeat || !d_th || !d_t1 || !d_t1s || !d_t2 || !d_mod ||
+    if (!d_kvlen || !d_convlen || !d_convlen_w || !d_plen || !d_seeds || !d_tvals || !d_tfeat || !d_th || !d_t1 || !d_t1s || !d_t2 || !d_mod ||
         !d_gcond || !d_flmod || !d_stylevec)
         return 1;
     seq_rows = (int)round_up(T + npre, 8);
@@ -993,6 +998,33 @@ __global__ void init_state_kernel(float* __restrict__ x, long ldx, half_t* __res
     for (int k = 0; k < n_copies; ++k) x16[k * copy_stride + ((long)b * rows + t) * ldx16 + c] = (half_t)v;
 }
 
+// The seeded start of the ODE: x[b][t][4 c4 .. 4 c4 + 3] = temperature * z of (seeds[b], channel, frame t) drawn here (one
+// Philox call per four channels), zero for t < prompt_len[b] and in the padding rows t >= T; the fp16 copies of every
+// stream for t < T.  What bct_to_btc_kernel + init_state_kernel leave when they are fed svc_cfm_noise_draws, bit for bit.
+__global__ __launch_bounds__(256) void init_state_seeded_kernel(const unsigned long long* __restrict__ seeds, float temperature,
+                                                                float* __restrict__ x, long ldx, half_t* __restrict__ x16, long ldx16,
+                                                                int rows, int B, int T, int C, const int* __restrict__ prompt_len,
+                                                                int n_copies, long copy_stride) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int C4 = C >> 2;
+    if (i >= (long)B * rows * C4) return;
+    const int c4 = (int)(i % C4);
+    const long bt = i / C4;
+    const int t = (int)(bt % rows), b = (int)(bt / rows);
+    float v[4] = {0.f, 0.f, 0.f, 0.f};
+    if (t < T && t >= prompt_len[b]) {
+        noise_normal4(seeds[b], NOISE_CFM_Z, (unsigned)c4, (unsigned)t, v);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] *= temperature;
+    }
+    const long row = (long)b * rows + t;
+    *reinterpret_cast<float4v*>(x + row * ldx + 4 * c4) = (float4v){v[0], v[1], v[2], v[3]};
+    if (t < T) {
+        const half4 h = {(half_t)v[0], (half_t)v[1], (half_t)v[2], (half_t)v[3]};
+        for (int k = 0; k < n_copies; ++k) *reinterpret_cast<half4*>(x16 + k * copy_stride + row * ldx16 + 4 * c4) = h;
+    }
+}
+
 __global__ void euler_kernel(float* __restrict__ x, long ldx, half_t* __restrict__ x16, long ldx16, int rows,
                              const float* __restrict__ v, long ldv, long v_stream_stride, int v_off, int B, int T, int C,
                              const int* __restrict__ prompt_len, float dt, float c0, float ca, float cb, int stream_a,
@@ -1026,7 +1058,7 @@ __global__ void prompt_rows_kernel(const float* __restrict__ src, int C, int P, 
 }
 }  // namespace
 
-int svc_dit::run_group(const svc_cfm_args_t* a, int b0, int nb, int n_streams, const int (*flags)[3],
+int svc_dit::run_group(const svc_cfm_args_t* a, const uint64_t* seeds, int b0, int nb, int n_streams, const int (*flags)[3],
                        const std::vector<float>& tvals, const std::vector<float>& dts, float c0, float ca, float cb,
                        int stream_a, int stream_b, hipStream_t st) {
     const int T = a->T, P = a->P;
@@ -1063,10 +1095,15 @@ int svc_dit::run_group(const svc_cfm_args_t* a, int b0, int nb, int n_streams, c
     for (size_t i = 0; i < cv.size(); ++i) cvw[i] = cv[i] - (win0 - npre > 0 ? win0 - npre : 0);
     {
         const size_t n = kv.size();
-        int* h = reinterpret_cast<int*>(staging.acquire((3 * n + pl.size()) * sizeof(int)));
+        const size_t n_int = round_up(3 * n + pl.size(), 2);      // the seeds behind them stay 8-byte aligned
+        int* h = reinterpret_cast<int*>(staging.acquire(n_int * sizeof(int) + (seeds ? (size_t)nb * 8 : 0)));
         if (!h) return 1;
         memcpy(h, kv.data(), n * 4); memcpy(h + n, cv.data(), n * 4); memcpy(h + 2 * n, cvw.data(), n * 4);
         memcpy(h + 3 * n, pl.data(), pl.size() * 4);
+        if (seeds) {
+            memcpy(h + n_int, seeds + b0, (size_t)nb * 8);
+            SVC_CHECK_HIP(hipMemcpyAsync(d_seeds, h + n_int, (size_t)nb * 8, hipMemcpyHostToDevice, st));
+        }
         SVC_CHECK_HIP(hipMemcpyAsync(d_kvlen, h, n * 4, hipMemcpyHostToDevice, st));
         SVC_CHECK_HIP(hipMemcpyAsync(d_convlen, h + n, n * 4, hipMemcpyHostToDevice, st));
         SVC_CHECK_HIP(hipMemcpyAsync(d_convlen_w, h + 2 * n, n * 4, hipMemcpyHostToDevice, st));
@@ -1078,9 +1115,14 @@ int svc_dit::run_group(const svc_cfm_args_t* a, int b0, int nb, int n_streams, c
     const long copy_stride = (long)nb * seq_rows * C16;
     const long n_el = (long)nb * T * C;
     // ODE state from z (temperature-scaled), prompt frames zeroed (flow_matching.py:50,76-79)
-    if (bct_to_btc_launch(a->z + (long)b0 * C * T, nb, C, T, x32, C16, nullptr, 0, seq_rows, T, a->temperature, st)) return 1;
-    hipLaunchKernelGGL(init_state_kernel, dim3(cdiv(n_el, 256)), dim3(256), 0, st, x32, (long)C16, x16, (long)C16, seq_rows,
-                       nb, T, C, d_plen, n_streams, copy_stride);
+    if (seeds) {
+        hipLaunchKernelGGL(init_state_seeded_kernel, dim3(cdiv((long)nb * seq_rows * (C / 4), 256)), dim3(256), 0, st, d_seeds,
+                           a->temperature, x32, (long)C16, x16, (long)C16, seq_rows, nb, T, C, d_plen, n_streams, copy_stride);
+    } else {
+        if (bct_to_btc_launch(a->z + (long)b0 * C * T, nb, C, T, x32, C16, nullptr, 0, seq_rows, T, a->temperature, st)) return 1;
+        hipLaunchKernelGGL(init_state_kernel, dim3(cdiv(n_el, 256)), dim3(256), 0, st, x32, (long)C16, x16, (long)C16, seq_rows,
+                           nb, T, C, d_plen, n_streams, copy_stride);
+    }
     SVC_CHECK_HIP(hipGetLastError());
     hipLaunchKernelGGL(prompt_rows_kernel, dim3(cdiv(n_el, 256)), dim3(256), 0, st, a->prompt + (long)b0 * C * P, C, P,
                        prompt32, (long)C32, seq_rows, T, d_plen, nb);
@@ -1217,11 +1259,24 @@ int svc_dit_set_graphs(svc_dit_t* m, int on) {
 
 int svc_cfm_sample(svc_dit_t* m, const svc_cfm_args_t* a, void* stream) {
     SVC_REQUIRE(m && a, "null argument");
+    return m->sample(a, nullptr, (hipStream_t)stream);
+}
+
+int svc_cfm_sample_seeded(svc_dit_t* m, const svc_cfm_args_t* a, const uint64_t* seeds, void* stream) {
+    SVC_REQUIRE(m && a, "null argument");
+    SVC_REQUIRE(seeds, "svc_cfm_sample_seeded: seeds is NULL (HOST [B], one per utterance)");
+    return m->sample(a, seeds, (hipStream_t)stream);
+}
+
+}  // extern "C"
+
+// svc_cfm_sample (seeds null: the ODE starts from a->z) and svc_cfm_sample_seeded (a->z ignored)
+int svc_dit::sample(const svc_cfm_args_t* a, const uint64_t* seeds, hipStream_t st) {
+    svc_dit* m = this;
     SVC_REQUIRE(a->B >= 1 && a->T >= 1 && a->P >= 0 && a->P <= a->T && a->n_timesteps >= 1, "bad sampler shape");
     SVC_REQUIRE(a->T + m->npre <= ROPE_POS, "sequence longer than the RoPE table");
-    SVC_REQUIRE(a->mu && (a->prompt || a->P == 0) && a->style && a->z && a->out, "null tensor");
+    SVC_REQUIRE(a->mu && (a->prompt || a->P == 0) && a->style && (a->z || seeds) && a->out, "null tensor");
     SVC_REQUIRE(current_device() == m->device, "this handle was created on another device (make it current before the call)");
-    hipStream_t st = (hipStream_t)stream;
     const int N = a->n_timesteps;
     // ---- time grid (fp32, like the reference)
     std::vector<float> ts = linspace01(N + 1);
@@ -1267,10 +1322,12 @@ int svc_cfm_sample(svc_dit_t* m, const svc_cfm_args_t* a, void* stream) {
     int mb = m->microbatch > 0 ? m->microbatch : 32;   // measured best on MI355X (tiny, B = 64): 8: 49.8k, 16: 51.7k, 32: 57.2k, 64: 55.7k frames/s
     for (int b0 = 0; b0 < a->B; b0 += mb) {
         const int nb = std::min(mb, a->B - b0);
-        if (m->run_group(a, b0, nb, n_streams, flags, tvals, dts, c0, ca, cb, sa, sb, st)) return 1;
+        if (m->run_group(a, seeds, b0, nb, n_streams, flags, tvals, dts, c0, ca, cb, sa, sb, st)) return 1;
     }
     return 0;
 }
+
+extern "C" {
 
 int svc_dit_forward(svc_dit_t* m, int N, int T, const float* x, const float* prompt_x, const int64_t* x_lens, float t,
                     const float* style, const float* mu, float* out, void* stream) {

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "conv_util.h"
+#include "noise.h"
 
 using namespace svc;
 
@@ -121,10 +122,30 @@ __global__ void hift_phase_prefix_kernel(const float* __restrict__ f0, double* _
     }
 }
 
+// The randn_like draw of one sample (generator.py:222), harmonic by harmonic in ascending order: loaded from the caller's
+// tensor ...
+struct HiftNoiseLoad {
+    const float* __restrict__ p;    // the utterance's [NH][ld] rows, already at sample n
+    long ld;
+    __device__ __forceinline__ float operator()(int h) { return p[(long)h * ld]; }
+};
+// ... or drawn here from the utterance's seed (noise.h, domain NOISE_HIFT_SOURCE: row = harmonic, pos = sample; one Philox call
+// per four harmonics, three for NH = 9).  No [NH][S * up] tensor exists on this path.
+struct HiftNoiseDraw {
+    unsigned long long seed;
+    unsigned pos;
+    float n[4];
+    __device__ __forceinline__ float operator()(int h) {
+        if ((h & 3) == 0) noise_normal4(seed, NOISE_HIFT_SOURCE, (unsigned)h >> 2, pos, n);
+        return (h & 3) == 0 ? n[0] : (h & 3) == 1 ? n[1] : (h & 3) == 2 ? n[2] : n[3];
+    }
+};
+
 // merged source sample: tanh(sum_h lin_w[h] * (sine_h * uv + noise_amp * noise_h) + lin_b) at sample r of frame f.
-// prefix: this utterance's [NH][S] rows; phase0: its [NH]; noise: its [NH][noise_ld] rows, already at sample n
+// prefix: this utterance's [NH][S] rows; phase0: its [NH]; noise(h): its draw for harmonic h at this sample
+template <typename Noise>
 __device__ __forceinline__ float hift_source_sample(float f0v, const double* __restrict__ prefix, const float* __restrict__ phase0,
-                                                    const float* __restrict__ noise, long noise_ld, const float* __restrict__ lin_w,
+                                                    Noise noise, const float* __restrict__ lin_w,
                                                     const float* __restrict__ lin_b, int S, int NH, int f, int r, float sr,
                                                     float sine_amp, float noise_std, float voiced_thr) {
     const float uv = f0v > voiced_thr ? 1.f : 0.f;
@@ -139,7 +160,7 @@ __device__ __forceinline__ float hift_source_sample(float f0v, const double* __r
         const float theta = two_pi * frac;
         const float ph = h == 0 ? 0.f : phase0[h];
         const float sine = sine_amp * sinf(theta + ph);
-        const float val = sine * uv + namp * noise[(long)h * noise_ld];
+        const float val = sine * uv + namp * noise(h);
         acc += lin_w[h] * val;
     }
     return tanhf(acc);
@@ -155,8 +176,24 @@ __global__ void hift_source_kernel(const float* __restrict__ f0, const double* _
     const int b = (int)(i / Lw);
     const long n = i - (long)b * Lw;
     const int f = (int)(n / up), r = (int)(n - (long)f * up);
-    s_out[i] = hift_source_sample(f0[(long)b * S + f], prefix + (long)b * NH * S, phase0 + (long)b * NH, noise + (long)b * NH * Lw + n,
-                                  Lw, lin_w, lin_b, S, NH, f, r, sr, sine_amp, noise_std, voiced_thr);
+    s_out[i] = hift_source_sample(f0[(long)b * S + f], prefix + (long)b * NH * S, phase0 + (long)b * NH,
+                                  HiftNoiseLoad{noise + (long)b * NH * Lw + n, Lw}, lin_w, lin_b, S, NH, f, r, sr, sine_amp, noise_std,
+                                  voiced_thr);
+}
+
+// The same with the noise of utterance b drawn from seeds[b] (svc_hift_forward_seeded)
+__global__ void hift_source_seeded_kernel(const float* __restrict__ f0, const double* __restrict__ prefix, const float* __restrict__ phase0,
+                                          const unsigned long long* __restrict__ seeds, const float* __restrict__ lin_w,
+                                          const float* __restrict__ lin_b, float* __restrict__ s_out, int B, int S, int NH, int up, float sr,
+                                          float sine_amp, float noise_std, float voiced_thr) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long Lw = (long)S * up;
+    if (i >= B * Lw) return;
+    const int b = (int)(i / Lw);
+    const long n = i - (long)b * Lw;
+    const int f = (int)(n / up), r = (int)(n - (long)f * up);
+    s_out[i] = hift_source_sample(f0[(long)b * S + f], prefix + (long)b * NH * S, phase0 + (long)b * NH,
+                                  HiftNoiseDraw{seeds[b], (unsigned)n, {}}, lin_w, lin_b, S, NH, f, r, sr, sine_amp, noise_std, voiced_thr);
 }
 
 // Ragged batch: row j of the micro-batch ([B][S] frames) is utterance src[j] of the caller's phase0 [..][NH] and noise
@@ -176,8 +213,30 @@ __global__ void hift_source_ragged_kernel(const float* __restrict__ f0, const do
     if (f < lens[b]) {
         const long Lw_in = (long)S_in * up;
         v = hift_source_sample(f0[(long)b * S + f], prefix + (long)b * NH * S, phase0 + (long)src[b] * NH,
-                               noise + (long)src[b] * NH * Lw_in + n, Lw_in, lin_w, lin_b, S, NH, f, r, sr, sine_amp, noise_std, voiced_thr);
+                               HiftNoiseLoad{noise + (long)src[b] * NH * Lw_in + n, Lw_in}, lin_w, lin_b, S, NH, f, r, sr, sine_amp,
+                               noise_std, voiced_thr);
     }
+    s_out[i] = v;
+}
+
+// Ragged and seeded: row j draws from seeds[src[j]], the seed of the caller's utterance, at its own sample index -- the draws of
+// the run alone whatever the row, the padding and the micro-batch
+__global__ void hift_source_ragged_seeded_kernel(const float* __restrict__ f0, const double* __restrict__ prefix,
+                                                 const float* __restrict__ phase0, const unsigned long long* __restrict__ seeds,
+                                                 const float* __restrict__ lin_w, const float* __restrict__ lin_b,
+                                                 float* __restrict__ s_out, const int* __restrict__ src, const int* __restrict__ lens, int B,
+                                                 int S, int NH, int up, float sr, float sine_amp, float noise_std, float voiced_thr) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long Lw = (long)S * up;
+    if (i >= B * Lw) return;
+    const int b = (int)(i / Lw);
+    const long n = i - (long)b * Lw;
+    const int f = (int)(n / up), r = (int)(n - (long)f * up);
+    float v = 0.f;
+    if (f < lens[b])
+        v = hift_source_sample(f0[(long)b * S + f], prefix + (long)b * NH * S, phase0 + (long)src[b] * NH,
+                               HiftNoiseDraw{seeds[src[b]], (unsigned)n, {}}, lin_w, lin_b, S, NH, f, r, sr, sine_amp, noise_std,
+                               voiced_thr);
     s_out[i] = v;
 }
 
@@ -617,12 +676,23 @@ struct svc_hift {
     Arena tab;
     int* d_tab = nullptr;
     size_t tab_cap = 0;
+    // seeded calls: the call's seeds [B] and the phase0 [B][NH] drawn from them (the only draws that are ever stored)
+    int device = -1;
+    Arena seed_ar;
+    unsigned long long* d_seeds = nullptr;
+    float* d_phase0 = nullptr;
+    int seed_cap = 0;
 
     int reserve(int B, int S, hipStream_t st);
     // rg == null: B utterances of S frames each.  rg != null: micro-batch of a ragged call; mel / f0 / phase0 / noise / out / f0_out
     // are the caller's whole tensors and S the micro-batch's longest member
+    // seeds (device, indexed like phase0) set: the source noise is drawn from them and `noise` is not read
     int run(const float* mel, const float* f0, const float* phase0, const float* noise, int B, int S, float* out, float* f0_out,
-            hipStream_t st, const RaggedMB* rg = nullptr);
+            hipStream_t st, const RaggedMB* rg = nullptr, const unsigned long long* seeds = nullptr);
+    int forward(const float* mel, const float* f0, const float* phase0, const float* noise, const unsigned long long* seeds, int B,
+                int S, float* out, float* f0_out, hipStream_t st);
+    int forward_ragged(const float* mel, const int32_t* lens, const float* f0, const float* phase0, const float* noise,
+                       const unsigned long long* seeds, int B, int S, float* out, float* f0_out, hipStream_t st);
     // valid rows of an utterance of S frames after `stage` up-sampling stages (the last stage's reflection pad adds one row)
     long rows_after(int stage, long S) const {
         long L = S;
@@ -696,7 +766,7 @@ int svc_hift::reserve(int B, int S, hipStream_t st) {
 // runs over those F_b frames.  What the convs write past the end (x, y, xsum, si, post and the operand planes) is touched by
 // pointwise ops only.
 int svc_hift::run(const float* mel, const float* f0_in, const float* phase0, const float* noise, int B, int S, float* out,
-                  float* f0_out, hipStream_t st, const RaggedMB* rg) {
+                  float* f0_out, hipStream_t st, const RaggedMB* rg, const unsigned long long* seeds) {
     const int vd = dtype;
     const int* len0 = rg ? rg->len[0] : nullptr;
     const int NH = cfg.nb_harmonics + 1;
@@ -746,16 +816,26 @@ int svc_hift::run(const float* mel, const float* f0_in, const float* phase0, con
     const int ld18 = cpad(cfg.istft_n_fft + 2, dtype);
     const int* len_f = rg ? rg->len[cfg.num_upsamples] : nullptr;      // frames of the STFT / iSTFT = rows of the last stage
     if (rg) {
-        hipLaunchKernelGGL(hift_source_ragged_kernel, dim3(cdiv((long)B * Lw, 256)), dim3(256), 0, st, f0, prefix, phase0, noise,
-                           src_lin_w, src_lin_b, s_buf, rg->src, len0, B, S, rg->S_in, NH, up_total, (float)cfg.sampling_rate,
-                           cfg.nsf_alpha, cfg.nsf_sigma, cfg.nsf_voiced_threshold);
+        if (seeds)
+            hipLaunchKernelGGL(hift_source_ragged_seeded_kernel, dim3(cdiv((long)B * Lw, 256)), dim3(256), 0, st, f0, prefix, phase0,
+                               seeds, src_lin_w, src_lin_b, s_buf, rg->src, len0, B, S, NH, up_total, (float)cfg.sampling_rate,
+                               cfg.nsf_alpha, cfg.nsf_sigma, cfg.nsf_voiced_threshold);
+        else
+            hipLaunchKernelGGL(hift_source_ragged_kernel, dim3(cdiv((long)B * Lw, 256)), dim3(256), 0, st, f0, prefix, phase0, noise,
+                               src_lin_w, src_lin_b, s_buf, rg->src, len0, B, S, rg->S_in, NH, up_total, (float)cfg.sampling_rate,
+                               cfg.nsf_alpha, cfg.nsf_sigma, cfg.nsf_voiced_threshold);
         SVC_CHECK_HIP(hipGetLastError());
         hipLaunchKernelGGL(hift_stft_ragged_kernel, dim3(cdiv((long)B * F, 256)), dim3(256), 0, st, s_buf, stft32, rg->lw, len_f, B, Lw,
                            F, ld18);
     } else {
-        hipLaunchKernelGGL(hift_source_kernel, dim3(cdiv((long)B * Lw, 256)), dim3(256), 0, st, f0, prefix, phase0, noise, src_lin_w,
-                           src_lin_b, s_buf, B, S, NH, up_total, (float)cfg.sampling_rate, cfg.nsf_alpha, cfg.nsf_sigma,
-                           cfg.nsf_voiced_threshold);
+        if (seeds)
+            hipLaunchKernelGGL(hift_source_seeded_kernel, dim3(cdiv((long)B * Lw, 256)), dim3(256), 0, st, f0, prefix, phase0, seeds,
+                               src_lin_w, src_lin_b, s_buf, B, S, NH, up_total, (float)cfg.sampling_rate, cfg.nsf_alpha, cfg.nsf_sigma,
+                               cfg.nsf_voiced_threshold);
+        else
+            hipLaunchKernelGGL(hift_source_kernel, dim3(cdiv((long)B * Lw, 256)), dim3(256), 0, st, f0, prefix, phase0, noise, src_lin_w,
+                               src_lin_b, s_buf, B, S, NH, up_total, (float)cfg.sampling_rate, cfg.nsf_alpha, cfg.nsf_sigma,
+                               cfg.nsf_voiced_threshold);
         SVC_CHECK_HIP(hipGetLastError());
         hipLaunchKernelGGL(hift_stft_kernel, dim3(cdiv((long)B * F, 256)), dim3(256), 0, st, s_buf, stft32, B, Lw, F, ld18);
     }
@@ -983,6 +1063,7 @@ int svc_hift_create(const svc_hift_config_t* cfg, const svc_tensor_desc_t* weigh
     hipStream_t st = (hipStream_t)stream;
     svc_hift* m = new svc_hift();
     m->cfg = *cfg;
+    m->device = current_device();
     m->dtype = cfg->precision == 1 ? 0 : (cfg->precision == 2 ? 2 : (cfg->precision == 3 ? 3 : 1));   // operand mode: fp32 | fp16 | fp16x3 | fp16 + fp8 corrections
     m->up_total = cfg->istft_hop;
     for (int i = 0; i < cfg->num_upsamples; ++i) m->up_total *= cfg->upsample_rates[i];
@@ -1050,7 +1131,51 @@ int svc_hift_set_microbatch(svc_hift_t* m, int utterances) {
 int svc_hift_forward(svc_hift_t* m, const float* mel, const float* f0, const float* phase0, const float* noise, int B, int S,
                      float* out, float* f0_out, void* stream) {
     SVC_REQUIRE(m && mel && phase0 && noise && out && B >= 1 && S >= 1, "bad argument");
+    return m->forward(mel, f0, phase0, noise, nullptr, B, S, out, f0_out, (hipStream_t)stream);
+}
+
+int svc_hift_forward_ragged(svc_hift_t* m, const float* mel, const int32_t* lens, const float* f0, const float* phase0,
+                            const float* noise, int B, int S, float* out, float* f0_out, void* stream) {
+    SVC_REQUIRE(m && mel && lens && phase0 && noise && out && B >= 1 && S >= 1, "bad argument");
+    return m->forward_ragged(mel, lens, f0, phase0, noise, nullptr, B, S, out, f0_out, (hipStream_t)stream);
+}
+
+int svc_hift_forward_seeded(svc_hift_t* m, const float* mel, const int32_t* lens, const float* f0, const uint64_t* seeds, int B,
+                            int S, float* out, float* f0_out, void* stream) {
+    SVC_REQUIRE(m && mel && out, "null argument");
+    SVC_REQUIRE(seeds, "svc_hift_forward_seeded: seeds is NULL (HOST [B], one per utterance)");
+    SVC_REQUIRE(B >= 1 && S >= 1, "svc_hift_forward_seeded: B and S must be at least 1");
+    SVC_REQUIRE((long)S * m->up_total <= 0x7fffffffL, "svc_hift_forward_seeded: the sample index is a 32-bit counter word");
+    SVC_REQUIRE(current_device() == m->device, "this handle was created on another device (make it current before the call)");
+    if (lens)
+        for (int b = 0; b < B; ++b) SVC_REQUIRE(lens[b] >= 0 && lens[b] <= S, "svc_hift_forward_seeded: lens out of range");
     hipStream_t st = (hipStream_t)stream;
+    const int NH = m->cfg.nb_harmonics + 1;
+    if (B > m->seed_cap) {
+        SVC_CHECK_HIP(hipStreamSynchronize(st));
+        m->seed_ar.release();
+        m->seed_cap = 0;
+        m->d_seeds = m->seed_ar.alloc_n<unsigned long long>(B, st);
+        m->d_phase0 = m->seed_ar.alloc_n<float>((size_t)B * NH, st);
+        if (!m->d_seeds || !m->d_phase0) return 1;
+        m->seed_cap = B;
+    }
+    void* h = m->staging.acquire((size_t)B * 8);
+    if (!h) return 1;
+    memcpy(h, seeds, (size_t)B * 8);
+    SVC_CHECK_HIP(hipMemcpyAsync(m->d_seeds, h, (size_t)B * 8, hipMemcpyHostToDevice, st));
+    if (m->staging.commit(st)) return 1;
+    hipLaunchKernelGGL(noise_phase0_kernel, dim3(cdiv(B * NH, 256)), dim3(256), 0, st, m->d_seeds, 0ull, B, NH, m->d_phase0);
+    SVC_CHECK_HIP(hipGetLastError());
+    if (lens) return m->forward_ragged(mel, lens, f0, m->d_phase0, nullptr, m->d_seeds, B, S, out, f0_out, st);
+    return m->forward(mel, f0, m->d_phase0, nullptr, m->d_seeds, B, S, out, f0_out, st);
+}
+
+}  // extern "C"
+
+int svc_hift::forward(const float* mel, const float* f0, const float* phase0, const float* noise, const unsigned long long* seeds,
+                      int B, int S, float* out, float* f0_out, hipStream_t st) {
+    svc_hift* m = this;
     const int NH = m->cfg.nb_harmonics + 1;
     const long Lw = (long)S * m->up_total;
     // measured, vocoder alone, B = 32 x S = 430 (round 3, fp16p8): 4: 37.4, 8: 29.5, 16: 28.2, 32: 26.9 ms
@@ -1059,17 +1184,17 @@ int svc_hift_forward(svc_hift_t* m, const float* mel, const float* f0, const flo
         const int nb = std::min(mb, B - b0);
         if (m->reserve(nb, S, st)) return 1;
         if (m->run(mel + (long)b0 * m->cfg.in_channels * S, f0 ? f0 + (long)b0 * S : nullptr, phase0 + (long)b0 * NH,
-                   noise + (long)b0 * NH * Lw, nb, S, out + (long)b0 * Lw, f0_out ? f0_out + (long)b0 * S : nullptr, st))
+                   noise ? noise + (long)b0 * NH * Lw : nullptr, nb, S, out + (long)b0 * Lw, f0_out ? f0_out + (long)b0 * S : nullptr, st,
+                   nullptr, seeds ? seeds + b0 : nullptr))
             return 1;
     }
     return 0;
 }
 
-int svc_hift_forward_ragged(svc_hift_t* m, const float* mel, const int32_t* lens, const float* f0, const float* phase0,
-                            const float* noise, int B, int S, float* out, float* f0_out, void* stream) {
-    SVC_REQUIRE(m && mel && lens && phase0 && noise && out && B >= 1 && S >= 1, "bad argument");
+int svc_hift::forward_ragged(const float* mel, const int32_t* lens, const float* f0, const float* phase0, const float* noise,
+                             const unsigned long long* seeds, int B, int S, float* out, float* f0_out, hipStream_t st) {
+    svc_hift* m = this;
     for (int b = 0; b < B; ++b) SVC_REQUIRE(lens[b] >= 0 && lens[b] <= S, "svc_hift_forward_ragged: lens out of range");
-    hipStream_t st = (hipStream_t)stream;
     const int nu = m->cfg.num_upsamples;
     // Longest first (stable: a batch of equal lengths runs exactly as svc_hift_forward runs it), cut into micro-batches of one
     // kernel class (svc_hift::kernel_class), each padded to its own longest member only.
@@ -1134,10 +1259,12 @@ int svc_hift_forward_ragged(svc_hift_t* m, const float* mel, const int32_t* lens
             }
             continue;
         }
-        if (m->run(mel, f0, phase0, noise, nb, Smb, out, f0_out, st, &rg)) return 1;
+        if (m->run(mel, f0, phase0, noise, nb, Smb, out, f0_out, st, &rg, seeds)) return 1;
     }
     return 0;
 }
+
+extern "C" {
 
 // ---- op-level entry points for the parity tests -------------------------------------------------------
 namespace {

@@ -85,6 +85,38 @@ def long_batch_plan(n_srcs, prompt_lens, max_context_window, overlap_frame_len=1
     return dict(chunks=chunks, bodies=bodies, out_lens=out_lens, micro_batches=micro)
 
 
+def derive_seed(seed, index):
+    """The seed of part `index` (a chunk of a file, a block of a stream) of the request seeded `seed`: the splitmix64
+    finaliser of (seed + (index + 1) * 0x9E3779B97F4A7C15) mod 2^64.  A pure host function, a bijection of the 64-bit
+    state for every index and injective in index for every seed; the one way the composite calls here make per-part seeds."""
+    seed, index = int(seed), int(index)
+    if not 0 <= seed < 1 << 64 or index < 0:
+        raise ValueError(f"derive_seed: seed {seed} outside [0, 2^64) or index {index} negative")
+    m = (1 << 64) - 1
+    x = (seed + (index + 1) * 0x9E3779B97F4A7C15) & m
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & m
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & m
+    return x ^ (x >> 31)
+
+
+def _seed_list(what, seeds, n, z=None, vocoder_kwargs=None):
+    """seeds of a pipeline call -> n host integers in [0, 2^64) (None stays None).  ValueError, before anything touches a
+    device, for a wrong count, a seed out of range, and seeds given together with the tensors they stand for."""
+    if seeds is None:
+        return None
+    if z is not None:
+        raise ValueError(f"{what}: give seeds or z, not both")
+    if vocoder_kwargs and ("phase0" in vocoder_kwargs or "noise" in vocoder_kwargs):
+        raise ValueError(f"{what}: give seeds or phase0 / noise in vocoder_kwargs, not both")
+    from . import _lib
+    return _lib.seed_ints(seeds, n, what)
+
+
+def _cfm_seeds(seeds):
+    """The sampler call's seeds keyword, passed only when there are seeds (a stand-in sampler need not know it)."""
+    return {} if seeds is None else {"seeds": seeds}
+
+
 def _index_runs(members):
     """[(a, b)]: the sorted indices `members` as consecutive ranges a .. b - 1 (slices need no index tensor on the device)."""
     runs = []
@@ -103,17 +135,25 @@ class HotPath:
         self.cfm = cfm
         self.vocoder = vocoder
 
+    def _vocoder_seeds(self, seeds):
+        """{"seeds": seeds} for a vocoder that draws (HiFT), {} for one that does not (BigVGAN) or without seeds."""
+        from .vocoder import HiFT
+        return {"seeds": seeds} if seeds is not None and isinstance(self.vocoder, HiFT) else {}
+
     @torch.inference_mode()
     def convert_batch(self, mu, prompt, style, n_timesteps, inference_cfg_rate, z=None, x_lens=None,
-                      prompt_lens=None, vocoder_kwargs=None):
-        """B utterances (each an independent reference run): -> (mel (B,C,S), wave (B, S*hop))."""
+                      prompt_lens=None, vocoder_kwargs=None, seeds=None):
+        """B utterances (each an independent reference run): -> (mel (B,C,S), wave (B, S*hop)).  seeds: B integers in
+        [0, 2^64), exclusive with z and with phase0 / noise in vocoder_kwargs: seeds[b] gives utterance b's sampler noise and,
+        if the vocoder is a HiFT, its source draws, all made on the device (`CFM.inference`, `HiFT.__call__`)."""
         B, T = mu.size(0), mu.size(1)
+        seeds = _seed_list("convert_batch", seeds, B, z, vocoder_kwargs)
         P = prompt.size(-1)
         lens = x_lens if x_lens is not None else torch.LongTensor([T] * B)
         mel = self.cfm.inference(mu, lens, prompt, style, None, n_timesteps, inference_cfg_rate=inference_cfg_rate,
-                                 z=z, prompt_lens=prompt_lens)
+                                 z=z, prompt_lens=prompt_lens, **_cfm_seeds(seeds))
         vc_target = mel[:, :, P:]                                   # inference.py:505
-        wave = self.vocoder(vc_target.float(), **(vocoder_kwargs or {}))
+        wave = self.vocoder(vc_target.float(), **(vocoder_kwargs or {}), **self._vocoder_seeds(seeds))
         return vc_target, wave.reshape(B, -1)
 
     @torch.inference_mode()
@@ -125,11 +165,28 @@ class HotPath:
         per-row lengths -> `svc_mel_strip_prompt` (padding = the log-mel floor) -> ONE `vocoder(vc, lens=S)` call, BigVGAN or HiFT
         (`svc_bigvgan_forward_ragged` / `svc_hift_forward_ragged`: no utterance sees its neighbour's padding); a batch of one
         output length is one plain vocoder call.  vocoder_kwargs: HiFT's pinned f0 (B, Smax) / phase0 / noise (B, nh, Smax * up),
-        row b being the draws of utterance b alone in its leading part.  Everything is enqueued from the host integers:
-        no synchronisation."""
+        row b being the draws of utterance b alone in its leading part (`convert_batch_ragged_seeded`: seeds instead of
+        tensors).  Everything is enqueued from the host integers: no synchronisation."""
+        return self._convert_batch_ragged(mu, prompt, style, x_lens, prompt_lens, n_timesteps, inference_cfg_rate, z, vocoder_kwargs, None)
+
+    @torch.inference_mode()
+    def convert_batch_ragged_seeded(self, mu, prompt, style, x_lens, prompt_lens, n_timesteps, inference_cfg_rate, seeds,
+                                    vocoder_kwargs=None):
+        """`convert_batch_ragged` with seeds (B integers in [0, 2^64)) in place of z and of phase0 / noise in vocoder_kwargs
+        (which may still pin HiFT's f0): utterance b's sampler noise and, if the vocoder is a HiFT, its source draws are those
+        of seeds[b], made on the device, whatever its row, the padding and its neighbours -- bit for bit `convert_batch_ragged`
+        fed `CFM.noise_draws` / `HiFT.noise_draws` of each seed.  (A method of its own: the parameter list of
+        `convert_batch_ragged` is part of its contract.)"""
+        if seeds is None:
+            raise ValueError("convert_batch_ragged_seeded: seeds is None")
+        return self._convert_batch_ragged(mu, prompt, style, x_lens, prompt_lens, n_timesteps, inference_cfg_rate, None, vocoder_kwargs,
+                                          seeds)
+
+    def _convert_batch_ragged(self, mu, prompt, style, x_lens, prompt_lens, n_timesteps, inference_cfg_rate, z, vocoder_kwargs, seeds):
         import ctypes as C
         from . import _lib
         B, T = mu.size(0), mu.size(1)
+        seeds = _seed_list("convert_batch_ragged_seeded", seeds, B, z, vocoder_kwargs)
         x_lens = [int(v) for v in (x_lens.tolist() if torch.is_tensor(x_lens) else x_lens)]
         P = [int(v) for v in (prompt_lens.tolist() if torch.is_tensor(prompt_lens) else prompt_lens)]
         if len(x_lens) != B or len(P) != B:
@@ -141,13 +198,13 @@ class HotPath:
         i32 = lambda v: (C.c_int32 * len(v))(*v)                                                    # noqa: E731
         with torch.cuda.device(dev):
             mel = self.cfm.inference(mu, x_lens, prompt, style, None, n_timesteps, inference_cfg_rate=inference_cfg_rate,
-                                     z=z, prompt_lens=P)
+                                     z=z, prompt_lens=P, **_cfm_seeds(seeds))
             mel = _lib.f32c(mel, dev)
             Cm, Smax = mel.size(1), max(max(S), 1)
             vc = torch.empty(B, Cm, Smax, device=dev)
             _lib.check(_lib.lib().svc_mel_strip_prompt(_lib.ptr(mel), i32(P), i32(x_lens), B, Cm, T, Smax, C.c_float(LOG_MEL_FLOOR),
                                                        _lib.ptr(vc), _lib.stream_ptr()))
-            kw = dict(vocoder_kwargs or {})
+            kw = dict(vocoder_kwargs or {}, **self._vocoder_seeds(seeds))
             if len(set(S)) > 1:
                 kw["lens"] = S
             wave = self.vocoder(vc, **kw).reshape(B, -1)
@@ -236,7 +293,7 @@ class HotPath:
 
     @torch.inference_mode()
     def convert_long_batch(self, utterances, n_timesteps, inference_cfg_rate, hop, max_context_window, overlap_frame_len=16,
-                           noise_fn=None, vocoder_kwargs_fn=None, max_chunks=64, ragged_vocoder=None):
+                           noise_fn=None, vocoder_kwargs_fn=None, max_chunks=64, ragged_vocoder=None, seeds=None):
         """Long-form conversion of one or more files with every chunk in ONE pool: a chunk reads the source, its file's
         prompt and fresh noise, never its neighbour, so the chunks of all files go through the sampler and the vocoder as
         ragged batches of up to `max_chunks` chunks, and one launch cross-fades and concatenates them (`svc_chunks_assemble`:
@@ -258,9 +315,17 @@ class HotPath:
         cannot be combined with the ragged call.
         noise_fn(T_k) -> (1, C, T_k) is called once per chunk in plan order with T_k = P_u + frames, the calls of the
         sequential loops.  With noise_fn=None the noise is one torch.randn per micro-batch: the same distribution, NOT the
-        stream of draws the sequential loops consume.  One host synchronisation, at the end."""
+        stream of draws the sequential loops consume.
+        seeds: one integer in [0, 2^64) per file, exclusive with noise_fn and vocoder_kwargs_fn: chunk k of file u draws its
+        sampler noise and, if the vocoder is a HiFT, its source draws from `derive_seed(seeds[u], k)`, on the device and inside
+        the batched calls -- a file's audio is then a function of its own inputs and seed, whatever shares the pool.  The
+        ragged HiFT call is allowed with seeds (ragged_vocoder=True): there are no positional draws.
+        One host synchronisation, at the end."""
         import ctypes as C
         from . import _lib
+        if seeds is not None and (noise_fn is not None or vocoder_kwargs_fn is not None):
+            raise ValueError("convert_long_batch: give seeds or noise_fn / vocoder_kwargs_fn, not both")
+        seeds = _seed_list("convert_long_batch", seeds, len(utterances))
         if ragged_vocoder is None:
             from .vocoder import BigVGAN
             ragged_vocoder = isinstance(self.vocoder, BigVGAN)
@@ -298,6 +363,12 @@ class HotPath:
                 mel_all[u, :, :P[u]] = mel2[0]
             style_all = torch.cat([_lib.f32c(t[3], dev) for t in utterances])
             utt = [c[0] for c in chunks]
+            chunk_seeds = None
+            if seeds is not None:       # chunk k of its file: the chunks are listed utterance-major
+                first_of = {}
+                for k, u in enumerate(utt):
+                    first_of.setdefault(u, k)
+                chunk_seeds = [derive_seed(seeds[u], k - first_of[u]) for k, u in enumerate(utt)]
             if U > 1:
                 idx = torch.tensor(utt, device=dev)
                 mel_chunks, style_chunks = mel_all.index_select(0, idx), style_all.index_select(0, idx)
@@ -324,21 +395,24 @@ class HotPath:
                     for i, t_k in enumerate(x_lens):
                         z[i, :, :t_k] = noise_fn(t_k)[0]
                 kws = [vocoder_kwargs_fn(s) for s in S] if vocoder_kwargs_fn is not None else None
+                mb_seeds = chunk_seeds[k0:k1] if chunk_seeds is not None else None
                 mel = self.cfm.inference(mu, x_lens, mel_chunks[k0:k1], style_chunks[k0:k1], None, n_timesteps,
-                                         inference_cfg_rate=inference_cfg_rate, z=z, prompt_lens=Pk)
+                                         inference_cfg_rate=inference_cfg_rate, z=z, prompt_lens=Pk, **_cfm_seeds(mb_seeds))
                 mel = _lib.f32c(mel, dev)
                 vc = torch.empty(n, Cm, Smax, device=dev)
                 _lib.check(_lib.lib().svc_mel_strip_prompt(_lib.ptr(mel), i32(Pk), i32(x_lens), n, Cm, T, Smax,
                                                            C.c_float(LOG_MEL_FLOOR), _lib.ptr(vc), _lib.stream_ptr()))
                 groups = group_by_length(S)
                 if ragged_vocoder and len(groups) > 1:
-                    self._store_waves(waves, [(k0, k1)], self.vocoder(vc, lens=S), Smax * hop)
+                    self._store_waves(waves, [(k0, k1)], self.vocoder(vc, lens=S, **self._vocoder_seeds(mb_seeds)), Smax * hop)
                 else:
                     for s_len, members in groups.items():
                         runs = _index_runs(members)
                         m = vc if len(members) == n and s_len == Smax else \
                             torch.cat([vc[a:b, :, :s_len] for a, b in runs]).contiguous()
                         kw = {key: torch.cat([kws[i][key] for i in members]) for key in kws[members[0]]} if kws else {}
+                        if mb_seeds is not None:
+                            kw = self._vocoder_seeds([mb_seeds[i] for i in members])
                         self._store_waves(waves, [(k0 + a, k0 + b) for a, b in runs], self.vocoder(m, **kw), s_len * hop)
             lens = [c[2] * hop for c in chunks]
             _lib.check(_lib.lib().svc_chunks_assemble(_lib.ptr(waves), C.c_longlong(stride), i32(lens), i32([int(c[3]) for c in chunks]),
@@ -447,10 +521,12 @@ class V2HotPath:
     @torch.inference_mode()
     def convert_batch(self, src_narrow, targets, frames_per_token, n_timesteps, cfg_rates=(0.7, 0.7), top_p=0.7,
                       temperature=0.7, repetition_penalty=1.5, max_new=4001, seeds=None, exp_noise=None, z=None,
-                      random_voice=False):
+                      random_voice=False, noise_seeds=None):
         """src_narrow: list of B (1, Ns_b) token tensors; targets: list of B records of `prepare_target`;
         frames_per_token: list of B floats (see `v2_target_frames`); seeds | exp_noise: the AR draws (`ARModel.generate_batch`);
-        z: the sampler's noise, a (B, C, >= T) tensor or a list of B (1, C, >= P_b + S_b) tensors (torch.randn when None).
+        z: the sampler's noise, a (B, C, >= T) tensor or a list of B (1, C, >= P_b + S_b) tensors (torch.randn when None);
+        noise_seeds: B integers in [0, 2^64) instead of z -- utterance b's sampler noise is drawn on the device from
+        noise_seeds[b] (`CFM.inference(seeds=)`; `seeds` keeps meaning the AR draws only).
         -> list of B dicts {tokens (1, n_b), mel (1, C, S_b), wave (1, S_b * hop)}.  One host synchronisation (the token
         counts); everything after it is enqueued from host integers."""
         import ctypes as C
@@ -460,6 +536,7 @@ class V2HotPath:
             raise ValueError("convert_batch: src_narrow, targets and frames_per_token must have one entry per utterance")
         if seeds is not None and exp_noise is not None:
             raise ValueError("convert_batch: give seeds or exp_noise, not both")
+        noise_seeds = _seed_list("convert_batch (noise_seeds)", noise_seeds, B, z)
         if B == 0:
             return []
         with torch.cuda.device(dev):
@@ -509,7 +586,8 @@ class V2HotPath:
                     zz[i, :, :x_lens[i]] = _lib.f32c(z[b], dev).reshape(Cm, -1)[:, :x_lens[i]]
                 z = zz
             mel = self.cfm.inference(mu, x_lens, st["mel"], st["style"], None, n_timesteps, inference_cfg_rate=list(cfg_rates),
-                                     random_voice=random_voice, z=z, prompt_lens=P)
+                                     random_voice=random_voice, z=z, prompt_lens=P,
+                                     **_cfm_seeds([noise_seeds[b] for b in live] if noise_seeds is not None else None))
             self._mark("cfm")
             vc = torch.empty(L, Cm, Smax, device=dev)
             _lib.check(_lib.lib().svc_mel_strip_prompt(_lib.ptr(mel), i32(P), i32(x_lens), L, Cm, T, Smax, C.c_float(LOG_MEL_FLOOR),
@@ -671,11 +749,26 @@ class RealtimeEngine:
     def step(self, slots, content, n_timesteps, inference_cfg_rate, z=None, vocoder_kwargs=None, return_parts=False):
         """One block for the streams `slots` (a list of open slots, no slot twice); content (n, Tin, Din), row k for
         slots[k]; z: the sampler's noise (n, C, Pmax + S), torch.randn when None; vocoder_kwargs: passed to the vocoder call
-        (HiFT's pinned draws).  -> (n, block) float32 on the device; with return_parts also
-        dict(mel (n, C, S), infer (n, n_inf), offsets (n,) int32)."""
+        (HiFT's pinned draws); `step_seeded` takes seeds instead of the tensors.  -> (n, block) float32 on the device; with
+        return_parts also dict(mel (n, C, S), infer (n, n_inf), offsets (n,) int32)."""
+        return self._step(slots, content, n_timesteps, inference_cfg_rate, z, vocoder_kwargs, return_parts, None)
+
+    @torch.inference_mode()
+    def step_seeded(self, slots, content, n_timesteps, inference_cfg_rate, seeds, vocoder_kwargs=None, return_parts=False):
+        """`step` with seeds -- n integers in [0, 2^64) for THIS block, row k for slots[k] -- in place of z and of phase0 /
+        noise in vocoder_kwargs (which may still pin HiFT's f0).  The caller derives them per block, e.g.
+        `derive_seed(stream_seed, block_index)`; they give the sampler noise and, if the vocoder is a HiFT, its source draws,
+        made on the device: bit for bit `step` fed `CFM.noise_draws` / `HiFT.noise_draws` of each seed.  (A method of its
+        own: the parameter list of `step` is part of its contract.)"""
+        if seeds is None:
+            raise ValueError("RealtimeEngine.step_seeded: seeds is None")
+        return self._step(slots, content, n_timesteps, inference_cfg_rate, None, vocoder_kwargs, return_parts, seeds)
+
+    def _step(self, slots, content, n_timesteps, inference_cfg_rate, z, vocoder_kwargs, return_parts, seeds):
         import ctypes as C
         from . import _lib
         slots = [int(s) for s in slots]
+        seeds = _seed_list("RealtimeEngine.step_seeded", seeds, len(slots), z, vocoder_kwargs)
         for s in slots:
             self._check_slot(s, "step")
         if len(set(slots)) != len(slots):
@@ -702,12 +795,14 @@ class RealtimeEngine:
                                                        Dc, T, _lib.ptr(mu), _lib.stream_ptr()))
             x_lens = [p + S for p in P]
             mel = self.cfm.inference(mu, x_lens, st["mel"], st["style"], None, n_timesteps, inference_cfg_rate=inference_cfg_rate,
-                                     z=z, prompt_lens=P)
+                                     z=z, prompt_lens=P, **_cfm_seeds(seeds))
             mel = _lib.f32c(mel, dev)
             vc = torch.empty(n, Cm, S, device=dev)
             _lib.check(_lib.lib().svc_mel_strip_prompt(_lib.ptr(mel), i32(P), i32(x_lens), n, Cm, T, S, C.c_float(LOG_MEL_FLOOR),
                                                        _lib.ptr(vc), _lib.stream_ptr()))
-            wave = _lib.f32c(self.vocoder(vc, **(vocoder_kwargs or {})), dev).reshape(n, -1)
+            from .vocoder import HiFT
+            vkw = dict(vocoder_kwargs or {}, **({"seeds": seeds} if seeds is not None and isinstance(self.vocoder, HiFT) else {}))
+            wave = _lib.f32c(self.vocoder(vc, **vkw), dev).reshape(n, -1)
             if wave.size(1) != S * self.hop:
                 raise ValueError(f"RealtimeEngine.step: the vocoder gave {wave.size(1)} samples per row, {S * self.hop} expected "
                                  f"(frames x hop)")

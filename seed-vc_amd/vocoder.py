@@ -7,7 +7,8 @@ drivers call it as `vocoder_fn(vc_target.float())`, inference.py:506, and `.sque
 operands with three MFMA products per step (fp32-class accuracy, faster), "fp16p8" = the same split with the two
 correction products of the long stride-1 convs in ONE block-scaled fp8 MFMA (waveform RMS ~1e-5: inside the 1e-4 bound
 with margin, faster again), "fp16" = plain fp16 operands (2.4e-4: outside the bound, reported only).  HiFT's random draws (SineGen phases and noise,
-generator.py:208-222) are drawn here with torch when the caller does not pass them.
+generator.py:208-222) are drawn here with torch when the caller does not pass them; with `seeds=` (one 64-bit seed per
+utterance) they are drawn on the device inside the source kernel instead and no (B, nh, S * up) tensor exists.
 """
 import ctypes as C
 import math
@@ -125,13 +126,19 @@ class HiFT:
         _lib.check(_lib.lib().svc_hift_set_microbatch(self._h, int(n)))
 
     @torch.inference_mode()
-    def __call__(self, x, f0=None, phase0=None, noise=None, return_f0=False, lens=None):
+    def __call__(self, x, f0=None, phase0=None, noise=None, return_f0=False, lens=None, seeds=None):
         """x (B, 80, S) -> (B, S * up) [, f0 (B, S)].  lens (list / LongTensor of B ints, 0 <= lens[b] <= S): a ragged batch in
         one call -- out[b, :lens[b] * up] is the waveform of x[b, :, :lens[b]] run alone with f0[b, :lens[b]], phase0[b] and
         noise[b, :, :lens[b] * up] (the draws of the run alone), the rest of the row and of the returned f0 is zero, and
         frames, f0 values and noise samples past an utterance's end may hold anything (svc_hift_forward_ragged in
-        include/seedvc_hip.h).  Draws made here have the same shapes with and without lens."""
+        include/seedvc_hip.h).  Draws made here have the same shapes with and without lens.
+        seeds (B integers in [0, 2^64), exclusive with phase0 / noise): utterance b uses the draws of seeds[b], made inside
+        the source kernel (`svc_hift_forward_seeded`; `noise_draws` returns them); with lens, row b is utterance b run alone
+        with its seed, bit for bit."""
         B, _, S = x.shape
+        if seeds is not None and (phase0 is not None or noise is not None):
+            raise ValueError("HiFT: give seeds or phase0 / noise, not both")
+        seeds_keep = _lib.seeds_host(seeds, B, "HiFT") if seeds is not None else None
         if lens is not None:
             lens = [int(v) for v in (lens.tolist() if torch.is_tensor(lens) else lens)]
             if len(lens) != B:
@@ -139,6 +146,16 @@ class HiFT:
         nh = self.cfg["nb_harmonics"] + 1
         Lw = S * self.total_up
         dev = self.device
+        if seeds is not None:
+            with torch.cuda.device(dev):
+                mel = _lib.f32c(x, dev)
+                f0t = _lib.f32c(f0, dev) if f0 is not None else None
+                out = torch.empty(B, Lw, device=dev, dtype=torch.float32)
+                f0_out = torch.empty(B, S, device=dev, dtype=torch.float32) if return_f0 else None
+                _lib.check(_lib.lib().svc_hift_forward_seeded(self._h, _lib.ptr(mel), (C.c_int32 * B)(*lens) if lens is not None else None,
+                                                              _lib.ptr(f0t), seeds_keep, B, S, _lib.ptr(out), _lib.ptr(f0_out),
+                                                              _lib.stream_ptr()))
+            return (out, f0_out) if return_f0 else out
         with torch.cuda.device(dev):
             mel = _lib.f32c(x, dev)
             if phase0 is None:     # Uniform(-pi, pi).sample((B, nh, 1)): generator.py:208-209
@@ -160,6 +177,18 @@ class HiFT:
 
     forward = __call__
     inference = __call__
+
+    @torch.inference_mode()
+    def noise_draws(self, seed, n_frames):
+        """(phase0 (1, nh, 1), noise (1, nh, n_frames * up)): the draws `__call__(seeds=[seed])` uses for an utterance of
+        n_frames frames (`svc_hift_noise_draws`)."""
+        seed = _lib.seeds_host([seed], 1, "HiFT.noise_draws")[0]
+        nh, n = self.cfg["nb_harmonics"] + 1, int(n_frames) * self.total_up
+        with torch.cuda.device(self.device):
+            phase0 = torch.empty(1, nh, 1, device=self.device, dtype=torch.float32)
+            noise = torch.empty(1, nh, n, device=self.device, dtype=torch.float32)
+            _lib.check(_lib.lib().svc_hift_noise_draws(seed, nh, n, _lib.ptr(phase0), _lib.ptr(noise), _lib.stream_ptr()))
+        return phase0, noise
 
     def close(self):
         if self._h:
