@@ -176,6 +176,11 @@ def make_descs(state_dict, device):
     return arr, len(items), keep
 
 
+def int_list(v):
+    """list / tensor / array of integers -> list of Python ints."""
+    return [int(x) for x in (v.tolist() if torch.is_tensor(v) else v)]
+
+
 def i64_host(values):
     if values is None:
         return None
@@ -183,9 +188,14 @@ def i64_host(values):
     return (C.c_int64 * len(vals))(*vals)
 
 
+def i32_host(values):
+    """Python ints -> a HOST int32 array (lengths and slots travel as kernel arguments)."""
+    return (C.c_int32 * len(values))(*values)
+
+
 def seed_ints(seeds, n, what):
     """seeds (list / tensor of n integers in [0, 2^64)) -> list of ints; ValueError for a wrong count or a seed out of range."""
-    vals = [int(v) for v in (seeds.tolist() if torch.is_tensor(seeds) else seeds)]
+    vals = int_list(seeds)
     if len(vals) != n:
         raise ValueError(f"{what}: {len(vals)} seeds for {n} utterances")
     for v in vals:

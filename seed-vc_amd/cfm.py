@@ -75,7 +75,7 @@ class Estimator:
             tval = float(t.reshape(-1)[0]) if torch.is_tensor(t) else float(t)
             lens = None
             if x_lens is not None:
-                xl = [int(v) for v in (x_lens.tolist() if torch.is_tensor(x_lens) else x_lens)]
+                xl = _lib.int_list(x_lens)
                 if len(xl) == 1 and N > 1:
                     xl = xl * N
                 lens = _lib.i64_host(xl)
@@ -135,7 +135,7 @@ class CFM:
             a.z = z.data_ptr() if z is not None else None
             xl = None
             if x_lens is not None:
-                xl = [int(v) for v in (x_lens.tolist() if torch.is_tensor(x_lens) else x_lens)]
+                xl = _lib.int_list(x_lens)
                 if len(xl) == 1 and B > 1:
                     xl = xl * B
             lens_keep = _lib.i64_host(xl)

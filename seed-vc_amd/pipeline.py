@@ -2,14 +2,25 @@
 chunk / crossfade loop around it (reference: inference.py:470-527, seed_vc_wrapper.py:561-623) and the
 multi-GPU sharding of utterance batches.
 """
+import collections
+import ctypes as C
+
 import numpy as np
 import torch
+
+from . import _lib
+
+
+def _cos2_windows(n):
+    """(fade_in, fade_out) of the drivers' cos^2 crossfade over n samples, float64 (reference: inference.py:343-350).  The
+    one place they are computed: `svc_crossfade` and `svc_chunks_assemble` take them as arrays and `crossfade` is their
+    yardstick, so the host and device paths agree bit for bit."""
+    return np.cos(np.linspace(np.pi / 2, 0, n)) ** 2, np.cos(np.linspace(0, np.pi / 2, n)) ** 2
 
 
 def crossfade(chunk1, chunk2, overlap):
     """cos^2 crossfade on numpy chunks, in place on chunk2 (reference: inference.py:343-350)."""
-    fade_out = np.cos(np.linspace(0, np.pi / 2, overlap)) ** 2
-    fade_in = np.cos(np.linspace(np.pi / 2, 0, overlap)) ** 2
+    fade_in, fade_out = _cos2_windows(overlap)
     if len(chunk2) < overlap:
         chunk2[:overlap] = chunk2[:overlap] * fade_in[:len(chunk2)] + (chunk1[-overlap:] * fade_out)[:len(chunk2)]
     else:
@@ -108,13 +119,63 @@ def _seed_list(what, seeds, n, z=None, vocoder_kwargs=None):
         raise ValueError(f"{what}: give seeds or z, not both")
     if vocoder_kwargs and ("phase0" in vocoder_kwargs or "noise" in vocoder_kwargs):
         raise ValueError(f"{what}: give seeds or phase0 / noise in vocoder_kwargs, not both")
-    from . import _lib
     return _lib.seed_ints(seeds, n, what)
 
 
 def _cfm_seeds(seeds):
     """The sampler call's seeds keyword, passed only when there are seeds (a stand-in sampler need not know it)."""
     return {} if seeds is None else {"seeds": seeds}
+
+
+# ------------------------------------------------- the second half of every composite call: prompts, strip, vocoder
+LOG_MEL_FLOOR = -11.512925464970229        # log(1e-5): the mel front-end's clamp (modules/audio.py:45-82)
+
+
+def _stack_prompts(records, device=None):
+    """records: [(prompt_condition (1, P_b, Dc), mel (1, C, P_b), style (1, Ds))], one per reference -> dict(prompt_condition
+    (n, Pmax, Dc), mel (n, C, Pmax), style (n, Ds), P = [P_b], Pmax), zero beyond each P_b."""
+    device = records[0][0].device if device is None else device
+    P = [int(mel.size(2)) for _, mel, _ in records]
+    Pmax = max(P)
+    pc = torch.zeros(len(records), Pmax, records[0][0].size(2), device=device)
+    mel = torch.zeros(len(records), records[0][1].size(1), Pmax, device=device)
+    for b, (c, m, _) in enumerate(records):
+        pc[b, :P[b]] = c[0]
+        mel[b, :, :P[b]] = m[0]
+    return dict(prompt_condition=pc, mel=mel, style=torch.cat([_lib.f32c(s, device) for _, _, s in records]), P=P, Pmax=Pmax)
+
+
+def _assemble_cond(prompt_condition, P, cond, S, T):
+    """mu (n, T, Dc): row b is prompt_condition[b, :P[b]], then cond[b, :S[b]], then zeros (`svc_v2_assemble_cond`).
+    prompt_condition (n, Pmax, Dc) and cond (n, >= max(S), Dc) on one device, P / S host integers."""
+    cond = _lib.f32c(cond, prompt_condition.device)
+    n, Dc = cond.size(0), cond.size(2)
+    mu = torch.empty(n, T, Dc, device=cond.device)
+    _lib.check(_lib.lib().svc_v2_assemble_cond(_lib.ptr(prompt_condition), _lib.i32_host(P), _lib.ptr(cond), _lib.i32_host(S), n,
+                                               prompt_condition.size(1), max(S), Dc, T, _lib.ptr(mu), _lib.stream_ptr()))
+    return mu
+
+
+def _strip_prompt(mel, P, x_lens, Smax):
+    """vc (n, C, Smax): row b is mel[b, :, P[b]:x_lens[b]], then the log-mel floor (`svc_mel_strip_prompt`; inference.py:505
+    for a ragged batch).  mel (n, C, T) as the sampler returns it, P / x_lens host integers."""
+    mel = _lib.f32c(mel)
+    n, Cm, T = mel.shape
+    vc = torch.empty(n, Cm, Smax, device=mel.device)
+    _lib.check(_lib.lib().svc_mel_strip_prompt(_lib.ptr(mel), _lib.i32_host(P), _lib.i32_host(x_lens), n, Cm, T, Smax,
+                                               C.c_float(LOG_MEL_FLOOR), _lib.ptr(vc), _lib.stream_ptr()))
+    return vc
+
+
+def group_by_length(lengths):
+    """{S: [indices b with lengths[b] == S]} for S > 0, in order of first appearance: the grouped vocoder path runs once
+    per group, because a plain vocoder call has no length argument and its convolutions would see another utterance's
+    padding (the ragged call, `BigVGAN.__call__(mel, lens=...)`, takes the lengths instead)."""
+    groups = {}
+    for b, s in enumerate(lengths):
+        if s > 0:
+            groups.setdefault(int(s), []).append(b)
+    return groups
 
 
 def _index_runs(members):
@@ -128,6 +189,64 @@ def _index_runs(members):
     return [tuple(r) for r in runs]
 
 
+_VocoderCall = collections.namedtuple("_VocoderCall", "runs frames mel wave")
+
+
+def _vocoder_seeds(vocoder, seeds):
+    """{"seeds": seeds} for a vocoder that draws (HiFT), {} for one that does not (BigVGAN) or without seeds."""
+    from .vocoder import HiFT
+    return {"seeds": seeds} if seeds is not None and isinstance(vocoder, HiFT) else {}
+
+
+def _vocode(vocoder, vc, S, ragged, what, hop=None, seeds=None, seed_kw=None, vocoder_kwargs=None, row_kwargs=None):
+    """The vocoder calls of a batch: vc (n, C, Smax) as `_strip_prompt` gives it, S the n host lengths.  A batch of one
+    length is one plain call on vc itself; one of several lengths is ONE `vocoder(vc, lens=S)` call with `ragged`, else one
+    plain call per `group_by_length` group, its rows gathered as slices (`_index_runs`: no index tensor, no host-to-device
+    copy).  A row without frames gets no call of its own.
+    seeds (n integers) reach a call as `seed_kw(its rows' seeds)` (default: `_vocoder_seeds`, i.e. only a HiFT is given
+    seeds); vocoder_kwargs describe all n rows and go to a call that covers them; row_kwargs ([dict of (1, ...) tensors] per
+    row, HiFT's pinned draws) are concatenated in the order of a call's rows.  With `hop` a call that does not give
+    frames x hop samples per row is a ValueError.
+    -> [_VocoderCall(runs = row ranges [(a, b)], frames, mel = the mel passed (rows, C, frames), wave (rows, samples))]."""
+    n, Smax = vc.size(0), vc.size(2)
+    everyone = list(range(n))
+    if len(set(S)) <= 1:
+        todo = [(S[0], everyone, {})] if S and S[0] > 0 else []
+    elif ragged:
+        todo = [(Smax, everyone, {"lens": S})]
+    else:
+        todo = [(frames, members, {}) for frames, members in group_by_length(S).items()]
+    calls = []
+    for frames, members, kw in todo:
+        runs = [(0, n)] if members is everyone else _index_runs(members)
+        whole = members is everyone and frames == Smax
+        if vocoder_kwargs:
+            if not whole:
+                raise ValueError(f"{what}: vocoder_kwargs describe the whole batch, a call per length needs them per row")
+            kw.update(vocoder_kwargs)
+        if row_kwargs:
+            kw.update({key: torch.cat([row_kwargs[i][key] for i in members]) for key in row_kwargs[members[0]]})
+        if seeds is not None:
+            part = seeds if whole else [seeds[i] for i in members]
+            kw.update(seed_kw(part) if seed_kw is not None else _vocoder_seeds(vocoder, part))
+        m = vc if whole else torch.cat([vc[a:b, :, :frames] for a, b in runs]).contiguous()
+        wave = vocoder(m, **kw).reshape(len(members), -1)
+        if hop is not None and wave.size(1) != frames * hop:
+            raise ValueError(f"{what}: the vocoder gave {wave.size(1)} samples per row, {frames * hop} expected (frames x hop)")
+        calls.append(_VocoderCall(runs, frames, m, wave))
+    return calls
+
+
+def _row_views(vc, S, calls):
+    """`_vocode`'s calls as one (mel (1, C, S_b), wave (1, S_b * hop)) pair of views per row; empty for a row without a call."""
+    rows = [(vc[b:b + 1, :, :0], vc.new_zeros(1, 0)) if s == 0 else None for b, s in enumerate(S)]
+    for call in calls:
+        hop = call.wave.size(1) // call.frames
+        for j, b in enumerate(b for run in call.runs for b in range(*run)):
+            rows[b] = (call.mel[j:j + 1, :, :S[b]], call.wave[j:j + 1, :S[b] * hop])
+    return rows
+
+
 class HotPath:
     """cfm: seedvc_amd.cfm.CFM ; vocoder: seedvc_amd.vocoder.BigVGAN | HiFT."""
 
@@ -136,9 +255,7 @@ class HotPath:
         self.vocoder = vocoder
 
     def _vocoder_seeds(self, seeds):
-        """{"seeds": seeds} for a vocoder that draws (HiFT), {} for one that does not (BigVGAN) or without seeds."""
-        from .vocoder import HiFT
-        return {"seeds": seeds} if seeds is not None and isinstance(self.vocoder, HiFT) else {}
+        return _vocoder_seeds(self.vocoder, seeds)
 
     @torch.inference_mode()
     def convert_batch(self, mu, prompt, style, n_timesteps, inference_cfg_rate, z=None, x_lens=None,
@@ -162,10 +279,9 @@ class HotPath:
         """B utterances of different lengths and prompts in one pass: mu (B, T, Dc), prompt (B, C, Pmax), style (B, Ds), x_lens /
         prompt_lens: B host integers each (prompt + output frames, prompt frames) -> list of B pairs (mel (1, C, S_b), wave
         (1, S_b * hop)), S_b = x_lens[b] - prompt_lens[b]: what `convert_batch` gives for each utterance alone.  The sampler with
-        per-row lengths -> `svc_mel_strip_prompt` (padding = the log-mel floor) -> ONE `vocoder(vc, lens=S)` call, BigVGAN or HiFT
-        (`svc_bigvgan_forward_ragged` / `svc_hift_forward_ragged`: no utterance sees its neighbour's padding); a batch of one
-        output length is one plain vocoder call.  vocoder_kwargs: HiFT's pinned f0 (B, Smax) / phase0 / noise (B, nh, Smax * up),
-        row b being the draws of utterance b alone in its leading part (`convert_batch_ragged_seeded`: seeds instead of
+        per-row lengths -> `_strip_prompt` -> `_vocode` with the ragged call, BigVGAN or HiFT (`svc_bigvgan_forward_ragged` /
+        `svc_hift_forward_ragged`: no utterance sees its neighbour's padding).  vocoder_kwargs: HiFT's pinned f0 (B, Smax) /
+        phase0 / noise (B, nh, Smax * up), row b being the draws of utterance b alone in its leading part (`convert_batch_ragged_seeded`: seeds instead of
         tensors).  Everything is enqueued from the host integers: no synchronisation."""
         return self._convert_batch_ragged(mu, prompt, style, x_lens, prompt_lens, n_timesteps, inference_cfg_rate, z, vocoder_kwargs, None)
 
@@ -183,33 +299,21 @@ class HotPath:
                                           seeds)
 
     def _convert_batch_ragged(self, mu, prompt, style, x_lens, prompt_lens, n_timesteps, inference_cfg_rate, z, vocoder_kwargs, seeds):
-        import ctypes as C
-        from . import _lib
         B, T = mu.size(0), mu.size(1)
         seeds = _seed_list("convert_batch_ragged_seeded", seeds, B, z, vocoder_kwargs)
-        x_lens = [int(v) for v in (x_lens.tolist() if torch.is_tensor(x_lens) else x_lens)]
-        P = [int(v) for v in (prompt_lens.tolist() if torch.is_tensor(prompt_lens) else prompt_lens)]
+        x_lens, P = _lib.int_list(x_lens), _lib.int_list(prompt_lens)
         if len(x_lens) != B or len(P) != B:
             raise ValueError(f"convert_batch_ragged: {len(x_lens)} x_lens and {len(P)} prompt_lens for a batch of {B}")
         S = [t - p for t, p in zip(x_lens, P)]
         if min(S) < 0 or max(x_lens) > T or max(P) > prompt.size(-1) or min(P) < 0:
             raise ValueError("convert_batch_ragged: need 0 <= prompt_lens[b] <= x_lens[b] <= T and prompt_lens[b] <= prompt frames")
-        dev = mu.device
-        i32 = lambda v: (C.c_int32 * len(v))(*v)                                                    # noqa: E731
-        with torch.cuda.device(dev):
+        with torch.cuda.device(mu.device):
             mel = self.cfm.inference(mu, x_lens, prompt, style, None, n_timesteps, inference_cfg_rate=inference_cfg_rate,
                                      z=z, prompt_lens=P, **_cfm_seeds(seeds))
-            mel = _lib.f32c(mel, dev)
-            Cm, Smax = mel.size(1), max(max(S), 1)
-            vc = torch.empty(B, Cm, Smax, device=dev)
-            _lib.check(_lib.lib().svc_mel_strip_prompt(_lib.ptr(mel), i32(P), i32(x_lens), B, Cm, T, Smax, C.c_float(LOG_MEL_FLOOR),
-                                                       _lib.ptr(vc), _lib.stream_ptr()))
-            kw = dict(vocoder_kwargs or {}, **self._vocoder_seeds(seeds))
-            if len(set(S)) > 1:
-                kw["lens"] = S
-            wave = self.vocoder(vc, **kw).reshape(B, -1)
-            hop = wave.size(1) // Smax
-        return [(vc[b:b + 1, :, :S[b]], wave[b:b + 1, :S[b] * hop]) for b in range(B)]
+            vc = _strip_prompt(mel, P, x_lens, max(max(S), 1))
+            calls = _vocode(self.vocoder, vc, S, True, "convert_batch_ragged", seeds=seeds, seed_kw=self._vocoder_seeds,
+                            vocoder_kwargs=vocoder_kwargs)
+        return _row_views(vc, S, calls)
 
     @torch.inference_mode()
     def convert_long(self, cond, prompt_condition, mel2, style2, n_timesteps, inference_cfg_rate, hop,
@@ -219,25 +323,18 @@ class HotPath:
         noise_fn(T) -> z (1,C,T) lets a caller pin the noise; vocoder_kwargs_fn(S) pins vocoder draws."""
         overlap_wave_len = overlap_frame_len * hop
         P = mel2.size(2)
-        max_source_window = max_context_window - P
-        processed = 0
         chunks, previous = [], None
-        while processed < cond.size(1):
-            chunk_cond = cond[:, processed:processed + max_source_window]
-            is_last = processed + max_source_window >= cond.size(1)
-            cat_condition = torch.cat([prompt_condition, chunk_cond], dim=1)
+        for p0, s_len, is_last in chunk_plan(cond.size(1), max_context_window - P, overlap_frame_len):
+            cat_condition = torch.cat([prompt_condition, cond[:, p0:p0 + s_len]], dim=1)
             T = cat_condition.size(1)
             z = noise_fn(T) if noise_fn is not None else None
             vc_target = self.cfm.inference(cat_condition, torch.LongTensor([T]), mel2, style2, None, n_timesteps,
                                            inference_cfg_rate=inference_cfg_rate, z=z)[:, :, P:]
             kw = vocoder_kwargs_fn(vc_target.size(2)) if vocoder_kwargs_fn is not None else {}
             vc_wave = self.vocoder(vc_target.float(), **kw).reshape(1, -1)
-            processed, previous, should_break = stream_wave_chunks(vc_wave, processed, vc_target.size(2), overlap_wave_len,
-                                                                   overlap_frame_len, chunks, previous, is_last)
-            if should_break:
-                break
+            _, previous, _ = stream_wave_chunks(vc_wave, p0, vc_target.size(2), overlap_wave_len, overlap_frame_len, chunks,
+                                                previous, is_last)
         return torch.tensor(np.concatenate(chunks))[None, :].float()
-
 
     @torch.inference_mode()
     def convert_long_device(self, cond, prompt_condition, mel2, style2, n_timesteps, inference_cfg_rate, hop,
@@ -246,26 +343,17 @@ class HotPath:
         crossfade done by `svc_crossfade` in the reference's float64 arithmetic (bit-identical), output assembled in one
         device buffer, and the vocoder of chunk k running on a second HIP stream beside the sampler of chunk k+1.
         One host synchronisation at the end instead of two `.cpu()` round trips per chunk."""
-        import ctypes as C
-        from . import _lib
         dev = cond.device
         ovw = overlap_frame_len * hop
         P = mel2.size(2)
-        msw = max_context_window - P
-        n_src = cond.size(1)
-        plan = chunk_plan(n_src, msw, overlap_frame_len)
-        sizes = []
-        for k, (_, s_len, is_last) in enumerate(plan):
-            full = s_len * hop
-            sizes.append(full if is_last else full - ovw)
-        out = torch.empty(sum(sizes), device=dev, dtype=torch.float32)
-        fade_out = torch.from_numpy(np.cos(np.linspace(0, np.pi / 2, ovw)) ** 2).to(dev)
-        fade_in = torch.from_numpy(np.cos(np.linspace(np.pi / 2, 0, ovw)) ** 2).to(dev)
+        plan = long_batch_plan([cond.size(1)], [P], max_context_window, overlap_frame_len, hop)     # one file: its chunks and samples
+        out = torch.empty(plan["out_lens"][0], device=dev, dtype=torch.float32)
+        fade_in, fade_out = (torch.from_numpy(w).to(dev) for w in _cos2_windows(ovw))
         s_main = torch.cuda.current_stream(dev)
         s_voc = Lanes._lane_stream(torch.device(dev), "vocoder")      # one per device for the process (see Lanes)
         s_voc.wait_stream(s_main)
         off, prev_tail, keep = 0, None, []
-        for k, (p0, s_len, is_last) in enumerate(plan):
+        for k, (_, p0, s_len, _, is_last) in enumerate(plan["chunks"]):
             cat_condition = torch.cat([prompt_condition, cond[:, p0:p0 + s_len]], dim=1)
             T = cat_condition.size(1)
             z = noise_fn(T) if noise_fn is not None else None
@@ -305,24 +393,21 @@ class HotPath:
         without source frames gives (1, 0).
 
         Per micro-batch (`long_batch_plan`, plan order = utterance-major): `svc_chunks_gather_cond` -> one `cfm.inference`
-        with per-row x_lens / prompt_lens -> `svc_mel_strip_prompt` (padding = the log-mel floor) -> the vocoder -> rows of
-        one wave buffer.  Seams are resolved once, after the last micro-batch, so a seam may cross micro-batches.
-        ragged_vocoder: None = one `vocoder(mel, lens=...)` call if the vocoder is a `BigVGAN`, else one plain call per
+        with per-row x_lens / prompt_lens -> `_strip_prompt` -> `_vocode` -> rows of one wave buffer.  Seams are resolved
+        once, after the last micro-batch, so a seam may cross micro-batches.
+        ragged_vocoder (`_vocode`'s `ragged`): None = the ragged call if the vocoder is a `BigVGAN`, else one plain call per
         distinct chunk length (a file has at most two: full windows and its last chunk); True / False force it, for either
-        vocoder (`HiFT` takes `lens=` too; a caller who wants its draws pinned in the ragged call wraps the vocoder; a
-        micro-batch of one length is one plain call either way).  vocoder_kwargs_fn(S) -> dict of tensors with a leading
-        batch axis of 1 (HiFT's pinned draws) is called once per chunk in plan order and concatenated per length group; it
-        cannot be combined with the ragged call.
+        vocoder (a caller who wants pinned draws in the ragged call wraps the vocoder).  vocoder_kwargs_fn(S) -> dict of
+        tensors with a leading batch axis of 1 (pinned draws) is called once per chunk in plan order and concatenated per
+        length group; it cannot be combined with the ragged call.
         noise_fn(T_k) -> (1, C, T_k) is called once per chunk in plan order with T_k = P_u + frames, the calls of the
         sequential loops.  With noise_fn=None the noise is one torch.randn per micro-batch: the same distribution, NOT the
         stream of draws the sequential loops consume.
         seeds: one integer in [0, 2^64) per file, exclusive with noise_fn and vocoder_kwargs_fn: chunk k of file u draws its
-        sampler noise and, if the vocoder is a HiFT, its source draws from `derive_seed(seeds[u], k)`, on the device and inside
-        the batched calls -- a file's audio is then a function of its own inputs and seed, whatever shares the pool.  The
-        ragged HiFT call is allowed with seeds (ragged_vocoder=True): there are no positional draws.
+        sampler noise and, if the vocoder draws (`_vocoder_seeds`), its source draws from `derive_seed(seeds[u], k)`, on the
+        device and inside the batched calls -- a file's audio is then a function of its own inputs and seed, whatever shares
+        the pool.  The ragged call of such a vocoder is allowed with seeds (ragged_vocoder=True): there are no positional draws.
         One host synchronisation, at the end."""
-        import ctypes as C
-        from . import _lib
         if seeds is not None and (noise_fn is not None or vocoder_kwargs_fn is not None):
             raise ValueError("convert_long_batch: give seeds or noise_fn / vocoder_kwargs_fn, not both")
         seeds = _seed_list("convert_long_batch", seeds, len(utterances))
@@ -344,7 +429,7 @@ class HotPath:
         chunks, out_lens = plan["chunks"], plan["out_lens"]
         dev = utterances[0][0].device
         ovw = overlap_frame_len * hop
-        i32 = lambda v: (C.c_int32 * len(v))(*v)                                                    # noqa: E731
+        i32 = _lib.i32_host
         with torch.cuda.device(dev):
             out = torch.empty(sum(out_lens), device=dev, dtype=torch.float32)
             offs = [sum(out_lens[:u]) for u in range(U)]
@@ -352,16 +437,12 @@ class HotPath:
             if not chunks:
                 return result
             N = len(chunks)
-            Pmax, Dc, Cm = max(P), utterances[0][0].size(2), utterances[0][2].size(1)
+            Dc, Cm = utterances[0][0].size(2), utterances[0][2].size(1)
             # the utterances' tensors, stacked once: condition rows along time, prompts padded to Pmax
             cond_all = torch.cat([_lib.f32c(t[0], dev)[0] for t in utterances])
             row_base = [sum(n_src[:u]) for u in range(U)]
-            pc_all = torch.zeros(U, Pmax, Dc, device=dev)
-            mel_all = torch.zeros(U, Cm, Pmax, device=dev)
-            for u, (_, pc, mel2, _) in enumerate(utterances):
-                pc_all[u, :P[u]] = pc[0]
-                mel_all[u, :, :P[u]] = mel2[0]
-            style_all = torch.cat([_lib.f32c(t[3], dev) for t in utterances])
+            st = _stack_prompts([t[1:] for t in utterances], dev)
+            pc_all, mel_all, style_all, Pmax = st["prompt_condition"], st["mel"], st["style"], st["Pmax"]
             utt = [c[0] for c in chunks]
             chunk_seeds = None
             if seeds is not None:       # chunk k of its file: the chunks are listed utterance-major
@@ -374,8 +455,7 @@ class HotPath:
                 mel_chunks, style_chunks = mel_all.index_select(0, idx), style_all.index_select(0, idx)
             else:
                 mel_chunks, style_chunks = mel_all.expand(N, -1, -1), style_all.expand(N, -1)
-            fade_out = torch.from_numpy(np.cos(np.linspace(0, np.pi / 2, ovw)) ** 2).to(dev)
-            fade_in = torch.from_numpy(np.cos(np.linspace(np.pi / 2, 0, ovw)) ** 2).to(dev)
+            fade_in, fade_out = (torch.from_numpy(w).to(dev) for w in _cos2_windows(ovw))
             stride = max(c[2] for c in chunks) * hop
             waves = torch.empty(N, stride, device=dev, dtype=torch.float32)      # row k: chunk k's waveform, lens[k] samples
             for k0, k1 in plan["micro_batches"]:
@@ -384,7 +464,7 @@ class HotPath:
                 S = [c[2] for c in mb]
                 Pk = [P[c[0]] for c in mb]
                 x_lens = [p + s for p, s in zip(Pk, S)]
-                T, Smax = max(x_lens), max(S)
+                T = max(x_lens)
                 mu = torch.empty(n, T, Dc, device=dev)
                 _lib.check(_lib.lib().svc_chunks_gather_cond(_lib.ptr(pc_all), i32(P), U, Pmax, _lib.ptr(cond_all), cond_all.size(0),
                                                              i32([c[0] for c in mb]), i32([row_base[c[0]] + c[1] for c in mb]),
@@ -398,41 +478,19 @@ class HotPath:
                 mb_seeds = chunk_seeds[k0:k1] if chunk_seeds is not None else None
                 mel = self.cfm.inference(mu, x_lens, mel_chunks[k0:k1], style_chunks[k0:k1], None, n_timesteps,
                                          inference_cfg_rate=inference_cfg_rate, z=z, prompt_lens=Pk, **_cfm_seeds(mb_seeds))
-                mel = _lib.f32c(mel, dev)
-                vc = torch.empty(n, Cm, Smax, device=dev)
-                _lib.check(_lib.lib().svc_mel_strip_prompt(_lib.ptr(mel), i32(Pk), i32(x_lens), n, Cm, T, Smax,
-                                                           C.c_float(LOG_MEL_FLOOR), _lib.ptr(vc), _lib.stream_ptr()))
-                groups = group_by_length(S)
-                if ragged_vocoder and len(groups) > 1:
-                    self._store_waves(waves, [(k0, k1)], self.vocoder(vc, lens=S, **self._vocoder_seeds(mb_seeds)), Smax * hop)
-                else:
-                    for s_len, members in groups.items():
-                        runs = _index_runs(members)
-                        m = vc if len(members) == n and s_len == Smax else \
-                            torch.cat([vc[a:b, :, :s_len] for a, b in runs]).contiguous()
-                        kw = {key: torch.cat([kws[i][key] for i in members]) for key in kws[members[0]]} if kws else {}
-                        if mb_seeds is not None:
-                            kw = self._vocoder_seeds([mb_seeds[i] for i in members])
-                        self._store_waves(waves, [(k0 + a, k0 + b) for a, b in runs], self.vocoder(m, **kw), s_len * hop)
+                vc = _strip_prompt(mel, Pk, x_lens, max(S))
+                for call in _vocode(self.vocoder, vc, S, ragged_vocoder, "convert_long_batch", hop=hop, seeds=mb_seeds,
+                                    seed_kw=self._vocoder_seeds, row_kwargs=kws):
+                    j = 0
+                    for a, b in call.runs:       # rows of a call -> rows of the chunk wave buffer (slices: no synchronisation)
+                        waves[k0 + a:k0 + b, :call.frames * hop].copy_(call.wave[j:j + b - a])
+                        j += b - a
             lens = [c[2] * hop for c in chunks]
             _lib.check(_lib.lib().svc_chunks_assemble(_lib.ptr(waves), C.c_longlong(stride), i32(lens), i32([int(c[3]) for c in chunks]),
                                                       i32([int(c[4]) for c in chunks]), N, _lib.ptr(fade_in), _lib.ptr(fade_out), ovw,
                                                       _lib.ptr(out), C.c_longlong(out.numel()), _lib.stream_ptr()))
             torch.cuda.current_stream(dev).synchronize()
         return result
-
-    @staticmethod
-    def _store_waves(waves, row_ranges, wave, n_samples):
-        """Rows of a vocoder call -> rows row_ranges of the chunk wave buffer (slices: no index tensor, no synchronisation)."""
-        n_rows = sum(b - a for a, b in row_ranges)
-        wave = wave.reshape(n_rows, -1)
-        if wave.size(1) != n_samples:
-            raise ValueError(f"convert_long_batch: the vocoder gave {wave.size(1)} samples per row, {n_samples} expected "
-                             f"(frames x hop)")
-        j = 0
-        for a, b in row_ranges:
-            waves[a:b, :n_samples].copy_(wave[j:j + b - a])
-            j += b - a
 
 
 # ----------------------------------------------------------------------------------------- v2: tokens in, audio out
@@ -450,20 +508,6 @@ def v2_ar_prompt(target_narrow, src_narrow):
     return torch.cat([target_narrow, src_narrow], dim=1)
 
 
-def group_by_length(lengths):
-    """{S: [indices b with lengths[b] == S]} for S > 0, in order of first appearance: the grouped vocoder path runs once
-    per group, because a plain vocoder call has no length argument and its convolutions would see another utterance's
-    padding (the ragged call, `BigVGAN.__call__(mel, lens=...)`, takes the lengths instead)."""
-    groups = {}
-    for b, s in enumerate(lengths):
-        if s > 0:
-            groups.setdefault(int(s), []).append(b)
-    return groups
-
-
-LOG_MEL_FLOOR = -11.512925464970229        # log(1e-5): the mel front-end's clamp (modules/audio.py:45-82)
-
-
 class V2HotPath:
     """The v2 chain as ONE call: narrow content tokens -> AR length regulator -> AR generate -> CFM length regulator ->
     cat([prompt_condition, cond]) -> CFM sampler (3-way CFG) -> strip the prompt frames -> BigVGAN
@@ -471,8 +515,8 @@ class V2HotPath:
 
     ar: seedvc_amd.ar.ARModel (setup_caches(max_batch_size=B) done by the caller); ar_lr / cfm_lr:
     seedvc_amd.length_regulator.InterpolateRegulator (v2_ar / v2_cfm); cfm: seedvc_amd.cfm.CFM (v2); vocoder: BigVGAN.
-    ragged_vocoder: a batch of more than one output length takes ONE vocoder call with per-utterance lengths (True) or one
-    call per distinct length (False); a batch of one length is one plain call either way."""
+    ragged_vocoder: `_vocode`'s `ragged` -- a batch of several output lengths is one ragged vocoder call (True) or one plain
+    call per length (False)."""
 
     def __init__(self, ar, ar_lr, cfm_lr, cfm, vocoder, ragged_vocoder=True, ar_prefill="slot"):
         self.ar, self.ar_lr, self.cfm_lr, self.cfm, self.vocoder = ar, ar_lr, cfm_lr, cfm, vocoder
@@ -492,7 +536,6 @@ class V2HotPath:
     def prepare_target(self, target_narrow, target_tokens, target_mel, style):
         """Per-voice work done once: prompt_condition = cfm_lr(target_tokens, ylens=[P]) (vc_wrapper.py, the reference
         computes it per call).  target_narrow (1, Nn), target_tokens (1, Np), target_mel (1, C, P), style (1, Ds)."""
-        from . import _lib
         dev = self.device
         P = int(target_mel.size(2))
         tok = target_tokens.to(dev).long()
@@ -507,14 +550,7 @@ class V2HotPath:
         key = tuple(id(t) for t in targets)
         if self._stacked[0] == key:
             return self._stacked[1]
-        dev, B = self.device, len(targets)
-        Pmax = max(t["P"] for t in targets)
-        pc = torch.zeros(B, Pmax, targets[0]["prompt_condition"].size(2), device=dev)
-        mel = torch.zeros(B, targets[0]["mel"].size(1), Pmax, device=dev)
-        for b, t in enumerate(targets):
-            pc[b, :t["P"]] = t["prompt_condition"][0]
-            mel[b, :, :t["P"]] = t["mel"][0]
-        st = dict(prompt_condition=pc, mel=mel, style=torch.cat([t["style"] for t in targets]), Pmax=Pmax, keep=list(targets))
+        st = dict(_stack_prompts([(t["prompt_condition"], t["mel"], t["style"]) for t in targets], self.device), keep=list(targets))
         self._stacked = (key, st)
         return st
 
@@ -529,8 +565,6 @@ class V2HotPath:
         noise_seeds[b] (`CFM.inference(seeds=)`; `seeds` keeps meaning the AR draws only).
         -> list of B dicts {tokens (1, n_b), mel (1, C, S_b), wave (1, S_b * hop)}.  One host synchronisation (the token
         counts); everything after it is enqueued from host integers."""
-        import ctypes as C
-        from . import _lib
         B, dev = len(src_narrow), self.device
         if not (B == len(targets) == len(frames_per_token)):
             raise ValueError("convert_batch: src_narrow, targets and frames_per_token must have one entry per utterance")
@@ -560,24 +594,18 @@ class V2HotPath:
                    for b in range(B)]
             if not live:
                 return out
-            sub = [targets[b] for b in live]
-            st = self._stack_targets(sub)
-            L = len(live)
-            P = [t["P"] for t in sub]
+            st = self._stack_targets([targets[b] for b in live])
+            L, P = len(live), st["P"]
             S = [ylens[b] for b in live]
             nl = [n[b] for b in live]
-            Pmax, Smax, T = st["Pmax"], max(S), max(p + s for p, s in zip(P, S))
+            x_lens = [p + s for p, s in zip(P, S)]
+            T = max(x_lens)
             # padded token rows hold zeros or an EOS: clamp so that every id is a row of the embedding
             idx = toks if L == B else toks[torch.tensor(live, device=dev)]
             tok = idx[:, :max(nl)].long().clamp_(max=self.cfm_lr.cfg["codebook_size"] - 1)
             cond = self.cfm_lr(tok, ylens=torch.LongTensor(S), in_lens=nl)[0]                     # (L, Smax, Dc), rows >= S_b zero
-            Dc = cond.size(2)
-            i32 = lambda v: (C.c_int32 * len(v))(*v)                                                # noqa: E731
-            mu = torch.empty(L, T, Dc, device=dev)
-            _lib.check(_lib.lib().svc_v2_assemble_cond(_lib.ptr(st["prompt_condition"]), i32(P), _lib.ptr(cond), i32(S), L, Pmax, Smax,
-                                                       Dc, T, _lib.ptr(mu), _lib.stream_ptr()))
+            mu = _assemble_cond(st["prompt_condition"], P, cond, S, T)
             self._mark("lr_assembly")
-            x_lens = [p + s for p, s in zip(P, S)]
             if z is not None:
                 zz = torch.zeros(L, Cm, T, device=dev)
                 for i, b in enumerate(live):
@@ -589,24 +617,10 @@ class V2HotPath:
                                      random_voice=random_voice, z=z, prompt_lens=P,
                                      **_cfm_seeds([noise_seeds[b] for b in live] if noise_seeds is not None else None))
             self._mark("cfm")
-            vc = torch.empty(L, Cm, Smax, device=dev)
-            _lib.check(_lib.lib().svc_mel_strip_prompt(_lib.ptr(mel), i32(P), i32(x_lens), L, Cm, T, Smax, C.c_float(LOG_MEL_FLOOR),
-                                                       _lib.ptr(vc), _lib.stream_ptr()))
-            groups = group_by_length(S)
-            if self.ragged_vocoder and len(groups) > 1:
-                # vc is already padded to Smax (floor-valued frames past S_b, which the ragged call never reads as values)
-                wave = self.vocoder(vc, lens=S).reshape(L, -1)
-                hop = wave.size(1) // Smax
-                for i in range(L):
-                    out[live[i]]["mel"] = vc[i:i + 1, :, :S[i]]
-                    out[live[i]]["wave"] = wave[i:i + 1, :S[i] * hop]
-            else:
-                for s_len, members in groups.items():
-                    m = vc if len(members) == L else vc[torch.tensor(members, device=dev)][:, :, :s_len].contiguous()
-                    wave = self.vocoder(m).reshape(len(members), -1)
-                    for j, i in enumerate(members):
-                        out[live[i]]["mel"] = m[j:j + 1]
-                        out[live[i]]["wave"] = wave[j:j + 1]
+            vc = _strip_prompt(mel, P, x_lens, max(S))
+            rows = _row_views(vc, S, _vocode(self.vocoder, vc, S, self.ragged_vocoder, "convert_batch"))
+            for b, (mel_b, wave_b) in zip(live, rows):
+                out[b]["mel"], out[b]["wave"] = mel_b, wave_b
             self._mark("strip_vocoder")
         return out
 
@@ -682,32 +696,27 @@ class RealtimeEngine:
         self.device = cfm.device
         if fade_in is None:
             fade_in, fade_out = gui_fade_windows(Lb)
-        from . import _lib
         self.fade_in, self.fade_out = (_lib.f32c(torch.as_tensor(f), self.device).reshape(-1) for f in (fade_in, fade_out))
         if self.fade_in.numel() != Lb or self.fade_out.numel() != Lb:
             raise ValueError(f"RealtimeEngine: the windows must have sola_buffer = {Lb} entries")
         self.state = torch.zeros(self.max_streams, Lb, device=self.device, dtype=torch.float32)      # row = a stream's sola_buffer
-        self._streams = {}                  # slot -> dict(prompt_condition, mel, style, P)
+        self._streams = {}                  # slot -> (prompt_condition, mel, style): a record of `_stack_prompts`
         self._stacked = (None, None)
 
     def open(self, prompt_condition, mel2, style2):
         """A new stream on the reference (prompt_condition (1, P, Dc), mel2 (1, C, P), style2 (1, Ds)) -> its slot, the
         lowest free one; its SOLA buffer starts from zeros."""
-        from . import _lib
         if prompt_condition.dim() != 3 or mel2.dim() != 3 or style2.dim() != 2 or prompt_condition.size(0) != 1 or \
                 mel2.size(0) != 1 or style2.size(0) != 1 or prompt_condition.size(1) != mel2.size(2):
             raise ValueError(f"RealtimeEngine.open: prompt_condition {tuple(prompt_condition.shape)}, mel2 {tuple(mel2.shape)} and "
                              f"style2 {tuple(style2.shape)} are not (1, P, Dc), (1, C, P), (1, Ds)")
-        for s in self._streams.values():
-            if s["prompt_condition"].size(2) != prompt_condition.size(2) or s["mel"].size(1) != mel2.size(1) or \
-                    s["style"].size(1) != style2.size(1):
+        for pc, mel, style in self._streams.values():
+            if pc.size(2) != prompt_condition.size(2) or mel.size(1) != mel2.size(1) or style.size(1) != style2.size(1):
                 raise ValueError("RealtimeEngine.open: Dc, C or Ds differ from the streams already open")
         slot = next((i for i in range(self.max_streams) if i not in self._streams), None)
         if slot is None:
             raise ValueError(f"RealtimeEngine.open: all {self.max_streams} slots are in use")
-        dev = self.device
-        self._streams[slot] = dict(prompt_condition=_lib.f32c(prompt_condition, dev), mel=_lib.f32c(mel2, dev),
-                                   style=_lib.f32c(style2, dev), P=int(mel2.size(2)))
+        self._streams[slot] = tuple(_lib.f32c(t, self.device) for t in (prompt_condition, mel2, style2))
         self._stacked = (None, None)
         self.state[slot].zero_()
         return slot
@@ -733,15 +742,7 @@ class RealtimeEngine:
         key = tuple(slots)
         if self._stacked[0] == key:
             return self._stacked[1]
-        dev, n = self.device, len(slots)
-        recs = [self._streams[s] for s in slots]
-        Pmax = max(r["P"] for r in recs)
-        pc = torch.zeros(n, Pmax, recs[0]["prompt_condition"].size(2), device=dev)
-        mel = torch.zeros(n, recs[0]["mel"].size(1), Pmax, device=dev)
-        for b, r in enumerate(recs):
-            pc[b, :r["P"]] = r["prompt_condition"][0]
-            mel[b, :, :r["P"]] = r["mel"][0]
-        st = dict(prompt_condition=pc, mel=mel, style=torch.cat([r["style"] for r in recs]), Pmax=Pmax, P=[r["P"] for r in recs])
+        st = _stack_prompts([self._streams[s] for s in slots], self.device)
         self._stacked = (key, st)
         return st
 
@@ -765,8 +766,6 @@ class RealtimeEngine:
         return self._step(slots, content, n_timesteps, inference_cfg_rate, None, vocoder_kwargs, return_parts, seeds)
 
     def _step(self, slots, content, n_timesteps, inference_cfg_rate, z, vocoder_kwargs, return_parts, seeds):
-        import ctypes as C
-        from . import _lib
         slots = [int(s) for s in slots]
         seeds = _seed_list("RealtimeEngine.step_seeded", seeds, len(slots), z, vocoder_kwargs)
         for s in slots:
@@ -781,40 +780,28 @@ class RealtimeEngine:
             parts = dict(mel=torch.zeros(0, self.cfm.in_channels, S, device=dev), infer=torch.zeros(0, self.n_inf, device=dev),
                          offsets=torch.zeros(0, dtype=torch.int32, device=dev))
             return (out, parts) if return_parts else out
-        i32 = lambda v: (C.c_int32 * len(v))(*v)                                                    # noqa: E731
         with torch.cuda.device(dev):
             st = self._stack_prompts(slots)
-            P, Pmax = st["P"], st["Pmax"]
+            P = st["P"]
             cond = self.length_regulator(content, ylens=torch.LongTensor([S] * n), n_quantizers=3, f0=None)[0]   # (n, S, Dc)
-            cond = _lib.f32c(cond, dev)
             if cond.size(1) != S:
                 raise ValueError(f"RealtimeEngine.step: the length regulator gave {cond.size(1)} frames, {S} expected")
-            Dc, Cm, T = cond.size(2), st["mel"].size(1), Pmax + S
-            mu = torch.empty(n, T, Dc, device=dev)
-            _lib.check(_lib.lib().svc_v2_assemble_cond(_lib.ptr(st["prompt_condition"]), i32(P), _lib.ptr(cond), i32([S] * n), n, Pmax, S,
-                                                       Dc, T, _lib.ptr(mu), _lib.stream_ptr()))
+            mu = _assemble_cond(st["prompt_condition"], P, cond, [S] * n, st["Pmax"] + S)
             x_lens = [p + S for p in P]
             mel = self.cfm.inference(mu, x_lens, st["mel"], st["style"], None, n_timesteps, inference_cfg_rate=inference_cfg_rate,
                                      z=z, prompt_lens=P, **_cfm_seeds(seeds))
-            mel = _lib.f32c(mel, dev)
-            vc = torch.empty(n, Cm, S, device=dev)
-            _lib.check(_lib.lib().svc_mel_strip_prompt(_lib.ptr(mel), i32(P), i32(x_lens), n, Cm, T, S, C.c_float(LOG_MEL_FLOOR),
-                                                       _lib.ptr(vc), _lib.stream_ptr()))
-            from .vocoder import HiFT
-            vkw = dict(vocoder_kwargs or {}, **({"seeds": seeds} if seeds is not None and isinstance(self.vocoder, HiFT) else {}))
-            wave = _lib.f32c(self.vocoder(vc, **vkw), dev).reshape(n, -1)
-            if wave.size(1) != S * self.hop:
-                raise ValueError(f"RealtimeEngine.step: the vocoder gave {wave.size(1)} samples per row, {S * self.hop} expected "
-                                 f"(frames x hop)")
+            vc = _strip_prompt(mel, P, x_lens, S)
+            calls = _vocode(self.vocoder, vc, [S] * n, False, "RealtimeEngine.step", hop=self.hop, seeds=seeds,
+                            vocoder_kwargs=vocoder_kwargs)                   # every row has S frames: one plain call
+            wave = _lib.f32c(calls[0].wave, dev)
             out = torch.empty(n, self.block, device=dev)
             offsets = torch.empty(n, dtype=torch.int32, device=dev) if return_parts else None
             _lib.check(_lib.lib().svc_sola_step(_lib.ptr(wave), wave.size(1), self.start, n, _lib.ptr(self.state), self.max_streams,
-                                                i32(slots), _lib.ptr(self.fade_in), _lib.ptr(self.fade_out), self.block, self.Lb,
-                                                self.Ls, _lib.ptr(out), _lib.ptr(offsets), _lib.stream_ptr()))
+                                                _lib.i32_host(slots), _lib.ptr(self.fade_in), _lib.ptr(self.fade_out), self.block,
+                                                self.Lb, self.Ls, _lib.ptr(out), _lib.ptr(offsets), _lib.stream_ptr()))
         if return_parts:
             return out, dict(mel=vc, infer=wave[:, self.start:self.start + self.n_inf], offsets=offsets)
         return out
-
 
 
 # ----------------------------------------------------------------------------------------- multi-GPU sharding

@@ -61,7 +61,7 @@ class BigVGAN:
         and frames at and above lens[b] may hold anything (svc_bigvgan_forward_ragged in include/seedvc_hip.h)."""
         B, _, S = mel.shape
         if lens is not None:
-            lens = [int(v) for v in (lens.tolist() if torch.is_tensor(lens) else lens)]
+            lens = _lib.int_list(lens)
             if len(lens) != B:
                 raise ValueError(f"BigVGAN: lens has {len(lens)} entries, the batch has {B} utterances")
         with torch.cuda.device(self.device):
@@ -70,7 +70,7 @@ class BigVGAN:
             if lens is None:
                 _lib.check(_lib.lib().svc_bigvgan_forward(self._h, _lib.ptr(mel), B, S, _lib.ptr(out), _lib.stream_ptr()))
             else:
-                _lib.check(_lib.lib().svc_bigvgan_forward_ragged(self._h, _lib.ptr(mel), (C.c_int32 * B)(*lens), B, S, _lib.ptr(out),
+                _lib.check(_lib.lib().svc_bigvgan_forward_ragged(self._h, _lib.ptr(mel), _lib.i32_host(lens), B, S, _lib.ptr(out),
                                                                  _lib.stream_ptr()))
         return out
 
@@ -140,39 +140,33 @@ class HiFT:
             raise ValueError("HiFT: give seeds or phase0 / noise, not both")
         seeds_keep = _lib.seeds_host(seeds, B, "HiFT") if seeds is not None else None
         if lens is not None:
-            lens = [int(v) for v in (lens.tolist() if torch.is_tensor(lens) else lens)]
+            lens = _lib.int_list(lens)
             if len(lens) != B:
                 raise ValueError(f"HiFT: lens has {len(lens)} entries, the batch has {B} utterances")
         nh = self.cfg["nb_harmonics"] + 1
         Lw = S * self.total_up
         dev = self.device
-        if seeds is not None:
-            with torch.cuda.device(dev):
-                mel = _lib.f32c(x, dev)
-                f0t = _lib.f32c(f0, dev) if f0 is not None else None
-                out = torch.empty(B, Lw, device=dev, dtype=torch.float32)
-                f0_out = torch.empty(B, S, device=dev, dtype=torch.float32) if return_f0 else None
-                _lib.check(_lib.lib().svc_hift_forward_seeded(self._h, _lib.ptr(mel), (C.c_int32 * B)(*lens) if lens is not None else None,
-                                                              _lib.ptr(f0t), seeds_keep, B, S, _lib.ptr(out), _lib.ptr(f0_out),
-                                                              _lib.stream_ptr()))
-            return (out, f0_out) if return_f0 else out
         with torch.cuda.device(dev):
             mel = _lib.f32c(x, dev)
-            if phase0 is None:     # Uniform(-pi, pi).sample((B, nh, 1)): generator.py:208-209
-                phase0 = (torch.rand(B, nh, 1, device=dev) * 2 - 1) * math.pi
-            if noise is None:      # torch.randn_like(sine_waves): generator.py:222
-                noise = torch.randn(B, nh, Lw, device=dev)
-            phase0, noise = _lib.f32c(phase0, dev), _lib.f32c(noise, dev)
+            if seeds is None:
+                if phase0 is None:     # Uniform(-pi, pi).sample((B, nh, 1)): generator.py:208-209
+                    phase0 = (torch.rand(B, nh, 1, device=dev) * 2 - 1) * math.pi
+                if noise is None:      # torch.randn_like(sine_waves): generator.py:222
+                    noise = torch.randn(B, nh, Lw, device=dev)
+                phase0, noise = _lib.f32c(phase0, dev), _lib.f32c(noise, dev)
             f0t = _lib.f32c(f0, dev) if f0 is not None else None
             out = torch.empty(B, Lw, device=dev, dtype=torch.float32)
             f0_out = torch.empty(B, S, device=dev, dtype=torch.float32) if return_f0 else None
-            if lens is None:
-                _lib.check(_lib.lib().svc_hift_forward(self._h, _lib.ptr(mel), _lib.ptr(f0t), _lib.ptr(phase0), _lib.ptr(noise),
-                                                       B, S, _lib.ptr(out), _lib.ptr(f0_out), _lib.stream_ptr()))
+            lens_keep = _lib.i32_host(lens) if lens is not None else None
+            args = (B, S, _lib.ptr(out), _lib.ptr(f0_out), _lib.stream_ptr())
+            if seeds is not None:
+                rc = _lib.lib().svc_hift_forward_seeded(self._h, _lib.ptr(mel), lens_keep, _lib.ptr(f0t), seeds_keep, *args)
+            elif lens is None:
+                rc = _lib.lib().svc_hift_forward(self._h, _lib.ptr(mel), _lib.ptr(f0t), _lib.ptr(phase0), _lib.ptr(noise), *args)
             else:
-                _lib.check(_lib.lib().svc_hift_forward_ragged(self._h, _lib.ptr(mel), (C.c_int32 * B)(*lens), _lib.ptr(f0t),
-                                                              _lib.ptr(phase0), _lib.ptr(noise), B, S, _lib.ptr(out),
-                                                              _lib.ptr(f0_out), _lib.stream_ptr()))
+                rc = _lib.lib().svc_hift_forward_ragged(self._h, _lib.ptr(mel), lens_keep, _lib.ptr(f0t), _lib.ptr(phase0),
+                                                        _lib.ptr(noise), *args)
+            _lib.check(rc)
         return (out, f0_out) if return_f0 else out
 
     forward = __call__

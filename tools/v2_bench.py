@@ -15,7 +15,6 @@ utterances' own token counts so that the lengths spread evenly over 120 ... `--f
 record gives the composite and its stages with `V2HotPath.ragged_vocoder` on (one vocoder call) and off (one call per
 distinct length), alternating run by run; the stages alone and the seeded / explicit comparison are not repeated."""
 import argparse
-import ctypes as C
 import json
 import os
 import sys
@@ -26,11 +25,11 @@ sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
 import _pkgload
 _pkgload.load_package()
 import torch
-from seedvc_amd import _lib, specs, weights
+from seedvc_amd import specs, weights
 from seedvc_amd.ar import ARModel
 from seedvc_amd.cfm import CFM
 from seedvc_amd.length_regulator import InterpolateRegulator
-from seedvc_amd.pipeline import LOG_MEL_FLOOR, V2HotPath
+from seedvc_amd.pipeline import V2HotPath, _assemble_cond, _strip_prompt
 from seedvc_amd.vocoder import BigVGAN
 
 ap = argparse.ArgumentParser()
@@ -177,26 +176,19 @@ for B in sizes:
     toks, n = ar.generate_batch_raw(texts, tgts, max_new=N_TOK, seeds=seeds)
     S = [int(FPT * k) for k in n]
     Smax, T = max(S), P + max(S)
-    i32 = lambda v: (C.c_int32 * len(v))(*v)      # noqa: E731
     pc = target["prompt_condition"].repeat(B, 1, 1)
     state = {}
 
     def lr_assembly():
         cond = cfm_lr(toks[:, :max(n)].long().clamp_(max=2047), ylens=torch.LongTensor(S), in_lens=n)[0]
-        mu = torch.empty(B, T, Dc, device=dev)
-        _lib.check(_lib.lib().svc_v2_assemble_cond(_lib.ptr(pc), i32([P] * B), _lib.ptr(cond), i32(S), B, P, Smax, Dc, T, _lib.ptr(mu),
-                                                   _lib.stream_ptr()))
-        state["mu"] = mu
+        state["mu"] = _assemble_cond(pc, [P] * B, cond, S, T)
 
     def sampler():
         state["mel"] = cfm.inference(state["mu"], [P + s for s in S], target["mel"].repeat(B, 1, 1), target["style"].repeat(B, 1), None,
                                      STEPS, inference_cfg_rate=[0.7, 0.7], prompt_lens=[P] * B)
 
     def strip_vocoder():
-        vc = torch.empty(B, Cm, Smax, device=dev)
-        _lib.check(_lib.lib().svc_mel_strip_prompt(_lib.ptr(state["mel"]), i32([P] * B), i32([P + s for s in S]), B, Cm, T, Smax,
-                                                   C.c_float(LOG_MEL_FLOOR), _lib.ptr(vc), _lib.stream_ptr()))
-        state["wave"] = voc(vc)
+        state["wave"] = voc(_strip_prompt(state["mel"], [P] * B, [P + s for s in S], Smax))
 
     alone["lr_assembly"] = stats(timed(lr_assembly))
     alone["cfm"] = stats(timed(sampler))
