@@ -385,6 +385,17 @@ void svc_mel_destroy(svc_mel_t* m);
 int svc_mel_frames(const svc_mel_t* m, int L);          /* frames for L samples: 1 + (L - hop) / hop */
 /* y [B][L] fp32 in [-1, 1] -> out [B][n_mels][frames] = log(clamp(mel @ sqrt(|STFT|^2 + 1e-9), 1e-5)). */
 int svc_mel_forward(svc_mel_t* m, const float* y, int B, int L, float* out, void* stream);
+/* The same for a batch of clips of different lengths, in one call (the contract of the ragged vocoder calls).
+ * y [B][L]; lens HOST int32 [B], consumed before the call returns (pinned staging inside the handle: no host synchronisation in
+ * steady state); out [B][n_mels][svc_mel_frames(L)].  out[b][:, :svc_mel_frames(lens[b])] is the log-mel of y[b][:lens[b]] run
+ * alone through svc_mel_forward (the reflect padding happens at the clip's own end, and a frame's row of the two GEMMs does not
+ * depend on its neighbours); every frame at and above that count is written as pad_value.  Samples at and above lens[b] are
+ * never read as values: they may hold anything, NaN included.  lens[b] == L for all b gives svc_mel_forward's result bit for bit.
+ * Legal lengths: (n_fft - hop) / 2 < lens[b] <= L and lens[b] >= hop (svc_mel_min_len <= lens[b] <= L).  lens == NULL, a length outside that range or B < 1:
+ * non-zero, a svc_last_error() that names lens, nothing enqueued; the checks that do not need n_fft and hop come before the
+ * handle is touched.  Workspace grows with B * L (the padded signal and three [B * frames] matrices). */
+int svc_mel_min_len(int n_fft, int hop);               /* the shortest legal lens[b]: max((n_fft - hop) / 2 + 1, hop); needs no handle */
+int svc_mel_forward_ragged(svc_mel_t* m, const float* y, const int32_t* lens, int B, int L, float pad_value, float* out, void* stream);
 
 /* ---------------------------------------------------------------- CAMPPlus style encoder + Kaldi fbank (second half) */
 typedef struct svc_campplus_config {  /* modules/campplus/DTDNN.py:54-62 (CAMPPlus.__init__ defaults; the drivers use embedding_size 192) */
@@ -405,6 +416,27 @@ int svc_campplus_forward(svc_campplus_t* m, const float* feat, int B, int T, flo
  * (inference.py:418-428): wave [n_samples] fp32 -> out [frames][feat_dim], frames = svc_kaldi_fbank_frames(n_samples). */
 int svc_kaldi_fbank_frames(int n_samples);
 int svc_kaldi_fbank(svc_campplus_t* m, const float* wave, int n_samples, float* out, void* stream);
+/* Both for a batch of reference clips of different lengths, in one call each (the contract of the ragged vocoder calls): lens is
+ * HOST int32 [B], consumed before the call returns (pinned staging inside the handle: no host synchronisation in steady state);
+ * values at and above a clip's end are never read as values (they may hold NaN); lens == NULL, a length out of range or B < 1:
+ * non-zero, a svc_last_error() that names lens, nothing enqueued, and the checks come before the handle is touched.
+ *
+ * svc_kaldi_fbank_ragged: wave [B][L] at 16 kHz, 400 <= lens[b] <= L samples; out [B][svc_kaldi_fbank_frames(L)][feat_dim].
+ * Clip b gets its own n_b = svc_kaldi_fbank_frames(lens[b]) frames, each what svc_kaldi_fbank gives for the clip alone; rows at
+ * and above n_b are written as zero.  subtract_mean != 0: the mean over the clip's own n_b frames is subtracted from them (the
+ * drivers' `feat - feat.mean(dim=0, keepdim=True)`, inference.py:429, in a kernel).
+ *
+ * svc_campplus_forward_ragged: feat [B][T][feat_dim], 8 <= lens[b] <= T frames (the lower bound is svc_campplus_forward's);
+ * out [B][embedding_size], out[b] = the embedding of feat[b][:lens[b]] run alone, whatever the other clips and their order:
+ * the FCM convs see zero time steps above the clip's end, the TDNN and the dilated CAM convs zero-pad at its own last row
+ * (T2_b = (lens[b] - 1) / 2 + 1 rows after the TDNN), the CAM context uses its own ceil(T2_b / seg_len) segments and its own
+ * global mean, and the statistics pool over T2_b rows (unbiased, T2_b - 1).  lens[b] == T for all b gives
+ * svc_campplus_forward's result bit for bit.
+ * Workspace grows with B * Tmax: the three FCM planes are B * (T + 2) * feat_dim * 32 * 4 bytes each (1.6 GB each for 64 clips
+ * of 25 s), the dense-block buffers B * T / 2 rows; a padded row costs what a live one does. */
+int svc_kaldi_fbank_ragged(svc_campplus_t* m, const float* wave, const int32_t* lens, int B, int L, int subtract_mean, float* out,
+                           void* stream);
+int svc_campplus_forward_ragged(svc_campplus_t* m, const float* feat, const int32_t* lens, int B, int T, float* out, void* stream);
 
 /* Device-side counterpart of `crossfade(chunk1, chunk2, overlap)` (inference.py:343-350): the first n samples of
  * chunk2 become chunk2 * fade_in + chunk1_tail * fade_out in float64, stored as float32 (bit-identical to the numpy

@@ -27,7 +27,8 @@ EXPORTS = [
     "svc_lr_create", "svc_lr_destroy", "svc_lr_forward", "svc_crossfade",
     "svc_chunks_gather_cond", "svc_chunks_assemble", "svc_sola_step",
     "svc_campplus_create", "svc_campplus_destroy", "svc_campplus_forward", "svc_kaldi_fbank_frames", "svc_kaldi_fbank",
-    "svc_mel_create", "svc_mel_destroy", "svc_mel_frames", "svc_mel_forward",
+    "svc_kaldi_fbank_ragged", "svc_campplus_forward_ragged",
+    "svc_mel_create", "svc_mel_destroy", "svc_mel_frames", "svc_mel_forward", "svc_mel_forward_ragged", "svc_mel_min_len",
     "svc_prof_enable", "svc_prof_collect",
     "svc_op_linear", "svc_op_conv1d", "svc_op_conv1d_ex", "svc_op_conv1d_last_took", "svc_op_conv_transpose1d", "svc_op_attention", "svc_op_rmsnorm",
 ]
@@ -128,6 +129,12 @@ def lib():
         l.svc_hift_forward_seeded.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_uint64),
                                               C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         l.svc_hift_noise_draws.argtypes = [C.c_uint64, C.c_int, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p]
+        # reference front-end, ragged: lengths as HOST int32 arrays
+        l.svc_mel_forward_ragged.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_float, C.c_void_p,
+                                             C.c_void_p]
+        l.svc_kaldi_fbank_ragged.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                             C.c_void_p]
+        l.svc_campplus_forward_ragged.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         _lib = l
     return _lib
 

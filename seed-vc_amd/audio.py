@@ -55,13 +55,23 @@ class MelSpectrogram:
                                                  _lib.stream_ptr(), C.byref(self._h)))
 
     @torch.inference_mode()
-    def __call__(self, y):
+    def __call__(self, y, lens=None, pad_value=0.0):
+        """y (B, L) -> (B, n_mels, frames).  lens (B host integers): a batch of clips of different lengths in one call
+        (`svc_mel_forward_ragged`): row b's first lens[b] // hop frames are the log-mel of y[b, :lens[b]] run alone (samples above
+        its end are never read); the frames above are pad_value."""
         with torch.cuda.device(self.device):
             yy = _lib.f32c(y, self.device)
             B, L = yy.shape
             frames = 1 + (L - self.hop) // self.hop
             out = torch.empty(B, self.n_mels, frames, device=self.device)
-            _lib.check(_lib.lib().svc_mel_forward(self._h, _lib.ptr(yy), B, L, _lib.ptr(out), _lib.stream_ptr()))
+            if lens is None:
+                _lib.check(_lib.lib().svc_mel_forward(self._h, _lib.ptr(yy), B, L, _lib.ptr(out), _lib.stream_ptr()))
+            else:
+                lens = _lib.int_list(lens)
+                if len(lens) != B:
+                    raise ValueError(f"MelSpectrogram: {len(lens)} lens for a batch of {B}")
+                _lib.check(_lib.lib().svc_mel_forward_ragged(self._h, _lib.ptr(yy), _lib.i32_host(lens), B, L, float(pad_value),
+                                                             _lib.ptr(out), _lib.stream_ptr()))
         return out
 
     def __del__(self):

@@ -33,15 +33,30 @@ class CAMPPlus:
         return self
 
     @torch.inference_mode()
-    def __call__(self, x, x_lens=None):
+    def __call__(self, x, x_lens=None, lens=None):
+        """x (B, T, feat_dim) -> (B, embedding_size).  lens (B host integers, 8 <= lens[b] <= T): a batch of clips of different
+        lengths in one call (`svc_campplus_forward_ragged`): row b is the embedding of x[b, :lens[b]] run alone; frames above a
+        clip's end are never read.  (x_lens is the reference's keyword for its masked pooling, which the drivers never use.)"""
         if x_lens is not None:
             raise NotImplementedError("masked statistics pooling (x_lens) is not on the inference path of the drivers")
         B, T, F = x.shape
         with torch.cuda.device(self.device):
             xx = _lib.f32c(x, self.device)
             out = torch.empty(B, self.cfg["embedding_size"], device=self.device)
-            _lib.check(_lib.lib().svc_campplus_forward(self._h, _lib.ptr(xx), B, T, _lib.ptr(out), _lib.stream_ptr()))
+            if lens is None:
+                _lib.check(_lib.lib().svc_campplus_forward(self._h, _lib.ptr(xx), B, T, _lib.ptr(out), _lib.stream_ptr()))
+            else:
+                lens = self._lens(lens, B)
+                _lib.check(_lib.lib().svc_campplus_forward_ragged(self._h, _lib.ptr(xx), _lib.i32_host(lens), B, T, _lib.ptr(out),
+                                                                  _lib.stream_ptr()))
         return out
+
+    @staticmethod
+    def _lens(lens, B):
+        lens = _lib.int_list(lens)
+        if len(lens) != B:
+            raise ValueError(f"CAMPPlus: {len(lens)} lens for a batch of {B}")
+        return lens
 
     forward = __call__
 
@@ -59,6 +74,28 @@ class CAMPPlus:
         feat = self.fbank(wave_16k)
         feat = feat - feat.mean(dim=0, keepdim=True)          # inference.py:429
         return self(feat.unsqueeze(0))
+
+    @torch.inference_mode()
+    def fbank_batch(self, waves, lens, subtract_mean=False):
+        """waves (B, L) at 16 kHz, lens B host integers (400 <= lens[b] <= L) -> (B, frames(L), feat_dim) in one call
+        (`svc_kaldi_fbank_ragged`): row b holds the 1 + (lens[b] - 400) // 160 frames of waves[b, :lens[b]], zero rows above
+        them; with subtract_mean each clip's own mean over time is subtracted from its frames (inference.py:429)."""
+        with torch.cuda.device(self.device):
+            w = _lib.f32c(waves, self.device)
+            B, L = w.shape
+            lens = self._lens(lens, B)
+            n = _lib.lib().svc_kaldi_fbank_frames(int(L))
+            out = torch.empty(B, n, self.cfg["feat_dim"], device=self.device)
+            _lib.check(_lib.lib().svc_kaldi_fbank_ragged(self._h, _lib.ptr(w), _lib.i32_host(lens), B, L, int(bool(subtract_mean)),
+                                                         _lib.ptr(out), _lib.stream_ptr()))
+        return out
+
+    def style_batch(self, waves_16k, lens):
+        """`style` for B reference clips of different lengths -> (B, embedding_size): fbank + mean normalisation, then the
+        embedding, in two library calls enqueued from the host lengths alone."""
+        lens = self._lens(lens, waves_16k.shape[0])
+        feat = self.fbank_batch(waves_16k, lens, subtract_mean=True)
+        return self(feat, lens=[1 + (n - 400) // 160 for n in lens])
 
     def close(self):
         if self._h:

@@ -4,7 +4,9 @@
 //
 // The STFT is ONE tap-GEMM on the fp32 MFMA: the padded signal is read as an [n_frames][n_fft] matrix whose rows
 // overlap in memory (row stride = hop), against the window-weighted DFT basis [2 (n_fft/2 + 1)][n_fft]; a second GEMM
-// applies the mel filterbank.  Runs once per source / reference clip.
+// applies the mel filterbank.  Runs once per source / reference clip, or once for a batch of clips of different lengths
+// (svc_mel_forward_ragged): the reflect padding ends at each clip's own last sample and the frames above its count are written
+// as the caller's pad value.
 #include <math.h>
 #include <string.h>
 
@@ -17,24 +19,27 @@ using namespace svc;
 
 namespace {
 
-// reflect padding without edge repeat (F.pad mode="reflect"): dst [B][stride], valid [0, L + 2 pad)
-__global__ void mel_pad_kernel(const float* __restrict__ y, int L, float* __restrict__ dst, long stride, int pad) {
+// reflect padding without edge repeat (F.pad mode="reflect"): y [B][Lrow], dst [B][stride], valid [0, L + 2 pad), zero above.
+// lens (device [B], or null): clip b has L = lens[b] <= Lrow samples of its own; nothing at and above them is read
+__global__ void mel_pad_kernel(const float* __restrict__ y, const int* __restrict__ lens, int Lrow, float* __restrict__ dst, long stride,
+                               int pad) {
     const int b = blockIdx.y;
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= stride) return;
+    const int L = lens ? lens[b] : Lrow;
     float v = 0.f;
     if (i < L + 2 * pad) {
         long q = i - pad;
         q = q < 0 ? -q : (q >= L ? 2L * (L - 1) - q : q);
-        v = y[(long)b * L + q];
+        v = y[(long)b * Lrow + q];
     }
     dst[(long)b * stride + i] = v;
 }
 
 // spec [M][ld_s] = (re[0..nb) | im[0..nb)) -> mag [M][ld_m] = sqrt(re^2 + im^2 + 1e-9), pad columns zero
 __global__ void mel_mag_kernel(const float* __restrict__ spec, long ld_s, float* __restrict__ mag, long ld_m, int nb, long M) {
-    const long m = blockIdx.y;
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    const long m = blockIdx.x;                              // rows on x: a batch has more than 65535 of them
+    const int k = blockIdx.y * blockDim.x + threadIdx.x;
     if (k >= ld_m) return;
     float v = 0.f;
     if (k < nb) {
@@ -44,11 +49,13 @@ __global__ void mel_mag_kernel(const float* __restrict__ spec, long ld_s, float*
     mag[m * ld_m + k] = v;
 }
 
-// out[b][mel][frame] = log(max(c[b * frames + frame][mel], 1e-5))
-__global__ void mel_log_kernel(const float* __restrict__ c, long ldc, float* __restrict__ out, int n_mels, int frames) {
+// out[b][mel][frame] = log(max(c[b * frames + frame][mel], 1e-5)); with lens, pad_value for frame >= lens[b] / hop (by selection)
+__global__ void mel_log_kernel(const float* __restrict__ c, long ldc, float* __restrict__ out, const int* __restrict__ lens, int hop,
+                               float pad_value, int n_mels, int frames) {
     const int b = blockIdx.z, f = blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y;
     if (f >= frames) return;
-    out[((long)b * n_mels + j) * frames + f] = logf(fmaxf(c[((long)b * frames + f) * ldc + j], 1e-5f));
+    const bool live = !lens || f < lens[b] / hop;
+    out[((long)b * n_mels + j) * frames + f] = live ? logf(fmaxf(c[((long)b * frames + f) * ldc + j], 1e-5f)) : pad_value;
 }
 
 }  // namespace
@@ -61,6 +68,12 @@ struct svc_mel {
     int cap_B = 0, cap_L = 0;
     float *padded = nullptr, *spec = nullptr, *mag = nullptr, *melc = nullptr;
     long stride = 0;
+    // ragged calls: pinned staging for the caller's lengths and their device copy
+    PinnedRing ring;
+    Arena lens_mem;
+    int cap_lens = 0;
+    int* d_lens = nullptr;
+    int forward(const float* y, const int32_t* lens, int B, int L, float pad_value, float* out, hipStream_t st);
 };
 
 extern "C" {
@@ -104,11 +117,49 @@ void svc_mel_destroy(svc_mel_t* m) { delete m; }
 
 int svc_mel_frames(const svc_mel_t* m, int L) { return m && L >= m->hop ? 1 + (L - m->hop) / m->hop : 0; }
 
+int svc_mel_min_len(int n_fft, int hop) { return std::max((n_fft - hop) / 2 + 1, hop); }
+
 int svc_mel_forward(svc_mel_t* m, const float* y, int B, int L, float* out, void* stream) {
     SVC_REQUIRE(m && y && out && B >= 1, "bad argument");
     const int pad = (m->n_fft - m->hop) / 2;
     SVC_REQUIRE(L > pad, "signal shorter than the reflect padding");
-    hipStream_t st = (hipStream_t)stream;
+    return m->forward(y, nullptr, B, L, 0.f, out, (hipStream_t)stream);
+}
+
+int svc_mel_forward_ragged(svc_mel_t* m, const float* y, const int32_t* lens, int B, int L, float pad_value, float* out, void* stream) {
+    // host checks first; every message names lens.  Only the last one needs the handle (its n_fft and hop)
+    SVC_REQUIRE(lens != nullptr, "svc_mel_forward_ragged: lens is NULL");
+    SVC_REQUIRE(m && y && out && B >= 1 && L >= 1, "svc_mel_forward_ragged: need B >= 1 clips, lens[b] in (pad, L]");
+    for (int b = 0; b < B; ++b) SVC_REQUIRE(lens[b] >= 1 && lens[b] <= L, "svc_mel_forward_ragged: lens outside [1, L]");
+    const int min_len = svc_mel_min_len(m->n_fft, m->hop);
+    for (int b = 0; b < B; ++b)
+        SVC_REQUIRE(lens[b] >= min_len, "svc_mel_forward_ragged: lens not above the reflect padding (n_fft - hop) / 2 or below one hop");
+    return m->forward(y, lens, B, L, pad_value, out, (hipStream_t)stream);
+}
+
+}  // extern "C"
+
+// lens: HOST [B] (checked by the caller) or null = every clip has L samples
+int svc_mel::forward(const float* y, const int32_t* lens, int B, int L, float pad_value, float* out, hipStream_t st) {
+    svc_mel* m = this;
+    const int pad = (m->n_fft - m->hop) / 2;
+    const int* dl = nullptr;
+    if (lens) {
+        if (B > cap_lens) {
+            SVC_CHECK_HIP(hipStreamSynchronize(st));
+            lens_mem.release();
+            cap_lens = 0;
+            d_lens = lens_mem.alloc_n<int>(B, st);
+            if (!d_lens) return 1;
+            cap_lens = B;
+        }
+        int* h = reinterpret_cast<int*>(ring.acquire((size_t)B * sizeof(int)));
+        if (!h) return 1;
+        for (int b = 0; b < B; ++b) h[b] = lens[b];
+        SVC_CHECK_HIP(hipMemcpyAsync(d_lens, h, (size_t)B * sizeof(int), hipMemcpyHostToDevice, st));
+        if (ring.commit(st)) return 1;
+        dl = d_lens;
+    }
     const int Lp = L + 2 * pad;
     const int frames = 1 + (Lp - m->n_fft) / m->hop;
     const int nbp = (int)m->ld_fb, ld_s = (int)round_up(2 * m->nb, 8), ld_c = (int)round_up(m->n_mels, 32);
@@ -125,7 +176,7 @@ int svc_mel_forward(svc_mel_t* m, const float* y, int B, int L, float* out, void
         m->melc = m->work.alloc_n<float>((size_t)m->cap_B * fr * ld_c, st);
         if (!m->padded || !m->spec || !m->mag || !m->melc) return 1;
     }
-    hipLaunchKernelGGL(mel_pad_kernel, dim3(cdiv(m->stride, 256), B), dim3(256), 0, st, y, L, m->padded, m->stride, pad);
+    hipLaunchKernelGGL(mel_pad_kernel, dim3(cdiv(m->stride, 256), B), dim3(256), 0, st, y, dl, L, m->padded, m->stride, pad);
     SVC_CHECK_HIP(hipGetLastError());
     // STFT: rows = frames (stride hop inside each padded sequence), K = n_fft
     KGemmParams p;
@@ -136,7 +187,7 @@ int svc_mel_forward(svc_mel_t* m, const float* y, int B, int L, float* out, void
     p.w = m->dft; p.ldw = m->ld_dft;
     p.c_seq_rows = frames; p.c32 = m->spec; p.ldc32 = ld_s; p.vec_ok = 1;      // pad columns (zero weight rows) land in the ld padding
     if (kgemm_launch(p, 1, KG_EPI_STORE, st)) return 1;
-    hipLaunchKernelGGL(mel_mag_kernel, dim3(cdiv(nbp, 128), B * frames), dim3(128), 0, st, m->spec, (long)ld_s, m->mag, (long)nbp,
+    hipLaunchKernelGGL(mel_mag_kernel, dim3(B * frames, cdiv(nbp, 128)), dim3(128), 0, st, m->spec, (long)ld_s, m->mag, (long)nbp,
                        m->nb, (long)B * frames);
     SVC_CHECK_HIP(hipGetLastError());
     memset(&p, 0, sizeof(p));
@@ -146,9 +197,8 @@ int svc_mel_forward(svc_mel_t* m, const float* y, int B, int L, float* out, void
     p.w = m->fb; p.ldw = m->ld_fb;
     p.c_seq_rows = frames; p.c32 = m->melc; p.ldc32 = ld_c; p.vec_ok = 1;
     if (kgemm_launch(p, 1, KG_EPI_STORE, st)) return 1;
-    hipLaunchKernelGGL(mel_log_kernel, dim3(cdiv(frames, 128), m->n_mels, B), dim3(128), 0, st, m->melc, (long)ld_c, out, m->n_mels, frames);
+    hipLaunchKernelGGL(mel_log_kernel, dim3(cdiv(frames, 128), m->n_mels, B), dim3(128), 0, st, m->melc, (long)ld_c, out, dl, m->hop, pad_value,
+                       m->n_mels, frames);
     SVC_CHECK_HIP(hipGetLastError());
     return 0;
 }
-
-}  // extern "C"

@@ -145,6 +145,25 @@ def _stack_prompts(records, device=None):
     return dict(prompt_condition=pc, mel=mel, style=torch.cat([_lib.f32c(s, device) for _, _, s in records]), P=P, Pmax=Pmax)
 
 
+@torch.inference_mode()
+def enrol_references(mel_fn, campplus, waves, lens, waves_16k, lens_16k):
+    """B reference clips of different lengths -> their prompt mels and style vectors, in three library calls instead of B x
+    (mel + fbank + CAMPPlus): mel_fn a `MelSpectrogram`, campplus a `CAMPPlus`; waves (B, L) at the mel rate with lens[b]
+    samples each, waves_16k (B, L16) at 16 kHz with lens_16k[b] samples each (the caller resamples, as for one clip).
+    -> dict(prompt (B, n_mels, Pmax) with zeros above each clip's frames, prompt_lens [P_b], style (B, E)): `prompt`,
+    `prompt_lens` and `style` of `HotPath.convert_batch_ragged`; prompt[b:b + 1, :, :P_b] and style[b:b + 1] are the
+    `target_mel` and `style` of `V2HotPath.prepare_target`.  Row b is what `mel_fn(waves[b:b + 1, :lens[b]])` and
+    `campplus.style(waves_16k[b, :lens_16k[b]])` give (`svc_mel_forward_ragged`, `svc_kaldi_fbank_ragged`,
+    `svc_campplus_forward_ragged`).  Everything is enqueued from the host integers: no synchronisation.  Pass waves with
+    L == max(lens): columns above the longest clip are cut off before the mel call, which costs a copy of the batch."""
+    lens, lens_16k = _lib.int_list(lens), _lib.int_list(lens_16k)
+    B = waves.size(0)
+    if len(lens) != B or len(lens_16k) != B or waves_16k.size(0) != B:
+        raise ValueError(f"enrol_references: {len(lens)} lens and {len(lens_16k)} lens_16k for {B} and {waves_16k.size(0)} clips")
+    prompt = mel_fn(waves[:, :max(lens)], lens=lens, pad_value=0.0)
+    return dict(prompt=prompt, prompt_lens=[n // mel_fn.hop for n in lens], style=campplus.style_batch(waves_16k, lens_16k))
+
+
 def _assemble_cond(prompt_condition, P, cond, S, T):
     """mu (n, T, Dc): row b is prompt_condition[b, :P[b]], then cond[b, :S[b]], then zeros (`svc_v2_assemble_cond`).
     prompt_condition (n, Pmax, Dc) and cond (n, >= max(S), Dc) on one device, P / S host integers."""
