@@ -438,6 +438,71 @@ int svc_kaldi_fbank_ragged(svc_campplus_t* m, const float* wave, const int32_t* 
                            void* stream);
 int svc_campplus_forward_ragged(svc_campplus_t* m, const float* feat, const int32_t* lens, int B, int T, float* out, void* stream);
 
+/* ---------------------------------------------------------------- RMVPE pitch extractor
+ * Replaces `rmvpe.infer_from_audio(wave_16k, thred=0.03)` of the drivers' f0-conditioned path and their pitch step (voiced-median
+ * shift + semitone shift).  Architecture of RVC's rmvpe.py, restated (the file is not on the build machine; parity with a real
+ * rmvpe.pt is unpinned): log-mel (16 kHz, n_fft = win = 1024, hop 160, Hann, center=True with reflect padding, sqrt(re^2 + im^2),
+ * caller's mel basis, log(max(., 1e-5))), the mel read as a one-channel (time, bin) image zero-padded in time to a multiple of
+ * 32 frames, BatchNorm, en_de_layers encoder levels of n_blocks ConvBlockRes + AvgPool(2, 2), inter_layers x n_blocks
+ * ConvBlockRes, decoder (stride-2 ConvTranspose2d + BatchNorm + ReLU, concatenation with the skip, n_blocks ConvBlockRes),
+ * Conv2d(., 3), bidirectional GRU(3 n_mels, gru_hidden), Linear(2 gru_hidden, n_bins) + sigmoid.  fp32 throughout.
+ * The state-dict keys are those of that module tree (unet.encoder.bn.*, unet.encoder.layers.L.conv.J.conv.{0,1,3,4}.*,
+ * ....shortcut.{weight,bias}, unet.intermediate.layers.*, unet.decoder.layers.D.conv1.{0,1}.* / .conv2.J.*, cnn.*,
+ * fc.0.gru.{weight,bias}_{ih,hh}_l0[_reverse], fc.1.*); num_batches_tracked is ignored.
+ *
+ * Ragged batches, as in the calls above: every lens / frame_lens array is HOST int32 [B], consumed before the call returns (kernel
+ * arguments: nothing is copied or synchronised), B <= 64; clip b is computed as if it ran alone, whatever the other clips, their
+ * order and the internal grouping are (bit for bit), and nothing at or above its end is read as a value (NaN is fine there).  The
+ * host checks come first, name the offending argument and touch no handle.  A call synchronises only to grow its workspace. */
+typedef struct svc_rmvpe_config {
+    int n_mels;            /* 128; a multiple of 8 and of 2^en_de_layers */
+    int en_de_layers;      /* 1 .. 5 (5); the time padding multiple is 32 whatever the depth */
+    int inter_layers;      /* >= 1 (4) */
+    int n_blocks;          /* >= 1 (4) */
+    int en_out_channels;   /* 16, or a multiple of 32 */
+    int gru_hidden;        /* 64 | 128 | 192 | 256 (256) */
+    int n_bins;            /* 360 */
+} svc_rmvpe_config_t;
+typedef struct svc_rmvpe svc_rmvpe_t;
+/* mel_basis: device fp32 [n_mels][513] (librosa.filters.mel(16000, 1024, n_mels, 30, 8000, htk=True) in the reference). */
+int svc_rmvpe_create(const svc_rmvpe_config_t* cfg, const svc_tensor_desc_t* weights, int n_weights, const float* mel_basis, void* stream,
+                     svc_rmvpe_t** out);
+void svc_rmvpe_destroy(svc_rmvpe_t* m);
+int svc_rmvpe_frames(int n_samples);                   /* frames of a clip: 1 + n_samples / 160 */
+int svc_rmvpe_min_len(void);                           /* the shortest legal clip: n_fft / 2 + 1 = 513 samples (reflect padding) */
+/* Workspace grows with B * Tpad: about 11 times one level-0 plane of B * (Tpad + 2) * n_mels * 32 * 4 bytes.  A call whose level-0
+ * plane would exceed the budget (default 256 MiB; 0 restores it) runs its clips in consecutive groups that fit (at least one clip
+ * per group); no row's bits depend on the grouping. */
+int svc_rmvpe_set_plane_budget(svc_rmvpe_t* m, long long bytes);
+/* Measurement aid (tools/rmvpe_bench.py): with timing on, every network pass records HIP events on its stream around its stages;
+ * svc_rmvpe_last_timing waits for the last pass (the last group of the last call) and fills ms4 = {U-Net, GRU input projection,
+ * GRU recurrence, output layer} in milliseconds. */
+int svc_rmvpe_set_timing(svc_rmvpe_t* m, int on);
+int svc_rmvpe_last_timing(svc_rmvpe_t* m, float* ms4);
+/* wave [B][L] at 16 kHz, svc_rmvpe_min_len() <= lens[b] <= L -> mel_out [B][n_mels][svc_rmvpe_frames(L)]; the frames at and above
+ * svc_rmvpe_frames(lens[b]) are 0. */
+int svc_rmvpe_mel(svc_rmvpe_t* m, const float* wave, const int32_t* lens, int B, int L, float* mel_out, void* stream);
+/* The network alone: mel [B][n_mels][T], 1 <= frame_lens[b] <= T -> out [B][T][n_bins] (salience in (0, 1)); rows at and above
+ * frame_lens[b] are 0. */
+int svc_rmvpe_salience(svc_rmvpe_t* m, const float* mel, const int32_t* frame_lens, int B, int T, float* out, void* stream);
+/* salience [B][T][360] -> f0_out [B][T] in Hz (needs no handle).  Per frame: arg-max bin (the first maximum on ties), the
+ * salience-weighted mean of cents[k] = 20 k + 1997.3794084376191 over the 9 bins around it (bins outside 0 .. 359 contribute zero),
+ * f0 = 10 * 2^(cents / 1200); a frame whose maximum is <= thred, and every frame at and above frame_lens[b], is exactly 0. */
+int svc_rmvpe_decode(const float* salience, const int32_t* frame_lens, int B, int T, float thred, float* f0_out, void* stream);
+/* The one call: wave [B][L] -> f0_out [B][svc_rmvpe_frames(L)].  lens may be NULL (every clip has L samples). */
+int svc_rmvpe_f0(svc_rmvpe_t* m, const float* wave, const int32_t* lens, int B, int L, float thred, float* f0_out, void* stream);
+/* The drivers' pitch step in one launch (inference.py, `if f0_condition:` block): f0_alt [B][Talt] (source), f0_ori [B][Tori]
+ * (reference), alt_lens / ori_lens HOST int32 [B] frames (0 .. Talt / Tori), semitones HOST float [B] or NULL (= 0), out [B][Talt].
+ * voiced = f0 > 1; m_x = torch's median (the lower middle element) of log(f0_x + 1e-5) over the voiced frames of row b, found by a
+ * 4-pass radix select on the bit pattern;
+ *   out = exp(log(f0_alt + 1e-5) - m_alt + m_ori) * 2^(semitones[b] / 12)     voiced frames, auto_adjust != 0
+ *   out = f0_alt' * 2^(semitones[b] / 12), f0_alt' = exp(log(f0_alt + 1e-5))   voiced frames, auto_adjust == 0
+ *   out = exp(log(f0_alt + 1e-5))  (1e-5 for an exact 0, not 0, as in the reference)   unvoiced frames;  0 at and above alt_lens[b].
+ * A row without a voiced frame on either side gets no median shift (the reference raises on the empty median).
+ * medians: optional device [B][2] = (m_alt, m_ori) of each row (0 where there is no voiced frame); NULL = not wanted. */
+int svc_f0_adjust(const float* f0_alt, const int32_t* alt_lens, const float* f0_ori, const int32_t* ori_lens, int B, int Talt, int Tori,
+                  int auto_adjust, const float* semitones, float* out, float* medians, void* stream);
+
 /* Device-side counterpart of `crossfade(chunk1, chunk2, overlap)` (inference.py:343-350): the first n samples of
  * chunk2 become chunk2 * fade_in + chunk1_tail * fade_out in float64, stored as float32 (bit-identical to the numpy
  * arithmetic).  fade_in / fade_out: the caller's cos^2 windows (double, device). */

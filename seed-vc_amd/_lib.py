@@ -29,6 +29,8 @@ EXPORTS = [
     "svc_campplus_create", "svc_campplus_destroy", "svc_campplus_forward", "svc_kaldi_fbank_frames", "svc_kaldi_fbank",
     "svc_kaldi_fbank_ragged", "svc_campplus_forward_ragged",
     "svc_mel_create", "svc_mel_destroy", "svc_mel_frames", "svc_mel_forward", "svc_mel_forward_ragged", "svc_mel_min_len",
+    "svc_rmvpe_create", "svc_rmvpe_destroy", "svc_rmvpe_frames", "svc_rmvpe_min_len", "svc_rmvpe_set_plane_budget", "svc_rmvpe_set_timing", "svc_rmvpe_last_timing", "svc_rmvpe_mel",
+    "svc_rmvpe_salience", "svc_rmvpe_decode", "svc_rmvpe_f0", "svc_f0_adjust",
     "svc_prof_enable", "svc_prof_collect",
     "svc_op_linear", "svc_op_conv1d", "svc_op_conv1d_ex", "svc_op_conv1d_last_took", "svc_op_conv_transpose1d", "svc_op_attention", "svc_op_rmsnorm",
 ]
@@ -89,6 +91,10 @@ class CampplusConfig(C.Structure):
                [("block_layers", C.c_int * 4), ("block_kernel", C.c_int * 4), ("block_dilation", C.c_int * 4), ("seg_len", C.c_int)]
 
 
+class RmvpeConfig(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("n_mels", "en_de_layers", "inter_layers", "n_blocks", "en_out_channels", "gru_hidden", "n_bins")]
+
+
 class LrConfig(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("channels", "in_channels", "out_channels", "is_discrete", "codebook_size", "n_convs",
                                        "interpolate", "has_final_conv", "f0_condition", "n_f0_bins")]
@@ -135,6 +141,18 @@ def lib():
         l.svc_kaldi_fbank_ragged.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_void_p,
                                              C.c_void_p]
         l.svc_campplus_forward_ragged.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        # RMVPE: lengths as HOST int32 arrays, semitones as a HOST float array
+        i32p = C.POINTER(C.c_int32)
+        l.svc_rmvpe_create.argtypes = [C.POINTER(RmvpeConfig), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+        l.svc_rmvpe_set_plane_budget.argtypes = [C.c_void_p, C.c_longlong]
+        l.svc_rmvpe_set_timing.argtypes = [C.c_void_p, C.c_int]
+        l.svc_rmvpe_last_timing.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        l.svc_rmvpe_mel.argtypes = [C.c_void_p, C.c_void_p, i32p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        l.svc_rmvpe_salience.argtypes = [C.c_void_p, C.c_void_p, i32p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        l.svc_rmvpe_decode.argtypes = [C.c_void_p, i32p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]
+        l.svc_rmvpe_f0.argtypes = [C.c_void_p, C.c_void_p, i32p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]
+        l.svc_f0_adjust.argtypes = [C.c_void_p, i32p, C.c_void_p, i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float),
+                                    C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = l
     return _lib
 

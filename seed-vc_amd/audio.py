@@ -39,6 +39,29 @@ def slaney_mel_basis(sr, n_fft, n_mels, fmin=0.0, fmax=None):
     return torch.from_numpy(w.astype(np.float32))
 
 
+def htk_mel_basis(sr, n_fft, n_mels, fmin=0.0, fmax=None):
+    """librosa.filters.mel(sr, n_fft, n_mels, fmin, fmax, htk=True) with its default Slaney area normalisation, float32
+    [n_mels][n_fft // 2 + 1]: triangles on the HTK scale mel = 2595 log10(1 + f / 700), each scaled by 2 / (its width in Hz).
+    RMVPE's basis (16 kHz, 1024, 128, 30, 8000).  Unpinned like `slaney_mel_basis`: librosa is absent from the build image."""
+    fmax = sr / 2.0 if fmax in (None, "None") else float(fmax)
+
+    def hz_to_mel(f):
+        return 2595.0 * np.log10(1.0 + np.asarray(f, dtype=np.float64) / 700.0)
+
+    def mel_to_hz(m):
+        return 700.0 * (10.0 ** (np.asarray(m, dtype=np.float64) / 2595.0) - 1.0)
+
+    fftfreqs = np.linspace(0, sr / 2.0, 1 + n_fft // 2)
+    mel_f = mel_to_hz(np.linspace(hz_to_mel(fmin), hz_to_mel(fmax), n_mels + 2))
+    fdiff = np.diff(mel_f)
+    ramps = mel_f[:, None] - fftfreqs[None, :]
+    w = np.zeros((n_mels, 1 + n_fft // 2))
+    for i in range(n_mels):
+        w[i] = np.maximum(0, np.minimum(-ramps[i] / fdiff[i], ramps[i + 2] / fdiff[i + 1]))
+    w *= (2.0 / (mel_f[2:n_mels + 2] - mel_f[:n_mels]))[:, None]
+    return torch.from_numpy(w.astype(np.float32))
+
+
 class MelSpectrogram:
     def __init__(self, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin=0, fmax=None, center=False, mel_basis=None,
                  device="cuda:0"):

@@ -164,6 +164,28 @@ def enrol_references(mel_fn, campplus, waves, lens, waves_16k, lens_16k):
     return dict(prompt=prompt, prompt_lens=[n // mel_fn.hop for n in lens], style=campplus.style_batch(waves_16k, lens_16k))
 
 
+@torch.inference_mode()
+def f0_conditions(rmvpe, src_16k, src_lens, ref_16k, ref_lens, auto_f0_adjust=True, pitch_shift=0):
+    """The drivers' F0 block for B (source, reference) pairs: `F0_ori = rmvpe.infer_from_audio(ref_16k)`,
+    `F0_alt = rmvpe.infer_from_audio(src_16k)`, the voiced-median shift in the log domain and the semitone shift, in two
+    `RMVPE.f0_batch` calls and one `svc_f0_adjust`.  src_16k (B, Ls) / ref_16k (B, Lr) at 16 kHz with src_lens[b] / ref_lens[b]
+    samples each (host integers); pitch_shift a number of semitones or one per row.
+    -> (F0_ori (B, To), ori_frames, shifted_f0_alt (B, Ta), alt_frames): the tracks and host frame counts that
+    `length_regulator(mel2, ylens=..., f0=F0_ori, f0_lens=ori_frames)` and `length_regulator(S_alt, ylens=..., f0=shifted_f0_alt,
+    f0_lens=alt_frames)` take.  Nothing is synchronised."""
+    from .rmvpe import f0_adjust
+    src_lens, ref_lens = _lib.int_list(src_lens), _lib.int_list(ref_lens)
+    B = src_16k.size(0)
+    if len(src_lens) != B or len(ref_lens) != B or ref_16k.size(0) != B:
+        raise ValueError(f"f0_conditions: {len(src_lens)} src_lens and {len(ref_lens)} ref_lens for {B} and {ref_16k.size(0)} clips")
+    f0_ori = rmvpe.f0_batch(ref_16k, ref_lens)
+    f0_alt = rmvpe.f0_batch(src_16k, src_lens)
+    ori_frames = [rmvpe.frames(n) for n in ref_lens]
+    alt_frames = [rmvpe.frames(n) for n in src_lens]
+    shifted = f0_adjust(f0_alt, alt_frames, f0_ori, ori_frames, auto_f0_adjust, pitch_shift)
+    return f0_ori, ori_frames, shifted, alt_frames
+
+
 def _assemble_cond(prompt_condition, P, cond, S, T):
     """mu (n, T, Dc): row b is prompt_condition[b, :P[b]], then cond[b, :S[b]], then zeros (`svc_v2_assemble_cond`).
     prompt_condition (n, Pmax, Dc) and cond (n, >= max(S), Dc) on one device, P / S host integers."""

@@ -1,0 +1,153 @@
+"""Host-side mirror of the RMVPE pitch extractor over the C ABI.
+
+`RMVPE(state_dict).infer_from_audio(audio_16k, thred=0.03)` has the call surface of the reference's
+`rmvpe.infer_from_audio(wave_16k, thred=0.03)`: one clip in, numpy F0 (Hz, 100 frames/s, 0 = unvoiced) out.
+`f0_batch` is the same for up to 64 clips of different lengths in one call, on the device, without a synchronisation;
+`mel`, `salience` and `decode` expose the three stages.  The state dict is the one of RVC's `E2E` module (`rmvpe.pt`).
+The default mel basis restates librosa's HTK filterbank (`audio.htk_mel_basis`, unpinned); pass the reference's own
+`mel_basis=` tensor (128, 513) when it is at hand.
+"""
+import ctypes as C
+
+import torch
+
+from . import _lib, specs
+from .audio import htk_mel_basis
+
+
+class RMVPE:
+    SR, HOP, N_FFT, FMIN, FMAX = 16000, 160, 1024, 30, 8000
+
+    def __init__(self, state_dict, mel_basis=None, device="cuda:0", cfg=None):
+        self.cfg = specs.rmvpe_config() if cfg is None else cfg
+        self.device = torch.device(device)
+        if mel_basis is None:
+            mel_basis = htk_mel_basis(self.SR, self.N_FFT, self.cfg["n_mels"], self.FMIN, self.FMAX)
+        c = _lib.RmvpeConfig()
+        for k in ("n_mels", "en_de_layers", "inter_layers", "n_blocks", "en_out_channels", "gru_hidden", "n_bins"):
+            setattr(c, k, int(self.cfg[k]))
+        self._h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            mb = _lib.f32c(mel_basis, self.device)
+            if tuple(mb.shape) != (self.cfg["n_mels"], self.N_FFT // 2 + 1):
+                raise ValueError(f"RMVPE: mel_basis must be ({self.cfg['n_mels']}, {self.N_FFT // 2 + 1}), got {tuple(mb.shape)}")
+            descs, n, keep = _lib.make_descs(state_dict, self.device)
+            _lib.check(_lib.lib().svc_rmvpe_create(C.byref(c), descs, n, _lib.ptr(mb), _lib.stream_ptr(), C.byref(self._h)))
+            torch.cuda.current_stream().synchronize()
+        del keep
+
+    def eval(self):
+        return self
+
+    @staticmethod
+    def frames(n_samples):
+        return 1 + int(n_samples) // RMVPE.HOP
+
+    @staticmethod
+    def _lens(lens, B, what):
+        lens = _lib.int_list(lens)
+        if len(lens) != B:
+            raise ValueError(f"RMVPE: {len(lens)} {what} for a batch of {B}")
+        return lens
+
+    def set_plane_budget(self, n_bytes):
+        """Bytes one level-0 plane of a group of clips may take (0 = the default, 256 MiB): larger batches run in groups."""
+        _lib.check(_lib.lib().svc_rmvpe_set_plane_budget(self._h, int(n_bytes)))
+
+    def set_timing(self, on):
+        """Measurement aid: record HIP events around the network's stages (see `last_timing`)."""
+        _lib.check(_lib.lib().svc_rmvpe_set_timing(self._h, int(bool(on))))
+
+    def last_timing(self):
+        """dict of milliseconds of the last network pass (synchronises): unet, gru_in, gru, head."""
+        ms = (C.c_float * 4)()
+        _lib.check(_lib.lib().svc_rmvpe_last_timing(self._h, ms))
+        return dict(zip(("unet", "gru_in", "gru", "head"), [float(v) for v in ms]))
+
+    @torch.inference_mode()
+    def mel(self, waves, lens):
+        """waves (B, L) at 16 kHz, lens B host integers -> (B, n_mels, frames(L)); zero above a clip's own frames."""
+        with torch.cuda.device(self.device):
+            w = _lib.f32c(waves, self.device)
+            B, L = w.shape
+            lens = self._lens(lens, B, "lens")
+            out = torch.empty(B, self.cfg["n_mels"], self.frames(L), device=self.device)
+            _lib.check(_lib.lib().svc_rmvpe_mel(self._h, _lib.ptr(w), _lib.i32_host(lens), B, L, _lib.ptr(out), _lib.stream_ptr()))
+        return out
+
+    @torch.inference_mode()
+    def salience(self, mel, frame_lens=None):
+        """mel (B, n_mels, T) -> (B, T, n_bins): the network alone.  frame_lens: B host integers (default: all T)."""
+        with torch.cuda.device(self.device):
+            m = _lib.f32c(mel, self.device)
+            B, _, T = m.shape
+            fl = [T] * B if frame_lens is None else self._lens(frame_lens, B, "frame_lens")
+            out = torch.empty(B, T, self.cfg["n_bins"], device=self.device)
+            _lib.check(_lib.lib().svc_rmvpe_salience(self._h, _lib.ptr(m), _lib.i32_host(fl), B, T, _lib.ptr(out), _lib.stream_ptr()))
+        return out
+
+    @torch.inference_mode()
+    def decode(self, salience, frame_lens=None, thred=0.03):
+        """salience (B, T, 360) -> F0 (B, T) in Hz, 0 on unvoiced frames and above a clip's frames."""
+        with torch.cuda.device(self.device):
+            s = _lib.f32c(salience, self.device)
+            B, T, n = s.shape
+            if n != 360:
+                raise ValueError("RMVPE.decode: the cents mapping is defined for 360 bins")
+            fl = [T] * B if frame_lens is None else self._lens(frame_lens, B, "frame_lens")
+            out = torch.empty(B, T, device=self.device)
+            _lib.check(_lib.lib().svc_rmvpe_decode(_lib.ptr(s), _lib.i32_host(fl), B, T, float(thred), _lib.ptr(out), _lib.stream_ptr()))
+        return out
+
+    @torch.inference_mode()
+    def f0_batch(self, waves, lens=None, thred=0.03):
+        """waves (B, L) at 16 kHz (B <= 64), lens B host integers or None -> device F0 (B, frames(L)); row b holds the
+        frames(lens[b]) values of waves[b, :lens[b]] run alone, zeros above.  Nothing is synchronised."""
+        with torch.cuda.device(self.device):
+            w = _lib.f32c(waves, self.device)
+            B, L = w.shape
+            hl = None if lens is None else _lib.i32_host(self._lens(lens, B, "lens"))
+            out = torch.empty(B, self.frames(L), device=self.device)
+            _lib.check(_lib.lib().svc_rmvpe_f0(self._h, _lib.ptr(w), hl, B, L, float(thred), _lib.ptr(out), _lib.stream_ptr()))
+        return out
+
+    def infer_from_audio(self, audio, thred=0.03):
+        """audio: 1-D numpy array or tensor at 16 kHz -> numpy F0 (frames,), as the reference returns it."""
+        a = torch.as_tensor(audio, dtype=torch.float32).reshape(1, -1)
+        return self.f0_batch(a, None, thred)[0].cpu().numpy()
+
+    def close(self):
+        if self._h:
+            _lib.lib().svc_rmvpe_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+@torch.inference_mode()
+def f0_adjust(f0_alt, alt_lens, f0_ori, ori_lens, auto_f0_adjust=True, pitch_shift=0, return_medians=False):
+    """The drivers' pitch step (`svc_f0_adjust`): f0_alt (B, Talt) source track, f0_ori (B, Tori) reference track, host frame
+    counts per row; pitch_shift a number of semitones or one per row -> shifted f0_alt (B, Talt)."""
+    dev = f0_alt.device
+    with torch.cuda.device(dev):
+        a, o = _lib.f32c(f0_alt), _lib.f32c(f0_ori, dev)
+        B, Talt = a.shape
+        Tori = o.shape[1]
+        al, ol = _lib.int_list(alt_lens), _lib.int_list(ori_lens)
+        if len(al) != B or len(ol) != B or o.shape[0] != B:
+            raise ValueError(f"f0_adjust: lengths and tracks must all have {B} rows")
+        if torch.is_tensor(pitch_shift):
+            pitch_shift = pitch_shift.tolist()
+        semis = [float(x) for x in pitch_shift] if isinstance(pitch_shift, (list, tuple)) else [float(pitch_shift)] * B
+        if len(semis) != B:
+            raise ValueError(f"f0_adjust: {len(semis)} pitch shifts for {B} rows")
+        out = torch.empty(B, Talt, device=dev)
+        med = torch.empty(B, 2, device=dev) if return_medians else None
+        _lib.check(_lib.lib().svc_f0_adjust(_lib.ptr(a), _lib.i32_host(al), _lib.ptr(o), _lib.i32_host(ol), B, Talt, Tori,
+                                            int(bool(auto_f0_adjust)), (C.c_float * B)(*semis), _lib.ptr(out), _lib.ptr(med),
+                                            _lib.stream_ptr()))
+    return (out, med) if return_medians else out

@@ -526,3 +526,61 @@ def campplus_state_spec(c):
     s["dense.linear.weight"] = (c["embedding_size"], 2 * ch, 1)
     _bn_spec(s, "dense.nonlinear.batchnorm", c["embedding_size"], affine=False)
     return s
+
+
+# --------------------------------------------------------------------------------------------- RMVPE pitch extractor
+# RVC's rmvpe.py as the reference vendors it: E2E(n_blocks=4, n_gru=1, kernel_size=(2, 2)) with its defaults
+RMVPE_PRESET = dict(n_mels=128, en_de_layers=5, inter_layers=4, n_blocks=4, en_out_channels=16, gru_hidden=256, n_bins=360)
+
+
+def rmvpe_config(**overrides):
+    cfg = deepcopy(RMVPE_PRESET)
+    cfg.update(overrides)
+    assert 1 <= cfg["en_de_layers"] <= 5 and cfg["n_mels"] % max(8, 1 << cfg["en_de_layers"]) == 0
+    assert cfg["en_out_channels"] == 16 or cfg["en_out_channels"] % 32 == 0
+    return cfg
+
+
+def _rmvpe_block_spec(s, p, cin, cout):
+    """ConvBlockRes(cin, cout): conv.0 / conv.3 bias-free 3 x 3 convs, conv.1 / conv.4 BatchNorms, 1 x 1 shortcut with bias."""
+    s[p + ".conv.0.weight"] = (cout, cin, 3, 3)
+    _bn_spec(s, p + ".conv.1", cout)
+    s[p + ".conv.3.weight"] = (cout, cout, 3, 3)
+    _bn_spec(s, p + ".conv.4", cout)
+    if cin != cout:
+        s[p + ".shortcut.weight"] = (cout, cin, 1, 1)
+        s[p + ".shortcut.bias"] = (cout,)
+
+
+def rmvpe_state_spec(c):
+    """State dict of RMVPE's `E2E` module tree, in torch's registration order (741 tensors, 90.42 M parameters at full size)."""
+    s = OrderedDict()
+    L, nb = c["en_de_layers"], c["n_blocks"]
+    _bn_spec(s, "unet.encoder.bn", 1)
+    cin, cout = 1, c["en_out_channels"]
+    for l in range(L):
+        for j in range(nb):
+            _rmvpe_block_spec(s, f"unet.encoder.layers.{l}.conv.{j}", cin if j == 0 else cout, cout)
+        cin, cout = cout, cout * 2
+    for i in range(c["inter_layers"]):
+        for j in range(nb):
+            _rmvpe_block_spec(s, f"unet.intermediate.layers.{i}.conv.{j}", cin if (i == 0 and j == 0) else cout, cout)
+    cin = cout
+    for d in range(L):
+        cout = cin // 2
+        s[f"unet.decoder.layers.{d}.conv1.0.weight"] = (cin, cout, 3, 3)
+        _bn_spec(s, f"unet.decoder.layers.{d}.conv1.1", cout)
+        for j in range(nb):
+            _rmvpe_block_spec(s, f"unet.decoder.layers.{d}.conv2.{j}", 2 * cout if j == 0 else cout, cout)
+        cin = cout
+    s["cnn.weight"] = (3, c["en_out_channels"], 3, 3)
+    s["cnn.bias"] = (3,)
+    H = c["gru_hidden"]
+    for sfx in ("", "_reverse"):
+        s["fc.0.gru.weight_ih_l0" + sfx] = (3 * H, 3 * c["n_mels"])
+        s["fc.0.gru.weight_hh_l0" + sfx] = (3 * H, H)
+        s["fc.0.gru.bias_ih_l0" + sfx] = (3 * H,)
+        s["fc.0.gru.bias_hh_l0" + sfx] = (3 * H,)
+    s["fc.1.weight"] = (c["n_bins"], 2 * H)
+    s["fc.1.bias"] = (c["n_bins"],)
+    return s
