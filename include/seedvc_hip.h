@@ -503,6 +503,52 @@ int svc_rmvpe_f0(svc_rmvpe_t* m, const float* wave, const int32_t* lens, int B, 
 int svc_f0_adjust(const float* f0_alt, const int32_t* alt_lens, const float* f0_ori, const int32_t* ori_lens, int B, int Talt, int Tori,
                   int auto_adjust, const float* semitones, float* out, float* medians, void* stream);
 
+/* ---------------------------------------------------------------- Whisper content encoder (csrc/whisper.hip)
+ * Replaces `semantic_fn(waves_16k)` of the drivers (WhisperFeatureExtractor + the encoder half of openai/whisper-small, one 30 s
+ * window at a time) and their loop over the windows of a long clip.  P = max_source_positions rows per window, W = 320 P samples.
+ * Log-mel: the window zero-padded to W, n_fft = win = 400, hop 160, periodic Hann, center=True with the reflect padding applied to
+ * the PADDED window, re^2 + im^2, the last of the 2 P + 1 frames dropped, mel_basis [n_mels][201] (device, copied),
+ * log10(max(., 1e-10)), max(x, m - 8) with m the maximum over the whole window, (x + 4) / 4.  Encoder: conv1 (k 3, pad 1) + GELU,
+ * conv2 (k 3, stride 2, pad 1) + GELU, + embed_positions.weight, n_layers pre-LN blocks (LayerNorm eps 1e-5; q (bias) / 8, k (no
+ * bias), v (bias); unmasked softmax attention over all P keys, heads of 64; out_proj + residual; LayerNorm; fc1 + erf-GELU; fc2 +
+ * residual), final layer_norm.  Residual stream, LayerNorm statistics and softmax are fp32; attention operands are fp16.
+ * precision 1: convs and linears with fp16 operands and fp32 accumulation; 0: on the fp32 tap-GEMM.
+ * weights: WhisperEncoder.state_dict() (device fp32); the prefixes "encoder." and "model.encoder." are accepted, other keys are
+ * ignored; a missing or mis-shaped key is named in the error.  d_model a multiple of 64 with n_heads * 64 == d_model, n_mels a
+ * multiple of 8, ffn_dim a multiple of 64.  Lengths are HOST int32 arrays consumed before the call returns; arguments are checked
+ * before the handle is touched; nothing synchronises in steady state (the workspace grows on the first call of a size).  Samples at
+ * and above a clip's length are never read as values.  A window's rows are bit-identical whatever else shares the call, in any
+ * order and with any group size. */
+typedef struct svc_whisper_config {
+    int n_mels, d_model, n_heads, n_layers, ffn_dim, max_source_positions, precision;
+} svc_whisper_config_t;
+typedef struct svc_whisper svc_whisper_t;
+
+int svc_whisper_create(const svc_whisper_config_t* cfg, const svc_tensor_desc_t* weights, int n_weights, const float* mel_basis, void* stream,
+                       svc_whisper_t** out);
+void svc_whisper_destroy(svc_whisper_t* m);
+/* The drivers' window plan of a clip of n_samples >= 1 samples, 0 <= overlap_rows < P (no handle; -1 on a bad argument): window j
+ * starts at j (W - O), O = 320 overlap_rows, and has min(W, n_samples - start) samples; window 0 always exists, window j >= 1 exists
+ * iff W + (j - 1)(W - O) < n_samples.  A window of n samples yields rows [0, min(P, n / 320 + 1)); every window but the first drops
+ * its first overlap_rows.  svc_whisper_rows = the kept rows of the clip. */
+int svc_whisper_n_windows(int P, int overlap_rows, long n_samples);
+int svc_whisper_rows(int P, int overlap_rows, long n_samples);
+/* Windows computed side by side (1 .. 64, 0 = the default of 16): bounds the workspace; results do not depend on it. */
+int svc_whisper_set_window_group(svc_whisper_t* m, int windows);
+/* Measurement aid (tools/whisper_bench.py): with timing on, svc_whisper_content records HIP events around its stages;
+ * svc_whisper_last_timing waits for the last group of the last call and fills ms4 = {log-mel, stem, layers, assemble} in ms. */
+int svc_whisper_set_timing(svc_whisper_t* m, int on);
+int svc_whisper_last_timing(svc_whisper_t* m, float* ms4);
+/* wave [B][L] at 16 kHz, 1 <= lens[b] <= min(L, W), B <= 64 -> feat [B][n_mels][2 P] (one window per clip). */
+int svc_whisper_mel(svc_whisper_t* m, const float* wave, const int32_t* lens, int B, int L, float* feat, void* stream);
+/* feat [B][n_mels][2 P] -> out [B][P][d_model]. */
+int svc_whisper_encode(svc_whisper_t* m, const float* feat, int B, float* out, void* stream);
+/* The one call: wave [B][L], lens HOST [B] in 1 .. L or NULL (= L), B <= 64 clips of any length -> out [B][Rmax][d_model]: rows
+ * [0, svc_whisper_rows(P, overlap_rows, lens[b])) of out[b] are the kept rows of the clip's windows in order, the rows above are
+ * zero.  Rmax >= the largest row count.  All windows of all clips run through the log-mel and the encoder together, in groups. */
+int svc_whisper_content(svc_whisper_t* m, const float* wave, const int32_t* lens, int B, int L, int overlap_rows, float* out, int Rmax,
+                        void* stream);
+
 /* Device-side counterpart of `crossfade(chunk1, chunk2, overlap)` (inference.py:343-350): the first n samples of
  * chunk2 become chunk2 * fade_in + chunk1_tail * fade_out in float64, stored as float32 (bit-identical to the numpy
  * arithmetic).  fade_in / fade_out: the caller's cos^2 windows (double, device). */
@@ -561,7 +607,8 @@ int svc_sola_step(const float* wave, long long stride, int start, int N, float* 
                   void* stream);
 
 /* ---------------------------------------------------------------- op-level entry points (parity tests) */
-/* C[M][N] (fp32) = A[M][K] * W[N][K]^T + bias ; dtype 0: operands rounded to fp16, 1: fp32 MFMA. */
+/* C[M][N] (fp32) = act(A[M][K] * W[N][K]^T + bias) ; dtype 0: operands rounded to fp16, 1: fp32 MFMA.  act: a KG_ACT_* value
+ * (0 none, 1 SiLU, 2 ELU, 3 leaky ReLU 0.1, 4 tanh, 5 abs, 6 clamp, 7 sigmoid, 8 GELU in the exact erf form). */
 int svc_op_linear(const float* a, const float* w, const float* bias, float* c, int M, int N, int K, int dtype,
                   int act, void* stream);
 /* Channels-last Conv1d through the tap-GEMM: x [B][L][Cin], w [Cout][Cin][k] (torch layout),
@@ -608,6 +655,8 @@ int svc_op_attention(const float* q, const float* k, const float* v, float* out,
 /* y = rmsnorm(x) * gamma * (add_one + w) + b ; x [rows][D]. */
 int svc_op_rmsnorm(const float* x, const float* gamma, const float* w, const float* b, int add_one, float* y,
                    int rows, int D, void* stream);
+/* y = LayerNorm(x) * gamma + beta ; x, y [rows][D], D a multiple of 64 (at most 2048); mean, then the variance about it, in fp32. */
+int svc_op_layernorm(const float* x, const float* gamma, const float* beta, float* y, int rows, int D, float eps, void* stream);
 
 /* Tuning / measurement aid (tools/gemm_bench.py, tools/gemm_small_bench.py; no model uses it): times `iters` launches of the
  * tap-GEMM on synthetic operands of shape M x N x K; dtype 0 fp16 / 1 fp32, epi = epilogue kind, debug = tile-form override

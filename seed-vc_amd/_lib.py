@@ -31,8 +31,11 @@ EXPORTS = [
     "svc_mel_create", "svc_mel_destroy", "svc_mel_frames", "svc_mel_forward", "svc_mel_forward_ragged", "svc_mel_min_len",
     "svc_rmvpe_create", "svc_rmvpe_destroy", "svc_rmvpe_frames", "svc_rmvpe_min_len", "svc_rmvpe_set_plane_budget", "svc_rmvpe_set_timing", "svc_rmvpe_last_timing", "svc_rmvpe_mel",
     "svc_rmvpe_salience", "svc_rmvpe_decode", "svc_rmvpe_f0", "svc_f0_adjust",
+    "svc_whisper_create", "svc_whisper_destroy", "svc_whisper_n_windows", "svc_whisper_rows", "svc_whisper_set_window_group",
+    "svc_whisper_set_timing", "svc_whisper_last_timing", "svc_whisper_mel", "svc_whisper_encode", "svc_whisper_content",
     "svc_prof_enable", "svc_prof_collect",
     "svc_op_linear", "svc_op_conv1d", "svc_op_conv1d_ex", "svc_op_conv1d_last_took", "svc_op_conv_transpose1d", "svc_op_attention", "svc_op_rmsnorm",
+    "svc_op_layernorm",
 ]
 
 
@@ -95,6 +98,10 @@ class RmvpeConfig(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("n_mels", "en_de_layers", "inter_layers", "n_blocks", "en_out_channels", "gru_hidden", "n_bins")]
 
 
+class WhisperConfig(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("n_mels", "d_model", "n_heads", "n_layers", "ffn_dim", "max_source_positions", "precision")]
+
+
 class LrConfig(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("channels", "in_channels", "out_channels", "is_discrete", "codebook_size", "n_convs",
                                        "interpolate", "has_final_conv", "f0_condition", "n_f0_bins")]
@@ -153,6 +160,18 @@ def lib():
         l.svc_rmvpe_f0.argtypes = [C.c_void_p, C.c_void_p, i32p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]
         l.svc_f0_adjust.argtypes = [C.c_void_p, i32p, C.c_void_p, i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float),
                                     C.c_void_p, C.c_void_p, C.c_void_p]
+        # Whisper content encoder: lengths as HOST int32 arrays, sample counts of the window plan as C long
+        l.svc_whisper_create.argtypes = [C.POINTER(WhisperConfig), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+        l.svc_whisper_destroy.argtypes = [C.c_void_p]
+        l.svc_whisper_n_windows.argtypes = [C.c_int, C.c_int, C.c_long]
+        l.svc_whisper_rows.argtypes = [C.c_int, C.c_int, C.c_long]
+        l.svc_whisper_set_window_group.argtypes = [C.c_void_p, C.c_int]
+        l.svc_whisper_set_timing.argtypes = [C.c_void_p, C.c_int]
+        l.svc_whisper_last_timing.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        l.svc_whisper_mel.argtypes = [C.c_void_p, C.c_void_p, i32p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        l.svc_whisper_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        l.svc_whisper_content.argtypes = [C.c_void_p, C.c_void_p, i32p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        l.svc_op_layernorm.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p]
         _lib = l
     return _lib
 

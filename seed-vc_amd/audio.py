@@ -16,6 +16,17 @@ from . import _lib
 
 def slaney_mel_basis(sr, n_fft, n_mels, fmin=0.0, fmax=None):
     """librosa.filters.mel defaults (htk=False, norm='slaney'), float32 [n_mels][n_fft // 2 + 1]."""
+    return torch.from_numpy(_slaney_weights(sr, n_fft, n_mels, fmin, fmax).astype(np.float32))
+
+
+def whisper_mel_basis(n_mels=80):
+    """The filterbank of `WhisperFeatureExtractor` (16 kHz, n_fft 400, 0 .. 8000 Hz, Slaney scale, Slaney normalisation:
+    `transformers.audio_utils.mel_filter_bank(201, n_mels, 0, 8000, 16000, "slaney", "slaney")` transposed), float64
+    [n_mels][201].  Pinned to that function by the host tests."""
+    return torch.from_numpy(_slaney_weights(16000, 400, n_mels, 0.0, 8000.0))
+
+
+def _slaney_weights(sr, n_fft, n_mels, fmin, fmax):
     fmax = sr / 2.0 if fmax in (None, "None") else float(fmax)
     f_sp, min_log_hz = 200.0 / 3, 1000.0
     min_log_mel, logstep = min_log_hz / f_sp, np.log(6.4) / 27.0
@@ -36,7 +47,7 @@ def slaney_mel_basis(sr, n_fft, n_mels, fmin=0.0, fmax=None):
     for i in range(n_mels):
         w[i] = np.maximum(0, np.minimum(-ramps[i] / fdiff[i], ramps[i + 2] / fdiff[i + 1]))
     w *= (2.0 / (mel_f[2:n_mels + 2] - mel_f[:n_mels]))[:, None]
-    return torch.from_numpy(w.astype(np.float32))
+    return w
 
 
 def htk_mel_basis(sr, n_fft, n_mels, fmin=0.0, fmax=None):

@@ -28,7 +28,7 @@ constexpr int ROWB = 128;
 
 __device__ __forceinline__ int lds_off(int row, int c16) { return row * ROWB + ((c16 ^ ((row >> 1) & 7)) << 4); }
 
-template <int QT, bool VPERM>
+template <int QT, bool VPERM, bool OUT32 = false>      // OUT32: fp32 output rows (AttnParams.out32) instead of fp16
 __global__ __launch_bounds__(256) void attn_kernel(const AttnParams p) {
     constexpr int BQ = 64 * QT;   // queries per block
     constexpr int NS = 3;         // ring stages: tiles kt + 1, kt + 2 in flight under the MFMAs of tile kt
@@ -230,7 +230,15 @@ __global__ __launch_bounds__(256) void attn_kernel(const AttnParams p) {
         const float l = __shfl(acc_l[qt][0], fr);
         const float inv = l > 0.f ? 1.0f / l : 0.f;
         const int qr = q0 + qt * 16 + fr;
-        if (qr < p.Tq) {
+        if constexpr (OUT32) {                              // fp32 rows instead of fp16 (same addressing)
+          if (qr < p.Tq) {
+            float* dst = p.out32 + (row_base + qr) * p.ld_out + h * 64 + fq * 4;
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt)
+                *reinterpret_cast<float4v*>(dst + dt * 16) =
+                    (float4v){acc_o[dt][qt][0] * inv, acc_o[dt][qt][1] * inv, acc_o[dt][qt][2] * inv, acc_o[dt][qt][3] * inv};
+          }
+        } else if (qr < p.Tq) {
             half_t* dst = p.out + (row_base + qr) * p.ld_out + h * 64 + fq * 4;
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt) {
@@ -270,7 +278,7 @@ typedef _Float16 half2v __attribute__((ext_vector_type(2)));
 
 // NW = waves per block: 4 (128 queries) for full grids, 2 (64 queries) for small ones (a single utterance gives only
 // 2 x H x 7 blocks of 128 queries for 256 CUs); a wave's arithmetic is the same in both, so the forms are bit-identical.
-template <int NW, int NS = 3, bool KPF = true, bool ONES = true>
+template <int NW, int NS = 3, bool KPF = true, bool ONES = true, bool OUT32 = false>
 __global__ __launch_bounds__(64 * NW) void attn32_kernel(const AttnParams p) {
     constexpr int BQ = 32 * NW;
     constexpr int RG = 8 / NW;    // 8-row groups of the K tile (and of the V^T tile) staged per wave
@@ -456,7 +464,17 @@ __global__ __launch_bounds__(64 * NW) void attn32_kernel(const AttnParams p) {
     }
     const float inv = l > 0.f ? 1.0f / l : 0.f;
     const int qr = q0 + fr;
-    if (qr < p.Tq) {
+    if constexpr (OUT32) {                                  // fp32 rows instead of fp16 (same addressing)
+      if (qr < p.Tq) {
+        float* dst = p.out32 + (row_base + qr) * p.ld_out + h * 64 + fh * 4;
+#pragma unroll
+        for (int hb = 0; hb < 2; ++hb)
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+                *reinterpret_cast<float4v*>(dst + hb * 32 + g * 8) = (float4v){acc_o[hb][4 * g] * inv, acc_o[hb][4 * g + 1] * inv,
+                                                                              acc_o[hb][4 * g + 2] * inv, acc_o[hb][4 * g + 3] * inv};
+      }
+    } else if (qr < p.Tq) {
         half_t* dst = p.out + (row_base + qr) * p.ld_out + h * 64 + fh * 4;
 #pragma unroll
         for (int hb = 0; hb < 2; ++hb)
@@ -506,10 +524,24 @@ int attention_launch(const AttnParams& p, hipStream_t st) {
     if (prof) prof_begin(PROF_ATTN, st);
     static const int qt_env = [] { const char* e = getenv("SVC_ATTN_QT"); return e ? atoi(e) : 0; }();
     const dim3 g64(cdiv(p.Tq - p.q_start, 64) * p.H * p.n_seq);
-    if (p.vt_perm == 2) {
-        if (g128 <= 256) hipLaunchKernelGGL((attn32_kernel<2>), g64, dim3(128), 0, st, p);
+    // a caller that needs the same bits for any number of sequences pins the form (qt_form); 0 = by the grid size
+    const bool small = p.qt_form ? p.qt_form == 1 : (qt_env == 1 || (qt_env == 0 && g128 <= 256));
+    const bool small32 = p.qt_form ? p.qt_form == 1 : g128 <= 256;
+    if (p.out32) {                                          // fp32 output rows: instantiations of their own, the others are unchanged
+        if (p.vt_perm == 2) {
+            if (small32) hipLaunchKernelGGL((attn32_kernel<2, 3, true, true, true>), g64, dim3(128), 0, st, p);
+            else hipLaunchKernelGGL((attn32_kernel<4, 3, true, true, true>), dim3(g128), dim3(256), 0, st, p);
+        } else if (small) {
+            if (p.vt_perm) hipLaunchKernelGGL((attn_kernel<1, true, true>), g64, dim3(256), 0, st, p);
+            else hipLaunchKernelGGL((attn_kernel<1, false, true>), g64, dim3(256), 0, st, p);
+        } else {
+            if (p.vt_perm) hipLaunchKernelGGL((attn_kernel<2, true, true>), dim3(g128), dim3(256), 0, st, p);
+            else hipLaunchKernelGGL((attn_kernel<2, false, true>), dim3(g128), dim3(256), 0, st, p);
+        }
+    } else if (p.vt_perm == 2) {
+        if (small32) hipLaunchKernelGGL((attn32_kernel<2>), g64, dim3(128), 0, st, p);
         else hipLaunchKernelGGL((attn32_kernel<4>), dim3(g128), dim3(256), 0, st, p);
-    } else if (qt_env == 1 || (qt_env == 0 && g128 <= 256)) {
+    } else if (small) {
         if (p.vt_perm) hipLaunchKernelGGL((attn_kernel<1, true>), g64, dim3(256), 0, st, p);
         else hipLaunchKernelGGL((attn_kernel<1, false>), g64, dim3(256), 0, st, p);
     } else {

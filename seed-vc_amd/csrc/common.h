@@ -108,13 +108,17 @@ constexpr int KG_MAX_TAPS = 48;   // 16-tap conv x 3 split-precision products
 
 enum { KG_PAD_ZERO = 0, KG_PAD_REFLECT = 1, KG_PAD_CLAMP = 2 };
 enum { KG_ACT_NONE = 0, KG_ACT_SILU = 1, KG_ACT_ELU = 2, KG_ACT_LRELU = 3, KG_ACT_TANH = 4, KG_ACT_ABS = 5,
-       KG_ACT_CLAMP = 6 /* clamp to +-act_slope */, KG_ACT_SIGMOID = 7 };
+       KG_ACT_CLAMP = 6 /* clamp to +-act_slope */, KG_ACT_SIGMOID = 7,
+       KG_ACT_GELU = 8 /* exact erf form; tap-GEMM STORE epilogue only, as its own instantiation (KG_EPI_STORE_GELU) */ };
 enum {
     KG_EPI_STORE = 0,     // bias / per-seq rowvec / activation / gate / residual; fp32 and/or fp16 out
     KG_EPI_SWIGLU = 1,    // columns (2j, 2j+1) = (w1_j, w3_j): out[j] = silu(a) * b           (fp16 out)
     KG_EPI_TANHSIG = 2,   // columns (2j, 2j+1) = (t_j, s_j):   out[j] = tanh(a) * sigmoid(b)  (+bias/rowvec)
     KG_EPI_QKV_ROPE = 3,  // q,k: interleaved-pair RoPE (+q scale) -> fp16 ; v: transposed store
+    KG_EPI_STORE_GELU = 4,  // KG_EPI_STORE with act == KG_ACT_GELU compiled in: kgemm_launch selects it, callers pass KG_EPI_STORE
 };
+
+__device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752f)); }
 
 __device__ __forceinline__ float act_apply(float v, int act, float slope) {
     switch (act) {
@@ -270,6 +274,9 @@ struct AttnParams {
     int q_start;
     const int* kv_len; int kv_len_const;             // keys [0, len) attended
     int vt_perm;                                     // column order of vt: 0 natural, 1 vt_perm_pos(), 2 vt_perm_pos16() (vt_pos)
+    int qt_form;                                     // query-tile form: 0 = chosen from the grid size (every caller but the Whisper
+                                                     // encoder), 1 = 64-query workgroups, 2 = 128-query workgroups
+    float* out32;                                    // optional: the output rows in fp32 (ld_out, as `out`) INSTEAD of fp16; null = fp16
 };
 // Column order of V^T inside every group of 32 keys: key 16 h + 4 f + r  ->  position 8 f + 4 h + r.  The P^T operand
 // of the PV MFMA holds, in lane group f, the keys {4 f .. 4 f + 3} and {16 + 4 f .. 16 + 4 f + 3} of a 32-key step (that is

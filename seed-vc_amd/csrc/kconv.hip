@@ -391,6 +391,7 @@ int kconv_go(DeviceState* ds, const KConvParams& p, int grid, hipStream_t st) {
 int kconv_launch(const KConvParams& p_in, hipStream_t st) {
     SVC_REQUIRE(p_in.k >= 1 && (p_in.k - 1) * p_in.dil <= CB_SPAN && p_in.cin_pad % 64 == 0 && p_in.N % 8 == 0, "kconv shape");
     SVC_REQUIRE(!p_in.seq_len || p_in.Lin == p_in.Lout, "kconv: per-sequence lengths need Lin == Lout");
+    SVC_REQUIRE(p_in.act != KG_ACT_GELU, "kconv: KG_ACT_GELU exists in the tap-GEMM's STORE epilogue only");
     DeviceState* ds = device_state();
     if (!ds) return 1;
     KConvParams p = p_in;

@@ -101,7 +101,8 @@ int kgemm_launch(const KGemmParams& p_in, int dtype, int epi, hipStream_t st) {
     const bool prof = prof_enabled();
     const int cls = dtype == 0 ? PROF_KGEMM_F16 : PROF_KGEMM_F32;
     if (prof) prof_begin(cls, st);
-    const int rc = kgemm_dispatch(p, dtype, epi, st);
+    // the erf-GELU lives in its own STORE instantiations: the other STORE kernels do not carry its code
+    const int rc = kgemm_dispatch(p, dtype, epi == KG_EPI_STORE && p.act == KG_ACT_GELU ? KG_EPI_STORE_GELU : epi, st);
     if (prof) {
         long kt = 0;
         for (int t = 0; t < p.n_taps; ++t) kt += p.a_ktiles[t];
@@ -121,6 +122,7 @@ int kgemm_dispatch(const KGemmParams& p, int dtype, int epi, hipStream_t st) {
     if (dtype == 0) {
         switch (epi) {
             case KG_EPI_STORE: return launch_bn<half_t, KG_EPI_STORE>(p, st);
+            case KG_EPI_STORE_GELU: return launch_bn<half_t, KG_EPI_STORE_GELU>(p, st);
             case KG_EPI_SWIGLU: return launch_wide<half_t, KG_EPI_SWIGLU>(p, st);
             case KG_EPI_TANHSIG: return launch_wide<half_t, KG_EPI_TANHSIG>(p, st);
             case KG_EPI_QKV_ROPE: return launch_wide<half_t, KG_EPI_QKV_ROPE>(p, st);
@@ -128,6 +130,7 @@ int kgemm_dispatch(const KGemmParams& p, int dtype, int epi, hipStream_t st) {
     } else {
         switch (epi) {
             case KG_EPI_STORE: return launch_bn<float, KG_EPI_STORE>(p, st);
+            case KG_EPI_STORE_GELU: return launch_bn<float, KG_EPI_STORE_GELU>(p, st);
             case KG_EPI_TANHSIG: return launch_wide<float, KG_EPI_TANHSIG>(p, st);
         }
     }

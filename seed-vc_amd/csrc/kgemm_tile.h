@@ -344,7 +344,7 @@ __global__ __launch_bounds__(NWV * 64, (NS * (BM + BN) * RB > 80 * 1024) ? 1 : 2
     // traffic dominates): C accumulators transposed through LDS so that 8 consecutive lanes cover 256 contiguous bytes
     // of a row -- 4x fewer memory requests per byte, which is what bounds that epilogue (measured: direct stores were
     // 10-20 % slower for wo / w2).
-    constexpr bool DIRECT = EPI != KG_EPI_STORE;
+    constexpr bool DIRECT = EPI != KG_EPI_STORE && EPI != KG_EPI_STORE_GELU;
     constexpr int CW = DIRECT ? 4 * G::TN : 8;         // consecutive output columns per lane
     // V blocks of the QKV GEMM (whole 128-column blocks: 2 D is a multiple of 128) keep the C orientation
     const bool v_blk = (EPI == KG_EPI_QKV_ROPE) && (n0 >= 2 * p.rope_D);
@@ -509,7 +509,10 @@ __global__ __launch_bounds__(NWV * 64, (NS * (BM + BN) * RB > 80 * 1024) ? 1 : 2
             }
 
             {
-                if (p.act != KG_ACT_NONE) {
+                if constexpr (EPI == KG_EPI_STORE_GELU) {
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) v[j] = gelu_erf(v[j]);
+                } else if (p.act != KG_ACT_NONE) {
 #pragma unroll
                     for (int j = 0; j < 8; ++j) v[j] = act_apply(v[j], p.act, p.act_slope);
                 }

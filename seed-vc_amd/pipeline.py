@@ -186,6 +186,34 @@ def f0_conditions(rmvpe, src_16k, src_lens, ref_16k, ref_lens, auto_f0_adjust=Tr
     return f0_ori, ori_frames, shifted, alt_frames
 
 
+@torch.inference_mode()
+def content_conditions(whisper, length_regulator, src_16k, src_lens, src_ylens, ref_16k, ref_lens, ref_ylens, f0_src=None, f0_ref=None,
+                       overlap_s=5.0):
+    """The drivers' content block for B (source, reference) pairs: `S_alt = semantic_fn(src_16k)`, `S_ori = semantic_fn(ref_16k)`
+    (with their loop over the windows of a long clip), `cond = length_regulator(S_alt, ylens=..., f0=shifted_f0_alt)[0]` and
+    `prompt_condition = length_regulator(S_ori, ylens=..., f0=F0_ori)[0]`: one `WhisperContent.content_batch` call over the 2 B clips
+    and two regulator calls, with no host round trip between the stages.  src_16k (B, Ls) / ref_16k (B, Lr) at 16 kHz with
+    src_lens[b] / ref_lens[b] samples each (host integers); src_ylens / ref_ylens: the target frame counts (B integers);
+    f0_src / f0_ref: None, or (track (B, T), frames) pairs as `f0_conditions` returns them; overlap_s: the windows' overlap (the
+    drivers' 5 s).
+    -> (cond (B, max(src_ylens), C), prompt_condition (B, max(ref_ylens), C))."""
+    src_lens, ref_lens = _lib.int_list(src_lens), _lib.int_list(ref_lens)
+    B = src_16k.size(0)
+    if len(src_lens) != B or len(ref_lens) != B or ref_16k.size(0) != B:
+        raise ValueError(f"content_conditions: {len(src_lens)} src_lens and {len(ref_lens)} ref_lens for {B} and {ref_16k.size(0)} clips")
+    L = max(src_16k.size(1), ref_16k.size(1))
+    waves = torch.zeros(2 * B, L, device=whisper.device)
+    waves[:B, :src_16k.size(1)] = _lib.f32c(src_16k, whisper.device)
+    waves[B:, :ref_16k.size(1)] = _lib.f32c(ref_16k, whisper.device)
+    S, rows = whisper.content_batch(waves, src_lens + ref_lens, overlap_s=overlap_s)
+    ylens = lambda v: torch.as_tensor(_lib.int_list(v), dtype=torch.long)      # noqa: E731
+    f0a, fla = f0_src if f0_src is not None else (None, None)
+    f0o, flo = f0_ref if f0_ref is not None else (None, None)
+    cond = length_regulator(S[:B], ylens=ylens(src_ylens), f0=f0a, in_lens=rows[:B], f0_lens=fla)[0]
+    prompt_condition = length_regulator(S[B:], ylens=ylens(ref_ylens), f0=f0o, in_lens=rows[B:], f0_lens=flo)[0]
+    return cond, prompt_condition
+
+
 def _assemble_cond(prompt_condition, P, cond, S, T):
     """mu (n, T, Dc): row b is prompt_condition[b, :P[b]], then cond[b, :S[b]], then zeros (`svc_v2_assemble_cond`).
     prompt_condition (n, Pmax, Dc) and cond (n, >= max(S), Dc) on one device, P / S host integers."""

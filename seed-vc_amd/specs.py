@@ -584,3 +584,35 @@ def rmvpe_state_spec(c):
     s["fc.1.weight"] = (c["n_bins"], 2 * H)
     s["fc.1.bias"] = (c["n_bins"],)
     return s
+
+
+# --------------------------------------------------------------------------------------------- Whisper content encoder
+# the encoder half of openai/whisper-small (transformers' WhisperEncoder), the content encoder of the v1 models
+WHISPER_PRESET = dict(n_mels=80, d_model=768, n_heads=12, n_layers=12, ffn_dim=3072, max_source_positions=1500)
+
+
+def whisper_config(**overrides):
+    cfg = deepcopy(WHISPER_PRESET)
+    cfg.update(overrides)
+    assert cfg["d_model"] % 64 == 0 and cfg["n_heads"] * 64 == cfg["d_model"] and cfg["n_mels"] % 8 == 0 and cfg["ffn_dim"] % 64 == 0
+    return cfg
+
+
+def whisper_state_spec(c):
+    """State dict of `WhisperEncoder`, in torch's registration order (k_proj has no bias; `embed_positions.weight` is part of it)."""
+    s = OrderedDict()
+    D, F = c["d_model"], c["ffn_dim"]
+    s["conv1.weight"], s["conv1.bias"] = (D, c["n_mels"], 3), (D,)
+    s["conv2.weight"], s["conv2.bias"] = (D, D, 3), (D,)
+    s["embed_positions.weight"] = (c["max_source_positions"], D)
+    for i in range(c["n_layers"]):
+        p = f"layers.{i}."
+        s[p + "self_attn.k_proj.weight"] = (D, D)
+        for n in ("v_proj", "q_proj", "out_proj"):
+            s[p + f"self_attn.{n}.weight"], s[p + f"self_attn.{n}.bias"] = (D, D), (D,)
+        s[p + "self_attn_layer_norm.weight"], s[p + "self_attn_layer_norm.bias"] = (D,), (D,)
+        s[p + "fc1.weight"], s[p + "fc1.bias"] = (F, D), (F,)
+        s[p + "fc2.weight"], s[p + "fc2.bias"] = (D, F), (D,)
+        s[p + "final_layer_norm.weight"], s[p + "final_layer_norm.bias"] = (D,), (D,)
+    s["layer_norm.weight"], s["layer_norm.bias"] = (D,), (D,)
+    return s
