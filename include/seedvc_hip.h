@@ -549,6 +549,64 @@ int svc_whisper_encode(svc_whisper_t* m, const float* feat, int B, float* out, v
 int svc_whisper_content(svc_whisper_t* m, const float* wave, const int32_t* lens, int B, int L, int overlap_rows, float* out, int Rmax,
                         void* stream);
 
+/* ---------------------------------------------------------------- wav2vec 2.0 content encoder (csrc/wav2vec2.hip)
+ * Replaces `semantic_fn(waves_16k)` of the drivers for the xlsr models (Wav2Vec2FeatureExtractor + the first n_layers layers of
+ * facebook/wav2vec2-xls-r-300m, one 30 s window at a time) and their loop over the windows of a long clip.  HuBERT-large is the same
+ * network.  Accepted: feat_extract_norm = "layer" with do_stable_layer_norm and conv_bias, one conv_dim (a multiple of 64, at most
+ * 512) for all n_conv <= 8 extractor convs whose strides multiply to 320 samples per row (the window plan counts rows of 320
+ * samples) and conv_kernel[0] * conv_dim <= 8192, heads of 64, erf-GELU, an even num_conv_pos_embeddings (pos_k <= 128) in groups of 64
+ * channels; anything else is refused by svc_w2v_create.  n_layers layers run, then encoder.layer_norm.
+ * frames(n): (n - conv_kernel[l]) / conv_stride[l] + 1 applied for every conv (0 once n < conv_kernel[l]).
+ * Stages: normalisation (x - mean) / sqrt(var + 1e-7) over the clip's (in the one call: the window's) own samples, population
+ * variance about the mean, fixed reduction order; the extractor (conv, LayerNorm over channels, GELU; then the feature projection's
+ * LayerNorm and Linear conv_dim -> d_model); the positional conv (grouped Conv1d, padding pos_k / 2, last output dropped, GELU,
+ * added to its input); n_layers pre-LN blocks (LayerNorm eps 1e-5; q / 8, k, v with biases; unmasked softmax attention over the
+ * clip's own rows; out_proj + residual; LayerNorm; intermediate_dense + GELU; output_dense + residual); encoder.layer_norm.
+ * Residual stream, LayerNorm statistics and softmax are fp32.  precision 1: fp16 operands with fp32 accumulation (the positional
+ * conv on its own MFMA kernel); 0: the fp32 tap-GEMM everywhere (attention operands stay fp16).
+ * weights: Wav2Vec2Model.state_dict() or HubertModel.state_dict() (device fp32); the prefixes "wav2vec2.", "hubert." and "model." are
+ * accepted, unknown keys (masked_spec_embed, ...) are ignored; the positional conv's weight norm (parametrizations.weight.original0 /
+ * original1, or weight_g / weight_v, or a plain weight) is folded at pack time.  Lengths and row counts are HOST int32 arrays consumed
+ * before the call returns; arguments are checked before the handle is touched; nothing synchronises once the workspace has its size.
+ * Samples / rows at and above a clip's length are never read as values.  Every clip (window) gets what it would get alone: its bits
+ * do not depend on what shares the call, on the order or on the group size. */
+typedef struct svc_w2v_config {
+    int conv_dim, n_conv, conv_kernel[8], conv_stride[8];
+    int d_model, n_heads, n_layers, ffn_dim, pos_k, pos_groups;
+    int feat_extract_norm_layer, do_stable_layer_norm, conv_bias;   /* must all be 1 */
+    int window_samples;     /* the drivers' window: 480000 (a multiple of 320) */
+    int precision;
+} svc_w2v_config_t;
+typedef struct svc_w2v svc_w2v_t;
+
+int svc_w2v_create(const svc_w2v_config_t* cfg, const svc_tensor_desc_t* weights, int n_weights, void* stream, svc_w2v_t** out);
+void svc_w2v_destroy(svc_w2v_t* m);
+/* Host-side counts (no handle; -1 on a bad argument).  svc_w2v_frames: rows of n_samples in one piece.  The window plan is the
+ * drivers' (svc_whisper_n_windows, with W = window_samples and O = 320 overlap_rows); a window of n samples yields frames(n) rows,
+ * every window but the first drops its first overlap_rows, a later window with frames(n) <= overlap_rows contributes nothing.
+ * A clip whose first window is shorter than the extractor's receptive field is an error. */
+long svc_w2v_frames(const svc_w2v_config_t* cfg, long n_samples);
+int svc_w2v_n_windows(const svc_w2v_config_t* cfg, int overlap_rows, long n_samples);
+int svc_w2v_rows(const svc_w2v_config_t* cfg, int overlap_rows, long n_samples);
+/* Windows computed side by side (1 .. 64, 0 = the default of 16): bounds the workspace; results do not depend on it. */
+int svc_w2v_set_window_group(svc_w2v_t* m, int windows);
+/* Measurement aid (tools/w2v_bench.py): ms4 = {normalisation + extractor, positional conv, layers, assemble} of the last group of the
+ * last svc_w2v_content call, in ms. */
+int svc_w2v_set_timing(svc_w2v_t* m, int on);
+int svc_w2v_last_timing(svc_w2v_t* m, float* ms4);
+/* wave [B][L], 1 <= lens[b] <= L, B <= 64 -> out [B][L]: samples below lens[b] normalised, the others not touched. */
+int svc_w2v_normalize(svc_w2v_t* m, const float* wave, const int32_t* lens, int B, int L, float* out, void* stream);
+/* normalised wave [B][L] -> out [B][Tmax][d_model]: the frames(lens[b]) projected rows of each clip; the rows above are not touched. */
+int svc_w2v_features(svc_w2v_t* m, const float* wave_norm, const int32_t* lens, int B, int L, float* out, int Tmax, void* stream);
+/* h [B][T][d_model], 1 <= rows[b] <= T -> out = h + gelu(pos_conv(h)) on rows below rows[b]; the rows above are not touched. */
+int svc_w2v_posconv(svc_w2v_t* m, const float* h, const int32_t* rows, int B, int T, float* out, void* stream);
+/* h (projected rows) -> out [B][T][d_model]: positional conv, n_layers layers, encoder.layer_norm; rows at and above rows[b] are not touched. */
+int svc_w2v_encode(svc_w2v_t* m, const float* h, const int32_t* rows, int B, int T, float* out, void* stream);
+/* The one call: wave [B][L], lens HOST [B] or NULL (= L), B <= 64 clips of any length -> out [B][Rmax][d_model]: rows
+ * [0, svc_w2v_rows(cfg, overlap_rows, lens[b])) of out[b] are the kept rows of the clip's windows in order, the rows above are zero.
+ * Each window is normalised on its own (the drivers call the feature extractor per window). */
+int svc_w2v_content(svc_w2v_t* m, const float* wave, const int32_t* lens, int B, int L, int overlap_rows, float* out, int Rmax, void* stream);
+
 /* Device-side counterpart of `crossfade(chunk1, chunk2, overlap)` (inference.py:343-350): the first n samples of
  * chunk2 become chunk2 * fade_in + chunk1_tail * fade_out in float64, stored as float32 (bit-identical to the numpy
  * arithmetic).  fade_in / fade_out: the caller's cos^2 windows (double, device). */
@@ -657,6 +715,9 @@ int svc_op_rmsnorm(const float* x, const float* gamma, const float* w, const flo
                    int rows, int D, void* stream);
 /* y = LayerNorm(x) * gamma + beta ; x, y [rows][D], D a multiple of 64 (at most 2048); mean, then the variance about it, in fp32. */
 int svc_op_layernorm(const float* x, const float* gamma, const float* beta, float* y, int rows, int D, float eps, void* stream);
+
+/* y = gelu(LayerNorm(x) * gamma + beta), erf form: the wav2vec 2.0 extractor's row kernel (one wave per row, two-pass statistics). */
+int svc_op_layernorm_gelu(const float* x, const float* gamma, const float* beta, float* y, int rows, int D, float eps, void* stream);
 
 /* Tuning / measurement aid (tools/gemm_bench.py, tools/gemm_small_bench.py; no model uses it): times `iters` launches of the
  * tap-GEMM on synthetic operands of shape M x N x K; dtype 0 fp16 / 1 fp32, epi = epilogue kind, debug = tile-form override

@@ -33,9 +33,12 @@ EXPORTS = [
     "svc_rmvpe_salience", "svc_rmvpe_decode", "svc_rmvpe_f0", "svc_f0_adjust",
     "svc_whisper_create", "svc_whisper_destroy", "svc_whisper_n_windows", "svc_whisper_rows", "svc_whisper_set_window_group",
     "svc_whisper_set_timing", "svc_whisper_last_timing", "svc_whisper_mel", "svc_whisper_encode", "svc_whisper_content",
+    "svc_w2v_create", "svc_w2v_destroy", "svc_w2v_frames", "svc_w2v_n_windows", "svc_w2v_rows", "svc_w2v_set_window_group",
+    "svc_w2v_set_timing", "svc_w2v_last_timing", "svc_w2v_normalize", "svc_w2v_features", "svc_w2v_posconv", "svc_w2v_encode",
+    "svc_w2v_content",
     "svc_prof_enable", "svc_prof_collect",
     "svc_op_linear", "svc_op_conv1d", "svc_op_conv1d_ex", "svc_op_conv1d_last_took", "svc_op_conv_transpose1d", "svc_op_attention", "svc_op_rmsnorm",
-    "svc_op_layernorm",
+    "svc_op_layernorm", "svc_op_layernorm_gelu",
 ]
 
 
@@ -100,6 +103,12 @@ class RmvpeConfig(C.Structure):
 
 class WhisperConfig(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("n_mels", "d_model", "n_heads", "n_layers", "ffn_dim", "max_source_positions", "precision")]
+
+
+class W2vConfig(C.Structure):
+    _fields_ = [("conv_dim", C.c_int), ("n_conv", C.c_int), ("conv_kernel", C.c_int * 8), ("conv_stride", C.c_int * 8)] + \
+               [(n, C.c_int) for n in ("d_model", "n_heads", "n_layers", "ffn_dim", "pos_k", "pos_groups", "feat_extract_norm_layer",
+                                       "do_stable_layer_norm", "conv_bias", "window_samples", "precision")]
 
 
 class LrConfig(C.Structure):
@@ -171,6 +180,23 @@ def lib():
         l.svc_whisper_mel.argtypes = [C.c_void_p, C.c_void_p, i32p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         l.svc_whisper_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         l.svc_whisper_content.argtypes = [C.c_void_p, C.c_void_p, i32p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        # wav2vec 2.0 content encoder: lengths and row counts as HOST int32 arrays, sample counts as C long
+        cp = C.POINTER(W2vConfig)
+        l.svc_w2v_create.argtypes = [cp, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]
+        l.svc_w2v_destroy.argtypes = [C.c_void_p]
+        l.svc_w2v_frames.argtypes = [cp, C.c_long]
+        l.svc_w2v_frames.restype = C.c_long
+        l.svc_w2v_n_windows.argtypes = [cp, C.c_int, C.c_long]
+        l.svc_w2v_rows.argtypes = [cp, C.c_int, C.c_long]
+        l.svc_w2v_set_window_group.argtypes = [C.c_void_p, C.c_int]
+        l.svc_w2v_set_timing.argtypes = [C.c_void_p, C.c_int]
+        l.svc_w2v_last_timing.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        l.svc_w2v_normalize.argtypes = [C.c_void_p, C.c_void_p, i32p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        l.svc_w2v_features.argtypes = [C.c_void_p, C.c_void_p, i32p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        l.svc_w2v_posconv.argtypes = [C.c_void_p, C.c_void_p, i32p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        l.svc_w2v_encode.argtypes = [C.c_void_p, C.c_void_p, i32p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        l.svc_w2v_content.argtypes = [C.c_void_p, C.c_void_p, i32p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        l.svc_op_layernorm_gelu.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p]
         l.svc_op_layernorm.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p]
         _lib = l
     return _lib

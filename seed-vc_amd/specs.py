@@ -616,3 +616,44 @@ def whisper_state_spec(c):
         s[p + "final_layer_norm.weight"], s[p + "final_layer_norm.bias"] = (D,), (D,)
     s["layer_norm.weight"], s["layer_norm.bias"] = (D,), (D,)
     return s
+
+
+# --------------------------------------------------------------------------------------------- wav2vec 2.0 content encoder
+# facebook/wav2vec2-xls-r-300m cut to its first 12 layers (the drivers' `output_layer`), the content encoder of the tiny v1 model;
+# HuBERT-large (the front half of the v2 ASTRAL tokenizer) is the same network
+W2V_PRESET = dict(conv_dim=512, conv_kernel=(10, 3, 3, 3, 3, 2, 2), conv_stride=(5, 2, 2, 2, 2, 2, 2), d_model=1024, n_heads=16, n_layers=12,
+                  ffn_dim=4096, pos_k=128, pos_groups=16, feat_extract_norm="layer", do_stable_layer_norm=True, conv_bias=True,
+                  window_samples=480000)
+
+
+def wav2vec2_config(**overrides):
+    cfg = deepcopy(W2V_PRESET)
+    cfg.update(overrides)
+    return cfg
+
+
+def wav2vec2_state_spec(c):
+    """State dict of `Wav2Vec2Model` (layer-norm extractor, stable layer norm), in torch's registration order; `HubertModel` has the
+    same keys."""
+    s = OrderedDict()
+    D, F, C, k = c["d_model"], c["ffn_dim"], c["conv_dim"], c["pos_k"]
+    s["masked_spec_embed"] = (D,)
+    for l, kl in enumerate(c["conv_kernel"]):
+        p = f"feature_extractor.conv_layers.{l}."
+        s[p + "conv.weight"], s[p + "conv.bias"] = (C, C if l else 1, kl), (C,)
+        s[p + "layer_norm.weight"], s[p + "layer_norm.bias"] = (C,), (C,)
+    s["feature_projection.layer_norm.weight"], s["feature_projection.layer_norm.bias"] = (C,), (C,)
+    s["feature_projection.projection.weight"], s["feature_projection.projection.bias"] = (D, C), (D,)
+    s["encoder.pos_conv_embed.conv.bias"] = (D,)
+    s["encoder.pos_conv_embed.conv.parametrizations.weight.original0"] = (1, 1, k)
+    s["encoder.pos_conv_embed.conv.parametrizations.weight.original1"] = (D, D // c["pos_groups"], k)
+    s["encoder.layer_norm.weight"], s["encoder.layer_norm.bias"] = (D,), (D,)
+    for i in range(c["n_layers"]):
+        p = f"encoder.layers.{i}."
+        for n in ("k_proj", "v_proj", "q_proj", "out_proj"):
+            s[p + f"attention.{n}.weight"], s[p + f"attention.{n}.bias"] = (D, D), (D,)
+        s[p + "layer_norm.weight"], s[p + "layer_norm.bias"] = (D,), (D,)
+        s[p + "feed_forward.intermediate_dense.weight"], s[p + "feed_forward.intermediate_dense.bias"] = (F, D), (F,)
+        s[p + "feed_forward.output_dense.weight"], s[p + "feed_forward.output_dense.bias"] = (D, F), (D,)
+        s[p + "final_layer_norm.weight"], s[p + "final_layer_norm.bias"] = (D,), (D,)
+    return s

@@ -1,0 +1,173 @@
+"""Host-side mirror of the wav2vec 2.0 content encoder over the C ABI (csrc/wav2vec2.hip).
+
+`Wav2Vec2Content(state_dict).semantic_fn(waves_16k)` has the drivers' closure signature for the xlsr models: (1, L <= 480 000)
+samples at 16 kHz in, (1, frames(L), 1024) content features out (`Wav2Vec2FeatureExtractor` + the first 12 layers of
+facebook/wav2vec2-xls-r-300m + `encoder.layer_norm`).  `content_batch` is the same for up to 64 clips of any length in one call,
+with the drivers' loop over 30 s windows (5 s overlap) done on the device; `normalize`, `features`, `posconv` and `encode` expose
+the stages.  The state dict is `Wav2Vec2Model.state_dict()`; `HubertModel.state_dict()` of the same shape loads unchanged.
+"""
+import ctypes as C
+
+import torch
+
+from . import _lib, specs
+from .whisper import SAMPLES_PER_ROW, window_plan as _window_plan
+
+
+def c_config(cfg, precision=1):
+    """cfg dict (specs.wav2vec2_config) -> _lib.W2vConfig"""
+    c = _lib.W2vConfig()
+    ks, ss = [int(v) for v in cfg["conv_kernel"]], [int(v) for v in cfg["conv_stride"]]
+    if len(ks) != len(ss) or not 2 <= len(ks) <= 8:
+        raise ValueError("wav2vec2: conv_kernel and conv_stride must have the same 2 .. 8 entries")
+    c.conv_dim, c.n_conv = int(cfg["conv_dim"]), len(ks)
+    for i, (k, s) in enumerate(zip(ks, ss)):
+        c.conv_kernel[i], c.conv_stride[i] = k, s
+    for k in ("d_model", "n_heads", "n_layers", "ffn_dim", "pos_k", "pos_groups", "window_samples"):
+        setattr(c, k, int(cfg[k]))
+    c.feat_extract_norm_layer = int(cfg.get("feat_extract_norm", "layer") == "layer")
+    c.do_stable_layer_norm = int(bool(cfg.get("do_stable_layer_norm", True)))
+    c.conv_bias = int(bool(cfg.get("conv_bias", True)))
+    c.precision = int(precision)
+    return c
+
+
+def frames(cfg, n):
+    """rows the extractor yields for n samples in one piece: (n - k) // s + 1 through every conv"""
+    n = int(n)
+    for k, s in zip(cfg["conv_kernel"], cfg["conv_stride"]):
+        n = (n - k) // s + 1 if n >= k else 0
+    return n
+
+
+def window_plan(cfg, L, overlap_rows):
+    """The drivers' windows of a clip of L samples (whisper.window_plan: the loop is shared by all tokenizers) with this encoder's
+    row rule: a list of (start, samples, first_kept_row, rows); a later window with rows <= first_kept_row contributes nothing."""
+    return [(s, n, d, frames(cfg, n)) for s, n, d, _ in _window_plan(L, cfg["window_samples"], int(overlap_rows) * SAMPLES_PER_ROW)]
+
+
+class Wav2Vec2Content:
+    SR = 16000
+
+    def __init__(self, state_dict, cfg=None, device="cuda:0", precision=1):
+        self.cfg = specs.wav2vec2_config() if cfg is None else cfg
+        self.device = torch.device(device)
+        self.D, self.W = int(self.cfg["d_model"]), int(self.cfg["window_samples"])
+        self._c = c_config(self.cfg, precision)
+        self._h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            descs, n, keep = _lib.make_descs(state_dict, self.device)
+            _lib.check(_lib.lib().svc_w2v_create(C.byref(self._c), descs, n, _lib.stream_ptr(), C.byref(self._h)))
+            torch.cuda.current_stream().synchronize()
+        del keep
+
+    def eval(self):
+        return self
+
+    def frames(self, n_samples):
+        return frames(self.cfg, n_samples)
+
+    def rows(self, n_samples, overlap_rows=250):
+        """content rows of a clip of n_samples (the window plan's kept rows)"""
+        r = _lib.lib().svc_w2v_rows(C.byref(self._c), int(overlap_rows), int(n_samples))
+        _lib.check(int(r < 0))
+        return r
+
+    def set_window_group(self, windows):
+        """Windows computed side by side (0 = the default): bounds the workspace; results do not depend on it."""
+        _lib.check(_lib.lib().svc_w2v_set_window_group(self._h, int(windows)))
+
+    def set_timing(self, on):
+        """Measurement aid: record HIP events around the stages of `content_batch` (see `last_timing`)."""
+        _lib.check(_lib.lib().svc_w2v_set_timing(self._h, int(bool(on))))
+
+    def last_timing(self):
+        """dict of milliseconds of the last window group of the last `content_batch` (synchronises)."""
+        ms = (C.c_float * 4)()
+        _lib.check(_lib.lib().svc_w2v_last_timing(self._h, ms))
+        return dict(zip(("extractor", "posconv", "layers", "assemble"), [float(v) for v in ms]))
+
+    @staticmethod
+    def _lens(lens, B):
+        lens = _lib.int_list(lens)
+        if len(lens) != B:
+            raise ValueError(f"Wav2Vec2Content: {len(lens)} lens for a batch of {B}")
+        return lens
+
+    @torch.inference_mode()
+    def normalize(self, waves, lens, out=None):
+        """waves (B, L), lens B host integers in 1 .. L -> (B, L): samples below lens[b] zero-mean / unit-variance normalised; the
+        others keep what `out` held (zeros when `out` is None)."""
+        with torch.cuda.device(self.device):
+            w = _lib.f32c(waves, self.device)
+            B, L = w.shape
+            out = torch.zeros(B, L, device=self.device) if out is None else out
+            _lib.check(_lib.lib().svc_w2v_normalize(self._h, _lib.ptr(w), _lib.i32_host(self._lens(lens, B)), B, L, _lib.ptr(out),
+                                                    _lib.stream_ptr()))
+        return out
+
+    @torch.inference_mode()
+    def features(self, waves_norm, lens, out=None):
+        """normalised waves (B, L) -> (projected rows (B, Tmax, D), rows [B]); rows at and above a clip's count keep what `out` held."""
+        with torch.cuda.device(self.device):
+            w = _lib.f32c(waves_norm, self.device)
+            B, L = w.shape
+            lens = self._lens(lens, B)
+            rows = [self.frames(n) for n in lens]
+            T = max(max(rows), 1) if out is None else out.size(1)
+            out = torch.zeros(B, T, self.D, device=self.device) if out is None else out
+            _lib.check(_lib.lib().svc_w2v_features(self._h, _lib.ptr(w), _lib.i32_host(lens), B, L, _lib.ptr(out), T, _lib.stream_ptr()))
+        return out, rows
+
+    def _rows_call(self, fn, h, rows, out):
+        with torch.cuda.device(self.device):
+            x = _lib.f32c(h, self.device)
+            if x.dim() != 3 or x.size(2) != self.D:
+                raise ValueError(f"Wav2Vec2Content: rows must be (B, T, {self.D}), got {tuple(x.shape)}")
+            B, T, _ = x.shape
+            out = torch.zeros_like(x) if out is None else out
+            _lib.check(fn(self._h, _lib.ptr(x), _lib.i32_host(self._lens(rows, B)), B, T, _lib.ptr(out), _lib.stream_ptr()))
+        return out
+
+    @torch.inference_mode()
+    def posconv(self, h, rows, out=None):
+        """h (B, T, D), rows [B] -> h + gelu(pos_conv(h)) on each clip's own rows; the rows above keep what `out` held."""
+        return self._rows_call(_lib.lib().svc_w2v_posconv, h, rows, out)
+
+    @torch.inference_mode()
+    def encode(self, h, rows, out=None):
+        """projected rows (B, T, D), rows [B] -> (B, T, D): positional conv, the layers and encoder.layer_norm."""
+        return self._rows_call(_lib.lib().svc_w2v_encode, h, rows, out)
+
+    @torch.inference_mode()
+    def content_batch(self, waves, lens=None, overlap_s=5.0):
+        """waves (B, L) at 16 kHz (B <= 64), lens B host integers or None -> (S (B, Rmax, D) on the device, rows [B]): row b holds
+        the rows[b] content rows of waves[b, :lens[b]] as the drivers' window loop gives them, zeros above.  Nothing is synchronised."""
+        ov = int(round(float(overlap_s) * self.SR)) // SAMPLES_PER_ROW
+        with torch.cuda.device(self.device):
+            w = _lib.f32c(waves, self.device)
+            B, L = w.shape
+            lens = [L] * B if lens is None else self._lens(lens, B)
+            rows = [self.rows(n, ov) for n in lens]
+            out = torch.empty(B, max(rows), self.D, device=self.device)
+            _lib.check(_lib.lib().svc_w2v_content(self._h, _lib.ptr(w), _lib.i32_host(lens), B, L, ov, _lib.ptr(out), max(rows),
+                                                  _lib.stream_ptr()))
+        return out, rows
+
+    def semantic_fn(self, waves_16k):
+        """The drivers' closure: (1, L <= W) -> (1, frames(L), D)."""
+        w = torch.as_tensor(waves_16k, dtype=torch.float32)
+        if w.dim() != 2 or w.size(1) > self.W:
+            raise ValueError(f"Wav2Vec2Content.semantic_fn: (B, L <= {self.W}) samples, got {tuple(w.shape)}")
+        return self.content_batch(w, None, overlap_s=0.0)[0]
+
+    def close(self):
+        if self._h:
+            _lib.lib().svc_w2v_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
