@@ -137,24 +137,25 @@ inline int resolve_weight(const StateDict& sd, const std::string& prefix, Arena&
     return 0;
 }
 
-inline int require_shape(const svc_tensor_desc_t* d, const std::string& name, std::initializer_list<long> shp) {
+// `who` (an entry point's name, may be empty) prefixes the error
+inline int require_shape(const svc_tensor_desc_t* d, const std::string& name, const std::vector<long>& shp, const std::string& who = "") {
+    const std::string pre = who.empty() ? who : who + ": ";
     if (!d) {
-        set_error("state_dict is missing " + name);
+        set_error(pre + "state_dict is missing " + name);
         return 1;
     }
     bool ok = d->ndim == (int)shp.size();
-    int i = 0;
-    for (long s : shp) {
-        if (ok && d->shape[i] != s) ok = false;
-        ++i;
-    }
+    for (size_t i = 0; ok && i < shp.size(); ++i) ok = d->shape[i] == shp[i];
     if (!ok) {
         std::string got;
         for (int j = 0; j < d->ndim; ++j) got += std::to_string(d->shape[j]) + (j + 1 < d->ndim ? "," : "");
-        set_error("shape mismatch for " + name + ": got (" + got + ")");
+        set_error(pre + "shape mismatch for " + name + ": got (" + got + ")");
         return 1;
     }
     return 0;
+}
+inline int require_shape(const svc_tensor_desc_t* d, const std::string& name, std::initializer_list<long> shp, const std::string& who = "") {
+    return require_shape(d, name, std::vector<long>(shp), who);
 }
 
 // element size helper

@@ -19,7 +19,7 @@
 #include <string>
 #include <vector>
 
-#include "model_util.h"
+#include "content_encoder.h"       // StageTimer, copy_f32
 
 using namespace svc;
 
@@ -370,18 +370,7 @@ struct svc_rmvpe {
     int cap_B = 0, cap_H = 0;
     Plane pin[RV_MAX_LEVELS + 1], pa[RV_MAX_LEVELS + 1], pb[RV_MAX_LEVELS + 1], pt[RV_MAX_LEVELS + 1], pk[RV_MAX_LEVELS];
     float *phases = nullptr, *cnn_out = nullptr, *xp = nullptr, *gru_out = nullptr;
-    // measurement aid (svc_rmvpe_set_timing): events around the stages of the last group of the last call
-    bool timing = false;
-    hipEvent_t ev[5] = {};
-    ~svc_rmvpe() {
-        for (auto& e : ev) if (e) (void)hipEventDestroy(e);
-    }
-    int mark(int i, hipStream_t st) {
-        if (!timing) return 0;
-        if (!ev[i]) SVC_CHECK_HIP(hipEventCreate(&ev[i]));
-        SVC_CHECK_HIP(hipEventRecord(ev[i], st));
-        return 0;
-    }
+    StageTimer tm;                  // svc_rmvpe_set_timing
     // svc_rmvpe_f0 scratch
     long f0_cap = 0;
     float *f0_mel = nullptr, *f0_sal = nullptr;
@@ -429,13 +418,6 @@ int rv_pack_conv(const float* src, int N, int Cin, int taps, int cin_ld, const f
     return 0;
 }
 
-float* rv_copy(const svc_tensor_desc_t* d, long n, Arena& ar, hipStream_t st) {
-    float* p = ar.alloc_n<float>(round_up(n, 8), st);
-    if (!p) return nullptr;
-    if (hipMemcpyAsync(p, d->data, (size_t)n * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) { set_error("weight copy failed"); return nullptr; }
-    return p;
-}
-
 }  // namespace
 
 #define GETW(var, name, ...)                                              \
@@ -463,7 +445,7 @@ int svc_rmvpe::pack_block(const StateDict& sd, const std::string& p, int cin, in
     if (b->has_sc) {
         GETW(w, p + ".shortcut.weight", cout, cin, 1, 1);
         GETW(bias, p + ".shortcut.bias", cout);
-        if (!(b->sc.b = rv_copy(bias, cout, wts, st))) return 1;
+        if (!(b->sc.b = copy_f32(bias->data, cout, wts, st))) return 1;
         if (rv_pack_conv(w->data, cout, cin, 1, cin_ld, nullptr, wts, st, &b->sc)) return 1;
     }
     return 0;
@@ -516,7 +498,7 @@ int svc_rmvpe::pack(const StateDict& sd, const float* mel_basis, hipStream_t st)
     {   // head conv: Conv2d(c0, 3, 3 x 3, bias)
         GETW(w, "cnn.weight", 3, C[0], 3, 3);
         GETW(b, "cnn.bias", 3);
-        if (!(cnn.b = rv_copy(b, 3, wts, st))) return 1;
+        if (!(cnn.b = copy_f32(b->data, 3, wts, st))) return 1;
         if (rv_pack_conv(w->data, 3, C[0], 9, ldl(0), nullptr, wts, st, &cnn)) return 1;
     }
     {   // GRU: the reference's feature index is c * W + bin, the head conv's rows are [bin][4] (channel 3 = zero)
@@ -542,7 +524,7 @@ int svc_rmvpe::pack(const StateDict& sd, const float* mel_basis, hipStream_t st)
     {
         GETW(w, "fc.1.weight", cfg.n_bins, 2 * Hd);
         GETW(b, "fc.1.bias", cfg.n_bins);
-        if (!(fc.b = rv_copy(b, cfg.n_bins, wts, st))) return 1;
+        if (!(fc.b = copy_f32(b->data, cfg.n_bins, wts, st))) return 1;
         fc.N = cfg.n_bins; fc.ldw = 2 * Hd;
         fc.w = wts.alloc_n<float>((size_t)round_up(cfg.n_bins, 128) * fc.ldw, st);
         if (!fc.w) return 1;
@@ -651,7 +633,7 @@ int svc_rmvpe::salience_group(const float* mel, int Tm, const Rows& fr, int B, i
     const int W = cfg.n_mels, Hd = cfg.gru_hidden;
     int H = 0;
     for (int b = 0; b < B; ++b) H = std::max(H, (fr.n[b] + RV_TMULT - 1) / RV_TMULT * RV_TMULT);
-    if (reserve(B, H, st) || mark(0, st)) return 1;
+    if (reserve(B, H, st) || tm.mark(0, st)) return 1;
     hipLaunchKernelGGL(rv_input_kernel, dim3(cdiv((long)B * (H + 2) * W, 256)), dim3(256), 0, st, mel, Tm, pin[0].p, fr, B, H, W, in_s, in_h);
     SVC_CHECK_HIP(hipGetLastError());
     const float* x = pin[0].p;
@@ -688,20 +670,20 @@ int svc_rmvpe::salience_group(const float* mel, int Tm, const Rows& fr, int B, i
         SVC_CHECK_HIP(hipGetLastError());
         if (run_blocks(dec[d], pk[l].p, 2 * c, l, nullptr, 0, fr, B, H, &x, st)) return 1;
     }
-    if (conv(cnn, x, ldl(0), cnn_out, 4, 0, 9, nullptr, 0, KG_ACT_NONE, false, fr, B, H, st) || mark(1, st)) return 1;
+    if (conv(cnn, x, ldl(0), cnn_out, 4, 0, 9, nullptr, 0, KG_ACT_NONE, false, fr, B, H, st) || tm.mark(1, st)) return 1;
     {   // GRU input projection, all frames and both directions: rows 1 .. H of every clip, K = [bin][4]
         Gemm g((long)B * H, 6 * Hd, H);
         g.p.a_seq_rows = H + 2; g.p.a_off = 1; g.p.a_len = H;
         g.p.a_ptr[0] = cnn_out; g.p.a_ld[0] = 4L * W; g.p.a_ktiles[0] = 4 * W / 32;
         g.p.w = gru_in.w; g.p.ldw = gru_in.ldw; g.p.bias = gru_in.b;
         g.p.c32 = xp; g.p.ldc32 = 6 * Hd;
-        if (g.run(st) || mark(2, st)) return 1;
+        if (g.run(st) || tm.mark(2, st)) return 1;
     }
     if (B >= 4) hipLaunchKernelGGL(rv_gru_kernel<4>, dim3(cdiv(B, 4), 2), dim3(Hd), 0, st, xp, w_hh4, b_hh, gru_out, fr, B, H, Hd);
     else if (B >= 2) hipLaunchKernelGGL(rv_gru_kernel<2>, dim3(cdiv(B, 2), 2), dim3(Hd), 0, st, xp, w_hh4, b_hh, gru_out, fr, B, H, Hd);
     else hipLaunchKernelGGL(rv_gru_kernel<1>, dim3(1, 2), dim3(Hd), 0, st, xp, w_hh4, b_hh, gru_out, fr, B, H, Hd);
     SVC_CHECK_HIP(hipGetLastError());
-    if (mark(3, st)) return 1;
+    if (tm.mark(3, st)) return 1;
     {   // fc.1 + sigmoid, cropped to the caller's T frames.  Rows [Tpad_b, T) of a shorter clip hold whatever an earlier call left in
         // gru_out (finite: the workspace starts as zero and only results are ever stored): a GEMM row depends on nothing but its
         // own input row, and rv_zero_rows_kernel overwrites every row at and above T_b, so none of it reaches a result
@@ -714,7 +696,7 @@ int svc_rmvpe::salience_group(const float* mel, int Tm, const Rows& fr, int B, i
     }
     hipLaunchKernelGGL(rv_zero_rows_kernel, dim3(cdiv((long)B * T * cfg.n_bins, 256)), dim3(256), 0, st, out, fr, B, T, cfg.n_bins);
     SVC_CHECK_HIP(hipGetLastError());
-    return mark(4, st);
+    return tm.mark(4, st);
 }
 
 // clips in groups that keep one level-0 plane inside plane_budget; a row's bits do not depend on its group
@@ -829,15 +811,14 @@ int svc_rmvpe_set_plane_budget(svc_rmvpe_t* m, long long bytes) {
 
 int svc_rmvpe_set_timing(svc_rmvpe_t* m, int on) {
     SVC_REQUIRE(m, "svc_rmvpe_set_timing: null handle");
-    m->timing = on != 0;
+    m->tm.on = on != 0;
     return 0;
 }
 
 int svc_rmvpe_last_timing(svc_rmvpe_t* m, float* ms4) {
-    SVC_REQUIRE(m && ms4 && m->timing && m->ev[4], "svc_rmvpe_last_timing: timing is off or no call was made");
-    SVC_CHECK_HIP(hipEventSynchronize(m->ev[4]));
-    for (int i = 0; i < 4; ++i) SVC_CHECK_HIP(hipEventElapsedTime(&ms4[i], m->ev[i], m->ev[i + 1]));
-    return 0;
+    const char* msg = "svc_rmvpe_last_timing: timing is off or no call was made";
+    SVC_REQUIRE(m, msg);
+    return m->tm.last(ms4, msg);
 }
 
 int svc_rmvpe_mel(svc_rmvpe_t* m, const float* wave, const int32_t* lens, int B, int L, float* mel_out, void* stream) {

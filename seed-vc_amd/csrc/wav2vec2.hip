@@ -2,46 +2,32 @@
 // transformer, grouped positional conv): 16 kHz audio -> content features at 50 rows/s (`semantic_fn` of the reference drivers for
 // the xlsr models: Wav2Vec2FeatureExtractor + the first layers of facebook/wav2vec2-xls-r-300m in float16).
 //
-// Stages.  Normalisation: per window (x - mean) / sqrt(var + 1e-7), mean first, then the variance about it, both from 64 block
-// partials folded in a fixed order (double accumulation, no atomics).  Extractor: conv0 (1 -> C) fused with its LayerNorm and
-// erf-GELU in one row kernel (one wave per output row, the raw 3200 rows/s x C plane is never written), convs 1..n-1 as 2- and
-// 3-tap tap-GEMMs on channels-last rows (stride in the row map, no padding) each followed by the LayerNorm+GELU row kernel, the
-// last of which also applies the feature projection's LayerNorm; then Linear C -> D.  Positional conv: a grouped Conv1d of k taps
-// as a Toeplitz product per (group, 64-position tile, window), input rows resident in LDS (w2v_posconv_kernel); precision 0 runs
-// it on the fp32 tap-GEMM, one accumulating launch per group and 48 taps.  Encoder: pre-LN blocks on the tap-GEMM and the
-// attention kernel with per-window key counts, then encoder.layer_norm.  Residual stream, LayerNorm statistics and softmax are
-// fp32.  Windows of long clips travel as a table in kernel arguments, exactly as in whisper.hip; every window is computed as if
-// alone (row-local kernels, per-element k order in the GEMMs, tile-independent tap order in the positional conv, pinned attention
-// form), so its bits do not depend on its companions, their order or the group size.
+// Normalisation: per window (x - mean) / sqrt(var + 1e-7), mean first, then the variance about it, both from 64 block partials
+// folded in a fixed order (double accumulation, no atomics).  Extractor: conv0 (1 -> C) fused with its LayerNorm and erf-GELU in
+// one row kernel (one wave per output row, the raw 3200 rows/s x C plane is never written), convs 1..n-1 as 2- and 3-tap
+// tap-GEMMs on channels-last rows (stride in the row map, no padding) each followed by the LayerNorm+GELU row kernel, the last of
+// which also applies the feature projection's LayerNorm; then Linear C -> D.  Positional conv: a grouped Conv1d of k taps as a
+// Toeplitz product per (group, 64-position tile, window), input rows resident in LDS (w2v_posconv_kernel); precision 0 runs it on
+// the fp32 tap-GEMM, one accumulating launch per group and 48 taps.  The transformer stack (with per-window key counts), the
+// window plan of long clips and the row gather are content_encoder.h's.  Every window is computed as if alone (tile-independent
+// tap order in the positional conv), so its bits do not depend on its companions, their order or the group size.
 #include <math.h>
 #include <string.h>
 
-#include <algorithm>
-#include <string>
-#include <vector>
-
-#include "model_util.h"
+#include "content_encoder.h"
 
 using namespace svc;
 
 namespace {
 
-constexpr int WV_MAX_WIN = 64, WV_MAX_B = 64, WV_NBLK = 64, WV_DEFAULT_GROUP = 16, WV_MAX_CONV = 8, WV_SPR = 320;
+constexpr int WV_MAX_B = 64, WV_NBLK = 64, WV_DEFAULT_GROUP = 16, WV_MAX_CONV = 8;
 constexpr int WV_PC_BM = 64, WV_PC_MAXK = 128, WV_PC_AHEAD = 4;    // positional conv: positions per workgroup, most taps, taps of weights in flight
-constexpr float WV_QSCALE = 0.125f * 1.4426950408889634f;     // 1 / sqrt(64), and the attention kernel's exp2
+constexpr StackNames WV_NAMES = {"encoder.layers.", "attention.q_proj", "attention.k_proj", "attention.k_proj.bias", "attention.v_proj",
+                                 "attention.out_proj", "layer_norm", "feed_forward.intermediate_dense", "feed_forward.output_dense",
+                                 "final_layer_norm", "encoder.layer_norm"};
 
-struct WinTab {                                   // one group of windows as a kernel argument
-    int clip[WV_MAX_WIN], start[WV_MAX_WIN], n[WV_MAX_WIN];           // source clip, first sample, samples
-    int dst0[WV_MAX_WIN], drop[WV_MAX_WIN], keep[WV_MAX_WIN];         // assemble: rows [drop, keep) go to out[clip][dst0 ...]
-    int zero_from[WV_MAX_WIN];                                        // last window of its clip: the clip's row count; else -1
-};
-struct LenTab { int v[WV_MAX_CONV + 1][WV_MAX_WIN]; };                // samples, then rows after each conv, per window
+struct LenTab { int v[WV_MAX_CONV + 1][MAX_WIN]; };                // samples, then rows after each conv, per window
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 __device__ __forceinline__ double wave_sum_d(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -50,8 +36,8 @@ __device__ __forceinline__ double wave_sum_d(double v) {
 
 __global__ void wv_lens_kernel(LenTab lt, int* __restrict__ dst, int n_rows) {
     const int i = threadIdx.x;
-    if (i < WV_MAX_WIN)
-        for (int r = 0; r < n_rows; ++r) dst[r * WV_MAX_WIN + i] = lt.v[r][i];
+    if (i < MAX_WIN)
+        for (int r = 0; r < n_rows; ++r) dst[r * MAX_WIN + i] = lt.v[r][i];
 }
 
 // part[g][blk] = sum over the block's share of window g of (x - sub)^POW, sub = 0 (POW 1) or the window's mean (POW 2): the
@@ -97,57 +83,6 @@ __global__ void wv_norm_kernel(const float* __restrict__ wave, WinTab wt, long L
     dst[(long)g * stride + i] = (float)((double)wave[(long)wt.clip[g] * Lrow + wt.start[g] + i] - mean) * rstd;
 }
 
-// LayerNorm statistics of a row held by one wave (v[i] = channel lane + 64 i): mean, then the variance about it
-template <int NMAX>
-__device__ __forceinline__ void wv_row_norm(float (&v)[NMAX], int n, int D, float eps, const float* __restrict__ gamma, const float* __restrict__ beta,
-                                            int lane, bool gelu) {
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < NMAX; ++i)
-        if (i < n) s += v[i];
-    const float mean = wave_sum(s) / (float)D;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < NMAX; ++i)
-        if (i < n) { const float d = v[i] - mean; q = fmaf(d, d, q); }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)D + eps);
-#pragma unroll
-    for (int i = 0; i < NMAX; ++i)
-        if (i < n) {
-            const int c = lane + 64 * i;
-            const float o = (v[i] - mean) * rstd * gamma[c] + beta[c];
-            v[i] = gelu ? gelu_erf(o) : o;
-        }
-}
-
-// Row kernel of the extractor and the encoder, one wave per row.  MODE 0: LayerNorm; 1: LayerNorm, erf-GELU; 2: LayerNorm, erf-GELU,
-// then a second LayerNorm (gamma2, beta2: the feature projection's).  Rows at and above lens[seq] (seq = row / seq_rows) are
-// neither read nor written; lens may be null.
-template <int MODE>
-__global__ __launch_bounds__(256) void wv_rownorm_kernel(const float* __restrict__ x, long ldx, float* __restrict__ y32, half_t* __restrict__ y16,
-                                                         long ldy, const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                         const float* __restrict__ gamma2, const float* __restrict__ beta2, long rows, int D,
-                                                         float eps, const int* __restrict__ lens, int seq_rows) {
-    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63, n = D / 64;
-    if (row >= rows) return;
-    if (lens && (int)(row % seq_rows) >= lens[row / seq_rows]) return;
-    const float* xr = x + row * ldx;
-    float v[32];
-#pragma unroll
-    for (int i = 0; i < 32; ++i)
-        if (i < n) v[i] = xr[lane + 64 * i];
-    wv_row_norm<32>(v, n, D, eps, gamma, beta, lane, MODE >= 1);
-    if (MODE == 2) wv_row_norm<32>(v, n, D, eps, gamma2, beta2, lane, false);
-#pragma unroll
-    for (int i = 0; i < 32; ++i)
-        if (i < n) {
-            const int c = lane + 64 * i;
-            if (y32) y32[row * ldy + c] = v[i];
-            if (y16) y16[row * ldy + c] = (half_t)v[i];
-        }
-}
-
 // conv0 (1 -> C channels, k0 taps, stride s0, bias) + LayerNorm(C) + erf-GELU: one wave per output row, weights [k0][C] in LDS
 __global__ __launch_bounds__(256) void wv_conv0_kernel(const float* __restrict__ wn, long stride, const float* __restrict__ w /*[k0][C]*/,
                                                        const float* __restrict__ bias, const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -169,7 +104,7 @@ __global__ __launch_bounds__(256) void wv_conv0_kernel(const float* __restrict__
             for (int i = 0; i < 8; ++i)
                 if (i < n) v[i] = fmaf(xv, w_s[t * C + lane + 64 * i], v[i]);
         }
-        wv_row_norm<8>(v, n, C, eps, gamma, beta, lane, true);
+        row_norm<8>(v, n, C, eps, gamma, beta, lane, true);
         const long o = ((long)g * L0 + row) * C;
 #pragma unroll
         for (int i = 0; i < 8; ++i)
@@ -286,23 +221,6 @@ __global__ void wv_pack_pos_kernel(const float* __restrict__ v, const float* __r
     if (w32) w32[((long)no * k + t) * 64 + c] = val;
 }
 
-// V columns of qkv [G * P][3 D] (fp16) -> vt [G][D][vt_ld] in the attention's column order; columns at and above the window's rows are zero
-__global__ __launch_bounds__(256) void wv_vt_kernel(const half_t* __restrict__ qkv, half_t* __restrict__ vt, const int* __restrict__ lens, int P, int D,
-                                                    long vt_ld, int mode) {
-    __shared__ half_t tile[32][34];
-    const int g = blockIdx.z, p0 = blockIdx.x * 32, d0 = blockIdx.y * 32, T = lens[g];
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    for (int i = ty; i < 32; i += 8) {
-        const int p = p0 + i;
-        tile[i][tx] = p < T ? qkv[((long)g * P + p) * 3 * D + 2 * D + d0 + tx] : (half_t)0.f;
-    }
-    __syncthreads();
-    for (int i = ty; i < 32; i += 8) {
-        const int p = p0 + tx;
-        if (p < vt_ld) vt[((long)g * D + d0 + i) * vt_ld + vt_pos(p, mode)] = tile[tx][i];
-    }
-}
-
 // src [G][P][D] rows below lens[g] -> dst [G][T][D]; the other rows of dst are not touched
 __global__ void wv_copy_rows_kernel(const float* __restrict__ src, int P, float* __restrict__ dst, int T, const int* __restrict__ lens, int D) {
     const int g = blockIdx.y, r = blockIdx.x;
@@ -311,34 +229,6 @@ __global__ void wv_copy_rows_kernel(const float* __restrict__ src, int P, float*
     float4* d = reinterpret_cast<float4*>(dst + ((long)g * T + r) * D);
     for (int i = threadIdx.x; i < D / 4; i += blockDim.x) d[i] = s[i];
 }
-
-// enc [G][P][D] -> out [B][Rmax][D]: block (r, g).  r < P: row r of window g, when kept, goes to its place in the clip's rows;
-// r >= P: row r - P of the clip is zeroed when window g is the clip's last and the row is at or above the clip's count
-__global__ void wv_assemble_kernel(const float* __restrict__ enc, WinTab wt, float* __restrict__ out, int P, int D, int Rmax) {
-    const int g = blockIdx.y, r = blockIdx.x;
-    float4* dst = nullptr;
-    const float4* src = nullptr;
-    if (r < P) {
-        if (r < wt.drop[g] || r >= wt.keep[g]) return;
-        dst = reinterpret_cast<float4*>(out + ((long)wt.clip[g] * Rmax + wt.dst0[g] + r - wt.drop[g]) * D);
-        src = reinterpret_cast<const float4*>(enc + ((long)g * P + r) * D);
-    } else {
-        const int z = r - P;
-        if (wt.zero_from[g] < 0 || z < wt.zero_from[g]) return;
-        dst = reinterpret_cast<float4*>(out + ((long)wt.clip[g] * Rmax + z) * D);
-    }
-    for (int i = threadIdx.x; i < D / 4; i += blockDim.x) dst[i] = src ? src[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-}
-
-KGemmParams wv_gemm(long M, int N, int Lout) {
-    KGemmParams p;
-    memset(&p, 0, sizeof(p));
-    p.M = (int)M; p.N = N; p.Lout = Lout; p.a_seq_rows = Lout; p.c_seq_rows = Lout; p.a_stride = 1; p.a_len = Lout; p.n_taps = 1;
-    p.vec_ok = 1;
-    return p;
-}
-
-long wv_n_windows(long W, long O, long n) { return n <= W ? 1 : 1 + (n - W + (W - O) - 1) / (W - O); }
 
 long wv_frames(const svc_w2v_config_t& c, long n, int upto = WV_MAX_CONV) {
     for (int l = 0; l < c.n_conv && l < upto; ++l) n = n >= c.conv_kernel[l] ? (n - c.conv_kernel[l]) / c.conv_stride[l] + 1 : 0;
@@ -353,9 +243,9 @@ int wv_check_cfg(const svc_w2v_config_t* c, const char* who) {
         if (c->conv_kernel[l] < 1 || c->conv_stride[l] < 1 || c->conv_kernel[l] > (l ? 8 : 64)) return bad("conv_kernel / conv_stride out of range");
     long hop = 1;
     for (int l = 0; l < c->n_conv; ++l) hop *= c->conv_stride[l];
-    if (hop != WV_SPR) return bad("the conv strides must multiply to 320 samples per row (the drivers' window plan counts rows of 320 samples)");
+    if (hop != SAMPLES_PER_ROW) return bad("the conv strides must multiply to 320 samples per row (the drivers' window plan counts rows of 320 samples)");
     if ((long)c->conv_kernel[0] * c->conv_dim > 8192) return bad("conv_kernel[0] * conv_dim must not exceed 8192 (conv0 keeps its weights in 32 KB of LDS)");
-    if (c->window_samples < WV_SPR || c->window_samples % WV_SPR) return bad("window_samples must be a positive multiple of 320");
+    if (c->window_samples < SAMPLES_PER_ROW || c->window_samples % SAMPLES_PER_ROW) return bad("window_samples must be a positive multiple of 320");
     if (wv_frames(*c, c->window_samples) < 1) return bad("window_samples is shorter than the extractor's receptive field");
     return 0;
 }
@@ -365,43 +255,26 @@ int wv_check_cfg(const svc_w2v_config_t* c, const char* who) {
 struct svc_w2v {
     svc_w2v_config_t cfg;
     int dt = 0;                      // tap-GEMM dtype of the convs and linears: 0 fp16 (precision 1), 1 fp32 (precision 0)
-    int group = WV_DEFAULT_GROUP, qt_form = 1;
+    int group = WV_DEFAULT_GROUP;
     Arena wts, ws_fe, ws_enc;
-    struct Lin { void* w = nullptr; float* b = nullptr; long ldw = 0; int N = 0; };
-    struct Layer { Lin qkv, o, fc1, fc2; float *g1 = nullptr, *b1 = nullptr, *g2 = nullptr, *b2 = nullptr; };
     float* w0 = nullptr; float* b0 = nullptr;                           // conv0 [k0][C], bias
     Lin conv[WV_MAX_CONV], proj;
-    float *cg[WV_MAX_CONV] = {}, *cb[WV_MAX_CONV] = {}, *pg = nullptr, *pb = nullptr, *gf = nullptr, *bf = nullptr;
+    float *cg[WV_MAX_CONV] = {}, *cb[WV_MAX_CONV] = {}, *pg = nullptr, *pb = nullptr;
     half_t* pos16 = nullptr; float* pos32 = nullptr; float* posb = nullptr;
-    std::vector<Layer> layers;
+    EncoderStack stack;
     // extractor workspace for cap_g windows of cap_n samples; encoder workspace for ecap_g windows of ecap_p rows
     int cap_g = 0; long cap_n = 0; int ecap_g = 0, ecap_p = 0;
     int Ls[WV_MAX_CONV + 1] = {};    // row strides of the stage buffers of the current call (its longest window)
     long nstride = 0;
     float* wn = nullptr; double* part = nullptr; int* dlens = nullptr;
     void *actA = nullptr, *actB = nullptr; float* raw = nullptr;
-    float *h32 = nullptr, *x = nullptr, *n32 = nullptr, *ao32 = nullptr, *ff32 = nullptr, *enc = nullptr, *acc32 = nullptr;
-    half_t *h16 = nullptr, *n16 = nullptr, *qkv16 = nullptr, *vt = nullptr, *ao16 = nullptr, *ff16 = nullptr;
-    long vt_ld = 0;
-    bool timing = false;
-    hipEvent_t ev[5] = {};
-    ~svc_w2v() {
-        for (auto& e : ev) if (e) (void)hipEventDestroy(e);
-    }
-    int mark(int i, hipStream_t st) {
-        if (!timing) return 0;
-        if (!ev[i]) SVC_CHECK_HIP(hipEventCreate(&ev[i]));
-        SVC_CHECK_HIP(hipEventRecord(ev[i], st));
-        return 0;
-    }
-    int pack_lin(const float* w, const float* bias, int N, int K, const float* scale, Lin* out, hipStream_t st);
+    float *h32 = nullptr, *enc = nullptr, *acc32 = nullptr;
+    half_t* h16 = nullptr;
+    StageTimer tm;
     int pack(const StateDict& sd, const std::string& pre, hipStream_t st);
     int reserve_fe(int G, long nmax, hipStream_t st);
     int reserve_enc(int G, int P, hipStream_t st);
     int put_lens(const LenTab& lt, hipStream_t st);
-    int lin(const Lin& l, const void* a, long K, long M, int Lout, int act, const float* res, float* c32, half_t* c16, hipStream_t st);
-    int rownorm(int mode, const float* x, long ldx, float* y32, half_t* y16, long ldy, const float* g, const float* b, const float* g2, const float* b2,
-                long rows, int D, const int* lens, int seq_rows, hipStream_t st);
     int normalize_group(const float* wave, long Lrow, const WinTab& wt, int G, float* dst, long stride, hipStream_t st);
     int features_group(const float* wnorm, long stride, int G, hipStream_t st);            // -> h32 (+ h16) [G][Ls[n_conv]][D]
     int posconv_group(const float* h, const half_t* h16v, int G, int P, float* out, hipStream_t st);
@@ -409,23 +282,6 @@ struct svc_w2v {
 };
 
 namespace {
-
-float* wv_copy(const float* src, long n, Arena& ar, hipStream_t st) {
-    float* p = ar.alloc_n<float>(round_up(n, 8), st);
-    if (!p) return nullptr;
-    if (hipMemcpyAsync(p, src, (size_t)n * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) { set_error("weight copy failed"); return nullptr; }
-    return p;
-}
-
-int wv_require(const svc_tensor_desc_t* d, const std::string& name, const std::vector<long>& shp) {
-    if (!d) { set_error("svc_w2v_create: state_dict is missing " + name); return 1; }
-    bool ok = d->ndim == (int)shp.size();
-    for (size_t i = 0; ok && i < shp.size(); ++i) ok = d->shape[i] == shp[i];
-    if (!ok) { set_error("svc_w2v_create: shape mismatch for " + name); return 1; }
-    return 0;
-}
-
-struct KeyShape { std::string name; std::vector<long> shape; };
 
 std::vector<KeyShape> wv_keys(const svc_w2v_config_t& c) {
     const long D = c.d_model, F = c.ffn_dim, C = c.conv_dim;
@@ -442,40 +298,14 @@ std::vector<KeyShape> wv_keys(const svc_w2v_config_t& c) {
     k.push_back({"feature_projection.projection.weight", {D, C}});
     k.push_back({"feature_projection.projection.bias", {D}});
     k.push_back({"encoder.pos_conv_embed.conv.bias", {D}});
-    k.push_back({"encoder.layer_norm.weight", {D}});
-    k.push_back({"encoder.layer_norm.bias", {D}});
-    for (int i = 0; i < c.n_layers; ++i) {
-        const std::string p = "encoder.layers." + std::to_string(i) + ".";
-        for (const char* n : {"k_proj", "v_proj", "q_proj", "out_proj"}) {
-            k.push_back({p + "attention." + n + ".weight", {D, D}});
-            k.push_back({p + "attention." + n + ".bias", {D}});
-        }
-        k.push_back({p + "layer_norm.weight", {D}});
-        k.push_back({p + "layer_norm.bias", {D}});
-        k.push_back({p + "feed_forward.intermediate_dense.weight", {F, D}});
-        k.push_back({p + "feed_forward.intermediate_dense.bias", {F}});
-        k.push_back({p + "feed_forward.output_dense.weight", {D, F}});
-        k.push_back({p + "feed_forward.output_dense.bias", {D}});
-        k.push_back({p + "final_layer_norm.weight", {D}});
-        k.push_back({p + "final_layer_norm.bias", {D}});
-    }
+    EncoderStack::keys(WV_NAMES, c.n_layers, D, F, k);
     return k;
 }
 
 }  // namespace
 
-// nn.Linear weight [N][K] -> [Npad128][K] in the GEMM's dtype, rows optionally scaled
-int svc_w2v::pack_lin(const float* w, const float* bias, int N, int K, const float* scale, Lin* out, hipStream_t st) {
-    out->N = N; out->ldw = K;
-    out->w = wts.alloc((size_t)round_up(N, 128) * K * esize(dt), st);
-    if (!out->w) return 1;
-    if (pack_any(dt, w, out->w, 0, N, 1, K, K, 0, 1, K, 0, 1, scale, st)) return 1;
-    if (bias && !(out->b = wv_copy(bias, N, wts, st))) return 1;
-    return 0;
-}
-
 int svc_w2v::pack(const StateDict& sd, const std::string& pre, hipStream_t st) {
-    const int D = cfg.d_model, F = cfg.ffn_dim, C = cfg.conv_dim, k = cfg.pos_k;
+    const int D = cfg.d_model, C = cfg.conv_dim, k = cfg.pos_k;
     auto get = [&](const std::string& key) { return sd.get(pre + key)->data; };       // every key was checked by the caller
     const std::string fe = "feature_extractor.conv_layers.";
     for (int l = 0; l < cfg.n_conv; ++l) {
@@ -484,7 +314,7 @@ int svc_w2v::pack(const StateDict& sd, const std::string& pre, hipStream_t st) {
         if (l == 0) {   // [C][1][k0] -> [k0][C] fp32
             w0 = wts.alloc_n<float>((size_t)kl * C, st);
             if (!w0 || pack_f32_launch(get(p + "conv.weight"), w0, kl, C, 1, 1, kl, 0, C, 1, 0, nullptr, st)) return 1;
-            if (!(b0 = wv_copy(get(p + "conv.bias"), C, wts, st))) return 1;
+            if (!(b0 = copy_f32(get(p + "conv.bias"), C, wts, st))) return 1;
         } else {        // [C][C][kl] -> [Cpad128][kl * C], tap-major
             Lin& c = conv[l];
             c.N = C; c.ldw = (long)kl * C;
@@ -492,13 +322,13 @@ int svc_w2v::pack(const StateDict& sd, const std::string& pre, hipStream_t st) {
             if (!c.w) return 1;
             for (int t = 0; t < kl; ++t)
                 if (pack_any(dt, get(p + "conv.weight") + t, c.w, (long)t * C, C, C, 1, (long)kl * C, kl, 0, c.ldw, 1, 0, nullptr, st)) return 1;
-            if (!(c.b = wv_copy(get(p + "conv.bias"), C, wts, st))) return 1;
+            if (!(c.b = copy_f32(get(p + "conv.bias"), C, wts, st))) return 1;
         }
-        if (!(cg[l] = wv_copy(get(p + "layer_norm.weight"), C, wts, st)) || !(cb[l] = wv_copy(get(p + "layer_norm.bias"), C, wts, st))) return 1;
+        if (!(cg[l] = copy_f32(get(p + "layer_norm.weight"), C, wts, st)) || !(cb[l] = copy_f32(get(p + "layer_norm.bias"), C, wts, st))) return 1;
     }
-    if (!(pg = wv_copy(get("feature_projection.layer_norm.weight"), C, wts, st)) || !(pb = wv_copy(get("feature_projection.layer_norm.bias"), C, wts, st)))
+    if (!(pg = copy_f32(get("feature_projection.layer_norm.weight"), C, wts, st)) || !(pb = copy_f32(get("feature_projection.layer_norm.bias"), C, wts, st)))
         return 1;
-    if (pack_lin(get("feature_projection.projection.weight"), get("feature_projection.projection.bias"), D, C, nullptr, &proj, st)) return 1;
+    if (pack_lin(dt, wts, get("feature_projection.projection.weight"), get("feature_projection.projection.bias"), D, C, nullptr, &proj, st)) return 1;
     {   // positional conv: weight norm (per tap, over dims 0 and 1) folded here
         const std::string pc = pre + "encoder.pos_conv_embed.conv.";
         const float *v = nullptr, *g = nullptr;
@@ -516,40 +346,11 @@ int svc_w2v::pack(const StateDict& sd, const std::string& pre, hipStream_t st) {
         else if (!(pos32 = wts.alloc_n<float>(nw + (size_t)128 * k * 64, st))) return 1;      // slack: the tap-GEMM stages whole weight tiles
         hipLaunchKernelGGL(wv_pack_pos_kernel, dim3(cdiv((long)nw, 256)), dim3(256), 0, st, v, sc, D, k, pos16, pos32);
         SVC_CHECK_HIP(hipGetLastError());
-        if (!(posb = wv_copy(get("encoder.pos_conv_embed.conv.bias"), D, wts, st))) return 1;
+        if (!(posb = copy_f32(get("encoder.pos_conv_embed.conv.bias"), D, wts, st))) return 1;
     }
-    float* qs = wts.alloc_n<float>(D, st);
-    if (!qs) return 1;
-    {
-        std::vector<float> h(D, WV_QSCALE);
-        SVC_CHECK_HIP(hipMemcpyAsync(qs, h.data(), (size_t)D * 4, hipMemcpyHostToDevice, st));
-        SVC_CHECK_HIP(hipStreamSynchronize(st));
-    }
-    layers.resize(cfg.n_layers);
-    for (int i = 0; i < cfg.n_layers; ++i) {
-        Layer& ly = layers[i];
-        const std::string p = "encoder.layers." + std::to_string(i) + ".";
-        // q | k | v rows of one [3 D][D] weight; the q rows and bias carry 1 / 8 and log2(e)
-        ly.qkv.N = 3 * D; ly.qkv.ldw = D;
-        ly.qkv.w = wts.alloc((size_t)round_up(3 * D, 128) * D * esize(dt), st);
-        ly.qkv.b = wts.alloc_n<float>(3 * D, st);
-        if (!ly.qkv.w || !ly.qkv.b) return 1;
-        if (pack_any(dt, get(p + "attention.q_proj.weight"), ly.qkv.w, 0, D, 1, D, D, 0, 1, D, 0, 1, qs, st)) return 1;
-        if (pack_any(dt, get(p + "attention.k_proj.weight"), ly.qkv.w, (long)D * D, D, 1, D, D, 0, 1, D, 0, 1, nullptr, st)) return 1;
-        if (pack_any(dt, get(p + "attention.v_proj.weight"), ly.qkv.w, 2L * D * D, D, 1, D, D, 0, 1, D, 0, 1, nullptr, st)) return 1;
-        if (pack_f32_launch(get(p + "attention.q_proj.bias"), ly.qkv.b, D, 1, 1, 1, 0, 0, 1, 0, 0, qs, st)) return 1;
-        SVC_CHECK_HIP(hipMemcpyAsync(ly.qkv.b + D, get(p + "attention.k_proj.bias"), (size_t)D * 4, hipMemcpyDeviceToDevice, st));
-        SVC_CHECK_HIP(hipMemcpyAsync(ly.qkv.b + 2 * D, get(p + "attention.v_proj.bias"), (size_t)D * 4, hipMemcpyDeviceToDevice, st));
-        if (pack_lin(get(p + "attention.out_proj.weight"), get(p + "attention.out_proj.bias"), D, D, nullptr, &ly.o, st)) return 1;
-        if (pack_lin(get(p + "feed_forward.intermediate_dense.weight"), get(p + "feed_forward.intermediate_dense.bias"), F, D, nullptr, &ly.fc1, st)) return 1;
-        if (pack_lin(get(p + "feed_forward.output_dense.weight"), get(p + "feed_forward.output_dense.bias"), D, F, nullptr, &ly.fc2, st)) return 1;
-        if (!(ly.g1 = wv_copy(get(p + "layer_norm.weight"), D, wts, st)) || !(ly.b1 = wv_copy(get(p + "layer_norm.bias"), D, wts, st)) ||
-            !(ly.g2 = wv_copy(get(p + "final_layer_norm.weight"), D, wts, st)) || !(ly.b2 = wv_copy(get(p + "final_layer_norm.bias"), D, wts, st)))
-            return 1;
-    }
-    if (!(gf = wv_copy(get("encoder.layer_norm.weight"), D, wts, st)) || !(bf = wv_copy(get("encoder.layer_norm.bias"), D, wts, st))) return 1;
-    if (!(dlens = wts.alloc_n<int>((size_t)(WV_MAX_CONV + 1) * WV_MAX_WIN, st))) return 1;
-    if (!(part = wts.alloc_n<double>((size_t)2 * WV_MAX_WIN * WV_NBLK, st))) return 1;
+    if (stack.pack(sd, pre, WV_NAMES, cfg.n_layers, wts, st)) return 1;
+    if (!(dlens = wts.alloc_n<int>((size_t)(WV_MAX_CONV + 1) * MAX_WIN, st))) return 1;
+    if (!(part = wts.alloc_n<double>((size_t)2 * MAX_WIN * WV_NBLK, st))) return 1;
     SVC_CHECK_HIP(hipStreamSynchronize(st));
     return 0;
 }
@@ -584,28 +385,12 @@ int svc_w2v::reserve_enc(int G, int P, hipStream_t st) {
     SVC_CHECK_HIP(hipStreamSynchronize(st));
     ws_enc.release();
     ecap_g = 0; ecap_p = 0;
-    const long D = cfg.d_model, F = cfg.ffn_dim, MP = (long)G * P;
-    SVC_REQUIRE(MP * std::max(3 * D, F) < (1L << 31), "w2v: the window group is too large for 32-bit row offsets");
-    const long vld = round_up(P, 64);
+    const long D = cfg.d_model, MP = (long)G * P;
     h32 = ws_enc.alloc_n<float>((size_t)MP * D, st);
-    x = ws_enc.alloc_n<float>((size_t)MP * D, st);
     enc = ws_enc.alloc_n<float>((size_t)MP * D, st);
-    qkv16 = ws_enc.alloc_n<half_t>((size_t)MP * 3 * D, st);
-    vt = ws_enc.alloc_n<half_t>((size_t)G * D * vld, st);
-    ao16 = ws_enc.alloc_n<half_t>((size_t)MP * D, st);
-    if (!h32 || !x || !enc || !qkv16 || !vt || !ao16) return 1;
-    if (dt == 0) {
-        h16 = ws_enc.alloc_n<half_t>((size_t)MP * D, st);
-        n16 = ws_enc.alloc_n<half_t>((size_t)MP * D, st);
-        ff16 = ws_enc.alloc_n<half_t>((size_t)MP * F, st);
-        if (!h16 || !n16 || !ff16) return 1;
-    } else {
-        n32 = ws_enc.alloc_n<float>((size_t)MP * D, st);
-        ao32 = ws_enc.alloc_n<float>((size_t)MP * D, st);
-        ff32 = ws_enc.alloc_n<float>((size_t)MP * F, st);
-        acc32 = ws_enc.alloc_n<float>((size_t)MP * D, st);
-        if (!n32 || !ao32 || !ff32 || !acc32) return 1;
-    }
+    if (!h32 || !enc || stack.reserve(ws_enc, G, P, st)) return 1;
+    if (dt == 0 && !(h16 = ws_enc.alloc_n<half_t>((size_t)MP * D, st))) return 1;
+    if (dt == 1 && !(acc32 = ws_enc.alloc_n<float>((size_t)MP * D, st))) return 1;
     SVC_CHECK_HIP(hipStreamSynchronize(st));
     ecap_g = G; ecap_p = P;
     return 0;
@@ -617,32 +402,10 @@ int svc_w2v::put_lens(const LenTab& lt, hipStream_t st) {
     return 0;
 }
 
-// c = act(a [M][K] W^T + b) (+ res): fp32 and / or fp16 out, leading dimension N
-int svc_w2v::lin(const Lin& l, const void* a, long K, long M, int Lout, int act, const float* res, float* c32, half_t* c16, hipStream_t st) {
-    KGemmParams p = wv_gemm(M, l.N, Lout);
-    p.a_ptr[0] = a; p.a_ld[0] = K; p.a_ktiles[0] = (int)(K / ktile_elems(dt));
-    p.w = l.w; p.ldw = l.ldw; p.bias = l.b; p.act = act;
-    p.res = res; p.ldres = l.N;
-    p.c32 = c32; p.ldc32 = l.N; p.c16 = c16; p.ldc16 = l.N;
-    return kgemm_launch(p, dt, KG_EPI_STORE, st);
-}
-
-int svc_w2v::rownorm(int mode, const float* xin, long ldx, float* y32, half_t* y16, long ldy, const float* g, const float* b, const float* g2,
-                     const float* b2, long rows, int D, const int* lens, int seq_rows, hipStream_t st) {
-    SVC_REQUIRE(D >= 64 && D % 64 == 0 && D <= 2048, "layernorm: D must be a multiple of 64, at most 2048");
-    if (rows == 0) return 0;
-    const dim3 grid(cdiv(rows, 4)), blk(256);
-    if (mode == 0) hipLaunchKernelGGL(wv_rownorm_kernel<0>, grid, blk, 0, st, xin, ldx, y32, y16, ldy, g, b, g2, b2, rows, D, 1e-5f, lens, seq_rows);
-    else if (mode == 1) hipLaunchKernelGGL(wv_rownorm_kernel<1>, grid, blk, 0, st, xin, ldx, y32, y16, ldy, g, b, g2, b2, rows, D, 1e-5f, lens, seq_rows);
-    else hipLaunchKernelGGL(wv_rownorm_kernel<2>, grid, blk, 0, st, xin, ldx, y32, y16, ldy, g, b, g2, b2, rows, D, 1e-5f, lens, seq_rows);
-    SVC_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-
 int svc_w2v::normalize_group(const float* wave, long Lrow, const WinTab& wt, int G, float* dst, long stride, hipStream_t st) {
     int nmax = 0;
     for (int g = 0; g < G; ++g) nmax = std::max(nmax, wt.n[g]);
-    double* sq = part + WV_MAX_WIN * WV_NBLK;
+    double* sq = part + MAX_WIN * WV_NBLK;
     hipLaunchKernelGGL(wv_stat_kernel<1>, dim3(WV_NBLK, G), dim3(256), 0, st, wave, wt, Lrow, (const double*)nullptr, part);
     hipLaunchKernelGGL(wv_stat_kernel<2>, dim3(WV_NBLK, G), dim3(256), 0, st, wave, wt, Lrow, (const double*)part, sq);
     hipLaunchKernelGGL(wv_norm_kernel, dim3(cdiv(nmax, 256), G), dim3(256), 0, st, wave, wt, Lrow, (const double*)part, (const double*)sq, dst, stride);
@@ -658,34 +421,34 @@ int svc_w2v::features_group(const float* wnorm, long stride, int G, hipStream_t 
         const int blocks = std::min(cdiv(Ls[1], 4), 2048);
         hipLaunchKernelGGL(wv_conv0_kernel, dim3(blocks, G), dim3(256), (size_t)cfg.conv_kernel[0] * C * 4, st, wnorm, stride, w0, b0, cg[0], cb[0],
                            f16 ? nullptr : (float*)actA, f16 ? (half_t*)actA : nullptr, C, cfg.conv_kernel[0], cfg.conv_stride[0], Ls[1],
-                           dlens + WV_MAX_WIN, 1e-5f);
+                           dlens + MAX_WIN, 1e-5f);
         SVC_CHECK_HIP(hipGetLastError());
     }
     void* cur = actA;
     void* nxt = actB;
     for (int l = 1; l < nc; ++l) {
         const int kl = cfg.conv_kernel[l];
-        KGemmParams p = wv_gemm((long)G * Ls[l + 1], C, Ls[l + 1]);
-        p.a_seq_rows = Ls[l]; p.a_len = Ls[l]; p.seq_len = dlens + l * WV_MAX_WIN; p.a_stride = cfg.conv_stride[l]; p.pad_mode = KG_PAD_ZERO;
+        KGemmParams p = kgemm_rows((long)G * Ls[l + 1], C, Ls[l + 1]);
+        p.a_seq_rows = Ls[l]; p.a_len = Ls[l]; p.seq_len = dlens + l * MAX_WIN; p.a_stride = cfg.conv_stride[l]; p.pad_mode = KG_PAD_ZERO;
         p.n_taps = kl;
         for (int t = 0; t < kl; ++t) { p.a_ptr[t] = cur; p.a_ld[t] = C; p.a_ktiles[t] = C / ktile_elems(dt); p.a_shift[t] = t; }
         p.w = conv[l].w; p.ldw = conv[l].ldw; p.bias = conv[l].b;
         p.c32 = raw; p.ldc32 = C;
         if (kgemm_launch(p, dt, KG_EPI_STORE, st)) return 1;
         const bool last = l == nc - 1;
-        if (rownorm(last ? 2 : 1, raw, C, f16 ? nullptr : (float*)nxt, f16 ? (half_t*)nxt : nullptr, C, cg[l], cb[l], pg, pb, (long)G * Ls[l + 1], C,
-                    dlens + (l + 1) * WV_MAX_WIN, Ls[l + 1], st))
+        if (rownorm_launch(last ? 2 : 1, raw, C, f16 ? nullptr : (float*)nxt, f16 ? (half_t*)nxt : nullptr, C, cg[l], cb[l], pg, pb,
+                           (long)G * Ls[l + 1], C, 1e-5f, dlens + (l + 1) * MAX_WIN, Ls[l + 1], st))
             return 1;
         std::swap(cur, nxt);
     }
     const int P = Ls[nc];
-    return lin(proj, cur, C, (long)G * P, P, KG_ACT_NONE, nullptr, h32, f16 ? h16 : nullptr, st);
+    return linear_launch(dt, proj, cur, C, (long)G * P, P, KG_ACT_NONE, nullptr, h32, f16 ? h16 : nullptr, st);
 }
 
 // h [G][P][D] (+ its fp16 copy in precision 1), rows per window in dlens row n_conv -> out = h + gelu(posconv(h)) on the valid rows
 int svc_w2v::posconv_group(const float* h, const half_t* h16v, int G, int P, float* out, hipStream_t st) {
     const int D = cfg.d_model, k = cfg.pos_k, NG = cfg.pos_groups;
-    const int* lens = dlens + cfg.n_conv * WV_MAX_WIN;
+    const int* lens = dlens + cfg.n_conv * MAX_WIN;
     if (dt == 0) {
         const int n_tiles = cdiv(P, WV_PC_BM);
         hipLaunchKernelGGL(w2v_posconv_kernel, dim3((unsigned)(n_tiles * G * NG)), dim3(256), 0, st, h16v, h, pos16, posb, out, lens, P, D, k, G, n_tiles);
@@ -695,7 +458,7 @@ int svc_w2v::posconv_group(const float* h, const half_t* h16v, int G, int P, flo
     for (int g = 0; g < NG; ++g)
         for (int t0 = 0; t0 < k; t0 += KG_MAX_TAPS) {
             const int nt = std::min(KG_MAX_TAPS, k - t0);
-            KGemmParams p = wv_gemm((long)G * P, 64, P);
+            KGemmParams p = kgemm_rows((long)G * P, 64, P);
             p.seq_len = lens; p.pad_mode = KG_PAD_ZERO; p.n_taps = nt;
             for (int t = 0; t < nt; ++t) { p.a_ptr[t] = h + g * 64; p.a_ld[t] = D; p.a_ktiles[t] = 2; p.a_shift[t] = t0 + t - k / 2; }
             p.w = pos32 + (long)g * 64 * k * 64 + (long)t0 * 64; p.ldw = (long)k * 64;
@@ -710,36 +473,9 @@ int svc_w2v::posconv_group(const float* h, const half_t* h16v, int G, int P, flo
 
 // h [G][P][D] -> out [G][P][D] (final LayerNorm); rows at and above a window's count are not written
 int svc_w2v::encode_group(const float* h, const half_t* h16v, int G, int P, float* out, hipStream_t st) {
-    const int D = cfg.d_model, F = cfg.ffn_dim, H = cfg.n_heads;
-    const long MP = (long)G * P;
-    const bool f16 = dt == 0;
-    const int* lens = dlens + cfg.n_conv * WV_MAX_WIN;
-    const long vld = round_up(P, 64);
-    if (posconv_group(h, h16v, G, P, x, st)) return 1;
-    if (mark(2, st)) return 1;
-    const void* nrm = f16 ? (const void*)n16 : (const void*)n32;
-    const int vmode = attention_vt_mode(G, H, P);
-    for (const Layer& ly : layers) {
-        if (rownorm(0, x, D, f16 ? nullptr : n32, f16 ? n16 : nullptr, D, ly.g1, ly.b1, nullptr, nullptr, MP, D, lens, P, st)) return 1;
-        if (lin(ly.qkv, nrm, D, MP, P, KG_ACT_NONE, nullptr, nullptr, qkv16, st)) return 1;
-        hipLaunchKernelGGL(wv_vt_kernel, dim3(cdiv(vld, 32), D / 32, G), dim3(256), 0, st, qkv16, vt, lens, P, D, vld, vmode);
-        SVC_CHECK_HIP(hipGetLastError());
-        AttnParams a;
-        memset(&a, 0, sizeof(a));
-        a.q = qkv16; a.k = qkv16 + D; a.ld_qk = 3 * D;
-        a.vt = vt; a.vt_seq_stride = (long)D * vld; a.vt_ld = vld; a.vt_perm = vmode;
-        a.out = ao16; a.ld_out = D;
-        a.out32 = f16 ? nullptr : ao32;
-        a.n_seq = G; a.H = H; a.seq_rows = P; a.Tq = P; a.kv_len = lens; a.kv_len_const = P;
-        a.qt_form = qt_form;
-        if (attention_launch(a, st)) return 1;
-        if (lin(ly.o, f16 ? (const void*)ao16 : (const void*)ao32, D, MP, P, KG_ACT_NONE, x, x, nullptr, st)) return 1;
-        if (rownorm(0, x, D, f16 ? nullptr : n32, f16 ? n16 : nullptr, D, ly.g2, ly.b2, nullptr, nullptr, MP, D, lens, P, st)) return 1;
-        if (lin(ly.fc1, nrm, D, MP, P, KG_ACT_GELU, nullptr, f16 ? nullptr : ff32, f16 ? ff16 : nullptr, st)) return 1;
-        if (lin(ly.fc2, f16 ? (const void*)ff16 : (const void*)ff32, F, MP, P, KG_ACT_NONE, x, x, nullptr, st)) return 1;
-    }
-    if (rownorm(0, x, D, out, nullptr, D, gf, bf, nullptr, nullptr, MP, D, lens, P, st)) return 1;
-    return mark(3, st);
+    if (posconv_group(h, h16v, G, P, stack.x, st)) return 1;
+    if (tm.mark(2, st) || stack.run(G, P, dlens + cfg.n_conv * MAX_WIN, out, st)) return 1;
+    return tm.mark(3, st);
 }
 
 extern "C" {
@@ -757,21 +493,22 @@ int svc_w2v_create(const svc_w2v_config_t* cfg, const svc_tensor_desc_t* weights
     SVC_REQUIRE(cfg->pos_k >= 2 && cfg->pos_k % 2 == 0 && cfg->pos_k <= WV_PC_MAXK, "svc_w2v_create: num_conv_pos_embeddings must be even, 2 .. 128");
     SVC_REQUIRE(cfg->pos_groups >= 1 && cfg->pos_groups * 64 == cfg->d_model, "svc_w2v_create: the positional conv needs groups of 64 channels");
     SVC_REQUIRE(cfg->precision == 0 || cfg->precision == 1, "svc_w2v_create: precision 0 (fp32 GEMMs) or 1 (fp16 GEMMs)");
+    const char* who = "svc_w2v_create";
     StateDict sd(weights, n_weights);
     std::string pre;
     for (const char* p : {"", "wav2vec2.", "hubert.", "model."})
         if (sd.has(std::string(p) + "feature_projection.projection.weight")) { pre = p; break; }
     for (const auto& k : wv_keys(*cfg))
-        if (wv_require(sd.get(pre + k.name), pre + k.name, k.shape)) return 1;
+        if (require_shape(sd.get(pre + k.name), pre + k.name, k.shape, who)) return 1;
     {
         const std::string pc = pre + "encoder.pos_conv_embed.conv.";
         const long D = cfg->d_model, k = cfg->pos_k;
-        if (sd.has(pc + "weight")) { if (wv_require(sd.get(pc + "weight"), pc + "weight", {D, 64, k})) return 1; }
+        if (sd.has(pc + "weight")) { if (require_shape(sd.get(pc + "weight"), pc + "weight", {D, 64, k}, who)) return 1; }
         else if (sd.has(pc + "parametrizations.weight.original1")) {
-            if (wv_require(sd.get(pc + "parametrizations.weight.original0"), pc + "parametrizations.weight.original0", {1, 1, k}) ||
-                wv_require(sd.get(pc + "parametrizations.weight.original1"), pc + "parametrizations.weight.original1", {D, 64, k}))
+            if (require_shape(sd.get(pc + "parametrizations.weight.original0"), pc + "parametrizations.weight.original0", {1, 1, k}, who) ||
+                require_shape(sd.get(pc + "parametrizations.weight.original1"), pc + "parametrizations.weight.original1", {D, 64, k}, who))
                 return 1;
-        } else if (wv_require(sd.get(pc + "weight_g"), pc + "weight_g", {1, 1, k}) || wv_require(sd.get(pc + "weight_v"), pc + "weight_v", {D, 64, k}))
+        } else if (require_shape(sd.get(pc + "weight_g"), pc + "weight_g", {1, 1, k}, who) || require_shape(sd.get(pc + "weight_v"), pc + "weight_v", {D, 64, k}, who))
             return 1;
     }
     hipStream_t st = (hipStream_t)stream;
@@ -780,7 +517,8 @@ int svc_w2v_create(const svc_w2v_config_t* cfg, const svc_tensor_desc_t* weights
     m->dt = cfg->precision ? 0 : 1;
     // the attention's query-tile form, from the configuration alone: what a group of four full windows would get from the grid-size rule
     const long Pw = wv_frames(*cfg, cfg->window_samples);
-    m->qt_form = (long)cdiv(Pw, 128) * cfg->n_heads * 4 <= 256 ? 1 : 2;
+    m->stack.dt = m->dt; m->stack.D = cfg->d_model; m->stack.F = cfg->ffn_dim; m->stack.H = cfg->n_heads;
+    m->stack.qt_form = (long)cdiv(Pw, 128) * cfg->n_heads * 4 <= 256 ? 1 : 2;
     if (m->pack(sd, pre, st)) { delete m; return 1; }
     *out = m;
     return 0;
@@ -796,7 +534,7 @@ long svc_w2v_frames(const svc_w2v_config_t* cfg, long n_samples) {
 
 static int wv_plan_check(const svc_w2v_config_t* cfg, int overlap_rows, long n_samples, const char* who) {
     if (wv_check_cfg(cfg, who)) return 1;
-    if (overlap_rows < 0 || (long)overlap_rows * WV_SPR >= cfg->window_samples) { set_error(std::string(who) + ": overlap_rows outside [0, window_samples / 320)"); return 1; }
+    if (overlap_rows < 0 || (long)overlap_rows * SAMPLES_PER_ROW >= cfg->window_samples) { set_error(std::string(who) + ": overlap_rows outside [0, window_samples / 320)"); return 1; }
     if (n_samples < 1 || wv_frames(*cfg, std::min<long>(n_samples, cfg->window_samples)) < 1) {
         set_error(std::string(who) + ": n_samples is shorter than the extractor's receptive field");
         return 1;
@@ -806,14 +544,14 @@ static int wv_plan_check(const svc_w2v_config_t* cfg, int overlap_rows, long n_s
 
 int svc_w2v_n_windows(const svc_w2v_config_t* cfg, int overlap_rows, long n_samples) {
     if (wv_plan_check(cfg, overlap_rows, n_samples, "svc_w2v_n_windows")) return -1;
-    const long nw = wv_n_windows(cfg->window_samples, (long)overlap_rows * WV_SPR, n_samples);
+    const long nw = window_count(cfg->window_samples, (long)overlap_rows * SAMPLES_PER_ROW, n_samples);
     if (nw > 0x7fffffffL) { set_error("svc_w2v_n_windows: n_samples is too large"); return -1; }
     return (int)nw;
 }
 
 int svc_w2v_rows(const svc_w2v_config_t* cfg, int overlap_rows, long n_samples) {
     if (wv_plan_check(cfg, overlap_rows, n_samples, "svc_w2v_rows")) return -1;
-    const long W = cfg->window_samples, O = (long)overlap_rows * WV_SPR, nw = wv_n_windows(W, O, n_samples);
+    const long W = cfg->window_samples, O = (long)overlap_rows * SAMPLES_PER_ROW, nw = window_count(W, O, n_samples);
     long rows = 0;
     for (long j = 0; j < nw; ++j) {
         const long f = wv_frames(*cfg, std::min(W, n_samples - j * (W - O)));
@@ -824,7 +562,7 @@ int svc_w2v_rows(const svc_w2v_config_t* cfg, int overlap_rows, long n_samples) 
 }
 
 int svc_w2v_set_window_group(svc_w2v_t* m, int windows) {
-    SVC_REQUIRE(windows >= 0 && windows <= WV_MAX_WIN, "svc_w2v_set_window_group: windows must be 0 (default) .. 64");
+    SVC_REQUIRE(windows >= 0 && windows <= MAX_WIN, "svc_w2v_set_window_group: windows must be 0 (default) .. 64");
     SVC_REQUIRE(m, "svc_w2v_set_window_group: null handle");
     m->group = windows ? windows : WV_DEFAULT_GROUP;
     return 0;
@@ -832,15 +570,14 @@ int svc_w2v_set_window_group(svc_w2v_t* m, int windows) {
 
 int svc_w2v_set_timing(svc_w2v_t* m, int on) {
     SVC_REQUIRE(m, "svc_w2v_set_timing: null handle");
-    m->timing = on != 0;
+    m->tm.on = on != 0;
     return 0;
 }
 
 int svc_w2v_last_timing(svc_w2v_t* m, float* ms4) {
-    SVC_REQUIRE(m && ms4 && m->timing && m->ev[0] && m->ev[4], "svc_w2v_last_timing: timing is off or no svc_w2v_content call was made");
-    SVC_CHECK_HIP(hipEventSynchronize(m->ev[4]));
-    for (int i = 0; i < 4; ++i) SVC_CHECK_HIP(hipEventElapsedTime(&ms4[i], m->ev[i], m->ev[i + 1]));
-    return 0;
+    const char* msg = "svc_w2v_last_timing: timing is off or no svc_w2v_content call was made";
+    SVC_REQUIRE(m, msg);
+    return m->tm.last(ms4, msg);
 }
 
 int svc_w2v_normalize(svc_w2v_t* m, const float* wave, const int32_t* lens, int B, int L, float* out, void* stream) {
@@ -884,7 +621,7 @@ int svc_w2v_features(svc_w2v_t* m, const float* wave_norm, const int32_t* lens, 
         if (m->put_lens(lt, st)) return 1;
         if (m->features_group(wave_norm + (long)b0 * L, L, nb, st)) return 1;
         hipLaunchKernelGGL(wv_copy_rows_kernel, dim3(P, nb), dim3(256), 0, st, (const float*)m->h32, P, out + (long)b0 * Tmax * D, Tmax,
-                           (const int*)(m->dlens + nc * WV_MAX_WIN), D);
+                           (const int*)(m->dlens + nc * MAX_WIN), D);
         SVC_CHECK_HIP(hipGetLastError());
     }
     return 0;
@@ -936,28 +673,17 @@ int svc_w2v_content(svc_w2v_t* m, const float* wave, const int32_t* lens, int B,
     SVC_REQUIRE(m, "svc_w2v_content: null handle");
     const svc_w2v_config_t& c = m->cfg;
     const int D = c.d_model, nc = c.n_conv;
-    const long W = c.window_samples, O = (long)overlap_rows * WV_SPR;
-    SVC_REQUIRE(O < W, "svc_w2v_content: overlap_rows outside [0, window_samples / 320)");
-    struct Win { int clip, start, n, dst0, drop, keep, zero_from; };
-    std::vector<Win> wins;
-    long nmax = 0;
+    const long W = c.window_samples;
+    SVC_REQUIRE((long)overlap_rows * SAMPLES_PER_ROW < W, "svc_w2v_content: overlap_rows outside [0, window_samples / 320)");
+    std::vector<Win> wins;                                   // the window plan of the whole call, in clip order
     for (int b = 0; b < B; ++b) {
         const long n = lens ? lens[b] : L;
         SVC_REQUIRE(wv_frames(c, std::min(n, W)) >= 1, "svc_w2v_content: lens shorter than the extractor's receptive field");
-        const int rows = svc_w2v_rows(&c, overlap_rows, n);
-        SVC_REQUIRE(rows >= 0 && rows <= Rmax, "svc_w2v_content: Rmax is smaller than the longest clip's rows (svc_w2v_rows)");
-        const long nw = wv_n_windows(W, O, n);
-        int dst = 0;
-        for (long j = 0; j < nw; ++j) {
-            const long s = j * (W - O), ns = std::min(W, n - s);
-            const int keep = (int)wv_frames(c, ns), drop = j ? overlap_rows : 0;
-            if (keep <= drop) continue;                          // a later window no longer than the overlap contributes nothing
-            wins.push_back({b, (int)s, (int)ns, dst, drop, keep, -1});
-            dst += keep - drop;
-            nmax = std::max(nmax, ns);
-        }
-        wins.back().zero_from = rows;                            // the clip's last computed window zeroes the rows above its count
+        const int rows = plan_clip(wins, b, n, W, overlap_rows, [&c](long ns) { return wv_frames(c, ns); });
+        SVC_REQUIRE(rows <= Rmax, "svc_w2v_content: Rmax is smaller than the longest clip's rows (svc_w2v_rows)");
     }
+    long nmax = 0;
+    for (const Win& w : wins) nmax = std::max<long>(nmax, w.n);
     hipStream_t st = (hipStream_t)stream;
     const int G = (int)std::min((size_t)m->group, wins.size());
     if (m->reserve_fe(G, nmax, st)) return 1;
@@ -965,25 +691,18 @@ int svc_w2v_content(svc_w2v_t* m, const float* wave, const int32_t* lens, int B,
     if (m->reserve_enc(G, P, st)) return 1;
     for (size_t w0 = 0; w0 < wins.size(); w0 += G) {
         const int nb = (int)std::min((size_t)G, wins.size() - w0);
-        WinTab wt;
+        const WinTab wt = win_table(wins, w0, nb);
         LenTab lt;
-        memset(&wt, 0, sizeof(wt));
         memset(&lt, 0, sizeof(lt));
-        for (int g = 0; g < nb; ++g) {
-            const Win& w = wins[w0 + g];
-            wt.clip[g] = w.clip; wt.start[g] = w.start; wt.n[g] = w.n; wt.dst0[g] = w.dst0; wt.drop[g] = w.drop;
-            wt.keep[g] = w.keep;
-            wt.zero_from[g] = w.zero_from;
-            for (int l = 0; l <= nc; ++l) lt.v[l][g] = (int)wv_frames(c, w.n, l);
-        }
-        if (m->mark(0, st)) return 1;
+        for (int g = 0; g < nb; ++g)
+            for (int l = 0; l <= nc; ++l) lt.v[l][g] = (int)wv_frames(c, wt.n[g], l);
+        if (m->tm.mark(0, st)) return 1;
         if (m->put_lens(lt, st)) return 1;
         if (m->normalize_group(wave, L, wt, nb, m->wn, m->nstride, st)) return 1;
-        if (m->features_group(m->wn, m->nstride, nb, st) || m->mark(1, st)) return 1;
+        if (m->features_group(m->wn, m->nstride, nb, st) || m->tm.mark(1, st)) return 1;
         if (m->encode_group(m->h32, m->h16, nb, P, m->enc, st)) return 1;
-        hipLaunchKernelGGL(wv_assemble_kernel, dim3(P + Rmax, nb), dim3(256), 0, st, (const float*)m->enc, wt, out, P, D, Rmax);
-        SVC_CHECK_HIP(hipGetLastError());
-        if (m->mark(4, st)) return 1;
+        if (assemble_launch(m->enc, wt, nb, out, P, D, Rmax, 256, st)) return 1;
+        if (m->tm.mark(4, st)) return 1;
     }
     return 0;
 }
@@ -992,11 +711,7 @@ int svc_w2v_content(svc_w2v_t* m, const float* wave, const int32_t* lens, int B,
 int svc_op_layernorm_gelu(const float* x, const float* gamma, const float* beta, float* y, int rows, int D, float eps, void* stream) {
     SVC_REQUIRE(x && gamma && beta && y && rows >= 0, "svc_op_layernorm_gelu: null argument or negative rows");
     SVC_REQUIRE(D >= 64 && D % 64 == 0 && D <= 2048, "svc_op_layernorm_gelu: D must be a multiple of 64, at most 2048");
-    if (rows == 0) return 0;
-    hipLaunchKernelGGL(wv_rownorm_kernel<1>, dim3(cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, x, (long)D, y, (half_t*)nullptr, (long)D, gamma, beta,
-                       (const float*)nullptr, (const float*)nullptr, (long)rows, D, eps, (const int*)nullptr, 1);
-    SVC_CHECK_HIP(hipGetLastError());
-    return 0;
+    return rownorm_launch(1, x, D, y, nullptr, D, gamma, beta, nullptr, nullptr, rows, D, eps, nullptr, 1, (hipStream_t)stream);
 }
 
 }  // extern "C"

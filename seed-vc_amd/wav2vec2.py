@@ -11,7 +11,7 @@ import ctypes as C
 import torch
 
 from . import _lib, specs
-from .whisper import SAMPLES_PER_ROW, window_plan as _window_plan
+from .content import SAMPLES_PER_ROW, ContentEncoder, window_plan as _window_plan
 
 
 def c_config(cfg, precision=1):
@@ -41,13 +41,13 @@ def frames(cfg, n):
 
 
 def window_plan(cfg, L, overlap_rows):
-    """The drivers' windows of a clip of L samples (whisper.window_plan: the loop is shared by all tokenizers) with this encoder's
+    """The drivers' windows of a clip of L samples (content.window_plan: the loop is shared by all tokenizers) with this encoder's
     row rule: a list of (start, samples, first_kept_row, rows); a later window with rows <= first_kept_row contributes nothing."""
     return [(s, n, d, frames(cfg, n)) for s, n, d, _ in _window_plan(L, cfg["window_samples"], int(overlap_rows) * SAMPLES_PER_ROW)]
 
 
-class Wav2Vec2Content:
-    SR = 16000
+class Wav2Vec2Content(ContentEncoder):
+    ABI, STAGES = "w2v", ("extractor", "posconv", "layers", "assemble")
 
     def __init__(self, state_dict, cfg=None, device="cuda:0", precision=1):
         self.cfg = specs.wav2vec2_config() if cfg is None else cfg
@@ -61,9 +61,6 @@ class Wav2Vec2Content:
             torch.cuda.current_stream().synchronize()
         del keep
 
-    def eval(self):
-        return self
-
     def frames(self, n_samples):
         return frames(self.cfg, n_samples)
 
@@ -72,27 +69,6 @@ class Wav2Vec2Content:
         r = _lib.lib().svc_w2v_rows(C.byref(self._c), int(overlap_rows), int(n_samples))
         _lib.check(int(r < 0))
         return r
-
-    def set_window_group(self, windows):
-        """Windows computed side by side (0 = the default): bounds the workspace; results do not depend on it."""
-        _lib.check(_lib.lib().svc_w2v_set_window_group(self._h, int(windows)))
-
-    def set_timing(self, on):
-        """Measurement aid: record HIP events around the stages of `content_batch` (see `last_timing`)."""
-        _lib.check(_lib.lib().svc_w2v_set_timing(self._h, int(bool(on))))
-
-    def last_timing(self):
-        """dict of milliseconds of the last window group of the last `content_batch` (synchronises)."""
-        ms = (C.c_float * 4)()
-        _lib.check(_lib.lib().svc_w2v_last_timing(self._h, ms))
-        return dict(zip(("extractor", "posconv", "layers", "assemble"), [float(v) for v in ms]))
-
-    @staticmethod
-    def _lens(lens, B):
-        lens = _lib.int_list(lens)
-        if len(lens) != B:
-            raise ValueError(f"Wav2Vec2Content: {len(lens)} lens for a batch of {B}")
-        return lens
 
     @torch.inference_mode()
     def normalize(self, waves, lens, out=None):
@@ -138,36 +114,3 @@ class Wav2Vec2Content:
     def encode(self, h, rows, out=None):
         """projected rows (B, T, D), rows [B] -> (B, T, D): positional conv, the layers and encoder.layer_norm."""
         return self._rows_call(_lib.lib().svc_w2v_encode, h, rows, out)
-
-    @torch.inference_mode()
-    def content_batch(self, waves, lens=None, overlap_s=5.0):
-        """waves (B, L) at 16 kHz (B <= 64), lens B host integers or None -> (S (B, Rmax, D) on the device, rows [B]): row b holds
-        the rows[b] content rows of waves[b, :lens[b]] as the drivers' window loop gives them, zeros above.  Nothing is synchronised."""
-        ov = int(round(float(overlap_s) * self.SR)) // SAMPLES_PER_ROW
-        with torch.cuda.device(self.device):
-            w = _lib.f32c(waves, self.device)
-            B, L = w.shape
-            lens = [L] * B if lens is None else self._lens(lens, B)
-            rows = [self.rows(n, ov) for n in lens]
-            out = torch.empty(B, max(rows), self.D, device=self.device)
-            _lib.check(_lib.lib().svc_w2v_content(self._h, _lib.ptr(w), _lib.i32_host(lens), B, L, ov, _lib.ptr(out), max(rows),
-                                                  _lib.stream_ptr()))
-        return out, rows
-
-    def semantic_fn(self, waves_16k):
-        """The drivers' closure: (1, L <= W) -> (1, frames(L), D)."""
-        w = torch.as_tensor(waves_16k, dtype=torch.float32)
-        if w.dim() != 2 or w.size(1) > self.W:
-            raise ValueError(f"Wav2Vec2Content.semantic_fn: (B, L <= {self.W}) samples, got {tuple(w.shape)}")
-        return self.content_batch(w, None, overlap_s=0.0)[0]
-
-    def close(self):
-        if self._h:
-            _lib.lib().svc_w2v_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
