@@ -607,6 +607,69 @@ int svc_w2v_encode(svc_w2v_t* m, const float* h, const int32_t* rows, int B, int
  * Each window is normalised on its own (the drivers call the feature extractor per window). */
 int svc_w2v_content(svc_w2v_t* m, const float* wave, const int32_t* lens, int B, int L, int overlap_rows, float* out, int Rmax, void* stream);
 
+/* ---------------------------------------------------------------- ASTRAL tokenizer (csrc/astral.hip)
+ * Replaces the v2 model's content tokenizers (`AstralQuantizer`: HubertModel of facebook/hubert-large-ll60k cut to ssl.n_layers
+ * layers with encoder.layer_norm replaced by Identity, then ConvNeXtV2Stage and BinarySphericalQuantize) and the drivers' loop over
+ * the windows of a long clip.  One SSL pass feeds n_heads heads (v2: wide, 2048 codes, and narrow, 32 codes).
+ * SSL front: the wav2vec 2.0 encoder above under `ssl` (its n_layers is the SSL output layer, its precision is shared by the heads),
+ * without the final LayerNorm.  A window of n samples yields min(frames(n), n / 320) rows.
+ * Head on rows h [T][ssl.d_model]: x = input_projection(h) (d_model -> dim); n_blocks times x += pwconv2(GRN(gelu(pwconv1(
+ * LayerNorm(dwconv(x)))))) with a depthwise conv of 7 taps whose zero padding sits at the window's own first and last row, LayerNorm
+ * over channels (eps 1e-6), erf-GELU, GRN: Gx[c] = sqrt(sum over the window's own rows of y[t][c]^2), Nx = Gx / (mean_c Gx + 1e-6),
+ * y = gamma (y Nx) + beta + y; then z = project_in(x) (dim -> bits) and index = sum_j [z_j > 0] 2^(bits - 1 - j).
+ * Residual stream, statistics and logits are fp32; the linears follow ssl.precision as in the w2v section; project_in is always fp32.
+ * weights: ssl_weights as svc_w2v_create takes them (encoder.layer_norm.* and layers at and above n_layers are ignored); per head
+ * encoder.input_projection.{weight (dim, d_model[, 1]), bias}, encoder.blocks.{i}.dwconv.{weight (dim, 1, 7), bias}, .norm.{weight,
+ * bias}, .pwconv1.{weight, bias}, .grn.{gamma, beta} ((1, 1, F) or (F,)), .pwconv2.{weight, bias}, quantizer.project_in.{weight,
+ * bias}; other keys are ignored.  Lengths and row counts are HOST int32 arrays consumed before the call returns; arguments are
+ * checked before the handle is touched where they can be; nothing synchronises once the workspace has its size.  Every window gets
+ * what it would get alone: its bits do not depend on what shares the call, on the order or on the group size. */
+#define SVC_ASTRAL_MAX_HEADS 2
+typedef struct svc_astral_head_config {
+    int dim, intermediate_dim;              /* multiples of 64, at most 2048 */
+    int n_blocks;                           /* 1 .. 64 */
+    int bits;                               /* 1 .. 16: log2(codebook_size) */
+    int dw_kernel;                          /* must be 7 */
+} svc_astral_head_config_t;
+typedef struct svc_astral_config {
+    svc_w2v_config_t ssl;
+    int n_heads;                            /* 1 or 2 */
+    svc_astral_head_config_t head[SVC_ASTRAL_MAX_HEADS];
+} svc_astral_config_t;
+typedef struct svc_astral svc_astral_t;
+
+/* head_weights[k] / n_head_weights[k]: the state dict of head k.  Configurations the kernels do not cover are refused with a message. */
+int svc_astral_create(const svc_astral_config_t* cfg, const svc_tensor_desc_t* ssl_weights, int n_ssl_weights,
+                      const svc_tensor_desc_t* const* head_weights, const int* n_head_weights, void* stream, svc_astral_t** out);
+void svc_astral_destroy(svc_astral_t* m);
+/* Host-side counts (no handle; -1 on a bad argument): the drivers' window plan as svc_w2v_n_windows / svc_w2v_rows, with
+ * min(frames(n), n / 320) rows per window. */
+int svc_astral_n_windows(const svc_astral_config_t* cfg, int overlap_rows, long n_samples);
+int svc_astral_rows(const svc_astral_config_t* cfg, int overlap_rows, long n_samples);
+int svc_astral_set_window_group(svc_astral_t* m, int windows);
+/* Measurement aid (tools/astral_bench.py): ms4 = {SSL front, ConvNeXt stages, BSQ heads, assemble} of the last group of the last
+ * svc_astral_tokens call, in ms. */
+int svc_astral_set_timing(svc_astral_t* m, int on);
+int svc_astral_last_timing(svc_astral_t* m, float* ms4);
+/* Seam: wave [B][L], 1 <= lens[b] <= min(L, window_samples), one window per clip -> out [B][T][ssl.d_model]: the residual stream
+ * after layer n_layers (no final LayerNorm) on each clip's rows; the rows above are not touched. */
+int svc_astral_ssl(svc_astral_t* m, const float* wave, const int32_t* lens, int B, int L, float* out, int T, void* stream);
+/* Seam: head `head`, h [B][T][ssl.d_model], 1 <= rows[b] <= T -> x [B][T][dim] after the last block; rows at and above rows[b] are
+ * neither read as values nor written. */
+int svc_astral_convnext(svc_astral_t* m, int head, const float* h, const int32_t* rows, int B, int T, float* x, void* stream);
+/* Seam: head `head`, x [B][T][dim] -> z [B][T][bits] = project_in(x), fp32; rows at and above rows[b] are not touched. */
+int svc_astral_logits(svc_astral_t* m, int head, const float* x, const int32_t* rows, int B, int T, float* z, void* stream);
+/* z [rows][bits] -> index[rows] = sum_j [z_j > 0] 2^(bits - 1 - j) (strict: +0, -0 and NaN give bit 0). */
+int svc_op_bsq_index(const float* z, int32_t* index, long rows, int bits, void* stream);
+/* Duration reduction (torch.unique_consecutive per clip): tokens [B][R], 0 <= rows[b] <= R (HOST) -> out [B][R]: the first token
+ * of every run in order, -1 above the count; counts [B] on the DEVICE.  tokens and out must not overlap. */
+int svc_tokens_reduce(const int32_t* tokens, const int32_t* rows, int B, int R, int32_t* out, int32_t* counts, void* stream);
+/* The one call: wave [B][L], lens HOST [B] or NULL (= L), B <= 64 clips of any length -> tokens [n_heads][B][Rmax]: tokens
+ * [0, svc_astral_rows(cfg, overlap_rows, lens[b])) of tokens[k][b] are head k's indices of the kept rows of the clip's windows in
+ * order, -1 above.  reduce_head >= 0: also reduced [B][Rmax] and counts [B] (device), svc_tokens_reduce of that head's tokens. */
+int svc_astral_tokens(svc_astral_t* m, const float* wave, const int32_t* lens, int B, int L, int overlap_rows, int32_t* tokens, int Rmax,
+                      int reduce_head, int32_t* reduced, int32_t* counts, void* stream);
+
 /* Device-side counterpart of `crossfade(chunk1, chunk2, overlap)` (inference.py:343-350): the first n samples of
  * chunk2 become chunk2 * fade_in + chunk1_tail * fade_out in float64, stored as float32 (bit-identical to the numpy
  * arithmetic).  fade_in / fade_out: the caller's cos^2 windows (double, device). */

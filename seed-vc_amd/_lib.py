@@ -36,6 +36,9 @@ EXPORTS = [
     "svc_w2v_create", "svc_w2v_destroy", "svc_w2v_frames", "svc_w2v_n_windows", "svc_w2v_rows", "svc_w2v_set_window_group",
     "svc_w2v_set_timing", "svc_w2v_last_timing", "svc_w2v_normalize", "svc_w2v_features", "svc_w2v_posconv", "svc_w2v_encode",
     "svc_w2v_content",
+    "svc_astral_create", "svc_astral_destroy", "svc_astral_n_windows", "svc_astral_rows", "svc_astral_set_window_group",
+    "svc_astral_set_timing", "svc_astral_last_timing", "svc_astral_ssl", "svc_astral_convnext", "svc_astral_logits", "svc_astral_tokens",
+    "svc_op_bsq_index", "svc_tokens_reduce",
     "svc_prof_enable", "svc_prof_collect",
     "svc_op_linear", "svc_op_conv1d", "svc_op_conv1d_ex", "svc_op_conv1d_last_took", "svc_op_conv_transpose1d", "svc_op_attention", "svc_op_rmsnorm",
     "svc_op_layernorm", "svc_op_layernorm_gelu",
@@ -109,6 +112,14 @@ class W2vConfig(C.Structure):
     _fields_ = [("conv_dim", C.c_int), ("n_conv", C.c_int), ("conv_kernel", C.c_int * 8), ("conv_stride", C.c_int * 8)] + \
                [(n, C.c_int) for n in ("d_model", "n_heads", "n_layers", "ffn_dim", "pos_k", "pos_groups", "feat_extract_norm_layer",
                                        "do_stable_layer_norm", "conv_bias", "window_samples", "precision")]
+
+
+class AstralHeadConfig(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("dim", "intermediate_dim", "n_blocks", "bits", "dw_kernel")]
+
+
+class AstralConfig(C.Structure):
+    _fields_ = [("ssl", W2vConfig), ("n_heads", C.c_int), ("head", AstralHeadConfig * 2)]
 
 
 class LrConfig(C.Structure):
@@ -196,6 +207,22 @@ def lib():
         l.svc_w2v_posconv.argtypes = [C.c_void_p, C.c_void_p, i32p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         l.svc_w2v_encode.argtypes = [C.c_void_p, C.c_void_p, i32p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         l.svc_w2v_content.argtypes = [C.c_void_p, C.c_void_p, i32p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        # ASTRAL tokenizer: lengths and row counts as HOST int32 arrays; token buffers are device int32
+        ap = C.POINTER(AstralConfig)
+        l.svc_astral_create.argtypes = [ap, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_void_p, C.POINTER(C.c_void_p)]
+        l.svc_astral_destroy.argtypes = [C.c_void_p]
+        l.svc_astral_n_windows.argtypes = [ap, C.c_int, C.c_long]
+        l.svc_astral_rows.argtypes = [ap, C.c_int, C.c_long]
+        l.svc_astral_set_window_group.argtypes = [C.c_void_p, C.c_int]
+        l.svc_astral_set_timing.argtypes = [C.c_void_p, C.c_int]
+        l.svc_astral_last_timing.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        l.svc_astral_ssl.argtypes = [C.c_void_p, C.c_void_p, i32p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        l.svc_astral_convnext.argtypes = [C.c_void_p, C.c_int, C.c_void_p, i32p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        l.svc_astral_logits.argtypes = [C.c_void_p, C.c_int, C.c_void_p, i32p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        l.svc_op_bsq_index.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_void_p]
+        l.svc_tokens_reduce.argtypes = [C.c_void_p, i32p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        l.svc_astral_tokens.argtypes = [C.c_void_p, C.c_void_p, i32p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]
         l.svc_op_layernorm_gelu.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p]
         l.svc_op_layernorm.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p]
         _lib = l

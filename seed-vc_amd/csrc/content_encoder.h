@@ -1,4 +1,4 @@
-// What the 16 kHz content encoders (whisper.hip, wav2vec2.hip) share: the window table and plan of long clips, the LayerNorm
+// What the 16 kHz content encoders (whisper.hip, wav2vec2.hip and, through the latter, astral.hip) share: the window table and plan of long clips, the LayerNorm
 // row kernel, the V transpose, the packed linears and the pre-LN transformer stack (kernels and launchers in
 // content_encoder.hip).  A model file supplies its stem, its "rows of a window of ns samples" rule and its key names.
 // StageTimer and copy_f32 also serve rmvpe.hip.
@@ -89,6 +89,9 @@ int rownorm_launch(int mode, const float* x, long ldx, float* y32, half_t* y16, 
 // window's rows (lens[g], or P when lens is null) are written as zeros
 int vt_launch(const half_t* qkv, half_t* vt, const int* lens, int G, int P, int D, long vt_ld, int mode, hipStream_t st);
 
+// src [G][P][D] rows below lens[g] -> dst [G][T][D]; the other rows of dst are not touched
+int copy_rows_launch(const float* src, int P, float* dst, int T, const int* lens, int G, int rows, int D, hipStream_t st);
+
 struct Lin { void* w = nullptr; float* b = nullptr; long ldw = 0; int N = 0; };
 struct Layer { Lin qkv, o, fc1, fc2; float *g1 = nullptr, *b1 = nullptr, *g2 = nullptr, *b2 = nullptr; };
 
@@ -115,14 +118,16 @@ struct EncoderStack {
     int dt = 0, D = 0, F = 0, H = 0;
     int qt_form = 1;                 // the attention's query-tile form, pinned per handle by the model
     std::vector<Layer> layers;
+    bool final_ln = true;            // internal: false ends at the residual stream after the last layer, left in x (the ASTRAL front, astral.hip)
     float *gf = nullptr, *bf = nullptr;
     float *x = nullptr, *n32 = nullptr, *ao32 = nullptr, *ff32 = nullptr;           // x [G * P][D]: the residual stream, filled by the stem
     half_t *n16 = nullptr, *qkv16 = nullptr, *vt = nullptr, *ao16 = nullptr, *ff16 = nullptr;
 
-    static void keys(const StackNames& nm, int n_layers, long D, long F, std::vector<KeyShape>& out);
+    static void keys(const StackNames& nm, int n_layers, long D, long F, std::vector<KeyShape>& out, bool final_ln = true);
     int pack(const StateDict& sd, const std::string& pre, const StackNames& nm, int n_layers, Arena& wts, hipStream_t st);     // after keys()
     int reserve(Arena& ws, int G, int P, hipStream_t st);
-    // x [G][P][D] -> out [G][P][D]; with lens, sequence g has lens[g] rows and the rows above are neither read nor written
+    // x [G][P][D] -> out [G][P][D]; with lens, sequence g has lens[g] rows and the rows above are neither read nor written.
+    // Without the final LayerNorm the result stays in x and `out` is not used.
     int run(int G, int P, const int* lens, float* out, hipStream_t st);
 };
 

@@ -68,7 +68,22 @@ __global__ void assemble_kernel(const float* __restrict__ enc, WinTab wt, float*
     for (int i = threadIdx.x; i < D / 4; i += blockDim.x) dst[i] = src ? src[i] : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
+// src [G][P][D] rows below lens[g] -> dst [G][T][D]; the other rows of dst are not touched
+__global__ void copy_rows_kernel(const float* __restrict__ src, int P, float* __restrict__ dst, int T, const int* __restrict__ lens, int D) {
+    const int g = blockIdx.y, r = blockIdx.x;
+    if (r >= lens[g]) return;
+    const float4* s = reinterpret_cast<const float4*>(src + ((long)g * P + r) * D);
+    float4* d = reinterpret_cast<float4*>(dst + ((long)g * T + r) * D);
+    for (int i = threadIdx.x; i < D / 4; i += blockDim.x) d[i] = s[i];
+}
+
 }  // namespace
+
+int copy_rows_launch(const float* src, int P, float* dst, int T, const int* lens, int G, int rows, int D, hipStream_t st) {
+    hipLaunchKernelGGL(copy_rows_kernel, dim3(rows, G), dim3(256), 0, st, src, P, dst, T, lens, D);
+    SVC_CHECK_HIP(hipGetLastError());
+    return 0;
+}
 
 WinTab win_table(const std::vector<Win>& wins, size_t w0, int G) {
     WinTab wt;
@@ -136,7 +151,7 @@ int linear_launch(int dt, const Lin& l, const void* a, long K, long M, int Lout,
     return kgemm_launch(p, dt, KG_EPI_STORE, st);
 }
 
-void EncoderStack::keys(const StackNames& nm, int n_layers, long D, long F, std::vector<KeyShape>& out) {
+void EncoderStack::keys(const StackNames& nm, int n_layers, long D, long F, std::vector<KeyShape>& out, bool final_ln) {
     for (int i = 0; i < n_layers; ++i) {
         const std::string p = nm.layers + std::to_string(i) + ".";
         for (const char* m : {nm.q, nm.k, nm.v, nm.o}) out.push_back({p + m + ".weight", {D, D}});
@@ -151,6 +166,7 @@ void EncoderStack::keys(const StackNames& nm, int n_layers, long D, long F, std:
             out.push_back({p + m + ".bias", {D}});
         }
     }
+    if (!final_ln) return;
     out.push_back({std::string(nm.ln_final) + ".weight", {D}});
     out.push_back({std::string(nm.ln_final) + ".bias", {D}});
 }
@@ -186,6 +202,7 @@ int EncoderStack::pack(const StateDict& sd, const std::string& pre, const StackN
             !(ly.g2 = copy_f32(get(p + nm.ln2 + ".weight"), D, wts, st)) || !(ly.b2 = copy_f32(get(p + nm.ln2 + ".bias"), D, wts, st)))
             return 1;
     }
+    if (!final_ln) return 0;
     if (!(gf = copy_f32(get(std::string(nm.ln_final) + ".weight"), D, wts, st)) ||
         !(bf = copy_f32(get(std::string(nm.ln_final) + ".bias"), D, wts, st)))
         return 1;
@@ -239,6 +256,7 @@ int EncoderStack::run(int G, int P, const int* lens, float* out, hipStream_t st)
         if (linear_launch(dt, ly.fc1, nrm, D, MP, P, KG_ACT_GELU, nullptr, f16 ? nullptr : ff32, f16 ? ff16 : nullptr, st)) return 1;
         if (linear_launch(dt, ly.fc2, f16 ? (const void*)ff16 : (const void*)ff32, F, MP, P, KG_ACT_NONE, x, x, nullptr, st)) return 1;
     }
+    if (!final_ln) return 0;                                 // the result is the residual stream x itself
     return norm(gf, bf, out, nullptr);
 }
 

@@ -14,19 +14,17 @@
 #include <math.h>
 #include <string.h>
 
-#include "content_encoder.h"
+#include "w2v_internal.h"
 
 using namespace svc;
 
 namespace {
 
-constexpr int WV_MAX_B = 64, WV_NBLK = 64, WV_DEFAULT_GROUP = 16, WV_MAX_CONV = 8;
+constexpr int WV_NBLK = 64;
 constexpr int WV_PC_BM = 64, WV_PC_MAXK = 128, WV_PC_AHEAD = 4;    // positional conv: positions per workgroup, most taps, taps of weights in flight
 constexpr StackNames WV_NAMES = {"encoder.layers.", "attention.q_proj", "attention.k_proj", "attention.k_proj.bias", "attention.v_proj",
                                  "attention.out_proj", "layer_norm", "feed_forward.intermediate_dense", "feed_forward.output_dense",
                                  "final_layer_norm", "encoder.layer_norm"};
-
-struct LenTab { int v[WV_MAX_CONV + 1][MAX_WIN]; };                // samples, then rows after each conv, per window
 
 __device__ __forceinline__ double wave_sum_d(double v) {
 #pragma unroll
@@ -221,16 +219,11 @@ __global__ void wv_pack_pos_kernel(const float* __restrict__ v, const float* __r
     if (w32) w32[((long)no * k + t) * 64 + c] = val;
 }
 
-// src [G][P][D] rows below lens[g] -> dst [G][T][D]; the other rows of dst are not touched
-__global__ void wv_copy_rows_kernel(const float* __restrict__ src, int P, float* __restrict__ dst, int T, const int* __restrict__ lens, int D) {
-    const int g = blockIdx.y, r = blockIdx.x;
-    if (r >= lens[g]) return;
-    const float4* s = reinterpret_cast<const float4*>(src + ((long)g * P + r) * D);
-    float4* d = reinterpret_cast<float4*>(dst + ((long)g * T + r) * D);
-    for (int i = threadIdx.x; i < D / 4; i += blockDim.x) d[i] = s[i];
-}
+}  // namespace
 
-long wv_frames(const svc_w2v_config_t& c, long n, int upto = WV_MAX_CONV) {
+namespace svc {
+
+long wv_frames(const svc_w2v_config_t& c, long n, int upto) {
     for (int l = 0; l < c.n_conv && l < upto; ++l) n = n >= c.conv_kernel[l] ? (n - c.conv_kernel[l]) / c.conv_stride[l] + 1 : 0;
     return n;
 }
@@ -250,40 +243,11 @@ int wv_check_cfg(const svc_w2v_config_t* c, const char* who) {
     return 0;
 }
 
-}  // namespace
-
-struct svc_w2v {
-    svc_w2v_config_t cfg;
-    int dt = 0;                      // tap-GEMM dtype of the convs and linears: 0 fp16 (precision 1), 1 fp32 (precision 0)
-    int group = WV_DEFAULT_GROUP;
-    Arena wts, ws_fe, ws_enc;
-    float* w0 = nullptr; float* b0 = nullptr;                           // conv0 [k0][C], bias
-    Lin conv[WV_MAX_CONV], proj;
-    float *cg[WV_MAX_CONV] = {}, *cb[WV_MAX_CONV] = {}, *pg = nullptr, *pb = nullptr;
-    half_t* pos16 = nullptr; float* pos32 = nullptr; float* posb = nullptr;
-    EncoderStack stack;
-    // extractor workspace for cap_g windows of cap_n samples; encoder workspace for ecap_g windows of ecap_p rows
-    int cap_g = 0; long cap_n = 0; int ecap_g = 0, ecap_p = 0;
-    int Ls[WV_MAX_CONV + 1] = {};    // row strides of the stage buffers of the current call (its longest window)
-    long nstride = 0;
-    float* wn = nullptr; double* part = nullptr; int* dlens = nullptr;
-    void *actA = nullptr, *actB = nullptr; float* raw = nullptr;
-    float *h32 = nullptr, *enc = nullptr, *acc32 = nullptr;
-    half_t* h16 = nullptr;
-    StageTimer tm;
-    int pack(const StateDict& sd, const std::string& pre, hipStream_t st);
-    int reserve_fe(int G, long nmax, hipStream_t st);
-    int reserve_enc(int G, int P, hipStream_t st);
-    int put_lens(const LenTab& lt, hipStream_t st);
-    int normalize_group(const float* wave, long Lrow, const WinTab& wt, int G, float* dst, long stride, hipStream_t st);
-    int features_group(const float* wnorm, long stride, int G, hipStream_t st);            // -> h32 (+ h16) [G][Ls[n_conv]][D]
-    int posconv_group(const float* h, const half_t* h16v, int G, int P, float* out, hipStream_t st);
-    int encode_group(const float* h, const half_t* h16v, int G, int P, float* out, hipStream_t st);
-};
+}  // namespace svc
 
 namespace {
 
-std::vector<KeyShape> wv_keys(const svc_w2v_config_t& c) {
+std::vector<KeyShape> wv_keys(const svc_w2v_config_t& c, bool final_ln) {
     const long D = c.d_model, F = c.ffn_dim, C = c.conv_dim;
     std::vector<KeyShape> k;
     for (int l = 0; l < c.n_conv; ++l) {
@@ -298,7 +262,7 @@ std::vector<KeyShape> wv_keys(const svc_w2v_config_t& c) {
     k.push_back({"feature_projection.projection.weight", {D, C}});
     k.push_back({"feature_projection.projection.bias", {D}});
     k.push_back({"encoder.pos_conv_embed.conv.bias", {D}});
-    EncoderStack::keys(WV_NAMES, c.n_layers, D, F, k);
+    EncoderStack::keys(WV_NAMES, c.n_layers, D, F, k, final_ln);
     return k;
 }
 
@@ -471,16 +435,15 @@ int svc_w2v::posconv_group(const float* h, const half_t* h16v, int G, int P, flo
     return 0;
 }
 
-// h [G][P][D] -> out [G][P][D] (final LayerNorm); rows at and above a window's count are not written
+// h [G][P][D] -> out [G][P][D] (final LayerNorm); rows at and above a window's count are not written.  A handle made without the
+// final LayerNorm leaves the residual stream in stack.x and does not use `out`.
 int svc_w2v::encode_group(const float* h, const half_t* h16v, int G, int P, float* out, hipStream_t st) {
     if (posconv_group(h, h16v, G, P, stack.x, st)) return 1;
     if (tm.mark(2, st) || stack.run(G, P, dlens + cfg.n_conv * MAX_WIN, out, st)) return 1;
     return tm.mark(3, st);
 }
 
-extern "C" {
-
-int svc_w2v_create(const svc_w2v_config_t* cfg, const svc_tensor_desc_t* weights, int n_weights, void* stream, svc_w2v_t** out) {
+int svc::w2v_create(const svc_w2v_config_t* cfg, const svc_tensor_desc_t* weights, int n_weights, void* stream, bool final_ln, svc_w2v_t** out) {
     SVC_REQUIRE(cfg && weights && out, "svc_w2v_create: null argument");
     SVC_REQUIRE(cfg->feat_extract_norm_layer == 1 && cfg->do_stable_layer_norm == 1 && cfg->conv_bias == 1,
                 "svc_w2v_create: only feat_extract_norm = \"layer\" with do_stable_layer_norm and conv_bias is supported (group-norm extractors and "
@@ -498,7 +461,7 @@ int svc_w2v_create(const svc_w2v_config_t* cfg, const svc_tensor_desc_t* weights
     std::string pre;
     for (const char* p : {"", "wav2vec2.", "hubert.", "model."})
         if (sd.has(std::string(p) + "feature_projection.projection.weight")) { pre = p; break; }
-    for (const auto& k : wv_keys(*cfg))
+    for (const auto& k : wv_keys(*cfg, final_ln))
         if (require_shape(sd.get(pre + k.name), pre + k.name, k.shape, who)) return 1;
     {
         const std::string pc = pre + "encoder.pos_conv_embed.conv.";
@@ -518,10 +481,17 @@ int svc_w2v_create(const svc_w2v_config_t* cfg, const svc_tensor_desc_t* weights
     // the attention's query-tile form, from the configuration alone: what a group of four full windows would get from the grid-size rule
     const long Pw = wv_frames(*cfg, cfg->window_samples);
     m->stack.dt = m->dt; m->stack.D = cfg->d_model; m->stack.F = cfg->ffn_dim; m->stack.H = cfg->n_heads;
+    m->stack.final_ln = final_ln;
     m->stack.qt_form = (long)cdiv(Pw, 128) * cfg->n_heads * 4 <= 256 ? 1 : 2;
     if (m->pack(sd, pre, st)) { delete m; return 1; }
     *out = m;
     return 0;
+}
+
+extern "C" {
+
+int svc_w2v_create(const svc_w2v_config_t* cfg, const svc_tensor_desc_t* weights, int n_weights, void* stream, svc_w2v_t** out) {
+    return w2v_create(cfg, weights, n_weights, stream, true, out);
 }
 
 void svc_w2v_destroy(svc_w2v_t* m) { delete m; }
@@ -620,9 +590,7 @@ int svc_w2v_features(svc_w2v_t* m, const float* wave_norm, const int32_t* lens, 
             for (int l = 0; l <= nc; ++l) lt.v[l][g] = (int)wv_frames(m->cfg, lens[b0 + g], l);
         if (m->put_lens(lt, st)) return 1;
         if (m->features_group(wave_norm + (long)b0 * L, L, nb, st)) return 1;
-        hipLaunchKernelGGL(wv_copy_rows_kernel, dim3(P, nb), dim3(256), 0, st, (const float*)m->h32, P, out + (long)b0 * Tmax * D, Tmax,
-                           (const int*)(m->dlens + nc * MAX_WIN), D);
-        SVC_CHECK_HIP(hipGetLastError());
+        if (copy_rows_launch(m->h32, P, out + (long)b0 * Tmax * D, Tmax, m->dlens + nc * MAX_WIN, nb, P, D, st)) return 1;
     }
     return 0;
 }

@@ -577,6 +577,30 @@ def v2_ar_prompt(target_narrow, src_narrow):
     return torch.cat([target_narrow, src_narrow], dim=1)
 
 
+@torch.inference_mode()
+def v2_content_tokens(astral, waves_16k, lens, overlap_s=5.0):
+    """The v2 model's content tokens of B clips (sources and targets together) from 16 kHz audio, on the device: ONE
+    `AstralTokenizer.tokens_batch` call (HuBERT once per window, the wide head 0 and the narrow head 1 on the same rows) with the
+    duration reduction of the narrow tokens in the same call, then one host synchronisation (the reduced counts).
+
+    waves_16k (B, L), lens B host integers -> a list of B records dict(wide (1, R), narrow (1, R), narrow_reduced (1, n)) of int64
+    device tensors.  The chain, for a source s and a target t of the list:
+
+        tok = v2_content_tokens(astral, waves, lens)
+        target = hot.prepare_target(target_narrow=tok[t]["narrow_reduced"], target_tokens=tok[t]["wide"], target_mel=mel, style=style)
+        wave = hot.convert_batch(src_narrow=[tok[s]["narrow_reduced"]], targets=[target], ...)
+
+    (vc_wrapper.py: the AR prompt is cat([target, source]) of the REDUCED narrow tokens, the CFM prompt condition comes from the
+    target's wide tokens; `narrow` is kept for callers that skip the reduction)."""
+    if astral.n_heads != 2:
+        raise ValueError("v2_content_tokens: the tokenizer needs the wide (0) and the narrow (1) head")
+    tok, rows, red, cnt = astral.tokens_batch(waves_16k, lens, overlap_s=overlap_s, reduce_head=1)
+    counts = cnt.tolist()
+    tok = tok.long()
+    red = red.long()
+    return [dict(wide=tok[0, b:b + 1, :r], narrow=tok[1, b:b + 1, :r], narrow_reduced=red[b:b + 1, :n]) for b, (r, n) in enumerate(zip(rows, counts))]
+
+
 class V2HotPath:
     """The v2 chain as ONE call: narrow content tokens -> AR length regulator -> AR generate -> CFM length regulator ->
     cat([prompt_condition, cond]) -> CFM sampler (3-way CFG) -> strip the prompt frames -> BigVGAN

@@ -620,7 +620,7 @@ def whisper_state_spec(c):
 
 # --------------------------------------------------------------------------------------------- wav2vec 2.0 content encoder
 # facebook/wav2vec2-xls-r-300m cut to its first 12 layers (the drivers' `output_layer`), the content encoder of the tiny v1 model;
-# HuBERT-large (the front half of the v2 ASTRAL tokenizer) is the same network
+# HuBERT-large (the front half of the v2 ASTRAL tokenizer, below) is the same network
 W2V_PRESET = dict(conv_dim=512, conv_kernel=(10, 3, 3, 3, 3, 2, 2), conv_stride=(5, 2, 2, 2, 2, 2, 2), d_model=1024, n_heads=16, n_layers=12,
                   ffn_dim=4096, pos_k=128, pos_groups=16, feat_extract_norm="layer", do_stable_layer_norm=True, conv_bias=True,
                   window_samples=480000)
@@ -656,4 +656,36 @@ def wav2vec2_state_spec(c):
         s[p + "feed_forward.intermediate_dense.weight"], s[p + "feed_forward.intermediate_dense.bias"] = (F, D), (F,)
         s[p + "feed_forward.output_dense.weight"], s[p + "feed_forward.output_dense.bias"] = (D, F), (D,)
         s[p + "final_layer_norm.weight"], s[p + "final_layer_norm.bias"] = (D,), (D,)
+    return s
+
+
+# --------------------------------------------------------------------------------------------- ASTRAL tokenizer
+# the v2 content tokenizers: facebook/hubert-large-ll60k cut after 18 layers (no encoder.layer_norm), then per tokenizer a
+# ConvNeXtV2Stage and a binary spherical quantizer; `wide` has 2^11 = 2048 codes, `narrow` 2^5 = 32
+ASTRAL_WIDE = dict(dim=512, intermediate_dim=1536, n_blocks=12, bits=11, dw_kernel=7)
+ASTRAL_NARROW = dict(dim=512, intermediate_dim=1536, n_blocks=12, bits=5, dw_kernel=7)
+
+
+def astral_config(**overrides):
+    """dict(ssl = wav2vec2 config with n_layers = the SSL output layer, heads = list of head dicts); v2 order: wide, narrow"""
+    cfg = dict(ssl=wav2vec2_config(n_layers=18), heads=[deepcopy(ASTRAL_WIDE), deepcopy(ASTRAL_NARROW)])
+    cfg.update(overrides)
+    return cfg
+
+
+def astral_head_state_spec(c, k):
+    """State dict of head k (`encoder` = ConvNeXtV2Stage, `quantizer` = BinarySphericalQuantize) under its canonical key names"""
+    h, Din = c["heads"][k], c["ssl"]["d_model"]
+    D, F = h["dim"], h["intermediate_dim"]
+    s = OrderedDict()
+    s["encoder.input_projection.weight"], s["encoder.input_projection.bias"] = (D, Din, 1), (D,)
+    for i in range(h["n_blocks"]):
+        p = f"encoder.blocks.{i}."
+        s[p + "dwconv.weight"], s[p + "dwconv.bias"] = (D, 1, h["dw_kernel"]), (D,)
+        s[p + "norm.weight"], s[p + "norm.bias"] = (D,), (D,)
+        s[p + "pwconv1.weight"], s[p + "pwconv1.bias"] = (F, D), (F,)
+        s[p + "grn.gamma"], s[p + "grn.beta"] = (1, 1, F), (1, 1, F)
+        s[p + "pwconv2.weight"], s[p + "pwconv2.bias"] = (D, F), (D,)
+    s["quantizer.project_in.weight"], s["quantizer.project_in.bias"] = (h["bits"], D), (h["bits"],)
+    s["quantizer.project_out.weight"], s["quantizer.project_out.bias"] = (D, h["bits"]), (D,)
     return s
