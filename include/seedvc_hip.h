@@ -397,6 +397,31 @@ int svc_mel_forward(svc_mel_t* m, const float* y, int B, int L, float* out, void
 int svc_mel_min_len(int n_fft, int hop);               /* the shortest legal lens[b]: max((n_fft - hop) / 2 + 1, hop); needs no handle */
 int svc_mel_forward_ragged(svc_mel_t* m, const float* y, const int32_t* lens, int B, int L, float pad_value, float* out, void* stream);
 
+/* ---------------------------------------------------------------- sample-rate conversion
+ * Replaces `torchaudio.functional.resample(wave, orig, new)` (inference.py:380-406) for any filter of that polyphase form.  With
+ * g = gcd(orig, new), o = orig / g, n = new / g the operator is out[i n + j] = sum_k K[j][k] xpad[i o + k], xpad = x padded by
+ * `width` zeros on the left; the library takes the non-zero run of every phase: taps HOST [n][ntaps] fp32 and first HOST [n]
+ * int32, the column of K where phase j's run starts (runs shorter than ntaps are padded with 0.0 at the end).  The host mirror
+ * builds both from torchaudio's float64 formula (audio.py: sinc_resample_taps).  Both arrays are copied before create returns.
+ * o so large that four periods of input do not fit the LDS (about 3900 with these filters) is refused. */
+typedef struct svc_resampler svc_resampler_t;
+int svc_resampler_create(int o, int n, int width, int ntaps, const int32_t* first, const float* taps, void* stream,
+                         svc_resampler_t** out);
+void svc_resampler_destroy(svc_resampler_t* r);
+long svc_resample_len(int o, int n, long L);           /* ceil(n L / o) in 64-bit integers; needs no handle and no GPU */
+long svc_resampler_tile(const svc_resampler_t* r);     /* outputs one workgroup owns (a multiple of n); for tests and tools */
+/* x [B][L] -> out [B][Lout], 1 <= B <= 64, Lout >= svc_resample_len(o, n, max lens).  lens HOST int32 [B] (1 <= lens[b] <= L) or
+ * NULL (every clip has L samples); they travel as kernel arguments: consumed before the call returns, nothing is copied or
+ * synchronised.  For m < svc_resample_len(o, n, lens[b]), with j = m mod n and i = m div n,
+ *     out[b][m] = sum_{k = 0}^{ntaps - 1} taps[j][k] * xx[i o + first[j] + k - width],
+ * accumulated in ascending k as one fp32 FMA chain, where xx is x[b] inside [0, lens[b]) and 0.0 outside: samples outside go
+ * through the same chain as zeros, so an output's bits depend on its clip's samples alone, not on its place in a tile, the
+ * batch or the other clips.  Every out[b][m] at and above that count is written as 0.0.  Samples at and above lens[b] are never
+ * read as values (NaN is fine there).  lens[b] == L for all b equals lens == NULL bit for bit.  All sample positions are 64-bit.
+ * A length outside [1, L], B outside [1, 64], Lout too small, a null pointer, x and out overlapping: non-zero, a
+ * svc_last_error() that names the argument, nothing enqueued. */
+int svc_resample(svc_resampler_t* r, const float* x, const int32_t* lens, int B, long L, float* out, long Lout, void* stream);
+
 /* ---------------------------------------------------------------- CAMPPlus style encoder + Kaldi fbank (second half) */
 typedef struct svc_campplus_config {  /* modules/campplus/DTDNN.py:54-62 (CAMPPlus.__init__ defaults; the drivers use embedding_size 192) */
     int feat_dim, embedding_size, growth_rate, bn_size, init_channels, m_channels;

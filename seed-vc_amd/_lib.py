@@ -29,6 +29,7 @@ EXPORTS = [
     "svc_campplus_create", "svc_campplus_destroy", "svc_campplus_forward", "svc_kaldi_fbank_frames", "svc_kaldi_fbank",
     "svc_kaldi_fbank_ragged", "svc_campplus_forward_ragged",
     "svc_mel_create", "svc_mel_destroy", "svc_mel_frames", "svc_mel_forward", "svc_mel_forward_ragged", "svc_mel_min_len",
+    "svc_resampler_create", "svc_resampler_destroy", "svc_resample_len", "svc_resampler_tile", "svc_resample",
     "svc_rmvpe_create", "svc_rmvpe_destroy", "svc_rmvpe_frames", "svc_rmvpe_min_len", "svc_rmvpe_set_plane_budget", "svc_rmvpe_set_timing", "svc_rmvpe_last_timing", "svc_rmvpe_mel",
     "svc_rmvpe_salience", "svc_rmvpe_decode", "svc_rmvpe_f0", "svc_f0_adjust",
     "svc_whisper_create", "svc_whisper_destroy", "svc_whisper_n_windows", "svc_whisper_rows", "svc_whisper_set_window_group",
@@ -168,8 +169,17 @@ def lib():
         l.svc_kaldi_fbank_ragged.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_void_p,
                                              C.c_void_p]
         l.svc_campplus_forward_ragged.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        # RMVPE: lengths as HOST int32 arrays, semitones as a HOST float array
         i32p = C.POINTER(C.c_int32)
+        # resampler: the taps table and the lengths as HOST arrays, sample counts as C long
+        l.svc_resampler_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, i32p, C.POINTER(C.c_float), C.c_void_p, C.POINTER(C.c_void_p)]
+        l.svc_resampler_destroy.argtypes = [C.c_void_p]
+        l.svc_resampler_destroy.restype = None
+        l.svc_resample_len.argtypes = [C.c_int, C.c_int, C.c_long]
+        l.svc_resample_len.restype = C.c_long
+        l.svc_resampler_tile.argtypes = [C.c_void_p]
+        l.svc_resampler_tile.restype = C.c_long
+        l.svc_resample.argtypes = [C.c_void_p, C.c_void_p, i32p, C.c_int, C.c_long, C.c_void_p, C.c_long, C.c_void_p]
+        # RMVPE: lengths as HOST int32 arrays, semitones as a HOST float array
         l.svc_rmvpe_create.argtypes = [C.POINTER(RmvpeConfig), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
         l.svc_rmvpe_set_plane_budget.argtypes = [C.c_void_p, C.c_longlong]
         l.svc_rmvpe_set_timing.argtypes = [C.c_void_p, C.c_int]

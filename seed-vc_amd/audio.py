@@ -5,8 +5,13 @@
 The mel filterbank is `librosa.filters.mel(sr, n_fft, n_mels, fmin, fmax)` in the reference; pass the reference's own
 cached tensor as `mel_basis=` when it is available, otherwise `slaney_mel_basis` restates librosa's default
 (Slaney scale, area normalisation) -- parity of that restatement is unpinned (librosa is absent from the build image).
+
+`Resample(orig_freq, new_freq)(x)` is `torchaudio.functional.resample(x, orig_freq, new_freq)` with its defaults, the step the
+drivers run in front of every 16 kHz model (inference.py:380-406): the filter is built here in float64 (`sinc_resample_taps`) and
+the library runs it as a polyphase dot product (`svc_resample`).
 """
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -112,6 +117,94 @@ class MelSpectrogram:
         try:
             if self._h:
                 _lib.lib().svc_mel_destroy(self._h)
+                self._h = C.c_void_p()
+        except Exception:
+            pass
+
+
+# ----------------------------------------------------------------------------------------- sample-rate conversion
+def _sinc_resample_kernel(orig, new, lowpass_filter_width=6, rolloff=0.99):
+    """torchaudio's `_get_sinc_resample_kernel` with its defaults (sinc_interp_hann), restated: float64 throughout, cast to
+    float32 at the end.  -> (o, n, width, K float32 [n][2 width + o])."""
+    g = math.gcd(int(orig), int(new))
+    o, n = int(orig) // g, int(new) // g
+    base = min(o, n) * rolloff
+    width = math.ceil(lowpass_filter_width * o / base)
+    idx = torch.arange(-width, width + o, dtype=torch.float64) / o
+    t = (torch.arange(0, -n, -1, dtype=torch.float64)[:, None] / n + idx[None, :]) * base
+    t = t.clamp(-lowpass_filter_width, lowpass_filter_width)
+    win = torch.cos(t * math.pi / lowpass_filter_width / 2) ** 2
+    t = t * math.pi
+    K = torch.where(t == 0, torch.ones_like(t), t.sin() / t) * win * (base / o)
+    return o, n, width, K.to(torch.float32)
+
+
+def sinc_resample_taps(orig, new, lowpass_filter_width=6, rolloff=0.99):
+    """The non-zero part of torchaudio's resampling kernel, for `svc_resampler_create`: -> (o, n, width, first int32 [n], taps
+    float32 [n][ntaps]).  In float32 the dense kernel K [n][2 width + o] is exactly 0.0 outside one contiguous run per phase (the
+    Hann window reaches zero where the argument is clamped); first[j] is the column where phase j's run starts, taps[j] the run,
+    padded with 0.0 at the end up to the longest one.  The values are K's, bit for bit."""
+    o, n, width, K = _sinc_resample_kernel(orig, new, lowpass_filter_width, rolloff)
+    nz = K != 0
+    count = nz.sum(dim=1)
+    first = nz.to(torch.int32).argmax(dim=1)
+    last = K.size(1) - 1 - nz.flip(1).to(torch.int32).argmax(dim=1)
+    assert bool((count > 0).all()) and bool((last - first + 1 == count).all()), "a phase's non-zero taps are not contiguous"
+    ntaps = int(count.max())
+    cols = first[:, None] + torch.arange(ntaps)[None, :]
+    taps = torch.where(cols < K.size(1), K.gather(1, cols.clamp(max=K.size(1) - 1)), torch.zeros(()))
+    return o, n, width, first.to(torch.int32), taps.contiguous()
+
+
+class Resample:
+    """`torchaudio.transforms.Resample(orig_freq, new_freq)` (sinc_interp_hann) on the device: `svc_resample`."""
+
+    def __init__(self, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99, device="cuda:0"):
+        self.device = torch.device(device)
+        self.orig_freq, self.new_freq = int(orig_freq), int(new_freq)
+        g = math.gcd(self.orig_freq, self.new_freq)
+        self.o, self.n = self.orig_freq // g, self.new_freq // g
+        self._h = C.c_void_p()
+        self.tile = 0
+        if self.o == self.n:
+            return
+        o, n, width, first, taps = sinc_resample_taps(orig_freq, new_freq, lowpass_filter_width, rolloff)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().svc_resampler_create(o, n, width, taps.size(1), _lib.i32_host(first.tolist()),
+                                                       (C.c_float * taps.numel())(*taps.flatten().tolist()), _lib.stream_ptr(),
+                                                       C.byref(self._h)))
+        self.tile = int(_lib.lib().svc_resampler_tile(self._h))           # outputs one workgroup owns
+
+    def out_len(self, L):
+        """Samples at the new rate for L at the old one: ceil(n L / o)."""
+        return -((-self.n * int(L)) // self.o)
+
+    @torch.inference_mode()
+    def __call__(self, x, lens=None):
+        """x (B, L) or (L,) -> (B, out_len(L)).  lens (B host integers): clips of different lengths in one call -> (out, out_lens);
+        row b's first out_len(lens[b]) samples are those of x[b, :lens[b]] run alone, bit for bit, the samples above are 0.0 and
+        nothing at or above lens[b] is read as a value.  Equal rates return a copy.  Nothing is synchronised."""
+        with torch.cuda.device(self.device):
+            xx = _lib.f32c(x, self.device)
+            if xx.dim() == 1:
+                xx = xx[None, :]
+            B, L = xx.shape
+            if lens is not None:
+                lens = _lib.int_list(lens)
+                if len(lens) != B:
+                    raise ValueError(f"Resample: {len(lens)} lens for a batch of {B}")
+            if self.o == self.n:
+                out = xx.clone()
+            else:
+                out = torch.empty(B, self.out_len(L), device=self.device)
+                _lib.check(_lib.lib().svc_resample(self._h, _lib.ptr(xx), _lib.i32_host(lens) if lens is not None else None, B, L,
+                                                   _lib.ptr(out), out.size(1), _lib.stream_ptr()))
+        return out if lens is None else (out, [self.out_len(v) for v in lens])
+
+    def __del__(self):
+        try:
+            if self._h:
+                _lib.lib().svc_resampler_destroy(self._h)
                 self._h = C.c_void_p()
         except Exception:
             pass

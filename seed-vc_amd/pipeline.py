@@ -149,7 +149,8 @@ def _stack_prompts(records, device=None):
 def enrol_references(mel_fn, campplus, waves, lens, waves_16k, lens_16k):
     """B reference clips of different lengths -> their prompt mels and style vectors, in three library calls instead of B x
     (mel + fbank + CAMPPlus): mel_fn a `MelSpectrogram`, campplus a `CAMPPlus`; waves (B, L) at the mel rate with lens[b]
-    samples each, waves_16k (B, L16) at 16 kHz with lens_16k[b] samples each (the caller resamples, as for one clip).
+    samples each, waves_16k (B, L16) at 16 kHz with lens_16k[b] samples each (`to_16k` makes them on the device;
+    `enrol_references_audio` is this call with that step in front).
     -> dict(prompt (B, n_mels, Pmax) with zeros above each clip's frames, prompt_lens [P_b], style (B, E)): `prompt`,
     `prompt_lens` and `style` of `HotPath.convert_batch_ragged`; prompt[b:b + 1, :, :P_b] and style[b:b + 1] are the
     `target_mel` and `style` of `V2HotPath.prepare_target`.  Row b is what `mel_fn(waves[b:b + 1, :lens[b]])` and
@@ -165,11 +166,29 @@ def enrol_references(mel_fn, campplus, waves, lens, waves_16k, lens_16k):
 
 
 @torch.inference_mode()
+def to_16k(resample, waves, lens):
+    """B clips at the file's rate -> (waves_16k (B, resample.out_len(L)), lens_16k): the drivers'
+    `torchaudio.functional.resample(wave, sr, 16000)` (inference.py:380-406) for a batch of clips of different lengths, in one
+    `svc_resample` call.  resample: an `audio.Resample(sr, 16000)`; waves (B, L) with lens[b] samples each (host integers).  Row b's
+    first lens_16k[b] = resample.out_len(lens[b]) samples are clip b resampled alone, the samples above are 0.0.  This is the one
+    place the 16 kHz length is computed; what it returns is what `enrol_references`, `f0_conditions`, `content_conditions` and
+    `v2_content_tokens` take.  Nothing is synchronised."""
+    return resample(waves, lens)
+
+
+@torch.inference_mode()
+def enrol_references_audio(mel_fn, campplus, resample, waves, lens):
+    """`enrol_references` from audio at the mel rate alone: the 16 kHz copies come from `to_16k` (resample: an
+    `audio.Resample(mel rate, 16000)`), so the prompt mels and style vectors of up to 64 reference clips take four library calls."""
+    return enrol_references(mel_fn, campplus, waves, lens, *to_16k(resample, waves, lens))
+
+
+@torch.inference_mode()
 def f0_conditions(rmvpe, src_16k, src_lens, ref_16k, ref_lens, auto_f0_adjust=True, pitch_shift=0):
     """The drivers' F0 block for B (source, reference) pairs: `F0_ori = rmvpe.infer_from_audio(ref_16k)`,
     `F0_alt = rmvpe.infer_from_audio(src_16k)`, the voiced-median shift in the log domain and the semitone shift, in two
     `RMVPE.f0_batch` calls and one `svc_f0_adjust`.  src_16k (B, Ls) / ref_16k (B, Lr) at 16 kHz with src_lens[b] / ref_lens[b]
-    samples each (host integers); pitch_shift a number of semitones or one per row.
+    samples each (host integers; `to_16k` gives both from audio at the file's rate); pitch_shift a number of semitones or one per row.
     -> (F0_ori (B, To), ori_frames, shifted_f0_alt (B, Ta), alt_frames): the tracks and host frame counts that
     `length_regulator(mel2, ylens=..., f0=F0_ori, f0_lens=ori_frames)` and `length_regulator(S_alt, ylens=..., f0=shifted_f0_alt,
     f0_lens=alt_frames)` take.  Nothing is synchronised."""
@@ -193,7 +212,8 @@ def content_conditions(whisper, length_regulator, src_16k, src_lens, src_ylens, 
     (with their loop over the windows of a long clip), `cond = length_regulator(S_alt, ylens=..., f0=shifted_f0_alt)[0]` and
     `prompt_condition = length_regulator(S_ori, ylens=..., f0=F0_ori)[0]`: one `WhisperContent.content_batch` call over the 2 B clips
     and two regulator calls, with no host round trip between the stages.  src_16k (B, Ls) / ref_16k (B, Lr) at 16 kHz with
-    src_lens[b] / ref_lens[b] samples each (host integers); src_ylens / ref_ylens: the target frame counts (B integers);
+    src_lens[b] / ref_lens[b] samples each (host integers; `to_16k` gives both from audio at the file's rate); src_ylens /
+    ref_ylens: the target frame counts (B integers);
     f0_src / f0_ref: None, or (track (B, T), frames) pairs as `f0_conditions` returns them; overlap_s: the windows' overlap (the
     drivers' 5 s).
     -> (cond (B, max(src_ylens), C), prompt_condition (B, max(ref_ylens), C))."""
@@ -583,7 +603,7 @@ def v2_content_tokens(astral, waves_16k, lens, overlap_s=5.0):
     `AstralTokenizer.tokens_batch` call (HuBERT once per window, the wide head 0 and the narrow head 1 on the same rows) with the
     duration reduction of the narrow tokens in the same call, then one host synchronisation (the reduced counts).
 
-    waves_16k (B, L), lens B host integers -> a list of B records dict(wide (1, R), narrow (1, R), narrow_reduced (1, n)) of int64
+    waves_16k (B, L), lens B host integers (`to_16k` gives both from audio at the file's rate) -> a list of B records dict(wide (1, R), narrow (1, R), narrow_reduced (1, n)) of int64
     device tensors.  The chain, for a source s and a target t of the list:
 
         tok = v2_content_tokens(astral, waves, lens)
