@@ -752,6 +752,43 @@ int svc_sola_step(const float* wave, long long stride, int start, int N, float* 
                   const float* fade_in, const float* fade_out, int block, int Lb, int Ls, float* out, int32_t* offsets,
                   void* stream);
 
+/* ---------------------------------------------------------------- real-time sessions: the audio history of one block step
+ * (DESIGN.md 8l).  Replaces the `input_wav` / `input_wav_res` lines of the reference GUI's audio callback (two clone-shifts, a
+ * resample of the last block with 2 zc samples of history, a slice copy; restated from memory) and the gather into the dense
+ * batch a content encoder takes, for N streams in one launch.  Conventions of svc_sola_step: `slots` is HOST int32 [N],
+ * consumed before the call returns; arguments are checked before anything is launched; nothing synchronises, copies or
+ * allocates.
+ *
+ * Per listed stream, s = slots[k]:  m = Lin / zc;  x = hist[s] ‖ block[k] (2 zc + Lin samples);  y = what svc_resample gives for
+ * x alone with r's taps (the same ascending-k fp32 FMA chain, zeros outside [0, len x)), y = x where r is NULL (equal rates);
+ * shift = m z16, n_new = shift + z16;  with c_old the slot's context before the call,
+ *     c[0 : L16 - n_new] = c_old[shift : L16 - z16]          c[L16 - n_new :] = y[z16 : z16 + n_new]
+ * (the last z16 samples of a context are computed again by the next push, then with real audio to their right instead of zero
+ * padding).  ctx[k] = c, the slot's context becomes c, hist[s] = x[-2 zc:].  Slots that are not listed keep every bit.
+ *
+ * `ring` holds svc_rt_ring_floats(max_slots, L16) = 2 max_slots (L16 + 1) floats: two planes [2][max_slots][L16], then
+ * uint64 tickets[max_slots].  A push reads a slot's current plane and writes its other one, so no workgroup reads what another
+ * writes; tickets[s] counts the workgroups that pushed to slot s, svc_rt_push_tiles(L16) per push, and the slot's current plane
+ * is (tickets[s] / svc_rt_push_tiles(L16)) & 1.  All zeros is a valid start (empty contexts).  To clear a slot, zero both of its
+ * planes and its hist row; its tickets word stays.  `ring` is 8-byte aligned; 16-byte accesses are used where shift, z16 and L16 are
+ * multiples of 4 and ring and ctx are 16-byte aligned.
+ *
+ * Refused (non-zero, svc_last_error() names it, no state touched): Lin not a positive multiple of zc; L16 < n_new;
+ * svc_resample_len(o, n, 2 zc + Lin) < z16 + n_new; zc % o != 0 or z16 % n != 0 (a block must start at resampling phase 0;
+ * o = n = 1 for r == NULL); N outside 1 .. 64; a slot outside [0, max_slots) or listed twice; stride < Lin; null pointers;
+ * block, hist, ring, ctx overlapping. */
+int svc_rt_push_tiles(int L16);                          /* workgroups per stream and push; needs no GPU */
+long long svc_rt_ring_floats(int max_slots, int L16);    /* floats to allocate for `ring`; needs no GPU */
+int svc_rt_push(const svc_resampler_t* r,            /* NULL: equal rates, samples are copied */
+                const float* block, long long stride, int Lin,   /* block[k][0..Lin): new samples of slots[k], stream rate */
+                int N, const int32_t* slots, int max_slots,      /* HOST int32[N], consumed before return (as svc_sola_step) */
+                int zc, int z16,                                  /* samples per 20 ms at the stream rate / content rate */
+                float* hist,        /* [max_slots][2 zc]  state */
+                float* ring,        /* state: svc_rt_ring_floats(max_slots, L16) floats, layout above */
+                int L16,
+                float* ctx,         /* out [N][L16]: row k = the new context of slots[k], dense, what the encoder takes */
+                void* stream);
+
 /* ---------------------------------------------------------------- op-level entry points (parity tests) */
 /* C[M][N] (fp32) = act(A[M][K] * W[N][K]^T + bias) ; dtype 0: operands rounded to fp16, 1: fp32 MFMA.  act: a KG_ACT_* value
  * (0 none, 1 SiLU, 2 ELU, 3 leaky ReLU 0.1, 4 tanh, 5 abs, 6 clamp, 7 sigmoid, 8 GELU in the exact erf form). */

@@ -16,26 +16,17 @@
 #include <algorithm>
 #include <vector>
 
-#include "model_util.h"
+#include "resample_core.h"
 
 using namespace svc;
 
 namespace {
 
-constexpr int RS_THREADS = 256;
-constexpr int RS_ROWS = 4;                  // outputs per work item, one phase in four periods
 constexpr int RS_MAX_B = 64;
 constexpr int RS_SPAN_BUDGET = 6144;        // floats of LDS a tile's input span may take when G > 1 (24 KB: six workgroups per CU)
 constexpr int RS_SPAN_LIMIT = 16000;        // floats, G = 1 (64 KB of static + dynamic LDS is what a launch gets without opting in)
 
 struct RsLens { int32_t v[RS_MAX_B]; };
-
-struct RsGeom {
-    int o, n, width, ntaps;
-    int G;                                  // periods per row group: a tile is RS_ROWS * G periods = RS_ROWS * G * n outputs
-    int fmin;                               // min first[j]: the tile's span starts at period * o + fmin - width
-    int span;                               // floats of LDS: (RS_ROWS G - 1) o + (fmax - fmin) + ntaps + 3, rounded up to 4
-};
 
 // x [B][L], out [B][Lout]; taps_kn [ntaps][n]; first [n]
 __global__ __launch_bounds__(RS_THREADS) void resample_kernel(const float* __restrict__ x, long L, RsLens lens, RsGeom q,
@@ -72,21 +63,10 @@ __global__ __launch_bounds__(RS_THREADS) void resample_kernel(const float* __res
         *reinterpret_cast<float4*>(xs + v) = t;
     }
     __syncthreads();
-    // ---- work item w = g n + j: phase j of periods g + G r.  Index of its first sample in xs: (g + G r) o + first[j] - fmin + shift
-    const int step = q.G * q.o;
+    // ---- work item w = g n + j: phase j of periods g + G r (resample_core.h: the dot product shared with svc_rt_push)
     for (int w = threadIdx.x; w < S; w += RS_THREADS) {
-        const int g = w / q.n, j = w - g * q.n;
-        const float* s0 = xs + g * q.o + first[j] - q.fmin + shift;
-        const float* tp = taps_kn + j;
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-#pragma unroll 4
-        for (int k = 0; k < q.ntaps; ++k) {                     // ascending k, one FMA chain per output
-            const float t = tp[(long)k * q.n];
-            a0 = fmaf(t, s0[k], a0);
-            a1 = fmaf(t, s0[k + step], a1);
-            a2 = fmaf(t, s0[k + 2 * step], a2);
-            a3 = fmaf(t, s0[k + 3 * step], a3);
-        }
+        float a0, a1, a2, a3;
+        rs_dot4(xs, shift, q, taps_kn, first, w, a0, a1, a2, a3);
         const long m = m0 + w;
         if (m < Lout) orow[m] = m < nout ? a0 : 0.f;
         if (m + S < Lout) orow[m + S] = m + S < nout ? a1 : 0.f;
@@ -96,13 +76,6 @@ __global__ __launch_bounds__(RS_THREADS) void resample_kernel(const float* __res
 }
 
 }  // namespace
-
-struct svc_resampler {
-    RsGeom q;
-    Arena mem;
-    float* taps_kn = nullptr;
-    int* first = nullptr;
-};
 
 extern "C" {
 

@@ -763,6 +763,29 @@ def realtime_geometry(sr, hop, block_time, crossfade_time, extra_time, extra_tim
                 skip_tail=skip_tail, return_length=return_length)
 
 
+def realtime_input_geometry(sr, block_time, crossfade_time, extra_time_ce, extra_time_right, content_rate=16000):
+    """The input side of the reference GUI's buffer arithmetic (real-time-gui.py: `start_vc`, quoted from memory: correct it
+    here if the reference differs).  zc = sr // 50 and z16 = content_rate // 50 samples are 20 ms at the two rates; every time is
+    rounded to a multiple of zc as in `realtime_geometry`; `input_wav` has extra_ce + crossfade + sola_search (zc) + block +
+    extra_right samples and `input_wav_res` z16 * len(input_wav) // zc.
+    -> dict(zc, z16, Lin (= block: the samples a block step takes), L16 (the content-rate context), hist (= 2 zc: the
+    stream-rate samples kept between blocks), rows (L16 // z16 - 1: what a stride-z16 convolutional extractor with a
+    z16 + z16 // 4 receptive field, wav2vec 2.0, yields for the context; Whisper yields L16 // z16 + 1)).
+    ValueError where sr or content_rate is not a multiple of 50: a block must start at resampling phase 0."""
+    sr, content_rate = int(sr), int(content_rate)
+    if sr < 50 or content_rate < 50 or sr % 50 or content_rate % 50:
+        raise ValueError(f"realtime_input_geometry: sr {sr} and content_rate {content_rate} must be multiples of 50 "
+                         f"(20 ms must be a whole number of samples at both rates)")
+    zc, z16 = sr // 50, content_rate // 50
+    to_frame = lambda t: int(round(t * sr / zc)) * zc                                              # noqa: E731
+    block = to_frame(block_time)
+    total = to_frame(extra_time_ce) + to_frame(crossfade_time) + zc + block + to_frame(extra_time_right)
+    L16 = z16 * total // zc
+    if block < zc or L16 < (block // zc + 1) * z16:
+        raise ValueError(f"realtime_input_geometry: a block of {block} samples does not fit a context of {L16}")
+    return dict(zc=zc, z16=z16, Lin=block, L16=L16, hist=2 * zc, rows=L16 // z16 - 1)
+
+
 def gui_fade_windows(Lb):
     """(fade_in, fade_out) of the reference GUI: sin(0.5 pi linspace(0, 1, Lb))^2 and 1 - fade_in, float32, computed on the
     host.  The engine takes its windows as arrays because device and host `sin` differ in the last bit."""
@@ -815,6 +838,7 @@ class RealtimeEngine:
         self.state = torch.zeros(self.max_streams, Lb, device=self.device, dtype=torch.float32)      # row = a stream's sola_buffer
         self._streams = {}                  # slot -> (prompt_condition, mel, style): a record of `_stack_prompts`
         self._stacked = (None, None)
+        self._audio = None                  # `attach_audio`: the input side of `step_audio`
 
     def open(self, prompt_condition, mel2, style2):
         """A new stream on the reference (prompt_condition (1, P, Dc), mel2 (1, C, P), style2 (1, Ds)) -> its slot, the
@@ -832,6 +856,7 @@ class RealtimeEngine:
         self._streams[slot] = tuple(_lib.f32c(t, self.device) for t in (prompt_condition, mel2, style2))
         self._stacked = (None, None)
         self.state[slot].zero_()
+        self._zero_audio(slot)
         return slot
 
     def _check_slot(self, slot, what):
@@ -849,6 +874,7 @@ class RealtimeEngine:
         """Zeroes the stream's SOLA buffer (the GUI does so when a stream restarts)."""
         self._check_slot(slot, "reset")
         self.state[slot].zero_()
+        self._zero_audio(slot)
 
     def _stack_prompts(self, slots):
         """Padded batch tensors of the streams' references (kept while the same slots come back in the same order)."""
@@ -915,6 +941,92 @@ class RealtimeEngine:
         if return_parts:
             return out, dict(mel=vc, infer=wave[:, self.start:self.start + self.n_inf], offsets=offsets)
         return out
+
+    # ------------------------------------------------------------------------------------------- audio in
+    def attach_audio(self, content, resample, Lin, L16, ce_dit_difference):
+        """The input side of a block step: after this call `step_audio` takes the microphone block itself.  content: anything
+        with `semantic_fn((n, L16) samples) -> (n, T, D)` (Wav2Vec2Content, WhisperContent); resample: an
+        `audio.Resample(stream_rate, content_rate)`, both rates multiples of 50; Lin: samples per block at the stream rate, a
+        multiple of zc = stream_rate // 50; L16: the content-rate context per stream (`realtime_input_geometry`);
+        ce_dit_difference: seconds of content dropped at the front (the GUI's `S_alt[:, int(ce_dit_difference * 50):]`).
+        Allocates the per-slot history (max_streams, 2 zc) and the two-plane context ring of `svc_rt_push`, zeros; `open` and
+        `reset` zero a slot's rows as they zero its SOLA buffer."""
+        orig, new = int(resample.orig_freq), int(resample.new_freq)
+        Lin, L16 = int(Lin), int(L16)
+        if orig < 50 or new < 50 or orig % 50 or new % 50:
+            raise ValueError(f"RealtimeEngine.attach_audio: the rates {orig} and {new} must be multiples of 50")
+        zc, z16 = orig // 50, new // 50
+        if Lin < zc or Lin % zc:
+            raise ValueError(f"RealtimeEngine.attach_audio: Lin = {Lin} is not a positive multiple of zc = {zc}")
+        n_new = (Lin // zc + 1) * z16
+        if L16 < n_new:
+            raise ValueError(f"RealtimeEngine.attach_audio: L16 = {L16} is below the {n_new} samples a block renews")
+        ce = int(float(ce_dit_difference) * 50)
+        if ce < 0:
+            raise ValueError("RealtimeEngine.attach_audio: ce_dit_difference is negative")
+        if not callable(getattr(content, "semantic_fn", None)):
+            raise ValueError("RealtimeEngine.attach_audio: content has no semantic_fn")
+        ms, planes = self.max_streams, 2 * self.max_streams * L16
+        ring = torch.zeros(int(_lib.lib().svc_rt_ring_floats(ms, L16)), device=self.device, dtype=torch.float32)
+        self._audio = dict(content=content, resample=resample, Lin=Lin, L16=L16, zc=zc, z16=z16, ce=ce, ring=ring,
+                           planes=ring[:planes].view(2, ms, L16), tickets=ring[planes:].view(torch.int64),
+                           tiles=int(_lib.lib().svc_rt_push_tiles(L16)),
+                           hist=torch.zeros(ms, 2 * zc, device=self.device, dtype=torch.float32))
+
+    def _zero_audio(self, slot):
+        if self._audio is not None:
+            self._audio["planes"][:, slot].zero_()
+            self._audio["hist"][slot].zero_()
+
+    def audio_context(self, slot):
+        """The content-rate context (L16,) of an open slot as the last `step_audio` left it (a copy; this call synchronises to
+        read the slot's plane bit: it is for tests and tools, not for the block loop)."""
+        self._check_slot(slot, "audio_context")
+        if self._audio is None:
+            raise ValueError("RealtimeEngine.audio_context: attach_audio has not been called")
+        a = self._audio
+        return a["planes"][(int(a["tickets"][slot]) // a["tiles"]) & 1, slot].clone()
+
+    @torch.inference_mode()
+    def step_audio(self, slots, audio, n_timesteps, inference_cfg_rate, z=None, vocoder_kwargs=None, return_parts=False):
+        """One block from audio: audio (n, Lin) float32 at the stream rate, row k the new samples of slots[k].  One
+        `svc_rt_push` (history, resampling, context shift and the dense batch), then
+        `content.semantic_fn(ctx)[:, int(ce_dit_difference * 50):]`, then `step`.  -> as `step`; with return_parts the dict also
+        carries ctx (n, L16) and content (n, T, D).  Lengths and slots are host integers: nothing synchronises."""
+        return self._step_audio(slots, audio, n_timesteps, inference_cfg_rate, z, vocoder_kwargs, return_parts, None)
+
+    @torch.inference_mode()
+    def step_audio_seeded(self, slots, audio, n_timesteps, inference_cfg_rate, seeds, vocoder_kwargs=None, return_parts=False):
+        """`step_audio` with per-block seeds in place of z and the vocoder's draws, as `step_seeded`."""
+        if seeds is None:
+            raise ValueError("RealtimeEngine.step_audio_seeded: seeds is None")
+        return self._step_audio(slots, audio, n_timesteps, inference_cfg_rate, None, vocoder_kwargs, return_parts, seeds)
+
+    def _step_audio(self, slots, audio, n_timesteps, inference_cfg_rate, z, vocoder_kwargs, return_parts, seeds):
+        a = self._audio
+        if a is None:
+            raise ValueError("RealtimeEngine.step_audio: attach_audio has not been called")
+        slots = [int(s) for s in slots]
+        for s in slots:
+            self._check_slot(s, "step_audio")
+        if len(set(slots)) != len(slots):
+            raise ValueError(f"RealtimeEngine.step_audio: a slot appears twice in {slots}")
+        n = len(slots)
+        if not 1 <= n <= 64:
+            raise ValueError(f"RealtimeEngine.step_audio: {n} slots, 1 .. 64 per call")
+        if audio.dim() != 2 or tuple(audio.shape) != (n, a["Lin"]):
+            raise ValueError(f"RealtimeEngine.step_audio: audio {tuple(audio.shape)} is not (n = {n}, Lin = {a['Lin']})")
+        with torch.cuda.device(self.device):
+            block = _lib.f32c(audio, self.device)
+            ctx = torch.empty(n, a["L16"], device=self.device, dtype=torch.float32)
+            _lib.check(_lib.lib().svc_rt_push(a["resample"]._h, _lib.ptr(block), block.stride(0), a["Lin"], n, _lib.i32_host(slots),
+                                              self.max_streams, a["zc"], a["z16"], _lib.ptr(a["hist"]), _lib.ptr(a["ring"]), a["L16"],
+                                              _lib.ptr(ctx), _lib.stream_ptr()))
+            content = a["content"].semantic_fn(ctx)[:, a["ce"]:]
+        res = self._step(slots, content, n_timesteps, inference_cfg_rate, z, vocoder_kwargs, return_parts, seeds)
+        if return_parts:
+            res[1].update(ctx=ctx, content=content)
+        return res
 
 
 # ----------------------------------------------------------------------------------------- multi-GPU sharding
