@@ -752,6 +752,27 @@ int svc_sola_step(const float* wave, long long stride, int start, int N, float* 
                   const float* fade_in, const float* fade_out, int block, int Lb, int Ls, float* out, int32_t* offsets,
                   void* stream);
 
+/* svc_sola_step behind a prologue, in the same launch: output at a rate other than the model's (the GUI's
+ * `resampler2` before SOLA) and the GUI's `infer_wav = zeros` while its VAD reports no speech.  svc_sola_step is this call with
+ * r = NULL, speech = NULL and no `infer` row (the prologue is compiled out of that form).  Per stream k:
+ *   y = what svc_resample gives for wave[k][start : start + n_in] alone (rs_dot4's ascending-k fp32 FMA chain, zeros outside the
+ *       segment); the segment itself where r is NULL;  y = +0.0 everywhere where speech[k] == 0  (`speech`: HOST int32 [N],
+ *       consumed before the call returns, NULL = all 1)
+ *   infer[k] = y  (device out [N][block + Lb + Ls]: what SOLA saw), then svc_sola_step's arithmetic on y with start 0 and the given
+ *       block, Lb, Ls, fade_in, fade_out, all at the output rate.
+ * out, sola_state, offsets and infer are bit-identical to svc_resample on the slice followed by svc_sola_step on its result.
+ * One workgroup per stream, one launch per 64 streams; the dynamic LDS is the larger of the two phases, at most 64 KB.
+ * Refused (non-zero, nothing touched): everything svc_sola_step refuses, and block + Lb + Ls != svc_resample_len(o, n, n_in)
+ * (!= n_in where r is NULL); start + n_in > stride; a resampler whose span is above the 16000 floats of svc_rt_push; infer NULL
+ * or overlapping wave, sola_state, out, the windows or offsets; a speech entry other than 0 or 1. */
+int svc_rt_out(const svc_resampler_t* r,       /* model rate -> output rate; NULL: equal rates */
+               const float* wave, long long stride, int start, int n_in, int N,
+               float* sola_state, int max_slots, const int32_t* slots,
+               const int32_t* speech,          /* HOST int32[N] or NULL (= all 1), consumed before return */
+               const float* fade_in, const float* fade_out, int block, int Lb, int Ls,
+               float* infer,                   /* device out [N][block + Lb + Ls]: what SOLA saw */
+               float* out, int32_t* offsets, void* stream);
+
 /* ---------------------------------------------------------------- real-time sessions: the audio history of one block step
  * (DESIGN.md 8l).  Replaces the `input_wav` / `input_wav_res` lines of the reference GUI's audio callback (two clone-shifts, a
  * resample of the last block with 2 zc samples of history, a slice copy; restated from memory) and the gather into the dense
@@ -788,6 +809,32 @@ int svc_rt_push(const svc_resampler_t* r,            /* NULL: equal rates, sampl
                 int L16,
                 float* ctx,         /* out [N][L16]: row k = the new context of slots[k], dense, what the encoder takes */
                 void* stream);
+
+/* svc_rt_push behind the input noise gate of the reference GUI (a causal statement of the GUI's gate: its window
+ * of 4 zc, hop zc, dB scale and off-switch, not its half-frame buffer offsets sample for sample).  svc_rt_push is this call with
+ * the three gate arguments NULL.  Per listed stream s = slots[k], with m = Lin / zc frames of 20 ms:
+ *   e_j = sum_{i<zc} block[k][j zc + i]^2 in fp32; the summation order is a function of zc alone, so a frame's energy does not
+ *         depend on N, k, the slot, Lin or j;
+ *   (g0, g1, g2) = gate_e[s]: the energies of the three raw frames before this block, oldest first; ..., g0, g1, g2, e_0, ...,
+ *         e_{m-1} is the stream's sequence of frame energies;
+ *   E_j = ((a + b) + c) + d over the four most recent frames ending at frame j, oldest first, in fp32: the energy of the last
+ *         80 ms;
+ *   frame j is muted when E_j < gate_pow[k] (a NaN energy never mutes); gate_mask[k][j] = 1 where it is, else 0;
+ *   x' = the block with its muted frames replaced by +0.0; everything else is svc_rt_push on x', bit for bit: ctx, both ring
+ *         planes, the ticket and hist (hist holds gated samples);
+ *   gate_e[s] becomes the energies of the last three RAW frames of this block.  Energies are tracked while the gate is off
+ *         (gate_pow NULL or 0.0f) too, so a threshold can be switched on in mid-stream; rows of gate_e of slots that are not
+ *         listed keep every bit.
+ * For a threshold in dB (RMS re 1.0) the host passes float(4 zc 10^(dB / 10)); at or below -60 dB it passes 0.0f, the GUI's "off".
+ * Refused (nothing touched): everything svc_rt_push refuses, and gate_e NULL while gate_pow is given; a negative or NaN
+ * gate_pow[k]; gate_e or gate_mask overlapping the other buffers or each other; Lin / zc above 256 while gate_e is given (the
+ * frame energies of a block are held in LDS). */
+int svc_rt_push_gated(const svc_resampler_t* r, const float* block, long long stride, int Lin, int N, const int32_t* slots,
+                      int max_slots, int zc, int z16, float* hist, float* ring, int L16, float* ctx,
+                      const float* gate_pow,   /* HOST float[N], consumed before return (as slots); NULL or 0.0f = gate off */
+                      float* gate_e,           /* device state [max_slots][3]; zeros = a fresh stream                       */
+                      int32_t* gate_mask,      /* device out [N][Lin / zc], 1 = frame muted; may be NULL                    */
+                      void* stream);
 
 /* ---------------------------------------------------------------- op-level entry points (parity tests) */
 /* C[M][N] (fp32) = act(A[M][K] * W[N][K]^T + bias) ; dtype 0: operands rounded to fp16, 1: fp32 MFMA.  act: a KG_ACT_* value

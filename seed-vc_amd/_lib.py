@@ -26,6 +26,7 @@ EXPORTS = [
     "svc_ar_session_active",
     "svc_lr_create", "svc_lr_destroy", "svc_lr_forward", "svc_crossfade",
     "svc_chunks_gather_cond", "svc_chunks_assemble", "svc_sola_step", "svc_rt_push", "svc_rt_push_tiles", "svc_rt_ring_floats",
+    "svc_rt_out", "svc_rt_push_gated",
     "svc_campplus_create", "svc_campplus_destroy", "svc_campplus_forward", "svc_kaldi_fbank_frames", "svc_kaldi_fbank",
     "svc_kaldi_fbank_ragged", "svc_campplus_forward_ragged",
     "svc_mel_create", "svc_mel_destroy", "svc_mel_frames", "svc_mel_forward", "svc_mel_forward_ragged", "svc_mel_min_len",
@@ -156,6 +157,11 @@ def lib():
                                     C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         l.svc_rt_push.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int,
                                   C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        # the live block step: the gate thresholds and the speech flags as HOST arrays
+        l.svc_rt_push_gated.argtypes = l.svc_rt_push.argtypes[:-1] + [C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p]
+        l.svc_rt_out.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int32),
+                                 C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p]
         l.svc_rt_push_tiles.argtypes = [C.c_int]
         l.svc_rt_ring_floats.argtypes = [C.c_int, C.c_int]
         l.svc_rt_ring_floats.restype = C.c_longlong

@@ -1,6 +1,6 @@
-// The polyphase dot product of the resampler, shared by `svc_resample` (resample.hip) and `svc_rt_push`
-// (rt_audio.hip): the handle, the tile geometry and the ONE statement of an output's FMA chain.  Both kernels stage an input
-// span in LDS and call `rs_dot4` on it, so a sample of a real-time context and the same sample of a one-shot conversion run
+// The polyphase dot product of the resampler, shared by `svc_resample` (resample.hip), `svc_rt_push`
+// (rt_audio.hip) and `svc_rt_out` (sola.hip): the handle, the tile geometry and the ONE statement of an output's FMA chain.  All
+// three kernels stage an input span in LDS and call `rs_dot4` on it, so a sample of a real-time context and the same sample of a one-shot conversion run
 // the same instructions in the same order.
 #pragma once
 #include "model_util.h"

@@ -4,6 +4,7 @@ multi-GPU sharding of utterance batches.
 """
 import collections
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -786,6 +787,34 @@ def realtime_input_geometry(sr, block_time, crossfade_time, extra_time_ce, extra
     return dict(zc=zc, z16=z16, Lin=block, L16=L16, hist=2 * zc, rows=L16 // z16 - 1)
 
 
+def realtime_output_geometry(g, sr_model, sr_out):
+    """The SOLA geometry of `realtime_geometry` (its dict `g`, or any dict with block, Lb, Ls) at another output rate: the GUI
+    resamples `infer_wav` from the model's rate to the sound card's before SOLA (`resampler2`), so the splice runs in 20 ms
+    units of zc_o = sr_out // 50 samples instead of zc_m = sr_model // 50.  -> dict(zc, block, Lb, Ls, n_inf) at the output
+    rate.  ValueError where a rate is not a multiple of 50 or a length is not a multiple of zc_m."""
+    sr_model, sr_out = int(sr_model), int(sr_out)
+    if sr_model < 50 or sr_out < 50 or sr_model % 50 or sr_out % 50:
+        raise ValueError(f"realtime_output_geometry: the rates {sr_model} and {sr_out} must be multiples of 50 "
+                         f"(20 ms must be a whole number of samples at both rates)")
+    zc_m, zc_o = sr_model // 50, sr_out // 50
+    out = dict(zc=zc_o)
+    for key in ("block", "Lb", "Ls"):
+        v = int(g[key])
+        if v % zc_m:
+            raise ValueError(f"realtime_output_geometry: {key} = {v} is not a multiple of zc = {zc_m} samples")
+        out[key] = v // zc_m * zc_o
+    out["n_inf"] = out["block"] + out["Lb"] + out["Ls"]
+    return out
+
+
+def gate_power(threshold_db, zc):
+    """The GUI's noise-gate threshold in dB (RMS re 1.0) as `svc_rt_push_gated` takes it: the energy of 4 zc samples at that RMS,
+    float32(4 zc 10^(dB / 10)); None or at most -60 dB -> 0.0, the GUI's "off"."""
+    if threshold_db is None or float(threshold_db) <= -60.0:
+        return 0.0
+    return float(np.float32(4.0 * zc * 10.0 ** (float(threshold_db) / 10.0)))
+
+
 def gui_fade_windows(Lb):
     """(fade_in, fade_out) of the reference GUI: sin(0.5 pi linspace(0, 1, Lb))^2 and 1 - fade_in, float32, computed on the
     host.  The engine takes its windows as arrays because device and host `sin` differ in the last bit."""
@@ -839,6 +868,9 @@ class RealtimeEngine:
         self._streams = {}                  # slot -> (prompt_condition, mel, style): a record of `_stack_prompts`
         self._stacked = (None, None)
         self._audio = None                  # `attach_audio`: the input side of `step_audio`
+        self._out = None                    # `attach_output`: the splice at another rate than the model's
+        self._speech = {}                   # slot -> the caller's VAD flag (`set_speech`)
+        self._gate = {}                     # slot -> gate threshold as an energy of 4 zc samples (`set_gate`); absent: off
 
     def open(self, prompt_condition, mel2, style2):
         """A new stream on the reference (prompt_condition (1, P, Dc), mel2 (1, C, P), style2 (1, Ds)) -> its slot, the
@@ -857,6 +889,8 @@ class RealtimeEngine:
         self._stacked = (None, None)
         self.state[slot].zero_()
         self._zero_audio(slot)
+        self._speech[slot] = True
+        self._gate.pop(slot, None)
         return slot
 
     def _check_slot(self, slot, what):
@@ -869,12 +903,69 @@ class RealtimeEngine:
         self._check_slot(slot, "close")
         del self._streams[slot]
         self._stacked = (None, None)
+        self._speech.pop(slot, None)
+        self._gate.pop(slot, None)
 
     def reset(self, slot):
         """Zeroes the stream's SOLA buffer (the GUI does so when a stream restarts)."""
         self._check_slot(slot, "reset")
         self.state[slot].zero_()
         self._zero_audio(slot)
+        self._speech[slot] = True
+
+    # ------------------------------------------------------------------------------------------- live settings (DESIGN.md 8m)
+    def attach_output(self, resample_out, fade_in=None, fade_out=None):
+        """Output at another rate than the model's: resample_out is an `audio.Resample(model_rate, output_rate)`, both rates
+        multiples of 50.  With zc_m and zc_o the 20 ms counts at the two rates, block, sola_buffer and sola_search must be
+        multiples of zc_m and zc_m a multiple of the reduced model rate o (the GUI's geometry always is; `realtime_geometry` with
+        the model's sr yields it).  The output geometry is the model's scaled by zc_o / zc_m (`realtime_output_geometry`); the
+        SOLA state is reallocated as (max_streams, Lb_out) zeros and the windows default to `gui_fade_windows(Lb_out)`.  Allowed
+        only while no stream is open.  After it every step method returns (n, block_out) at the output rate, and
+        return_parts["infer"] is the (n, n_inf_out) row SOLA saw: one `svc_rt_out` resamples and splices."""
+        if self._streams:
+            raise ValueError("RealtimeEngine.attach_output: streams are open")
+        if (fade_in is None) != (fade_out is None):
+            raise ValueError("RealtimeEngine.attach_output: give both windows or neither")
+        orig, new = int(resample_out.orig_freq), int(resample_out.new_freq)
+        try:
+            g = realtime_output_geometry(dict(block=self.block, Lb=self.Lb, Ls=self.Ls), orig, new)
+        except ValueError as e:
+            raise ValueError(f"RealtimeEngine.attach_output: {e}") from None
+        o = orig // math.gcd(orig, new)
+        if (orig // 50) % o:
+            raise ValueError(f"RealtimeEngine.attach_output: 20 ms at the model rate ({orig // 50} samples) is not a multiple of "
+                             f"the reduced rate o = {o}")
+        if fade_in is None:
+            fade_in, fade_out = gui_fade_windows(g["Lb"])
+        fade_in, fade_out = (_lib.f32c(torch.as_tensor(f), self.device).reshape(-1) for f in (fade_in, fade_out))
+        if fade_in.numel() != g["Lb"] or fade_out.numel() != g["Lb"]:
+            raise ValueError(f"RealtimeEngine.attach_output: the windows must have {g['Lb']} entries at the output rate")
+        self._out = dict(g, resample=resample_out, fade_in=fade_in, fade_out=fade_out)
+        self.state = torch.zeros(self.max_streams, g["Lb"], device=self.device, dtype=torch.float32)
+
+    def set_speech(self, slot, detected):
+        """The GUI's `vad_speech_detected` for one stream, from whatever VAD the caller runs: True on `open` and `reset`; while
+        False the stream's blocks are zeros before SOLA (the GUI's `infer_wav = zeros`).  The model still runs for the stream, so
+        the batch stays one call."""
+        self._check_slot(slot, "set_speech")
+        self._speech[slot] = bool(detected)
+
+    def set_gate(self, slot, threshold_db):
+        """The GUI's input noise-gate threshold for one stream, in dB (RMS re 1.0): 20 ms frames whose last 80 ms lie below it are
+        zeroed before they enter the history (`svc_rt_push_gated`).  None or at most -60: off, the default on `open`; kept across
+        `reset`.  Needs `attach_audio`."""
+        self._check_slot(slot, "set_gate")
+        if self._audio is None:
+            raise ValueError("RealtimeEngine.set_gate: attach_audio has not been called")
+        p = gate_power(threshold_db, self._audio["zc"])
+        if not p >= 0.0 or p == float("inf"):
+            raise ValueError(f"RealtimeEngine.set_gate: threshold_db = {threshold_db!r}")
+        if p == 0.0:
+            self._gate.pop(slot, None)
+            return
+        if slot not in self._gate:          # energies are tracked only by gated pushes: a gate switched on starts from none
+            self._audio["gate_e"][slot].zero_()
+        self._gate[slot] = p
 
     def _stack_prompts(self, slots):
         """Padded batch tensors of the streams' references (kept while the same slots come back in the same order)."""
@@ -890,7 +981,8 @@ class RealtimeEngine:
         """One block for the streams `slots` (a list of open slots, no slot twice); content (n, Tin, Din), row k for
         slots[k]; z: the sampler's noise (n, C, Pmax + S), torch.randn when None; vocoder_kwargs: passed to the vocoder call
         (HiFT's pinned draws); `step_seeded` takes seeds instead of the tensors.  -> (n, block) float32 on the device; with
-        return_parts also dict(mel (n, C, S), infer (n, n_inf), offsets (n,) int32)."""
+        return_parts also dict(mel (n, C, S), infer (n, n_inf), offsets (n,) int32).  After `attach_output` block and n_inf
+        are those of the output rate; a slot whose `set_speech` flag is False gets a row of zeros before SOLA."""
         return self._step(slots, content, n_timesteps, inference_cfg_rate, z, vocoder_kwargs, return_parts, None)
 
     @torch.inference_mode()
@@ -914,9 +1006,11 @@ class RealtimeEngine:
         n, dev, S = len(slots), self.device, self.S
         if content.dim() != 3 or content.size(0) != n:
             raise ValueError(f"RealtimeEngine.step: content {tuple(content.shape)} is not (n = {n}, Tin, Din)")
+        live = self._out
         if n == 0:
-            out = torch.zeros(0, self.block, device=dev)
-            parts = dict(mel=torch.zeros(0, self.cfm.in_channels, S, device=dev), infer=torch.zeros(0, self.n_inf, device=dev),
+            out = torch.zeros(0, live["block"] if live else self.block, device=dev)
+            parts = dict(mel=torch.zeros(0, self.cfm.in_channels, S, device=dev),
+                         infer=torch.zeros(0, live["n_inf"] if live else self.n_inf, device=dev),
                          offsets=torch.zeros(0, dtype=torch.int32, device=dev))
             return (out, parts) if return_parts else out
         with torch.cuda.device(dev):
@@ -933,13 +1027,25 @@ class RealtimeEngine:
             calls = _vocode(self.vocoder, vc, [S] * n, False, "RealtimeEngine.step", hop=self.hop, seeds=seeds,
                             vocoder_kwargs=vocoder_kwargs)                   # every row has S frames: one plain call
             wave = _lib.f32c(calls[0].wave, dev)
-            out = torch.empty(n, self.block, device=dev)
             offsets = torch.empty(n, dtype=torch.int32, device=dev) if return_parts else None
-            _lib.check(_lib.lib().svc_sola_step(_lib.ptr(wave), wave.size(1), self.start, n, _lib.ptr(self.state), self.max_streams,
-                                                _lib.i32_host(slots), _lib.ptr(self.fade_in), _lib.ptr(self.fade_out), self.block,
-                                                self.Lb, self.Ls, _lib.ptr(out), _lib.ptr(offsets), _lib.stream_ptr()))
+            speech = [1 if self._speech.get(s, True) else 0 for s in slots]
+            if live is None and all(speech):                                     # host state decides which entry splices
+                out = torch.empty(n, self.block, device=dev)
+                _lib.check(_lib.lib().svc_sola_step(_lib.ptr(wave), wave.size(1), self.start, n, _lib.ptr(self.state), self.max_streams,
+                                                    _lib.i32_host(slots), _lib.ptr(self.fade_in), _lib.ptr(self.fade_out), self.block,
+                                                    self.Lb, self.Ls, _lib.ptr(out), _lib.ptr(offsets), _lib.stream_ptr()))
+                infer = wave[:, self.start:self.start + self.n_inf]
+            else:
+                g = live or dict(block=self.block, Lb=self.Lb, Ls=self.Ls, n_inf=self.n_inf, fade_in=self.fade_in, fade_out=self.fade_out)
+                out = torch.empty(n, g["block"], device=dev)
+                infer = torch.empty(n, g["n_inf"], device=dev)
+                _lib.check(_lib.lib().svc_rt_out(live["resample"]._h if live else None, _lib.ptr(wave), wave.size(1), self.start,
+                                                 self.n_inf, n, _lib.ptr(self.state), self.max_streams, _lib.i32_host(slots),
+                                                 None if all(speech) else _lib.i32_host(speech), _lib.ptr(g["fade_in"]),
+                                                 _lib.ptr(g["fade_out"]), g["block"], g["Lb"], g["Ls"], _lib.ptr(infer), _lib.ptr(out),
+                                                 _lib.ptr(offsets), _lib.stream_ptr()))
         if return_parts:
-            return out, dict(mel=vc, infer=wave[:, self.start:self.start + self.n_inf], offsets=offsets)
+            return out, dict(mel=vc, infer=infer, offsets=offsets)
         return out
 
     # ------------------------------------------------------------------------------------------- audio in
@@ -971,12 +1077,15 @@ class RealtimeEngine:
         self._audio = dict(content=content, resample=resample, Lin=Lin, L16=L16, zc=zc, z16=z16, ce=ce, ring=ring,
                            planes=ring[:planes].view(2, ms, L16), tickets=ring[planes:].view(torch.int64),
                            tiles=int(_lib.lib().svc_rt_push_tiles(L16)),
-                           hist=torch.zeros(ms, 2 * zc, device=self.device, dtype=torch.float32))
+                           hist=torch.zeros(ms, 2 * zc, device=self.device, dtype=torch.float32),
+                           gate_e=torch.zeros(ms, 3, device=self.device, dtype=torch.float32))
+        self._gate = {}
 
     def _zero_audio(self, slot):
         if self._audio is not None:
             self._audio["planes"][:, slot].zero_()
             self._audio["hist"][slot].zero_()
+            self._audio["gate_e"][slot].zero_()
 
     def audio_context(self, slot):
         """The content-rate context (L16,) of an open slot as the last `step_audio` left it (a copy; this call synchronises to
@@ -992,7 +1101,8 @@ class RealtimeEngine:
         """One block from audio: audio (n, Lin) float32 at the stream rate, row k the new samples of slots[k].  One
         `svc_rt_push` (history, resampling, context shift and the dense batch), then
         `content.semantic_fn(ctx)[:, int(ce_dit_difference * 50):]`, then `step`.  -> as `step`; with return_parts the dict also
-        carries ctx (n, L16) and content (n, T, D).  Lengths and slots are host integers: nothing synchronises."""
+        carries ctx (n, L16) and content (n, T, D).  Lengths and slots are host integers: nothing synchronises.  Where a listed
+        slot has a gate (`set_gate`) the push is `svc_rt_push_gated` and the dict also carries gate_mask (n, Lin / zc) int32."""
         return self._step_audio(slots, audio, n_timesteps, inference_cfg_rate, z, vocoder_kwargs, return_parts, None)
 
     @torch.inference_mode()
@@ -1019,13 +1129,24 @@ class RealtimeEngine:
         with torch.cuda.device(self.device):
             block = _lib.f32c(audio, self.device)
             ctx = torch.empty(n, a["L16"], device=self.device, dtype=torch.float32)
-            _lib.check(_lib.lib().svc_rt_push(a["resample"]._h, _lib.ptr(block), block.stride(0), a["Lin"], n, _lib.i32_host(slots),
-                                              self.max_streams, a["zc"], a["z16"], _lib.ptr(a["hist"]), _lib.ptr(a["ring"]), a["L16"],
-                                              _lib.ptr(ctx), _lib.stream_ptr()))
+            pows = [self._gate.get(s, 0.0) for s in slots]
+            mask = None
+            if not any(pows):                                                    # host state decides which entry pushes
+                _lib.check(_lib.lib().svc_rt_push(a["resample"]._h, _lib.ptr(block), block.stride(0), a["Lin"], n, _lib.i32_host(slots),
+                                                  self.max_streams, a["zc"], a["z16"], _lib.ptr(a["hist"]), _lib.ptr(a["ring"]), a["L16"],
+                                                  _lib.ptr(ctx), _lib.stream_ptr()))
+            else:
+                mask = torch.empty(n, a["Lin"] // a["zc"], device=self.device, dtype=torch.int32) if return_parts else None
+                _lib.check(_lib.lib().svc_rt_push_gated(a["resample"]._h, _lib.ptr(block), block.stride(0), a["Lin"], n,
+                                                        _lib.i32_host(slots), self.max_streams, a["zc"], a["z16"], _lib.ptr(a["hist"]),
+                                                        _lib.ptr(a["ring"]), a["L16"], _lib.ptr(ctx), (C.c_float * n)(*pows),
+                                                        _lib.ptr(a["gate_e"]), _lib.ptr(mask), _lib.stream_ptr()))
             content = a["content"].semantic_fn(ctx)[:, a["ce"]:]
         res = self._step(slots, content, n_timesteps, inference_cfg_rate, z, vocoder_kwargs, return_parts, seeds)
         if return_parts:
             res[1].update(ctx=ctx, content=content)
+            if mask is not None:
+                res[1]["gate_mask"] = mask
         return res
 
 
