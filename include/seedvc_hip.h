@@ -853,6 +853,7 @@ int svc_op_conv1d(const float* x, const float* w, const float* bias, float* y, i
  *   seq_len: HOST [B] valid input rows per sequence (the ragged form; needs Lout == L).
  *   epilogue, in this order: + bias, act (KG_ACT_* value, act_slope), + res, * out_scale (0 = 1), + res2;
  *   y, res, res2 [B][c_rows][Cout] fp32 (c_rows 0 = Lout); the conv writes rows c_off .. c_off + Lout of y, the others are kept.
+ *   res and / or res2 may be y itself: the conv then runs in place, reading the addend from the buffer it writes.
  *   post_a / post_ib [Cout]: fused Snake sv = v + post_ib sin^2(post_a v) towards plane_hi / plane_lo [B][c_rows][cout_pad]
  *   (raw 16-bit words over all cout_pad = Cout rounded up to 64 columns, written in place): hi = fp16(sv), lo = fp16(sv - hi) or,
  *   with next_p8, the byte pair (fp8(hi), fp8(2^11 (sv - hi))); y keeps v.

@@ -132,6 +132,24 @@ __device__ __forceinline__ float act_apply(float v, int act, float slope) {
         default: return v;
     }
 }
+// the same on the 8 columns of an epilogue chunk with the (launch-uniform) switch taken once, not per element
+__device__ __forceinline__ void act_apply8(float* v, int act, float slope) {
+#define SVC_ACT8(A)                                                     \
+    case A:                                                             \
+        _Pragma("unroll") for (int j = 0; j < 8; ++j) v[j] = act_apply(v[j], A, slope); \
+        break;
+    switch (act) {
+        SVC_ACT8(KG_ACT_SILU)
+        SVC_ACT8(KG_ACT_ELU)
+        SVC_ACT8(KG_ACT_LRELU)
+        SVC_ACT8(KG_ACT_TANH)
+        SVC_ACT8(KG_ACT_ABS)
+        SVC_ACT8(KG_ACT_CLAMP)
+        SVC_ACT8(KG_ACT_SIGMOID)
+        default: break;
+    }
+#undef SVC_ACT8
+}
 
 struct KGemmParams {
     // A
@@ -192,12 +210,16 @@ struct KConvParams {
     float* c32; long ldc32;
     half_t* c16; half_t* c16_lo; long ldc16;
     const float* post_a; const float* post_ib; int post_n;
+    // res and / or res2 may be c32 itself, element for element (same base, same leading dimension: HiFT sums its ResBlocks into
+    // one buffer that way).  The epilogue requests the addends of all the chunks a thread handles in a pass ahead of that pass's
+    // stores; each output element is read and written by one thread only, which reads it before it writes it.  Any other overlap
+    // of res / res2 with an output is not supported.
     const float* res; long ldres;
     const float* res2; long ldres2;
     float out_scale;
     int act; float act_slope;
     const void* zero_page;
-    int w8_exp;        // nsub == 2 ("fp16 + fp8 corrections"): log2 of the power-of-two scale the fp8 weight bytes carry
+    int w8_exp;       // nsub == 2 ("fp16 + fp8 corrections"): log2 of the power-of-two scale the fp8 weight bytes carry
     int c16_lo_fmt;    // format of the c16_lo plane written by the epilogue: 0 = fp16 residual, 1 = fp8 pair (lo_pair_p8)
     // ragged batches (needs Lin == Lout): device [B] valid rows per sequence.  Input rows at and above seq_len[b] read as the
     // zero padding does (they are never loaded: they may hold NaN); position tiles that start there are skipped, so output

@@ -213,11 +213,49 @@ __global__ __launch_bounds__(CB_NT, BM < 256 ? 2 : 1) void kconv_kernel(const KC
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
-    // ---- epilogue: accumulators transposed through LDS (passes of RP = 32 | 16 rows per wave), 8 consecutive columns per lane
+    // ---- epilogue: accumulators transposed through LDS (passes of RP = 32 | 16 rows per wave), 8 consecutive columns per lane.
+    // Every global operand of a pass is requested before the first of them is waited for.  A lane's eight columns are the same in
+    // every chunk it handles (64 is a multiple of the 8 chunks of a row), so bias and the Snake's a, 1/b are loaded once per lane;
+    // the res / res2 rows of all chunks of a pass are requested before the transposition and land while it runs.  The loads of a
+    // pass sit above its stores in program order: res == c32 and res2 == c32 stay legal (KConvParams), a thread reads an element
+    // before it writes it.
     constexpr int RP = TM >= 2 ? 32 : 16;
+    constexpr int NCH = RP / 8;                       // chunks per lane and pass: RP rows x 8 chunks per wave
     float* ep = reinterpret_cast<float*>(smem) + wave * RP * CB_EPI_LD;
+    const int cc = lane & 7, row0 = lane >> 3;        // chunk i of a lane: row row0 + 8 i, columns cc * 8 ..
+    const int n = n0 + wn0 + cc * 8;
+    const bool n_ok = n < p.N;
+    const int n_ld = n_ok ? n : 0;                    // predicated-off lanes load from column 0 of output row 0 of the sequence
+    float cb[8], ca[8], cib[8];                       // bias, Snake a and 1 / b of the lane's columns
+#pragma unroll
+    for (int j = 0; j < 8; ++j) cb[j] = ca[j] = cib[j] = 0.f;
 #pragma unroll
     for (int pass = 0; pass < TM * 16 / RP; ++pass) {
+        bool ok[NCH];
+        long orow[NCH];
+        float4v q[NCH][2], q2[NCH][2];
+#pragma unroll
+        for (int i = 0; i < NCH; ++i) {
+            const int pos = p0 + wm0 + pass * RP + row0 + 8 * i;
+            ok[i] = n_ok & (pos < p.Lout);
+            orow[i] = (long)b * p.c_seq_rows + p.c_off + (ok[i] ? pos : 0);
+        }
+        if (p.res) {
+#pragma unroll
+            for (int i = 0; i < NCH; ++i) {
+                const float* s = p.res + orow[i] * p.ldres + n_ld;
+                q[i][0] = *reinterpret_cast<const float4v*>(s);
+                q[i][1] = *reinterpret_cast<const float4v*>(s + 4);
+            }
+        }
+        if (p.res2) {
+#pragma unroll
+            for (int i = 0; i < NCH; ++i) {
+                const float* s = p.res2 + orow[i] * p.ldres2 + n_ld;
+                q2[i][0] = *reinterpret_cast<const float4v*>(s);
+                q2[i][1] = *reinterpret_cast<const float4v*>(s + 4);
+            }
+        }
         if (pass > 0) __syncthreads();
 #pragma unroll
         for (int mi = 0; mi < RP / 16; ++mi)
@@ -226,13 +264,39 @@ __global__ __launch_bounds__(CB_NT, BM < 256 ? 2 : 1) void kconv_kernel(const KC
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
                     ep[(mi * 16 + fq * 4 + r) * CB_EPI_LD + nt * 16 + fr] = acc[pass * (RP / 16) + mi][nt][r];
+        if (pass == 0) {
+            // the column vectors, once the first pass's accumulators have left their registers
+            if (p.bias) {
+                const float4v b0 = *reinterpret_cast<const float4v*>(p.bias + n_ld);
+                const float4v b1 = *reinterpret_cast<const float4v*>(p.bias + n_ld + 4);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { cb[j] = b0[j]; cb[4 + j] = b1[j]; }
+            }
+            if (p.post_a && p.post_n > 0) {
+                // whole eight-groups below post_n as 16-byte loads; the group post_n cuts (and the groups above it, whose values the
+                // select below drops) element by element at clamped indices: nothing is read past the end of the vectors
+                const bool vec = n_ok && n + 8 <= p.post_n && ((reinterpret_cast<uintptr_t>(p.post_a) | reinterpret_cast<uintptr_t>(p.post_ib)) & 15) == 0;
+                if (vec) {
+                    const float4v a0 = *reinterpret_cast<const float4v*>(p.post_a + n);
+                    const float4v a1 = *reinterpret_cast<const float4v*>(p.post_a + n + 4);
+                    const float4v i0 = *reinterpret_cast<const float4v*>(p.post_ib + n);
+                    const float4v i1 = *reinterpret_cast<const float4v*>(p.post_ib + n + 4);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) { ca[j] = a0[j]; ca[4 + j] = a1[j]; cib[j] = i0[j]; cib[4 + j] = i1[j]; }
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) {
+                        const int nn = n_ld + j < p.post_n ? n_ld + j : p.post_n - 1;
+                        ca[j] = p.post_a[nn];
+                        cib[j] = p.post_ib[nn];
+                    }
+                }
+            }
+        }
         __syncthreads();
 #pragma unroll
-        for (int i = 0; i < RP / 8; ++i) {            // RP rows x 8 chunks per wave pass
-            const int ch = lane + 64 * i;
-            const int row = ch >> 3, cc = ch & 7;
-            const int pos = p0 + wm0 + pass * RP + row;
-            const int n = n0 + wn0 + cc * 8;
+        for (int i = 0; i < NCH; ++i) {
+            const int row = row0 + 8 * i;
             float v[8];
             {
                 const float4v x0 = *reinterpret_cast<const float4v*>(ep + row * CB_EPI_LD + cc * 8);
@@ -240,45 +304,35 @@ __global__ __launch_bounds__(CB_NT, BM < 256 ? 2 : 1) void kconv_kernel(const KC
 #pragma unroll
                 for (int j = 0; j < 4; ++j) { v[j] = x0[j]; v[4 + j] = x1[j]; }
             }
-            if (pos >= p.Lout || n >= p.N) continue;
-            const long orow = (long)b * p.c_seq_rows + p.c_off + pos;
+            if (!ok[i]) continue;
             if (p.bias) {
-                const float4v b0 = *reinterpret_cast<const float4v*>(p.bias + n);
-                const float4v b1 = *reinterpret_cast<const float4v*>(p.bias + n + 4);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) { v[j] += b0[j]; v[4 + j] += b1[j]; }
+                for (int j = 0; j < 8; ++j) v[j] += cb[j];
             }
-            if (p.act != KG_ACT_NONE) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) v[j] = act_apply(v[j], p.act, p.act_slope);
-            }
+            if (p.act != KG_ACT_NONE) act_apply8(v, p.act, p.act_slope);
             if (p.res) {
-                const float4v q0 = *reinterpret_cast<const float4v*>(p.res + orow * p.ldres + n);
-                const float4v q1 = *reinterpret_cast<const float4v*>(p.res + orow * p.ldres + n + 4);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) { v[j] += q0[j]; v[4 + j] += q1[j]; }
+                for (int j = 0; j < 4; ++j) { v[j] += q[i][0][j]; v[4 + j] += q[i][1][j]; }
             }
             if (p.out_scale != 0.f) {
 #pragma unroll
                 for (int j = 0; j < 8; ++j) v[j] *= p.out_scale;
             }
             if (p.res2) {
-                const float4v q0 = *reinterpret_cast<const float4v*>(p.res2 + orow * p.ldres2 + n);
-                const float4v q1 = *reinterpret_cast<const float4v*>(p.res2 + orow * p.ldres2 + n + 4);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) { v[j] += q0[j]; v[4 + j] += q1[j]; }
+                for (int j = 0; j < 4; ++j) { v[j] += q2[i][0][j]; v[4 + j] += q2[i][1][j]; }
             }
             if (p.c32) {
-                *reinterpret_cast<float4v*>(p.c32 + orow * p.ldc32 + n) = (float4v){v[0], v[1], v[2], v[3]};
-                *reinterpret_cast<float4v*>(p.c32 + orow * p.ldc32 + n + 4) = (float4v){v[4], v[5], v[6], v[7]};
+                *reinterpret_cast<float4v*>(p.c32 + orow[i] * p.ldc32 + n) = (float4v){v[0], v[1], v[2], v[3]};
+                *reinterpret_cast<float4v*>(p.c32 + orow[i] * p.ldc32 + n + 4) = (float4v){v[4], v[5], v[6], v[7]};
             }
             if (p.post_a) {
                 float lo[8];
                 float hf[8];
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
-                    const int nn = n + j;
-                    const float sv = nn < p.post_n ? v[j] + p.post_ib[nn] * sin_sq(p.post_a[nn] * v[j]) : 0.f;
+                    const float t = v[j] + cib[j] * sin_sq(ca[j] * v[j]);
+                    const float sv = n + j < p.post_n ? t : 0.f;      // a select on the value: columns at and above post_n are zero planes
                     const half_t hh = (half_t)sv;
                     v[j] = sv;
                     lo[j] = sv - (float)hh;
@@ -288,12 +342,12 @@ __global__ __launch_bounds__(CB_NT, BM < 256 ? 2 : 1) void kconv_kernel(const KC
                     if (p.c16_lo_fmt) {
                                 const u32x4 pr = {lo_pair_p8(hf[0], lo[0]) | (lo_pair_p8(hf[1], lo[1]) << 16), lo_pair_p8(hf[2], lo[2]) | (lo_pair_p8(hf[3], lo[3]) << 16),
                                                   lo_pair_p8(hf[4], lo[4]) | (lo_pair_p8(hf[5], lo[5]) << 16), lo_pair_p8(hf[6], lo[6]) | (lo_pair_p8(hf[7], lo[7]) << 16)};
-                                *reinterpret_cast<u32x4*>(p.c16_lo + orow * p.ldc16 + n) = pr;
+                                *reinterpret_cast<u32x4*>(p.c16_lo + orow[i] * p.ldc16 + n) = pr;
                             }
-                    else *reinterpret_cast<uint4*>(p.c16_lo + orow * p.ldc16 + n) = pack8(lo);
+                    else *reinterpret_cast<uint4*>(p.c16_lo + orow[i] * p.ldc16 + n) = pack8(lo);
                 }
             }
-            if (p.c16) *reinterpret_cast<uint4*>(p.c16 + orow * p.ldc16 + n) = pack8(v);
+            if (p.c16) *reinterpret_cast<uint4*>(p.c16 + orow[i] * p.ldc16 + n) = pack8(v);
         }
     }
 }

@@ -430,6 +430,28 @@ __global__ __launch_bounds__(NWV * 64, (NS * (BM + BN) * RB > 80 * 1024) ? 1 : 2
     constexpr int NCH = ROWS_P * CPR / 64;             // chunks per lane per pass
     static_assert(ROWS_P * CPR % 64 == 0, "epilogue chunking");
     float* ep = reinterpret_cast<float*>(smem) + wave * ROWS_P * G::EPI_LD;
+    // A lane's CW columns are the same in every chunk it handles (CPR divides 64): bias is loaded once per lane.  The res rows of
+    // a pass are requested before the LDS transposition.  res2, the per-sequence rowvec / gate rows and the Snake's a, 1 / b stay
+    // per chunk, each as two 16-byte loads behind ONE wait (the Snake's `nn < post_n` is a select on the value, not a branch per
+    // element).  Registers decide this split: with the operands of every chunk of a pass in flight at once (24 more registers per
+    // chunk) the 128 x 128 forms drop from 3 to 2 waves per SIMD and the 256-row forms spill; even one chunk's operands requested
+    // together, or the Snake vectors kept per lane, cost the 128 x 128 x 64 form its third wave (184 VGPRs against 153).
+    // A chunk's loads sit above its stores in program order, so res == c32 and res2 == c32 stay legal element for element.
+    static_assert(64 % CPR == 0, "a lane keeps its columns");
+    const int cc = lane % CPR, row0 = lane / CPR;      // chunk i of a lane: row row0 + (64 / CPR) i of the pass
+    const int n = n0 + wn0 + cc * CW;
+    const int nv = (p.N - n) < CW ? (p.N - n) : CW;    // <= 0: no column of this lane is inside the matrix
+    const int n_ld = nv > 0 ? n : 0;                   // predicated-off lanes load from column 0 of row 0: in range
+    // 16-byte loads of the lane's slice of a per-sequence row: whole slices only (N % 8 == 0, so nv is CW or the lane is off) of
+    // rows that start on 16-byte boundaries.  Launch-uniform, as vec_ok is.
+    const bool rv_vec = p.vec_ok && (p.N & 7) == 0 && (p.ld_rowvec & 3) == 0 && (reinterpret_cast<uintptr_t>(p.rowvec) & 15) == 0;
+    const bool gt_vec = p.vec_ok && (p.N & 7) == 0 && (p.ld_gate & 3) == 0 && (reinterpret_cast<uintptr_t>(p.gate) & 15) == 0;
+    // the Snake's vectors as 16-byte loads: whole groups below post_n only (the group post_n cuts and the groups above it take
+    // clamped indices: nothing is read past the end of the vectors)
+    const bool sn_vec = n + CW <= p.post_n && ((reinterpret_cast<uintptr_t>(p.post_a) | reinterpret_cast<uintptr_t>(p.post_ib)) & 15) == 0;
+    float cb[CW];
+#pragma unroll
+    for (int j = 0; j < CW; ++j) cb[j] = 0.f;
 
 #pragma unroll
     for (int pass = 0; pass < G::EP; ++pass) {
@@ -440,23 +462,19 @@ __global__ __launch_bounds__(NWV * 64, (NS * (BM + BN) * RB > 80 * 1024) ? 1 : 2
         float4v rs0[NCH], rs1[NCH];
 #pragma unroll
         for (int i = 0; i < NCH; ++i) {
-            const int ch = lane + 64 * i;
-            const int row = ch / CPR;
-            const int cc = ch - row * CPR;
-            const int m = m0 + wm0 + prow0 + row;
-            const int n = n0 + wn0 + cc * CW;
-            ok_[i] = (m < p.M) & (n < p.N);
+            const int m = m0 + wm0 + prow0 + row0 + (64 / CPR) * i;
+            ok_[i] = (m < p.M) & (nv > 0);
             const int mm = ok_[i] ? m : 0;
             seq_[i] = mm / p.Lout;
             pos_[i] = mm - seq_[i] * p.Lout;
             orow_[i] = (long)seq_[i] * p.c_seq_rows + p.c_off + pos_[i];
-            rs0[i] = (float4v){0.f, 0.f, 0.f, 0.f};
-            rs1[i] = rs0[i];
-            {
-                if (p.res && p.vec_ok && ok_[i]) {
-                    rs0[i] = *reinterpret_cast<const float4v*>(p.res + orow_[i] * p.ldres + n);
-                    rs1[i] = *reinterpret_cast<const float4v*>(p.res + orow_[i] * p.ldres + n + 4);
-                }
+        }
+        // (launch-uniform conditions, unconditional loads: a lane-predicated load would be a branch with its own wait)
+        if (p.res && p.vec_ok) {
+#pragma unroll
+            for (int i = 0; i < NCH; ++i) {
+                rs0[i] = *reinterpret_cast<const float4v*>(p.res + orow_[i] * p.ldres + n_ld);
+                rs1[i] = *reinterpret_cast<const float4v*>(p.res + orow_[i] * p.ldres + n_ld + 4);
             }
         }
         if (pass > 0) __syncthreads();                 // the previous pass has been read out
@@ -468,14 +486,27 @@ __global__ __launch_bounds__(NWV * 64, (NS * (BM + BN) * RB > 80 * 1024) ? 1 : 2
 #pragma unroll
                 for (int r = 0; r < 4; ++r) ep[(mi * 16 + fq * 4 + r) * G::EPI_LD + nt * 16 + fr] = a4[r];
             }
+        if (pass == 0 && nv > 0) {
+            // the column vectors, once the first pass's accumulators have left their registers
+            if (p.bias) {
+                if (nv == CW) {
+#pragma unroll
+                    for (int q4 = 0; q4 < CW / 4; ++q4) {
+                        const float4v b = *reinterpret_cast<const float4v*>(p.bias + n + q4 * 4);
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) cb[q4 * 4 + j] = b[j];
+                    }
+                } else {
+#pragma unroll
+                    for (int j = 0; j < CW; ++j) if (j < nv) cb[j] = p.bias[n + j];
+                }
+            }
+        }
         __syncthreads();
 
 #pragma unroll
         for (int i = 0; i < NCH; ++i) {
-            const int ch = lane + 64 * i;
-            const int row = ch / CPR;
-            const int cc = ch - row * CPR;
-            const int n = n0 + wn0 + cc * CW;
+            const int row = row0 + (64 / CPR) * i;
             float v[CW];
 #pragma unroll
             for (int q4 = 0; q4 < CW / 4; ++q4) {
@@ -487,25 +518,21 @@ __global__ __launch_bounds__(NWV * 64, (NS * (BM + BN) * RB > 80 * 1024) ? 1 : 2
             const int seq = seq_[i];
             const int pos = pos_[i];
             const long orow = orow_[i];
-            const int nv = (p.N - n) < CW ? (p.N - n) : CW;
 
             if (p.bias) {
-                if (nv == CW) {
 #pragma unroll
-                    for (int q4 = 0; q4 < CW / 4; ++q4) {
-                        const float4v b = *reinterpret_cast<const float4v*>(p.bias + n + q4 * 4);
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) v[q4 * 4 + j] += b[j];
-                    }
-                } else {
-#pragma unroll
-                    for (int j = 0; j < CW; ++j) if (j < nv) v[j] += p.bias[n + j];
-                }
+                for (int j = 0; j < CW; ++j) if (j < nv) v[j] += cb[j];
             }
             if (p.rowvec) {
                 const float* rv = p.rowvec + (long)seq * p.ld_rowvec + n;
+                if (rv_vec) {
+                    const float4v rv0 = *reinterpret_cast<const float4v*>(rv), rv1 = *reinterpret_cast<const float4v*>(rv + 4);
 #pragma unroll
-                for (int j = 0; j < CW; ++j) if (j < nv) v[j] += rv[j];
+                    for (int j = 0; j < 4; ++j) { v[j] += rv0[j]; v[4 + j] += rv1[j]; }
+                } else {
+#pragma unroll
+                    for (int j = 0; j < CW; ++j) if (j < nv) v[j] += rv[j];
+                }
             }
 
             {
@@ -513,13 +540,18 @@ __global__ __launch_bounds__(NWV * 64, (NS * (BM + BN) * RB > 80 * 1024) ? 1 : 2
 #pragma unroll
                     for (int j = 0; j < 8; ++j) v[j] = gelu_erf(v[j]);
                 } else if (p.act != KG_ACT_NONE) {
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) v[j] = act_apply(v[j], p.act, p.act_slope);
+                    act_apply8(v, p.act, p.act_slope);
                 }
                 if (p.gate) {
                     const float* gv = p.gate + (long)seq * p.ld_gate + n;
+                    if (gt_vec) {
+                        const float4v gt0 = *reinterpret_cast<const float4v*>(gv), gt1 = *reinterpret_cast<const float4v*>(gv + 4);
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) if (j < nv) v[j] *= gv[j];
+                        for (int j = 0; j < 4; ++j) { v[j] *= gt0[j]; v[4 + j] *= gt1[j]; }
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) if (j < nv) v[j] *= gv[j];
+                    }
                 }
                 if (p.vec_ok) {
                     if (p.res) {
@@ -545,11 +577,27 @@ __global__ __launch_bounds__(NWV * 64, (NS * (BM + BN) * RB > 80 * 1024) ? 1 : 2
                         *reinterpret_cast<float4v*>(p.c32 + orow * p.ldc32 + n + 4) = (float4v){v[4], v[5], v[6], v[7]};
                     }
                     if (p.post_a) {      // fused pointwise Snake on the way to the next conv's fp16 (hi / lo) operand planes
-                        float lo[8];
+                        float lo[8], ca[8], cib[8];
+                        if (sn_vec) {
+#pragma unroll
+                            for (int q4 = 0; q4 < 2; ++q4) {
+                                const float4v a4 = *reinterpret_cast<const float4v*>(p.post_a + n + q4 * 4);
+                                const float4v i4 = *reinterpret_cast<const float4v*>(p.post_ib + n + q4 * 4);
+#pragma unroll
+                                for (int j = 0; j < 4; ++j) { ca[q4 * 4 + j] = a4[j]; cib[q4 * 4 + j] = i4[j]; }
+                            }
+                        } else {
+#pragma unroll
+                            for (int j = 0; j < 8; ++j) {
+                                const int nn = n + j < p.post_n ? n + j : (p.post_n > 0 ? p.post_n - 1 : 0);
+                                ca[j] = p.post_n > 0 ? p.post_a[nn] : 0.f;
+                                cib[j] = p.post_n > 0 ? p.post_ib[nn] : 0.f;
+                            }
+                        }
 #pragma unroll
                         for (int j = 0; j < 8; ++j) {
-                            const int nn = n + j;
-                            const float sv = nn < p.post_n ? v[j] + p.post_ib[nn] * sin_sq(p.post_a[nn] * v[j]) : 0.f;
+                            const float t = v[j] + cib[j] * sin_sq(ca[j] * v[j]);
+                            const float sv = n + j < p.post_n ? t : 0.f;      // a select on the value: zero planes at and above post_n
                             const half_t h = (half_t)sv;
                             v[j] = sv;
                             lo[j] = sv - (float)h;

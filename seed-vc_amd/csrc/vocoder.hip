@@ -1312,9 +1312,12 @@ int op_conv1d_body(svc_conv1d_ex_t& e, int stride, int pad_mode, bool ex, hipStr
         const float* src[2] = {e.res, e.res2};
         for (int i = 0; i < 2; ++i) {
             if (!src[i]) continue;
-            float* q = ar.alloc_n<float>(n_c, st);
-            if (!q) return 1;
-            if (pack_f32_launch(src[i], q, B * c_rows, 1, Cout, Cout, 0, 1, cw.cout_pad, 0, 1, nullptr, st)) return 1;
+            float* q = c;      // res / res2 == y: in place, the conv reads the addend from the buffer it writes
+            if (src[i] != e.y) {
+                q = ar.alloc_n<float>(n_c, st);
+                if (!q) return 1;
+                if (pack_f32_launch(src[i], q, B * c_rows, 1, Cout, Cout, 0, 1, cw.cout_pad, 0, 1, nullptr, st)) return 1;
+            }
             if (i == 0) { r.res = q; r.ldres = cw.cout_pad; } else { r.res2 = q; r.ldres2 = cw.cout_pad; }
         }
         if (e.seq_len) {

@@ -59,12 +59,13 @@ PLANE_FILL = 0x7E7E      # what conv1d_cl_ex's planes hold where the conv did no
 
 def conv1d_cl_ex(x, w, bias=None, dilation=1, pad_left=0, Lout=None, dtype="f16x3", seq_len=None, res=None, res2=None,
                  out_scale=0.0, act=0, act_slope=0.0, c_rows=0, c_off=0, y_fill=None, post_a=None, post_ib=None, next_p8=False,
-                 bm=0, force_gemm=False, planes=None):
+                 bm=0, force_gemm=False, planes=None, y_init=None):
     """Test aid over svc_op_conv1d_ex (include/seedvc_hip.h): one stride-1 zero-padded channels-last conv with the epilogue, the
     fused Snake, the ragged form, the fp16 + fp8-corrections mode ("p8") and a tile-form override.
     x (B, L, Cin) fp32, or planes = (hi, lo) int16 (B, L, cin_pad) as a fused Snake returned them (x then only gives the shape).
     Returns (y (B, c_rows, Cout), plane_hi, plane_lo, took): the planes are int16 (B, c_rows, cout_pad) or None without a Snake,
-    took = dict(kconv=bool, bm=int, bn=int).  Rows of y the conv does not write hold y_fill."""
+    took = dict(kconv=bool, bm=int, bn=int).  Rows of y the conv does not write hold y_fill, or y_init's (B, c_rows, Cout) where
+    given.  res / res2 = "y" passes y itself as that addend (the conv runs in place on what y_init put there)."""
     import ctypes as C
     B, L, Cin = x.shape
     Cout, _, k = w.shape
@@ -87,7 +88,7 @@ def conv1d_cl_ex(x, w, bias=None, dilation=1, pad_left=0, Lout=None, dtype="f16x
             e.x = keep[-1].data_ptr()
         for name, t, shape in (("bias", bias, (Cout,)), ("res", res, (B, rows, Cout)), ("res2", res2, (B, rows, Cout)),
                                ("post_a", post_a, (Cout,)), ("post_ib", post_ib, (Cout,))):
-            if t is not None:
+            if t is not None and not isinstance(t, str):
                 assert tuple(t.shape) == shape, name
                 keep.append(_lib.f32c(t))
                 setattr(e, name, keep[-1].data_ptr())
@@ -99,8 +100,16 @@ def conv1d_cl_ex(x, w, bias=None, dilation=1, pad_left=0, Lout=None, dtype="f16x
             e.seq_len = C.cast(lens, C.POINTER(C.c_int32))
         e.out_scale, e.act, e.act_slope, e.c_rows, e.c_off = out_scale, act, act_slope, c_rows, c_off
         e.next_p8, e.bm, e.force_gemm = int(next_p8), bm, int(force_gemm)
-        y = torch.full((B, rows, Cout), float("nan") if y_fill is None else y_fill, device=dev)
+        if y_init is not None:
+            assert tuple(y_init.shape) == (B, rows, Cout)
+            y = _lib.f32c(y_init).clone()
+        else:
+            y = torch.full((B, rows, Cout), float("nan") if y_fill is None else y_fill, device=dev)
         e.y = y.data_ptr()
+        for name, t in (("res", res), ("res2", res2)):
+            if isinstance(t, str):
+                assert t == "y" and y_init is not None, name
+                setattr(e, name, e.y)
         p_hi = p_lo = None
         if post_a is not None:
             p_hi = torch.full((B, rows, cout_pad), PLANE_FILL, dtype=torch.int16, device=dev)
