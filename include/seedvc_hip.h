@@ -66,6 +66,11 @@ int svc_dit_set_microbatch(svc_dit_t* m, int utterances);
  * 384 or 512); smaller launches use the tap-GEMM kernels.  rows < 0 restores the default (10240), 0 forces the fused
  * kernel, a huge value disables it.  The two paths agree to fp16-operand rounding (not bit for bit). */
 int svc_dit_set_fused_min_rows(svc_dit_t* m, long rows);
+/* Sampler seams run inside the fused row-panel launches of a step: bit 0 = the x block of the merge linear, the prefix-token
+ * rows and the zeroed pad rows are built by the first panel (in_channels in (64, 128]); bit 1 = the mlp output head runs
+ * in the last panel (final_layer_type mlp, in_channels a multiple of 16).  Default 3; unsupported bits are ignored; 0 issues
+ * the separate launches (prefix rows, merge GEMM, two head GEMMs).  The two forms agree to fp16-operand rounding. */
+int svc_dit_set_fused_seams(svc_dit_t* m, int mask);
 int svc_dit_fused_available(svc_dit_t* m);
 /* Optional (off by default: the sampler is GPU-bound on MI355X, replay measured 3 % slower than eager launches at B = 1):
  * the Euler loop of svc_cfm_sample (all steps of a micro-batch group: estimator + state update) is captured into a hipGraph

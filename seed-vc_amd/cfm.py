@@ -58,6 +58,10 @@ class Estimator:
         """Token rows per launch from which the transformer layers use the fused row-panel kernel (-1: default)."""
         _lib.check(_lib.lib().svc_dit_set_fused_min_rows(self._h, C.c_long(int(rows))))
 
+    def set_fused_seams(self, mask):
+        """Sampler seams inside the fused row-panel launches: bit 0 merge linear + token rows, bit 1 mlp head (default 3)."""
+        _lib.check(_lib.lib().svc_dit_set_fused_seams(self._h, int(mask)))
+
     def set_graphs(self, on):
         """hipGraph capture / replay of the sampler's Euler loop (off by default; bit-identical to eager launches)."""
         _lib.check(_lib.lib().svc_dit_set_graphs(self._h, int(bool(on))))

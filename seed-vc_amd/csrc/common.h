@@ -278,13 +278,31 @@ struct PanelParams {
     // after the last layer: final adaptive norm -> fp16 rows for the head
     int do_final;
     const float* g_fin; const float* w_fin; const float* b_fin; half_t* n16;
+    // sampler seams run inside the first / last panel of a step (fused.hip, "seams"); 0 = none
+    int seam;                    // PANEL_SEAM_MERGE: first panel (do_qkv only); PANEL_SEAM_HEAD: last panel (do_final)
+    // merge: x[seq][pos] = st_term[seq][pos] + x16[seq][pos - npre] Wx^T on data rows, the token vector on prefix rows, 0 on pad rows
+    const half_t* x16;           // [n_seq][seq_rows][128], row t = position npre + t
+    const float* st_term;        // [n_seq][seq_rows][D]
+    const float* tok_time; const float* tok_style;       // [D] of this step ; [n_seq][D]
+    const float* zero_row;       // [D] zeros: what prefix and pad rows multiply, and what pad rows start from
+    int npre, time_first, T;
+    // head: v = W2 silu(Wa n + b0) + b2 on the rows of the launch; n16 is not written
+    const float* head_b0; const float* head_b2;          // [D] ; [head_C]
+    float* v32; int ldv; int head_C;                     // [rows][ldv], columns < head_C written
 };
+enum { PANEL_SEAM_NONE = 0, PANEL_SEAM_MERGE = 1, PANEL_SEAM_HEAD = 2 };
+enum { PANEL_MERGE_K = 128 };    // the merge seam takes x16 rows of exactly this width
 bool fused_supported(int D, int I);
+// slots the seam phases add to a stream: merge in front of the first panel's QKV slots, head behind the last layer's MLP slots
+long fused_seam_slots(int D, int seam, int C);
 // bytes of the fragment stream of one layer: [wo | mlp | skip? | qkv?]
 long fused_stream_halfs(int D, int I, bool post, bool skip, bool qkv);
 // packs nn.Linear weights (fp32, [out][in]) into the stream at `dst`; returns the number of halfs written (0 on error)
 long fused_pack_stream(half_t* dst, int D, int I, const float* wo, const float* w1, const float* w3, const float* w2,
                        const float* wskip, const float* wqkv, hipStream_t st);
+// seam extensions: the x block (columns [0, C) of w_merge [D][ldw]) as PANEL_MERGE_K / 32 slots; the mlp head (wa [D][D], w2 [C][D])
+long fused_pack_merge(half_t* dst, int D, const float* w_merge, int ldw, int C, hipStream_t st);
+long fused_pack_head(half_t* dst, int D, const float* wa, const float* w2, int C, hipStream_t st);
 int fused_panel_launch(const PanelParams& p, int D, bool gated, hipStream_t st);
 
 // ------------------------------------------------------------------ attention (attention.hip)

@@ -79,6 +79,14 @@ struct svc_dit {
     };
     half_t* stream_pre = nullptr;   // [qkv(0)]
     int stream_pre_slots = 0;
+    // sampler seams inside the first / last panel (fused.hip): the x block of the merge linear sits in merge_slots slots in
+    // FRONT of stream_pre (stream_first), the mlp head in head_slots slots BEHIND the last layer's stream.  A launch without
+    // the seam starts at stream_pre / stops after stream_slots and never touches them.
+    half_t* stream_first = nullptr;
+    float* zero_row = nullptr;      // [D] zeros: the merge seam's operand / start value of prefix and pad rows
+    int merge_slots = 0, head_slots = 0;
+    bool merge_ok = false, head_ok = false;
+    int seams = 3;                  // svc_dit_set_fused_seams: bit 0 merge, bit 1 head
     bool fused_ok = false;
     long fused_min_rows = 10240;    // measured crossover (tiny and small, B = 4 vs 8 utterances x 2 streams): below ~80 row panels the tap-GEMMs win
     std::vector<Layer> layers;
@@ -133,7 +141,7 @@ struct svc_dit {
                   int stream_a, int stream_b, hipStream_t st);
     int sample(const svc_cfm_args_t* a, const uint64_t* seeds, hipStream_t st);
     int body(int n_streams, int B, int T, int step, hipStream_t st);
-    int body_fused(int n_streams, int B, int T, int step, hipStream_t st);
+    int body_fused(int n_streams, int B, int T, int step, bool seam_merge, bool seam_head, hipStream_t st);
     int head(int n_streams, int B, int T, int step, hipStream_t st);
 };
 
@@ -221,7 +229,9 @@ int svc_dit::pack(const StateDict& sd, hipStream_t st) {
             const bool nskip = !last && layers[i + 1].wskip != nullptr;
             const std::string pn = "transformer.layers." + std::to_string(i + 1) + ".";
             const long halfs = fused_stream_halfs(D, I, true, nskip, !last);
-            layers[i].stream = wts.alloc_n<half_t>(halfs, st);
+            head_ok = !wavenet && C % 16 == 0;
+            if (last && head_ok) head_slots = (int)fused_seam_slots(D, PANEL_SEAM_HEAD, C);
+            layers[i].stream = wts.alloc_n<half_t>(halfs + (last ? (long)head_slots * slot_halfs : 0), st);
             if (!layers[i].stream) return 1;
             const long wr = fused_pack_stream(layers[i].stream, D, I, W(p + "attention.wo.weight"), W(p + "feed_forward.w1.weight"),
                                               W(p + "feed_forward.w3.weight"), W(p + "feed_forward.w2.weight"),
@@ -231,8 +241,13 @@ int svc_dit::pack(const StateDict& sd, hipStream_t st) {
             layers[i].stream_slots = (int)(halfs / slot_halfs);
         }
         const long halfs = fused_stream_halfs(D, I, false, false, true);
-        stream_pre = wts.alloc_n<half_t>(halfs, st);
-        if (!stream_pre) return 1;
+        merge_ok = C16 == PANEL_MERGE_K;
+        if (merge_ok) merge_slots = (int)fused_seam_slots(D, PANEL_SEAM_MERGE, C);
+        stream_first = wts.alloc_n<half_t>((long)merge_slots * slot_halfs + halfs, st);
+        if (!stream_first) return 1;
+        stream_pre = stream_first + (long)merge_slots * slot_halfs;
+        zero_row = wts.alloc_n<float>(D, st);      // the arena hands out zeroed memory
+        if (!zero_row) return 1;
         if (fused_pack_stream(stream_pre, D, I, nullptr, nullptr, nullptr, nullptr, nullptr,
                               W("transformer.layers.0.attention.wqkv.weight"), st) != halfs) { set_error("fused stream packing failed"); return 1; }
         stream_pre_slots = (int)(halfs / slot_halfs);
@@ -299,6 +314,10 @@ int svc_dit::pack(const StateDict& sd, hipStream_t st) {
     w_merge_x = new16(D, C16);
     if (!w_merge_x) return 1;
     if (pack_block(0, wm->data, Kin, 0, D, C, w_merge_x, C16, 0, 0, 1, nullptr, st)) return 1;
+    if (merge_ok && fused_pack_merge(stream_first, D, wm->data, Kin, C, st) != (long)merge_slots * (D / 16) * 512) {
+        set_error("fused stream packing failed");
+        return 1;
+    }
     const long Ks = C32 + Dc;
     w_stat = wts.alloc_n<float>(Dp * Ks, st);
     stat_const = wts.alloc_n<float>(D, st);
@@ -338,6 +357,11 @@ int svc_dit::pack(const StateDict& sd, hipStream_t st) {
         if (!head_wa || !head_w2) return 1;
         if (pack_block(0, a->data, D, 0, D, D, head_wa, D, 0, 0, 1, nullptr, st)) return 1;
         if (pack_block(0, c->data, D, 0, C, D, head_w2, D, 0, 0, 1, nullptr, st)) return 1;
+        if (head_ok) {
+            const long slot_halfs = (long)(D / 16) * 512;
+            half_t* dst = layers[L - 1].stream + (long)layers[L - 1].stream_slots * slot_halfs;
+            if (fused_pack_head(dst, D, a->data, c->data, C, st) != head_slots * slot_halfs) { set_error("fused stream packing failed"); return 1; }
+        }
         head_b0 = copy_vec(wts, b->data, D, st);
         head_b2 = copy_vec(wts, d->data, C, st);
         if (!head_b0 || !head_b2) return 1;
@@ -620,11 +644,14 @@ int svc_dit::body(int n_streams, int B, int T, int step, hipStream_t st) {
     const int nseq = n_streams * B;
     const int M = nseq * seq_rows;
     const float* mod = d_mod + (long)step * mod_n;
+    const bool fused = fused_ok && (long)M >= fused_min_rows;
+    // the first panel builds the rows of xin itself (merge seam), the last one runs the mlp head (head seam)
+    const bool seam_merge = fused && merge_ok && (seams & 1), seam_head = fused && head_ok && (seams & 2);
     // 1. prefix tokens + zeroed pad rows
-    if (prefix_rows_launch(xin, nseq, seq_rows, D, npre, T + npre, d_t1 + (long)step * D, tok_style,
-                           cfg.time_as_token ? 1 : 0, st)) return 1;
+    if (!seam_merge && prefix_rows_launch(xin, nseq, seq_rows, D, npre, T + npre, d_t1 + (long)step * D, tok_style,
+                                          cfg.time_as_token ? 1 : 0, st)) return 1;
     // 2. x block of the merge linear + static term
-    {
+    if (!seam_merge) {
         KGemmParams p = gemm_base(nseq * T, D, T);
         p.a_ptr[0] = x16; p.a_ld[0] = C16; p.a_ktiles[0] = C16 / 64;
         p.a_seq_rows = seq_rows; p.a_len = T;
@@ -634,9 +661,9 @@ int svc_dit::body(int n_streams, int B, int T, int step, hipStream_t st) {
         p.res = st_term; p.ldres = D;
         if (kgemm_launch(p, 0, KG_EPI_STORE, st)) return 1;
     }
-    if (fused_ok && (long)M >= fused_min_rows) {
-        if (body_fused(n_streams, B, T, step, st)) return 1;
-        return head(n_streams, B, T, step, st);
+    if (fused) {
+        if (body_fused(n_streams, B, T, step, seam_merge, seam_head, st)) return 1;
+        return seam_head ? 0 : head(n_streams, B, T, step, st);
     }
     // The head and the LAST transformer layer's query-side work are evaluated on rows >= win0 only: the sampler discards the velocity on prompt frames
     // (flow_matching.py:105-110 zeroes x[..., :prompt_len] after every step), and every head op is row-local except the
@@ -855,7 +882,7 @@ int svc_dit::head(int n_streams, int B, int T, int step, hipStream_t st) {
 
 // Transformer stack on the fused row-panel kernel (fused.hip): one launch per layer besides attention.  Layer i's kernel
 // also runs the next layer's skip linear, attention norm, QKV projection and RoPE; the last one ends with the final norm.
-int svc_dit::body_fused(int n_streams, int B, int T, int step, hipStream_t st) {
+int svc_dit::body_fused(int n_streams, int B, int T, int step, bool seam_merge, bool seam_head, hipStream_t st) {
     const int nseq = n_streams * B;
     const int M = nseq * seq_rows;
     const float* mod = d_mod + (long)step * mod_n;
@@ -890,6 +917,12 @@ int svc_dit::body_fused(int n_streams, int B, int T, int step, hipStream_t st) {
         PanelParams p = base();
         p.wstream = stream_pre; p.n_slots = stream_pre_slots;
         set_qkv(p, 0);
+        if (seam_merge) {
+            p.seam = PANEL_SEAM_MERGE;
+            p.wstream = stream_first; p.n_slots = merge_slots + stream_pre_slots;
+            p.x16 = x16; p.st_term = st_term; p.zero_row = zero_row; p.T = T; p.npre = npre;
+            p.tok_time = d_t1 + (long)step * D; p.tok_style = tok_style; p.time_first = cfg.time_as_token ? 1 : 0;
+        }
         if (fused_panel_launch(p, D, v2, st)) return 1;
     }
     size_t emit_i = 0;
@@ -931,6 +964,11 @@ int svc_dit::body_fused(int n_streams, int B, int T, int step, hipStream_t st) {
             const float* fm = mod + (long)L * mod_layer_n;
             p.do_final = 1; p.g_fin = g_final; p.w_fin = fm; p.b_fin = fm + D; p.n16 = n16;
             if (tail_only) { p.Lout = seq_rows - win0; p.row_off = win0; p.M = nseq * p.Lout; }
+            if (seam_head) {
+                p.seam = PANEL_SEAM_HEAD;
+                p.n_slots = layers[i].stream_slots + head_slots;
+                p.head_b0 = head_b0; p.head_b2 = head_b2; p.v32 = v32; p.ldv = C16; p.head_C = C;
+            }
         }
         if (fused_panel_launch(p, D, v2, st)) return 1;
     }
@@ -1144,7 +1182,7 @@ int svc_dit::run_group(const svc_cfm_args_t* a, const uint64_t* seeds, int b0, i
     bool done = false;
     if ((graph_env >= 0 ? graph_env : use_graphs) && !prof_enabled()) {
         std::vector<float> key = {(float)n_streams, (float)nb, (float)T, (float)n_steps, (float)win0, (float)seq_rows, c0, ca, cb,
-                                  (float)stream_a, (float)stream_b, (float)fused_min_rows};
+                                  (float)stream_a, (float)stream_b, (float)fused_min_rows, (float)seams};
         key.insert(key.end(), dts.begin(), dts.end());
         StepGraph* g = nullptr;
         for (auto& c : graphs) if (c.key == key) { g = &c; break; }
@@ -1245,6 +1283,12 @@ int svc_dit_set_microbatch(svc_dit_t* m, int utterances) {
 int svc_dit_set_fused_min_rows(svc_dit_t* m, long rows) {
     SVC_REQUIRE(m, "null argument");
     m->fused_min_rows = rows < 0 ? 10240 : rows;
+    return 0;
+}
+
+int svc_dit_set_fused_seams(svc_dit_t* m, int mask) {
+    SVC_REQUIRE(m && mask >= 0 && mask <= 3, "svc_dit_set_fused_seams: mask is bit 0 (merge) | bit 1 (head)");
+    m->seams = mask;
     return 0;
 }
 

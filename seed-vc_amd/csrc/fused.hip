@@ -23,6 +23,7 @@
 // on the tap-GEMM path.  Built WITHOUT -amdgpu-mfma-vgpr-form: the accumulators must be allowed to live in AGPRs.
 #include <stdlib.h>
 
+#include <type_traits>
 #include <utility>
 
 #include "common.h"
@@ -130,7 +131,15 @@ enum { V_AF = 0, V_BF = 1, V_GA = 2, V_GF = 3, V_AA = 4, V_BA = 5, V_BS = 6, V_A
 // every LDS read latency at the start of a slot and every barrier is time the SIMD's matrix pipe idles (measured: 45 % of
 // a panel's time in MFMAs); with two, the partner wave computes meanwhile, at the price of every fragment being read from
 // LDS by twice as many waves (the LDS read port then runs at the MFMA rate).
-template <int D, bool GATED, int TM>
+//
+// SEAM adds a sampler seam to the first / last panel of a step (compile-time: the PANEL_SEAM_NONE instantiations, which the
+// middle layers launch, hold none of this code):
+//   PANEL_SEAM_MERGE  the first panel (do_qkv alone) builds its rows instead of loading them: data rows are the x block of
+//                     the merge linear (x16 row, PANEL_MERGE_K / 32 natural-order slots in front of the QKV slots) plus
+//                     the static term, prefix rows the token vector, pad rows zero; the rows are stored for layer 0.
+//   PANEL_SEAM_HEAD   the last panel (do_post + do_final) runs the mlp head on the final-norm rows it holds: D / 32 slots
+//                     of head linear 1 (kperm order, as P5), SiLU, then head linear 2 as 16-column tiles, two per slot.
+template <int D, bool GATED, int TM, int SEAM>
 __global__ __launch_bounds__(128 / (16 * TM) * 64, 128 / (16 * TM) / 4) void dit_panel_kernel(const PanelParams p) {
     using G = PG<D>;
     constexpr int NT = G::NT, KC = G::KC, NS = G::NS, PF = G::PF;
@@ -143,6 +152,10 @@ __global__ __launch_bounds__(128 / (16 * TM) * 64, 128 / (16 * TM) / 4) void dit
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fr = lane & 15, fq = lane >> 4;
     const int m0 = blockIdx.x * 128 + wave * (16 * TM);
+    // a seam fixes the phases of its launch at compile time; without one the flags are read where they are tested, as before
+#define DO_POST (SEAM == PANEL_SEAM_MERGE ? 0 : SEAM == PANEL_SEAM_HEAD ? 1 : p.do_post)
+#define DO_SKIP (SEAM == PANEL_SEAM_NONE ? p.do_skip : 0)
+#define DO_QKV (SEAM == PANEL_SEAM_MERGE ? 1 : SEAM == PANEL_SEAM_HEAD ? 0 : p.do_qkv)
 
     // ---- per-column vectors -> LDS (plain loads; before any LDS-DMA is in flight)
     for (int c = tid; c < D; c += NTHR) {
@@ -156,6 +169,10 @@ __global__ __launch_bounds__(128 / (16 * TM) * 64, 128 / (16 * TM) / 4) void dit
         vec[V_BS * D + c] = p.bskip ? p.bskip[c] : 0.f;
         vec[V_AN * D + c] = p.g_fin ? p.g_fin[c] * (p.w_fin ? one + p.w_fin[c] : 1.f) : 0.f;
         vec[V_BN * D + c] = p.b_fin ? p.b_fin[c] : 0.f;
+        if constexpr (SEAM == PANEL_SEAM_HEAD) {      // the last panel runs neither P5 nor P6: their slots carry the head biases
+            vec[V_AA * D + c] = p.head_b0[c];
+            vec[V_BA * D + c] = c < p.head_C ? p.head_b2[c] : 0.f;
+        }
     }
     __syncthreads();
 
@@ -234,7 +251,9 @@ __global__ __launch_bounds__(128 / (16 * TM) * 64, 128 / (16 * TM) / 4) void dit
     half8 xn[KC][TM];             // fp16 B-operand fragments: k slot (fq, j) of chunk c <-> column 32 c + 16 (j >> 2) + 4 fq + (j & 3)
 
     // RMSNorm (+ adaptive modulation) of the rows held in acc -> xn;  A = gamma * (add_one + w), B = b
-    auto norm_to_xn = [&](const float* va, const float* vb) {
+    // fenced: every chunk is finished where it is written.  In front of straight-line slot code (the head seam) hipcc
+    // otherwise sinks the arithmetic to the slot that uses the chunk and keeps all the vectors live instead: spills.
+    auto norm_to_xn = [&](const float* va, const float* vb, auto fenced) {
         float rs[TM];
 #pragma unroll
         for (int mt = 0; mt < TM; ++mt) {
@@ -263,6 +282,11 @@ __global__ __launch_bounds__(128 / (16 * TM) * 64, 128 / (16 * TM) / 4) void dit
                 }
                 xn[c][mt] = h;
             }
+            if constexpr (decltype(fenced)::value) {
+#pragma unroll
+                for (int mt = 0; mt < TM; ++mt) asm volatile("" : "+v"(xn[c][mt]));
+                __builtin_amdgcn_sched_barrier(0);
+            }
         }
     };
     auto store_x = [&]() {
@@ -274,7 +298,7 @@ __global__ __launch_bounds__(128 / (16 * TM) * 64, 128 / (16 * TM) / 4) void dit
             }
     };
 
-    if (p.do_post) {
+    if (DO_POST) {
         // ---------------------------------------------------------------- P1: x1 = x + [gate_a *] ao Wo^T
         {
             half8 af[KC][TM];
@@ -310,7 +334,7 @@ __global__ __launch_bounds__(128 / (16 * TM) * 64, 128 / (16 * TM) / 4) void dit
             store_x();          // x1 is re-read after the MLP (the registers are needed for the MLP accumulators)
         }
         // ---------------------------------------------------------------- P2: n = ffn_norm(x1)
-        norm_to_xn(vec + V_AF * D, vec + V_BF * D);
+        norm_to_xn(vec + V_AF * D, vec + V_BF * D, std::false_type{});
         if constexpr (GATED) {
 #pragma unroll
             for (int mt = 0; mt < TM; ++mt)
@@ -382,7 +406,7 @@ __global__ __launch_bounds__(128 / (16 * TM) * 64, 128 / (16 * TM) / 4) void dit
                 }
         }
         // ---------------------------------------------------------------- P4: layer output
-        if (!p.do_skip) store_x();
+        if (!DO_SKIP && SEAM != PANEL_SEAM_HEAD) store_x();          // nothing reads x behind the head seam
         if (p.c16) {
 #pragma unroll
             for (int mt = 0; mt < TM; ++mt)
@@ -394,6 +418,41 @@ __global__ __launch_bounds__(128 / (16 * TM) * 64, 128 / (16 * TM) / 4) void dit
                     }
                 }
         }
+    } else if constexpr (SEAM == PANEL_SEAM_MERGE) {
+        // ---------------------------------------------------------------- merge seam: x = st_term + x16 Wx^T | token | 0
+        // As P1 without gates: the accumulators start from a row of fp32 values and the MFMAs add the x block on top.  What
+        // a lane starts from and multiplies is chosen by ADDRESS, never by a select on loaded values (hipcc turns those
+        // into a branch and a full wait around every load): data rows take their st_term and x16 rows; prefix rows the
+        // token vector and p.zero_row as the operand, so the MFMAs add exact zeros to it; pad rows p.zero_row for both.
+        // The row index is clamped into [0, T) first, so no lane forms an address outside the buffers.
+        constexpr int KM = PANEL_MERGE_K / 32;
+        half8 af[KM][TM];
+#pragma unroll
+        for (int mt = 0; mt < TM; ++mt) {
+            const int m = m0 + 16 * mt + fr;
+            const int mm = m < p.M ? m : p.M - 1;
+            const int seq = mm / p.Lout;
+            const int pos = p.row_off + (mm - seq * p.Lout);
+            const int t = pos - p.npre;
+            const bool is_data = t >= 0 && t < p.T;
+            const int tc = t < 0 ? 0 : (t < p.T ? t : p.T - 1);
+            const half_t* xr = is_data ? p.x16 + ((long)seq * p.seq_rows + tc) * PANEL_MERGE_K : reinterpret_cast<const half_t*>(p.zero_row);
+            const float* tok = (p.time_first && pos == 0) ? p.tok_time : p.tok_style + (long)seq * D;
+            const float* rsrc = is_data ? p.st_term + ((long)seq * p.seq_rows + p.npre + tc) * D : (t < 0 ? tok : p.zero_row);
+#pragma unroll
+            for (int kc = 0; kc < KM; ++kc) af[kc][mt] = *reinterpret_cast<const half8*>(xr + 32 * kc + 8 * fq);
+#pragma unroll
+            for (int t_ = 0; t_ < NT; ++t_) acc[t_][mt] = *reinterpret_cast<const float4v*>(rsrc + 16 * t_ + 4 * fq);
+        }
+#pragma unroll
+        for (int kc = 0; kc < KM; ++kc) {
+            const char* base = acquire();
+            stream_frags<NT, PF, TM, RFI>(base, [&](int t, half8 w) {
+#pragma unroll
+                for (int mt = 0; mt < TM; ++mt) acc[t][mt] = MFMA(w, af[kc][mt], acc[t][mt]);
+            }, refill);
+        }
+        store_x();          // layer 0 reads p.x
     } else {
 #pragma unroll
         for (int mt = 0; mt < TM; ++mt)
@@ -401,7 +460,7 @@ __global__ __launch_bounds__(128 / (16 * TM) * 64, 128 / (16 * TM) / 4) void dit
             for (int t = 0; t < NT; ++t) acc[t][mt] = *reinterpret_cast<const float4v*>(p.x + grow[mt] * D + 16 * t + 4 * fq);
     }
 
-    if (p.do_skip) {
+    if (DO_SKIP) {
         // ---------------------------------------------------------------- P5: x = Wskip [x | skip] + b (UViT receiver)
 #pragma unroll
         for (int c = 0; c < KC; ++c)
@@ -443,7 +502,72 @@ __global__ __launch_bounds__(128 / (16 * TM) * 64, 128 / (16 * TM) / 4) void dit
         store_x();
     }
 
-    if (p.do_final) {
+    if constexpr (SEAM == PANEL_SEAM_HEAD) {
+        // ---------------------------------------------------------------- head seam: v = W2 silu(Wa n + b0) + b2, n = final norm
+        norm_to_xn(vec + V_AN * D, vec + V_BN * D, std::true_type{});          // the fp16 rows the tap-GEMM head reads from n16
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+            for (int mt = 0; mt < TM; ++mt) acc[t][mt] = (float4v){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int kc = 0; kc < KC; ++kc) {
+            const char* base = acquire();
+            stream_frags<NT, PF, TM, RFI>(base, [&](int t, half8 w) {
+#pragma unroll
+                for (int mt = 0; mt < TM; ++mt) acc[t][mt] = MFMA(w, xn[kc][mt], acc[t][mt]);
+            }, refill);
+        }
+        // the biases join behind the sums, as in a GEMM epilogue (and are read from LDS only where they are used)
+        constexpr float LOG2E = 1.4426950408889634f;
+#pragma unroll
+        for (int c = 0; c < KC; ++c) {
+            const float4v b0 = *reinterpret_cast<const float4v*>(vec + V_AA * D + 32 * c + 4 * fq);
+            const float4v b1 = *reinterpret_cast<const float4v*>(vec + V_AA * D + 32 * c + 16 + 4 * fq);
+#pragma unroll
+            for (int mt = 0; mt < TM; ++mt) {
+                half8 h;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float a = acc[2 * c][mt][j] + b0[j], b = acc[2 * c + 1][mt][j] + b1[j];
+                    h[j] = (half_t)(a * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-a * LOG2E)));
+                    h[4 + j] = (half_t)(b * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-b * LOG2E)));
+                }
+                xn[c][mt] = h;
+                asm volatile("" : "+v"(xn[c][mt]));          // computed here, not sunk to the slot that uses it
+            }
+        }
+        // output tiles of 16 columns, two per slot (fragment f of slot s: tile 2 s + f / KC, chunk f % KC); head_C <= 128
+        constexpr int HS = 4;
+        float4v hv[2 * HS][TM];
+#pragma unroll
+        for (int t = 0; t < 2 * HS; ++t)
+#pragma unroll
+            for (int mt = 0; mt < TM; ++mt) hv[t][mt] = (float4v){0.f, 0.f, 0.f, 0.f};
+        const int n_tiles = p.head_C / 16;
+#pragma unroll
+        for (int s = 0; s < HS; ++s) {
+            if (2 * s < n_tiles) {
+                const char* base = acquire();
+                stream_frags<NT, PF, TM, RFI>(base, [&](int f, half8 w) {
+#pragma unroll
+                    for (int mt = 0; mt < TM; ++mt) hv[2 * s + f / KC][mt] = MFMA(w, xn[f % KC][mt], hv[2 * s + f / KC][mt]);
+                }, refill);
+            }
+        }
+#pragma unroll
+        for (int mt = 0; mt < TM; ++mt)
+            if (rok[mt]) {
+#pragma unroll
+                for (int t = 0; t < 2 * HS; ++t)
+                    if (t < n_tiles) {
+                        const float4v b2 = *reinterpret_cast<const float4v*>(vec + V_BA * D + 16 * t + 4 * fq);
+                        float4v o;
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) o[j] = hv[t][mt][j] + b2[j];
+                        *reinterpret_cast<float4v*>(p.v32 + grow[mt] * p.ldv + 16 * t + 4 * fq) = o;
+                    }
+            }
+    } else if (SEAM == PANEL_SEAM_NONE && p.do_final) {
         // ---------------------------------------------------------------- final adaptive norm -> fp16 rows for the head
         float rs[TM];
 #pragma unroll
@@ -472,9 +596,9 @@ __global__ __launch_bounds__(128 / (16 * TM) * 64, 128 / (16 * TM) / 4) void dit
         }
     }
 
-    if (p.do_qkv) {
+    if (DO_QKV) {
         // ---------------------------------------------------------------- P6: n = attention_norm(x) of the next layer
-        norm_to_xn(vec + V_AA * D, vec + V_BA * D);
+        norm_to_xn(vec + V_AA * D, vec + V_BA * D, std::bool_constant<SEAM == PANEL_SEAM_MERGE>{});
         // ---------------------------------------------------------------- P7: q, k (RoPE) and v^T, 64 columns (one head) per trip
         float rp[TM][16];          // (cos, sin) of pairs 8 fq .. 8 fq + 7 at this lane's positions
         int posl[TM];
@@ -567,12 +691,18 @@ __global__ __launch_bounds__(128 / (16 * TM) * 64, 128 / (16 * TM) / 4) void dit
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #undef FRAG
 #undef MFMA
+#undef DO_POST
+#undef DO_SKIP
+#undef DO_QKV
 }
 
 // ---------------------------------------------------------------------------------------------- fragment packing
-// One thread per fp16 element of the stream.  mode: 0 wo, 1 mlp, 2 skip, 3 qkv (see the fragment definitions in DESIGN.md 5)
+// One thread per fp16 element of the stream.  mode: 0 wo, 1 mlp, 2 skip, 3 qkv (see the fragment definitions in DESIGN.md 5);
+// seams: 4 natural-order chunks of a [D][ldw] weight (columns >= kvalid read as zero), 5 kperm-order chunks of a [D][ldw]
+// weight, 6 head linear 2 ([kvalid][D], kperm order): 16-row tiles, KC fragments each, two tiles per slot, zero past the end.
+// Modes 0-3 take ldw = D.
 __global__ void pack_stream_kernel(half_t* __restrict__ dst, long n_elems, int mode, int D, int I, const float* __restrict__ w0,
-                                   const float* __restrict__ w1, const float* __restrict__ w2) {
+                                   const float* __restrict__ w1, const float* __restrict__ w2, int ldw, int kvalid) {
     const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n_elems) return;
     const int NT = D / 16, KC = D / 32;
@@ -601,6 +731,17 @@ __global__ void pack_stream_kernel(half_t* __restrict__ dst, long n_elems, int m
         const int kc = (int)(f / NT), t = (int)(f % NT);
         const int k = kc < KC ? 32 * kc + kperm : D + 32 * (kc - KC) + knat;
         v = w0[(long)(16 * t + fr) * (2 * D) + k];
+    } else if (mode == 4) {                // natural-order chunks: f = kc * NT + t
+        const int kc = (int)(f / NT), t = (int)(f % NT);
+        const int k = 32 * kc + knat;
+        v = k < kvalid ? w0[(long)(16 * t + fr) * ldw + k] : 0.f;
+    } else if (mode == 5) {                // kperm-order chunks: f = kc * NT + t
+        const int kc = (int)(f / NT), t = (int)(f % NT);
+        v = w0[(long)(16 * t + fr) * ldw + 32 * kc + kperm];
+    } else if (mode == 6) {                // head linear 2: f = tile * KC + kc
+        const int t = (int)(f / KC), kc = (int)(f % KC);
+        const int n = 16 * t + fr;
+        v = n < kvalid ? w0[(long)n * D + 32 * kc + kperm] : 0.f;
     } else {                               // qkv: f = (grp * KC + kc) * 4 + t ; weight [3 D][D]
         const int grp = (int)(f / (4 * KC)), q = (int)(f % (4 * KC));
         const int kc = q / 4, t = q % 4;
@@ -621,6 +762,13 @@ static long slots_post(int D, int I) { return D / 32 + 3L * (I / 32); }
 static long slots_skip(int D) { return 2L * (D / 32); }
 static long slots_qkv(int D) { return 2L * (3 * D / 64); }
 
+static long head_slots2(int C) { return (C / 16 + 1) / 2; }          // 16-column tiles of head linear 2, two per slot
+long fused_seam_slots(int D, int seam, int C) {
+    if (seam == PANEL_SEAM_MERGE) return PANEL_MERGE_K / 32;
+    if (seam == PANEL_SEAM_HEAD) return D / 32 + head_slots2(C);
+    return 0;
+}
+
 long fused_stream_halfs(int D, int I, bool post, bool skip, bool qkv) {
     const long slot_halfs = (long)(D / 16) * 512;
     return ((post ? slots_post(D, I) : 0) + (skip ? slots_skip(D) : 0) + (qkv ? slots_qkv(D) : 0)) * slot_halfs;
@@ -632,7 +780,7 @@ long fused_pack_stream(half_t* dst, int D, int I, const float* wo, const float* 
     long off = 0;
     auto run = [&](int mode, long slots, const float* a, const float* b, const float* c) -> bool {
         const long n = slots * slot_halfs;
-        hipLaunchKernelGGL(pack_stream_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, dst + off, n, mode, D, I, a, b, c);
+        hipLaunchKernelGGL(pack_stream_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, dst + off, n, mode, D, I, a, b, c, D, 0);
         off += n;
         return hipGetLastError() == hipSuccess;
     };
@@ -645,6 +793,21 @@ long fused_pack_stream(half_t* dst, int D, int I, const float* wo, const float* 
     return off;
 }
 
+long fused_pack_merge(half_t* dst, int D, const float* w_merge, int ldw, int C, hipStream_t st) {
+    const long n = fused_seam_slots(D, PANEL_SEAM_MERGE, C) * (D / 16) * 512;
+    hipLaunchKernelGGL(pack_stream_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, dst, n, 4, D, 0, w_merge, nullptr, nullptr, ldw, C);
+    return hipGetLastError() == hipSuccess ? n : 0;
+}
+
+long fused_pack_head(half_t* dst, int D, const float* wa, const float* w2, int C, hipStream_t st) {
+    const long slot_halfs = (long)(D / 16) * 512;
+    const long n1 = (D / 32) * slot_halfs, n2 = head_slots2(C) * slot_halfs;
+    hipLaunchKernelGGL(pack_stream_kernel, dim3(cdiv(n1, 256)), dim3(256), 0, st, dst, n1, 5, D, 0, wa, nullptr, nullptr, D, D);
+    if (hipGetLastError() != hipSuccess) return 0;
+    hipLaunchKernelGGL(pack_stream_kernel, dim3(cdiv(n2, 256)), dim3(256), 0, st, dst + n1, n2, 6, D, 0, w2, nullptr, nullptr, D, C);
+    return hipGetLastError() == hipSuccess ? n1 + n2 : 0;
+}
+
 int fused_panel_launch(const PanelParams& p, int D, bool gated, hipStream_t st) {
     SVC_REQUIRE(D == 384 || D == 512, "fused panel kernel: D must be 384 or 512");
     SVC_REQUIRE(p.M > 0 && p.Lout > 0 && p.I % 32 == 0, "fused panel kernel: shape");
@@ -652,13 +815,28 @@ int fused_panel_launch(const PanelParams& p, int D, bool gated, hipStream_t st) 
     DeviceState* ds = device_state();
     if (!ds) return 1;
     if (!ds->fused_attr.load(std::memory_order_acquire)) {
-#define SVC_PANEL_ATTR(DD, GG, TT) SVC_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(dit_panel_kernel<DD, GG, TT>), hipFuncAttributeMaxDynamicSharedMemorySize, PG<DD>::LDS))
+#define SVC_PANEL_ATTR1(DD, GG, TT, SS) SVC_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(dit_panel_kernel<DD, GG, TT, SS>), hipFuncAttributeMaxDynamicSharedMemorySize, PG<DD>::LDS))
+        // the merge seam runs no gated phase: one instantiation serves both
+#define SVC_PANEL_ATTR(DD, GG, TT) SVC_PANEL_ATTR1(DD, GG, TT, PANEL_SEAM_NONE); SVC_PANEL_ATTR1(DD, GG, TT, PANEL_SEAM_HEAD); if (!GG) SVC_PANEL_ATTR1(DD, false, TT, PANEL_SEAM_MERGE)
         SVC_PANEL_ATTR(384, false, 1); SVC_PANEL_ATTR(384, true, 1); SVC_PANEL_ATTR(512, false, 1); SVC_PANEL_ATTR(512, true, 1);
         SVC_PANEL_ATTR(384, false, 2); SVC_PANEL_ATTR(384, true, 2); SVC_PANEL_ATTR(512, false, 2); SVC_PANEL_ATTR(512, true, 2);
 #undef SVC_PANEL_ATTR
+#undef SVC_PANEL_ATTR1
         ds->fused_attr.store(true, std::memory_order_release);
     }
-    const long want = (p.do_post ? slots_post(D, p.I) : 0) + (p.do_skip ? slots_skip(D) : 0) + (p.do_qkv ? slots_qkv(D) : 0);
+    if (p.seam == PANEL_SEAM_MERGE) {
+        SVC_REQUIRE(!p.do_post && !p.do_skip && !p.do_final && p.do_qkv && p.row_off == 0, "fused panel kernel: the merge seam belongs to the first panel");
+        SVC_REQUIRE(p.x16 && p.st_term && p.zero_row && p.T >= 1 && p.npre >= 0 && p.npre + p.T <= p.seq_rows, "fused panel kernel: merge seam operands");
+        SVC_REQUIRE(p.npre == 0 || ((p.tok_time || !p.time_first) && (p.tok_style || (p.time_first && p.npre == 1))), "fused panel kernel: merge seam tokens");
+    } else if (p.seam == PANEL_SEAM_HEAD) {
+        SVC_REQUIRE(p.do_post && !p.do_skip && p.do_final && !p.do_qkv && !p.c16, "fused panel kernel: the head seam belongs to the last panel");
+        SVC_REQUIRE(p.head_b0 && p.head_b2 && p.v32 && p.head_C >= 16 && p.head_C % 16 == 0 && p.head_C <= 128 && p.ldv >= p.head_C && p.ldv % 4 == 0,
+                    "fused panel kernel: head seam operands");
+    } else {
+        SVC_REQUIRE(p.seam == PANEL_SEAM_NONE, "fused panel kernel: unknown seam");
+    }
+    const long want = (p.do_post ? slots_post(D, p.I) : 0) + (p.do_skip ? slots_skip(D) : 0) + (p.do_qkv ? slots_qkv(D) : 0) +
+                      fused_seam_slots(D, p.seam, p.head_C);
     SVC_REQUIRE(want == p.n_slots, "fused panel kernel: slot count does not match the enabled phases");
     const int grid = cdiv(p.M, 128);
     const bool prof = prof_enabled();
@@ -668,7 +846,13 @@ int fused_panel_launch(const PanelParams& p, int D, bool gated, hipStream_t st) 
     // residual accumulators leave no room and the side accumulators need the inline-asm path).  SVC_FUSED_TM overrides.
     static const int tm_env = [] { const char* e = getenv("SVC_FUSED_TM"); return e ? atoi(e) : 0; }();
     const int tm = (tm_env == 1 || tm_env == 2) ? tm_env : (D == 384 ? 2 : 1);
-#define SVC_PANEL_LAUNCH(DD, GG, TT) hipLaunchKernelGGL((dit_panel_kernel<DD, GG, TT>), dim3(grid), dim3(128 / (16 * TT) * 64), PG<DD>::LDS, st, p)
+#define SVC_PANEL_LAUNCH1(DD, GG, TT, SS) hipLaunchKernelGGL((dit_panel_kernel<DD, GG, TT, SS>), dim3(grid), dim3(128 / (16 * TT) * 64), PG<DD>::LDS, st, p)
+#define SVC_PANEL_LAUNCH(DD, GG, TT)                                              \
+    do {                                                                          \
+        if (p.seam == PANEL_SEAM_MERGE) SVC_PANEL_LAUNCH1(DD, false, TT, PANEL_SEAM_MERGE); \
+        else if (p.seam == PANEL_SEAM_HEAD) SVC_PANEL_LAUNCH1(DD, GG, TT, PANEL_SEAM_HEAD); \
+        else SVC_PANEL_LAUNCH1(DD, GG, TT, PANEL_SEAM_NONE);                      \
+    } while (0)
     if (tm == 2) {
         if (D == 384) { if (gated) SVC_PANEL_LAUNCH(384, true, 2); else SVC_PANEL_LAUNCH(384, false, 2); }
         else { if (gated) SVC_PANEL_LAUNCH(512, true, 2); else SVC_PANEL_LAUNCH(512, false, 2); }
@@ -677,6 +861,7 @@ int fused_panel_launch(const PanelParams& p, int D, bool gated, hipStream_t st) 
         else { if (gated) SVC_PANEL_LAUNCH(512, true, 1); else SVC_PANEL_LAUNCH(512, false, 1); }
     }
 #undef SVC_PANEL_LAUNCH
+#undef SVC_PANEL_LAUNCH1
     SVC_CHECK_HIP(hipGetLastError());
     if (prof) {
         const double M = p.M, Dd = D;
@@ -684,12 +869,16 @@ int fused_panel_launch(const PanelParams& p, int D, bool gated, hipStream_t st) 
         if (p.do_post) macs += Dd * Dd + 3.0 * Dd * p.I;
         if (p.do_skip) macs += 2.0 * Dd * Dd;
         if (p.do_qkv) macs += 3.0 * Dd * Dd;
+        if (p.seam == PANEL_SEAM_MERGE) macs += Dd * (double)PANEL_MERGE_K;
+        if (p.seam == PANEL_SEAM_HEAD) macs += Dd * Dd + Dd * p.head_C;
         // algorithmic bytes: x in/out fp32, attn_out in, q/k/v out, skip in, fp16 copies out, weights once
         double bytes = 2.0 * macs;
         bytes += M * Dd * ((p.do_post ? 4 + 2 : 4) + ((p.do_post && !p.do_skip) || p.do_skip ? 4 : 0) + (p.c16 ? 2 : 0) +
-                           (p.do_skip ? 2 : 0) + (p.do_qkv ? 6 : 0) + (p.do_final ? 2 : 0));
+                           (p.do_skip ? 2 : 0) + (p.do_qkv ? 6 : 0) + (p.do_final && !p.seam ? 2 : 0));
+        if (p.seam == PANEL_SEAM_MERGE) bytes += M * (2.0 * (double)PANEL_MERGE_K + 4.0 * Dd);      // x16 and st_term in (x out is counted above)
+        if (p.seam == PANEL_SEAM_HEAD) bytes += M * (4.0 * p.head_C - 4.0 * Dd);            // v out; the layer output is not stored
         const unsigned long long tag = ((unsigned long long)p.M << 40) | ((unsigned long long)(D & 0xFFFFF) << 20) |
-                                       ((unsigned long long)(p.I & 0xFFFF) << 4) |
+                                       ((unsigned long long)((p.I + p.seam) & 0xFFFF) << 4) |      // I % 32 == 0: K column = I + seam
                                        (unsigned)((p.do_post ? 1 : 0) | (p.do_skip ? 2 : 0) | (p.do_qkv ? 4 : 0) | (p.do_final ? 8 : 0));
         prof_end(PROF_FUSED, 2.0 * M * macs, bytes, st, tag);
     }
