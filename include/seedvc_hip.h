@@ -882,6 +882,48 @@ int svc_op_conv1d_ex(svc_conv1d_ex_t* args, void* stream);
 /* Test aid: the `took` word of this thread's last successful svc_op_conv1d or svc_op_conv1d_ex call (the first has no argument
  * for it). */
 int svc_op_conv1d_last_took(void);
+/* Test aid (tests/test_gpu_panel.py; no model uses it): ONE launch of the fused DiT row-panel kernel (csrc/fused.hip) on
+ * unpacked nn.Linear weights.  The call packs the given weights with the model's own packers into a temporary stream in the
+ * model's order ([merge | wo, mlp | skip | qkv | head]), launches once and synchronises.  Device pointers; NULL = absent.
+ *   D 384 | 512, I a multiple of 32, gated: the AdaLN-zero form (x += gate * ...), tm: 16-row tiles per wave 1 | 2, 0 = the
+ *   launcher's choice.  Local row m < M = n_seq * Lout is buffer row (m / Lout) * seq_rows + row_off + m % Lout; every
+ *   activation buffer has n_seq * seq_rows rows, row_off + Lout <= seq_rows.
+ *   phases: do_post (wo, w1, w3 [I][D], w2 [D][I], ao, g_ffn, optional gates and w_f / b_f; c16 = fp16 copy of its output),
+ *   do_skip (wskip [D][2 D], skip_in, bskip), do_final (g_fin, w_fin, b_fin -> n16), do_qkv (wqkv [3 D][D], g_attn, w_a, b_a,
+ *   rope [>= row_off + Lout][32][2] -> qk [rows][2 D], vt[seq][d][vt_pos(position, vt_mode)] with vt_ld >= the written positions
+ *   rounded up to 32).  norm vectors: A = g * (add_one + w), or g without w.
+ *   seam 1 (merge, with do_qkv alone, row_off 0): x[seq][pos] = tok_time (time_first and pos 0) | tok_style[seq] for pos < npre,
+ *   st_term[seq][pos] + w_merge[:, :C] x16[seq][pos - npre] for npre <= pos < npre + T, zeros beyond; w_merge [D][ldw], C <= 128,
+ *   x16 [n_seq][seq_rows][128] (columns >= C are multiplied by zero weights), st_term [n_seq][seq_rows][D].
+ *   seam 2 (head, with do_post and do_final, no c16): v32[row][< head_C] = head_w2 silu(head_wa n + head_b0) + head_b2 on the
+ *   final-norm rows n; head_wa [D][D], head_w2 [head_C][D], head_C 16 .. 128 in steps of 16, ldv >= head_C; n16 is not
+ *   written, and x is scratch (the gated form leaves x + gate_a * wo(ao) there, the ungated form leaves it alone).
+ *   x is read and written in place.  Refused (nothing launched): whatever fused_panel_launch refuses, a launch without a
+ *   streamed phase, and a NULL operand of an enabled phase. */
+typedef struct {
+    int32_t D, I, gated, tm;
+    int32_t M, Lout, seq_rows, row_off, n_seq;
+    float eps; int32_t add_one;
+    int32_t do_post, do_skip, do_qkv, do_final, seam;
+    const float* wo; const float* w1; const float* w3; const float* w2; const float* wskip; const float* wqkv;
+    const float* w_merge; int32_t ldw, C;
+    const float* head_wa; const float* head_w2;
+    const float* gate_a; const float* gate_f;
+    const float* g_ffn; const float* w_f; const float* b_f;
+    const float* g_attn; const float* w_a; const float* b_a;
+    const float* bskip;
+    const float* g_fin; const float* w_fin; const float* b_fin;
+    const float* head_b0; const float* head_b2;
+    const float* tok_time; const float* tok_style;
+    const uint16_t* ao; const uint16_t* skip_in; const uint16_t* x16;
+    float* x; const float* st_term;
+    uint16_t* c16; uint16_t* n16; uint16_t* qk;
+    uint16_t* vt; int64_t vt_seq_stride, vt_ld; int32_t vt_mode;
+    float* v32; int32_t ldv, head_C;
+    const float* rope; float q_scale;
+    int32_t npre, time_first, T;
+} svc_dit_panel_t;
+int svc_op_dit_panel(const svc_dit_panel_t* args, void* stream);
 /* ConvTranspose1d (k = 2*stride, padding = stride/2): x [B][L][Cin], w [Cin][Cout][k], y [B][L*stride][Cout]. */
 int svc_op_conv_transpose1d(const float* x, const float* w, const float* bias, float* y, int B, int L, int Cin,
                             int Cout, int k, int stride, int dtype, void* stream);

@@ -42,7 +42,7 @@ EXPORTS = [
     "svc_astral_set_timing", "svc_astral_last_timing", "svc_astral_ssl", "svc_astral_convnext", "svc_astral_logits", "svc_astral_tokens",
     "svc_op_bsq_index", "svc_tokens_reduce",
     "svc_prof_enable", "svc_prof_collect",
-    "svc_op_linear", "svc_op_conv1d", "svc_op_conv1d_ex", "svc_op_conv1d_last_took", "svc_op_conv_transpose1d", "svc_op_attention", "svc_op_rmsnorm",
+    "svc_op_linear", "svc_op_conv1d", "svc_op_conv1d_ex", "svc_op_conv1d_last_took", "svc_op_dit_panel", "svc_op_conv_transpose1d", "svc_op_attention", "svc_op_rmsnorm",
     "svc_op_layernorm", "svc_op_layernorm_gelu",
 ]
 
@@ -139,6 +139,21 @@ class Conv1dEx(C.Structure):
                 ("y", C.c_void_p), ("plane_hi", C.c_void_p), ("plane_lo", C.c_void_p), ("took", C.c_int32)]
 
 
+class DitPanel(C.Structure):
+    """svc_dit_panel_t: the arguments of svc_op_dit_panel (test aid)."""
+    _fields_ = [(n, C.c_int32) for n in ("D", "I", "gated", "tm", "M", "Lout", "seq_rows", "row_off", "n_seq")] + \
+               [("eps", C.c_float), ("add_one", C.c_int32)] + \
+               [(n, C.c_int32) for n in ("do_post", "do_skip", "do_qkv", "do_final", "seam")] + \
+               [(n, C.c_void_p) for n in ("wo", "w1", "w3", "w2", "wskip", "wqkv", "w_merge")] + \
+               [("ldw", C.c_int32), ("C", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("head_wa", "head_w2", "gate_a", "gate_f", "g_ffn", "w_f", "b_f", "g_attn", "w_a", "b_a", "bskip",
+                                          "g_fin", "w_fin", "b_fin", "head_b0", "head_b2", "tok_time", "tok_style",
+                                          "ao", "skip_in", "x16", "x", "st_term", "c16", "n16", "qk", "vt")] + \
+               [("vt_seq_stride", C.c_int64), ("vt_ld", C.c_int64), ("vt_mode", C.c_int32),
+                ("v32", C.c_void_p), ("ldv", C.c_int32), ("head_C", C.c_int32), ("rope", C.c_void_p), ("q_scale", C.c_float),
+                ("npre", C.c_int32), ("time_first", C.c_int32), ("T", C.c_int32)]
+
+
 _lib = None
 
 
@@ -168,6 +183,7 @@ def lib():
         l.svc_hift_forward_ragged.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         l.svc_op_conv1d_ex.argtypes = [C.POINTER(Conv1dEx), C.c_void_p]
+        l.svc_op_dit_panel.argtypes = [C.POINTER(DitPanel), C.c_void_p]
         # seeded noise: 64-bit seeds by value and as HOST arrays
         l.svc_cfm_sample_seeded.argtypes = [C.c_void_p, C.POINTER(CfmArgs), C.POINTER(C.c_uint64), C.c_void_p]
         l.svc_cfm_noise_draws.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]

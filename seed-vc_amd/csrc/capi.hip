@@ -292,6 +292,87 @@ int svc_op_rmsnorm(const float* x, const float* gamma, const float* w, const flo
     return 0;
 }
 
+// One launch of the fused DiT row-panel kernel on unpacked weights (tests/test_gpu_panel.py): packs the stream of the enabled
+// phases in the order dit.hip builds its streams ([merge | wo, mlp | skip | qkv | head]) and launches once.
+int svc_op_dit_panel(const svc_dit_panel_t* e, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    SVC_REQUIRE(e, "svc_op_dit_panel: null argument");
+    const int D = e->D, I = e->I;
+    SVC_REQUIRE(D == 384 || D == 512, "svc_op_dit_panel: D must be 384 or 512");
+    SVC_REQUIRE(I >= 0 && I % 32 == 0 && (!e->do_post || I >= 32), "svc_op_dit_panel: I is a positive multiple of 32");
+    SVC_REQUIRE(e->n_seq >= 1 && e->Lout >= 1 && e->M == e->n_seq * e->Lout && e->row_off >= 0 && e->row_off + e->Lout <= e->seq_rows,
+                "svc_op_dit_panel: M = n_seq * Lout rows, row_off + Lout <= seq_rows");
+    SVC_REQUIRE(e->x, "svc_op_dit_panel: x is null");
+    SVC_REQUIRE(!e->do_post || (e->wo && e->w1 && e->w3 && e->w2 && e->ao && e->g_ffn), "svc_op_dit_panel: do_post needs wo, w1, w3, w2, ao and g_ffn");
+    SVC_REQUIRE(e->do_post || !e->c16, "svc_op_dit_panel: c16 is an output of do_post");
+    SVC_REQUIRE(!e->do_skip || (e->wskip && e->skip_in), "svc_op_dit_panel: do_skip needs wskip and skip_in");
+    SVC_REQUIRE(!e->do_qkv || (e->wqkv && e->g_attn && e->rope && e->qk && e->vt), "svc_op_dit_panel: do_qkv needs wqkv, g_attn, rope, qk and vt");
+    if (e->do_qkv) {
+        const long reach = round_up(e->row_off + e->Lout, 32);      // vt_pos permutes inside groups of 32 (mode 2: 16) positions
+        SVC_REQUIRE(e->vt_mode >= 0 && e->vt_mode <= 2 && e->vt_ld >= reach && e->vt_ld % 4 == 0 && e->vt_seq_stride >= (long)D * e->vt_ld &&
+                    e->vt_seq_stride % 4 == 0, "svc_op_dit_panel: vt_mode 0 .. 2, vt_ld covers the positions rounded up to 32, vt_seq_stride >= D vt_ld");
+    }
+    SVC_REQUIRE(!e->do_final || e->g_fin, "svc_op_dit_panel: do_final needs g_fin");
+    SVC_REQUIRE(!e->do_final || e->seam == PANEL_SEAM_HEAD || e->n16, "svc_op_dit_panel: do_final needs n16");
+    SVC_REQUIRE(e->seam != PANEL_SEAM_MERGE || (e->w_merge && e->C >= 1 && e->C <= PANEL_MERGE_K && e->ldw >= e->C),
+                "svc_op_dit_panel: the merge seam needs w_merge [D][ldw] with 1 <= C <= 128 and ldw >= C");
+    SVC_REQUIRE(e->seam != PANEL_SEAM_HEAD || (e->head_wa && e->head_w2), "svc_op_dit_panel: the head seam needs head_wa and head_w2");
+
+    const bool merge = e->seam == PANEL_SEAM_MERGE, head = e->seam == PANEL_SEAM_HEAD;
+    const long slot_halfs = (long)(D / 16) * 512;
+    const long merge_halfs = merge ? fused_seam_slots(D, PANEL_SEAM_MERGE, e->C) * slot_halfs : 0;
+    const long body_halfs = fused_stream_halfs(D, I, e->do_post != 0, e->do_skip != 0, e->do_qkv != 0);
+
+    PanelParams p;
+    memset(&p, 0, sizeof(p));
+    p.M = e->M; p.Lout = e->Lout; p.seq_rows = e->seq_rows; p.row_off = e->row_off;
+    p.eps = e->eps; p.add_one = e->add_one; p.I = I;
+    p.do_post = e->do_post; p.do_skip = e->do_skip; p.do_qkv = e->do_qkv; p.do_final = e->do_final; p.seam = e->seam;
+    p.ao = reinterpret_cast<const half_t*>(e->ao); p.x = e->x;
+    p.gate_a = e->gate_a; p.gate_f = e->gate_f; p.g_ffn = e->g_ffn; p.w_f = e->w_f; p.b_f = e->b_f;
+    p.c16 = reinterpret_cast<half_t*>(e->c16);
+    p.skip_in = reinterpret_cast<const half_t*>(e->skip_in); p.bskip = e->bskip;
+    p.g_attn = e->g_attn; p.w_a = e->w_a; p.b_a = e->b_a; p.rope = e->rope; p.q_scale = e->q_scale;
+    p.qk = reinterpret_cast<half_t*>(e->qk); p.vt = reinterpret_cast<half_t*>(e->vt);
+    p.vt_seq_stride = e->vt_seq_stride; p.vt_ld = e->vt_ld; p.vt_mode = e->vt_mode;
+    p.g_fin = e->g_fin; p.w_fin = e->w_fin; p.b_fin = e->b_fin; p.n16 = reinterpret_cast<half_t*>(e->n16);
+    p.x16 = reinterpret_cast<const half_t*>(e->x16); p.st_term = e->st_term; p.tok_time = e->tok_time; p.tok_style = e->tok_style;
+    p.zero_row = e->st_term;      // stands in until the checks have passed: they ask only that the row is there
+    p.npre = e->npre; p.time_first = e->time_first; p.T = e->T;
+    p.head_b0 = e->head_b0; p.head_b2 = e->head_b2; p.v32 = e->v32; p.ldv = e->ldv; p.head_C = e->head_C;
+    p.n_slots = (int)((merge_halfs + body_halfs) / slot_halfs + (head ? fused_seam_slots(D, PANEL_SEAM_HEAD, e->head_C) : 0));
+    if (fused_panel_check(p, D, e->tm)) return 1;      // before anything is packed: head_C sizes the head's part of the stream
+
+    Scratch s;
+    float* zero_row = s.ar.alloc_n<float>(D, st);      // the arena hands out zeroed memory
+    if (!zero_row) return 1;
+    p.zero_row = zero_row;
+    const long total = (long)p.n_slots * slot_halfs;
+    half_t* ws = s.ar.alloc_n<half_t>((size_t)total, st);
+    if (!ws) return 1;
+    long off = 0;
+    if (merge) {
+        if (fused_pack_merge(ws, D, e->w_merge, e->ldw, e->C, st) != merge_halfs) { set_error("fused stream packing failed"); return 1; }
+        off += merge_halfs;
+    }
+    if (body_halfs) {
+        const bool post = e->do_post != 0;
+        if (fused_pack_stream(ws + off, D, I, post ? e->wo : nullptr, post ? e->w1 : nullptr, post ? e->w3 : nullptr, post ? e->w2 : nullptr,
+                              e->do_skip ? e->wskip : nullptr, e->do_qkv ? e->wqkv : nullptr, st) != body_halfs) {
+            set_error("fused stream packing failed");
+            return 1;
+        }
+        off += body_halfs;
+    }
+    if (head) {
+        if (fused_pack_head(ws + off, D, e->head_wa, e->head_w2, e->head_C, st) != total - off) { set_error("fused stream packing failed"); return 1; }
+    }
+    p.wstream = ws;
+    if (fused_panel_launch(p, D, e->gated != 0, st, e->tm)) return 1;
+    SVC_CHECK_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
 // chunk2[i] = float(double(chunk2[i]) * fade_in[i] + double(chunk1_tail[i]) * fade_out[i]), i < n: the reference's
 // numpy crossfade (inference.py:343-350; float32 * float64 -> float64, stored back to float32), bit for bit
 // (separately rounded products and sum, no fma contraction).

@@ -303,7 +303,10 @@ long fused_pack_stream(half_t* dst, int D, int I, const float* wo, const float* 
 // seam extensions: the x block (columns [0, C) of w_merge [D][ldw]) as PANEL_MERGE_K / 32 slots; the mlp head (wa [D][D], w2 [C][D])
 long fused_pack_merge(half_t* dst, int D, const float* w_merge, int ldw, int C, hipStream_t st);
 long fused_pack_head(half_t* dst, int D, const float* wa, const float* w2, int C, hipStream_t st);
-int fused_panel_launch(const PanelParams& p, int D, bool gated, hipStream_t st);
+// what fused_panel_launch refuses, without launching (the op-level entry point asks before it packs a stream)
+int fused_panel_check(const PanelParams& p, int D, int tm);
+// tm: 16-row tiles per wave, 1 | 2; 0 = the launcher's choice by D (or SVC_FUSED_TM)
+int fused_panel_launch(const PanelParams& p, int D, bool gated, hipStream_t st, int tm = 0);
 
 // ------------------------------------------------------------------ attention (attention.hip)
 struct AttnParams {

@@ -808,22 +808,11 @@ long fused_pack_head(half_t* dst, int D, const float* wa, const float* w2, int C
     return hipGetLastError() == hipSuccess ? n1 + n2 : 0;
 }
 
-int fused_panel_launch(const PanelParams& p, int D, bool gated, hipStream_t st) {
+int fused_panel_check(const PanelParams& p, int D, int tm) {
     SVC_REQUIRE(D == 384 || D == 512, "fused panel kernel: D must be 384 or 512");
+    SVC_REQUIRE(tm >= 0 && tm <= 2, "fused panel kernel: tm is 0 (the launcher's choice), 1 or 2");
     SVC_REQUIRE(p.M > 0 && p.Lout > 0 && p.I % 32 == 0, "fused panel kernel: shape");
     SVC_REQUIRE(!p.do_qkv || (p.M % 4 == 0 && p.Lout % 4 == 0 && p.row_off % 4 == 0), "fused panel kernel: v^T stores need 4-row groups");
-    DeviceState* ds = device_state();
-    if (!ds) return 1;
-    if (!ds->fused_attr.load(std::memory_order_acquire)) {
-#define SVC_PANEL_ATTR1(DD, GG, TT, SS) SVC_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(dit_panel_kernel<DD, GG, TT, SS>), hipFuncAttributeMaxDynamicSharedMemorySize, PG<DD>::LDS))
-        // the merge seam runs no gated phase: one instantiation serves both
-#define SVC_PANEL_ATTR(DD, GG, TT) SVC_PANEL_ATTR1(DD, GG, TT, PANEL_SEAM_NONE); SVC_PANEL_ATTR1(DD, GG, TT, PANEL_SEAM_HEAD); if (!GG) SVC_PANEL_ATTR1(DD, false, TT, PANEL_SEAM_MERGE)
-        SVC_PANEL_ATTR(384, false, 1); SVC_PANEL_ATTR(384, true, 1); SVC_PANEL_ATTR(512, false, 1); SVC_PANEL_ATTR(512, true, 1);
-        SVC_PANEL_ATTR(384, false, 2); SVC_PANEL_ATTR(384, true, 2); SVC_PANEL_ATTR(512, false, 2); SVC_PANEL_ATTR(512, true, 2);
-#undef SVC_PANEL_ATTR
-#undef SVC_PANEL_ATTR1
-        ds->fused_attr.store(true, std::memory_order_release);
-    }
     if (p.seam == PANEL_SEAM_MERGE) {
         SVC_REQUIRE(!p.do_post && !p.do_skip && !p.do_final && p.do_qkv && p.row_off == 0, "fused panel kernel: the merge seam belongs to the first panel");
         SVC_REQUIRE(p.x16 && p.st_term && p.zero_row && p.T >= 1 && p.npre >= 0 && p.npre + p.T <= p.seq_rows, "fused panel kernel: merge seam operands");
@@ -838,14 +827,34 @@ int fused_panel_launch(const PanelParams& p, int D, bool gated, hipStream_t st) 
     const long want = (p.do_post ? slots_post(D, p.I) : 0) + (p.do_skip ? slots_skip(D) : 0) + (p.do_qkv ? slots_qkv(D) : 0) +
                       fused_seam_slots(D, p.seam, p.head_C);
     SVC_REQUIRE(want == p.n_slots, "fused panel kernel: slot count does not match the enabled phases");
+    // the prologue prefetches slot min(s, n_slots - 1): a launch without a streamed phase would read in front of the stream
+    SVC_REQUIRE(p.n_slots >= 1, "fused panel kernel: no streamed phase enabled");
+    return 0;
+}
+
+int fused_panel_launch(const PanelParams& p, int D, bool gated, hipStream_t st, int tm_force) {
+    if (fused_panel_check(p, D, tm_force)) return 1;
+    DeviceState* ds = device_state();
+    if (!ds) return 1;
+    if (!ds->fused_attr.load(std::memory_order_acquire)) {
+#define SVC_PANEL_ATTR1(DD, GG, TT, SS) SVC_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(dit_panel_kernel<DD, GG, TT, SS>), hipFuncAttributeMaxDynamicSharedMemorySize, PG<DD>::LDS))
+        // the merge seam runs no gated phase: one instantiation serves both
+#define SVC_PANEL_ATTR(DD, GG, TT) SVC_PANEL_ATTR1(DD, GG, TT, PANEL_SEAM_NONE); SVC_PANEL_ATTR1(DD, GG, TT, PANEL_SEAM_HEAD); if (!GG) SVC_PANEL_ATTR1(DD, false, TT, PANEL_SEAM_MERGE)
+        SVC_PANEL_ATTR(384, false, 1); SVC_PANEL_ATTR(384, true, 1); SVC_PANEL_ATTR(512, false, 1); SVC_PANEL_ATTR(512, true, 1);
+        SVC_PANEL_ATTR(384, false, 2); SVC_PANEL_ATTR(384, true, 2); SVC_PANEL_ATTR(512, false, 2); SVC_PANEL_ATTR(512, true, 2);
+#undef SVC_PANEL_ATTR
+#undef SVC_PANEL_ATTR1
+        ds->fused_attr.store(true, std::memory_order_release);
+    }
     const int grid = cdiv(p.M, 128);
     const bool prof = prof_enabled();
     if (prof) prof_begin(PROF_FUSED, st);
     // waves per SIMD, measured on MI355X: D = 384 is fastest with one wave per SIMD owning 32 rows
     // (811 vs 806 TFLOP/s), D = 512 with two waves per SIMD owning 16 rows each (845 vs 751: with 32 rows its 256
-    // residual accumulators leave no room and the side accumulators need the inline-asm path).  SVC_FUSED_TM overrides.
+    // residual accumulators leave no room and the side accumulators need the inline-asm path).  SVC_FUSED_TM overrides;
+    // tm_force (the op-level entry point) overrides both.
     static const int tm_env = [] { const char* e = getenv("SVC_FUSED_TM"); return e ? atoi(e) : 0; }();
-    const int tm = (tm_env == 1 || tm_env == 2) ? tm_env : (D == 384 ? 2 : 1);
+    const int tm = tm_force ? tm_force : (tm_env == 1 || tm_env == 2) ? tm_env : (D == 384 ? 2 : 1);
 #define SVC_PANEL_LAUNCH1(DD, GG, TT, SS) hipLaunchKernelGGL((dit_panel_kernel<DD, GG, TT, SS>), dim3(grid), dim3(128 / (16 * TT) * 64), PG<DD>::LDS, st, p)
 #define SVC_PANEL_LAUNCH(DD, GG, TT)                                              \
     do {                                                                          \

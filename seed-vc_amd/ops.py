@@ -128,6 +128,64 @@ def conv1d_last_took():
     return _took(_lib.lib().svc_op_conv1d_last_took())
 
 
+_PANEL_F32 = ("wo", "w1", "w3", "w2", "wskip", "wqkv", "w_merge", "head_wa", "head_w2", "gate_a", "gate_f", "g_ffn", "w_f", "b_f", "g_attn",
+              "w_a", "b_a", "bskip", "g_fin", "w_fin", "b_fin", "head_b0", "head_b2", "tok_time", "tok_style", "st_term", "rope")
+_PANEL_F16 = ("ao", "skip_in", "x16")
+_PANEL_INT = ("D", "I", "gated", "tm", "M", "Lout", "seq_rows", "row_off", "n_seq", "add_one", "do_post", "do_skip", "do_qkv", "do_final",
+              "seam", "ldw", "C", "vt_mode", "ldv", "head_C", "npre", "time_first", "T")
+
+
+def dit_panel(a, device="cuda:0", fill16=0x6A5A, fill32=-777.25):
+    """Test aid over svc_op_dit_panel (include/seedvc_hip.h): ONE launch of the fused DiT row-panel kernel on unpacked weights.
+    `a` maps the fields of svc_dit_panel_t to ints / floats and CPU or device tensors (fp32 weights, vectors, x, st_term and
+    rope; fp16 ao, skip_in, x16; None = absent), plus want_c16.  Every activation buffer has n_seq * seq_rows rows.
+    Returns {name: device tensor} of every output buffer handed to the kernel, whether the launch writes it or not: x (a copy
+    of a["x"], run in place), c16 (with want_c16), n16 (with do_final, the head seam included), qk and vt (n_seq, D, vt_ld) (with
+    do_qkv), v32 (rows, ldv) (with the head seam).  Where the kernel does not write, fp16 buffers hold the bit pattern fill16
+    and v32 holds fill32."""
+    import ctypes as C
+    dev = torch.device(device)
+    D, n_rows = int(a["D"]), int(a["n_seq"]) * int(a["seq_rows"])
+    with torch.cuda.device(dev):
+        e = _lib.DitPanel()
+        keep = []
+        for name in _PANEL_INT:
+            setattr(e, name, int(a.get(name) or 0))
+        e.eps, e.q_scale = float(a["eps"]), float(a.get("q_scale") or 0.0)
+        for names, dt in ((_PANEL_F32, torch.float32), (_PANEL_F16, torch.float16)):
+            for name in names:
+                t = a.get(name)
+                if t is not None:
+                    assert t.dtype == dt, name
+                    keep.append(t.to(dev).contiguous())
+                    setattr(e, name, keep[-1].data_ptr())
+        for name, rows in (("ao", n_rows), ("skip_in", n_rows), ("st_term", n_rows)):
+            assert a.get(name) is None or tuple(a[name].shape) == (rows, D), name
+        assert a.get("x16") is None or tuple(a["x16"].shape) == (n_rows, 128)
+        assert a.get("rope") is None or (a["rope"].shape[0] >= e.row_off + e.Lout and tuple(a["rope"].shape[1:]) == (32, 2))
+        assert a.get("tok_style") is None or tuple(a["tok_style"].shape) == (e.n_seq, D)
+        assert tuple(a["x"].shape) == (n_rows, D) and a["x"].dtype == torch.float32
+        out = {"x": a["x"].to(dev).contiguous().clone()}
+        e.x = out["x"].data_ptr()
+        f16 = lambda *shape: torch.full(shape, fill16, dtype=torch.int16, device=dev).view(torch.float16)     # noqa: E731
+        if a.get("want_c16"):
+            out["c16"] = f16(n_rows, D)
+            e.c16 = out["c16"].data_ptr()
+        if e.do_final:
+            out["n16"] = f16(n_rows, D)
+            e.n16 = out["n16"].data_ptr()
+        if e.do_qkv:
+            vt_ld = int(a["vt_ld"])
+            out["qk"] = f16(n_rows, 2 * D)
+            out["vt"] = f16(e.n_seq, D, vt_ld)
+            e.qk, e.vt, e.vt_ld, e.vt_seq_stride = out["qk"].data_ptr(), out["vt"].data_ptr(), vt_ld, D * vt_ld
+        if e.seam == 2:
+            out["v32"] = torch.full((n_rows, max(e.ldv, 1)), fill32, dtype=torch.float32, device=dev)
+            e.v32 = out["v32"].data_ptr()
+        _lib.check(_lib.lib().svc_op_dit_panel(C.byref(e), _lib.stream_ptr()))
+    return out
+
+
 def conv_transpose1d_cl(x, w, bias, stride, dtype="f32"):
     """x (B, L, Cin), w (Cin, Cout, k = 2*stride) -> (B, L*stride, Cout); padding = stride // 2."""
     B, L, Cin = x.shape
