@@ -930,6 +930,28 @@ int svc_op_conv_transpose1d(const float* x, const float* w, const float* bias, f
 /* softmax(q k^T / 8 + key-padding mask) v ; q,k,v,out [N][T][H][64] fp32 (computed in fp16 MFMA). */
 int svc_op_attention(const float* q, const float* k, const float* v, float* out, int N, int T, int H,
                      const int64_t* kv_lens_host, void* stream);
+/* Test aid (tests/test_gpu_attention.py; no model uses it): ONE attention launch on buffers that are ALREADY in the kernels' layout.
+ * Nothing is packed, permuted or padded, so the caller owns every byte the kernels read.  Device pointers, fp16:
+ *   q, k [n_seq * seq_rows][ld_qk] with head h at column 64 h (separate buffers, or two column blocks of one), q pre-scaled by
+ *   log2(e) / 8; vt [n_seq][H * 64][vt_ld] with key p of a sequence at column vt_pos(p, vt_perm) (0 natural, 1 and 2 the orders of
+ *   the 16x16x32 and the 32x32x16 kernels, which vt_perm thereby selects); out (fp16) or out32 (fp32) [n_seq * seq_rows][ld_out],
+ *   exactly one of them.  Queries [q_start, Tq) of every sequence are computed, over keys [0, kv_len[seq]) (HOST array) or
+ *   [0, kv_len_const) when kv_len is NULL; rows outside are not written; kv_len 0 gives zero rows.  qt_form: 0 = by the grid size,
+ *   1 = 64-query workgroups, 2 = 128-query workgroups.  K rows at and past kv_len may hold anything; V^T columns
+ *   [kv_len, round_up(kv_len, 64)) must hold finite values (they meet P = 0 in the MFMA); nothing past that is read.
+ *   Refused, before anything is allocated or launched: a NULL q, k or vt; both or neither of out and out32; vt_perm or qt_form
+ *   outside 0 .. 2; n_seq or H < 1; Tq < 1 or > seq_rows; q_start < 0 or >= Tq; a kv_len < 0, > seq_rows or with
+ *   round_up(kv_len, 64) > vt_ld; vt_seq_stride < H * 64 * vt_ld; ld_qk or ld_out < H * 64; vt_ld not a multiple of 64, ld_qk or
+ *   vt_seq_stride not of 8, ld_out not of 4; q, k, vt, out32 not 16-byte or out not 8-byte aligned. */
+typedef struct {
+    const uint16_t* q; const uint16_t* k; const uint16_t* vt;
+    uint16_t* out; float* out32;
+    int64_t ld_qk, vt_seq_stride, vt_ld, ld_out;
+    int32_t n_seq, H, seq_rows, Tq, q_start;
+    const int64_t* kv_len;
+    int32_t kv_len_const, vt_perm, qt_form;
+} svc_attention_t;
+int svc_op_attention_ex(const svc_attention_t* args, void* stream);
 /* y = rmsnorm(x) * gamma * (add_one + w) + b ; x [rows][D]. */
 int svc_op_rmsnorm(const float* x, const float* gamma, const float* w, const float* b, int add_one, float* y,
                    int rows, int D, void* stream);

@@ -42,7 +42,7 @@ EXPORTS = [
     "svc_astral_set_timing", "svc_astral_last_timing", "svc_astral_ssl", "svc_astral_convnext", "svc_astral_logits", "svc_astral_tokens",
     "svc_op_bsq_index", "svc_tokens_reduce",
     "svc_prof_enable", "svc_prof_collect",
-    "svc_op_linear", "svc_op_conv1d", "svc_op_conv1d_ex", "svc_op_conv1d_last_took", "svc_op_dit_panel", "svc_op_conv_transpose1d", "svc_op_attention", "svc_op_rmsnorm",
+    "svc_op_linear", "svc_op_conv1d", "svc_op_conv1d_ex", "svc_op_conv1d_last_took", "svc_op_dit_panel", "svc_op_conv_transpose1d", "svc_op_attention", "svc_op_attention_ex", "svc_op_rmsnorm",
     "svc_op_layernorm", "svc_op_layernorm_gelu",
 ]
 
@@ -154,6 +154,15 @@ class DitPanel(C.Structure):
                 ("npre", C.c_int32), ("time_first", C.c_int32), ("T", C.c_int32)]
 
 
+class Attention(C.Structure):
+    """svc_attention_t: the arguments of svc_op_attention_ex (test aid)."""
+    _fields_ = [(n, C.c_void_p) for n in ("q", "k", "vt", "out", "out32")] + \
+               [(n, C.c_int64) for n in ("ld_qk", "vt_seq_stride", "vt_ld", "ld_out")] + \
+               [(n, C.c_int32) for n in ("n_seq", "H", "seq_rows", "Tq", "q_start")] + \
+               [("kv_len", C.POINTER(C.c_int64))] + \
+               [(n, C.c_int32) for n in ("kv_len_const", "vt_perm", "qt_form")]
+
+
 _lib = None
 
 
@@ -184,6 +193,7 @@ def lib():
                                               C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         l.svc_op_conv1d_ex.argtypes = [C.POINTER(Conv1dEx), C.c_void_p]
         l.svc_op_dit_panel.argtypes = [C.POINTER(DitPanel), C.c_void_p]
+        l.svc_op_attention_ex.argtypes = [C.POINTER(Attention), C.c_void_p]
         # seeded noise: 64-bit seeds by value and as HOST arrays
         l.svc_cfm_sample_seeded.argtypes = [C.c_void_p, C.POINTER(CfmArgs), C.POINTER(C.c_uint64), C.c_void_p]
         l.svc_cfm_noise_draws.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]

@@ -8,8 +8,9 @@
 // Block = 4 waves = 64 QT queries of one (sequence, head); each wave owns QT 16-wide MFMA column tiles of queries
 // (QT = 2 for full grids; QT = 1 doubles the workgroup count of small launches -- a single utterance gives only
 // 2 x H x 7 blocks of 128 queries for 256 CUs and is bound by the serial chain of one workgroup over the key tiles).
-// Every per-query quantity, including the deferred-rescale decision, depends only on the query's own 16-wide tile,
-// so both forms are bit-identical.  Scores are computed transposed, S^T = K Q^T (keys on the accumulator rows),
+// Every per-query quantity depends only on the query's own scores: the 16-wide tile decides together only WHETHER the
+// baseline-move code runs, and a query that did not ask for it moves by delta = 0.  So both forms are bit-identical, and so are
+// a q_start window and the full launch (tests/test_gpu_attention.py).  Scores are computed transposed, S^T = K Q^T (keys on the accumulator rows),
 // which makes the softmax row statistics lane-local up to two cross-lane maxima and lets the
 // accumulator registers feed P^T straight into O^T += V^T P^T as the B operand (no LDS round trip).
 // K and V^T tiles (64 keys) stream through a 3-stage LDS-DMA ring (counted vmcnt + one raw s_barrier per tile, as in
@@ -27,6 +28,16 @@ constexpr int KT = 64;        // keys per tile
 constexpr int ROWB = 128;
 
 __device__ __forceinline__ int lds_off(int row, int c16) { return row * ROWB + ((c16 ^ ((row >> 1) & 7)) << 4); }
+
+// The fp16 output is the fp32 output rounded to nearest: fp16(acc * inv) with the product formed in fp32 FIRST.  Left to itself
+// hipcc folds some of a lane's products into v_fma_mixlo_f16 (one rounding) and converts the others from fp32 (two roundings),
+// so which elements round how depended on instruction selection, and the fp16 and fp32 instantiations disagreed in about one
+// word in 30 000.  The empty asm makes the fp32 product a value of its own.
+__device__ __forceinline__ half_t out16(float acc, float inv) {
+    float r = acc * inv;
+    asm volatile("" : "+v"(r));
+    return (half_t)r;
+}
 
 template <int QT, bool VPERM, bool OUT32 = false>      // OUT32: fp32 output rows (AttnParams.out32) instead of fp16
 __global__ __launch_bounds__(256) void attn_kernel(const AttnParams p) {
@@ -155,8 +166,8 @@ __global__ __launch_bounds__(256) void attn_kernel(const AttnParams p) {
                 }
         }
         // ---- baseline move (always on the first tile; afterwards only when some score of the 16-query tile overshoots the
-        // baseline by more than THR -- decided per tile, so a query's arithmetic does not depend on which tiles share
-        // its wave).  The decision only needs each lane's own maximum; the row maxima (two cross-lane exchanges) are
+        // baseline by more than THR: the tile decides whether the code runs, each query whether ITS baseline moves, so a
+        // query's arithmetic depends neither on the tiles that share its wave nor on the queries that share its tile).  The decision only needs each lane's own maximum; the row maxima (two cross-lane exchanges) are
         // taken on the rare path that moves the baseline.
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt) {
@@ -167,7 +178,9 @@ __global__ __launch_bounds__(256) void attn_kernel(const AttnParams p) {
             if (__builtin_expect(kt == 0 || __any(a > THR), 0)) {
                 a = fmaxf(a, __shfl_xor(a, 16));
                 a = fmaxf(a, __shfl_xor(a, 32));
-                const float delta = kt == 0 ? a : fmaxf(a, 0.f);
+                // per QUERY: one whose own scores stay within THR keeps its baseline (delta = 0, alpha = 1: no bit moves), so
+                // its arithmetic does not depend on which queries share its 16-wide tile (q_start windows, junk pad rows)
+                const float delta = kt == 0 ? a : (a > THR ? a : 0.f);
                 const float alpha = __builtin_amdgcn_exp2f(-delta);
                 m_run[qt] += delta;
                 acc_l[qt] *= alpha;
@@ -242,8 +255,8 @@ __global__ __launch_bounds__(256) void attn_kernel(const AttnParams p) {
             half_t* dst = p.out + (row_base + qr) * p.ld_out + h * 64 + fq * 4;
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt) {
-                half4 o = {(half_t)(acc_o[dt][qt][0] * inv), (half_t)(acc_o[dt][qt][1] * inv),
-                           (half_t)(acc_o[dt][qt][2] * inv), (half_t)(acc_o[dt][qt][3] * inv)};
+                half4 o = {out16(acc_o[dt][qt][0], inv), out16(acc_o[dt][qt][1], inv),
+                           out16(acc_o[dt][qt][2], inv), out16(acc_o[dt][qt][3], inv)};
                 *reinterpret_cast<half4*>(dst + dt * 16) = o;
             }
         }
@@ -414,7 +427,7 @@ __global__ __launch_bounds__(64 * NW) void attn32_kernel(const AttnParams p) {
                     a = fmaxf(a, fmaxf(fmaxf(acc_s[b][i], acc_s[b][i + 1]), fmaxf(acc_s[b][i + 2], acc_s[b][i + 3])));
             if (__builtin_expect(kt == 0 || __any(a > THR), 0)) {
                 a = fmaxf(a, __shfl_xor(a, 32));             // the query's other 32 keys of this tile
-                const float delta = kt == 0 ? a : fmaxf(a, 0.f);
+                const float delta = kt == 0 ? a : (a > THR ? a : 0.f);       // per query, as in attn_kernel
                 const float alpha = __builtin_amdgcn_exp2f(-delta);
                 m_run += delta;
                 acc_l[0] *= alpha;
@@ -480,8 +493,8 @@ __global__ __launch_bounds__(64 * NW) void attn32_kernel(const AttnParams p) {
         for (int hb = 0; hb < 2; ++hb)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                half4 o = {(half_t)(acc_o[hb][4 * g] * inv), (half_t)(acc_o[hb][4 * g + 1] * inv),
-                           (half_t)(acc_o[hb][4 * g + 2] * inv), (half_t)(acc_o[hb][4 * g + 3] * inv)};
+                half4 o = {out16(acc_o[hb][4 * g], inv), out16(acc_o[hb][4 * g + 1], inv),
+                           out16(acc_o[hb][4 * g + 2], inv), out16(acc_o[hb][4 * g + 3], inv)};
                 *reinterpret_cast<half4*>(dst + hb * 32 + g * 8) = o;
             }
     }
@@ -519,6 +532,11 @@ int attention_permute_vt(half_t* vt, long rows, long vt_ld, int mode, hipStream_
 int attention_launch(const AttnParams& p, hipStream_t st) {
     SVC_REQUIRE(p.n_seq > 0 && p.H > 0 && p.Tq > 0 && p.q_start >= 0 && p.q_start < p.Tq, "attention shape");
     SVC_REQUIRE(p.vt_ld % 64 == 0 && p.ld_qk % 8 == 0 && p.ld_out % 4 == 0, "attention alignment");
+    SVC_REQUIRE(p.Tq <= p.seq_rows, "attention: Tq <= seq_rows");
+    SVC_REQUIRE(p.vt_perm >= 0 && p.vt_perm <= 2 && p.qt_form >= 0 && p.qt_form <= 2, "attention: vt_perm and qt_form are 0 .. 2");
+    SVC_REQUIRE((p.out != nullptr) != (p.out32 != nullptr), "attention: exactly one of out and out32");
+    SVC_REQUIRE(p.kv_len || (p.kv_len_const >= 0 && p.kv_len_const <= p.seq_rows && round_up(p.kv_len_const, 64) <= p.vt_ld),
+                "attention: kv_len_const within seq_rows, and within vt_ld when rounded up to a key tile");
     const int g128 = cdiv(p.Tq - p.q_start, 128) * p.H * p.n_seq;
     const bool prof = prof_enabled();
     if (prof) prof_begin(PROF_ATTN, st);

@@ -138,7 +138,7 @@ int svc_op_gemm_bench(int M, int N, int K, int dtype, int epi, int iters, int de
     if (epi == KG_EPI_STORE) { p.c32 = c32; p.ldc32 = N; p.res = c32; p.ldres = N; }
     else if (epi == KG_EPI_SWIGLU) { p.c16 = c16; p.ldc16 = N / 2; }
     else if (epi == KG_EPI_QKV_ROPE) { p.c16 = c16; p.ldc16 = 2 * (N / 3); p.rope = rope; p.rope_D = N / 3; p.q_scale = 1.f;
-                                       p.vt = vt; p.vt_seq_stride = (long)(N / 3) * 896; p.vt_ld = 896; }
+                                       p.vt = vt; p.vt_seq_stride = (long)(N / 3) * 896; p.vt_ld = 896; p.vt_mode = 1; }
     else { p.c16 = c16; p.ldc16 = N / 2; }
     hipEvent_t e0, e1;
     SVC_CHECK_HIP(hipEventCreate(&e0));
@@ -207,7 +207,7 @@ int svc_op_gemm_forms_diff(int M, int N, int K, int epi, int debug_a, int debug_
         p.w = wp; p.ldw = Kp; p.vec_ok = 1; p.debug = v ? debug_b : debug_a; p.bias = bias;
         if (epi == KG_EPI_STORE) { p.c32 = c32[v]; p.ldc32 = N; p.res = res; p.ldres = N; p.c16 = c16[v]; p.ldc16 = N; }
         else if (epi == KG_EPI_QKV_ROPE) { p.c16 = c16[v]; p.ldc16 = 2 * (N / 3); p.rope = rope; p.rope_D = N / 3; p.q_scale = 0.125f;
-                                           p.vt = vt[v]; p.vt_seq_stride = (long)(N / 3) * 896; p.vt_ld = 896; }
+                                           p.vt = vt[v]; p.vt_seq_stride = (long)(N / 3) * 896; p.vt_ld = 896; p.vt_mode = 1; }
         else { p.c16 = c16[v]; p.ldc16 = N / 2; }
         if (kgemm_launch(p, 0, epi, st)) return 1;
     }
@@ -273,6 +273,52 @@ int svc_op_attention(const float* q, const float* k, const float* v, float* out,
                 for (int d = 0; d < D; ++d) f[((size_t)n * T + t) * D + d] = (float)h[((size_t)n * Tr + t) * D + d];
         SVC_CHECK_HIP(hipMemcpy(out, f.data(), f.size() * 4, hipMemcpyHostToDevice));
     }
+    return 0;
+}
+
+// One attention_launch on buffers already in the kernels' layout (tests/test_gpu_attention.py): no packing, so the test owns every
+// byte the kernels read.  Everything is checked before the first allocation; the lengths travel as a host array.
+int svc_op_attention_ex(const svc_attention_t* e, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    SVC_REQUIRE(e, "svc_op_attention_ex: null argument");
+    SVC_REQUIRE(e->q && e->k && e->vt, "svc_op_attention_ex: q, k and vt are required");
+    SVC_REQUIRE((e->out != nullptr) != (e->out32 != nullptr), "svc_op_attention_ex: exactly one of out and out32");
+    SVC_REQUIRE(e->vt_perm >= 0 && e->vt_perm <= 2, "svc_op_attention_ex: vt_perm is 0 .. 2");
+    SVC_REQUIRE(e->qt_form >= 0 && e->qt_form <= 2, "svc_op_attention_ex: qt_form is 0 .. 2");
+    SVC_REQUIRE(e->n_seq >= 1 && e->H >= 1 && e->seq_rows >= 1, "svc_op_attention_ex: n_seq, H and seq_rows are positive");
+    SVC_REQUIRE(e->Tq >= 1 && e->Tq <= e->seq_rows, "svc_op_attention_ex: 1 <= Tq <= seq_rows");
+    SVC_REQUIRE(e->q_start >= 0 && e->q_start < e->Tq, "svc_op_attention_ex: 0 <= q_start < Tq");
+    const long D = (long)e->H * 64;
+    SVC_REQUIRE(e->vt_ld > 0 && e->vt_ld % 64 == 0 && e->ld_qk % 8 == 0 && e->ld_out % 4 == 0 && e->vt_seq_stride % 8 == 0,
+                "svc_op_attention_ex: alignment: vt_ld a multiple of 64, ld_qk and vt_seq_stride of 8, ld_out of 4");
+    SVC_REQUIRE(e->ld_qk >= D && e->ld_out >= D, "svc_op_attention_ex: ld_qk and ld_out cover H * 64 columns");
+    SVC_REQUIRE(e->vt_seq_stride >= D * e->vt_ld, "svc_op_attention_ex: vt_seq_stride >= H * 64 * vt_ld");
+    SVC_REQUIRE((uintptr_t)e->q % 16 == 0 && (uintptr_t)e->k % 16 == 0 && (uintptr_t)e->vt % 16 == 0 && (uintptr_t)e->out % 8 == 0 &&
+                (uintptr_t)e->out32 % 16 == 0, "svc_op_attention_ex: alignment: q, k, vt and out32 to 16 bytes, out to 8");
+    for (int n = 0; n < (e->kv_len ? e->n_seq : 1); ++n) {
+        const long len = e->kv_len ? (long)e->kv_len[n] : (long)e->kv_len_const;
+        SVC_REQUIRE(len >= 0 && len <= e->seq_rows && round_up(len, 64) <= e->vt_ld,
+                    "svc_op_attention_ex: kv_len within [0, seq_rows], and within vt_ld when rounded up to a key tile of 64");
+    }
+    Scratch s;
+    AttnParams a;
+    memset(&a, 0, sizeof(a));
+    if (e->kv_len) {
+        int* d_len = s.ar.alloc_n<int>(e->n_seq, st);
+        if (!d_len) return 1;
+        std::vector<int> lens(e->n_seq);
+        for (int n = 0; n < e->n_seq; ++n) lens[n] = (int)e->kv_len[n];
+        SVC_CHECK_HIP(hipMemcpyAsync(d_len, lens.data(), (size_t)e->n_seq * 4, hipMemcpyHostToDevice, st));
+        SVC_CHECK_HIP(hipStreamSynchronize(st));            // `lens` leaves scope below
+        a.kv_len = d_len;
+    }
+    a.q = (const half_t*)e->q; a.k = (const half_t*)e->k; a.ld_qk = e->ld_qk;
+    a.vt = (const half_t*)e->vt; a.vt_seq_stride = e->vt_seq_stride; a.vt_ld = e->vt_ld;
+    a.out = (half_t*)e->out; a.out32 = e->out32; a.ld_out = e->ld_out;
+    a.n_seq = e->n_seq; a.H = e->H; a.seq_rows = e->seq_rows; a.Tq = e->Tq; a.q_start = e->q_start;
+    a.kv_len_const = e->kv_len_const; a.vt_perm = e->vt_perm; a.qt_form = e->qt_form;
+    if (attention_launch(a, st)) return 1;
+    SVC_CHECK_HIP(hipStreamSynchronize(st));
     return 0;
 }
 

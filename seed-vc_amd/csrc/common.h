@@ -191,7 +191,7 @@ struct KGemmParams {
     int rope_D;                              // model dim D (q: [0,D), k: [D,2D), v: [2D,3D))
     float q_scale;
     half_t* vt; long vt_seq_stride; long vt_ld; // V^T buffer [seq][D][vt_ld]
-    int vt_mode;                                // column order the consumer wants (vt_pos); 0 is treated as 1
+    int vt_mode;                                // column order the consumer wants (vt_pos): 0 natural, 1, 2 (AttnParams.vt_perm)
 };
 
 int kgemm_launch(const KGemmParams& p, int dtype /*0=f16,1=f32*/, int epi, hipStream_t st);
@@ -309,6 +309,13 @@ int fused_panel_check(const PanelParams& p, int D, int tm);
 int fused_panel_launch(const PanelParams& p, int D, bool gated, hipStream_t st, int tm = 0);
 
 // ------------------------------------------------------------------ attention (attention.hip)
+// What the kernels read beyond the keys they attend (tests/test_gpu_attention.py poisons all of it): key tiles are 64 wide, so the
+// last tile of a sequence loads K rows and V^T columns [kv_len, round_up(kv_len, 64)) and masks them.  The mask is a select on the
+// scores, so those K rows may hold ANYTHING (NaN included; rows past seq_rows are not read, the load clamps to the last row).
+// The V^T columns there are multiplied by P = 0 in the PV MFMA and MUST HOLD FINITE VALUES (0 x NaN and 0 x Inf are NaN); hence
+// vt_ld >= round_up(kv_len, 64) for every sequence.  V^T columns past round_up(kv_len, 64), Q rows [Tq, seq_rows) and Q rows below
+// q_start are never looked at (Q rows [Tq, seq_rows) are loaded into lanes whose results are dropped).  Output rows outside
+// [q_start, Tq) of each sequence are not written.  kv_len = 0 writes zero rows.  Exactly one of out / out32 is set.
 struct AttnParams {
     const half_t* q; const half_t* k; long ld_qk;   // rows = seq * seq_rows + pos ; head h at column h*64
     const half_t* vt; long vt_seq_stride; long vt_ld;  // [seq][H*64][vt_ld]

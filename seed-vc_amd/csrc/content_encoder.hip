@@ -246,8 +246,9 @@ int EncoderStack::run(int G, int P, const int* lens, float* out, hipStream_t st)
         memset(&a, 0, sizeof(a));
         a.q = qkv16; a.k = qkv16 + D; a.ld_qk = 3 * D;
         a.vt = vt; a.vt_seq_stride = (long)D * vt_ld; a.vt_ld = vt_ld; a.vt_perm = vmode;
-        a.out = ao16; a.ld_out = D;
-        a.out32 = f16 ? nullptr : ao32;                      // precision 0: the fp32 out_proj reads the attention's fp32 rows
+        a.ld_out = D;                                        // one of the two: precision 0's fp32 out_proj reads the attention's fp32 rows
+        a.out = f16 ? ao16 : nullptr;
+        a.out32 = f16 ? nullptr : ao32;
         a.n_seq = G; a.H = H; a.seq_rows = P; a.Tq = P; a.kv_len = lens; a.kv_len_const = P;
         a.qt_form = qt_form;
         if (attention_launch(a, st)) return 1;

@@ -401,14 +401,14 @@ __global__ __launch_bounds__(NWV * 64, (NS * (BM + BN) * RB > 80 * 1024) ? 1 : 2
                     const float4v a4 = KG_ACC(mt, nt);
                     if (m + 4 <= p.M && (pos & 3) == 0 && pos + 4 <= p.Lout) {
                         const half4 h = {(half_t)a4[0], (half_t)a4[1], (half_t)a4[2], (half_t)a4[3]};
-                        *reinterpret_cast<half4*>(p.vt + (long)seq * p.vt_seq_stride + (long)d * p.vt_ld + vt_pos(pos, p.vt_mode ? p.vt_mode : 1)) = h;
+                        *reinterpret_cast<half4*>(p.vt + (long)seq * p.vt_seq_stride + (long)d * p.vt_ld + vt_pos(pos, p.vt_mode)) = h;
                     } else {
                         for (int j = 0; j < 4; ++j) {
                             const int mj = m + j;
                             if (mj >= p.M) break;
                             const int sj = mj / p.Lout;
                             const int pj = mj - sj * p.Lout;
-                            p.vt[(long)sj * p.vt_seq_stride + (long)d * p.vt_ld + vt_pos(pj, p.vt_mode ? p.vt_mode : 1)] = (half_t)a4[j];
+                            p.vt[(long)sj * p.vt_seq_stride + (long)d * p.vt_ld + vt_pos(pj, p.vt_mode)] = (half_t)a4[j];
                         }
                     }
                 }

@@ -214,6 +214,52 @@ def attention(q, k, v, kv_lens=None):
     return out
 
 
+def attention_ex(a, device="cuda:0", fill16=0x6A5A, fill32=-777.25):
+    """Test aid over svc_op_attention_ex (include/seedvc_hip.h): ONE attention launch on buffers already in the kernels' layout.
+    `a` maps the fields of svc_attention_t to ints and fp16 CPU or device tensors, taken exactly as given: either qk
+    (n_seq * seq_rows, ld_qk) with q at column q_col (default 0) and k at column k_col (default H * 64), or q and k
+    (n_seq * seq_rows, ld_qk) each; vt (n_seq, H * 64, vt_ld); kv_len a list of n_seq ints or None (then kv_len_const);
+    out32 truthy for the fp32 output; ld_out (default H * 64).  Returns the whole output buffer (n_seq * seq_rows, ld_out): fp16
+    filled with the bit pattern fill16, or fp32 filled with fill32, wherever the launch does not write."""
+    import ctypes as C
+    dev = torch.device(device)
+    H, n_rows = int(a["H"]), int(a["n_seq"]) * int(a["seq_rows"])
+    with torch.cuda.device(dev):
+        e = _lib.Attention()
+        put = lambda t: t.to(dev).contiguous()     # noqa: E731
+        if a.get("qk") is not None:
+            qk = put(a["qk"])
+            keep = [qk]
+            assert qk.dtype == torch.float16 and qk.dim() == 2 and qk.shape[0] == n_rows
+            e.ld_qk = qk.shape[1]
+            e.q = qk.data_ptr() + 2 * int(a.get("q_col", 0))
+            e.k = qk.data_ptr() + 2 * int(a.get("k_col", H * 64))
+        else:
+            q, k = put(a["q"]), put(a["k"])
+            keep = [q, k]
+            assert q.dtype == torch.float16 and k.dtype == torch.float16 and q.shape == k.shape and q.dim() == 2 and q.shape[0] == n_rows
+            e.ld_qk, e.q, e.k = q.shape[1], q.data_ptr(), k.data_ptr()
+        vt = put(a["vt"])
+        keep.append(vt)
+        assert vt.dtype == torch.float16 and vt.dim() == 3 and vt.shape[0] == int(a["n_seq"])
+        e.vt, e.vt_ld, e.vt_seq_stride = vt.data_ptr(), vt.shape[2], vt.shape[1] * vt.shape[2]
+        for name in ("n_seq", "H", "seq_rows", "Tq", "q_start", "kv_len_const", "vt_perm", "qt_form"):
+            setattr(e, name, int(a.get(name) or 0))
+        lens = _lib.i64_host(a.get("kv_len"))
+        if lens is not None:
+            assert len(lens) == e.n_seq
+            e.kv_len = C.cast(lens, C.POINTER(C.c_int64))
+        e.ld_out = int(a.get("ld_out") or H * 64)
+        if a.get("out32"):
+            out = torch.full((n_rows, e.ld_out), fill32, dtype=torch.float32, device=dev)
+            e.out32 = out.data_ptr()
+        else:
+            out = torch.full((n_rows, e.ld_out), fill16, dtype=torch.int16, device=dev).view(torch.float16)
+            e.out = out.data_ptr()
+        _lib.check(_lib.lib().svc_op_attention_ex(C.byref(e), _lib.stream_ptr()))
+    return out
+
+
 def rmsnorm(x, gamma, w=None, b=None, add_one=False):
     rows, D = x.shape
     dev = x.device

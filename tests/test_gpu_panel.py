@@ -114,8 +114,7 @@ def rows_equal(a, full, s, part, off=0, n=None):
     lo = a["row_off"] + off
     for k in part:
         if k == "vt":
-            mode = a["vt_mode"] if a["vt_mode"] else 1
-            cols = torch.tensor([P.vt_pos(p, mode) for p in range(lo, lo + n)])
+            cols = torch.tensor([P.vt_pos(p, a["vt_mode"]) for p in range(lo, lo + n)])
             assert torch.equal(bits(part[k])[0][:, cols], bits(full[k])[s][:, cols]), k
         else:
             assert torch.equal(bits(part[k])[lo:lo + n], bits(full[k])[s * R + lo:s * R + lo + n]), k
