@@ -778,6 +778,84 @@ int svc_rt_out(const svc_resampler_t* r,       /* model rate -> output rate; NUL
                float* infer,                   /* device out [N][block + Lb + Ls]: what SOLA saw */
                float* out, int32_t* offsets, void* stream);
 
+/* svc_rt_out with the mute flags of a device-resident VAD (svc_vad_step below): speech_dev is DEVICE int32 [max_slots] or NULL.
+ * Stream k is muted when its host speech[k] is 0 or speech_dev[slots[k]] == 0 (read once by the stream's workgroup, before
+ * anything else).  With speech_dev == NULL this is svc_rt_out, bit for bit; svc_rt_out and svc_sola_step keep their forms.
+ * Refused: everything svc_rt_out refuses, and speech_dev overlapping wave, infer, sola_state, out, the windows or offsets. */
+int svc_rt_out_dev(const svc_resampler_t* r, const float* wave, long long stride, int start, int n_in, int N,
+                   float* sola_state, int max_slots, const int32_t* slots, const int32_t* speech,
+                   const int32_t* speech_dev,  /* DEVICE int32[max_slots] or NULL */
+                   const float* fade_in, const float* fade_out, int block, int Lb, int Ls,
+                   float* infer, float* out, int32_t* offsets, void* stream);
+
+/* ---------------------------------------------------------------- FSMN voice activity detector
+ * 16 kHz audio -> P(silence) per 10 ms frame -> speech segments and a mute flag per live stream: funasr's `fsmn-vad`
+ * (WavFrontendOnline + FSMN + E2EVadModel), restated from memory; parity with the released checkpoint is not pinned.
+ *
+ * Front-end: Kaldi fbank (x 32768, DC removal, pre-emphasis 0.97, Hamming, 512-point power spectrum, 80 mel bins, log with
+ * the fp32 epsilon floor), F(n) = n < 400 ? 0 : (n - 400) / 160 + 1 frames; LFR m = 5, n = 1: row i = frames i-2 .. i+2
+ * (400 values), indices below 0 read frame 0 and, at a final call, indices above F - 1 read frame F - 1; then
+ * (row + shift400) * scale400.  Rows R(n, final) = final ? F(n) : max(0, F(n) - 2) = svc_vad_rows.
+ * Encoder: in_linear1 (400 -> 140) -> in_linear2 (140 -> 250) -> ReLU; 4 x { linear (250 -> 128, no bias) = p;
+ * y[t] = (sum_{k<20} w[c][k] p[t - 19 + k], an fp32 FMA chain in ascending k) + p[t], rows before the stream's start zero;
+ * affine (128 -> 250) -> ReLU }; out_linear1 (250 -> 140) -> out_linear2 (140 -> 248) -> softmax; p_sil = column 0.
+ * `weights`: the state dict of the encoder, names with or without an "encoder." prefix:
+ *   in_linear1.linear.{weight,bias}  in_linear2.linear.{weight,bias}  fsmn.{l}.linear.linear.weight
+ *   fsmn.{l}.fsmn_block.conv_left.weight [128,1,20,1]  fsmn.{l}.affine.linear.{weight,bias}
+ *   out_linear1.linear.{weight,bias}  out_linear2.linear.{weight,bias}
+ * Every p_sil element's bits are a function of its row's samples and the 76 rows before it: not of the batch, the slot, N, the
+ * segment split or the position of the row inside a call.
+ *
+ * Detector (integers only, one frame = 10 ms): frame t is speech iff p_sil[t] <= p_max in fp32 (NaN: silence).  A ring of the
+ * last `win` decisions has the sum s; window state Sil: s >= on_count -> Speech; else window state Speech: s <= off_count ->
+ * Sil.  Outside a segment a Sil -> Speech switch at t opens one: event (SVC_VAD_BEGIN, 10 max(prev_end, t - lookback)).
+ * Inside one, sil_run counts consecutive frames whose window state is Sil; sil_run == end_silence: event (SVC_VAD_END, 10 t),
+ * prev_end = t; otherwise t - begin + 1 >= max_segment: the same, and the ring and the window state are cleared.
+ * flags[slot] = 1 iff the stream was inside a segment at any frame of this call (a segment that closes within it included);
+ * a call that handles no frame leaves the flag alone.  events [N][8][2] = (kind, time_ms): the first 8 of the call are kept,
+ * n_events counts all of them.
+ *
+ * `state`: svc_vad_state_floats(max_slots) floats, [max_slots][SVC_VAD_STATE_FLOATS]: the last 19 p rows of the four layers
+ * (4 x 19 x 128 floats), then 32 int32 words (frames seen, ring bits, ring position, s, window state, in-segment, begin,
+ * sil_run, prev_end; the rest reserved).  All zeros is a fresh stream; so is flags = 0.
+ *
+ * Conventions of svc_rt_push: host arrays (lens, n_rows, total, slots) are consumed before the call returns (they become
+ * kernel arguments); every argument is checked before anything is launched, the handle last, and svc_last_error() names it; nothing
+ * synchronises or allocates in steady state (scratch grows when a call needs more rows than any before it); rows of slots
+ * that are not listed keep every bit; N and B in 1 .. 64; no slot twice; overlapping buffers are refused.
+ *
+ * svc_vad_scores: wave [B][L], lens[b] in 0 .. L; p_sil [B][svc_vad_rows(L, final)], row b holds svc_vad_rows(lens[b], final)
+ * values, the rest is not written (p_sil may be NULL where svc_vad_rows(L, final) is 0).  A clip is cut into runs of seg_rows rows (0: the handle's default, else >= 16); a run that
+ * does not start at row 0 first runs the 76 rows before it from zero caches and drops their output, which is bit-exact.
+ * svc_vad_detect: p_sil [N][ld], row k has n_rows[k] <= min(ld, 6000) new frames of stream slots[k]; frame_speech (int32
+ * [N][ld], may be NULL) receives the frame decisions; the thresholds are the handle's config.  Needs no weights: the op-level seam of the detector.
+ * svc_vad_step: row k of x holds the stream's samples ending at x[k][end), the last n_new of them new, total[k] before them;
+ * n_new a positive multiple of 160 up to 16000 and total[k] a multiple of 160; produces rows svc_vad_rows(total, 0) ..
+ * svc_vad_rows(total + n_new, 0) - 1 into p_sil[k] (ld max_rows >= n_new / 160; may be NULL), runs the detector on them and
+ * leaves flags[slot].  Reads svc_vad_history(total[k]) = min(total[k], 960) samples before the new ones: refused when
+ * end - n_new is below that for a listed stream, or end > stride. */
+typedef struct svc_vad_config {
+    float p_max;                 /* 0.2 = (1 - speech_noise_thres 0.6) / 2 */
+    int32_t win, on_count, off_count, lookback, end_silence, max_segment;   /* 20, 15, 15, 20, 65, 6000 */
+    int32_t seg_rows;            /* default run length of svc_vad_scores; 0 = 512 */
+} svc_vad_config_t;
+typedef struct svc_vad svc_vad_t;
+enum { SVC_VAD_BEGIN = 1, SVC_VAD_END = 2, SVC_VAD_MAX_EVENTS = 8, SVC_VAD_STATE_FLOATS = 4 * 19 * 128 + 32, SVC_VAD_MAX_ROWS = 6000 };
+int svc_vad_create(const svc_vad_config_t* cfg, const svc_tensor_desc_t* weights, int n_weights, const float* shift400,
+                   const float* scale400, void* stream, svc_vad_t** out);
+void svc_vad_destroy(svc_vad_t* vad);
+long svc_vad_rows(long n_samples, int final_);                 /* needs no GPU */
+long svc_vad_history(long total);                              /* samples svc_vad_step reads before the new ones; needs no GPU */
+long long svc_vad_state_floats(int max_slots);                 /* needs no GPU */
+int svc_vad_scores(svc_vad_t* vad, const float* wave, const int32_t* lens /* HOST [B] */, int B, long L, int final_, int seg_rows,
+                   float* p_sil, void* stream);
+int svc_vad_detect(svc_vad_t* vad, const float* p_sil, long ld, const int32_t* n_rows /* HOST [N] */, int N,
+                   const int32_t* slots /* HOST [N] */, int max_slots, float* state, int32_t* frame_speech, int32_t* events,
+                   int32_t* n_events, int32_t* flags, void* stream);
+int svc_vad_step(svc_vad_t* vad, const float* x, long long stride, long end, int n_new, const int64_t* total /* HOST [N] */, int N,
+                 const int32_t* slots /* HOST [N] */, int max_slots, float* state, int32_t* flags, float* p_sil, int max_rows,
+                 int32_t* events, int32_t* n_events, void* stream);
+
 /* ---------------------------------------------------------------- real-time sessions: the audio history of one block step
  * (DESIGN.md 8l).  Replaces the `input_wav` / `input_wav_res` lines of the reference GUI's audio callback (two clone-shifts, a
  * resample of the last block with 2 zc samples of history, a slice copy; restated from memory) and the gather into the dense

@@ -26,7 +26,9 @@ EXPORTS = [
     "svc_ar_session_active",
     "svc_lr_create", "svc_lr_destroy", "svc_lr_forward", "svc_crossfade",
     "svc_chunks_gather_cond", "svc_chunks_assemble", "svc_sola_step", "svc_rt_push", "svc_rt_push_tiles", "svc_rt_ring_floats",
-    "svc_rt_out", "svc_rt_push_gated",
+    "svc_rt_out", "svc_rt_push_gated", "svc_rt_out_dev",
+    "svc_vad_create", "svc_vad_destroy", "svc_vad_rows", "svc_vad_history", "svc_vad_state_floats", "svc_vad_scores", "svc_vad_detect",
+    "svc_vad_step",
     "svc_campplus_create", "svc_campplus_destroy", "svc_campplus_forward", "svc_kaldi_fbank_frames", "svc_kaldi_fbank",
     "svc_kaldi_fbank_ragged", "svc_campplus_forward_ragged",
     "svc_mel_create", "svc_mel_destroy", "svc_mel_frames", "svc_mel_forward", "svc_mel_forward_ragged", "svc_mel_min_len",
@@ -124,6 +126,12 @@ class AstralConfig(C.Structure):
     _fields_ = [("ssl", W2vConfig), ("n_heads", C.c_int), ("head", AstralHeadConfig * 2)]
 
 
+class VadConfig(C.Structure):
+    """svc_vad_config_t: the detector's thresholds (frames of 10 ms) and the default run length of svc_vad_scores."""
+    _fields_ = [("p_max", C.c_float)] + [(n, C.c_int32) for n in ("win", "on_count", "off_count", "lookback", "end_silence",
+                                                                  "max_segment", "seg_rows")]
+
+
 class LrConfig(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("channels", "in_channels", "out_channels", "is_discrete", "codebook_size", "n_convs",
                                        "interpolate", "has_final_conv", "f0_condition", "n_f0_bins")]
@@ -186,6 +194,25 @@ def lib():
         l.svc_rt_out.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int32),
                                  C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p]
+        # svc_rt_out with DEVICE mute flags behind the host ones
+        a = l.svc_rt_out.argtypes
+        l.svc_rt_out_dev.argtypes = a[:10] + [C.c_void_p] + a[10:]
+        # FSMN-VAD: lengths, row counts and slots as HOST int32 arrays, totals as a HOST int64 array, sample counts as C long
+        l.svc_vad_create.argtypes = [C.POINTER(VadConfig), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+        l.svc_vad_destroy.argtypes = [C.c_void_p]
+        l.svc_vad_destroy.restype = None
+        l.svc_vad_rows.argtypes = [C.c_long, C.c_int]
+        l.svc_vad_rows.restype = C.c_long
+        l.svc_vad_history.argtypes = [C.c_long]
+        l.svc_vad_history.restype = C.c_long
+        l.svc_vad_state_floats.argtypes = [C.c_int]
+        l.svc_vad_state_floats.restype = C.c_longlong
+        l.svc_vad_scores.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_long, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        l.svc_vad_detect.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.c_int,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        l.svc_vad_step.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_long, C.c_int, C.POINTER(C.c_int64), C.c_int,
+                                   C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                   C.c_void_p]
         l.svc_rt_push_tiles.argtypes = [C.c_int]
         l.svc_rt_ring_floats.argtypes = [C.c_int, C.c_int]
         l.svc_rt_ring_floats.restype = C.c_longlong

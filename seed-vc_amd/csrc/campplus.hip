@@ -20,6 +20,7 @@
 #include <string>
 #include <vector>
 
+#include "kaldi_tables.h"
 #include "model_util.h"
 
 using namespace svc;
@@ -391,26 +392,10 @@ int svc_campplus::pack(const StateDict& sd, hipStream_t st) {
     }
     // ---- Kaldi fbank constants: 25 ms / 10 ms frames at 16 kHz, 512-point DFT, 80 Kaldi-mel triangles from 20 Hz to Nyquist
     {
-        const int win = 400, nfft = 512, nb = nfft / 2 + 1, bins = cfg.feat_dim;
-        std::vector<float> wv(win), basis((size_t)round_up(2 * nb, 128) * nfft, 0.f), mel((size_t)round_up(bins, 128) * round_up(nb, 32), 0.f);
+        const int win = 400, bins = cfg.feat_dim;
+        std::vector<float> wv(win);
         for (int i = 0; i < win; ++i) wv[i] = powf(0.5f - 0.5f * cosf(2.0f * (float)M_PI * (float)i / (float)(win - 1)), 0.85f);
-        for (int k = 0; k < nb; ++k)
-            for (int n = 0; n < nfft; ++n) {
-                const double ang = 2.0 * M_PI * (double)(((long)k * n) % nfft) / (double)nfft;
-                basis[(size_t)k * nfft + n] = (float)cos(ang);
-                basis[(size_t)(nb + k) * nfft + n] = (float)(-sin(ang));
-            }
-        auto melf = [](float f) { return 1127.0f * logf(1.0f + f / 700.0f); };
-        const float mlo = melf(20.0f), mhi = melf(8000.0f), delta = (mhi - mlo) / (float)(bins + 1);
-        const long ldm = round_up(nb, 32);
-        for (int b = 0; b < bins; ++b) {
-            const float left = mlo + b * delta, center = mlo + (b + 1.0f) * delta, right = mlo + (b + 2.0f) * delta;
-            for (int k = 0; k < nfft / 2; ++k) {
-                const float m = melf(16000.0f / nfft * (float)k);
-                const float up = (m - left) / (center - left), down = (right - m) / (right - center);
-                mel[(size_t)b * ldm + k] = std::max(0.0f, std::min(up, down));
-            }
-        }
+        const std::vector<float> basis = kaldi_dft_basis(), mel = kaldi_mel_bank(bins);
         fb_window = wts.alloc_n<float>(win, st);
         fb_dft = wts.alloc_n<float>(basis.size(), st);
         fb_mel = wts.alloc_n<float>(mel.size(), st);

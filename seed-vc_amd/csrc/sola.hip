@@ -25,6 +25,7 @@ struct SolaSlots { int slot[SOLA_MAXN]; };
 // bit k of `muted` is set
 struct SolaPro {
     float* infer; int n_in, n_inf, resample; unsigned long long muted;
+    const int* speech_dev;                   // svc_rt_out_dev: device flags [max_slots], 0 mutes (the DEV forms only read it)
     RsGeom q; const float* taps_kn; const int* first;
 };
 
@@ -47,8 +48,9 @@ __device__ __forceinline__ float fade_mix(float y, float fi, float b, float fo) 
 // No sample at or above start + block + Lb + Ls is read.  VEC: block and Lb are multiples of 4 and out / state / fades
 // are 16-byte aligned, so a group of 4 samples lies on one side of the fade and of the out / state boundary.
 // PRO: x is the stream's row of pro.infer, which this workgroup writes first (and reads back behind the barrier: a workgroup's
-// own global writes are visible to it there); `start` then counts in `wave` only.
-template <bool VEC, bool PRO>
+// own global writes are visible to it there); `start` then counts in `wave` only.  DEV (with PRO): the stream is also muted
+// where pro.speech_dev[slot] is 0, one workgroup-uniform read; the other forms are compiled without it.
+template <bool VEC, bool PRO, bool DEV>
 __global__ __launch_bounds__(SOLA_THREADS) void sola_step_kernel(const float* __restrict__ wave, long stride, int start,
                                                                  float* __restrict__ state, const SolaSlots slots,
                                                                  const float* __restrict__ fade_in, const float* __restrict__ fade_out,
@@ -64,7 +66,9 @@ __global__ __launch_bounds__(SOLA_THREADS) void sola_step_kernel(const float* __
     if constexpr (PRO) {
         float* y = pro.infer + (long)k * pro.n_inf;
         const float* seg = x;
-        if ((pro.muted >> k) & 1ULL) {
+        bool muted = (pro.muted >> k) & 1ULL;
+        if constexpr (DEV) muted = muted || pro.speech_dev[slots.slot[k]] == 0;
+        if (muted) {
             for (int i = tid; i < pro.n_inf; i += SOLA_THREADS) y[i] = 0.f;
         } else if (!pro.resample) {
             for (int i = tid; i < pro.n_inf; i += SOLA_THREADS) y[i] = seg[i];
@@ -193,7 +197,8 @@ inline bool apart(uintptr_t a0, uintptr_t a1, uintptr_t b0, uintptr_t b1) { retu
 // The checks and launches of both entries.  !pro: svc_sola_step, the kernel without the prologue.
 int sola_launch(const char* who, const float* wave, long long stride, int start, int N, float* sola_state, int max_slots,
                 const int32_t* slots, const float* fade_in, const float* fade_out, int block, int Lb, int Ls, float* out,
-                int32_t* offsets, const svc_resampler_t* r, int n_in, const int32_t* speech, float* infer, bool pro, void* stream) {
+                int32_t* offsets, const svc_resampler_t* r, int n_in, const int32_t* speech, const int32_t* speech_dev, float* infer, bool pro,
+                void* stream) {
 #define SOLA_REQUIRE(cond, msg) \
     do { if (!(cond)) { set_error(std::string(who) + msg); return 1; } } while (0)
     SOLA_REQUIRE(N >= 0 && stride >= 0 && start >= 0 && max_slots >= 0, ": negative argument");
@@ -226,6 +231,13 @@ int sola_launch(const char* who, const float* wave, long long stride, int start,
         SOLA_REQUIRE(apart(i0, i1, w0, w1) && apart(i0, i1, s0, s1) && apart(i0, i1, o0, o1) && apart(i0, i1, f0, f1) &&
                      apart(i0, i1, g0, g1) && (!offsets || apart(i0, i1, d0, d1)),
                      ": infer overlaps wave, sola_state, out, the windows or offsets");
+        if (speech_dev) {
+            SOLA_REQUIRE(((uintptr_t)speech_dev & 3) == 0, ": speech_dev is not aligned to 4 bytes");
+            const uintptr_t v0 = (uintptr_t)speech_dev, v1 = v0 + (uintptr_t)max_slots * 4;
+            SOLA_REQUIRE(apart(v0, v1, i0, i1) && apart(v0, v1, w0, w1) && apart(v0, v1, s0, s1) && apart(v0, v1, o0, o1) &&
+                         apart(v0, v1, f0, f1) && apart(v0, v1, g0, g1) && (!offsets || apart(v0, v1, d0, d1)),
+                         ": speech_dev overlaps wave, infer, sola_state, out, the windows or offsets");
+        }
     }
 #undef SOLA_REQUIRE
     const bool vec = block % 4 == 0 && Lb % 4 == 0 &&
@@ -243,6 +255,7 @@ int sola_launch(const char* who, const float* wave, long long stride, int start,
             p.infer = infer + (long long)k0 * n_inf; p.n_in = n_in; p.n_inf = (int)n_inf; p.resample = r ? 1 : 0;
             for (int k = 0; speech && k < nk; ++k)
                 if (!speech[k0 + k]) p.muted |= 1ULL << k;
+            p.speech_dev = speech_dev;
             if (r) { p.q = r->q; p.taps_kn = r->taps_kn; p.first = r->first; }
         }
         const float* w = wave + (long long)k0 * stride;
@@ -252,8 +265,9 @@ int sola_launch(const char* who, const float* wave, long long stride, int start,
             hipLaunchKernelGGL(kernel, dim3(nk), dim3(SOLA_THREADS), lds, (hipStream_t)stream, w, (long)stride, start, sola_state, s,
                                fade_in, fade_out, block, Lb, Ls, o, off, p);
         };
-        if (pro) { if (vec) launch(sola_step_kernel<true, true>); else launch(sola_step_kernel<false, true>); }
-        else { if (vec) launch(sola_step_kernel<true, false>); else launch(sola_step_kernel<false, false>); }
+        if (pro && speech_dev) { if (vec) launch(sola_step_kernel<true, true, true>); else launch(sola_step_kernel<false, true, true>); }
+        else if (pro) { if (vec) launch(sola_step_kernel<true, true, false>); else launch(sola_step_kernel<false, true, false>); }
+        else { if (vec) launch(sola_step_kernel<true, false, false>); else launch(sola_step_kernel<false, false, false>); }
         SVC_CHECK_HIP(hipGetLastError());
     }
     return 0;
@@ -264,12 +278,19 @@ extern "C" int svc_sola_step(const float* wave, long long stride, int start, int
                              const int32_t* slots, const float* fade_in, const float* fade_out, int block, int Lb, int Ls,
                              float* out, int32_t* offsets, void* stream) {
     return sola_launch("sola_step", wave, stride, start, N, sola_state, max_slots, slots, fade_in, fade_out, block, Lb, Ls, out, offsets,
-                       nullptr, 0, nullptr, nullptr, false, stream);
+                       nullptr, 0, nullptr, nullptr, nullptr, false, stream);
 }
 
 extern "C" int svc_rt_out(const svc_resampler_t* r, const float* wave, long long stride, int start, int n_in, int N, float* sola_state,
                           int max_slots, const int32_t* slots, const int32_t* speech, const float* fade_in, const float* fade_out,
                           int block, int Lb, int Ls, float* infer, float* out, int32_t* offsets, void* stream) {
     return sola_launch("rt_out", wave, stride, start, N, sola_state, max_slots, slots, fade_in, fade_out, block, Lb, Ls, out, offsets,
-                       r, n_in, speech, infer, true, stream);
+                       r, n_in, speech, nullptr, infer, true, stream);
+}
+
+extern "C" int svc_rt_out_dev(const svc_resampler_t* r, const float* wave, long long stride, int start, int n_in, int N, float* sola_state,
+                              int max_slots, const int32_t* slots, const int32_t* speech, const int32_t* speech_dev, const float* fade_in,
+                              const float* fade_out, int block, int Lb, int Ls, float* infer, float* out, int32_t* offsets, void* stream) {
+    return sola_launch("rt_out_dev", wave, stride, start, N, sola_state, max_slots, slots, fade_in, fade_out, block, Lb, Ls, out, offsets,
+                       r, n_in, speech, speech_dev, infer, true, stream);
 }

@@ -871,6 +871,7 @@ class RealtimeEngine:
         self._out = None                    # `attach_output`: the splice at another rate than the model's
         self._speech = {}                   # slot -> the caller's VAD flag (`set_speech`)
         self._gate = {}                     # slot -> gate threshold as an energy of 4 zc samples (`set_gate`); absent: off
+        self._vad = None                    # `attach_vad`: the device-resident VAD of `step_audio`
 
     def open(self, prompt_condition, mel2, style2):
         """A new stream on the reference (prompt_condition (1, P, Dc), mel2 (1, C, P), style2 (1, Ds)) -> its slot, the
@@ -891,6 +892,7 @@ class RealtimeEngine:
         self._zero_audio(slot)
         self._speech[slot] = True
         self._gate.pop(slot, None)
+        self._zero_vad(slot, on=False)
         return slot
 
     def _check_slot(self, slot, what):
@@ -905,6 +907,7 @@ class RealtimeEngine:
         self._stacked = (None, None)
         self._speech.pop(slot, None)
         self._gate.pop(slot, None)
+        self._zero_vad(slot, on=False)
 
     def reset(self, slot):
         """Zeroes the stream's SOLA buffer (the GUI does so when a stream restarts)."""
@@ -912,6 +915,8 @@ class RealtimeEngine:
         self.state[slot].zero_()
         self._zero_audio(slot)
         self._speech[slot] = True
+        if self._vad is not None:
+            self._zero_vad(slot, on=slot in self._vad["on"])
 
     # ------------------------------------------------------------------------------------------- live settings
     def attach_output(self, resample_out, fade_in=None, fade_out=None):
@@ -967,6 +972,46 @@ class RealtimeEngine:
             self._audio["gate_e"][slot].zero_()
         self._gate[slot] = p
 
+    def attach_vad(self, vad):
+        """A device-resident VAD (seedvc_amd.vad.FsmnVad) for `step_audio`: needs `attach_audio` with a 16 kHz
+        content rate and a context that keeps the 960 samples of history `svc_vad_step` reads before a block's new ones.
+        Allocates the per-slot VAD state and the mute flags (device int32, one per slot).  The VAD is off per slot until
+        `set_vad(slot, True)`; a slot with its VAD off has its flag held at 1, so only `set_speech` mutes it."""
+        a = self._audio
+        if a is None:
+            raise ValueError("RealtimeEngine.attach_vad: attach_audio has not been called")
+        if a["z16"] != 320:
+            raise ValueError(f"RealtimeEngine.attach_vad: the content rate is {a['z16'] * 50} Hz, the VAD takes 16000")
+        n_new, end = a["Lin"] // a["zc"] * a["z16"], a["L16"] - a["z16"]
+        if end - n_new < 960:
+            raise ValueError(f"RealtimeEngine.attach_vad: the context keeps {end - n_new} samples before a block's {n_new} new ones, "
+                             f"the VAD reads 960")
+        if not callable(getattr(vad, "step", None)):
+            raise ValueError("RealtimeEngine.attach_vad: vad has no step")
+        from .vad import STATE_FLOATS
+        self._vad = dict(vad=vad, n_new=n_new, end=end, on=set(), total={},
+                         state=torch.zeros(self.max_streams, STATE_FLOATS, device=self.device, dtype=torch.float32),
+                         flags=torch.ones(self.max_streams, device=self.device, dtype=torch.int32))
+
+    def set_vad(self, slot, on):
+        """Switches the attached VAD on or off for one stream.  On: the stream's VAD state starts fresh (flag 0: muted until a
+        speech segment opens, the GUI's `vad_speech_detected = False`) from the next `step_audio` block.  Off (the default on
+        `open`): the flag is held at 1.  Kept across `reset`, which restarts the state."""
+        self._check_slot(slot, "set_vad")
+        if self._vad is None:
+            raise ValueError("RealtimeEngine.set_vad: attach_vad has not been called")
+        if bool(on) != (slot in self._vad["on"]):
+            self._zero_vad(slot, on=bool(on))
+
+    def _zero_vad(self, slot, on):
+        v = self._vad
+        if v is None:
+            return
+        v["state"][slot].zero_()
+        v["flags"][slot] = 0 if on else 1
+        v["total"][slot] = 0
+        (v["on"].add if on else v["on"].discard)(slot)
+
     def _stack_prompts(self, slots):
         """Padded batch tensors of the streams' references (kept while the same slots come back in the same order)."""
         key = tuple(slots)
@@ -996,7 +1041,7 @@ class RealtimeEngine:
             raise ValueError("RealtimeEngine.step_seeded: seeds is None")
         return self._step(slots, content, n_timesteps, inference_cfg_rate, None, vocoder_kwargs, return_parts, seeds)
 
-    def _step(self, slots, content, n_timesteps, inference_cfg_rate, z, vocoder_kwargs, return_parts, seeds):
+    def _step(self, slots, content, n_timesteps, inference_cfg_rate, z, vocoder_kwargs, return_parts, seeds, speech_dev=None):
         slots = [int(s) for s in slots]
         seeds = _seed_list("RealtimeEngine.step_seeded", seeds, len(slots), z, vocoder_kwargs)
         for s in slots:
@@ -1029,7 +1074,16 @@ class RealtimeEngine:
             wave = _lib.f32c(calls[0].wave, dev)
             offsets = torch.empty(n, dtype=torch.int32, device=dev) if return_parts else None
             speech = [1 if self._speech.get(s, True) else 0 for s in slots]
-            if live is None and all(speech):                                     # host state decides which entry splices
+            if speech_dev is not None:                                           # a listed slot has its VAD on: device flags too
+                g = live or dict(block=self.block, Lb=self.Lb, Ls=self.Ls, n_inf=self.n_inf, fade_in=self.fade_in, fade_out=self.fade_out)
+                out = torch.empty(n, g["block"], device=dev)
+                infer = torch.empty(n, g["n_inf"], device=dev)
+                _lib.check(_lib.lib().svc_rt_out_dev(live["resample"]._h if live else None, _lib.ptr(wave), wave.size(1), self.start,
+                                                     self.n_inf, n, _lib.ptr(self.state), self.max_streams, _lib.i32_host(slots),
+                                                     None if all(speech) else _lib.i32_host(speech), _lib.ptr(speech_dev),
+                                                     _lib.ptr(g["fade_in"]), _lib.ptr(g["fade_out"]), g["block"], g["Lb"], g["Ls"],
+                                                     _lib.ptr(infer), _lib.ptr(out), _lib.ptr(offsets), _lib.stream_ptr()))
+            elif live is None and all(speech):                                   # host state decides which entry splices
                 out = torch.empty(n, self.block, device=dev)
                 _lib.check(_lib.lib().svc_sola_step(_lib.ptr(wave), wave.size(1), self.start, n, _lib.ptr(self.state), self.max_streams,
                                                     _lib.i32_host(slots), _lib.ptr(self.fade_in), _lib.ptr(self.fade_out), self.block,
@@ -1141,10 +1195,24 @@ class RealtimeEngine:
                                                         _lib.i32_host(slots), self.max_streams, a["zc"], a["z16"], _lib.ptr(a["hist"]),
                                                         _lib.ptr(a["ring"]), a["L16"], _lib.ptr(ctx), (C.c_float * n)(*pows),
                                                         _lib.ptr(a["gate_e"]), _lib.ptr(mask), _lib.stream_ptr()))
+            # the VAD runs on the samples of the context that no later push computes again (everything but its last z16): the
+            # gated, resampled stream bit for bit, 20 ms behind the microphone
+            v, vad_parts, speech_dev = self._vad, None, None
+            rows = [k for k, s in enumerate(slots) if v is not None and s in v["on"]]
+            if rows:
+                x = ctx if len(rows) == n else torch.stack([ctx[k] for k in rows])      # device copies only: nothing synchronises
+                on = [slots[k] for k in rows]
+                vad_parts = v["vad"].step(x, v["end"], v["n_new"], [v["total"][s] for s in on], on, v["state"], v["flags"],
+                                          return_parts=return_parts)
+                for s in on:
+                    v["total"][s] += v["n_new"]
+                speech_dev = v["flags"]
             content = a["content"].semantic_fn(ctx)[:, a["ce"]:]
-        res = self._step(slots, content, n_timesteps, inference_cfg_rate, z, vocoder_kwargs, return_parts, seeds)
+        res = self._step(slots, content, n_timesteps, inference_cfg_rate, z, vocoder_kwargs, return_parts, seeds, speech_dev)
         if return_parts:
             res[1].update(ctx=ctx, content=content)
+            if vad_parts is not None:
+                res[1]["vad"] = dict(vad_parts, slots=on, flags=speech_dev.clone())
             if mask is not None:
                 res[1]["gate_mask"] = mask
         return res
