@@ -429,3 +429,11 @@ class ARSession:
         while self._waiting or self._active:
             out += self.step()
         return out
+
+    def close(self):
+        """Drops what is waiting and retires what is in flight, so that the model is free again (a caller's way out of an
+        error between `submit` and the end of `drain`)."""
+        self._waiting.clear()
+        for slot in sorted(self._active):
+            self.ar.session_retire(slot, 0)
+        self._active.clear()

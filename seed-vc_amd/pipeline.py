@@ -337,6 +337,90 @@ def _row_views(vc, S, calls):
     return rows
 
 
+def _long_pool(cfm, vocoder, utterances, n_timesteps, inference_cfg_rate, hop, max_context_window, overlap_frame_len, noise_fn,
+               vocoder_kwargs_fn, max_chunks, ragged_vocoder, seeds, seed_kw, cfm_kwargs=None):
+    """The chunk pool of `HotPath.convert_long_batch` and of the timbre branch of `V2HotPath.convert_long_batch`, behind their
+    argument checks: `long_batch_plan`, then per micro-batch `svc_chunks_gather_cond` -> one `cfm.inference` with per-row
+    x_lens / prompt_lens -> `_strip_prompt` -> `_vocode` -> rows of one wave buffer, one `svc_chunks_assemble` and one host
+    synchronisation at the end.  utterances, noise_fn, vocoder_kwargs_fn, ragged_vocoder (a bool here) and seeds (host
+    integers or None) as `HotPath.convert_long_batch` documents them; seed_kw: `_vocode`'s; cfm_kwargs: further keywords of
+    every sampler call (the v2 caller's `random_voice`)."""
+    U = len(utterances)
+    if U == 0:
+        return []
+    for u, (cond, pc, mel2, style2) in enumerate(utterances):
+        if pc.size(1) != mel2.size(2):
+            raise ValueError(f"convert_long_batch: utterance {u}: prompt_condition has {pc.size(1)} frames, mel2 {mel2.size(2)}")
+    P = [int(t[2].size(2)) for t in utterances]
+    n_src = [int(t[0].size(1)) for t in utterances]
+    plan = long_batch_plan(n_src, P, max_context_window, overlap_frame_len, hop, max_chunks)
+    chunks, out_lens = plan["chunks"], plan["out_lens"]
+    dev = utterances[0][0].device
+    ovw = overlap_frame_len * hop
+    i32 = _lib.i32_host
+    with torch.cuda.device(dev):
+        out = torch.empty(sum(out_lens), device=dev, dtype=torch.float32)
+        offs = [sum(out_lens[:u]) for u in range(U)]
+        result = [out[o:o + n][None, :] for o, n in zip(offs, out_lens)]
+        if not chunks:
+            return result
+        N = len(chunks)
+        Dc, Cm = utterances[0][0].size(2), utterances[0][2].size(1)
+        # the utterances' tensors, stacked once: condition rows along time, prompts padded to Pmax
+        cond_all = torch.cat([_lib.f32c(t[0], dev)[0] for t in utterances])
+        row_base = [sum(n_src[:u]) for u in range(U)]
+        st = _stack_prompts([t[1:] for t in utterances], dev)
+        pc_all, mel_all, style_all, Pmax = st["prompt_condition"], st["mel"], st["style"], st["Pmax"]
+        utt = [c[0] for c in chunks]
+        chunk_seeds = None
+        if seeds is not None:       # chunk k of its file: the chunks are listed utterance-major
+            first_of = {}
+            for k, u in enumerate(utt):
+                first_of.setdefault(u, k)
+            chunk_seeds = [derive_seed(seeds[u], k - first_of[u]) for k, u in enumerate(utt)]
+        if U > 1:
+            idx = torch.tensor(utt, device=dev)
+            mel_chunks, style_chunks = mel_all.index_select(0, idx), style_all.index_select(0, idx)
+        else:
+            mel_chunks, style_chunks = mel_all.expand(N, -1, -1), style_all.expand(N, -1)
+        fade_in, fade_out = (torch.from_numpy(w).to(dev) for w in _cos2_windows(ovw))
+        stride = max(c[2] for c in chunks) * hop
+        waves = torch.empty(N, stride, device=dev, dtype=torch.float32)      # row k: chunk k's waveform, lens[k] samples
+        for k0, k1 in plan["micro_batches"]:
+            mb = chunks[k0:k1]
+            n = k1 - k0
+            S = [c[2] for c in mb]
+            Pk = [P[c[0]] for c in mb]
+            x_lens = [p + s for p, s in zip(Pk, S)]
+            T = max(x_lens)
+            mu = torch.empty(n, T, Dc, device=dev)
+            _lib.check(_lib.lib().svc_chunks_gather_cond(_lib.ptr(pc_all), i32(P), U, Pmax, _lib.ptr(cond_all), cond_all.size(0),
+                                                         i32([c[0] for c in mb]), i32([row_base[c[0]] + c[1] for c in mb]),
+                                                         i32(S), n, Dc, T, _lib.ptr(mu), _lib.stream_ptr()))
+            z = None
+            if noise_fn is not None:
+                z = torch.zeros(n, Cm, T, device=dev)
+                for i, t_k in enumerate(x_lens):
+                    z[i, :, :t_k] = noise_fn(t_k)[0]
+            kws = [vocoder_kwargs_fn(s) for s in S] if vocoder_kwargs_fn is not None else None
+            mb_seeds = chunk_seeds[k0:k1] if chunk_seeds is not None else None
+            mel = cfm.inference(mu, x_lens, mel_chunks[k0:k1], style_chunks[k0:k1], None, n_timesteps, inference_cfg_rate=inference_cfg_rate,
+                                z=z, prompt_lens=Pk, **_cfm_seeds(mb_seeds), **(cfm_kwargs or {}))
+            vc = _strip_prompt(mel, Pk, x_lens, max(S))
+            for call in _vocode(vocoder, vc, S, ragged_vocoder, "convert_long_batch", hop=hop, seeds=mb_seeds,
+                                seed_kw=seed_kw, row_kwargs=kws):
+                j = 0
+                for a, b in call.runs:       # rows of a call -> rows of the chunk wave buffer (slices: no synchronisation)
+                    waves[k0 + a:k0 + b, :call.frames * hop].copy_(call.wave[j:j + b - a])
+                    j += b - a
+        lens = [c[2] * hop for c in chunks]
+        _lib.check(_lib.lib().svc_chunks_assemble(_lib.ptr(waves), C.c_longlong(stride), i32(lens), i32([int(c[3]) for c in chunks]),
+                                                  i32([int(c[4]) for c in chunks]), N, _lib.ptr(fade_in), _lib.ptr(fade_out), ovw,
+                                                  _lib.ptr(out), C.c_longlong(out.numel()), _lib.stream_ptr()))
+        torch.cuda.current_stream(dev).synchronize()
+    return result
+
+
 class HotPath:
     """cfm: seedvc_amd.cfm.CFM ; vocoder: seedvc_amd.vocoder.BigVGAN | HiFT."""
 
@@ -507,80 +591,8 @@ class HotPath:
         if ragged_vocoder and vocoder_kwargs_fn is not None:
             raise ValueError("convert_long_batch: vocoder_kwargs_fn pins per-chunk draws of a plain vocoder call; "
                              "it cannot be combined with the ragged vocoder call")
-        U = len(utterances)
-        if U == 0:
-            return []
-        for u, (cond, pc, mel2, style2) in enumerate(utterances):
-            if pc.size(1) != mel2.size(2):
-                raise ValueError(f"convert_long_batch: utterance {u}: prompt_condition has {pc.size(1)} frames, mel2 {mel2.size(2)}")
-        P = [int(t[2].size(2)) for t in utterances]
-        n_src = [int(t[0].size(1)) for t in utterances]
-        plan = long_batch_plan(n_src, P, max_context_window, overlap_frame_len, hop, max_chunks)
-        chunks, out_lens = plan["chunks"], plan["out_lens"]
-        dev = utterances[0][0].device
-        ovw = overlap_frame_len * hop
-        i32 = _lib.i32_host
-        with torch.cuda.device(dev):
-            out = torch.empty(sum(out_lens), device=dev, dtype=torch.float32)
-            offs = [sum(out_lens[:u]) for u in range(U)]
-            result = [out[o:o + n][None, :] for o, n in zip(offs, out_lens)]
-            if not chunks:
-                return result
-            N = len(chunks)
-            Dc, Cm = utterances[0][0].size(2), utterances[0][2].size(1)
-            # the utterances' tensors, stacked once: condition rows along time, prompts padded to Pmax
-            cond_all = torch.cat([_lib.f32c(t[0], dev)[0] for t in utterances])
-            row_base = [sum(n_src[:u]) for u in range(U)]
-            st = _stack_prompts([t[1:] for t in utterances], dev)
-            pc_all, mel_all, style_all, Pmax = st["prompt_condition"], st["mel"], st["style"], st["Pmax"]
-            utt = [c[0] for c in chunks]
-            chunk_seeds = None
-            if seeds is not None:       # chunk k of its file: the chunks are listed utterance-major
-                first_of = {}
-                for k, u in enumerate(utt):
-                    first_of.setdefault(u, k)
-                chunk_seeds = [derive_seed(seeds[u], k - first_of[u]) for k, u in enumerate(utt)]
-            if U > 1:
-                idx = torch.tensor(utt, device=dev)
-                mel_chunks, style_chunks = mel_all.index_select(0, idx), style_all.index_select(0, idx)
-            else:
-                mel_chunks, style_chunks = mel_all.expand(N, -1, -1), style_all.expand(N, -1)
-            fade_in, fade_out = (torch.from_numpy(w).to(dev) for w in _cos2_windows(ovw))
-            stride = max(c[2] for c in chunks) * hop
-            waves = torch.empty(N, stride, device=dev, dtype=torch.float32)      # row k: chunk k's waveform, lens[k] samples
-            for k0, k1 in plan["micro_batches"]:
-                mb = chunks[k0:k1]
-                n = k1 - k0
-                S = [c[2] for c in mb]
-                Pk = [P[c[0]] for c in mb]
-                x_lens = [p + s for p, s in zip(Pk, S)]
-                T = max(x_lens)
-                mu = torch.empty(n, T, Dc, device=dev)
-                _lib.check(_lib.lib().svc_chunks_gather_cond(_lib.ptr(pc_all), i32(P), U, Pmax, _lib.ptr(cond_all), cond_all.size(0),
-                                                             i32([c[0] for c in mb]), i32([row_base[c[0]] + c[1] for c in mb]),
-                                                             i32(S), n, Dc, T, _lib.ptr(mu), _lib.stream_ptr()))
-                z = None
-                if noise_fn is not None:
-                    z = torch.zeros(n, Cm, T, device=dev)
-                    for i, t_k in enumerate(x_lens):
-                        z[i, :, :t_k] = noise_fn(t_k)[0]
-                kws = [vocoder_kwargs_fn(s) for s in S] if vocoder_kwargs_fn is not None else None
-                mb_seeds = chunk_seeds[k0:k1] if chunk_seeds is not None else None
-                mel = self.cfm.inference(mu, x_lens, mel_chunks[k0:k1], style_chunks[k0:k1], None, n_timesteps,
-                                         inference_cfg_rate=inference_cfg_rate, z=z, prompt_lens=Pk, **_cfm_seeds(mb_seeds))
-                vc = _strip_prompt(mel, Pk, x_lens, max(S))
-                for call in _vocode(self.vocoder, vc, S, ragged_vocoder, "convert_long_batch", hop=hop, seeds=mb_seeds,
-                                    seed_kw=self._vocoder_seeds, row_kwargs=kws):
-                    j = 0
-                    for a, b in call.runs:       # rows of a call -> rows of the chunk wave buffer (slices: no synchronisation)
-                        waves[k0 + a:k0 + b, :call.frames * hop].copy_(call.wave[j:j + b - a])
-                        j += b - a
-            lens = [c[2] * hop for c in chunks]
-            _lib.check(_lib.lib().svc_chunks_assemble(_lib.ptr(waves), C.c_longlong(stride), i32(lens), i32([int(c[3]) for c in chunks]),
-                                                      i32([int(c[4]) for c in chunks]), N, _lib.ptr(fade_in), _lib.ptr(fade_out), ovw,
-                                                      _lib.ptr(out), C.c_longlong(out.numel()), _lib.stream_ptr()))
-            torch.cuda.current_stream(dev).synchronize()
-        return result
+        return _long_pool(self.cfm, self.vocoder, utterances, n_timesteps, inference_cfg_rate, hop, max_context_window, overlap_frame_len,
+                          noise_fn, vocoder_kwargs_fn, max_chunks, ragged_vocoder, seeds, self._vocoder_seeds)
 
 
 # ----------------------------------------------------------------------------------------- v2: tokens in, audio out
@@ -596,6 +608,54 @@ def v2_target_frames(frames_per_token, n_tokens):
 def v2_ar_prompt(target_narrow, src_narrow):
     """The AR model's condition tokens: target then source narrow tokens along time (vc_wrapper.py:636-712, from memory)."""
     return torch.cat([target_narrow, src_narrow], dim=1)
+
+
+def v2_chunk_plan(n_tokens, chunk_tokens):
+    """Token ranges of the style branch of `convert_voice_with_streaming` (modules/v2/vc_wrapper.py, quoted from memory:
+    correct it here if the reference differs): the reduced narrow tokens of the source are cut at `range(0, n, max_chunk_size)`
+    into disjoint ranges, each generated by the AR model on its own, and the range that reaches the end is the last chunk.
+    -> [(first token, tokens, is_last)], is_last = first + chunk_tokens >= n_tokens; no chunks for n_tokens == 0."""
+    n, c = int(n_tokens), int(chunk_tokens)
+    if c < 1:
+        raise ValueError(f"v2_chunk_plan: chunk_tokens = {chunk_tokens}, a chunk needs at least one token")
+    return [(i, min(c, n - i), i + c >= n) for i in range(0, n, c)]
+
+
+def v2_seam_plan(chunk_files, wave_lens, is_last, overlap_wave_len, n_files):
+    """Which chunk waveforms of the style branch are spliced, and how (host integers only).  chunk_files[k] / wave_lens[k] /
+    is_last[k]: file, samples and `v2_chunk_plan` flag of chunk k, the chunks listed file-major; ov = overlap_wave_len.
+
+    The AR model decides a chunk's length, and the reference's loop is only defined for long chunks: a chunk that is not the
+    last and has fewer than ov samples is a numpy shape error there, and one of ov .. 2 ov - 1 samples would hand on a tail
+    that already holds cross-faded samples, which `svc_chunks_assemble` (raw tails) does not do.  The rule here: a chunk is
+    KEPT if it has at least 2 ov samples, or if it is the last chunk of its file; an empty chunk is never kept.  Chunks that
+    are not kept contribute nothing.  `first` / `last` are taken over the kept chunks of a file, so a file whose final chunk
+    is empty ends on its last kept chunk, which is emitted whole; a file without a kept chunk has no samples.  Over the kept
+    chunks the result is `stream_wave_chunks` run on them in order, bit for bit.
+    -> dict(kept, first, last: one bool per chunk (first / last False where not kept), out_lens: samples per file)."""
+    N, ov = len(chunk_files), int(overlap_wave_len)
+    if not (N == len(wave_lens) == len(is_last)):
+        raise ValueError("v2_seam_plan: chunk_files, wave_lens and is_last must have one entry per chunk")
+    kept = [n > 0 and (n >= 2 * ov or bool(l)) for n, l in zip(wave_lens, is_last)]
+    first, last, out_lens = [False] * N, [False] * N, [0] * n_files
+    for u in range(n_files):
+        ks = [k for k in range(N) if chunk_files[k] == u and kept[k]]
+        if ks:
+            first[ks[0]], last[ks[-1]] = True, True
+            out_lens[u] = sum(wave_lens[k] - (0 if last[k] else ov) for k in ks)
+    return dict(kept=kept, first=first, last=last, out_lens=out_lens)
+
+
+def v2_file_record(tokens_record, n_samples, hop, target, length_adjust=1.0):
+    """One file of `V2HotPath.convert_long_batch` from one entry of `v2_content_tokens`: n_samples the source's samples at
+    the mel rate (source_mel_len = n_samples // hop frames), target a record of `prepare_target`.  frames_per_token =
+    source_mel_len / source_content_len * length_adjust with source_content_len the reduced narrow tokens (see
+    `v2_target_frames`; 0.0 for a source without tokens), source_frames = int(source_mel_len * length_adjust)."""
+    mel_len = int(n_samples) // int(hop)
+    narrow = tokens_record["narrow_reduced"]
+    return dict(target=target, src_narrow=narrow, src_tokens=tokens_record["wide"],
+                frames_per_token=mel_len / narrow.size(1) * float(length_adjust) if narrow.size(1) else 0.0,
+                source_frames=int(mel_len * float(length_adjust)))
 
 
 @torch.inference_mode()
@@ -737,6 +797,226 @@ class V2HotPath:
                 out[b]["mel"], out[b]["wave"] = mel_b, wave_b
             self._mark("strip_vocoder")
         return out
+
+    @torch.inference_mode()
+    def convert_long_batch(self, files, n_timesteps, cfg_rates=(0.7, 0.7), *, max_context_window, hop, convert_style=True,
+                           anonymization_only=False, random_voice=False, ar_chunk_tokens=1000, overlap_frame_len=16, top_p=0.7,
+                           temperature=0.7, repetition_penalty=1.5, max_new=4001, seeds=None, exp_noise_fn=None, noise_fn=None,
+                           max_chunks=64, steps_per_run=16, return_parts=False):
+        """Whole files through the v2 chain, every chunk of every file in ONE pool: `convert_voice_with_streaming`
+        (modules/v2/vc_wrapper.py, quoted from memory: correct it here if the reference differs).  The reference loops over
+        chunks one after the other; its chunks read the same target, disjoint ranges of the source and fresh draws, never each
+        other, so here they fill the AR batch and the sampler's batch together, and one launch splices them.
+
+        files: list of dict(target = a `prepare_target` record, src_narrow (1, Ns) reduced narrow tokens, src_tokens (1, Nw)
+        wide tokens, frames_per_token float, source_frames int) -- `v2_file_record` builds one.  max_context_window: frames of
+        one sampler call, prompt included (the reference: 30 s); hop: samples per mel frame; overlap_frame_len: frames of the
+        cos^2 cross-fade.  -> list of (1, L_u) waves, views of one buffer.
+
+        convert_style=True (the style branch; reads src_narrow, frames_per_token): the reference cuts the source's narrow
+        tokens into ranges of at most max_chunk_size (1000) tokens (`v2_chunk_plan`, ar_chunk_tokens), generates each with
+        the AR model prompted by cat([target narrow, range]) and the target's wide tokens, runs CFM regulator -> sampler ->
+        vocoder per chunk and splices the waves with `_stream_wave_chunks`.  Here, with the chunks listed file-major: one
+        ragged `ar_lr` call over the AR conditions of all chunks; every chunk one request of an `ARSession(ar, steps_per_run)`
+        (`ar.max_batch_size` slots, recycled as chunks finish), submitted in plan order and drained -- the token counts are the
+        call's synchronisation point; ylen_k = v2_target_frames(frames_per_token_u, n_k); then per micro-batch of at most
+        max_chunks chunks: clamp the ids, one ragged `cfm_lr` call, `svc_chunks_gather_cond` over its output, one
+        `cfm.inference` with per-row lengths, `_strip_prompt`, `_vocode`, rows of one chunk-wave buffer; one
+        `svc_chunks_assemble` at the end.  Seams: `v2_seam_plan` (a chunk shorter than two overlaps is dropped unless it ends
+        its file).  anonymization_only: the AR condition is the range alone and the AR prompt has no target tokens; the CFM
+        still uses the target record (or random_voice).  A chunk whose AR prompt does not fit the cache is a ValueError before
+        anything is enqueued; a chunk the sampler refuses (prompt + ylen above its length limit) re-raises its error with the
+        file and the chunk: use a smaller ar_chunk_tokens.
+
+        convert_style=False (the timbre branch, the reference's default; reads src_tokens, source_frames): no AR.  One
+        ragged `cfm_lr` call over the files' wide tokens with ylens = source_frames, then the pool of
+        `HotPath.convert_long_batch` on its output (`_long_pool`): windows of max_context_window - P_u frames, the same seams.
+
+        Draws.  seeds: one integer in [0, 2^64) per file; chunk k of file u uses derive_seed(seeds[u], k) for its AR draws and
+        as its sampler-noise seed (the two Philox domains differ), so a file's audio is a function of its inputs and seed,
+        whatever shares the pool and whichever slot a chunk gets.  exp_noise_fn(u, k) -> (>= max_new, vocab) Exp(1) draws and
+        noise_fn(u, k, T) -> (1, C, T) pin the AR draws / the sampler noise of chunk k of file u (exclusive with seeds; the
+        timbre branch has no AR draws).  With neither, the AR seeds come from torch's CPU generator as in `generate_batch` and
+        the sampler noise is one torch.randn per micro-batch.
+
+        return_parts (style branch): -> (waves, parts), parts[u] a list with one dict(tokens (1, n), ylen, mel (1, C, ylen),
+        wave (1, ylen * hop), kept) per chunk of file u."""
+        U, dev = len(files), self.device
+        if seeds is not None and (exp_noise_fn is not None or noise_fn is not None):
+            raise ValueError("convert_long_batch: give seeds or exp_noise_fn / noise_fn, not both")
+        seeds = _seed_list("convert_long_batch", seeds, U)
+        if max_chunks < 1:
+            raise ValueError(f"convert_long_batch: max_chunks = {max_chunks}, at least one chunk per micro-batch is needed")
+        if not convert_style:
+            if exp_noise_fn is not None or return_parts:
+                raise ValueError("convert_long_batch: exp_noise_fn and return_parts belong to the style branch (convert_style=True)")
+            return self._convert_long_timbre(files, n_timesteps, cfg_rates, random_voice, hop, max_context_window, overlap_frame_len,
+                                             noise_fn, max_chunks, seeds)
+        v2_chunk_plan(0, ar_chunk_tokens)          # its ValueError, with or without files
+        if U == 0:
+            return ([], []) if return_parts else []
+        # (file, chunk of the file, first token, tokens, is_last), file-major
+        plan = [(u, j) + c for u, f in enumerate(files) for j, c in enumerate(v2_chunk_plan(f["src_narrow"].size(1), ar_chunk_tokens))]
+        K, ovw = len(plan), overlap_frame_len * hop
+        Lmax = self.ar.cfg["max_seq_len"]
+        for u, j, p0, n, _ in plan:
+            t = files[u]["target"]
+            rows = n + 2 if anonymization_only else t["narrow"].size(1) + n + 2 + t["tokens"].size(1)
+            if rows > Lmax:
+                raise ValueError(f"convert_long_batch: file {u}, chunk {j}: an AR prompt of {rows} rows does not fit the cache "
+                                 f"({Lmax} positions); use a smaller ar_chunk_tokens")
+        Cm = self.cfm.in_channels
+        i32 = _lib.i32_host
+        with torch.cuda.device(dev):
+            self._mark("start")
+            toks = []
+            if K:
+                # AR condition of every chunk: one ragged regulator call over cat([target narrow, range]) (not assumed position-wise)
+                narrow = []
+                for u, j, p0, n, _ in plan:
+                    chunk = files[u]["src_narrow"][:, p0:p0 + n].to(dev).long()
+                    narrow.append(chunk if anonymization_only else v2_ar_prompt(files[u]["target"]["narrow"], chunk))
+                nlen = [int(x.size(1)) for x in narrow]
+                tok_in = torch.zeros(K, max(nlen), dtype=torch.int64, device=dev)
+                for k, x in enumerate(narrow):
+                    tok_in[k, :nlen[k]] = x[0]
+                ar_cond = self.ar_lr(tok_in, in_lens=nlen)[0]
+                if seeds is not None:
+                    chunk_seeds = [derive_seed(seeds[u], j) for u, j, *_ in plan]
+                    ar_seeds = chunk_seeds
+                else:
+                    chunk_seeds = None
+                    ar_seeds = torch.randint(0, 2 ** 62, (K,), dtype=torch.int64).tolist() if exp_noise_fn is None else None
+                from .ar import ARSession
+                sess = ARSession(self.ar, steps_per_run)
+                no_target = torch.zeros(1, 0, dtype=torch.int64, device=dev)
+                try:
+                    for k, (u, j, *_) in enumerate(plan):
+                        draws = dict(exp_noise=exp_noise_fn(u, j)) if exp_noise_fn is not None else dict(seed=ar_seeds[k])
+                        sess.submit(ar_cond[k:k + 1, :nlen[k]], no_target if anonymization_only else files[u]["target"]["tokens"],
+                                    max_new=max_new, top_p=top_p, temperature=temperature, repetition_penalty=repetition_penalty, **draws)
+                    done = dict(sess.drain())          # tickets count from 0 in submit order: ticket k is chunk k
+                finally:
+                    sess.close()
+                toks = [done[k] for k in range(K)]
+            self._mark("ar")
+            # ---- the token counts are host integers from here on: everything below is enqueued from them
+            ylens = [v2_target_frames(files[u]["frames_per_token"], toks[k].size(1)) for k, (u, *_) in enumerate(plan)]
+            seam = v2_seam_plan([c[0] for c in plan], [y * hop for y in ylens], [c[4] for c in plan], ovw, U)
+            out_lens = seam["out_lens"]
+            out = torch.empty(sum(out_lens), device=dev, dtype=torch.float32)
+            offs = [sum(out_lens[:u]) for u in range(U)]
+            result = [out[o:o + n][None, :] for o, n in zip(offs, out_lens)]
+            parts = [[] for _ in range(U)]
+            if return_parts:
+                for k, (u, *_) in enumerate(plan):
+                    parts[u].append(dict(tokens=toks[k], ylen=ylens[k], mel=torch.zeros(1, Cm, 0, device=dev),
+                                         wave=torch.zeros(1, 0, device=dev), kept=seam["kept"][k]))
+            live = [k for k in range(K) if ylens[k] > 0]
+            if live:
+                st = self._stack_targets([f["target"] for f in files])
+                P, Pmax, pc_all = st["P"], st["Pmax"], st["prompt_condition"]
+                Dc = pc_all.size(2)
+                if U > 1:
+                    idx = torch.tensor([plan[k][0] for k in live], device=dev)
+                    mel_chunks, style_chunks = st["mel"].index_select(0, idx), st["style"].index_select(0, idx)
+                else:
+                    mel_chunks, style_chunks = st["mel"].expand(len(live), -1, -1), st["style"].expand(len(live), -1)
+                stride = max(ylens) * hop
+                waves = torch.empty(len(live), stride, device=dev, dtype=torch.float32)     # row i: the wave of chunk live[i]
+                top = self.cfm_lr.cfg["codebook_size"] - 1
+                for m0 in range(0, len(live), max_chunks):
+                    ks = live[m0:m0 + max_chunks]
+                    n = len(ks)
+                    S, nl = [ylens[k] for k in ks], [toks[k].size(1) for k in ks]
+                    Pk = [P[plan[k][0]] for k in ks]
+                    x_lens = [p + s for p, s in zip(Pk, S)]
+                    T, Smax = max(x_lens), max(S)
+                    tok = torch.zeros(n, max(nl), dtype=torch.int64, device=dev)
+                    for i, k in enumerate(ks):
+                        tok[i, :nl[i]] = toks[k][0]
+                    tok.clamp_(max=top)          # an id above the codebook (the AR vocabulary's EOS) is no row of the embedding
+                    cond = self.cfm_lr(tok, ylens=torch.LongTensor(S), in_lens=nl)[0]           # (n, Smax, Dc)
+                    mu = torch.empty(n, T, Dc, device=dev)
+                    _lib.check(_lib.lib().svc_chunks_gather_cond(_lib.ptr(pc_all), i32(P), U, Pmax, _lib.ptr(cond), n * Smax,
+                                                                 i32([plan[k][0] for k in ks]), i32([i * Smax for i in range(n)]), i32(S),
+                                                                 n, Dc, T, _lib.ptr(mu), _lib.stream_ptr()))
+                    self._mark("lr_assembly")
+                    z = None
+                    if noise_fn is not None:
+                        z = torch.zeros(n, Cm, T, device=dev)
+                        for i, k in enumerate(ks):
+                            z[i, :, :x_lens[i]] = _lib.f32c(noise_fn(plan[k][0], plan[k][1], x_lens[i]), dev)[0]
+                    mb_seeds = [chunk_seeds[k] for k in ks] if chunk_seeds is not None else None
+                    try:
+                        mel = self.cfm.inference(mu, x_lens, mel_chunks[m0:m0 + n], style_chunks[m0:m0 + n], None, n_timesteps,
+                                                 inference_cfg_rate=list(cfg_rates), random_voice=random_voice, z=z, prompt_lens=Pk,
+                                                 **_cfm_seeds(mb_seeds))
+                    except RuntimeError as e:
+                        i = max(range(n), key=lambda i: x_lens[i])
+                        raise RuntimeError(f"convert_long_batch: file {plan[ks[i]][0]}, chunk {plan[ks[i]][1]}: the sampler refused "
+                                           f"{x_lens[i]} frames (prompt {Pk[i]} + {S[i]} generated): {e}; use a smaller ar_chunk_tokens") from e
+                    self._mark("cfm")
+                    vc = _strip_prompt(mel, Pk, x_lens, Smax)
+                    calls = _vocode(self.vocoder, vc, S, self.ragged_vocoder, "convert_long_batch", hop=hop)
+                    for call in calls:
+                        r = 0
+                        for a, b in call.runs:       # rows of a call -> rows of the chunk wave buffer (slices: no synchronisation)
+                            waves[m0 + a:m0 + b, :call.frames * hop].copy_(call.wave[r:r + b - a])
+                            r += b - a
+                    if return_parts:
+                        for i, (k, (mel_k, _)) in enumerate(zip(ks, _row_views(vc, S, calls))):
+                            part = parts[plan[k][0]][plan[k][1]]
+                            part["mel"], part["wave"] = mel_k, waves[m0 + i:m0 + i + 1, :S[i] * hop]
+                    self._mark("strip_vocoder")
+                rows = [i for i, k in enumerate(live) if seam["kept"][k]]
+                if rows:
+                    kept_waves = waves if len(rows) == len(live) else torch.cat([waves[a:b] for a, b in _index_runs(rows)])
+                    kept = [live[i] for i in rows]
+                    fade_in, fade_out = (torch.from_numpy(w).to(dev) for w in _cos2_windows(ovw))
+                    _lib.check(_lib.lib().svc_chunks_assemble(_lib.ptr(kept_waves), C.c_longlong(stride), i32([ylens[k] * hop for k in kept]),
+                                                              i32([int(seam["first"][k]) for k in kept]), i32([int(seam["last"][k]) for k in kept]),
+                                                              len(kept), _lib.ptr(fade_in), _lib.ptr(fade_out), ovw, _lib.ptr(out),
+                                                              C.c_longlong(out.numel()), _lib.stream_ptr()))
+                self._mark("assemble")
+            torch.cuda.current_stream(dev).synchronize()
+        return (result, parts) if return_parts else result
+
+    def _convert_long_timbre(self, files, n_timesteps, cfg_rates, random_voice, hop, max_context_window, overlap_frame_len, noise_fn,
+                             max_chunks, seeds):
+        """The timbre branch of `convert_long_batch`: the CFM regulator over the files' wide tokens, then `_long_pool`."""
+        U, dev = len(files), self.device
+        if U == 0:
+            return []
+        frames = [int(f["source_frames"]) if f["src_tokens"].size(1) else 0 for f in files]
+        live = [u for u in range(U) if frames[u] > 0]
+        with torch.cuda.device(dev):
+            self._mark("start")
+            if live:
+                nw = [int(files[u]["src_tokens"].size(1)) for u in live]
+                tok = torch.zeros(len(live), max(nw), dtype=torch.int64, device=dev)
+                for i, u in enumerate(live):
+                    tok[i, :nw[i]] = files[u]["src_tokens"][0]
+                cond = self.cfm_lr(tok, ylens=torch.LongTensor([frames[u] for u in live]), in_lens=nw)[0]
+            self._mark("lr_assembly")
+            none = torch.zeros(1, 0, self.cfm_lr.cfg["out_channels"], device=dev)
+            conds = [none] * U
+            for i, u in enumerate(live):
+                conds[u] = cond[i:i + 1, :frames[u]]
+            utterances = [(conds[u], f["target"]["prompt_condition"], f["target"]["mel"], f["target"]["style"]) for u, f in enumerate(files)]
+            pool_noise = None
+            if noise_fn is not None:          # the pool asks per chunk in plan order: give each call its (file, chunk)
+                order = long_batch_plan(frames, [f["target"]["P"] for f in files], max_context_window, overlap_frame_len, hop, max_chunks)
+                first_of, uk = {}, []
+                for k, c in enumerate(order["chunks"]):
+                    uk.append((c[0], k - first_of.setdefault(c[0], k)))
+                it = iter(uk)
+                pool_noise = lambda T: noise_fn(*next(it), T)          # noqa: E731
+            result = _long_pool(self.cfm, self.vocoder, utterances, n_timesteps, list(cfg_rates), hop, max_context_window, overlap_frame_len,
+                                pool_noise, None, max_chunks, self.ragged_vocoder, seeds, lambda s: _vocoder_seeds(self.vocoder, s),
+                                dict(random_voice=True) if random_voice else None)
+            self._mark("pool")
+        return result
 
 
 # ----------------------------------------------------------------------------------------- real-time sessions
