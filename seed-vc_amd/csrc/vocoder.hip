@@ -19,6 +19,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <functional>
 #include <vector>
 
 #include "conv_util.h"
@@ -41,33 +42,29 @@ __global__ void snake_params_kernel(const float* alpha, const float* beta, float
     inv_b[c] = 1.0f / (be + 1e-9f);
 }
 
-// (B, C, S) fp32 -> channels-last [B][S][ld] in fp32 or fp16, pad channels zero
-template <typename OutT>
-__global__ void mel_to_cl_kernel(const float* __restrict__ mel, OutT* __restrict__ dst, OutT* __restrict__ dst_lo, int B, int C,
-                                 int S, int ld) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long)B * S * ld) return;
-    const int c = (int)(i % ld);
-    const long bs = i / ld;
-    const int s = (int)(bs % S), b = (int)(bs / S);
-    const float v = c < C ? mel[((long)b * C + c) * S + s] : 0.f;
-    const OutT h = (OutT)v;
-    dst[i] = h;
-    if (dst_lo) dst_lo[i] = (OutT)(v - (float)h);
-}
+// How the rows of a micro-batch map onto the caller's batch, for the pointwise stages that serve the plain and the ragged call
+// alike.  Plain call (the default): row j is utterance j of the pointers handed in and all S frames are valid.  Ragged call: row
+// j is utterance src[j] of the caller's whole tensors and ends after len[j] frames.
+struct RowMap {
+    const int* src = nullptr;   // device [B], or null: row j is utterance j
+    const int* len = nullptr;   // device [B] valid frames, or null: all S
+    int S_in = 0;               // frames per utterance of the caller's tensors (their row stride); S in a plain call
+    __device__ __forceinline__ int utt(int b) const { return src ? src[b] : b; }
+    __device__ __forceinline__ int frames(int b, int S) const { return len ? len[b] : S; }
+};
 
-// Ragged batch: row j of the micro-batch is utterance src[j] of the caller's (B, C, S_in) mel, cut to S frames; frames at and
-// above lens[j] become zero rows by selection (they may hold NaN, and 0 * NaN is NaN) and are never loaded
+// (.., C, S_in) fp32 -> channels-last [B][S][ld] in fp32 or fp16, pad channels zero.  Frames at and above the row's end become zero
+// rows by selection (they may hold NaN, and 0 * NaN is NaN) and are never loaded
 template <typename OutT>
-__global__ void mel_to_cl_ragged_kernel(const float* __restrict__ mel, OutT* __restrict__ dst, OutT* __restrict__ dst_lo,
-                                        const int* __restrict__ src, const int* __restrict__ lens, int B, int C, int S_in, int S, int ld) {
+__global__ void mel_to_cl_kernel(const float* __restrict__ mel, OutT* __restrict__ dst, OutT* __restrict__ dst_lo, RowMap rm, int B,
+                                 int C, int S, int ld) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long)B * S * ld) return;
     const int c = (int)(i % ld);
     const long bs = i / ld;
     const int s = (int)(bs % S), b = (int)(bs / S);
     float v = 0.f;
-    if (c < C && s < lens[b]) v = mel[((long)src[b] * C + c) * S_in + s];
+    if (c < C && s < rm.frames(b, S)) v = mel[((long)rm.utt(b) * C + c) * rm.S_in + s];
     const OutT h = (OutT)v;
     dst[i] = h;
     if (dst_lo) dst_lo[i] = (OutT)(v - (float)h);
@@ -125,16 +122,20 @@ __global__ void hift_phase_prefix_kernel(const float* __restrict__ f0, double* _
 // The randn_like draw of one sample (generator.py:222), harmonic by harmonic in ascending order: loaded from the caller's
 // tensor ...
 struct HiftNoiseLoad {
+    typedef const float* Src;       // the caller's [..][NH][ld] draws
     const float* __restrict__ p;    // the utterance's [NH][ld] rows, already at sample n
     long ld;
+    __device__ __forceinline__ HiftNoiseLoad(Src noise, int u, int NH, long n, long ld_) : p(noise + (long)u * NH * ld_ + n), ld(ld_) {}
     __device__ __forceinline__ float operator()(int h) { return p[(long)h * ld]; }
 };
 // ... or drawn here from the utterance's seed (noise.h, domain NOISE_HIFT_SOURCE: row = harmonic, pos = sample; one Philox call
 // per four harmonics, three for NH = 9).  No [NH][S * up] tensor exists on this path.
 struct HiftNoiseDraw {
+    typedef const unsigned long long* Src;      // the caller's [..] seeds
     unsigned long long seed;
     unsigned pos;
     float n[4];
+    __device__ __forceinline__ HiftNoiseDraw(Src seeds, int u, int, long n_, long) : seed(seeds[u]), pos((unsigned)n_), n{} {}
     __device__ __forceinline__ float operator()(int h) {
         if ((h & 3) == 0) noise_normal4(seed, NOISE_HIFT_SOURCE, (unsigned)h >> 2, pos, n);
         return (h & 3) == 0 ? n[0] : (h & 3) == 1 ? n[1] : (h & 3) == 2 ? n[2] : n[3];
@@ -166,43 +167,15 @@ __device__ __forceinline__ float hift_source_sample(float f0v, const double* __r
     return tanhf(acc);
 }
 
+// Row j of the micro-batch ([B][S] frames) is utterance u = rm.utt(j) of phase0 [..][NH] and of the noise source: draws
+// [..][NH][S_in * up], of which it uses the first frames * up samples of its rows (the draws of the run alone), or seeds [..], from
+// which it draws at its own sample index -- the draws of the run alone whatever the row, the padding and the micro-batch.  f0 and
+// prefix are the micro-batch's own [B][S] / [B][NH][S].  Samples past the row's end are written as zero and nothing is read for them.
+template <typename Noise>
 __global__ void hift_source_kernel(const float* __restrict__ f0, const double* __restrict__ prefix, const float* __restrict__ phase0,
-                                   const float* __restrict__ noise, const float* __restrict__ lin_w, const float* __restrict__ lin_b,
-                                   float* __restrict__ s_out, int B, int S, int NH, int up, float sr, float sine_amp, float noise_std,
-                                   float voiced_thr) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long Lw = (long)S * up;
-    if (i >= B * Lw) return;
-    const int b = (int)(i / Lw);
-    const long n = i - (long)b * Lw;
-    const int f = (int)(n / up), r = (int)(n - (long)f * up);
-    s_out[i] = hift_source_sample(f0[(long)b * S + f], prefix + (long)b * NH * S, phase0 + (long)b * NH,
-                                  HiftNoiseLoad{noise + (long)b * NH * Lw + n, Lw}, lin_w, lin_b, S, NH, f, r, sr, sine_amp, noise_std,
-                                  voiced_thr);
-}
-
-// The same with the noise of utterance b drawn from seeds[b] (svc_hift_forward_seeded)
-__global__ void hift_source_seeded_kernel(const float* __restrict__ f0, const double* __restrict__ prefix, const float* __restrict__ phase0,
-                                          const unsigned long long* __restrict__ seeds, const float* __restrict__ lin_w,
-                                          const float* __restrict__ lin_b, float* __restrict__ s_out, int B, int S, int NH, int up, float sr,
-                                          float sine_amp, float noise_std, float voiced_thr) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long Lw = (long)S * up;
-    if (i >= B * Lw) return;
-    const int b = (int)(i / Lw);
-    const long n = i - (long)b * Lw;
-    const int f = (int)(n / up), r = (int)(n - (long)f * up);
-    s_out[i] = hift_source_sample(f0[(long)b * S + f], prefix + (long)b * NH * S, phase0 + (long)b * NH,
-                                  HiftNoiseDraw{seeds[b], (unsigned)n, {}}, lin_w, lin_b, S, NH, f, r, sr, sine_amp, noise_std, voiced_thr);
-}
-
-// Ragged batch: row j of the micro-batch ([B][S] frames) is utterance src[j] of the caller's phase0 [..][NH] and noise
-// [..][NH][S_in * up]; it uses the first lens[j] * up samples of its noise rows (the draws of the run alone).  f0 and prefix are the
-// micro-batch's own [B][S] / [B][NH][S].  Samples at and above lens[j] * up are written as zero and nothing is read for them.
-__global__ void hift_source_ragged_kernel(const float* __restrict__ f0, const double* __restrict__ prefix, const float* __restrict__ phase0,
-                                          const float* __restrict__ noise, const float* __restrict__ lin_w, const float* __restrict__ lin_b,
-                                          float* __restrict__ s_out, const int* __restrict__ src, const int* __restrict__ lens, int B, int S,
-                                          int S_in, int NH, int up, float sr, float sine_amp, float noise_std, float voiced_thr) {
+                                   typename Noise::Src noise, const float* __restrict__ lin_w, const float* __restrict__ lin_b,
+                                   float* __restrict__ s_out, RowMap rm, int B, int S, int NH, int up, float sr, float sine_amp,
+                                   float noise_std, float voiced_thr) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const long Lw = (long)S * up;
     if (i >= B * Lw) return;
@@ -210,33 +183,11 @@ __global__ void hift_source_ragged_kernel(const float* __restrict__ f0, const do
     const long n = i - (long)b * Lw;
     const int f = (int)(n / up), r = (int)(n - (long)f * up);
     float v = 0.f;
-    if (f < lens[b]) {
-        const long Lw_in = (long)S_in * up;
-        v = hift_source_sample(f0[(long)b * S + f], prefix + (long)b * NH * S, phase0 + (long)src[b] * NH,
-                               HiftNoiseLoad{noise + (long)src[b] * NH * Lw_in + n, Lw_in}, lin_w, lin_b, S, NH, f, r, sr, sine_amp,
-                               noise_std, voiced_thr);
+    if (f < rm.frames(b, S)) {
+        const int u = rm.utt(b);
+        v = hift_source_sample(f0[(long)b * S + f], prefix + (long)b * NH * S, phase0 + (long)u * NH,
+                               Noise(noise, u, NH, n, (long)rm.S_in * up), lin_w, lin_b, S, NH, f, r, sr, sine_amp, noise_std, voiced_thr);
     }
-    s_out[i] = v;
-}
-
-// Ragged and seeded: row j draws from seeds[src[j]], the seed of the caller's utterance, at its own sample index -- the draws of
-// the run alone whatever the row, the padding and the micro-batch
-__global__ void hift_source_ragged_seeded_kernel(const float* __restrict__ f0, const double* __restrict__ prefix,
-                                                 const float* __restrict__ phase0, const unsigned long long* __restrict__ seeds,
-                                                 const float* __restrict__ lin_w, const float* __restrict__ lin_b,
-                                                 float* __restrict__ s_out, const int* __restrict__ src, const int* __restrict__ lens, int B,
-                                                 int S, int NH, int up, float sr, float sine_amp, float noise_std, float voiced_thr) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long Lw = (long)S * up;
-    if (i >= B * Lw) return;
-    const int b = (int)(i / Lw);
-    const long n = i - (long)b * Lw;
-    const int f = (int)(n / up), r = (int)(n - (long)f * up);
-    float v = 0.f;
-    if (f < lens[b])
-        v = hift_source_sample(f0[(long)b * S + f], prefix + (long)b * NH * S, phase0 + (long)src[b] * NH,
-                               HiftNoiseDraw{seeds[src[b]], (unsigned)n, {}}, lin_w, lin_b, S, NH, f, r, sr, sine_amp, noise_std,
-                               voiced_thr);
     s_out[i] = v;
 }
 
@@ -276,22 +227,16 @@ __device__ __forceinline__ void hift_stft_frame(const float* __restrict__ s, flo
     for (int c = 18; c < ld; ++c) o[c] = 0.f;
 }
 
-__global__ void hift_stft_kernel(const float* __restrict__ s, float* __restrict__ out, int B, long Lw, int F, int ld) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long)B * F) return;
-    const int b = (int)(i / F), fr = (int)(i - (long)b * F);
-    hift_stft_frame(s + (long)b * Lw, out + i * ld, Lw, fr, ld);
-}
-
-// Ragged batch: utterance b holds lw[b] samples of its Lw-sample row and gets nf[b] = lw[b] / 4 + 1 frames, reflected at ITS last
-// sample; frame rows at and above nf[b] are written as zero (the source_downs convs read them as their zero padding)
-__global__ void hift_stft_ragged_kernel(const float* __restrict__ s, float* __restrict__ out, const int* __restrict__ lw,
-                                        const int* __restrict__ nf, int B, long Lw, int F, int ld) {
+// lw, nf (device [B], ragged batch; null: Lw samples and F frames each): utterance b holds lw[b] samples of its Lw-sample row and
+// gets nf[b] = lw[b] / 4 + 1 frames, reflected at ITS last sample; frame rows at and above nf[b] are written as zero (the
+// source_downs convs read them as their zero padding)
+__global__ void hift_stft_kernel(const float* __restrict__ s, float* __restrict__ out, const int* __restrict__ lw,
+                                 const int* __restrict__ nf, int B, long Lw, int F, int ld) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long)B * F) return;
     const int b = (int)(i / F), fr = (int)(i - (long)b * F);
     float* o = out + i * ld;
-    if (fr < nf[b]) hift_stft_frame(s + (long)b * Lw, o, lw[b], fr, ld);
+    if (fr < (nf ? nf[b] : F)) hift_stft_frame(s + (long)b * Lw, o, lw ? lw[b] : Lw, fr, ld);
     else for (int c = 0; c < ld; ++c) o[c] = 0.f;
 }
 
@@ -340,23 +285,16 @@ __device__ __forceinline__ float hift_ola_sample(const float* __restrict__ frame
     return fminf(fmaxf(v, -limit), limit);
 }
 
-__global__ void hift_ola_kernel(const float* __restrict__ frames, float* __restrict__ out, int B, int F, long Lw, float limit) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long)B * Lw) return;
-    const int b = (int)(i / Lw);
-    const long n = i - (long)b * Lw;
-    out[i] = hift_ola_sample(frames + (long)b * F * 16, F, n, limit);
-}
-
-// Ragged batch, last step: utterance j of the micro-batch overlap-adds its own nf[j] frames (of the F-frame row) into row src[j] of
-// the caller's [..][Lw_out] output; samples at and above lw[j] are written as zero and no frame is read for them
-__global__ void hift_ola_ragged_kernel(const float* __restrict__ frames, float* __restrict__ out, const int* __restrict__ src,
-                                       const int* __restrict__ lw, const int* __restrict__ nf, int B, int F, long Lw_out, float limit) {
+// Last step: row j of the micro-batch overlap-adds its frames (of the F-frame row) into row rm.utt(j) of the [..][Lw_out] output,
+// Lw_out = S_in * up.  lw, nf (device [B], ragged batch; null: Lw_out samples from F frames each): samples at and above lw[j] are
+// written as zero and no frame is read for them; the others come from the utterance's own nf[j] frames
+__global__ void hift_ola_kernel(const float* __restrict__ frames, float* __restrict__ out, RowMap rm, const int* __restrict__ lw,
+                                const int* __restrict__ nf, int B, int F, long Lw_out, float limit) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long)B * Lw_out) return;
     const int b = (int)(i / Lw_out);
     const long n = i - (long)b * Lw_out;
-    out[(long)src[b] * Lw_out + n] = n < lw[b] ? hift_ola_sample(frames + (long)b * F * 16, nf[b], n, limit) : 0.f;
+    out[(long)rm.utt(b) * Lw_out + n] = !lw || n < lw[b] ? hift_ola_sample(frames + (long)b * F * 16, nf ? nf[b] : F, n, limit) : 0.f;
 }
 
 __global__ void abs_copy_kernel(const float* __restrict__ src, long ld, float* __restrict__ dst, long n) {
@@ -383,26 +321,14 @@ int ew_cl(const float* x, ActOut y, int vd, long rows, int C, int ld, int mode, 
     return 0;
 }
 
-int mel_to_cl(const float* mel, ActOut dst, int vd, int B, int C, int S, int ld, hipStream_t st) {
+int mel_to_cl(const float* mel, ActOut dst, int vd, RowMap rm, int B, int C, int S, int ld, hipStream_t st) {
     const long n = (long)B * S * ld;
     if (vd != 1)
         hipLaunchKernelGGL(mel_to_cl_kernel<half_t>, dim3(cdiv(n, 256)), dim3(256), 0, st, mel, (half_t*)dst.hi,
-                           is_split(vd) ? (half_t*)dst.lo : nullptr, B, C, S, ld);
+                           is_split(vd) ? (half_t*)dst.lo : nullptr, rm, B, C, S, ld);
     else
-        hipLaunchKernelGGL(mel_to_cl_kernel<float>, dim3(cdiv(n, 256)), dim3(256), 0, st, mel, (float*)dst.hi, (float*)nullptr, B, C, S, ld);
-    SVC_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-
-int mel_to_cl_ragged(const float* mel, ActOut dst, int vd, const int* src, const int* lens, int B, int C, int S_in, int S, int ld,
-                     hipStream_t st) {
-    const long n = (long)B * S * ld;
-    if (vd != 1)
-        hipLaunchKernelGGL(mel_to_cl_ragged_kernel<half_t>, dim3(cdiv(n, 256)), dim3(256), 0, st, mel, (half_t*)dst.hi,
-                           is_split(vd) ? (half_t*)dst.lo : nullptr, src, lens, B, C, S_in, S, ld);
-    else
-        hipLaunchKernelGGL(mel_to_cl_ragged_kernel<float>, dim3(cdiv(n, 256)), dim3(256), 0, st, mel, (float*)dst.hi, (float*)nullptr,
-                           src, lens, B, C, S_in, S, ld);
+        hipLaunchKernelGGL(mel_to_cl_kernel<float>, dim3(cdiv(n, 256)), dim3(256), 0, st, mel, (float*)dst.hi, (float*)nullptr, rm, B, C, S,
+                           ld);
     SVC_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -441,13 +367,101 @@ struct ResBlockW {
 // One micro-batch of a ragged call (device pointers into the call's length table): row j is utterance src[j] of the caller's
 // batch and holds len[i][j] valid rows after i up-sampling stages
 struct RaggedMB {
+    int nb = 0, S = 0;      // its rows, and the frames of the longest of them (row 0)
     const int* src = nullptr;
     const int* len[9] = {};
     int S_in = 0;           // frames per utterance of the caller's mel (its row stride)
-    // HiFT only: waveform samples per row (device) and the rows' frame counts on the host (len[0] again)
-    const int* lw = nullptr;
-    const int* h_len0 = nullptr;
+    const int* lw = nullptr;        // HiFT only: waveform samples per row (device)
+    const int* h_len0 = nullptr;    // the rows' frame counts on the host (len[0] again)
+    RowMap rows() const { return RowMap{src, len[0], S_in}; }
 };
+
+// The batch plan of a ragged call, one for both vocoders.  Longest first, micro-batch by micro-batch, each padded to its own
+// longest member only: a batch padded to the longest utterance of all would compute B * Smax rows.  The stable sort keeps the
+// order of equal lengths, so a batch of equal lengths runs exactly as the plain call runs it.
+struct RaggedPlan {
+    PinnedRing staging;     // pinned slots for what the host builds per call: the length table (and a seeded call's seeds)
+    Arena tab;              // the table's device copy
+    int* d_tab = nullptr;
+    size_t tab_cap = 0;
+    std::vector<int> first;             // the first row of each micro-batch, then B
+    const int* h_tab = nullptr;         // this call's table in its pinned slot
+    int nu = 0, n_arr = 0, S_in = 0;
+    bool has_lw = false;
+    int nb_max = 0, S_max = 0;          // the largest micro-batch and the longest utterance: one workspace reservation per call
+
+    // lens: HOST [B].  Comes first in a ragged call: before the handle is touched or anything is launched
+    static int check(const char* who, const int32_t* lens, int B, int S) {
+        for (int b = 0; b < B; ++b) SVC_REQUIRE(lens[b] >= 0 && lens[b] <= S, std::string(who) + ": lens out of range");
+        return 0;
+    }
+    // A micro-batch ends after `microbatch` members (0: 32) or where cls(length) changes (cls empty: nowhere else).
+    // rows_after(i, l): valid rows of an utterance of l frames after i of the nu up-sampling stages.  lw_up > 0: a row's
+    // lw = l * lw_up waveform samples as well.
+    // Length table, per micro-batch of nb rows: src[nb], the valid rows after 0 .. nu stages ([nb] each), lw[nb].  Built in a
+    // pinned slot and copied once: the caller's array is consumed here and nothing waits for the stream.
+    int build(const int32_t* lens, int B, int S, int microbatch, int nu_, const std::function<long(int, long)>& rows_after,
+              const std::function<int(long)>& cls, int lw_up, hipStream_t st) {
+        std::vector<int> order(B);
+        for (int b = 0; b < B; ++b) order[b] = b;
+        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return lens[a] > lens[b]; });
+        const int mb = microbatch > 0 ? microbatch : 32;
+        first.clear();
+        for (int b = 0; b < B; ++b)
+            if (b == 0 || b - first.back() == mb || (cls && cls(lens[order[b]]) != cls(lens[order[first.back()]]))) first.push_back(b);
+        first.push_back(B);
+        nu = nu_; S_in = S; has_lw = lw_up > 0;
+        n_arr = nu + 2 + (has_lw ? 1 : 0);
+        const size_t n_tab = (size_t)B * n_arr;
+        if (n_tab > tab_cap) {
+            SVC_CHECK_HIP(hipStreamSynchronize(st));
+            tab.release();
+            d_tab = tab.alloc_n<int>(n_tab, st);
+            if (!d_tab) { tab_cap = 0; return 1; }
+            tab_cap = n_tab;
+        }
+        int* h = reinterpret_cast<int*>(staging.acquire(n_tab * sizeof(int)));
+        if (!h) return 1;
+        h_tab = h;
+        nb_max = 0;
+        S_max = lens[order[0]];
+        for (int k = 0; k < count(); ++k) {
+            const int b0 = first[k], nb = first[k + 1] - b0;
+            nb_max = std::max(nb_max, nb);
+            int* row = h + (size_t)b0 * n_arr;
+            for (int j = 0; j < nb; ++j) {
+                const long l = lens[order[b0 + j]];
+                row[j] = order[b0 + j];
+                for (int i = 0; i <= nu; ++i) row[(size_t)(i + 1) * nb + j] = (int)rows_after(i, l);
+                if (has_lw) row[(size_t)(nu + 2) * nb + j] = (int)(l * lw_up);
+            }
+        }
+        SVC_CHECK_HIP(hipMemcpyAsync(d_tab, h, n_tab * sizeof(int), hipMemcpyHostToDevice, st));
+        return staging.commit(st);
+    }
+    int count() const { return (int)first.size() - 1; }
+    RaggedMB mb(int k) const {
+        const int b0 = first[k];
+        RaggedMB rg;
+        rg.nb = first[k + 1] - b0;
+        const int* row = d_tab + (size_t)b0 * n_arr;
+        rg.src = row;
+        for (int i = 0; i <= nu; ++i) rg.len[i] = row + (size_t)(i + 1) * rg.nb;
+        if (has_lw) rg.lw = row + (size_t)(nu + 2) * rg.nb;
+        rg.h_len0 = h_tab + (size_t)b0 * n_arr + rg.nb;
+        rg.S = rg.h_len0[0];
+        rg.S_in = S_in;
+        return rg;
+    }
+};
+
+// A micro-batch of nothing but empty utterances (they sort last): rows src[j] of the caller's [..][row_len] output are all tail
+int zero_rows(const RaggedMB& rg, float* out, long row_len, hipStream_t st) {
+    hipLaunchKernelGGL(wave_scatter_kernel, dim3(cdiv((long)rg.nb * row_len, 256)), dim3(256), 0, st, (const float*)nullptr, out, rg.src,
+                       rg.len[0], rg.nb, 0L, row_len);
+    SVC_CHECK_HIP(hipGetLastError());
+    return 0;
+}
 
 }  // namespace
 
@@ -465,11 +479,7 @@ struct svc_bigvgan {
     ActOut mel_a, act_a;
     float *x, *y, *t, *xsum;
     int microbatch = 0;
-    // ragged calls: pinned staging for the host-built length table and its device copy
-    PinnedRing staging;
-    Arena tab;
-    int* d_tab = nullptr;
-    size_t tab_cap = 0;
+    RaggedPlan plan;    // ragged calls
 
     int reserve(int B, int S, hipStream_t st);
     // rg == null: B utterances of S frames each.  rg != null: micro-batch of a ragged call, `mel` / `out` are the caller's
@@ -582,9 +592,8 @@ int svc_bigvgan::reserve(int B, int S, hipStream_t st) {
 // are unchanged; what they write past lens[b] (x, y, t, xsum) is read only by pointwise ops and by the masked producers.
 int svc_bigvgan::run(const float* mel, int B, int S, float* out, hipStream_t st, const RaggedMB* rg) {
     const int vd = dtype;
-    if (rg) {
-        if (mel_to_cl_ragged(mel, mel_a, vd, rg->src, rg->len[0], B, cfg.num_mels, rg->S_in, S, cpad(cfg.num_mels, vd), st)) return 1;
-    } else if (mel_to_cl(mel, mel_a, vd, B, cfg.num_mels, S, cpad(cfg.num_mels, vd), st)) return 1;
+    const RowMap rm = rg ? rg->rows() : RowMap{nullptr, nullptr, S};
+    if (mel_to_cl(mel, mel_a, vd, rm, B, cfg.num_mels, S, cpad(cfg.num_mels, vd), st)) return 1;
     int ch = cfg.upsample_initial_channel;
     long L = S;
     {
@@ -671,11 +680,7 @@ struct svc_hift {
     void *f0_a, *f0_b;
     float *f0_buf, *s_buf, *stft32, *x, *y, *t, *xsum, *si, *post, *frames;
     double* prefix;
-    // ragged calls: pinned staging for the host-built length table and its device copy
-    PinnedRing staging;
-    Arena tab;
-    int* d_tab = nullptr;
-    size_t tab_cap = 0;
+    RaggedPlan plan;    // ragged calls
     // seeded calls: the call's seeds [B] and the phase0 [B][NH] drawn from them (the only draws that are ever stored)
     int device = -1;
     Arena seed_ar;
@@ -768,7 +773,8 @@ int svc_hift::reserve(int B, int S, hipStream_t st) {
 int svc_hift::run(const float* mel, const float* f0_in, const float* phase0, const float* noise, int B, int S, float* out,
                   float* f0_out, hipStream_t st, const RaggedMB* rg, const unsigned long long* seeds) {
     const int vd = dtype;
-    const int* len0 = rg ? rg->len[0] : nullptr;
+    const RowMap rm = rg ? rg->rows() : RowMap{nullptr, nullptr, S};
+    const int* len0 = rm.len;
     const int NH = cfg.nb_harmonics + 1;
     const long Lw = (long)S * up_total;
     const int F = (int)(Lw / cfg.istft_hop) + 1;
@@ -779,9 +785,7 @@ int svc_hift::run(const float* mel, const float* f0_in, const float* phase0, con
         const int fc = cfg.f0_cond_channels, fld = cpad(fc, 1);
         ActOut f0in;
         f0in.hi = f0_a;
-        if (rg) {
-            if (mel_to_cl_ragged(mel, f0in, 1, rg->src, len0, B, cfg.in_channels, rg->S_in, S, cpad(cfg.in_channels, 1), st)) return 1;
-        } else if (mel_to_cl(mel, f0in, 1, B, cfg.in_channels, S, cpad(cfg.in_channels, 1), st)) return 1;
+        if (mel_to_cl(mel, f0in, 1, rm, B, cfg.in_channels, S, cpad(cfg.in_channels, 1), st)) return 1;
         void* src = f0_a;
         void* dst = f0_b;
         for (int i = 0; i < 5; ++i) {
@@ -815,30 +819,15 @@ int svc_hift::run(const float* mel, const float* f0_in, const float* phase0, con
     SVC_CHECK_HIP(hipGetLastError());
     const int ld18 = cpad(cfg.istft_n_fft + 2, dtype);
     const int* len_f = rg ? rg->len[cfg.num_upsamples] : nullptr;      // frames of the STFT / iSTFT = rows of the last stage
-    if (rg) {
-        if (seeds)
-            hipLaunchKernelGGL(hift_source_ragged_seeded_kernel, dim3(cdiv((long)B * Lw, 256)), dim3(256), 0, st, f0, prefix, phase0,
-                               seeds, src_lin_w, src_lin_b, s_buf, rg->src, len0, B, S, NH, up_total, (float)cfg.sampling_rate,
-                               cfg.nsf_alpha, cfg.nsf_sigma, cfg.nsf_voiced_threshold);
-        else
-            hipLaunchKernelGGL(hift_source_ragged_kernel, dim3(cdiv((long)B * Lw, 256)), dim3(256), 0, st, f0, prefix, phase0, noise,
-                               src_lin_w, src_lin_b, s_buf, rg->src, len0, B, S, rg->S_in, NH, up_total, (float)cfg.sampling_rate,
-                               cfg.nsf_alpha, cfg.nsf_sigma, cfg.nsf_voiced_threshold);
-        SVC_CHECK_HIP(hipGetLastError());
-        hipLaunchKernelGGL(hift_stft_ragged_kernel, dim3(cdiv((long)B * F, 256)), dim3(256), 0, st, s_buf, stft32, rg->lw, len_f, B, Lw,
-                           F, ld18);
-    } else {
-        if (seeds)
-            hipLaunchKernelGGL(hift_source_seeded_kernel, dim3(cdiv((long)B * Lw, 256)), dim3(256), 0, st, f0, prefix, phase0, seeds,
-                               src_lin_w, src_lin_b, s_buf, B, S, NH, up_total, (float)cfg.sampling_rate, cfg.nsf_alpha, cfg.nsf_sigma,
-                               cfg.nsf_voiced_threshold);
-        else
-            hipLaunchKernelGGL(hift_source_kernel, dim3(cdiv((long)B * Lw, 256)), dim3(256), 0, st, f0, prefix, phase0, noise, src_lin_w,
-                               src_lin_b, s_buf, B, S, NH, up_total, (float)cfg.sampling_rate, cfg.nsf_alpha, cfg.nsf_sigma,
-                               cfg.nsf_voiced_threshold);
-        SVC_CHECK_HIP(hipGetLastError());
-        hipLaunchKernelGGL(hift_stft_kernel, dim3(cdiv((long)B * F, 256)), dim3(256), 0, st, s_buf, stft32, B, Lw, F, ld18);
-    }
+    const int* lw = rg ? rg->lw : nullptr;                             // its waveform samples
+    auto source = [&](auto kernel, auto draws) {
+        hipLaunchKernelGGL(kernel, dim3(cdiv((long)B * Lw, 256)), dim3(256), 0, st, f0, prefix, phase0, draws, src_lin_w, src_lin_b, s_buf,
+                           rm, B, S, NH, up_total, (float)cfg.sampling_rate, cfg.nsf_alpha, cfg.nsf_sigma, cfg.nsf_voiced_threshold);
+    };
+    if (seeds) source(hift_source_kernel<HiftNoiseDraw>, seeds);
+    else source(hift_source_kernel<HiftNoiseLoad>, noise);
+    SVC_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(hift_stft_kernel, dim3(cdiv((long)B * F, 256)), dim3(256), 0, st, s_buf, stft32, lw, len_f, B, Lw, F, ld18);
     SVC_CHECK_HIP(hipGetLastError());
     ActBuf stft_in;
     stft_in.hi = stft32;
@@ -847,9 +836,7 @@ int svc_hift::run(const float* mel, const float* f0_in, const float* phase0, con
         stft_in = stft_a.in();
     }
     // ---- main path
-    if (rg) {
-        if (mel_to_cl_ragged(mel, mel_a, vd, rg->src, len0, B, cfg.in_channels, rg->S_in, S, cpad(cfg.in_channels, dtype), st)) return 1;
-    } else if (mel_to_cl(mel, mel_a, vd, B, cfg.in_channels, S, cpad(cfg.in_channels, dtype), st)) return 1;
+    if (mel_to_cl(mel, mel_a, vd, rm, B, cfg.in_channels, S, cpad(cfg.in_channels, dtype), st)) return 1;
     {
         ConvRun r;
         r.a = mel_a.in(); r.B = B; r.Lin = S; r.Lout = S; r.pad_left = 3;
@@ -916,13 +903,9 @@ int svc_hift::run(const float* mel, const float* f0_in, const float* phase0, con
     }
     hipLaunchKernelGGL(hift_frames_kernel, dim3(cdiv((long)B * F, 256)), dim3(256), 0, st, post, frames, (long)B * F, ld18);
     SVC_CHECK_HIP(hipGetLastError());
-    if (rg) {   // straight into the caller's rows, tails zeroed
-        const long Lw_out = (long)rg->S_in * up_total;
-        hipLaunchKernelGGL(hift_ola_ragged_kernel, dim3(cdiv((long)B * Lw_out, 256)), dim3(256), 0, st, frames, out, rg->src, rg->lw,
-                           len_f, B, F, Lw_out, cfg.audio_limit);
-    } else {
-        hipLaunchKernelGGL(hift_ola_kernel, dim3(cdiv((long)B * Lw, 256)), dim3(256), 0, st, frames, out, B, F, Lw, cfg.audio_limit);
-    }
+    const long Lw_out = (long)rm.S_in * up_total;      // ragged: straight into the caller's rows, tails zeroed
+    hipLaunchKernelGGL(hift_ola_kernel, dim3(cdiv((long)B * Lw_out, 256)), dim3(256), 0, st, frames, out, rm, lw, len_f, B, F, Lw_out,
+                       cfg.audio_limit);
     SVC_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -996,61 +979,24 @@ int svc_bigvgan_forward(svc_bigvgan_t* m, const float* mel, int B, int S, float*
 
 int svc_bigvgan_forward_ragged(svc_bigvgan_t* m, const float* mel, const int32_t* lens, int B, int S, float* out, void* stream) {
     SVC_REQUIRE(m && mel && lens && out && B >= 1 && S >= 1, "bad argument");
-    for (int b = 0; b < B; ++b) SVC_REQUIRE(lens[b] >= 0 && lens[b] <= S, "svc_bigvgan_forward_ragged: lens out of range");
+    if (RaggedPlan::check("svc_bigvgan_forward_ragged", lens, B, S)) return 1;
     hipStream_t st = (hipStream_t)stream;
     const int nu = m->cfg.num_upsamples;
     long total = 1;
     for (int i = 0; i < nu; ++i) total *= m->cfg.upsample_rates[i];
-    // Longest first, micro-batch by micro-batch, each padded to its own longest member only: a batch padded to the longest
-    // utterance of all would compute B * Smax rows.  The stable sort keeps the order of equal lengths, so a batch of equal
-    // lengths runs exactly as svc_bigvgan_forward runs it.
-    std::vector<int> order(B);
-    for (int b = 0; b < B; ++b) order[b] = b;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return lens[a] > lens[b]; });
-    // length table, per micro-batch of nb rows: src[nb], then the valid rows after 0 .. nu up-sampling stages, [nb] each.
-    // Built in a pinned slot and copied once: the caller's array is consumed here and nothing waits for the stream.
-    const size_t n_tab = (size_t)B * (nu + 2);
-    if (n_tab > m->tab_cap) {
-        SVC_CHECK_HIP(hipStreamSynchronize(st));
-        m->tab.release();
-        m->d_tab = m->tab.alloc_n<int>(n_tab, st);
-        if (!m->d_tab) { m->tab_cap = 0; return 1; }
-        m->tab_cap = n_tab;
-    }
-    int* h = reinterpret_cast<int*>(m->staging.acquire(n_tab * sizeof(int)));
-    if (!h) return 1;
-    const int mb = m->microbatch > 0 ? m->microbatch : 32;
-    for (int b0 = 0; b0 < B; b0 += mb) {
-        const int nb = std::min(mb, B - b0);
-        int* row = h + (size_t)b0 * (nu + 2);
-        for (int j = 0; j < nb; ++j) {
-            row[j] = order[b0 + j];
-            long l = lens[order[b0 + j]];
-            for (int i = 0; i <= nu; ++i) {
-                row[(size_t)(i + 1) * nb + j] = (int)l;
-                if (i < nu) l *= m->cfg.upsample_rates[i];
-            }
-        }
-    }
-    SVC_CHECK_HIP(hipMemcpyAsync(m->d_tab, h, n_tab * sizeof(int), hipMemcpyHostToDevice, st));
-    if (m->staging.commit(st)) return 1;
-    for (int b0 = 0; b0 < B; b0 += mb) {
-        const int nb = std::min(mb, B - b0);
-        const int* row = m->d_tab + (size_t)b0 * (nu + 2);
-        RaggedMB rg;
-        rg.src = row;
-        for (int i = 0; i <= nu; ++i) rg.len[i] = row + (size_t)(i + 1) * nb;
-        rg.S_in = S;
-        const int Smb = lens[order[b0]];
-        if (Smb == 0) {     // nothing but empty utterances left: their rows are all tail
-            const long Lw = (long)S * total;
-            hipLaunchKernelGGL(wave_scatter_kernel, dim3(cdiv((long)nb * Lw, 256)), dim3(256), 0, st, (const float*)nullptr, out, rg.src,
-                               rg.len[nu], nb, 0L, Lw);
-            SVC_CHECK_HIP(hipGetLastError());
-            continue;
-        }
-        if (m->reserve(nb, Smb, st)) return 1;
-        if (m->run(mel, nb, Smb, out, st, &rg)) return 1;
+    // No class cut: a short utterance may share a padded micro-batch with a long one
+    auto rows_after = [&](int stage, long l) {
+        for (int i = 0; i < stage; ++i) l *= m->cfg.upsample_rates[i];
+        return l;
+    };
+    RaggedPlan& plan = m->plan;
+    if (plan.build(lens, B, S, m->microbatch, nu, rows_after, nullptr, 0, st)) return 1;
+    if (plan.S_max > 0 && m->reserve(plan.nb_max, plan.S_max, st)) return 1;
+    for (int k = 0; k < plan.count(); ++k) {
+        const RaggedMB rg = plan.mb(k);
+        if (rg.S == 0) {
+            if (zero_rows(rg, out, (long)S * total, st)) return 1;
+        } else if (m->run(mel, rg.nb, rg.S, out, st, &rg)) return 1;
     }
     return 0;
 }
@@ -1160,11 +1106,11 @@ int svc_hift_forward_seeded(svc_hift_t* m, const float* mel, const int32_t* lens
         if (!m->d_seeds || !m->d_phase0) return 1;
         m->seed_cap = B;
     }
-    void* h = m->staging.acquire((size_t)B * 8);
+    void* h = m->plan.staging.acquire((size_t)B * 8);
     if (!h) return 1;
     memcpy(h, seeds, (size_t)B * 8);
     SVC_CHECK_HIP(hipMemcpyAsync(m->d_seeds, h, (size_t)B * 8, hipMemcpyHostToDevice, st));
-    if (m->staging.commit(st)) return 1;
+    if (m->plan.staging.commit(st)) return 1;
     hipLaunchKernelGGL(noise_phase0_kernel, dim3(cdiv(B * NH, 256)), dim3(256), 0, st, m->d_seeds, 0ull, B, NH, m->d_phase0);
     SVC_CHECK_HIP(hipGetLastError());
     if (lens) return m->forward_ragged(mel, lens, f0, m->d_phase0, nullptr, m->d_seeds, B, S, out, f0_out, st);
@@ -1193,73 +1139,19 @@ int svc_hift::forward(const float* mel, const float* f0, const float* phase0, co
 
 int svc_hift::forward_ragged(const float* mel, const int32_t* lens, const float* f0, const float* phase0, const float* noise,
                              const unsigned long long* seeds, int B, int S, float* out, float* f0_out, hipStream_t st) {
-    svc_hift* m = this;
-    for (int b = 0; b < B; ++b) SVC_REQUIRE(lens[b] >= 0 && lens[b] <= S, "svc_hift_forward_ragged: lens out of range");
-    const int nu = m->cfg.num_upsamples;
-    // Longest first (stable: a batch of equal lengths runs exactly as svc_hift_forward runs it), cut into micro-batches of one
-    // kernel class (svc_hift::kernel_class), each padded to its own longest member only.
-    std::vector<int> order(B);
-    for (int b = 0; b < B; ++b) order[b] = b;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return lens[a] > lens[b]; });
-    const int mb = m->microbatch > 0 ? m->microbatch : 32;
-    std::vector<int> first;     // first row of each micro-batch, then B
-    for (int b = 0; b < B; ++b)
-        if (b == 0 || b - first.back() == mb || m->kernel_class(lens[order[b]]) != m->kernel_class(lens[order[first.back()]]))
-            first.push_back(b);
-    first.push_back(B);
-    // length table, per micro-batch of nb rows: src[nb], the valid rows after 0 .. nu up-sampling stages ([nb] each; the last
-    // is the STFT's frame count as well), the waveform samples [nb].  Built in a pinned slot and copied once: the caller's array
-    // is consumed here and nothing waits for the stream.
-    const int n_arr = nu + 3;
-    const size_t n_tab = (size_t)B * n_arr;
-    if (n_tab > m->tab_cap) {
-        SVC_CHECK_HIP(hipStreamSynchronize(st));
-        m->tab.release();
-        m->d_tab = m->tab.alloc_n<int>(n_tab, st);
-        if (!m->d_tab) { m->tab_cap = 0; return 1; }
-        m->tab_cap = n_tab;
-    }
-    int* h = reinterpret_cast<int*>(m->staging.acquire(n_tab * sizeof(int)));
-    if (!h) return 1;
-    int nb_max = 0;
-    for (size_t k = 0; k + 1 < first.size(); ++k) {
-        const int b0 = first[k], nb = first[k + 1] - b0;
-        nb_max = std::max(nb_max, nb);
-        int* row = h + (size_t)b0 * n_arr;
-        for (int j = 0; j < nb; ++j) {
-            const long l = lens[order[b0 + j]];
-            row[j] = order[b0 + j];
-            for (int i = 0; i <= nu; ++i) row[(size_t)(i + 1) * nb + j] = (int)m->rows_after(i, l);
-            row[(size_t)(nu + 2) * nb + j] = (int)(l * m->up_total);
-        }
-    }
-    SVC_CHECK_HIP(hipMemcpyAsync(m->d_tab, h, n_tab * sizeof(int), hipMemcpyHostToDevice, st));
-    if (m->staging.commit(st)) return 1;
-    // one reservation for the whole call: the first micro-batch is the longest, not necessarily the largest
-    if (lens[order[0]] > 0 && m->reserve(nb_max, lens[order[0]], st)) return 1;
-    for (size_t k = 0; k + 1 < first.size(); ++k) {
-        const int b0 = first[k], nb = first[k + 1] - b0;
-        const int* row = m->d_tab + (size_t)b0 * n_arr;
-        RaggedMB rg;
-        rg.src = row;
-        for (int i = 0; i <= nu; ++i) rg.len[i] = row + (size_t)(i + 1) * nb;
-        rg.lw = row + (size_t)(nu + 2) * nb;
-        rg.h_len0 = h + (size_t)b0 * n_arr + nb;
-        rg.S_in = S;
-        const int Smb = lens[order[b0]];
-        if (Smb == 0) {     // nothing but empty utterances left: their rows are all tail
-            const long Lw = (long)S * m->up_total;
-            hipLaunchKernelGGL(wave_scatter_kernel, dim3(cdiv((long)nb * Lw, 256)), dim3(256), 0, st, (const float*)nullptr, out, rg.src,
-                               rg.lw, nb, 0L, Lw);
-            SVC_CHECK_HIP(hipGetLastError());
-            if (f0_out) {
-                hipLaunchKernelGGL(wave_scatter_kernel, dim3(cdiv((long)nb * S, 256)), dim3(256), 0, st, (const float*)nullptr, f0_out,
-                                   rg.src, rg.len[0], nb, 0L, (long)S);
-                SVC_CHECK_HIP(hipGetLastError());
-            }
-            continue;
-        }
-        if (m->run(mel, f0, phase0, noise, nb, Smb, out, f0_out, st, &rg, seeds)) return 1;
+    if (RaggedPlan::check("svc_hift_forward_ragged", lens, B, S)) return 1;
+    // Micro-batches of one kernel class (svc_hift::kernel_class); one reservation for the whole call: the first micro-batch is the
+    // longest, not necessarily the largest
+    if (plan.build(lens, B, S, microbatch, cfg.num_upsamples, [&](int i, long l) { return rows_after(i, l); },
+                   [&](long l) { return kernel_class(l); }, up_total, st))
+        return 1;
+    if (plan.S_max > 0 && reserve(plan.nb_max, plan.S_max, st)) return 1;
+    for (int k = 0; k < plan.count(); ++k) {
+        const RaggedMB rg = plan.mb(k);
+        if (rg.S == 0) {
+            if (zero_rows(rg, out, (long)S * up_total, st)) return 1;
+            if (f0_out && zero_rows(rg, f0_out, (long)S, st)) return 1;
+        } else if (run(mel, f0, phase0, noise, rg.nb, rg.S, out, f0_out, st, &rg, seeds)) return 1;
     }
     return 0;
 }

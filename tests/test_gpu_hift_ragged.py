@@ -174,6 +174,8 @@ def test_equal_lengths_equal_the_uniform_call(precision):
         y0, f0 = voc(bt["mel"], phase0=bt["phase0"], noise=bt["noise"], return_f0=True)
         y1, f1 = voc(bt["mel"], phase0=bt["phase0"], noise=bt["noise"], return_f0=True, lens=[S] * 5)
         assert torch.equal(y0, y1) and torch.equal(f0, f1)
+        seeds = [11 + b for b in range(5)]                 # the draws made on the device: seeded plain against seeded ragged
+        assert torch.equal(voc(bt["mel"], f0=bt["f0"], seeds=seeds), voc(bt["mel"], f0=bt["f0"], seeds=seeds, lens=[S] * 5))
 
 
 def test_ragged_errors_leave_the_handle_usable():
