@@ -1030,6 +1030,53 @@ typedef struct {
     int32_t kv_len_const, vt_perm, qt_form;
 } svc_attention_t;
 int svc_op_attention_ex(const svc_attention_t* args, void* stream);
+/* Test aid (tests/test_gpu_vocoder_pointwise.py; no model uses it): ONE call of the vocoders' channels-last activation launch
+ * (csrc/aa_act.hip, act_cl_launch) with every argument taken as given.  Device pointers unless noted.
+ *   x fp32 [B][L][ldx]; y_hi and y_lo planes [B][L][ldy]: fp32 (out_f16 0, no y_lo) or 16-bit words (out_f16 1; y_lo may be NULL);
+ *   lo_fmt 0: y_lo = fp16(v - hi), 1: the byte pair (fp8(hi), fp8(2^11 (v - hi))); taps: the 12 filter taps, by value;
+ *   a, inv_b [C]; mode 0 anti-aliased Snake, 1 Snake v + inv_b sin^2(a v), 2 leaky ReLU with `slope`;
+ *   lens: HOST [B] valid rows per sequence (mode 0 only) or NULL.
+ *   Refused (nothing launched): NULL x or y_hi; B, C or L < 1; ldx or ldy < C; mode outside 0 .. 2; a Snake mode without a and
+ *   inv_b; lo_fmt outside 0 .. 1, or 1 without y_lo; y_lo or lo_fmt with the fp32 output; lens with mode 1 or 2, or outside
+ *   [0, L]; x not 8-byte or a plane not 4-byte aligned. */
+typedef struct {
+    const float* x; void* y_hi; void* y_lo;
+    int64_t ldx, ldy;
+    int32_t out_f16, lo_fmt;
+    float taps[12];
+    const float* a; const float* inv_b;
+    int32_t B, C, L, mode;
+    float slope;
+    const int32_t* lens;
+} svc_act_cl_t;
+int svc_op_act_cl(const svc_act_cl_t* args, void* stream);
+/* Test aid (tests/test_gpu_vocoder_pointwise.py; no model uses it): ONE signal stage of HiFT (csrc/vocoder.hip) on explicit
+ * buffers, through the launcher the model calls.  Device pointers unless noted; NULL = absent.  Rows: B micro-batch rows; row j
+ * is utterance src[j] (HOST [B]; NULL: j) of the caller's n_utt-utterance tensors and holds len[j] (HOST [B]; NULL: S) frames.
+ *   stage 1  phase prefix + source, loaded noise: in = f0 [B][S], phase0 [n_utt][NH], noise [n_utt][NH][S_in * up], lin_w [NH],
+ *            lin_b [1] -> out fp32 [B][S * up]; scalars NH, up, sr, sine_amp, noise_std, voiced_thr
+ *   stage 2  STFT: in = s [B][Lw] -> out fp32 [B][F][ld] (9 real | 9 imaginary | zeros); lw, nf HOST [B] or NULL (Lw, F)
+ *   stage 3  frames: in = [B * F][ld] (9 log-magnitudes | 9 phase pre-activations) -> out fp32 [B * F][16]
+ *   stage 4  overlap-add: in = frames [B][F][16] -> out fp32 [n_utt][Lw], row src[j]; lw, nf as in stage 2; limit
+ *   stage 5  mel_to_cl: in = mel [n_utt][C][S_in] -> out (and out_lo) [B][S][ld]; vd 0 fp16, 1 fp32, 2 | 3 fp16 hi + lo
+ *   stage 6  ew_cl: in = [B * S][ld] -> out (and out_lo) [B * S][ld]; vd as above; mode 2 leaky ReLU with `slope`, 3 cast
+ *   Refused (nothing launched): a stage outside 1 .. 6; NULL in or out; B or n_utt < 1; src outside [0, n_utt) (without src: B >
+ *   n_utt); stages 1, 5: S < 1, S_in < S, len outside [0, S]; stages 2, 4: F or Lw < 1, one of lw and nf alone, lw outside
+ *   [0, Lw], nf outside [0, F]; stage 2: ld < 18, a row with frames and lw < 9 or nf > lw / 4 + 1; stage 3: ld < 18;
+ *   stages 5, 6: vd outside 0 .. 3, C < 1, ld < C, a split mode without out_lo; stage 6: a mode other than 2 or 3. */
+typedef struct {
+    int32_t stage;
+    const float* in; const float* phase0; const float* noise; const float* lin_w; const float* lin_b;
+    void* out; void* out_lo;
+    int32_t B, n_utt, NH, up;
+    float sr, sine_amp, noise_std, voiced_thr, limit;
+    int32_t S, S_in, F;
+    int64_t Lw;
+    int32_t ld, C, vd, mode;
+    float slope;
+    const int32_t* src; const int32_t* len; const int32_t* lw; const int32_t* nf;
+} svc_hift_signal_t;
+int svc_op_hift_signal(const svc_hift_signal_t* args, void* stream);
 /* y = rmsnorm(x) * gamma * (add_one + w) + b ; x [rows][D]. */
 int svc_op_rmsnorm(const float* x, const float* gamma, const float* w, const float* b, int add_one, float* y,
                    int rows, int D, void* stream);

@@ -45,7 +45,7 @@ EXPORTS = [
     "svc_op_bsq_index", "svc_tokens_reduce",
     "svc_prof_enable", "svc_prof_collect",
     "svc_op_linear", "svc_op_conv1d", "svc_op_conv1d_ex", "svc_op_conv1d_last_took", "svc_op_dit_panel", "svc_op_conv_transpose1d", "svc_op_attention", "svc_op_attention_ex", "svc_op_rmsnorm",
-    "svc_op_layernorm", "svc_op_layernorm_gelu",
+    "svc_op_layernorm", "svc_op_layernorm_gelu", "svc_op_act_cl", "svc_op_hift_signal",
 ]
 
 
@@ -171,6 +171,24 @@ class Attention(C.Structure):
                [(n, C.c_int32) for n in ("kv_len_const", "vt_perm", "qt_form")]
 
 
+class ActCl(C.Structure):
+    """svc_act_cl_t: the arguments of svc_op_act_cl (test aid)."""
+    _fields_ = [("x", C.c_void_p), ("y_hi", C.c_void_p), ("y_lo", C.c_void_p), ("ldx", C.c_int64), ("ldy", C.c_int64),
+                ("out_f16", C.c_int32), ("lo_fmt", C.c_int32), ("taps", C.c_float * 12), ("a", C.c_void_p), ("inv_b", C.c_void_p)] + \
+               [(n, C.c_int32) for n in ("B", "C", "L", "mode")] + [("slope", C.c_float), ("lens", C.POINTER(C.c_int32))]
+
+
+class HiftSignal(C.Structure):
+    """svc_hift_signal_t: the arguments of svc_op_hift_signal (test aid)."""
+    _fields_ = [("stage", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("in", "phase0", "noise", "lin_w", "lin_b", "out", "out_lo")] + \
+               [(n, C.c_int32) for n in ("B", "n_utt", "NH", "up")] + \
+               [(n, C.c_float) for n in ("sr", "sine_amp", "noise_std", "voiced_thr", "limit")] + \
+               [(n, C.c_int32) for n in ("S", "S_in", "F")] + [("Lw", C.c_int64)] + \
+               [(n, C.c_int32) for n in ("ld", "C", "vd", "mode")] + [("slope", C.c_float)] + \
+               [(n, C.POINTER(C.c_int32)) for n in ("src", "len", "lw", "nf")]
+
+
 _lib = None
 
 
@@ -221,6 +239,8 @@ def lib():
         l.svc_op_conv1d_ex.argtypes = [C.POINTER(Conv1dEx), C.c_void_p]
         l.svc_op_dit_panel.argtypes = [C.POINTER(DitPanel), C.c_void_p]
         l.svc_op_attention_ex.argtypes = [C.POINTER(Attention), C.c_void_p]
+        l.svc_op_act_cl.argtypes = [C.POINTER(ActCl), C.c_void_p]
+        l.svc_op_hift_signal.argtypes = [C.POINTER(HiftSignal), C.c_void_p]
         # seeded noise: 64-bit seeds by value and as HOST arrays
         l.svc_cfm_sample_seeded.argtypes = [C.c_void_p, C.POINTER(CfmArgs), C.POINTER(C.c_uint64), C.c_void_p]
         l.svc_cfm_noise_draws.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]

@@ -333,6 +333,45 @@ int mel_to_cl(const float* mel, ActOut dst, int vd, RowMap rm, int B, int C, int
     return 0;
 }
 
+// The HiFT signal stages' launches, one function each: svc_hift::run and the parity tests' svc_op_hift_signal call the same
+// launch geometry.
+// phase prefix + merged source: draws from `seeds` ([..] per utterance) when given, else loaded from `noise`
+int hift_source_launch(const float* f0, double* prefix, const float* phase0, const float* noise, const unsigned long long* seeds,
+                       const float* lin_w, const float* lin_b, float* s_out, RowMap rm, int B, int S, int NH, int up, float sr,
+                       float sine_amp, float noise_std, float voiced_thr, hipStream_t st) {
+    hipLaunchKernelGGL(hift_phase_prefix_kernel, dim3(cdiv(B * NH, 64)), dim3(64), 0, st, f0, prefix, B, S, NH, up, sr);
+    SVC_CHECK_HIP(hipGetLastError());
+    const long Lw = (long)S * up;
+    auto source = [&](auto kernel, auto draws) {
+        hipLaunchKernelGGL(kernel, dim3(cdiv((long)B * Lw, 256)), dim3(256), 0, st, f0, prefix, phase0, draws, lin_w, lin_b, s_out,
+                           rm, B, S, NH, up, sr, sine_amp, noise_std, voiced_thr);
+    };
+    if (seeds) source(hift_source_kernel<HiftNoiseDraw>, seeds);
+    else source(hift_source_kernel<HiftNoiseLoad>, noise);
+    SVC_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int hift_stft_launch(const float* s, float* out, const int* lw, const int* nf, int B, long Lw, int F, int ld, hipStream_t st) {
+    hipLaunchKernelGGL(hift_stft_kernel, dim3(cdiv((long)B * F, 256)), dim3(256), 0, st, s, out, lw, nf, B, Lw, F, ld);
+    SVC_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int hift_frames_launch(const float* post, float* frames, long BF, int ld, hipStream_t st) {
+    hipLaunchKernelGGL(hift_frames_kernel, dim3(cdiv(BF, 256)), dim3(256), 0, st, post, frames, BF, ld);
+    SVC_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int hift_ola_launch(const float* frames, float* out, RowMap rm, const int* lw, const int* nf, int B, int F, long Lw_out, float limit,
+                    hipStream_t st) {
+    hipLaunchKernelGGL(hift_ola_kernel, dim3(cdiv((long)B * Lw_out, 256)), dim3(256), 0, st, frames, out, rm, lw, nf, B, F, Lw_out,
+                       limit);
+    SVC_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
 struct SnakeP {
     float* a = nullptr;
     float* inv_b = nullptr;
@@ -814,21 +853,12 @@ int svc_hift::run(const float* mel, const float* f0_in, const float* phase0, con
         } else SVC_CHECK_HIP(hipMemcpyAsync(f0_out, f0, (size_t)B * S * 4, hipMemcpyDeviceToDevice, st));
     }
     // ---- harmonic source + its STFT
-    hipLaunchKernelGGL(hift_phase_prefix_kernel, dim3(cdiv(B * NH, 64)), dim3(64), 0, st, f0, prefix, B, S, NH, up_total,
-                       (float)cfg.sampling_rate);
-    SVC_CHECK_HIP(hipGetLastError());
     const int ld18 = cpad(cfg.istft_n_fft + 2, dtype);
     const int* len_f = rg ? rg->len[cfg.num_upsamples] : nullptr;      // frames of the STFT / iSTFT = rows of the last stage
     const int* lw = rg ? rg->lw : nullptr;                             // its waveform samples
-    auto source = [&](auto kernel, auto draws) {
-        hipLaunchKernelGGL(kernel, dim3(cdiv((long)B * Lw, 256)), dim3(256), 0, st, f0, prefix, phase0, draws, src_lin_w, src_lin_b, s_buf,
-                           rm, B, S, NH, up_total, (float)cfg.sampling_rate, cfg.nsf_alpha, cfg.nsf_sigma, cfg.nsf_voiced_threshold);
-    };
-    if (seeds) source(hift_source_kernel<HiftNoiseDraw>, seeds);
-    else source(hift_source_kernel<HiftNoiseLoad>, noise);
-    SVC_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(hift_stft_kernel, dim3(cdiv((long)B * F, 256)), dim3(256), 0, st, s_buf, stft32, lw, len_f, B, Lw, F, ld18);
-    SVC_CHECK_HIP(hipGetLastError());
+    if (hift_source_launch(f0, prefix, phase0, noise, seeds, src_lin_w, src_lin_b, s_buf, rm, B, S, NH, up_total,
+                           (float)cfg.sampling_rate, cfg.nsf_alpha, cfg.nsf_sigma, cfg.nsf_voiced_threshold, st)) return 1;
+    if (hift_stft_launch(s_buf, stft32, lw, len_f, B, Lw, F, ld18, st)) return 1;
     ActBuf stft_in;
     stft_in.hi = stft32;
     if (vd != 1) {
@@ -901,13 +931,9 @@ int svc_hift::run(const float* mel, const float* f0_in, const float* phase0, con
         r.seq_len = len_f; r.seq_kconv = true;
         if (conv1d_run(conv_post, r, st)) return 1;
     }
-    hipLaunchKernelGGL(hift_frames_kernel, dim3(cdiv((long)B * F, 256)), dim3(256), 0, st, post, frames, (long)B * F, ld18);
-    SVC_CHECK_HIP(hipGetLastError());
+    if (hift_frames_launch(post, frames, (long)B * F, ld18, st)) return 1;
     const long Lw_out = (long)rm.S_in * up_total;      // ragged: straight into the caller's rows, tails zeroed
-    hipLaunchKernelGGL(hift_ola_kernel, dim3(cdiv((long)B * Lw_out, 256)), dim3(256), 0, st, frames, out, rm, lw, len_f, B, F, Lw_out,
-                       cfg.audio_limit);
-    SVC_CHECK_HIP(hipGetLastError());
-    return 0;
+    return hift_ola_launch(frames, out, rm, lw, len_f, B, F, Lw_out, cfg.audio_limit, st);
 }
 
 // ================================================================================================ C ABI
@@ -1288,6 +1314,111 @@ int svc_op_conv_transpose1d(const float* x, const float* w, const float* bias, f
     ab.hi = a; ab.lo = a_lo;
     if (convT_run(cw, ab, B, L, c, 0, 0, st)) return 1;
     if (pack_f32_launch(c, y, B * L * stride, 1, Cout, cw.cout_pad, 0, 1, Cout, 0, 1, nullptr, st)) return 1;
+    SVC_CHECK_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
+namespace {
+// a HOST int32 array of a test aid -> the device (null stays null)
+int op_host_ints(const int32_t* h, int n, Arena& ar, hipStream_t st, const int** out) {
+    *out = nullptr;
+    if (!h) return 0;
+    int* d = ar.alloc_n<int>(n, st);
+    if (!d) return 1;
+    SVC_CHECK_HIP(hipMemcpyAsync(d, h, n * sizeof(int), hipMemcpyHostToDevice, st));
+    SVC_CHECK_HIP(hipStreamSynchronize(st));      // the caller's array is pageable
+    *out = d;
+    return 0;
+}
+}  // namespace
+
+int svc_op_act_cl(const svc_act_cl_t* e, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    SVC_REQUIRE(e, "svc_op_act_cl: null argument");
+    SVC_REQUIRE(e->x && e->y_hi, "svc_op_act_cl: x and y_hi are required");
+    SVC_REQUIRE(e->B >= 1 && e->C >= 1 && e->L >= 1, "svc_op_act_cl: B, C and L are positive");
+    SVC_REQUIRE(e->ldx >= e->C && e->ldy >= e->C, "svc_op_act_cl: ldx and ldy cover C channels");
+    SVC_REQUIRE(e->mode >= 0 && e->mode <= 2, "svc_op_act_cl: mode is 0 .. 2");
+    SVC_REQUIRE(e->mode == 2 || (e->a && e->inv_b), "svc_op_act_cl: the Snake modes need a and inv_b");
+    SVC_REQUIRE(e->lo_fmt == 0 || e->lo_fmt == 1, "svc_op_act_cl: lo_fmt is 0 (fp16 residual) or 1 (fp8 byte pair)");
+    SVC_REQUIRE(e->out_f16 || (!e->y_lo && !e->lo_fmt), "svc_op_act_cl: the lo plane belongs to the fp16 output");
+    SVC_REQUIRE(!e->lo_fmt || e->y_lo, "svc_op_act_cl: lo_fmt 1 needs y_lo");
+    SVC_REQUIRE(!e->lens || e->mode == 0, "svc_op_act_cl: lens is for mode 0 only");
+    SVC_REQUIRE((uintptr_t)e->x % 8 == 0 && (uintptr_t)e->y_hi % 4 == 0 && (uintptr_t)e->y_lo % 4 == 0,
+                "svc_op_act_cl: alignment: x to 8 bytes, the planes to 4");
+    if (e->lens)
+        for (int b = 0; b < e->B; ++b) SVC_REQUIRE(e->lens[b] >= 0 && e->lens[b] <= e->L, "svc_op_act_cl: lens out of range");
+    Arena ar;
+    const int* d_lens = nullptr;
+    if (op_host_ints(e->lens, e->B, ar, st, &d_lens)) return 1;
+    if (act_cl_launch(e->x, (long)e->ldx, e->y_hi, e->y_lo, (long)e->ldy, e->out_f16, e->taps, e->a, e->inv_b, e->B, e->C, e->L, e->mode,
+                      e->slope, st, e->lo_fmt, d_lens)) return 1;
+    SVC_CHECK_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
+int svc_op_hift_signal(const svc_hift_signal_t* e, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    SVC_REQUIRE(e, "svc_op_hift_signal: null argument");
+    SVC_REQUIRE(e->stage >= 1 && e->stage <= 6, "svc_op_hift_signal: stage is 1 .. 6");
+    SVC_REQUIRE(e->in && e->out, "svc_op_hift_signal: in and out are required");
+    const int B = e->B;
+    SVC_REQUIRE(B >= 1 && e->n_utt >= 1, "svc_op_hift_signal: B and n_utt are positive");
+    SVC_REQUIRE(e->src || B <= e->n_utt, "svc_op_hift_signal: without src, row j is utterance j < n_utt");
+    if (e->src)
+        for (int b = 0; b < B; ++b) SVC_REQUIRE(e->src[b] >= 0 && e->src[b] < e->n_utt, "svc_op_hift_signal: src out of range");
+    const int stage = e->stage;
+    if (stage == 1 || stage == 5) {
+        SVC_REQUIRE(e->S >= 1 && e->S_in >= e->S, "svc_op_hift_signal: 1 <= S <= S_in");
+        if (e->len)
+            for (int b = 0; b < B; ++b) SVC_REQUIRE(e->len[b] >= 0 && e->len[b] <= e->S, "svc_op_hift_signal: len out of range");
+    }
+    if (stage == 2 || stage == 4) {
+        SVC_REQUIRE(e->F >= 1 && e->Lw >= 1 && !e->lw == !e->nf, "svc_op_hift_signal: F and Lw are positive; lw and nf come together");
+        if (e->lw)
+            for (int b = 0; b < B; ++b)
+                SVC_REQUIRE(e->lw[b] >= 0 && e->lw[b] <= e->Lw && e->nf[b] >= 0 && e->nf[b] <= e->F, "svc_op_hift_signal: lw or nf out of range");
+    }
+    if (stage == 1) {
+        SVC_REQUIRE(e->phase0 && e->noise && e->lin_w && e->lin_b, "svc_op_hift_signal: the source needs phase0, noise, lin_w and lin_b");
+        SVC_REQUIRE(e->NH >= 1 && e->up >= 1, "svc_op_hift_signal: NH and up are positive");
+    } else if (stage == 2) {
+        // every sample index a frame reflects to lies inside the row: 4 fr + 7 <= lw + 7 reflects to >= lw - 9, and 8 to 8
+        SVC_REQUIRE(e->ld >= 18, "svc_op_hift_signal: the STFT writes 18 columns");
+        for (int b = 0; b < B; ++b) {
+            const long lwb = e->lw ? e->lw[b] : e->Lw, nfb = e->nf ? e->nf[b] : e->F;
+            SVC_REQUIRE(nfb == 0 || (lwb >= 9 && nfb <= lwb / 4 + 1), "svc_op_hift_signal: frames need lw >= 9 and nf <= lw / 4 + 1");
+        }
+    } else if (stage == 3) {
+        SVC_REQUIRE(e->F >= 1 && e->ld >= 18, "svc_op_hift_signal: F is positive, ld >= 18");
+    } else if (stage >= 5) {
+        SVC_REQUIRE(e->vd >= 0 && e->vd <= 3 && e->C >= 1 && e->ld >= e->C, "svc_op_hift_signal: vd is 0 .. 3, 1 <= C <= ld");
+        SVC_REQUIRE(!is_split(e->vd) || e->out_lo, "svc_op_hift_signal: a split mode needs out_lo");
+        SVC_REQUIRE(stage == 5 || (e->S >= 1 && (e->mode == 2 || e->mode == 3)), "svc_op_hift_signal: S is positive; ew_cl mode is 2 or 3");
+    }
+    Arena ar;
+    const int *d_src, *d_len, *d_lw, *d_nf;
+    if (op_host_ints(e->src, B, ar, st, &d_src) || op_host_ints(e->len, B, ar, st, &d_len) || op_host_ints(e->lw, B, ar, st, &d_lw) ||
+        op_host_ints(e->nf, B, ar, st, &d_nf)) return 1;
+    const RowMap rm{d_src, d_len, e->S_in};
+    ActOut y;
+    y.hi = e->out; y.lo = e->out_lo;
+    if (stage == 1) {
+        double* prefix = ar.alloc_n<double>((size_t)B * e->NH * e->S, st);
+        if (!prefix) return 1;
+        if (hift_source_launch(e->in, prefix, e->phase0, e->noise, nullptr, e->lin_w, e->lin_b, (float*)e->out, rm, B, e->S, e->NH, e->up,
+                               e->sr, e->sine_amp, e->noise_std, e->voiced_thr, st)) return 1;
+    } else if (stage == 2) {
+        if (hift_stft_launch(e->in, (float*)e->out, d_lw, d_nf, B, (long)e->Lw, e->F, e->ld, st)) return 1;
+    } else if (stage == 3) {
+        if (hift_frames_launch(e->in, (float*)e->out, (long)B * e->F, e->ld, st)) return 1;
+    } else if (stage == 4) {
+        if (hift_ola_launch(e->in, (float*)e->out, rm, d_lw, d_nf, B, e->F, (long)e->Lw, e->limit, st)) return 1;
+    } else if (stage == 5) {
+        if (mel_to_cl(e->in, y, e->vd, rm, B, e->C, e->S, e->ld, st)) return 1;
+    } else {
+        if (ew_cl(e->in, y, e->vd, (long)B * e->S, e->C, e->ld, e->mode, e->slope, st)) return 1;
+    }
     SVC_CHECK_HIP(hipStreamSynchronize(st));
     return 0;
 }

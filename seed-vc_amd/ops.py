@@ -260,6 +260,107 @@ def attention_ex(a, device="cuda:0", fill16=0x6A5A, fill32=-777.25):
     return out
 
 
+def _i32_field(values, n, what):
+    """list of n ints (or None) -> (HOST int32 array kept alive by the caller, pointer for a struct field)"""
+    import ctypes as C
+    if values is None:
+        return None, None
+    assert len(values) == n, what
+    arr = _lib.i32_host([int(v) for v in values])
+    return arr, C.cast(arr, C.POINTER(C.c_int32))
+
+
+def act_cl(x, C, ldy, taps=None, a=None, inv_b=None, out="f32", lo=None, mode=0, slope=0.0, lens=None, device="cuda:0", guard=8,
+           fill16=0x6A5A, fill32=-777.25):
+    """Test aid over svc_op_act_cl (include/seedvc_hip.h): ONE act_cl_launch, every argument as given.
+    x (B, L, ldx) fp32 (it may hold NaN wherever the kernel must not read); C channels; taps (12,), a, inv_b (C,) fp32 or None;
+    out "f32" | "f16"; lo None | "f16" | "p8" (the fp16 residual or the fp8 byte pair); lens a list of B ints or None.
+    x sits between `guard` rows of NaN on the device.  Returns (hi, lo, guard): the WHOLE plane buffers (guard + B * L + guard,
+    ldy), fp32 or int16 words, guard rows in front and behind included, holding fill32 / the bit pattern fill16 wherever the launch
+    did not write; lo is None when not asked for."""
+    import ctypes as Ct
+    dev = torch.device(device)
+    B, L, ldx = x.shape
+    assert x.dtype == torch.float32 and out in ("f32", "f16") and lo in (None, "f16", "p8") and (guard * ldx) % 2 == 0
+    with torch.cuda.device(dev):
+        e = _lib.ActCl()
+        xg = torch.full((guard + B * L + guard, ldx), float("nan"), dtype=torch.float32, device=dev)
+        xg[guard:guard + B * L] = x.reshape(B * L, ldx).to(dev)
+        keep = [xg]
+        e.x = xg.data_ptr() + 4 * guard * ldx
+
+        def plane():
+            if out == "f32":
+                return torch.full((guard + B * L + guard, ldy), fill32, dtype=torch.float32, device=dev)
+            return torch.full((guard + B * L + guard, ldy), fill16, dtype=torch.int16, device=dev)
+        esz = 4 if out == "f32" else 2
+        hi = plane()
+        e.y_hi = hi.data_ptr() + esz * guard * ldy
+        p_lo = None
+        if lo is not None:
+            p_lo = plane()
+            e.y_lo = p_lo.data_ptr() + esz * guard * ldy
+        e.ldx, e.ldy, e.out_f16, e.lo_fmt = ldx, ldy, int(out == "f16"), int(lo == "p8")
+        if taps is not None:
+            e.taps = (Ct.c_float * 12)(*[float(v) for v in taps.reshape(12).tolist()])
+        for name, t in (("a", a), ("inv_b", inv_b)):
+            if t is not None:
+                assert tuple(t.shape) == (C,) and t.dtype == torch.float32, name
+                keep.append(t.to(dev).contiguous())
+                setattr(e, name, keep[-1].data_ptr())
+        e.B, e.C, e.L, e.mode, e.slope = B, C, L, mode, slope
+        arr, p = _i32_field(lens, B, "lens")
+        if p is not None:
+            e.lens = p
+        _lib.check(_lib.lib().svc_op_act_cl(Ct.byref(e), _lib.stream_ptr()))
+    return hi, p_lo, guard
+
+
+_HIFT_SCALARS_I = ("stage", "B", "n_utt", "NH", "up", "S", "S_in", "F", "Lw", "ld", "C", "vd", "mode")
+_HIFT_SCALARS_F = ("sr", "sine_amp", "noise_std", "voiced_thr", "limit", "slope")
+
+
+def hift_signal(a, device="cuda:0", fill16=0x6A5A, fill32=-777.25):
+    """Test aid over svc_op_hift_signal (include/seedvc_hip.h): ONE HiFT signal stage through the model's launcher.
+    `a` maps the fields of svc_hift_signal_t: ints and floats; `in`, phase0, noise, lin_w, lin_b as fp32 CPU or device tensors
+    (None = absent), taken as given; src, len, lw, nf as lists of B ints or None.  The output buffer is allocated here in the
+    stage's shape (1: (B, S up), 2: (B, F, ld), 3: (B F, 16), 4: (n_utt, Lw), 5: (B, S, ld), 6: (B S, ld)), fp32 holding fill32 or,
+    for the fp16 forms of stages 5 and 6 (vd != 1), int16 words holding the bit pattern fill16.  Returns (out, out_lo): the whole
+    buffers; out_lo only for vd 2 | 3, else None."""
+    import ctypes as C
+    dev = torch.device(device)
+    with torch.cuda.device(dev):
+        e = _lib.HiftSignal()
+        for name in _HIFT_SCALARS_I:
+            setattr(e, name, int(a.get(name) or 0))
+        for name in _HIFT_SCALARS_F:
+            setattr(e, name, float(a.get(name) or 0.0))
+        keep = []
+        for name in ("in", "phase0", "noise", "lin_w", "lin_b"):
+            t = a.get(name)
+            if t is not None:
+                assert t.dtype == torch.float32, name
+                keep.append(t.to(dev).contiguous())
+                setattr(e, name, keep[-1].data_ptr())
+        for name in ("src", "len", "lw", "nf"):
+            arr, p = _i32_field(a.get(name), e.B, name)
+            if p is not None:
+                keep.append(arr)
+                setattr(e, name, p)
+        shape = {1: (e.B, e.S * e.up), 2: (e.B, e.F, e.ld), 3: (e.B * e.F, 16), 4: (e.n_utt, e.Lw), 5: (e.B, e.S, e.ld),
+                 6: (e.B * e.S, e.ld)}[e.stage]
+        half_out = e.stage >= 5 and e.vd != 1
+        new = lambda: (torch.full(shape, fill16, dtype=torch.int16, device=dev) if half_out     # noqa: E731
+                       else torch.full(shape, fill32, dtype=torch.float32, device=dev))
+        out, out_lo = new(), None
+        e.out = out.data_ptr()
+        if half_out and e.vd in (2, 3):
+            out_lo = new()
+            e.out_lo = out_lo.data_ptr()
+        _lib.check(_lib.lib().svc_op_hift_signal(C.byref(e), _lib.stream_ptr()))
+    return out, out_lo
+
+
 def rmsnorm(x, gamma, w=None, b=None, add_one=False):
     rows, D = x.shape
     dev = x.device
