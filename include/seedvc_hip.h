@@ -74,8 +74,9 @@ int svc_dit_set_fused_seams(svc_dit_t* m, int mask);
 int svc_dit_fused_available(svc_dit_t* m);
 /* Optional (off by default: the sampler is GPU-bound on MI355X, replay measured 3 % slower than eager launches at B = 1):
  * the Euler loop of svc_cfm_sample (all steps of a micro-batch group: estimator + state update) is captured into a hipGraph
- * the second time a (batch, length, steps, guidance) combination is seen and replayed afterwards (the reference's
- * counterpart: `compile_cfm`, modules/v2/vc_wrapper.py:116-123).  Replays are bit-identical to eager runs.  on = 0 turns
+ * the second time a (batch, length, steps, guidance streams) combination is seen and replayed afterwards (the reference's
+ * counterpart: `compile_cfm`, modules/v2/vc_wrapper.py:116-123).  The guidance rates and temperatures are not part of the
+ * combination: the loop reads them from the handle's settings table.  Replays are bit-identical to eager runs.  on = 0 turns
  * capture off and drops the cached graphs; the environment variable SVC_DIT_GRAPH=0|1 overrides. */
 int svc_dit_set_graphs(svc_dit_t* m, int on);
 
@@ -117,6 +118,43 @@ int svc_cfm_sample(svc_dit_t* m, const svc_cfm_args_t* args, void* stream);
 int svc_cfm_sample_seeded(svc_dit_t* m, const svc_cfm_args_t* args, const uint64_t* seeds, void* stream);
 /* z (device, [C][T]) = the sampler noise of `seed`: what svc_cfm_sample_seeded draws for an utterance of that seed. */
 int svc_cfm_noise_draws(uint64_t seed, int C, int T, float* z, void* stream);
+
+/* ---- per-utterance sampler settings: steps, guidance and temperature of every utterance in one call.
+ * The guidance rates and the temperature enter the sampler in two places only, the start state (temperature * z) and the
+ * update x += dt (c0 v - ca v_a - cb v_b); the estimator never sees them.  Both read them per utterance from a small device
+ * table, so utterances with different rates and temperatures share every launch.  What cannot be shared is the time grid (a
+ * function of n_timesteps) and the set of guidance streams, so the batch is partitioned into CLASSES: two rows are in one
+ * class when they have the same n_timesteps and the same guidance structure, which is the branch the sampler takes --
+ * v1: cfg_rate[0] > 0 or not; v2: random_voice, then (0, 0), (0, rb), (ra, 0), (ra, rb).  The temperature and the values of
+ * the rates never split a class.  A class runs like one svc_cfm_sample call over its members in batch order (micro-batches
+ * of the handle's size over that list); the classes run one after the other on the stream, numbered by first appearance.
+ * Members of a class need not be adjacent: mu / prompt / style / z are read and out is written through a row map, nothing
+ * is gathered or copied.
+ *
+ * Contract.  (a) Rows that all carry one setting give bit for bit the result of svc_cfm_sample[_seeded] with that setting
+ * (they are the same code: the uniform entries are this one with B copies of args' setting).  (b) In general the call is bit
+ * for bit the sequence of svc_cfm_sample[_seeded] runs over each class's members stacked in batch order -- so a class whose
+ * members share all four settings equals the existing call on those rows.  (c) Every row is an independent B = 1 run of the
+ * reference sampler with its own settings.
+ * With svc_dit_set_graphs the captured loop is keyed by the class shape and reads the settings table at replay: a replay
+ * with other rates or temperatures uses the new ones. */
+typedef struct svc_cfm_row {          /* HOST, one per utterance */
+    int32_t n_timesteps;              /* >= 1 */
+    float   temperature;
+    float   cfg_rate[2];              /* v1: [0] ; v2: [intelligibility, similarity] */
+    int32_t random_voice;             /* v2 only */
+} svc_cfm_row_t;
+
+/* svc_cfm_sample / _seeded with the four settings taken per row (args->n_timesteps, temperature, cfg_rate, random_voice
+ * are ignored).  rows: HOST [B], consumed before the call returns.  seeds: HOST [B] or NULL (then args->z).
+ * Refused before anything is enqueued, with svc_last_error(): rows == NULL, n_timesteps < 1, a non-finite temperature or
+ * rate, random_voice on a v1 handle, seeds and args->z both NULL, and everything svc_cfm_sample refuses. */
+int svc_cfm_sample_rows(svc_dit_t* m, const svc_cfm_args_t* args, const svc_cfm_row_t* rows,
+                        const uint64_t* seeds, void* stream);
+/* The partition svc_cfm_sample_rows uses for a handle of `version` (1 or 2); needs no GPU.  class_of[b] (HOST [B]) = class
+ * of row b, classes numbered by first appearance; n_streams[c] (HOST, room for B) = guidance streams of class c (estimator
+ * evaluations per step: 1, 2 or 3).  Either may be NULL.  Returns the number of classes, < 0 on bad rows (svc_last_error()). */
+int svc_cfm_rows_plan(int version, const svc_cfm_row_t* rows, int B, int32_t* class_of, int32_t* n_streams);
 
 /* Replaces one estimator evaluation `estimator(x, prompt_x, x_lens, t, style, mu)` =
  * DiT.forward (modules/diffusion_transformer.py:486-537, modules/v2/dit_wrapper.py:114-152).

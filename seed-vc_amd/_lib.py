@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libseedvc_hip.so")
 EXPORTS = [
     "svc_abi_version", "svc_last_error",
     "svc_dit_create", "svc_dit_destroy", "svc_dit_set_microbatch", "svc_dit_set_fused_min_rows", "svc_dit_set_fused_seams", "svc_dit_fused_available", "svc_dit_set_graphs", "svc_cfm_sample", "svc_dit_forward",
-    "svc_cfm_sample_seeded", "svc_cfm_noise_draws", "svc_hift_forward_seeded", "svc_hift_noise_draws",
+    "svc_cfm_sample_seeded", "svc_cfm_noise_draws", "svc_cfm_sample_rows", "svc_cfm_rows_plan", "svc_hift_forward_seeded", "svc_hift_noise_draws",
     "svc_bigvgan_create", "svc_bigvgan_destroy", "svc_bigvgan_forward", "svc_bigvgan_forward_ragged", "svc_bigvgan_set_microbatch",
     "svc_hift_create", "svc_hift_destroy", "svc_hift_forward", "svc_hift_forward_ragged", "svc_hift_set_microbatch",
     "svc_anti_alias_act_fwd",
@@ -66,6 +66,11 @@ class CfmArgs(C.Structure):
                 ("x_lens", C.POINTER(C.c_int64)), ("prompt_lens", C.POINTER(C.c_int64)),
                 ("n_timesteps", C.c_int), ("temperature", C.c_float), ("cfg_rate", C.c_float * 2),
                 ("random_voice", C.c_int), ("out", C.c_void_p)]
+
+
+class CfmRow(C.Structure):
+    """svc_cfm_row_t: the sampler settings of one utterance (svc_cfm_sample_rows)."""
+    _fields_ = [("n_timesteps", C.c_int32), ("temperature", C.c_float), ("cfg_rate", C.c_float * 2), ("random_voice", C.c_int32)]
 
 
 class BigVGANConfig(C.Structure):
@@ -244,6 +249,9 @@ def lib():
         # seeded noise: 64-bit seeds by value and as HOST arrays
         l.svc_cfm_sample_seeded.argtypes = [C.c_void_p, C.POINTER(CfmArgs), C.POINTER(C.c_uint64), C.c_void_p]
         l.svc_cfm_noise_draws.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        # per-utterance sampler settings: the rows, the seeds and the plan's outputs as HOST arrays
+        l.svc_cfm_sample_rows.argtypes = [C.c_void_p, C.POINTER(CfmArgs), C.POINTER(CfmRow), C.POINTER(C.c_uint64), C.c_void_p]
+        l.svc_cfm_rows_plan.argtypes = [C.c_int, C.POINTER(CfmRow), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         l.svc_hift_forward_seeded.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_uint64),
                                               C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         l.svc_hift_noise_draws.argtypes = [C.c_uint64, C.c_int, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p]

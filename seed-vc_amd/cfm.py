@@ -32,6 +32,42 @@ def _cfg_struct(cfg):
     return c
 
 
+def sampler_setting(entry, what="settings"):
+    """One utterance's sampler settings -> (n_timesteps, (rate_a, rate_b), temperature, random_voice).  entry: a dict with
+    the keys n_timesteps, inference_cfg_rate and optionally temperature (1.0), random_voice (False), or a tuple in that
+    order.  A rate is a float (v2: both rates) or a pair, as `CFM.inference` takes it."""
+    if isinstance(entry, dict):
+        unknown = set(entry) - {"n_timesteps", "inference_cfg_rate", "temperature", "random_voice"}
+        if unknown or "n_timesteps" not in entry or "inference_cfg_rate" not in entry:
+            raise ValueError(f"{what}: an entry needs n_timesteps and inference_cfg_rate (optional: temperature, random_voice), "
+                             f"got the keys {sorted(entry)}")
+        entry = (entry["n_timesteps"], entry["inference_cfg_rate"], entry.get("temperature", 1.0), entry.get("random_voice", False))
+    if not isinstance(entry, (list, tuple)) or not 2 <= len(entry) <= 4:
+        raise ValueError(f"{what}: an entry is a dict or (n_timesteps, inference_cfg_rate[, temperature[, random_voice]]), got {entry!r}")
+    steps, rate = entry[0], entry[1]
+    temperature = entry[2] if len(entry) > 2 else 1.0
+    random_voice = entry[3] if len(entry) > 3 else False
+    if isinstance(rate, (list, tuple)):
+        if len(rate) != 2:
+            raise ValueError(f"{what}: a pair of rates has two entries, got {rate!r}")
+        rate = (float(rate[0]), float(rate[1]))
+    else:
+        rate = (float(rate), float(rate))
+    return int(steps), rate, float(temperature), bool(random_voice)
+
+
+def _rows_struct(settings, B, what):
+    """settings (B entries of `sampler_setting`) -> the HOST svc_cfm_row_t array."""
+    settings = list(settings)
+    if len(settings) != B:
+        raise ValueError(f"{what}: {len(settings)} settings for {B} utterances")
+    rows = (_lib.CfmRow * B)()
+    for r, e in zip(rows, settings):
+        r.n_timesteps, (r.cfg_rate[0], r.cfg_rate[1]), r.temperature, rv = sampler_setting(e, what)
+        r.random_voice = int(rv)
+    return rows
+
+
 class Estimator:
     """Packed DiT on one device (mirror of `CFM.estimator`)."""
 
@@ -157,6 +193,56 @@ class CFM:
                 _lib.check(_lib.lib().svc_cfm_sample_seeded(self.estimator._h, C.byref(a), seeds_keep, _lib.stream_ptr()))
             else:
                 _lib.check(_lib.lib().svc_cfm_sample(self.estimator._h, C.byref(a), _lib.stream_ptr()))
+        return out
+
+    def rows_plan(self, settings):
+        """The partition `inference_rows` uses for these settings (`svc_cfm_rows_plan`; needs no GPU) ->
+        (class_of, n_streams): class_of[b] = class of utterance b, classes numbered by first appearance; n_streams[c] =
+        guidance streams (estimator evaluations per step) of class c.  Two utterances share a class, and with it every
+        launch, when they have the same n_timesteps and the same guidance structure (include/seedvc_hip.h)."""
+        settings = list(settings)
+        B = len(settings)
+        rows = _rows_struct(settings, B, "CFM.rows_plan")
+        class_of, n_streams = (C.c_int32 * max(B, 1))(), (C.c_int32 * max(B, 1))()
+        n = _lib.lib().svc_cfm_rows_plan(int(self.cfg["version"]), rows, B, class_of, n_streams)
+        if n < 0:
+            raise ValueError(_lib.lib().svc_last_error().decode())
+        return list(class_of[:B]), list(n_streams[:n])
+
+    @torch.inference_mode()
+    def inference_rows(self, mu, x_lens, prompt, style, settings, z=None, prompt_lens=None, seeds=None):
+        """`inference` with the steps, the guidance rate(s), the temperature and random_voice of every utterance taken from
+        settings[b] (`sampler_setting`: a dict or (n_timesteps, inference_cfg_rate, temperature=1.0, random_voice=False)) in
+        ONE call (`svc_cfm_sample_rows`).  Utterance b is the B = 1 run `inference(..., *settings[b])` on its own inputs;
+        utterances of one class (`rows_plan`) share every launch whatever their rates and temperatures.  z / seeds as
+        `inference` (neither: torch.randn)."""
+        if seeds is not None and z is not None:
+            raise ValueError("CFM.inference_rows: give seeds or z, not both")
+        B, T = mu.size(0), mu.size(1)
+        seeds_keep = _lib.seeds_host(seeds, B, "CFM.inference_rows") if seeds is not None else None
+        rows = _rows_struct(settings, B, "CFM.inference_rows")
+        dev = self.device
+        with torch.cuda.device(dev):
+            mu, prompt, style = (_lib.f32c(a, dev) for a in (mu, prompt, style))
+            if seeds is None:
+                if z is None:
+                    z = torch.randn([B, self.in_channels, T], device=dev)
+                z = _lib.f32c(z, dev)
+            out = torch.empty(B, self.in_channels, T, device=dev, dtype=torch.float32)
+            a = _lib.CfmArgs()
+            a.B, a.T, a.P = B, T, prompt.size(-1)
+            a.mu, a.prompt, a.style, a.out = (t.data_ptr() for t in (mu, prompt, style, out))
+            a.z = z.data_ptr() if z is not None else None
+            xl = None
+            if x_lens is not None:
+                xl = _lib.int_list(x_lens)
+                if len(xl) == 1 and B > 1:
+                    xl = xl * B
+            lens_keep = _lib.i64_host(xl)
+            plens_keep = _lib.i64_host(prompt_lens)
+            a.x_lens = lens_keep
+            a.prompt_lens = plens_keep
+            _lib.check(_lib.lib().svc_cfm_sample_rows(self.estimator._h, C.byref(a), rows, seeds_keep, _lib.stream_ptr()))
         return out
 
     @torch.inference_mode()

@@ -162,7 +162,8 @@ struct KGemmParams {
     int reflect_min;            // KG_PAD_REFLECT on a sequence shorter than this reflects inside the sequence zero-extended to
                                 // this length (encodec.py pad1d: extra zeros when length <= max_pad); 0 = plain reflect
     const int* seq_len;         // optional per-sequence valid length (positions), overrides a_len
-    const void* zero_page;      // filled in by kgemm_launch
+    const int* a_seq_map;       // optional: the A rows of sequence s start at a_seq_map[s] * a_seq_rows (a gather over sequences)
+    const void* zero_page;     // filled in by kgemm_launch
     float prof_flop_scale;      // launch-timing bookkeeping: algorithmic / issued FLOPs (1/3 for split-precision taps); 0 = 1
     int debug;                  // diagnostics only: bit0 skip tile loads after the first, bit1 skip the epilogue
     int group_n;                // tile order: column tiles walked in groups of this many (0 = all of N); set by kgemm_launch

@@ -12,6 +12,9 @@
 //  * residual stream, ODE state, norms, RoPE, softmax statistics and all accumulators are fp32; GEMM and
 //    attention operands are fp16 (the reference autocasts the same ops to fp16: inference.py:499).
 #include <math.h>
+#include <cmath>
+#include <string>
+#include <utility>
 #include <string.h>
 
 #include <algorithm>
@@ -125,6 +128,10 @@ struct svc_dit {
     std::vector<half_t*> skip16;
     int *d_kvlen, *d_convlen, *d_plen;
     unsigned long long* d_seeds = nullptr;   // [cap_B] seeds of the micro-batch (svc_cfm_sample_seeded)
+    // per-utterance sampler settings of the micro-batch: {c0, ca, cb, temperature} (what the start-state and update kernels
+    // read; a captured loop reads them through this fixed pointer) and the caller's batch row of every member
+    float4* d_rowtab = nullptr;              // [cap_B]
+    int* d_rowmap = nullptr;                 // [cap_B]
     int* d_convlen_w = nullptr;   // conv lengths relative to the head window
     int win0 = 0;                 // first sequence row the output head is evaluated on (0 = all rows)
     float *d_tvals, *d_tfeat, *d_th, *d_t1, *d_t1s, *d_t2, *d_mod, *d_gcond, *d_flmod, *d_stylevec;
@@ -133,13 +140,16 @@ struct svc_dit {
     int pack(const StateDict& sd, hipStream_t st);
     int reserve(int n_streams, int B, int T, int n_steps, hipStream_t st);
     int tables(const std::vector<float>& tvals, hipStream_t st);
+    // row_map: DEVICE [B] or null; set, sequence b reads row row_map[b] of mu / style_dev
     int statics(int n_streams, const int (*flags)[3], int B, int T, const float* mu, const float* style_dev,
-                hipStream_t st);
-    // seeds: HOST [a->B] or null; set, the ODE state starts from the draws of seeds[b0 + b] instead of a->z (noise.h)
-    int run_group(const svc_cfm_args_t* a, const uint64_t* seeds, int b0, int nb, int n_streams, const int (*flags)[3],
-                  const std::vector<float>& tvals, const std::vector<float>& dts, float c0, float ca, float cb,
-                  int stream_a, int stream_b, hipStream_t st);
-    int sample(const svc_cfm_args_t* a, const uint64_t* seeds, hipStream_t st);
+                const int* row_map, hipStream_t st);
+    // One micro-batch of one class: members[0 .. nb) are rows of the caller's batch (any order, need not be adjacent), coef
+    // their {c0, ca, cb, temperature}.  seeds: HOST [a->B] or null; set, the ODE state of member i starts from the draws of
+    // seeds[members[i]] instead of a->z (noise.h)
+    int run_group(const svc_cfm_args_t* a, const uint64_t* seeds, const int* members, const float4* coef, int nb, int n_streams,
+                  const int (*flags)[3], const std::vector<float>& tvals, const std::vector<float>& dts, int stream_a,
+                  int stream_b, hipStream_t st);
+    int sample(const svc_cfm_args_t* a, const svc_cfm_row_t* rows, const uint64_t* seeds, hipStream_t st);
     int body(int n_streams, int B, int T, int step, hipStream_t st);
     int body_fused(int n_streams, int B, int T, int step, bool seam_merge, bool seam_head, hipStream_t st);
     int head(int n_streams, int B, int T, int step, hipStream_t st);
@@ -574,6 +584,8 @@ int svc_dit::reserve(int n_streams, int B, int T, int n_steps, hipStream_t st) {
     d_convlen_w = ws.alloc_n<int>(nseq, st);
     d_plen = ws.alloc_n<int>(cap_B, st);
     d_seeds = ws.alloc_n<unsigned long long>(cap_B, st);
+    d_rowtab = ws.alloc_n<float4>(cap_B, st);
+    d_rowmap = ws.alloc_n<int>(cap_B, st);
     const long Sx = cap_steps;
     d_tvals = ws.alloc_n<float>(Sx, st);
     d_tfeat = ws.alloc_n<float>(Sx * 256, st);
@@ -585,7 +597,7 @@ int svc_dit::reserve(int n_streams, int B, int T, int n_steps, hipStream_t st) {
     d_gcond = ws.alloc_n<float>(Sx * std::max(2L * W * NL, 1L), st);
     d_flmod = ws.alloc_n<float>(Sx * std::max(2 * W, 1), st);
     d_stylevec = ws.alloc_n<float>((long)cap_B * D, st);
-    if (!d_kvlen || !d_convlen || !d_convlen_w || !d_plen || !d_seeds || !d_tvals || !d_tfeat || !d_th || !d_t1 || !d_t1s || !d_t2 || !d_mod ||
+    if (!d_kvlen || !d_convlen || !d_convlen_w || !d_plen || !d_seeds || !d_rowtab || !d_rowmap || !d_tvals || !d_tfeat || !d_th || !d_t1 || !d_t1s || !d_t2 || !d_mod ||
         !d_gcond || !d_flmod || !d_stylevec)
         return 1;
     seq_rows = (int)round_up(T + npre, 8);
@@ -979,10 +991,10 @@ int svc_dit::body_fused(int n_streams, int B, int T, int step, bool seam_merge, 
 // Per-utterance static part of the merge linear for every stream; flags = {use prompt, use style, use content}.
 // Needs prompt32 (token-major prompt, zero beyond each prompt) to be filled already.
 int svc_dit::statics(int n_streams, const int (*flags)[3], int B, int T, const float* mu, const float* style_dev,
-                     hipStream_t st) {
+                     const int* row_map, hipStream_t st) {
     const long Ks = C32 + Dc;
     if (w_style_merge)
-        if (small_linear_launch(style_dev, S, w_style_merge, S, nullptr, d_stylevec, D, B, D, S, KG_ACT_NONE, st)) return 1;
+        if (small_linear_launch(style_dev, S, w_style_merge, S, nullptr, d_stylevec, D, B, D, S, KG_ACT_NONE, st, row_map)) return 1;
     for (int j = 0; j < n_streams; ++j) {
         const bool use_p = flags[j][0], use_s = flags[j][1], use_m = flags[j][2];
         float* u = u_rowvec + (long)j * B * D;
@@ -991,7 +1003,7 @@ int svc_dit::statics(int n_streams, const int (*flags)[3], int B, int T, const f
         {
             KGemmParams p = gemm_base(B * T, D, T);
             p.a_ptr[0] = mu; p.a_ld[0] = Dc; p.a_ktiles[0] = use_m ? Dc / 32 : 0;
-            p.a_seq_rows = T; p.a_len = T;
+            p.a_seq_rows = T; p.a_len = T; p.a_seq_map = row_map;
             p.w = w_stat + C32; p.ldw = Ks;
             p.c_seq_rows = seq_rows; p.c_off = npre;
             p.c32 = dst; p.ldc32 = D;
@@ -1011,7 +1023,7 @@ int svc_dit::statics(int n_streams, const int (*flags)[3], int B, int T, const f
         if (style_in_w) {
             float* tk = tok_style + (long)j * B * D;
             if (use_s) {
-                if (small_linear_launch(style_dev, S, style_in_w, S, style_in_b, tk, D, B, D, S, KG_ACT_NONE, st)) return 1;
+                if (small_linear_launch(style_dev, S, style_in_w, S, style_in_b, tk, D, B, D, S, KG_ACT_NONE, st, row_map)) return 1;
             } else {
                 if (add_rowvec_launch(tk, nullptr, 0, style_in_b, B, D, st)) return 1;
             }
@@ -1036,11 +1048,12 @@ __global__ void init_state_kernel(float* __restrict__ x, long ldx, half_t* __res
     for (int k = 0; k < n_copies; ++k) x16[k * copy_stride + ((long)b * rows + t) * ldx16 + c] = (half_t)v;
 }
 
-// The seeded start of the ODE: x[b][t][4 c4 .. 4 c4 + 3] = temperature * z of (seeds[b], channel, frame t) drawn here (one
+// The seeded start of the ODE: x[b][t][4 c4 .. 4 c4 + 3] = temperature[b] * z of (seeds[b], channel, frame t) drawn here (one
 // Philox call per four channels), zero for t < prompt_len[b] and in the padding rows t >= T; the fp16 copies of every
 // stream for t < T.  What bct_to_btc_kernel + init_state_kernel leave when they are fed svc_cfm_noise_draws, bit for bit.
-__global__ __launch_bounds__(256) void init_state_seeded_kernel(const unsigned long long* __restrict__ seeds, float temperature,
-                                                                float* __restrict__ x, long ldx, half_t* __restrict__ x16, long ldx16,
+// row_tab[b] = {c0, ca, cb, temperature} of utterance b.
+__global__ __launch_bounds__(256) void init_state_seeded_kernel(const unsigned long long* __restrict__ seeds,
+                                                                const float4* __restrict__ row_tab, float* __restrict__ x, long ldx, half_t* __restrict__ x16, long ldx16,
                                                                 int rows, int B, int T, int C, const int* __restrict__ prompt_len,
                                                                 int n_copies, long copy_stride) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1052,6 +1065,7 @@ __global__ __launch_bounds__(256) void init_state_seeded_kernel(const unsigned l
     float v[4] = {0.f, 0.f, 0.f, 0.f};
     if (t < T && t >= prompt_len[b]) {
         noise_normal4(seeds[b], NOISE_CFM_Z, (unsigned)c4, (unsigned)t, v);
+        const float temperature = row_tab[b].w;
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[j] *= temperature;
     }
@@ -1063,9 +1077,21 @@ __global__ __launch_bounds__(256) void init_state_seeded_kernel(const unsigned l
     }
 }
 
+// One Euler step with classifier-free guidance on one element: x + dt (c0 v - ca v_a - cb v_b).  The only statement of the
+// update: whoever calls it with the same values gets the same bits (one expression, one contraction by the compiler).
+__device__ __forceinline__ float cfm_update(float x, const float* __restrict__ v, long vo, long v_stream_stride, int stream_a,
+                                            int stream_b, float dt, float c0, float ca, float cb) {
+    float d = c0 * v[vo];
+    if (stream_a >= 0) d -= ca * v[vo + stream_a * v_stream_stride];
+    if (stream_b >= 0) d -= cb * v[vo + stream_b * v_stream_stride];
+    return x + dt * d;
+}
+
+// row_tab[b] = {c0, ca, cb, temperature} of utterance b: the guidance rates are per utterance, the streams they weigh
+// (stream_a, stream_b) and dt belong to the launch
 __global__ void euler_kernel(float* __restrict__ x, long ldx, half_t* __restrict__ x16, long ldx16, int rows,
                              const float* __restrict__ v, long ldv, long v_stream_stride, int v_off, int B, int T, int C,
-                             const int* __restrict__ prompt_len, float dt, float c0, float ca, float cb, int stream_a,
+                             const int* __restrict__ prompt_len, float dt, const float4* __restrict__ row_tab, int stream_a,
                              int stream_b, int n_copies, long copy_stride) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long)B * T * C) return;
@@ -1073,31 +1099,31 @@ __global__ void euler_kernel(float* __restrict__ x, long ldx, half_t* __restrict
     const long bt = i / C;
     const int t = (int)(bt % T), b = (int)(bt / T);
     const long vo = ((long)b * rows + v_off + t) * ldv + c;
-    float d = c0 * v[vo];
-    if (stream_a >= 0) d -= ca * v[vo + stream_a * v_stream_stride];
-    if (stream_b >= 0) d -= cb * v[vo + stream_b * v_stream_stride];
+    const float4 k = row_tab[b];
     const long xo = ((long)b * rows + t) * ldx + c;
-    float nx = x[xo] + dt * d;
+    float nx = cfm_update(x[xo], v, vo, v_stream_stride, stream_a, stream_b, dt, k.x, k.y, k.z);
     if (t < prompt_len[b]) nx = 0.f;
     x[xo] = nx;
     for (int k = 0; k < n_copies; ++k) x16[k * copy_stride + ((long)b * rows + t) * ldx16 + c] = (half_t)nx;
 }
 
-// prompt (B, C, P) -> token-major [B][rows][ld], zero beyond each utterance's prompt length
+// prompt (B, C, P) -> token-major [B][rows][ld], zero beyond each utterance's prompt length; row_map (optional): utterance b
+// is row row_map[b] of src
 __global__ void prompt_rows_kernel(const float* __restrict__ src, int C, int P, float* __restrict__ dst, long ld, int rows,
-                                   int T, const int* __restrict__ prompt_len, int B) {
+                                   int T, const int* __restrict__ prompt_len, int B, const int* __restrict__ row_map) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long)B * T * C) return;
     const int t = (int)(i % T);
     const long bc = i / T;
     const int c = (int)(bc % C), b = (int)(bc / C);
-    const float v = (t < prompt_len[b] && t < P) ? src[((long)b * C + c) * P + t] : 0.f;
+    const long sb = row_map ? row_map[b] : b;
+    const float v = (t < prompt_len[b] && t < P) ? src[(sb * C + c) * P + t] : 0.f;
     dst[((long)b * rows + t) * ld + c] = v;
 }
 }  // namespace
 
-int svc_dit::run_group(const svc_cfm_args_t* a, const uint64_t* seeds, int b0, int nb, int n_streams, const int (*flags)[3],
-                       const std::vector<float>& tvals, const std::vector<float>& dts, float c0, float ca, float cb,
+int svc_dit::run_group(const svc_cfm_args_t* a, const uint64_t* seeds, const int* members, const float4* coef, int nb,
+                       int n_streams, const int (*flags)[3], const std::vector<float>& tvals, const std::vector<float>& dts,
                        int stream_a, int stream_b, hipStream_t st) {
     const int T = a->T, P = a->P;
     const int n_steps = (int)tvals.size();
@@ -1105,8 +1131,8 @@ int svc_dit::run_group(const svc_cfm_args_t* a, const uint64_t* seeds, int b0, i
     // lengths
     std::vector<int> kv(n_streams * nb), cv(n_streams * nb), pl(nb);
     for (int b = 0; b < nb; ++b) {
-        const int len = a->x_lens ? (int)a->x_lens[b0 + b] : T;
-        const int plen = a->prompt_lens ? (int)a->prompt_lens[b0 + b] : P;
+        const int len = a->x_lens ? (int)a->x_lens[members[b]] : T;
+        const int plen = a->prompt_lens ? (int)a->prompt_lens[members[b]] : P;
         SVC_REQUIRE(len >= 1 && len <= T, "x_lens out of range");
         SVC_REQUIRE(plen >= 0 && plen <= P && plen <= len, "prompt_lens out of range");
         pl[b] = plen;
@@ -1133,15 +1159,21 @@ int svc_dit::run_group(const svc_cfm_args_t* a, const uint64_t* seeds, int b0, i
     for (size_t i = 0; i < cv.size(); ++i) cvw[i] = cv[i] - (win0 - npre > 0 ? win0 - npre : 0);
     {
         const size_t n = kv.size();
-        const size_t n_int = round_up(3 * n + pl.size(), 2);      // the seeds behind them stay 8-byte aligned
-        int* h = reinterpret_cast<int*>(staging.acquire(n_int * sizeof(int) + (seeds ? (size_t)nb * 8 : 0)));
+        // [kv | cv | cvw | pl | row map] as ints, then the 16-byte settings, then the 8-byte seeds: every part stays aligned
+        const size_t n_int = round_up(3 * n + 2 * (size_t)nb, 4);
+        int* h = reinterpret_cast<int*>(staging.acquire(n_int * sizeof(int) + (size_t)nb * sizeof(float4) + (seeds ? (size_t)nb * 8 : 0)));
         if (!h) return 1;
         memcpy(h, kv.data(), n * 4); memcpy(h + n, cv.data(), n * 4); memcpy(h + 2 * n, cvw.data(), n * 4);
         memcpy(h + 3 * n, pl.data(), pl.size() * 4);
+        memcpy(h + 3 * n + nb, members, (size_t)nb * 4);
+        memcpy(h + n_int, coef, (size_t)nb * sizeof(float4));
         if (seeds) {
-            memcpy(h + n_int, seeds + b0, (size_t)nb * 8);
-            SVC_CHECK_HIP(hipMemcpyAsync(d_seeds, h + n_int, (size_t)nb * 8, hipMemcpyHostToDevice, st));
+            unsigned long long* hs = reinterpret_cast<unsigned long long*>(h + n_int + 4 * (size_t)nb);
+            for (int b = 0; b < nb; ++b) hs[b] = seeds[members[b]];
+            SVC_CHECK_HIP(hipMemcpyAsync(d_seeds, hs, (size_t)nb * 8, hipMemcpyHostToDevice, st));
         }
+        SVC_CHECK_HIP(hipMemcpyAsync(d_rowmap, h + 3 * n + nb, (size_t)nb * 4, hipMemcpyHostToDevice, st));
+        SVC_CHECK_HIP(hipMemcpyAsync(d_rowtab, h + n_int, (size_t)nb * sizeof(float4), hipMemcpyHostToDevice, st));
         SVC_CHECK_HIP(hipMemcpyAsync(d_kvlen, h, n * 4, hipMemcpyHostToDevice, st));
         SVC_CHECK_HIP(hipMemcpyAsync(d_convlen, h + n, n * 4, hipMemcpyHostToDevice, st));
         SVC_CHECK_HIP(hipMemcpyAsync(d_convlen_w, h + 2 * n, n * 4, hipMemcpyHostToDevice, st));
@@ -1155,33 +1187,34 @@ int svc_dit::run_group(const svc_cfm_args_t* a, const uint64_t* seeds, int b0, i
     // ODE state from z (temperature-scaled), prompt frames zeroed (flow_matching.py:50,76-79)
     if (seeds) {
         hipLaunchKernelGGL(init_state_seeded_kernel, dim3(cdiv((long)nb * seq_rows * (C / 4), 256)), dim3(256), 0, st, d_seeds,
-                           a->temperature, x32, (long)C16, x16, (long)C16, seq_rows, nb, T, C, d_plen, n_streams, copy_stride);
+                           (const float4*)d_rowtab, x32, (long)C16, x16, (long)C16, seq_rows, nb, T, C, d_plen, n_streams, copy_stride);
     } else {
-        if (bct_to_btc_launch(a->z + (long)b0 * C * T, nb, C, T, x32, C16, nullptr, 0, seq_rows, T, a->temperature, st)) return 1;
+        if (bct_to_btc_launch(a->z, nb, C, T, x32, C16, nullptr, 0, seq_rows, T, 1.0f, st, d_rowmap, d_rowtab)) return 1;
         hipLaunchKernelGGL(init_state_kernel, dim3(cdiv(n_el, 256)), dim3(256), 0, st, x32, (long)C16, x16, (long)C16, seq_rows,
                            nb, T, C, d_plen, n_streams, copy_stride);
     }
     SVC_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(prompt_rows_kernel, dim3(cdiv(n_el, 256)), dim3(256), 0, st, a->prompt + (long)b0 * C * P, C, P,
-                       prompt32, (long)C32, seq_rows, T, d_plen, nb);
+    hipLaunchKernelGGL(prompt_rows_kernel, dim3(cdiv(n_el, 256)), dim3(256), 0, st, a->prompt, C, P, prompt32, (long)C32,
+                       seq_rows, T, d_plen, nb, (const int*)d_rowmap);
     SVC_CHECK_HIP(hipGetLastError());
-    if (statics(n_streams, flags, nb, T, a->mu + (long)b0 * T * Dc, a->style + (long)b0 * S, st)) return 1;
+    if (statics(n_streams, flags, nb, T, a->mu, a->style, d_rowmap, st)) return 1;
 
     auto steps = [&](hipStream_t s_) -> int {
         for (int s = 0; s < n_steps; ++s) {
             if (body(n_streams, nb, T, s, s_)) return 1;
             hipLaunchKernelGGL(euler_kernel, dim3(cdiv(n_el, 256)), dim3(256), 0, s_, x32, (long)C16, x16, (long)C16, seq_rows,
-                               v32, (long)C16, (long)nb * seq_rows * C16, npre, nb, T, C, d_plen, dts[s], c0, ca, cb,
-                               stream_a, stream_b, n_streams, copy_stride);
+                               v32, (long)C16, (long)nb * seq_rows * C16, npre, nb, T, C, d_plen, dts[s],
+                               (const float4*)d_rowtab, stream_a, stream_b, n_streams, copy_stride);
             SVC_CHECK_HIP(hipGetLastError());
         }
         return 0;
     };
-    // Everything the loop's kernel arguments depend on besides the (fixed) workspace pointers.
+    // Everything the loop's kernel arguments depend on besides the (fixed) workspace pointers: the class shape.  The rates and
+    // temperatures are not in it; the loop reads them from d_rowtab, which every call fills before it launches or replays.
     static const int graph_env = [] { const char* e = getenv("SVC_DIT_GRAPH"); return e ? (e[0] == '0' ? 0 : 1) : -1; }();
     bool done = false;
     if ((graph_env >= 0 ? graph_env : use_graphs) && !prof_enabled()) {
-        std::vector<float> key = {(float)n_streams, (float)nb, (float)T, (float)n_steps, (float)win0, (float)seq_rows, c0, ca, cb,
+        std::vector<float> key = {(float)n_streams, (float)nb, (float)T, (float)n_steps, (float)win0, (float)seq_rows,
                                   (float)stream_a, (float)stream_b, (float)fused_min_rows, (float)seams};
         key.insert(key.end(), dts.begin(), dts.end());
         StepGraph* g = nullptr;
@@ -1213,7 +1246,7 @@ int svc_dit::run_group(const svc_cfm_args_t* a, const uint64_t* seeds, int b0, i
         }
     }
     if (!done && steps(st)) return 1;
-    return btc_to_bct_launch(x32, C16, seq_rows, a->out + (long)b0 * C * T, nb, C, T, st);
+    return btc_to_bct_launch(x32, C16, seq_rows, a->out, nb, C, T, st, d_rowmap);
 }
 
 // --------------------------------------------------------------------------------------------- C ABI
@@ -1303,70 +1336,166 @@ int svc_dit_set_graphs(svc_dit_t* m, int on) {
 
 int svc_cfm_sample(svc_dit_t* m, const svc_cfm_args_t* a, void* stream) {
     SVC_REQUIRE(m && a, "null argument");
-    return m->sample(a, nullptr, (hipStream_t)stream);
+    return m->sample(a, nullptr, nullptr, (hipStream_t)stream);
 }
 
 int svc_cfm_sample_seeded(svc_dit_t* m, const svc_cfm_args_t* a, const uint64_t* seeds, void* stream) {
     SVC_REQUIRE(m && a, "null argument");
     SVC_REQUIRE(seeds, "svc_cfm_sample_seeded: seeds is NULL (HOST [B], one per utterance)");
-    return m->sample(a, seeds, (hipStream_t)stream);
+    return m->sample(a, nullptr, seeds, (hipStream_t)stream);
+}
+
+int svc_cfm_sample_rows(svc_dit_t* m, const svc_cfm_args_t* a, const svc_cfm_row_t* rows, const uint64_t* seeds, void* stream) {
+    SVC_REQUIRE(m && a, "svc_cfm_sample_rows: null handle or arguments");
+    SVC_REQUIRE(rows, "svc_cfm_sample_rows: rows is NULL (HOST [B], one per utterance)");
+    SVC_REQUIRE(seeds || a->z, "svc_cfm_sample_rows: seeds and args->z are both NULL");
+    return m->sample(a, rows, seeds, (hipStream_t)stream);
 }
 
 }  // extern "C"
 
-// svc_cfm_sample (seeds null: the ODE starts from a->z) and svc_cfm_sample_seeded (a->z ignored)
-int svc_dit::sample(const svc_cfm_args_t* a, const uint64_t* seeds, hipStream_t st) {
+namespace {
+// Guidance structure of a row = the branch the sampler takes for it (flow_matching.py:84-101, v2/cfm.py:77-125)
+enum { CFG_V1_PLAIN = 0, CFG_V1_GUIDED, CFG_V2_RANDOM_VOICE, CFG_V2_PLAIN, CFG_V2_SIMILARITY, CFG_V2_INTELLIGIBILITY, CFG_V2_BOTH };
+
+int cfg_structure(bool v2, const svc_cfm_row_t& r) {
+    const float ra = r.cfg_rate[0], rb = r.cfg_rate[1];
+    if (!v2) return ra > 0.f ? CFG_V1_GUIDED : CFG_V1_PLAIN;
+    if (r.random_voice) return CFG_V2_RANDOM_VOICE;
+    if (ra == 0.f && rb == 0.f) return CFG_V2_PLAIN;
+    if (ra == 0.f) return CFG_V2_SIMILARITY;
+    if (rb == 0.f) return CFG_V2_INTELLIGIBILITY;
+    return CFG_V2_BOTH;
+}
+
+int cfg_streams(int structure) {
+    return structure == CFG_V1_PLAIN || structure == CFG_V2_PLAIN ? 1 : structure == CFG_V2_BOTH ? 3 : 2;
+}
+
+// {c0, ca, cb, temperature} of a row: the update is x += dt (c0 v - ca v_a - cb v_b)
+float4 cfg_coef(int structure, const svc_cfm_row_t& r) {
+    const float ra = r.cfg_rate[0], rb = r.cfg_rate[1];
+    float c0 = 1.f, ca = 0.f, cb = 0.f;
+    switch (structure) {
+        case CFG_V1_GUIDED: case CFG_V2_RANDOM_VOICE: case CFG_V2_INTELLIGIBILITY: c0 = 1.f + ra; ca = ra; break;
+        case CFG_V2_SIMILARITY: c0 = 1.f + rb; ca = rb; break;
+        case CFG_V2_BOTH: c0 = 1.f + ra + rb; ca = ra; cb = rb; break;
+        default: break;
+    }
+    return make_float4(c0, ca, cb, r.temperature);
+}
+
+// The partition of svc_cfm_rows_plan; `who` prefixes the messages.
+int rows_plan(const char* who, int version, const svc_cfm_row_t* rows, int B, int32_t* class_of, int32_t* n_streams,
+              std::vector<int>* structures) {
+    auto fail = [&](int b, const char* what) {
+        set_error(std::string(who) + ": rows[" + std::to_string(b) + "] " + what);
+        return -1;
+    };
+    if (version != 1 && version != 2) { set_error(std::string(who) + ": version must be 1 or 2"); return -1; }
+    if (!rows || B < 1) { set_error(std::string(who) + ": rows is NULL or B < 1"); return -1; }
+    const bool v2 = version == 2;
+    std::vector<std::pair<int, int>> classes;     // (n_timesteps, structure), by first appearance
+    for (int b = 0; b < B; ++b) {
+        const svc_cfm_row_t& r = rows[b];
+        if (r.n_timesteps < 1) return fail(b, "has n_timesteps < 1");
+        if (!std::isfinite(r.temperature)) return fail(b, "has a non-finite temperature");
+        if (!std::isfinite(r.cfg_rate[0]) || (v2 && !std::isfinite(r.cfg_rate[1]))) return fail(b, "has a non-finite cfg_rate");
+        if (!v2 && r.random_voice) return fail(b, "sets random_voice, which is v2 only");
+        const std::pair<int, int> key(r.n_timesteps, cfg_structure(v2, r));
+        size_t c = 0;
+        while (c < classes.size() && classes[c] != key) ++c;
+        if (c == classes.size()) {
+            classes.push_back(key);
+            if (n_streams) n_streams[c] = cfg_streams(key.second);
+            if (structures) structures->push_back(key.second);
+        }
+        if (class_of) class_of[b] = (int32_t)c;
+    }
+    return (int)classes.size();
+}
+}  // namespace
+
+extern "C" int svc_cfm_rows_plan(int version, const svc_cfm_row_t* rows, int B, int32_t* class_of, int32_t* n_streams) {
+    return rows_plan("svc_cfm_rows_plan", version, rows, B, class_of, n_streams, nullptr);
+}
+
+// svc_cfm_sample (rows and seeds null: one setting from a, the ODE starts from a->z), svc_cfm_sample_seeded (a->z ignored)
+// and svc_cfm_sample_rows (rows: HOST [a->B], the four settings per utterance).  One path: a call without rows is the call
+// with B copies of the setting in a.
+int svc_dit::sample(const svc_cfm_args_t* a, const svc_cfm_row_t* rows, const uint64_t* seeds, hipStream_t st) {
     svc_dit* m = this;
-    SVC_REQUIRE(a->B >= 1 && a->T >= 1 && a->P >= 0 && a->P <= a->T && a->n_timesteps >= 1, "bad sampler shape");
+    SVC_REQUIRE(a->B >= 1 && a->T >= 1 && a->P >= 0 && a->P <= a->T && (rows || a->n_timesteps >= 1), "bad sampler shape");
     SVC_REQUIRE(a->T + m->npre <= ROPE_POS, "sequence longer than the RoPE table");
     SVC_REQUIRE(a->mu && (a->prompt || a->P == 0) && a->style && (a->z || seeds) && a->out, "null tensor");
-    SVC_REQUIRE(current_device() == m->device, "this handle was created on another device (make it current before the call)");
-    const int N = a->n_timesteps;
-    // ---- time grid (fp32, like the reference)
-    std::vector<float> ts = linspace01(N + 1);
-    std::vector<float> tvals(N), dts(N);
-    if (!m->v2) {
-        // flow_matching.py:70,83,105-106 : dt recomputed from t_span every step, t accumulated
-        float t = ts[0];
-        for (int s = 1; s <= N; ++s) {
-            const float dt = ts[s] - ts[s - 1];
-            tvals[s - 1] = t;
-            dts[s - 1] = dt;
-            t = t + dt;
-        }
+    const int B = a->B;
+    std::vector<svc_cfm_row_t> uniform;
+    if (!rows) {
+        svc_cfm_row_t r;
+        r.n_timesteps = a->n_timesteps; r.temperature = a->temperature;
+        r.cfg_rate[0] = a->cfg_rate[0]; r.cfg_rate[1] = a->cfg_rate[1];
+        r.random_voice = m->v2 ? a->random_voice : 0;       // v1 never read it
+        uniform.assign(B, r);
+    }
+    const svc_cfm_row_t* R = rows ? rows : uniform.data();
+    std::vector<int32_t> class_of(B);
+    std::vector<int> structures;
+    int n_classes = 1;
+    if (rows) {
+        n_classes = rows_plan("svc_cfm_sample_rows", m->v2 ? 2 : 1, rows, B, class_of.data(), nullptr, &structures);
+        if (n_classes < 0) return 1;
     } else {
-        // v2/cfm.py:47-48,70,126-129 : cosine warp; dt follows the accumulated t
-        for (auto& v : ts) v = v + (-1.0f) * (cosf((float)M_PI / 2.0f * v) - 1.0f + v);
-        float t = ts[0], dt = ts[1] - ts[0];
-        for (int s = 1; s <= N; ++s) {
-            tvals[s - 1] = t;
-            dts[s - 1] = dt;
-            t = t + dt;
-            if (s < N) dt = ts[s + 1] - t;
+        structures.push_back(cfg_structure(m->v2, R[0]));   // the uniform entries keep today's checks: any rate goes
+    }
+    SVC_REQUIRE(current_device() == m->device, "this handle was created on another device (make it current before the call)");
+    const int mb = m->microbatch > 0 ? m->microbatch : 32;   // measured best on MI355X (tiny, B = 64): 8: 49.8k, 16: 51.7k, 32: 57.2k, 64: 55.7k frames/s
+    std::vector<int> members;
+    std::vector<float4> coef;
+    for (int c = 0; c < n_classes; ++c) {
+        members.clear(); coef.clear();
+        for (int b = 0; b < B; ++b)
+            if (class_of[b] == c) { members.push_back(b); coef.push_back(cfg_coef(structures[c], R[b])); }
+        const int N = R[members[0]].n_timesteps;
+        // ---- time grid (fp32, like the reference)
+        std::vector<float> ts = linspace01(N + 1);
+        std::vector<float> tvals(N), dts(N);
+        if (!m->v2) {
+            // flow_matching.py:70,83,105-106 : dt recomputed from t_span every step, t accumulated
+            float t = ts[0];
+            for (int s = 1; s <= N; ++s) {
+                const float dt = ts[s] - ts[s - 1];
+                tvals[s - 1] = t;
+                dts[s - 1] = dt;
+                t = t + dt;
+            }
+        } else {
+            // v2/cfm.py:47-48,70,126-129 : cosine warp; dt follows the accumulated t
+            for (auto& v : ts) v = v + (-1.0f) * (cosf((float)M_PI / 2.0f * v) - 1.0f + v);
+            float t = ts[0], dt = ts[1] - ts[0];
+            for (int s = 1; s <= N; ++s) {
+                tvals[s - 1] = t;
+                dts[s - 1] = dt;
+                t = t + dt;
+                if (s < N) dt = ts[s + 1] - t;
+            }
         }
-    }
-    // ---- guidance streams
-    int flags[MAX_STREAMS][3] = {{1, 1, 1}, {0, 0, 0}, {0, 0, 0}};
-    int n_streams = 1, sa = -1, sb = -1;
-    float c0 = 1.f, ca = 0.f, cb = 0.f;
-    const float ra = a->cfg_rate[0], rb = a->cfg_rate[1];
-    if (!m->v2) {
-        if (ra > 0.f) { n_streams = 2; sa = 1; c0 = 1.f + ra; ca = ra; }          // flow_matching.py:84-101
-    } else if (a->random_voice) {                                                 // v2/cfm.py:77-87
-        n_streams = 2; flags[0][0] = 0; flags[0][1] = 0; sa = 1; c0 = 1.f + ra; ca = ra;
-    } else if (ra == 0.f && rb == 0.f) {
-        n_streams = 1;
-    } else if (ra == 0.f) {                                                       // similarity only: v2/cfm.py:90-101
-        n_streams = 2; flags[1][2] = 1; sa = 1; c0 = 1.f + rb; ca = rb;
-    } else if (rb == 0.f) {                                                       // v2/cfm.py:102-112
-        n_streams = 2; sa = 1; c0 = 1.f + ra; ca = ra;
-    } else {                                                                      // 3-way: v2/cfm.py:113-125
-        n_streams = 3; flags[1][2] = 1; sa = 2; sb = 1; c0 = 1.f + ra + rb; ca = ra; cb = rb;
-    }
-    int mb = m->microbatch > 0 ? m->microbatch : 32;   // measured best on MI355X (tiny, B = 64): 8: 49.8k, 16: 51.7k, 32: 57.2k, 64: 55.7k frames/s
-    for (int b0 = 0; b0 < a->B; b0 += mb) {
-        const int nb = std::min(mb, a->B - b0);
-        if (m->run_group(a, seeds, b0, nb, n_streams, flags, tvals, dts, c0, ca, cb, sa, sb, st)) return 1;
+        // ---- guidance streams of the class; the rates that weigh them are per row (cfg_coef)
+        int flags[MAX_STREAMS][3] = {{1, 1, 1}, {0, 0, 0}, {0, 0, 0}};
+        int sa = -1, sb = -1;
+        switch (structures[c]) {
+            case CFG_V1_GUIDED: sa = 1; break;                                              // flow_matching.py:84-101
+            case CFG_V2_RANDOM_VOICE: flags[0][0] = 0; flags[0][1] = 0; sa = 1; break;      // v2/cfm.py:77-87
+            case CFG_V2_SIMILARITY: flags[1][2] = 1; sa = 1; break;                         // v2/cfm.py:90-101
+            case CFG_V2_INTELLIGIBILITY: sa = 1; break;                                     // v2/cfm.py:102-112
+            case CFG_V2_BOTH: flags[1][2] = 1; sa = 2; sb = 1; break;                       // 3-way: v2/cfm.py:113-125
+            default: break;
+        }
+        const int n_streams = cfg_streams(structures[c]);
+        const int n_mem = (int)members.size();
+        for (int i0 = 0; i0 < n_mem; i0 += mb) {
+            const int nb = std::min(mb, n_mem - i0);
+            if (m->run_group(a, seeds, members.data() + i0, coef.data() + i0, nb, n_streams, flags, tvals, dts, sa, sb, st)) return 1;
+        }
     }
     return 0;
 }
@@ -1404,9 +1533,9 @@ int svc_dit_forward(svc_dit_t* m, int N, int T, const float* x, const float* pro
     if (bct_to_btc_launch(x, N, C, T, m->x32, C16, m->x16, C16, rows, T, 1.0f, st)) return 1;
     const long n_el = (long)N * T * C;
     hipLaunchKernelGGL(prompt_rows_kernel, dim3(cdiv(n_el, 256)), dim3(256), 0, st, prompt_x, C, T, m->prompt32, (long)C32,
-                       rows, T, m->d_plen, N);
+                       rows, T, m->d_plen, N, (const int*)nullptr);
     SVC_CHECK_HIP(hipGetLastError());
-    if (m->statics(1, flags, N, T, mu, style, st)) return 1;
+    if (m->statics(1, flags, N, T, mu, style, nullptr, st)) return 1;
     if (m->body(1, N, T, 0, st)) return 1;
     return btc_to_bct_launch(m->v32 + (long)m->npre * C16, C16, rows, out, N, C, T, st);
 }

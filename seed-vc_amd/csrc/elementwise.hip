@@ -98,16 +98,21 @@ __global__ __launch_bounds__(256) void layernorm_mod_kernel(const float* __restr
     }
 }
 
-// (B, C, T) fp32 channel-major -> token-major [B][T_rows][ld] fp32 and/or fp16 (zero where t >= t_valid)
+// (B, C, T) fp32 channel-major -> token-major [B][T_rows][ld] fp32 and/or fp16 (zero where t >= t_valid).
+// row_map (optional): sequence b is read from source row row_map[b]; row_tab (optional, svc_cfm_row_coef per sequence):
+// the scale of sequence b is its temperature instead of `scale`.
 __global__ void bct_to_btc_kernel(const float* __restrict__ src, int B, int C, int T_src, float* dst32, long ld32,
-                                  half_t* dst16, long ld16, int seq_rows, int t_valid, float scale) {
+                                  half_t* dst16, long ld16, int seq_rows, int t_valid, float scale,
+                                  const int* __restrict__ row_map, const float4* __restrict__ row_tab) {
     __shared__ float tile[32][33];
     const int b = blockIdx.z;
+    const long sb = row_map ? row_map[b] : b;
+    if (row_tab) scale = row_tab[b].w;
     const int t0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;   // 256 threads: ty 0..7
     for (int i = ty; i < 32; i += 8) {
         const int c = c0 + i, t = t0 + tx;
-        tile[i][tx] = (c < C && t < T_src && t < t_valid) ? src[((long)b * C + c) * T_src + t] * scale : 0.f;
+        tile[i][tx] = (c < C && t < T_src && t < t_valid) ? src[(sb * C + c) * T_src + t] * scale : 0.f;
     }
     __syncthreads();
     for (int i = ty; i < 32; i += 8) {
@@ -120,11 +125,12 @@ __global__ void bct_to_btc_kernel(const float* __restrict__ src, int B, int C, i
     }
 }
 
-// token-major [B][seq_rows][ld] fp32 -> (B, C, T) fp32
+// token-major [B][seq_rows][ld] fp32 -> (B, C, T) fp32; row_map (optional): sequence b is written to destination row row_map[b]
 __global__ void btc_to_bct_kernel(const float* __restrict__ src, long ld, int seq_rows, float* __restrict__ dst, int B,
-                                  int C, int T) {
+                                  int C, int T, const int* __restrict__ row_map) {
     __shared__ float tile[32][33];
     const int b = blockIdx.z;
+    const long db = row_map ? row_map[b] : b;
     const int t0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     for (int i = ty; i < 32; i += 8) {
@@ -134,7 +140,7 @@ __global__ void btc_to_bct_kernel(const float* __restrict__ src, long ld, int se
     __syncthreads();
     for (int i = ty; i < 32; i += 8) {
         const int c = c0 + i, t = t0 + tx;
-        if (c < C && t < T) dst[((long)b * C + c) * T + t] = tile[tx][i];
+        if (c < C && t < T) dst[(db * C + c) * T + t] = tile[tx][i];
     }
 }
 
@@ -183,29 +189,6 @@ __global__ void prefix_rows_kernel(float* __restrict__ xin, int n_seq, int seq_r
     }
 }
 
-// x += dt * ((1 + w_a + w_b) * v0 - w_a * v_a - w_b * v_b); zero the prompt region; refresh the fp16 copy.
-// v: [n_stream][B][seq_rows_v][ldv] (stream 0 = fully conditional); x: [B][T_rows][ldx]
-__global__ void euler_cfg_kernel(float* __restrict__ x, long ldx, half_t* __restrict__ x16, long ldx16, int x_rows,
-                                 const float* __restrict__ v, long ldv, long v_stream_stride, int v_rows, int B, int T,
-                                 int C, const int* __restrict__ prompt_len, float dt, float c0, float ca, float cb,
-                                 int stream_a, int stream_b) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long total = (long)B * T * C;
-    if (i >= total) return;
-    const int c = (int)(i % C);
-    const long bt = i / C;
-    const int t = (int)(bt % T), b = (int)(bt / T);
-    const long vrow = ((long)b * v_rows + t) * ldv + c;
-    float d = c0 * v[vrow];
-    if (stream_a >= 0) d -= ca * v[vrow + stream_a * v_stream_stride];
-    if (stream_b >= 0) d -= cb * v[vrow + stream_b * v_stream_stride];
-    const long xo = ((long)b * x_rows + t) * ldx + c;
-    float nx = x[xo] + dt * d;
-    if (t < prompt_len[b]) nx = 0.f;
-    x[xo] = nx;
-    x16[((long)b * x_rows + t) * ldx16 + c] = (half_t)nx;
-}
-
 // generic strided pack copy with optional per-dim0 scale: dst[i0*d0 + i1*d1 + i2*d2] = src[i0*s0+i1*s1+i2*s2]*scale[i0]
 // lo_part (fp16 only): store the residual v - float(half(v)) instead of half(v) (split-precision operands)
 template <typename OutT>
@@ -240,15 +223,18 @@ __global__ void wn_scale_kernel(const float* __restrict__ g, const float* __rest
 
 // small dense fp32 mat-vec batch used at pack time / per call for conditioning vectors:
 // out[r][n] = act(bias[n] + sum_k in[r][k] * W[n][k])      (one wave per output element group)
+// row_map (optional): input row r is in[row_map[r]]
 __global__ __launch_bounds__(256) void small_linear_kernel(const float* __restrict__ in, long ld_in, const float* __restrict__ W,
                                                            long ldw, const float* __restrict__ bias, float* __restrict__ out,
-                                                           long ld_out, int R, int N, int K, int act) {
+                                                           long ld_out, int R, int N, int K, int act,
+                                                           const int* __restrict__ row_map) {
     const int wave = (blockIdx.x * 256 + threadIdx.x) >> 6;
     const int lane = threadIdx.x & 63;
     if (wave >= R * N) return;
     const int r = wave / N, n = wave - r * N;
+    const long ir = row_map ? row_map[r] : r;
     float s = 0.f;
-    for (int k = lane; k < K; k += 64) s += in[(long)r * ld_in + k] * W[(long)n * ldw + k];
+    for (int k = lane; k < K; k += 64) s += in[ir * ld_in + k] * W[(long)n * ldw + k];
     s = wave_sum(s);
     if (lane == 0) {
         if (bias) s += bias[n];
@@ -295,17 +281,18 @@ int layernorm_mod_launch(const float* x, long ldx, half_t* y, long ldy, const fl
 }
 
 int bct_to_btc_launch(const float* src, int B, int C, int T_src, float* dst32, long ld32, half_t* dst16, long ld16,
-                      int seq_rows, int t_valid, float scale, hipStream_t st) {
+                      int seq_rows, int t_valid, float scale, hipStream_t st, const int* row_map, const float4* row_tab) {
     dim3 grid(cdiv(seq_rows, 32), cdiv(C, 32), B);
     hipLaunchKernelGGL(bct_to_btc_kernel, grid, dim3(256), 0, st, src, B, C, T_src, dst32, ld32, dst16, ld16, seq_rows,
-                       t_valid, scale);
+                       t_valid, scale, row_map, row_tab);
     LAUNCH_CHECK();
     return 0;
 }
 
-int btc_to_bct_launch(const float* src, long ld, int seq_rows, float* dst, int B, int C, int T, hipStream_t st) {
+int btc_to_bct_launch(const float* src, long ld, int seq_rows, float* dst, int B, int C, int T, hipStream_t st,
+                      const int* row_map) {
     dim3 grid(cdiv(T, 32), cdiv(C, 32), B);
-    hipLaunchKernelGGL(btc_to_bct_kernel, grid, dim3(256), 0, st, src, ld, seq_rows, dst, B, C, T);
+    hipLaunchKernelGGL(btc_to_bct_kernel, grid, dim3(256), 0, st, src, ld, seq_rows, dst, B, C, T, row_map);
     LAUNCH_CHECK();
     return 0;
 }
@@ -335,16 +322,6 @@ int prefix_rows_launch(float* xin, int n_seq, int seq_rows, int D, int n_prefix,
     if (n_prefix + (seq_rows - t_rows) == 0) return 0;
     hipLaunchKernelGGL(prefix_rows_kernel, dim3(n_seq), dim3(256), 0, st, xin, n_seq, seq_rows, D, n_prefix, t_rows,
                        tok_time, tok_style, time_first);
-    LAUNCH_CHECK();
-    return 0;
-}
-
-int euler_cfg_launch(float* x, long ldx, half_t* x16, long ldx16, int x_rows, const float* v, long ldv,
-                     long v_stream_stride, int v_rows, int B, int T, int C, const int* prompt_len, float dt, float c0,
-                     float ca, float cb, int stream_a, int stream_b, hipStream_t st) {
-    const long n = (long)B * T * C;
-    hipLaunchKernelGGL(euler_cfg_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, x, ldx, x16, ldx16, x_rows, v, ldv,
-                       v_stream_stride, v_rows, B, T, C, prompt_len, dt, c0, ca, cb, stream_a, stream_b);
     LAUNCH_CHECK();
     return 0;
 }
@@ -386,11 +363,11 @@ int wn_scale_launch(const float* g, const float* v, int rows, long row_elems, fl
 }
 
 int small_linear_launch(const float* in, long ld_in, const float* W, long ldw, const float* bias, float* out, long ld_out,
-                        int R, int N, int K, int act, hipStream_t st) {
+                        int R, int N, int K, int act, hipStream_t st, const int* row_map) {
     const long waves = (long)R * N;
     if (waves == 0) return 0;
     hipLaunchKernelGGL(small_linear_kernel, dim3(cdiv(waves, 4)), dim3(256), 0, st, in, ld_in, W, ldw, bias, out, ld_out,
-                       R, N, K, act);
+                       R, N, K, act, row_map);
     LAUNCH_CHECK();
     return 0;
 }

@@ -137,7 +137,7 @@ __global__ __launch_bounds__(NWV * 64, (NS * (BM + BN) * RB > 80 * 1024) ? 1 : 2
         const int mm = a_ok[i] ? m : 0;
         const int seq = mm / p.Lout;
         const int pos = mm - seq * p.Lout;
-        a_base[i] = seq * p.a_seq_rows + p.a_off;
+        a_base[i] = (p.a_seq_map ? p.a_seq_map[seq] : seq) * p.a_seq_rows + p.a_off;
         a_pos[i] = pos * p.a_stride;
         a_len[i] = p.seq_len ? p.seq_len[seq] : p.a_len;
     }

@@ -132,6 +132,19 @@ def _cfm_seeds(seeds):
 LOG_MEL_FLOOR = -11.512925464970229        # log(1e-5): the mel front-end's clamp (modules/audio.py:45-82)
 
 
+def _file_settings(what, sampler, n, n_timesteps, inference_cfg_rate, random_voice=False):
+    """`sampler=` of the long-form entry points -> None (sampler is None: the calls made without it), or one
+    `cfm.sampler_setting` tuple per file, a file whose entry is None getting the call's arguments."""
+    if sampler is None:
+        return None
+    from .cfm import sampler_setting
+    sampler = list(sampler)
+    if len(sampler) != n:
+        raise ValueError(f"{what}: {len(sampler)} sampler entries for {n} files")
+    call = sampler_setting((n_timesteps, inference_cfg_rate, 1.0, random_voice), what)
+    return [call if e is None else sampler_setting(e, f"{what}: sampler[{u}]") for u, e in enumerate(sampler)]
+
+
 def _stack_prompts(records, device=None):
     """records: [(prompt_condition (1, P_b, Dc), mel (1, C, P_b), style (1, Ds))], one per reference -> dict(prompt_condition
     (n, Pmax, Dc), mel (n, C, Pmax), style (n, Ds), P = [P_b], Pmax), zero beyond each P_b."""
@@ -338,16 +351,19 @@ def _row_views(vc, S, calls):
 
 
 def _long_pool(cfm, vocoder, utterances, n_timesteps, inference_cfg_rate, hop, max_context_window, overlap_frame_len, noise_fn,
-               vocoder_kwargs_fn, max_chunks, ragged_vocoder, seeds, seed_kw, cfm_kwargs=None):
+               vocoder_kwargs_fn, max_chunks, ragged_vocoder, seeds, seed_kw, cfm_kwargs=None, sampler=None):
     """The chunk pool of `HotPath.convert_long_batch` and of the timbre branch of `V2HotPath.convert_long_batch`, behind their
     argument checks: `long_batch_plan`, then per micro-batch `svc_chunks_gather_cond` -> one `cfm.inference` with per-row
     x_lens / prompt_lens -> `_strip_prompt` -> `_vocode` -> rows of one wave buffer, one `svc_chunks_assemble` and one host
     synchronisation at the end.  utterances, noise_fn, vocoder_kwargs_fn, ragged_vocoder (a bool here) and seeds (host
     integers or None) as `HotPath.convert_long_batch` documents them; seed_kw: `_vocode`'s; cfm_kwargs: further keywords of
-    every sampler call (the v2 caller's `random_voice`)."""
+    every sampler call (the v2 caller's `random_voice`); sampler: None, or per file a `cfm.sampler_setting` entry or None
+    (checked by `_file_settings`): every chunk of a file then runs with its file's entry, the micro-batch in one
+    `cfm.inference_rows` call."""
     U = len(utterances)
     if U == 0:
         return []
+    file_settings = _file_settings("convert_long_batch", sampler, U, n_timesteps, inference_cfg_rate, **(cfm_kwargs or {}))
     for u, (cond, pc, mel2, style2) in enumerate(utterances):
         if pc.size(1) != mel2.size(2):
             raise ValueError(f"convert_long_batch: utterance {u}: prompt_condition has {pc.size(1)} frames, mel2 {mel2.size(2)}")
@@ -404,8 +420,12 @@ def _long_pool(cfm, vocoder, utterances, n_timesteps, inference_cfg_rate, hop, m
                     z[i, :, :t_k] = noise_fn(t_k)[0]
             kws = [vocoder_kwargs_fn(s) for s in S] if vocoder_kwargs_fn is not None else None
             mb_seeds = chunk_seeds[k0:k1] if chunk_seeds is not None else None
-            mel = cfm.inference(mu, x_lens, mel_chunks[k0:k1], style_chunks[k0:k1], None, n_timesteps, inference_cfg_rate=inference_cfg_rate,
-                                z=z, prompt_lens=Pk, **_cfm_seeds(mb_seeds), **(cfm_kwargs or {}))
+            if file_settings is None:
+                mel = cfm.inference(mu, x_lens, mel_chunks[k0:k1], style_chunks[k0:k1], None, n_timesteps, inference_cfg_rate=inference_cfg_rate,
+                                    z=z, prompt_lens=Pk, **_cfm_seeds(mb_seeds), **(cfm_kwargs or {}))
+            else:
+                mel = cfm.inference_rows(mu, x_lens, mel_chunks[k0:k1], style_chunks[k0:k1], [file_settings[c[0]] for c in mb],
+                                         z=z, prompt_lens=Pk, **_cfm_seeds(mb_seeds))
             vc = _strip_prompt(mel, Pk, x_lens, max(S))
             for call in _vocode(vocoder, vc, S, ragged_vocoder, "convert_long_batch", hop=hop, seeds=mb_seeds,
                                 seed_kw=seed_kw, row_kwargs=kws):
@@ -555,7 +575,7 @@ class HotPath:
 
     @torch.inference_mode()
     def convert_long_batch(self, utterances, n_timesteps, inference_cfg_rate, hop, max_context_window, overlap_frame_len=16,
-                           noise_fn=None, vocoder_kwargs_fn=None, max_chunks=64, ragged_vocoder=None, seeds=None):
+                           noise_fn=None, vocoder_kwargs_fn=None, max_chunks=64, ragged_vocoder=None, seeds=None, *, sampler=None):
         """Long-form conversion of one or more files with every chunk in ONE pool: a chunk reads the source, its file's
         prompt and fresh noise, never its neighbour, so the chunks of all files go through the sampler and the vocoder as
         ragged batches of up to `max_chunks` chunks, and one launch cross-fades and concatenates them (`svc_chunks_assemble`:
@@ -581,6 +601,10 @@ class HotPath:
         sampler noise and, if the vocoder draws (`_vocoder_seeds`), its source draws from `derive_seed(seeds[u], k)`, on the
         device and inside the batched calls -- a file's audio is then a function of its own inputs and seed, whatever shares
         the pool.  The ragged call of such a vocoder is allowed with seeds (ragged_vocoder=True): there are no positional draws.
+        sampler: per file a sampler setting -- a dict or (n_timesteps, inference_cfg_rate, temperature=1.0) as
+        `CFM.inference_rows` takes it -- or None for the call's arguments; every chunk of a file uses its file's entry and a
+        micro-batch is still one sampler call (`CFM.inference_rows`: files of one class share its launches).  sampler=None:
+        every call is made with n_timesteps / inference_cfg_rate, as without the keyword.
         One host synchronisation, at the end."""
         if seeds is not None and (noise_fn is not None or vocoder_kwargs_fn is not None):
             raise ValueError("convert_long_batch: give seeds or noise_fn / vocoder_kwargs_fn, not both")
@@ -592,7 +616,7 @@ class HotPath:
             raise ValueError("convert_long_batch: vocoder_kwargs_fn pins per-chunk draws of a plain vocoder call; "
                              "it cannot be combined with the ragged vocoder call")
         return _long_pool(self.cfm, self.vocoder, utterances, n_timesteps, inference_cfg_rate, hop, max_context_window, overlap_frame_len,
-                          noise_fn, vocoder_kwargs_fn, max_chunks, ragged_vocoder, seeds, self._vocoder_seeds)
+                          noise_fn, vocoder_kwargs_fn, max_chunks, ragged_vocoder, seeds, self._vocoder_seeds, sampler=sampler)
 
 
 # ----------------------------------------------------------------------------------------- v2: tokens in, audio out
@@ -802,7 +826,7 @@ class V2HotPath:
     def convert_long_batch(self, files, n_timesteps, cfg_rates=(0.7, 0.7), *, max_context_window, hop, convert_style=True,
                            anonymization_only=False, random_voice=False, ar_chunk_tokens=1000, overlap_frame_len=16, top_p=0.7,
                            temperature=0.7, repetition_penalty=1.5, max_new=4001, seeds=None, exp_noise_fn=None, noise_fn=None,
-                           max_chunks=64, steps_per_run=16, return_parts=False):
+                           max_chunks=64, steps_per_run=16, return_parts=False, sampler=None):
         """Whole files through the v2 chain, every chunk of every file in ONE pool: `convert_voice_with_streaming`
         (modules/v2/vc_wrapper.py, quoted from memory: correct it here if the reference differs).  The reference loops over
         chunks one after the other; its chunks read the same target, disjoint ranges of the source and fresh draws, never each
@@ -839,6 +863,11 @@ class V2HotPath:
         timbre branch has no AR draws).  With neither, the AR seeds come from torch's CPU generator as in `generate_batch` and
         the sampler noise is one torch.randn per micro-batch.
 
+        sampler: per file a sampler setting -- a dict or (n_timesteps, inference_cfg_rate, temperature=1.0, random_voice=False),
+        a rate being a float or the pair (intelligibility, similarity) -- or None for the call's n_timesteps / cfg_rates /
+        random_voice; every chunk of a file uses its file's entry, in both branches, and a micro-batch stays one sampler call
+        (`CFM.inference_rows`).  sampler=None: the calls made without the keyword.
+
         return_parts (style branch): -> (waves, parts), parts[u] a list with one dict(tokens (1, n), ylen, mel (1, C, ylen),
         wave (1, ylen * hop), kept) per chunk of file u."""
         U, dev = len(files), self.device
@@ -851,8 +880,9 @@ class V2HotPath:
             if exp_noise_fn is not None or return_parts:
                 raise ValueError("convert_long_batch: exp_noise_fn and return_parts belong to the style branch (convert_style=True)")
             return self._convert_long_timbre(files, n_timesteps, cfg_rates, random_voice, hop, max_context_window, overlap_frame_len,
-                                             noise_fn, max_chunks, seeds)
+                                             noise_fn, max_chunks, seeds, sampler)
         v2_chunk_plan(0, ar_chunk_tokens)          # its ValueError, with or without files
+        file_settings = _file_settings("convert_long_batch", sampler, U, n_timesteps, list(cfg_rates), random_voice)
         if U == 0:
             return ([], []) if return_parts else []
         # (file, chunk of the file, first token, tokens, is_last), file-major
@@ -949,9 +979,14 @@ class V2HotPath:
                             z[i, :, :x_lens[i]] = _lib.f32c(noise_fn(plan[k][0], plan[k][1], x_lens[i]), dev)[0]
                     mb_seeds = [chunk_seeds[k] for k in ks] if chunk_seeds is not None else None
                     try:
-                        mel = self.cfm.inference(mu, x_lens, mel_chunks[m0:m0 + n], style_chunks[m0:m0 + n], None, n_timesteps,
-                                                 inference_cfg_rate=list(cfg_rates), random_voice=random_voice, z=z, prompt_lens=Pk,
-                                                 **_cfm_seeds(mb_seeds))
+                        if file_settings is None:
+                            mel = self.cfm.inference(mu, x_lens, mel_chunks[m0:m0 + n], style_chunks[m0:m0 + n], None, n_timesteps,
+                                                     inference_cfg_rate=list(cfg_rates), random_voice=random_voice, z=z, prompt_lens=Pk,
+                                                     **_cfm_seeds(mb_seeds))
+                        else:
+                            mel = self.cfm.inference_rows(mu, x_lens, mel_chunks[m0:m0 + n], style_chunks[m0:m0 + n],
+                                                          [file_settings[plan[k][0]] for k in ks], z=z, prompt_lens=Pk,
+                                                          **_cfm_seeds(mb_seeds))
                     except RuntimeError as e:
                         i = max(range(n), key=lambda i: x_lens[i])
                         raise RuntimeError(f"convert_long_batch: file {plan[ks[i]][0]}, chunk {plan[ks[i]][1]}: the sampler refused "
@@ -983,7 +1018,7 @@ class V2HotPath:
         return (result, parts) if return_parts else result
 
     def _convert_long_timbre(self, files, n_timesteps, cfg_rates, random_voice, hop, max_context_window, overlap_frame_len, noise_fn,
-                             max_chunks, seeds):
+                             max_chunks, seeds, sampler=None):
         """The timbre branch of `convert_long_batch`: the CFM regulator over the files' wide tokens, then `_long_pool`."""
         U, dev = len(files), self.device
         if U == 0:
@@ -1014,7 +1049,7 @@ class V2HotPath:
                 pool_noise = lambda T: noise_fn(*next(it), T)          # noqa: E731
             result = _long_pool(self.cfm, self.vocoder, utterances, n_timesteps, list(cfg_rates), hop, max_context_window, overlap_frame_len,
                                 pool_noise, None, max_chunks, self.ragged_vocoder, seeds, lambda s: _vocoder_seeds(self.vocoder, s),
-                                dict(random_voice=True) if random_voice else None)
+                                dict(random_voice=True) if random_voice else None, sampler=sampler)
             self._mark("pool")
         return result
 
@@ -1152,6 +1187,7 @@ class RealtimeEngine:
         self._speech = {}                   # slot -> the caller's VAD flag (`set_speech`)
         self._gate = {}                     # slot -> gate threshold as an energy of 4 zc samples (`set_gate`); absent: off
         self._vad = None                    # `attach_vad`: the device-resident VAD of `step_audio`
+        self._sampler = {}                  # slot -> (n_timesteps, inference_cfg_rate, temperature), None = the step call's (`set_sampler`)
 
     def open(self, prompt_condition, mel2, style2):
         """A new stream on the reference (prompt_condition (1, P, Dc), mel2 (1, C, P), style2 (1, Ds)) -> its slot, the
@@ -1172,6 +1208,7 @@ class RealtimeEngine:
         self._zero_audio(slot)
         self._speech[slot] = True
         self._gate.pop(slot, None)
+        self._sampler.pop(slot, None)
         self._zero_vad(slot, on=False)
         return slot
 
@@ -1187,6 +1224,7 @@ class RealtimeEngine:
         self._stacked = (None, None)
         self._speech.pop(slot, None)
         self._gate.pop(slot, None)
+        self._sampler.pop(slot, None)
         self._zero_vad(slot, on=False)
 
     def reset(self, slot):
@@ -1251,6 +1289,24 @@ class RealtimeEngine:
         if slot not in self._gate:          # energies are tracked only by gated pushes: a gate switched on starts from none
             self._audio["gate_e"][slot].zero_()
         self._gate[slot] = p
+
+    def set_sampler(self, slot, n_timesteps=None, inference_cfg_rate=None, temperature=None):
+        """The GUI's `diffusion_steps` and `inference_cfg_rate` (and the sampler temperature) for one stream.  None: what the
+        step call says (temperature: 1.0), the default on `open`; kept across `reset`.  While no listed slot has an override a
+        step is the one `cfm.inference` call it always was; otherwise it is one `cfm.inference_rows` call, in which streams of
+        one class (same steps, guided or not) share every launch whatever their rates."""
+        self._check_slot(slot, "set_sampler")
+        if n_timesteps is not None and int(n_timesteps) < 1:
+            raise ValueError(f"RealtimeEngine.set_sampler: n_timesteps = {n_timesteps!r}")
+        for name, v in (("inference_cfg_rate", inference_cfg_rate), ("temperature", temperature)):
+            if v is not None and not math.isfinite(float(v)):
+                raise ValueError(f"RealtimeEngine.set_sampler: {name} = {v!r}")
+        if n_timesteps is None and inference_cfg_rate is None and temperature is None:
+            self._sampler.pop(slot, None)
+        else:
+            self._sampler[slot] = (None if n_timesteps is None else int(n_timesteps),
+                                   None if inference_cfg_rate is None else float(inference_cfg_rate),
+                                   None if temperature is None else float(temperature))
 
     def attach_vad(self, vad):
         """A device-resident VAD (seedvc_amd.vad.FsmnVad) for `step_audio`: needs `attach_audio` with a 16 kHz
@@ -1346,8 +1402,13 @@ class RealtimeEngine:
                 raise ValueError(f"RealtimeEngine.step: the length regulator gave {cond.size(1)} frames, {S} expected")
             mu = _assemble_cond(st["prompt_condition"], P, cond, [S] * n, st["Pmax"] + S)
             x_lens = [p + S for p in P]
-            mel = self.cfm.inference(mu, x_lens, st["mel"], st["style"], None, n_timesteps, inference_cfg_rate=inference_cfg_rate,
-                                     z=z, prompt_lens=P, **_cfm_seeds(seeds))
+            if not any(s in self._sampler for s in slots):
+                mel = self.cfm.inference(mu, x_lens, st["mel"], st["style"], None, n_timesteps, inference_cfg_rate=inference_cfg_rate,
+                                         z=z, prompt_lens=P, **_cfm_seeds(seeds))
+            else:                                                                # per-slot sampler settings: still one call
+                call = (n_timesteps, inference_cfg_rate, 1.0)
+                settings = [tuple(c if o is None else o for o, c in zip(self._sampler.get(s, (None,) * 3), call)) for s in slots]
+                mel = self.cfm.inference_rows(mu, x_lens, st["mel"], st["style"], settings, z=z, prompt_lens=P, **_cfm_seeds(seeds))
             vc = _strip_prompt(mel, P, x_lens, S)
             calls = _vocode(self.vocoder, vc, [S] * n, False, "RealtimeEngine.step", hop=self.hop, seeds=seeds,
                             vocoder_kwargs=vocoder_kwargs)                   # every row has S frames: one plain call
