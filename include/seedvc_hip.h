@@ -364,7 +364,15 @@ int svc_ar_retire(svc_ar_t* m, int slot, void* stream);
 int svc_ar_session_active(svc_ar_t* m);               /* occupied slots; 0 = no session */
 /* Replaces `sample(logits, previous_tokens, suppress_tokens, temperature, top_p, repetition_penalty)`
  * (modules/v2/ar.py:712-763): repetition penalty, top-p, temperature softmax, argmax(probs / q) with q = exp_noise
- * (the Exp(1) draw of multinomial_sample_one_no_sync, supplied by the caller).  suppress_token < 0 = none. */
+ * (the Exp(1) draw of multinomial_sample_one_no_sync, supplied by the caller).  suppress_token < 0 = none;
+ * suppress_token >= vocab is refused.  Vocabulary <= 4096.
+ * Contract, in order: the penalty (score < 0 ? score * rp : score / rp) is taken from the ORIGINAL logit of every
+ * previous token (duplicates do not compound); then suppression; the descending order is torch's stable one (ties: lower
+ * index first); the cumulative sum of exp(s - s0) is NORMALISED BY ITS OWN TOTAL before it is compared with top_p, so its
+ * last value is exactly 1 and top_p >= 1 removes nothing (a softmax-then-cumsum may overshoot 1 by an ulp and drop tail
+ * tokens at top_p = 1); an entry is removed where that value > top_p, never the first; the kept logits are divided by
+ * max(temperature, 1e-5); softmax; the winner is argmax(probs / q), ties to the lower index.
+ * Not specified: NaN logits, and a vector whose entries are all -inf. */
 int svc_ar_sample(svc_ar_t* m, const float* logits, const int32_t* prev_tokens, int n_prev, int suppress_token,
                   float temperature, float top_p, float repetition_penalty, const float* exp_noise, int32_t* idx_out,
                   float* probs_out, void* stream);
@@ -1115,6 +1123,47 @@ typedef struct {
     const int32_t* src; const int32_t* len; const int32_t* lw; const int32_t* nf;
 } svc_hift_signal_t;
 int svc_op_hift_signal(const svc_hift_signal_t* args, void* stream);
+/* Test aid (tests/test_gpu_ar_sampler.py; no model uses it, and it needs no svc_ar_t): ONE call of the AR sampler's launch
+ * (csrc/ar_sampler.h) on explicit inputs.  It allocates the rank -> sample buffers, the slot state, the slot count and the
+ * device positions itself, launches once, synchronises, copies the state back and frees its buffers.  Device pointers
+ * unless noted; NULL = absent.  The contract of the sampler is that of svc_ar_sample.
+ *   form 0  explicit: ar_sampler_launch without loop state.  logits [V], prev [n_prev], suppress (negative: none), rep_pen,
+ *           temperature, top_p; draws exp_noise [V], or NULL: those of (seed, step), as the generate loops draw them
+ *           -> idx_out [1], probs_out [V] (optional).
+ *   form 1  one sequence's loop state (GenState): logits [V], toks [max_new] (read: toks[0]; written: toks[cnt]), noise
+ *           [max_new][V] or NULL (seeded), emb [V][D] -> next_x [D], probs_out [V] (optional).  The per-slot HOST arrays
+ *           below hold one entry; s_done, s_max_new and s_has_noise are not read.  pos HOST [2] (input, kv), in and out.
+ *   form 2  B slots (GenSlot) of Bp = B rounded up to 16 rows, *nb = B: ar_sampler_batch_launch.  logits [Bp][V], toks
+ *           [B][max_new], noise [B][max_new][V] (rows of slots with s_has_noise; may be NULL when none has), emb [V][D]
+ *           -> next_x [Bp][D].  pos HOST [2][B], in and out.  max_new is the row stride; a slot's own limit is s_max_new[b].
+ *   HOST per-slot arrays [B]: s_cnt (in and out), s_done (in and out), s_max_new, s_min_before_eos, s_eos, s_temperature,
+ *   s_top_p, s_rep_pen, s_seed, s_has_noise.
+ *   Token values inside prev and toks live on the device and are NOT checked: the caller keeps them in [0, V).
+ *   Refused (nothing allocated or launched): form outside 0 .. 2; V outside 1 .. 4096; NULL logits; form 0: NULL idx_out,
+ *   n_prev < 0 or tokens without prev, suppress >= V, a NaN or negative rep_pen, step < 0; forms 1, 2: max_new or D < 1,
+ *   missing emb, next_x, toks, pos or per-slot arrays, a slot's max_new outside [1, max_new], cnt < 1, cnt >= max_new (form
+ *   2: cnt > max_new, or cnt == max_new in a slot that is not done -- token cnt is written at toks[cnt]), eos outside [0, V),
+ *   a NaN or negative rep_pen; form 2: B outside 1 .. 64, Lmax < 1, a position outside [0, Lmax), a slot with noise and no
+ *   noise buffer. */
+typedef struct {
+    int32_t form, V, D, B, max_new, Lmax;
+    const float* logits;
+    const int32_t* prev;
+    int32_t n_prev, suppress;
+    float rep_pen, temperature, top_p;
+    const float* exp_noise;
+    uint64_t seed;
+    int32_t step;
+    int32_t* idx_out; float* probs_out;
+    int32_t* toks; const float* noise; const float* emb; float* next_x;
+    int32_t* s_cnt; int32_t* s_done;
+    const int32_t* s_max_new; const int32_t* s_min_before_eos; const int32_t* s_eos;
+    const float* s_temperature; const float* s_top_p; const float* s_rep_pen;
+    const uint64_t* s_seed;
+    const int32_t* s_has_noise;
+    int32_t* pos;
+} svc_ar_sampler_t;
+int svc_op_ar_sampler(const svc_ar_sampler_t* args, void* stream);
 /* y = rmsnorm(x) * gamma * (add_one + w) + b ; x [rows][D]. */
 int svc_op_rmsnorm(const float* x, const float* gamma, const float* w, const float* b, int add_one, float* y,
                    int rows, int D, void* stream);

@@ -45,7 +45,7 @@ EXPORTS = [
     "svc_op_bsq_index", "svc_tokens_reduce",
     "svc_prof_enable", "svc_prof_collect",
     "svc_op_linear", "svc_op_conv1d", "svc_op_conv1d_ex", "svc_op_conv1d_last_took", "svc_op_dit_panel", "svc_op_conv_transpose1d", "svc_op_attention", "svc_op_attention_ex", "svc_op_rmsnorm",
-    "svc_op_layernorm", "svc_op_layernorm_gelu", "svc_op_act_cl", "svc_op_hift_signal",
+    "svc_op_layernorm", "svc_op_layernorm_gelu", "svc_op_act_cl", "svc_op_hift_signal", "svc_op_ar_sampler",
 ]
 
 
@@ -194,6 +194,18 @@ class HiftSignal(C.Structure):
                [(n, C.POINTER(C.c_int32)) for n in ("src", "len", "lw", "nf")]
 
 
+class ArSampler(C.Structure):
+    """svc_ar_sampler_t: the arguments of svc_op_ar_sampler (test aid)."""
+    _fields_ = [(n, C.c_int32) for n in ("form", "V", "D", "B", "max_new", "Lmax")] + \
+               [("logits", C.c_void_p), ("prev", C.c_void_p), ("n_prev", C.c_int32), ("suppress", C.c_int32)] + \
+               [(n, C.c_float) for n in ("rep_pen", "temperature", "top_p")] + \
+               [("exp_noise", C.c_void_p), ("seed", C.c_uint64), ("step", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("idx_out", "probs_out", "toks", "noise", "emb", "next_x")] + \
+               [(n, C.POINTER(C.c_int32)) for n in ("s_cnt", "s_done", "s_max_new", "s_min_before_eos", "s_eos")] + \
+               [(n, C.POINTER(C.c_float)) for n in ("s_temperature", "s_top_p", "s_rep_pen")] + \
+               [("s_seed", C.POINTER(C.c_uint64)), ("s_has_noise", C.POINTER(C.c_int32)), ("pos", C.POINTER(C.c_int32))]
+
+
 _lib = None
 
 
@@ -246,6 +258,7 @@ def lib():
         l.svc_op_attention_ex.argtypes = [C.POINTER(Attention), C.c_void_p]
         l.svc_op_act_cl.argtypes = [C.POINTER(ActCl), C.c_void_p]
         l.svc_op_hift_signal.argtypes = [C.POINTER(HiftSignal), C.c_void_p]
+        l.svc_op_ar_sampler.argtypes = [C.POINTER(ArSampler), C.c_void_p]
         # seeded noise: 64-bit seeds by value and as HOST arrays
         l.svc_cfm_sample_seeded.argtypes = [C.c_void_p, C.POINTER(CfmArgs), C.POINTER(C.c_uint64), C.c_void_p]
         l.svc_cfm_noise_draws.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]

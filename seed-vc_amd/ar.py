@@ -77,6 +77,8 @@ class ARModel:
     def sample(self, logits, previous_tokens=None, suppress_tokens=None, temperature=0.7, top_p=0.7, repetition_penalty=1.5,
                exp_noise=None, return_probs=False):
         V = self.cfg["vocab_size"]
+        if suppress_tokens is not None and len(suppress_tokens) > 1:
+            raise ValueError(f"ARModel.sample suppresses one token, not {len(suppress_tokens)}: the sampler kernel takes a single index")
         with torch.cuda.device(self.device):
             lg = _lib.f32c(logits, self.device).reshape(-1)[-V:].contiguous()
             if exp_noise is None:

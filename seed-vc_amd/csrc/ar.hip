@@ -1041,9 +1041,110 @@ int svc_ar_exp_draws(svc_ar_t* m, uint64_t seed, int step0, int n_steps, float* 
 int svc_ar_sample(svc_ar_t* m, const float* logits, const int32_t* prev_tokens, int n_prev, int suppress_token, float temperature,
                   float top_p, float repetition_penalty, const float* exp_noise, int32_t* idx_out, float* probs_out, void* stream) {
     SVC_REQUIRE(m && logits && exp_noise && idx_out && n_prev >= 0 && (n_prev == 0 || prev_tokens), "bad argument");
+    SVC_REQUIRE(suppress_token < m->V, "AR: suppress_token is a vocabulary index (negative: none)");      // it indexes the rank kernel's LDS
     if (m->reserve(1, (hipStream_t)stream)) return 1;
     return m->sample(logits, prev_tokens, n_prev, suppress_token, temperature, top_p, repetition_penalty, exp_noise, idx_out, probs_out,
                      nullptr, (hipStream_t)stream);
+}
+
+// Test aid: ONE call of the sampler launch the model makes (ar_sampler_launch without or with a GenState, or
+// ar_sampler_batch_launch over the slots), on buffers of its own; see include/seedvc_hip.h.
+int svc_op_ar_sampler(const svc_ar_sampler_t* e, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    SVC_REQUIRE(e, "svc_op_ar_sampler: null argument");
+    SVC_REQUIRE(e->form >= 0 && e->form <= 2, "svc_op_ar_sampler: form is 0 .. 2");
+    const int form = e->form, V = e->V, D = e->D;
+    SVC_REQUIRE(V >= 1 && V <= SORT_N, "svc_op_ar_sampler: V is 1 .. 4096");
+    SVC_REQUIRE(e->logits, "svc_op_ar_sampler: logits are required");
+    const int B = form == 2 ? e->B : 1;
+    if (form == 0) {
+        SVC_REQUIRE(e->idx_out, "svc_op_ar_sampler: form 0 writes idx_out");
+        SVC_REQUIRE(e->n_prev >= 0 && (e->n_prev == 0 || e->prev), "svc_op_ar_sampler: n_prev tokens need prev");
+        SVC_REQUIRE(e->suppress < V, "svc_op_ar_sampler: suppress is a vocabulary index (negative: none)");
+        SVC_REQUIRE(e->rep_pen >= 0.f, "svc_op_ar_sampler: rep_pen is a number >= 0");       // false for NaN
+        SVC_REQUIRE(e->step >= 0, "svc_op_ar_sampler: step >= 0");
+    } else {
+        SVC_REQUIRE(form == 1 || (B >= 1 && B <= MAXB), "svc_op_ar_sampler: B is 1 .. 64");
+        SVC_REQUIRE(e->max_new >= 1 && D >= 1, "svc_op_ar_sampler: max_new and D are positive");
+        SVC_REQUIRE(e->emb && e->next_x && e->toks && e->pos, "svc_op_ar_sampler: the loop forms need emb, next_x, toks and pos");
+        SVC_REQUIRE(e->s_cnt && e->s_min_before_eos && e->s_eos && e->s_temperature && e->s_top_p && e->s_rep_pen && e->s_seed,
+                    "svc_op_ar_sampler: the loop forms need the per-slot arrays");
+        SVC_REQUIRE(form == 1 || (e->s_done && e->s_max_new && e->s_has_noise), "svc_op_ar_sampler: form 2 needs done, max_new and has_noise per slot");
+        SVC_REQUIRE(form == 1 || e->Lmax >= 1, "svc_op_ar_sampler: Lmax is positive");
+        for (int b = 0; b < B; ++b) {
+            const int mn = form == 2 ? e->s_max_new[b] : e->max_new;
+            SVC_REQUIRE(mn >= 1 && mn <= e->max_new, "svc_op_ar_sampler: a slot's max_new is 1 .. max_new");
+            SVC_REQUIRE(e->s_cnt[b] >= 1, "svc_op_ar_sampler: cnt >= 1");
+            // token cnt is written at toks[cnt]: only a finished slot (which records nothing) may sit at cnt == max_new
+            SVC_REQUIRE(e->s_cnt[b] < mn || (form == 2 && e->s_cnt[b] == mn && e->s_done[b]),
+                        "svc_op_ar_sampler: cnt < max_new (form 2: cnt == max_new for a finished slot)");
+            SVC_REQUIRE(e->s_eos[b] >= 0 && e->s_eos[b] < V, "svc_op_ar_sampler: eos is a vocabulary index");
+            SVC_REQUIRE(e->s_rep_pen[b] >= 0.f, "svc_op_ar_sampler: rep_pen is a number >= 0");
+            SVC_REQUIRE(form == 1 || !e->s_has_noise[b] || e->noise, "svc_op_ar_sampler: a slot with noise needs the noise buffer");
+            if (form == 2)
+                SVC_REQUIRE(e->pos[b] >= 0 && e->pos[b] < e->Lmax && e->pos[B + b] >= 0 && e->pos[B + b] < e->Lmax,
+                            "svc_op_ar_sampler: positions lie in [0, Lmax)");
+        }
+    }
+    Arena ar;
+    const int rows = form == 2 ? MAXB : 1;
+    float* skey = ar.alloc_n<float>((size_t)rows * SORT_N, st);
+    int* sidx = ar.alloc_n<int>((size_t)rows * SORT_N, st);
+    float* lgp = ar.alloc_n<float>((size_t)rows * SORT_N, st);
+    if (!skey || !sidx || !lgp) return 1;
+    if (form == 0) {
+        if (ar_sampler_launch(e->logits, V, e->prev, e->n_prev, e->suppress, e->rep_pen, e->temperature, e->top_p, e->exp_noise, e->seed,
+                              e->step, e->idx_out, e->probs_out, nullptr, nullptr, nullptr, 0, nullptr, skey, sidx, lgp, st)) return 1;
+        SVC_CHECK_HIP(hipStreamSynchronize(st));
+        return 0;
+    }
+    std::vector<GenSlot> slots(B);
+    for (int b = 0; b < B; ++b) {
+        GenSlot& g = slots[b];
+        const bool has_noise = form == 2 ? e->s_has_noise[b] != 0 : e->noise != nullptr;
+        g.noise = has_noise ? e->noise + (size_t)b * e->max_new * V : nullptr;
+        g.seed = e->s_seed[b];
+        g.toks = e->toks + (size_t)b * e->max_new;
+        g.cnt = e->s_cnt[b];
+        g.min_before_eos = e->s_min_before_eos[b];
+        g.eos = e->s_eos[b];
+        g.temperature = e->s_temperature[b];
+        g.top_p = e->s_top_p[b];
+        g.rep_pen = e->s_rep_pen[b];
+        g.done = form == 2 ? e->s_done[b] : 0;
+        g.max_new = form == 2 ? e->s_max_new[b] : e->max_new;
+    }
+    std::vector<int> pos(form == 2 ? 2 * MAXB : 2, 0);
+    for (int b = 0; b < B; ++b) {
+        pos[b] = e->pos[b];
+        pos[(form == 2 ? MAXB : 1) + b] = e->pos[B + b];
+    }
+    GenSlot* d_slots = ar.alloc_n<GenSlot>(form == 2 ? MAXB : 1, st);
+    int* d_pos = ar.alloc_n<int>(pos.size(), st);
+    int* d_nb = ar.alloc_n<int>(1, st);
+    if (!d_slots || !d_pos || !d_nb) return 1;
+    SVC_CHECK_HIP(hipMemcpyAsync(d_slots, slots.data(), (size_t)B * sizeof(GenSlot), hipMemcpyHostToDevice, st));
+    SVC_CHECK_HIP(hipMemcpyAsync(d_pos, pos.data(), pos.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    SVC_CHECK_HIP(hipMemcpyAsync(d_nb, &B, sizeof(int), hipMemcpyHostToDevice, st));
+    SVC_CHECK_HIP(hipStreamSynchronize(st));            // the host arrays are pageable
+    if (form == 1) {
+        // a GenSlot begins with its GenState
+        if (ar_sampler_launch(e->logits, V, nullptr, 0, -1, 1.f, 0.f, 0.f, nullptr, 0, 0, nullptr, e->probs_out, d_slots, e->emb, e->next_x, D,
+                              d_pos, skey, sidx, lgp, st)) return 1;
+    } else {
+        if (ar_sampler_batch_launch(e->logits, V, d_slots, d_nb, skey, sidx, lgp, e->emb, e->next_x, D, d_pos, e->Lmax,
+                                    (int)round_up(B, 16), st)) return 1;
+    }
+    SVC_CHECK_HIP(hipMemcpyAsync(slots.data(), d_slots, (size_t)B * sizeof(GenSlot), hipMemcpyDeviceToHost, st));
+    SVC_CHECK_HIP(hipMemcpyAsync(pos.data(), d_pos, pos.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+    SVC_CHECK_HIP(hipStreamSynchronize(st));
+    for (int b = 0; b < B; ++b) {
+        e->s_cnt[b] = slots[b].cnt;
+        if (form == 2) e->s_done[b] = slots[b].done;
+        e->pos[b] = pos[b];
+        e->pos[B + b] = pos[(form == 2 ? MAXB : 1) + b];
+    }
+    return 0;
 }
 
 }  // extern "C"

@@ -361,6 +361,104 @@ def hift_signal(a, device="cuda:0", fill16=0x6A5A, fill32=-777.25):
     return out, out_lo
 
 
+_AR_SLOT_I = ("cnt", "done", "max_new", "min_before_eos", "eos", "has_noise")
+_AR_SLOT_F = ("temperature", "top_p", "rep_pen")
+
+
+def ar_sampler(a, device="cuda:0", guard=2, fill32=-777.25, fill_tok=-7777):
+    """Test aid over svc_op_ar_sampler (include/seedvc_hip.h): ONE launch of the AR sampler, in the form a["form"].
+    form 0: logits (V,), prev (list of ints or None), suppress, rep_pen, temperature, top_p, exp_noise (V,) or None with seed and
+            step, probs (bool).  Returns dict(idx, probs).
+    form 1: logits (V,), toks (max_new,) int32, noise (max_new, V) or None, emb (V, D), pos [input, kv], and the scalars cnt,
+            min_before_eos, eos, temperature, top_p, rep_pen, seed; probs (bool).  Returns dict(cnt, pos, toks, next_x, probs).
+    form 2: logits (B, V), toks (B, max_new) int32, noise (B, max_new, V) or None, emb (V, D), pos [[input] * B, [kv] * B], Lmax
+            and lists of B values: cnt, done, max_new, min_before_eos, eos, has_noise, temperature, top_p, rep_pen, seed.
+            Returns dict(cnt, done, pos, toks, next_x).
+    Every returned buffer is the WHOLE device buffer with `guard` canary rows in front and behind (probs, next_x: fill32; toks:
+    fill_tok); next_x of form 2 has Bp = B rounded up to 16 rows between the guards, all holding fill32 before the launch."""
+    import ctypes as C
+    dev = torch.device(device)
+    form = int(a["form"])
+    with torch.cuda.device(dev):
+        e = _lib.ArSampler()
+        keep = []
+
+        def put(t, dtype):
+            keep.append(t.to(dev, dtype).contiguous())
+            return keep[-1]
+
+        def guarded(rows, cols, fill, dtype):
+            keep.append(torch.full((guard + rows + guard, cols), fill, dtype=dtype, device=dev))
+            return keep[-1]
+
+        lg = a["logits"]
+        V = lg.shape[-1]
+        e.form, e.V = form, V
+        B = lg.shape[0] if form == 2 else 1
+        Bp = (B + 15) // 16 * 16
+        if form == 2:
+            rows = torch.full((Bp, V), float("nan"), dtype=torch.float32)
+            rows[:B] = lg
+            lg = rows
+        e.logits = put(lg, torch.float32).data_ptr()
+        out = {}
+        if form != 2 and a.get("probs"):
+            out["probs"] = guarded(1, V, fill32, torch.float32)
+            e.probs_out = out["probs"].data_ptr() + 4 * guard * V
+        if form == 0:
+            prev = a.get("prev")
+            if prev is not None and len(prev):
+                e.prev = put(torch.tensor([int(v) for v in prev], dtype=torch.int32), torch.int32).data_ptr()
+                e.n_prev = len(prev)
+            sup = a.get("suppress")
+            e.suppress = -1 if sup is None else int(sup)
+            e.rep_pen, e.temperature, e.top_p = float(a["rep_pen"]), float(a["temperature"]), float(a["top_p"])
+            if a.get("exp_noise") is not None:
+                e.exp_noise = put(a["exp_noise"], torch.float32).data_ptr()
+            e.seed, e.step = int(a.get("seed") or 0), int(a.get("step") or 0)
+            idx = torch.full((1,), fill_tok, dtype=torch.int32, device=dev)
+            e.idx_out = idx.data_ptr()
+        else:
+            emb = put(a["emb"], torch.float32)
+            D = emb.shape[1]
+            toks_in = a["toks"].reshape(B, -1)
+            max_new = toks_in.shape[1]
+            e.D, e.B, e.max_new, e.Lmax = D, B, max_new, int(a.get("Lmax") or 0)
+            e.emb = emb.data_ptr()
+            toks = guarded(B, max_new, fill_tok, torch.int32)
+            toks[guard:guard + B] = toks_in.to(dev, torch.int32)
+            e.toks = toks.data_ptr() + 4 * guard * max_new
+            next_x = guarded(Bp if form == 2 else 1, D, fill32, torch.float32)
+            e.next_x = next_x.data_ptr() + 4 * guard * D
+            if a.get("noise") is not None:
+                e.noise = put(a["noise"], torch.float32).data_ptr()
+            host = {}
+            slot = lambda name: a[name] if form == 2 else [a.get(name) or 0]      # noqa: E731
+            for name in _AR_SLOT_I:
+                host[name] = _lib.i32_host([int(v) for v in slot(name)])
+                setattr(e, "s_" + name, C.cast(host[name], C.POINTER(C.c_int32)))
+            for name in _AR_SLOT_F:
+                host[name] = (C.c_float * B)(*[float(v) for v in slot(name)])
+                setattr(e, "s_" + name, C.cast(host[name], C.POINTER(C.c_float)))
+            host["seed"] = (C.c_uint64 * B)(*[int(v) for v in slot("seed")])
+            e.s_seed = C.cast(host["seed"], C.POINTER(C.c_uint64))
+            p = a["pos"] if form == 2 else [[a["pos"][0]], [a["pos"][1]]]
+            host["pos"] = _lib.i32_host([int(v) for v in list(p[0]) + list(p[1])])
+            e.pos = C.cast(host["pos"], C.POINTER(C.c_int32))
+        _lib.check(_lib.lib().svc_op_ar_sampler(C.byref(e), _lib.stream_ptr()))
+        if form == 0:
+            out["idx"] = int(idx.item())
+        else:
+            out["toks"], out["next_x"] = toks, next_x
+            cnt, pos = list(host["cnt"]), [list(host["pos"])[:B], list(host["pos"])[B:]]
+            if form == 2:
+                out.update(cnt=cnt, done=list(host["done"]), pos=pos)
+            else:
+                out.update(cnt=cnt[0], pos=[pos[0][0], pos[1][0]])
+    out["guard"] = guard
+    return out
+
+
 def rmsnorm(x, gamma, w=None, b=None, add_one=False):
     rows, D = x.shape
     dev = x.device
