@@ -265,7 +265,9 @@ int svc_ar_forward_generate(svc_ar_t* m, const float* x, int S, const int64_t* i
                             float* logits_out, void* stream);
 /* The same one-token step replayed from a captured hipGraph (replaces `compiled_decode_fn`, the
  * torch.compile(mode="reduce-overhead") step of modules/v2/vc_wrapper.py:105-114).  set_pos != 0 (re)sets the device
- * positions; every call afterwards advances input_pos and kv_pos by one (ar.py:402-403). */
+ * positions; every call afterwards advances input_pos and kv_pos by one (ar.py:402-403).  Refused before anything is
+ * launched: a call without set_pos that is not preceded by one (or that follows another B = 1 call -- svc_ar_forward_generate,
+ * svc_ar_generate -- which rewrite the device positions), and a replay whose position has reached max_seq_len. */
 int svc_ar_decode_step(svc_ar_t* m, const float* x, int set_pos, int64_t input_pos, int64_t kv_pos, float* logits_out,
                        void* stream);
 /* Replaces the token loop of `NaiveWrapper.generate(prompt_text, prompt_target, ...)` (modules/v2/ar.py:382-422), B = 1
@@ -1164,6 +1166,72 @@ typedef struct {
     int32_t* pos;
 } svc_ar_sampler_t;
 int svc_op_ar_sampler(const svc_ar_sampler_t* args, void* stream);
+/* Test aid (tests/test_gpu_ar_step.py; no model uses it, and it needs no svc_ar_t): ONE call of the launch function of an AR
+ * kernel that reads or writes the KV cache (csrc/ar_prefill.h, ar_decode1.h, ar_batch.h, ar_prefill_attn.h), on explicit
+ * buffers.  It builds the device tables the launch needs (cache bases per slot, positions, live-slot count, PrefillTabs),
+ * launches once, synchronises and frees them.  Device pointers unless noted.  D = 64 H, kvd = 64 Hkv.
+ *   kc, vc  the caches of n_slots slots, [n_slots][Hkv][Lmax][64] fp32;  rope [Lmax][32][2] fp32 (cos, sin), taken as given
+ *   slots   HOST: the slot of the call (kinds 0, 1, 4: one entry), of every row (kind 2: [n]) or of every sequence (kinds 3, 5: [n])
+ *   pos     HOST [2][R]: input_pos of the R rows, then kv_pos (kind 1: R = 1; kinds 0, 4: R = n; kind 2: R = n; kinds 3, 5: the
+ *           rows of the n sequences one after another, R = sum of seq_S)
+ *   kind 0  ar_attn_launch: x = q [n][D] -> y16 [n][D]; reads rows 0 .. kv_pos of the slot's cache and nothing above
+ *   kind 1  dec_attn2_launch: x = qkv_raw [D + 2 kvd], hres [D], eps, rope, wo fp16 [D][D] -> part [H][D] and cache row kv_pos.
+ *           Rows above kv_pos MAY be read (by position, clamped to the cache) and must be finite; row kv_pos is never used
+ *   kind 2  battn_launch: x = q [Bp][D], Bp = n rounded up to 16, *nb = n -> y16 [Bp][D] (rows >= n untouched).  The cache table
+ *           holds slots[b] for b < n and NULL above.  Reads rows 0 .. kv_pos[b] only
+ *   kind 3  ar_prefill_attn_launch: x = q [R][D], tiles of 16 rows per sequence as the ragged prefill builds them -> y16 [R][D].
+ *           Reads rows 0 .. the tile's largest kv_pos only
+ *   kind 4  ar_rope_cache_launch: x = qkv [n][ldq] -> q_out [n][D], cache rows kv_pos of the slot
+ *   kind 5  ar_rope_cache_ragged_launch: x = qkv [R][ldq] -> q_out [R][D], cache rows kv_pos of each row's slot
+ *   Refused (nothing allocated or launched): NULL args; kind outside 0 .. 5; H or Hkv < 1, H > 64, H % Hkv != 0; Lmax outside
+ *   8 .. 8192; n_slots outside 1 .. 64; NULL x, kc, vc, slots or pos; n < 1 (kinds 0, 4: n > 8192; kinds 2, 3, 5: n > 64); a
+ *   slot outside [0, n_slots); a slot named twice (kinds 2, 3, 5); kinds 3, 5: NULL seq_S, seq_S[i] < 1, R > 8192; a position
+ *   outside [0, Lmax); kinds 0, 2, 3: NULL y16; kinds 1, 4, 5: NULL rope; kinds 4, 5: NULL q_out, ldq < D + 2 kvd; kind 1:
+ *   NULL hres, wo or part, D > 1024 (the shapes for which svc_ar_create keeps the decode step). */
+typedef struct {
+    int32_t kind, H, Hkv, Lmax, n_slots, n;
+    const float* x;
+    int64_t ldq;
+    float* kc; float* vc;
+    const float* rope;
+    const int32_t* slots; const int32_t* seq_S; const int32_t* pos;
+    void* y16; float* q_out;
+    const float* hres; float eps; const void* wo; float* part;
+} svc_ar_attn_t;
+int svc_op_ar_attn(const svc_ar_attn_t* args, void* stream);
+/* Test aid (tests/test_gpu_ar_step.py; no model uses it, and it needs no svc_ar_t): ONE call of the launch function of a skinny
+ * AR linear on explicit buffers, with the template instance the model selects for (D, I, H) and the row count.  W is fp16, packed
+ * as svc_ar_create packs it: row-major [N rounded up to 128][K] (rows >= N are read by the batched path and must be finite).
+ * Nqkv = D + 2 * 64 Hkv.  role: 0 qkv, 1 wo, 2 w13, 3 w2, 4 head.
+ *   path 0  gemv_pair_launch, rows = S in 1 .. 8:
+ *           qkv  x fp32 [S][D], gamma, eps, W [Nqkv][D] -> q_out [S][D], cache rows (kc, vc, rope, slots[0], pos HOST [2][S])
+ *           wo   x fp16 [S][D], W [D][D], res [S][D] -> out32 [S][D]       w2    x fp16 [S][I], W [D][I], res -> out32 [S][D]
+ *           w13  x fp32 [S][D], gamma, eps, W [2 I][D] ((w1_j, w3_j) rows interleaved) -> out16 [S][I]
+ *           head x fp32 [S][D], gamma, eps, W [V][D] -> out32 [S][V]
+ *   path 1  bgemm_launch, rows = B in 1 .. 64, Bp = B rounded up to 16 rows in x, res and the outputs; the same five roles (qkv:
+ *           slots HOST [B], pos HOST [2][B], *nb = B, the cache table NULL above B; q_out rows >= B untouched)
+ *   path 2  the B = 1 decode step's launches, rows ignored:
+ *           qkv  dec_qkvraw: x fp32 [D], W [Nqkv][D] -> out32 [Nqkv]
+ *           wo   dec_w2qkv:  x fp16 ff [I], res = h_mid [D], W2 = w2 [D][I], W = wc [Nqkv][I + D] -> out32 = h_out [D], out2 = qkv_raw [Nqkv]
+ *           w13  dec_ffn13:  x fp32 h_in [D], part [H][D], gamma, eps, W [2 I][D] -> out2 = h_out [D], out16 = ff [I]
+ *           w2   dec_w2:     x fp16 [I], W [D][I], res [D] -> out32 [D]     head  dec_head: x fp32 [D], gamma, eps, W [V][D] -> out32 [V]
+ *   res may be the same buffer as out32 (the model runs wo and w2 in place).
+ *   Refused (nothing allocated or launched): NULL args; path outside 0 .. 2; role outside 0 .. 4; D != 64 H; H < 1, Hkv < 1,
+ *   H % Hkv != 0; D or I not a positive multiple of 64, or above 8192; V outside 1 .. 4096; path 0: rows outside 1 .. 8; path 1:
+ *   rows outside 1 .. 64; path 2: D > 1024 or I > 2560 (svc_ar_create clears the decode step there); NULL x or W; a role's
+ *   missing buffer (gamma, res, part, W2, out32, out16, out2); qkv on paths 0, 1: NULL q_out, kc, vc, rope, slots or pos, Lmax
+ *   outside 8 .. 8192, n_slots outside 1 .. 64, a slot outside [0, n_slots) or named twice, a position outside [0, Lmax). */
+typedef struct {
+    int32_t path, role, D, I, H, Hkv, V, Lmax, rows, n_slots;
+    const void* x;
+    const float* gamma; float eps;
+    const void* W; const void* W2;
+    const float* res; const float* part;
+    float* out32; void* out16; float* out2;
+    float* q_out; float* kc; float* vc; const float* rope;
+    const int32_t* slots; const int32_t* pos;
+} svc_ar_linear_t;
+int svc_op_ar_linear(const svc_ar_linear_t* args, void* stream);
 /* y = rmsnorm(x) * gamma * (add_one + w) + b ; x [rows][D]. */
 int svc_op_rmsnorm(const float* x, const float* gamma, const float* w, const float* b, int add_one, float* y,
                    int rows, int D, void* stream);

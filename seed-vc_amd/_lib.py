@@ -46,6 +46,7 @@ EXPORTS = [
     "svc_prof_enable", "svc_prof_collect",
     "svc_op_linear", "svc_op_conv1d", "svc_op_conv1d_ex", "svc_op_conv1d_last_took", "svc_op_dit_panel", "svc_op_conv_transpose1d", "svc_op_attention", "svc_op_attention_ex", "svc_op_rmsnorm",
     "svc_op_layernorm", "svc_op_layernorm_gelu", "svc_op_act_cl", "svc_op_hift_signal", "svc_op_ar_sampler",
+    "svc_op_ar_attn", "svc_op_ar_linear",
 ]
 
 
@@ -206,6 +207,23 @@ class ArSampler(C.Structure):
                [("s_seed", C.POINTER(C.c_uint64)), ("s_has_noise", C.POINTER(C.c_int32)), ("pos", C.POINTER(C.c_int32))]
 
 
+class ArAttn(C.Structure):
+    """svc_ar_attn_t: the arguments of svc_op_ar_attn (test aid)."""
+    _fields_ = [(n, C.c_int32) for n in ("kind", "H", "Hkv", "Lmax", "n_slots", "n")] + \
+               [("x", C.c_void_p), ("ldq", C.c_int64), ("kc", C.c_void_p), ("vc", C.c_void_p), ("rope", C.c_void_p)] + \
+               [(n, C.POINTER(C.c_int32)) for n in ("slots", "seq_S", "pos")] + \
+               [("y16", C.c_void_p), ("q_out", C.c_void_p), ("hres", C.c_void_p), ("eps", C.c_float), ("wo", C.c_void_p),
+                ("part", C.c_void_p)]
+
+
+class ArLinear(C.Structure):
+    """svc_ar_linear_t: the arguments of svc_op_ar_linear (test aid)."""
+    _fields_ = [(n, C.c_int32) for n in ("path", "role", "D", "I", "H", "Hkv", "V", "Lmax", "rows", "n_slots")] + \
+               [("x", C.c_void_p), ("gamma", C.c_void_p), ("eps", C.c_float), ("W", C.c_void_p), ("W2", C.c_void_p)] + \
+               [(n, C.c_void_p) for n in ("res", "part", "out32", "out16", "out2", "q_out", "kc", "vc", "rope")] + \
+               [(n, C.POINTER(C.c_int32)) for n in ("slots", "pos")]
+
+
 _lib = None
 
 
@@ -259,6 +277,8 @@ def lib():
         l.svc_op_act_cl.argtypes = [C.POINTER(ActCl), C.c_void_p]
         l.svc_op_hift_signal.argtypes = [C.POINTER(HiftSignal), C.c_void_p]
         l.svc_op_ar_sampler.argtypes = [C.POINTER(ArSampler), C.c_void_p]
+        l.svc_op_ar_attn.argtypes = [C.POINTER(ArAttn), C.c_void_p]
+        l.svc_op_ar_linear.argtypes = [C.POINTER(ArLinear), C.c_void_p]
         # seeded noise: 64-bit seeds by value and as HOST arrays
         l.svc_cfm_sample_seeded.argtypes = [C.c_void_p, C.POINTER(CfmArgs), C.POINTER(C.c_uint64), C.c_void_p]
         l.svc_cfm_noise_draws.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]

@@ -77,6 +77,11 @@ struct svc_ar {
     float *h32b, *part;           // S = 1 step: second residual buffer, per-head wo partials
     half_t *n16, *y16, *ff16, *x16;
     int* d_pos;                   // [2 S] input_pos then kv_pos of the rows in h32
+    // Host mirror of the device positions {input_pos, kv_pos} that svc_ar_decode_step replays advance: valid from a set_pos call
+    // until anything else rewrites d_pos (a prefill, svc_ar_generate, a reallocation), so a replay is checked against the cache
+    // BEFORE it is launched -- the step itself writes cache row kv_pos and reads RoPE row input_pos unchecked.
+    int h_pos[2] = {0, 0};
+    bool pos_valid = false;
     GenState* d_gen = nullptr;    // generate-loop state (device)
     float *d_skey = nullptr, *d_lgp = nullptr;   // sampler stage 1 -> stage 2
     int* d_sidx = nullptr;
@@ -196,6 +201,7 @@ int svc_ar::reserve(int S, hipStream_t st) {
     if (S <= cap_S) return 0;
     SVC_CHECK_HIP(hipStreamSynchronize(st));
     ws.release();
+    pos_valid = false;
     cap_S = std::max(S, 8);
     const long Sr = cap_S;
     h32 = ws.alloc_n<float>(Sr * D, st);
@@ -229,6 +235,7 @@ int svc_ar::prefill(int slot, const float* x, int S, const int64_t* input_pos, c
                     bool b1_step) {
     if (reserve(S, st)) return 1;
     SVC_REQUIRE(rows_in_cache(input_pos, kv_pos, S), "position out of range");
+    pos_valid = false;            // d_pos is rewritten below
     std::vector<int> pos(2 * S);
     for (int s = 0; s < S; ++s) {
         pos[s] = (int)input_pos[s];
@@ -726,10 +733,17 @@ int svc_ar_decode_step(svc_ar_t* m, const float* x, int set_pos, int64_t input_p
         const int pos[2] = {(int)input_pos, (int)kv_pos};
         SVC_CHECK_HIP(hipMemcpyAsync(m->d_pos, pos, 8, hipMemcpyHostToDevice, st));
         SVC_CHECK_HIP(hipStreamSynchronize(st));
+        m->h_pos[0] = pos[0]; m->h_pos[1] = pos[1];
+        m->pos_valid = true;
+    } else {
+        // every replay advanced both positions by one: the next one must still lie inside the cache and the RoPE table
+        SVC_REQUIRE(m->pos_valid, "AR: svc_ar_decode_step needs set_pos on its first step and after any other B = 1 call");
+        SVC_REQUIRE(m->h_pos[0] < m->Lmax && m->h_pos[1] < m->Lmax, "position out of range");
     }
     if (m->ensure_graph()) return 1;
     SVC_CHECK_HIP(hipMemcpyAsync(m->gx, x, (size_t)m->D * 4, hipMemcpyDeviceToDevice, st));
     SVC_CHECK_HIP(hipGraphLaunch(m->graph.exec, st));
+    m->h_pos[0] += 1; m->h_pos[1] += 1;
     SVC_CHECK_HIP(hipMemcpyAsync(logits_out, m->logits, (size_t)m->V * 4, hipMemcpyDeviceToDevice, st));
     return 0;
 }
@@ -1144,6 +1158,251 @@ int svc_op_ar_sampler(const svc_ar_sampler_t* e, void* stream) {
         e->pos[b] = pos[b];
         e->pos[B + b] = pos[(form == 2 ? MAXB : 1) + b];
     }
+    return 0;
+}
+
+}  // extern "C"
+
+namespace {
+// What the cache-touching test aids share: the slots named by the caller, checked, and the device cache table over them.
+int op_check_slots(const int32_t* slots, int n, int n_slots, bool distinct, const char* who) {
+    bool seen[MAXB] = {};
+    for (int i = 0; i < n; ++i) {
+        SVC_REQUIRE(slots[i] >= 0 && slots[i] < n_slots, std::string(who) + ": a slot lies in [0, n_slots)");
+        SVC_REQUIRE(!distinct || !seen[slots[i]], std::string(who) + ": a slot is named twice");
+        seen[slots[i]] = true;
+    }
+    return 0;
+}
+int op_check_pos(const int32_t* pos, long R, int Lmax, const char* who) {
+    for (long i = 0; i < 2 * R; ++i) SVC_REQUIRE(pos[i] >= 0 && pos[i] < Lmax, std::string(who) + ": positions lie in [0, Lmax)");
+    return 0;
+}
+// device [2][MAXB] cache bases: entry b = the cache of slot tab_slots[b] for b < n, NULL above
+int op_kvtab(Arena& ar, float* kc, float* vc, size_t slot_elems, const int32_t* tab_slots, int n, float*** out, hipStream_t st) {
+    std::vector<float*> tab(2 * MAXB, nullptr);
+    for (int b = 0; b < n; ++b) {
+        tab[b] = kc + (size_t)tab_slots[b] * slot_elems;
+        tab[MAXB + b] = vc + (size_t)tab_slots[b] * slot_elems;
+    }
+    float** d = reinterpret_cast<float**>(ar.alloc(tab.size() * sizeof(float*), st));
+    if (!d) return 1;
+    SVC_CHECK_HIP(hipMemcpyAsync(d, tab.data(), tab.size() * sizeof(float*), hipMemcpyHostToDevice, st));
+    SVC_CHECK_HIP(hipStreamSynchronize(st));
+    *out = d;
+    return 0;
+}
+int op_upload_ints(Arena& ar, const std::vector<int>& v, int** out, hipStream_t st) {
+    int* d = ar.alloc_n<int>(v.size(), st);
+    if (!d) return 1;
+    SVC_CHECK_HIP(hipMemcpyAsync(d, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    SVC_CHECK_HIP(hipStreamSynchronize(st));            // the host vector is pageable
+    *out = d;
+    return 0;
+}
+}  // namespace
+
+extern "C" {
+
+// Test aid: ONE call of the launch function of a cache-touching AR kernel, on buffers of the caller; see include/seedvc_hip.h.
+int svc_op_ar_attn(const svc_ar_attn_t* e, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    const char* who = "svc_op_ar_attn";
+    SVC_REQUIRE(e, "svc_op_ar_attn: null argument");
+    const int kind = e->kind, H = e->H, Hkv = e->Hkv, Lmax = e->Lmax, n = e->n;
+    SVC_REQUIRE(kind >= 0 && kind <= 5, "svc_op_ar_attn: kind is 0 .. 5");
+    SVC_REQUIRE(H >= 1 && H <= 64 && Hkv >= 1, "svc_op_ar_attn: H is 1 .. 64, Hkv >= 1");
+    SVC_REQUIRE(H % Hkv == 0, "svc_op_ar_attn: H % Hkv == 0");
+    SVC_REQUIRE(Lmax >= 8 && Lmax <= 8192, "svc_op_ar_attn: Lmax is 8 .. 8192");
+    SVC_REQUIRE(e->n_slots >= 1 && e->n_slots <= MAXB, "svc_op_ar_attn: n_slots is 1 .. 64");
+    SVC_REQUIRE(e->x && e->kc && e->vc && e->slots && e->pos, "svc_op_ar_attn: x, kc, vc, slots and pos are required");
+    const int D = H * 64, kvd = Hkv * 64;
+    const bool ragged = kind == 3 || kind == 5;
+    if (kind != 1) SVC_REQUIRE(n >= 1 && n <= (kind == 0 || kind == 4 ? 8192 : MAXB), "svc_op_ar_attn: n is 1 .. 8192 rows (kinds 0, 4) or 1 .. 64 slots or sequences");
+    const int n_named = kind == 2 || ragged ? n : 1;
+    if (op_check_slots(e->slots, n_named, e->n_slots, n_named > 1, who)) return 1;
+    long R = kind == 1 ? 1 : n;
+    int T = 0;
+    if (ragged) {
+        SVC_REQUIRE(e->seq_S, "svc_op_ar_attn: kinds 3 and 5 need seq_S");
+        R = 0;
+        for (int i = 0; i < n; ++i) {
+            SVC_REQUIRE(e->seq_S[i] >= 1 && e->seq_S[i] <= 8192, "svc_op_ar_attn: S[i] is 1 .. 8192");
+            R += e->seq_S[i];
+            T += cdiv(e->seq_S[i], PA_ROWS);
+        }
+        SVC_REQUIRE(R <= 8192, "svc_op_ar_attn: at most 8192 rows");
+    }
+    if (op_check_pos(e->pos, R, Lmax, who)) return 1;
+    if (kind == 0 || kind == 2 || kind == 3) SVC_REQUIRE(e->y16, "svc_op_ar_attn: kinds 0, 2 and 3 write y16");
+    if (kind == 1 || kind >= 4) SVC_REQUIRE(e->rope, "svc_op_ar_attn: kinds 1, 4 and 5 need rope");
+    if (kind >= 4) SVC_REQUIRE(e->q_out && e->ldq >= D + 2 * kvd, "svc_op_ar_attn: kinds 4 and 5 write q_out; ldq >= D + 2 kvd");
+    if (kind == 1) {
+        SVC_REQUIRE(e->hres && e->wo && e->part, "svc_op_ar_attn: kind 1 needs hres, wo and part");
+        SVC_REQUIRE(D <= 64 * DA_WO * DEC_NS, "svc_op_ar_attn: kind 1 holds D <= 1024 (svc_ar_create clears the decode step above)");
+    }
+    const size_t slot_elems = (size_t)Hkv * Lmax * 64;
+    float* kc0 = e->kc + (size_t)e->slots[0] * slot_elems;
+    float* vc0 = e->vc + (size_t)e->slots[0] * slot_elems;
+    half_t* y16 = reinterpret_cast<half_t*>(e->y16);
+    Arena ar;
+    int rc = 1;
+    if (kind == 0 || kind == 1 || kind == 4) {
+        int* d_pos;
+        if (op_upload_ints(ar, std::vector<int>(e->pos, e->pos + 2 * R), &d_pos, st)) return 1;
+        if (kind == 0) rc = ar_attn_launch(e->x, kc0, vc0, y16, d_pos, n, H, Hkv, Lmax, st);
+        else if (kind == 1) rc = dec_attn2_launch(e->hres, e->x, e->eps, e->rope, kc0, vc0, reinterpret_cast<const half_t*>(e->wo), e->part, d_pos, H, Hkv, Lmax, st);
+        else rc = ar_rope_cache_launch(e->x, e->ldq, e->q_out, kc0, vc0, e->rope, d_pos, n, H, Hkv, Lmax, st);
+    } else if (kind == 2) {
+        std::vector<int> pos(2 * MAXB + 1, 0);
+        for (int b = 0; b < n; ++b) { pos[b] = e->pos[b]; pos[MAXB + b] = e->pos[n + b]; }
+        pos[2 * MAXB] = n;
+        int* d_pos;
+        float** tab;
+        if (op_upload_ints(ar, pos, &d_pos, st) || op_kvtab(ar, e->kc, e->vc, slot_elems, e->slots, n, &tab, st)) return 1;
+        rc = battn_launch(e->x, tab, tab + MAXB, y16, d_pos, d_pos + 2 * MAXB, (int)round_up(n, 16), H, Hkv, Lmax, st);
+    } else {
+        // the tables of one ragged pass, as svc_ar::prefill_pass builds them; the cache table is indexed by slot
+        std::vector<int> tab(3 * R + 3 * T + n), ident(e->n_slots);
+        for (int i = 0; i < e->n_slots; ++i) ident[i] = i;
+        int *ip = tab.data(), *kp = ip + R, *rs = kp + R, *tiles = rs + R, *last = tiles + 3 * T;
+        long r = 0;
+        for (int i = 0; i < n; ++i) {
+            for (int s0 = 0; s0 < e->seq_S[i]; s0 += PA_ROWS) {
+                *tiles++ = (int)r + s0;
+                *tiles++ = std::min(PA_ROWS, e->seq_S[i] - s0);
+                *tiles++ = e->slots[i];
+            }
+            for (int s = 0; s < e->seq_S[i]; ++s, ++r) { ip[r] = e->pos[r]; kp[r] = e->pos[R + r]; rs[r] = e->slots[i]; }
+            last[i] = (int)r - 1;
+        }
+        int* d;
+        float** kvt;
+        if (op_upload_ints(ar, tab, &d, st) || op_kvtab(ar, e->kc, e->vc, slot_elems, ident.data(), e->n_slots, &kvt, st)) return 1;
+        const PrefillTabs tb{d, d + R, d + 2 * R, d + 3 * R, d + 3 * R + 3 * T};
+        rc = kind == 3 ? ar_prefill_attn_launch(e->x, kvt, kvt + MAXB, y16, tb, T, H, Hkv, Lmax, st)
+                       : ar_rope_cache_ragged_launch(e->x, e->ldq, e->q_out, kvt, kvt + MAXB, e->rope, tb, (int)R, H, Hkv, Lmax, st);
+    }
+    if (rc) return 1;
+    SVC_CHECK_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
+// Test aid: ONE call of the launch function of a skinny AR linear, in the instance the model selects; see include/seedvc_hip.h.
+int svc_op_ar_linear(const svc_ar_linear_t* e, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    const char* who = "svc_op_ar_linear";
+    SVC_REQUIRE(e, "svc_op_ar_linear: null argument");
+    const int path = e->path, role = e->role, D = e->D, I = e->I, H = e->H, Hkv = e->Hkv, V = e->V, rows = e->rows;
+    SVC_REQUIRE(path >= 0 && path <= 2, "svc_op_ar_linear: path is 0 .. 2");
+    SVC_REQUIRE(role >= 0 && role <= 4, "svc_op_ar_linear: role is 0 .. 4");
+    SVC_REQUIRE(H >= 1 && Hkv >= 1 && H % Hkv == 0, "svc_op_ar_linear: H % Hkv == 0");
+    SVC_REQUIRE(D >= 64 && D <= 8192 && D % 64 == 0 && I >= 64 && I <= 8192 && I % 64 == 0, "svc_op_ar_linear: D and I are multiples of 64, at most 8192");
+    SVC_REQUIRE(D == H * 64, "svc_op_ar_linear: D == 64 H");
+    SVC_REQUIRE(V >= 1 && V <= SORT_N, "svc_op_ar_linear: V is 1 .. 4096");
+    if (path == 0) SVC_REQUIRE(rows >= 1 && rows <= 8, "svc_op_ar_linear: path 0 holds S = 1 .. 8 rows");
+    if (path == 1) SVC_REQUIRE(rows >= 1 && rows <= MAXB, "svc_op_ar_linear: path 1 holds B = 1 .. 64 rows");
+    if (path == 2)
+        SVC_REQUIRE(D <= 64 * DA_WO * DEC_NS && D <= 64 * 8 * DEC_MAXC && I <= 64 * 8 * DEC_MAXC,
+                    "svc_op_ar_linear: path 2 holds D <= 1024 and I <= 2560 (svc_ar_create clears the decode step above)");
+    SVC_REQUIRE(e->x && e->W, "svc_op_ar_linear: x and W are required");
+    const bool norm = role == 0 || role == 2 || role == 4;
+    const bool cache = role == 0 && path != 2;
+    if (norm && !(path == 2 && role == 0)) SVC_REQUIRE(e->gamma, "svc_op_ar_linear: the role needs gamma");
+    if (role == 1 || role == 3) SVC_REQUIRE(e->res, "svc_op_ar_linear: wo and w2 need res");
+    if (role == 2) SVC_REQUIRE(e->out16, "svc_op_ar_linear: w13 writes out16");
+    if (role != 2 && !cache) SVC_REQUIRE(e->out32, "svc_op_ar_linear: the role writes out32");
+    if (path == 2 && role == 1) SVC_REQUIRE(e->W2 && e->out2, "svc_op_ar_linear: dec_w2qkv needs W2 and out2");
+    if (path == 2 && role == 2) SVC_REQUIRE(e->part && e->out2, "svc_op_ar_linear: dec_ffn13 needs part and out2");
+    const int kvd = Hkv * 64, Nqkv = D + 2 * kvd;
+    if (cache) {
+        SVC_REQUIRE(e->q_out && e->kc && e->vc && e->rope && e->slots && e->pos, "svc_op_ar_linear: the qkv role needs q_out, kc, vc, rope, slots and pos");
+        SVC_REQUIRE(e->Lmax >= 8 && e->Lmax <= 8192, "svc_op_ar_linear: Lmax is 8 .. 8192");
+        SVC_REQUIRE(e->n_slots >= 1 && e->n_slots <= MAXB, "svc_op_ar_linear: n_slots is 1 .. 64");
+        if (op_check_slots(e->slots, path == 1 ? rows : 1, e->n_slots, path == 1, who)) return 1;
+        if (op_check_pos(e->pos, rows, e->Lmax, who)) return 1;
+    }
+    const half_t* W = reinterpret_cast<const half_t*>(e->W);
+    half_t* out16 = reinterpret_cast<half_t*>(e->out16);
+    const size_t slot_elems = (size_t)Hkv * e->Lmax * 64;
+    Arena ar;
+    int rc = 1;
+    if (path == 0) {
+        const int S = rows;
+        if (role == 0) {
+            int* d_pos;
+            if (op_upload_ints(ar, std::vector<int>(e->pos, e->pos + 2 * S), &d_pos, st)) return 1;
+            GemvArgs a(e->x, D, W, D, S, Nqkv, D);
+            a.gamma = e->gamma; a.eps = e->eps;
+            a.q_out = e->q_out; a.kc = e->kc + (size_t)e->slots[0] * slot_elems; a.vc = e->vc + (size_t)e->slots[0] * slot_elems;
+            a.rope = e->rope; a.pos = d_pos; a.H = H; a.Hkv = Hkv; a.Lmax = e->Lmax;
+            rc = gemv_pair_launch<true, GV_QKV>(a, st);
+        } else if (role == 1 || role == 3) {
+            const int K = role == 1 ? D : I;
+            GemvArgs a(e->x, K, W, K, S, D, K);
+            a.res = e->res; a.ldres = D; a.out32 = e->out32; a.ldo = D;
+            rc = gemv_pair_launch<false, GV_PLAIN>(a, st);
+        } else if (role == 2) {
+            GemvArgs a(e->x, D, W, D, S, 2 * I, D);
+            a.gamma = e->gamma; a.eps = e->eps; a.out16 = out16; a.ldo = I;
+            rc = gemv_pair_launch<true, GV_GLU>(a, st);
+        } else {
+            GemvArgs a(e->x, D, W, D, S, V, D);
+            a.gamma = e->gamma; a.eps = e->eps; a.out32 = e->out32; a.ldo = V;
+            rc = gemv_pair_launch<true, GV_PLAIN>(a, st);
+        }
+    } else if (path == 1) {
+        const int B = rows, Bp = (int)round_up(B, 16);
+        int* d_pos = nullptr;
+        float** tab = nullptr;
+        if (role == 0) {
+            std::vector<int> pos(2 * MAXB + 1, 0);
+            for (int b = 0; b < B; ++b) { pos[b] = e->pos[b]; pos[MAXB + b] = e->pos[B + b]; }
+            pos[2 * MAXB] = B;
+            if (op_upload_ints(ar, pos, &d_pos, st) || op_kvtab(ar, e->kc, e->vc, slot_elems, e->slots, B, &tab, st)) return 1;
+        }
+        rc = with_ar_sizes(D, I, [&](auto KD, auto KI) {
+            if (role == 0) {
+                BGemmArgs a(e->x, D, W, D, Nqkv, D);
+                a.gamma = e->gamma; a.eps = e->eps;
+                a.q_out = e->q_out; a.kc = tab; a.vc = tab + MAXB; a.rope = e->rope; a.pos = d_pos; a.nb = d_pos + 2 * MAXB;
+                a.H = H; a.Hkv = Hkv; a.Lmax = e->Lmax;
+                return bgemm_launch<true, BG_QKV, 1, KD>(a, Bp, st);
+            }
+            if (role == 1) {
+                BGemmArgs a(e->x, D, W, D, D, D);
+                a.res = e->res; a.out32 = e->out32; a.ldo = D;
+                return bgemm_launch<false, BG_PLAIN, 1, KD>(a, Bp, st);
+            }
+            if (role == 2) {
+                BGemmArgs a(e->x, D, W, D, 2 * I, D);
+                a.gamma = e->gamma; a.eps = e->eps; a.out16 = out16; a.ldo = I;
+                return bgemm_launch<true, BG_GLU, 2, KD>(a, Bp, st);
+            }
+            if (role == 3) {
+                BGemmArgs a(e->x, I, W, I, D, I);
+                a.res = e->res; a.out32 = e->out32; a.ldo = D;
+                return bgemm_launch<false, BG_PLAIN, 1, KI>(a, Bp, st);
+            }
+            BGemmArgs a(e->x, D, W, D, V, D);
+            a.gamma = e->gamma; a.eps = e->eps; a.out32 = e->out32; a.ldo = V;
+            return bgemm_launch<true, BG_PLAIN, 1, KD>(a, Bp, st);
+        });
+    } else {
+        const float* xf = reinterpret_cast<const float*>(e->x);
+        const half_t* xh = reinterpret_cast<const half_t*>(e->x);
+        rc = with_dec_sizes(D, I, H, [&](auto KD, auto KI, auto NP) {
+            switch (role) {
+                case 0: return dec_qkvraw_launch<KD>(xf, W, D, Nqkv, e->out32, st);
+                case 1: return dec_w2qkv_launch<KD, KI>(xh, e->res, reinterpret_cast<const half_t*>(e->W2), W, I, D, Nqkv, e->out32, e->out2, st);
+                case 2: return dec_ffn13_launch<NP, KD>(xf, e->part, H, e->out2, e->gamma, e->eps, W, D, 2 * I, out16, st);
+                case 3: return dec_w2_launch<KI>(xh, W, I, D, e->res, e->out32, st);
+                default: return dec_head_launch<KD>(xf, e->gamma, e->eps, W, D, V, e->out32, st);
+            }
+        });
+    }
+    if (rc) return 1;
+    SVC_CHECK_HIP(hipStreamSynchronize(st));
     return 0;
 }
 

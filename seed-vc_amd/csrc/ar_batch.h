@@ -205,6 +205,10 @@ __global__ __launch_bounds__(256) void bgemm_kernel(const BGemmArgs a) {
     }
 }
 
+// Contract (held by tests/test_gpu_ar_step.py): K a multiple of 32; rows [0, N rounded up to 16 NT) of W are read; all Bp rows of
+// x are read and may hold anything in the padding rows (NaN included): a column of the MFMA never meets another.  PLAIN and GLU
+// store all Bp rows of the output; QKV stores q_out and cache rows of slots b < *nb only and never dereferences the table above.
+// `res` may be `out32` (a lane reads its four residuals before it stores the same four elements).
 template <bool NORM, int EPI, int NT, int KC>
 int bgemm_launch(const BGemmArgs& a, int Bp, hipStream_t st) {
     const dim3 grid(cdiv(a.N, 16 * NT)), block(256);
@@ -355,6 +359,8 @@ __global__ __launch_bounds__(512) void battn_kernel(const float* __restrict__ q,
 }
 
 // Bp rows (live slots + padding of the M tile); GT = 3, 2 or 1 query heads per workgroup, whichever divides H / Hkv first.
+// Contract: rows b >= *nb of y keep their bits and their table entries (NULL in the model) are loaded but never dereferenced;
+// slot b addresses cache rows 0 .. kv_pos[b] only; pos holds 2 MAXB entries whatever Bp is.
 int battn_launch(const float* q, float* const* kc_tab, float* const* vc_tab, half_t* y, const int* pos, const int* nb, int Bp, int H,
                  int Hkv, int Lmax, hipStream_t st) {
     const int G = H / Hkv;

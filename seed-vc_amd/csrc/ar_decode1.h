@@ -238,7 +238,7 @@ __global__ __launch_bounds__(64) void dec_w2qkv_kernel(const half_t* __restrict_
 
 // Attention of the decode step, spread over the chip: grid = (DEC_NS wo-row slices) x (heads), 512 threads.
 // q / k / v arrive unnormalised (qkv_raw).  Every workgroup of head h recomputes that head's softmax over the valid cache
-// prefix [0, kv_pos] -- <= 4096 x 64 fp32 keys and values, read from L2 / Infinity Cache -- and applies 1 / DEC_NS of the
+// prefix [0, kv_pos] -- up to max_seq_len (<= 8192) x 64 fp32 keys and values, read from L2 / Infinity Cache -- and applies 1 / DEC_NS of the
 // head's wo column slice (D / DEC_NS rows x 64 columns, held in registers), so 96 workgroups carry the 12 heads of ar_base
 // instead of 12 (with one workgroup per head, a CU moved 154 KB of K / V + 98 KB of wo and ran eight 1024-thread barriers).
 //   * every request that does not depend on `pos` goes out first: the first two batches of cache rows (by position,
@@ -494,6 +494,9 @@ int dec_w2qkv_launch(const half_t* ff, const float* h_mid, const half_t* W2, con
     return 0;
 }
 
+// Contract (held by tests/test_gpu_ar_step.py, Lmax up to 8192): part [H][D] is written whole; cache row kv_pos of every KV head
+// is written and nothing else; what that row held before never reaches the result (position kv_pos is served from registers);
+// rows ABOVE kv_pos may be read (by position, clamped to Lmax - 1) and must be finite -- they enter as 0 x value; D <= 1024.
 int dec_attn2_launch(const float* hres, const float* qkv_raw, float eps, const float* rope, float* kc, float* vc, const half_t* wo,
                      float* part, const int* pos, int H, int Hkv, int Lmax, hipStream_t st) {
     hipLaunchKernelGGL(dec_attn2_kernel, dim3(DEC_NS, H), dim3(512), 0, st, hres, qkv_raw, eps, rope, kc, vc, wo, part, pos, H, Hkv, Lmax);

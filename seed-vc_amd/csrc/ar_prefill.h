@@ -128,6 +128,9 @@ __global__ __launch_bounds__(256) void gemv_pair_kernel(const GemvArgs a) {
     }
 }
 
+// Contract (held by tests/test_gpu_ar_step.py): S <= 8 rows, K a multiple of 8; rows [0, N) of W are read and nothing beyond
+// (an odd last row is read twice and stored once); `res` may be `out32` (a lane reads its residual before it stores the same
+// element); QKV writes q_out [S][D] and row kv_pos[s] of every KV head of the one cache given, nothing else.
 template <bool NORM, int EPI>
 int gemv_pair_launch(const GemvArgs& a, hipStream_t st) {
     const int waves = (a.N + 1) / 2;
@@ -170,6 +173,8 @@ __global__ void ar_rope_cache_kernel(const float* __restrict__ qkv, long ldq, fl
     }
 }
 
+// Contract: writes q_out [S][D] and row kv_pos[s] of every KV head (two rows of one call may be neighbours in the cache); every
+// other cache element keeps its bits.  Positions are the caller's to keep inside [0, Lmax).
 int ar_rope_cache_launch(const float* qkv, long ldq, float* q_out, float* kc, float* vc, const float* rope, const int* pos, int S, int H,
                          int Hkv, int Lmax, hipStream_t st) {
     hipLaunchKernelGGL(ar_rope_cache_kernel, dim3(S), dim3(256), 0, st, qkv, ldq, q_out, kc, vc, rope, pos, S, H, Hkv, Lmax);
@@ -239,6 +244,8 @@ __global__ __launch_bounds__(1024) void ar_attn_kernel(const float* __restrict__
     }
 }
 
+// Contract: row s addresses cache rows 0 .. kv_pos[s] and none above (NaN there cannot reach y); the cache is not written.
+// Dynamic LDS is (Lmax + 1024) floats: 36 KB at the largest max_seq_len, 8192.
 int ar_attn_launch(const float* q, const float* kc, const float* vc, half_t* y, const int* pos, int S, int H, int Hkv, int Lmax,
                    hipStream_t st) {
     const size_t lds = ((size_t)Lmax + 1024) * sizeof(float);

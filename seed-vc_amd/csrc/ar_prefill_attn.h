@@ -210,7 +210,8 @@ __global__ __launch_bounds__(GW * 64) void ar_prefill_attn_kernel(const float* _
     }
 }
 
-// GW = the largest divisor of H / Hkv that is at most 8 (ar_base: 6).
+// GW = the largest divisor of H / Hkv that is at most 8 (ar_base: 6).  Contract (held by tests/test_gpu_ar_step.py): a tile
+// addresses cache rows 0 .. its largest kv_pos of its own slot only; a row's output does not depend on the later rows of its tile.
 int ar_prefill_attn_launch(const float* q, float* const* kc_tab, float* const* vc_tab, half_t* y, const PrefillTabs& tb, int n_tiles, int H,
                            int Hkv, int Lmax, hipStream_t st) {
     const int G = H / Hkv;

@@ -459,6 +459,152 @@ def ar_sampler(a, device="cuda:0", guard=2, fill32=-777.25, fill_tok=-7777):
     return out
 
 
+class _ArOpBuffers:
+    """The device buffers of one ar_attn / ar_linear call: inputs as given, outputs and caches with canary guard rows."""
+
+    def __init__(self, dev, guard, fill32, fill16):
+        self.dev, self.guard, self.fill32, self.fill16, self.keep = dev, guard, fill32, fill16, []
+
+    def put(self, t, dtype=torch.float32):
+        self.keep.append(t.to(self.dev, dtype).contiguous())
+        return self.keep[-1].data_ptr()
+
+    def padded(self, t, rows, pad, dtype=torch.float32):
+        """t (r, cols) in the first rows of a (rows, cols) buffer whose other rows hold `pad`"""
+        buf = torch.full((rows, t.shape[1]), pad, dtype=dtype)
+        buf[:t.shape[0]] = t.to(dtype)
+        return self.put(buf, dtype)
+
+    def guarded(self, rows, cols, dtype=torch.float32, init=None):
+        """(guard + rows + guard, cols) holding the fill (rows [guard, guard + len(init)) = init); returns (tensor, pointer to row guard)"""
+        g = self.guard
+        t = torch.full((g + rows + g, cols), self.fill16 if dtype == torch.float16 else self.fill32, dtype=dtype, device=self.dev)
+        if init is not None:
+            t[g:g + init.shape[0]] = init.to(self.dev, dtype)
+        self.keep.append(t)
+        return t, t.data_ptr() + g * cols * t.element_size()
+
+    def caches(self, a):
+        """kc, vc (n_slots, Hkv, Lmax, 64) -> guarded (guard + n_slots Hkv Lmax + guard, 64) buffers"""
+        kc, pk = self.guarded(a["kc"].numel() // 64, 64, init=a["kc"].reshape(-1, 64))
+        vc, pv = self.guarded(a["vc"].numel() // 64, 64, init=a["vc"].reshape(-1, 64))
+        return kc, pk, vc, pv
+
+
+def ar_attn(a, device="cuda:0", guard=2, fill32=-777.25, fill16=-777.0):
+    """Test aid over svc_op_ar_attn (include/seedvc_hip.h): ONE launch of a cache-touching AR kernel, a["kind"] = 0 ar_attn, 1
+    dec_attn2, 2 battn, 3 ar_prefill_attn, 4 ar_rope_cache, 5 ar_rope_cache_ragged.  a: H, Hkv, Lmax; x (rows, cols) fp32 (q |
+    qkv_raw (1, D + 2 kvd) | qkv); kc, vc (n_slots, Hkv, Lmax, 64) fp32; rope (Lmax, 32, 2); slots (list); seq_S (list, kinds 3
+    and 5); pos [[input_pos ...], [kv_pos ...]]; kind 1: hres (D,), eps, wo (D, D) fp16; kind 2: pad = what the rows n .. Bp - 1 of
+    q hold (NaN).  Returns dict(y16 | q_out | part, kc, vc, guard): the WHOLE device buffers, `guard` canary rows in front and
+    behind (fp32: fill32, fp16: fill16); y16 of kind 2 has Bp rows between the guards; kc, vc are (guard + n_slots Hkv Lmax +
+    guard, 64)."""
+    import ctypes as C
+    dev = torch.device(device)
+    kind = int(a["kind"])
+    with torch.cuda.device(dev):
+        b = _ArOpBuffers(dev, guard, fill32, fill16)
+        e = _lib.ArAttn()
+        e.kind, e.H, e.Hkv, e.Lmax = kind, int(a["H"]), int(a["Hkv"]), int(a["Lmax"])
+        D = 64 * e.H
+        x = a["x"]
+        pos = a["pos"]
+        R = len(pos[0])
+        e.n_slots = a["kc"].shape[0]
+        e.n = len(a["slots"]) if kind in (2, 3, 5) else R
+        rows = (e.n + 15) // 16 * 16 if kind == 2 else R
+        e.x = b.padded(x, rows, a.get("pad", float("nan"))) if kind == 2 else b.put(x)
+        e.ldq = x.shape[1]
+        out = {"guard": guard}
+        out["kc"], e.kc, out["vc"], e.vc = b.caches(a)
+        if a.get("rope") is not None:
+            e.rope = b.put(a["rope"])
+        host = [_lib.i32_host([int(v) for v in a["slots"]]), _lib.i32_host([int(v) for v in list(pos[0]) + list(pos[1])])]
+        e.slots, e.pos = C.cast(host[0], C.POINTER(C.c_int32)), C.cast(host[1], C.POINTER(C.c_int32))
+        if a.get("seq_S") is not None:
+            host.append(_lib.i32_host([int(v) for v in a["seq_S"]]))
+            e.seq_S = C.cast(host[-1], C.POINTER(C.c_int32))
+        if kind in (0, 2, 3):
+            out["y16"], e.y16 = b.guarded(rows, D, torch.float16)
+        if kind in (4, 5):
+            out["q_out"], e.q_out = b.guarded(rows, D)
+        if kind == 1:
+            e.hres, e.eps, e.wo = b.put(a["hres"]), float(a["eps"]), b.put(a["wo"], torch.float16)
+            out["part"], e.part = b.guarded(e.H, D)
+        _lib.check(_lib.lib().svc_op_ar_attn(C.byref(e), _lib.stream_ptr()))
+    return out
+
+
+_AR_ROLES = {"qkv": 0, "wo": 1, "w13": 2, "w2": 3, "head": 4}
+
+
+def ar_linear(a, device="cuda:0", guard=2, fill32=-777.25, fill16=-777.0, w_pad=0.5):
+    """Test aid over svc_op_ar_linear (include/seedvc_hip.h): ONE launch of a skinny AR linear.  a: path (0 GEMV pair, 1 batched, 2
+    the B = 1 decode step), role ("qkv", "wo", "w13", "w2", "head"), D, I, H, Hkv, V; x (rows, K) fp32 or fp16 as the role takes it;
+    W (N, K) fp16 (packed here into N rounded up to 128 rows, the others holding w_pad); gamma, eps; res (rows, D) and inplace (the
+    output buffer starts as res and res points at it); path 2: W2, part (H, D); the qkv role of paths 0 and 1: kc, vc, rope, slots,
+    pos, Lmax as in ar_attn.  Path 1 pads x and res to Bp = rows rounded up to 16 with a["pad"] (NaN).  Returns dict(out32 | out16 |
+    out2 | q_out, kc, vc, guard): the WHOLE buffers with `guard` canary rows in front and behind; path 1 outputs have Bp rows."""
+    import ctypes as C
+    dev = torch.device(device)
+    path, role = int(a["path"]), _AR_ROLES[a["role"]]
+    with torch.cuda.device(dev):
+        b = _ArOpBuffers(dev, guard, fill32, fill16)
+        e = _lib.ArLinear()
+        e.path, e.role = path, role
+        for n in ("D", "I", "H", "Hkv", "V"):
+            setattr(e, n, int(a[n]))
+        D, I, V = e.D, e.I, e.V
+        Nqkv = D + 128 * e.Hkv
+        x = a["x"].reshape(-1, a["x"].shape[-1])
+        S = x.shape[0]
+        e.rows = S
+        rows = (S + 15) // 16 * 16 if path == 1 else S
+        pad = a.get("pad", float("nan"))
+        e.x = b.padded(x, rows, pad, x.dtype)
+
+        def packed(w):
+            buf = torch.full(((w.shape[0] + 127) // 128 * 128, w.shape[1]), w_pad, dtype=torch.float16)
+            buf[:w.shape[0]] = w
+            return b.put(buf, torch.float16)
+        e.W = packed(a["W"])
+        if a.get("W2") is not None:
+            e.W2 = packed(a["W2"])
+        if a.get("gamma") is not None:
+            e.gamma, e.eps = b.put(a["gamma"]), float(a["eps"])
+        out = {"guard": guard}
+        host = []
+        if role == 0 and path != 2:
+            e.Lmax, e.n_slots = int(a["Lmax"]), a["kc"].shape[0]
+            out["kc"], e.kc, out["vc"], e.vc = b.caches(a)
+            e.rope = b.put(a["rope"])
+            host = [_lib.i32_host([int(v) for v in a["slots"]]), _lib.i32_host([int(v) for v in list(a["pos"][0]) + list(a["pos"][1])])]
+            e.slots, e.pos = C.cast(host[0], C.POINTER(C.c_int32)), C.cast(host[1], C.POINTER(C.c_int32))
+            out["q_out"], e.q_out = b.guarded(rows, D)
+        else:
+            cols = {0: Nqkv, 1: D, 3: D, 4: V}.get(role)
+            res = a.get("res")
+            if res is not None:
+                res = res.reshape(-1, D)
+                if path == 1:
+                    res = torch.cat([res, torch.full((rows - S, D), pad)])
+            if role == 2:
+                out["out16"], e.out16 = b.guarded(rows, I, torch.float16)
+            elif a.get("inplace"):
+                out["out32"], e.out32 = b.guarded(rows, cols, init=res)
+                e.res = e.out32
+            else:
+                out["out32"], e.out32 = b.guarded(rows, cols)
+                if res is not None:
+                    e.res = b.put(res)
+            if path == 2 and role in (1, 2):
+                out["out2"], e.out2 = b.guarded(1, Nqkv if role == 1 else D)
+            if a.get("part") is not None:
+                e.part = b.put(a["part"])
+        _lib.check(_lib.lib().svc_op_ar_linear(C.byref(e), _lib.stream_ptr()))
+    return out
+
+
 def rmsnorm(x, gamma, w=None, b=None, add_one=False):
     rows, D = x.shape
     dev = x.device
