@@ -967,6 +967,63 @@ int svc_rt_push_gated(const svc_resampler_t* r, const float* block, long long st
                       int32_t* gate_mask,      /* device out [N][Lin / zc], 1 = frame muted; may be NULL                    */
                       void* stream);
 
+/* ---------------------------------------------------------------- real-time sessions: pitch (csrc/rt_pitch.hip)
+ * The drivers' pitch step (svc_f0_adjust: voiced-median shift in the log domain, semitone shift) for streams, which have no
+ * "whole source" to take a median of: every slot keeps running voiced-pitch statistics on the device, in which each 10 ms frame
+ * of the stream is counted exactly once, and the applied shift glides towards its target.  One launch for N streams;
+ * conventions of svc_rt_push: `slots`, `auto_adjust` and `semitones` are HOST arrays consumed before the call returns,
+ * arguments are checked before anything is launched, nothing synchronises, copies or allocates.
+ *
+ * `state`: svc_rt_pitch_state_words(max_slots) int32 words, [max_slots][SVC_RT_PITCH_STATE_WORDS]; per slot
+ *   words 0 .. 1535  the histogram of voiced frames, 256 bins per octave over [32, 2048) Hz;
+ *   word 1536        n, the number of voiced frames counted so far;
+ *   word 1537        the bits of the float s, the log shift that was applied by the last call;
+ *   word 1538        the median bin the last call found (0 while n == 0);  words 1539 .. 1543 are reserved and kept.
+ * All zeros is a fresh stream.  Per listed stream s = slots[k], in this order:
+ *   counted frames: the frames i in [Tf - lag - n_new, Tf - lag) of row k.  A block advances the context by exactly n_new frames
+ *         (n_new = 2 Lin / zc at hop 160), so every frame of the stream is counted exactly once, when it is `lag` frames from the
+ *         end of the context (the last frames of a context are provisional: the next push computes their samples again);
+ *   voicing and binning: a counted frame is voiced iff f0 > 1.f (svc_f0_adjust's rule; NaN is unvoiced).  A voiced frame adds 1
+ *         to state[s][bin], bin = clamp((float_bits(f0) >> 15) - 33792, 0, 1535): the bit pattern of f0 itself, no
+ *         transcendental, so a host statement reproduces it in exact integers; values outside [32, 2048) Hz, +inf included, go
+ *         to the end bins.  n grows by the number of voiced counted frames;
+ *   running median: r = (n - 1) / 2, the lower-middle rank (torch's rule, as svc_f0_adjust); the median bin is the first bin
+ *         whose cumulative count exceeds r, in the histogram that includes this call's frames;  m_run = logf(c + 1e-5f) with c
+ *         the float of bits ((bin + 33792) << 15) | 0x4000, the bin's centre;
+ *   target: d = ref_median[s] - m_run when auto_adjust[k] != 0, n >= max(warmup, 1) and ref_median[s] > 0, else d = 0.  A voiced
+ *         median is the log of a float above 1, so it is positive; 0 (what svc_f0_adjust's `medians` holds for a reference
+ *         without a voiced frame), a negative value or NaN stands for "no reference" and gives no shift, as svc_f0_adjust
+ *         applies none when a side has no voiced frame;
+ *   glide: with s_old the float of word 1537, s_new = d when |d - s_old| <= max_step or the step is off (max_step <= 0 or
+ *         +inf): arrival is exact; otherwise s_new = s_old + max_step when d > s_old, else s_old - max_step.  Word 1537 becomes
+ *         s_new, shift_out[k] = s_new;
+ *   output, for all i < Tf, lg = logf(f0 + 1e-5f), factor = exp2f(semitones[k] * (1.f / 12.f)):
+ *         out = expf(s_new == 0 ? lg : lg + s_new) * factor     voiced frames
+ *         out = expf(lg)                                        unvoiced frames
+ *         (the expressions of svc_f0_adjust: with auto_adjust[k] == 0 and s_old == 0 the row equals
+ *         svc_f0_adjust(auto_adjust = 0) bit for bit).
+ * Rows of slots that are not listed keep every bit.  A stream's state and output are a function of its own frames and settings
+ * alone: not of N, k, the slot or its companions; all counting is in integers, so no result depends on an order.  The statistics
+ * never forget: a stream that changes register keeps the median of its whole past until the slot's row is zeroed.
+ *
+ * Refused (non-zero, svc_last_error() names it, nothing touched): n_new < 1, lag < 0 or Tf - lag - n_new < 0; N outside 1 .. 64;
+ * a slot outside [0, max_slots) or listed twice; stride or out_stride below Tf; warmup < 0; a NaN max_step; a semitones entry
+ * that is not finite; null pointers (semitones and shift_out may be NULL); out overlapping f0 or state. */
+enum { SVC_RT_PITCH_BINS = 1536, SVC_RT_PITCH_STATE_WORDS = 1536 + 8 };
+long long svc_rt_pitch_state_words(int max_slots);          /* int32 words to allocate for `state`; needs no GPU */
+int svc_rt_pitch(const float* f0, long long stride, int Tf,  /* f0[k][0..Tf): Hz, the RMVPE track of slots[k]'s context */
+                 int n_new, int lag,                         /* frames a block renews; frames at the end that are still provisional */
+                 int N, const int32_t* slots, int max_slots, /* HOST [N], consumed before return (as svc_rt_push) */
+                 int32_t* state,                             /* device [max_slots][SVC_RT_PITCH_STATE_WORDS]; zeros = fresh stream */
+                 const float* ref_median,                    /* device [max_slots]: log-domain median of the slot's reference */
+                 const int32_t* auto_adjust,                 /* HOST [N] 0/1 */
+                 const float* semitones,                     /* HOST [N] or NULL (= 0) */
+                 int warmup, float max_step,                 /* voiced frames before the median is used; largest change of the
+                                                                applied log shift per call (<= 0 or +inf: none) */
+                 float* out, long long out_stride,           /* out[k][0..Tf): the shifted track the regulator takes */
+                 float* shift_out,                           /* device [N] applied log shift, or NULL */
+                 void* stream);
+
 /* ---------------------------------------------------------------- op-level entry points (parity tests) */
 /* C[M][N] (fp32) = act(A[M][K] * W[N][K]^T + bias) ; dtype 0: operands rounded to fp16, 1: fp32 MFMA.  act: a KG_ACT_* value
  * (0 none, 1 SiLU, 2 ELU, 3 leaky ReLU 0.1, 4 tanh, 5 abs, 6 clamp, 7 sigmoid, 8 GELU in the exact erf form). */

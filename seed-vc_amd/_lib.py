@@ -26,7 +26,7 @@ EXPORTS = [
     "svc_ar_session_active",
     "svc_lr_create", "svc_lr_destroy", "svc_lr_forward", "svc_crossfade",
     "svc_chunks_gather_cond", "svc_chunks_assemble", "svc_sola_step", "svc_rt_push", "svc_rt_push_tiles", "svc_rt_ring_floats",
-    "svc_rt_out", "svc_rt_push_gated", "svc_rt_out_dev",
+    "svc_rt_out", "svc_rt_push_gated", "svc_rt_out_dev", "svc_rt_pitch_state_words", "svc_rt_pitch",
     "svc_vad_create", "svc_vad_destroy", "svc_vad_rows", "svc_vad_history", "svc_vad_state_floats", "svc_vad_scores", "svc_vad_detect",
     "svc_vad_step",
     "svc_campplus_create", "svc_campplus_destroy", "svc_campplus_forward", "svc_kaldi_fbank_frames", "svc_kaldi_fbank",
@@ -266,6 +266,12 @@ def lib():
         l.svc_vad_step.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_long, C.c_int, C.POINTER(C.c_int64), C.c_int,
                                    C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                    C.c_void_p]
+        # the streams' pitch step: slots, auto flags and semitones as HOST arrays
+        l.svc_rt_pitch_state_words.argtypes = [C.c_int]
+        l.svc_rt_pitch_state_words.restype = C.c_longlong
+        l.svc_rt_pitch.argtypes = [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int,
+                                   C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int, C.c_float,
+                                   C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]
         l.svc_rt_push_tiles.argtypes = [C.c_int]
         l.svc_rt_ring_floats.argtypes = [C.c_int, C.c_int]
         l.svc_rt_ring_floats.restype = C.c_longlong

@@ -1188,6 +1188,7 @@ class RealtimeEngine:
         self._gate = {}                     # slot -> gate threshold as an energy of 4 zc samples (`set_gate`); absent: off
         self._vad = None                    # `attach_vad`: the device-resident VAD of `step_audio`
         self._sampler = {}                  # slot -> (n_timesteps, inference_cfg_rate, temperature), None = the step call's (`set_sampler`)
+        self._pitch = None                  # `attach_pitch`: the device-resident pitch track of `step_audio` (f0-conditioned models)
 
     def open(self, prompt_condition, mel2, style2):
         """A new stream on the reference (prompt_condition (1, P, Dc), mel2 (1, C, P), style2 (1, Ds)) -> its slot, the
@@ -1210,6 +1211,7 @@ class RealtimeEngine:
         self._gate.pop(slot, None)
         self._sampler.pop(slot, None)
         self._zero_vad(slot, on=False)
+        self._zero_pitch(slot, forget=True)
         return slot
 
     def _check_slot(self, slot, what):
@@ -1226,6 +1228,7 @@ class RealtimeEngine:
         self._gate.pop(slot, None)
         self._sampler.pop(slot, None)
         self._zero_vad(slot, on=False)
+        self._zero_pitch(slot, forget=True)
 
     def reset(self, slot):
         """Zeroes the stream's SOLA buffer (the GUI does so when a stream restarts)."""
@@ -1235,6 +1238,7 @@ class RealtimeEngine:
         self._speech[slot] = True
         if self._vad is not None:
             self._zero_vad(slot, on=slot in self._vad["on"])
+        self._zero_pitch(slot, forget=False)
 
     # ------------------------------------------------------------------------------------------- live settings
     def attach_output(self, resample_out, fade_in=None, fade_out=None):
@@ -1367,6 +1371,30 @@ class RealtimeEngine:
         return self._step(slots, content, n_timesteps, inference_cfg_rate, z, vocoder_kwargs, return_parts, None)
 
     @torch.inference_mode()
+    def step_f0(self, slots, content, f0, f0_lens, n_timesteps, inference_cfg_rate, z=None, vocoder_kwargs=None, return_parts=False,
+                seeds=None):
+        """`step` for an f0-conditioned regulator with the caller's pitch track: f0 (n, Tf) in Hz, row k for slots[k], f0_lens n
+        host frame counts (None: all Tf), handed to the regulator as `length_regulator(content, ylens=[S] * n, n_quantizers=3,
+        f0=f0, f0_lens=f0_lens)`; seeds as `step_seeded` (then z is None).  `step_audio` after `attach_pitch` is this step on
+        the track `svc_rt_pitch` wrote.  (A method of its own: the parameter list of `step` is part of its contract.)"""
+        if f0 is None:
+            raise ValueError("RealtimeEngine.step_f0: f0 is None")
+        if f0.dim() != 2 or f0.size(0) != len(slots):
+            raise ValueError(f"RealtimeEngine.step_f0: f0 {tuple(f0.shape)} is not (n = {len(slots)}, Tf)")
+        if f0_lens is not None:
+            f0_lens = _lib.int_list(f0_lens)
+            if len(f0_lens) != len(slots) or not all(0 <= v <= f0.size(1) for v in f0_lens):
+                raise ValueError(f"RealtimeEngine.step_f0: f0_lens {f0_lens} for {len(slots)} rows of {f0.size(1)} frames")
+        return self._step(slots, content, n_timesteps, inference_cfg_rate, z, vocoder_kwargs, return_parts, seeds, None, f0, f0_lens)
+
+    def _regulate(self, content, n, f0, f0_lens):
+        """The regulator call of a step.  Without a pitch track it is the call it always was."""
+        ylens = torch.LongTensor([self.S] * n)
+        if f0 is None:
+            return self.length_regulator(content, ylens=ylens, n_quantizers=3, f0=None)[0]
+        return self.length_regulator(content, ylens=ylens, n_quantizers=3, f0=f0, f0_lens=f0_lens)[0]
+
+    @torch.inference_mode()
     def step_seeded(self, slots, content, n_timesteps, inference_cfg_rate, seeds, vocoder_kwargs=None, return_parts=False):
         """`step` with seeds -- n integers in [0, 2^64) for THIS block, row k for slots[k] -- in place of z and of phase0 /
         noise in vocoder_kwargs (which may still pin HiFT's f0).  The caller derives them per block, e.g.
@@ -1377,7 +1405,8 @@ class RealtimeEngine:
             raise ValueError("RealtimeEngine.step_seeded: seeds is None")
         return self._step(slots, content, n_timesteps, inference_cfg_rate, None, vocoder_kwargs, return_parts, seeds)
 
-    def _step(self, slots, content, n_timesteps, inference_cfg_rate, z, vocoder_kwargs, return_parts, seeds, speech_dev=None):
+    def _step(self, slots, content, n_timesteps, inference_cfg_rate, z, vocoder_kwargs, return_parts, seeds, speech_dev=None,
+              f0=None, f0_lens=None):
         slots = [int(s) for s in slots]
         seeds = _seed_list("RealtimeEngine.step_seeded", seeds, len(slots), z, vocoder_kwargs)
         for s in slots:
@@ -1397,7 +1426,7 @@ class RealtimeEngine:
         with torch.cuda.device(dev):
             st = self._stack_prompts(slots)
             P = st["P"]
-            cond = self.length_regulator(content, ylens=torch.LongTensor([S] * n), n_quantizers=3, f0=None)[0]   # (n, S, Dc)
+            cond = self._regulate(content, n, f0, f0_lens)                       # (n, S, Dc)
             if cond.size(1) != S:
                 raise ValueError(f"RealtimeEngine.step: the length regulator gave {cond.size(1)} frames, {S} expected")
             mu = _assemble_cond(st["prompt_condition"], P, cond, [S] * n, st["Pmax"] + S)
@@ -1442,6 +1471,131 @@ class RealtimeEngine:
         if return_parts:
             return out, dict(mel=vc, infer=infer, offsets=offsets)
         return out
+
+    # ------------------------------------------------------------------------------------------- pitch
+    def attach_pitch(self, rmvpe, lag_frames=8, warmup_frames=50, max_step_cents=100.0, thred=0.03):
+        """Pitch for f0-conditioned (singing) models in `step_audio`: the offline drivers' `auto_f0_adjust` / `pitch_shift` for a
+        stream.  rmvpe: anything with `f0_batch((n, L16) samples, thred=) -> (n, frames(L16))` and `frames(n_samples)`
+        (seedvc_amd.rmvpe.RMVPE).  Per block the 16 kHz context goes through `rmvpe.f0_batch`, one `svc_rt_pitch` counts the
+        2 Lin / zc frames the block renews -- those `lag_frames` before the end of the context -- into the slot's running
+        voiced-pitch histogram and shifts the track by (reference median - running median), gliding by at most `max_step_cents`
+        per block, and by the slot's semitones (`set_pitch`); the regulator takes the track from frame 2 ce on (a content row
+        of 20 ms is two f0 frames).  Needs `attach_audio` with a 16 kHz content rate, a regulator with `f0_condition`,
+        lag_frames >= 2 (the last z16 samples of a context are computed again by the next push),
+        rmvpe.frames(L16) - lag_frames - 2 Lin / zc >= 0 and 2 ce < rmvpe.frames(L16).  Allocates the per-slot statistics and
+        reference medians; `open` and `reset` zero a slot's statistics as they zero its SOLA buffer.  max_step_cents <= 0 or
+        +inf means no limit: the shift goes to its target at once.  A second call replaces everything the first one allocated,
+        so it is refused while a slot holds a reference median or a `set_pitch` setting.
+
+        The defaults are judgement, not measurements: 8 frames of lag keep the counted frames clear of the samples the next
+        push recomputes and of RMVPE's view of the zero padding behind them; 50 voiced frames (0.5 s) before a median is
+        trusted; 100 cents per block, so a settled shift of an octave arrives in about 2 s of 180 ms blocks."""
+        a, old = self._audio, self._pitch
+        if a is None:
+            raise ValueError("RealtimeEngine.attach_pitch: attach_audio has not been called")
+        if old is not None and (old["has_ref"] or old["auto"] or old["semis"]):
+            raise ValueError(f"RealtimeEngine.attach_pitch: slots {sorted(old['has_ref'] | set(old['auto']) | set(old['semis']))} hold a "
+                             f"reference median or pitch settings that a second attach would drop")
+        if a["z16"] != 320:
+            raise ValueError(f"RealtimeEngine.attach_pitch: the content rate is {a['z16'] * 50} Hz, RMVPE takes 16000")
+        if not getattr(self.length_regulator, "cfg", {}).get("f0_condition"):
+            raise ValueError("RealtimeEngine.attach_pitch: the length regulator is not f0-conditioned (cfg['f0_condition'])")
+        if not callable(getattr(rmvpe, "f0_batch", None)) or not callable(getattr(rmvpe, "frames", None)):
+            raise ValueError("RealtimeEngine.attach_pitch: rmvpe has no f0_batch / frames")
+        lag, warmup, cents, thred = int(lag_frames), int(warmup_frames), float(max_step_cents), float(thred)
+        if lag < 2:
+            raise ValueError(f"RealtimeEngine.attach_pitch: lag_frames = {lag_frames!r}, at least 2 (the last 20 ms of a context are "
+                             f"provisional)")
+        if warmup < 0 or math.isnan(cents) or math.isnan(thred):
+            raise ValueError(f"RealtimeEngine.attach_pitch: warmup_frames = {warmup_frames!r}, max_step_cents = {max_step_cents!r}, "
+                             f"thred = {thred!r}")
+        Tf, n_new = int(rmvpe.frames(a["L16"])), 2 * (a["Lin"] // a["zc"])
+        if Tf - lag - n_new < 0:
+            raise ValueError(f"RealtimeEngine.attach_pitch: the context has {Tf} f0 frames, a block counts {n_new} of them "
+                             f"{lag} before its end")
+        if 2 * a["ce"] >= Tf:
+            raise ValueError(f"RealtimeEngine.attach_pitch: 2 ce = {2 * a['ce']} frames are dropped of a track of {Tf}")
+        from . import rmvpe as _rmvpe
+        max_step = cents * math.log(2.0) / 1200.0 if 0.0 < cents < float("inf") else 0.0       # cents -> natural-log units; 0: no limit
+        self._pitch = dict(rmvpe=rmvpe, lag=lag, warmup=warmup, max_step=max_step, thred=thred, Tf=Tf, n_new=n_new,
+                           state=torch.zeros(self.max_streams, _rmvpe.PITCH_STATE_WORDS, device=self.device, dtype=torch.int32),
+                           ref_median=torch.zeros(self.max_streams, device=self.device, dtype=torch.float32),
+                           has_ref=set(), auto={}, semis={})
+
+    def set_reference_f0(self, slot, f0_ref, f0_ref_frames=None):
+        """The pitch track of an open slot's reference (f0_ref (1, To) | (To,) in Hz, `rmvpe.f0_batch` of the reference clip;
+        f0_ref_frames: its valid frames, default all): the slot's reference median -- torch's lower-middle median of
+        log(f0 + 1e-5) over the voiced frames -- is written on the device from the `medians` output of `svc_f0_adjust` (column
+        m_ori), with no synchronisation, and the automatic shift is switched on for the slot.  Until this call a slot has no
+        automatic shift and `set_pitch(auto_adjust=True)` raises.  A reference without a voiced frame has the median 0.0, which
+        the host cannot see without a synchronisation: `svc_rt_pitch` takes a median that is not positive as "no reference" and
+        applies no automatic shift, as `svc_f0_adjust` applies none.  (A method of its own: the parameter list of `open` is
+        part of its contract.)  Needs `attach_pitch`."""
+        self._check_slot(slot, "set_reference_f0")
+        p = self._pitch
+        if p is None:
+            raise ValueError("RealtimeEngine.set_reference_f0: attach_pitch has not been called")
+        f = f0_ref.reshape(1, -1) if f0_ref.dim() == 1 else f0_ref
+        if f.dim() != 2 or f.size(0) != 1 or f.size(1) < 1:
+            raise ValueError(f"RealtimeEngine.set_reference_f0: f0_ref {tuple(f0_ref.shape)} is not (1, To)")
+        To = f.size(1)
+        frames = To if f0_ref_frames is None else int(f0_ref_frames)
+        if not 1 <= frames <= To:
+            raise ValueError(f"RealtimeEngine.set_reference_f0: f0_ref_frames = {f0_ref_frames!r} of {To}")
+        from .rmvpe import f0_adjust
+        f = _lib.f32c(f, self.device)
+        _, med = f0_adjust(f, [frames], f, [frames], auto_f0_adjust=False, pitch_shift=0, return_medians=True)
+        p["ref_median"][slot:slot + 1].copy_(med[:, 1])
+        p["has_ref"].add(slot)
+        p["auto"].setdefault(slot, True)
+
+    def set_pitch(self, slot, semitones=None, auto_adjust=None):
+        """The offline drivers' `pitch_shift` (semitones, any finite number) and `auto_f0_adjust` for one stream; None keeps
+        what the slot has.  Defaults on `open`: 0 semitones, and the automatic shift on iff the slot has a reference median
+        (`set_reference_f0`); kept across `reset`.  Switching the automatic shift lets the applied shift glide to its new
+        target.  Needs `attach_pitch`."""
+        self._check_slot(slot, "set_pitch")
+        p = self._pitch
+        if p is None:
+            raise ValueError("RealtimeEngine.set_pitch: attach_pitch has not been called")
+        if semitones is not None and not math.isfinite(float(semitones)):
+            raise ValueError(f"RealtimeEngine.set_pitch: semitones = {semitones!r}")
+        if auto_adjust and slot not in p["has_ref"]:
+            raise ValueError(f"RealtimeEngine.set_pitch: slot {slot} has no reference median (set_reference_f0): no automatic shift")
+        if semitones is not None:
+            p["semis"][slot] = float(semitones)
+        if auto_adjust is not None:
+            p["auto"][slot] = bool(auto_adjust)
+
+    def _zero_pitch(self, slot, forget):
+        """Fresh statistics for the slot; forget: also its reference median and settings (`open`, `close`)."""
+        p = self._pitch
+        if p is None:
+            return
+        p["state"][slot].zero_()
+        if forget:
+            p["ref_median"][slot] = 0.0
+            p["has_ref"].discard(slot)
+            p["auto"].pop(slot, None)
+            p["semis"].pop(slot, None)
+
+    def _pitch_track(self, slots, ctx, return_parts):
+        """The pitch stage of `step_audio`: ctx (n, L16) -> (f0 (n, Tf - 2 ce) for the regulator, f0_lens, parts | None)."""
+        from . import rmvpe as _rmvpe
+        p, ce2 = self._pitch, 2 * self._audio["ce"]
+        raw = p["rmvpe"].f0_batch(ctx, thred=p["thred"])
+        if raw.dim() != 2 or tuple(raw.shape) != (len(slots), p["Tf"]):
+            raise ValueError(f"RealtimeEngine.step_audio: rmvpe.f0_batch gave {tuple(raw.shape)}, ({len(slots)}, {p['Tf']}) expected")
+        res = _rmvpe.rt_pitch(raw, p["n_new"], p["lag"], slots, p["state"], p["ref_median"],
+                              [1 if p["auto"].get(s, False) else 0 for s in slots], [p["semis"].get(s, 0.0) for s in slots],
+                              warmup=p["warmup"], max_step=p["max_step"], return_shift=return_parts)
+        f0, shift = res if return_parts else (res, None)
+        parts = None
+        if return_parts:
+            # one device copy per slot, addressed by host integers: an index tensor would be a blocking host-to-device copy
+            voiced = torch.stack([p["state"][s, _rmvpe.PITCH_BINS] for s in slots])
+            parts = dict(f0_raw=raw, f0=f0, pitch_shift=shift, pitch_voiced=voiced)
+        return f0[:, ce2:], [p["Tf"] - ce2] * len(slots), parts
 
     # ------------------------------------------------------------------------------------------- audio in (DESIGN.md 8l)
     def attach_audio(self, content, resample, Lin, L16, ce_dit_difference):
@@ -1497,7 +1651,9 @@ class RealtimeEngine:
         `svc_rt_push` (history, resampling, context shift and the dense batch), then
         `content.semantic_fn(ctx)[:, int(ce_dit_difference * 50):]`, then `step`.  -> as `step`; with return_parts the dict also
         carries ctx (n, L16) and content (n, T, D).  Lengths and slots are host integers: nothing synchronises.  Where a listed
-        slot has a gate (`set_gate`) the push is `svc_rt_push_gated` and the dict also carries gate_mask (n, Lin / zc) int32."""
+        slot has a gate (`set_gate`) the push is `svc_rt_push_gated` and the dict also carries gate_mask (n, Lin / zc) int32.
+        After `attach_pitch` the regulator also gets the streams' shifted pitch tracks (`rmvpe.f0_batch(ctx)`, one `svc_rt_pitch`;
+        DESIGN.md 8q) and the dict carries f0_raw and f0 (n, Tf), pitch_shift (n,) and pitch_voiced (n,) int32."""
         return self._step_audio(slots, audio, n_timesteps, inference_cfg_rate, z, vocoder_kwargs, return_parts, None)
 
     @torch.inference_mode()
@@ -1549,9 +1705,12 @@ class RealtimeEngine:
                     v["total"][s] += v["n_new"]
                 speech_dev = v["flags"]
             content = a["content"].semantic_fn(ctx)[:, a["ce"]:]
-        res = self._step(slots, content, n_timesteps, inference_cfg_rate, z, vocoder_kwargs, return_parts, seeds, speech_dev)
+            f0, f0_lens, pitch_parts = self._pitch_track(slots, ctx, return_parts) if self._pitch is not None else (None, None, None)
+        res = self._step(slots, content, n_timesteps, inference_cfg_rate, z, vocoder_kwargs, return_parts, seeds, speech_dev, f0, f0_lens)
         if return_parts:
             res[1].update(ctx=ctx, content=content)
+            if pitch_parts is not None:
+                res[1].update(pitch_parts)
             if vad_parts is not None:
                 res[1]["vad"] = dict(vad_parts, slots=on, flags=speech_dev.clone())
             if mask is not None:

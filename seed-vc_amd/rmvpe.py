@@ -151,3 +151,50 @@ def f0_adjust(f0_alt, alt_lens, f0_ori, ori_lens, auto_f0_adjust=True, pitch_shi
                                             int(bool(auto_f0_adjust)), (C.c_float * B)(*semis), _lib.ptr(out), _lib.ptr(med),
                                             _lib.stream_ptr()))
     return (out, med) if return_medians else out
+
+
+PITCH_BINS, PITCH_STATE_WORDS = 1536, 1536 + 8         # SVC_RT_PITCH_BINS, SVC_RT_PITCH_STATE_WORDS
+
+
+def rt_pitch_state(max_slots, device="cuda:0"):
+    """The per-slot running pitch statistics of `rt_pitch`: (max_slots, PITCH_STATE_WORDS) int32 zeros, a fresh stream per row
+    (words 0 .. 1535 the histogram, 1536 the voiced count, 1537 the bits of the applied log shift, 1538 the median bin)."""
+    n = int(_lib.lib().svc_rt_pitch_state_words(int(max_slots)))
+    if n <= 0:
+        raise ValueError(f"rt_pitch_state: max_slots = {max_slots!r}")
+    return torch.zeros(int(max_slots), n // int(max_slots), device=device, dtype=torch.int32)
+
+
+@torch.inference_mode()
+def rt_pitch(f0, n_new, lag, slots, state, ref_median, auto_adjust, semitones=None, warmup=50, max_step=0.0, return_shift=False):
+    """The pitch step of live streams (`svc_rt_pitch`): f0 (N, Tf) device float32, row k the RMVPE track of the
+    context of stream slots[k]; the n_new frames that lie `lag` frames before the end are counted into the slot's row of `state`
+    (`rt_pitch_state`), the applied log shift glides by at most max_step per call towards ref_median[slot] - running median
+    where auto_adjust[k] is set, ref_median[slot] is positive (0: a reference without a voiced frame) and the slot has
+    counted `warmup` voiced frames (else towards 0), and every frame is shifted
+    by it and by semitones[k].  slots, auto_adjust, semitones: N host values (semitones: one number for all, or None = 0).
+    -> the shifted track (N, Tf); with return_shift also the applied log shifts (N,).  Nothing is synchronised."""
+    dev = f0.device
+    with torch.cuda.device(dev):
+        f = f0 if f0.dtype == torch.float32 and f0.stride(-1) == 1 and f0.dim() == 2 else _lib.f32c(f0)
+        if f.dim() != 2:
+            raise ValueError(f"rt_pitch: f0 {tuple(f0.shape)} is not (N, Tf)")
+        N, Tf = f.shape
+        slots, aut = _lib.int_list(slots), [int(bool(v)) for v in _lib.int_list(auto_adjust)]
+        if torch.is_tensor(semitones):
+            semitones = semitones.tolist()
+        semis = None if semitones is None else \
+            [float(x) for x in semitones] if isinstance(semitones, (list, tuple)) else [float(semitones)] * N
+        if len(slots) != N or len(aut) != N or (semis is not None and len(semis) != N):
+            raise ValueError(f"rt_pitch: slots, auto_adjust and semitones must all have {N} entries")
+        if state.dtype != torch.int32 or state.dim() != 2 or state.size(1) != PITCH_STATE_WORDS or not state.is_contiguous():
+            raise ValueError(f"rt_pitch: state must be contiguous int32 (max_slots, {PITCH_STATE_WORDS})")
+        if ref_median.dtype != torch.float32 or ref_median.numel() != state.size(0) or not ref_median.is_contiguous():
+            raise ValueError("rt_pitch: ref_median must be contiguous float32 (max_slots,)")
+        out = torch.empty(N, Tf, device=dev)
+        shift = torch.empty(N, device=dev) if return_shift else None
+        _lib.check(_lib.lib().svc_rt_pitch(_lib.ptr(f), f.stride(0), Tf, int(n_new), int(lag), N, _lib.i32_host(slots), state.size(0),
+                                           _lib.ptr(state), _lib.ptr(ref_median), _lib.i32_host(aut),
+                                           None if semis is None else (C.c_float * N)(*semis), int(warmup), float(max_step),
+                                           _lib.ptr(out), out.stride(0), _lib.ptr(shift), _lib.stream_ptr()))
+    return (out, shift) if return_shift else out
