@@ -1024,6 +1024,53 @@ int svc_rt_pitch(const float* f0, long long stride, int Tf,  /* f0[k][0..Tf): Hz
                  float* shift_out,                           /* device [N] applied log shift, or NULL */
                  void* stream);
 
+/* ---------------------------------------------------------------- real-time sessions: pitch on the context's tail
+ * svc_rt_pitch for a stream whose RMVPE track covers only the LAST W frames of its context: every slot keeps the raw track of
+ * its whole context in a cache row that moves with the stream, and (memory > 0) the bins of its last `memory` counted frames
+ * in a ring, so that the statistics forget.  One launch, one workgroup per listed stream, conventions and state of svc_rt_pitch.
+ *
+ * `cache`: svc_rt_pitch_cache_words(max_slots, Tf) floats, [max_slots][Tf], raw Hz; zeros = a fresh stream (0 Hz is unvoiced).
+ * `ring`:  svc_rt_pitch_ring_words(max_slots, memory) int32 words, [max_slots][memory + 2]; per slot
+ *   words 0 .. memory - 1  the entries: the bin of a counted voiced frame, or -1 for a counted unvoiced frame;
+ *   word memory            head, the index of the oldest entry;   word memory + 1   fill, the number of entries held.
+ *   All zeros is a fresh stream.  memory == 0 with ring == NULL: the statistics never forget (svc_rt_pitch's).
+ * Per listed stream s = slots[k], with `old` the slot's cache row before the call, in this order:
+ *   cache update: new[i] = f0_win[k][i - (Tf - W)]   for i >= Tf - W + guard   (the window's frame j is context frame Tf - W + j;
+ *                 new[i] = old[i + n_new]             for i <  Tf - W + guard    its first `guard` frames are not trusted)
+ *         W - guard >= n_new, so i + n_new < Tf and no frame is left unwritten.  cache[s] becomes new; raw_out[k] = new.
+ *   counted frames: the frames i in [Tf - lag - n_new, Tf - lag) of new, voicing and binning as svc_rt_pitch:
+ *         voiced iff new[i] > 1.f, bin = clamp((float_bits(new[i]) >> 15) - 33792, 0, 1535);
+ *   forgetting (memory > 0): the ring is a FIFO of `memory` entries.  The counted frames are pushed in frame order; with
+ *         fill the count before the call, e = max(0, fill + n_new - memory) entries are pushed out: the oldest e, those at
+ *         (head + j) % memory for j < e.  An entry pushed out that is a bin takes 1 from state[s][bin] and from n.  Counted frame
+ *         j goes to (head + fill + j) % memory; then head = (head + e) % memory, fill = fill + n_new - e.  So n, the rank
+ *         r = (n - 1) / 2, the median bin and the comparison with `warmup` are over what the ring holds; when n falls below
+ *         max(warmup, 1) the target is 0 and the shift glides there;
+ *   running median, target, glide, words 1536 .. 1538, shift_out and the Tf outputs over new: svc_rt_pitch's, by the same
+ *         device code (with memory == 0 the call equals svc_rt_pitch on raw_out[k] bit for bit).
+ * Rows of slots that are not listed keep every bit of cache, ring and state.  A stream's state, cache, ring and output are a
+ * function of its own frames and settings alone: not of N, k, the slot or its companions.  The shift of the cache is in
+ * place: a workgroup stages its whole row in LDS across a barrier before it stores a frame, so Tf is at most
+ * SVC_RT_PITCH_WIN_MAX_TF = 4096 frames (16 KB of LDS; 41 s of context); any n_new is safe.
+ *
+ * Refused (non-zero, svc_last_error() names it, nothing touched): everything svc_rt_pitch refuses (stride is compared with W);
+ * Tf above SVC_RT_PITCH_WIN_MAX_TF; W < 1 or W > Tf; guard < 0; W - guard < n_new; memory < 0, or 0 < memory < n_new; ring NULL
+ * while memory > 0 or given while memory == 0; cache NULL; raw_stride below Tf while raw_out is given; out or raw_out overlapping
+ * f0_win, cache, state, ring or each other; f0_win, cache, state and ring overlapping one another. */
+enum { SVC_RT_PITCH_WIN_MAX_TF = 4096 };
+long long svc_rt_pitch_cache_words(int max_slots, int Tf);       /* floats to allocate for `cache`; 0 for arguments out of range */
+long long svc_rt_pitch_ring_words(int max_slots, int memory);    /* int32 words to allocate for `ring`; 0 for memory == 0 */
+int svc_rt_pitch_win(const float* f0_win, long long stride,      /* f0_win[k][0..W): Hz, the RMVPE track of the last samples of slots[k]'s context */
+                     int W, int guard, int Tf,                   /* window frames; untrusted frames at its start; frames of a context */
+                     int n_new, int lag, int N, const int32_t* slots, int max_slots,     /* as svc_rt_pitch */
+                     float* cache,                               /* device [max_slots][Tf]; zeros = fresh stream */
+                     int32_t* ring, int memory,                  /* device [max_slots][memory + 2], or NULL with memory == 0 */
+                     int32_t* state, const float* ref_median, const int32_t* auto_adjust, const float* semitones, int warmup,
+                     float max_step,                             /* as svc_rt_pitch */
+                     float* out, long long out_stride,           /* out[k][0..Tf): the shifted track over new */
+                     float* raw_out, long long raw_stride,       /* raw_out[k][0..Tf) = new, or NULL */
+                     float* shift_out, void* stream);
+
 /* ---------------------------------------------------------------- op-level entry points (parity tests) */
 /* C[M][N] (fp32) = act(A[M][K] * W[N][K]^T + bias) ; dtype 0: operands rounded to fp16, 1: fp32 MFMA.  act: a KG_ACT_* value
  * (0 none, 1 SiLU, 2 ELU, 3 leaky ReLU 0.1, 4 tanh, 5 abs, 6 clamp, 7 sigmoid, 8 GELU in the exact erf form). */

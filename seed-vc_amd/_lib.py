@@ -27,6 +27,7 @@ EXPORTS = [
     "svc_lr_create", "svc_lr_destroy", "svc_lr_forward", "svc_crossfade",
     "svc_chunks_gather_cond", "svc_chunks_assemble", "svc_sola_step", "svc_rt_push", "svc_rt_push_tiles", "svc_rt_ring_floats",
     "svc_rt_out", "svc_rt_push_gated", "svc_rt_out_dev", "svc_rt_pitch_state_words", "svc_rt_pitch",
+    "svc_rt_pitch_cache_words", "svc_rt_pitch_ring_words", "svc_rt_pitch_win",
     "svc_vad_create", "svc_vad_destroy", "svc_vad_rows", "svc_vad_history", "svc_vad_state_floats", "svc_vad_scores", "svc_vad_detect",
     "svc_vad_step",
     "svc_campplus_create", "svc_campplus_destroy", "svc_campplus_forward", "svc_kaldi_fbank_frames", "svc_kaldi_fbank",
@@ -272,6 +273,13 @@ def lib():
         l.svc_rt_pitch.argtypes = [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int,
                                    C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int, C.c_float,
                                    C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]
+        # the same on the context's tail: window, guard, the slots' cache rows and rings of counted bins
+        l.svc_rt_pitch_cache_words.argtypes = l.svc_rt_pitch_ring_words.argtypes = [C.c_int, C.c_int]
+        l.svc_rt_pitch_cache_words.restype = l.svc_rt_pitch_ring_words.restype = C.c_longlong
+        l.svc_rt_pitch_win.argtypes = [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32),
+                                       C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32),
+                                       C.POINTER(C.c_float), C.c_int, C.c_float, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong,
+                                       C.c_void_p, C.c_void_p]
         l.svc_rt_push_tiles.argtypes = [C.c_int]
         l.svc_rt_ring_floats.argtypes = [C.c_int, C.c_int]
         l.svc_rt_ring_floats.restype = C.c_longlong

@@ -11,6 +11,8 @@ import torch
 
 from . import _lib
 
+_PITCH_HOP = 160                 # samples per f0 frame at 16 kHz (RMVPE.HOP): frame j of a clip is centred on sample 160 j
+
 
 def _cos2_windows(n):
     """(fade_in, fade_out) of the drivers' cos^2 crossfade over n samples, float64 (reference: inference.py:343-350).  The
@@ -1485,7 +1487,8 @@ class RealtimeEngine:
         rmvpe.frames(L16) - lag_frames - 2 Lin / zc >= 0 and 2 ce < rmvpe.frames(L16).  Allocates the per-slot statistics and
         reference medians; `open` and `reset` zero a slot's statistics as they zero its SOLA buffer.  max_step_cents <= 0 or
         +inf means no limit: the shift goes to its target at once.  A second call replaces everything the first one allocated,
-        so it is refused while a slot holds a reference median or a `set_pitch` setting.
+        so it is refused while a slot holds a reference median or a `set_pitch` setting; it also switches `set_pitch_window` and
+        `set_pitch_memory` off again.
 
         The defaults are judgement, not measurements: 8 frames of lag keep the counted frames clear of the samples the next
         push recomputes and of RMVPE's view of the zero padding behind them; 50 voiced frames (0.5 s) before a median is
@@ -1520,7 +1523,8 @@ class RealtimeEngine:
         self._pitch = dict(rmvpe=rmvpe, lag=lag, warmup=warmup, max_step=max_step, thred=thred, Tf=Tf, n_new=n_new,
                            state=torch.zeros(self.max_streams, _rmvpe.PITCH_STATE_WORDS, device=self.device, dtype=torch.int32),
                            ref_median=torch.zeros(self.max_streams, device=self.device, dtype=torch.float32),
-                           has_ref=set(), auto={}, semis={})
+                           has_ref=set(), auto={}, semis={},
+                           win=None, memory=0, cache=None, ring=None)       # `set_pitch_window`, `set_pitch_memory`: off
 
     def set_reference_f0(self, slot, f0_ref, f0_ref_frames=None):
         """The pitch track of an open slot's reference (f0_ref (1, To) | (To,) in Hz, `rmvpe.f0_batch` of the reference clip;
@@ -1567,12 +1571,91 @@ class RealtimeEngine:
         if auto_adjust is not None:
             p["auto"][slot] = bool(auto_adjust)
 
+    def set_pitch_window(self, window_frames, guard_frames=None):
+        """RMVPE on the context's tail: per block `rmvpe.f0_batch` sees only the last `window_frames` f0 frames of
+        the context (160 samples each), not all Tf; the older frames of a slot's raw track stay in a per-slot device cache that
+        moves with the stream, and one `svc_rt_pitch_win` updates it, counts and shifts.  The first `guard_frames` of a window
+        are not trusted (they sit next to RMVPE's reflect padding): the cache keeps what an earlier block wrote there.
+        Engine-wide (geometry and allocations are shared): needs `attach_pitch`, and is refused while any slot is open.
+        `set_pitch_window(None)` switches it off again.  Requires window_frames - guard_frames >= 2 Lin / zc + lag_frames (a counted
+        frame is one this block's window wrote), guard_frames >= 0, window_frames <= Tf <= 4096 and a window of at least
+        `svc_rmvpe_min_len()` samples.  With the window on, return_parts["f0_raw"] is the slots' cache rows (n, Tf) and
+        "f0_window" (n, window_frames) is RMVPE's track of the tail.
+
+        No values are proposed: suitable ones depend on RMVPE's receptive field (how far a frame's estimate looks to either
+        side), and the window's effect on the released checkpoint's accuracy is unmeasured here, because the checkpoint is
+        absent.  Internally RMVPE pads a clip's frames to a multiple of 32 (RV_TMULT), so windows of 33 .. 64 frames cost the
+        same network pass."""
+        p = self._pitch_setting("set_pitch_window")
+        if window_frames is None:
+            p["win"] = None
+            self._pitch_buffers()
+            return
+        if guard_frames is None:
+            raise ValueError("RealtimeEngine.set_pitch_window: guard_frames is needed with window_frames (no default is proposed)")
+        self._pitch_tf_limit("set_pitch_window")
+        W, guard = int(window_frames), int(guard_frames)
+        if guard < 0 or W > p["Tf"] or W - guard < p["n_new"] + p["lag"]:
+            raise ValueError(f"RealtimeEngine.set_pitch_window: window_frames = {window_frames!r}, guard_frames = {guard_frames!r}: "
+                             f"guard_frames >= 0, window_frames <= Tf = {p['Tf']} and window_frames - guard_frames >= "
+                             f"{p['n_new']} + {p['lag']} (the frames a block counts lie lag_frames before the end) are required")
+        n_win = self._audio["L16"] - _PITCH_HOP * (p["Tf"] - W)
+        if n_win < int(_lib.lib().svc_rmvpe_min_len()):
+            raise ValueError(f"RealtimeEngine.set_pitch_window: a window of {W} frames is {n_win} samples, RMVPE takes at least "
+                             f"{int(_lib.lib().svc_rmvpe_min_len())}")
+        p["win"] = (W, guard)
+        self._pitch_buffers()
+
+    def set_pitch_memory(self, memory_frames):
+        """Statistics that forget: the running median of a slot is taken over its last `memory_frames` counted
+        frames (10 ms each, voiced or not) instead of its whole past: a per-slot device ring holds their bins, and what a block
+        pushes out of it leaves the histogram again.  A hard window, not a decay; when fewer than `warmup_frames` voiced frames
+        remain the shift glides back to 0.  Engine-wide: needs `attach_pitch`, refused while any slot is open;
+        `set_pitch_memory(None)` switches it off again.  memory_frames >= 2 Lin / zc.  No value is proposed.  With only the
+        memory on the pitch step is `svc_rt_pitch_win` with the whole context as its window (window = Tf, guard = 0)."""
+        p = self._pitch_setting("set_pitch_memory")
+        if memory_frames is None:
+            p["memory"] = 0
+            self._pitch_buffers()
+            return
+        m = int(memory_frames)
+        if m < p["n_new"]:
+            raise ValueError(f"RealtimeEngine.set_pitch_memory: memory_frames = {memory_frames!r} is below the {p['n_new']} frames a "
+                             f"block counts")
+        self._pitch_tf_limit("set_pitch_memory")
+        p["memory"] = m
+        self._pitch_buffers()
+
+    def _pitch_setting(self, what):
+        if self._pitch is None:
+            raise ValueError(f"RealtimeEngine.{what}: attach_pitch has not been called")
+        if self._streams:
+            raise ValueError(f"RealtimeEngine.{what}: streams are open")
+        return self._pitch
+
+    def _pitch_tf_limit(self, what):
+        from .rmvpe import PITCH_WIN_MAX_TF
+        if self._pitch["Tf"] > PITCH_WIN_MAX_TF:
+            raise ValueError(f"RealtimeEngine.{what}: the context has {self._pitch['Tf']} f0 frames, svc_rt_pitch_win stages at most "
+                             f"{PITCH_WIN_MAX_TF}")
+
+    def _pitch_buffers(self):
+        """The slots' cache rows and rings for the settings as they stand (no slot is open: everything starts fresh)."""
+        from . import rmvpe as _rmvpe
+        p = self._pitch
+        on = p["win"] is not None or p["memory"] > 0
+        p["cache"] = _rmvpe.rt_pitch_cache(self.max_streams, p["Tf"], self.device) if on else None
+        p["ring"] = _rmvpe.rt_pitch_ring(self.max_streams, p["memory"], self.device) if on else None
+
     def _zero_pitch(self, slot, forget):
         """Fresh statistics for the slot; forget: also its reference median and settings (`open`, `close`)."""
         p = self._pitch
         if p is None:
             return
         p["state"][slot].zero_()
+        for name in ("cache", "ring"):
+            if p[name] is not None:
+                p[name][slot].zero_()
         if forget:
             p["ref_median"][slot] = 0.0
             p["has_ref"].discard(slot)
@@ -1583,6 +1666,8 @@ class RealtimeEngine:
         """The pitch stage of `step_audio`: ctx (n, L16) -> (f0 (n, Tf - 2 ce) for the regulator, f0_lens, parts | None)."""
         from . import rmvpe as _rmvpe
         p, ce2 = self._pitch, 2 * self._audio["ce"]
+        if p["cache"] is not None:
+            return self._pitch_track_win(slots, ctx, return_parts)
         raw = p["rmvpe"].f0_batch(ctx, thred=p["thred"])
         if raw.dim() != 2 or tuple(raw.shape) != (len(slots), p["Tf"]):
             raise ValueError(f"RealtimeEngine.step_audio: rmvpe.f0_batch gave {tuple(raw.shape)}, ({len(slots)}, {p['Tf']}) expected")
@@ -1596,6 +1681,28 @@ class RealtimeEngine:
             voiced = torch.stack([p["state"][s, _rmvpe.PITCH_BINS] for s in slots])
             parts = dict(f0_raw=raw, f0=f0, pitch_shift=shift, pitch_voiced=voiced)
         return f0[:, ce2:], [p["Tf"] - ce2] * len(slots), parts
+
+    def _pitch_track_win(self, slots, ctx, return_parts):
+        """`_pitch_track` with `set_pitch_window` or `set_pitch_memory` on: RMVPE on the context's tail, one `svc_rt_pitch_win`."""
+        from . import rmvpe as _rmvpe
+        p, ce2, n = self._pitch, 2 * self._audio["ce"], len(slots)
+        Tf = p["Tf"]
+        W, guard = p["win"] if p["win"] is not None else (Tf, 0)
+        s0 = _PITCH_HOP * (Tf - W)
+        # the slice starts on a frame centre, so its frame j is centred on context frame Tf - W + j and it has exactly W frames
+        assert int(p["rmvpe"].frames(ctx.size(1) - s0)) == W, (ctx.size(1), s0, W)
+        win = p["rmvpe"].f0_batch(ctx[:, s0:].contiguous(), thred=p["thred"])
+        if win.dim() != 2 or tuple(win.shape) != (n, W):
+            raise ValueError(f"RealtimeEngine.step_audio: rmvpe.f0_batch gave {tuple(win.shape)}, ({n}, {W}) expected")
+        res = _rmvpe.rt_pitch_win(win, guard, p["n_new"], p["lag"], slots, p["cache"], p["ring"], p["state"], p["ref_median"],
+                                  [1 if p["auto"].get(s, False) else 0 for s in slots], [p["semis"].get(s, 0.0) for s in slots],
+                                  warmup=p["warmup"], max_step=p["max_step"], return_shift=return_parts, return_raw=return_parts)
+        f0, shift, raw = res if return_parts else (res, None, None)
+        parts = None
+        if return_parts:
+            voiced = torch.stack([p["state"][s, _rmvpe.PITCH_BINS] for s in slots])
+            parts = dict(f0_raw=raw, f0=f0, pitch_shift=shift, pitch_voiced=voiced, f0_window=win)
+        return f0[:, ce2:], [Tf - ce2] * n, parts
 
     # ------------------------------------------------------------------------------------------- audio in (DESIGN.md 8l)
     def attach_audio(self, content, resample, Lin, L16, ce_dit_difference):
@@ -1653,7 +1760,9 @@ class RealtimeEngine:
         carries ctx (n, L16) and content (n, T, D).  Lengths and slots are host integers: nothing synchronises.  Where a listed
         slot has a gate (`set_gate`) the push is `svc_rt_push_gated` and the dict also carries gate_mask (n, Lin / zc) int32.
         After `attach_pitch` the regulator also gets the streams' shifted pitch tracks (`rmvpe.f0_batch(ctx)`, one `svc_rt_pitch`;
-        DESIGN.md 8q) and the dict carries f0_raw and f0 (n, Tf), pitch_shift (n,) and pitch_voiced (n,) int32."""
+        DESIGN.md 8q) and the dict carries f0_raw and f0 (n, Tf), pitch_shift (n,) and pitch_voiced (n,) int32.  With
+        `set_pitch_window` or `set_pitch_memory` on, RMVPE runs on the context's tail and the step is one `svc_rt_pitch_win`
+        (DESIGN.md 8r): f0_raw is the slots' cached track and the dict also carries f0_window (n, window_frames)."""
         return self._step_audio(slots, audio, n_timesteps, inference_cfg_rate, z, vocoder_kwargs, return_parts, None)
 
     @torch.inference_mode()

@@ -198,3 +198,75 @@ def rt_pitch(f0, n_new, lag, slots, state, ref_median, auto_adjust, semitones=No
                                            None if semis is None else (C.c_float * N)(*semis), int(warmup), float(max_step),
                                            _lib.ptr(out), out.stride(0), _lib.ptr(shift), _lib.stream_ptr()))
     return (out, shift) if return_shift else out
+
+
+PITCH_WIN_MAX_TF = 4096                                # SVC_RT_PITCH_WIN_MAX_TF
+
+
+def rt_pitch_cache(max_slots, Tf, device="cuda:0"):
+    """The per-slot raw pitch track of `rt_pitch_win`: (max_slots, Tf) float32 zeros, Hz; a fresh stream per row (0 Hz is unvoiced).
+    Tf is at most PITCH_WIN_MAX_TF."""
+    n = int(_lib.lib().svc_rt_pitch_cache_words(int(max_slots), int(Tf)))
+    if n <= 0:
+        raise ValueError(f"rt_pitch_cache: max_slots = {max_slots!r}, Tf = {Tf!r} (1 .. {PITCH_WIN_MAX_TF})")
+    return torch.zeros(int(max_slots), int(Tf), device=device, dtype=torch.float32)
+
+
+def rt_pitch_ring(max_slots, memory, device="cuda:0"):
+    """The per-slot ring of `rt_pitch_win`'s last `memory` counted frames: (max_slots, memory + 2) int32 zeros (words 0 .. memory - 1
+    the entries, a bin or -1 for an unvoiced frame; then head and fill), a fresh stream per row.  memory = 0 -> None: the
+    statistics never forget."""
+    if int(memory) == 0:
+        return None
+    n = int(_lib.lib().svc_rt_pitch_ring_words(int(max_slots), int(memory)))
+    if n <= 0:
+        raise ValueError(f"rt_pitch_ring: max_slots = {max_slots!r}, memory = {memory!r}")
+    return torch.zeros(int(max_slots), n // int(max_slots), device=device, dtype=torch.int32)
+
+
+@torch.inference_mode()
+def rt_pitch_win(f0_win, guard, n_new, lag, slots, cache, ring, state, ref_median, auto_adjust, semitones=None, warmup=50, max_step=0.0,
+                 return_shift=False, return_raw=False):
+    """`rt_pitch` on the context's tail (`svc_rt_pitch_win`): f0_win (N, W) device float32, row k the RMVPE track of
+    the LAST samples of the context of stream slots[k], its frame j being context frame Tf - W + j.  The slot's row of `cache`
+    (`rt_pitch_cache`, (max_slots, Tf) raw Hz) moves n_new frames to the left and takes the window's frames from `guard` on; the
+    counted frames, the statistics, the glide and the shifted track (N, Tf) are `rt_pitch`'s over that row.  ring
+    (`rt_pitch_ring`, or None = never forget): the bins of the slot's last `memory` counted frames; what is pushed out of it leaves
+    the histogram, so the median is over the last `memory` frames.  Needs W - guard >= n_new, W <= Tf <= PITCH_WIN_MAX_TF and
+    memory >= n_new.  -> the shifted track; with return_shift / return_raw also the applied shifts (N,) / the new cache rows
+    (N, Tf), in this order.  Nothing is synchronised."""
+    dev = f0_win.device
+    with torch.cuda.device(dev):
+        f = f0_win if f0_win.dtype == torch.float32 and f0_win.stride(-1) == 1 and f0_win.dim() == 2 else _lib.f32c(f0_win)
+        if f.dim() != 2:
+            raise ValueError(f"rt_pitch_win: f0_win {tuple(f0_win.shape)} is not (N, W)")
+        N, W = f.shape
+        slots, aut = _lib.int_list(slots), [int(bool(v)) for v in _lib.int_list(auto_adjust)]
+        if torch.is_tensor(semitones):
+            semitones = semitones.tolist()
+        semis = None if semitones is None else \
+            [float(x) for x in semitones] if isinstance(semitones, (list, tuple)) else [float(semitones)] * N
+        if len(slots) != N or len(aut) != N or (semis is not None and len(semis) != N):
+            raise ValueError(f"rt_pitch_win: slots, auto_adjust and semitones must all have {N} entries")
+        if state.dtype != torch.int32 or state.dim() != 2 or state.size(1) != PITCH_STATE_WORDS or not state.is_contiguous():
+            raise ValueError(f"rt_pitch_win: state must be contiguous int32 (max_slots, {PITCH_STATE_WORDS})")
+        ms = state.size(0)
+        if ref_median.dtype != torch.float32 or ref_median.numel() != ms or not ref_median.is_contiguous():
+            raise ValueError("rt_pitch_win: ref_median must be contiguous float32 (max_slots,)")
+        if cache.dtype != torch.float32 or cache.dim() != 2 or cache.size(0) != ms or not cache.is_contiguous():
+            raise ValueError("rt_pitch_win: cache must be contiguous float32 (max_slots, Tf)")
+        Tf = cache.size(1)
+        if ring is not None and (ring.dtype != torch.int32 or ring.dim() != 2 or ring.size(0) != ms or ring.size(1) < 3 or
+                                 not ring.is_contiguous()):
+            raise ValueError("rt_pitch_win: ring must be contiguous int32 (max_slots, memory + 2) or None")
+        memory = 0 if ring is None else ring.size(1) - 2
+        out = torch.empty(N, Tf, device=dev)
+        shift = torch.empty(N, device=dev) if return_shift else None
+        raw = torch.empty(N, Tf, device=dev) if return_raw else None
+        _lib.check(_lib.lib().svc_rt_pitch_win(_lib.ptr(f), f.stride(0), W, int(guard), Tf, int(n_new), int(lag), N, _lib.i32_host(slots),
+                                               ms, _lib.ptr(cache), _lib.ptr(ring), memory, _lib.ptr(state), _lib.ptr(ref_median),
+                                               _lib.i32_host(aut), None if semis is None else (C.c_float * N)(*semis), int(warmup),
+                                               float(max_step), _lib.ptr(out), out.stride(0), _lib.ptr(raw), Tf, _lib.ptr(shift),
+                                               _lib.stream_ptr()))
+    res = (out,) + ((shift,) if return_shift else ()) + ((raw,) if return_raw else ())
+    return res if len(res) > 1 else out
