@@ -726,7 +726,7 @@ int svc_astral_n_windows(const svc_astral_config_t* cfg, int overlap_rows, long 
 int svc_astral_rows(const svc_astral_config_t* cfg, int overlap_rows, long n_samples);
 int svc_astral_set_window_group(svc_astral_t* m, int windows);
 /* Measurement aid (tools/astral_bench.py): ms4 = {SSL front, ConvNeXt stages, BSQ heads, assemble} of the last group of the last
- * svc_astral_tokens call, in ms. */
+ * svc_astral_tokens / svc_astral_tokens_heads call, in ms. */
 int svc_astral_set_timing(svc_astral_t* m, int on);
 int svc_astral_last_timing(svc_astral_t* m, float* ms4);
 /* Seam: wave [B][L], 1 <= lens[b] <= min(L, window_samples), one window per clip -> out [B][T][ssl.d_model]: the residual stream
@@ -747,6 +747,17 @@ int svc_tokens_reduce(const int32_t* tokens, const int32_t* rows, int B, int R, 
  * order, -1 above.  reduce_head >= 0: also reduced [B][Rmax] and counts [B] (device), svc_tokens_reduce of that head's tokens. */
 int svc_astral_tokens(svc_astral_t* m, const float* wave, const int32_t* lens, int B, int L, int overlap_rows, int32_t* tokens, int Rmax,
                       int reduce_head, int32_t* reduced, int32_t* counts, void* stream);
+/* svc_astral_tokens for a subset of the heads: bit k of head_mask means "head k runs"; the mask is non-zero and inside
+ * (1 << n_heads) - 1.  tokens [popcount(head_mask)][B][Rmax]: the selected heads' planes in ascending head order.  reduce_head
+ * stays a head index: -1 or a selected head.  svc_astral_tokens is this call with every bit set (one code path).  Contract:
+ *   - a selected head's plane is bit for bit the plane svc_astral_tokens writes for that head;
+ *   - an unselected head launches nothing (no ConvNeXt group, no BSQ, no assemble plane), and memory past the popcount planes
+ *     is neither read nor written (the overlap check of `reduced` uses the compacted size);
+ *   - every refusal -- those of svc_astral_tokens, a mask that is zero or out of range, a reduce_head that is not selected, null
+ *     pointers -- happens before any launch and is reported through svc_last_error().
+ * svc_astral_last_timing keeps its four stages; stages 2 and 3 cover the selected heads. */
+int svc_astral_tokens_heads(svc_astral_t* m, const float* wave, const int32_t* lens, int B, int L, int overlap_rows, unsigned head_mask,
+                            int32_t* tokens, int Rmax, int reduce_head, int32_t* reduced, int32_t* counts, void* stream);
 
 /* Device-side counterpart of `crossfade(chunk1, chunk2, overlap)` (inference.py:343-350): the first n samples of
  * chunk2 become chunk2 * fade_in + chunk1_tail * fade_out in float64, stored as float32 (bit-identical to the numpy

@@ -43,7 +43,7 @@ EXPORTS = [
     "svc_w2v_content",
     "svc_astral_create", "svc_astral_destroy", "svc_astral_n_windows", "svc_astral_rows", "svc_astral_set_window_group",
     "svc_astral_set_timing", "svc_astral_last_timing", "svc_astral_ssl", "svc_astral_convnext", "svc_astral_logits", "svc_astral_tokens",
-    "svc_op_bsq_index", "svc_tokens_reduce",
+    "svc_astral_tokens_heads", "svc_op_bsq_index", "svc_tokens_reduce",
     "svc_prof_enable", "svc_prof_collect",
     "svc_op_linear", "svc_op_conv1d", "svc_op_conv1d_ex", "svc_op_conv1d_last_took", "svc_op_dit_panel", "svc_op_conv_transpose1d", "svc_op_attention", "svc_op_attention_ex", "svc_op_rmsnorm",
     "svc_op_layernorm", "svc_op_layernorm_gelu", "svc_op_act_cl", "svc_op_hift_signal", "svc_op_ar_sampler",
@@ -372,6 +372,8 @@ def lib():
         l.svc_tokens_reduce.argtypes = [C.c_void_p, i32p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         l.svc_astral_tokens.argtypes = [C.c_void_p, C.c_void_p, i32p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                         C.c_void_p, C.c_void_p]
+        l.svc_astral_tokens_heads.argtypes = [C.c_void_p, C.c_void_p, i32p, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_void_p, C.c_int, C.c_int,
+                                              C.c_void_p, C.c_void_p, C.c_void_p]
         l.svc_op_layernorm_gelu.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p]
         l.svc_op_layernorm.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p]
         _lib = l

@@ -71,7 +71,7 @@ class AstralTokenizer(ContentEncoder):
         raise NotImplementedError("AstralTokenizer yields tokens, not features: use tokens_batch")
 
     def semantic_fn(self, waves_16k):
-        raise NotImplementedError("AstralTokenizer yields tokens, not features: use tokenize")
+        raise NotImplementedError("AstralTokenizer yields tokens, not features: use tokenize (real-time sessions: tokens_fn)")
 
     def rows(self, n_samples, overlap_rows=250):
         """tokens of a clip of n_samples (the window plan's kept rows)"""
@@ -79,26 +79,70 @@ class AstralTokenizer(ContentEncoder):
         _lib.check(int(r < 0))
         return r
 
+    def codebook_size(self, head=0):
+        """ids of head `head` lie in [0, 2 ** bits)"""
+        return 2 ** int(self.cfg["heads"][self._head(head, "codebook_size")]["bits"])
+
+    def _head(self, head, what):
+        k = int(head)
+        if not 0 <= k < self.n_heads:
+            raise ValueError(f"AstralTokenizer.{what}: head {head!r} outside [0, {self.n_heads})")
+        return k
+
     @torch.inference_mode()
-    def tokens_batch(self, waves, lens=None, overlap_s=5.0, reduce_head=None):
+    def tokens_batch(self, waves, lens=None, overlap_s=5.0, reduce_head=None, heads=None):
         """waves (B, L) at 16 kHz (B <= 64), lens B host integers or None -> (tokens (n_heads, B, Rmax) int32 on the device, rows [B]):
         tokens[k, b, :rows[b]] are head k's indices of waves[b, :lens[b]] as the drivers' window loop gives them, -1 above.  With
-        reduce_head = k also (reduced (B, Rmax) int32, counts (B,) int32 on the device) of that head.  Nothing is synchronised."""
+        reduce_head = k also (reduced (B, Rmax) int32, counts (B,) int32 on the device) of that head.  heads: None (the call it
+        always was), or a tuple of distinct head indices: only those heads run (`svc_astral_tokens_heads`), tokens has len(heads)
+        planes in ascending head order, and reduce_head must be one of them.  Nothing is synchronised."""
         ov = int(round(float(overlap_s) * self.SR)) // SAMPLES_PER_ROW
+        mask = None
+        if heads is not None:
+            hs = [self._head(k, "tokens_batch") for k in heads]
+            if not hs or len(set(hs)) != len(hs):
+                raise ValueError(f"AstralTokenizer.tokens_batch: heads {tuple(heads)!r} must be distinct head indices, at least one")
+            if reduce_head is not None and int(reduce_head) not in hs:
+                raise ValueError(f"AstralTokenizer.tokens_batch: reduce_head {reduce_head!r} is not in heads {tuple(hs)}")
+            mask = sum(1 << k for k in hs)
         with torch.cuda.device(self.device):
             w = _lib.f32c(waves, self.device)
             B, L = w.shape
             lens = [L] * B if lens is None else self._lens(lens, B)
             rows = [self.rows(n, ov) for n in lens]
             R = max(rows)
-            out = torch.empty(self.n_heads, B, R, dtype=torch.int32, device=self.device)
+            out = torch.empty(self.n_heads if mask is None else len(hs), B, R, dtype=torch.int32, device=self.device)
             red = cnt = None
             if reduce_head is not None:
                 red = torch.empty(B, R, dtype=torch.int32, device=self.device)
                 cnt = torch.empty(B, dtype=torch.int32, device=self.device)
-            _lib.check(self._fn("tokens")(self._h, _lib.ptr(w), _lib.i32_host(lens), B, L, ov, _lib.ptr(out), R,
-                                          -1 if reduce_head is None else int(reduce_head), _lib.ptr(red), _lib.ptr(cnt), _lib.stream_ptr()))
+            rh = -1 if reduce_head is None else int(reduce_head)
+            if mask is None:
+                _lib.check(self._fn("tokens")(self._h, _lib.ptr(w), _lib.i32_host(lens), B, L, ov, _lib.ptr(out), R, rh, _lib.ptr(red),
+                                              _lib.ptr(cnt), _lib.stream_ptr()))
+            else:
+                _lib.check(self._fn("tokens_heads")(self._h, _lib.ptr(w), _lib.i32_host(lens), B, L, ov, mask, _lib.ptr(out), R, rh,
+                                                    _lib.ptr(red), _lib.ptr(cnt), _lib.stream_ptr()))
         return (out, rows) if reduce_head is None else (out, rows, red, cnt)
+
+    @torch.inference_mode()
+    def tokens_fn(self, waves_16k, head=0):
+        """The per-block call of a real-time session (`RealtimeEngine.attach_audio`): (n, L <= window_samples)
+        full-length rows -> (n, rows(L)) int32 on the device, head `head` alone from one `svc_astral_tokens_heads` call (the other
+        head launches nothing).  Nothing is synchronised."""
+        k = self._head(head, "tokens_fn")
+        if waves_16k.dim() != 2 or not 1 <= waves_16k.size(0) <= 64 or waves_16k.size(1) > self.W:
+            raise ValueError(f"AstralTokenizer.tokens_fn: (n <= 64, L <= {self.W}) samples, got {tuple(waves_16k.shape)}")
+        with torch.cuda.device(self.device):
+            w = _lib.f32c(waves_16k, self.device)
+            n, L = w.shape
+            R = window_rows(self.cfg, L)
+            if R < 1:
+                raise ValueError(f"AstralTokenizer.tokens_fn: {L} samples are shorter than the extractor's receptive field")
+            out = torch.empty(n, R, dtype=torch.int32, device=self.device)
+            _lib.check(self._fn("tokens_heads")(self._h, _lib.ptr(w), None, n, L, 0, 1 << k, _lib.ptr(out), R, -1, None, None,
+                                                _lib.stream_ptr()))
+        return out
 
     def tokenize(self, waves_16k, lens=None, head=0):
         """The reference's call for one head: (B, L <= 480 000) samples, lens -> (None, indices (B, T) int64, feature_lens (B,) int64);

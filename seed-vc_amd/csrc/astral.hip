@@ -23,6 +23,7 @@ namespace {
 constexpr int AS_MAX_HEADS = SVC_ASTRAL_MAX_HEADS, AS_DW_K = 7, AS_TILE = 64, AS_MAX_BITS = 16;
 
 struct RowTab { int v[MAX_WIN]; };
+struct HeadMap { int v[AS_MAX_HEADS]; };                     // output plane -> head (svc_astral_tokens_heads)
 
 __global__ void as_rows_kernel(RowTab t, int* __restrict__ dst) {
     if (threadIdx.x < MAX_WIN) dst[threadIdx.x] = t.v[threadIdx.x];
@@ -153,11 +154,13 @@ __global__ void as_index_kernel(const float* __restrict__ z, int* __restrict__ i
     index[r] = idx;
 }
 
-// idx [heads][G * P] -> tokens [heads][B][Rmax]: thread (r, g, head).  r < P: row r of window g, when kept, goes to its place in
-// the clip's tokens; r >= P: token r - P of the clip becomes -1 when window g is the clip's last and r - P is at or above the count
-__global__ void as_assemble_kernel(const int* __restrict__ idx, WinTab wt, int* __restrict__ tokens, int P, int G, int B, int Rmax, long idx_stride) {
-    const int g = blockIdx.y, head = blockIdx.z, r = blockIdx.x * blockDim.x + threadIdx.x;
-    int* out = tokens + ((long)head * B + wt.clip[g]) * Rmax;
+// idx [heads][G * P] -> tokens [planes][B][Rmax]: thread (r, g, plane), plane p holding head hm.v[p].  r < P: row r of window g,
+// when kept, goes to its place in the clip's tokens; r >= P: token r - P of the clip becomes -1 when window g is the clip's last
+// and r - P is at or above the count
+__global__ void as_assemble_kernel(const int* __restrict__ idx, WinTab wt, int* __restrict__ tokens, int P, int G, int B, int Rmax, long idx_stride,
+                                   HeadMap hm) {
+    const int g = blockIdx.y, plane = blockIdx.z, head = hm.v[plane], r = blockIdx.x * blockDim.x + threadIdx.x;
+    int* out = tokens + ((long)plane * B + wt.clip[g]) * Rmax;
     if (r < P) {
         if (r >= wt.drop[g] && r < wt.keep[g]) out[wt.dst0[g] + r - wt.drop[g]] = idx[(long)head * idx_stride + (long)g * P + r];
     } else if (r < P + Rmax) {
@@ -595,34 +598,54 @@ int svc_tokens_reduce(const int32_t* tokens, const int32_t* rows, int B, int R, 
     return as_reduce_launch(tokens, rows, B, R, out, counts, (hipStream_t)stream);
 }
 
-int svc_astral_tokens(svc_astral_t* m, const float* wave, const int32_t* lens, int B, int L, int overlap_rows, int32_t* tokens, int Rmax,
-                      int reduce_head, int32_t* reduced, int32_t* counts, void* stream) {
-    SVC_REQUIRE(B >= 1 && B <= WV_MAX_B, "svc_astral_tokens: B must be 1 .. 64 clips");
-    SVC_REQUIRE(L >= 1, "svc_astral_tokens: L must be at least 1 sample");
+}  // extern "C"
+
+namespace {
+
+// The one code path of svc_astral_tokens and svc_astral_tokens_heads; full: every head, whatever their number (the mask is not read)
+int as_tokens(const char* who, svc_astral_t* m, const float* wave, const int32_t* lens, int B, int L, int overlap_rows, bool full,
+              unsigned head_mask, int32_t* tokens, int Rmax, int reduce_head, int32_t* reduced, int32_t* counts, void* stream) {
+    const std::string w(who);
+#define AS_REQ(cond, msg) do { if (!(cond)) { set_error(w + msg); return 1; } } while (0)
+    AS_REQ(B >= 1 && B <= WV_MAX_B, ": B must be 1 .. 64 clips");
+    AS_REQ(L >= 1, ": L must be at least 1 sample");
     if (lens)
-        for (int b = 0; b < B; ++b) SVC_REQUIRE(lens[b] >= 1 && lens[b] <= L, "svc_astral_tokens: lens outside [1, L]");
-    SVC_REQUIRE(overlap_rows >= 0, "svc_astral_tokens: overlap_rows outside [0, window_samples / 320)");
-    SVC_REQUIRE(Rmax >= 1, "svc_astral_tokens: Rmax is smaller than the longest clip's rows (svc_astral_rows)");
-    SVC_REQUIRE(wave && tokens, "svc_astral_tokens: null wave or tokens");
-    SVC_REQUIRE(reduce_head < 0 || (reduced && counts), "svc_astral_tokens: reduce_head needs reduced and counts");
-    SVC_REQUIRE(m, "svc_astral_tokens: null handle");
-    SVC_REQUIRE(reduce_head < m->cfg.n_heads, "svc_astral_tokens: reduce_head outside [-1, n_heads)");
-    SVC_REQUIRE(reduce_head < 0 || reduced + (long)B * Rmax <= tokens || tokens + (long)m->cfg.n_heads * B * Rmax <= reduced,
-                "svc_astral_tokens: reduced must not overlap tokens");
+        for (int b = 0; b < B; ++b) AS_REQ(lens[b] >= 1 && lens[b] <= L, ": lens outside [1, L]");
+    AS_REQ(overlap_rows >= 0, ": overlap_rows outside [0, window_samples / 320)");
+    AS_REQ(Rmax >= 1, ": Rmax is smaller than the longest clip's rows (svc_astral_rows)");
+    AS_REQ(wave && tokens, ": null wave or tokens");
+    AS_REQ(reduce_head < 0 || (reduced && counts), ": reduce_head needs reduced and counts");
+    AS_REQ(full || (head_mask != 0 && head_mask < (1u << AS_MAX_HEADS)), ": head_mask must be non-zero and inside (1 << n_heads) - 1");
+    AS_REQ(m, ": null handle");
+    const int nh = m->cfg.n_heads;
+    if (full) head_mask = (1u << nh) - 1u;
+    AS_REQ(head_mask < (1u << nh), ": head_mask must be non-zero and inside (1 << n_heads) - 1");
+    AS_REQ(reduce_head < nh, ": reduce_head outside [-1, n_heads)");
+    AS_REQ(reduce_head < 0 || (head_mask >> reduce_head & 1u), ": reduce_head is not a selected head");
+    HeadMap hm;
+    memset(&hm, 0, sizeof(hm));
+    int np = 0, reduce_plane = -1;                           // selected heads in ascending order: plane p holds head hm.v[p]
+    for (int k = 0; k < nh; ++k)
+        if (head_mask >> k & 1u) {
+            if (k == reduce_head) reduce_plane = np;
+            hm.v[np++] = k;
+        }
+    AS_REQ(reduce_head < 0 || reduced + (long)B * Rmax <= tokens || tokens + (long)np * B * Rmax <= reduced, ": reduced must not overlap tokens");
     const svc_w2v_config_t& c = m->ssl->cfg;
-    const int nc = c.n_conv, nh = m->cfg.n_heads;
+    const int nc = c.n_conv;
     const long W = c.window_samples;
-    SVC_REQUIRE((long)overlap_rows * SAMPLES_PER_ROW < W, "svc_astral_tokens: overlap_rows outside [0, window_samples / 320)");
+    AS_REQ((long)overlap_rows * SAMPLES_PER_ROW < W, ": overlap_rows outside [0, window_samples / 320)");
     std::vector<Win> wins;                                   // the window plan of the whole call, in clip order
     int clip_rows[WV_MAX_B];
     for (int b = 0; b < B; ++b) {
         const long n = lens ? lens[b] : L;
-        SVC_REQUIRE(as_rows_of(c, std::min(n, W)) >= 1, "svc_astral_tokens: lens shorter than the extractor's receptive field");
+        AS_REQ(as_rows_of(c, std::min(n, W)) >= 1, ": lens shorter than the extractor's receptive field");
         clip_rows[b] = plan_clip(wins, b, n, W, overlap_rows, [&c](long ns) { return as_rows_of(c, ns); });
-        SVC_REQUIRE(clip_rows[b] <= Rmax, "svc_astral_tokens: Rmax is smaller than the longest clip's rows (svc_astral_rows)");
+        AS_REQ(clip_rows[b] <= Rmax, ": Rmax is smaller than the longest clip's rows (svc_astral_rows)");
     }
+#undef AS_REQ
     long nmax = 0;
-    for (const Win& w : wins) nmax = std::max<long>(nmax, w.n);
+    for (const Win& wn : wins) nmax = std::max<long>(nmax, wn.n);
     hipStream_t st = (hipStream_t)stream;
     const int G = (int)std::min((size_t)m->group, wins.size());
     if (m->ssl->reserve_fe(G, nmax, st)) return 1;
@@ -633,19 +656,34 @@ int svc_astral_tokens(svc_astral_t* m, const float* wave, const int32_t* lens, i
         const WinTab wt = win_table(wins, w0, nb);
         if (m->tm.mark(0, st)) return 1;
         if (as_ssl_group(m, wave, L, wt, nb, P, st) || m->tm.mark(1, st)) return 1;
-        for (int k = 0; k < nh; ++k)                         // every head on the group's SSL rows before the workspace is reused
-            if (m->convnext_group(k, m->ssl->stack.x, nb, P, st)) return 1;
+        for (int p = 0; p < np; ++p)                         // every selected head on the group's SSL rows before the workspace is reused
+            if (m->convnext_group(hm.v[p], m->ssl->stack.x, nb, P, st)) return 1;
         if (m->tm.mark(2, st)) return 1;
-        for (int k = 0; k < nh; ++k)
-            if (m->bsq_group(k, m->heads[k].x, nb, P, m->idx + (long)k * m->cap_g * m->cap_p, nullptr, st)) return 1;
+        for (int p = 0; p < np; ++p)
+            if (m->bsq_group(hm.v[p], m->heads[hm.v[p]].x, nb, P, m->idx + (long)hm.v[p] * m->cap_g * m->cap_p, nullptr, st)) return 1;
         if (m->tm.mark(3, st)) return 1;
-        hipLaunchKernelGGL(as_assemble_kernel, dim3(cdiv(P + Rmax, 256), nb, nh), dim3(256), 0, st, (const int*)m->idx, wt, tokens, P, nb, B, Rmax,
-                           (long)m->cap_g * m->cap_p);
+        hipLaunchKernelGGL(as_assemble_kernel, dim3(cdiv(P + Rmax, 256), nb, np), dim3(256), 0, st, (const int*)m->idx, wt, tokens, P, nb, B, Rmax,
+                           (long)m->cap_g * m->cap_p, hm);
         SVC_CHECK_HIP(hipGetLastError());
         if (m->tm.mark(4, st)) return 1;
     }
-    if (reduce_head >= 0) return as_reduce_launch(tokens + (long)reduce_head * B * Rmax, clip_rows, B, Rmax, reduced, counts, st);
+    if (reduce_plane >= 0) return as_reduce_launch(tokens + (long)reduce_plane * B * Rmax, clip_rows, B, Rmax, reduced, counts, st);
     return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int svc_astral_tokens(svc_astral_t* m, const float* wave, const int32_t* lens, int B, int L, int overlap_rows, int32_t* tokens, int Rmax,
+                      int reduce_head, int32_t* reduced, int32_t* counts, void* stream) {
+    return as_tokens("svc_astral_tokens", m, wave, lens, B, L, overlap_rows, true, 0u, tokens, Rmax, reduce_head, reduced, counts, stream);
+}
+
+int svc_astral_tokens_heads(svc_astral_t* m, const float* wave, const int32_t* lens, int B, int L, int overlap_rows, unsigned head_mask,
+                            int32_t* tokens, int Rmax, int reduce_head, int32_t* reduced, int32_t* counts, void* stream) {
+    return as_tokens("svc_astral_tokens_heads", m, wave, lens, B, L, overlap_rows, false, head_mask, tokens, Rmax, reduce_head, reduced, counts,
+                     stream);
 }
 
 }  // extern "C"

@@ -1088,7 +1088,9 @@ def realtime_input_geometry(sr, block_time, crossfade_time, extra_time_ce, extra
     extra_right samples and `input_wav_res` z16 * len(input_wav) // zc.
     -> dict(zc, z16, Lin (= block: the samples a block step takes), L16 (the content-rate context), hist (= 2 zc: the
     stream-rate samples kept between blocks), rows (L16 // z16 - 1: what a stride-z16 convolutional extractor with a
-    z16 + z16 // 4 receptive field, wav2vec 2.0, yields for the context; Whisper yields L16 // z16 + 1)).
+    z16 + z16 // 4 receptive field, wav2vec 2.0, yields for the context, and with it the ASTRAL tokenizer's token count for
+    the context, `AstralTokenizer.tokens_fn`: min(frames, L16 // z16) over the same HuBERT extractor; Whisper yields
+    L16 // z16 + 1)).
     ValueError where sr or content_rate is not a multiple of 50: a block must start at resampling phase 0."""
     sr, content_rate = int(sr), int(content_rate)
     if sr < 50 or content_rate < 50 or sr % 50 or content_rate % 50:
@@ -1158,8 +1160,25 @@ class RealtimeEngine:
     with prompt_lens, `svc_mel_strip_prompt`, one plain vocoder call (every row has S frames), `svc_sola_step` -- from host
     integers only: nothing synchronises, and the data-dependent offset never leaves the device.
 
-    length_regulator: seedvc_amd.length_regulator.InterpolateRegulator (v1); cfm: seedvc_amd.cfm.CFM; vocoder: HiFT | BigVGAN
-    with S * hop samples per row; fade_in / fade_out: (Lb,) float32 windows (default: `gui_fade_windows`)."""
+    length_regulator: seedvc_amd.length_regulator.InterpolateRegulator, v1 or the v2 model's discrete `v2_cfm`; cfm:
+    seedvc_amd.cfm.CFM; vocoder: HiFT | BigVGAN with S * hop samples per row; fade_in / fade_out: (Lb,) float32 windows (default:
+    `gui_fade_windows`).
+
+    Token mode is the state of an engine whose regulator has `cfg["is_discrete"]`: the timbre branch of the v2
+    wrapper (`convert_style=False`: wide content tokens -> `cfm_length_regulator` -> `cfm.inference` -> vocoder, no AR) block
+    by block.  Per stream, given the wide tokens t (1, Tin) of the context, the first line above becomes
+
+        cond  = length_regulator(t, ylens=[S])[0]
+
+    and everything after it is the same step.  Such an engine steps with `step_tokens` (or `step_audio` after `attach_audio`
+    with a tokenizer); `step` and `step_f0` are refused, as `step_tokens` is on a feature engine.  The wiring, with
+    t = V2HotPath.prepare_target(...) of the reference:
+
+        eng  = RealtimeEngine(hot.cfm_lr, hot.cfm, hot.vocoder, **geometry)
+        slot = eng.open(t["prompt_condition"], t["mel"], t["style"])
+        eng.attach_audio(astral, Resample(stream_rate, 16000), Lin, L16, ce_dit_difference)      # head 0: the wide tokens
+
+    The v2 style branch (AR) has no real-time form: it changes durations and samples freely, so it has no block-aligned step."""
 
     def __init__(self, length_regulator, cfm, vocoder, S, hop, block, sola_buffer, sola_search, tail=0, max_streams=64,
                  fade_in=None, fade_out=None):
@@ -1176,6 +1195,7 @@ class RealtimeEngine:
         self.S, self.hop, self.block, self.Lb, self.Ls, self.tail = S, hop, block, Lb, Ls, tail
         self.n_inf, self.start, self.max_streams = n_inf, S * hop - tail - n_inf, int(max_streams)
         self.device = cfm.device
+        self.token_mode = bool((getattr(length_regulator, "cfg", None) or {}).get("is_discrete"))       # not an option: the regulator's kind
         if fade_in is None:
             fade_in, fade_out = gui_fade_windows(Lb)
         self.fade_in, self.fade_out = (_lib.f32c(torch.as_tensor(f), self.device).reshape(-1) for f in (fade_in, fade_out))
@@ -1189,7 +1209,7 @@ class RealtimeEngine:
         self._speech = {}                   # slot -> the caller's VAD flag (`set_speech`)
         self._gate = {}                     # slot -> gate threshold as an energy of 4 zc samples (`set_gate`); absent: off
         self._vad = None                    # `attach_vad`: the device-resident VAD of `step_audio`
-        self._sampler = {}                  # slot -> (n_timesteps, inference_cfg_rate, temperature), None = the step call's (`set_sampler`)
+        self._sampler = {}                  # slot -> (n_timesteps, inference_cfg_rate, temperature, random_voice), None = the step call's (`set_sampler`)
         self._pitch = None                  # `attach_pitch`: the device-resident pitch track of `step_audio` (f0-conditioned models)
 
     def open(self, prompt_condition, mel2, style2):
@@ -1296,23 +1316,34 @@ class RealtimeEngine:
             self._audio["gate_e"][slot].zero_()
         self._gate[slot] = p
 
-    def set_sampler(self, slot, n_timesteps=None, inference_cfg_rate=None, temperature=None):
+    def set_sampler(self, slot, n_timesteps=None, inference_cfg_rate=None, temperature=None, random_voice=None):
         """The GUI's `diffusion_steps` and `inference_cfg_rate` (and the sampler temperature) for one stream.  None: what the
-        step call says (temperature: 1.0), the default on `open`; kept across `reset`.  While no listed slot has an override a
-        step is the one `cfm.inference` call it always was; otherwise it is one `cfm.inference_rows` call, in which streams of
-        one class (same steps, guided or not) share every launch whatever their rates."""
+        step call says (temperature: 1.0, random_voice: False), the default on `open`; kept across `reset`.  While no listed slot
+        has an override a step is the one `cfm.inference` call it always was; otherwise it is one `cfm.inference_rows` call, in
+        which streams of one class (same steps, guided or not) share every launch whatever their rates.  With a
+        v2 sampler (`cfm.cfg["version"] == 2`) inference_cfg_rate may be the pair `CFM.inference` takes and random_voice the
+        v2 wrapper's anonymisation flag for the stream (classes follow `CFM.rows_plan`); a v1 sampler refuses both."""
         self._check_slot(slot, "set_sampler")
         if n_timesteps is not None and int(n_timesteps) < 1:
             raise ValueError(f"RealtimeEngine.set_sampler: n_timesteps = {n_timesteps!r}")
-        for name, v in (("inference_cfg_rate", inference_cfg_rate), ("temperature", temperature)):
-            if v is not None and not math.isfinite(float(v)):
+        rate = inference_cfg_rate
+        if isinstance(rate, (list, tuple)):
+            if len(rate) != 2:
+                raise ValueError(f"RealtimeEngine.set_sampler: a pair of rates has two entries, got {rate!r}")
+            rate = (float(rate[0]), float(rate[1]))
+        elif rate is not None:
+            rate = float(rate)
+        for name, v in (("inference_cfg_rate", rate), ("temperature", temperature)):
+            if v is not None and not all(math.isfinite(float(x)) for x in (v if isinstance(v, tuple) else (v,))):
                 raise ValueError(f"RealtimeEngine.set_sampler: {name} = {v!r}")
-        if n_timesteps is None and inference_cfg_rate is None and temperature is None:
+        if (isinstance(rate, tuple) or random_voice is not None) and (getattr(self.cfm, "cfg", None) or {}).get("version") != 2:
+            raise ValueError("RealtimeEngine.set_sampler: a pair of rates and random_voice need a v2 sampler (cfm.cfg['version'] == 2)")
+        if n_timesteps is None and rate is None and temperature is None and random_voice is None:
             self._sampler.pop(slot, None)
         else:
-            self._sampler[slot] = (None if n_timesteps is None else int(n_timesteps),
-                                   None if inference_cfg_rate is None else float(inference_cfg_rate),
-                                   None if temperature is None else float(temperature))
+            self._sampler[slot] = (None if n_timesteps is None else int(n_timesteps), rate,
+                                   None if temperature is None else float(temperature),
+                                   None if random_voice is None else bool(random_voice))
 
     def attach_vad(self, vad):
         """A device-resident VAD (seedvc_amd.vad.FsmnVad) for `step_audio`: needs `attach_audio` with a 16 kHz
@@ -1370,6 +1401,7 @@ class RealtimeEngine:
         (HiFT's pinned draws); `step_seeded` takes seeds instead of the tensors.  -> (n, block) float32 on the device; with
         return_parts also dict(mel (n, C, S), infer (n, n_inf), offsets (n,) int32).  After `attach_output` block and n_inf
         are those of the output rate; a slot whose `set_speech` flag is False gets a row of zeros before SOLA."""
+        self._check_mode("step", False)
         return self._step(slots, content, n_timesteps, inference_cfg_rate, z, vocoder_kwargs, return_parts, None)
 
     @torch.inference_mode()
@@ -1379,6 +1411,7 @@ class RealtimeEngine:
         host frame counts (None: all Tf), handed to the regulator as `length_regulator(content, ylens=[S] * n, n_quantizers=3,
         f0=f0, f0_lens=f0_lens)`; seeds as `step_seeded` (then z is None).  `step_audio` after `attach_pitch` is this step on
         the track `svc_rt_pitch` wrote.  (A method of its own: the parameter list of `step` is part of its contract.)"""
+        self._check_mode("step_f0", False)
         if f0 is None:
             raise ValueError("RealtimeEngine.step_f0: f0 is None")
         if f0.dim() != 2 or f0.size(0) != len(slots):
@@ -1389,9 +1422,29 @@ class RealtimeEngine:
                 raise ValueError(f"RealtimeEngine.step_f0: f0_lens {f0_lens} for {len(slots)} rows of {f0.size(1)} frames")
         return self._step(slots, content, n_timesteps, inference_cfg_rate, z, vocoder_kwargs, return_parts, seeds, None, f0, f0_lens)
 
+    @torch.inference_mode()
+    def step_tokens(self, slots, tokens, n_timesteps, inference_cfg_rate, z=None, vocoder_kwargs=None, return_parts=False, seeds=None):
+        """`step` of a token-mode engine (the v2 timbre branch): tokens (n, Tin) integer, row k the wide content
+        tokens of slots[k]'s context; the regulator call is `length_regulator(tokens, ylens=[S] * n)[0]` and everything after it
+        is `step` unchanged.  inference_cfg_rate: a float or the v2 sampler's pair, as `CFM.inference` takes it; seeds as
+        `step_seeded` (then z is None).  (A method of its own: the parameter list of `step` is part of its contract.)"""
+        self._check_mode("step_tokens", True)
+        if not torch.is_tensor(tokens) or tokens.dim() != 2 or tokens.size(0) != len(slots):
+            raise ValueError(f"RealtimeEngine.step_tokens: tokens {tuple(getattr(tokens, 'shape', ()))} is not (n = {len(slots)}, Tin)")
+        if tokens.is_floating_point() or tokens.is_complex() or tokens.dtype == torch.bool:
+            raise ValueError(f"RealtimeEngine.step_tokens: tokens are {tokens.dtype}, an integer tensor is expected")
+        return self._step(slots, tokens, n_timesteps, inference_cfg_rate, z, vocoder_kwargs, return_parts, seeds)
+
+    def _check_mode(self, what, tokens):
+        if tokens != self.token_mode:
+            raise ValueError(f"RealtimeEngine.{what}: the length regulator is discrete (token mode): use step_tokens" if self.token_mode
+                             else f"RealtimeEngine.{what}: the length regulator is not discrete (cfg['is_discrete']): use step")
+
     def _regulate(self, content, n, f0, f0_lens):
-        """The regulator call of a step.  Without a pitch track it is the call it always was."""
+        """The regulator call of a step.  Without a pitch track it is the call it always was; in token mode the v2 regulator's."""
         ylens = torch.LongTensor([self.S] * n)
+        if self.token_mode:
+            return self.length_regulator(content, ylens=ylens)[0]
         if f0 is None:
             return self.length_regulator(content, ylens=ylens, n_quantizers=3, f0=None)[0]
         return self.length_regulator(content, ylens=ylens, n_quantizers=3, f0=f0, f0_lens=f0_lens)[0]
@@ -1416,8 +1469,8 @@ class RealtimeEngine:
         if len(set(slots)) != len(slots):
             raise ValueError(f"RealtimeEngine.step: a slot appears twice in {slots}")
         n, dev, S = len(slots), self.device, self.S
-        if content.dim() != 3 or content.size(0) != n:
-            raise ValueError(f"RealtimeEngine.step: content {tuple(content.shape)} is not (n = {n}, Tin, Din)")
+        if content.dim() != (2 if self.token_mode else 3) or content.size(0) != n:
+            raise ValueError(f"RealtimeEngine.step: content {tuple(content.shape)} is not (n = {n}, Tin" + ("" if self.token_mode else ", Din") + ")")
         live = self._out
         if n == 0:
             out = torch.zeros(0, live["block"] if live else self.block, device=dev)
@@ -1437,8 +1490,8 @@ class RealtimeEngine:
                 mel = self.cfm.inference(mu, x_lens, st["mel"], st["style"], None, n_timesteps, inference_cfg_rate=inference_cfg_rate,
                                          z=z, prompt_lens=P, **_cfm_seeds(seeds))
             else:                                                                # per-slot sampler settings: still one call
-                call = (n_timesteps, inference_cfg_rate, 1.0)
-                settings = [tuple(c if o is None else o for o, c in zip(self._sampler.get(s, (None,) * 3), call)) for s in slots]
+                call = (n_timesteps, inference_cfg_rate, 1.0, False)
+                settings = [tuple(c if o is None else o for o, c in zip(self._sampler.get(s, (None,) * 4), call)) for s in slots]
                 mel = self.cfm.inference_rows(mu, x_lens, st["mel"], st["style"], settings, z=z, prompt_lens=P, **_cfm_seeds(seeds))
             vc = _strip_prompt(mel, P, x_lens, S)
             calls = _vocode(self.vocoder, vc, [S] * n, False, "RealtimeEngine.step", hop=self.hop, seeds=seeds,
@@ -1707,12 +1760,26 @@ class RealtimeEngine:
     # ------------------------------------------------------------------------------------------- audio in
     def attach_audio(self, content, resample, Lin, L16, ce_dit_difference):
         """The input side of a block step: after this call `step_audio` takes the microphone block itself.  content: anything
-        with `semantic_fn((n, L16) samples) -> (n, T, D)` (Wav2Vec2Content, WhisperContent); resample: an
+        with `semantic_fn((n, L16) samples) -> (n, T, D)` (Wav2Vec2Content, WhisperContent); on a token-mode engine anything
+        with `tokens_fn((n, L16) samples, head=) -> (n, R) integer` and `codebook_size(head)` (AstralTokenizer), read at head 0,
+        the wide tokens of the v2 timbre branch (`attach_tokens` names another head), whose codebook must fit the regulator's;
+        resample: an
         `audio.Resample(stream_rate, content_rate)`, both rates multiples of 50; Lin: samples per block at the stream rate, a
         multiple of zc = stream_rate // 50; L16: the content-rate context per stream (`realtime_input_geometry`);
         ce_dit_difference: seconds of content dropped at the front (the GUI's `S_alt[:, int(ce_dit_difference * 50):]`).
         Allocates the per-slot history (max_streams, 2 zc) and the two-plane context ring of `svc_rt_push`, zeros; `open` and
         `reset` zero a slot's rows as they zero its SOLA buffer."""
+        self._attach_audio(content, resample, Lin, L16, ce_dit_difference, 0)
+
+    def attach_tokens(self, content, resample, Lin, L16, ce_dit_difference, head=0):
+        """`attach_audio` of a token-mode engine with the tokenizer's head named: `step_audio` reads
+        `content.tokens_fn(ctx, head=head)`.  (A method of its own: the parameter list of `attach_audio` is part of its
+        contract.)  Refused on a feature engine."""
+        if not self.token_mode:
+            raise ValueError("RealtimeEngine.attach_audio: attach_tokens needs a discrete length regulator (cfg['is_discrete'])")
+        self._attach_audio(content, resample, Lin, L16, ce_dit_difference, head)
+
+    def _attach_audio(self, content, resample, Lin, L16, ce_dit_difference, head):
         orig, new = int(resample.orig_freq), int(resample.new_freq)
         Lin, L16 = int(Lin), int(L16)
         if orig < 50 or new < 50 or orig % 50 or new % 50:
@@ -1726,11 +1793,22 @@ class RealtimeEngine:
         ce = int(float(ce_dit_difference) * 50)
         if ce < 0:
             raise ValueError("RealtimeEngine.attach_audio: ce_dit_difference is negative")
-        if not callable(getattr(content, "semantic_fn", None)):
+        head = int(head)
+        if self.token_mode:
+            if not callable(getattr(content, "tokens_fn", None)) or not callable(getattr(content, "codebook_size", None)):
+                raise ValueError("RealtimeEngine.attach_audio: the length regulator is discrete (token mode): content needs tokens_fn "
+                                 "and codebook_size (a tokenizer), a feature encoder does not fit")
+            K, Kr = int(content.codebook_size(head)), int(self.length_regulator.cfg["codebook_size"])
+            if K > Kr:
+                raise ValueError(f"RealtimeEngine.attach_audio: head {head} has {K} codes, the length regulator's codebook_size is {Kr}")
+        elif callable(getattr(content, "tokens_fn", None)):
+            raise ValueError("RealtimeEngine.attach_audio: content is a tokenizer (tokens_fn), the length regulator is not discrete "
+                             "(cfg['is_discrete'])")
+        elif not callable(getattr(content, "semantic_fn", None)):
             raise ValueError("RealtimeEngine.attach_audio: content has no semantic_fn")
         ms, planes = self.max_streams, 2 * self.max_streams * L16
         ring = torch.zeros(int(_lib.lib().svc_rt_ring_floats(ms, L16)), device=self.device, dtype=torch.float32)
-        self._audio = dict(content=content, resample=resample, Lin=Lin, L16=L16, zc=zc, z16=z16, ce=ce, ring=ring,
+        self._audio = dict(content=content, head=head, resample=resample, Lin=Lin, L16=L16, zc=zc, z16=z16, ce=ce, ring=ring,
                            planes=ring[:planes].view(2, ms, L16), tickets=ring[planes:].view(torch.int64),
                            tiles=int(_lib.lib().svc_rt_push_tiles(L16)),
                            hist=torch.zeros(ms, 2 * zc, device=self.device, dtype=torch.float32),
@@ -1757,7 +1835,10 @@ class RealtimeEngine:
         """One block from audio: audio (n, Lin) float32 at the stream rate, row k the new samples of slots[k].  One
         `svc_rt_push` (history, resampling, context shift and the dense batch), then
         `content.semantic_fn(ctx)[:, int(ce_dit_difference * 50):]`, then `step`.  -> as `step`; with return_parts the dict also
-        carries ctx (n, L16) and content (n, T, D).  Lengths and slots are host integers: nothing synchronises.  Where a listed
+        carries ctx (n, L16) and content (n, T, D).  In token mode the middle is
+        `content.tokens_fn(ctx, head=head)[:, int(ce_dit_difference * 50):]`, then `step_tokens`, inference_cfg_rate may be the
+        v2 pair, and the dict carries ctx and tokens (n, R - ce) instead of content.  Lengths and slots are host integers:
+        nothing synchronises.  Where a listed
         slot has a gate (`set_gate`) the push is `svc_rt_push_gated` and the dict also carries gate_mask (n, Lin / zc) int32.
         After `attach_pitch` the regulator also gets the streams' shifted pitch tracks (`rmvpe.f0_batch(ctx)`, one `svc_rt_pitch`;
         DESIGN.md 8q) and the dict carries f0_raw and f0 (n, Tf), pitch_shift (n,) and pitch_voiced (n,) int32.  With
@@ -1813,11 +1894,14 @@ class RealtimeEngine:
                 for s in on:
                     v["total"][s] += v["n_new"]
                 speech_dev = v["flags"]
-            content = a["content"].semantic_fn(ctx)[:, a["ce"]:]
+            if self.token_mode:
+                content = a["content"].tokens_fn(ctx, head=a["head"])[:, a["ce"]:]
+            else:
+                content = a["content"].semantic_fn(ctx)[:, a["ce"]:]
             f0, f0_lens, pitch_parts = self._pitch_track(slots, ctx, return_parts) if self._pitch is not None else (None, None, None)
         res = self._step(slots, content, n_timesteps, inference_cfg_rate, z, vocoder_kwargs, return_parts, seeds, speech_dev, f0, f0_lens)
         if return_parts:
-            res[1].update(ctx=ctx, content=content)
+            res[1].update(ctx=ctx, **({"tokens": content} if self.token_mode else {"content": content}))
             if pitch_parts is not None:
                 res[1].update(pitch_parts)
             if vad_parts is not None:
