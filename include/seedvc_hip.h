@@ -647,17 +647,37 @@ int svc_whisper_content(svc_whisper_t* m, const float* wave, const int32_t* lens
  * original1, or weight_g / weight_v, or a plain weight) is folded at pack time.  Lengths and row counts are HOST int32 arrays consumed
  * before the call returns; arguments are checked before the handle is touched; nothing synchronises once the workspace has its size.
  * Samples / rows at and above a clip's length are never read as values.  Every clip (window) gets what it would get alone: its bits
- * do not depend on what shares the call, on the order or on the group size. */
+ * do not depend on what shares the call, on the order or on the group size.
+ *
+ * The base family (facebook/wav2vec2-base, facebook/hubert-base-ls960 and their fine-tunes) enters through
+ * svc_w2v_create_ex with a non-NULL `ext`: feat_extract_norm = "group" (feat_extract_norm_layer = 0) together with
+ * do_stable_layer_norm = 0; the two flags must agree (the mixed forms exist in no released model and are refused by name), conv_bias
+ * may be 0 or 1 in either family, and the positional conv's groups may be 16, 32, 48 or 64 channels wide (d_model / pos_groups).
+ * Group-norm extractor: conv0, then GroupNorm(conv_dim groups of one channel, eps 1e-5, affine) = a per-channel normalisation over
+ * the window's own conv0 frames, then GELU; convs 1 .. n - 1 are conv, GELU without a norm; then the feature projection as above.
+ * The channel statistics are derived from the window's own samples (the means of the conv_kernel[0] tap positions and their
+ * centred covariance, 64 block partials each, folded in index order in double), so they depend on nothing but the window.  In this
+ * family conv_kernel[0] <= 16.  Post-LN encoder: encoder.layer_norm on h + gelu(pos_conv(h)) BEFORE the layers, each layer
+ * x = layer_norm(x + attention(x)), x = final_layer_norm(x + feed_forward(x)), no norm after the last layer.
+ * ext->do_normalize = 0 feeds the samples as they are (svc_w2v_normalize then copies, svc_w2v_content skips the normalisation).
+ * Every other call serves both families unchanged. */
 typedef struct svc_w2v_config {
     int conv_dim, n_conv, conv_kernel[8], conv_stride[8];
     int d_model, n_heads, n_layers, ffn_dim, pos_k, pos_groups;
-    int feat_extract_norm_layer, do_stable_layer_norm, conv_bias;   /* must all be 1 */
+    int feat_extract_norm_layer, do_stable_layer_norm, conv_bias;   /* svc_w2v_create: must all be 1; svc_w2v_create_ex: see above */
     int window_samples;     /* the drivers' window: 480000 (a multiple of 320) */
     int precision;
 } svc_w2v_config_t;
+typedef struct svc_w2v_ext {
+    int do_normalize;          /* 1: per-window zero-mean / unit-variance (svc_w2v_create's behaviour); 0: samples as they are */
+    int feat_proj_layer_norm;  /* must be 1 (HubertConfig.feat_proj_layer_norm; wav2vec2 always has it) */
+} svc_w2v_ext_t;
 typedef struct svc_w2v svc_w2v_t;
 
 int svc_w2v_create(const svc_w2v_config_t* cfg, const svc_tensor_desc_t* weights, int n_weights, void* stream, svc_w2v_t** out);
+/* svc_w2v_create is this call with ext == NULL (the strict checks above).  With ext the base family is accepted as well. */
+int svc_w2v_create_ex(const svc_w2v_config_t* cfg, const svc_w2v_ext_t* ext, const svc_tensor_desc_t* weights, int n_weights,
+                      void* stream, svc_w2v_t** out);
 void svc_w2v_destroy(svc_w2v_t* m);
 /* Host-side counts (no handle; -1 on a bad argument).  svc_w2v_frames: rows of n_samples in one piece.  The window plan is the
  * drivers' (svc_whisper_n_windows, with W = window_samples and O = 320 overlap_rows); a window of n samples yields frames(n) rows,

@@ -40,7 +40,7 @@ EXPORTS = [
     "svc_whisper_set_timing", "svc_whisper_last_timing", "svc_whisper_mel", "svc_whisper_encode", "svc_whisper_content",
     "svc_w2v_create", "svc_w2v_destroy", "svc_w2v_frames", "svc_w2v_n_windows", "svc_w2v_rows", "svc_w2v_set_window_group",
     "svc_w2v_set_timing", "svc_w2v_last_timing", "svc_w2v_normalize", "svc_w2v_features", "svc_w2v_posconv", "svc_w2v_encode",
-    "svc_w2v_content",
+    "svc_w2v_content", "svc_w2v_create_ex",
     "svc_astral_create", "svc_astral_destroy", "svc_astral_n_windows", "svc_astral_rows", "svc_astral_set_window_group",
     "svc_astral_set_timing", "svc_astral_last_timing", "svc_astral_ssl", "svc_astral_convnext", "svc_astral_logits", "svc_astral_tokens",
     "svc_astral_tokens_heads", "svc_op_bsq_index", "svc_tokens_reduce",
@@ -123,6 +123,10 @@ class W2vConfig(C.Structure):
     _fields_ = [("conv_dim", C.c_int), ("n_conv", C.c_int), ("conv_kernel", C.c_int * 8), ("conv_stride", C.c_int * 8)] + \
                [(n, C.c_int) for n in ("d_model", "n_heads", "n_layers", "ffn_dim", "pos_k", "pos_groups", "feat_extract_norm_layer",
                                        "do_stable_layer_norm", "conv_bias", "window_samples", "precision")]
+
+
+class W2vExt(C.Structure):
+    _fields_ = [("do_normalize", C.c_int), ("feat_proj_layer_norm", C.c_int)]
 
 
 class AstralHeadConfig(C.Structure):
@@ -343,6 +347,7 @@ def lib():
         # wav2vec 2.0 content encoder: lengths and row counts as HOST int32 arrays, sample counts as C long
         cp = C.POINTER(W2vConfig)
         l.svc_w2v_create.argtypes = [cp, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]
+        l.svc_w2v_create_ex.argtypes = [cp, C.POINTER(W2vExt), C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]
         l.svc_w2v_destroy.argtypes = [C.c_void_p]
         l.svc_w2v_frames.argtypes = [cp, C.c_long]
         l.svc_w2v_frames.restype = C.c_long

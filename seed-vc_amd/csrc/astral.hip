@@ -443,7 +443,7 @@ int svc_astral_create(const svc_astral_config_t* cfg, const svc_tensor_desc_t* s
     auto* m = new svc_astral();
     m->cfg = *cfg;
     m->dt = cfg->ssl.precision ? 0 : 1;
-    if (w2v_create(&cfg->ssl, ssl_weights, n_ssl_weights, stream, false, &m->ssl)) {
+    if (w2v_create(&cfg->ssl, nullptr, ssl_weights, n_ssl_weights, stream, false, &m->ssl)) {
         set_error(std::string(who) + ": the SSL front: " + get_error());
         delete m;
         return 1;

@@ -110,7 +110,7 @@ struct KeyShape { std::string name; std::vector<long> shape; };
 // the whole key under the layer, or null for a key projection without bias.
 struct StackNames { const char *layers, *q, *k, *k_bias, *v, *o, *ln1, *fc1, *fc2, *ln2, *ln_final; };
 
-// Pre-LN transformer encoder, head dimension 64: per layer LayerNorm, q | k | v in one GEMM (1 / 8 and the attention's log2(e)
+// Transformer encoder (pre-LN; post-LN with `post_ln`), head dimension 64: per layer LayerNorm, q | k | v in one GEMM (1 / 8 and the attention's log2(e)
 // folded into the q rows), fp16 rows for the attention and a small transpose for V^T, out_proj + residual, LayerNorm, GELU MLP
 // + residual; then the final LayerNorm.  Residual stream, LayerNorm statistics and softmax are fp32; the linears run on the fp16
 // tap-GEMM (dt 0) or the fp32 one (dt 1).  Every sequence is computed as if alone.
@@ -119,6 +119,12 @@ struct EncoderStack {
     int qt_form = 1;                 // the attention's query-tile form, pinned per handle by the model
     std::vector<Layer> layers;
     bool final_ln = true;            // internal: false ends at the residual stream after the last layer, left in x (the ASTRAL front, astral.hip)
+    // post-LN order (the wav2vec 2.0 base family): ln_final on the stem's rows BEFORE the layers, each layer x = ln1(x + attention(x)),
+    // x = ln2(x + mlp(x)), nothing after the last layer.  The sums go to `y`, the LayerNorms bring them back to x (needs final_ln).
+    // In precision 0 the post-LN order keeps q, k, v and the softmax weights in fp32 (attn_f32_kernel on qkv32): their fp16
+    // rounding alone is above the 1e-4 bound there.  The pre-LN order is what it was.
+    bool post_ln = false;
+    float *y = nullptr, *qkv32 = nullptr;
     float *gf = nullptr, *bf = nullptr;
     float *x = nullptr, *n32 = nullptr, *ao32 = nullptr, *ff32 = nullptr;           // x [G * P][D]: the residual stream, filled by the stem
     half_t *n16 = nullptr, *qkv16 = nullptr, *vt = nullptr, *ao16 = nullptr, *ff16 = nullptr;
@@ -129,6 +135,7 @@ struct EncoderStack {
     // x [G][P][D] -> out [G][P][D]; with lens, sequence g has lens[g] rows and the rows above are neither read nor written.
     // Without the final LayerNorm the result stays in x and `out` is not used.
     int run(int G, int P, const int* lens, float* out, hipStream_t st);
+    int run_post(int G, int P, const int* lens, float* out, hipStream_t st);        // run() with post_ln
 };
 
 // measurement aid: events around the stages of the last group of the last call

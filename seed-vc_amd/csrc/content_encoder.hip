@@ -50,6 +50,50 @@ __global__ __launch_bounds__(256) void vt_kernel(const half_t* __restrict__ qkv,
     }
 }
 
+// Attention on fp32 operands (precision 0 of the post-LN order, where the fp16 rounding of q, k, v and the softmax weights alone is
+// 1.4e-4 of the output): one wave per (query row, head, window), head dimension 64.  qkv [G * P][3 D] fp32 with
+// 1 / 8 and log2(e) already in q.  Keys in chunks of 64 in ascending order: lane j scores key t0 + j (q from LDS, the key's row from
+// memory), the running maximum and sum are the online softmax's, lane d accumulates output dimension d over the chunk's keys in
+// ascending order.  Keys at and above the window's own count are never read.  A row's result depends on its window alone.
+__global__ __launch_bounds__(256) void attn_f32_kernel(const float* __restrict__ qkv, float* __restrict__ out, const int* __restrict__ lens, int P, int D,
+                                                       int H) {
+    __shared__ float q_s[4][64];
+    const int g = blockIdx.z, h = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int T = lens ? lens[g] : P, row = blockIdx.x * 4 + wave;
+    const float* base = qkv + (long)g * P * 3 * D + h * 64;
+    if (row < T) q_s[wave][lane] = base[(long)row * 3 * D + lane];
+    __syncthreads();
+    if (row >= T) return;                                    // per wave, after the only barrier
+    float m = -1e30f, l = 0.f, acc = 0.f;
+    for (int t0 = 0; t0 < T; t0 += 64) {
+        const int t = t0 + lane;
+        float s = -1e30f;
+        if (t < T) {
+            const float4* kr = reinterpret_cast<const float4*>(base + (long)t * 3 * D + D);
+            float a = 0.f;
+#pragma unroll
+            for (int d4 = 0; d4 < 16; ++d4) {
+                const float4 kv = kr[d4];
+                a = fmaf(q_s[wave][4 * d4], kv.x, a); a = fmaf(q_s[wave][4 * d4 + 1], kv.y, a);
+                a = fmaf(q_s[wave][4 * d4 + 2], kv.z, a); a = fmaf(q_s[wave][4 * d4 + 3], kv.w, a);
+            }
+            s = a;
+        }
+        float cm = s;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) cm = fmaxf(cm, __shfl_xor(cm, o));
+        const float mn = fmaxf(m, cm), sc = exp2f(m - mn);
+        const float p = t < T ? exp2f(s - mn) : 0.f;
+        l = l * sc + wave_sum(p);
+        acc *= sc;
+        const int nk = min(64, T - t0);
+        const float* vr = base + (long)t0 * 3 * D + 2 * D + lane;
+        for (int j = 0; j < nk; ++j) acc = fmaf(__shfl(p, j), vr[(long)j * 3 * D], acc);
+        m = mn;
+    }
+    out[((long)g * P + row) * D + h * 64 + lane] = acc / l;
+}
+
 // block (r, g).  r < P: row r of window g, when kept, goes to its place in the clip's rows; r >= P: row r - P of the clip is
 // zeroed when window g is the clip's last and the row is at or above the clip's count
 __global__ void assemble_kernel(const float* __restrict__ enc, WinTab wt, float* __restrict__ out, int P, int D, int Rmax) {
@@ -217,6 +261,8 @@ int EncoderStack::reserve(Arena& ws, int G, int P, hipStream_t st) {
     vt = ws.alloc_n<half_t>((size_t)G * D * round_up(P, 64), st);
     ao16 = ws.alloc_n<half_t>((size_t)MP * D, st);
     if (!x || !qkv16 || !vt || !ao16) return 1;
+    if (post_ln && !(y = ws.alloc_n<float>((size_t)MP * D, st))) return 1;
+    if (post_ln && dt == 1 && !(qkv32 = ws.alloc_n<float>((size_t)MP * 3 * D, st))) return 1;
     if (dt == 0) {
         n16 = ws.alloc_n<half_t>((size_t)MP * D, st);
         ff16 = ws.alloc_n<half_t>((size_t)MP * F, st);
@@ -238,6 +284,7 @@ int EncoderStack::run(int G, int P, const int* lens, float* out, hipStream_t st)
     auto norm = [&](const float* g, const float* b, float* y32, half_t* y16) {
         return rownorm_launch(0, x, D, y32, y16, D, g, b, nullptr, nullptr, MP, D, 1e-5f, lens, P, st);
     };
+    if (post_ln) return run_post(G, P, lens, out, st);
     for (const Layer& ly : layers) {
         if (norm(ly.g1, ly.b1, f16 ? nullptr : n32, f16 ? n16 : nullptr)) return 1;
         if (linear_launch(dt, ly.qkv, nrm, D, MP, P, KG_ACT_NONE, nullptr, nullptr, qkv16, st)) return 1;
@@ -259,6 +306,49 @@ int EncoderStack::run(int G, int P, const int* lens, float* out, hipStream_t st)
     }
     if (!final_ln) return 0;                                 // the result is the residual stream x itself
     return norm(gf, bf, out, nullptr);
+}
+
+// Post-LN order.  The residual stream r lives in y once ln_final has normalised the stem's rows out of x; x then takes the sums
+// r + branch(r) of the residual epilogues and each LayerNorm brings them back to r (and its fp16 copy, the next GEMM's operand).
+// The last LayerNorm writes `out`.  No buffer is read and written by one launch except by the residual epilogues' own element.
+int EncoderStack::run_post(int G, int P, const int* lens, float* out, hipStream_t st) {
+    SVC_REQUIRE(final_ln && y, "content encoder: the post-LN order needs encoder.layer_norm and its workspace");
+    const long MP = (long)G * P, vt_ld = round_up(P, 64);
+    const bool f16 = dt == 0;
+    float* r = y;
+    float* s = x;
+    const void* nrm = f16 ? (const void*)n16 : (const void*)r;
+    const int vmode = attention_vt_mode(G, H, P);
+    auto norm = [&](const float* g, const float* b, float* y32) {
+        return rownorm_launch(0, s, D, y32, f16 && y32 == r ? n16 : nullptr, D, g, b, nullptr, nullptr, MP, D, 1e-5f, lens, P, st);
+    };
+    if (norm(gf, bf, r)) return 1;
+    for (size_t i = 0; i < layers.size(); ++i) {
+        const Layer& ly = layers[i];
+        if (f16) {
+            if (linear_launch(dt, ly.qkv, nrm, D, MP, P, KG_ACT_NONE, nullptr, nullptr, qkv16, st)) return 1;
+            if (vt_launch(qkv16, vt, lens, G, P, D, vt_ld, vmode, st)) return 1;
+            AttnParams a;
+            memset(&a, 0, sizeof(a));
+            a.q = qkv16; a.k = qkv16 + D; a.ld_qk = 3 * D;
+            a.vt = vt; a.vt_seq_stride = (long)D * vt_ld; a.vt_ld = vt_ld; a.vt_perm = vmode;
+            a.ld_out = D;
+            a.out = ao16;
+            a.n_seq = G; a.H = H; a.seq_rows = P; a.Tq = P; a.kv_len = lens; a.kv_len_const = P;
+            a.qt_form = qt_form;
+            if (attention_launch(a, st)) return 1;
+        } else {
+            if (linear_launch(dt, ly.qkv, nrm, D, MP, P, KG_ACT_NONE, nullptr, qkv32, nullptr, st)) return 1;
+            hipLaunchKernelGGL(attn_f32_kernel, dim3(cdiv(P, 4), H, G), dim3(256), 0, st, (const float*)qkv32, ao32, lens, P, D, H);
+            SVC_CHECK_HIP(hipGetLastError());
+        }
+        if (linear_launch(dt, ly.o, f16 ? (const void*)ao16 : (const void*)ao32, D, MP, P, KG_ACT_NONE, r, s, nullptr, st)) return 1;
+        if (norm(ly.g1, ly.b1, r)) return 1;
+        if (linear_launch(dt, ly.fc1, nrm, D, MP, P, KG_ACT_GELU, nullptr, f16 ? nullptr : ff32, f16 ? ff16 : nullptr, st)) return 1;
+        if (linear_launch(dt, ly.fc2, f16 ? (const void*)ff16 : (const void*)ff32, F, MP, P, KG_ACT_NONE, r, s, nullptr, st)) return 1;
+        if (norm(ly.g2, ly.b2, i + 1 == layers.size() ? out : r)) return 1;
+    }
+    return 0;
 }
 
 }  // namespace svc

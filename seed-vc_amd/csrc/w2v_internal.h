@@ -14,7 +14,9 @@ long wv_frames(const svc_w2v_config_t& c, long n, int upto = WV_MAX_CONV);
 // the checks svc_w2v_frames / _rows / _n_windows make of a configuration (error set, prefixed with `who`)
 int wv_check_cfg(const svc_w2v_config_t* c, const char* who);
 // svc_w2v_create; final_ln false: encoder.layer_norm.* is neither required nor applied, the output is the residual stream
-int w2v_create(const svc_w2v_config_t* cfg, const svc_tensor_desc_t* weights, int n_weights, void* stream, bool final_ln, svc_w2v_t** out);
+// ext null: the strict checks of svc_w2v_create; else svc_w2v_create_ex's (the base family: group-norm extractor, post-LN encoder)
+int w2v_create(const svc_w2v_config_t* cfg, const svc_w2v_ext_t* ext, const svc_tensor_desc_t* weights, int n_weights, void* stream, bool final_ln,
+               svc_w2v_t** out);
 
 }  // namespace svc
 
@@ -36,6 +38,12 @@ struct svc_w2v {
     void *actA = nullptr, *actB = nullptr; float* raw = nullptr;
     float *h32 = nullptr, *enc = nullptr, *acc32 = nullptr;
     svc::half_t* h16 = nullptr;
+    // base family: group-norm extractor, samples as they are, positional-conv groups narrower than 64 channels
+    bool group_norm = false, do_normalize = true;
+    int pos_w = 64;                                                      // channels per positional-conv group (16, 32, 48, 64)
+    double* gpart = nullptr;                                             // [MAX_WIN][WV_NBLK][k0 + k0 (k0 + 1) / 2] block partials
+    float *gmean = nullptr, *gscale = nullptr, *gshift = nullptr;        // [MAX_WIN][16] tap means; [MAX_WIN][C] scale and shift of conv0
+    float* hpad = nullptr;                                               // precision 0, pos_w < 64: h with every group zero-padded to 64 channels
     svc::StageTimer tm;
     int pack(const svc::StateDict& sd, const std::string& pre, hipStream_t st);
     int reserve_fe(int G, long nmax, hipStream_t st);

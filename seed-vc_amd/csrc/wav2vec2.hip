@@ -11,6 +11,10 @@
 // the fp32 tap-GEMM, one accumulating launch per group and 48 taps.  The transformer stack (with per-window key counts), the
 // window plan of long clips and the row gather are content_encoder.h's.  Every window is computed as if alone (tile-independent
 // tap order in the positional conv), so its bits do not depend on its companions, their order or the group size.
+//
+// The base family (HuBERT-base / wav2vec2-base, through svc_w2v_create_ex): a group norm over the window's own conv0
+// frames instead of the LayerNorms (statistics from the window's samples: wv_gn_*_kernel below), positional-conv groups of 16 .. 64
+// channels (the kernel is a template on the width) and the stack's post-LN order.
 #include <math.h>
 #include <string.h>
 
@@ -121,8 +125,13 @@ __global__ __launch_bounds__(256) void wv_conv0_kernel(const float* __restrict__
 // accumulator tiles): the waves share the rows in LDS, and no two waves need the same weights, so the pre-packed weight fragments
 // (1 KiB per (tap, k-step, wave), lane order) go straight from L2 to registers, four taps ahead, with no LDS ring.  Every output element
 // accumulates (tap 0 .. k-1) x (channels 0..31, 32..63) in that order in fp32, whatever T, the batch or the tile.
+// Groups of WD = 16, 32 or 48 channels (the base family: 768 / 16 = 48) keep the 128-byte rows and the K steps of 32: the 16-byte
+// chunks at and above WD / 8 of every row are WRITTEN as zeros (0 x a stale NaN would be NaN), the weight fragments of the channels
+// at and above WD are zeros from the pack, WD / 16 waves own output channels (the others only help to load the rows) and WD <= 32
+// runs one K step.  WD = 64 is the kernel it was, instruction for instruction.
 __device__ __forceinline__ int wv_pc_swz(int row) { return (row >> 1) & 7; }
 
+template <int WD>
 __global__ __launch_bounds__(256) void w2v_posconv_kernel(const half_t* __restrict__ x16, const float* __restrict__ x32, const half_t* __restrict__ wp,
                                                           const float* __restrict__ bias, float* __restrict__ out, const int* __restrict__ lens,
                                                           int P, int D, int k, int n_win, int n_tiles) {
@@ -131,32 +140,35 @@ __global__ __launch_bounds__(256) void w2v_posconv_kernel(const half_t* __restri
     const int T = lens[win], p0 = tile * WV_PC_BM;
     if (p0 >= T) return;                                    // uniform over the workgroup, before any barrier
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fq = lane >> 4;
+    constexpr int NW = WD / 16, KS = WD > 32 ? 2 : 1;        // waves that own output channels, K steps of 32 channels
     const int R = WV_PC_BM + k - 1, half = k / 2;
-    const half_t* xg = x16 + (long)win * P * D + grp * 64;
+    const half_t* xg = x16 + (long)win * P * D + grp * WD;
     for (int idx = tid; idx < R * 8; idx += 256) {
         const int r = idx >> 3, c = idx & 7, q = p0 + r - half;
         uint4 v = make_uint4(0u, 0u, 0u, 0u);
-        if (q >= 0 && q < T) v = *reinterpret_cast<const uint4*>(xg + (long)q * D + c * 8);
+        if ((WD == 64 || c < WD / 8) && q >= 0 && q < T) v = *reinterpret_cast<const uint4*>(xg + (long)q * D + c * 8);
         *reinterpret_cast<uint4*>(rows_s + r * 128 + ((c ^ wv_pc_swz(r)) << 4)) = v;
     }
     __syncthreads();
+    if (NW < 4 && wave >= NW) return;                        // after the only barrier
     float4v acc[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) acc[i] = (float4v){0.f, 0.f, 0.f, 0.f};
-    // fragment (tap t, k-step ks, wave w): wp[(((grp k + t) 2 + ks) 4 + w) 64 + lane] (16 bytes)
-    const uint4* wf = reinterpret_cast<const uint4*>(wp) + ((long)grp * k * 8 + wave) * 64 + lane;
+    // fragment (tap t, k-step ks, wave w): wp[(((grp k + t) KS + ks) NW + w) 64 + lane] (16 bytes)
+    constexpr int TS = KS * NW * 64, K1 = (KS - 1) * NW * 64;   // fragments per tap; offset of the second K step (0: there is none)
+    const uint4* wf = reinterpret_cast<const uint4*>(wp) + ((long)grp * k * KS * NW + wave) * 64 + lane;
     // the weights of the next WV_PC_AHEAD taps are in flight under the MFMAs of a tap (a tap's 8 MFMAs are shorter than an L2 round trip)
     uint4 wb[WV_PC_AHEAD][2];
 #pragma unroll
     for (int u = 0; u < WV_PC_AHEAD; ++u)
-        if (u < k) { wb[u][0] = wf[(long)u * 8 * 64]; wb[u][1] = wf[(long)u * 8 * 64 + 4 * 64]; }
+        if (u < k) { wb[u][0] = wf[(long)u * TS]; wb[u][1] = wf[(long)u * TS + K1]; }
     for (int t0 = 0; t0 < k; t0 += WV_PC_AHEAD) {
 #pragma unroll
         for (int u = 0; u < WV_PC_AHEAD; ++u) {
             const int t = t0 + u;
             if (t >= k) break;
             const uint4 c0 = wb[u][0], c1 = wb[u][1];
-            if (t + WV_PC_AHEAD < k) { wb[u][0] = wf[(long)(t + WV_PC_AHEAD) * 8 * 64]; wb[u][1] = wf[(long)(t + WV_PC_AHEAD) * 8 * 64 + 4 * 64]; }
+            if (t + WV_PC_AHEAD < k) { wb[u][0] = wf[(long)(t + WV_PC_AHEAD) * TS]; wb[u][1] = wf[(long)(t + WV_PC_AHEAD) * TS + K1]; }
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt) {
                 const int row = mt * 16 + fr + t;
@@ -165,12 +177,12 @@ __global__ __launch_bounds__(256) void w2v_posconv_kernel(const half_t* __restri
                 const uint4 a0 = *reinterpret_cast<const uint4*>(rp + ((fq ^ sw) << 4));
                 const uint4 a1 = *reinterpret_cast<const uint4*>(rp + (((4 + fq) ^ sw) << 4));
                 acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, a0), __builtin_bit_cast(half8, c0), acc[mt], 0, 0, 0);
-                acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, a1), __builtin_bit_cast(half8, c1), acc[mt], 0, 0, 0);
+                if (KS == 2) acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, a1), __builtin_bit_cast(half8, c1), acc[mt], 0, 0, 0);
             }
         }
     }
     // acc[mt][r] = C[position p0 + 16 mt + 4 fq + r][channel 16 wave + fr]
-    const int nch = grp * 64 + wave * 16 + fr;
+    const int nch = grp * WD + wave * 16 + fr;
     const float bv = bias[nch];
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt)
@@ -204,19 +216,155 @@ __global__ __launch_bounds__(256) void wv_wn_scale_kernel(const float* __restric
     __syncthreads();
     if (threadIdx.x == 0) sc[t] = (float)((double)g[t] / sqrt((red[0] + red[1]) + (red[2] + red[3])));
 }
-// v [D][64][k] (x sc[t], or as it is when sc is null) -> the fp16 fragment stream of w2v_posconv_kernel and / or the fp32 tap-GEMM
-// rows w32[(grp 64 + n)][t 64 + c]
-__global__ void wv_pack_pos_kernel(const float* __restrict__ v, const float* __restrict__ sc, int D, int k, half_t* __restrict__ wp, float* __restrict__ w32) {
+// v [D][wd][k] (x sc[t], or as it is when sc is null), groups of wd channels -> the fp16 fragment stream of w2v_posconv_kernel and /
+// or the fp32 tap-GEMM rows w32[(grp wd + n)][t 64 + c].  With wd < 64 the slots of the channels wd .. 63 (wd .. 31 at wd = 16) are
+// not written here: the caller zeroed the whole destination first.
+__global__ void wv_pack_pos_kernel(const float* __restrict__ v, const float* __restrict__ sc, int D, int wd, int k, half_t* __restrict__ wp,
+                                   float* __restrict__ w32) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long)D * 64 * k) return;
-    const int t = (int)(i % k), c = (int)((i / k) % 64), no = (int)(i / ((long)k * 64));
+    if (i >= (long)D * wd * k) return;
+    const int t = (int)(i % k), c = (int)((i / k) % wd), no = (int)(i / ((long)k * wd));
     const float val = v[i] * (sc ? sc[t] : 1.f);
-    const int grp = no / 64, n = no % 64;
+    const int grp = no / wd, n = no % wd, nw = wd / 16, nks = wd > 32 ? 2 : 1;
     if (wp) {
         const int w = n >> 4, fr = n & 15, ks = c >> 5, fq = (c & 31) >> 3, j = c & 7;
-        wp[((((long)(grp * k + t) * 2 + ks) * 4 + w) * 64 + fq * 16 + fr) * 8 + j] = (half_t)val;
+        wp[((((long)(grp * k + t) * nks + ks) * nw + w) * 64 + fq * 16 + fr) * 8 + j] = (half_t)val;
     }
     if (w32) w32[((long)no * k + t) * 64 + c] = val;
+}
+// precision 0, groups narrower than 64 channels: dst [rows][NG 64] = the rows of h [rows][NG wd] with every group zero-padded to 64
+// channels (the fp32 tap-GEMM reads K in steps of 32).  Rows at and above the window's count are written as zeros, never read.
+__global__ void wv_padgroups_kernel(const float* __restrict__ h, float* __restrict__ dst, const int* __restrict__ lens, int P, int D, int wd) {
+    const int win = blockIdx.y, p = blockIdx.x, ng = D / wd;
+    const bool live = p < lens[win];
+    const long i = (long)win * P + p;
+    for (int c = threadIdx.x; c < ng * 64; c += blockDim.x) {
+        const int g = c >> 6, cc = c & 63;
+        dst[i * ng * 64 + c] = live && cc < wd ? h[i * D + g * wd + cc] : 0.f;
+    }
+}
+
+// ---- group-norm extractor (the base family).  GroupNorm with one channel per group normalises channel c of conv0
+// over the window's own T0 frames.  conv0 is linear in its k0 taps, so with m_j = mean_t x[s0 t + j] and Cov_jk = mean_t (x[s0 t + j]
+// - m_j)(x[s0 t + k] - m_k) the channel's mean is b_c + sum_j w_cj m_j and its variance sum_jk w_cj w_ck Cov_jk: the raw T0 x C plane
+// is never written.  Statistics: item = a tap j (POW 1) or a pair j <= k (POW 2); block blk of 64 sums its share of the frames (the
+// share depends on T0 only), thread (item, frame lane fl) sums the frames fl, fl + FL, ... of the share in order, the FL lanes are
+// folded in index order; the 64 block partials are folded in index order by the consumer.  Double throughout, no atomics.
+constexpr int WV_GN_MAXK = 16, WV_GN_MAXP = WV_GN_MAXK * (WV_GN_MAXK + 1) / 2;      // most taps of conv0 in this family, most pairs
+template <int POW>
+__global__ __launch_bounds__(256) void wv_gn_stat_kernel(const float* __restrict__ x, long stride, const int* __restrict__ lens0, int k0, int s0,
+                                                         int n_items, int items_pad, const double* __restrict__ sums, double* __restrict__ part) {
+    __shared__ double red[256];
+    __shared__ double mean_s[WV_GN_MAXK];
+    const int g = blockIdx.y, blk = blockIdx.x, T0 = lens0[g];
+    const float* xg = x + (long)g * stride;
+    const int per = (T0 + WV_NBLK - 1) / WV_NBLK, i0 = blk * per, i1 = min(T0, i0 + per);
+    const int item = threadIdx.x % items_pad, fl = threadIdx.x / items_pad, FL = 256 / items_pad;
+    if (POW == 2 && threadIdx.x < k0) {
+        double m = 0.0;
+        for (int b = 0; b < WV_NBLK; ++b) m += sums[((long)g * WV_NBLK + b) * k0 + threadIdx.x];
+        mean_s[threadIdx.x] = m / (double)T0;
+    }
+    __syncthreads();
+    int j = item, kk = item;
+    if (POW == 2) {                                          // pair index -> (j <= kk), rows of the upper triangle in order
+        j = 0;
+        int left = item;
+        while (j < k0 - 1 && left >= k0 - j) { left -= k0 - j; ++j; }
+        kk = j + left;
+    }
+    double s = 0.0;
+    if (item < n_items) {
+        const double mj = POW == 2 ? mean_s[j] : 0.0, mk = POW == 2 ? mean_s[kk] : 0.0;
+        for (int t = i0 + fl; t < i1; t += FL) {
+            const float* xt = xg + (long)t * s0;
+            s += POW == 2 ? ((double)xt[j] - mj) * ((double)xt[kk] - mk) : (double)xt[j];
+        }
+    }
+    red[threadIdx.x] = s;
+    __syncthreads();
+    if (fl == 0 && item < n_items) {
+        double a = 0.0;
+        for (int f = 0; f < FL; ++f) a += red[f * items_pad + item];
+        part[((long)g * WV_NBLK + blk) * n_items + item] = a;
+    }
+}
+// one block per window: fold the partials, then per channel y = (conv0 of the centred samples) * scale + shift with
+// scale = gamma / sqrt(var_c + eps), shift = beta (the conv bias cancels against the channel's mean); the tap means go to `mean`
+__global__ __launch_bounds__(256) void wv_gn_affine_kernel(const double* __restrict__ psum, const double* __restrict__ pcov, const int* __restrict__ lens0,
+                                                           const float* __restrict__ w /*[k0][C]*/, const float* __restrict__ gamma,
+                                                           const float* __restrict__ beta, int C, int k0, float eps, float* __restrict__ mean,
+                                                           float* __restrict__ scale, float* __restrict__ shift) {
+    __shared__ double cov_s[WV_GN_MAXK][WV_GN_MAXK];
+    const int g = blockIdx.x, T0 = lens0[g], np = k0 * (k0 + 1) / 2;
+    if (T0 < 1) return;
+    for (int item = threadIdx.x; item < np + k0; item += 256) {
+        const bool is_mean = item >= np;
+        const int it = is_mean ? item - np : item, n_items = is_mean ? k0 : np;
+        const double* p = (is_mean ? psum : pcov) + (long)g * WV_NBLK * n_items + it;
+        double a = 0.0;
+        for (int b = 0; b < WV_NBLK; ++b) a += p[(long)b * n_items];
+        a /= (double)T0;
+        if (is_mean) mean[g * WV_GN_MAXK + it] = (float)a;
+        else {
+            int j = 0, left = it;
+            while (j < k0 - 1 && left >= k0 - j) { left -= k0 - j; ++j; }
+            cov_s[j][j + left] = a;
+            cov_s[j + left][j] = a;
+        }
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < C; c += 256) {
+        double var = 0.0;
+        for (int j = 0; j < k0; ++j) {
+            double r = 0.0;
+            for (int kk = 0; kk < k0; ++kk) r += (double)w[kk * C + c] * cov_s[j][kk];
+            var += (double)w[j * C + c] * r;
+        }
+        scale[(long)g * C + c] = (float)((double)gamma[c] / sqrt(fmax(var, 0.0) + (double)eps));
+        shift[(long)g * C + c] = beta[c];
+    }
+}
+// conv0 on the centred samples + the channel's scale and shift + erf-GELU: one wave per output row, weights [k0][C] in LDS
+__global__ __launch_bounds__(256) void wv_conv0_gn_kernel(const float* __restrict__ wn, long stride, const float* __restrict__ w /*[k0][C]*/,
+                                                          const float* __restrict__ mean, const float* __restrict__ scale, const float* __restrict__ shift,
+                                                          float* __restrict__ y32, half_t* __restrict__ y16, int C, int k0, int s0, int L0,
+                                                          const int* __restrict__ lens0) {
+    extern __shared__ float w_s[];
+    const int g = blockIdx.y, lane = threadIdx.x & 63, n = C / 64, len = lens0[g];
+    for (int i = threadIdx.x; i < k0 * C; i += 256) w_s[i] = w[i];
+    __syncthreads();
+    const float* xg = wn + (long)g * stride;
+    const float* mg = mean + g * WV_GN_MAXK;
+    float sc[8], sh[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+        if (i < n && len > 0) { sc[i] = scale[(long)g * C + lane + 64 * i]; sh[i] = shift[(long)g * C + lane + 64 * i]; }
+    for (int row = blockIdx.x * 4 + (threadIdx.x >> 6); row < len; row += gridDim.x * 4) {
+        float v[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = 0.f;
+        for (int t = 0; t < k0; ++t) {
+            const float xv = xg[(long)row * s0 + t] - mg[t];
+#pragma unroll
+            for (int i = 0; i < 8; ++i)
+                if (i < n) v[i] = fmaf(xv, w_s[t * C + lane + 64 * i], v[i]);
+        }
+        const long o = ((long)g * L0 + row) * C;
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+            if (i < n) {
+                const float yv = gelu_erf(fmaf(v[i], sc[i], sh[i]));
+                if (y32) y32[o + lane + 64 * i] = yv;
+                if (y16) y16[o + lane + 64 * i] = (half_t)yv;
+            }
+    }
+}
+// do_normalize = 0: dst[g][i] = the window's samples as they are, i < n; nothing at or above n is read or written
+__global__ void wv_copy_kernel(const float* __restrict__ wave, WinTab wt, long Lrow, float* __restrict__ dst, long stride) {
+    const int g = blockIdx.y;
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < wt.n[g]) dst[(long)g * stride + i] = wave[(long)wt.clip[g] * Lrow + wt.start[g] + i];
 }
 
 }  // namespace
@@ -253,7 +401,8 @@ std::vector<KeyShape> wv_keys(const svc_w2v_config_t& c, bool final_ln) {
     for (int l = 0; l < c.n_conv; ++l) {
         const std::string p = "feature_extractor.conv_layers." + std::to_string(l) + ".";
         k.push_back({p + "conv.weight", {C, l ? C : 1, c.conv_kernel[l]}});
-        k.push_back({p + "conv.bias", {C}});
+        if (c.conv_bias) k.push_back({p + "conv.bias", {C}});
+        if (!c.feat_extract_norm_layer && l) continue;       // group norm: conv 0 alone has a norm (a GroupNorm, under the same name)
         k.push_back({p + "layer_norm.weight", {C}});
         k.push_back({p + "layer_norm.bias", {C}});
     }
@@ -278,7 +427,11 @@ int svc_w2v::pack(const StateDict& sd, const std::string& pre, hipStream_t st) {
         if (l == 0) {   // [C][1][k0] -> [k0][C] fp32
             w0 = wts.alloc_n<float>((size_t)kl * C, st);
             if (!w0 || pack_f32_launch(get(p + "conv.weight"), w0, kl, C, 1, 1, kl, 0, C, 1, 0, nullptr, st)) return 1;
-            if (!(b0 = copy_f32(get(p + "conv.bias"), C, wts, st))) return 1;
+            if (cfg.conv_bias) { if (!(b0 = copy_f32(get(p + "conv.bias"), C, wts, st))) return 1; }
+            else {               // the layer-norm conv0 kernel adds a bias: zeros (the group-norm one has none: it cancels against the mean)
+                if (!(b0 = wts.alloc_n<float>(C, st))) return 1;
+                SVC_CHECK_HIP(hipMemsetAsync(b0, 0, (size_t)C * 4, st));
+            }
         } else {        // [C][C][kl] -> [Cpad128][kl * C], tap-major
             Lin& c = conv[l];
             c.N = C; c.ldw = (long)kl * C;
@@ -286,8 +439,9 @@ int svc_w2v::pack(const StateDict& sd, const std::string& pre, hipStream_t st) {
             if (!c.w) return 1;
             for (int t = 0; t < kl; ++t)
                 if (pack_any(dt, get(p + "conv.weight") + t, c.w, (long)t * C, C, C, 1, (long)kl * C, kl, 0, c.ldw, 1, 0, nullptr, st)) return 1;
-            if (!(c.b = copy_f32(get(p + "conv.bias"), C, wts, st))) return 1;
+            if (cfg.conv_bias && !(c.b = copy_f32(get(p + "conv.bias"), C, wts, st))) return 1;
         }
+        if (group_norm && l) continue;
         if (!(cg[l] = copy_f32(get(p + "layer_norm.weight"), C, wts, st)) || !(cb[l] = copy_f32(get(p + "layer_norm.bias"), C, wts, st))) return 1;
     }
     if (!(pg = copy_f32(get("feature_projection.layer_norm.weight"), C, wts, st)) || !(pb = copy_f32(get("feature_projection.layer_norm.bias"), C, wts, st)))
@@ -302,19 +456,28 @@ int svc_w2v::pack(const StateDict& sd, const std::string& pre, hipStream_t st) {
         float* sc = nullptr;
         if (g) {
             if (!(sc = wts.alloc_n<float>(k, st))) return 1;
-            hipLaunchKernelGGL(wv_wn_scale_kernel, dim3(k), dim3(256), 0, st, g, v, (long)D * 64, k, sc);
+            hipLaunchKernelGGL(wv_wn_scale_kernel, dim3(k), dim3(256), 0, st, g, v, (long)D * pos_w, k, sc);
             SVC_CHECK_HIP(hipGetLastError());
         }
-        const size_t nw = (size_t)D * 64 * k;
-        if (dt == 0) { if (!(pos16 = wts.alloc_n<half_t>(nw, st))) return 1; }
-        else if (!(pos32 = wts.alloc_n<float>(nw + (size_t)128 * k * 64, st))) return 1;      // slack: the tap-GEMM stages whole weight tiles
-        hipLaunchKernelGGL(wv_pack_pos_kernel, dim3(cdiv((long)nw, 256)), dim3(256), 0, st, v, sc, D, k, pos16, pos32);
+        const size_t nw = (size_t)D * pos_w * k;            // weights; fp16 fragment slots: whole K steps of 32 channels; fp32 rows: 64 channels
+        const size_t n16 = (size_t)D * (pos_w > 32 ? 64 : 32) * k, n32 = (size_t)D * 64 * k + (size_t)128 * k * 64;   // slack: the tap-GEMM stages whole weight tiles
+        if (dt == 0) { if (!(pos16 = wts.alloc_n<half_t>(n16, st))) return 1; }
+        else if (!(pos32 = wts.alloc_n<float>(n32, st))) return 1;
+        if (pos_w < 64) SVC_CHECK_HIP(dt == 0 ? hipMemsetAsync(pos16, 0, n16 * 2, st) : hipMemsetAsync(pos32, 0, n32 * 4, st));   // the padded channels' slots
+        hipLaunchKernelGGL(wv_pack_pos_kernel, dim3(cdiv((long)nw, 256)), dim3(256), 0, st, v, sc, D, pos_w, k, pos16, pos32);
         SVC_CHECK_HIP(hipGetLastError());
         if (!(posb = copy_f32(get("encoder.pos_conv_embed.conv.bias"), D, wts, st))) return 1;
     }
     if (stack.pack(sd, pre, WV_NAMES, cfg.n_layers, wts, st)) return 1;
     if (!(dlens = wts.alloc_n<int>((size_t)(WV_MAX_CONV + 1) * MAX_WIN, st))) return 1;
     if (!(part = wts.alloc_n<double>((size_t)2 * MAX_WIN * WV_NBLK, st))) return 1;
+    if (group_norm) {
+        const int k0 = cfg.conv_kernel[0];
+        if (!(gpart = wts.alloc_n<double>((size_t)MAX_WIN * WV_NBLK * (k0 + k0 * (k0 + 1) / 2), st)) ||
+            !(gmean = wts.alloc_n<float>((size_t)MAX_WIN * WV_GN_MAXK, st)) || !(gscale = wts.alloc_n<float>((size_t)MAX_WIN * C, st)) ||
+            !(gshift = wts.alloc_n<float>((size_t)MAX_WIN * C, st)))
+            return 1;
+    }
     SVC_CHECK_HIP(hipStreamSynchronize(st));
     return 0;
 }
@@ -355,6 +518,7 @@ int svc_w2v::reserve_enc(int G, int P, hipStream_t st) {
     if (!h32 || !enc || stack.reserve(ws_enc, G, P, st)) return 1;
     if (dt == 0 && !(h16 = ws_enc.alloc_n<half_t>((size_t)MP * D, st))) return 1;
     if (dt == 1 && !(acc32 = ws_enc.alloc_n<float>((size_t)MP * D, st))) return 1;
+    if (dt == 1 && pos_w < 64 && !(hpad = ws_enc.alloc_n<float>((size_t)MP * cfg.pos_groups * 64, st))) return 1;
     SVC_CHECK_HIP(hipStreamSynchronize(st));
     ecap_g = G; ecap_p = P;
     return 0;
@@ -369,6 +533,11 @@ int svc_w2v::put_lens(const LenTab& lt, hipStream_t st) {
 int svc_w2v::normalize_group(const float* wave, long Lrow, const WinTab& wt, int G, float* dst, long stride, hipStream_t st) {
     int nmax = 0;
     for (int g = 0; g < G; ++g) nmax = std::max(nmax, wt.n[g]);
+    if (!do_normalize) {
+        hipLaunchKernelGGL(wv_copy_kernel, dim3(cdiv(nmax, 256), G), dim3(256), 0, st, wave, wt, Lrow, dst, stride);
+        SVC_CHECK_HIP(hipGetLastError());
+        return 0;
+    }
     double* sq = part + MAX_WIN * WV_NBLK;
     hipLaunchKernelGGL(wv_stat_kernel<1>, dim3(WV_NBLK, G), dim3(256), 0, st, wave, wt, Lrow, (const double*)nullptr, part);
     hipLaunchKernelGGL(wv_stat_kernel<2>, dim3(WV_NBLK, G), dim3(256), 0, st, wave, wt, Lrow, (const double*)part, sq);
@@ -381,7 +550,20 @@ int svc_w2v::normalize_group(const float* wave, long Lrow, const WinTab& wt, int
 int svc_w2v::features_group(const float* wnorm, long stride, int G, hipStream_t st) {
     const int C = cfg.conv_dim, nc = cfg.n_conv;
     const bool f16 = dt == 0;
-    {
+    if (group_norm) {
+        const int k0 = cfg.conv_kernel[0], s0 = cfg.conv_stride[0], np = k0 * (k0 + 1) / 2;
+        auto pad = [](int n) { int p = 16; while (p < n) p *= 2; return p; };
+        double* pcov = gpart + (size_t)MAX_WIN * WV_NBLK * k0;
+        const int* lens0 = dlens + MAX_WIN;
+        hipLaunchKernelGGL(wv_gn_stat_kernel<1>, dim3(WV_NBLK, G), dim3(256), 0, st, wnorm, stride, lens0, k0, s0, k0, pad(k0), (const double*)nullptr, gpart);
+        hipLaunchKernelGGL(wv_gn_stat_kernel<2>, dim3(WV_NBLK, G), dim3(256), 0, st, wnorm, stride, lens0, k0, s0, np, pad(np), (const double*)gpart, pcov);
+        hipLaunchKernelGGL(wv_gn_affine_kernel, dim3(G), dim3(256), 0, st, (const double*)gpart, (const double*)pcov, lens0, w0, cg[0], cb[0], C, k0, 1e-5f,
+                           gmean, gscale, gshift);
+        const int blocks = std::min(cdiv(Ls[1], 4), 2048);
+        hipLaunchKernelGGL(wv_conv0_gn_kernel, dim3(blocks, G), dim3(256), (size_t)k0 * C * 4, st, wnorm, stride, w0, gmean, gscale, gshift,
+                           f16 ? nullptr : (float*)actA, f16 ? (half_t*)actA : nullptr, C, k0, s0, Ls[1], lens0);
+        SVC_CHECK_HIP(hipGetLastError());
+    } else {
         const int blocks = std::min(cdiv(Ls[1], 4), 2048);
         hipLaunchKernelGGL(wv_conv0_kernel, dim3(blocks, G), dim3(256), (size_t)cfg.conv_kernel[0] * C * 4, st, wnorm, stride, w0, b0, cg[0], cb[0],
                            f16 ? nullptr : (float*)actA, f16 ? (half_t*)actA : nullptr, C, cfg.conv_kernel[0], cfg.conv_stride[0], Ls[1],
@@ -397,9 +579,20 @@ int svc_w2v::features_group(const float* wnorm, long stride, int G, hipStream_t 
         p.n_taps = kl;
         for (int t = 0; t < kl; ++t) { p.a_ptr[t] = cur; p.a_ld[t] = C; p.a_ktiles[t] = C / ktile_elems(dt); p.a_shift[t] = t; }
         p.w = conv[l].w; p.ldw = conv[l].ldw; p.bias = conv[l].b;
+        const bool last = l == nc - 1;
+        if (group_norm) {       // conv, GELU (in the epilogue), no norm; the last one is followed by the feature projection's LayerNorm
+            p.act = KG_ACT_GELU;
+            if (last || !f16) { p.c32 = last ? raw : (float*)nxt; p.ldc32 = C; }
+            else { p.c16 = (half_t*)nxt; p.ldc16 = C; }
+            if (kgemm_launch(p, dt, KG_EPI_STORE, st)) return 1;
+            if (last && rownorm_launch(0, raw, C, f16 ? nullptr : (float*)nxt, f16 ? (half_t*)nxt : nullptr, C, pg, pb, nullptr, nullptr,
+                                       (long)G * Ls[l + 1], C, 1e-5f, dlens + (l + 1) * MAX_WIN, Ls[l + 1], st))
+                return 1;
+            std::swap(cur, nxt);
+            continue;
+        }
         p.c32 = raw; p.ldc32 = C;
         if (kgemm_launch(p, dt, KG_EPI_STORE, st)) return 1;
-        const bool last = l == nc - 1;
         if (rownorm_launch(last ? 2 : 1, raw, C, f16 ? nullptr : (float*)nxt, f16 ? (half_t*)nxt : nullptr, C, cg[l], cb[l], pg, pb,
                            (long)G * Ls[l + 1], C, 1e-5f, dlens + (l + 1) * MAX_WIN, Ls[l + 1], st))
             return 1;
@@ -415,19 +608,28 @@ int svc_w2v::posconv_group(const float* h, const half_t* h16v, int G, int P, flo
     const int* lens = dlens + cfg.n_conv * MAX_WIN;
     if (dt == 0) {
         const int n_tiles = cdiv(P, WV_PC_BM);
-        hipLaunchKernelGGL(w2v_posconv_kernel, dim3((unsigned)(n_tiles * G * NG)), dim3(256), 0, st, h16v, h, pos16, posb, out, lens, P, D, k, G, n_tiles);
+        const auto kernel = pos_w == 64 ? w2v_posconv_kernel<64> : pos_w == 48 ? w2v_posconv_kernel<48> : pos_w == 32 ? w2v_posconv_kernel<32> : w2v_posconv_kernel<16>;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)(n_tiles * G * NG)), dim3(256), 0, st, h16v, h, pos16, posb, out, lens, P, D, k, G, n_tiles);
         SVC_CHECK_HIP(hipGetLastError());
         return 0;
+    }
+    const int wd = pos_w;
+    const float* a = h;                                      // groups of 64 channels are read in place; narrower ones from their padded copy
+    long lda = D;
+    if (wd < 64) {
+        hipLaunchKernelGGL(wv_padgroups_kernel, dim3(P, G), dim3(256), 0, st, h, hpad, lens, P, D, wd);
+        SVC_CHECK_HIP(hipGetLastError());
+        a = hpad; lda = (long)NG * 64;
     }
     for (int g = 0; g < NG; ++g)
         for (int t0 = 0; t0 < k; t0 += KG_MAX_TAPS) {
             const int nt = std::min(KG_MAX_TAPS, k - t0);
-            KGemmParams p = kgemm_rows((long)G * P, 64, P);
+            KGemmParams p = kgemm_rows((long)G * P, wd, P);
             p.seq_len = lens; p.pad_mode = KG_PAD_ZERO; p.n_taps = nt;
-            for (int t = 0; t < nt; ++t) { p.a_ptr[t] = h + g * 64; p.a_ld[t] = D; p.a_ktiles[t] = 2; p.a_shift[t] = t0 + t - k / 2; }
-            p.w = pos32 + (long)g * 64 * k * 64 + (long)t0 * 64; p.ldw = (long)k * 64;
-            p.c32 = acc32 + g * 64; p.ldc32 = D;
-            if (t0) { p.res = acc32 + g * 64; p.ldres = D; }
+            for (int t = 0; t < nt; ++t) { p.a_ptr[t] = a + g * 64; p.a_ld[t] = lda; p.a_ktiles[t] = 2; p.a_shift[t] = t0 + t - k / 2; }
+            p.w = pos32 + (long)g * wd * k * 64 + (long)t0 * 64; p.ldw = (long)k * 64;
+            p.c32 = acc32 + g * wd; p.ldc32 = D;
+            if (t0) { p.res = acc32 + g * wd; p.ldres = D; }
             if (kgemm_launch(p, 1, KG_EPI_STORE, st)) return 1;
         }
     hipLaunchKernelGGL(wv_posadd_kernel, dim3(P, G), dim3(256), 0, st, h, (const float*)acc32, posb, out, lens, P, D);
@@ -443,20 +645,42 @@ int svc_w2v::encode_group(const float* h, const half_t* h16v, int G, int P, floa
     return tm.mark(3, st);
 }
 
-int svc::w2v_create(const svc_w2v_config_t* cfg, const svc_tensor_desc_t* weights, int n_weights, void* stream, bool final_ln, svc_w2v_t** out) {
+int svc::w2v_create(const svc_w2v_config_t* cfg, const svc_w2v_ext_t* ext, const svc_tensor_desc_t* weights, int n_weights, void* stream, bool final_ln,
+                    svc_w2v_t** out) {
     SVC_REQUIRE(cfg && weights && out, "svc_w2v_create: null argument");
-    SVC_REQUIRE(cfg->feat_extract_norm_layer == 1 && cfg->do_stable_layer_norm == 1 && cfg->conv_bias == 1,
-                "svc_w2v_create: only feat_extract_norm = \"layer\" with do_stable_layer_norm and conv_bias is supported (group-norm extractors and "
-                "post-LN encoders are refused)");
+    if (!ext)
+        SVC_REQUIRE(cfg->feat_extract_norm_layer == 1 && cfg->do_stable_layer_norm == 1 && cfg->conv_bias == 1,
+                    "svc_w2v_create: only feat_extract_norm = \"layer\" with do_stable_layer_norm and conv_bias is supported (group-norm extractors and "
+                    "post-LN encoders are refused)");
+    else {
+        const int fl = cfg->feat_extract_norm_layer, sl = cfg->do_stable_layer_norm;
+        SVC_REQUIRE((fl == 0 || fl == 1) && (sl == 0 || sl == 1) && (cfg->conv_bias == 0 || cfg->conv_bias == 1),
+                    "svc_w2v_create_ex: feat_extract_norm_layer, do_stable_layer_norm and conv_bias must each be 0 or 1");
+        SVC_REQUIRE(!(fl == 0 && sl == 1), "svc_w2v_create_ex: feat_extract_norm = \"group\" with do_stable_layer_norm is a mixed form no released model "
+                                           "has (the group-norm extractor goes with the post-LN encoder)");
+        SVC_REQUIRE(!(fl == 1 && sl == 0), "svc_w2v_create_ex: feat_extract_norm = \"layer\" without do_stable_layer_norm is a mixed form no released "
+                                           "model has (the layer-norm extractor goes with the stable-layer-norm encoder)");
+        SVC_REQUIRE(ext->do_normalize == 0 || ext->do_normalize == 1, "svc_w2v_create_ex: do_normalize must be 0 or 1");
+        SVC_REQUIRE(ext->feat_proj_layer_norm == 1, "svc_w2v_create_ex: feat_proj_layer_norm must be 1 (a feature projection without its LayerNorm is not "
+                                                    "supported)");
+        SVC_REQUIRE(final_ln || sl == 1, "svc_w2v_create_ex: the post-LN encoder cannot run without encoder.layer_norm");
+    }
     if (wv_check_cfg(cfg, "svc_w2v_create")) return 1;
+    SVC_REQUIRE(cfg->feat_extract_norm_layer == 1 || cfg->conv_kernel[0] <= WV_GN_MAXK,
+                "svc_w2v_create_ex: a group-norm extractor needs conv_kernel[0] <= 16 (its statistics hold every pair of taps)");
     SVC_REQUIRE(cfg->conv_dim >= 64 && cfg->conv_dim % 64 == 0 && cfg->conv_dim <= 512, "svc_w2v_create: conv_dim must be a multiple of 64, at most 512");
     SVC_REQUIRE(cfg->d_model >= 64 && cfg->d_model % 64 == 0 && cfg->d_model <= 2048 && cfg->n_heads >= 1 && cfg->n_heads * 64 == cfg->d_model,
                 "svc_w2v_create: d_model must be a multiple of 64 (at most 2048) and the head dimension 64 (n_heads * 64 == d_model)");
     SVC_REQUIRE(cfg->n_layers >= 1 && cfg->ffn_dim >= 64 && cfg->ffn_dim % 64 == 0, "svc_w2v_create: n_layers >= 1, ffn_dim a multiple of 64");
     SVC_REQUIRE(cfg->pos_k >= 2 && cfg->pos_k % 2 == 0 && cfg->pos_k <= WV_PC_MAXK, "svc_w2v_create: num_conv_pos_embeddings must be even, 2 .. 128");
-    SVC_REQUIRE(cfg->pos_groups >= 1 && cfg->pos_groups * 64 == cfg->d_model, "svc_w2v_create: the positional conv needs groups of 64 channels");
+    if (!ext) SVC_REQUIRE(cfg->pos_groups >= 1 && cfg->pos_groups * 64 == cfg->d_model, "svc_w2v_create: the positional conv needs groups of 64 channels");
+    else
+        SVC_REQUIRE(cfg->pos_groups >= 1 && cfg->d_model % cfg->pos_groups == 0 && (cfg->d_model / cfg->pos_groups) % 16 == 0 &&
+                        cfg->d_model / cfg->pos_groups <= 64,
+                    "svc_w2v_create_ex: the positional conv needs groups of 16, 32, 48 or 64 channels (d_model / pos_groups a multiple of 16, at most 64)");
     SVC_REQUIRE(cfg->precision == 0 || cfg->precision == 1, "svc_w2v_create: precision 0 (fp32 GEMMs) or 1 (fp16 GEMMs)");
     const char* who = "svc_w2v_create";
+    const long pos_w = cfg->d_model / cfg->pos_groups;
     StateDict sd(weights, n_weights);
     std::string pre;
     for (const char* p : {"", "wav2vec2.", "hubert.", "model."})
@@ -466,22 +690,26 @@ int svc::w2v_create(const svc_w2v_config_t* cfg, const svc_tensor_desc_t* weight
     {
         const std::string pc = pre + "encoder.pos_conv_embed.conv.";
         const long D = cfg->d_model, k = cfg->pos_k;
-        if (sd.has(pc + "weight")) { if (require_shape(sd.get(pc + "weight"), pc + "weight", {D, 64, k}, who)) return 1; }
+        if (sd.has(pc + "weight")) { if (require_shape(sd.get(pc + "weight"), pc + "weight", {D, pos_w, k}, who)) return 1; }
         else if (sd.has(pc + "parametrizations.weight.original1")) {
             if (require_shape(sd.get(pc + "parametrizations.weight.original0"), pc + "parametrizations.weight.original0", {1, 1, k}, who) ||
-                require_shape(sd.get(pc + "parametrizations.weight.original1"), pc + "parametrizations.weight.original1", {D, 64, k}, who))
+                require_shape(sd.get(pc + "parametrizations.weight.original1"), pc + "parametrizations.weight.original1", {D, pos_w, k}, who))
                 return 1;
-        } else if (require_shape(sd.get(pc + "weight_g"), pc + "weight_g", {1, 1, k}, who) || require_shape(sd.get(pc + "weight_v"), pc + "weight_v", {D, 64, k}, who))
+        } else if (require_shape(sd.get(pc + "weight_g"), pc + "weight_g", {1, 1, k}, who) || require_shape(sd.get(pc + "weight_v"), pc + "weight_v", {D, pos_w, k}, who))
             return 1;
     }
     hipStream_t st = (hipStream_t)stream;
     auto* m = new svc_w2v();
     m->cfg = *cfg;
     m->dt = cfg->precision ? 0 : 1;
+    m->group_norm = cfg->feat_extract_norm_layer == 0;
+    m->do_normalize = !ext || ext->do_normalize == 1;
+    m->pos_w = (int)pos_w;
     // the attention's query-tile form, from the configuration alone: what a group of four full windows would get from the grid-size rule
     const long Pw = wv_frames(*cfg, cfg->window_samples);
     m->stack.dt = m->dt; m->stack.D = cfg->d_model; m->stack.F = cfg->ffn_dim; m->stack.H = cfg->n_heads;
     m->stack.final_ln = final_ln;
+    m->stack.post_ln = cfg->do_stable_layer_norm == 0;
     m->stack.qt_form = (long)cdiv(Pw, 128) * cfg->n_heads * 4 <= 256 ? 1 : 2;
     if (m->pack(sd, pre, st)) { delete m; return 1; }
     *out = m;
@@ -491,7 +719,12 @@ int svc::w2v_create(const svc_w2v_config_t* cfg, const svc_tensor_desc_t* weight
 extern "C" {
 
 int svc_w2v_create(const svc_w2v_config_t* cfg, const svc_tensor_desc_t* weights, int n_weights, void* stream, svc_w2v_t** out) {
-    return w2v_create(cfg, weights, n_weights, stream, true, out);
+    return w2v_create(cfg, nullptr, weights, n_weights, stream, true, out);
+}
+
+int svc_w2v_create_ex(const svc_w2v_config_t* cfg, const svc_w2v_ext_t* ext, const svc_tensor_desc_t* weights, int n_weights, void* stream,
+                      svc_w2v_t** out) {
+    return w2v_create(cfg, ext, weights, n_weights, stream, true, out);
 }
 
 void svc_w2v_destroy(svc_w2v_t* m) { delete m; }

@@ -632,16 +632,39 @@ def wav2vec2_config(**overrides):
     return cfg
 
 
+# facebook/hubert-base-ls960 / facebook/wav2vec2-base (and chinese-hubert-base, ContentVec): the base family: a group norm
+# after conv 0 only, no conv biases, post-LN encoder, positional-conv groups of 768 / 16 = 48 channels
+W2V_BASE_PRESET = dict(conv_dim=512, conv_kernel=(10, 3, 3, 3, 3, 2, 2), conv_stride=(5, 2, 2, 2, 2, 2, 2), d_model=768, n_heads=12, n_layers=12,
+                       ffn_dim=3072, pos_k=128, pos_groups=16, feat_extract_norm="group", do_stable_layer_norm=False, conv_bias=False,
+                       window_samples=480000)
+
+
+def wav2vec2_base_config(**overrides):
+    cfg = deepcopy(W2V_BASE_PRESET)
+    cfg.update(overrides)
+    return cfg
+
+
+def wav2vec2_is_base(c):
+    """True for the group-norm / post-LN family"""
+    return c.get("feat_extract_norm", "layer") == "group" or not c.get("do_stable_layer_norm", True)
+
+
 def wav2vec2_state_spec(c):
-    """State dict of `Wav2Vec2Model` (layer-norm extractor, stable layer norm), in torch's registration order; `HubertModel` has the
-    same keys."""
+    """State dict of `Wav2Vec2Model` in torch's registration order; `HubertModel` has the same keys.  Family-aware: with
+    feat_extract_norm = "group" only conv 0 has a norm (a GroupNorm, registered as `layer_norm`), and without conv_bias there are no
+    `conv.bias` keys.  The encoder's keys are the same in the pre-LN and the post-LN order."""
     s = OrderedDict()
     D, F, C, k = c["d_model"], c["ffn_dim"], c["conv_dim"], c["pos_k"]
+    group, bias = c.get("feat_extract_norm", "layer") == "group", bool(c.get("conv_bias", True))
     s["masked_spec_embed"] = (D,)
     for l, kl in enumerate(c["conv_kernel"]):
         p = f"feature_extractor.conv_layers.{l}."
-        s[p + "conv.weight"], s[p + "conv.bias"] = (C, C if l else 1, kl), (C,)
-        s[p + "layer_norm.weight"], s[p + "layer_norm.bias"] = (C,), (C,)
+        s[p + "conv.weight"] = (C, C if l else 1, kl)
+        if bias:
+            s[p + "conv.bias"] = (C,)
+        if not group or l == 0:
+            s[p + "layer_norm.weight"], s[p + "layer_norm.bias"] = (C,), (C,)
     s["feature_projection.layer_norm.weight"], s["feature_projection.layer_norm.bias"] = (C,), (C,)
     s["feature_projection.projection.weight"], s["feature_projection.projection.bias"] = (D, C), (D,)
     s["encoder.pos_conv_embed.conv.bias"] = (D,)

@@ -5,6 +5,10 @@ samples at 16 kHz in, (1, frames(L), 1024) content features out (`Wav2Vec2Featur
 facebook/wav2vec2-xls-r-300m + `encoder.layer_norm`).  `content_batch` is the same for up to 64 clips of any length in one call,
 with the drivers' loop over 30 s windows (5 s overlap) done on the device; `normalize`, `features`, `posconv` and `encode` expose
 the stages.  The state dict is `Wav2Vec2Model.state_dict()`; `HubertModel.state_dict()` of the same shape loads unchanged.
+
+A cfg of the base family (`specs.wav2vec2_base_config()`: facebook/hubert-base-ls960, facebook/wav2vec2-base and their fine-tunes:
+feat_extract_norm "group", do_stable_layer_norm False, 768 / 16 = 48 channels per positional-conv group) or one that names
+`do_normalize` is created through svc_w2v_create_ex; everything else here serves both families.
 """
 import ctypes as C
 
@@ -32,6 +36,17 @@ def c_config(cfg, precision=1):
     return c
 
 
+def c_ext(cfg):
+    """The second argument of svc_w2v_create_ex for a cfg of the base family (group-norm extractor, post-LN encoder) or one that names
+    `do_normalize`; None for every other cfg, which goes through svc_w2v_create as it always did."""
+    if not (specs.wav2vec2_is_base(cfg) or "do_normalize" in cfg):
+        return None
+    e = _lib.W2vExt()
+    e.do_normalize = int(bool(cfg.get("do_normalize", True)))
+    e.feat_proj_layer_norm = int(bool(cfg.get("feat_proj_layer_norm", True)))
+    return e
+
+
 def frames(cfg, n):
     """rows the extractor yields for n samples in one piece: (n - k) // s + 1 through every conv"""
     n = int(n)
@@ -57,7 +72,11 @@ class Wav2Vec2Content(ContentEncoder):
         self._h = C.c_void_p()
         with torch.cuda.device(self.device):
             descs, n, keep = _lib.make_descs(state_dict, self.device)
-            _lib.check(_lib.lib().svc_w2v_create(C.byref(self._c), descs, n, _lib.stream_ptr(), C.byref(self._h)))
+            ext = c_ext(self.cfg)
+            if ext is None:
+                _lib.check(_lib.lib().svc_w2v_create(C.byref(self._c), descs, n, _lib.stream_ptr(), C.byref(self._h)))
+            else:
+                _lib.check(_lib.lib().svc_w2v_create_ex(C.byref(self._c), C.byref(ext), descs, n, _lib.stream_ptr(), C.byref(self._h)))
             torch.cuda.current_stream().synchronize()
         del keep
 
