@@ -1384,6 +1384,55 @@ int svc_op_gemm_bench(int M, int N, int K, int dtype, int epi, int iters, int de
  * two tile-form overrides on the same pseudo-random operands; *n_diff = 32-bit output words that differ (every tile form keeps
  * the k order of each output element, so 0 is the contract). */
 int svc_op_gemm_forms_diff(int M, int N, int K, int epi, int debug_a, int debug_b, long long* n_diff, void* stream);
+/* Test aid (tests/test_gpu_kgemm.py; no model uses it): ONE kgemm_launch (csrc/kgemm.hip) on caller-supplied operands.  The call
+ * checks every row the launch can address, packs A and W to the dtype (0 fp16, 1 fp32), launches once and synchronises; nothing
+ * else runs between packing and readback.  Device pointers unless noted; NULL = absent.
+ *   a_src[i]  fp32 [a_rows[i]][a_K[i]], i < n_src <= 4: the source buffers; packed to [a_rows][a_K rounded up to the k-tile] (zeros)
+ *   taps      tap t < n_taps <= 48 reads source tap_src[t] at row shift tap_shift[t]; tap_K[t] must equal the source's K
+ *   w         fp32 [w_rows][sum of tap_K]: w_rows = N rounded up to 256, the caller fills the rows at and above N (finite);
+ *             packed tap by tap, each tap's K padded with zeros to the k-tile
+ *   row map   m = s Lout + pos < M reads source row (a_seq_map ? a_seq_map[s] : s) a_seq_rows + a_off + pad(pos a_stride + shift)
+ *             with pad over [0, seq_len ? seq_len[s] : a_len) by pad_mode / reflect_min as KGemmParams states; seq_len and
+ *             a_seq_map are HOST arrays of ceil(M / Lout) entries.  Output row s c_seq_rows + c_off + pos.
+ *   outputs   c32 fp32, c16 and c16_lo 16-bit words, res and res2 fp32: all [c_rows][ldc]; res / res2 may equal c32.
+ *             vt [ceil(M / Lout)][rope_D][vt_ld] 16-bit words; rope fp32 [rope_rows][32][2].
+ *   vectors   bias [N], rowvec / gate [nseq][ld] (ld 0: one row), post_a / post_ib [post_n]: sizes are the caller's to keep
+ *   epi       KG_EPI_* 0 store, 1 SwiGLU, 2 tanh-sigmoid, 3 QKV + RoPE; form: launch_wide's tile-form bits (0 = its own choice)
+ * Refused (nothing allocated or launched): NULL args, w or an output the epilogue needs; dtype outside 0 .. 1; n_src outside
+ * 1 .. 4, n_taps outside 1 .. 48, a tap's source outside [0, n_src) or K other than its source's; M, N, Lout < 1, a_stride < 1,
+ * pad_mode outside 0 .. 2; a sequence length < 0, or 0 under KG_PAD_CLAMP; an a_seq_map entry < 0; ANY (m, tap) whose source row
+ * lies outside [0, a_rows) of its buffer; c_off < 0, c_off + Lout > c_seq_rows, nseq c_seq_rows > c_rows, ldc below the written
+ * width; QKV: rope_rows < Lout, vt_ld < Lout rounded up to 32 or not a multiple of 4, vt_mode outside 0 .. 2; vec_ok or a
+ * paired / QKV epilogue with N, ldc (a multiple of 8) or a pointer that breaks 16-byte access; form bits outside 0xF0; and
+ * whatever kgemm_launch refuses.  check_only != 0: return 0 once every check has passed, before the first allocation (no device
+ * is touched and no pointer is dereferenced, so the host tests can show an argument set to be acceptable without a GPU). */
+typedef struct {
+    int32_t dtype, epi, form;
+    int32_t n_src;
+    const float* a_src[4]; int64_t a_rows[4]; int32_t a_K[4];
+    int32_t n_taps;
+    int32_t tap_src[48]; int32_t tap_shift[48]; int32_t tap_K[48];
+    const float* w; int64_t w_rows;
+    int32_t M, N, Lout, a_seq_rows, a_off, a_stride, a_len, pad_mode, reflect_min;
+    const int32_t* seq_len; const int32_t* a_seq_map;
+    int32_t c_seq_rows, c_off;
+    int64_t c_rows, ldc;
+    float* c32; uint16_t* c16; uint16_t* c16_lo;
+    const float* bias;
+    const float* rowvec; int64_t ld_rowvec;
+    const float* gate; int64_t ld_gate;
+    const float* res; const float* res2;
+    const float* post_a; const float* post_ib; int32_t post_n;
+    float out_scale; int32_t act; float act_slope; int32_t post_relu, vec_ok;
+    const float* rope; int32_t rope_rows, rope_D; float q_scale;
+    uint16_t* vt; int64_t vt_ld; int32_t vt_mode;
+    int32_t check_only;
+} svc_kgemm_t;
+int svc_op_kgemm(const svc_kgemm_t* args, void* stream);
+/* Test aid (tests/test_gpu_kgemm.py; no model uses it): attention_permute_vt (csrc/attention.hip) on a caller's buffer: the in-place
+ * column permutation of a natural-order V^T buffer [rows][vt_ld] (16-bit words, device) into order `mode` (vt_pos), as
+ * svc_op_attention applies it; synchronises.  Refused: NULL vt, rows < 1, vt_ld < 32 or not a multiple of 32, mode outside 0 .. 2. */
+int svc_op_permute_vt(uint16_t* vt, int64_t rows, int64_t vt_ld, int mode, void* stream);
 
 /* Optional launch timing: HIP events around every tap-GEMM / attention launch on its stream.
  * svc_prof_collect fills out[cls*4 + {0..3}] = {launches, total ms, algorithmic flops, algorithmic bytes}

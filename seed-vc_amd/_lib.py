@@ -47,7 +47,7 @@ EXPORTS = [
     "svc_prof_enable", "svc_prof_collect",
     "svc_op_linear", "svc_op_conv1d", "svc_op_conv1d_ex", "svc_op_conv1d_last_took", "svc_op_dit_panel", "svc_op_conv_transpose1d", "svc_op_attention", "svc_op_attention_ex", "svc_op_rmsnorm",
     "svc_op_layernorm", "svc_op_layernorm_gelu", "svc_op_act_cl", "svc_op_hift_signal", "svc_op_ar_sampler",
-    "svc_op_ar_attn", "svc_op_ar_linear",
+    "svc_op_ar_attn", "svc_op_ar_linear", "svc_op_kgemm", "svc_op_permute_vt",
 ]
 
 
@@ -229,6 +229,21 @@ class ArLinear(C.Structure):
                [(n, C.POINTER(C.c_int32)) for n in ("slots", "pos")]
 
 
+class KGemm(C.Structure):
+    """svc_kgemm_t: the arguments of svc_op_kgemm (test aid)."""
+    _fields_ = [(n, C.c_int32) for n in ("dtype", "epi", "form", "n_src")] + \
+               [("a_src", C.c_void_p * 4), ("a_rows", C.c_int64 * 4), ("a_K", C.c_int32 * 4), ("n_taps", C.c_int32),
+                ("tap_src", C.c_int32 * 48), ("tap_shift", C.c_int32 * 48), ("tap_K", C.c_int32 * 48), ("w", C.c_void_p), ("w_rows", C.c_int64)] + \
+               [(n, C.c_int32) for n in ("M", "N", "Lout", "a_seq_rows", "a_off", "a_stride", "a_len", "pad_mode", "reflect_min")] + \
+               [("seq_len", C.POINTER(C.c_int32)), ("a_seq_map", C.POINTER(C.c_int32)), ("c_seq_rows", C.c_int32), ("c_off", C.c_int32),
+                ("c_rows", C.c_int64), ("ldc", C.c_int64), ("c32", C.c_void_p), ("c16", C.c_void_p), ("c16_lo", C.c_void_p),
+                ("bias", C.c_void_p), ("rowvec", C.c_void_p), ("ld_rowvec", C.c_int64), ("gate", C.c_void_p), ("ld_gate", C.c_int64),
+                ("res", C.c_void_p), ("res2", C.c_void_p), ("post_a", C.c_void_p), ("post_ib", C.c_void_p), ("post_n", C.c_int32),
+                ("out_scale", C.c_float), ("act", C.c_int32), ("act_slope", C.c_float), ("post_relu", C.c_int32), ("vec_ok", C.c_int32),
+                ("rope", C.c_void_p), ("rope_rows", C.c_int32), ("rope_D", C.c_int32), ("q_scale", C.c_float),
+                ("vt", C.c_void_p), ("vt_ld", C.c_int64), ("vt_mode", C.c_int32), ("check_only", C.c_int32)]
+
+
 _lib = None
 
 
@@ -297,6 +312,8 @@ def lib():
         l.svc_op_ar_sampler.argtypes = [C.POINTER(ArSampler), C.c_void_p]
         l.svc_op_ar_attn.argtypes = [C.POINTER(ArAttn), C.c_void_p]
         l.svc_op_ar_linear.argtypes = [C.POINTER(ArLinear), C.c_void_p]
+        l.svc_op_kgemm.argtypes = [C.POINTER(KGemm), C.c_void_p]
+        l.svc_op_permute_vt.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p]
         # seeded noise: 64-bit seeds by value and as HOST arrays
         l.svc_cfm_sample_seeded.argtypes = [C.c_void_p, C.POINTER(CfmArgs), C.POINTER(C.c_uint64), C.c_void_p]
         l.svc_cfm_noise_draws.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]

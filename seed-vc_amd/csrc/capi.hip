@@ -204,7 +204,8 @@ int svc_op_gemm_forms_diff(int M, int N, int K, int epi, int debug_a, int debug_
         memset(&p, 0, sizeof(p));
         p.M = M; p.N = N; p.Lout = L; p.a_seq_rows = L; p.c_seq_rows = L; p.a_stride = 1; p.a_len = L;
         p.n_taps = 1; p.a_ptr[0] = ap; p.a_ld[0] = Kp; p.a_ktiles[0] = (int)(Kp / 64);
-        p.w = wp; p.ldw = Kp; p.vec_ok = 1; p.debug = v ? debug_b : debug_a; p.bias = bias;
+        p.w = wp; p.ldw = Kp; p.vec_ok = 1; p.debug = v ? debug_b : debug_a;
+        if (epi != KG_EPI_QKV_ROPE) p.bias = bias;      // the QKV epilogue takes none (kgemm_launch refuses it)
         if (epi == KG_EPI_STORE) { p.c32 = c32[v]; p.ldc32 = N; p.res = res; p.ldres = N; p.c16 = c16[v]; p.ldc16 = N; }
         else if (epi == KG_EPI_QKV_ROPE) { p.c16 = c16[v]; p.ldc16 = 2 * (N / 3); p.rope = rope; p.rope_D = N / 3; p.q_scale = 0.125f;
                                            p.vt = vt[v]; p.vt_seq_stride = (long)(N / 3) * 896; p.vt_ld = 896; p.vt_mode = 1; }
@@ -218,6 +219,156 @@ int svc_op_gemm_forms_diff(int M, int N, int K, int epi, int debug_a, int debug_
     SVC_CHECK_HIP(hipMemcpyAsync(&h, cnt, 8, hipMemcpyDeviceToHost, st));
     SVC_CHECK_HIP(hipStreamSynchronize(st));
     *n_diff = (long long)h;
+    return 0;
+}
+
+// The tap-GEMM's row map on the host (kgemm_tile.h, KG_TAP_SETUP): the row of its sequence that (pos, shift) reads, or -1 where
+// the kernel takes the zero page instead.
+static long kgemm_host_row(long pos, int a_stride, int shift, long len, int pad_mode, int reflect_min) {
+    const long q0 = pos * a_stride + shift;
+    const bool oob = q0 < 0 || q0 >= len;
+    if (!oob) return q0;
+    if (pad_mode == KG_PAD_ZERO) return -1;
+    if (pad_mode == KG_PAD_CLAMP) return q0 < 0 ? 0 : len - 1;
+    const long lenx = len > reflect_min ? len : reflect_min;
+    const long q = q0 < 0 ? -q0 : (q0 >= lenx ? 2 * (lenx - 1) - q0 : q0);      // [len, lenx): a row of the zero extension
+    return (q < 0 || q >= len) ? -1 : q;
+}
+
+// One kgemm_launch on caller-supplied operands (tests/test_gpu_kgemm.py).  Every row the launch can address is checked on the
+// host first: the kernel itself checks nothing.
+int svc_op_kgemm(const svc_kgemm_t* e, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    SVC_REQUIRE(e, "svc_op_kgemm: null argument");
+    SVC_REQUIRE(e->dtype == 0 || e->dtype == 1, "svc_op_kgemm: dtype is 0 (fp16) or 1 (fp32)");
+    SVC_REQUIRE(e->epi >= KG_EPI_STORE && e->epi <= KG_EPI_QKV_ROPE, "svc_op_kgemm: epi is 0 .. 3");
+    SVC_REQUIRE((e->form & ~0xF0) == 0, "svc_op_kgemm: form holds launch_wide's bits 0xF0 only");
+    SVC_REQUIRE(e->n_src >= 1 && e->n_src <= 4, "svc_op_kgemm: n_src is 1 .. 4");
+    SVC_REQUIRE(e->n_taps >= 1 && e->n_taps <= KG_MAX_TAPS, "svc_op_kgemm: n_taps is 1 .. 48");
+    SVC_REQUIRE(e->M >= 1 && e->N >= 1 && e->Lout >= 1 && e->a_stride >= 1 && e->a_seq_rows >= 0 && e->a_off >= 0,
+                "svc_op_kgemm: M, N, Lout and a_stride are positive, a_seq_rows and a_off are not negative");
+    SVC_REQUIRE(e->pad_mode >= KG_PAD_ZERO && e->pad_mode <= KG_PAD_CLAMP && e->reflect_min >= 0, "svc_op_kgemm: pad_mode is 0 .. 2, reflect_min >= 0");
+    SVC_REQUIRE(e->w, "svc_op_kgemm: w is required");
+    for (int i = 0; i < e->n_src; ++i)
+        SVC_REQUIRE(e->a_src[i] && e->a_rows[i] >= 1 && e->a_K[i] >= 1, "svc_op_kgemm: every source has a buffer, rows and K");
+    long Ktot = 0;
+    for (int t = 0; t < e->n_taps; ++t) {
+        SVC_REQUIRE(e->tap_src[t] >= 0 && e->tap_src[t] < e->n_src, "svc_op_kgemm: a tap's source lies in [0, n_src)");
+        SVC_REQUIRE(e->tap_K[t] == e->a_K[e->tap_src[t]], "svc_op_kgemm: a tap's K is its source's K");
+        Ktot += e->tap_K[t];
+    }
+    const long nseq = (e->M + (long)e->Lout - 1) / e->Lout;
+    SVC_REQUIRE(e->w_rows == round_up(e->N, 256), "svc_op_kgemm: w has N rounded up to 256 rows");
+
+    // ---- the rows the launch reads: every (m, tap), as the kernel maps them
+    for (long s = 0; s < nseq; ++s) {
+        const long len = e->seq_len ? e->seq_len[s] : e->a_len;
+        SVC_REQUIRE(len >= 0, "svc_op_kgemm: a sequence length is negative");
+        SVC_REQUIRE(e->pad_mode != KG_PAD_CLAMP || len >= 1, "svc_op_kgemm: KG_PAD_CLAMP has no row to clamp to in a sequence of length 0");
+        const long smap = e->a_seq_map ? e->a_seq_map[s] : s;
+        SVC_REQUIRE(smap >= 0, "svc_op_kgemm: an a_seq_map entry is negative");
+        const long base = smap * e->a_seq_rows + e->a_off;
+        const long npos = std::min<long>(e->Lout, e->M - s * e->Lout);
+        for (int t = 0; t < e->n_taps; ++t) {
+            long lo = -1, hi = -1;
+            for (long pos = 0; pos < npos; ++pos) {
+                const long q = kgemm_host_row(pos, e->a_stride, e->tap_shift[t], len, e->pad_mode, e->reflect_min);
+                if (q < 0) continue;
+                lo = lo < 0 || q < lo ? q : lo;
+                hi = q > hi ? q : hi;
+            }
+            SVC_REQUIRE(hi < 0 || (base + lo >= 0 && base + hi < e->a_rows[e->tap_src[t]]),
+                        "svc_op_kgemm: a source row addressed by the row map lies outside its buffer");
+        }
+    }
+    // ---- the rows and columns it writes
+    const bool paired = e->epi == KG_EPI_SWIGLU || e->epi == KG_EPI_TANHSIG, qkv = e->epi == KG_EPI_QKV_ROPE;
+    const long width = paired ? e->N / 2 : (qkv ? 2L * e->rope_D : e->N);
+    SVC_REQUIRE(e->c32 || e->c16, "svc_op_kgemm: an output (c32 or c16) is required");
+    SVC_REQUIRE(!e->c16_lo || (e->post_a && e->post_ib), "svc_op_kgemm: c16_lo is an output of the Snake (post_a, post_ib)");
+    SVC_REQUIRE(!e->post_a == !e->post_ib && e->post_n >= 0, "svc_op_kgemm: post_a and post_ib come together, post_n >= 0");
+    SVC_REQUIRE(e->c_off >= 0 && e->c_off + (long)e->Lout <= e->c_seq_rows && nseq * e->c_seq_rows <= e->c_rows,
+                "svc_op_kgemm: output rows: c_off + Lout <= c_seq_rows, nseq c_seq_rows <= c_rows");
+    SVC_REQUIRE(e->ldc >= width && width >= 1, "svc_op_kgemm: ldc covers the written width");
+    SVC_REQUIRE(e->ld_rowvec >= 0 && e->ld_gate >= 0, "svc_op_kgemm: ld_rowvec and ld_gate are not negative");
+    if (e->vec_ok || paired || qkv) {
+        auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+        SVC_REQUIRE(e->N % 8 == 0 && e->ldc % 8 == 0, "svc_op_kgemm: 16-byte access needs N and ldc to be multiples of 8");
+        SVC_REQUIRE(al16(e->c32) && al16(e->c16) && al16(e->c16_lo) && al16(e->res) && al16(e->res2) && al16(e->bias) && al16(e->rope) && al16(e->vt),
+                    "svc_op_kgemm: 16-byte access needs 16-byte aligned c32, c16, c16_lo, res, res2, bias, rope and vt");
+    }
+    if (qkv) {
+        SVC_REQUIRE(e->rope && e->vt && e->rope_D >= 1, "svc_op_kgemm: QKV_ROPE needs rope, vt and rope_D");
+        SVC_REQUIRE(e->rope_rows >= e->Lout, "svc_op_kgemm: rope has a row for every position below Lout");
+        SVC_REQUIRE(e->vt_mode >= 0 && e->vt_mode <= 2 && e->vt_ld % 4 == 0 && e->vt_ld >= round_up(e->Lout, 32),
+                    "svc_op_kgemm: vt_mode is 0 .. 2, vt_ld a multiple of 4 that covers Lout rounded up to 32 (vt_pos permutes inside 32)");
+    }
+
+    KGemmParams p;
+    memset(&p, 0, sizeof(p));
+    const int kt = ktile_elems(e->dtype);
+    p.n_taps = e->n_taps;
+    p.Lout = e->Lout; p.a_seq_rows = e->a_seq_rows; p.a_off = e->a_off; p.a_stride = e->a_stride; p.a_len = e->a_len;
+    p.pad_mode = e->pad_mode; p.reflect_min = e->reflect_min; p.debug = e->form;
+    p.M = e->M; p.N = e->N; p.c_seq_rows = e->c_seq_rows; p.c_off = e->c_off;
+    p.c32 = e->c32; p.ldc32 = e->ldc; p.c16 = (half_t*)e->c16; p.c16_lo = (half_t*)e->c16_lo; p.ldc16 = e->ldc;
+    p.post_a = e->post_a; p.post_ib = e->post_ib; p.post_n = e->post_n;
+    p.bias = e->bias; p.rowvec = e->rowvec; p.ld_rowvec = e->ld_rowvec; p.gate = e->gate; p.ld_gate = e->ld_gate;
+    p.res = e->res; p.ldres = e->ldc; p.res2 = e->res2; p.ldres2 = e->ldc;
+    p.out_scale = e->out_scale; p.act = e->act; p.act_slope = e->act_slope; p.post_relu = e->post_relu; p.vec_ok = e->vec_ok;
+    p.rope = e->rope; p.rope_D = e->rope_D; p.q_scale = e->q_scale;
+    p.vt = (half_t*)e->vt; p.vt_ld = e->vt_ld; p.vt_seq_stride = (long)e->rope_D * e->vt_ld; p.vt_mode = e->vt_mode;
+    if (kgemm_check(p, e->epi)) return 1;      // the launch's own refusals, ahead of the first allocation
+    SVC_REQUIRE(e->dtype == 0 || e->epi == KG_EPI_STORE || e->epi == KG_EPI_TANHSIG, "svc_op_kgemm: fp32 operands: STORE and TANHSIG only");
+    if (e->check_only) return 0;               // every check has passed; nothing is allocated, packed or launched
+
+    Scratch s;
+    void* src[4];
+    long src_ld[4];
+    for (int i = 0; i < e->n_src; ++i) {
+        src_ld[i] = round_up(e->a_K[i], kt);
+        src[i] = s.ar.alloc((size_t)e->a_rows[i] * src_ld[i] * esize(e->dtype), st);
+        if (!src[i]) return 1;
+        if (pack_any(e->dtype, e->a_src[i], src[i], 0, (int)e->a_rows[i], 1, e->a_K[i], e->a_K[i], 0, 1, src_ld[i], 0, 1, nullptr, st)) return 1;
+    }
+    long Kp = 0;
+    for (int t = 0; t < e->n_taps; ++t) Kp += round_up(e->tap_K[t], kt);
+    void* wp = s.ar.alloc((size_t)e->w_rows * Kp * esize(e->dtype), st);
+    if (!wp) return 1;
+    long k_in = 0, k_out = 0;
+    for (int t = 0; t < e->n_taps; ++t) {
+        const int i = e->tap_src[t];
+        p.a_ptr[t] = src[i]; p.a_ld[t] = src_ld[i]; p.a_shift[t] = e->tap_shift[t];
+        p.a_ktiles[t] = (int)(src_ld[i] * (long)esize(e->dtype) / 128);
+        if (pack_any(e->dtype, e->w + k_in, wp, k_out, (int)e->w_rows, 1, e->tap_K[t], Ktot, 0, 1, Kp, 0, 1, nullptr, st)) return 1;
+        k_in += e->tap_K[t];
+        k_out += src_ld[i];
+    }
+    p.w = wp; p.ldw = Kp;
+    if (e->seq_len || e->a_seq_map) {
+        int* d = s.ar.alloc_n<int>((size_t)2 * nseq, st);
+        if (!d) return 1;
+        std::vector<int> h((size_t)2 * nseq, 0);
+        for (long i = 0; i < nseq; ++i) {
+            if (e->seq_len) h[i] = e->seq_len[i];
+            if (e->a_seq_map) h[nseq + i] = e->a_seq_map[i];
+        }
+        SVC_CHECK_HIP(hipMemcpyAsync(d, h.data(), h.size() * 4, hipMemcpyHostToDevice, st));
+        SVC_CHECK_HIP(hipStreamSynchronize(st));            // `h` leaves scope below
+        if (e->seq_len) p.seq_len = d;
+        if (e->a_seq_map) p.a_seq_map = d + nseq;
+    }
+    if (kgemm_launch(p, e->dtype, e->epi, st)) return 1;
+    SVC_CHECK_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
+int svc_op_permute_vt(uint16_t* vt, int64_t rows, int64_t vt_ld, int mode, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    SVC_REQUIRE(vt && rows >= 1 && vt_ld >= 32 && vt_ld % 32 == 0 && mode >= 0 && mode <= 2,
+                "svc_op_permute_vt: vt [rows >= 1][vt_ld a positive multiple of 32], mode 0 .. 2");
+    if (attention_permute_vt(reinterpret_cast<half_t*>(vt), rows, vt_ld, mode, st)) return 1;
+    SVC_CHECK_HIP(hipStreamSynchronize(st));
     return 0;
 }
 

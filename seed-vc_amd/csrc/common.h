@@ -196,6 +196,8 @@ struct KGemmParams {
 };
 
 int kgemm_launch(const KGemmParams& p, int dtype /*0=f16,1=f32*/, int epi, hipStream_t st);
+// the argument checks of kgemm_launch alone (no device needed): 0 = the launch would accept p
+int kgemm_check(const KGemmParams& p, int epi);
 // 256 x 256 tiles (kgemm_big.hip), fp16 only, N % 256 == 0: tuning-harness form 0x90 of the launch (not a default)
 int kgemm_big_launch(const KGemmParams& p, int epi, hipStream_t st);
 

@@ -84,11 +84,37 @@ int launch_bn(const KGemmParams& p, hipStream_t st) {
 
 int kgemm_dispatch(const KGemmParams& p, int dtype, int epi, hipStream_t st);
 
-int kgemm_launch(const KGemmParams& p_in, int dtype, int epi, hipStream_t st) {
-    const KGemmParams& p0 = p_in;
+// What a launch refuses, before anything touches a device (svc_op_kgemm calls it ahead of its allocations).
+int kgemm_check(const KGemmParams& p0, int epi) {
     SVC_REQUIRE(p0.n_taps >= 1 && p0.n_taps <= KG_MAX_TAPS, "tap count");
     SVC_REQUIRE(p0.Lout > 0 && p0.M >= 0 && p0.N > 0, "shape");
     if (p0.M == 0) return 0;
+    if (epi == KG_EPI_SWIGLU || epi == KG_EPI_TANHSIG || epi == KG_EPI_QKV_ROPE) {
+        // The DIRECT epilogues (kgemm_tile.h) apply bias and rowvec and nothing else of the STORE chain, and they write whole lane
+        // groups: a field they would ignore, and a width they would overrun, are refused here.
+        SVC_REQUIRE(p0.act == KG_ACT_NONE && !p0.gate && !p0.res && !p0.res2 && p0.out_scale == 0.f && !p0.post_relu && !p0.post_a && !p0.c16_lo,
+                    "kgemm: SWIGLU / TANHSIG / QKV_ROPE ignore act, gate, res, res2, out_scale, post_relu and the Snake: leave them unset");
+        // A lane stores its CW = 4 TN consecutive columns (CW / 2 outputs of the paired epilogues) without a guard by the columns
+        // left in the row; only lanes whose FIRST column is outside are off (n >= N).  TN = WTN / 16 with WTN = 64 in every form
+        // launch_wide instantiates (128 x 128, 256 x 128 with 8 or 4 waves, 64 x 64 and 64 x 128 with 4 waves): CW = 16, N % 16 == 0.
+        // The 256 x 256 form (WTN = 128, CW = 32) is only taken with N % 256 == 0; otherwise the launch falls back to the others.
+        SVC_REQUIRE(p0.N % 16 == 0, "kgemm: SWIGLU / TANHSIG / QKV_ROPE store whole groups of 16 columns: N must be a multiple of 16");
+        if (epi == KG_EPI_QKV_ROPE) {
+            // the V block stores its accumulators as they are: a bias or rowvec would reach q and k only
+            SVC_REQUIRE(!p0.bias && !p0.rowvec, "kgemm: QKV_ROPE takes no bias and no rowvec (its V block would not apply them)");
+            SVC_REQUIRE(p0.c16 && p0.vt && p0.rope && !p0.c32, "kgemm: QKV_ROPE writes c16 (q | k) and vt from rope; it has no c32 output");
+            // V blocks are whole column tiles from 2 D on (BN = 64 or 128; 256 only with 2 D % 256 == 0, see launch_wide)
+            SVC_REQUIRE(p0.rope_D > 0 && p0.rope_D % 64 == 0 && p0.N == 3 * p0.rope_D, "kgemm: QKV_ROPE: N = 3 rope_D, rope_D a multiple of 64");
+        } else {
+            SVC_REQUIRE(p0.c16, "kgemm: SWIGLU / TANHSIG write c16 (c32 as well where given)");
+        }
+    }
+    return 0;
+}
+
+int kgemm_launch(const KGemmParams& p_in, int dtype, int epi, hipStream_t st) {
+    if (kgemm_check(p_in, epi)) return 1;
+    if (p_in.M == 0) return 0;
     DeviceState* ds = device_state();
     if (!ds) return 1;
     KGemmParams p = p_in;

@@ -605,6 +605,111 @@ def ar_linear(a, device="cuda:0", guard=2, fill32=-777.25, fill16=-777.0, w_pad=
     return out
 
 
+_KGEMM_INT = ("dtype", "epi", "form", "M", "N", "Lout", "a_seq_rows", "a_off", "a_stride", "a_len", "pad_mode", "reflect_min", "c_seq_rows",
+              "c_off", "post_n", "act", "post_relu", "vec_ok", "rope_D", "vt_mode", "check_only")
+_KGEMM_F32 = ("out_scale", "act_slope", "q_scale")
+
+
+def kgemm(a, device="cuda:0", guard=2, fill32=-777.25, fill16=0x6A5A, w_pad=0.5):
+    """Test aid over svc_op_kgemm (include/seedvc_hip.h): ONE kgemm_launch on unpacked fp32 operands.  `a` maps the scalars of
+    svc_kgemm_t to ints / floats, plus: src (list of up to 4 (rows, K) tensors), taps (list of (source index, shift)), W (N, sum
+    of the taps' K; packed into N rounded up to 256 rows, the others holding w_pad), bias (N,), rowvec and gate ((N,) = ld 0, or
+    (nseq, N)), res and res2 ((c_rows, ldc), or "c32": the output itself, which then starts as a["c_init"]), post_a and post_ib
+    (post_n,), rope (rows, 32, 2), seq_len and a_seq_map (lists), ldc, c_rows (default nseq * c_seq_rows), vt_ld, and want_c32 /
+    want_c16 / want_c16_lo.  Returns dict(c32 | c16 | c16_lo (guard + c_rows + guard, ldc), vt (guard + nseq rope_D + guard,
+    vt_ld), guard): the WHOLE device buffers, fp32 holding fill32 and the 16-bit ones (returned as float16) the bit pattern
+    fill16 wherever the launch did not write."""
+    import ctypes as C
+    dev = torch.device(device)
+    with torch.cuda.device(dev):
+        b = _ArOpBuffers(dev, guard, fill32, fill16)
+        e = _lib.KGemm()
+        for n in _KGEMM_INT:
+            setattr(e, n, int(a.get(n) or 0))
+        for n in _KGEMM_F32:
+            setattr(e, n, float(a.get(n) or 0.0))
+        src = a["src"]
+        assert 1 <= len(src) <= 4 and 1 <= len(a["taps"]) <= 48
+        e.n_src = len(src)
+        for i, t in enumerate(src[:4]):
+            assert t.dim() == 2 and t.dtype == torch.float32
+            e.a_src[i], e.a_rows[i], e.a_K[i] = b.put(t), t.shape[0], t.shape[1]
+        e.n_taps = len(a["taps"])
+        for t, (i, shift) in enumerate(a["taps"][:48]):
+            e.tap_src[t], e.tap_shift[t], e.tap_K[t] = int(i), int(shift), src[i].shape[1] if 0 <= i < len(src) else 0
+        W = a["W"]
+        assert W.dim() == 2 and W.shape[0] == e.N and W.dtype == torch.float32
+        # the entry point strides W by the sum of the taps' K and takes the vectors' sizes on trust: they are held here
+        assert W.shape[1] == sum(src[i].shape[1] for i, _ in a["taps"] if 0 <= i < len(src)), "W has the taps' K columns"
+        assert a.get("bias") is None or a["bias"].numel() >= e.N, "bias has N entries"
+        for n in ("post_a", "post_ib"):
+            assert a.get(n) is None or a[n].numel() >= e.post_n, n + " has post_n entries"
+        wbuf = torch.full(((e.N + 255) // 256 * 256, W.shape[1]), w_pad, dtype=torch.float32)
+        wbuf[:e.N] = W
+        e.w, e.w_rows = b.put(wbuf), wbuf.shape[0]
+        nseq = -(-e.M // max(e.Lout, 1))
+        host = []
+        for n in ("seq_len", "a_seq_map"):
+            if a.get(n) is not None:
+                assert len(a[n]) == nseq, n
+                host.append(_lib.i32_host([int(v) for v in a[n]]))
+                setattr(e, n, C.cast(host[-1], C.POINTER(C.c_int32)))
+        e.ldc = ldc = int(a["ldc"])
+        e.c_rows = c_rows = int(a.get("c_rows") or nseq * e.c_seq_rows)
+        for n in ("bias", "post_a", "post_ib"):
+            if a.get(n) is not None:
+                setattr(e, n, b.put(a[n]))
+        for n in ("rowvec", "gate"):
+            t = a.get(n)
+            if t is not None:
+                assert tuple(t.shape) in ((e.N,), (nseq, e.N)), n
+                setattr(e, n, b.put(t))
+                setattr(e, "ld_" + n, 0 if t.dim() == 1 else e.N)
+        out = {"guard": guard}
+
+        def plane():
+            t = torch.full((guard + c_rows + guard, ldc), fill16, dtype=torch.int16, device=dev).view(torch.float16)
+            b.keep.append(t)
+            return t, t.data_ptr() + guard * ldc * 2
+        if a.get("want_c32"):
+            init = a.get("c_init")
+            assert init is None or tuple(init.shape) == (c_rows, ldc)
+            out["c32"], e.c32 = b.guarded(c_rows, ldc, init=init)
+        if a.get("want_c16"):
+            out["c16"], e.c16 = plane()
+        if a.get("want_c16_lo"):
+            out["c16_lo"], e.c16_lo = plane()
+        for n in ("res", "res2"):
+            t = a.get(n)
+            if isinstance(t, str):
+                assert t == "c32" and a.get("want_c32") and a.get("c_init") is not None, n
+                setattr(e, n, e.c32)
+            elif t is not None:
+                assert tuple(t.shape) == (c_rows, ldc), n
+                setattr(e, n, b.put(t))
+        if a.get("rope") is not None:
+            assert tuple(a["rope"].shape[1:]) == (32, 2) and a["rope"].dtype == torch.float32
+            e.rope, e.rope_rows = b.put(a["rope"]), a["rope"].shape[0]
+        if e.epi == 3:
+            e.vt_ld = vt_ld = int(a["vt_ld"])
+            rows = nseq * e.rope_D
+            t = torch.full((guard + rows + guard, vt_ld), fill16, dtype=torch.int16, device=dev).view(torch.float16)
+            b.keep.append(t)
+            out["vt"], e.vt = t, t.data_ptr() + guard * vt_ld * 2
+        _lib.check(_lib.lib().svc_op_kgemm(C.byref(e), _lib.stream_ptr()))
+    return out
+
+
+def permute_vt(vt, mode):
+    """Test aid over svc_op_permute_vt: a copy of the natural-order V^T buffer vt (rows, vt_ld) fp16 on the device, its columns
+    permuted in place into order `mode` by attention_permute_vt."""
+    assert vt.is_cuda and vt.dtype == torch.float16 and vt.dim() == 2
+    out = vt.contiguous().clone()
+    with torch.cuda.device(vt.device):
+        _lib.check(_lib.lib().svc_op_permute_vt(out.data_ptr(), out.shape[0], out.shape[1], int(mode), _lib.stream_ptr()))
+    return out
+
+
 def rmsnorm(x, gamma, w=None, b=None, add_one=False):
     rows, D = x.shape
     dev = x.device
