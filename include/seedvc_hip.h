@@ -814,6 +814,29 @@ int svc_chunks_gather_cond(const float* prompt_cond, const int32_t* prompt_lens,
  * set, first[k] set exactly when last[k-1] is; out_len == sum(body); ov >= 0. */
 int svc_chunks_assemble(const float* wave, long long stride, const int32_t* lens, const int32_t* first, const int32_t* last, int N,
                         const double* fade_in, const double* fade_out, int ov, float* out, long long out_len, void* stream);
+/* svc_chunks_assemble for an arbitrary list of N pieces of the same chunk-wave buffer (n_rows rows of `stride` floats), so
+ * that a file's audio can be spliced while later chunks do not exist yet: rows in any order, any subset of them, a chunk
+ * delivered in one piece or several.  Piece p, HOST arrays consumed before the call returns (one launch per 64 pieces):
+ *   row[p]       the row holding the chunk, len[p] its samples;
+ *   prev_row[p]  the row of the chunk before it in its file, or -1 (no seam); prev_len[p] that row's samples;
+ *   begin[p] <= end[p] <= len[p]   the samples of the chunk this piece delivers;
+ *   out_off[p]   (int64) where sample begin[p] lands in `out`.
+ * For begin[p] <= i < end[p]:
+ *   out[out_off + i - begin] = wave[row][i]                                                          prev_row < 0 or i >= ov
+ *                            = float(double(wave[row][i]) * fade_in[i] + double(wave[prev_row][prev_len - ov + i]) * fade_out[i])
+ * with the products and the sum rounded separately: the device function svc_chunks_assemble's kernel calls, so a file
+ * emitted piece by piece is bit for bit the file assembled at once.  No sample at or above len / prev_len is read; nothing
+ * outside the pieces' ranges is written (`out` is NOT otherwise initialised).  Every piece of a chunk carries
+ * the chunk's prev_row: samples below ov are seam samples whichever piece delivers them, and a tail held back for a
+ * successor that never came (begin = len - ov, end = len) is one more piece of its chunk.
+ * pcm (int16, may be NULL): a second plane written at the same offsets, the reference streaming leg's
+ * `(wave * 32768.0).astype(np.int16)`: the float scaled exactly, truncated toward zero, SATURATED to [-32768, 32767].
+ * Saturation is the one deliberate deviation: numpy wraps +1.0 (where the vocoders' clamp can land) to -32768.  NaN gives 0.
+ * Refused before anything is launched: row / prev_row outside the buffer, len or prev_len outside 0 .. stride, a range
+ * outside its chunk, prev_row >= 0 with prev_len < ov, pieces that overlap in `out`, a piece outside 0 .. out_len. */
+int svc_chunks_emit(const float* wave, long long stride, int n_rows, const int32_t* row, const int32_t* len, const int32_t* prev_row,
+                    const int32_t* prev_len, const int32_t* begin, const int32_t* end, const int64_t* out_off, int N,
+                    const double* fade_in, const double* fade_out, int ov, float* out, int16_t* pcm, long long out_len, void* stream);
 
 /* ---------------------------------------------------------------- real-time sessions: the SOLA splice of one block step
  * Replaces the SOLA lines of the reference GUI's audio callback (real-time-gui.py, `audio_callback`: two conv1d, an argmax,

@@ -25,7 +25,7 @@ EXPORTS = [
     "svc_ar_prefill_batch", "svc_ar_set_prefill_rows", "svc_ar_prefill_passes", "svc_ar_admit", "svc_ar_run", "svc_ar_retire",
     "svc_ar_session_active",
     "svc_lr_create", "svc_lr_destroy", "svc_lr_forward", "svc_crossfade",
-    "svc_chunks_gather_cond", "svc_chunks_assemble", "svc_sola_step", "svc_rt_push", "svc_rt_push_tiles", "svc_rt_ring_floats",
+    "svc_chunks_gather_cond", "svc_chunks_assemble", "svc_chunks_emit", "svc_sola_step", "svc_rt_push", "svc_rt_push_tiles", "svc_rt_ring_floats",
     "svc_rt_out", "svc_rt_push_gated", "svc_rt_out_dev", "svc_rt_pitch_state_words", "svc_rt_pitch",
     "svc_rt_pitch_cache_words", "svc_rt_pitch_ring_words", "svc_rt_pitch_win",
     "svc_vad_create", "svc_vad_destroy", "svc_vad_rows", "svc_vad_history", "svc_vad_state_floats", "svc_vad_scores", "svc_vad_detect",
@@ -258,6 +258,9 @@ def lib():
         l.svc_last_error.restype = C.c_char_p
         if l.svc_abi_version() != 1:
             raise ImportError("libseedvc_hip.so ABI version mismatch")
+        # the streaming splice: the pieces' rows, lengths and ranges as HOST int32 arrays, their output offsets as HOST int64
+        l.svc_chunks_emit.argtypes = ([C.c_void_p, C.c_longlong, C.c_int] + [C.POINTER(C.c_int32)] * 6 + [C.POINTER(C.c_int64), C.c_int,
+                                      C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p])
         l.svc_sola_step.argtypes = [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int32),
                                     C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         l.svc_rt_push.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int,

@@ -663,6 +663,15 @@ __global__ __launch_bounds__(256) void chunks_gather_cond_kernel(const VT* __res
     }
 }
 
+// One seam sample: float(double(cur) * fade_in + double(tail) * fade_out), the products and the sum rounded separately
+// (crossfade_kernel's arithmetic, bit-identical to numpy's).  The one statement of it for chunks_assemble_kernel and
+// chunks_emit_kernel, so a file emitted piece by piece cannot drift from the file assembled at once.
+__device__ __forceinline__ float seam_sample(float cur, float tail, double fin, double fout) {
+    const double a = __dmul_rn((double)cur, fin);
+    const double b = __dmul_rn((double)tail, fout);
+    return (float)__dadd_rn(a, b);
+}
+
 struct AssembleChunks {
     long long off[CHUNK_MAXN];      // first output sample of the chunk's body
     int len[CHUNK_MAXN], body[CHUNK_MAXN];
@@ -703,14 +712,78 @@ __global__ __launch_bounds__(256) void chunks_assemble_kernel(const float* __res
                 p[0] = tail[i0];
             }
 #pragma unroll
-            for (int j = 0; j < W; ++j) {
-                const double a = __dmul_rn((double)v[j], fin[i0 + j]);
-                const double b = __dmul_rn((double)p[j], fout[i0 + j]);
-                v[j] = (float)__dadd_rn(a, b);
-            }
+            for (int j = 0; j < W; ++j) v[j] = seam_sample(v[j], p[j], fin[i0 + j], fout[i0 + j]);
         }
         if constexpr (VEC) *reinterpret_cast<float4v*>(dst + i0) = (float4v){v[0], v[1], v[2], v[3]};
         else dst[i0] = v[0];
+    }
+}
+
+struct EmitPieces {
+    long long src[CHUNK_MAXN];      // first float of the piece's row in the wave buffer
+    long long tail[CHUNK_MAXN];     // float of the wave buffer that sample 0 of the chunk is faded with, -1 without a seam
+    long long dst[CHUNK_MAXN];      // out_off - begin: sample i of the chunk lands at out[dst + i]
+    int begin[CHUNK_MAXN], end[CHUNK_MAXN];
+};
+
+// (wave * 32768.0).astype(np.int16) with saturation instead of numpy's wrap: the scaling is exact (a power of two),
+// the conversion truncates toward zero; NaN gives 0.
+__device__ __forceinline__ int16_t pcm16_sample(float v) {
+    const float x = v * 32768.0f;
+    if (!(x == x)) return 0;
+    return (int16_t)(int)fminf(fmaxf(x, -32768.0f), 32767.0f);
+}
+
+// out[dst[p] + i] = wave[src[p] + i] for i >= ov or a piece without a seam, else seam_sample(wave[src[p] + i],
+// wave[tail[p] + i], fade_in[i], fade_out[i]), begin[p] <= i < end[p]; pcm (may be null) gets pcm16_sample of the same value
+// at the same offset.  Only samples begin .. end - 1 of the row and, below ov, the same indices of the tail are read, only
+// the piece's range is written.  VEC: 4 samples per thread, a 16-byte load and store and an 8-byte pcm store (the caller has
+// checked that ov, every begin, end, out_off, len and prev_len, the row stride and the pointers allow it: then src, tail
+// and dst are multiples of 4 floats and a group of 4 lies on one side of ov).
+template <bool VEC>
+__global__ __launch_bounds__(256) void chunks_emit_kernel(const float* __restrict__ wave, const EmitPieces pc,
+                                                          const double* __restrict__ fin, const double* __restrict__ fout, int ov,
+                                                          float* __restrict__ out, int16_t* __restrict__ pcm) {
+    constexpr int W = VEC ? 4 : 1;
+    const int p = blockIdx.y;
+    const int begin = pc.begin[p], end = pc.end[p];
+    const float* cur = wave + pc.src[p];
+    const long long t = pc.tail[p];
+    const float* tail = wave + (t < 0 ? 0 : t);
+    const int n_fade = t < 0 ? 0 : ov;
+    float* dst = out + pc.dst[p];
+    int16_t* dpcm = pcm ? pcm + pc.dst[p] : nullptr;
+    for (long g = (long)blockIdx.x * 256 + threadIdx.x; begin + g * W < end; g += (long)gridDim.x * 256) {
+        const int i0 = begin + (int)g * W;
+        float v[W];
+        if constexpr (VEC) {
+            const float4v x = *reinterpret_cast<const float4v*>(cur + i0);
+            v[0] = x[0]; v[1] = x[1]; v[2] = x[2]; v[3] = x[3];
+        } else {
+            v[0] = cur[i0];
+        }
+        if (i0 < n_fade) {
+            float q[W];
+            if constexpr (VEC) {
+                const float4v x = *reinterpret_cast<const float4v*>(tail + i0);
+                q[0] = x[0]; q[1] = x[1]; q[2] = x[2]; q[3] = x[3];
+            } else {
+                q[0] = tail[i0];
+            }
+#pragma unroll
+            for (int j = 0; j < W; ++j) v[j] = seam_sample(v[j], q[j], fin[i0 + j], fout[i0 + j]);
+        }
+        if constexpr (VEC) *reinterpret_cast<float4v*>(dst + i0) = (float4v){v[0], v[1], v[2], v[3]};
+        else dst[i0] = v[0];
+        if (dpcm) {
+            if constexpr (VEC) {
+                typedef short short4v __attribute__((ext_vector_type(4)));
+                *reinterpret_cast<short4v*>(dpcm + i0) =
+                    (short4v){pcm16_sample(v[0]), pcm16_sample(v[1]), pcm16_sample(v[2]), pcm16_sample(v[3])};
+            } else {
+                dpcm[i0] = pcm16_sample(v[0]);
+            }
+        }
     }
 }
 }  // namespace
@@ -848,6 +921,57 @@ int svc_chunks_assemble(const float* wave, long long stride, const int32_t* lens
         const float* w = wave + (long long)k0 * stride;
         if (vec) hipLaunchKernelGGL(chunks_assemble_kernel<true>, dim3(gx, nk), dim3(256), 0, (hipStream_t)stream, w, (long)stride, ch, fade_in, fade_out, ov, out);
         else hipLaunchKernelGGL(chunks_assemble_kernel<false>, dim3(gx, nk), dim3(256), 0, (hipStream_t)stream, w, (long)stride, ch, fade_in, fade_out, ov, out);
+        SVC_CHECK_HIP(hipGetLastError());
+    }
+    return 0;
+}
+
+int svc_chunks_emit(const float* wave, long long stride, int n_rows, const int32_t* row, const int32_t* len, const int32_t* prev_row,
+                    const int32_t* prev_len, const int32_t* begin, const int32_t* end, const int64_t* out_off, int N,
+                    const double* fade_in, const double* fade_out, int ov, float* out, int16_t* pcm, long long out_len, void* stream) {
+    SVC_REQUIRE(N >= 0 && ov >= 0 && out_len >= 0 && stride >= 0 && n_rows >= 0, "chunks_emit: bad argument");
+    SVC_REQUIRE(N == 0 || (row && len && prev_row && prev_len && begin && end && out_off), "chunks_emit: null argument");
+    std::vector<std::pair<long long, long long>> spans;      // [first, one past the last) output sample of every non-empty piece
+    int max_n = 0;
+    bool seams = false;
+    bool vec = ov % 4 == 0 && stride % 4 == 0 && (((uintptr_t)wave | (uintptr_t)out) & 15) == 0 && ((uintptr_t)pcm & 7) == 0;
+    for (int p = 0; p < N; ++p) {
+        SVC_REQUIRE(row[p] >= 0 && row[p] < n_rows, "chunks_emit: a row outside 0 .. n_rows - 1");
+        SVC_REQUIRE(len[p] >= 0 && len[p] <= stride, "chunks_emit: a chunk length outside 0 .. stride");
+        SVC_REQUIRE(begin[p] >= 0 && begin[p] <= end[p] && end[p] <= len[p], "chunks_emit: a piece's range outside 0 <= begin <= end <= len");
+        SVC_REQUIRE(prev_row[p] < n_rows, "chunks_emit: a prev_row outside -1 .. n_rows - 1");
+        if (prev_row[p] >= 0) {
+            SVC_REQUIRE(prev_len[p] <= stride, "chunks_emit: a previous chunk's length outside 0 .. stride");
+            SVC_REQUIRE(prev_len[p] >= ov, "chunks_emit: a previous chunk is shorter than the overlap");
+            seams = seams || begin[p] < std::min(end[p], ov);
+            vec = vec && prev_len[p] % 4 == 0;
+        }
+        const long long n = end[p] - begin[p];
+        SVC_REQUIRE(out_off[p] >= 0 && out_off[p] <= out_len - n, "chunks_emit: a piece lies outside out (0 .. out_len)");
+        if (n > 0) spans.emplace_back((long long)out_off[p], (long long)out_off[p] + n);
+        max_n = std::max(max_n, (int)n);
+        vec = vec && len[p] % 4 == 0 && begin[p] % 4 == 0 && end[p] % 4 == 0 && out_off[p] % 4 == 0;
+    }
+    std::sort(spans.begin(), spans.end());
+    for (size_t i = 1; i < spans.size(); ++i)
+        SVC_REQUIRE(spans[i - 1].second <= spans[i].first, "chunks_emit: two pieces overlap in out");
+    if (max_n == 0) return 0;
+    SVC_REQUIRE(wave && out && (!seams || (fade_in && fade_out)), "chunks_emit: null argument");
+    const int gx = (int)std::min<long>(cdiv(cdiv(max_n, vec ? 4 : 1), 256), 4096);
+    for (int p0 = 0; p0 < N; p0 += CHUNK_MAXN) {
+        const int np = std::min(N - p0, CHUNK_MAXN);
+        EmitPieces pc;
+        memset(&pc, 0, sizeof(pc));
+        for (int p = 0; p < np; ++p) {
+            const int g = p0 + p;
+            pc.src[p] = (long long)row[g] * stride;
+            pc.tail[p] = prev_row[g] < 0 ? -1 : (long long)prev_row[g] * stride + (prev_len[g] - ov);
+            pc.dst[p] = (long long)out_off[g] - begin[g];
+            pc.begin[p] = begin[g];
+            pc.end[p] = end[g];
+        }
+        if (vec) hipLaunchKernelGGL(chunks_emit_kernel<true>, dim3(gx, np), dim3(256), 0, (hipStream_t)stream, wave, pc, fade_in, fade_out, ov, out, pcm);
+        else hipLaunchKernelGGL(chunks_emit_kernel<false>, dim3(gx, np), dim3(256), 0, (hipStream_t)stream, wave, pc, fade_in, fade_out, ov, out, pcm);
         SVC_CHECK_HIP(hipGetLastError());
     }
     return 0;

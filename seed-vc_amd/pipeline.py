@@ -99,6 +99,150 @@ def long_batch_plan(n_srcs, prompt_lens, max_context_window, overlap_frame_len=1
     return dict(chunks=chunks, bodies=bodies, out_lens=out_lens, micro_batches=micro)
 
 
+# ------------------------------------------------------------ long-form streaming: the schedule and the splice, on the host
+def _ramp_size(m, first_chunks, growth, max_chunks):
+    """Chunks of micro-batch m of the streaming ramp: min(max_chunks, ceil(first_chunks * growth ** m))."""
+    size = first_chunks
+    for _ in range(m):
+        if size >= max_chunks:
+            break
+        size *= growth
+    return min(int(max_chunks), int(math.ceil(size)))
+
+
+def _ramp_args(what, n_chunks, first_chunks, growth, max_chunks):
+    """The ramp's (first_chunks, growth, max_chunks) behind their checks; first_chunks None = one chunk per file that has one."""
+    if max_chunks < 1:
+        raise ValueError(f"{what}: max_chunks = {max_chunks}, at least one chunk per micro-batch is needed")
+    if growth < 1:
+        raise ValueError(f"{what}: growth = {growth}, a ramp that shrinks never reaches max_chunks")
+    if first_chunks is None:
+        first_chunks = max(1, sum(1 for n in n_chunks if n > 0))
+    if first_chunks < 1:
+        raise ValueError(f"{what}: first_chunks = {first_chunks}, the first micro-batch needs at least one chunk")
+    return min(first_chunks, max_chunks), growth, int(max_chunks)
+
+
+def stream_schedule(n_chunks, first_chunks=None, growth=4, max_chunks=64):
+    """The order in which `convert_long_stream` runs the chunks of its files, from the chunk counts alone.  n_chunks[u]: chunks
+    of file u.
+      order        [(file, chunk)], chunk-major: chunk 0 of every file that has one, then chunk 1, ... -- every file's first
+                   audio comes before any file's tail (`long_batch_plan` lists utterance-major: best for the whole call)
+      micro_batches[(i0, i1)]: consecutive ranges of `order`; micro-batch m has min(max_chunks, ceil(first_chunks * growth ** m))
+                   chunks, first_chunks None = one per file with chunks (capped at max_chunks): small early micro-batches
+                   bring the first audio forward, large late ones use the device as the pool does.  growth 4 is the
+                   measured choice: first audio as early as with 2, less of the call spent in small batches.
+    growth=1, first_chunks=max_chunks with one file is `long_batch_plan`'s partition.  ValueError for first_chunks < 1,
+    growth < 1, max_chunks < 1."""
+    n_chunks = [int(n) for n in n_chunks]
+    first_chunks, growth, max_chunks = _ramp_args("stream_schedule", n_chunks, first_chunks, growth, max_chunks)
+    order = [(u, k) for k in range(max(n_chunks, default=0)) for u, n in enumerate(n_chunks) if k < n]
+    micro, i0, m = [], 0, 0
+    while i0 < len(order):
+        i1 = min(len(order), i0 + _ramp_size(m, first_chunks, growth, max_chunks))
+        micro.append((i0, i1))
+        i0, m = i1, m + 1
+    return dict(order=order, micro_batches=micro)
+
+
+_SplicePiece = collections.namedtuple("_SplicePiece", "file offset chunk len prev_chunk prev_len begin end final")
+
+
+class _StreamSplicer:
+    """Which samples of which chunk waves may be handed out, as the chunks of `n_files` files complete in any order (host
+    integers only).  chunks_per_file[u]: chunks of file u by plan; ov: samples of the cross-fade.
+
+    `complete(file, chunk, samples, plan_is_last)` -> the pieces that became deliverable, in file order:
+    _SplicePiece(file, offset = the piece's first sample in the file, chunk, len, prev_chunk (-1: no seam), prev_len, begin,
+    end, final) -- samples begin .. end - 1 of `chunk`, cross-faded below ov with the last ov samples of `prev_chunk`, the
+    arguments of `svc_chunks_emit` once the caller has mapped chunks to rows.  A chunk's piece is released only when every
+    earlier chunk of its file is complete.  The keep rule is `v2_seam_plan`'s: kept = samples >= 2 ov, or the file's last
+    chunk by plan; an empty chunk is never kept.  keep_all (a v1 plan, `long_batch_plan`): every chunk is kept, as
+    `svc_chunks_assemble` takes them -- a window may be shorter than two overlaps there, and a chunk before the last has at
+    least ov samples (ValueError otherwise).  A kept chunk that may still get a kept successor delivers
+    [0, len - ov) and holds its tail for the seam; when the file's last chunk is not kept, the held tail of the last kept
+    chunk is one more piece of that chunk (chunk = its index, [len - ov, len)).  The piece that ends a file has final=True;
+    a file without a kept chunk ends with one empty final piece (chunk -1), and `start()` gives those of the files without
+    chunks.  Over any completion order a file's pieces laid end to end are `v2_seam_plan` / `long_batch_plan` +
+    `svc_chunks_assemble` on the same lengths."""
+
+    def __init__(self, n_files, chunks_per_file, ov, keep_all=False):
+        if len(chunks_per_file) != n_files:
+            raise ValueError("_StreamSplicer: chunks_per_file must have one entry per file")
+        self.ov, self.keep_all = int(ov), bool(keep_all)
+        self.n = [int(c) for c in chunks_per_file]
+        self.lens = [[None] * c for c in self.n]
+        self.next = [0] * n_files               # first chunk of the file that is not spliced yet
+        self.held = [None] * n_files            # (chunk, len, prev_chunk, prev_len) of the kept chunk whose tail waits
+        self.offset = [0] * n_files             # samples of the file handed out so far
+
+    def start(self):
+        return [_SplicePiece(u, 0, -1, 0, -1, 0, 0, 0, True) for u, c in enumerate(self.n) if c == 0]
+
+    def _piece(self, u, chunk, n, prev, begin, end, final):
+        p = _SplicePiece(u, self.offset[u], chunk, n, prev[0], prev[1], begin, end, final)
+        self.offset[u] += end - begin
+        return p
+
+    def complete(self, file, chunk, samples, plan_is_last):
+        u, k, ov = int(file), int(chunk), self.ov
+        if not 0 <= u < len(self.n) or not 0 <= k < self.n[u] or self.lens[u][k] is not None or samples < 0:
+            raise ValueError(f"_StreamSplicer: file {file}, chunk {chunk}: no such chunk, completed twice, or a negative length")
+        if bool(plan_is_last) != (k == self.n[u] - 1):
+            raise ValueError(f"_StreamSplicer: file {file}, chunk {chunk}: the plan's last chunk is the file's last chunk, and no other")
+        self.lens[u][k] = int(samples)
+        out = []
+        while self.next[u] < self.n[u] and self.lens[u][self.next[u]] is not None:
+            j = self.next[u]
+            n, ends = self.lens[u][j], j == self.n[u] - 1
+            self.next[u] += 1
+            held = self.held[u]
+            prev = (held[0], held[1]) if held is not None else (-1, 0)
+            if self.keep_all or (n > 0 and (n >= 2 * ov or ends)):
+                if ends:
+                    out.append(self._piece(u, j, n, prev, 0, n, True))
+                    self.held[u] = None
+                else:
+                    if n < ov:
+                        raise ValueError(f"_StreamSplicer: file {u}, chunk {j}: {n} samples, shorter than the overlap of {ov}")
+                    if n > ov:
+                        out.append(self._piece(u, j, n, prev, 0, n - ov, False))
+                    self.held[u] = (j, n) + prev
+            elif ends:
+                if held is not None:
+                    out.append(self._piece(u, held[0], held[1], held[2:], held[1] - ov, held[1], True))
+                    self.held[u] = None
+                else:
+                    out.append(self._piece(u, -1, 0, (-1, 0), 0, 0, True))
+        return out
+
+
+StreamPiece = collections.namedtuple("StreamPiece", "file offset wave final parts", defaults=(None,))
+StreamPiece.__doc__ = """One piece of a file's audio as `convert_long_stream` hands it out: samples offset .. offset + n - 1 of
+file `file` in `wave` (1, n), float32 or int16; final: the piece that ends its file (it may be empty); parts: the v2 call's
+return_parts (the per-chunk dicts of the chunks whose waves completed with this piece), else None."""
+
+
+def collect_stream(pieces, n_files):
+    """The pieces of `convert_long_stream` -> a list of n_files (1, L_u) tensors, what `convert_long_batch` returns.
+    ValueError unless every file's pieces are contiguous, start at 0 and end with exactly one `final`."""
+    waves, at, done = [[] for _ in range(n_files)], [0] * n_files, [False] * n_files
+    for p in pieces:
+        if not 0 <= p.file < n_files:
+            raise ValueError(f"collect_stream: a piece of file {p.file}, {n_files} files expected")
+        if done[p.file]:
+            raise ValueError(f"collect_stream: file {p.file}: a piece after its final piece")
+        if p.offset != at[p.file]:
+            raise ValueError(f"collect_stream: file {p.file}: a piece at sample {p.offset}, {at[p.file]} expected (a gap or an overlap)")
+        waves[p.file].append(p.wave)
+        at[p.file] += p.wave.size(1)
+        done[p.file] = bool(p.final)
+    missing = [u for u in range(n_files) if not done[u]]
+    if missing:
+        raise ValueError(f"collect_stream: files {missing} have no final piece")
+    return [torch.cat(w, dim=1) for w in waves]
+
+
 def derive_seed(seed, index):
     """The seed of part `index` (a chunk of a file, a block of a stream) of the request seeded `seed`: the splitmix64
     finaliser of (seed + (index + 1) * 0x9E3779B97F4A7C15) mod 2^64.  A pure host function, a bijection of the 64-bit
@@ -352,12 +496,81 @@ def _row_views(vc, S, calls):
     return rows
 
 
+class _PoolFiles:
+    """The files of a chunk pool behind their checks, stacked once: condition rows along time, prompts padded to Pmax, and the
+    chunk table of `long_batch_plan`.  `what` names the entry point in errors."""
+
+    def __init__(self, what, utterances, max_context_window, overlap_frame_len, hop, max_chunks):
+        for u, (cond, pc, mel2, style2) in enumerate(utterances):
+            if pc.size(1) != mel2.size(2):
+                raise ValueError(f"{what}: utterance {u}: prompt_condition has {pc.size(1)} frames, mel2 {mel2.size(2)}")
+        self.U = len(utterances)
+        self.P = [int(t[2].size(2)) for t in utterances]
+        self.n_src = [int(t[0].size(1)) for t in utterances]
+        self.plan = long_batch_plan(self.n_src, self.P, max_context_window, overlap_frame_len, hop, max_chunks)
+        self.dev = utterances[0][0].device
+        self.utterances = utterances
+
+    def stack(self):
+        """The device tensors (called under the files' device, once there is a chunk to run)."""
+        t0, dev = self.utterances[0], self.dev
+        self.Dc, self.Cm = t0[0].size(2), t0[2].size(1)
+        self.cond_all = torch.cat([_lib.f32c(t[0], dev)[0] for t in self.utterances])
+        self.row_base = [sum(self.n_src[:u]) for u in range(self.U)]
+        st = _stack_prompts([t[1:] for t in self.utterances], dev)
+        self.pc_all, self.mel_all, self.style_all, self.Pmax = st["prompt_condition"], st["mel"], st["style"], st["Pmax"]
+
+    def prompts_of(self, utt):
+        """(mel, style) rows of the chunks whose files are `utt`."""
+        if self.U > 1:
+            idx = torch.tensor(utt, device=self.dev)
+            return self.mel_all.index_select(0, idx), self.style_all.index_select(0, idx)
+        return self.mel_all.expand(len(utt), -1, -1), self.style_all.expand(len(utt), -1)
+
+
+def _pool_micro_batch(what, cfm, vocoder, files, mb, mel_rows, style_rows, waves, row0, n_timesteps, inference_cfg_rate, hop, noise_of,
+                      kwargs_of, mb_seeds, seed_kw, ragged_vocoder, cfm_kwargs, file_settings):
+    """One micro-batch of a chunk pool: `svc_chunks_gather_cond` -> one sampler call with per-row x_lens / prompt_lens ->
+    `_strip_prompt` -> `_vocode` -> rows row0 .. of the chunk-wave buffer `waves`.  files: a stacked `_PoolFiles`; mb: the
+    micro-batch's entries of its chunk table; mel_rows / style_rows: the chunks' prompt rows; noise_of(i, T) / kwargs_of(i, S):
+    None, or the pinned sampler noise / vocoder draws of the micro-batch's chunk i."""
+    i32, dev, P = _lib.i32_host, files.dev, files.P
+    n = len(mb)
+    S = [c[2] for c in mb]
+    Pk = [P[c[0]] for c in mb]
+    x_lens = [p + s for p, s in zip(Pk, S)]
+    T = max(x_lens)
+    mu = torch.empty(n, T, files.Dc, device=dev)
+    _lib.check(_lib.lib().svc_chunks_gather_cond(_lib.ptr(files.pc_all), i32(P), files.U, files.Pmax, _lib.ptr(files.cond_all),
+                                                 files.cond_all.size(0), i32([c[0] for c in mb]),
+                                                 i32([files.row_base[c[0]] + c[1] for c in mb]), i32(S), n, files.Dc, T, _lib.ptr(mu),
+                                                 _lib.stream_ptr()))
+    z = None
+    if noise_of is not None:
+        z = torch.zeros(n, files.Cm, T, device=dev)
+        for i, t_k in enumerate(x_lens):
+            z[i, :, :t_k] = noise_of(i, t_k)[0]
+    kws = [kwargs_of(i, s) for i, s in enumerate(S)] if kwargs_of is not None else None
+    if file_settings is None:
+        mel = cfm.inference(mu, x_lens, mel_rows, style_rows, None, n_timesteps, inference_cfg_rate=inference_cfg_rate,
+                            z=z, prompt_lens=Pk, **_cfm_seeds(mb_seeds), **(cfm_kwargs or {}))
+    else:
+        mel = cfm.inference_rows(mu, x_lens, mel_rows, style_rows, [file_settings[c[0]] for c in mb],
+                                 z=z, prompt_lens=Pk, **_cfm_seeds(mb_seeds))
+    vc = _strip_prompt(mel, Pk, x_lens, max(S))
+    for call in _vocode(vocoder, vc, S, ragged_vocoder, what, hop=hop, seeds=mb_seeds, seed_kw=seed_kw, row_kwargs=kws):
+        j = 0
+        for a, b in call.runs:       # rows of a call -> rows of the chunk wave buffer (slices: no synchronisation)
+            waves[row0 + a:row0 + b, :call.frames * hop].copy_(call.wave[j:j + b - a])
+            j += b - a
+
+
 def _long_pool(cfm, vocoder, utterances, n_timesteps, inference_cfg_rate, hop, max_context_window, overlap_frame_len, noise_fn,
                vocoder_kwargs_fn, max_chunks, ragged_vocoder, seeds, seed_kw, cfm_kwargs=None, sampler=None):
     """The chunk pool of `HotPath.convert_long_batch` and of the timbre branch of `V2HotPath.convert_long_batch`, behind their
-    argument checks: `long_batch_plan`, then per micro-batch `svc_chunks_gather_cond` -> one `cfm.inference` with per-row
-    x_lens / prompt_lens -> `_strip_prompt` -> `_vocode` -> rows of one wave buffer, one `svc_chunks_assemble` and one host
-    synchronisation at the end.  utterances, noise_fn, vocoder_kwargs_fn, ragged_vocoder (a bool here) and seeds (host
+    argument checks: `long_batch_plan`, then per micro-batch `_pool_micro_batch` (`svc_chunks_gather_cond` -> one `cfm.inference`
+    with per-row x_lens / prompt_lens -> `_strip_prompt` -> `_vocode` -> rows of one wave buffer), one `svc_chunks_assemble` and
+    one host synchronisation at the end.  utterances, noise_fn, vocoder_kwargs_fn, ragged_vocoder (a bool here) and seeds (host
     integers or None) as `HotPath.convert_long_batch` documents them; seed_kw: `_vocode`'s; cfm_kwargs: further keywords of
     every sampler call (the v2 caller's `random_voice`); sampler: None, or per file a `cfm.sampler_setting` entry or None
     (checked by `_file_settings`): every chunk of a file then runs with its file's entry, the micro-batch in one
@@ -366,14 +579,10 @@ def _long_pool(cfm, vocoder, utterances, n_timesteps, inference_cfg_rate, hop, m
     if U == 0:
         return []
     file_settings = _file_settings("convert_long_batch", sampler, U, n_timesteps, inference_cfg_rate, **(cfm_kwargs or {}))
-    for u, (cond, pc, mel2, style2) in enumerate(utterances):
-        if pc.size(1) != mel2.size(2):
-            raise ValueError(f"convert_long_batch: utterance {u}: prompt_condition has {pc.size(1)} frames, mel2 {mel2.size(2)}")
-    P = [int(t[2].size(2)) for t in utterances]
-    n_src = [int(t[0].size(1)) for t in utterances]
-    plan = long_batch_plan(n_src, P, max_context_window, overlap_frame_len, hop, max_chunks)
+    files = _PoolFiles("convert_long_batch", utterances, max_context_window, overlap_frame_len, hop, max_chunks)
+    plan = files.plan
     chunks, out_lens = plan["chunks"], plan["out_lens"]
-    dev = utterances[0][0].device
+    dev = files.dev
     ovw = overlap_frame_len * hop
     i32 = _lib.i32_host
     with torch.cuda.device(dev):
@@ -383,12 +592,7 @@ def _long_pool(cfm, vocoder, utterances, n_timesteps, inference_cfg_rate, hop, m
         if not chunks:
             return result
         N = len(chunks)
-        Dc, Cm = utterances[0][0].size(2), utterances[0][2].size(1)
-        # the utterances' tensors, stacked once: condition rows along time, prompts padded to Pmax
-        cond_all = torch.cat([_lib.f32c(t[0], dev)[0] for t in utterances])
-        row_base = [sum(n_src[:u]) for u in range(U)]
-        st = _stack_prompts([t[1:] for t in utterances], dev)
-        pc_all, mel_all, style_all, Pmax = st["prompt_condition"], st["mel"], st["style"], st["Pmax"]
+        files.stack()
         utt = [c[0] for c in chunks]
         chunk_seeds = None
         if seeds is not None:       # chunk k of its file: the chunks are listed utterance-major
@@ -396,51 +600,144 @@ def _long_pool(cfm, vocoder, utterances, n_timesteps, inference_cfg_rate, hop, m
             for k, u in enumerate(utt):
                 first_of.setdefault(u, k)
             chunk_seeds = [derive_seed(seeds[u], k - first_of[u]) for k, u in enumerate(utt)]
-        if U > 1:
-            idx = torch.tensor(utt, device=dev)
-            mel_chunks, style_chunks = mel_all.index_select(0, idx), style_all.index_select(0, idx)
-        else:
-            mel_chunks, style_chunks = mel_all.expand(N, -1, -1), style_all.expand(N, -1)
+        mel_chunks, style_chunks = files.prompts_of(utt)
         fade_in, fade_out = (torch.from_numpy(w).to(dev) for w in _cos2_windows(ovw))
         stride = max(c[2] for c in chunks) * hop
         waves = torch.empty(N, stride, device=dev, dtype=torch.float32)      # row k: chunk k's waveform, lens[k] samples
+        noise_of = (lambda i, t_k: noise_fn(t_k)) if noise_fn is not None else None
+        kwargs_of = (lambda i, s: vocoder_kwargs_fn(s)) if vocoder_kwargs_fn is not None else None
         for k0, k1 in plan["micro_batches"]:
-            mb = chunks[k0:k1]
-            n = k1 - k0
-            S = [c[2] for c in mb]
-            Pk = [P[c[0]] for c in mb]
-            x_lens = [p + s for p, s in zip(Pk, S)]
-            T = max(x_lens)
-            mu = torch.empty(n, T, Dc, device=dev)
-            _lib.check(_lib.lib().svc_chunks_gather_cond(_lib.ptr(pc_all), i32(P), U, Pmax, _lib.ptr(cond_all), cond_all.size(0),
-                                                         i32([c[0] for c in mb]), i32([row_base[c[0]] + c[1] for c in mb]),
-                                                         i32(S), n, Dc, T, _lib.ptr(mu), _lib.stream_ptr()))
-            z = None
-            if noise_fn is not None:
-                z = torch.zeros(n, Cm, T, device=dev)
-                for i, t_k in enumerate(x_lens):
-                    z[i, :, :t_k] = noise_fn(t_k)[0]
-            kws = [vocoder_kwargs_fn(s) for s in S] if vocoder_kwargs_fn is not None else None
-            mb_seeds = chunk_seeds[k0:k1] if chunk_seeds is not None else None
-            if file_settings is None:
-                mel = cfm.inference(mu, x_lens, mel_chunks[k0:k1], style_chunks[k0:k1], None, n_timesteps, inference_cfg_rate=inference_cfg_rate,
-                                    z=z, prompt_lens=Pk, **_cfm_seeds(mb_seeds), **(cfm_kwargs or {}))
-            else:
-                mel = cfm.inference_rows(mu, x_lens, mel_chunks[k0:k1], style_chunks[k0:k1], [file_settings[c[0]] for c in mb],
-                                         z=z, prompt_lens=Pk, **_cfm_seeds(mb_seeds))
-            vc = _strip_prompt(mel, Pk, x_lens, max(S))
-            for call in _vocode(vocoder, vc, S, ragged_vocoder, "convert_long_batch", hop=hop, seeds=mb_seeds,
-                                seed_kw=seed_kw, row_kwargs=kws):
-                j = 0
-                for a, b in call.runs:       # rows of a call -> rows of the chunk wave buffer (slices: no synchronisation)
-                    waves[k0 + a:k0 + b, :call.frames * hop].copy_(call.wave[j:j + b - a])
-                    j += b - a
+            _pool_micro_batch("convert_long_batch", cfm, vocoder, files, chunks[k0:k1], mel_chunks[k0:k1], style_chunks[k0:k1], waves, k0,
+                              n_timesteps, inference_cfg_rate, hop, noise_of, kwargs_of,
+                              chunk_seeds[k0:k1] if chunk_seeds is not None else None, seed_kw, ragged_vocoder, cfm_kwargs, file_settings)
         lens = [c[2] * hop for c in chunks]
         _lib.check(_lib.lib().svc_chunks_assemble(_lib.ptr(waves), C.c_longlong(stride), i32(lens), i32([int(c[3]) for c in chunks]),
                                                   i32([int(c[4]) for c in chunks]), N, _lib.ptr(fade_in), _lib.ptr(fade_out), ovw,
                                                   _lib.ptr(out), C.c_longlong(out.numel()), _lib.stream_ptr()))
         torch.cuda.current_stream(dev).synchronize()
     return result
+
+
+# ------------------------------------------------------------------------ long-form streaming: emit, stage, hand out
+class _StreamOut:
+    """The delivery path of `convert_long_stream`: per micro-batch one `svc_chunks_emit` for the pieces the splicer released
+    into a device staging buffer, one non-blocking copy into pinned host memory (to_host) and one event; `pop` waits for the
+    oldest micro-batch's event -- never for the device or the stream -- and gives its `StreamPiece`s.  Pieces start at
+    multiples of 4 samples of the staging buffer, so the 16-byte path of the kernel stays open to them."""
+
+    def __init__(self, dev, ovw, pcm16, to_host):
+        self.dev, self.ovw, self.pcm16, self.to_host = dev, ovw, pcm16, to_host
+        self.fade_in, self.fade_out = (torch.from_numpy(w).to(dev) for w in _cos2_windows(ovw))
+        self.pending = collections.deque()          # (event or None, [(piece, staging offset)], staging buffer, parts)
+        self.carry = []
+
+    def push(self, pieces, waves, rows, parts=None):
+        """pieces: `_SplicePiece`s; waves (n_rows, stride): the chunk-wave buffer; rows[(file, chunk)] -> (row, samples it holds,
+        first sample of the chunk it holds) for the chunks the pieces name.  Enqueues on the current stream."""
+        if not pieces and not parts:
+            return
+        off, total = [], 0
+        for p in pieces:
+            off.append(total)
+            total += -(-(p.end - p.begin) // 4) * 4
+        buf = ev = None
+        if total:
+            i32 = _lib.i32_host
+            a = dict(row=[], len=[], prev_row=[], prev_len=[], begin=[], end=[])
+            for p in pieces:
+                row, n, skip = rows[(p.file, p.chunk)] if p.chunk >= 0 else (0, 0, 0)
+                prow, pn = -1, 0
+                if p.prev_chunk >= 0 and p.begin < min(p.end, self.ovw):
+                    prow, held, pskip = rows[(p.file, p.prev_chunk)]
+                    pn = p.prev_len - pskip
+                    assert held == pn and pn >= self.ovw
+                assert n == p.len - skip and p.begin >= skip and (skip == 0 or prow < 0)      # a row that holds a tail only has no seam
+                for key, v in zip(a, (row, n, prow, pn, p.begin - skip, p.end - skip)):
+                    a[key].append(v)
+            dev_f = torch.empty(total, device=self.dev, dtype=torch.float32)
+            dev_p = torch.empty(total, device=self.dev, dtype=torch.int16) if self.pcm16 else None
+            _lib.check(_lib.lib().svc_chunks_emit(_lib.ptr(waves), waves.stride(0), waves.size(0), i32(a["row"]), i32(a["len"]),
+                                                  i32(a["prev_row"]), i32(a["prev_len"]), i32(a["begin"]), i32(a["end"]),
+                                                  _lib.i64_host(off), len(pieces), _lib.ptr(self.fade_in), _lib.ptr(self.fade_out),
+                                                  self.ovw, _lib.ptr(dev_f), _lib.ptr(dev_p), total, _lib.stream_ptr()))
+            buf = dev_p if self.pcm16 else dev_f
+            if self.to_host:
+                host = torch.empty(total, dtype=buf.dtype, pin_memory=True)
+                host.copy_(buf, non_blocking=True)
+                buf = host
+            ev = torch.cuda.Event()
+            ev.record()
+        self.pending.append((ev, list(zip(pieces, off)), buf, parts))
+
+    def pop(self):
+        """-> the `StreamPiece`s of the oldest pushed micro-batch, after its event; its parts ride on the first of them (parts of
+        a micro-batch that released no piece wait for the next piece)."""
+        ev, placed, buf, parts = self.pending.popleft()
+        if ev is not None:
+            ev.synchronize()
+        dtype = torch.int16 if self.pcm16 else torch.float32
+        empty = torch.empty(1, 0, dtype=dtype, device="cpu" if self.to_host else self.dev)
+        out = []
+        for p, o in placed:
+            n = p.end - p.begin
+            out.append(StreamPiece(p.file, p.offset, buf[o:o + n][None, :] if n else empty, p.final, None))
+        if parts is not None:
+            self.carry = self.carry + parts
+        if out and self.carry:
+            out[0] = out[0]._replace(parts=self.carry)
+            self.carry = []
+        return out
+
+
+def _long_stream(what, cfm, vocoder, utterances, n_timesteps, inference_cfg_rate, hop, max_context_window, overlap_frame_len, noise_fn,
+                 vocoder_kwargs_fn, max_chunks, first_chunks, growth, ragged_vocoder, seeds, seed_kw, pcm16, to_host, lookahead,
+                 cfm_kwargs=None, sampler=None):
+    """The generator behind `HotPath.convert_long_stream` and the timbre branch of `V2HotPath.convert_long_stream`, behind their
+    argument checks: `long_batch_plan`'s chunks in `stream_schedule`'s order, per micro-batch `_pool_micro_batch` (the pool's
+    body) into rows of one wave buffer in schedule order, then `_StreamOut.push` for the pieces `_StreamSplicer` released.
+    Micro-batch m + lookahead is enqueued before micro-batch m's event is waited for."""
+    U = len(utterances)
+    if lookahead < 0:
+        raise ValueError(f"{what}: lookahead = {lookahead}, a count of micro-batches enqueued ahead")
+    if U == 0:
+        return
+    file_settings = _file_settings(what, sampler, U, n_timesteps, inference_cfg_rate, **(cfm_kwargs or {}))
+    files = _PoolFiles(what, utterances, max_context_window, overlap_frame_len, hop, max_chunks)
+    dev, ovw = files.dev, overlap_frame_len * hop
+    by_file = [[c for c in files.plan["chunks"] if c[0] == u] for u in range(U)]
+    sched = stream_schedule([len(c) for c in by_file], first_chunks, growth, max_chunks)
+    order, micro = sched["order"], sched["micro_batches"]
+    splicer = _StreamSplicer(U, [len(c) for c in by_file], ovw, keep_all=True)
+    with torch.cuda.device(dev):
+        out = _StreamOut(dev, ovw, pcm16, to_host)
+        out.push(splicer.start(), None, {})
+        if order:
+            files.stack()
+            chunks = [by_file[u][k] for u, k in order]
+            rows = {uk: (i, chunks[i][2] * hop, 0) for i, uk in enumerate(order)}
+            chunk_seeds = [derive_seed(seeds[u], k) for u, k in order] if seeds is not None else None
+            waves = torch.empty(len(order), max(c[2] for c in chunks) * hop, device=dev, dtype=torch.float32)
+
+    def enqueue(m):
+        i0, i1 = micro[m]
+        with torch.cuda.device(dev):
+            mel_rows, style_rows = files.prompts_of([u for u, _ in order[i0:i1]])
+            noise_of = (lambda i, T: noise_fn(*order[i0 + i], T)) if noise_fn is not None else None
+            kwargs_of = (lambda i, S: vocoder_kwargs_fn(*order[i0 + i], S)) if vocoder_kwargs_fn is not None else None
+            _pool_micro_batch(what, cfm, vocoder, files, chunks[i0:i1], mel_rows, style_rows, waves, i0, n_timesteps, inference_cfg_rate,
+                              hop, noise_of, kwargs_of, chunk_seeds[i0:i1] if chunk_seeds is not None else None, seed_kw,
+                              ragged_vocoder, cfm_kwargs, file_settings)
+            pieces = [p for i in range(i0, i1) for p in splicer.complete(*order[i], chunks[i][2] * hop, chunks[i][4])]
+            out.push(pieces, waves, rows)
+
+    enqueued = 0
+    while out.pending or enqueued < len(micro):
+        # the first pending entry may be the empty files' pieces: micro-batches 0 .. lookahead are enqueued before it is handed out
+        while enqueued < len(micro) and len(out.pending) <= lookahead:
+            enqueue(enqueued)
+            enqueued += 1
+        if out.pending:
+            yield from out.pop()
 
 
 class HotPath:
@@ -619,6 +916,41 @@ class HotPath:
                              "it cannot be combined with the ragged vocoder call")
         return _long_pool(self.cfm, self.vocoder, utterances, n_timesteps, inference_cfg_rate, hop, max_context_window, overlap_frame_len,
                           noise_fn, vocoder_kwargs_fn, max_chunks, ragged_vocoder, seeds, self._vocoder_seeds, sampler=sampler)
+
+    @torch.inference_mode()
+    def convert_long_stream(self, utterances, n_timesteps, inference_cfg_rate, hop, max_context_window, overlap_frame_len=16, *,
+                            seeds=None, noise_fn=None, vocoder_kwargs_fn=None, sampler=None, max_chunks=64, first_chunks=None, growth=4,
+                            ragged_vocoder=None, pcm16=False, to_host=True, lookahead=1):
+        """`convert_long_batch` as a generator of `StreamPiece(file, offset, wave, final)`: every file's audio is handed out
+        as its chunks finish, in file order per file, instead of once at the end (the reference's streaming leg of
+        `_stream_wave_chunks`, for many files at once).  `collect_stream(pieces, len(utterances))` gives what
+        `convert_long_batch` returns; with exact stand-ins the two are bit-identical, whatever the schedule.
+
+        The arguments are `convert_long_batch`'s, except: noise_fn(u, k, T) and vocoder_kwargs_fn(u, k, S) are keyed by file and
+        chunk of the file (the order of the calls is the schedule's, not the sequential loop's); seeds still give chunk k of
+        file u `derive_seed(seeds[u], k)`.  Schedule (`stream_schedule`): chunk-major over the files, micro-batches of
+        min(max_chunks, ceil(first_chunks * growth ** m)) chunks, first_chunks None = one per file with chunks.
+        wave: (1, n) float32, or int16 with pcm16 (`svc_chunks_emit`'s pcm plane: truncated toward zero, saturated); in pinned
+        host memory with to_host, else a view of a device buffer that is valid on the current stream.
+
+        Everything runs on the caller's current stream.  Per micro-batch: the pool's body (`_pool_micro_batch`), one
+        `svc_chunks_emit` for the pieces `_StreamSplicer` released, one non-blocking copy into pinned memory, one event.
+        Micro-batch m + lookahead is enqueued before the generator waits for the event of micro-batch m -- that event only,
+        never the device or the stream -- so the device works while the consumer handles a piece.  Nothing further is enqueued
+        until the consumer asks for the next piece (back-pressure); closing the generator early leaves the models usable.
+        Argument errors are raised at the first next(), before anything is enqueued."""
+        if seeds is not None and (noise_fn is not None or vocoder_kwargs_fn is not None):
+            raise ValueError("convert_long_stream: give seeds or noise_fn / vocoder_kwargs_fn, not both")
+        seeds = _seed_list("convert_long_stream", seeds, len(utterances))
+        if ragged_vocoder is None:
+            from .vocoder import BigVGAN
+            ragged_vocoder = isinstance(self.vocoder, BigVGAN)
+        if ragged_vocoder and vocoder_kwargs_fn is not None:
+            raise ValueError("convert_long_stream: vocoder_kwargs_fn pins per-chunk draws of a plain vocoder call; "
+                             "it cannot be combined with the ragged vocoder call")
+        yield from _long_stream("convert_long_stream", self.cfm, self.vocoder, utterances, n_timesteps, inference_cfg_rate, hop,
+                                max_context_window, overlap_frame_len, noise_fn, vocoder_kwargs_fn, max_chunks, first_chunks, growth,
+                                ragged_vocoder, seeds, self._vocoder_seeds, pcm16, to_host, lookahead, sampler=sampler)
 
 
 # ----------------------------------------------------------------------------------------- v2: tokens in, audio out
@@ -824,6 +1156,103 @@ class V2HotPath:
             self._mark("strip_vocoder")
         return out
 
+    def _style_chunks(self, what, files, ar_chunk_tokens, anonymization_only):
+        """The style branch's chunk table, file-major: [(file, chunk of the file, first token, tokens, is_last)] (`v2_chunk_plan`
+        per file).  ValueError for a chunk whose AR prompt does not fit the cache."""
+        plan = [(u, j) + c for u, f in enumerate(files) for j, c in enumerate(v2_chunk_plan(f["src_narrow"].size(1), ar_chunk_tokens))]
+        Lmax = self.ar.cfg["max_seq_len"]
+        for u, j, p0, n, _ in plan:
+            t = files[u]["target"]
+            rows = n + 2 if anonymization_only else t["narrow"].size(1) + n + 2 + t["tokens"].size(1)
+            if rows > Lmax:
+                raise ValueError(f"{what}: file {u}, chunk {j}: an AR prompt of {rows} rows does not fit the cache "
+                                 f"({Lmax} positions); use a smaller ar_chunk_tokens")
+        return plan
+
+    def _style_ar_requests(self, files, plan, anonymization_only, seeds, exp_noise_fn, ar_kw):
+        """The AR side of the style branch's chunks: one ragged `ar_lr` call over the AR conditions of all chunks of `plan`
+        (at least one), the chunks' seeds, and submit(sess, k): chunk k as one request of an `ARSession`.
+        -> (chunk_seeds or None, submit); ar_kw: max_new, top_p, temperature, repetition_penalty of every request."""
+        dev, K = self.device, len(plan)
+        # AR condition of every chunk: one ragged regulator call over cat([target narrow, range]) (not assumed position-wise)
+        narrow = []
+        for u, j, p0, n, _ in plan:
+            chunk = files[u]["src_narrow"][:, p0:p0 + n].to(dev).long()
+            narrow.append(chunk if anonymization_only else v2_ar_prompt(files[u]["target"]["narrow"], chunk))
+        nlen = [int(x.size(1)) for x in narrow]
+        tok_in = torch.zeros(K, max(nlen), dtype=torch.int64, device=dev)
+        for k, x in enumerate(narrow):
+            tok_in[k, :nlen[k]] = x[0]
+        ar_cond = self.ar_lr(tok_in, in_lens=nlen)[0]
+        if seeds is not None:
+            chunk_seeds = [derive_seed(seeds[u], j) for u, j, *_ in plan]
+            ar_seeds = chunk_seeds
+        else:
+            chunk_seeds = None
+            ar_seeds = torch.randint(0, 2 ** 62, (K,), dtype=torch.int64).tolist() if exp_noise_fn is None else None
+        no_target = torch.zeros(1, 0, dtype=torch.int64, device=dev)
+
+        def submit(sess, k):
+            u, j = plan[k][:2]
+            draws = dict(exp_noise=exp_noise_fn(u, j)) if exp_noise_fn is not None else dict(seed=ar_seeds[k])
+            return sess.submit(ar_cond[k:k + 1, :nlen[k]], no_target if anonymization_only else files[u]["target"]["tokens"],
+                               **ar_kw, **draws)
+        return chunk_seeds, submit
+
+    def _style_micro_batch(self, what, files, plan, ks, toks, ylens, st, mel_rows, style_rows, waves, row0, hop, n_timesteps, cfg_rates,
+                           random_voice, noise_fn, chunk_seeds, file_settings):
+        """One micro-batch of the style branch, the chunks `ks` of `plan` (all with ylen > 0): clamp the ids, one ragged `cfm_lr`
+        call, `svc_chunks_gather_cond` over its output, one sampler call with per-row lengths, `_strip_prompt`, `_vocode`, rows
+        row0 .. of the chunk-wave buffer `waves`.  toks / ylens: by chunk; st: `_stack_targets` of the files; mel_rows /
+        style_rows: the chunks' prompt rows.  -> (vc, S, calls) as `_row_views` takes them."""
+        dev, i32 = self.device, _lib.i32_host
+        P, Pmax, pc_all = st["P"], st["Pmax"], st["prompt_condition"]
+        Dc, Cm, U = pc_all.size(2), self.cfm.in_channels, len(files)
+        top = self.cfm_lr.cfg["codebook_size"] - 1
+        n = len(ks)
+        S, nl = [ylens[k] for k in ks], [toks[k].size(1) for k in ks]
+        Pk = [P[plan[k][0]] for k in ks]
+        x_lens = [p + s for p, s in zip(Pk, S)]
+        T, Smax = max(x_lens), max(S)
+        tok = torch.zeros(n, max(nl), dtype=torch.int64, device=dev)
+        for i, k in enumerate(ks):
+            tok[i, :nl[i]] = toks[k][0]
+        tok.clamp_(max=top)          # an id above the codebook (the AR vocabulary's EOS) is no row of the embedding
+        cond = self.cfm_lr(tok, ylens=torch.LongTensor(S), in_lens=nl)[0]           # (n, Smax, Dc)
+        mu = torch.empty(n, T, Dc, device=dev)
+        _lib.check(_lib.lib().svc_chunks_gather_cond(_lib.ptr(pc_all), i32(P), U, Pmax, _lib.ptr(cond), n * Smax,
+                                                     i32([plan[k][0] for k in ks]), i32([i * Smax for i in range(n)]), i32(S),
+                                                     n, Dc, T, _lib.ptr(mu), _lib.stream_ptr()))
+        self._mark("lr_assembly")
+        z = None
+        if noise_fn is not None:
+            z = torch.zeros(n, Cm, T, device=dev)
+            for i, k in enumerate(ks):
+                z[i, :, :x_lens[i]] = _lib.f32c(noise_fn(plan[k][0], plan[k][1], x_lens[i]), dev)[0]
+        mb_seeds = [chunk_seeds[k] for k in ks] if chunk_seeds is not None else None
+        try:
+            if file_settings is None:
+                mel = self.cfm.inference(mu, x_lens, mel_rows, style_rows, None, n_timesteps,
+                                         inference_cfg_rate=list(cfg_rates), random_voice=random_voice, z=z, prompt_lens=Pk,
+                                         **_cfm_seeds(mb_seeds))
+            else:
+                mel = self.cfm.inference_rows(mu, x_lens, mel_rows, style_rows,
+                                              [file_settings[plan[k][0]] for k in ks], z=z, prompt_lens=Pk,
+                                              **_cfm_seeds(mb_seeds))
+        except RuntimeError as e:
+            i = max(range(n), key=lambda i: x_lens[i])
+            raise RuntimeError(f"{what}: file {plan[ks[i]][0]}, chunk {plan[ks[i]][1]}: the sampler refused "
+                               f"{x_lens[i]} frames (prompt {Pk[i]} + {S[i]} generated): {e}; use a smaller ar_chunk_tokens") from e
+        self._mark("cfm")
+        vc = _strip_prompt(mel, Pk, x_lens, Smax)
+        calls = _vocode(self.vocoder, vc, S, self.ragged_vocoder, what, hop=hop)
+        for call in calls:
+            r = 0
+            for a, b in call.runs:       # rows of a call -> rows of the chunk wave buffer (slices: no synchronisation)
+                waves[row0 + a:row0 + b, :call.frames * hop].copy_(call.wave[r:r + b - a])
+                r += b - a
+        return vc, S, calls
+
     @torch.inference_mode()
     def convert_long_batch(self, files, n_timesteps, cfg_rates=(0.7, 0.7), *, max_context_window, hop, convert_style=True,
                            anonymization_only=False, random_voice=False, ar_chunk_tokens=1000, overlap_frame_len=16, top_p=0.7,
@@ -887,46 +1316,22 @@ class V2HotPath:
         file_settings = _file_settings("convert_long_batch", sampler, U, n_timesteps, list(cfg_rates), random_voice)
         if U == 0:
             return ([], []) if return_parts else []
-        # (file, chunk of the file, first token, tokens, is_last), file-major
-        plan = [(u, j) + c for u, f in enumerate(files) for j, c in enumerate(v2_chunk_plan(f["src_narrow"].size(1), ar_chunk_tokens))]
+        plan = self._style_chunks("convert_long_batch", files, ar_chunk_tokens, anonymization_only)
         K, ovw = len(plan), overlap_frame_len * hop
-        Lmax = self.ar.cfg["max_seq_len"]
-        for u, j, p0, n, _ in plan:
-            t = files[u]["target"]
-            rows = n + 2 if anonymization_only else t["narrow"].size(1) + n + 2 + t["tokens"].size(1)
-            if rows > Lmax:
-                raise ValueError(f"convert_long_batch: file {u}, chunk {j}: an AR prompt of {rows} rows does not fit the cache "
-                                 f"({Lmax} positions); use a smaller ar_chunk_tokens")
         Cm = self.cfm.in_channels
         i32 = _lib.i32_host
         with torch.cuda.device(dev):
             self._mark("start")
             toks = []
             if K:
-                # AR condition of every chunk: one ragged regulator call over cat([target narrow, range]) (not assumed position-wise)
-                narrow = []
-                for u, j, p0, n, _ in plan:
-                    chunk = files[u]["src_narrow"][:, p0:p0 + n].to(dev).long()
-                    narrow.append(chunk if anonymization_only else v2_ar_prompt(files[u]["target"]["narrow"], chunk))
-                nlen = [int(x.size(1)) for x in narrow]
-                tok_in = torch.zeros(K, max(nlen), dtype=torch.int64, device=dev)
-                for k, x in enumerate(narrow):
-                    tok_in[k, :nlen[k]] = x[0]
-                ar_cond = self.ar_lr(tok_in, in_lens=nlen)[0]
-                if seeds is not None:
-                    chunk_seeds = [derive_seed(seeds[u], j) for u, j, *_ in plan]
-                    ar_seeds = chunk_seeds
-                else:
-                    chunk_seeds = None
-                    ar_seeds = torch.randint(0, 2 ** 62, (K,), dtype=torch.int64).tolist() if exp_noise_fn is None else None
+                chunk_seeds, submit = self._style_ar_requests(files, plan, anonymization_only, seeds, exp_noise_fn,
+                                                              dict(max_new=max_new, top_p=top_p, temperature=temperature,
+                                                                   repetition_penalty=repetition_penalty))
                 from .ar import ARSession
                 sess = ARSession(self.ar, steps_per_run)
-                no_target = torch.zeros(1, 0, dtype=torch.int64, device=dev)
                 try:
-                    for k, (u, j, *_) in enumerate(plan):
-                        draws = dict(exp_noise=exp_noise_fn(u, j)) if exp_noise_fn is not None else dict(seed=ar_seeds[k])
-                        sess.submit(ar_cond[k:k + 1, :nlen[k]], no_target if anonymization_only else files[u]["target"]["tokens"],
-                                    max_new=max_new, top_p=top_p, temperature=temperature, repetition_penalty=repetition_penalty, **draws)
+                    for k in range(K):
+                        submit(sess, k)
                     done = dict(sess.drain())          # tickets count from 0 in submit order: ticket k is chunk k
                 finally:
                     sess.close()
@@ -947,8 +1352,6 @@ class V2HotPath:
             live = [k for k in range(K) if ylens[k] > 0]
             if live:
                 st = self._stack_targets([f["target"] for f in files])
-                P, Pmax, pc_all = st["P"], st["Pmax"], st["prompt_condition"]
-                Dc = pc_all.size(2)
                 if U > 1:
                     idx = torch.tensor([plan[k][0] for k in live], device=dev)
                     mel_chunks, style_chunks = st["mel"].index_select(0, idx), st["style"].index_select(0, idx)
@@ -956,51 +1359,12 @@ class V2HotPath:
                     mel_chunks, style_chunks = st["mel"].expand(len(live), -1, -1), st["style"].expand(len(live), -1)
                 stride = max(ylens) * hop
                 waves = torch.empty(len(live), stride, device=dev, dtype=torch.float32)     # row i: the wave of chunk live[i]
-                top = self.cfm_lr.cfg["codebook_size"] - 1
                 for m0 in range(0, len(live), max_chunks):
                     ks = live[m0:m0 + max_chunks]
                     n = len(ks)
-                    S, nl = [ylens[k] for k in ks], [toks[k].size(1) for k in ks]
-                    Pk = [P[plan[k][0]] for k in ks]
-                    x_lens = [p + s for p, s in zip(Pk, S)]
-                    T, Smax = max(x_lens), max(S)
-                    tok = torch.zeros(n, max(nl), dtype=torch.int64, device=dev)
-                    for i, k in enumerate(ks):
-                        tok[i, :nl[i]] = toks[k][0]
-                    tok.clamp_(max=top)          # an id above the codebook (the AR vocabulary's EOS) is no row of the embedding
-                    cond = self.cfm_lr(tok, ylens=torch.LongTensor(S), in_lens=nl)[0]           # (n, Smax, Dc)
-                    mu = torch.empty(n, T, Dc, device=dev)
-                    _lib.check(_lib.lib().svc_chunks_gather_cond(_lib.ptr(pc_all), i32(P), U, Pmax, _lib.ptr(cond), n * Smax,
-                                                                 i32([plan[k][0] for k in ks]), i32([i * Smax for i in range(n)]), i32(S),
-                                                                 n, Dc, T, _lib.ptr(mu), _lib.stream_ptr()))
-                    self._mark("lr_assembly")
-                    z = None
-                    if noise_fn is not None:
-                        z = torch.zeros(n, Cm, T, device=dev)
-                        for i, k in enumerate(ks):
-                            z[i, :, :x_lens[i]] = _lib.f32c(noise_fn(plan[k][0], plan[k][1], x_lens[i]), dev)[0]
-                    mb_seeds = [chunk_seeds[k] for k in ks] if chunk_seeds is not None else None
-                    try:
-                        if file_settings is None:
-                            mel = self.cfm.inference(mu, x_lens, mel_chunks[m0:m0 + n], style_chunks[m0:m0 + n], None, n_timesteps,
-                                                     inference_cfg_rate=list(cfg_rates), random_voice=random_voice, z=z, prompt_lens=Pk,
-                                                     **_cfm_seeds(mb_seeds))
-                        else:
-                            mel = self.cfm.inference_rows(mu, x_lens, mel_chunks[m0:m0 + n], style_chunks[m0:m0 + n],
-                                                          [file_settings[plan[k][0]] for k in ks], z=z, prompt_lens=Pk,
-                                                          **_cfm_seeds(mb_seeds))
-                    except RuntimeError as e:
-                        i = max(range(n), key=lambda i: x_lens[i])
-                        raise RuntimeError(f"convert_long_batch: file {plan[ks[i]][0]}, chunk {plan[ks[i]][1]}: the sampler refused "
-                                           f"{x_lens[i]} frames (prompt {Pk[i]} + {S[i]} generated): {e}; use a smaller ar_chunk_tokens") from e
-                    self._mark("cfm")
-                    vc = _strip_prompt(mel, Pk, x_lens, Smax)
-                    calls = _vocode(self.vocoder, vc, S, self.ragged_vocoder, "convert_long_batch", hop=hop)
-                    for call in calls:
-                        r = 0
-                        for a, b in call.runs:       # rows of a call -> rows of the chunk wave buffer (slices: no synchronisation)
-                            waves[m0 + a:m0 + b, :call.frames * hop].copy_(call.wave[r:r + b - a])
-                            r += b - a
+                    vc, S, calls = self._style_micro_batch("convert_long_batch", files, plan, ks, toks, ylens, st, mel_chunks[m0:m0 + n],
+                                                           style_chunks[m0:m0 + n], waves, m0, hop, n_timesteps, cfg_rates, random_voice,
+                                                           noise_fn, chunk_seeds, file_settings)
                     if return_parts:
                         for i, (k, (mel_k, _)) in enumerate(zip(ks, _row_views(vc, S, calls))):
                             part = parts[plan[k][0]][plan[k][1]]
@@ -1019,28 +1383,33 @@ class V2HotPath:
             torch.cuda.current_stream(dev).synchronize()
         return (result, parts) if return_parts else result
 
+    def _timbre_utterances(self, files):
+        """The timbre branch's files as utterances of `_long_pool` / `_long_stream`: one ragged `cfm_lr` call over the files'
+        wide tokens with ylens = source_frames.  -> (utterances, frames per file); called under the device, with files."""
+        U, dev = len(files), self.device
+        frames = [int(f["source_frames"]) if f["src_tokens"].size(1) else 0 for f in files]
+        live = [u for u in range(U) if frames[u] > 0]
+        self._mark("start")
+        if live:
+            nw = [int(files[u]["src_tokens"].size(1)) for u in live]
+            tok = torch.zeros(len(live), max(nw), dtype=torch.int64, device=dev)
+            for i, u in enumerate(live):
+                tok[i, :nw[i]] = files[u]["src_tokens"][0]
+            cond = self.cfm_lr(tok, ylens=torch.LongTensor([frames[u] for u in live]), in_lens=nw)[0]
+        self._mark("lr_assembly")
+        none = torch.zeros(1, 0, self.cfm_lr.cfg["out_channels"], device=dev)
+        conds = [none] * U
+        for i, u in enumerate(live):
+            conds[u] = cond[i:i + 1, :frames[u]]
+        return [(conds[u], f["target"]["prompt_condition"], f["target"]["mel"], f["target"]["style"]) for u, f in enumerate(files)], frames
+
     def _convert_long_timbre(self, files, n_timesteps, cfg_rates, random_voice, hop, max_context_window, overlap_frame_len, noise_fn,
                              max_chunks, seeds, sampler=None):
         """The timbre branch of `convert_long_batch`: the CFM regulator over the files' wide tokens, then `_long_pool`."""
-        U, dev = len(files), self.device
-        if U == 0:
+        if len(files) == 0:
             return []
-        frames = [int(f["source_frames"]) if f["src_tokens"].size(1) else 0 for f in files]
-        live = [u for u in range(U) if frames[u] > 0]
-        with torch.cuda.device(dev):
-            self._mark("start")
-            if live:
-                nw = [int(files[u]["src_tokens"].size(1)) for u in live]
-                tok = torch.zeros(len(live), max(nw), dtype=torch.int64, device=dev)
-                for i, u in enumerate(live):
-                    tok[i, :nw[i]] = files[u]["src_tokens"][0]
-                cond = self.cfm_lr(tok, ylens=torch.LongTensor([frames[u] for u in live]), in_lens=nw)[0]
-            self._mark("lr_assembly")
-            none = torch.zeros(1, 0, self.cfm_lr.cfg["out_channels"], device=dev)
-            conds = [none] * U
-            for i, u in enumerate(live):
-                conds[u] = cond[i:i + 1, :frames[u]]
-            utterances = [(conds[u], f["target"]["prompt_condition"], f["target"]["mel"], f["target"]["style"]) for u, f in enumerate(files)]
+        with torch.cuda.device(self.device):
+            utterances, frames = self._timbre_utterances(files)
             pool_noise = None
             if noise_fn is not None:          # the pool asks per chunk in plan order: give each call its (file, chunk)
                 order = long_batch_plan(frames, [f["target"]["P"] for f in files], max_context_window, overlap_frame_len, hop, max_chunks)
@@ -1054,6 +1423,159 @@ class V2HotPath:
                                 dict(random_voice=True) if random_voice else None, sampler=sampler)
             self._mark("pool")
         return result
+
+    @torch.inference_mode()
+    def convert_long_stream(self, files, n_timesteps, cfg_rates=(0.7, 0.7), *, max_context_window, hop, convert_style=True,
+                            anonymization_only=False, random_voice=False, ar_chunk_tokens=1000, overlap_frame_len=16, top_p=0.7,
+                            temperature=0.7, repetition_penalty=1.5, max_new=4001, seeds=None, exp_noise_fn=None, noise_fn=None,
+                            max_chunks=64, steps_per_run=16, sampler=None, first_chunks=None, growth=4, pcm16=False, to_host=True,
+                            lookahead=1, return_parts=False):
+        """`convert_long_batch` as a generator of `StreamPiece(file, offset, wave, final, parts)`: every file's audio is handed
+        out as its chunks finish (`convert_voice_with_streaming` hands each chunk's audio to its caller; here for many files
+        at once).  The keywords are `convert_long_batch`'s plus `HotPath.convert_long_stream`'s first_chunks, growth, pcm16,
+        to_host and lookahead; `collect_stream(pieces, len(files))` gives the waves `convert_long_batch` returns.  Everything
+        runs on the current stream; argument errors are raised at the first next(), before anything is enqueued.
+
+        convert_style=False (timbre branch): the ragged `cfm_lr` call, then the generator behind `HotPath.convert_long_stream`.
+
+        convert_style=True (style branch): the chunks are submitted to the `ARSession` chunk-major (`stream_schedule`'s order:
+        chunk 0 of every file first).  After every `sess.step()` the retired chunks join a ready list; micro-batch m of the
+        ramp is launched once min(its size, chunks not yet dispatched) chunks are ready, lowest (chunk, file) first: regulator,
+        sampler and vocoder (`_style_micro_batch`, the pool's body), then one `svc_chunks_emit` for the pieces the splicer
+        released, one copy into pinned memory, one event.  AR steps and sampler work interleave on one stream; an AR step reads
+        its token counts, so what was enqueued before it is finished when it returns and is handed out then.  A chunk's
+        length is the AR model's decision: the splicer gets ylen * hop when the chunk is dispatched, and a chunk may complete
+        before an earlier chunk of its file -- its wave is kept on the device until the file's pieces up to it are released.
+        The session is closed in a `finally`: closing the generator early leaves the models usable.
+
+        return_parts (style branch): pieces carry `parts`, a list of dict(file, chunk, tokens, ylen, mel, wave, kept) for the
+        chunks dispatched since the previous piece that carried parts (None on the other pieces)."""
+        what = "convert_long_stream"
+        U, dev = len(files), self.device
+        if seeds is not None and (exp_noise_fn is not None or noise_fn is not None):
+            raise ValueError(f"{what}: give seeds or exp_noise_fn / noise_fn, not both")
+        seeds = _seed_list(what, seeds, U)
+        if max_chunks < 1:
+            raise ValueError(f"{what}: max_chunks = {max_chunks}, at least one chunk per micro-batch is needed")
+        if lookahead < 0:
+            raise ValueError(f"{what}: lookahead = {lookahead}, a count of micro-batches enqueued ahead")
+        if not convert_style:
+            if exp_noise_fn is not None or return_parts:
+                raise ValueError(f"{what}: exp_noise_fn and return_parts belong to the style branch (convert_style=True)")
+            if U == 0:
+                return
+            with torch.cuda.device(dev):
+                utterances, _ = self._timbre_utterances(files)
+            yield from _long_stream(what, self.cfm, self.vocoder, utterances, n_timesteps, list(cfg_rates), hop, max_context_window,
+                                    overlap_frame_len, noise_fn, None, max_chunks, first_chunks, growth, self.ragged_vocoder, seeds,
+                                    lambda s: _vocoder_seeds(self.vocoder, s), pcm16, to_host, lookahead,
+                                    dict(random_voice=True) if random_voice else None, sampler=sampler)
+            return
+        v2_chunk_plan(0, ar_chunk_tokens)          # its ValueError, with or without files
+        file_settings = _file_settings(what, sampler, U, n_timesteps, list(cfg_rates), random_voice)
+        plan = self._style_chunks(what, files, ar_chunk_tokens, anonymization_only)
+        n_chunks = [sum(1 for c in plan if c[0] == u) for u in range(U)]
+        ramp = _ramp_args(what, n_chunks, first_chunks, growth, max_chunks)
+        if U == 0:
+            return
+        K, ovw, Cm = len(plan), overlap_frame_len * hop, self.cfm.in_channels
+        index = {c[:2]: k for k, c in enumerate(plan)}
+        submit_order = [index[uj] for uj in stream_schedule(n_chunks)["order"]]        # chunk-major; ticket t is chunk submit_order[t]
+        splicer = _StreamSplicer(U, n_chunks, ovw)
+        with torch.cuda.device(dev):
+            out = _StreamOut(dev, ovw, pcm16, to_host)
+            out.push(splicer.start(), None, {})
+        if K == 0:
+            while out.pending:
+                yield from out.pop()
+            return
+        toks, ylens, old_waves = {}, {}, {}
+
+        def launch(ks):
+            """One micro-batch: the chunks ks (plan indices) -> sampler and vocoder for those with frames, emit for what the
+            splicer releases."""
+            live = [k for k in ks if ylens[k] > 0]
+            pieces, parts = [], []
+            for k in ks:
+                u, j, _, _, is_last = plan[k]
+                pieces += splicer.complete(u, j, ylens[k] * hop, is_last)
+            # rows 0 .. of this micro-batch's buffer are its own chunks; behind them, what the pieces need of older chunks:
+            # samples `skip` .. of a chunk delivered late, the last ovw samples of one that is only faded out
+            rows = {plan[k][:2]: (i, ylens[k] * hop, 0) for i, k in enumerate(live)}
+            skip = {}
+            for p in pieces:
+                if p.chunk >= 0 and (p.file, p.chunk) not in rows:
+                    skip[(p.file, p.chunk)] = min(skip.get((p.file, p.chunk), p.begin), p.begin)
+                if p.prev_chunk >= 0 and p.begin < min(p.end, ovw) and (p.file, p.prev_chunk) not in rows:
+                    skip[(p.file, p.prev_chunk)] = min(skip.get((p.file, p.prev_chunk), p.prev_len - ovw), p.prev_len - ovw)
+            for i, (uj, first) in enumerate(skip.items()):
+                rows[uj] = (len(live) + i, old_waves[uj].size(1) - first, first)
+            stride = max([1] + [r[1] for r in rows.values()])
+            waves = torch.empty(len(rows), -(-stride // 4) * 4, device=dev, dtype=torch.float32)
+            if live:
+                st = self._stack_targets([f["target"] for f in files])
+                if U > 1:
+                    idx = torch.tensor([plan[k][0] for k in live], device=dev)
+                    mel_rows, style_rows = st["mel"].index_select(0, idx), st["style"].index_select(0, idx)
+                else:
+                    mel_rows, style_rows = st["mel"].expand(len(live), -1, -1), st["style"].expand(len(live), -1)
+                vc, S, calls = self._style_micro_batch(what, files, plan, live, toks, ylens, st, mel_rows, style_rows, waves, 0, hop,
+                                                       n_timesteps, cfg_rates, random_voice, noise_fn, chunk_seeds, file_settings)
+                mels = dict(zip(live, (m for m, _ in _row_views(vc, S, calls))))
+                for i, k in enumerate(live):
+                    old_waves[plan[k][:2]] = waves[i:i + 1, :ylens[k] * hop]
+                self._mark("strip_vocoder")
+            for uj, first in skip.items():
+                waves[rows[uj][0], :rows[uj][1]].copy_(old_waves[uj][0, first:])
+            if return_parts:
+                for k in ks:
+                    n, live_k = ylens[k] * hop, ylens[k] > 0
+                    parts.append(dict(file=plan[k][0], chunk=plan[k][1], tokens=toks[k], ylen=ylens[k],
+                                      mel=mels[k] if live_k else torch.zeros(1, Cm, 0, device=dev),
+                                      wave=old_waves[plan[k][:2]] if live_k else torch.zeros(1, 0, device=dev),
+                                      kept=n > 0 and (n >= 2 * ovw or bool(plan[k][4]))))
+            out.push(pieces, waves, rows, parts if return_parts else None)
+            self._mark("emit")
+            for p in pieces:
+                if p.final:          # the file is spliced: its chunk waves are not needed any more
+                    for uj in [uj for uj in old_waves if uj[0] == p.file]:
+                        del old_waves[uj]
+
+        from .ar import ARSession
+        with torch.cuda.device(dev):
+            self._mark("start")
+            chunk_seeds, submit = self._style_ar_requests(files, plan, anonymization_only, seeds, exp_noise_fn,
+                                                          dict(max_new=max_new, top_p=top_p, temperature=temperature,
+                                                               repetition_penalty=repetition_penalty))
+            sess = ARSession(self.ar, steps_per_run)
+        try:
+            with torch.cuda.device(dev):
+                for k in submit_order:
+                    submit(sess, k)
+            ready, dispatched, m = [], 0, 0
+            while dispatched < K:
+                size = min(_ramp_size(m, *ramp), K - dispatched)
+                if len(ready) >= size:
+                    ready.sort()
+                    with torch.cuda.device(dev):
+                        launch([k for _, _, k in ready[:size]])
+                    del ready[:size]
+                    dispatched, m = dispatched + size, m + 1
+                    while len(out.pending) > lookahead:
+                        yield from out.pop()
+                    continue
+                with torch.cuda.device(dev):
+                    retired = sess.step()
+                for t, tk in retired:
+                    k = submit_order[t]
+                    toks[k], ylens[k] = tk, v2_target_frames(files[plan[k][0]]["frames_per_token"], tk.size(1))
+                    ready.append((plan[k][1], plan[k][0], k))
+                while out.pending:          # the step read its token counts: everything enqueued before it is finished
+                    yield from out.pop()
+            while out.pending:
+                yield from out.pop()
+        finally:
+            sess.close()
 
 
 # ----------------------------------------------------------------------------------------- real-time sessions
