@@ -1456,6 +1456,41 @@ int svc_op_kgemm(const svc_kgemm_t* args, void* stream);
  * column permutation of a natural-order V^T buffer [rows][vt_ld] (16-bit words, device) into order `mode` (vt_pos), as
  * svc_op_attention applies it; synchronises.  Refused: NULL vt, rows < 1, vt_ld < 32 or not a multiple of 32, mode outside 0 .. 2. */
 int svc_op_permute_vt(uint16_t* vt, int64_t rows, int64_t vt_ld, int mode, void* stream);
+/* Test aid (tests/test_gpu_lr_ops.py; no model uses it): ONE launch of one of the length regulator's four kernels (csrc/lr.hip)
+ * through the launch function svc_lr_forward calls, with the model's grid and block, on caller buffers; synchronises.  Device
+ * pointers unless noted; NULL = absent.  Activations are channels-last rows of ld floats, utterance b at row b tout_max.
+ *   stage 0 gather     x [B][tout_max][ld] (written whole) = row src of feat [B][tin_max][ld_feat] or of emb [.][C] at tokens
+ *                      [B][tin_max] (int64; their values are device data and the caller's to keep inside the table), src =
+ *                      interpolate ? min(floor(t (float)in_lens[b] / (float)ylens[b]), in_lens[b] - 1) : t; with f0_emb
+ *                      [n_bins][C]: + f0_emb[bin(f0[b][nearest index over f0_lens[b]])] (f0 [B][tf0_max]), or + f0_mask [C]
+ *                      when f0 is NULL; rows t >= ylens[b] and columns [C, ld) are zeros
+ *   stage 1 gn_stats   stats [B][32][2] doubles: workgroup i's (sum, sum of squares) over rows [i rpb, min((i + 1) rpb, ylens[b]))
+ *                      x C of x, rpb = ceil(ylens[b] / 32); zeros where it has no row
+ *   stage 2 gn_mish    x = Mish(GroupNorm(x; the 32 partials of stats folded in index order, gamma [C], beta [C], eps)) in place;
+ *                      rows t >= ylens[b] and columns [C, ld) become zeros
+ *   stage 3 mask_copy  out [B][tout_max][ld_out] columns [0, N) = x [B][tout_max][ld] for t < ylens[b], else zeros
+ * ylens, in_lens and f0_lens are HOST arrays of B entries.  Refused (nothing allocated or launched): NULL args, ylens or x; stage
+ * outside 0 .. 3; B outside 1 .. 65535; tout_max < 1; ylens[b] outside [0, tout_max]; stages 0 .. 2: C < 1 or ld < C; stage 0: feat
+ * and tokens both or neither, ld_feat < C, tokens without emb, tin_max < 1, NULL in_lens, in_lens[b] outside [1, tin_max],
+ * ylens[b] > in_lens[b] without interpolate, f0 without f0_emb, n_bins < 2, f0_emb with neither f0 nor f0_mask, f0 with tf0_max < 1,
+ * NULL f0_lens or f0_lens[b] outside [1, tf0_max]; stages 1 and 2: NULL stats; stage 2: NULL gamma or beta, eps <= 0; stage 3: NULL
+ * out, N < 1, ld < N or ld_out < N.  check_only != 0: return 0 once every check has passed, before the first allocation. */
+typedef struct {
+    int32_t stage;
+    int32_t B, tout_max, C, ld;
+    const int32_t* ylens;
+    float* x;
+    const float* feat; int64_t ld_feat; int32_t tin_max;
+    const int64_t* tokens; const float* emb;
+    const int32_t* in_lens; int32_t interpolate;
+    const float* f0; int32_t tf0_max; const int32_t* f0_lens;
+    const float* f0_emb; const float* f0_mask; int32_t n_bins;
+    double* stats;
+    const float* gamma; const float* beta; float eps;
+    float* out; int32_t ld_out, N;
+    int32_t check_only;
+} svc_lr_op_t;
+int svc_op_lr(const svc_lr_op_t* args, void* stream);
 
 /* Optional launch timing: HIP events around every tap-GEMM / attention launch on its stream.
  * svc_prof_collect fills out[cls*4 + {0..3}] = {launches, total ms, algorithmic flops, algorithmic bytes}

@@ -47,7 +47,7 @@ EXPORTS = [
     "svc_prof_enable", "svc_prof_collect",
     "svc_op_linear", "svc_op_conv1d", "svc_op_conv1d_ex", "svc_op_conv1d_last_took", "svc_op_dit_panel", "svc_op_conv_transpose1d", "svc_op_attention", "svc_op_attention_ex", "svc_op_rmsnorm",
     "svc_op_layernorm", "svc_op_layernorm_gelu", "svc_op_act_cl", "svc_op_hift_signal", "svc_op_ar_sampler",
-    "svc_op_ar_attn", "svc_op_ar_linear", "svc_op_kgemm", "svc_op_permute_vt",
+    "svc_op_ar_attn", "svc_op_ar_linear", "svc_op_kgemm", "svc_op_permute_vt", "svc_op_lr",
 ]
 
 
@@ -244,6 +244,16 @@ class KGemm(C.Structure):
                 ("vt", C.c_void_p), ("vt_ld", C.c_int64), ("vt_mode", C.c_int32), ("check_only", C.c_int32)]
 
 
+class LrOp(C.Structure):
+    """svc_lr_op_t: the arguments of svc_op_lr (test aid)."""
+    _fields_ = [(n, C.c_int32) for n in ("stage", "B", "tout_max", "C", "ld")] + \
+               [("ylens", C.POINTER(C.c_int32)), ("x", C.c_void_p), ("feat", C.c_void_p), ("ld_feat", C.c_int64), ("tin_max", C.c_int32),
+                ("tokens", C.c_void_p), ("emb", C.c_void_p), ("in_lens", C.POINTER(C.c_int32)), ("interpolate", C.c_int32),
+                ("f0", C.c_void_p), ("tf0_max", C.c_int32), ("f0_lens", C.POINTER(C.c_int32)), ("f0_emb", C.c_void_p),
+                ("f0_mask", C.c_void_p), ("n_bins", C.c_int32), ("stats", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p),
+                ("eps", C.c_float), ("out", C.c_void_p), ("ld_out", C.c_int32), ("N", C.c_int32), ("check_only", C.c_int32)]
+
+
 _lib = None
 
 
@@ -317,6 +327,7 @@ def lib():
         l.svc_op_ar_linear.argtypes = [C.POINTER(ArLinear), C.c_void_p]
         l.svc_op_kgemm.argtypes = [C.POINTER(KGemm), C.c_void_p]
         l.svc_op_permute_vt.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p]
+        l.svc_op_lr.argtypes = [C.POINTER(LrOp), C.c_void_p]
         # seeded noise: 64-bit seeds by value and as HOST arrays
         l.svc_cfm_sample_seeded.argtypes = [C.c_void_p, C.POINTER(CfmArgs), C.POINTER(C.c_uint64), C.c_void_p]
         l.svc_cfm_noise_draws.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]

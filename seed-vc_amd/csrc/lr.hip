@@ -77,12 +77,17 @@ __global__ void lr_gather_kernel(const float* __restrict__ feat, long ld_feat, i
     }
 }
 
-// GroupNorm(1, C) statistics of one utterance: sum and sum of squares over its ylens[b] x C values (double)
+// GroupNorm(1, C) statistics of one utterance: sum and sum of squares over its ylens[b] x C values (double), as LR_GN_PARTS
+// partials in fixed slots: workgroup i of utterance b sums rows [i rpb, min((i + 1) rpb, len)), rpb = ceil(len / LR_GN_PARTS),
+// and writes stats[b][i][0..1] (zeros where it has no row).  No atomics: the consumer folds the slots in index order, so the
+// statistics of an utterance are the same bits whatever else the launch holds.
+constexpr int LR_GN_PARTS = 32;
+
 __global__ __launch_bounds__(256) void lr_gn_stats_kernel(const float* __restrict__ x, int tmax, int ld, int C,
                                                           const int* __restrict__ ylens, double* __restrict__ stats) {
     const int b = blockIdx.y;
     const int len = ylens[b];
-    const int rows_per_block = (len + gridDim.x - 1) / gridDim.x;
+    const int rows_per_block = (len + LR_GN_PARTS - 1) / LR_GN_PARTS;
     const int r0 = blockIdx.x * rows_per_block;
     const int r1 = min(r0 + rows_per_block, len);
     double s = 0.0, q = 0.0;
@@ -105,9 +110,10 @@ __global__ __launch_bounds__(256) void lr_gn_stats_kernel(const float* __restric
         }
         __syncthreads();
     }
-    if (threadIdx.x == 0 && r1 > r0) {
-        atomicAdd(&stats[2 * b], sh[0][0]);
-        atomicAdd(&stats[2 * b + 1], sh[1][0]);
+    if (threadIdx.x == 0) {
+        double* slot = stats + ((long)b * LR_GN_PARTS + blockIdx.x) * 2;
+        slot[0] = sh[0][0];
+        slot[1] = sh[1][0];
     }
 }
 
@@ -122,9 +128,14 @@ __global__ void lr_gn_mish_kernel(float* __restrict__ x, int tmax, int ld, int C
         for (int c = threadIdx.x; c < ld; c += blockDim.x) row[c] = 0.f;
         return;
     }
+    double s = 0.0, q = 0.0;                   // the partials of lr_gn_stats_kernel, folded in index order
+    for (int i = 0; i < LR_GN_PARTS; ++i) {
+        s += stats[((long)b * LR_GN_PARTS + i) * 2];
+        q += stats[((long)b * LR_GN_PARTS + i) * 2 + 1];
+    }
     const double n = (double)len * C;
-    const double mean = stats[2 * b] / n;
-    double var = stats[2 * b + 1] / n - mean * mean;
+    const double mean = s / n;
+    double var = q / n - mean * mean;
     var = var > 0.0 ? var : 0.0;
     const float rstd = (float)(1.0 / sqrt(var + (double)eps));
     const float mu = (float)mean;
@@ -147,6 +158,47 @@ __global__ void lr_mask_copy_kernel(const float* __restrict__ src, int ld_src, f
     const float* s = src + ((long)b * tmax + t) * ld_src;
     float* d = out + ((long)b * tmax + t) * ld_out;
     for (int c = threadIdx.x; c < N; c += blockDim.x) d[c] = ok ? s[c] : 0.f;
+}
+
+// The four launches, one function each: svc_lr_forward and the parity tests' svc_op_lr call the same ones.  Lengths are DEVICE arrays.
+struct GatherArgs {
+    const float* feat = nullptr; long ld_feat = 0; int tin_max = 0;
+    const long* tokens = nullptr; const float* emb = nullptr;
+    const int* in_lens = nullptr; const int* ylens = nullptr; int interpolate = 0;
+    const float* f0 = nullptr; int tf0_max = 0; const int* f0_lens = nullptr;
+    const float* f0_emb = nullptr; const float* f0_mask = nullptr; int n_bins = 0;
+};
+
+int lr_gather_launch(const GatherArgs& g, float* out, int B, int tout_max, int C, int ld, hipStream_t st) {
+    // a, b of f0_to_coarse are Python doubles in the reference; the tensor arithmetic runs in fp32
+    const double mel_min = 1127.0 * log(1.0 + 50.0 / 700.0), mel_max = 1127.0 * log(1.0 + 1100.0 / 700.0);
+    const double fa = g.f0_emb ? (g.n_bins - 2) / (mel_max - mel_min) : 0.0;
+    const double fb = mel_min * fa - 1.0;
+    hipLaunchKernelGGL(lr_gather_kernel, dim3(tout_max, B), dim3(128), 0, st, g.feat, g.ld_feat, g.tin_max, g.tokens, g.emb, g.in_lens,
+                       g.ylens, g.interpolate, g.f0, g.tf0_max, g.f0_lens, g.f0_emb, g.f0_mask, g.n_bins, (float)fa, (float)fb, out,
+                       tout_max, C, ld);
+    SVC_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int lr_gn_stats_launch(const float* x, int B, int tout_max, int ld, int C, const int* ylens, double* stats, hipStream_t st) {
+    hipLaunchKernelGGL(lr_gn_stats_kernel, dim3(LR_GN_PARTS, B), dim3(256), 0, st, x, tout_max, ld, C, ylens, stats);
+    SVC_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int lr_gn_mish_launch(float* x, int B, int tout_max, int ld, int C, const int* ylens, const double* stats, const float* gamma,
+                      const float* beta, float eps, hipStream_t st) {
+    hipLaunchKernelGGL(lr_gn_mish_kernel, dim3(tout_max, B), dim3(128), 0, st, x, tout_max, ld, C, ylens, stats, gamma, beta, eps);
+    SVC_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int lr_mask_copy_launch(const float* src, int ld_src, float* out, int ld_out, int N, int B, int tout_max, const int* ylens,
+                        hipStream_t st) {
+    hipLaunchKernelGGL(lr_mask_copy_kernel, dim3(tout_max, B), dim3(128), 0, st, src, ld_src, out, ld_out, N, tout_max, ylens);
+    SVC_CHECK_HIP(hipGetLastError());
+    return 0;
 }
 
 // nn.Linear weight [N][K] -> ConvW with one tap (fp32 operands)
@@ -203,7 +255,7 @@ struct svc_lr {
         d_in_lens = work.alloc_n<int>(cap_B, st);
         d_ylens = work.alloc_n<int>(cap_B, st);
         d_f0_lens = work.alloc_n<int>(cap_B, st);
-        stats = work.alloc_n<double>((size_t)2 * cap_B * std::max(1, cfg.n_convs), st);
+        stats = work.alloc_n<double>((size_t)2 * LR_GN_PARTS * cap_B, st);      // [B][LR_GN_PARTS][2], reused by every conv
         if ((inp && !h0) || !a || !y || !d_in_lens || !d_ylens || !d_f0_lens || !stats) return 1;
         return 0;
     }
@@ -305,31 +357,26 @@ int svc_lr_forward(svc_lr_t* m, const float* x, const int64_t* tokens, const int
     }
     // 2. nearest interpolation (+ f0 embedding) -> a
     {
-        // a, b of f0_to_coarse are Python doubles in the reference; the tensor arithmetic runs in fp32
-        const double mel_min = 1127.0 * log(1.0 + 50.0 / 700.0), mel_max = 1127.0 * log(1.0 + 1100.0 / 700.0);
-        const double fa = c.f0_condition ? (c.n_f0_bins - 2) / (mel_max - mel_min) : 0.0;
-        const double fb = mel_min * fa - 1.0;
-        hipLaunchKernelGGL(lr_gather_kernel, dim3(tout_max, B), dim3(128), 0, st, m->h0, (long)Cp, tin_max,
-                           reinterpret_cast<const long*>(tokens), m->emb, m->d_in_lens, m->d_ylens, c.interpolate, f0, tf0_max,
-                           m->d_f0_lens, c.f0_condition ? m->f0_emb : nullptr, m->f0_mask, c.n_f0_bins, (float)fa, (float)fb,
-                           m->a, tout_max, C, Cp);
-        SVC_CHECK_HIP(hipGetLastError());
+        GatherArgs g;
+        g.feat = m->h0; g.ld_feat = Cp; g.tin_max = tin_max;
+        g.tokens = reinterpret_cast<const long*>(tokens); g.emb = m->emb;
+        g.in_lens = m->d_in_lens; g.ylens = m->d_ylens; g.interpolate = c.interpolate;
+        g.f0 = f0; g.tf0_max = tf0_max; g.f0_lens = m->d_f0_lens;
+        g.f0_emb = c.f0_condition ? m->f0_emb : nullptr; g.f0_mask = m->f0_mask; g.n_bins = c.n_f0_bins;
+        if (lr_gather_launch(g, m->a, B, tout_max, C, Cp, st)) return 1;
     }
     // 3. conv stack
     float* cur = m->a;
     float* nxt = m->y;
-    if (c.n_convs) SVC_CHECK_HIP(hipMemsetAsync(m->stats, 0, sizeof(double) * 2 * B * c.n_convs, st));
     for (int i = 0; i < c.n_convs; ++i) {
         ConvRun r;
         r.a.hi = cur; r.B = B; r.Lin = tout_max; r.Lout = tout_max; r.pad_left = 1;
         r.seq_len = m->d_ylens;
         r.c32 = nxt; r.ldc32 = Cp;
         if (conv1d_run(m->convs[i], r, st)) return 1;
-        double* stt = m->stats + (size_t)2 * B * i;
-        hipLaunchKernelGGL(lr_gn_stats_kernel, dim3(32, B), dim3(256), 0, st, nxt, tout_max, Cp, C, m->d_ylens, stt);
-        hipLaunchKernelGGL(lr_gn_mish_kernel, dim3(tout_max, B), dim3(128), 0, st, nxt, tout_max, Cp, C, m->d_ylens, stt,
-                           m->gn_w[i], m->gn_b[i], 1e-5f);
-        SVC_CHECK_HIP(hipGetLastError());
+        // every slot of stats is rewritten by each stats launch, and the stream orders it behind the previous conv's reader
+        if (lr_gn_stats_launch(nxt, B, tout_max, Cp, C, m->d_ylens, m->stats, st)) return 1;
+        if (lr_gn_mish_launch(nxt, B, tout_max, Cp, C, m->d_ylens, m->stats, m->gn_w[i], m->gn_b[i], 1e-5f, st)) return 1;
         std::swap(cur, nxt);
     }
     // 4. tail + mask
@@ -344,9 +391,78 @@ int svc_lr_forward(svc_lr_t* m, const float* x, const int64_t* tokens, const int
         fin = nxt;
         ld_fin = m->tail.cout_pad;
     }
-    hipLaunchKernelGGL(lr_mask_copy_kernel, dim3(tout_max, B), dim3(128), 0, st, fin, ld_fin, out, c.out_channels,
-                       c.out_channels, tout_max, m->d_ylens);
-    SVC_CHECK_HIP(hipGetLastError());
+    return lr_mask_copy_launch(fin, ld_fin, out, c.out_channels, c.out_channels, B, tout_max, m->d_ylens, st);
+}
+
+// ONE launch of one of the four kernels above on caller buffers (tests/test_gpu_lr_ops.py): the checks, then the lengths to the
+// device, the launch function the model calls, a synchronisation.
+int svc_op_lr(const svc_lr_op_t* e, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    SVC_REQUIRE(e, "svc_op_lr: null argument");
+    SVC_REQUIRE(e->stage >= 0 && e->stage <= 3, "svc_op_lr: stage is 0 .. 3");
+    const int B = e->B, T = e->tout_max;
+    SVC_REQUIRE(B >= 1 && B <= 65535, "svc_op_lr: B is 1 .. 65535");
+    SVC_REQUIRE(T >= 1, "svc_op_lr: tout_max is positive");
+    SVC_REQUIRE(e->ylens, "svc_op_lr: ylens is required");
+    for (int b = 0; b < B; ++b) SVC_REQUIRE(e->ylens[b] >= 0 && e->ylens[b] <= T, "svc_op_lr: ylens out of range");
+    SVC_REQUIRE(e->x, "svc_op_lr: x is required");
+    if (e->stage == 3) {
+        SVC_REQUIRE(e->out, "svc_op_lr: mask_copy needs out");
+        SVC_REQUIRE(e->N >= 1 && e->ld >= e->N && e->ld_out >= e->N, "svc_op_lr: mask_copy: 1 <= N <= ld and N <= ld_out");
+    } else {
+        SVC_REQUIRE(e->C >= 1 && e->ld >= e->C, "svc_op_lr: 1 <= C <= ld");
+    }
+    if (e->stage == 0) {
+        SVC_REQUIRE(!e->feat != !e->tokens, "svc_op_lr: gather reads feat or tokens, not both");
+        SVC_REQUIRE(!e->feat || e->ld_feat >= e->C, "svc_op_lr: ld_feat covers C");
+        SVC_REQUIRE(!e->tokens || e->emb, "svc_op_lr: tokens need emb");
+        SVC_REQUIRE(e->tin_max >= 1 && e->in_lens, "svc_op_lr: tin_max is positive, in_lens is required");
+        for (int b = 0; b < B; ++b) {
+            SVC_REQUIRE(e->in_lens[b] >= 1 && e->in_lens[b] <= e->tin_max, "svc_op_lr: in_lens out of range");
+            SVC_REQUIRE(e->interpolate || e->ylens[b] <= e->in_lens[b], "svc_op_lr: without interpolate ylens must not exceed in_lens");
+        }
+        SVC_REQUIRE(!e->f0 || e->f0_emb, "svc_op_lr: f0 needs f0_emb");
+        SVC_REQUIRE(!e->f0_emb || e->n_bins >= 2, "svc_op_lr: n_bins is at least 2");
+        SVC_REQUIRE(!e->f0_emb || e->f0 || e->f0_mask, "svc_op_lr: f0_emb without f0 needs f0_mask");
+        if (e->f0) {
+            SVC_REQUIRE(e->tf0_max >= 1 && e->f0_lens, "svc_op_lr: tf0_max is positive, f0_lens is required");
+            for (int b = 0; b < B; ++b) SVC_REQUIRE(e->f0_lens[b] >= 1 && e->f0_lens[b] <= e->tf0_max, "svc_op_lr: f0_lens out of range");
+        }
+    } else if (e->stage == 1 || e->stage == 2) {
+        SVC_REQUIRE(e->stats, "svc_op_lr: stats is required");
+        SVC_REQUIRE(e->stage == 1 || (e->gamma && e->beta && e->eps > 0.f), "svc_op_lr: gn_mish needs gamma, beta and eps > 0");
+    }
+    if (e->check_only) return 0;
+    Arena ar;
+    auto to_device = [&](const int32_t* h, const int** out) -> int {      // the caller's array is pageable: synchronise before it may go
+        *out = nullptr;
+        if (!h) return 0;
+        int* d = ar.alloc_n<int>(B, st);
+        if (!d) return 1;
+        SVC_CHECK_HIP(hipMemcpyAsync(d, h, B * sizeof(int), hipMemcpyHostToDevice, st));
+        SVC_CHECK_HIP(hipStreamSynchronize(st));
+        *out = d;
+        return 0;
+    };
+    const int *d_ylens, *d_in_lens, *d_f0_lens;
+    if (to_device(e->ylens, &d_ylens) || to_device(e->stage == 0 ? e->in_lens : nullptr, &d_in_lens) ||
+        to_device(e->stage == 0 && e->f0 ? e->f0_lens : nullptr, &d_f0_lens)) return 1;
+    if (e->stage == 0) {
+        GatherArgs g;
+        g.feat = e->feat; g.ld_feat = (long)e->ld_feat; g.tin_max = e->tin_max;
+        g.tokens = reinterpret_cast<const long*>(e->tokens); g.emb = e->emb;
+        g.in_lens = d_in_lens; g.ylens = d_ylens; g.interpolate = e->interpolate;
+        g.f0 = e->f0; g.tf0_max = e->tf0_max; g.f0_lens = d_f0_lens;
+        g.f0_emb = e->f0_emb; g.f0_mask = e->f0_mask; g.n_bins = e->n_bins;
+        if (lr_gather_launch(g, e->x, B, T, e->C, e->ld, st)) return 1;
+    } else if (e->stage == 1) {
+        if (lr_gn_stats_launch(e->x, B, T, e->ld, e->C, d_ylens, e->stats, st)) return 1;
+    } else if (e->stage == 2) {
+        if (lr_gn_mish_launch(e->x, B, T, e->ld, e->C, d_ylens, e->stats, e->gamma, e->beta, e->eps, st)) return 1;
+    } else {
+        if (lr_mask_copy_launch(e->x, e->ld, e->out, e->ld_out, e->N, B, T, d_ylens, st)) return 1;
+    }
+    SVC_CHECK_HIP(hipStreamSynchronize(st));
     return 0;
 }
 

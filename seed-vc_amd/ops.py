@@ -710,6 +710,88 @@ def permute_vt(vt, mode):
     return out
 
 
+LR_STAGES = {"gather": 0, "gn_stats": 1, "gn_mish": 2, "mask_copy": 3}
+LR_GN_PARTS = 32          # lr.hip's LR_GN_PARTS: the partials of the GroupNorm statistics per utterance
+
+
+def lr_stage(a, device="cuda:0", guard=2, fill32=-777.25):
+    """Test aid over svc_op_lr (include/seedvc_hip.h): ONE launch of one length-regulator kernel.  a: stage (a key of LR_STAGES),
+    tout_max, C, ld, ylens (list; B = its length), plus
+      gather     feat (B, tin_max, ld_feat) fp32 | tokens (B, tin_max) int64 + emb (codebook, C); in_lens (list), interpolate;
+                 f0_emb (n_bins, C) with f0 (B, tf0_max) + f0_lens (list), or with f0_mask (C,)
+      gn_stats   x (B, tout_max, ld)
+      gn_mish    x (B, tout_max, ld), stats (B, 32, 2) float64, gamma (C,), beta (C,), eps
+      mask_copy  x (B, tout_max, ld), N, ld_out
+    Returns dict(guard, inputs = {name: the device buffer of every tensor the kernel only reads, AFTER the launch}, and the
+    written buffer WHOLE, `guard` canary rows in front and behind holding fill32: x (guard + B tout_max + guard, ld) for gather
+    and gn_mish (in place on a copy of a["x"]), stats (guard + 32 B + guard, 2) float64, out (guard + B tout_max + guard, ld_out))."""
+    import ctypes as C
+    dev = torch.device(device)
+    with torch.cuda.device(dev):
+        b = _ArOpBuffers(dev, guard, fill32, 0)
+        e = _lib.LrOp()
+        stage = a["stage"]
+        e.stage = LR_STAGES[stage] if stage in LR_STAGES else int(stage)
+        ylens = [int(v) for v in a["ylens"]]
+        B = len(ylens)
+        e.B, e.tout_max, e.C, e.ld = B, int(a["tout_max"]), int(a.get("C") or 0), int(a["ld"])
+        rows = B * e.tout_max
+        host = [_lib.i32_host(ylens)]
+        e.ylens = C.cast(host[0], C.POINTER(C.c_int32))
+        e.check_only = int(a.get("check_only") or 0)
+        out, inputs = {"guard": guard}, {}
+
+        def read_only(name, t, dtype=torch.float32):
+            ptr = b.put(t, dtype)
+            inputs[name] = b.keep[-1]
+            return ptr
+
+        def lens(name):
+            assert len(a[name]) == B, name
+            host.append(_lib.i32_host([int(v) for v in a[name]]))
+            return C.cast(host[-1], C.POINTER(C.c_int32))
+        if stage == "gather":
+            if a.get("tokens") is not None:
+                tok = a["tokens"]
+                assert tok.dim() == 2 and tok.shape[0] == B and tuple(a["emb"].shape[1:]) == (e.C,)
+                assert 0 <= int(tok.min()) and int(tok.max()) < a["emb"].shape[0], "tokens lie inside the table"
+                e.tokens, e.emb, e.tin_max = read_only("tokens", tok, torch.int64), read_only("emb", a["emb"]), tok.shape[1]
+            else:
+                feat = a["feat"]
+                assert feat.dim() == 3 and feat.shape[0] == B
+                e.feat, e.ld_feat, e.tin_max = read_only("feat", feat), feat.shape[2], feat.shape[1]
+            e.in_lens, e.interpolate = lens("in_lens"), int(a["interpolate"])
+            if a.get("f0_emb") is not None:
+                assert a["f0_emb"].dim() == 2 and a["f0_emb"].shape[1] == e.C
+                e.f0_emb, e.n_bins = read_only("f0_emb", a["f0_emb"]), a["f0_emb"].shape[0]
+                if a.get("f0_mask") is not None:
+                    assert a["f0_mask"].numel() == e.C
+                    e.f0_mask = read_only("f0_mask", a["f0_mask"])
+            if a.get("f0") is not None:
+                assert a["f0"].dim() == 2 and a["f0"].shape[0] == B
+                e.f0, e.tf0_max, e.f0_lens = read_only("f0", a["f0"]), a["f0"].shape[1], lens("f0_lens")
+            out["x"], e.x = b.guarded(rows, e.ld)
+        else:
+            x = a["x"]
+            assert tuple(x.shape) == (B, e.tout_max, e.ld) and x.dtype == torch.float32
+            if stage == "gn_mish":
+                out["x"], e.x = b.guarded(rows, e.ld, init=x.reshape(rows, e.ld))
+            else:
+                e.x = read_only("x", x)
+            if stage == "gn_stats":
+                out["stats"], e.stats = b.guarded(LR_GN_PARTS * B, 2, dtype=torch.float64)
+            elif stage == "gn_mish":
+                assert tuple(a["stats"].shape) == (B, LR_GN_PARTS, 2) and a["gamma"].numel() == e.C and a["beta"].numel() == e.C
+                e.stats = read_only("stats", a["stats"], torch.float64)
+                e.gamma, e.beta, e.eps = read_only("gamma", a["gamma"]), read_only("beta", a["beta"]), float(a["eps"])
+            elif stage == "mask_copy":
+                e.N, e.ld_out = int(a["N"]), int(a["ld_out"])
+                out["out"], e.out = b.guarded(rows, e.ld_out)
+        _lib.check(_lib.lib().svc_op_lr(C.byref(e), _lib.stream_ptr()))
+        out["inputs"] = inputs
+    return out
+
+
 def rmsnorm(x, gamma, w=None, b=None, add_one=False):
     rows, D = x.shape
     dev = x.device
