@@ -55,6 +55,27 @@ typedef struct svc_dit svc_dit_t;
  * the first forward would have prepared (RoPE table, skip lists). */
 int svc_dit_create(const svc_dit_config_t* cfg, const svc_tensor_desc_t* weights, int n_weights,
                    void* stream, svc_dit_t** out);
+/* svc_dit_create with the arithmetic chosen; numbering follows the vocoders' `precision`.
+ *   1  fp16 GEMM and attention operands, fp32 accumulation (svc_dit_create is create_ex(..., 1, ...), bit for bit).
+ *   2  fp16x3 ("full precision"): every value that precision 1 rounds to fp16 on its way into a GEMM or the attention is carried
+ *      as two fp16 planes, hi = half(v) and lo = half(v - float(hi)), and every product is hi*hi + lo*hi + hi*lo with fp32
+ *      accumulation (the lo*lo term is dropped).  This covers the merge linear, QKV, wo, w1/w3, w2, the UViT and long skip
+ *      linears, the mlp head, conv1 / conv2, the WaveNet in_layer / res_skip convs and FinalLayer, and QK^T and PV of the
+ *      attention (P is split after the exponent; softmax statistics are fp32).  What is fp32 in precision 1 stays fp32: the
+ *      time / style MLPs, the AdaLN tables, the residual stream, the norms, RoPE and the ODE state.  For users whose reference
+ *      runs the sampler in fp32 (inference.py --fp16 False, CPU runs, the v2 timbre-only branch).
+ * Any other value is refused before anything is allocated or launched: non-zero return, the reason in svc_last_error(), *out
+ * untouched.  A handle has one precision for life (svc_dit_precision).  Its weights are packed once in that form: precision 2 packs
+ * the split taps' sub-blocks [w_hi | w_lo | w_hi] per tap ([N][3][K]), so its weight memory is 3x the fp16 pack, and its workspace
+ * holds a lo plane beside every fp16 operand plane plus one fp32 scratch of [rows][max(3 hidden, 2 ffn, 2 wn_hidden)].
+ * On a precision-2 handle the fused row-panel kernel does not exist: svc_dit_fused_available returns 0, and
+ * svc_dit_set_fused_min_rows / svc_dit_set_fused_seams succeed and change nothing.  Everything else works unchanged and keeps its
+ * contracts (ragged batches equal the runs alone bit for bit, micro-batching, graph replay, seeds, per-row settings):
+ * svc_cfm_sample, _seeded, _rows, svc_dit_forward, svc_dit_set_microbatch, svc_dit_set_graphs. */
+int svc_dit_create_ex(const svc_dit_config_t* cfg, const svc_tensor_desc_t* weights, int n_weights, int precision,
+                      void* stream, svc_dit_t** out);
+/* 1 or 2: the precision the handle was created with (0 for NULL) */
+int svc_dit_precision(svc_dit_t* m);
 void svc_dit_destroy(svc_dit_t* m);
 
 /* Utterances processed together inside one sampler call (micro-batch whose activations stay cache
@@ -1456,6 +1477,16 @@ int svc_op_kgemm(const svc_kgemm_t* args, void* stream);
  * column permutation of a natural-order V^T buffer [rows][vt_ld] (16-bit words, device) into order `mode` (vt_pos), as
  * svc_op_attention applies it; synchronises.  Refused: NULL vt, rows < 1, vt_ld < 32 or not a multiple of 32, mode outside 0 .. 2. */
 int svc_op_permute_vt(uint16_t* vt, int64_t rows, int64_t vt_ld, int mode, void* stream);
+/* Op-level seam of the split-precision (fp16x3) attention of the DiT's precision 2 (csrc/attention.hip, attn_x3): q, k, v, out are
+ * DEVICE fp32 [n_seq][seq_rows][H][64], RoPE already applied to q and k; out = softmax(q k^T / 8 over keys < kv_len) v for the
+ * query rows [q_start, Tq) of every sequence, other rows of out are not written.  kv_lens: HOST [n_seq], each in [0, seq_rows]
+ * (0 writes zero rows).  The call scales q by log2(e) / 8 in fp32, splits q, k and v into hi / lo fp16 planes (V transposed, natural
+ * column order) with the model's own kernels and issues ONE launch; synchronises.  Contracts: keys are walked in a fixed order
+ * without atomics; a sequence's rows do not depend on the other sequences of the call (bit for bit); k and v rows at and above
+ * kv_len are never used as values and may hold NaN.  Refused before anything is allocated: NULL pointers, n_seq, H or seq_rows < 1,
+ * Tq outside [1, seq_rows], q_start outside [0, Tq), a length outside [0, seq_rows]. */
+int svc_op_attention_x3(const float* q, const float* k, const float* v, float* out, int n_seq, int seq_rows, int H, int Tq,
+                        int q_start, const int64_t* kv_lens, void* stream);
 /* Test aid (tests/test_gpu_lr_ops.py; no model uses it): ONE launch of one of the length regulator's four kernels (csrc/lr.hip)
  * through the launch function svc_lr_forward calls, with the model's grid and block, on caller buffers; synchronises.  Device
  * pointers unless noted; NULL = absent.  Activations are channels-last rows of ld floats, utterance b at row b tout_max.

@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_HERE, "libseedvc_hip.so")
 
 EXPORTS = [
     "svc_abi_version", "svc_last_error",
-    "svc_dit_create", "svc_dit_destroy", "svc_dit_set_microbatch", "svc_dit_set_fused_min_rows", "svc_dit_set_fused_seams", "svc_dit_fused_available", "svc_dit_set_graphs", "svc_cfm_sample", "svc_dit_forward",
+    "svc_dit_create", "svc_dit_create_ex", "svc_dit_precision", "svc_dit_destroy", "svc_dit_set_microbatch", "svc_dit_set_fused_min_rows", "svc_dit_set_fused_seams", "svc_dit_fused_available", "svc_dit_set_graphs", "svc_cfm_sample", "svc_dit_forward",
     "svc_cfm_sample_seeded", "svc_cfm_noise_draws", "svc_cfm_sample_rows", "svc_cfm_rows_plan", "svc_hift_forward_seeded", "svc_hift_noise_draws",
     "svc_bigvgan_create", "svc_bigvgan_destroy", "svc_bigvgan_forward", "svc_bigvgan_forward_ragged", "svc_bigvgan_set_microbatch",
     "svc_hift_create", "svc_hift_destroy", "svc_hift_forward", "svc_hift_forward_ragged", "svc_hift_set_microbatch",
@@ -47,7 +47,7 @@ EXPORTS = [
     "svc_prof_enable", "svc_prof_collect",
     "svc_op_linear", "svc_op_conv1d", "svc_op_conv1d_ex", "svc_op_conv1d_last_took", "svc_op_dit_panel", "svc_op_conv_transpose1d", "svc_op_attention", "svc_op_attention_ex", "svc_op_rmsnorm",
     "svc_op_layernorm", "svc_op_layernorm_gelu", "svc_op_act_cl", "svc_op_hift_signal", "svc_op_ar_sampler",
-    "svc_op_ar_attn", "svc_op_ar_linear", "svc_op_kgemm", "svc_op_permute_vt", "svc_op_lr",
+    "svc_op_ar_attn", "svc_op_ar_linear", "svc_op_kgemm", "svc_op_permute_vt", "svc_op_lr", "svc_op_attention_x3",
 ]
 
 
@@ -328,6 +328,9 @@ def lib():
         l.svc_op_kgemm.argtypes = [C.POINTER(KGemm), C.c_void_p]
         l.svc_op_permute_vt.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p]
         l.svc_op_lr.argtypes = [C.POINTER(LrOp), C.c_void_p]
+        l.svc_op_attention_x3.argtypes = [C.c_void_p] * 4 + [C.c_int] * 5 + [C.POINTER(C.c_int64), C.c_void_p]
+        l.svc_dit_create_ex.argtypes = [C.POINTER(DitConfig), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]
+        l.svc_dit_precision.argtypes = [C.c_void_p]
         # seeded noise: 64-bit seeds by value and as HOST arrays
         l.svc_cfm_sample_seeded.argtypes = [C.c_void_p, C.POINTER(CfmArgs), C.POINTER(C.c_uint64), C.c_void_p]
         l.svc_cfm_noise_draws.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]

@@ -68,20 +68,37 @@ def _rows_struct(settings, B, what):
     return rows
 
 
-class Estimator:
-    """Packed DiT on one device (mirror of `CFM.estimator`)."""
+PRECISIONS = {1: 1, 2: 2, "fp16": 1, "fp16x3": 2}
 
-    def __init__(self, cfg, state_dict, device="cuda:0"):
+
+def dit_precision(precision):
+    """1 | "fp16" (fp16 GEMM / attention operands) or 2 | "fp16x3" (split precision, fp32-level results) -> 1 | 2
+    (`svc_dit_create_ex`, include/seedvc_hip.h).  Anything else raises before a handle or a weight is touched."""
+    if isinstance(precision, bool) or not isinstance(precision, (int, str)) or precision not in PRECISIONS:
+        raise ValueError(f"DiT precision must be 1 / 'fp16' or 2 / 'fp16x3', got {precision!r}")
+    return PRECISIONS[precision]
+
+
+class Estimator:
+    """Packed DiT on one device (mirror of `CFM.estimator`).  precision: see `dit_precision`; fixed for the handle's life."""
+
+    def __init__(self, cfg, state_dict, device="cuda:0", precision=1):
+        self._h = C.c_void_p()
+        self._precision = dit_precision(precision)
         self.cfg = cfg
         self.device = torch.device(device)
         self.in_channels = cfg["C"]
-        self._h = C.c_void_p()
         with torch.cuda.device(self.device):
             descs, n, keep = _lib.make_descs(state_dict, self.device)
             cs = _cfg_struct(cfg)
-            _lib.check(_lib.lib().svc_dit_create(C.byref(cs), descs, n, _lib.stream_ptr(), C.byref(self._h)))
+            _lib.check(_lib.lib().svc_dit_create_ex(C.byref(cs), descs, n, self._precision, _lib.stream_ptr(), C.byref(self._h)))
             torch.cuda.current_stream().synchronize()
         del keep
+
+    @property
+    def precision(self):
+        """1 (fp16 operands) or 2 (fp16x3)."""
+        return self._precision
 
     def setup_caches(self, max_batch_size=1, max_seq_length=8192):
         """No-op kept for call compatibility (inference.py:90): RoPE table and skip lists are built at pack time."""
@@ -139,15 +156,20 @@ class Estimator:
 class CFM:
     """Mirror of modules.flow_matching.CFM / modules.v2.cfm.CFM for inference."""
 
-    def __init__(self, cfg, state_dict, device="cuda:0"):
+    def __init__(self, cfg, state_dict, device="cuda:0", precision=1):
         self.cfg = cfg
-        self.estimator = Estimator(cfg, state_dict, device)
+        self.estimator = Estimator(cfg, state_dict, device, precision)
         self.in_channels = cfg["C"]
         self.device = self.estimator.device
 
     @classmethod
     def from_preset(cls, name, state_dict, device="cuda:0", **overrides):
         return cls(dit_config(name, **overrides), state_dict, device)
+
+    @property
+    def precision(self):
+        """1 (fp16 operands) or 2 (fp16x3): the estimator's (`dit_precision`)."""
+        return self.estimator.precision
 
     @torch.inference_mode()
     def inference(self, mu, x_lens, prompt, style, f0=None, n_timesteps=10, temperature=1.0,

@@ -576,4 +576,229 @@ int attention_launch(const AttnParams& p, hipStream_t st) {
     return 0;
 }
 
+// ------------------------------------------------------------------ split-precision (fp16x3) attention
+// The DiT's full-precision mode (svc_dit_create_ex, precision 2).  Operands are fp32 values carried as two fp16 planes,
+// hi = half(v) and lo = half(v - float(hi)); a product of two such values is hi*hi + lo*hi + hi*lo on v_mfma_f32_16x16x32_f16 with
+// fp32 accumulation (the lo*lo term, 2^-22 of the product, is dropped as in the tap-GEMM's split taps).  The form built is
+// this split form, not the fp32-MFMA substitute.
+namespace {
+
+// q, k (fp32 rows, head h at column 64 h) -> RoPE on interleaved pairs (rope null: none), q times q_scale, hi / lo planes.
+// One thread per (row, pair) rotates the pair of q and the pair of k.
+__global__ __launch_bounds__(256) void rope_split_kernel(const float* __restrict__ q, const float* __restrict__ k, long ld_in,
+                                                         const float* __restrict__ rope, float q_scale, half_t* __restrict__ q_hi,
+                                                         half_t* __restrict__ q_lo, half_t* __restrict__ k_hi,
+                                                         half_t* __restrict__ k_lo, long ld_out, long rows, int D, int seq_rows) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int n2 = D >> 1;
+    if (i >= rows * n2) return;
+    const long row = i / n2;
+    const int pr = (int)(i - row * n2);
+    const int pos = (int)(row % seq_rows);
+    float cs = 1.f, sn = 0.f;
+    if (rope) {
+        const float2 t = *reinterpret_cast<const float2*>(rope + ((long)pos * 32 + (pr & 31)) * 2);
+        cs = t.x; sn = t.y;
+    }
+    const float2 a = *reinterpret_cast<const float2*>(q + row * ld_in + 2 * pr);
+    const float2 b = *reinterpret_cast<const float2*>(k + row * ld_in + 2 * pr);
+    const float o[4] = {(a.x * cs - a.y * sn) * q_scale, (a.y * cs + a.x * sn) * q_scale, b.x * cs - b.y * sn, b.y * cs + b.x * sn};
+    half_t hi[4], lo[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { hi[j] = (half_t)o[j]; lo[j] = (half_t)(o[j] - (float)hi[j]); }
+    const long oo = row * ld_out + 2 * pr;
+    *reinterpret_cast<half2v*>(q_hi + oo) = (half2v){hi[0], hi[1]};
+    *reinterpret_cast<half2v*>(q_lo + oo) = (half2v){lo[0], lo[1]};
+    *reinterpret_cast<half2v*>(k_hi + oo) = (half2v){hi[2], hi[3]};
+    *reinterpret_cast<half2v*>(k_lo + oo) = (half2v){lo[2], lo[3]};
+}
+
+// v (fp32 rows [seq][seq_rows][ld_in]) -> V^T hi / lo planes [seq][D][vt_ld], natural column order (32 x 32 LDS transpose)
+__global__ __launch_bounds__(256) void vt_split_kernel(const float* __restrict__ v, long ld_in, half_t* __restrict__ vt_hi,
+                                                       half_t* __restrict__ vt_lo, long vt_seq_stride, long vt_ld, int D, int seq_rows) {
+    __shared__ float tile[32][33];
+    const int seq = blockIdx.z;
+    const int t0 = blockIdx.x * 32, d0 = blockIdx.y * 32;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    for (int i = ty; i < 32; i += 8) {
+        const int t = t0 + i, d = d0 + tx;
+        tile[i][tx] = (t < seq_rows && d < D) ? v[((long)seq * seq_rows + t) * ld_in + d] : 0.f;
+    }
+    __syncthreads();
+    for (int i = ty; i < 32; i += 8) {
+        const int d = d0 + i, t = t0 + tx;
+        if (d < D && t < seq_rows) {
+            const float x = tile[tx][i];
+            const half_t h = (half_t)x;
+            const long o = (long)seq * vt_seq_stride + (long)d * vt_ld + t;
+            vt_hi[o] = h;
+            vt_lo[o] = (half_t)(x - (float)h);
+        }
+    }
+}
+
+__device__ __forceinline__ half8 join8(half4 a, half4 b) { return (half8){a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]}; }
+
+// Block = 4 waves = 64 queries of one (sequence, head); a wave owns 16 queries and walks the keys [0, kv_len) in steps of 32, in
+// order, with no atomics and nothing shared between waves: a query row's result depends on its own sequence alone.  Scores
+// are computed transposed (S^T = K Q^T, lane (fr, fq) holds keys 16 t + 4 fq + r of query fr), so the softmax statistics
+// (fp32) need two cross-lane steps and the exponentials feed P^T into O^T += V^T P^T as the B operand.  Keys at and above kv_len
+// are masked by a select on the score (their K rows may hold anything) and their V^T values are replaced by zero before the
+// MFMA (they may hold NaN too).  K rows are clamped to the sequence's last row, V^T loads stay below vt_ld.
+__global__ __launch_bounds__(256) void attn_x3_kernel(const AttnX3Params p) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int fr = lane & 15, fq = lane >> 4;
+    const int nqt = (p.Tq - p.q_start + 63) / 64;
+    const int qt_idx = blockIdx.x % nqt, sh_idx = blockIdx.x / nqt;
+    const int h = sh_idx % p.H, seq = sh_idx / p.H;
+    const int q0 = p.q_start + qt_idx * 64 + wave * 16;
+    if (q0 >= p.Tq) return;
+    int kv_len = p.kv_len[seq];
+    kv_len = kv_len < 0 ? 0 : (kv_len > p.seq_rows ? p.seq_rows : kv_len);
+    const long row_base = (long)seq * p.seq_rows;
+
+    half8 qh[2], ql[2];
+    {
+        const int qr = q0 + fr < p.Tq ? q0 + fr : p.Tq - 1;
+        const long qo = (row_base + qr) * p.ld_qk + h * 64 + fq * 8;
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            qh[ks] = *reinterpret_cast<const half8*>(p.q_hi + qo + ks * 32);
+            ql[ks] = *reinterpret_cast<const half8*>(p.q_lo + qo + ks * 32);
+        }
+    }
+    float4v acc_o[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) acc_o[i] = (float4v){0.f, 0.f, 0.f, 0.f};
+    float m_run = -INFINITY, l_run = 0.f;
+    const long vbase = (long)seq * p.vt_seq_stride + (long)(h * 64 + fr) * p.vt_ld + 4 * fq;
+
+    for (int k0 = 0; k0 < kv_len; k0 += 32) {
+        float s[8];
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            int kr = k0 + 16 * t + fr;
+            kr = kr < p.seq_rows ? kr : p.seq_rows - 1;
+            const long ko = (row_base + kr) * p.ld_qk + h * 64 + fq * 8;
+            float4v acc = (float4v){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {
+                const half8 kh = *reinterpret_cast<const half8*>(p.k_hi + ko + ks * 32);
+                const half8 kl = *reinterpret_cast<const half8*>(p.k_lo + ko + ks * 32);
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(kl, qh[ks], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(kh, ql[ks], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(kh, qh[ks], acc, 0, 0, 0);
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) s[4 * t + r] = k0 + 16 * t + 4 * fq + r < kv_len ? acc[r] : -INFINITY;
+        }
+        float mt = s[0];
+#pragma unroll
+        for (int j = 1; j < 8; ++j) mt = fmaxf(mt, s[j]);
+        mt = fmaxf(mt, __shfl_xor(mt, 16));
+        mt = fmaxf(mt, __shfl_xor(mt, 32));
+        const float m_new = fmaxf(m_run, mt);            // finite: key k0 is below kv_len
+        const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+        m_run = m_new;
+        half8 ph, pl;
+        float ls = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float e = __builtin_amdgcn_exp2f(s[j] - m_new);
+            ls += e;
+            const half_t hi = (half_t)e;
+            ph[j] = hi;
+            pl[j] = (half_t)(e - (float)hi);
+        }
+        l_run = l_run * alpha + ls;
+        const bool ok0 = k0 + 4 * fq + 3 < kv_len, ok1 = k0 + 16 + 4 * fq + 3 < kv_len;
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) {
+            const long vo = vbase + (long)dt * 16 * p.vt_ld + k0;
+            half4 h0 = *reinterpret_cast<const half4*>(p.vt_hi + vo), h1 = *reinterpret_cast<const half4*>(p.vt_hi + vo + 16);
+            half4 l0 = *reinterpret_cast<const half4*>(p.vt_lo + vo), l1 = *reinterpret_cast<const half4*>(p.vt_lo + vo + 16);
+            if (!ok0) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (k0 + 4 * fq + r >= kv_len) { h0[r] = (half_t)0.f; l0[r] = (half_t)0.f; }
+            }
+            if (!ok1) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (k0 + 16 + 4 * fq + r >= kv_len) { h1[r] = (half_t)0.f; l1[r] = (half_t)0.f; }
+            }
+            const half8 vh = join8(h0, h1), vl = join8(l0, l1);
+            float4v acc = acc_o[dt];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[r] *= alpha;
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(vl, ph, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(vh, pl, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(vh, ph, acc, 0, 0, 0);
+            acc_o[dt] = acc;
+        }
+    }
+    l_run += __shfl_xor(l_run, 16);
+    l_run += __shfl_xor(l_run, 32);
+    const float inv = l_run > 0.f ? 1.0f / l_run : 0.f;       // kv_len = 0 writes zero rows
+    if (q0 + fr >= p.Tq) return;
+    const long orow = (row_base + q0 + fr) * p.ld_out + h * 64 + 4 * fq;
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {
+        float o[4];
+        half4 hi, lo;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            o[r] = acc_o[dt][r] * inv;
+            hi[r] = (half_t)o[r];
+            lo[r] = (half_t)(o[r] - (float)hi[r]);
+        }
+        if (p.out32) *reinterpret_cast<float4v*>(p.out32 + orow + dt * 16) = (float4v){o[0], o[1], o[2], o[3]};
+        if (p.out_hi) *reinterpret_cast<half4*>(p.out_hi + orow + dt * 16) = hi;
+        if (p.out_lo) *reinterpret_cast<half4*>(p.out_lo + orow + dt * 16) = lo;
+    }
+}
+
+}  // namespace
+
+int attention_x3_prepare(const float* q, const float* k, const float* v, long ld_in, const float* rope, float q_scale,
+                         half_t* q_hi, half_t* q_lo, half_t* k_hi, half_t* k_lo, long ld_qk, half_t* vt_hi, half_t* vt_lo,
+                         long vt_seq_stride, long vt_ld, int n_seq, int seq_rows, int D, hipStream_t st) {
+    SVC_REQUIRE(n_seq > 0 && seq_rows > 0 && D > 0 && D % 64 == 0, "attention_x3_prepare: shape");
+    SVC_REQUIRE(ld_in % 2 == 0 && ld_qk % 8 == 0 && vt_ld >= seq_rows && vt_seq_stride >= (long)D * vt_ld, "attention_x3_prepare: layout");
+    const long rows = (long)n_seq * seq_rows;
+    hipLaunchKernelGGL(rope_split_kernel, dim3(cdiv(rows * (D / 2), 256)), dim3(256), 0, st, q, k, ld_in, rope, q_scale, q_hi, q_lo,
+                       k_hi, k_lo, ld_qk, rows, D, seq_rows);
+    SVC_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(vt_split_kernel, dim3(cdiv(seq_rows, 32), D / 32, n_seq), dim3(256), 0, st, v, ld_in, vt_hi, vt_lo,
+                       vt_seq_stride, vt_ld, D, seq_rows);
+    SVC_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int attention_x3_check(const AttnX3Params& p) {
+    SVC_REQUIRE(p.n_seq > 0 && p.H > 0 && p.seq_rows > 0, "attention_x3: n_seq, H and seq_rows are positive");
+    SVC_REQUIRE(p.Tq >= 1 && p.Tq <= p.seq_rows && p.q_start >= 0 && p.q_start < p.Tq, "attention_x3: 0 <= q_start < Tq <= seq_rows");
+    SVC_REQUIRE(p.vt_ld % 32 == 0 && p.vt_ld >= p.seq_rows && p.ld_qk % 8 == 0 && p.ld_out % 4 == 0 && p.vt_seq_stride % 4 == 0,
+                "attention_x3: vt_ld a multiple of 32 that covers seq_rows, ld_qk of 8, ld_out and vt_seq_stride of 4");
+    SVC_REQUIRE(p.ld_qk >= p.H * 64 && p.ld_out >= p.H * 64 && p.vt_seq_stride >= (long)p.H * 64 * p.vt_ld, "attention_x3: strides cover H * 64 columns");
+    SVC_REQUIRE(p.q_hi && p.q_lo && p.k_hi && p.k_lo && p.vt_hi && p.vt_lo && p.kv_len, "attention_x3: q, k, vt planes and kv_len are required");
+    SVC_REQUIRE(p.out32 || (p.out_hi && p.out_lo), "attention_x3: an output is required (out32, or out_hi with out_lo)");
+    return 0;
+}
+
+int attention_x3_launch(const AttnX3Params& p, hipStream_t st) {
+    if (attention_x3_check(p)) return 1;
+    const bool prof = prof_enabled();
+    if (prof) prof_begin(PROF_ATTN, st);
+    hipLaunchKernelGGL(attn_x3_kernel, dim3(cdiv(p.Tq - p.q_start, 64) * p.H * p.n_seq), dim3(256), 0, st, p);
+    SVC_CHECK_HIP(hipGetLastError());
+    if (prof) {
+        // algorithmic work, as attention_launch counts it (the split form issues three MFMAs per product); operands are two planes
+        const double tk = p.seq_rows;
+        prof_end(PROF_ATTN, 4.0 * p.n_seq * p.H * (double)(p.Tq - p.q_start) * tk * 64.0,
+                 4.0 * p.n_seq * p.H * 64.0 * (2.0 * (p.Tq - p.q_start) + 2.0 * tk), st);
+    }
+    return 0;
+}
+
 }  // namespace svc

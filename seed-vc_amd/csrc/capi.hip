@@ -427,6 +427,40 @@ int svc_op_attention(const float* q, const float* k, const float* v, float* out,
     return 0;
 }
 
+int svc_op_attention_x3(const float* q, const float* k, const float* v, float* out, int n_seq, int seq_rows, int H, int Tq,
+                        int q_start, const int64_t* kv_lens, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    SVC_REQUIRE(q && k && v && out && kv_lens, "svc_op_attention_x3: null argument");
+    SVC_REQUIRE(n_seq >= 1 && H >= 1 && seq_rows >= 1, "svc_op_attention_x3: n_seq, H and seq_rows are positive");
+    SVC_REQUIRE(Tq >= 1 && Tq <= seq_rows && q_start >= 0 && q_start < Tq, "svc_op_attention_x3: 0 <= q_start < Tq <= seq_rows");
+    std::vector<int> lens(n_seq);
+    for (int n = 0; n < n_seq; ++n) {
+        SVC_REQUIRE(kv_lens[n] >= 0 && kv_lens[n] <= seq_rows, "svc_op_attention_x3: kv_lens within [0, seq_rows]");
+        lens[n] = (int)kv_lens[n];
+    }
+    Scratch s;
+    const int D = H * 64;
+    const long rows = (long)n_seq * seq_rows;
+    const long vt_ld = round_up(seq_rows, 32);
+    half_t* qk = s.ar.alloc_n<half_t>((size_t)rows * 4 * D, st);          // [q_hi | k_hi | q_lo | k_lo] rows
+    half_t* vt = s.ar.alloc_n<half_t>((size_t)n_seq * D * vt_ld * 2, st);  // hi planes of all sequences, then lo
+    int* d_len = s.ar.alloc_n<int>(n_seq, st);
+    if (!qk || !vt || !d_len) return 1;
+    SVC_CHECK_HIP(hipMemcpyAsync(d_len, lens.data(), (size_t)n_seq * 4, hipMemcpyHostToDevice, st));
+    half_t* vt_lo = vt + (long)n_seq * D * vt_ld;
+    if (attention_x3_prepare(q, k, v, D, nullptr, 0.125f * 1.4426950408889634f, qk, qk + 2 * D, qk + D, qk + 3 * D, 4 * D, vt,
+                             vt_lo, (long)D * vt_ld, vt_ld, n_seq, seq_rows, D, st)) return 1;
+    AttnX3Params a;
+    memset(&a, 0, sizeof(a));
+    a.q_hi = qk; a.q_lo = qk + 2 * D; a.k_hi = qk + D; a.k_lo = qk + 3 * D; a.ld_qk = 4 * D;
+    a.vt_hi = vt; a.vt_lo = vt_lo; a.vt_seq_stride = (long)D * vt_ld; a.vt_ld = vt_ld;
+    a.out32 = out; a.ld_out = D;
+    a.n_seq = n_seq; a.H = H; a.seq_rows = seq_rows; a.Tq = Tq; a.q_start = q_start; a.kv_len = d_len;
+    if (attention_x3_launch(a, st)) return 1;
+    SVC_CHECK_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
 // One attention_launch on buffers already in the kernels' layout (tests/test_gpu_attention.py): no packing, so the test owns every
 // byte the kernels read.  Everything is checked before the first allocation; the lengths travel as a host array.
 int svc_op_attention_ex(const svc_attention_t* e, void* stream) {

@@ -355,6 +355,28 @@ int attention_launch(const AttnParams& p, hipStream_t st);
 // in-place column permutation of a natural-order V^T buffer [rows][vt_ld] into `mode` (op-level entry point only)
 int attention_permute_vt(half_t* vt, long rows, long vt_ld, int mode, hipStream_t st);
 
+// Split-precision (fp16x3) attention of the DiT's full-precision mode (attention.hip): every operand is a pair of fp16 planes,
+// hi = half(v) and lo = half(v - float(hi)), addressed like AttnParams (q / k rows = seq * seq_rows + pos, head h at column 64 h;
+// V^T [seq][H * 64][vt_ld] in NATURAL column order).  q carries RoPE and log2(e) / 8.  Queries [q_start, Tq) attend keys
+// [0, kv_len[seq]) in a fixed order without atomics; a query row's result depends on its own sequence alone.  K rows and V^T
+// columns at and above kv_len are never used as values (they may hold NaN); K rows past seq_rows and V^T columns past vt_ld are
+// not read.  Outputs (any subset, at least one form): fp32 rows out32 and the planes out_hi / out_lo, all [rows][ld_out].  Rows
+// outside [q_start, Tq) are not written; kv_len = 0 writes zero rows.
+struct AttnX3Params {
+    const half_t* q_hi; const half_t* q_lo; const half_t* k_hi; const half_t* k_lo; long ld_qk;
+    const half_t* vt_hi; const half_t* vt_lo; long vt_seq_stride; long vt_ld;     // vt_ld: a multiple of 32, >= seq_rows
+    float* out32; half_t* out_hi; half_t* out_lo; long ld_out;
+    int n_seq, H, seq_rows, Tq, q_start;
+    const int* kv_len;                                                            // DEVICE [n_seq]
+};
+int attention_x3_check(const AttnX3Params& p);      // what the launch refuses, without launching
+int attention_x3_launch(const AttnX3Params& p, hipStream_t st);
+// fp32 q, k, v rows ([n_seq * seq_rows][ld_in], D = H * 64 columns each) -> the planes above: interleaved-pair RoPE from `rope`
+// ([pos][32][2] cos / sin; null = none) on q and k, q times q_scale, all in fp32, then the hi / lo split
+int attention_x3_prepare(const float* q, const float* k, const float* v, long ld_in, const float* rope, float q_scale,
+                         half_t* q_hi, half_t* q_lo, half_t* k_hi, half_t* k_lo, long ld_qk, half_t* vt_hi, half_t* vt_lo,
+                         long vt_seq_stride, long vt_ld, int n_seq, int seq_rows, int D, hipStream_t st);
+
 // ------------------------------------------------------------------ elementwise / norm kernels (elementwise.hip)
 // y16[row] = (rmsnorm(x[row]) * gamma) * (mul_add1 + w[seq]) + b[seq]      (w/b may be null)
 int rmsnorm_mod_launch(const float* x, long ldx, half_t* y, long ldy, const float* gamma,
@@ -363,5 +385,17 @@ int rmsnorm_mod_launch(const float* x, long ldx, half_t* y, long ldy, const floa
 // LayerNorm (no affine) * (1 + scale) + shift
 int layernorm_mod_launch(const float* x, long ldx, half_t* y, long ldy, const float* scale,
                          const float* shift, int rows, int D, float eps, hipStream_t st);
+// The same two row kernels with a split-precision result: y = half(v), y_lo = half(v - float(y)) (operands of fp16x3 GEMMs)
+int rmsnorm_mod_hl_launch(const float* x, long ldx, half_t* y, half_t* y_lo, long ldy, const float* gamma,
+                          const float* w, const float* b, long ld_wb, int add_one,
+                          int rows, int D, int seq_rows, float eps, hipStream_t st);
+int layernorm_mod_hl_launch(const float* x, long ldx, half_t* y, half_t* y_lo, long ldy, const float* scale,
+                            const float* shift, int rows, int D, float eps, hipStream_t st);
+// fp32 rows -> hi / lo planes.  SPLIT_PLAIN: out[j] = src[j]; SPLIT_SWIGLU: out[j] = silu(src[2j]) * src[2j+1]; SPLIT_TANHSIG:
+// out[j] = tanh(src[2j]) * sigmoid(src[2j+1]) (the tap-GEMM's paired epilogues, applied to a fp32 STORE).  cols = output
+// columns; the planes are written n_copies times, copy_stride elements apart.
+enum { SPLIT_PLAIN = 0, SPLIT_SWIGLU = 1, SPLIT_TANHSIG = 2 };
+int split_rows_launch(const float* src, long ld_src, half_t* hi, half_t* lo, long ld_out, long rows, int cols, int mode,
+                      int n_copies, long copy_stride, hipStream_t st);
 
 }  // namespace svc

@@ -10,7 +10,9 @@
 //  * every timestep-only quantity (t-embeddings, all AdaLN projections, WaveNet cond_layer, FinalLayer
 //    modulation) is tabulated for all steps at the start of a call.
 //  * residual stream, ODE state, norms, RoPE, softmax statistics and all accumulators are fp32; GEMM and
-//    attention operands are fp16 (the reference autocasts the same ops to fp16: inference.py:499).
+//    attention operands are fp16 (the reference autocasts the same ops to fp16: inference.py:499).  A handle created with
+//    precision 2 (svc_dit_create_ex) carries those operands as hi / lo fp16 planes and takes three products per product instead
+//    (body_x3 / head_x3 below): the reference's fp32 runs (--fp16 False, CPU, the v2 timbre-only branch).
 #include <math.h>
 #include <cmath>
 #include <string>
@@ -51,6 +53,10 @@ struct svc_dit {
     svc_dit_config_t cfg;
     int D, H, L, C, Dc, S, I, W, NL, WK, npre, C16, C32;
     bool v2, wavenet, adaptive_blocks;   // adaptive_blocks: per-layer modulation used (v1: !time_as_token, v2: always)
+    // 1: fp16 GEMM / attention operands.  2: fp16x3 -- every such operand is a hi / lo pair of fp16 planes, every weight is packed as
+    // the split taps' sub-blocks [w_hi | w_lo | w_hi] (conv_util.h; 3x the fp16 pack), attention runs attn_x3 (attention.hip); the
+    // fused row-panel path is off.  Fixed at creation.
+    int precision = 1;
     Arena wts, ws;
     // hipGraphs of the Euler loop (all steps of one micro-batch group: estimator body + state update), keyed by everything
     // that is baked into the captured kernel arguments.  The reference's counterpart is `compile_cfm` (torch.compile of the
@@ -126,6 +132,13 @@ struct svc_dit {
     float *x32, *xin, *st_term, *v32, *u_rowvec, *tok_style, *prompt32, *wnx32, *flin32;
     half_t *x16, *n16, *qk16, *vt, *ao16, *ff16, *h16, *hm16, *xr16, *wnx16, *acts16, *fl16, *fo16;
     std::vector<half_t*> skip16;
+    // precision 2: the lo planes of the operand buffers above (same shapes) and a fp32 scratch [M][max(3 D, 2 I, 2 W)] for the GEMM
+    // outputs that a row kernel turns into the next operand (QKV, w1 | w3, the gated convs, head intermediates)
+    half_t *x16_lo = nullptr, *n16_lo = nullptr, *qk16_lo = nullptr, *vt_lo = nullptr, *ao16_lo = nullptr, *ff16_lo = nullptr,
+           *h16_lo = nullptr, *hm16_lo = nullptr, *xr16_lo = nullptr, *wnx16_lo = nullptr, *acts16_lo = nullptr, *fl16_lo = nullptr,
+           *fo16_lo = nullptr;
+    std::vector<half_t*> skip16_lo;
+    float* g32 = nullptr;
     int *d_kvlen, *d_convlen, *d_plen;
     unsigned long long* d_seeds = nullptr;   // [cap_B] seeds of the micro-batch (svc_cfm_sample_seeded)
     // per-utterance sampler settings of the micro-batch: {c0, ca, cb, temperature} (what the start-state and update kernels
@@ -153,6 +166,13 @@ struct svc_dit {
     int body(int n_streams, int B, int T, int step, hipStream_t st);
     int body_fused(int n_streams, int B, int T, int step, bool seam_merge, bool seam_head, hipStream_t st);
     int head(int n_streams, int B, int T, int step, hipStream_t st);
+    int body_x3(int n_streams, int B, int T, int step, hipStream_t st);
+    int head_x3(int n_streams, int B, int T, int step, hipStream_t st);
+    // precision 2: the lo plane of x16 (and hi again) from the fp32 ODE state, for every stream's copy
+    int split_state(int n_streams, int B, hipStream_t st) {
+        if (precision != 2) return 0;
+        return split_rows_launch(x32, C16, x16, x16_lo, C16, (long)B * seq_rows, C16, SPLIT_PLAIN, n_streams, (long)B * seq_rows * C16, st);
+    }
 };
 
 // --------------------------------------------------------------------------------------------- packing
@@ -183,7 +203,20 @@ float* copy_vec(Arena& ar, const float* src, long n, hipStream_t st) {
 
 int svc_dit::pack(const StateDict& sd, hipStream_t st) {
     const long Dp = round_up(D, 128);
-    auto new16 = [&](long rows, long ld) { return wts.alloc_n<half_t>(round_up(rows, 128) * ld, st); };
+    const int ns = precision == 2 ? 3 : 1;
+    auto new16 = [&](long rows, long ld) { return wts.alloc_n<half_t>(round_up(rows, 128) * ld * ns, st); };
+    // One tap block of a GEMM weight: K columns of src from src_col, for the tap that is tapw wide and starts at column dst_col of
+    // a [..][ldw] row.  Precision 2: the tap's sub-blocks [w_hi | w_lo | w_hi] from column 3 dst_col of a [..][3 ldw] row.
+    auto packw = [&](const float* src, long src_ld, long src_col, int N, int K, half_t* dst, long ldw, long dst_col, long tapw,
+                     long row0, long row_step, const float* scale) -> int {
+        if (ns == 1) return pack_block(0, src, src_ld, src_col, N, K, dst, ldw, dst_col, row0, row_step, scale, st);
+        for (int sub = 0; sub < 3; ++sub) {
+            half_t* d = dst + row0 * 3 * ldw + 3 * dst_col + sub * tapw;
+            if ((sub == 1 ? pack_f16_lo_launch : pack_f16_launch)(src + src_col, d, N, 1, K, src_ld, 0, 1, row_step * 3 * ldw, 0, 1, scale, st))
+                return 1;
+        }
+        return 0;
+    };
     layers.resize(L);
     for (int i = 0; i < L; ++i) {
         const std::string p = "transformer.layers." + std::to_string(i) + ".";
@@ -198,11 +231,11 @@ int svc_dit::pack(const StateDict& sd, hipStream_t st) {
         ly.w13 = new16(2 * I, D);
         ly.w2 = new16(D, I);
         if (!ly.wqkv || !ly.wo || !ly.w13 || !ly.w2) return 1;
-        if (pack_block(0, wqkv->data, D, 0, 3 * D, D, ly.wqkv, D, 0, 0, 1, nullptr, st)) return 1;
-        if (pack_block(0, wo->data, D, 0, D, D, ly.wo, D, 0, 0, 1, nullptr, st)) return 1;
-        if (pack_block(0, w1->data, D, 0, I, D, ly.w13, D, 0, 0, 2, nullptr, st)) return 1;   // rows 2j   = w1_j
-        if (pack_block(0, w3->data, D, 0, I, D, ly.w13, D, 0, 1, 2, nullptr, st)) return 1;   // rows 2j+1 = w3_j
-        if (pack_block(0, w2->data, I, 0, D, I, ly.w2, I, 0, 0, 1, nullptr, st)) return 1;
+        if (packw(wqkv->data, D, 0, 3 * D, D, ly.wqkv, D, 0, D, 0, 1, nullptr)) return 1;
+        if (packw(wo->data, D, 0, D, D, ly.wo, D, 0, D, 0, 1, nullptr)) return 1;
+        if (packw(w1->data, D, 0, I, D, ly.w13, D, 0, D, 0, 2, nullptr)) return 1;   // rows 2j   = w1_j
+        if (packw(w3->data, D, 0, I, D, ly.w13, D, 0, D, 1, 2, nullptr)) return 1;   // rows 2j+1 = w3_j
+        if (packw(w2->data, I, 0, D, I, ly.w2, I, 0, I, 0, 1, nullptr)) return 1;
         const std::string an = v2 ? p + "attention_norm.norm.weight" : p + "attention_norm.norm.weight";
         const std::string fn = v2 ? p + "ffn_norm.weight" : p + "ffn_norm.norm.weight";
         GETW(ga, an, D);
@@ -217,7 +250,8 @@ int svc_dit::pack(const StateDict& sd, hipStream_t st) {
             GETW(bs_, p + "skip_in_linear.bias", D);
             ly.wskip = new16(D, 2 * D);
             if (!ly.wskip) return 1;
-            if (pack_block(0, ws_->data, 2 * D, 0, D, 2 * D, ly.wskip, 2 * D, 0, 0, 1, nullptr, st)) return 1;
+            for (int tap = 0; tap < 2; ++tap)       // [x | skip_in]: two taps of D columns
+                if (packw(ws_->data, 2 * D, (long)tap * D, D, D, ly.wskip, 2 * D, (long)tap * D, D, 0, 1, nullptr)) return 1;
             ly.bskip = copy_vec(wts, bs_->data, D, st);
             if (!ly.bskip) return 1;
         }
@@ -229,7 +263,7 @@ int svc_dit::pack(const StateDict& sd, hipStream_t st) {
     }
     // ---- fragment streams of the fused row-panel kernel (fused.hip): layer i carries wo_i, mlp_i and the NEXT layer's
     // skip linear / QKV projection; the stream of layer L-1 ends after the MLP
-    fused_ok = fused_supported(D, I);
+    fused_ok = precision == 1 && fused_supported(D, I);
     if (fused_ok) {
         auto W = [&](const std::string& k) { return sd.get(k)->data; };
         const int slot_halfs = (D / 16) * 512;
@@ -323,7 +357,7 @@ int svc_dit::pack(const StateDict& sd, hipStream_t st) {
     GETW(bcp, "cond_projection.bias", D);
     w_merge_x = new16(D, C16);
     if (!w_merge_x) return 1;
-    if (pack_block(0, wm->data, Kin, 0, D, C, w_merge_x, C16, 0, 0, 1, nullptr, st)) return 1;
+    if (packw(wm->data, Kin, 0, D, C, w_merge_x, C16, 0, C16, 0, 1, nullptr)) return 1;
     if (merge_ok && fused_pack_merge(stream_first, D, wm->data, Kin, C, st) != (long)merge_slots * (D / 16) * 512) {
         set_error("fused stream packing failed");
         return 1;
@@ -365,8 +399,8 @@ int svc_dit::pack(const StateDict& sd, hipStream_t st) {
         head_wa = new16(D, D);
         head_w2 = new16(C, D);
         if (!head_wa || !head_w2) return 1;
-        if (pack_block(0, a->data, D, 0, D, D, head_wa, D, 0, 0, 1, nullptr, st)) return 1;
-        if (pack_block(0, c->data, D, 0, C, D, head_w2, D, 0, 0, 1, nullptr, st)) return 1;
+        if (packw(a->data, D, 0, D, D, head_wa, D, 0, D, 0, 1, nullptr)) return 1;
+        if (packw(c->data, D, 0, C, D, head_w2, D, 0, D, 0, 1, nullptr)) return 1;
         if (head_ok) {
             const long slot_halfs = (long)(D / 16) * 512;
             half_t* dst = layers[L - 1].stream + (long)layers[L - 1].stream_slots * slot_halfs;
@@ -382,7 +416,9 @@ int svc_dit::pack(const StateDict& sd, hipStream_t st) {
             GETW(b, "skip_linear.bias", D);
             w_longskip = new16(D, D + C16);
             if (!w_longskip) return 1;
-            if (pack_block(0, a->data, D + C, 0, D, D + C, w_longskip, D + C16, 0, 0, 1, nullptr, st)) return 1;
+            // [final-norm rows | x]: a tap of D columns and one of C16 (C packed, the rest zero)
+            if (packw(a->data, D + C, 0, D, D, w_longskip, D + C16, 0, D, 0, 1, nullptr)) return 1;
+            if (packw(a->data, D + C, D, D, C, w_longskip, D + C16, D, C16, 0, 1, nullptr)) return 1;
             b_longskip = copy_vec(wts, b->data, D, st);
             if (!b_longskip) return 1;
         }
@@ -396,9 +432,9 @@ int svc_dit::pack(const StateDict& sd, hipStream_t st) {
         w_resproj = new16(W, D);
         w_conv2 = new16(C, W);
         if (!w_conv1 || !w_resproj || !w_conv2) return 1;
-        if (pack_block(0, c1w->data, D, 0, W, D, w_conv1, D, 0, 0, 1, nullptr, st)) return 1;
-        if (pack_block(0, rpw->data, D, 0, W, D, w_resproj, D, 0, 0, 1, nullptr, st)) return 1;
-        if (pack_block(0, c2w->data, W, 0, C, W, w_conv2, W, 0, 0, 1, nullptr, st)) return 1;
+        if (packw(c1w->data, D, 0, W, D, w_conv1, D, 0, D, 0, 1, nullptr)) return 1;
+        if (packw(rpw->data, D, 0, W, D, w_resproj, D, 0, D, 0, 1, nullptr)) return 1;
+        if (packw(c2w->data, W, 0, C, W, w_conv2, W, 0, W, 0, 1, nullptr)) return 1;
         b_conv1 = copy_vec(wts, c1b->data, W, st);
         b_resproj = copy_vec(wts, rpb->data, W, st);
         b_conv2 = copy_vec(wts, c2b->data, C, st);
@@ -413,7 +449,7 @@ int svc_dit::pack(const StateDict& sd, hipStream_t st) {
             GETW(mb, "final_layer.adaLN_modulation.1.bias", 2 * W);
             w_fl = new16(W, W);
             if (!w_fl) return 1;
-            if (pack_block(0, fl.v, W, 0, W, W, w_fl, W, 0, 0, 1, fl.scale, st)) return 1;
+            if (packw(fl.v, W, 0, W, W, w_fl, W, 0, W, 0, 1, fl.scale)) return 1;
             b_fl = copy_vec(wts, flb->data, W, st);
             fl_mod_w = copy_vec(wts, mw->data, 2L * W * W, st);
             fl_mod_b = copy_vec(wts, mb->data, 2 * W, st);
@@ -452,8 +488,10 @@ int svc_dit::pack(const StateDict& sd, hipStream_t st) {
                 if (!wn_in[i] || !inb_perm) return 1;
                 for (int half = 0; half < 2; ++half) {
                     // src [2W][W][k] -> dst row (2j+half), column tap*W + ci
-                    if (pack_f16_launch(in.v + (long)half * W * W * WK, wn_in[i] + (long)half * WK * W, W, WK, W,
-                                        (long)W * WK, 1, WK, 2L * WK * W, W, 1, in.scale ? in.scale + (long)half * W : nullptr, st)) return 1;
+                    for (int sub = 0; sub < ns; ++sub)      // precision 2: [w_hi | w_lo | w_hi] per tap
+                        if ((sub == 1 ? pack_f16_lo_launch : pack_f16_launch)(
+                                in.v + (long)half * W * W * WK, wn_in[i] + (long)half * WK * W * ns + (long)sub * W, W, WK, W, (long)W * WK, 1,
+                                WK, 2L * WK * W * ns, (long)W * ns, 1, in.scale ? in.scale + (long)half * W : nullptr, st)) return 1;
                     if (pack_f32_launch(inb->data + (long)half * W, inb_perm + half, W, 1, 1, 1, 0, 0, 2, 0, 0, nullptr, st)) return 1;
                 }
                 // total per-layer additive vector = permuted(cond bias) + permuted(in bias)
@@ -470,14 +508,13 @@ int svc_dit::pack(const StateDict& sd, hipStream_t st) {
                 if (i < NL - 1) {
                     wn_res[i] = new16(W, W);
                     if (!wn_res[i]) return 1;
-                    if (pack_block(0, rs.v, W, 0, W, W, wn_res[i], W, 0, 0, 1, rs.scale, st)) return 1;
+                    if (packw(rs.v, W, 0, W, W, wn_res[i], W, 0, W, 0, 1, rs.scale)) return 1;
                     wn_res_b[i] = copy_vec(wts, rsb->data, W, st);
                     if (!wn_res_b[i]) return 1;
                 }
                 wn_skip[i] = new16(W, W);
                 if (!wn_skip[i]) return 1;
-                if (pack_block(0, rs.v + skip_row0 * W, W, 0, W, W, wn_skip[i], W, 0, 0, 1,
-                               rs.scale ? rs.scale + skip_row0 : nullptr, st)) return 1;
+                if (packw(rs.v + skip_row0 * W, W, 0, W, W, wn_skip[i], W, 0, W, 0, 1, rs.scale ? rs.scale + skip_row0 : nullptr)) return 1;
                 wn_skip_b[i] = copy_vec(wts, rsb->data + skip_row0, W, st);
                 if (!wn_skip_b[i]) return 1;
             }
@@ -491,9 +528,10 @@ int svc_dit::pack(const StateDict& sd, hipStream_t st) {
         wn_tail = new16(W, Kt);
         b_tail = wts.alloc_n<float>(W, st);
         if (!wn_tail || !b_tail) return 1;
+        // (a tap's block is ns times as wide in precision 2 and keeps its place in the tap order)
         for (int i = 0; i < NL; ++i)
-            SVC_CHECK_HIP(hipMemcpy2DAsync(wn_tail + (long)i * W, Kt * 2, wn_skip[i], (size_t)W * 2, (size_t)W * 2, W, hipMemcpyDeviceToDevice, st));
-        SVC_CHECK_HIP(hipMemcpy2DAsync(wn_tail + (long)NL * W, Kt * 2, w_resproj, (size_t)D * 2, (size_t)D * 2, W, hipMemcpyDeviceToDevice, st));
+            SVC_CHECK_HIP(hipMemcpy2DAsync(wn_tail + (long)i * W * ns, Kt * ns * 2, wn_skip[i], (size_t)W * ns * 2, (size_t)W * ns * 2, W, hipMemcpyDeviceToDevice, st));
+        SVC_CHECK_HIP(hipMemcpy2DAsync(wn_tail + (long)NL * W * ns, Kt * ns * 2, w_resproj, (size_t)D * ns * 2, (size_t)D * ns * 2, W, hipMemcpyDeviceToDevice, st));
         if (add_rowvec_launch(b_tail, b_resproj, 0, wn_skip_b[0], 1, W, st)) return 1;
         for (int i = 1; i < NL; ++i)
             if (add_rowvec_launch(b_tail, b_tail, 0, wn_skip_b[i], 1, W, st)) return 1;
@@ -579,6 +617,21 @@ int svc_dit::reserve(int n_streams, int B, int T, int n_steps, hipStream_t st) {
         fo16 = ws.alloc_n<half_t>(M * W, st);
         if (!xr16 || !wnx32 || !wnx16 || !acts16 || !flin32 || !fl16 || !fo16) return 1;
     }
+    if (precision == 2) {
+        auto lo16 = [&](const half_t* hi, long n) -> half_t* { return hi ? ws.alloc_n<half_t>(n, st) : nullptr; };
+        x16_lo = lo16(x16, M * C16); n16_lo = lo16(n16, M * D); qk16_lo = lo16(qk16, M * 2 * D); vt_lo = lo16(vt, nseq * D * vtl);
+        ao16_lo = lo16(ao16, M * D); ff16_lo = lo16(ff16, M * I); h16_lo = lo16(h16, M * D); hm16_lo = lo16(hm16, M * D);
+        xr16_lo = lo16(xr16, M * D); wnx16_lo = lo16(wnx16, M * W); acts16_lo = lo16(acts16, (long)NL * acts_stride);
+        fl16_lo = lo16(fl16, M * W); fo16_lo = lo16(fo16, M * W);
+        skip16_lo.assign(emit.size(), nullptr);
+        for (auto& p : skip16_lo) {
+            p = ws.alloc_n<half_t>(M * D, st);
+            if (!p) return 1;
+        }
+        g32 = ws.alloc_n<float>(M * std::max(3L * D, std::max(2L * I, 2L * W)), st);
+        if (!x16_lo || !n16_lo || !qk16_lo || !vt_lo || !ao16_lo || !ff16_lo || !h16_lo || !g32) return 1;
+        if (wavenet ? (!xr16_lo || !wnx16_lo || !acts16_lo || !fl16_lo || !fo16_lo) : !hm16_lo) return 1;
+    }
     d_kvlen = ws.alloc_n<int>(nseq, st);
     d_convlen = ws.alloc_n<int>(nseq, st);
     d_convlen_w = ws.alloc_n<int>(nseq, st);
@@ -655,6 +708,7 @@ KGemmParams gemm_base(int M, int N, int Lout) {
 int svc_dit::body(int n_streams, int B, int T, int step, hipStream_t st) {
     const int nseq = n_streams * B;
     const int M = nseq * seq_rows;
+    if (precision == 2) return body_x3(n_streams, B, T, step, st);
     const float* mod = d_mod + (long)step * mod_n;
     const bool fused = fused_ok && (long)M >= fused_min_rows;
     // the first panel builds the rows of xin itself (merge seam), the last one runs the mlp head (head seam)
@@ -888,6 +942,277 @@ int svc_dit::head(int n_streams, int B, int T, int step, hipStream_t st) {
         p.w = w_conv2; p.ldw = W; p.bias = b_conv2;
         p.c32 = v32; p.ldc32 = C16;
         if (kgemm_launch(p, 0, KG_EPI_STORE, st)) return 1;
+    }
+    return 0;
+}
+
+// --------------------------------------------------------------------------------------------- precision 2 (fp16x3)
+// The tap-GEMM path of body() / head() with every fp16 operand carried as hi / lo planes.  A linear's taps become the split taps
+// of conv_util.h -- operand sub-taps [a_hi | a_hi | a_lo] against the weight sub-blocks [w_hi | w_lo | w_hi], fp32 accumulate -- on
+// the STORE epilogue with a fp32 result; what the fp16 path's epilogues hand to the next GEMM as fp16 (c16, SwiGLU, gated tanh,
+// RoPE'd q / k, V^T) is made from that fp32 result by a row kernel that writes both planes.  No existing kernel instantiation
+// takes part in a new way: the GEMMs are the split-tap STORE launches the vocoders use.
+namespace {
+// taps [0, n) of p (filled as for the fp16 path, a_ptr = the hi planes) -> 3 n split taps; lo[t] = the lo plane of tap t
+void split_taps(KGemmParams& p, const half_t* const* lo) {
+    const int n = p.n_taps;
+    for (int t = n - 1; t >= 0; --t) {
+        const void* hi = p.a_ptr[t];
+        const long ld = p.a_ld[t];
+        const int shift = p.a_shift[t], kt = p.a_ktiles[t];
+        for (int sub = 2; sub >= 0; --sub) {
+            const int i = 3 * t + sub;
+            p.a_ptr[i] = sub == 2 ? (const void*)lo[t] : hi;
+            p.a_ld[i] = ld; p.a_shift[i] = shift; p.a_ktiles[i] = kt;
+        }
+    }
+    p.n_taps = 3 * n;
+    p.ldw *= 3;
+    p.prof_flop_scale = 1.0f / 3.0f;
+}
+int gemm_x3(KGemmParams& p, std::initializer_list<const half_t*> lo, hipStream_t st) {
+    SVC_REQUIRE((int)lo.size() == p.n_taps && 3 * p.n_taps <= KG_MAX_TAPS, "fp16x3 tap count");
+    split_taps(p, lo.begin());
+    return kgemm_launch(p, 0, KG_EPI_STORE, st);
+}
+}  // namespace
+
+int svc_dit::body_x3(int n_streams, int B, int T, int step, hipStream_t st) {
+    const int nseq = n_streams * B;
+    const int M = nseq * seq_rows;
+    const float* mod = d_mod + (long)step * mod_n;
+    if (prefix_rows_launch(xin, nseq, seq_rows, D, npre, T + npre, d_t1 + (long)step * D, tok_style, cfg.time_as_token ? 1 : 0, st)) return 1;
+    {
+        KGemmParams p = gemm_base(nseq * T, D, T);
+        p.a_ptr[0] = x16; p.a_ld[0] = C16; p.a_ktiles[0] = C16 / 64;
+        p.a_seq_rows = seq_rows; p.a_len = T;
+        p.w = w_merge_x; p.ldw = C16;
+        p.c_seq_rows = seq_rows; p.c_off = npre;
+        p.c32 = xin; p.ldc32 = D;
+        p.res = st_term; p.ldres = D;
+        if (gemm_x3(p, {x16_lo}, st)) return 1;
+    }
+    const int Lw = seq_rows - win0;       // see body(): the last layer's query side and the head run on rows >= win0
+    auto gemm_win = [&](int N) {
+        KGemmParams p = gemm_base(nseq * Lw, N, Lw);
+        p.a_seq_rows = seq_rows; p.c_seq_rows = seq_rows;
+        p.a_off = win0; p.c_off = win0;
+        return p;
+    };
+    const long vts = (long)D * vt_ld;
+    size_t emit_i = 0;
+    std::vector<int> skip_stack;
+    for (int i = 0; i < L; ++i) {
+        const bool tail_only = i == L - 1 && win0 > 0;
+        const Layer& ly = layers[i];
+        const float* lmod = adaptive_blocks ? mod + (long)i * mod_layer_n : nullptr;
+        if (ly.wskip) {
+            const int src = skip_stack.back();
+            skip_stack.pop_back();
+            KGemmParams p = gemm_base(M, D, seq_rows);
+            p.n_taps = 2;
+            p.a_ptr[0] = h16; p.a_ld[0] = D; p.a_ktiles[0] = D / 64;
+            p.a_ptr[1] = skip16[src]; p.a_ld[1] = D; p.a_ktiles[1] = D / 64;
+            p.w = ly.wskip; p.ldw = 2 * D;
+            p.bias = ly.bskip;
+            p.c32 = xin; p.ldc32 = D;
+            if (gemm_x3(p, {h16_lo, skip16_lo[src]}, st)) return 1;
+        }
+        const float *w_a = nullptr, *b_a = nullptr, *gate_a = nullptr, *w_f = nullptr, *b_f = nullptr, *gate_f = nullptr;
+        if (lmod) {
+            if (v2) {
+                b_a = lmod; w_a = lmod + D; gate_a = lmod + 2 * D;
+                b_f = lmod + 3 * D; w_f = lmod + 4 * D; gate_f = lmod + 5 * D;
+            } else {
+                w_a = lmod; b_a = lmod + D; w_f = lmod + 2 * D; b_f = lmod + 3 * D;
+            }
+        }
+        if (rmsnorm_mod_hl_launch(xin, D, n16, n16_lo, D, ly.g_attn, w_a, b_a, 0, v2 ? 1 : 0, M, D, seq_rows, 1e-5f, st)) return 1;
+        {
+            KGemmParams p = gemm_base(M, 3 * D, seq_rows);
+            p.a_ptr[0] = n16; p.a_ld[0] = D; p.a_ktiles[0] = D / 64;
+            p.w = ly.wqkv; p.ldw = D;
+            p.c32 = g32; p.ldc32 = 3 * D;
+            if (gemm_x3(p, {n16_lo}, st)) return 1;
+        }
+        // RoPE and the q scale in fp32 on the stored projection, then q | k as hi / lo rows and V^T as hi / lo planes
+        if (attention_x3_prepare(g32, g32 + D, g32 + 2 * D, 3 * D, rope, 0.125f * 1.4426950408889634f, qk16, qk16_lo, qk16 + D,
+                                 qk16_lo + D, 2 * D, vt, vt_lo, vts, vt_ld, nseq, seq_rows, D, st)) return 1;
+        {
+            AttnX3Params a;
+            memset(&a, 0, sizeof(a));
+            a.q_hi = qk16; a.q_lo = qk16_lo; a.k_hi = qk16 + D; a.k_lo = qk16_lo + D; a.ld_qk = 2 * D;
+            a.vt_hi = vt; a.vt_lo = vt_lo; a.vt_seq_stride = vts; a.vt_ld = vt_ld;
+            a.out_hi = ao16; a.out_lo = ao16_lo; a.ld_out = D;
+            a.n_seq = nseq; a.H = H; a.seq_rows = seq_rows; a.Tq = seq_rows;
+            a.q_start = tail_only ? win0 : 0;
+            a.kv_len = d_kvlen;
+            if (attention_x3_launch(a, st)) return 1;
+        }
+        {
+            KGemmParams p = tail_only ? gemm_win(D) : gemm_base(M, D, seq_rows);
+            p.a_ptr[0] = ao16; p.a_ld[0] = D; p.a_ktiles[0] = D / 64;
+            p.w = ly.wo; p.ldw = D;
+            p.gate = gate_a; p.ld_gate = 0;
+            p.res = xin; p.ldres = D;
+            p.c32 = xin; p.ldc32 = D;
+            if (gemm_x3(p, {ao16_lo}, st)) return 1;
+        }
+        if (rmsnorm_mod_hl_launch(xin, D, n16, n16_lo, D, ly.g_ffn, w_f, b_f, 0, v2 ? 1 : 0, M, D, seq_rows, 1e-5f, st)) return 1;
+        {
+            KGemmParams p = tail_only ? gemm_win(2 * I) : gemm_base(M, 2 * I, seq_rows);
+            p.a_ptr[0] = n16; p.a_ld[0] = D; p.a_ktiles[0] = D / 64;
+            p.w = ly.w13; p.ldw = D;
+            p.c32 = g32; p.ldc32 = 2 * I;
+            if (gemm_x3(p, {n16_lo}, st)) return 1;
+            if (split_rows_launch(g32, 2 * I, ff16, ff16_lo, I, M, I, SPLIT_SWIGLU, 1, 0, st)) return 1;
+        }
+        {
+            KGemmParams p = tail_only ? gemm_win(D) : gemm_base(M, D, seq_rows);
+            p.a_ptr[0] = ff16; p.a_ld[0] = I; p.a_ktiles[0] = I / 64;
+            p.w = ly.w2; p.ldw = I;
+            p.gate = gate_f; p.ld_gate = 0;
+            p.res = xin; p.ldres = D;
+            p.c32 = xin; p.ldc32 = D;
+            if (gemm_x3(p, {ff16_lo}, st)) return 1;
+            // the UViT skip operands: the layer output (the residual stream itself) as planes
+            const bool is_emit = std::find(emit.begin(), emit.end(), i) != emit.end();
+            const bool next_recv = i + 1 < L && layers[i + 1].wskip != nullptr;
+            if (is_emit) {
+                if (split_rows_launch(xin, D, skip16[emit_i], skip16_lo[emit_i], D, M, D, SPLIT_PLAIN, 1, 0, st)) return 1;
+                skip_stack.push_back((int)emit_i);
+                ++emit_i;
+            } else if (next_recv) {
+                if (split_rows_launch(xin, D, h16, h16_lo, D, M, D, SPLIT_PLAIN, 1, 0, st)) return 1;
+            }
+        }
+    }
+    {
+        const float* fm = mod + (long)L * mod_layer_n;
+        if (rmsnorm_mod_hl_launch(xin, D, n16, n16_lo, D, g_final, fm, fm + D, 0, v2 ? 1 : 0, M, D, seq_rows, 1e-5f, st)) return 1;
+    }
+    return head_x3(n_streams, B, T, step, st);
+}
+
+int svc_dit::head_x3(int n_streams, int B, int T, int step, hipStream_t st) {
+    const int nseq = n_streams * B;
+    const int M = nseq * seq_rows;
+    const int Lw = seq_rows - win0;
+    auto gemm_win = [&](int N) {
+        KGemmParams p = gemm_base(nseq * Lw, N, Lw);
+        p.a_seq_rows = seq_rows; p.c_seq_rows = seq_rows;
+        p.a_off = win0; p.c_off = win0;
+        return p;
+    };
+    // a GEMM result that is the next GEMM's operand: fp32 rows (dst32, row stride N) -> planes.  Rows below win0 are split too; nothing reads them.
+    auto planes = [&](const float* src, int N, half_t* hi, half_t* lo, int mode = SPLIT_PLAIN) {
+        return split_rows_launch(src, mode == SPLIT_PLAIN ? N : 2 * N, hi, lo, N, M, N, mode, 1, 0, st);
+    };
+    if (!wavenet) {
+        {
+            KGemmParams p = gemm_win(D);
+            p.a_ptr[0] = n16; p.a_ld[0] = D; p.a_ktiles[0] = D / 64;
+            p.w = head_wa; p.ldw = D; p.bias = head_b0; p.act = KG_ACT_SILU;
+            p.c32 = g32; p.ldc32 = D;
+            if (gemm_x3(p, {n16_lo}, st)) return 1;
+            if (planes(g32, D, hm16, hm16_lo)) return 1;
+        }
+        {
+            KGemmParams p = gemm_win(C);
+            p.a_ptr[0] = hm16; p.a_ld[0] = D; p.a_ktiles[0] = D / 64;
+            p.w = head_w2; p.ldw = D; p.bias = head_b2;
+            p.c32 = v32; p.ldc32 = C16;
+            if (gemm_x3(p, {hm16_lo}, st)) return 1;
+        }
+        return 0;
+    }
+    const half_t *xres16 = n16, *xres16_lo = n16_lo;
+    if (cfg.long_skip_connection) {
+        KGemmParams p = gemm_win(D);
+        p.n_taps = 2;
+        p.a_ptr[0] = n16; p.a_ld[0] = D; p.a_ktiles[0] = D / 64;
+        p.a_ptr[1] = x16; p.a_ld[1] = C16; p.a_ktiles[1] = C16 / 64;
+        p.w = w_longskip; p.ldw = D + C16; p.bias = b_longskip;
+        p.c32 = g32; p.ldc32 = D;
+        if (gemm_x3(p, {n16_lo, x16_lo}, st)) return 1;
+        if (planes(g32, D, xr16, xr16_lo)) return 1;
+        xres16 = xr16; xres16_lo = xr16_lo;
+    }
+    {
+        KGemmParams p = gemm_win(W);
+        p.a_ptr[0] = xres16; p.a_ld[0] = D; p.a_ktiles[0] = D / 64;
+        p.w = w_conv1; p.ldw = D; p.bias = b_conv1;
+        p.c32 = wnx32; p.ldc32 = W;
+        if (gemm_x3(p, {xres16_lo}, st)) return 1;
+        if (planes(wnx32, W, wnx16, wnx16_lo)) return 1;
+    }
+    const half_t* tap_lo[KG_MAX_TAPS / 3];
+    for (int i = 0; i < NL; ++i) {
+        int dil = 1;
+        for (int j = 0; j < i; ++j) dil *= cfg.wn_dilation_rate;
+        half_t* acts = acts16 + (long)i * acts_stride;
+        half_t* acts_lo = acts16_lo + (long)i * acts_stride;
+        {
+            KGemmParams p = gemm_win(2 * W);
+            p.n_taps = WK;
+            const int total = (WK - 1) * dil;
+            const int left = total - total / 2;
+            for (int t = 0; t < WK; ++t) {
+                p.a_ptr[t] = wnx16; p.a_ld[t] = W; p.a_ktiles[t] = W / 64; p.a_shift[t] = t * dil - left;
+                tap_lo[t] = wnx16_lo;
+            }
+            p.pad_mode = KG_PAD_REFLECT;
+            p.reflect_min = std::max(left, total - left) + 1;
+            p.seq_len = d_convlen_w;
+            p.w = wn_in[i]; p.ldw = (long)WK * W;
+            p.rowvec = d_gcond + (long)step * 2 * W * NL + 2L * W * i; p.ld_rowvec = 0;
+            p.c32 = g32; p.ldc32 = 2 * W;
+            split_taps(p, tap_lo);
+            if (kgemm_launch(p, 0, KG_EPI_STORE, st)) return 1;
+            if (planes(g32, W, acts, acts_lo, SPLIT_TANHSIG)) return 1;
+        }
+        if (i < NL - 1) {
+            KGemmParams p = gemm_win(W);
+            p.a_ptr[0] = acts; p.a_ld[0] = W; p.a_ktiles[0] = W / 64;
+            p.w = wn_res[i]; p.ldw = W; p.bias = wn_res_b[i];
+            p.res = wnx32; p.ldres = W;
+            p.c32 = wnx32; p.ldc32 = W;
+            if (gemm_x3(p, {acts_lo}, st)) return 1;
+            if (planes(wnx32, W, wnx16, wnx16_lo)) return 1;
+        }
+    }
+    {
+        KGemmParams p = gemm_win(W);
+        p.n_taps = NL + 1;
+        for (int i = 0; i < NL; ++i) {
+            p.a_ptr[i] = acts16 + (long)i * acts_stride; p.a_ld[i] = W; p.a_ktiles[i] = W / 64;
+            tap_lo[i] = acts16_lo + (long)i * acts_stride;
+        }
+        p.a_ptr[NL] = xres16; p.a_ld[NL] = D; p.a_ktiles[NL] = D / 64;
+        tap_lo[NL] = xres16_lo;
+        p.w = wn_tail; p.ldw = (long)NL * W + D; p.bias = b_tail;
+        p.c32 = flin32; p.ldc32 = W;
+        split_taps(p, tap_lo);
+        if (kgemm_launch(p, 0, KG_EPI_STORE, st)) return 1;
+    }
+    {
+        const float* fm = d_flmod + (long)step * 2 * W;
+        if (layernorm_mod_hl_launch(flin32, W, fl16, fl16_lo, W, fm + W, fm, M, W, 1e-6f, st)) return 1;
+    }
+    {
+        KGemmParams p = gemm_win(W);
+        p.a_ptr[0] = fl16; p.a_ld[0] = W; p.a_ktiles[0] = W / 64;
+        p.w = w_fl; p.ldw = W; p.bias = b_fl;
+        p.c32 = g32; p.ldc32 = W;
+        if (gemm_x3(p, {fl16_lo}, st)) return 1;
+        if (planes(g32, W, fo16, fo16_lo)) return 1;
+    }
+    {
+        KGemmParams p = gemm_win(C);
+        p.a_ptr[0] = fo16; p.a_ld[0] = W; p.a_ktiles[0] = W / 64;
+        p.w = w_conv2; p.ldw = W; p.bias = b_conv2;
+        p.c32 = v32; p.ldc32 = C16;
+        if (gemm_x3(p, {fo16_lo}, st)) return 1;
     }
     return 0;
 }
@@ -1194,6 +1519,7 @@ int svc_dit::run_group(const svc_cfm_args_t* a, const uint64_t* seeds, const int
                            nb, T, C, d_plen, n_streams, copy_stride);
     }
     SVC_CHECK_HIP(hipGetLastError());
+    if (split_state(n_streams, nb, st)) return 1;
     hipLaunchKernelGGL(prompt_rows_kernel, dim3(cdiv(n_el, 256)), dim3(256), 0, st, a->prompt, C, P, prompt32, (long)C32,
                        seq_rows, T, d_plen, nb, (const int*)d_rowmap);
     SVC_CHECK_HIP(hipGetLastError());
@@ -1206,6 +1532,7 @@ int svc_dit::run_group(const svc_cfm_args_t* a, const uint64_t* seeds, const int
                                v32, (long)C16, (long)nb * seq_rows * C16, npre, nb, T, C, d_plen, dts[s],
                                (const float4*)d_rowtab, stream_a, stream_b, n_streams, copy_stride);
             SVC_CHECK_HIP(hipGetLastError());
+            if (split_state(n_streams, nb, s_)) return 1;
         }
         return 0;
     };
@@ -1254,12 +1581,22 @@ extern "C" {
 
 int svc_dit_create(const svc_dit_config_t* cfg, const svc_tensor_desc_t* weights, int n_weights, void* stream,
                    svc_dit_t** out) {
+    return svc_dit_create_ex(cfg, weights, n_weights, 1, stream, out);
+}
+
+int svc_dit_precision(svc_dit_t* m) { return m ? m->precision : 0; }
+
+int svc_dit_create_ex(const svc_dit_config_t* cfg, const svc_tensor_desc_t* weights, int n_weights, int precision, void* stream,
+                      svc_dit_t** out) {
     SVC_REQUIRE(cfg && weights && out, "null argument");
+    SVC_REQUIRE(precision == 1 || precision == 2,
+                "svc_dit_create_ex: precision must be 1 (fp16 operands) or 2 (fp16x3); got " + std::to_string(precision));
     SVC_REQUIRE(cfg->hidden_dim == cfg->num_heads * 64, "head_dim must be 64 (hidden_dim = 64 * num_heads)");
     SVC_REQUIRE(cfg->content_dim % 32 == 0, "content_dim must be a multiple of 32");
     SVC_REQUIRE(cfg->in_channels % 8 == 0 && cfg->in_channels <= 128, "in_channels must be a multiple of 8, <= 128");
     svc_dit* m = new svc_dit();
     m->cfg = *cfg;
+    m->precision = precision;
     m->device = current_device();
     m->v2 = cfg->version == 2;
     m->D = cfg->hidden_dim; m->H = cfg->num_heads; m->L = cfg->depth; m->C = cfg->in_channels;
@@ -1277,7 +1614,8 @@ int svc_dit_create(const svc_dit_config_t* cfg, const svc_tensor_desc_t* weights
     m->C32 = (int)round_up(m->C, 32);
     m->adaptive_blocks = m->v2 || !cfg->time_as_token;
     if (m->wavenet) {
-        if (m->W % 64 != 0 || m->W != m->D || m->WK * 1 > KG_MAX_TAPS || m->npre != 0) {
+        const int sub = precision == 2 ? 3 : 1;      // split taps: three per tap
+        if (m->W % 64 != 0 || m->W != m->D || m->WK * sub > KG_MAX_TAPS || (sub > 1 && (m->NL + 1) * sub > KG_MAX_TAPS) || m->npre != 0) {
             set_error("wavenet head needs wn_hidden_dim == hidden_dim (FinalLayer modulates with t1), no prefix tokens");
             delete m;
             return 1;
@@ -1315,12 +1653,14 @@ int svc_dit_set_microbatch(svc_dit_t* m, int utterances) {
 
 int svc_dit_set_fused_min_rows(svc_dit_t* m, long rows) {
     SVC_REQUIRE(m, "null argument");
+    if (m->precision != 1) return 0;              // no fused path to steer
     m->fused_min_rows = rows < 0 ? 10240 : rows;
     return 0;
 }
 
 int svc_dit_set_fused_seams(svc_dit_t* m, int mask) {
     SVC_REQUIRE(m && mask >= 0 && mask <= 3, "svc_dit_set_fused_seams: mask is bit 0 (merge) | bit 1 (head)");
+    if (m->precision != 1) return 0;
     m->seams = mask;
     return 0;
 }
@@ -1531,6 +1871,7 @@ int svc_dit_forward(svc_dit_t* m, int N, int T, const float* x, const float* pro
     if (m->tables(tv, st)) return 1;
     const int C = m->C, C16 = m->C16, C32 = m->C32, rows = m->seq_rows;
     if (bct_to_btc_launch(x, N, C, T, m->x32, C16, m->x16, C16, rows, T, 1.0f, st)) return 1;
+    if (m->split_state(1, N, st)) return 1;
     const long n_el = (long)N * T * C;
     hipLaunchKernelGGL(prompt_rows_kernel, dim3(cdiv(n_el, 256)), dim3(256), 0, st, prompt_x, C, T, m->prompt32, (long)C32,
                        rows, T, m->d_plen, N, (const int*)nullptr);

@@ -258,6 +258,125 @@ __global__ void add_rowvec_kernel(float* __restrict__ dst, const float* __restri
     dst[(long)s * n + c] = (a ? a[(long)s * lda + c] : 0.f) + bvec[c];
 }
 
+
+// ---- split-precision results (the DiT's fp16x3 mode): the value v a fp16 kernel would round once leaves as two planes,
+// hi = half(v) and lo = half(v - float(hi))
+__device__ __forceinline__ void split2(float a, float b, half2v* hi, half2v* lo) {
+    const half_t ha = (half_t)a, hb = (half_t)b;
+    *hi = (half2v){ha, hb};
+    *lo = (half2v){(half_t)(a - (float)ha), (half_t)(b - (float)hb)};
+}
+
+// rmsnorm_mod_kernel with hi / lo output planes
+__global__ __launch_bounds__(256) void rmsnorm_mod_hl_kernel(const float* __restrict__ x, long ldx, half_t* __restrict__ y,
+                                                             half_t* __restrict__ y_lo, long ldy, const float* __restrict__ gamma,
+                                                             const float* __restrict__ w, const float* __restrict__ b,
+                                                             long ld_wb, int add_one, int rows, int D, int seq_rows, float eps) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= rows) return;
+    const float2* xr = reinterpret_cast<const float2*>(x + (long)row * ldx);
+    const int n2 = D >> 1;
+    const int seq = row / seq_rows;
+    const float2* g2 = reinterpret_cast<const float2*>(gamma);
+    const float2* w2 = w ? reinterpret_cast<const float2*>(w + (long)seq * ld_wb) : nullptr;
+    const float2* b2 = b ? reinterpret_cast<const float2*>(b + (long)seq * ld_wb) : nullptr;
+    const float one = add_one ? 1.f : 0.f;
+    float2 v[8];
+    float ss = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int e = lane + 64 * i;
+        if (e < n2) { v[i] = xr[e]; ss += v[i].x * v[i].x + v[i].y * v[i].y; }
+    }
+    ss = wave_sum(ss);
+    const float rs = rsqrtf(ss / (float)D + eps);
+    half2v* yh = reinterpret_cast<half2v*>(y + (long)row * ldy);
+    half2v* yl = reinterpret_cast<half2v*>(y_lo + (long)row * ldy);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int e = lane + 64 * i;
+        if (e < n2) {
+            const float2 g = g2[e];
+            float o0 = v[i].x * rs * g.x, o1 = v[i].y * rs * g.y;
+            if (w2) { const float2 ww = w2[e]; o0 *= (one + ww.x); o1 *= (one + ww.y); }
+            if (b2) { const float2 bb = b2[e]; o0 += bb.x; o1 += bb.y; }
+            split2(o0, o1, yh + e, yl + e);
+        }
+    }
+}
+
+// layernorm_mod_kernel with hi / lo output planes
+__global__ __launch_bounds__(256) void layernorm_mod_hl_kernel(const float* __restrict__ x, long ldx, half_t* __restrict__ y,
+                                                               half_t* __restrict__ y_lo, long ldy, const float* __restrict__ scale,
+                                                               const float* __restrict__ shift, int rows, int D, float eps) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= rows) return;
+    const float2* xr = reinterpret_cast<const float2*>(x + (long)row * ldx);
+    const int n2 = D >> 1;
+    float2 v[8];
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int e = lane + 64 * i;
+        if (e < n2) { v[i] = xr[e]; s += v[i].x + v[i].y; }
+    }
+    const float mean = wave_sum(s) / (float)D;
+    float ss = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int e = lane + 64 * i;
+        if (e < n2) { const float a = v[i].x - mean, c = v[i].y - mean; ss += a * a + c * c; }
+    }
+    const float rs = rsqrtf(wave_sum(ss) / (float)D + eps);
+    const float2* sc2 = reinterpret_cast<const float2*>(scale);
+    const float2* sh2 = reinterpret_cast<const float2*>(shift);
+    half2v* yh = reinterpret_cast<half2v*>(y + (long)row * ldy);
+    half2v* yl = reinterpret_cast<half2v*>(y_lo + (long)row * ldy);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int e = lane + 64 * i;
+        if (e < n2) {
+            const float2 sc = sc2[e], sh = sh2[e];
+            split2((v[i].x - mean) * rs * (1.f + sc.x) + sh.x, (v[i].y - mean) * rs * (1.f + sc.y) + sh.y, yh + e, yl + e);
+        }
+    }
+}
+
+// fp32 rows -> hi / lo planes, two output columns per thread (see split_rows_launch)
+template <int MODE>
+__global__ __launch_bounds__(256) void split_rows_kernel(const float* __restrict__ src, long ld_src, half_t* __restrict__ hi,
+                                                         half_t* __restrict__ lo, long ld_out, long rows, int cols, int n_copies,
+                                                         long copy_stride) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int n2 = cols >> 1;
+    if (i >= rows * n2) return;
+    const long row = i / n2;
+    const int c = 2 * (int)(i - row * n2);
+    float o0, o1;
+    if constexpr (MODE == SPLIT_PLAIN) {
+        const float2 a = *reinterpret_cast<const float2*>(src + row * ld_src + c);
+        o0 = a.x; o1 = a.y;
+    } else {
+        constexpr float LOG2E = 1.4426950408889634f;
+        const float4v a = *reinterpret_cast<const float4v*>(src + row * ld_src + 2 * c);
+        if constexpr (MODE == SPLIT_SWIGLU) {
+            o0 = a[0] * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-a[0] * LOG2E)) * a[1];
+            o1 = a[2] * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-a[2] * LOG2E)) * a[3];
+        } else {
+            o0 = tanhf(a[0]) / (1.0f + expf(-a[1]));
+            o1 = tanhf(a[2]) / (1.0f + expf(-a[3]));
+        }
+    }
+    half2v h, l;
+    split2(o0, o1, &h, &l);
+    for (int k = 0; k < n_copies; ++k) {
+        *reinterpret_cast<half2v*>(hi + k * copy_stride + row * ld_out + c) = h;
+        *reinterpret_cast<half2v*>(lo + k * copy_stride + row * ld_out + c) = l;
+    }
+}
+
 }  // namespace
 
 #define LAUNCH_CHECK() SVC_CHECK_HIP(hipGetLastError())
@@ -276,6 +395,41 @@ int layernorm_mod_launch(const float* x, long ldx, half_t* y, long ldy, const fl
     SVC_REQUIRE(D % 2 == 0 && D <= 1024, "layernorm shape");
     hipLaunchKernelGGL(layernorm_mod_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, st, x, ldx, y, ldy, scale, shift, rows,
                        D, eps);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int rmsnorm_mod_hl_launch(const float* x, long ldx, half_t* y, half_t* y_lo, long ldy, const float* gamma, const float* w,
+                          const float* b, long ld_wb, int add_one, int rows, int D, int seq_rows, float eps, hipStream_t st) {
+    SVC_REQUIRE(D % 2 == 0 && D <= 1024 && ldx % 2 == 0 && ldy % 2 == 0 && y && y_lo, "rmsnorm (hi / lo) shape");
+    hipLaunchKernelGGL(rmsnorm_mod_hl_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, st, x, ldx, y, y_lo, ldy, gamma, w, b, ld_wb,
+                       add_one, rows, D, seq_rows, eps);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int layernorm_mod_hl_launch(const float* x, long ldx, half_t* y, half_t* y_lo, long ldy, const float* scale, const float* shift,
+                            int rows, int D, float eps, hipStream_t st) {
+    SVC_REQUIRE(D % 2 == 0 && D <= 1024 && ldx % 2 == 0 && ldy % 2 == 0 && y && y_lo, "layernorm (hi / lo) shape");
+    hipLaunchKernelGGL(layernorm_mod_hl_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, st, x, ldx, y, y_lo, ldy, scale, shift, rows,
+                       D, eps);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int split_rows_launch(const float* src, long ld_src, half_t* hi, half_t* lo, long ld_out, long rows, int cols, int mode,
+                      int n_copies, long copy_stride, hipStream_t st) {
+    SVC_REQUIRE(src && hi && lo && cols % 2 == 0 && ld_out % 2 == 0 && ld_src % (mode == SPLIT_PLAIN ? 2 : 4) == 0 && n_copies >= 1,
+                "split_rows: even column count and plane stride, source stride a multiple of 2 (paired modes: 4)");
+    const long n = rows * (cols / 2);
+    if (n == 0) return 0;
+    const dim3 grid(cdiv(n, 256));
+    if (mode == SPLIT_SWIGLU)
+        hipLaunchKernelGGL(split_rows_kernel<SPLIT_SWIGLU>, grid, dim3(256), 0, st, src, ld_src, hi, lo, ld_out, rows, cols, n_copies, copy_stride);
+    else if (mode == SPLIT_TANHSIG)
+        hipLaunchKernelGGL(split_rows_kernel<SPLIT_TANHSIG>, grid, dim3(256), 0, st, src, ld_src, hi, lo, ld_out, rows, cols, n_copies, copy_stride);
+    else
+        hipLaunchKernelGGL(split_rows_kernel<SPLIT_PLAIN>, grid, dim3(256), 0, st, src, ld_src, hi, lo, ld_out, rows, cols, n_copies, copy_stride);
     LAUNCH_CHECK();
     return 0;
 }

@@ -214,6 +214,23 @@ def attention(q, k, v, kv_lens=None):
     return out
 
 
+def attention_x3(q, k, v, kv_lens, Tq=None, q_start=0, out=None):
+    """Mirror of svc_op_attention_x3 (include/seedvc_hip.h): the split-precision (fp16x3) attention of the DiT's precision 2.
+    q, k, v (n_seq, seq_rows, H, 64) fp32, RoPE already applied -> softmax(q k^T / 8, keys < kv_lens[seq]) v for the query rows
+    [q_start, Tq) of every sequence; the other rows of `out` (given, or NaN-filled) are left as they are."""
+    n_seq, seq_rows, H, hd = q.shape
+    assert hd == 64 and k.shape == q.shape and v.shape == q.shape
+    dev = q.device
+    with torch.cuda.device(dev):
+        q, k, v = _lib.f32c(q), _lib.f32c(k), _lib.f32c(v)
+        if out is None:
+            out = torch.full_like(q, float("nan"))
+        lens = _lib.i64_host([int(x) for x in kv_lens])
+        _lib.check(_lib.lib().svc_op_attention_x3(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(out), n_seq, seq_rows, H,
+                                                  seq_rows if Tq is None else int(Tq), int(q_start), lens, _lib.stream_ptr()))
+    return out
+
+
 def attention_ex(a, device="cuda:0", fill16=0x6A5A, fill32=-777.25):
     """Test aid over svc_op_attention_ex (include/seedvc_hip.h): ONE attention launch on buffers already in the kernels' layout.
     `a` maps the fields of svc_attention_t to ints and fp16 CPU or device tensors, taken exactly as given: either qk

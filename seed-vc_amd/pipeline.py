@@ -1048,10 +1048,17 @@ class V2HotPath:
     ar: seedvc_amd.ar.ARModel (setup_caches(max_batch_size=B) done by the caller); ar_lr / cfm_lr:
     seedvc_amd.length_regulator.InterpolateRegulator (v2_ar / v2_cfm); cfm: seedvc_amd.cfm.CFM (v2); vocoder: BigVGAN.
     ragged_vocoder: `_vocode`'s `ragged` -- a batch of several output lengths is one ragged vocoder call (True) or one plain
-    call per length (False)."""
+    call per length (False).
+    cfm_timbre: None, or a second CFM (same weights and device) that samples the timbre branch -- `convert_long_batch` /
+    `convert_long_stream` with convert_style=False -- instead of `cfm`.  The reference runs that branch's CFM in fp32
+    (modules/v2/vc_wrapper.py:745) beside a fp16 style branch: CFM(..., precision="fp16x3") here reproduces it.  With None
+    every call is the call it was."""
 
-    def __init__(self, ar, ar_lr, cfm_lr, cfm, vocoder, ragged_vocoder=True, ar_prefill="slot"):
+    def __init__(self, ar, ar_lr, cfm_lr, cfm, vocoder, ragged_vocoder=True, ar_prefill="slot", cfm_timbre=None):
         self.ar, self.ar_lr, self.cfm_lr, self.cfm, self.vocoder = ar, ar_lr, cfm_lr, cfm, vocoder
+        if cfm_timbre is not None and (cfm_timbre.device != cfm.device or cfm_timbre.in_channels != cfm.in_channels):
+            raise ValueError("V2HotPath: cfm_timbre must sit on cfm's device and have its in_channels")
+        self.cfm_timbre = cfm_timbre
         self.ragged_vocoder = ragged_vocoder
         self.ar_prefill = ar_prefill           # "slot" | "ragged": how the AR prompts are prefilled (ARModel.generate_batch)
         self.device = cfm.device
@@ -1418,7 +1425,7 @@ class V2HotPath:
                     uk.append((c[0], k - first_of.setdefault(c[0], k)))
                 it = iter(uk)
                 pool_noise = lambda T: noise_fn(*next(it), T)          # noqa: E731
-            result = _long_pool(self.cfm, self.vocoder, utterances, n_timesteps, list(cfg_rates), hop, max_context_window, overlap_frame_len,
+            result = _long_pool(self.cfm_timbre or self.cfm, self.vocoder, utterances, n_timesteps, list(cfg_rates), hop, max_context_window, overlap_frame_len,
                                 pool_noise, None, max_chunks, self.ragged_vocoder, seeds, lambda s: _vocoder_seeds(self.vocoder, s),
                                 dict(random_voice=True) if random_voice else None, sampler=sampler)
             self._mark("pool")
@@ -1466,7 +1473,7 @@ class V2HotPath:
                 return
             with torch.cuda.device(dev):
                 utterances, _ = self._timbre_utterances(files)
-            yield from _long_stream(what, self.cfm, self.vocoder, utterances, n_timesteps, list(cfg_rates), hop, max_context_window,
+            yield from _long_stream(what, self.cfm_timbre or self.cfm, self.vocoder, utterances, n_timesteps, list(cfg_rates), hop, max_context_window,
                                     overlap_frame_len, noise_fn, None, max_chunks, first_chunks, growth, self.ragged_vocoder, seeds,
                                     lambda s: _vocoder_seeds(self.vocoder, s), pcm16, to_host, lookahead,
                                     dict(random_voice=True) if random_voice else None, sampler=sampler)

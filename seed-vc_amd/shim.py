@@ -58,14 +58,15 @@ def dit_cfg_from_v2_module(estimator):
                             style_as_token=bool(estimator.style_as_token), uvit=bool(estimator.uvit_skip_connection))
 
 
-def patch_cfm(ref_cfm, model_params=None, device=None):
+def patch_cfm(ref_cfm, model_params=None, device=None, precision=1):
     """Replace `ref_cfm.inference` (modules/flow_matching.py:30; v2 modules/v2/cfm.py:16) by the HIP sampler; same
     signature.  v1: pass the preset's `model_params`; v2 (hydra-built `modules.v2.cfm.CFM`): the configuration is read
-    from the estimator module itself."""
+    from the estimator module itself.  precision: 1 / "fp16" where the driver runs the sampler under fp16 autocast
+    (`fp16=True`), 2 / "fp16x3" where it runs it in fp32 (`--fp16 False`, CPU runs, the v2 timbre-only branch): `cfm.dit_precision`."""
     device = device or next(ref_cfm.parameters()).device
     is_v2 = type(ref_cfm.estimator).__module__.endswith("v2.dit_wrapper")
     cfg = dit_cfg_from_v2_module(ref_cfm.estimator) if is_v2 else dit_cfg_from_reference_args(model_params)
-    hip = CFM(cfg, ref_cfm.estimator.state_dict(), device)
+    hip = CFM(cfg, ref_cfm.estimator.state_dict(), device, precision)
 
     if is_v2:
         def inference(self, mu, x_lens, prompt, style, n_timesteps, temperature=1.0, inference_cfg_rate=(0.5, 0.5),
