@@ -269,6 +269,66 @@ int svc_hift_noise_draws(uint64_t seed, int NH, long n, float* phase0, float* no
 int svc_bigvgan_set_microbatch(svc_bigvgan_t* m, int utterances);
 int svc_hift_set_microbatch(svc_hift_t* m, int utterances);
 
+/* ---- precision plan of an fp16p8 handle (precision 3): which convs run as fp16 + fp8 corrections.
+ * The fp8 correction bytes have a fixed window: activations carry no scale (bytes fp8(hi), fp8(2^11 lo), clamp +-448), weights
+ * one power-of-two scale per layer.  A conv whose operands lie outside it silently falls back to plain-fp16 operand error.
+ * The plan holds one veto per CANDIDATE conv; a vetoed conv runs the fp16x3 form instead (and whoever writes its operand planes
+ * writes fp16 residuals): a layer property, never the batch's, so batched, ragged and micro-batched runs stay bit-identical
+ * to the run alone under any plan.  The empty plan (the default) is today's fp16p8, launch for launch; the full plan gives
+ * the bits of a precision-2 (fp16x3) handle.
+ * Candidates: the ResBlock convs that own the fp8 weight packing (k >= 3, at least 64 padded channels in and out), in model
+ * order: BigVGAN resblocks.<i> for i ascending, HiFT per stage i source_resblocks.<i> then resblocks.<i * num_kernels + j>;
+ * inside a ResBlock convs1.<d>, convs2.<d> for d ascending.  svc_*_plan_name gives candidate i's state-dict prefix (e.g.
+ * "resblocks.3.convs2.1"; valid while the handle lives; NULL out of range), so a plan can be stored next to a checkpoint and
+ * restored with svc_*_plan_set without calibration data.
+ * get / set: veto[n] bytes (0 = runs p8), n == svc_*_plan_size(m).  reset clears every veto.  All of them, and calibrate,
+ * are host-side state changes of the handle: call them between forwards, not concurrently with one.
+ * Refused (non-zero, svc_last_error(), plan untouched): a NULL argument, a handle of another precision, n != plan size. */
+int svc_bigvgan_plan_size(svc_bigvgan_t* m);          /* -1: NULL handle or not an fp16p8 handle */
+const char* svc_bigvgan_plan_name(svc_bigvgan_t* m, int i);
+int svc_bigvgan_plan_get(svc_bigvgan_t* m, uint8_t* veto, int n);
+int svc_bigvgan_plan_set(svc_bigvgan_t* m, const uint8_t* veto, int n);
+int svc_bigvgan_plan_reset(svc_bigvgan_t* m);
+/* One census record (csrc/range_census.hip): counts over the live elements of a conv's operand planes (hi fp16, lo fp16
+ * residual) and the energy of each term and of what its fp8 byte loses; the bytes are those of the hardware convert the p8
+ * producers use.  n: hi != 0; n_hi_clamp: |hi| > 448; n_hi_sub: 0 < |hi| < 2^-6 (e4m3 subnormal); n_lo_flush: lo != 0 whose
+ * byte fp8(2^11 lo) is zero; n_lo_clamp: |2^11 lo| > 448; s_hi2 = sum hi^2, s_hi_err2 = sum (hi - dq fp8(hi))^2, s_lo2 =
+ * sum lo^2, s_lo_err2 = sum (lo - 2^-11 dq fp8(2^11 lo))^2. */
+typedef struct svc_census {
+    int64_t n, n_hi_clamp, n_hi_sub, n_lo_flush, n_lo_clamp;
+    double max_hi;
+    double s_hi2, s_hi_err2, s_lo2, s_lo_err2;
+} svc_census_t;
+/* One report row of calibrate.  rho = s_lo_err2 / s_lo2 and eta = s_hi_err2 / s_hi2 of the conv's activation planes (0 for an
+ * all-zero term); omega_hi / omega_lo: the same two ratios of its weight bytes, the largest over the output channels
+ * (all-zero channels exempt); L: the conv's rows per utterance (of the longest utterance); veto: THIS call's decision (the
+ * plan holds the OR of all calls since the last reset / set). */
+typedef struct svc_plan_row {
+    int32_t index, veto, L, reserved;
+    double rho, eta, omega_hi, omega_lo;
+    svc_census_t census;
+} svc_plan_row_t;
+/* Calibrates the plan on the caller's own material: runs ONE forward with every candidate vetoed (the fp16x3 forward, so all
+ * operand planes are in the fp16 format; its waveform is discarded), takes the census of each candidate's operand planes at
+ * the point the conv consumes them (rows at and above an utterance's end are never read), combines it with the weight
+ * census, vetoes a conv when rho, eta or an omega exceeds tau, ORs the vetoes into the plan -- several calls on different
+ * material accumulate -- and fills rows[i] for candidate i.  mel [B][num_mels][S]; lens HOST [B], 1 <= lens[b] <= S, or
+ * NULL (all S).  tau in (0, 1]; the default of the Python mirrors is 2^-6 (it rests on a CPU
+ * simulation of one conv).  Deterministic: counts are integers and every sum has one fixed order, so equal material gives
+ * equal rows and the same plan.  Synchronises the stream.
+ * Refused before any launch (non-zero, svc_last_error(), plan untouched): a handle that is not fp16p8, NULL m / mel / rows,
+ * n_rows != plan size, tau outside (0, 1] or NaN, B or S < 1, B * S * up >= 2^31, a lens entry outside [1, S]. */
+int svc_bigvgan_calibrate(svc_bigvgan_t* m, const float* mel, const int32_t* lens, int B, int S, float tau, svc_plan_row_t* rows,
+                          int n_rows, void* stream);
+/* The same for HiFT; f0 / phase0 / noise as in svc_hift_forward(_ragged) (f0 may be NULL: the model's predictor). */
+int svc_hift_plan_size(svc_hift_t* m);
+const char* svc_hift_plan_name(svc_hift_t* m, int i);
+int svc_hift_plan_get(svc_hift_t* m, uint8_t* veto, int n);
+int svc_hift_plan_set(svc_hift_t* m, const uint8_t* veto, int n);
+int svc_hift_plan_reset(svc_hift_t* m);
+int svc_hift_calibrate(svc_hift_t* m, const float* mel, const int32_t* lens, const float* f0, const float* phase0, const float* noise,
+                       int B, int S, float tau, svc_plan_row_t* rows, int n_rows, void* stream);
+
 /* ---------------------------------------------------------------- v2 AR model (decode step, B = 1 and batched) */
 typedef struct svc_ar_config {        /* configs/v2/vc_wrapper.yaml:39-53 (modules.v2.ar.NaiveModelArgs) */
     int dim, n_head, n_local_heads, head_dim, n_layer, intermediate_size, vocab_size, max_seq_len;
@@ -1304,6 +1364,32 @@ typedef struct {
     const int32_t* src; const int32_t* len; const int32_t* lw; const int32_t* nf;
 } svc_hift_signal_t;
 int svc_op_hift_signal(const svc_hift_signal_t* args, void* stream);
+/* Test aid (tests/test_gpu_voc_plan.py; no model uses it): ONE range census (csrc/range_census.hip, census_launch) of explicit
+ * operand planes, through the launcher svc_*_calibrate calls.  hi, lo: DEVICE fp16 planes [B][L][ld] (lo = the fp16 residual),
+ * C live channels; lens: HOST [B] valid rows per sequence or NULL (rows at and above lens[b] are never read: they may hold
+ * NaN); out: HOST, one record.
+ *   Refused (nothing launched): NULL args, hi, lo or out; B, L or C < 1; B * L >= 2^31; ld < C or ld % 4 != 0; a plane not
+ *   8-byte aligned; lens outside [0, L]. */
+typedef struct {
+    const void* hi; const void* lo;
+    int32_t B, L, C, ld;
+    const int32_t* lens;
+    svc_census_t* out;
+} svc_range_census_t;
+int svc_op_range_census(const svc_range_census_t* args, void* stream);
+/* Test aid: the pack-time weight census of one Conv1d.  w DEVICE fp32 [Cout][Cin][k] is packed as an fp16p8 model packs it
+ * (fp16x3 rows and [w_hi | fp8 byte pairs] rows with one power-of-two scale s = 2^w8_exp from max|w|); out HOST
+ * [Cout][4] doubles per output channel: sum w_hi^2, sum (w_hi - dq fp8(s w_hi) / s)^2, sum w_lo^2, sum (w_lo - dq fp8(2^11 s
+ * w_lo) / (2^11 s))^2; w8_exp_out (HOST, optional) receives log2 s.
+ *   Refused: NULL w or out; Cout or Cin < 1; k outside 3 .. 16 (a conv with fewer taps gets no fp8 packing). */
+int svc_op_weight_census(const float* w, int Cout, int Cin, int k, double* out, int* w8_exp_out, void* stream);
+/* Test aids (tests/test_host_voc_plan.py; they need no device).  svc_op_plan_fake: a BigVGAN handle of `precision` that holds
+ * nothing but a precision plan of n_candidates (<= 96) candidates named resblocks.<i>.convs{1,2}.<d>; it supports the
+ * svc_bigvgan_plan_* calls, the refusals of svc_bigvgan_calibrate, svc_op_plan_apply and svc_bigvgan_destroy, nothing else.
+ * svc_op_plan_apply: the decision step of calibrate alone on the caller's rows -- rows[i].veto = rho, eta, omega_hi or
+ * omega_lo above tau, ORed into the plan. */
+int svc_op_plan_fake(int precision, int n_candidates, svc_bigvgan_t** out);
+int svc_op_plan_apply(svc_bigvgan_t* m, svc_plan_row_t* rows, int n_rows, float tau);
 /* Test aid (tests/test_gpu_ar_sampler.py; no model uses it, and it needs no svc_ar_t): ONE call of the AR sampler's launch
  * (csrc/ar_sampler.h) on explicit inputs.  It allocates the rank -> sample buffers, the slot state, the slot count and the
  * device positions itself, launches once, synchronises, copies the state back and frees its buffers.  Device pointers

@@ -48,6 +48,10 @@ EXPORTS = [
     "svc_op_linear", "svc_op_conv1d", "svc_op_conv1d_ex", "svc_op_conv1d_last_took", "svc_op_dit_panel", "svc_op_conv_transpose1d", "svc_op_attention", "svc_op_attention_ex", "svc_op_rmsnorm",
     "svc_op_layernorm", "svc_op_layernorm_gelu", "svc_op_act_cl", "svc_op_hift_signal", "svc_op_ar_sampler",
     "svc_op_ar_attn", "svc_op_ar_linear", "svc_op_kgemm", "svc_op_permute_vt", "svc_op_lr", "svc_op_attention_x3",
+    "svc_bigvgan_plan_size", "svc_bigvgan_plan_name", "svc_bigvgan_plan_get", "svc_bigvgan_plan_set", "svc_bigvgan_plan_reset",
+    "svc_bigvgan_calibrate", "svc_hift_plan_size", "svc_hift_plan_name", "svc_hift_plan_get", "svc_hift_plan_set",
+    "svc_hift_plan_reset", "svc_hift_calibrate", "svc_op_range_census", "svc_op_weight_census", "svc_op_plan_fake",
+    "svc_op_plan_apply",
 ]
 
 
@@ -200,6 +204,24 @@ class HiftSignal(C.Structure):
                [(n, C.POINTER(C.c_int32)) for n in ("src", "len", "lw", "nf")]
 
 
+class Census(C.Structure):
+    """svc_census_t: one range-census record (csrc/range_census.hip)."""
+    _fields_ = [(n, C.c_int64) for n in ("n", "n_hi_clamp", "n_hi_sub", "n_lo_flush", "n_lo_clamp")] + \
+               [(n, C.c_double) for n in ("max_hi", "s_hi2", "s_hi_err2", "s_lo2", "s_lo_err2")]
+
+
+class PlanRow(C.Structure):
+    """svc_plan_row_t: one report row of svc_bigvgan_calibrate / svc_hift_calibrate."""
+    _fields_ = [(n, C.c_int32) for n in ("index", "veto", "L", "reserved")] + \
+               [(n, C.c_double) for n in ("rho", "eta", "omega_hi", "omega_lo")] + [("census", Census)]
+
+
+class RangeCensus(C.Structure):
+    """svc_range_census_t: the arguments of svc_op_range_census (test aid)."""
+    _fields_ = [("hi", C.c_void_p), ("lo", C.c_void_p)] + [(n, C.c_int32) for n in ("B", "L", "C", "ld")] + \
+               [("lens", C.POINTER(C.c_int32)), ("out", C.POINTER(Census))]
+
+
 class ArSampler(C.Structure):
     """svc_ar_sampler_t: the arguments of svc_op_ar_sampler (test aid)."""
     _fields_ = [(n, C.c_int32) for n in ("form", "V", "D", "B", "max_new", "Lmax")] + \
@@ -322,6 +344,23 @@ def lib():
         l.svc_op_attention_ex.argtypes = [C.POINTER(Attention), C.c_void_p]
         l.svc_op_act_cl.argtypes = [C.POINTER(ActCl), C.c_void_p]
         l.svc_op_hift_signal.argtypes = [C.POINTER(HiftSignal), C.c_void_p]
+        # precision plan of the fp16p8 vocoders: vetoes as HOST bytes, report rows and lengths as HOST arrays
+        u8p = C.POINTER(C.c_uint8)
+        for voc in ("bigvgan", "hift"):
+            getattr(l, f"svc_{voc}_plan_size").argtypes = [C.c_void_p]
+            getattr(l, f"svc_{voc}_plan_name").argtypes = [C.c_void_p, C.c_int]
+            getattr(l, f"svc_{voc}_plan_name").restype = C.c_char_p
+            getattr(l, f"svc_{voc}_plan_get").argtypes = [C.c_void_p, u8p, C.c_int]
+            getattr(l, f"svc_{voc}_plan_set").argtypes = [C.c_void_p, u8p, C.c_int]
+            getattr(l, f"svc_{voc}_plan_reset").argtypes = [C.c_void_p]
+        l.svc_bigvgan_calibrate.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_float,
+                                            C.POINTER(PlanRow), C.c_int, C.c_void_p]
+        l.svc_hift_calibrate.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                         C.c_int, C.c_float, C.POINTER(PlanRow), C.c_int, C.c_void_p]
+        l.svc_op_range_census.argtypes = [C.POINTER(RangeCensus), C.c_void_p]
+        l.svc_op_weight_census.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_void_p]
+        l.svc_op_plan_fake.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+        l.svc_op_plan_apply.argtypes = [C.c_void_p, C.POINTER(PlanRow), C.c_int, C.c_float]
         l.svc_op_ar_sampler.argtypes = [C.POINTER(ArSampler), C.c_void_p]
         l.svc_op_ar_attn.argtypes = [C.POINTER(ArAttn), C.c_void_p]
         l.svc_op_ar_linear.argtypes = [C.POINTER(ArLinear), C.c_void_p]

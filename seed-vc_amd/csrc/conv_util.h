@@ -19,6 +19,9 @@ struct ConvW {
     void* w8 = nullptr;
     long ldw8 = 0;
     int w8_exp = 0;
+    // host flag of the precision plan (vocoder.hip): a vetoed conv never runs as fp16 + fp8 corrections (conv_p8_ok is false)
+    // and runs the fp16x3 form on `w` instead
+    bool p8_veto = false;
     // ConvTranspose only
     int stride = 0;
 };
@@ -173,12 +176,23 @@ inline int kconv_min_n() {
 // shortest sequence (output rows) sent to the resident-tile kernel: the ONLY length-dependent kernel choice of the vocoders
 constexpr int KCONV_MIN_ROWS = 192;
 
-// A conv of a vd == 3 model runs as fp16 + fp8 corrections iff it has the second packing and its call takes the
-// resident-tile kernel: a layer / length property, never the batch's.  The producer of its operand planes asks the same
-// question to choose the lo-plane format.
+// A conv of a vd == 3 model runs as fp16 + fp8 corrections iff it has the second packing, the precision plan does not veto it
+// and its call takes the resident-tile kernel: a layer / length property, never the batch's.  The producer of its operand
+// planes asks the same question to choose the lo-plane format.
 inline bool conv_p8_ok(const ConvW& w, int Lout, int dilation) {
-    return w.w8 != nullptr && kconv_enabled() && (w.k - 1) * dilation <= 64 && Lout >= KCONV_MIN_ROWS && w.cout_pad >= kconv_min_n() &&
+    return w.w8 != nullptr && !w.p8_veto && kconv_enabled() && (w.k - 1) * dilation <= 64 && Lout >= KCONV_MIN_ROWS && w.cout_pad >= kconv_min_n() &&
            w.cout_pad % 8 == 0;
+}
+
+// Long stride-1 convs with several taps keep their activation tile resident in LDS (kconv.hip).  The choice depends on the
+// layer and the sequence length only, never on the batch size, so batched and single runs stay bit-identical.  Only such a
+// conv can write byte-pair planes from its epilogue, so resblock_run asks this of the conv that produces a p8 operand.
+inline bool conv_takes_kconv(const ConvW& w, const ConvRun& r) {
+    const int N = r.n_override ? r.n_override : w.cout_pad;
+    const bool vec_ok = (N % 8 == 0) && (r.ldc32 % 8 == 0) && (r.ldc16 % 8 == 0) && (r.ldres % 8 == 0) && (r.ldres2 % 8 == 0);
+    return !r.force_gemm && kconv_enabled() && w.dtype == 0 && r.stride == 1 && w.k >= 3 && (w.k - 1) * r.dilation <= 64 &&
+           r.pad_mode == KG_PAD_ZERO && (!r.seq_len || (r.seq_kconv && r.Lin == r.Lout)) && !r.n_override && vec_ok &&
+           r.Lout >= KCONV_MIN_ROWS && w.cin_pad >= 64 && N >= kconv_min_n();
 }
 
 inline int conv1d_run(const ConvW& w, const ConvRun& r, hipStream_t st) {
@@ -218,14 +232,9 @@ inline int conv1d_run(const ConvW& w, const ConvRun& r, hipStream_t st) {
     p.post_a = r.post_a; p.post_ib = r.post_ib; p.post_n = r.post_n; p.c16_lo = r.c16_lo;
     p.prof_flop_scale = 1.0f / nsub;
     p.vec_ok = (p.N % 8 == 0) && (r.ldc32 % 8 == 0) && (r.ldc16 % 8 == 0) && (r.ldres % 8 == 0) && (r.ldres2 % 8 == 0);
-    // Long stride-1 convs with several taps keep their activation tile resident in LDS (kconv.hip).  The choice depends
-    // on the layer and the sequence length only, never on the batch size, so batched and single runs stay bit-identical.
-    const bool kconv_ok = !r.force_gemm && kconv_enabled() && w.dtype == 0 && r.stride == 1 && w.k >= 3 && (w.k - 1) * r.dilation <= 64 &&
-                          r.pad_mode == KG_PAD_ZERO && (!r.seq_len || (r.seq_kconv && r.Lin == r.Lout)) && !r.n_override && p.vec_ok &&
-                          r.Lout >= KCONV_MIN_ROWS && w.cin_pad >= 64 &&
-                          p.N >= kconv_min_n();
-    // (a conv and the conv it feeds inside a residual stack have the same shape, so both take the same kernel: the tap-GEMM
-    // epilogue never has to write byte pairs)
+    const bool kconv_ok = conv_takes_kconv(w, r);
+    // (resblock_run asks conv_takes_kconv of a producing conv before it lets the consumer run p8: the tap-GEMM epilogue never
+    // has to write byte pairs)
     SVC_REQUIRE((!r.p8 && !r.c16_lo_fmt) || (kconv_ok && (!r.p8 || conv_p8_ok(w, r.Lout, r.dilation))),
                 "conv1d_run: the fp8-pair operand format needs the resident-tile kernel");
     if (kconv_ok) {

@@ -24,6 +24,7 @@
 
 #include "conv_util.h"
 #include "noise.h"
+#include "range_census.h"
 
 using namespace svc;
 
@@ -401,6 +402,41 @@ struct ResBlockW {
     int dil[3] = {1, 1, 1};
     ConvW c1[3], c2[3];
     SnakeP a1[3], a2[3];
+    int cand1[3] = {-1, -1, -1}, cand2[3] = {-1, -1, -1};   // index of c1[d] / c2[d] in the handle's precision plan, -1: no candidate
+};
+
+// The precision plan of an fp16p8 handle: its p8 candidates -- the ResBlock convs that own the fp8 packing -- in model order,
+// each with its state-dict prefix.  The veto itself lives in the conv (ConvW::p8_veto), where conv_p8_ok reads it.
+struct P8Plan {
+    std::vector<ConvW*> conv;
+    std::vector<std::string> name;
+    int size() const { return (int)conv.size(); }
+    void add(ResBlockW& rb, const std::string& prefix) {
+        for (int d = 0; d < rb.ndil; ++d) {
+            ConvW* c[2] = {&rb.c1[d], &rb.c2[d]};
+            int* idx[2] = {&rb.cand1[d], &rb.cand2[d]};
+            for (int i = 0; i < 2; ++i) {
+                if (!c[i]->w8) continue;
+                *idx[i] = size();
+                conv.push_back(c[i]);
+                name.push_back(prefix + (i == 0 ? ".convs1." : ".convs2.") + std::to_string(d));
+            }
+        }
+    }
+};
+
+// Where a calibration forward leaves the census of each candidate's operand planes (resblock_run): rec[i] (device)
+// accumulates candidate i's records over the micro-batches in stream order; L[i] (host) keeps its rows per utterance
+struct CensusSink {
+    svc_census_t* rec = nullptr;
+    svc_census_t* part = nullptr;
+    long part_cap = 0;
+    int* L = nullptr;
+    int take(int cand, const ActBuf& a, int B, int L_, int C, int ld, const int* lens, hipStream_t st) const {
+        if (cand < 0) return 0;
+        L[cand] = std::max(L[cand], L_);
+        return census_launch(a.hi, a.lo, B, L_, C, ld, lens, rec + cand, part, part_cap, st);
+    }
 };
 
 // One micro-batch of a ragged call (device pointers into the call's length table): row j is utterance src[j] of the caller's
@@ -519,6 +555,8 @@ struct svc_bigvgan {
     float *x, *y, *t, *xsum;
     int microbatch = 0;
     RaggedPlan plan;    // ragged calls
+    P8Plan p8;          // precision plan (dtype == 3)
+    const CensusSink* sink = nullptr;   // set for the forward of svc_bigvgan_calibrate only
 
     int reserve(int B, int S, hipStream_t st);
     // rg == null: B utterances of S frames each.  rg != null: micro-batch of a ragged call, `mel` / `out` are the caller's
@@ -542,7 +580,7 @@ int act_cl_any(const float* x, int ld, ActOut y, int vd, const float* taps, cons
 // conv's operand load (tap-GEMM: seq_len; resident-tile conv: its ragged form) and the operand planes past the end hold anything.
 int resblock_run(const ResBlockW& rb, int dtype, const float* taps, int act_mode, const float* x_in, float* y, float* t, ActOut act_a,
                  int B, int L, float out_scale, const float* res2, float* final_dst, hipStream_t st, ActOut act_b = ActOut(),
-                 const int* lens = nullptr, const int* conv_lens = nullptr) {
+                 const int* lens = nullptr, const int* conv_lens = nullptr, const CensusSink* sink = nullptr) {
     const int f16 = dtype;      // operand mode handed to the activation writers
     const int ld = cpad(rb.ch, dtype);
     const float* cur = x_in;
@@ -551,16 +589,24 @@ int resblock_run(const ResBlockW& rb, int dtype, const float* taps, int act_mode
     // planes straight into the other operand buffer.  The fp32 intermediate `t` disappears.
     const bool fuse = act_mode == 1 && dtype != 1 && act_b.hi != nullptr;
     // vd == 3: whoever writes a conv's operand planes (an activation kernel or the previous conv's epilogue) writes the lo
-    // plane in the format that conv will read: fp8 byte pairs when it runs as fp16 + fp8 corrections (conv_p8_ok)
-    auto fuse_into = [&](ConvRun& r, const SnakeP& sp, const ActOut& dst, bool next_p8) {
+    // plane in the format that conv will read: fp8 byte pairs when it runs as fp16 + fp8 corrections (conv_p8_ok).  The
+    // decision is per producer / consumer pair: a consumer runs p8 only if its producer can write byte pairs -- an activation
+    // kernel always can, a conv only from the resident-tile kernel's epilogue (conv_takes_kconv; an 11-tap conv of dilation 7
+    // spans 70 rows and runs on the tap-GEMM).  Otherwise the consumer runs the fp16x3 form on fp16 planes.
+    // Returns whether `next` (null: none) runs p8 on the planes r's epilogue writes.
+    auto fuse_into = [&](const ConvW& w, ConvRun& r, const SnakeP& sp, const ActOut& dst, const ConvW* next, int next_dil) {
         r.post_a = sp.a; r.post_ib = sp.inv_b; r.post_n = rb.ch;
         r.c16 = reinterpret_cast<half_t*>(dst.hi); r.ldc16 = ld;
         r.c16_lo = is_split(dtype) ? reinterpret_cast<half_t*>(dst.lo) : nullptr;
+        const bool next_p8 = dtype == 3 && next && conv_p8_ok(*next, L, next_dil) && conv_takes_kconv(w, r);
         r.c16_lo_fmt = next_p8 ? 1 : 0;
+        return next_p8;
     };
+    const int* live = lens ? lens : conv_lens;     // the census of a calibration forward stops at each utterance's end
+    bool p8_next = false;       // fused path: c1[d + 1] runs p8 (decided when c2[d]'s epilogue was set up)
     for (int d = 0; d < rb.ndil; ++d) {
-        const bool p8_1 = dtype == 3 && conv_p8_ok(rb.c1[d], L, rb.dil[d]);
-        const bool p8_2 = dtype == 3 && conv_p8_ok(rb.c2[d], L, 1);
+        const bool p8_1 = fuse && d > 0 ? p8_next : dtype == 3 && conv_p8_ok(rb.c1[d], L, rb.dil[d]);
+        bool p8_2 = dtype == 3 && conv_p8_ok(rb.c2[d], L, 1);
         if (!fuse || d == 0) {
             if (act_cl_any(cur, ld, act_a, f16, taps, rb.a1[d], B, rb.ch, L, act_mode, 0.f, st, p8_1, lens)) return 1;
         }
@@ -569,8 +615,9 @@ int resblock_run(const ResBlockW& rb, int dtype, const float* taps, int act_mode
         r1.pad_left = (rb.k * rb.dil[d] - rb.dil[d]) / 2;
         r1.p8 = p8_1;
         r1.seq_len = conv_lens; r1.seq_kconv = true;
-        if (fuse) fuse_into(r1, rb.a2[d], act_b, p8_2);
+        if (fuse) p8_2 = fuse_into(rb.c1[d], r1, rb.a2[d], act_b, &rb.c2[d], 1);
         else { r1.c32 = t; r1.ldc32 = ld; }
+        if (sink && sink->take(rb.cand1[d], r1.a, B, L, rb.ch, ld, live, st)) return 1;
         if (conv1d_run(rb.c1[d], r1, st)) return 1;
         if (!fuse) {
             if (act_cl_any(t, ld, act_a, f16, taps, rb.a2[d], B, rb.ch, L, act_mode, 0.f, st, p8_2, lens)) return 1;
@@ -588,8 +635,9 @@ int resblock_run(const ResBlockW& rb, int dtype, const float* taps, int act_mode
             r2.c32 = final_dst; r2.ldc32 = ld;
         } else {
             r2.c32 = y; r2.ldc32 = ld;
-            if (fuse) fuse_into(r2, rb.a1[d + 1], act_a, dtype == 3 && conv_p8_ok(rb.c1[d + 1], L, rb.dil[d + 1]));
+            if (fuse) p8_next = fuse_into(rb.c2[d], r2, rb.a1[d + 1], act_a, &rb.c1[d + 1], rb.dil[d + 1]);
         }
+        if (sink && sink->take(rb.cand2[d], r2.a, B, L, rb.ch, ld, live, st)) return 1;
         if (conv1d_run(rb.c2[d], r2, st)) return 1;
         cur = y;
     }
@@ -656,7 +704,7 @@ int svc_bigvgan::run(const float* mel, int B, int S, float* out, hipStream_t st,
         for (int j = 0; j < nk; ++j) {
             // x = mean_j block_j(x): block j's last conv writes (y_j) / nk + (j > 0 ? xsum : 0) into xsum
             if (resblock_run(blocks[i * nk + j], vd, taps, 0, x, y, t, act_a, B, (int)L, 1.0f / (float)nk,
-                             j > 0 ? xsum : nullptr, xsum, st, ActOut(), rg ? rg->len[i + 1] : nullptr)) return 1;
+                             j > 0 ? xsum : nullptr, xsum, st, ActOut(), rg ? rg->len[i + 1] : nullptr, nullptr, sink)) return 1;
         }
     }
     const int* len_w = rg ? rg->len[cfg.num_upsamples] : nullptr;
@@ -720,6 +768,8 @@ struct svc_hift {
     float *f0_buf, *s_buf, *stft32, *x, *y, *t, *xsum, *si, *post, *frames;
     double* prefix;
     RaggedPlan plan;    // ragged calls
+    P8Plan p8;          // precision plan (dtype == 3)
+    const CensusSink* sink = nullptr;   // set for the forward of svc_hift_calibrate only
     // seeded calls: the call's seeds [B] and the phase0 [B][NH] drawn from them (the only draws that are ever stored)
     int device = -1;
     Arena seed_ar;
@@ -917,10 +967,10 @@ int svc_hift::run(const float* mel, const float* f0_in, const float* phase0, con
             if (conv1d_run(src_down[i], r, st)) return 1;
         }
         // x <- x + source_resblock(si): last conv of the stack adds res2 = x and writes x
-        if (resblock_run(src_rb[i], dtype, nullptr, 1, si, y, t, act_a, B, (int)L, 1.0f, x, x, st, act_b, nullptr, len_i)) return 1;
+        if (resblock_run(src_rb[i], dtype, nullptr, 1, si, y, t, act_a, B, (int)L, 1.0f, x, x, st, act_b, nullptr, len_i, sink)) return 1;
         for (int j = 0; j < nk; ++j) {
             if (resblock_run(blocks[i * nk + j], dtype, nullptr, 1, x, y, t, act_a, B, (int)L, 1.0f / (float)nk,
-                             j > 0 ? xsum : nullptr, xsum, st, act_b, nullptr, len_i)) return 1;
+                             j > 0 ? xsum : nullptr, xsum, st, act_b, nullptr, len_i, sink)) return 1;
         }
     }
     if (ew_cl(xsum, act_a, vd, (long)B * L, ch, cpad(ch, dtype), 2, 0.01f, st)) return 1;     // F.leaky_relu default slope
@@ -975,6 +1025,8 @@ int svc_bigvgan_create(const svc_bigvgan_config_t* cfg, const svc_tensor_desc_t*
         if (hipMemcpy(m->taps, f->data, 48, hipMemcpyDeviceToHost) != hipSuccess) { set_error("filter copy failed"); return fail(); }
     }
     if (hipStreamSynchronize(st) != hipSuccess) { set_error("sync failed"); return fail(); }
+    if (m->dtype == 3)
+        for (size_t i = 0; i < m->blocks.size(); ++i) m->p8.add(m->blocks[i], "resblocks." + std::to_string(i));
     *out = m;
     return 0;
 }
@@ -1088,6 +1140,12 @@ int svc_hift_create(const svc_hift_config_t* cfg, const svc_tensor_desc_t* weigh
     }
     if (pack_conv1d(sd, "conv_post", cfg->istft_n_fft + 2, ch, 7, true, m->dtype, m->wts, st, &m->conv_post)) return fail();
     if (hipStreamSynchronize(st) != hipSuccess) { set_error("sync failed"); return fail(); }
+    if (m->dtype == 3)
+        for (int i = 0; i < 2; ++i) {
+            m->p8.add(m->src_rb[i], "source_resblocks." + std::to_string(i));
+            for (int j = 0; j < cfg->num_kernels; ++j)
+                m->p8.add(m->blocks[i * cfg->num_kernels + j], "resblocks." + std::to_string(i * cfg->num_kernels + j));
+        }
     *out = m;
     return 0;
 }
@@ -1182,9 +1240,202 @@ int svc_hift::forward_ragged(const float* mel, const int32_t* lens, const float*
     return 0;
 }
 
+// ================================================================================================ precision plan
+namespace {
+int plan_handle_ok(const void* m, int dtype, const std::string& who) {
+    SVC_REQUIRE(m != nullptr, who + ": null handle");
+    SVC_REQUIRE(dtype == 3, who + ": the precision plan belongs to an fp16p8 handle (precision 3)");
+    return 0;
+}
+
+int plan_get(const P8Plan& p8, uint8_t* veto, int n, const std::string& who) {
+    SVC_REQUIRE(veto != nullptr, who + ": veto is NULL");
+    SVC_REQUIRE(n == p8.size(), who + ": n differs from the plan size");
+    for (int i = 0; i < n; ++i) veto[i] = p8.conv[i]->p8_veto ? 1 : 0;
+    return 0;
+}
+
+int plan_set(P8Plan& p8, const uint8_t* veto, int n, const std::string& who) {
+    SVC_REQUIRE(veto != nullptr, who + ": veto is NULL");
+    SVC_REQUIRE(n == p8.size(), who + ": n differs from the plan size");
+    for (int i = 0; i < n; ++i) p8.conv[i]->p8_veto = veto[i] != 0;
+    return 0;
+}
+
+// The decision of calibrate, row by row: a conv is vetoed when a loss ratio of its activations or weights exceeds tau, and the
+// vetoes are ORed into the plan (calls on different material accumulate)
+void plan_apply(P8Plan& p8, svc_plan_row_t* rows, float tau) {
+    for (int i = 0; i < p8.size(); ++i) {
+        svc_plan_row_t& r = rows[i];
+        r.veto = r.rho > tau || r.eta > tau || r.omega_hi > tau || r.omega_lo > tau;
+        if (r.veto) p8.conv[i]->p8_veto = true;
+    }
+}
+
+// the argument checks of both calibrate calls: before the handle is touched or anything is launched.  up: waveform samples per frame
+int calibrate_check(const std::string& who, const void* mel, const int32_t* lens, int B, int S, long up, float tau, const void* rows,
+                    int n_rows, int n_plan) {
+    SVC_REQUIRE(mel != nullptr && rows != nullptr, who + ": mel and rows are required");
+    SVC_REQUIRE(n_rows == n_plan, who + ": n_rows differs from the plan size");
+    SVC_REQUIRE(tau > 0.f && tau <= 1.f, who + ": tau lies in (0, 1]");      // false for NaN
+    SVC_REQUIRE(B >= 1 && S >= 1, who + ": B and S must be at least 1");
+    SVC_REQUIRE((double)B * ((double)S * (double)up + 1.0) < 2147483648.0, who + ": B * S * up must stay below 2^31");
+    if (lens)
+        for (int b = 0; b < B; ++b) SVC_REQUIRE(lens[b] >= 1 && lens[b] <= S, who + ": lens outside [1, S]");
+    return 0;
+}
+
+// The body of both calibrate calls.  fwd(out) runs the handle's forward (plain or ragged) into the scratch waveform `out`
+// ([B][S * up]); while it runs every candidate is vetoed and *slot points at the sink resblock_run feeds.
+int calibrate_run(P8Plan& p8, const CensusSink** slot, int B, int S, long up, float tau, svc_plan_row_t* rows, hipStream_t st,
+                  const std::function<int(float*)>& fwd) {
+    const int n = p8.size();
+    if (n == 0) return 0;
+    Arena ar;
+    std::vector<int> L(n, 0);
+    std::vector<long> wc_off(n + 1, 0);
+    for (int i = 0; i < n; ++i) wc_off[i + 1] = wc_off[i] + 4L * p8.conv[i]->cout;
+    CensusSink sink;
+    sink.part_cap = census_parts(B, (int)(S * up + 1));      // no conv of either vocoder has more rows per utterance
+    sink.rec = ar.alloc_n<svc_census_t>(n, st);
+    sink.part = ar.alloc_n<svc_census_t>((size_t)sink.part_cap, st);
+    sink.L = L.data();
+    double* d_wc = ar.alloc_n<double>((size_t)wc_off[n], st);
+    float* out = ar.alloc_n<float>((size_t)B * S * up, st);
+    if (!sink.rec || !sink.part || !d_wc || !out) return 1;
+    std::vector<uint8_t> saved(n);
+    for (int i = 0; i < n; ++i) { saved[i] = p8.conv[i]->p8_veto; p8.conv[i]->p8_veto = true; }
+    *slot = &sink;
+    int rc = fwd(out);
+    *slot = nullptr;
+    for (int i = 0; i < n; ++i) p8.conv[i]->p8_veto = saved[i] != 0;
+    for (int i = 0; i < n && !rc; ++i) rc = weight_census_launch(*p8.conv[i], d_wc + wc_off[i], st);
+    if (rc) { (void)hipStreamSynchronize(st); return 1; }       // the arena's buffers may still be in use
+    std::vector<svc_census_t> rec(n);
+    std::vector<double> wc((size_t)wc_off[n]);
+    hipError_t e = hipMemcpyAsync(rec.data(), sink.rec, n * sizeof(svc_census_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(wc.data(), d_wc, wc.size() * sizeof(double), hipMemcpyDeviceToHost, st);
+    const hipError_t e2 = hipStreamSynchronize(st);
+    SVC_CHECK_HIP(e);
+    SVC_CHECK_HIP(e2);
+    auto ratio = [](double err, double s) { return s > 0.0 ? err / s : 0.0; };
+    for (int i = 0; i < n; ++i) {
+        svc_plan_row_t& r = rows[i];
+        memset(&r, 0, sizeof(r));
+        r.index = i;
+        r.L = L[i];
+        r.census = rec[i];
+        r.rho = ratio(rec[i].s_lo_err2, rec[i].s_lo2);
+        r.eta = ratio(rec[i].s_hi_err2, rec[i].s_hi2);
+        for (int c = 0; c < p8.conv[i]->cout; ++c) {       // all-zero channels are exempt: their ratio is 0
+            const double* w = &wc[(size_t)wc_off[i] + 4 * c];
+            r.omega_hi = std::max(r.omega_hi, ratio(w[1], w[0]));
+            r.omega_lo = std::max(r.omega_lo, ratio(w[3], w[2]));
+        }
+    }
+    plan_apply(p8, rows, tau);
+    return 0;
+}
+}  // namespace
+
 extern "C" {
 
+int svc_bigvgan_plan_size(svc_bigvgan_t* m) { return m && m->dtype == 3 ? m->p8.size() : -1; }
+const char* svc_bigvgan_plan_name(svc_bigvgan_t* m, int i) {
+    return m && m->dtype == 3 && i >= 0 && i < m->p8.size() ? m->p8.name[i].c_str() : nullptr;
+}
+int svc_bigvgan_plan_get(svc_bigvgan_t* m, uint8_t* veto, int n) {
+    if (plan_handle_ok(m, m ? m->dtype : 0, "svc_bigvgan_plan_get")) return 1;
+    return plan_get(m->p8, veto, n, "svc_bigvgan_plan_get");
+}
+int svc_bigvgan_plan_set(svc_bigvgan_t* m, const uint8_t* veto, int n) {
+    if (plan_handle_ok(m, m ? m->dtype : 0, "svc_bigvgan_plan_set")) return 1;
+    return plan_set(m->p8, veto, n, "svc_bigvgan_plan_set");
+}
+int svc_bigvgan_plan_reset(svc_bigvgan_t* m) {
+    if (plan_handle_ok(m, m ? m->dtype : 0, "svc_bigvgan_plan_reset")) return 1;
+    for (ConvW* c : m->p8.conv) c->p8_veto = false;
+    return 0;
+}
+int svc_bigvgan_calibrate(svc_bigvgan_t* m, const float* mel, const int32_t* lens, int B, int S, float tau, svc_plan_row_t* rows,
+                          int n_rows, void* stream) {
+    const char* who = "svc_bigvgan_calibrate";
+    if (plan_handle_ok(m, m ? m->dtype : 0, who)) return 1;
+    long up = 1;
+    for (int i = 0; i < m->cfg.num_upsamples; ++i) up *= m->cfg.upsample_rates[i];
+    if (calibrate_check(who, mel, lens, B, S, up, tau, rows, n_rows, m->p8.size())) return 1;
+    return calibrate_run(m->p8, &m->sink, B, S, up, tau, rows, (hipStream_t)stream, [&](float* out) {
+        return lens ? svc_bigvgan_forward_ragged(m, mel, lens, B, S, out, stream) : svc_bigvgan_forward(m, mel, B, S, out, stream);
+    });
+}
+
+int svc_hift_plan_size(svc_hift_t* m) { return m && m->dtype == 3 ? m->p8.size() : -1; }
+const char* svc_hift_plan_name(svc_hift_t* m, int i) {
+    return m && m->dtype == 3 && i >= 0 && i < m->p8.size() ? m->p8.name[i].c_str() : nullptr;
+}
+int svc_hift_plan_get(svc_hift_t* m, uint8_t* veto, int n) {
+    if (plan_handle_ok(m, m ? m->dtype : 0, "svc_hift_plan_get")) return 1;
+    return plan_get(m->p8, veto, n, "svc_hift_plan_get");
+}
+int svc_hift_plan_set(svc_hift_t* m, const uint8_t* veto, int n) {
+    if (plan_handle_ok(m, m ? m->dtype : 0, "svc_hift_plan_set")) return 1;
+    return plan_set(m->p8, veto, n, "svc_hift_plan_set");
+}
+int svc_hift_plan_reset(svc_hift_t* m) {
+    if (plan_handle_ok(m, m ? m->dtype : 0, "svc_hift_plan_reset")) return 1;
+    for (ConvW* c : m->p8.conv) c->p8_veto = false;
+    return 0;
+}
+int svc_hift_calibrate(svc_hift_t* m, const float* mel, const int32_t* lens, const float* f0, const float* phase0, const float* noise,
+                       int B, int S, float tau, svc_plan_row_t* rows, int n_rows, void* stream) {
+    const char* who = "svc_hift_calibrate";
+    if (plan_handle_ok(m, m ? m->dtype : 0, who)) return 1;
+    SVC_REQUIRE(phase0 && noise, std::string(who) + ": phase0 and noise are required");
+    if (calibrate_check(who, mel, lens, B, S, m->up_total, tau, rows, n_rows, m->p8.size())) return 1;
+    hipStream_t st = (hipStream_t)stream;
+    return calibrate_run(m->p8, &m->sink, B, S, m->up_total, tau, rows, st, [&](float* out) {
+        return lens ? m->forward_ragged(mel, lens, f0, phase0, noise, nullptr, B, S, out, nullptr, st)
+                    : m->forward(mel, f0, phase0, noise, nullptr, B, S, out, nullptr, st);
+    });
+}
+
 // ---- op-level entry points for the parity tests -------------------------------------------------------
+// A BigVGAN handle that holds nothing but a precision plan of n candidates (one 3-pair ResBlock per six of them): no device is
+// touched, no weight exists, and the only calls it supports are the svc_bigvgan_plan_* family, the refusals of
+// svc_bigvgan_calibrate, svc_op_plan_apply and svc_bigvgan_destroy.
+int svc_op_plan_fake(int precision, int n_candidates, svc_bigvgan_t** out) {
+    SVC_REQUIRE(out && precision >= 0 && precision <= 3 && n_candidates >= 0 && n_candidates <= 96, "svc_op_plan_fake: bad argument");
+    static char never_read;
+    svc_bigvgan* m = new svc_bigvgan();
+    memset(&m->cfg, 0, sizeof(m->cfg));
+    m->cfg.precision = precision;
+    m->cfg.num_upsamples = 1;
+    m->cfg.upsample_rates[0] = 4;
+    m->dtype = precision == 1 ? 0 : (precision == 2 ? 2 : (precision == 3 ? 3 : 1));
+    m->x = m->y = m->t = m->xsum = nullptr;
+    m->blocks.resize((n_candidates + 5) / 6);
+    int left = n_candidates;
+    for (ResBlockW& rb : m->blocks) {
+        rb.ndil = 3;
+        for (int d = 0; d < 3; ++d) {
+            if (left-- > 0) rb.c1[d].w8 = &never_read;
+            if (left-- > 0) rb.c2[d].w8 = &never_read;
+        }
+    }
+    if (m->dtype == 3)
+        for (size_t i = 0; i < m->blocks.size(); ++i) m->p8.add(m->blocks[i], "resblocks." + std::to_string(i));
+    *out = m;
+    return 0;
+}
+
+// calibrate's decision step alone on the caller's rows (rho, eta, omega_hi, omega_lo in; veto out; the plan takes the OR)
+int svc_op_plan_apply(svc_bigvgan_t* m, svc_plan_row_t* rows, int n_rows, float tau) {
+    if (plan_handle_ok(m, m ? m->dtype : 0, "svc_op_plan_apply")) return 1;
+    SVC_REQUIRE(rows && n_rows == m->p8.size() && tau > 0.f && tau <= 1.f, "svc_op_plan_apply: bad argument");
+    plan_apply(m->p8, rows, tau);
+    return 0;
+}
+
 namespace {
 thread_local int g_conv1d_took = 0;      // svc_op_conv1d_last_took
 

@@ -820,3 +820,49 @@ def rmsnorm(x, gamma, w=None, b=None, add_one=False):
         _lib.check(_lib.lib().svc_op_rmsnorm(_lib.ptr(x), _lib.ptr(gamma), _lib.ptr(w), _lib.ptr(b), int(add_one),
                                              _lib.ptr(y), rows, D, _lib.stream_ptr()))
     return y
+
+
+CENSUS_COUNTS = ("n", "n_hi_clamp", "n_hi_sub", "n_lo_flush", "n_lo_clamp")
+CENSUS_SUMS = ("s_hi2", "s_hi_err2", "s_lo2", "s_lo_err2")
+
+
+def census_dict(c):
+    """svc_census_t -> dict (counts as ints, max_hi and the four sums as floats)."""
+    d = {k: int(getattr(c, k)) for k in CENSUS_COUNTS}
+    d["max_hi"] = float(c.max_hi)
+    d.update({k: float(getattr(c, k)) for k in CENSUS_SUMS})
+    return d
+
+
+def range_census(hi, lo, C, lens=None, device="cuda:0"):
+    """Test aid over svc_op_range_census (include/seedvc_hip.h): ONE range census of the fp16 operand planes hi, lo (B, L, ld)
+    (they may hold NaN in rows at and above lens[b]); C live channels; lens a list of B ints or None.  Returns the record as a
+    dict (census_dict)."""
+    import ctypes as Ct
+    dev = torch.device(device)
+    B, L, ld = hi.shape
+    assert hi.dtype == lo.dtype == torch.float16 and hi.shape == lo.shape
+    with torch.cuda.device(dev):
+        h, l = hi.to(dev).contiguous(), lo.to(dev).contiguous()
+        e, out = _lib.RangeCensus(), _lib.Census()
+        e.hi, e.lo, e.B, e.L, e.C, e.ld = h.data_ptr(), l.data_ptr(), B, L, C, ld
+        arr, p = _i32_field(lens, B, "lens")
+        if p is not None:
+            e.lens = p
+        e.out = Ct.pointer(out)
+        _lib.check(_lib.lib().svc_op_range_census(Ct.byref(e), _lib.stream_ptr()))
+    return census_dict(out)
+
+
+def weight_census(w, device="cuda:0"):
+    """Test aid over svc_op_weight_census: w (Cout, Cin, k) fp32 packed as an fp16p8 model packs it -> (sums (Cout, 4) float64:
+    sum w_hi^2, sum (w_hi - dq)^2, sum w_lo^2, sum (w_lo - dq)^2 per output channel, w8_exp)."""
+    import ctypes as Ct
+    dev = torch.device(device)
+    Cout, Cin, k = w.shape
+    with torch.cuda.device(dev):
+        wd = _lib.f32c(w, dev)
+        out = (Ct.c_double * (Cout * 4))()
+        ex = Ct.c_int(0)
+        _lib.check(_lib.lib().svc_op_weight_census(_lib.ptr(wd), Cout, Cin, k, out, Ct.byref(ex), _lib.stream_ptr()))
+    return torch.tensor(list(out), dtype=torch.float64).reshape(Cout, 4), ex.value

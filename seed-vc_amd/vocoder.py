@@ -9,6 +9,13 @@ correction products of the long stride-1 convs in ONE block-scaled fp8 MFMA (wav
 with margin, faster again), "fp16" = plain fp16 operands (2.4e-4: outside the bound, reported only).  HiFT's random draws (SineGen phases and noise,
 generator.py:208-222) are drawn here with torch when the caller does not pass them; with `seeds=` (one 64-bit seed per
 utterance) they are drawn on the device inside the source kernel instead and no (B, nh, S * up) tensor exists.
+
+"fp16p8" has a fixed operand window (the fp8 correction bytes carry no activation scale and one weight scale per layer);
+outside it a conv silently degrades to plain-fp16 operand error.  `calibrate(...)` measures, on the caller's own weights and
+material, how much each candidate conv's correction bytes lose and vetoes the convs that lose more than `tau`: a vetoed conv
+runs the fp16x3 form.  The vetoes are the handle's `precision_plan` ({state-dict prefix: bool}); it can be stored next to a
+checkpoint and set again without calibration data.  The empty plan (the default) is plain "fp16p8", the full plan gives the
+bits of "fp16x3"; no plan depends on the batch.
 """
 import ctypes as C
 import math
@@ -20,9 +27,69 @@ from .specs import bigvgan_total_upsample, hift_total_upsample
 
 
 PRECISIONS = {"fp32": 0, "fp16": 1, "fp16x3": 2, "fp16p8": 3}
+DEFAULT_TAU = 2.0 ** -6     # calibrate's veto threshold on the loss ratios
 
 
-class BigVGAN:
+class _PrecisionPlan:
+    """The precision plan of an fp16p8 handle over svc_<voc>_plan_* (include/seedvc_hip.h)."""
+    _voc = None     # "bigvgan" | "hift"
+
+    def _plan(self, name):
+        return getattr(_lib.lib(), f"svc_{self._voc}_{name}")
+
+    def plan_names(self):
+        """State-dict prefixes of the p8 candidate convs, in plan order (an "fp16p8" handle only)."""
+        n = self._plan("plan_size")(self._h)
+        if n < 0:
+            raise RuntimeError('the precision plan belongs to a precision="fp16p8" handle')
+        return [self._plan("plan_name")(self._h, i).decode() for i in range(n)]
+
+    @property
+    def precision_plan(self):
+        """{prefix: vetoed} for every candidate conv; a vetoed conv runs the fp16x3 form instead of fp16 + fp8 corrections."""
+        names = self.plan_names()
+        veto = (C.c_uint8 * max(len(names), 1))()
+        _lib.check(self._plan("plan_get")(self._h, veto, len(names)))
+        return {k: bool(veto[i]) for i, k in enumerate(names)}
+
+    @precision_plan.setter
+    def precision_plan(self, plan):
+        names = self.plan_names()
+        unknown = sorted(set(plan) - set(names))
+        if unknown:
+            raise KeyError(f"precision_plan: not a p8 candidate of this model: {unknown}")
+        cur = self.precision_plan
+        cur.update({k: bool(v) for k, v in plan.items()})
+        veto = (C.c_uint8 * max(len(names), 1))(*[int(cur[k]) for k in names])
+        _lib.check(self._plan("plan_set")(self._h, veto, len(names)))
+
+    def reset_plan(self):
+        """Clears every veto: plain fp16p8 again."""
+        _lib.check(self._plan("plan_reset")(self._h))
+
+    def _report(self, names, rows):
+        from .ops import census_dict
+        out = []
+        for k, r in zip(names, rows):
+            d = {"index": r.index, "name": k, "veto": bool(r.veto), "L": r.L, "rho": r.rho, "eta": r.eta, "omega_hi": r.omega_hi,
+                 "omega_lo": r.omega_lo}
+            d.update(census_dict(r.census))
+            out.append(d)
+        return out
+
+    @staticmethod
+    def _lens_host(lens, B, who):
+        if lens is None:
+            return None
+        lens = _lib.int_list(lens)
+        if len(lens) != B:
+            raise ValueError(f"{who}: lens has {len(lens)} entries, the batch has {B} utterances")
+        return _lib.i32_host(lens)
+
+
+class BigVGAN(_PrecisionPlan):
+    _voc = "bigvgan"
+
     def __init__(self, h, state_dict, device="cuda:0", precision="fp16p8"):
         self.h = h
         self.device = torch.device(device)
@@ -76,6 +143,22 @@ class BigVGAN:
 
     forward = __call__
 
+    @torch.inference_mode()
+    def calibrate(self, mel, lens=None, tau=DEFAULT_TAU):
+        """Calibrates the precision plan on mel (B, num_mels, S) [lens: B ints in [1, S]]: one fp16x3 forward with a range
+        census of every candidate conv's operand planes, combined with the weight census; a conv whose loss ratios rho, eta
+        or omega exceed tau is vetoed, and the vetoes are ORed into the plan (`svc_bigvgan_calibrate`).  Returns one report
+        row (dict) per candidate: name, veto (this call's decision), rho, eta, omega_hi, omega_lo, L, the counts, max_hi."""
+        B, _, S = mel.shape
+        names = self.plan_names()
+        rows = (_lib.PlanRow * max(len(names), 1))()
+        lens_keep = self._lens_host(lens, B, "BigVGAN.calibrate")
+        with torch.cuda.device(self.device):
+            mel = _lib.f32c(mel, self.device)
+            _lib.check(_lib.lib().svc_bigvgan_calibrate(self._h, _lib.ptr(mel), lens_keep, B, S, float(tau), rows, len(names),
+                                                        _lib.stream_ptr()))
+        return self._report(names, rows)
+
     def close(self):
         if self._h:
             _lib.lib().svc_bigvgan_destroy(self._h)
@@ -88,7 +171,9 @@ class BigVGAN:
             pass
 
 
-class HiFT:
+class HiFT(_PrecisionPlan):
+    _voc = "hift"
+
     def __init__(self, cfg, state_dict, device="cuda:0", precision="fp16p8"):
         self.cfg = cfg
         self.device = torch.device(device)
@@ -171,6 +256,27 @@ class HiFT:
 
     forward = __call__
     inference = __call__
+
+    @torch.inference_mode()
+    def calibrate(self, x, f0=None, phase0=None, noise=None, lens=None, tau=DEFAULT_TAU):
+        """BigVGAN.calibrate for HiFT (`svc_hift_calibrate`): x (B, 80, S), f0 / phase0 / noise as in `__call__` (drawn here with
+        torch when not given; f0 None = the model's predictor)."""
+        B, _, S = x.shape
+        nh, Lw, dev = self.cfg["nb_harmonics"] + 1, S * self.total_up, self.device
+        names = self.plan_names()
+        rows = (_lib.PlanRow * max(len(names), 1))()
+        lens_keep = self._lens_host(lens, B, "HiFT.calibrate")
+        with torch.cuda.device(dev):
+            mel = _lib.f32c(x, dev)
+            if phase0 is None:
+                phase0 = (torch.rand(B, nh, 1, device=dev) * 2 - 1) * math.pi
+            if noise is None:
+                noise = torch.randn(B, nh, Lw, device=dev)
+            phase0, noise = _lib.f32c(phase0, dev), _lib.f32c(noise, dev)
+            f0t = _lib.f32c(f0, dev) if f0 is not None else None
+            _lib.check(_lib.lib().svc_hift_calibrate(self._h, _lib.ptr(mel), lens_keep, _lib.ptr(f0t), _lib.ptr(phase0),
+                                                     _lib.ptr(noise), B, S, float(tau), rows, len(names), _lib.stream_ptr()))
+        return self._report(names, rows)
 
     @torch.inference_mode()
     def noise_draws(self, seed, n_frames):
